@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
-"""bench.py -- 256x256 images/sec of the Local-Hints forward pass on MI355X (+ p50 click latency).
+"""bench.py -- 256x256 images/sec of the Local-Hints forward pass on MI355X (+ p50 click latency with --full).
 
     python bench.py --gpus N --steps K --warmup W          (N > 1 without a launcher: bench.py starts its own N ranks, see self_launch)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
+    python bench.py ... --full                             (every diagnostic leg listed below)
+    python bench.py ... --dump-outputs DIR                 (the timed path's output of its last step -> DIR/*.npy)
 
 A "step" = one pass of the hot path (the 29 conv/deconv layers as 25 implicit-GEMM launches: input pack, model1, the
 shortcut convs and the tanh head fused into them, i.e. SIGGRAPHGenerator.forward, models/pytorch/model.py:134-175) over one batch of 32
@@ -13,12 +15,16 @@ images/sec target is quoted on.  Inputs and outputs are resident in HBM during t
 With N ranks every rank runs its own 32 images (weak scaling, no data-path collective); the
 weights are packed on rank 0 and broadcast once over RCCL before the timed region.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps once and prints the contract fields
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`) with the run's configuration; nothing else runs.
+With --full the same line also carries (each leg after the timed region, never `value`)
+  repeats       : two more timed regions of K steps (--repeats), the run-to-run spread;
+  layers_ms     : a separate untimed pass with an event pair around every launch;
   roofline      : the conv stack (kernels conv_igemm_v2p / conv_ds_fused_m / conv1_block_fused_t; --precision: their split / fp16 forms) against the dense bf16 MFMA peak,
                   from per-layer HIP events recorded on the engine's stream inside the timed region;
   cpu_baseline  : the torch-CPU oracle (same ATen kernels as the reference's PyTorch backend)
                   timed on this box's host cores on a bounded sample (rank 0, N=1 only);
-  fp32_contract_path : (N = 1 GPU, default run) the same batch, weights and step count on precision fp16x3 -- the fastest path inside the reference's
+  fp32_contract_path : (N = 1 GPU, bf16) the same batch, weights and step count on precision fp16x3 -- the fastest path inside the reference's
                   1e-3 contract (data/colorize_image.py:263) -- and `parity.max_abs_err`: the distance of the bf16 and fp16x3 outputs of images 0, 1 from the
                   CPU baseline's own fp32 outputs of those images; never `value`;
   latency       : p50 per-click recolor latency, BASELINE.json configs[1] (one 256x256 image,
@@ -44,6 +50,7 @@ LAYER_PASS_FORWARDS = 20                # per-launch event pass (untimed): forwa
 PEAK_FP32_MFMA_TFLOPS = 157.3
 PER_GPU_BATCH = 32
 H = W = 256
+DUMP_BYTES = 64 * 10 ** 6               # --dump-outputs: budget over all ranks' files
 
 
 def parse_args():
@@ -51,6 +58,13 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=10)      # 40 ms: the clock ramp from idle ends inside the warm-up, not inside the timed region
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, run every diagnostic leg as well (repeats, per-layer pass, roofline, end-to-end, other weight "
+                         "style, zero-operand and MFMA-peak probes, click latency, fp16x3 contract path, CPU baseline); the --no-* options "
+                         "below drop single legs of such a run.  Off by default: a plain run does only what `value` needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the ab map of the timed path's last step to DIR/out_ab.npy (float32; DIR/out_ab_rank<r>.npy per rank when "
+                         "N > 1), at most %d MB in all: above that a fixed seeded sample of the images; the line says which" % (DUMP_BYTES // 10 ** 6))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-latency", action="store_true")
     ap.add_argument("--no-contract-leg", action="store_true",
@@ -73,7 +87,7 @@ def parse_args():
     ap.add_argument("--no-end-to-end", action="store_true", help="skip the host-pointer (PCIe-inclusive) pipeline leg")
     ap.add_argument("--no-peak-probe", action="store_true", help="skip the 3 s MFMA-peak probe (tools/ubench/mfma_peak)")
     ap.add_argument("--repeats", type=int, default=3,
-                    help="timed regions of --steps forwards each: `value` is the FIRST (the contract's K steps); the others "
+                    help="--full: timed regions of --steps forwards each: `value` is the FIRST (the contract's K steps); the others "
                          "only feed `repeats` (min / median / max), the run-to-run spread on this box")
     ap.add_argument("--transport", default="torch", choices=["torch", "c_abi"],
                     help="weight broadcast at N>1: torch.distributed.broadcast (RCCL) or the library's own "
@@ -496,7 +510,8 @@ def main():
     e.sync()
     # Timed region: one HIP-event pair per forward on the engine's own stream (first conv launch .. end of the last
     # kernel) gives the conv family's duration live; per-launch pairs would slow the region by ~4 % and are taken in
-    # a separate, untimed pass below for the per-layer table.
+    # a separate, untimed pass below for the per-layer table.  (The pairs are recorded with or without --full, so the
+    # timed region is the same in both.)
     e.set_profiling("forward")
 
     def timed_region():
@@ -508,16 +523,19 @@ def main():
         return time.perf_counter() - t0
 
     elapsed = timed_region()                    # THE timed region of the contract: exactly --steps forwards
-    forward_ms = float(e.layer_times_ms()[0])
     my_elapsed = elapsed
-    extra = [timed_region() for _ in range(max(args.repeats, 1) - 1)]     # spread only, never `value`
-    e.set_profiling(True)                       # untimed: per-launch events, LAYER_PASS_FORWARDS forwards (median per layer)
-    for _ in range(LAYER_PASS_FORWARDS):
-        e.forward_device(nb, dL, dab, dm, dout, 0.0, sync=False)
-    e.sync()
-    layer_min, layer_ms, layer_max = e.layer_times_stats()
-    e.set_profiling(False)
-    out_head = dout[:2].cpu().numpy().copy() if world == 1 else None      # images 0 and 1 of the timed workload (for `fp32_contract_path.parity`)
+    dumped = dump_outputs(args.dump_outputs, dout, rank, world) if args.dump_outputs else None
+    extra = []
+    if args.full:
+        forward_ms = float(e.layer_times_ms()[0])   # the timed region's last forward (event pair): the roofline's conv time
+        extra = [timed_region() for _ in range(max(args.repeats, 1) - 1)]     # spread only, never `value`
+        e.set_profiling(True)                   # untimed: per-launch events, LAYER_PASS_FORWARDS forwards (median per layer)
+        for _ in range(LAYER_PASS_FORWARDS):
+            e.forward_device(nb, dL, dab, dm, dout, 0.0, sync=False)
+        e.sync()
+        layer_min, layer_ms, layer_max = e.layer_times_stats()
+        e.set_profiling(False)
+        out_head = dout[:2].cpu().numpy().copy() if world == 1 else None  # images 0 and 1 of the timed workload (for `fp32_contract_path.parity`)
 
     per_rank = [my_elapsed]
     bcast_ms = [sc.weights_broadcast_ms]
@@ -537,23 +555,8 @@ def main():
             dist.barrier()
         return
 
-    # ---- accounting -------------------------------------------------------------------------------------
-    table = e.layer_table()
-    # every conv / deconv launch of the graph: conv_igemm<..>, conv_igemm_v2<..>[+head|+shortcut], conv1_block_fused
-    # (rows of layers that ran fused inside another launch say "fused into ..." and carry no FLOP of their own)
-    conv_rows = [(r, float(layer_ms[r["index"]])) for r in table if r["kernel"].startswith("conv") and r["launches"] > 0]
-    traffic = _pmc_traffic()
-    conv_ms_layers = sum(ms for _, ms in conv_rows)                          # untimed per-launch pass
-    other_ms = float(sum(layer_ms)) - conv_ms_layers                          # non-conv kernels (softmax / glob branch)
-    conv_ms = forward_ms - other_ms                                          # timed region: the conv launches incl. their boundaries
-    conv_flops = sum(r["flops"] for r, _ in conv_rows) * nb                 # algorithmic, per launch-set
-    achieved_tflops = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
-    # operand-split precisions: every algorithmic FLOP costs 3 (6) bf16 MFMA FLOPs, so the bound is the bf16 peak / products
-    products = {"bf16x3": 3, "bf16x6": 6, "fp16x3": 3}.get(args.precision, 1)     # (fp16x3: three fp16 MFMA products, same dense rate as bf16)
-    peak = (PEAK_BF16_DENSE_TFLOPS / products) if args.precision != "fp32" else PEAK_FP32_MFMA_TFLOPS
     ms_per_step = elapsed / args.steps * 1e3
     value = world * nb * args.steps / elapsed
-    worst = sorted(conv_rows, key=lambda x: -x[1])[:6]
     result = {
         "metric": "256x256 images/sec",
         "value": round(value, 2),
@@ -568,6 +571,7 @@ def main():
         "vs_baseline": None,
         "dtype": args.precision,
         "data": "synthetic",
+        "full": args.full,
         "config": {"workload": "BASELINE.json configs[2]: batch %d random 256x256 L-channels + random sparse ab "
                                "hint masks per GPU, %s MFMA conv path, Local-Hints SIGGRAPHGenerator forward "
                                "(dist=False), seeded random-init weights (%s)" % (
@@ -580,6 +584,38 @@ def main():
                    "weights_blob_bytes": int(e.blob_bytes()),
                    "weights_broadcast_ms": sc.weights_broadcast_ms,
                    "weights_broadcast_ms_per_rank": [None if x is None else round(float(x), 3) for x in bcast_ms]},
+        "per_rank_images_per_sec": [round(nb * args.steps / t_, 2) for t_ in per_rank],
+        "process_group": {"backend": (dist.get_backend() if world > 1 else None), "ranks": world,
+                          "rccl_ranks": world if (world > 1 and dist.get_backend() == "nccl") else (1 if world == 1 else 0),
+                          "launched_by": os.environ.get("IDC_BENCH_LAUNCHED_BY", "external launcher" if world > 1 else "single process")},
+        "scaling_note": "no hardware scaling curve exists from the builder (1-GPU boxes only): per-N values are whatever the "
+                        "driver's 8-GPU run of this command measures; the path has no data-path collective",
+    }
+    if dumped is not None:
+        result["outputs_dumped"] = dumped
+    if args.dryrun_single_gpu:
+        result["dryrun_single_gpu"] = ("%d ranks shared ONE GPU over a gloo group: control-flow check only, `value` is not a "
+                                       "scaling measurement" % world)
+    if not args.full:
+        e.close()
+        return print_line(result, world, dist)
+
+    # ---- accounting (--full) ------------------------------------------------------------------------------
+    table = e.layer_table()
+    # every conv / deconv launch of the graph: conv_igemm<..>, conv_igemm_v2<..>[+head|+shortcut], conv1_block_fused
+    # (rows of layers that ran fused inside another launch say "fused into ..." and carry no FLOP of their own)
+    conv_rows = [(r, float(layer_ms[r["index"]])) for r in table if r["kernel"].startswith("conv") and r["launches"] > 0]
+    traffic = _pmc_traffic()
+    conv_ms_layers = sum(ms for _, ms in conv_rows)                          # untimed per-launch pass
+    other_ms = float(sum(layer_ms)) - conv_ms_layers                          # non-conv kernels (softmax / glob branch)
+    conv_ms = forward_ms - other_ms                                          # timed region: the conv launches incl. their boundaries
+    conv_flops = sum(r["flops"] for r, _ in conv_rows) * nb                 # algorithmic, per launch-set
+    achieved_tflops = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
+    # operand-split precisions: every algorithmic FLOP costs 3 (6) bf16 MFMA FLOPs, so the bound is the bf16 peak / products
+    products = {"bf16x3": 3, "bf16x6": 6, "fp16x3": 3}.get(args.precision, 1)     # (fp16x3: three fp16 MFMA products, same dense rate as bf16)
+    peak = (PEAK_BF16_DENSE_TFLOPS / products) if args.precision != "fp32" else PEAK_FP32_MFMA_TFLOPS
+    worst = sorted(conv_rows, key=lambda x: -x[1])[:6]
+    result.update({
         "roofline": {"bound": "mfma", "achieved": round(achieved_tflops, 2), "peak": round(peak, 2), "unit": "TFLOP/s",
                      "peak_is": ("dense bf16 MFMA peak %.0f TFLOP/s / %d bf16 products per fp32 product" % (PEAK_BF16_DENSE_TFLOPS, products)) if products > 1
                                 else ("dense bf16 MFMA peak" if args.precision == "bf16" else "exact-fp32 MFMA peak"),
@@ -598,12 +634,6 @@ def main():
                      "slowest_layers_ms": {r["name"]: round(ms, 4) for r, ms in worst},
                      "whole_forward_frac": round(FLOP_PER_IMAGE_256 * nb / (ms_per_step * 1e-3) / 1e12 / peak, 4)},
         "repeats": _spread([world * nb * args.steps / t_ for t_ in [elapsed] + extra], args.steps),
-        "per_rank_images_per_sec": [round(nb * args.steps / t_, 2) for t_ in per_rank],
-        "process_group": {"backend": (dist.get_backend() if world > 1 else None), "ranks": world,
-                          "rccl_ranks": world if (world > 1 and dist.get_backend() == "nccl") else (1 if world == 1 else 0),
-                          "launched_by": os.environ.get("IDC_BENCH_LAUNCHED_BY", "external launcher" if world > 1 else "single process")},
-        "scaling_note": "no hardware scaling curve exists from the builder (1-GPU boxes only): per-N values are whatever the "
-                        "driver's 8-GPU run of this command measures; the path has no data-path collective",
         "layers_ms": {r["name"]: round(float(layer_ms[r["index"]]), 4) for r in table},
         "layers_ms_min": {r["name"]: round(float(layer_min[r["index"]]), 4) for r in table if r["launches"] > 0},
         # same-shape layers that differ (conv5_1 / conv3_2 on the driver's boxes): median vs min over the
@@ -615,7 +645,7 @@ def main():
         "layers_ms_note": "separate untimed pass of %d forwards with an event pair around every launch (these pairs cost ~4 %%): "
                           "`layers_ms` is the per-layer MEDIAN, `layers_ms_min` the minimum, `layers_unsteady` lists launches whose "
                           "max exceeds their min by more than 10 %%" % LAYER_PASS_FORWARDS,
-    }
+    })
     if world == 1 and not args.no_end_to_end:
         result["end_to_end"] = measure_end_to_end(e, nb, args.steps, args.warmup, value)
     if world == 1:
@@ -670,9 +700,6 @@ def main():
         except Exception as ex:                                   # never let a diagnostic leg take the bench line down
             result["roofline"]["zero_operand_probe"] = {"error": str(ex)[:200]}
     e.close()
-    if args.dryrun_single_gpu:
-        result["dryrun_single_gpu"] = ("%d ranks shared ONE GPU over a gloo group: control-flow check only, `value` is not a "
-                                       "scaling measurement" % world)
     if world == 1 and not args.no_peak_probe and args.precision == "bf16":
         probe = mfma_peak_probe()
         if probe:
@@ -724,10 +751,32 @@ def main():
                 "weights": args.weights}
     elif world == 1:
         result["cpu_baseline"] = None
+    print_line(result, world, dist)
+
+
+def print_line(result, world, dist):
+    """Rank 0's one JSON line; the other ranks wait in the matching barrier."""
     print(json.dumps(result))
     sys.stdout.flush()
     if world > 1:
         dist.barrier()
+
+
+def dump_outputs(dirname, dout, rank, world):
+    """--dump-outputs: the (images, 2, H, W) float32 ab map the timed path wrote in its last step -> DIR/out_ab.npy, or
+    DIR/out_ab_rank<r>.npy per rank when N > 1 (rank r's shard = global images r * batch ...).  Every image when they fit this
+    rank's share of DUMP_BYTES, else a fixed seeded sample of them (the same images on every run).  Returns what the line
+    reports under `outputs_dumped`."""
+    nb = int(dout.shape[0])
+    per_image = int(dout[0].numel()) * 4
+    keep = max(1, min(nb, (DUMP_BYTES // world - 4096) // per_image))       # (4096: room for the .npy header)
+    idx = np.arange(nb) if keep == nb else np.sort(np.random.RandomState(0).choice(nb, keep, replace=False))
+    out = np.ascontiguousarray(dout.float().cpu().numpy()[idx])
+    names = ["out_ab.npy"] if world == 1 else ["out_ab_rank%d.npy" % r for r in range(world)]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, names[rank]), out)
+    return {"dir": os.path.abspath(dirname), "files": names, "shape_per_file": list(out.shape), "dtype": "float32",
+            "images_per_file": "all %d" % nb if keep == nb else idx.tolist()}
 
 
 def measure_end_to_end(e, nb, steps, warmup, device_resident_value):

@@ -12,7 +12,8 @@ from interactive_deep_colorization_amd import api, color_bins
 from oracle import display
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_BINS = "/root/reference/data/color_bins"
+# the reference's data/color_bins/*.npy, stored unchanged as fixtures
+REF_BINS = os.path.join(REPO, "tests", "golden", "color_bins")
 
 
 def test_color_bin_tables_definition():
@@ -24,7 +25,6 @@ def test_color_bin_tables_definition():
     assert not np.array_equal(api._grid_529(), g) and np.array_equal(np.sort(api._grid_529(), axis=0), np.sort(g, axis=0))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_BINS), reason="reference checkout not present (authoring container only)")
 def test_color_bin_tables_equal_the_reference_files():
     assert np.array_equal(color_bins.pts_in_hull(), np.load(os.path.join(REF_BINS, "pts_in_hull.npy")))
     assert np.array_equal(color_bins.pts_grid(), np.load(os.path.join(REF_BINS, "pts_grid.npy")))
