@@ -141,15 +141,19 @@ __global__ __launch_bounds__(512) void conv1_1_bf16_kernel(const ConvArgs a) {
 }
 
 // conv1_1 (kConvIm2col) in its throughput form; needs bf16, the fused-pack planes, ReLU/none and no BN / shortcut
+bool conv1_1_bf16_applies(const ConvArgs& a) {
+    return a.pk_L != nullptr && a.bn_scale == nullptr && a.resid == nullptr && !a.out_f32 && a.act != 2 && a.ncg == 1 && a.ksplit <= 1;
+}
+
 hipError_t launch_conv1_1_bf16(const ConvArgs& a, hipStream_t s) {
-    if (a.pk_L == nullptr || a.bn_scale != nullptr || a.resid != nullptr || a.out_f32 || a.act == 2 || a.ncg != 1 || a.ksplit > 1)
-        return hipErrorInvalidConfiguration;
+    if (!conv1_1_bf16_applies(a)) return hipErrorInvalidConfiguration;
     const long long blocks = (long long)((a.Ws + 31) / 32) * ((a.Hs + 31) / 32) * a.N;
     if (blocks <= 0 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
     hipLaunchKernelGGL(conv1_1_bf16_kernel, dim3((unsigned)blocks), dim3(512), 34 * 34 * 16 + 8 * 4096, s, a);
     return hipGetLastError();
 }
 #else
+bool conv1_1_bf16_applies(const ConvArgs&) { return false; }
 hipError_t launch_conv1_1_bf16(const ConvArgs&, hipStream_t) { return hipErrorInvalidConfiguration; }
 #endif
 
@@ -542,9 +546,12 @@ hipError_t init_kernels_conv1() {
     return hipFuncSetAttribute((const void*)conv1_block_fused_t<8, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, conv1_block_lds(8, 4, false));
 }
 
+bool conv1_block_applies(const ConvArgs& a) {
+    return a.pk_L != nullptr && a.wgt2 != nullptr && a.head_b != nullptr && a.ncg == 1 && !a.out_f32 && a.resid == nullptr;
+}
+
 hipError_t launch_conv1_block(const ConvArgs& a, hipStream_t s) {
-    if (a.pk_L == nullptr || a.wgt2 == nullptr || a.head_b == nullptr || a.ncg != 1 || a.out_f32 || a.resid != nullptr)
-        return hipErrorInvalidConfiguration;
+    if (!conv1_block_applies(a)) return hipErrorInvalidConfiguration;
     const bool big = a.tiles_y != 8;                        // a.tiles_y = the engine's request: 8 on the batch-1 click path (too few 32x32 tiles)
     const int th = !big ? 8 : g_c1_lw ? 12 : 32;
     const long long blocks = (long long)((a.Ws + 31) / 32) * ((a.Hs + th - 1) / th) * a.N;
@@ -646,10 +653,13 @@ __global__ __launch_bounds__(256, 2) void conv1_1_split_kernel(const ConvArgs a)
 
 // conv1_1 of an operand-split handle at throughput size: fp32 planes in, a.out_parts (2 | 3) planes out; hipErrorInvalidConfiguration if the launch does not
 // qualify (the caller keeps conv_igemm<float>)
+bool conv1_1_split_applies(const ConvArgs& a) {
+    return a.pk_L != nullptr && a.bn_scale == nullptr && a.resid == nullptr && a.img_shift == nullptr && a.ncg == 1 && a.nkc == 2 && a.so == 1 &&
+           a.out_parts >= 1 && a.out_parts <= 3 && a.in2 == nullptr;
+}
+
 hipError_t launch_conv1_1_split(const ConvArgs& a, hipStream_t s) {
-    if (a.pk_L == nullptr || a.bn_scale != nullptr || a.resid != nullptr || a.img_shift != nullptr || a.ncg != 1 || a.nkc != 2 || a.so != 1 ||
-        a.out_parts < 1 || a.out_parts > 3 || a.in2 != nullptr)
-        return hipErrorInvalidConfiguration;
+    if (!conv1_1_split_applies(a)) return hipErrorInvalidConfiguration;
     const long long blocks = (long long)((a.Ws + 31) / 32) * ((a.Hs + 15) / 16) * a.N;
     if (blocks <= 0 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
     const int lds = 4 * 4096 + 34 * 18 * 16;
@@ -868,11 +878,14 @@ static hipError_t init_kernels_conv1_split() {
 constexpr int kConv12SplitLds = ((34 * 14 * kSlots + 255) / 256) * 256 * kSlotBytes + 2 * kWBlockBytes;      // 77,824
 
 // conv1_2 of an operand-split handle (64 -> 64, 3x3 stride 1, ReLU, optional BN; split tensors in and out); hipErrorInvalidConfiguration otherwise
+bool conv1_2_split_applies(const ConvArgs& a) {
+    return a.ncg == 1 && a.nkc == 1 && a.nphase == 1 && a.ntaps == 9 && a.si == 1 && a.so == 1 && a.dy[8] == 1 && a.act == 1 && a.resid == nullptr &&
+           a.img_shift == nullptr && a.in2 == nullptr && a.pk_L == nullptr && a.head_w == nullptr && !a.out_f32 && a.in_parts >= 1 && a.in_parts <= 3 &&
+           a.out_parts == a.in_parts && a.nseg >= 1 && a.nseg <= 6 && a.w_part_bytes != 0 && (long long)a.Hs * a.Ws * a.in_parts * kRowBytes < 0x7fffffffLL;
+}
+
 hipError_t launch_conv1_2_split(const ConvArgs& a, hipStream_t s) {
-    if (a.ncg != 1 || a.nkc != 1 || a.nphase != 1 || a.ntaps != 9 || a.si != 1 || a.so != 1 || a.dy[8] != 1 || a.act != 1 || a.resid != nullptr ||
-        a.img_shift != nullptr || a.in2 != nullptr || a.pk_L != nullptr || a.head_w != nullptr || a.out_f32 || a.in_parts < 1 || a.in_parts > 3 ||
-        a.out_parts != a.in_parts || a.nseg < 1 || a.nseg > 6 || a.w_part_bytes == 0 || (long long)a.Hs * a.Ws * a.in_parts * kRowBytes >= 0x7fffffffLL)
-        return hipErrorInvalidConfiguration;
+    if (!conv1_2_split_applies(a)) return hipErrorInvalidConfiguration;
     const long long blocks = (long long)((a.Ws + 31) / 32) * ((a.Hs + 11) / 12) * a.N;
     if (blocks <= 0 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
     if (a.split_f16) hipLaunchKernelGGL(conv1_2_split_kernel<true>, dim3((unsigned)blocks), dim3(256), kConv12SplitLds, s, a);

@@ -521,11 +521,14 @@ bool conv_ds_m_fits(int Hs, int Ws, int nkc, int nkc2) {
     return (long long)4 * Hs * Ws * ((long long)(nkc2 > nkc ? nkc2 : nkc) * kRowBytes) < 0x7fffffffLL;
 }
 
+bool conv_ds_m_applies(const ConvArgs& a) {
+    return a.in2 != nullptr && a.wgt2 != nullptr && a.zeros != nullptr && a.nphase == 4 && a.so == 2 && a.si == 1 && !(a.ncg & 1) && !a.out_f32 &&
+           a.bn_scale == nullptr && a.act != 2 && a.img_shift == nullptr && a.resid == nullptr && a.head_w == nullptr &&
+           conv_ds_m_fits(a.Hs, a.Ws, a.nkc, a.nkc2);
+}
+
 hipError_t launch_conv_ds_m(const ConvArgs& a, hipStream_t s) {
-    if (a.in2 == nullptr || a.wgt2 == nullptr || a.zeros == nullptr || a.nphase != 4 || a.so != 2 || a.si != 1 || (a.ncg & 1) || a.out_f32 ||
-        a.bn_scale != nullptr || a.act == 2 || a.img_shift != nullptr || a.resid != nullptr || a.head_w != nullptr ||
-        !conv_ds_m_fits(a.Hs, a.Ws, a.nkc, a.nkc2))
-        return hipErrorInvalidConfiguration;
+    if (!conv_ds_m_applies(a)) return hipErrorInvalidConfiguration;
     const long long blocks = (long long)((a.Ws + 31) / 32) * ((a.Hs + 3) / 4) * a.N * (a.ncg / 2);
     if (blocks <= 0 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
     // fewer 128-cout workgroups than CUs (model10up + shortcut of ONE 256x256 image: 128) and a single shortcut chunk: the 64-cout, 4-wave form
@@ -543,12 +546,15 @@ hipError_t launch_conv_ds_m(const ConvArgs& a, hipStream_t s) {
 }
 
 // ... its operand-split form: a.in / a.in2 / a.out split tensors of a.in_parts (= a.out_parts) planes, a.wgt / a.wgt2 the weight parts' layout-1 images
+bool conv_ds_ms_applies(const ConvArgs& a) {
+    return a.in2 != nullptr && a.wgt2 != nullptr && a.zeros != nullptr && a.nphase == 4 && a.so == 2 && a.si == 1 && !(a.ncg & 1) && !a.out_f32 &&
+           a.img_shift == nullptr && a.resid == nullptr && a.head_w == nullptr && a.in_parts >= 1 && a.in_parts <= 3 && a.out_parts == a.in_parts &&
+           a.nseg >= 1 && a.nseg <= 6 && a.w_part_bytes != 0 && a.w_part_bytes2 != 0 &&
+           conv_ds_m_fits(a.Hs, a.Ws, a.nkc * a.in_parts, a.nkc2 * a.in_parts);
+}
+
 hipError_t launch_conv_ds_ms(const ConvArgs& a, hipStream_t s) {
-    if (a.in2 == nullptr || a.wgt2 == nullptr || a.zeros == nullptr || a.nphase != 4 || a.so != 2 || a.si != 1 || (a.ncg & 1) || a.out_f32 ||
-        a.img_shift != nullptr || a.resid != nullptr || a.head_w != nullptr || a.in_parts < 1 || a.in_parts > 3 || a.out_parts != a.in_parts ||
-        a.nseg < 1 || a.nseg > 6 || a.w_part_bytes == 0 || a.w_part_bytes2 == 0 ||
-        !conv_ds_m_fits(a.Hs, a.Ws, a.nkc * a.in_parts, a.nkc2 * a.in_parts))
-        return hipErrorInvalidConfiguration;
+    if (!conv_ds_ms_applies(a)) return hipErrorInvalidConfiguration;
     const long long blocks = (long long)((a.Ws + 31) / 32) * ((a.Hs + 3) / 4) * a.N * (a.ncg / 2);
     if (blocks <= 0 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
     if (a.split_f16) hipLaunchKernelGGL(conv_ds_fused_msh, dim3((unsigned)blocks), dim3(512), 160 * 1024, s, a);

@@ -479,24 +479,28 @@ struct Tensor {
     size_t bytes = 0;
 };
 
+// The launch_* conv entry point a layer runs (idc_kernels.h).  set_geometry sizes a launch for one of the tile families kConvIgemm,
+// kConvClick, kConvWino, kDeconvWino, kConvKwave (the deconv form and the persistent trunk chain are reached through it) or kConvV2 (the
+// large tile) and records it; choose_kernel then names the entry point, once per layer per forward, and everything after reads that.
+enum Kernel {
+    kConvIgemm, kConvClick, kConvWino, kDeconvWino, kConvKwave,      // launch_conv (+ splitk_epilogue), launch_conv_click, _conv_wino, _deconv_wino, _conv_kwave
+    kConvV2, kConvV2m, kConvV2p, kConvV2s, kConvV2ps,                // the large tile: launch_conv_v2 (partner build), _v2m, _v2p (IDC_FP16: v2ph), _v2s, _v2ps
+    kConvDs, kConvDsM, kConvDsMs,                                    // deconv + shortcut conv: launch_conv_ds (partner build), _ds_m (IDC_FP16: _mh), _ds_ms
+    kConv1Block, kConv1_1Bf16, kConv1_1Split, kConv1_2Split,         // model1: launch_conv1_block, _conv1_1_bf16 (partner build), _conv1_1_split, _conv1_2_split
+    kFused,                                                          // not launched: rides in another layer's launch (its fused_next / fused_short)
+};
+
 struct Layer {
     const LayerSpec* spec = nullptr;
     LayerBlob blob;
     int src = -1, dst = -1, resid = -1;
     int halo = 0;
     ConvConfig cfg{2, 2};
-    bool v2 = false;                     // bf16 large-tile kernel (layout-2 weights)
-    bool m16 = false;                    // ... its 16x16x32-MFMA build (conv_igemm_v2m, layout-1 weights): set per launch in run_graph
-    bool v2p = false;                    // ... conv_igemm_v2p (padded halo rows, unrolled taps): set per launch in run_graph
-    bool f16fast = false;                // IDC_FP16: this launch runs the bf16 throughput kernel's fp16 twin (conv_igemm_v2ph / conv_ds_fused_mh): set per launch in run_graph
-    bool click = false;                  // batch-1 click-path kernel (conv_click: whole K slice by LDS-DMA)
-    bool wino = false;                   // fp32 Winograd F(2x2,3x3) kernel (conv_wino_f32, idc_wino.hip)
-    bool kw = false;                     // bf16 click path: conv_kwave_bf16 (idc_kw.hip: K split over the waves of a workgroup, layout-1 weights)
+    Kernel kernel = kConvIgemm;          // set_geometry's tile family until choose_kernel names the entry point (per forward)
     int chain_len = 0;                   // > 0: this layer and the chain_len - 1 after it ran as ONE conv_kwave_chain_bf16 launch (last forward)
     int chained_into = -1;               // >= 0: ran inside the chain launch headed by that layer (last forward)
     bool fused_head = false;             // conv10_2 only: model_out + tanh run in this layer's epilogue
     int fused_short = -1;                // deconv layers: index of the shortcut conv layer riding in this launch's K loop
-    bool skip = false;                   // layer fused into another launch: not launched itself
     int fused_next = -1;                 // conv1_1 only: index of conv1_2 when model1 runs as one launch (conv1_block_fused)
     int lprec = 0;                       // the precision this layer's kernels run in (the handle's; IDC_FP32 on the fp32 island of a split handle)
     bool split = false;                  // operand-split launch (conv_igemm_v2s / conv_igemm_v2ps)
@@ -729,7 +733,7 @@ static void set_geometry(Layer& L, int precision, int n, int n_policy, int Hs, i
     a.out_f32 = L.spec->out_f32;
     // fp32 path: every 3x3 stride-1 layer whose U image is in the blob runs as Winograd F(2x2,3x3): 2.25x fewer multiplies
     // on the exact-fp32 matrix pipe, no split-K at batch 1 (one workgroup per 16 tiles x 32 couts)
-    L.wino = precision == IDC_FP32 && g_wino && g_tile_policy != 1 && L.blob.w3_off != (size_t)-1 &&
+    bool wino = precision == IDC_FP32 && g_wino && g_tile_policy != 1 && L.blob.w3_off != (size_t)-1 &&
              (L.spec->kind == kDeconv4x4
                   ? (g_wino_deconv == 2 || (g_wino_deconv == 1 && a.nkc >= 8 &&
                                             (long long)((Ws + 7) / 8) * ((Hs + 7) / 8) * n_policy * (a.ncg * 4) <= 1024))
@@ -738,12 +742,10 @@ static void set_geometry(Layer& L, int precision, int n, int n_policy, int Hs, i
     //  workgroup at the 168-register budget of its 12 waves): model10up (4 chunks) 123 us vs 96 us direct at batch 1, and at N = 32
     //  model8up / model9up 1.30 / 1.54 ms vs 1.23 / 1.31 ms direct; "winograd_deconv" = 2 forces it everywhere for the tests)
     const bool wino_fits = wino_offsets_fit(Hs, Ws, L.spec->kind == kDeconv4x4 ? 1 : L.spec->in_stride, a.nkc);   // 32-bit patch offsets
-    L.wino = L.wino && wino_fits;
-    L.kw = false;
-    if (L.wino) { L.v2 = false; L.click = false; a.ksplit = 1; a.kc_per = a.nkc; a.tiles_x = a.tiles_y = 0; return; }
+    wino = wino && wino_fits;
+    if (wino) { L.kernel = L.spec->kind == kDeconv4x4 ? kDeconvWino : kConvWino; a.ksplit = 1; a.kc_per = a.nkc; a.tiles_x = a.tiles_y = 0; return; }
     // large-tile bf16 kernel: 256 couts x (32x8 sites) when the cout groups divide by 4, else
     // 128 couts x (32x16 sites); used when its grid covers at least half of the 256 CUs
-    L.v2 = false;
     const bool split = is_split(precision);      // operand-split precisions: a throughput path, the large tile on every layer whatever the grid
     // (default library: fp32-output launches -- class_logits -- stay on the small tile: conv_igemm_v2m / v2p write bf16 only)
     const bool v2_covers = allow_v2 && (kAbPartners || !L.spec->out_f32);
@@ -770,14 +772,13 @@ static void set_geometry(Layer& L, int precision, int n, int n_policy, int Hs, i
             blocks = (long long)tx * ty * n_policy * (a.ncg / c2.wm) * a.nphase;
         }
         if (split || g_tile_policy == 2 || blocks >= tuning().v2_min_blocks) {
-            L.v2 = true; L.cfg = c2; a.tiles_x = tx; a.tiles_y = ty;
+            L.kernel = kConvV2; L.cfg = c2; a.tiles_x = tx; a.tiles_y = ty;
             a.ksplit = 1; a.kc_per = a.nkc;
             return;
         }
     }
     // batch-1 click path: small launches are chains of exposed memory round trips in conv_igemm's K loop; conv_click
     // requests a workgroup's whole K slice at entry (as many cin chunks as fit in LDS next to their halo tiles)
-    L.click = false;
     // ... "small" = fewer than v2_min_blocks big tiles (the criterion that hands a layer to the throughput kernels, applied to
     // every precision and cout width): conv_igemm's ring loop is the better kernel once the K loop is long and the chip full
     const int wm_big = a.ncg % 4 == 0 ? 4 : (a.ncg % 2 == 0 ? 2 : 1), rows_big = wm_big == 4 ? 8 : 16;
@@ -785,15 +786,14 @@ static void set_geometry(Layer& L, int precision, int n, int n_policy, int Hs, i
     // bf16 click path, deconvs: the direct form with K split over the waves of a workgroup (conv_kwave_deconv_bf16, idc_kw.hip)
     if (precision == IDC_BF16 && g_kwave && g_tile_policy != 1 && big_tiles < tuning().v2_min_blocks && wino_fits &&
         L.spec->kind == kDeconv4x4 && (a.nkc == 2 || a.nkc == 4 || a.nkc == 8)) {
-        L.kw = true; a.ksplit = 1; a.kc_per = a.nkc; a.tiles_x = a.tiles_y = 0;
+        L.kernel = kConvKwave; a.ksplit = 1; a.kc_per = a.nkc; a.tiles_x = a.tiles_y = 0;
         return;
     }
     // bf16 click path, 3x3 stride-1 layers: the direct form with K split over the waves of a workgroup (idc_kw.hip) -- 9/16 of the Winograd
     // form's weight stream, no reduction launch either
-    L.kw = false;
     if (precision == IDC_BF16 && g_kwave && g_tile_policy != 1 && big_tiles < tuning().v2_min_blocks && wino_fits && L.spec->resid == nullptr &&
         L.spec->kind == kConv3x3 && (a.nkc == 1 || a.nkc == 2 || a.nkc == 4 || a.nkc == 8)) {
-        L.kw = true; a.ksplit = 1; a.kc_per = a.nkc; a.tiles_x = a.tiles_y = 0;
+        L.kernel = kConvKwave; a.ksplit = 1; a.kc_per = a.nkc; a.tiles_x = a.tiles_y = 0;
         return;
     }
     if ((g_click < 0 ? tuning().click : g_click) && g_tile_policy != 1 && big_tiles < tuning().v2_min_blocks &&
@@ -811,13 +811,14 @@ static void set_geometry(Layer& L, int precision, int n, int n_policy, int Hs, i
             if (kc_per >= 1) {
                 const int ks = (a.nkc + kc_per - 1) / kc_per;
                 if (tiles * ks <= tuning().click_max_wgs) {
-                    L.click = true; L.cfg = ConvConfig{1, wp};
+                    L.kernel = kConvClick; L.cfg = ConvConfig{1, wp};
                     a.tiles_x = tx; a.tiles_y = ty; a.kc_per = kc_per; a.ksplit = ks;
                     return;
                 }
             }
         }
     }
+    L.kernel = kConvIgemm;
     L.cfg = choose_config(n_policy, Hs, Ws, L.blob.ncg * kCoutGroup, a.nphase);
     a.tiles_x = (Ws + 15) / 16;
     a.tiles_y = (Hs + 4 * L.cfg.wp - 1) / (4 * L.cfg.wp);
@@ -835,6 +836,96 @@ static void set_geometry(Layer& L, int precision, int n, int n_policy, int Hs, i
             a.ksplit = (a.nkc + a.kc_per - 1) / a.kc_per;          // every slice is non-empty
             if (a.ksplit < 2) { a.ksplit = 1; a.kc_per = a.nkc; }
         }
+    }
+}
+
+// The entry point a layer launches this forward: set_geometry's tile family (L.kernel) refined by the fusions planned on the layer, its bound
+// arguments and the options.  An exclusive chain in precedence order; where an entry point covers only some launches, its predicate decides
+// here, so the launch that follows is never refused (a refusal is a planning bug: run_graph / run_single_op report it).
+// max_batch: the batch the variant is chosen for (as set_geometry's n_policy), so that a result never depends on how many images share a call.
+static Kernel choose_kernel(const Layer& L, int precision, int max_batch) {
+    const ConvArgs& a = L.args;
+    const Kernel tile = L.kernel;
+    const long long tiles32 = (long long)((a.Ws + 31) / 32) * max_batch;       // x (tile rows) = workgroups of a 32-wide tile
+    if (tile == kFused) return kFused;
+    if (L.fused_next >= 0) return kConv1Block;
+    if (L.fused_short >= 0) {
+        if (L.split)              // IDC_FP16: conv_ds_fused_mh (the bf16 kernel's fp16 twin) where it covers the launch
+            return precision == IDC_FP16 && g_fp16_fast && conv_ds_m_applies(a) ? kConvDsM : kConvDsMs;
+        return g_ds_m16 && conv_ds_m_applies(a) ? kConvDsM : kConvDs;      // (huge images: conv_ds_fused, 64-bit addressing)
+    }
+    if (L.spec->kind == kConvIm2col) {
+        // conv1_1 with >= 128 big tiles: the 32x32-tile form (the small-tile kernel keeps the batch-1 click path)
+        if (L.lprec == IDC_BF16 && a.ksplit <= 1 && tiles32 * ((a.Hs + 31) / 32) >= 128 && conv1_1_bf16_applies(a)) return kConv1_1Bf16;
+        // the fp32 island of an operand-split handle where the grid is throughput-sized
+        if (is_split(precision) && !L.split && g_conv1_1_split && tiles32 * ((a.Hs + 15) / 16) >= 128 && conv1_1_split_applies(a)) return kConv1_1Split;
+    }
+    if (L.split) {                // (every operand-split layer is planned on the large tile: set_geometry)
+        // IDC_FP16: where the bf16 forward's own kernels cover the launch, their fp16 twins (same tile, bias in the accumulators, packed-pair epilogue)
+        if (precision == IDC_FP16 && g_fp16_fast && g_v2p && conv_v2p_applies(L.cfg, L.halo, a)) return kConvV2p;
+        if (g_conv1_2_split && conv1_2_split_layer(*L.spec) && tiles32 * ((a.Hs + 11) / 12) >= 256 && conv1_2_split_applies(a)) return kConv1_2Split;
+        return g_v2p && conv_v2ps_applies(L.cfg, L.halo, a) ? kConvV2ps : kConvV2s;
+    }
+    if (tile == kConvV2 && g_mfma16 && conv_v2m_applies(a))      // the 16x16x32-MFMA builds read the layout-1 image
+        return g_v2p && conv_v2p_applies(L.cfg, L.halo, a) ? kConvV2p : kConvV2m;
+    return tile;
+}
+
+// One launch of the entry point `k` (kConvKwave: one layer; run_graph tries the persistent chain first).
+static hipError_t launch_kernel(Kernel k, const Layer& L, const ConvArgs& a, hipStream_t s) {
+    switch (k) {
+        case kConvIgemm: return launch_conv(L.lprec, L.cfg, L.halo, a, s);
+        case kConvClick: return launch_conv_click(L.lprec, L.cfg.wp, L.halo, a, s);
+        case kConvWino: return launch_conv_wino(L.lprec, a, s);
+        case kDeconvWino: return launch_deconv_wino(L.lprec, a, s);
+        case kConvKwave: return launch_conv_kwave(a, s);
+        case kConvV2: return launch_conv_v2(L.cfg, L.halo, a, s);
+        case kConvV2m: return launch_conv_v2m(L.cfg, L.halo, a, s);
+        case kConvV2p: return launch_conv_v2p(L.cfg, L.halo, a, s);
+        case kConvV2s: return launch_conv_v2s(L.cfg, L.halo, a, s);
+        case kConvV2ps: return launch_conv_v2ps(L.cfg, L.halo, a, s);
+        case kConvDs: return launch_conv_ds(a, s);
+        case kConvDsM: return launch_conv_ds_m(a, s);
+        case kConvDsMs: return launch_conv_ds_ms(a, s);
+        case kConv1Block: return launch_conv1_block(a, s);
+        case kConv1_1Bf16: return launch_conv1_1_bf16(a, s);
+        case kConv1_1Split: return launch_conv1_1_split(a, s);
+        case kConv1_2Split: return launch_conv1_2_split(a, s);
+        case kFused: break;
+    }
+    return hipErrorInvalidConfiguration;
+}
+
+// The kernel a layer's launch ran (idc_layer_info_get; the names rocprofv3 shows, template arguments as <WM,WP>), from its entry point
+static void kernel_label(const Layer& L, int precision, char* out, size_t cap) {
+    const int wm = L.cfg.wm, wp = L.cfg.wp, nseg = split_segments(precision);
+    const bool f16 = split_is_f16(precision), deconv = L.spec->kind == kDeconv4x4;
+    const char* const t = L.lprec == IDC_BF16 ? "bf16" : "f32";
+    switch (L.kernel) {
+        case kConvIgemm: snprintf(out, cap, "conv_igemm<%s,%d,%d>", t, wm, wp); break;
+        case kConvClick: snprintf(out, cap, "conv_click<%s,%d,%d>", t, wm, wp); break;
+        case kConvWino: snprintf(out, cap, "conv_wino_f32"); break;
+        case kDeconvWino: snprintf(out, cap, "conv_wino_deconv_f32"); break;
+        case kConvKwave: snprintf(out, cap, deconv ? "conv_kwave_deconv_bf16" : "conv_kwave_bf16"); break;
+        case kConvV2: snprintf(out, cap, "conv_igemm_v2<%d,%d>", wm, wp); break;
+        case kConvV2m: snprintf(out, cap, "conv_igemm_v2<%d,%d>+m16", wm, wp); break;
+        case kConvV2p: snprintf(out, cap, f16 ? "conv_igemm_v2ph<%d,%d>" : "conv_igemm_v2<%d,%d>+m16p", wm, wp); break;
+        case kConvV2s: snprintf(out, cap, f16 ? "conv_igemm_v2sh<%d,%d>x%d" : "conv_igemm_v2s<%d,%d>x%d", wm, wp, nseg); break;
+        case kConvV2ps: snprintf(out, cap, f16 ? "conv_igemm_v2psh<%d,%d>x%d" : "conv_igemm_v2ps<%d,%d>x%d", wm, wp, nseg); break;
+        // (the deconv and its 3x3 shortcut conv in one K loop)
+        case kConvDs: snprintf(out, cap, "conv_ds_fused+shortcut"); break;
+        case kConvDsM: snprintf(out, cap, f16 ? "conv_ds_fused_mh+shortcut" : "conv_ds_fused_m+shortcut"); break;
+        case kConvDsMs: snprintf(out, cap, f16 ? "conv_ds_fused_msh+shortcut x%d" : "conv_ds_fused_ms+shortcut x%d", L.args.nseg); break;
+        case kConv1Block: snprintf(out, cap, "conv1_block_fused"); break;
+        case kConv1_1Bf16: snprintf(out, cap, "conv1_1_bf16_kernel"); break;
+        case kConv1_1Split: snprintf(out, cap, "conv1_1_split_kernel"); break;
+        case kConv1_2Split: snprintf(out, cap, "conv1_2_split_kernel x%d", nseg); break;
+        case kFused: snprintf(out, cap, "fused"); break;
+    }
+    if (L.fused_head) strncat(out, "+head", cap - strlen(out) - 1);
+    if (L.args.ksplit > 1) {
+        char sk[16]; snprintf(sk, sizeof(sk), " splitK%d", L.args.ksplit);
+        strncat(out, sk, cap - strlen(out) - 1);
     }
 }
 
@@ -973,6 +1064,63 @@ static int alloc_graph(idc_context* c) {
 
 static int check_chain_abort(idc_context* c);
 
+// The run of same-shape 8-chunk conv_kwave_bf16 layers that starts at layer li (conv4_2 .. conv7_3 at batch 1) as ONE persistent
+// conv_kwave_chain_bf16 launch, where the handle and the device allow it: on success L.chain_len > 0 and *chain_until = the run's last
+// layer; otherwise nothing is launched and the caller launches layer li alone.
+static int launch_kwave_chain(idc_context* c, int li, hipStream_t s, int* chain_until) {
+    Layer& L = c->layers[li];
+    const ConvArgs& a = L.args;
+    if (!g_kwave_chain || c->kw_chain_off || c->profiling == 1 || !c->d_kw_bar || L.spec->kind != kConv3x3 || a.nkc != 8 || a.si != 1 ||
+        a.img_shift != nullptr || a.out_f32)
+        return IDC_OK;
+    const int blocks = conv_kwave_chain_blocks(a.Hs, a.Ws, a.N, a.ncg, a.dy[8]);
+    KwChainArgs ch{};
+    ch.H = a.Hs; ch.W = a.Ws; ch.N = a.N; ch.ncg = a.ncg;
+    ch.spin_limit = 200000u;                   // x ~1.5 us per poll: a third of a second, then the workgroup gives up
+    int last = li, prev_dst = L.src;
+    for (int j = li; j < (int)c->layers.size() && ch.nlayers < kKwChainMax; ++j) {
+        Layer& Q = c->layers[j];
+        const bool shifted = (c->flags & IDC_FLAG_GLOBAL_HINTS) && Q.dst == c->t_conv4_3;
+        if (Q.kernel != kConvKwave || Q.spec->kind != kConv3x3 || Q.blob.nkc != 8 || Q.spec->in_stride != 1 || Q.resid >= 0 || shifted ||
+            c->tensors[Q.dst].is_f32 || Q.src != prev_dst || Q.args.Hs != a.Hs || Q.args.Ws != a.Ws || Q.args.ncg != a.ncg ||
+            conv_kwave_chain_blocks(a.Hs, a.Ws, a.N, a.ncg, Q.args.dy[8]) != blocks)
+            break;
+        KwChainLayer& y = ch.layer[ch.nlayers++];
+        y.in = c->tensors[Q.src].ptr; y.out = c->tensors[Q.dst].ptr;
+        y.wgt = c->d_blob + Q.blob.w_off;
+        y.bias = (const float*)(c->d_blob + Q.blob.bias_off);
+        y.bn_scale = Q.blob.bn_scale_off != (size_t)-1 ? (const float*)(c->d_blob + Q.blob.bn_scale_off) : nullptr;
+        y.bn_shift = Q.blob.bn_shift_off != (size_t)-1 ? (const float*)(c->d_blob + Q.blob.bn_shift_off) : nullptr;
+        y.act = Q.spec->act; y.d = Q.args.dy[8];
+        prev_dst = Q.dst; last = j;
+    }
+    if (ch.nlayers < 2 || blocks <= 0) return IDC_OK;
+    if (c->kw_chain_fits < 0) c->kw_chain_fits = conv_kwave_chain_capacity(c->device);
+    if (c->kw_chain_fits < blocks) return IDC_OK;   // more workgroups than the chip holds at once: this launch goes layer by layer
+    if (blocks != c->kw_bar_blocks) {      // counters hold (barriers so far) x (arrivals per barrier of THIS grid)
+        HIPCHK(c, hipMemsetAsync(c->d_kw_bar, 0, 1024, s));
+        c->kw_bar_count = 0; c->kw_bar_blocks = blocks;
+    }
+    ch.bar = c->d_kw_bar; ch.bar_base = c->kw_bar_count; ch.abort_flag = c->h_kw_abort;
+    // test hook (tests/test_round5_gpu.py): IDC_KW_FORCE_ABORT=1 makes the first grid barrier unreachable and the give-up
+    // counter tiny, i.e. it plays "the workgroups never become co-resident" on a healthy device
+    if (g_kw_force_abort) { ch.bar_base += 1000; ch.spin_limit = 20u; }
+    static const bool want_stamps = idc_env_int("IDC_KW_STAMPS", 0) != 0;
+    if (want_stamps && !c->d_kw_stamps) HIPCHK(c, hipMalloc((void**)&c->d_kw_stamps, (size_t)4096 * kKwChainMax * 8 * 8));
+    ch.stamps = (want_stamps && blocks <= 4096) ? c->d_kw_stamps : nullptr;
+    c->kw_stamp_layers = ch.nlayers; c->kw_stamp_blocks = blocks;
+    if (launch_conv_kwave_chain(ch, blocks, g_kwave_chain, s) != hipSuccess) {
+        (void)hipGetLastError();          // refused (e.g. hipErrorCooperativeLaunchTooLarge): one launch per layer from now on
+        c->kw_chain_off = true;
+        return IDC_OK;
+    }
+    c->kw_bar_count += (unsigned long long)(ch.nlayers - 1);
+    L.chain_len = ch.nlayers;
+    for (int j = li + 1; j <= last; ++j) c->layers[j].chained_into = li;
+    *chain_until = last;
+    return IDC_OK;
+}
+
 static int run_graph(idc_context* c, int n, const float* dL, const float* dab, const float* dmask, float maskcent,
                      float* dout, float* ddist) {
     hipStream_t s = c->stream;
@@ -989,14 +1137,14 @@ static int run_graph(idc_context* c, int n, const float* dL, const float* dab, c
     if (c->flags & IDC_FLAG_GLOBAL_HINTS)      // four GEMVs per image; its output is consumed by conv4_3's epilogue
         HIPCHK(c, launch_glob_branch(c->d_glob_in, (const float*)(c->d_blob + c->plan.glob_off), c->d_glob_vec, n, s));
     toc();
-    // pass 1: kernel variant per layer, then which shortcut convs ride in their consumer's launch
+    // pass 1: tile family per layer, then which shortcut convs ride in their consumer's launch
     for (auto& L : c->layers) {
         const Tensor& ti = c->tensors[L.src];
         const Tensor& to = c->tensors[L.dst];
         const int Hs = L.spec->kind == kDeconv4x4 ? ti.H : to.H;
         const int Ws = L.spec->kind == kDeconv4x4 ? ti.W : to.W;
         set_geometry(L, L.lprec, n, c->max_batch, Hs, Ws);
-        L.fused_short = -1; L.skip = false; L.fused_next = -1;
+        L.fused_short = -1; L.fused_next = -1;
     }
     // model1 in one launch: conv1_1 (input pack fused) followed by conv1_2 on the small-tile bf16 path, >= 128 big tiles
     for (size_t i = 0; i + 1 < c->layers.size(); ++i) {
@@ -1012,15 +1160,16 @@ static int run_graph(idc_context* c, int n, const float* dL, const float* dab, c
         for (size_t j = 0; j < c->layers.size(); ++j) {
             Layer& P = c->layers[j];
             const LayerSpec& ps = *P.spec;
-            if (P.src != L.dst || (P.v2 && !f16blk) || ps.kind != kConv3x3 || ps.cin != 64 || ps.cout != 64 || ps.dilation != 1 ||
-                ps.in_stride != 1 || ps.act != 1 || ps.resid || c->tensors[P.dst].is_f32 || P.args.ksplit > 1 || P.click || P.wino) continue;
+            if (P.src != L.dst || (P.kernel == kConvV2 && !f16blk) || ps.kind != kConv3x3 || ps.cin != 64 || ps.cout != 64 || ps.dilation != 1 ||
+                ps.in_stride != 1 || ps.act != 1 || ps.resid || c->tensors[P.dst].is_f32 || P.args.ksplit > 1 || P.kernel == kConvClick ||
+                P.kernel == kConvWino) continue;
             bool only_consumer = true;
             for (const Layer& Q : c->layers) if (&Q != &P && (Q.src == L.dst || Q.resid == L.dst)) only_consumer = false;
-            if (only_consumer) { L.fused_next = (int)j; P.skip = true; L.args.tiles_y = tile_req; }
+            if (only_consumer) { L.fused_next = (int)j; P.kernel = kFused; L.args.tiles_y = tile_req; }
         }
     }
     for (auto& L : c->layers) {
-        if (L.spec->kind != kDeconv4x4 || L.resid < 0 || !L.v2 || !fuse_shortcut_enabled() || (L.split && !g_split_ds_fuse)) continue;
+        if (L.spec->kind != kDeconv4x4 || L.resid < 0 || L.kernel != kConvV2 || !fuse_shortcut_enabled() || (L.split && !g_split_ds_fuse)) continue;
         if (L.spec->cout % 128 != 0 || L.spec->bnkey || L.spec->act == 2 || c->tensors[L.dst].is_f32) continue;   // conv_ds_fused's domain
         for (size_t j = 0; j < c->layers.size(); ++j) {
             Layer& P = c->layers[j];
@@ -1033,24 +1182,27 @@ static int run_graph(idc_context* c, int n, const float* dL, const float* dab, c
                     ps.cout == L.spec->cout && pin.H == to.H && pin.W == to.W && !pin.is_f32 && pin.parts == to.parts &&
                     c->tensors[L.src].parts == to.parts && !c->tensors[L.src].is_f32 &&
                     conv_ds_m_fits(L.args.Hs, L.args.Ws, L.blob.nkc * to.parts, P.blob.nkc * to.parts)) {
-                    L.fused_short = (int)j; P.skip = true;
+                    L.fused_short = (int)j; P.kernel = kFused;
                 }
                 continue;
             }
             if (ps.kind == kConv3x3 && ps.dilation == 1 && ps.in_stride == 1 && ps.act == 0 && !ps.bnkey && !ps.resid &&
                 ps.cout == L.spec->cout && pin.H == to.H && pin.W == to.W && !pin.is_f32 && (!kAbPartners || P.blob.w2_off != (size_t)-1) &&
                 (kAbPartners || (g_ds_m16 != 0 && conv_ds_m_fits(L.args.Hs, L.args.Ws, L.blob.nkc, P.blob.nkc)))) {      // (default library: conv_ds_fused_m or two launches)
-                L.fused_short = (int)j; P.skip = true;
+                L.fused_short = (int)j; P.kernel = kFused;
             }
         }
     }
     if (!kAbPartners)            // a large-tile deconv that keeps its shortcut SUM (not fused: images beyond 32-bit offsets) has no 16x16x32 kernel: small tile
         for (auto& L : c->layers)
-            if (L.v2 && !L.split && L.resid >= 0 && L.fused_short < 0) {
+            if (L.kernel == kConvV2 && !L.split && L.resid >= 0 && L.fused_short < 0) {
                 const Tensor& ti = c->tensors[L.src];
                 const Tensor& to = c->tensors[L.dst];
                 set_geometry(L, L.lprec, n, c->max_batch, L.spec->kind == kDeconv4x4 ? ti.H : to.H, L.spec->kind == kDeconv4x4 ? ti.W : to.W, false);
             }
+    // diagnostic (IDC_DOUBLE_LAUNCH=1): every launch issued twice, the event pair around the SECOND -- a layer that is slow only as
+    // the first launch of its kernel after other kernels (cold instruction cache / first touch) shows its warm time here
+    static const bool double_launch = idc_env_int("IDC_DOUBLE_LAUNCH", 0) != 0;
     bool head_done = false;
     int chain_until = -1;                      // layers up to this index ran inside the conv_kwave_chain_bf16 launch of an earlier layer
     for (auto& L : c->layers) {
@@ -1059,7 +1211,8 @@ static int run_graph(idc_context* c, int n, const float* dL, const float* dab, c
         const int li_ = (int)(&L - &c->layers[0]);
         L.chain_len = 0;
         if (li_ > chain_until) L.chained_into = -1;
-        if (L.skip || li_ <= chain_until) { tic(); toc(); continue; }
+        if (L.kernel == kFused || li_ <= chain_until) { tic(); toc(); continue; }
+        // 1. bind: this forward's tensors, the layer's parameters in the blob (layout-1 weight images) and what rides in the launch
         ConvArgs& a = L.args;
         a.in = ti.ptr; a.out = to.ptr;
         a.zeros = c->d_zeros;
@@ -1074,25 +1227,23 @@ static int run_graph(idc_context* c, int n, const float* dL, const float* dab, c
         } else {
             a.pk_L = nullptr;
         }
-        a.wgt = c->d_blob + (L.wino ? L.blob.w3_off : (L.v2 && L.blob.w2_off != (size_t)-1) ? L.blob.w2_off : L.blob.w_off);
+        a.wgt = c->d_blob + L.blob.w_off;
         a.bias = (const float*)(c->d_blob + L.blob.bias_off);
         a.bn_scale = L.blob.bn_scale_off != (size_t)-1 ? (const float*)(c->d_blob + L.blob.bn_scale_off) : nullptr;
         a.bn_shift = L.blob.bn_shift_off != (size_t)-1 ? (const float*)(c->d_blob + L.blob.bn_shift_off) : nullptr;
         if (L.fused_short >= 0) {            // model8up(.) + model3short8(.) in one K loop (model.py:156,170,172)
             const Layer& P = c->layers[L.fused_short];
             a.resid = nullptr; a.resid_bf16 = 0;
-            a.in2 = c->tensors[P.src].ptr; a.wgt2 = c->d_blob + (P.blob.w2_off != (size_t)-1 ? P.blob.w2_off : P.blob.w_off); a.nkc2 = P.blob.nkc;
+            a.in2 = c->tensors[P.src].ptr; a.wgt2 = c->d_blob + P.blob.w_off; a.nkc2 = P.blob.nkc;
             a.bias = (const float*)(c->d_blob + L.blob.fbias_off);
-            L.m16 = g_ds_m16 != 0 && conv_ds_m_fits(a.Hs, a.Ws, a.nkc, P.blob.nkc);   // (huge images: conv_ds_fused, 64-bit addressing)
-            if (L.m16) { a.wgt = c->d_blob + L.blob.w_off; a.wgt2 = c->d_blob + P.blob.w_off; }   // conv_ds_fused_m reads the layout-1 images
-            if (L.split) { L.m16 = true; a.wgt = c->d_blob + L.blob.w_off; a.wgt2 = c->d_blob + P.blob.w_off; a.w_part_bytes2 = P.blob.w_bytes; }
+            if (L.split) a.w_part_bytes2 = P.blob.w_bytes;
         } else {
             a.resid = L.resid >= 0 ? c->tensors[L.resid].ptr : nullptr;
             a.resid_bf16 = (L.resid >= 0 && !c->tensors[L.resid].is_f32) ? 1 : 0;
             a.in2 = nullptr; a.wgt2 = nullptr; a.nkc2 = 0;
         }
         // the regression head rides in conv10_2's epilogue when one workgroup owns all 128 channels
-        L.fused_head = L.dst == c->t_conv10_2 && L.v2 && L.cfg.wm == 2 && a.ncg == 2 && L.spec->bnkey == nullptr;
+        L.fused_head = L.dst == c->t_conv10_2 && L.kernel == kConvV2 && L.cfg.wm == 2 && a.ncg == 2 && L.spec->bnkey == nullptr;
         a.head_w = L.fused_head ? (const float*)(c->d_blob + c->plan.head_w_off) : nullptr;
         a.head_b = (const float*)(c->d_blob + c->plan.head_b_off);
         a.head_out = dout; a.head_mul = c->out_mul;
@@ -1124,131 +1275,37 @@ static int run_graph(idc_context* c, int n, const float* dL, const float* dab, c
         if (is_split(c->precision) && !L.split) {        // fp32 island: conv_igemm<f32> with a split store (no split-K: its epilogue kernel writes fp32)
             a.out_parts = to.is_f32 ? 0 : to.parts;
             a.out_f32 = 1; a.ksplit = 1; a.kc_per = a.nkc;
-            if (L.wino || L.click || L.v2 || L.kw) return fail(&c->err, IDC_ERR_INTERNAL, "layer %s: fp32 island outside conv_igemm", L.spec->name);
+            if (L.kernel != kConvIgemm) return fail(&c->err, IDC_ERR_INTERNAL, "layer %s: fp32 island outside conv_igemm", L.spec->name);
         }
         if (L.split) {
             // operand-split launch: nseg passes of the K loop (input part x weight part) into one accumulator set; split in / out tensors
-            a.wgt = c->d_blob + L.blob.w_off;
             a.in_parts = ti.parts; a.out_parts = (to.is_f32 || L.fused_head) ? 0 : to.parts;
             a.nseg = split_segments(c->precision); a.seg_x = split_seg_x(c->precision); a.seg_w = split_seg_w(c->precision);
             a.w_part_bytes = L.blob.w_bytes;
-            if (L.fused_short < 0 && (!L.v2 || !conv_v2s_applies(a)))
-                return fail(&c->err, IDC_ERR_INTERNAL, "layer %s: no operand-split kernel covers this launch", L.spec->name);
-            L.m16 = true;
-            L.v2p = L.fused_short < 0 && g_v2p && conv_v2ps_applies(L.cfg, L.halo, a);
-            // IDC_FP16: where the bf16 forward's own kernels cover the launch, their fp16 twins (same tile, bias in the accumulators, packed-pair epilogue)
-            L.f16fast = c->precision == IDC_FP16 && g_fp16_fast && !to.is_f32 &&
-                        (L.fused_short >= 0 ? (L.spec->act != 2 && !L.spec->bnkey && (a.ncg & 1) == 0) : (L.v2 && g_v2p && conv_v2p_applies(L.cfg, L.halo, a)));
-        } else if (L.fused_short < 0) {
-            L.m16 = L.v2 && g_mfma16 && L.fused_next < 0 && !L.wino && !L.click && conv_v2m_applies(a);
-            if (L.m16) a.wgt = c->d_blob + L.blob.w_off;            // the layout-1 image (the one conv_igemm / conv_click read)
-            L.v2p = L.m16 && g_v2p && conv_v2p_applies(L.cfg, L.halo, a);
         }
-        // diagnostic (IDC_DOUBLE_LAUNCH=1): every launch issued twice, the event pair around the SECOND -- a layer that is slow only as
-        // the first launch of its kernel after other kernels (cold instruction cache / first touch) shows its warm time here
-        static const bool double_launch = idc_env_int("IDC_DOUBLE_LAUNCH", 0) != 0;
+        // 2. choose
+        L.kernel = choose_kernel(L, c->precision, c->max_batch);
+        // ... and the weight images it reads where they are not layout 1
+        if (L.kernel == kConvWino || L.kernel == kDeconvWino) a.wgt = c->d_blob + L.blob.w3_off;
+        if ((L.kernel == kConvV2 || L.kernel == kConvDs) && L.blob.w2_off != (size_t)-1) a.wgt = c->d_blob + L.blob.w2_off;
+        if (L.kernel == kConvDs && c->layers[L.fused_short].blob.w2_off != (size_t)-1) a.wgt2 = c->d_blob + c->layers[L.fused_short].blob.w2_off;
+        // 3. launch
         for (int rep = double_launch ? 0 : 1; rep < 2; ++rep) {
-        if (rep == 1) tic();
-        {
-            hipError_t le = hipErrorInvalidConfiguration;
-            // conv1_1 with >= 128 big tiles: the 32x32-tile form (the small-tile kernel keeps the batch-1 click path).
-            // Chosen by the handle's max_batch like every other kernel variant, so a result never depends on how many
-            // images share the call.
-            if (L.fused_next >= 0) le = launch_conv1_block(a, s);
-            else if (L.spec->kind == kConvIm2col && L.lprec == IDC_BF16 && a.ksplit <= 1 &&
-                (long long)((a.Ws + 31) / 32) * ((a.Hs + 31) / 32) * c->max_batch >= 128)
-                le = launch_conv1_1_bf16(a, s);
-            if (is_split(c->precision) && !L.split && L.fused_next < 0 && L.spec->kind == kConvIm2col && g_conv1_1_split && a.out_parts >= 1 &&
-                (long long)((a.Ws + 31) / 32) * ((a.Hs + 15) / 16) * c->max_batch >= 128)
-                le = launch_conv1_1_split(a, s);
-            if (L.split && L.f16fast) le = L.fused_short >= 0 ? launch_conv_ds_m(a, s) : launch_conv_v2p(L.cfg, L.halo, a, s);
-            else
-            if (L.split && L.fused_short < 0 && g_conv1_2_split && conv1_2_split_layer(*L.spec) && !to.is_f32 &&
-                (long long)((a.Ws + 31) / 32) * ((a.Hs + 11) / 12) * c->max_batch >= 256)
-                le = launch_conv1_2_split(a, s);
-            if (L.fused_short >= 0 && !(L.split && L.f16fast)) le = L.split ? launch_conv_ds_ms(a, s) : L.m16 ? launch_conv_ds_m(a, s) : launch_conv_ds(a, s);
-            if (L.fused_short >= 0 && L.split && le == hipErrorInvalidConfiguration)
-                return fail(&c->err, IDC_ERR_INTERNAL, "layer %s: conv_ds_fused_ms planned for a launch it does not cover", L.spec->name);
-    // deconv + its shortcut conv in one K loop
-            if (L.wino) {
-                // a.wgt points at the Winograd U image and L.cfg / tiles were never set for this layer: a refused launch must not fall
-                // through to the direct kernels below -- it is a variant-selection bug and says so
-                if (!conv_wino_applies(L.lprec, a, L.spec->kind == kDeconv4x4))
-                    return fail(&c->err, IDC_ERR_INTERNAL, "layer %s: Winograd variant selected for a launch it does not cover", L.spec->name);
-                le = L.spec->kind == kDeconv4x4 ? launch_deconv_wino(L.lprec, a, s) : launch_conv_wino(L.lprec, a, s);
-                HIPCHK(c, le);
+            if (rep == 1) tic();
+            bool chained = false;
+            if (L.kernel == kConvKwave && !double_launch) {
+                const int rc = launch_kwave_chain(c, li_, s, &chain_until);
+                if (rc) return rc;
+                chained = L.chain_len > 0;
             }
-            if (L.kw) {
-                if (!conv_kwave_applies(a))
-                    return fail(&c->err, IDC_ERR_INTERNAL, "layer %s: conv_kwave_bf16 selected for a launch it does not cover", L.spec->name);
-                le = hipErrorInvalidConfiguration;
-                // the run of same-shape 8-chunk layers that starts here (conv4_2 .. conv7_3 at batch 1) as ONE persistent launch
-                if (g_kwave_chain && !c->kw_chain_off && c->profiling != 1 && !double_launch && c->d_kw_bar && L.spec->kind == kConv3x3 && a.nkc == 8 &&
-                    a.si == 1 && a.img_shift == nullptr && !a.out_f32) {
-                    const int blocks = conv_kwave_chain_blocks(a.Hs, a.Ws, a.N, a.ncg, a.dy[8]);
-                    KwChainArgs ch{};
-                    ch.H = a.Hs; ch.W = a.Ws; ch.N = a.N; ch.ncg = a.ncg;
-                    ch.spin_limit = 200000u;                   // x ~1.5 us per poll: a third of a second, then the workgroup gives up
-                    int last = li_, prev_dst = L.src;
-                    for (int j = li_; j < (int)c->layers.size() && ch.nlayers < kKwChainMax; ++j) {
-                        Layer& Q = c->layers[j];
-                        const bool shifted = (c->flags & IDC_FLAG_GLOBAL_HINTS) && Q.dst == c->t_conv4_3;
-                        if (Q.skip || !Q.kw || Q.spec->kind != kConv3x3 || Q.blob.nkc != 8 || Q.spec->in_stride != 1 || Q.resid >= 0 || shifted ||
-                            c->tensors[Q.dst].is_f32 || Q.src != prev_dst || Q.args.Hs != a.Hs || Q.args.Ws != a.Ws || Q.args.ncg != a.ncg ||
-                            conv_kwave_chain_blocks(a.Hs, a.Ws, a.N, a.ncg, Q.args.dy[8]) != blocks)
-                            break;
-                        KwChainLayer& y = ch.layer[ch.nlayers++];
-                        y.in = c->tensors[Q.src].ptr; y.out = c->tensors[Q.dst].ptr;
-                        y.wgt = c->d_blob + Q.blob.w_off;
-                        y.bias = (const float*)(c->d_blob + Q.blob.bias_off);
-                        y.bn_scale = Q.blob.bn_scale_off != (size_t)-1 ? (const float*)(c->d_blob + Q.blob.bn_scale_off) : nullptr;
-                        y.bn_shift = Q.blob.bn_shift_off != (size_t)-1 ? (const float*)(c->d_blob + Q.blob.bn_shift_off) : nullptr;
-                        y.act = Q.spec->act; y.d = Q.args.dy[8];
-                        prev_dst = Q.dst; last = j;
-                    }
-                    if (ch.nlayers >= 2 && blocks > 0) {
-                        if (c->kw_chain_fits < 0) c->kw_chain_fits = conv_kwave_chain_capacity(c->device);
-                        if (c->kw_chain_fits >= blocks) {
-                            if (blocks != c->kw_bar_blocks) {      // counters hold (barriers so far) x (arrivals per barrier of THIS grid)
-                                HIPCHK(c, hipMemsetAsync(c->d_kw_bar, 0, 1024, s));
-                                c->kw_bar_count = 0; c->kw_bar_blocks = blocks;
-                            }
-                            ch.bar = c->d_kw_bar; ch.bar_base = c->kw_bar_count; ch.abort_flag = c->h_kw_abort;
-                            // test hook (tests/test_round5_gpu.py): IDC_KW_FORCE_ABORT=1 makes the first grid barrier unreachable and the give-up
-                            // counter tiny, i.e. it plays "the workgroups never become co-resident" on a healthy device
-                            if (g_kw_force_abort) { ch.bar_base += 1000; ch.spin_limit = 20u; }
-                            static const bool want_stamps = idc_env_int("IDC_KW_STAMPS", 0) != 0;
-                            if (want_stamps && !c->d_kw_stamps) HIPCHK(c, hipMalloc((void**)&c->d_kw_stamps, (size_t)4096 * kKwChainMax * 8 * 8));
-                            ch.stamps = (want_stamps && blocks <= 4096) ? c->d_kw_stamps : nullptr;
-                            c->kw_stamp_layers = ch.nlayers; c->kw_stamp_blocks = blocks;
-                            const hipError_t ce = launch_conv_kwave_chain(ch, blocks, g_kwave_chain, s);
-                            if (ce == hipSuccess) {
-                                c->kw_bar_count += (unsigned long long)(ch.nlayers - 1);
-                                L.chain_len = ch.nlayers;
-                                for (int j = li_ + 1; j <= last; ++j) c->layers[j].chained_into = li_;
-                                chain_until = last;
-                                le = hipSuccess;
-                            } else {
-                                (void)hipGetLastError();          // refused (e.g. hipErrorCooperativeLaunchTooLarge): one launch per layer from now on
-                                c->kw_chain_off = true;
-                            }
-                        }                                          // (else: more workgroups than the chip holds at once -- this launch goes layer by layer)
-                    }
-                }
-                if (le != hipSuccess) le = launch_conv_kwave(a, s);
-                HIPCHK(c, le);
+            const hipError_t le = chained ? hipSuccess : launch_kernel(L.kernel, L, a, s);
+            if (le == hipErrorInvalidConfiguration) {
+                char k[64]; kernel_label(L, c->precision, k, sizeof(k));
+                return fail(&c->err, IDC_ERR_INTERNAL, "layer %s: %s planned for a launch it does not cover%s", L.spec->name, k,
+                            kAbPartners ? "" : " (the default library has no conv_igemm_v2 / conv_ds_fused / conv1_1_bf16_kernel: -DIDC_AB_PARTNERS)");
             }
-            if (!kAbPartners && le == hipErrorInvalidConfiguration && !L.split && !L.click && L.v2 && !L.m16)
-                return fail(&c->err, IDC_ERR_INTERNAL, "layer %s: planned on the large tile but no 16x16x32 kernel covers this launch (default library: no "
-                            "conv_igemm_v2 / conv_ds_fused; build with -DIDC_AB_PARTNERS)", L.spec->name);
-            if (le == hipErrorInvalidConfiguration)
-                le = L.split ? (L.v2p ? launch_conv_v2ps(L.cfg, L.halo, a, s) : launch_conv_v2s(L.cfg, L.halo, a, s))
-                   : L.click ? launch_conv_click(L.lprec, L.cfg.wp, L.halo, a, s)
-                   : L.v2 ? (L.v2p ? launch_conv_v2p(L.cfg, L.halo, a, s) : L.m16 ? launch_conv_v2m(L.cfg, L.halo, a, s) : launch_conv_v2(L.cfg, L.halo, a, s))
-                          : launch_conv(L.lprec, L.cfg, L.halo, a, s);
             HIPCHK(c, le);
-        }
-        if (a.ksplit > 1) HIPCHK(c, launch_splitk_epilogue(L.lprec, a, s));
+            if (a.ksplit > 1) HIPCHK(c, launch_splitk_epilogue(L.lprec, a, s));
         }
         toc();
     }
@@ -2356,7 +2413,7 @@ int idc_layer_info_get(idc_handle h, int layer, idc_layer_info* out) {
     } else if (layer <= nl) {
         const Layer& L = h->layers[layer - 1];
         snprintf(out->name, sizeof(out->name), "%s", L.spec->name);
-        if (L.skip) {                        // its MACs and bytes are accounted to the launch that runs them
+        if (L.kernel == kFused) {            // its MACs and bytes are accounted to the launch that runs them
             for (const Layer& C : h->layers)
                 if (C.fused_short == layer - 1 || C.fused_next == layer - 1) snprintf(out->kernel, sizeof(out->kernel), "fused into %s", C.spec->name);
             out->flops = 0; out->min_bytes = 0; out->launches = 0;
@@ -2367,38 +2424,15 @@ int idc_layer_info_get(idc_handle h, int layer, idc_layer_info* out) {
             snprintf(out->kernel, sizeof(out->kernel), "conv_kwave_chain_bf16 x%d", L.chain_len);
             out->flops = L.flops; out->min_bytes = L.min_bytes; out->launches = 1;
         } else {
-            snprintf(out->kernel, sizeof(out->kernel), L.kw ? (L.spec->kind == kDeconv4x4 ? "conv_kwave_deconv_bf16" : "conv_kwave_bf16") : L.wino ? (L.spec->kind == kDeconv4x4 ? "conv_wino_deconv_f32" : "conv_wino_f32") : L.click ? (L.lprec == IDC_BF16 ? "conv_click<bf16,%d,%d>" : "conv_click<f32,%d,%d>")
-                     : L.v2 ? "conv_igemm_v2<%d,%d>" : (L.lprec == IDC_BF16 ? "conv_igemm<bf16,%d,%d>" : "conv_igemm<f32,%d,%d>"),
-                     L.cfg.wm, L.cfg.wp);
-            if (L.split) snprintf(out->kernel, sizeof(out->kernel), split_is_f16(h->precision) ? (L.v2p ? "conv_igemm_v2psh<%d,%d>x%d" : "conv_igemm_v2sh<%d,%d>x%d")
-                                                                                                    : (L.v2p ? "conv_igemm_v2ps<%d,%d>x%d" : "conv_igemm_v2s<%d,%d>x%d"),
-                                  L.cfg.wm, L.cfg.wp, split_segments(h->precision));
-            else if (L.m16) strncat(out->kernel, L.v2p ? "+m16p" : "+m16", sizeof(out->kernel) - strlen(out->kernel) - 1);
-            if (L.split && L.f16fast) snprintf(out->kernel, sizeof(out->kernel), "conv_igemm_v2ph<%d,%d>", L.cfg.wm, L.cfg.wp);
-            if (is_split(h->precision) && !L.split && L.spec->kind == kConvIm2col && g_conv1_1_split && !h->tensors[L.dst].is_f32 &&
-                (long long)((h->W + 31) / 32) * ((h->H + 15) / 16) * h->max_batch >= 128)
-                snprintf(out->kernel, sizeof(out->kernel), "conv1_1_split_kernel");
-            if (L.split && L.fused_short < 0 && g_conv1_2_split && conv1_2_split_layer(*L.spec) && !h->tensors[L.dst].is_f32 &&
-                (long long)((h->W + 31) / 32) * ((h->H + 11) / 12) * h->max_batch >= 256)
-                snprintf(out->kernel, sizeof(out->kernel), "conv1_2_split_kernel x%d", split_segments(h->precision));
-            if (L.fused_head) strncat(out->kernel, "+head", sizeof(out->kernel) - strlen(out->kernel) - 1);
-            if (L.args.ksplit > 1) {
-                char sk[16]; snprintf(sk, sizeof(sk), " splitK%d", L.args.ksplit);
-                strncat(out->kernel, sk, sizeof(out->kernel) - strlen(out->kernel) - 1);
-            }
+            kernel_label(L, h->precision, out->kernel, sizeof(out->kernel));
             out->flops = L.flops; out->min_bytes = L.min_bytes; out->launches = 1;
             if (L.fused_next >= 0) {
                 const Layer& P = h->layers[L.fused_next];
-                snprintf(out->kernel, sizeof(out->kernel), "conv1_block_fused");
                 out->flops += P.flops;
                 out->min_bytes += P.min_bytes - 2.0 * (double)h->tensors[L.dst].H * h->tensors[L.dst].W * h->tensors[L.dst].Cpad * eb;
             }
             if (L.fused_short >= 0) {
                 const Layer& P = h->layers[L.fused_short];
-                // the name rocprofv3 shows for this launch (the deconv and its 3x3 shortcut conv in one K loop)
-                if (L.split && L.f16fast) snprintf(out->kernel, sizeof(out->kernel), "conv_ds_fused_mh+shortcut");
-                else if (L.split) snprintf(out->kernel, sizeof(out->kernel), split_is_f16(h->precision) ? "conv_ds_fused_msh+shortcut x%d" : "conv_ds_fused_ms+shortcut x%d", L.args.nseg);
-                else snprintf(out->kernel, sizeof(out->kernel), L.m16 ? "conv_ds_fused_m+shortcut" : "conv_ds_fused+shortcut");
                 out->flops += P.flops;
                 // (the shortcut sums are neither written nor read: fp32 in the operand-split graph, bf16 otherwise)
                 out->min_bytes += P.min_bytes - 2.0 * (double)h->tensors[P.dst].H * h->tensors[P.dst].W * h->tensors[P.dst].Cpad * (h->tensors[P.dst].is_f32 ? 4 : eb);
@@ -2543,8 +2577,7 @@ static int run_single_op(int device_id, int precision, LayerSpec spec, int n, in
     const bool wino_ok = !split && ((wino_eligible(spec) && spec.cin % kc == 0 && resid == nullptr) || wino_dc);
     L.blob.w3_off = wino_ok ? 0 : (size_t)-1;
     L.blob.w3_bytes = wino_ok ? (size_t)spec.cin * cpad * (wino_dc ? 36 : 16) * eb : 0;
-    if (wino_ok && L.blob.w3_bytes > L.blob.w_bytes) L.blob.w_bytes = L.blob.w3_bytes;      // one staging buffer serves either image
-    std::vector<uint8_t> wimg(L.blob.w_bytes * parts);
+    const size_t wimg_bytes = std::max(L.blob.w_bytes * parts, L.blob.w3_bytes);             // one staging buffer serves either image
     L.lprec = precision; L.split = split;
     const int Hs = h / spec.in_stride, Ws = w / spec.in_stride;
     const int so = spec.kind == kDeconv4x4 ? 2 : 1;
@@ -2552,17 +2585,8 @@ static int run_single_op(int device_id, int precision, LayerSpec spec, int n, in
     fill_taps(L);
     // (default library: the large tile only where conv_igemm_v2m / v2p cover the launch -- no shortcut sum, no LeakyReLU without the fused head)
     set_geometry(L, precision, n, n, Hs, Ws, kAbPartners || is_split(precision) || (resid == nullptr && spec.act != 2));
-    int op_wexp = 0;
-    if (L.wino && wino_dc) pack_wino_deconv_weights(wimg.data(), precision, spec, L.blob, weight);
-    else if (L.wino) pack_wino_weights(wimg.data(), precision, spec, L.blob, weight);
-    else {
-        if (wino_ok) L.blob.w_bytes = (size_t)weight_taps(spec.kind) * L.blob.nkc * L.blob.ncg * kWBlockBytes;
-        L.m16 = split || (L.v2 && g_mfma16 && resid == nullptr && spec.act != 2);       // as in the network: conv_igemm_v2m where it applies
-        const size_t wcount = (size_t)spec.cin * spec.cout * (spec.kind == kDeconv4x4 ? 16 : spec.kind == kConv1x1 ? 1 : 9);
-        op_wexp = (split_is_f16(precision) && parts > 1) ? f16_weight_exponent(weight, wcount) : 0;      // as the blob packer does per layer
-        for (int part = 0; part < parts; ++part)
-            pack_layer_weights(wimg.data() + (size_t)part * L.blob.w_bytes, precision, (L.v2 && !L.m16) ? 2 : 1, spec, L.blob, weight, part, ldexpf(1.f, op_wexp));
-    }
+    const size_t wcount = (size_t)spec.cin * spec.cout * (spec.kind == kDeconv4x4 ? 16 : spec.kind == kConv1x1 ? 1 : 9);
+    const int op_wexp = (split_is_f16(precision) && parts > 1) ? f16_weight_exponent(weight, wcount) : 0;      // as the blob packer does per layer
     std::vector<float> hb(cpad, 0.f), hs(cpad, 1.f), ht(cpad, 0.f);
     for (int c = 0; c < spec.cout; ++c) {
         hb[c] = bias[c];
@@ -2572,12 +2596,11 @@ static int run_single_op(int device_id, int precision, LayerSpec spec, int n, in
     const size_t xin = (size_t)n * spec.cin * h * w, yout = (size_t)n * spec.cout * Ho * Wo;
     HIPCHK(nullctx, d_x.alloc(xin * 4));
     HIPCHK(nullctx, d_xn.alloc(xin * eb * parts));
-    HIPCHK(nullctx, d_w.alloc(L.blob.w_bytes * parts));
+    HIPCHK(nullctx, d_w.alloc(wimg_bytes));
     HIPCHK(nullctx, d_b.alloc(cpad * 4)); HIPCHK(nullctx, d_s.alloc(cpad * 4)); HIPCHK(nullctx, d_t.alloc(cpad * 4));
     HIPCHK(nullctx, d_yn.alloc((size_t)n * Ho * Wo * cpad * (split ? 2 * parts : 4)));
     HIPCHK(nullctx, d_y.alloc(yout * 4));
     HIPCHK(nullctx, hipMemcpy(d_x.p, x, xin * 4, hipMemcpyHostToDevice));
-    HIPCHK(nullctx, hipMemcpy(d_w.p, wimg.data(), L.blob.w_bytes * parts, hipMemcpyHostToDevice));
     HIPCHK(nullctx, hipMemcpy(d_b.p, hb.data(), cpad * 4, hipMemcpyHostToDevice));
     HIPCHK(nullctx, hipMemcpy(d_s.p, hs.data(), cpad * 4, hipMemcpyHostToDevice));
     HIPCHK(nullctx, hipMemcpy(d_t.p, ht.data(), cpad * 4, hipMemcpyHostToDevice));
@@ -2621,18 +2644,21 @@ static int run_single_op(int device_id, int precision, LayerSpec spec, int n, in
     HIPCHK(nullctx, d_zero.alloc(256));
     HIPCHK(nullctx, hipMemset(d_zero.p, 0, 256));
     a.zeros = d_zero.p;
-    if (L.wino && !conv_wino_applies(precision, a, wino_dc))
-        return fail(nullptr, IDC_ERR_INTERNAL, "single op: Winograd variant selected for a launch it does not cover");
-    if (split && (!L.v2 || !conv_v2s_applies(a)))
-        return fail(nullptr, IDC_ERR_INTERNAL, "single op: no operand-split kernel covers this launch");
-    if (!split && L.m16 && !conv_v2m_applies(a))
-        return fail(nullptr, IDC_ERR_INTERNAL, "single op: conv_igemm_v2m selected for a launch it does not cover");
-    L.v2p = split ? (g_v2p && conv_v2ps_applies(L.cfg, L.halo, a)) : (L.m16 && g_v2p && conv_v2p_applies(L.cfg, L.halo, a));
-    if (L.kw && !conv_kwave_applies(a))
-        return fail(nullptr, IDC_ERR_INTERNAL, "single op: conv_kwave_bf16 selected for a launch it does not cover");
-    HIPCHK(nullctx, split ? (L.v2p ? launch_conv_v2ps(L.cfg, L.halo, a, nullptr) : launch_conv_v2s(L.cfg, L.halo, a, nullptr)) : L.kw ? launch_conv_kwave(a, nullptr) : L.wino ? (wino_dc ? launch_deconv_wino(precision, a, nullptr) : launch_conv_wino(precision, a, nullptr)) : L.click ? launch_conv_click(precision, L.cfg.wp, L.halo, a, nullptr)
-                    : L.v2 ? (L.v2p ? launch_conv_v2p(L.cfg, L.halo, a, nullptr) : L.m16 ? launch_conv_v2m(L.cfg, L.halo, a, nullptr) : launch_conv_v2(L.cfg, L.halo, a, nullptr))
-                           : launch_conv(precision, L.cfg, L.halo, a, nullptr));
+    // the kernel the network launches for this layer at batch n, and the weight image it reads
+    L.kernel = choose_kernel(L, precision, n);
+    std::vector<uint8_t> wimg(wimg_bytes);
+    if (L.kernel == kDeconvWino) pack_wino_deconv_weights(wimg.data(), precision, spec, L.blob, weight);
+    else if (L.kernel == kConvWino) pack_wino_weights(wimg.data(), precision, spec, L.blob, weight);
+    else
+        for (int part = 0; part < parts; ++part)
+            pack_layer_weights(wimg.data() + (size_t)part * L.blob.w_bytes, precision, L.kernel == kConvV2 ? 2 : 1, spec, L.blob, weight, part, ldexpf(1.f, op_wexp));
+    HIPCHK(nullctx, hipMemcpy(d_w.p, wimg.data(), wimg_bytes, hipMemcpyHostToDevice));
+    const hipError_t le = launch_kernel(L.kernel, L, a, nullptr);
+    if (le == hipErrorInvalidConfiguration) {
+        char k[64]; kernel_label(L, precision, k, sizeof(k));
+        return fail(nullptr, IDC_ERR_INTERNAL, "single op: %s planned for a launch it does not cover", k);
+    }
+    HIPCHK(nullctx, le);
     if (a.ksplit > 1) HIPCHK(nullctx, launch_splitk_epilogue(precision, a, nullptr));
     if (split) HIPCHK(nullctx, launch_split_to_nchw(d_yn.p, (float*)d_y.p, n, spec.cout, Ho, Wo, cpad, parts, split_is_f16(precision) ? 1 : 0, nullptr));
     else HIPCHK(nullctx, launch_nhwc_to_nchw(io_bf16, d_yn.p, (float*)d_y.p, n, spec.cout, Ho, Wo, cpad, nullptr));

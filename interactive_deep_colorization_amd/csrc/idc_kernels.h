@@ -140,18 +140,23 @@ hipError_t launch_conv_ds_m(const ConvArgs& a, hipStream_t s);
 // ... and its operand-split form (conv_ds_fused_ms / _msh: split tensors in and out, fp32 accumulation of both K loops, split epilogue)
 hipError_t launch_conv_ds_ms(const ConvArgs& a, hipStream_t s);
 bool conv_ds_m_fits(int Hs, int Ws, int nkc, int nkc2);   // (else conv_ds_fused, which addresses with 64-bit pointers)
+bool conv_ds_m_applies(const ConvArgs& a);
+bool conv_ds_ms_applies(const ConvArgs& a);
 hipError_t init_kernels_dsm();
 void set_ds_half(int v);              // 1 (default): grids with fewer 128-cout workgroups than CUs run the 64-cout, 4-wave form of conv_ds_fused_m
 // model1 = conv1_1 + conv1_2 of a 32x32 tile in one workgroup (conv1_block_fused): `a` = conv1_1's arguments with conv1_2's
 // riding in (wgt2 = its layout-1 weights, head_b = its bias, bn_scale/bn_shift, out = its output)
 hipError_t launch_conv1_block(const ConvArgs& a, hipStream_t s);
+bool conv1_block_applies(const ConvArgs& a);
 // conv1_1 as the exact-fp32 island of an operand-split handle (conv1_1_split_kernel: fp32 MFMA straight from the input patch, a.out_parts planes out)
 hipError_t launch_conv1_1_split(const ConvArgs& a, hipStream_t s);
+bool conv1_1_split_applies(const ConvArgs& a);
 // conv1_2 of an operand-split handle on conv1_block_fused_t's conv1_2 tile (conv1_2_split_kernel: 32 x 12 pixels, two workgroups per CU, segments over a static halo)
 hipError_t launch_conv1_2_split(const ConvArgs& a, hipStream_t s);
-// conv1_1 (4 -> 64, input pack fused) as one 32x32 tile per workgroup, bf16; hipErrorInvalidConfiguration if the
-// launch does not qualify (the caller then uses launch_conv)
+bool conv1_2_split_applies(const ConvArgs& a);
+// conv1_1 (4 -> 64, input pack fused) as one 32x32 tile per workgroup, bf16 (-DIDC_AB_PARTNERS build only: the default library's predicate is false)
 hipError_t launch_conv1_1_bf16(const ConvArgs& a, hipStream_t s);
+bool conv1_1_bf16_applies(const ConvArgs& a);
 // Batch-1 click-path kernel (conv_click): tile 16 x 4*wp sites x 64 couts, the workgroup's whole K slice (kc_per chunks x
 // all taps) requested by LDS-DMA at entry; a.kc_per <= conv_click_max_chunks(wp, halo, ntaps), a.ksplit = ceil(nkc / kc_per),
 // a.tiles_x / tiles_y count 16 x 4*wp tiles, a.zeros set.  Layout-1 weights.
