@@ -382,6 +382,49 @@ int idc_layer_times_stats(idc_handle h, float* ms_min, float* ms_median, float* 
 int idc_get_activation(idc_handle h, const char* name, int n, float* out, size_t capacity_floats,
                        int* C, int* H, int* W);
 
+/* ---- range audit: does this checkpoint fit the storage format of this precision? ----------- *
+ * The fp16 forms (IDC_FP16X3, IDC_FP16) clamp every stored activation to +-65504 and keep only a subnormal's absolute precision below 2^-14,
+ * silently.  While the audit is on, every forward (blocking, resident and device-pointer forms; the pipelined slots answer
+ * IDC_ERR_UNSUPPORTED) runs one streaming reduction over each layer's STORED output right after the layer's launch -- the values the next layer
+ * reads: scaled by 2^act_exp on a handle loaded with activation exponents, the sum of the parts for the operand-split forms -- and folds it
+ * into a per-layer record that is sticky across forwards (max of maxima, sums of counts) until the reset call.  The forward's results do not
+ * change by a bit.  The report call synchronises the stream; `layer` indexes the table of idc_layer_info_get.  Layers without a stored output
+ * of their own in the current plan (conv1_1 inside the fused conv1 block, a shortcut conv inside the fused deconv launch, conv10_2 when the
+ * head rides in its epilogue) and the non-conv rows report n_values = 0. */
+enum { IDC_STORE_NONE = 0, IDC_STORE_F32 = 1, IDC_STORE_BF16 = 2, IDC_STORE_F16 = 3 };
+typedef struct idc_range_info {
+    char name[32];           /* idc_layer_info.name */
+    int storage;             /* IDC_STORE_*: element type of the stored tensor */
+    int parts;               /* planes per pixel whose sum is the value (1; 2 / 3 for the operand-split precisions) */
+    int act_exp;             /* the stored tensor holds value * 2^act_exp (0 unless the weights were loaded with exponents) */
+    float max_abs;           /* over the finite stored values */
+    uint64_t n_values;       /* n * cout * h * w, summed over the audited forwards */
+    uint64_t n_saturated;    /* |value| >= 65504 in an fp16 storage form (0 for bf16 / fp32 storage) */
+    uint64_t n_tiny;         /* non-zero and |value| < 2^-14: the hi part itself would be subnormal in fp16 */
+    uint64_t n_nonfinite;    /* NaN / inf (not part of max_abs) */
+} idc_range_info;
+int idc_set_range_audit(idc_handle h, int on);
+int idc_range_reset(idc_handle h);
+int idc_range_report(idc_handle h, int layer, idc_range_info* out);
+
+/* ---- calibrated activation exponents (IDC_FP16X3) ------------------------------------------ *
+ * act_exp[i] (integer, |a| <= 24) belongs to the output of layer i of the layer table (n_layers = what idc_num_layers answers for these
+ * flags: the conv layers + 3; the non-conv rows are ignored): the tensor is stored as value * 2^a, so that a checkpoint whose activations
+ * leave fp16's range (or sink below its normals) keeps all 22 bits of the two parts.  The scale costs nothing at run time: it is folded,
+ * exactly (powers of two), into numbers the kernels read anyway -- the producer's BatchNorm scale / shift (layers without one: its bias and
+ * accumulator scale; the ReLU is positively homogeneous), and the consumer's accumulator scale 2^-(wexp + a[input]).  NULL or all zeros gives
+ * the blob of the plain call, byte for byte.  The packer resolves what the graph forces: a tensor has ONE exponent for all its consumers; the
+ * fp32 island (conv1_1), fp32 outputs and conv10_2 (read by the head in its own epilogue) stay at 0; a shortcut conv takes the exponent of the
+ * ConvTranspose it is summed into, and the two weight exponents of that pair are lowered until wexp + a[input] agree (one accumulator set, one
+ * accumulator scale; the fused launch refuses to run on a blob where they differ).  The exponents in effect travel in the blob header
+ * (header flag bit 0x100), idc_range_report returns them, and idc_get_activation returns UNSCALED values.
+ * Non-zero exponents are refused with IDC_ERR_UNSUPPORTED for every other precision, and with IDC_FLAG_DIST_HEAD, IDC_FLAG_DIST313 or
+ * IDC_FLAG_GLOBAL_HINTS (their heads / per-image shift read or add to tensors that would be scaled); n_layers that does not match is
+ * IDC_ERR_INVALID_ARG. */
+int idc_pack_weights_ex(int precision, unsigned flags, const idc_tensor_desc* tensors, int n_tensors, const int* act_exp, int n_layers,
+                        void* blob, size_t blob_bytes);
+int idc_load_weights_ex(idc_handle h, const idc_tensor_desc* tensors, int n_tensors, const int* act_exp, int n_layers);
+
 /* ---- single operators (parity tests drive the same kernels the network uses) --------------- *
  * x NCHW fp32 [n,cin,h,w]; w/b in torch layouts; optional post-activation affine (eval-BN):
  * y = act(conv(x)+b [+ resid]) * bn_scale + bn_shift.  act: 0 none, 1 ReLU, 2 LeakyReLU(0.2).

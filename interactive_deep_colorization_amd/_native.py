@@ -29,7 +29,9 @@ EXPORTED_SYMBOLS = [
     "idc_dist_bins", "idc_keep_dist", "idc_dist_at", "idc_get_dist", "idc_suggest_colors",
     "idc_stream_wait", "idc_stream_signal", "idc_alloc_host", "idc_free_host", "idc_forward_async", "idc_wait", "idc_pipeline_times",
     "idc_comm_unique_id", "idc_broadcast_weights", "idc_upsample_lab2rgb",
+    "idc_set_range_audit", "idc_range_reset", "idc_range_report", "idc_pack_weights_ex", "idc_load_weights_ex",
 ]
+IDC_STORE_NONE, IDC_STORE_F32, IDC_STORE_BF16, IDC_STORE_F16 = 0, 1, 2, 3
 IDC_INTERP_CUBIC, IDC_INTERP_LINEAR, IDC_INTERP_NEAREST = 0, 1, 2
 IDC_SRC_OUTPUT_AB, IDC_SRC_OUTPUT_AB_RAW, IDC_SRC_INPUT_AB = 0, 1, 2
 IDC_UNIQUE_ID_BYTES = 128
@@ -56,6 +58,13 @@ class Hint(ctypes.Structure):
 class LayerInfo(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 32), ("kernel", ctypes.c_char * 48), ("flops", ctypes.c_double),
                 ("min_bytes", ctypes.c_double), ("launches", ctypes.c_int)]
+
+
+class RangeInfo(ctypes.Structure):
+    """idc_range_info: one layer's sticky range-audit record."""
+    _fields_ = [("name", ctypes.c_char * 32), ("storage", ctypes.c_int), ("parts", ctypes.c_int), ("act_exp", ctypes.c_int),
+                ("max_abs", ctypes.c_float), ("n_values", ctypes.c_uint64), ("n_saturated", ctypes.c_uint64),
+                ("n_tiny", ctypes.c_uint64), ("n_nonfinite", ctypes.c_uint64)]
 
 
 _lib = None
@@ -139,6 +148,11 @@ def load():
     proto("idc_comm_unique_id", ci, [vp])
     proto("idc_broadcast_weights", ci, [vp, vp, ci, ci, ci])
     proto("idc_upsample_lab2rgb", ci, [vp, ci, ci, ci, ci, ci, vp, vp])
+    proto("idc_set_range_audit", ci, [vp, ci])
+    proto("idc_range_reset", ci, [vp])
+    proto("idc_range_report", ci, [vp, ci, ctypes.POINTER(RangeInfo)])
+    proto("idc_pack_weights_ex", ci, [ci, ctypes.c_uint, ctypes.POINTER(TensorDesc), ci, ctypes.POINTER(ci), ci, vp, csz])
+    proto("idc_load_weights_ex", ci, [vp, ctypes.POINTER(TensorDesc), ci, ctypes.POINTER(ci), ci])
     _lib = lib
     return lib
 

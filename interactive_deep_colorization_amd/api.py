@@ -28,6 +28,7 @@ from scipy.ndimage import zoom
 from . import color_bins, colorspace
 from .colorspace import lab2rgb_transpose, rgb2lab_transpose  # same helper names as the reference
 from ._native import IdcError
+from . import engine as _engine
 from .engine import HipColorizer
 from .workloads import put_point  # noqa: F401  notebook helper (DemoInteractiveColorization.ipynb:131-139)
 
@@ -160,6 +161,60 @@ class ColorizeImageBase(object):
         if old is not None and old is not net and hasattr(old, 'close'):
             old.close()
         self.net_set = True
+
+    # ------------------------------------------------------------------ range audit / calibration (not in the reference)
+    def check_ranges(self):
+        """Does this checkpoint fit the storage format of ``self.precision`` on this image?  Repeats the last forward's inputs (zero hints
+        if there was none) with the engine's range audit on and returns its report (``HipColorizer.range_report``: one dict per layer with
+        max_abs, n_saturated, n_tiny, ... of the STORED activations).  Layers that saturated (the fp16 forms clamp at +-65504, silently) are
+        named in one warning.  Run it once per checkpoint before trusting ``precision='fp16x3'`` / ``'fp16'``; ``net_forward`` itself
+        never pays for it."""
+        import warnings
+        if not self.img_l_set:
+            raise RuntimeError('I need to have an image!')
+        if not self.net_set:
+            raise RuntimeError('I need to have a net!')
+        X = self.Xd
+        ab = self.input_ab
+        mask = self.input_mask
+        ab_mc = np.zeros((2, X, X), np.float32) if ab is None else (np.asarray(ab, np.float32) - self.ab_mean) / self.ab_norm
+        mask_mult = np.zeros((1, X, X), np.float32) if mask is None else np.asarray(mask, np.float32) * self.mask_mult
+        self.net.set_range_audit(True)
+        try:
+            self.net.range_reset()
+            self.net.forward(self._img_l_mc_f32[None], ab_mc[None], mask_mult[None], getattr(self, 'mask_cent', 0))
+            report = self.net.range_report()
+        finally:
+            self.net.set_range_audit(False)
+        self._dev_out_valid = False               # the engine's resident maps are now this call's, not net_forward's
+        hot = [r['name'] for r in report if r['n_saturated'] > 0]
+        if hot:
+            warnings.warn("stored activations saturate at +-65504 in layer(s) %s with precision %r: the result is wrong without any error. "
+                          "Use precision='bf16x6', or for 'fp16x3' prep_net(..., calibrate=True) / calibrate=(L_mc, ab, mask) to load the "
+                          "weights with calibrated activation exponents." % (', '.join(hot), getattr(self, 'precision', None)), RuntimeWarning)
+        return report
+
+    def _calibrated_exponents(self, sd, calibrate, device, io_scales=None):
+        """``prep_net``'s ``calibrate`` argument -> activation exponents for ``load_state_dict`` (None = the plain load).  ``True`` = this
+        object's current image with zero hints; a tuple ``(L_mc, ab, mask)`` = arrays as ``net_forward`` takes them ((n,C,X,X) or (C,X,X):
+        L - 50, raw ab, 0/1 mask), ideally several images."""
+        if calibrate is None or calibrate is False:
+            return None
+        if _engine._PREC[self.precision] != _engine._PREC['fp16x3']:
+            raise ValueError("calibrate= applies to precision='fp16x3' only (this object has %r)" % (self.precision,))
+        if calibrate is True:
+            if not self.img_l_set:
+                raise RuntimeError('calibrate=True needs an image: call load_image / set_image first')
+            L = self._img_l_mc_f32[None]
+            ab = np.zeros((1, 2) + L.shape[2:], np.float32)
+            mask = np.zeros((1, 1) + L.shape[2:], np.float32)
+        else:
+            L, ab, mask = (np.asarray(a, np.float32) for a in calibrate)
+            if L.ndim == 3:
+                L, ab, mask = L[None], ab[None], mask[None]
+        ab = (ab - self.ab_mean) / self.ab_norm
+        mask = mask * self.mask_mult
+        return _engine.calibrate_activation_exponents(sd, L, ab, mask, getattr(self, 'mask_cent', 0), device=device, io_scales=io_scales)
 
     # input_ab / input_mask: plain attributes after net_forward; after net_forward_hints they are read back from the
     # device planes only when something (get_input_img, get_sup_img, ...) asks for them
@@ -461,15 +516,21 @@ class ColorizeImageTorch(ColorizeImageBase):
         self.precision = precision
         self.pts_in_hull = _grid_529()
 
-    def prep_net(self, gpu_id=None, path='', dist=False, state_dict=None):
+    def prep_net(self, gpu_id=None, path='', dist=False, state_dict=None, calibrate=None):
         """``gpu_id=None`` selects device 0 (the reference's torch backend stayed on the CPU:
-        ``ideepcolor.py:68-72``).  ``state_dict`` may replace ``path``."""
+        ``ideepcolor.py:68-72``).  ``state_dict`` may replace ``path``.  ``calibrate`` (not in the reference; ``precision='fp16x3'`` only):
+        ``True`` or an ``(L_mc, ab, mask)`` tuple loads the weights with activation exponents calibrated on that input, so that a checkpoint
+        whose activations leave fp16's range still fits (``check_ranges`` tells); ``None`` = the plain load."""
         print('path = %s' % path)
         print('Model set! dist mode? ', dist)
         sd = read_state_dict(path) if state_dict is None else state_dict
-        net = HipColorizer(H=self.Xd, W=self.Xd, max_batch=1, precision=self.precision,
-                           device=0 if gpu_id is None else int(gpu_id), dist=dist)
-        net.load_state_dict(sd)
+        device = 0 if gpu_id is None else int(gpu_id)
+        act_exp = self._calibrated_exponents(sd, calibrate, device)
+        net = HipColorizer(H=self.Xd, W=self.Xd, max_batch=1, precision=self.precision, device=device, dist=dist)
+        if act_exp is None:
+            net.load_state_dict(sd)
+        else:
+            net.load_state_dict(sd, act_exp=act_exp)
         self._new_engine(net)
 
     def net_forward(self, input_ab, input_mask):
@@ -599,17 +660,24 @@ class ColorizeImageCaffe(ColorizeImageBase):
     _global_hints = False
     _dist313 = False
 
-    def prep_net(self, gpu_id, prototxt_path='', caffemodel_path='', state_dict=None):
+    def prep_net(self, gpu_id, prototxt_path='', caffemodel_path='', state_dict=None, calibrate=None):
+        """``calibrate``: as ``ColorizeImageTorch.prep_net`` (``precision='fp16x3'``; the plain regression net only -- the engine refuses
+        activation exponents on the global-hints and 313-bin graphs)."""
         print('gpu_id = %d, net_path = %s, model_path = %s' % (gpu_id, prototxt_path, caffemodel_path))
         if gpu_id == -1:
             raise RuntimeError('cpu mode is not available: this backend runs on gfx950 only')
         sd, out_mul = read_caffe_weights(caffemodel_path, state_dict, net="global" if self._global_hints else ("nopred" if self._dist313 else "nodist"))
         out_mul = self.__dict__.pop('_file_out_mul', out_mul)      # (a subclass that already read the file passes what it found)
         self.gpu_id = gpu_id
+        io_scales = dict(l_div=1., ab_div=1., mask_mul=1., out_mul=out_mul)
+        act_exp = self._calibrated_exponents(sd, calibrate, int(gpu_id), io_scales)
         net = HipColorizer(H=self.Xd, W=self.Xd, max_batch=1, precision=self.precision, device=int(gpu_id),
                            global_hints=self._global_hints, dist313=self._dist313)
-        net.set_io_scales(l_div=1., ab_div=1., mask_mul=1., out_mul=out_mul)
-        net.load_state_dict(sd)
+        net.set_io_scales(**io_scales)
+        if act_exp is None:
+            net.load_state_dict(sd)
+        else:
+            net.load_state_dict(sd, act_exp=act_exp)
         self._new_engine(net)
 
     def net_forward(self, input_ab, input_mask):

@@ -290,11 +290,58 @@ static void run_pack_tasks(std::vector<std::function<void()>>& t) {
     t.clear();
 }
 
+// Activation exponents (idc_pack_weights_ex): what the caller asked for, resolved into what the graph can carry.  a_out[li]: active layer li's output is
+// stored as value * 2^a_out; a_in[li]: the exponent of the tensor it reads.  Forced to 0: the fp32 island, fp32 outputs and conv10_2 (the head reads it
+// unscaled in its own epilogue).  A shortcut conv takes the exponent of the ConvTranspose it is summed into (fused: one accumulator set; unfused: its fp32
+// sums join the deconv's accumulators before the activation).
+static int resolve_act_exp(const BlobPlan& plan, int precision, unsigned flags, const int* act_exp, int n_layers, std::vector<int>* a_out,
+                           std::vector<int>* a_in, std::string* err) {
+    const auto& specs = layer_specs();
+    const size_t nl = plan.active.size();
+    a_out->assign(nl, 0); a_in->assign(nl, 0);
+    if (!act_exp) return IDC_OK;
+    if (n_layers != (int)nl + 3)
+        return fail(err, IDC_ERR_INVALID_ARG, "act_exp: n_layers %d, but the layer table of these flags has %d rows", n_layers, (int)nl + 3);
+    bool any = false;
+    for (size_t li = 0; li < nl; ++li) {
+        const int a = act_exp[li + 1];
+        if (a < -kActExpMax || a > kActExpMax) return fail(err, IDC_ERR_INVALID_ARG, "act_exp[%d] = %d outside +-%d", (int)li + 1, a, kActExpMax);
+        any = any || a != 0;
+    }
+    if (!any) return IDC_OK;
+    if (precision != IDC_FP16X3)
+        return fail(err, IDC_ERR_UNSUPPORTED, "non-zero activation exponents need precision IDC_FP16X3 (got %d): the other precisions carry no accumulator scale", precision);
+    if (flags & (IDC_FLAG_DIST_HEAD | IDC_FLAG_DIST313 | IDC_FLAG_GLOBAL_HINTS))
+        return fail(err, IDC_ERR_UNSUPPORTED, "non-zero activation exponents are not supported with %s: it reads or adds to tensors that would be scaled",
+                    (flags & IDC_FLAG_DIST_HEAD) ? "IDC_FLAG_DIST_HEAD" : (flags & IDC_FLAG_DIST313) ? "IDC_FLAG_DIST313" : "IDC_FLAG_GLOBAL_HINTS");
+    if (nl > sizeof(((BlobHeader*)nullptr)->pad)) return fail(err, IDC_ERR_INTERNAL, "act_exp: %d layers do not fit the blob header", (int)nl);
+    auto find = [&](const char* name) { for (size_t lj = 0; lj < nl; ++lj) if (strcmp(specs[plan.active[lj]].name, name) == 0) return (int)lj; return -1; };
+    for (size_t li = 0; li < nl; ++li) {
+        const LayerSpec& s = specs[plan.active[li]];
+        (*a_out)[li] = (plan.layers[li].f32 || s.out_f32 || strcmp(s.name, "conv10_2") == 0) ? 0 : act_exp[li + 1];
+    }
+    for (size_t li = 0; li < nl; ++li) {
+        const LayerSpec& s = specs[plan.active[li]];
+        const int lj = s.resid ? find(s.resid) : -1;
+        if (lj >= 0) (*a_out)[lj] = (*a_out)[li];
+    }
+    for (size_t li = 0; li < nl; ++li) {
+        const int lj = find(specs[plan.active[li]].src);
+        (*a_in)[li] = lj >= 0 ? (*a_out)[lj] : 0;
+    }
+    return IDC_OK;
+}
+
 static int pack_weights_impl(int precision, unsigned flags, const idc_tensor_desc* tensors, int n_tensors,
-                             void* blob, size_t blob_bytes, std::string* err) {
+                             void* blob, size_t blob_bytes, std::string* err, const int* act_exp = nullptr, int n_layers = 0) {
     if (precision < IDC_FP32 || precision > IDC_FP16) return fail(err, IDC_ERR_INVALID_ARG, "bad precision %d", precision);
     if (!tensors || n_tensors <= 0 || !blob) return fail(err, IDC_ERR_INVALID_ARG, "null tensors/blob");
     const BlobPlan plan = make_blob_plan(precision, flags);
+    std::vector<int> a_out, a_in;
+    {
+        const int arc = resolve_act_exp(plan, precision, flags, act_exp, n_layers, &a_out, &a_in, err);
+        if (arc) return arc;
+    }
     if (blob_bytes < plan.total_bytes)
         return fail(err, IDC_ERR_INVALID_ARG, "blob too small: %zu < %zu", blob_bytes, plan.total_bytes);
     std::map<std::string, TensorView> sd;
@@ -333,8 +380,11 @@ static int pack_weights_impl(int precision, unsigned flags, const idc_tensor_des
             const LayerSpec& s = specs[plan.active[li]];
             if (!s.resid) continue;
             for (size_t lj = 0; lj < plan.active.size(); ++lj)
-                if (strcmp(specs[plan.active[lj]].name, s.resid) == 0 && !plan.layers[lj].f32 && !plan.layers[li].f32)
-                    wexp[li] = wexp[lj] = std::min(wexp[li], wexp[lj]);
+                if (strcmp(specs[plan.active[lj]].name, s.resid) == 0 && !plan.layers[lj].f32 && !plan.layers[li].f32) {
+                    // ONE accumulator scale 2^-(wexp + a_in) for both K loops: the larger side's weight exponent comes down (a_in = 0: the smaller wexp for both)
+                    const int t = std::min(wexp[li] + a_in[li], wexp[lj] + a_in[lj]);
+                    wexp[li] = t - a_in[li]; wexp[lj] = t - a_in[lj];
+                }
         }
     }
     for (size_t li = 0; li < plan.active.size(); ++li) {
@@ -354,7 +404,10 @@ static int pack_weights_impl(int precision, unsigned flags, const idc_tensor_des
         // the weight images are independent of each other: queued here, packed by the worker threads below (round 6: 1.4 s -> 0.2 s for a bf16 blob)
         const LayerSpec* sp = &s; const LayerBlob* lbp = &lb; const float* wd = w->data;
         const float wmul = ldexpf(1.f, wexp[li]);
-        if (lb.wscale_off != (size_t)-1) *(float*)(base + lb.wscale_off) = ldexpf(1.f, -wexp[li]);
+        // the accumulators come back from weights * 2^wexp and inputs * 2^a_in; a layer without BatchNorm also puts its own output exponent here and on its
+        // bias (act(x) 2^a = act(x 2^a): ReLU / LeakyReLU / none are positively homogeneous), a layer with one on the BatchNorm scale and shift below
+        const int a_epi = s.bnkey ? 0 : a_out[li];
+        if (lb.wscale_off != (size_t)-1) *(float*)(base + lb.wscale_off) = ldexpf(1.f, a_epi - wexp[li] - a_in[li]);
         for (int part = 0; part < lb.parts; ++part)
             tasks.push_back([=]() { pack_layer_weights(base + lbp->w_off + (size_t)part * lbp->w_bytes, lprec, 1, *sp, *lbp, wd, part, wmul); });
         if (precision == IDC_FP16 && s.kind == kConvIm2col && lb.w2_off != (size_t)-1) {
@@ -366,7 +419,7 @@ static int pack_weights_impl(int precision, unsigned flags, const idc_tensor_des
             else tasks.push_back([=]() { pack_wino_weights(base + lbp->w3_off, lprec, *sp, *lbp, wd); });
         }
         float* bias = (float*)(base + lb.bias_off);
-        for (int c = 0; c < s.cout; ++c) bias[c] = b->data[c];
+        for (int c = 0; c < s.cout; ++c) bias[c] = a_epi ? ldexpf(b->data[c], a_epi) : b->data[c];
         if (s.bnkey) {
             const TensorView *g = nullptr, *be = nullptr, *mu = nullptr, *var = nullptr;
             const std::string p = s.bnkey;
@@ -382,6 +435,7 @@ static int pack_weights_impl(int precision, unsigned flags, const idc_tensor_des
                 const double sd_ = (double)g->data[c] / sqrt((double)var->data[c] + 1e-5);
                 sc[c] = (float)sd_;
                 sh[c] = (float)((double)be->data[c] - (double)mu->data[c] * sd_);
+                if (a_out[li]) { sc[c] = ldexpf(sc[c], a_out[li]); sh[c] = ldexpf(sh[c], a_out[li]); }      // (after the rounding to fp32: exact)
             }
         }
     }
@@ -463,6 +517,8 @@ static int pack_weights_impl(int precision, unsigned flags, const idc_tensor_des
     BlobHeader h;
     memset(&h, 0, sizeof(h));
     h.magic = kBlobMagic; h.version = IDC_VERSION; h.precision = (uint32_t)precision; h.flags = plan.flags;
+    for (size_t li = 0; li < a_out.size(); ++li)
+        if (a_out[li] != 0) { h.flags |= kBlobFlagActExp; h.pad[li] = (uint8_t)(int8_t)a_out[li]; }
     h.total_bytes = plan.total_bytes;
     h.checksum = fnv1a(base + sizeof(BlobHeader), plan.total_bytes - sizeof(BlobHeader));
     memcpy(base, &h, sizeof(h));
@@ -575,6 +631,13 @@ struct idc_context {
     int n_timed = 0;
     long long prof_count = 0;            // forwards recorded since profiling was switched on
     int last_n = 0;
+    // range audit (idc_set_range_audit): one sticky AuditRecord per row of the layer table in device memory, the value counts on the host
+    bool audit = false;
+    AuditRecord* d_audit = nullptr;
+    std::vector<unsigned long long> audit_values;
+    // from the blob in use (cache_blob_meta): the activation exponent of each active layer's output and its accumulator-scale word
+    std::vector<int> act_exp;
+    std::vector<float> wscale;
 };
 
 #define HIPCHK(ctx, expr)                                                                                  \
@@ -1132,6 +1195,14 @@ static int run_graph(idc_context* c, int n, const float* dL, const float* dab, c
     const size_t ring = (size_t)(c->prof_count % kProfRing) * c->n_timed * 2;
     auto tic = [&]() { if (c->profiling == 1) (void)hipEventRecord(c->ev[ring + step * 2], s); };
     auto toc = [&]() { if (c->profiling == 1) (void)hipEventRecord(c->ev[ring + step * 2 + 1], s); ++step; };
+    // range audit: the stored output of layer index lj, folded into its record right behind the launch that wrote it (outside the event pairs)
+    auto audit_layer = [&](int lj) -> hipError_t {
+        const Layer& Q = c->layers[lj];
+        const Tensor& t = c->tensors[Q.dst];
+        const int parts = t.is_f32 ? 0 : t.parts;
+        c->audit_values[lj + 1] += (unsigned long long)n * t.C * t.H * t.W;
+        return launch_range_audit(t.ptr, (long long)n * t.H * t.W, t.C, t.Cpad, parts, split_is_f16(c->precision) ? 1 : 0, c->d_audit + lj + 1, s);
+    };
     if (c->profiling == 2) (void)hipEventRecord(c->ev[ring], s);          // whole-forward pair: slot 0
     tic();   // (slot 0: the input pack is fused into conv1_1's operand staging; only the global-hints branch runs here)
     if (c->flags & IDC_FLAG_GLOBAL_HINTS)      // four GEMVs per image; its output is consumed by conv4_3's epilogue
@@ -1182,6 +1253,11 @@ static int run_graph(idc_context* c, int n, const float* dL, const float* dab, c
                     ps.cout == L.spec->cout && pin.H == to.H && pin.W == to.W && !pin.is_f32 && pin.parts == to.parts &&
                     c->tensors[L.src].parts == to.parts && !c->tensors[L.src].is_f32 &&
                     conv_ds_m_fits(L.args.Hs, L.args.Ws, L.blob.nkc * to.parts, P.blob.nkc * to.parts)) {
+                    // both K loops land in ONE accumulator set with ONE accumulator scale: the packer made the two layers' words equal
+                    const size_t li = (size_t)(&L - &c->layers[0]);
+                    if (li < c->wscale.size() && j < c->wscale.size() && memcmp(&c->wscale[li], &c->wscale[j], 4) != 0)
+                        return fail(&c->err, IDC_ERR_INTERNAL, "layers %s and %s would share one launch but their accumulator scales differ (%g, %g): the blob "
+                                    "was not packed by this library's packer", L.spec->name, ps.name, (double)c->wscale[li], (double)c->wscale[j]);
                     L.fused_short = (int)j; P.kernel = kFused;
                 }
                 continue;
@@ -1308,6 +1384,11 @@ static int run_graph(idc_context* c, int n, const float* dL, const float* dab, c
             if (a.ksplit > 1) HIPCHK(c, launch_splitk_epilogue(L.lprec, a, s));
         }
         toc();
+        if (c->audit) {
+            if (L.fused_next >= 0) HIPCHK(c, audit_layer(L.fused_next));              // model1 in one launch: conv1_2's output is what was stored
+            else if (L.chain_len > 0) { for (int j = li_; j <= chain_until; ++j) HIPCHK(c, audit_layer(j)); }
+            else if (!L.fused_head) HIPCHK(c, audit_layer(li_));                      // (conv10_2 under the fused head: never stored)
+        }
     }
     tic();
     if (!head_done && is_split(c->precision))
@@ -1470,6 +1551,7 @@ static void destroy_ctx(idc_context* c) {
     if (c->s_out) (void)hipStreamDestroy(c->s_out);
     if (c->ev_sync) (void)hipEventDestroy(c->ev_sync);
     if (c->d_zeros) (void)hipFree(c->d_zeros);
+    if (c->d_audit) (void)hipFree(c->d_audit);
     if (c->d_kw_stamps && c->kw_stamp_blocks > 0) {      // diagnostic: where a layer of the last chain launch spent its cycles (mean over workgroups)
         std::vector<long long> st((size_t)c->kw_stamp_blocks * kKwChainMax * 8);
         if (hipMemcpy(st.data(), c->d_kw_stamps, st.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
@@ -1624,12 +1706,28 @@ int idc_pack_weights(int precision, unsigned flags, const idc_tensor_desc* tenso
 static int validate_header(idc_context* h, const BlobHeader& hd, size_t blob_bytes) {
     if (hd.magic != kBlobMagic || hd.version != IDC_VERSION)
         return fail(&h->err, IDC_ERR_INVALID_ARG, "not an ideepcolor weight blob (bad magic/version)");
-    if ((int)hd.precision != h->precision || hd.flags != h->plan.flags)
-        return fail(&h->err, IDC_ERR_INVALID_ARG, "blob was packed for precision %u flags %u, handle needs %d/%u",
-                    hd.precision, hd.flags, h->precision, h->plan.flags);
+    const bool with_exp = (hd.flags & kBlobFlagActExp) != 0;        // packed with activation exponents: not a handle flag, IDC_FP16X3 blobs only
+    if ((int)hd.precision != h->precision || (hd.flags & ~kBlobFlagActExp) != h->plan.flags)
+        return fail(&h->err, IDC_ERR_INVALID_ARG, "blob was packed for precision %u flags %u%s, handle needs %d/%u",
+                    hd.precision, hd.flags & ~kBlobFlagActExp, with_exp ? " (+ activation exponents)" : "", h->precision, h->plan.flags);
+    if (with_exp && (h->precision != IDC_FP16X3 || h->plan.active.size() > sizeof(hd.pad)))
+        return fail(&h->err, IDC_ERR_INVALID_ARG, "blob carries activation exponents (header flag 0x%x): only IDC_FP16X3 handles without head flags take them", kBlobFlagActExp);
     if (hd.total_bytes != h->plan.total_bytes || blob_bytes < h->plan.total_bytes)
         return fail(&h->err, IDC_ERR_INVALID_ARG, "blob size mismatch");
     return IDC_OK;
+}
+
+// What the host side needs to know about the blob in use: the activation exponent of every active layer (header) and the accumulator-scale words
+// (the fused deconv + shortcut launch checks that its two layers agree before it shares one).  host_blob: the whole validated blob in host memory.
+static void cache_blob_meta(idc_context* h, const uint8_t* host_blob) {
+    BlobHeader hd;
+    memcpy(&hd, host_blob, sizeof(hd));
+    const size_t nl = h->plan.active.size();
+    h->act_exp.assign(nl, 0); h->wscale.assign(nl, 1.f);
+    for (size_t li = 0; li < nl; ++li) {
+        if ((hd.flags & kBlobFlagActExp) && li < sizeof(hd.pad)) h->act_exp[li] = (int)(int8_t)hd.pad[li];
+        if (h->plan.layers[li].wscale_off != (size_t)-1) memcpy(&h->wscale[li], host_blob + h->plan.layers[li].wscale_off, 4);
+    }
 }
 
 int idc_set_weights_host(idc_handle h, const void* blob, size_t blob_bytes) {
@@ -1648,6 +1746,7 @@ int idc_set_weights_host(idc_handle h, const void* blob, size_t blob_bytes) {
         h->own_blob = true;
     }
     HIPCHK(h, hipMemcpy(h->d_blob, blob, h->plan.total_bytes, hipMemcpyHostToDevice));
+    cache_blob_meta(h, (const uint8_t*)blob);
     h->weights_set = true;
     return IDC_OK;
 }
@@ -1664,6 +1763,7 @@ static int verify_device_blob(idc_context* h, const void* dev_blob, size_t blob_
     HIPCHK(h, hipMemcpy(tmp.data(), dev_blob, tmp.size(), hipMemcpyDeviceToHost));
     if (fnv1a(tmp.data() + sizeof(hd), tmp.size() - sizeof(hd)) != hd.checksum)
         return fail(&h->err, IDC_ERR_INVALID_ARG, "device blob checksum mismatch");
+    cache_blob_meta(h, tmp.data());
     return IDC_OK;
 }
 
@@ -1688,12 +1788,21 @@ int idc_set_weights_device(idc_handle h, const void* dev_blob, size_t blob_bytes
     return IDC_OK;
 }
 
-int idc_load_weights(idc_handle h, const idc_tensor_desc* tensors, int n_tensors) {
+int idc_pack_weights_ex(int precision, unsigned flags, const idc_tensor_desc* tensors, int n_tensors, const int* act_exp, int n_layers,
+                        void* blob, size_t blob_bytes) {
+    return pack_weights_impl(precision, flags, tensors, n_tensors, blob, blob_bytes, nullptr, act_exp, n_layers);
+}
+
+int idc_load_weights_ex(idc_handle h, const idc_tensor_desc* tensors, int n_tensors, const int* act_exp, int n_layers) {
     if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
     std::vector<uint8_t> blob(h->plan.total_bytes);
-    int rc = pack_weights_impl(h->precision, h->flags, tensors, n_tensors, blob.data(), blob.size(), &h->err);
+    int rc = pack_weights_impl(h->precision, h->flags, tensors, n_tensors, blob.data(), blob.size(), &h->err, act_exp, n_layers);
     if (rc) return rc;
     return idc_set_weights_host(h, blob.data(), blob.size());
+}
+
+int idc_load_weights(idc_handle h, const idc_tensor_desc* tensors, int n_tensors) {
+    return idc_load_weights_ex(h, tensors, n_tensors, nullptr, 0);
 }
 
 const void* idc_weights_device_ptr(idc_handle h) { return (h && h->weights_set) ? h->d_blob : nullptr; }
@@ -2177,6 +2286,7 @@ int idc_forward_async(idc_handle h, int slot, int n, const float* L_mc, const fl
     if (rc) return rc;
     if (slot < 0 || slot > 1) return fail(&h->err, IDC_ERR_INVALID_ARG, "slot %d not in 0..1", slot);
     if (!L_mc || !ab || !mask || !out_ab) return fail(&h->err, IDC_ERR_INVALID_ARG, "null tensor pointer");
+    if (h->audit) return fail(&h->err, IDC_ERR_UNSUPPORTED, "the range audit covers the blocking, resident and device-pointer forwards, not the pipelined slots");
     HIPCHK(h, hipSetDevice(h->device));
     rc = ensure_pipeline(h);
     if (rc) return rc;
@@ -2451,6 +2561,58 @@ int idc_layer_info_get(idc_handle h, int layer, idc_layer_info* out) {
     return IDC_OK;
 }
 
+int idc_set_range_audit(idc_handle h, int on) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (on && !h->d_audit) {
+        HIPCHK(h, hipSetDevice(h->device));
+        HIPCHK(h, hipMalloc((void**)&h->d_audit, (size_t)h->n_timed * sizeof(AuditRecord)));
+        HIPCHK(h, hipMemsetAsync(h->d_audit, 0, (size_t)h->n_timed * sizeof(AuditRecord), h->stream));
+        h->audit_values.assign((size_t)h->n_timed, 0);
+    }
+    h->audit = on != 0;
+    return IDC_OK;
+}
+
+int idc_range_reset(idc_handle h) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (h->d_audit) {
+        HIPCHK(h, hipSetDevice(h->device));
+        HIPCHK(h, hipMemsetAsync(h->d_audit, 0, (size_t)h->n_timed * sizeof(AuditRecord), h->stream));     // stream-ordered behind the audited forwards
+        h->audit_values.assign((size_t)h->n_timed, 0);
+    }
+    return IDC_OK;
+}
+
+int idc_range_report(idc_handle h, int layer, idc_range_info* out) {
+    if (!h || !out) return fail(h ? &h->err : nullptr, IDC_ERR_INVALID_ARG, "null argument");
+    if (layer < 0 || layer >= h->n_timed) return fail(&h->err, IDC_ERR_INVALID_ARG, "layer %d out of range", layer);
+    memset(out, 0, sizeof(*out));
+    idc_layer_info info;
+    int rc = idc_layer_info_get(h, layer, &info);
+    if (rc) return rc;
+    snprintf(out->name, sizeof(out->name), "%s", info.name);
+    const int nl = (int)h->layers.size();
+    if (layer >= 1 && layer <= nl) {
+        const Tensor& t = h->tensors[h->layers[layer - 1].dst];
+        const bool f32 = t.is_f32 || h->precision == IDC_FP32;
+        out->storage = f32 ? IDC_STORE_F32 : (split_is_f16(h->precision) ? IDC_STORE_F16 : IDC_STORE_BF16);
+        out->parts = f32 ? 1 : t.parts;
+        if ((size_t)(layer - 1) < h->act_exp.size()) out->act_exp = h->act_exp[layer - 1];
+    }
+    if (!h->d_audit) return IDC_OK;                  // never switched on: all counts zero
+    HIPCHK(h, hipSetDevice(h->device));
+    AuditRecord r;
+    HIPCHK(h, hipMemcpyAsync(&r, h->d_audit + layer, sizeof(r), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    rc = check_chain_abort(h);
+    if (rc) return rc;
+    memcpy(&out->max_abs, &r.max_abs_bits, 4);
+    out->n_values = h->audit_values[(size_t)layer];
+    out->n_saturated = r.n_saturated; out->n_tiny = r.n_tiny; out->n_nonfinite = r.n_nonfinite;
+    if (out->n_values == 0) out->storage = IDC_STORE_NONE;
+    return IDC_OK;
+}
+
 int idc_set_profiling(idc_handle h, int on) {
     if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
     if (on != 0 && h->ev.empty()) {
@@ -2538,6 +2700,9 @@ int idc_get_activation(idc_handle h, const char* name, int n, float* out, size_t
     else HIPCHK(h, launch_nhwc_to_nchw(src_bf16, t.ptr, h->d_scratch, n, t.C, t.H, t.W, t.Cpad, h->stream));
     HIPCHK(h, hipMemcpyAsync(out, h->d_scratch, need * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (size_t li = 0; li < h->layers.size() && li < h->act_exp.size(); ++li)      // stored as value * 2^a: hand out the value (a power of two: exact)
+        if (h->layers[li].dst == ti && h->act_exp[li] != 0)
+            for (size_t i = 0; i < need; ++i) out[i] = ldexpf(out[i], -h->act_exp[li]);
     if (C) *C = t.C;
     if (H) *H = t.H;
     if (W) *W = t.W;

@@ -262,6 +262,16 @@ constexpr int kSuggestMaxBins = 1024, kSuggestMaxK = 16;
 hipError_t launch_suggest(const float* pdf, long long stride, int B, const float* centres, int K, int N, unsigned seed,
                           double* out_centres, double* out_conf, unsigned* out_counts, hipStream_t s);
 
+// Range audit (idc_audit.hip; idc_set_range_audit): one layer's sticky record in device memory, and the streaming reduction that folds a stored
+// tensor into it -- npix pixels of [parts][Cpad] 16-bit values (bf16, or fp16 when f16; value = sum of the parts) or, parts = 0, of [Cpad] fp32;
+// channels >= C are padding and skipped.  max_abs over the finite values (atomicMax on the bit pattern); |value| >= 65504 counts as saturated in
+// the fp16 forms only; non-zero |value| < 2^-14 counts as tiny in every form.
+struct AuditRecord {
+    unsigned max_abs_bits, pad;
+    unsigned long long n_saturated, n_tiny, n_nonfinite;
+};
+hipError_t launch_range_audit(const void* src, long long npix, int C, int Cpad, int parts, int f16, AuditRecord* rec, hipStream_t s);
+
 // layout converters for the single-operator test entry points and idc_get_activation
 hipError_t launch_nchw_to_nhwc(int precision, const float* src, void* dst, int N, int C, int H, int W,
                                int Cpad, hipStream_t s);

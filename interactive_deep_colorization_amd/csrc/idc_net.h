@@ -123,8 +123,10 @@ struct BlobHeader {
     uint32_t magic, version, precision, flags;
     uint64_t total_bytes;
     uint64_t checksum;                   // FNV-1a over the payload after the header
-    uint8_t pad[32];
+    uint8_t pad[32];                     // kBlobFlagActExp: int8 activation exponent of active layer i in pad[i] (as resolved by the packer); else zeros
 };
+constexpr uint32_t kBlobFlagActExp = 0x100u;   // BlobHeader.flags: packed with non-zero activation exponents (idc_pack_weights_ex); not an idc_create flag
+constexpr int kActExpMax = 24;                 // |exponent| an activation tensor may carry
 static_assert(sizeof(BlobHeader) == 64, "blob header is 64 bytes");
 
 BlobPlan make_blob_plan(int precision, unsigned flags);

@@ -93,19 +93,102 @@ def set_splitk_policy(policy="auto"):
     N.check(N.load().idc_set_splitk_policy(SPLITK_POLICIES[policy] if isinstance(policy, str) else int(policy)))
 
 
-def pack_weights(sd, precision="bf16", dist=False, global_hints=False, dist313=False, throughput_blob=False):
+# The conv layers in the order of the engine's layer table (csrc/idc_net.h; HipColorizer.layer_table() on a handle): row 0 is the global-hints
+# branch, the conv layers follow, then the head and the 529-bin softmax.  Activation exponents are indexed by that table.
+_CONV_LAYERS = ("conv1_1", "conv1_2", "conv2_1", "conv2_2", "conv3_1", "conv3_2", "conv3_3", "conv4_1", "conv4_2", "conv4_3",
+                "conv5_1", "conv5_2", "conv5_3", "conv6_1", "conv6_2", "conv6_3", "conv7_1", "conv7_2", "conv7_3",
+                "conv3_3_short", "conv8_1", "conv8_2", "conv8_3", "class_logits", "conv2_2_short", "conv9_1", "conv9_2",
+                "conv1_2_short", "conv10_1", "conv10_2")
+_PRED_LAYERS = ("conv3_pred", "conv34_pred", "conv345_pred", "conv3456_pred", "conv34567_pred", "conv345678_pred", "pred_313")
+
+
+def layer_table_names(dist=False, dist313=False):
+    """Row names of the layer table a handle with these flags has (no handle, no GPU needed)."""
+    rows = [n for n in _CONV_LAYERS if dist or n != "class_logits"] + (list(_PRED_LAYERS) if dist313 else [])
+    return ["glob_branch"] + rows + ["head", "dist_softmax"]
+
+
+def _act_exp_array(act_exp, dist=False, dist313=False):
+    """``act_exp`` as the C int array of the ``_ex`` entry points: None -> (None, 0); a dict {layer name: exponent} is laid out over the layer
+    table of these flags (unnamed layers 0); a sequence is passed on as it is (its length is checked by the library)."""
+    if act_exp is None:
+        return None, 0
+    if isinstance(act_exp, dict):
+        names = layer_table_names(dist, dist313)
+        unknown = sorted(set(act_exp) - set(names))
+        if unknown:
+            raise KeyError("no layer named %s" % ", ".join(unknown))
+        act_exp = [int(act_exp.get(nm, 0)) for nm in names]
+    vals = [int(v) for v in act_exp]
+    return (ctypes.c_int * max(len(vals), 1))(*vals), len(vals)
+
+
+def pack_weights(sd, precision="bf16", dist=False, global_hints=False, dist313=False, throughput_blob=False, act_exp=None):
     """Host-only: reference ``state_dict`` -> packed device-ready blob (uint8 ndarray).
     Needs no GPU (used by rank 0 before the RCCL broadcast).  ``throughput_blob``: without the Winograd images of the
-    batch-1 / fp32 kernels (IDC_FLAG_THROUGHPUT_BLOB: fp32 136 MB instead of 384 MB; a bf16 blob is 68 MB either way) -- must match the handle's."""
+    batch-1 / fp32 kernels (IDC_FLAG_THROUGHPUT_BLOB: fp32 136 MB instead of 384 MB; a bf16 blob is 68 MB either way) -- must match the handle's.
+    ``act_exp`` (fp16x3 only; ``calibrate_activation_exponents``): per-layer activation exponents, a sequence over the layer table or a dict
+    {layer name: exponent}; None or all zeros = the plain blob, byte for byte."""
     lib = N.load()
     prec = _PREC[precision]
     flags = _flags(dist, global_hints, dist313, throughput_blob)
     nbytes = lib.idc_weights_blob_bytes(prec, flags)
     blob = np.zeros(nbytes, dtype=np.uint8)
     arr, n, keep = _tensor_descs(sd)
-    N.check(lib.idc_pack_weights(prec, flags, arr, n, blob.ctypes.data_as(ctypes.c_void_p), nbytes))
+    ae, n_layers = _act_exp_array(act_exp, dist, dist313)
+    if ae is None:
+        N.check(lib.idc_pack_weights(prec, flags, arr, n, blob.ctypes.data_as(ctypes.c_void_p), nbytes))
+    else:
+        N.check(lib.idc_pack_weights_ex(prec, flags, arr, n, ae, n_layers, blob.ctypes.data_as(ctypes.c_void_p), nbytes))
     del keep
     return blob
+
+
+# Calibration target: the largest value a calibration image produced in a tensor lands in (2^(TARGET_EXP-1), 2^TARGET_EXP] = (2048, 4096].
+# fp16 saturates at 65504 ~ 2^16, so images the calibration did not see have 16x headroom; and the lo part of a stored value v 2^a is a normal
+# fp16 number while |v 2^a| >= 2^-14 * 2^11 = 2^-3, i.e. values down to 2^-15 of the tensor's maximum keep all 22 bits of hi + lo.
+TARGET_EXP = 12
+ACT_EXP_RANGE = (-24, 24)       # what the packer accepts (csrc/idc_net.h kActExpMax); exponents beyond are clipped to it
+
+
+def exponents_from_report(report, target_exp=TARGET_EXP, clip=ACT_EXP_RANGE):
+    """Range-audit report (``HipColorizer.range_report()``) -> activation exponents over the same layer table:
+    a = target_exp - ceil(log2(max_abs)), clipped; 0 where the layer stored nothing (n_values == 0) or stored only zeros."""
+    out = []
+    for row in report:
+        mx = float(row["max_abs"])
+        if row["n_values"] == 0 or not (mx > 0.0) or not np.isfinite(mx):
+            out.append(0)
+            continue
+        m, e = np.frexp(mx)                                  # mx = m 2^e, m in [0.5, 1): ceil(log2(mx)) = e, or e - 1 for an exact power of two
+        ceil_log2 = int(e) - 1 if m == 0.5 else int(e)
+        a = int(target_exp) - ceil_log2 + int(row.get("act_exp", 0))      # (a report of scaled tensors: max_abs is of value * 2^act_exp)
+        out.append(int(min(max(a, clip[0]), clip[1])))
+    return out
+
+
+def calibrate_activation_exponents(sd, L_mc, ab, mask, maskcent=0.0, device=0, dist=False, throughput_blob=False, io_scales=None,
+                                   target_exp=TARGET_EXP, engine_factory=None):
+    """Activation exponents for ``precision='fp16x3'`` from calibration images: a temporary ``bf16x6`` engine (fp16x3's layer table and
+    kernels, fp32's exponent range) runs the batch with the range audit on; each layer's exponent brings the largest value seen to
+    ``2^target_exp`` (``exponents_from_report``).  Returns a list over the layer table, for ``load_state_dict(sd, act_exp=...)`` /
+    ``pack_weights(..., act_exp=...)``.  ``io_scales``: keyword arguments of ``set_io_scales`` (the Caffe twin's)."""
+    L_mc = np.asarray(L_mc)
+    if L_mc.ndim == 3:
+        L_mc, ab, mask = L_mc[None], np.asarray(ab)[None], np.asarray(mask)[None]
+    n, H, W = L_mc.shape[0], L_mc.shape[2], L_mc.shape[3]
+    make = engine_factory or HipColorizer
+    e = make(H, W, max_batch=n, precision="bf16x6", device=device, dist=dist, throughput_blob=throughput_blob)
+    try:
+        if io_scales:
+            e.set_io_scales(**io_scales)
+        e.load_state_dict(sd)
+        e.set_range_audit(True)
+        e.forward(L_mc, ab, mask, maskcent)
+        report = e.range_report()
+    finally:
+        e.close()
+    return exponents_from_report(report, target_exp)
 
 
 class _PinnedBuffer(object):
@@ -282,10 +365,39 @@ class HipColorizer(object):
         return N.check(status, self._h)
 
     # ---- weights --------------------------------------------------------------------------
-    def load_state_dict(self, sd):
+    def load_state_dict(self, sd, act_exp=None):
+        """``act_exp`` (fp16x3 only): per-layer activation exponents as ``pack_weights`` takes them; None = the plain load."""
         arr, n, keep = _tensor_descs(sd)
-        self._chk(self.lib.idc_load_weights(self._h, arr, n))
+        ae, n_layers = _act_exp_array(act_exp, self.dist, self.dist313)
+        if ae is None:
+            self._chk(self.lib.idc_load_weights(self._h, arr, n))
+        else:
+            self._chk(self.lib.idc_load_weights_ex(self._h, arr, n, ae, n_layers))
         del keep
+
+    # ---- range audit ----------------------------------------------------------------------
+    def set_range_audit(self, on=True):
+        """While on, every forward folds each layer's STORED output into a sticky per-layer record (``range_report``); results do not change."""
+        self._chk(self.lib.idc_set_range_audit(self._h, 1 if on else 0))
+
+    def range_reset(self):
+        self._chk(self.lib.idc_range_reset(self._h))
+
+    def range_report(self):
+        """One dict per row of ``layer_table()``: {index, name, storage, act_exp, max_abs, n_values, n_saturated, n_tiny, n_nonfinite}.
+        ``storage``: 'fp32', 'bf16', 'fp16', 'bf16x2' / 'bf16x3' / 'fp16x2' (planes whose sum is the value), or None where the layer
+        stored nothing of its own (n_values == 0).  The figures are of the stored values, i.e. value * 2^act_exp."""
+        rows = []
+        kinds = {N.IDC_STORE_F32: "fp32", N.IDC_STORE_BF16: "bf16", N.IDC_STORE_F16: "fp16"}
+        for i in range(self.lib.idc_num_layers(self._h)):
+            r = N.RangeInfo()
+            self._chk(self.lib.idc_range_report(self._h, i, ctypes.byref(r)))
+            kind = kinds.get(r.storage)
+            storage = None if kind is None else (kind if r.parts <= 1 else "%sx%d" % (kind, r.parts))
+            rows.append(dict(index=i, name=r.name.decode(), storage=storage, act_exp=int(r.act_exp), max_abs=float(r.max_abs),
+                             n_values=int(r.n_values), n_saturated=int(r.n_saturated), n_tiny=int(r.n_tiny),
+                             n_nonfinite=int(r.n_nonfinite)))
+        return rows
 
     def blob_bytes(self):
         return int(self.lib.idc_weights_blob_bytes(self._prec, self._flags))
