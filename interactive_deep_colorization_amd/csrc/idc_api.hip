@@ -1,0 +1,493 @@
+// idc_api.hip -- the handle and what a caller does with it besides weights and forwards (C ABI, include/ideepcolor.h): create / destroy, the last-error
+// string (fail), I/O scales, global hints, the click session, Lab -> RGB, colour suggestions and distributions, the global histogram, stream
+// ordering and the display upsample.
+#include <stdarg.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "idc_engine.h"
+
+namespace idc {
+
+static thread_local std::string g_last_error;
+
+int fail(std::string* err, int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    g_last_error = buf;
+    if (err) *err = buf;
+    return code;
+}
+
+static void destroy_ctx(idc_context* c) {
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    if (c->d_arena) (void)hipFree(c->d_arena);
+    else for (auto& t : c->tensors) if (t.ptr) (void)hipFree(t.ptr);
+    for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
+    if (c->own_blob && c->d_blob) (void)hipFree(c->d_blob);
+    for (auto& sl : c->pipe) {
+        void* dv[] = {sl.d_L, sl.d_ab, sl.d_mask, sl.d_out};
+        for (void* p : dv) if (p) (void)hipFree(p);
+        if (sl.h_in) (void)hipHostFree(sl.h_in);
+        if (sl.h_out) (void)hipHostFree(sl.h_out);
+        hipEvent_t evs[] = {sl.ev_in, sl.ev_comp, sl.ev_out, sl.ev_in0, sl.ev_comp0, sl.ev_out0};
+        for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
+    }
+    if (c->ev_pipe_base) (void)hipEventDestroy(c->ev_pipe_base);
+    if (c->s_in) (void)hipStreamDestroy(c->s_in);
+    if (c->s_out) (void)hipStreamDestroy(c->s_out);
+    if (c->ev_sync) (void)hipEventDestroy(c->ev_sync);
+    if (c->d_zeros) (void)hipFree(c->d_zeros);
+    if (c->d_audit) (void)hipFree(c->d_audit);
+    if (c->d_kw_stamps && c->kw_stamp_blocks > 0) {      // diagnostic: where a layer of the last chain launch spent its cycles (mean over workgroups)
+        std::vector<long long> st((size_t)c->kw_stamp_blocks * kKwChainMax * 8);
+        if (hipMemcpy(st.data(), c->d_kw_stamps, st.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
+            static const char* names[] = {"prefetch+barrier wait", "halo issue", "halo landed", "taps", "reduce+epilogue", "stores acked+wg barrier"};
+            static const int seq[] = {0, 1, 6, 2, 3, 4, 5};
+            for (int li = 0; li < c->kw_stamp_layers; ++li) {
+                double d[6] = {0, 0, 0, 0, 0, 0};
+                for (int b = 0; b < c->kw_stamp_blocks; ++b) {
+                    const long long* p = &st[((size_t)b * kKwChainMax + li) * 8];
+                    for (int k = 0; k < 6; ++k) {
+                        if (li + 1 == c->kw_stamp_layers && k == 5) continue;
+                        d[k] += (double)(p[seq[k + 1]] - p[seq[k]]);
+                    }
+                }
+                fprintf(stderr, "kw_chain stamps layer %2d:", li);
+                for (int k = 0; k < 6; ++k) fprintf(stderr, " %s %.0f |", names[k], d[k] / c->kw_stamp_blocks);
+                fprintf(stderr, "\n");
+            }
+        }
+        (void)hipFree(c->d_kw_stamps);
+    }
+    if (c->d_kw_bar) (void)hipFree(c->d_kw_bar);
+    if (c->h_kw_abort) (void)hipHostFree(c->h_kw_abort);
+    if (c->d_up_rgb) (void)hipFree(c->d_up_rgb);
+    if (c->d_up_L) (void)hipFree(c->d_up_L);
+    if (c->h_up_rgb) (void)hipHostFree(c->h_up_rgb);
+    if (c->h_up_L) (void)hipHostFree(c->h_up_L);
+    void* dev[] = {c->d_L, c->d_ab, c->d_mask, c->d_out, c->d_dist, c->d_scratch, c->d_glob_in, c->d_glob_vec, c->d_pred_ab, c->d_dist313, c->d_partial, c->d_rgb, c->d_labq, c->d_hints, c->d_centres, c->d_sugg, c->d_sugg_counts, c->d_post_in};
+    for (void* p : dev) if (p) (void)hipFree(p);
+    void* host[] = {c->h_in, c->h_out, c->h_dist, c->h_pred_ab, c->h_rgb, c->h_labq, c->h_hints};
+    for (void* p : host) if (p) (void)hipHostFree(p);
+    if (c->stream) (void)hipStreamDestroy(c->stream);
+    delete c;
+}
+
+int check_device(int device_id, std::string* err) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
+        return fail(err, IDC_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)");
+    if (device_id < 0 || device_id >= count) return fail(err, IDC_ERR_NO_DEVICE, "device %d not in 0..%d", device_id, count - 1);
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device_id) != hipSuccess) return fail(err, IDC_ERR_HIP, "hipGetDeviceProperties failed");
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return fail(err, IDC_ERR_NO_DEVICE, "device %d is %s; this library is built for gfx950 only", device_id, prop.gcnArchName);
+    return IDC_OK;
+}
+
+int ensure_post_buffers(idc_context* h) {
+    if (h->d_rgb) return IDC_OK;
+    const size_t hw = (size_t)h->H * h->W, nb = (size_t)h->max_batch;
+    HIPCHK(h, hipMalloc((void**)&h->d_rgb, nb * hw * 3));
+    HIPCHK(h, hipMalloc((void**)&h->d_labq, nb * hw * 3 * 8));
+    HIPCHK(h, hipMalloc((void**)&h->d_post_in, nb * hw * 3 * 4));
+    HIPCHK(h, hipHostMalloc((void**)&h->h_rgb, nb * hw * 3, hipHostMallocDefault));
+    HIPCHK(h, hipHostMalloc((void**)&h->h_labq, nb * hw * 3 * 8, hipHostMallocDefault));
+    return IDC_OK;
+}
+
+// post step on device-resident planes: d_Lp [n,1,H,W] (+ l_add), d_abp [n,2,H,W] -> host rgb / lab_q
+int run_lab_post(idc_context* h, int n, const float* d_Lp, float l_add, const float* d_abp, uint8_t* rgb, double* lab_q) {
+    const size_t hw = (size_t)h->H * h->W;
+    int rc = ensure_post_buffers(h);
+    if (rc) return rc;
+    HIPCHK(h, launch_lab_post(d_Lp, l_add, d_abp, h->d_rgb, lab_q ? h->d_labq : nullptr, n, h->H, h->W, h->stream));
+    const bool rgb_direct = is_pinned(rgb), lab_direct = lab_q && is_pinned(lab_q);      // pinned caller buffers: no staging copy
+    HIPCHK(h, copy_h2d_or_d2h(h, h->d_rgb, rgb_direct ? (void*)rgb : (void*)h->h_rgb, (size_t)n * hw * 3, false));
+    if (lab_q) HIPCHK(h, copy_h2d_or_d2h(h, h->d_labq, lab_direct ? (void*)lab_q : (void*)h->h_labq, (size_t)n * hw * 3 * 8, false));
+    HIPCHK(h, wait_stream(h, n));
+    rc = check_chain_abort(h);
+    if (rc) return rc;
+    if (!rgb_direct) memcpy(rgb, h->h_rgb, (size_t)n * hw * 3);
+    if (lab_q && !lab_direct) memcpy(lab_q, h->h_labq, (size_t)n * hw * 3 * 8);
+    return IDC_OK;
+}
+
+}  // namespace idc
+
+extern "C" {
+
+int idc_version(void) { return IDC_VERSION; }
+
+int idc_device_count(void) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess) return 0;
+    return count;
+}
+
+const char* idc_last_error(idc_handle h) { return h ? h->err.c_str() : g_last_error.c_str(); }
+
+int idc_create(int device_id, int height, int width, int max_batch, int precision, unsigned flags, idc_handle* out) {
+    if (!out) return fail(nullptr, IDC_ERR_INVALID_ARG, "null out handle");
+    *out = nullptr;
+    if (height <= 0 || width <= 0 || height % 8 || width % 8)
+        return fail(nullptr, IDC_ERR_INVALID_ARG, "H and W must be positive multiples of 8 (got %dx%d)", height, width);
+    if (max_batch <= 0) return fail(nullptr, IDC_ERR_INVALID_ARG, "max_batch must be positive");
+    if (precision < IDC_FP32 || precision > IDC_FP16) return fail(nullptr, IDC_ERR_INVALID_ARG, "bad precision %d", precision);
+    int rc = check_device(device_id, nullptr);
+    if (rc) return rc;
+    if (hipSetDevice(device_id) != hipSuccess) return fail(nullptr, IDC_ERR_HIP, "hipSetDevice(%d) failed", device_id);
+    idc_context* c = new idc_context();
+    c->device = device_id; c->H = height; c->W = width; c->max_batch = max_batch; c->precision = precision; c->flags = flags;
+    c->plan = make_blob_plan(precision, flags);
+    hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = init_kernels();
+    if (e != hipSuccess) {
+        rc = fail(nullptr, IDC_ERR_HIP, "stream/kernel init failed: %s", hipGetErrorString(e));
+        destroy_ctx(c);
+        return rc;
+    }
+    rc = build_graph(c);
+    if (rc == IDC_OK) rc = alloc_graph(c);
+    if (rc != IDC_OK) { g_last_error = c->err; destroy_ctx(c); return rc; }
+    *out = c;
+    return IDC_OK;
+}
+
+int idc_destroy(idc_handle h) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    destroy_ctx(h);
+    return IDC_OK;
+}
+
+int idc_set_io_scales(idc_handle h, float l_div, float ab_div, float mask_mul, float out_mul) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (l_div == 0.f || ab_div == 0.f) return fail(&h->err, IDC_ERR_INVALID_ARG, "zero divisor");
+    h->l_div = l_div; h->ab_div = ab_div; h->mask_mul = mask_mul; h->out_mul = out_mul;
+    return IDC_OK;
+}
+
+int idc_set_global_hints(idc_handle h, int n, const float* glob_ab_313_mask, const float* s_avg_mask) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (!(h->flags & IDC_FLAG_GLOBAL_HINTS)) return fail(&h->err, IDC_ERR_UNSUPPORTED, "handle was created without IDC_FLAG_GLOBAL_HINTS");
+    if (n <= 0 || n > h->max_batch) return fail(&h->err, IDC_ERR_BATCH, "batch %d outside 1..%d", n, h->max_batch);
+    if (!glob_ab_313_mask) return fail(&h->err, IDC_ERR_INVALID_ARG, "null glob_ab_313_mask");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::vector<float> host((size_t)h->max_batch * kGlobIn, 0.f);
+    for (int i = 0; i < n; ++i) {
+        memcpy(&host[(size_t)i * kGlobIn], glob_ab_313_mask + (size_t)i * 314, 314 * 4);
+        if (s_avg_mask) memcpy(&host[(size_t)i * kGlobIn + 314], s_avg_mask + (size_t)i * 2, 2 * 4);
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(h->d_glob_in, host.data(), host.size() * 4, hipMemcpyHostToDevice));
+    return IDC_OK;
+}
+
+int idc_clear_global_hints(idc_handle h) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (!(h->flags & IDC_FLAG_GLOBAL_HINTS)) return fail(&h->err, IDC_ERR_UNSUPPORTED, "handle was created without IDC_FLAG_GLOBAL_HINTS");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemset(h->d_glob_in, 0, (size_t)h->max_batch * kGlobIn * 4));
+    return IDC_OK;
+}
+
+int idc_set_dist_temperature(idc_handle h, float S) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (!(S > 0.f)) return fail(&h->err, IDC_ERR_INVALID_ARG, "temperature must be positive");
+    h->dist_S = S;
+    return IDC_OK;
+}
+
+int idc_lab2rgb(idc_handle h, int n, const float* L, const float* ab, uint8_t* rgb, double* lab_q) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (n <= 0 || n > h->max_batch) return fail(&h->err, IDC_ERR_BATCH, "batch %d outside 1..%d", n, h->max_batch);
+    if (!L || !ab || !rgb) return fail(&h->err, IDC_ERR_INVALID_ARG, "null tensor pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = ensure_post_buffers(h);
+    if (rc) return rc;
+    const size_t hw = (size_t)h->H * h->W;
+    memcpy(h->h_in, L, (size_t)n * hw * 4);
+    memcpy(h->h_in + (size_t)n * hw, ab, (size_t)n * hw * 2 * 4);
+    HIPCHK(h, hipMemcpyAsync(h->d_post_in, h->h_in, (size_t)n * hw * 3 * 4, hipMemcpyHostToDevice, h->stream));
+    rc = run_lab_post(h, n, h->d_post_in, 0.f, h->d_post_in + (size_t)n * hw, rgb, lab_q);
+    h->labq_resident = rc == IDC_OK && lab_q != nullptr;        // d_labq = rgb2lab of exactly what was passed in
+    if (h->labq_resident && h->last_n < n) h->last_n = n;
+    return rc;
+}
+
+// ---------------------------------------------------------------------------------------------- click session
+static int check_img(idc_context* h, int img) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (img < 0 || img >= h->max_batch) return fail(&h->err, IDC_ERR_BATCH, "image %d outside 0..%d", img, h->max_batch - 1);
+    return IDC_OK;
+}
+
+int idc_set_image_l(idc_handle h, int img, const float* L_mc) {
+    int rc = check_img(h, img);
+    if (rc) return rc;
+    if (!L_mc) return fail(&h->err, IDC_ERR_INVALID_ARG, "null L_mc");
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t hw = (size_t)h->H * h->W;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(h->d_L + (size_t)img * hw, L_mc, hw * 4, hipMemcpyHostToDevice));
+    h->l_set[img] = 1;
+    return IDC_OK;
+}
+
+int idc_set_hints(idc_handle h, int img, int n_hints, const idc_hint* hints, int mode, float mask_value) {
+    int rc = check_img(h, img);
+    if (rc) return rc;
+    if (n_hints < 0 || (n_hints > 0 && !hints)) return fail(&h->err, IDC_ERR_INVALID_ARG, "bad hint list");
+    if (mode != IDC_HINT_AB && mode != IDC_HINT_RGB) return fail(&h->err, IDC_ERR_INVALID_ARG, "hint mode %d", mode);
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));            // the pinned list of the previous call may still be in flight
+    if (n_hints > h->hints_cap) {
+        const int cap = n_hints < 256 ? 256 : 2 * n_hints;
+        if (h->d_hints) (void)hipFree(h->d_hints);
+        if (h->h_hints) (void)hipHostFree(h->h_hints);
+        h->d_hints = nullptr; h->h_hints = nullptr; h->hints_cap = 0;
+        HIPCHK(h, hipMalloc((void**)&h->d_hints, (size_t)cap * sizeof(HintRect)));
+        HIPCHK(h, hipHostMalloc((void**)&h->h_hints, (size_t)cap * sizeof(HintRect), hipHostMallocDefault));
+        h->hints_cap = cap;
+    }
+    int kept = 0;
+    for (int i = 0; i < n_hints; ++i) {                    // cv2.rectangle: corners in either order, inclusive, clipped
+        HintRect r;
+        r.y0 = hints[i].y0 < hints[i].y1 ? hints[i].y0 : hints[i].y1; r.y1 = hints[i].y0 < hints[i].y1 ? hints[i].y1 : hints[i].y0;
+        r.x0 = hints[i].x0 < hints[i].x1 ? hints[i].x0 : hints[i].x1; r.x1 = hints[i].x0 < hints[i].x1 ? hints[i].x1 : hints[i].x0;
+        if (r.y0 < 0) r.y0 = 0;
+        if (r.x0 < 0) r.x0 = 0;
+        if (r.y1 > h->H - 1) r.y1 = h->H - 1;
+        if (r.x1 > h->W - 1) r.x1 = h->W - 1;
+        if (r.y0 > r.y1 || r.x0 > r.x1) continue;          // entirely outside
+        r.c0 = hints[i].c0; r.c1 = hints[i].c1; r.c2 = hints[i].c2;
+        if (mode == IDC_HINT_RGB)
+            if (!(r.c0 >= 0.f && r.c0 <= 255.f && r.c1 >= 0.f && r.c1 <= 255.f && r.c2 >= 0.f && r.c2 <= 255.f))
+                return fail(&h->err, IDC_ERR_INVALID_ARG, "hint %d: RGB outside 0..255", i);
+        h->h_hints[kept++] = r;
+    }
+    const size_t hw = (size_t)h->H * h->W;
+    if (kept) HIPCHK(h, hipMemcpyAsync(h->d_hints, h->h_hints, (size_t)kept * sizeof(HintRect), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, launch_raster_hints(h->d_hints, kept, mode, mask_value, h->d_ab + (size_t)img * hw * 2, h->d_mask + (size_t)img * hw,
+                                  h->H, h->W, h->stream));
+    return IDC_OK;
+}
+
+int idc_get_hint_planes(idc_handle h, int img, float* ab, float* mask) {
+    int rc = check_img(h, img);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t hw = (size_t)h->H * h->W;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (ab) HIPCHK(h, hipMemcpy(ab, h->d_ab + (size_t)img * hw * 2, hw * 2 * 4, hipMemcpyDeviceToHost));
+    if (mask) HIPCHK(h, hipMemcpy(mask, h->d_mask + (size_t)img * hw, hw * 4, hipMemcpyDeviceToHost));
+    return IDC_OK;
+}
+
+int idc_forward_resident(idc_handle h, int n, float maskcent, float l_cent, float* out_ab, uint8_t* rgb, double* lab_q) {
+    int rc = check_forward_args(h, n);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    for (int i = 0; i < n; ++i)
+        if (!h->l_set[i]) return fail(&h->err, IDC_ERR_INVALID_ARG, "I need to have an image! (slot %d has no L plane: idc_set_image_l)", i);
+    rc = drain_pipeline(h);
+    if (rc) return rc;
+    const size_t hw = (size_t)h->H * h->W;
+    rc = run_graph(h, n, h->d_L, h->d_ab, h->d_mask, maskcent, h->d_out, (h->flags & IDC_FLAG_DIST_HEAD) ? h->d_dist : nullptr);
+    if (rc) return rc;
+    h->out_resident = true; h->labq_resident = rgb != nullptr && lab_q != nullptr;
+    if (out_ab) HIPCHK(h, hipMemcpyAsync(h->h_out, h->d_out, (size_t)n * hw * 2 * 4, hipMemcpyDeviceToHost, h->stream));
+    if (rgb) {
+        rc = run_lab_post(h, n, h->d_L, l_cent, h->d_out, rgb, lab_q);      // synchronises the stream
+        if (rc) return rc;
+    } else {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    rc = check_chain_abort(h);
+    if (rc) return rc;
+    if (out_ab) memcpy(out_ab, h->h_out, (size_t)n * hw * 2 * 4);
+    return IDC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- colour suggestions
+int idc_keep_dist(idc_handle h, int on) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (!(h->flags & IDC_FLAG_DIST313)) return fail(&h->err, IDC_ERR_UNSUPPORTED, "handle was created without IDC_FLAG_DIST313");
+    h->keep_dist313 = on != 0;
+    return IDC_OK;
+}
+
+// where the resident distribution of image `img` lives: bins, element stride between bins, pointer to bin 0 at (y, x)
+static int dist_locate(idc_context* h, int img, int y, int x, int* B, long long* stride, const float** p) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (h->dist_n <= 0) return fail(&h->err, IDC_ERR_UNSUPPORTED, "Need to set prediction first (no resident distribution)");
+    if (img < 0 || img >= h->dist_n) return fail(&h->err, IDC_ERR_BATCH, "image %d outside 0..%d", img, h->dist_n - 1);
+    if (y < 0 || y >= h->H || x < 0 || x >= h->W) return fail(&h->err, IDC_ERR_INVALID_ARG, "pixel (%d,%d) outside the image", y, x);
+    if (h->flags & IDC_FLAG_DIST313) {
+        *B = 313; *stride = (long long)h->H * h->W;
+        *p = h->d_dist313 + (size_t)img * 313 * (*stride) + (size_t)y * h->W + x;
+    } else {                                               // 529 bins at H/4 x W/4; out_cl is its nearest x4 upsample (model.py:131)
+        const int h4 = h->H / 4, w4 = h->W / 4;
+        *B = 529; *stride = (long long)h4 * w4;
+        *p = h->d_dist + (size_t)img * 529 * (*stride) + (size_t)(y / 4) * w4 + (x / 4);
+    }
+    return IDC_OK;
+}
+
+int idc_dist_bins(idc_handle h) { return !h ? 0 : (h->flags & IDC_FLAG_DIST313) ? 313 : (h->flags & IDC_FLAG_DIST_HEAD) ? 529 : 0; }
+
+int idc_dist_at(idc_handle h, int img, int y, int x, float* pdf) {
+    int B; long long stride; const float* p;
+    int rc = dist_locate(h, img, y, x, &B, &stride, &p);
+    if (rc) return rc;
+    if (!pdf) return fail(&h->err, IDC_ERR_INVALID_ARG, "null pdf");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy2D(pdf, 4, p, (size_t)stride * 4, 4, (size_t)B, hipMemcpyDeviceToHost));
+    return IDC_OK;
+}
+
+int idc_get_dist(idc_handle h, int n, float* dist) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (h->dist_n <= 0) return fail(&h->err, IDC_ERR_UNSUPPORTED, "Need to set prediction first (no resident distribution)");
+    if (n <= 0 || n > h->dist_n) return fail(&h->err, IDC_ERR_BATCH, "batch %d outside 1..%d", n, h->dist_n);
+    if (!dist) return fail(&h->err, IDC_ERR_INVALID_ARG, "null dist");
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t hw = (size_t)h->H * h->W;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->flags & IDC_FLAG_DIST313) HIPCHK(h, hipMemcpy(dist, h->d_dist313, (size_t)n * 313 * hw * 4, hipMemcpyDeviceToHost));
+    else HIPCHK(h, hipMemcpy(dist, h->d_dist, (size_t)n * 529 * (hw / 16) * 4, hipMemcpyDeviceToHost));
+    return IDC_OK;
+}
+
+int idc_suggest_colors(idc_handle h, int img, int y, int x, int K, int N, unsigned seed, const float* centres,
+                       double* out_centres, double* out_conf, unsigned* out_counts) {
+    int B; long long stride; const float* p;
+    int rc = dist_locate(h, img, y, x, &B, &stride, &p);
+    if (rc) return rc;
+    if (!centres || !out_centres || !out_conf) return fail(&h->err, IDC_ERR_INVALID_ARG, "null pointer");
+    if (K < 1 || K > kSuggestMaxK) return fail(&h->err, IDC_ERR_INVALID_ARG, "K %d outside 1..%d", K, kSuggestMaxK);
+    if (N < 1) return fail(&h->err, IDC_ERR_INVALID_ARG, "N must be positive");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->d_centres) {
+        HIPCHK(h, hipMalloc((void**)&h->d_centres, (size_t)kSuggestMaxBins * 2 * 4));
+        HIPCHK(h, hipMalloc((void**)&h->d_sugg, (size_t)kSuggestMaxK * 3 * 8));
+        HIPCHK(h, hipMalloc((void**)&h->d_sugg_counts, (size_t)kSuggestMaxBins * 4));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(h->d_centres, centres, (size_t)B * 2 * 4, hipMemcpyHostToDevice));
+    HIPCHK(h, launch_suggest(p, stride, B, h->d_centres, K, N, seed, h->d_sugg, h->d_sugg + 2 * kSuggestMaxK, h->d_sugg_counts, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(out_centres, h->d_sugg, (size_t)K * 2 * 8, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(out_conf, h->d_sugg + 2 * kSuggestMaxK, (size_t)K * 8, hipMemcpyDeviceToHost));
+    if (out_counts) HIPCHK(h, hipMemcpy(out_counts, h->d_sugg_counts, (size_t)B * 4, hipMemcpyDeviceToHost));
+    return IDC_OK;
+}
+
+int idc_global_histogram(idc_handle h, int n, const uint8_t* rgb, const float* centres, float* hist, float* s_avg) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (n <= 0 || n > h->max_batch) return fail(&h->err, IDC_ERR_BATCH, "batch %d outside 1..%d", n, h->max_batch);
+    if (!rgb || !centres || !hist) return fail(&h->err, IDC_ERR_INVALID_ARG, "null pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = ensure_post_buffers(h);                      // d_rgb doubles as the upload buffer of the reference image
+    if (rc) return rc;
+    const size_t hw = (size_t)h->H * h->W;
+    DevBuf d_c, d_counts, d_sat;
+    HIPCHK(h, d_c.alloc(626 * 4)); HIPCHK(h, d_counts.alloc((size_t)n * 313 * 4)); HIPCHK(h, d_sat.alloc((size_t)n * 8));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(h->d_rgb, rgb, (size_t)n * hw * 3, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d_c.p, centres, 626 * 4, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemset(d_counts.p, 0, (size_t)n * 313 * 4));
+    HIPCHK(h, hipMemset(d_sat.p, 0, (size_t)n * 8));
+    HIPCHK(h, launch_global_stats(h->d_rgb, (const float*)d_c.p, (unsigned*)d_counts.p, (double*)d_sat.p, n, h->H, h->W, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    std::vector<unsigned> cnt((size_t)n * 313);
+    std::vector<double> sat(n);
+    HIPCHK(h, hipMemcpy(cnt.data(), d_counts.p, cnt.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(sat.data(), d_sat.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    const double nblk = (double)(h->H / 4) * (h->W / 4);
+    for (int i = 0; i < n; ++i) {
+        for (int k = 0; k < 313; ++k) hist[(size_t)i * 313 + k] = (float)(cnt[(size_t)i * 313 + k] / nblk);
+        if (s_avg) s_avg[i] = (float)(sat[i] / (double)hw);
+    }
+    return IDC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- stream ordering
+// The handle's work runs on its own non-blocking stream.  A caller that produces device inputs or consumes device
+// outputs on ANOTHER stream orders the two with these (or synchronises fully): wait = "the handle's stream waits for
+// everything enqueued so far on caller_stream"; signal = "caller_stream waits for everything the handle enqueued so far".
+int idc_stream_wait(idc_handle h, void* caller_stream) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipEventRecord(h->ev_sync, (hipStream_t)caller_stream));
+    HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_sync, 0));
+    return IDC_OK;
+}
+
+int idc_stream_signal(idc_handle h, void* caller_stream) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipEventRecord(h->ev_sync, h->stream));
+    HIPCHK(h, hipStreamWaitEvent((hipStream_t)caller_stream, h->ev_sync, 0));
+    return IDC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- display step
+int idc_upsample_lab2rgb(idc_handle h, int img, int source, int interp, int out_h, int out_w, const double* L, uint8_t* rgb) {
+    int rc = check_img(h, img);
+    if (rc) return rc;
+    if (!L || !rgb || out_h <= 0 || out_w <= 0) return fail(&h->err, IDC_ERR_INVALID_ARG, "bad output geometry / null pointer");
+    if (interp < 0 || interp > 2) return fail(&h->err, IDC_ERR_INVALID_ARG, "interp %d not in 0..2", interp);
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t hw = (size_t)h->H * h->W;
+    const void *pa = nullptr, *pb = nullptr; int f64 = 0;
+    if (source == IDC_SRC_OUTPUT_AB) {
+        if (!h->labq_resident || img >= h->last_n) return fail(&h->err, IDC_ERR_UNSUPPORTED, "no refreshed output_ab is resident (run idc_forward_rgb / idc_forward_resident with lab_q first)");
+        pa = h->d_labq + ((size_t)img * 3 + 1) * hw; pb = h->d_labq + ((size_t)img * 3 + 2) * hw; f64 = 1;
+    } else if (source == IDC_SRC_OUTPUT_AB_RAW) {
+        if (!h->out_resident || img >= h->last_n) return fail(&h->err, IDC_ERR_UNSUPPORTED, "no forward result is resident");
+        pa = h->d_out + (size_t)img * 2 * hw; pb = h->d_out + ((size_t)img * 2 + 1) * hw;
+    } else if (source == IDC_SRC_INPUT_AB) {
+        pa = h->d_ab + (size_t)img * 2 * hw; pb = h->d_ab + ((size_t)img * 2 + 1) * hw;
+    } else {
+        return fail(&h->err, IDC_ERR_INVALID_ARG, "source %d not in 0..2", source);
+    }
+    rc = drain_pipeline(h);
+    if (rc) return rc;
+    const size_t np = (size_t)out_h * out_w;
+    if (h->up_cap < np) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (h->d_up_rgb) (void)hipFree(h->d_up_rgb);
+        if (h->d_up_L) (void)hipFree(h->d_up_L);
+        if (h->h_up_rgb) (void)hipHostFree(h->h_up_rgb);
+        if (h->h_up_L) (void)hipHostFree(h->h_up_L);
+        h->d_up_rgb = nullptr; h->d_up_L = nullptr; h->h_up_rgb = nullptr; h->h_up_L = nullptr; h->up_cap = 0;
+        HIPCHK(h, hipMalloc((void**)&h->d_up_rgb, np * 3));
+        HIPCHK(h, hipMalloc((void**)&h->d_up_L, np * 8));
+        HIPCHK(h, hipHostMalloc((void**)&h->h_up_rgb, np * 3, hipHostMallocDefault));
+        HIPCHK(h, hipHostMalloc((void**)&h->h_up_L, np * 8, hipHostMallocDefault));
+        h->up_cap = np;
+    }
+    memcpy(h->h_up_L, L, np * 8);
+    HIPCHK(h, hipMemcpyAsync(h->d_up_L, h->h_up_L, np * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, launch_upsample_lab2rgb(pa, pb, f64, h->H, h->W, interp, (const double*)h->d_up_L, out_h, out_w, h->d_up_rgb, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->h_up_rgb, h->d_up_rgb, np * 3, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    memcpy(rgb, h->h_up_rgb, np * 3);
+    return IDC_OK;
+}
+
+void* idc_stream(idc_handle h) { return h ? (void*)h->stream : nullptr; }
+
+}  // extern "C"

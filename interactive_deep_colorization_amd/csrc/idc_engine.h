@@ -1,0 +1,238 @@
+// idc_engine.h -- what the host units of libideepcolor_hip.so share (idc_pack / idc_plan / idc_exec / idc_api / idc_rccl / idc_diag .hip): the graph's
+// types, the handle, the options, HIPCHK / fail() and the functions that cross a unit boundary.  Everything else is static in its unit.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "../../include/ideepcolor.h"
+#include "idc_kernels.h"
+#include "idc_layout.h"
+#include "idc_net.h"
+
+namespace idc {
+
+// The 32x32x16-MFMA partners of the throughput kernels (conv_igemm_v2, conv_ds_fused, conv1_1_bf16_kernel: idc_v2.hip, idc_conv1.hip) exist only in the
+// -DIDC_AB_PARTNERS build (round 6).  The default library plans every launch on conv_igemm_v2p / conv_igemm_v2m / conv_ds_fused_m / conv1_block_fused_t or
+// the small-tile kernels, and refuses the option values that ask for a partner.
+#ifdef IDC_AB_PARTNERS
+static constexpr bool kAbPartners = true;
+#else
+static constexpr bool kAbPartners = false;
+#endif
+
+static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+struct Tensor {
+    std::string name;
+    void* ptr = nullptr;
+    int C = 0, Cpad = 0, H = 0, W = 0;
+    int is_f32 = 0;                      // fp32 storage (else the context's element type)
+    int parts = 1;                       // operand-split precisions: bf16 planes per pixel ([part][Cpad]); 1 otherwise
+    size_t bytes = 0;
+};
+
+// The launch_* conv entry point a layer runs (idc_kernels.h).  set_geometry sizes a launch for one of the tile families kConvIgemm,
+// kConvClick, kConvWino, kDeconvWino, kConvKwave (the deconv form and the persistent trunk chain are reached through it) or kConvV2 (the
+// large tile) and records it; choose_kernel then names the entry point, once per layer per forward, and everything after reads that.
+enum Kernel {
+    kConvIgemm, kConvClick, kConvWino, kDeconvWino, kConvKwave,      // launch_conv (+ splitk_epilogue), launch_conv_click, _conv_wino, _deconv_wino, _conv_kwave
+    kConvV2, kConvV2m, kConvV2p, kConvV2s, kConvV2ps,                // the large tile: launch_conv_v2 (partner build), _v2m, _v2p (IDC_FP16: v2ph), _v2s, _v2ps
+    kConvDs, kConvDsM, kConvDsMs,                                    // deconv + shortcut conv: launch_conv_ds (partner build), _ds_m (IDC_FP16: _mh), _ds_ms
+    kConv1Block, kConv1_1Bf16, kConv1_1Split, kConv1_2Split,         // model1: launch_conv1_block, _conv1_1_bf16 (partner build), _conv1_1_split, _conv1_2_split
+    kFused,                                                          // not launched: rides in another layer's launch (its fused_next / fused_short)
+};
+
+struct Layer {
+    const LayerSpec* spec = nullptr;
+    LayerBlob blob;
+    int src = -1, dst = -1, resid = -1;
+    int halo = 0;
+    ConvConfig cfg{2, 2};
+    Kernel kernel = kConvIgemm;          // set_geometry's tile family until choose_kernel names the entry point (per forward)
+    int chain_len = 0;                   // > 0: this layer and the chain_len - 1 after it ran as ONE conv_kwave_chain_bf16 launch (last forward)
+    int chained_into = -1;               // >= 0: ran inside the chain launch headed by that layer (last forward)
+    bool fused_head = false;             // conv10_2 only: model_out + tanh run in this layer's epilogue
+    int fused_short = -1;                // deconv layers: index of the shortcut conv layer riding in this launch's K loop
+    int fused_next = -1;                 // conv1_1 only: index of conv1_2 when model1 runs as one launch (conv1_block_fused)
+    int lprec = 0;                       // the precision this layer's kernels run in (the handle's; IDC_FP32 on the fp32 island of a split handle)
+    bool split = false;                  // operand-split launch (conv_igemm_v2s / conv_igemm_v2ps)
+    ConvArgs args{};                     // zero-initialised; pointers patched per forward where they depend on weights
+    double flops = 0, min_bytes = 0;
+};
+
+struct DevBuf {
+    void* p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 16); }
+};
+
+// The options of idc_set_option / idc_set_tile_policy / idc_set_splitk_policy (idc_plan.hip): one object per process, options().
+struct Options {
+    // Tile policy (speed only; every choice computes the same result): 0 = automatic, 1 = always the
+    // small-tile kernels (conv_igemm), 2 = the large-tile bf16 kernel (conv_igemm_v2) wherever it applies.
+    int tile_policy = 0;
+    int fuse_conv1 = idc_env_int("IDC_FUSE_CONV1", 1) != 0;        // model1 (conv1_1 + conv1_2) as one launch on the bf16 throughput path (idc_set_option / env IDC_FUSE_CONV1=0 for A/B)
+    // Split-K policy of the small-tile kernels (speed only): 0 = automatic (launches that would leave most CUs idle,
+    // i.e. the batch-1 click path), 1 = never, 2 = always split as far as the cin chunks allow (tests).
+    int splitk_policy = 0;
+    // fp32 path: 3x3 stride-1 layers as Winograd F(2x2,3x3), small deconv launches as F(2x2,2x2) (idc_set_option "winograd"): 0 = off (direct kernels),
+    // 1 = automatic (default), 2 = wherever the forms are implemented (deconvs at every size: tests), 12 / 21 / 22 = automatic with the 3x3 form
+    // <TB,CB> forced (tests, tuning).  The bf16 twins of round 3 were retired in round 5 (docs/experiments/conv_wino_bf16_round3.hip.txt).
+    int wino = 1;
+    int wino_deconv = 1;                 // 1 = small launches with Cin >= 256 only; 2 = every deconv ("winograd" = 2)
+    // conv_igemm_v2 launches that qualify run as conv_igemm_v2m (16x16x32 MFMA: fewer joules per FLOP at the power cap; idc_set_option "mfma16")
+    int mfma16 = idc_env_int("IDC_MFMA16", 1);
+    // ... and so do the three deconv + shortcut launches (conv_ds_fused_m, idc_dsm.hip; idc_set_option "ds_mfma16" / env IDC_DS_M16=0 for A/B)
+    int ds_m16 = idc_env_int("IDC_DS_M16", 1);
+    // operand-split precisions: the deconv + shortcut pairs as ONE launch (conv_ds_fused_ms / _msh) instead of shortcut conv (fp32 sums to HBM) + deconv
+    // (idc_set_option "split_ds_fuse", 0 for A/B)
+    int split_ds_fuse = 1;
+    // ... and conv1_1, their exact-fp32 island, on conv1_1_split_kernel where the grid is throughput-sized (>= 128 tiles of 32 x 16; "conv1_1_split", 0 = conv_igemm<float>)
+    int conv1_1_split = 1;
+    // ... and conv1_2 (64 -> 64 at full resolution) on conv1_2_split_kernel instead of the generic 64-cout tile ("conv1_2_split", 0 = conv_igemm_v2ps<1,4,1>)
+    int conv1_2_split = 1;
+    // IDC_FP16 (one fp16 part, one segment): launches the bf16 throughput kernels cover run their fp16 twins (conv_igemm_v2ph, conv_ds_fused_mh: bias in the
+    // accumulators, packed-pair epilogue) instead of the one-segment split kernels ("fp16_fast", 0 = the split kernels everywhere)
+    int fp16_fast = 1;
+    // ... and the 3x3 convs among them as conv_igemm_v2p (no address arithmetic in the K loop; idc_set_option "v2p" / env IDC_V2P=0 for A/B)
+    int v2p = idc_env_int("IDC_V2P", 1);
+    // throughput kernels touch their own code at entry (idc_warm_own_code, idc_kernels.h; env IDC_CODE_WARM=0 for the A/B of profiles/r04_firstuse.txt)
+    int code_warm = idc_env_int("IDC_CODE_WARM", 1);
+    // bf16 click path: the 3x3 stride-1 layers and the deconvs as conv_kwave_bf16 / conv_kwave_deconv_bf16 ("kwave"; 0 = conv_click + split-K, round 2's kernels)
+    int kwave = 1;
+    // ... and runs of consecutive same-shape 8-chunk conv_kwave_bf16 layers (the 512 -> 512 trunk at batch 1) as ONE persistent launch with a
+    // grid barrier between layers ("kwave_chain" / IDC_KWAVE_CHAIN): 0 = off, 1 = hipLaunchCooperativeKernel (+24 us per launch on this runtime),
+    // 2 = plain launch after an occupancy check (default; a workgroup that never sees the others gives up after ~0.3 s and the handle falls back)
+    int kwave_chain = idc_env_int("IDC_KWAVE_CHAIN", 2);
+    int spin_sync = 1;                   // one- and two-image calls poll the stream instead of parking on an interrupt ("spin_sync"; 0 = the blocking wait of rounds 1-4)
+    int pcie_kernel = 1;                 // their host <-> device transfers as copy kernels on the forward's stream ("pcie_kernel"; 0 = hipMemcpyAsync / the copy engines)
+    int kw_force_abort = 0;              // test hook ("kw_force_abort"): the persistent trunk launch's first grid barrier is unreachable and its give-up counter tiny
+    int click = -1;                      // conv_click for small launches: -1 = environment default (on), 0 off, 1 on (idc_set_option "click")
+};
+Options& options();
+
+}  // namespace idc
+
+using namespace idc;
+
+struct idc_context {
+    int device = 0, H = 0, W = 0, max_batch = 0, precision = 0;
+    unsigned flags = 0;
+    hipStream_t stream = nullptr;
+    std::string err;
+    float l_div = 100.f, ab_div = 110.f, mask_mul = 1.f, out_mul = 110.f;
+    BlobPlan plan;
+    uint8_t* d_blob = nullptr;
+    bool own_blob = false, weights_set = false;
+    std::vector<Tensor> tensors;
+    std::vector<Layer> layers;
+    int t_input = -1, t_conv10_2 = -1, t_logits = -1;
+    // staging for the host-pointer forward
+    float *h_in = nullptr, *h_out = nullptr, *h_dist = nullptr;
+    float *d_L = nullptr, *d_ab = nullptr, *d_mask = nullptr, *d_out = nullptr, *d_dist = nullptr;
+    float* d_scratch = nullptr; size_t scratch_bytes = 0;
+    float* d_partial = nullptr; size_t partial_bytes = 0;    // split-K slice sums (grown on demand)
+    void* d_zeros = nullptr;             // 256 zero bytes: LDS-DMA source of out-of-image halo rows (conv_click)
+    unsigned long long* d_kw_bar = nullptr;   // conv_kwave_chain_bf16's grid-barrier counter (monotone) ...
+    unsigned long long kw_bar_count = 0;      // ... grid barriers done by every launch so far (each adds its arrivals to its counter)
+    int kw_bar_blocks = 0;                    // ... workgroups per launch those counts are for (a different grid resets the counters)
+    long long* d_kw_stamps = nullptr;         // IDC_KW_STAMPS=1: per-phase cycle stamps of the last chain launch, printed when the handle is destroyed
+    int kw_stamp_layers = 0, kw_stamp_blocks = 0;
+    int* h_kw_abort = nullptr;                // pinned, device-visible: a chain workgroup that gave up waiting sets it
+    bool kw_chain_off = false;                // set after a refused / aborted chain launch: the handle falls back to one launch per layer
+    int kw_chain_fits = -1;                   // workgroups of the chain kernel this device holds at once (-1: not asked yet)
+    float *d_glob_in = nullptr, *d_glob_vec = nullptr;   // global hints: [max_batch][316] inputs, [max_batch][512] branch output
+    int t_conv4_3 = -1, t_pred313 = -1;
+    float *d_pred_ab = nullptr, *d_dist313 = nullptr, *h_pred_ab = nullptr, *h_dist313 = nullptr;   // 313 head outputs
+    float dist_S = 0.2f;
+    unsigned char *d_rgb = nullptr, *h_rgb = nullptr;   // colour post-processing (allocated on first use)
+    double *d_labq = nullptr, *h_labq = nullptr;
+    float* d_post_in = nullptr;          // idc_lab2rgb staging (L + ab planes): the resident L / hint planes are left alone
+    bool want_dist313 = false;           // the next forward also writes the full-resolution dist_S
+    bool keep_dist313 = false;           // idc_keep_dist: every forward leaves dist_S resident (colour suggestions)
+    int dist_n = 0;                      // images whose distribution is resident from the last forward (0 = none)
+    HintRect *d_hints = nullptr, *h_hints = nullptr; int hints_cap = 0;   // click session: hint list staging
+    float* d_centres = nullptr; double* d_sugg = nullptr; unsigned* d_sugg_counts = nullptr;   // colour suggestions
+    std::vector<char> l_set;             // per image slot: d_L holds an uploaded L plane (idc_forward_resident refuses otherwise)
+    hipEvent_t ev_sync = nullptr;        // idc_stream_wait / idc_stream_signal
+    // two-slot transfer pipeline (idc_forward_async / idc_wait): each slot owns its device planes
+    struct PipeSlot {
+        float *d_L = nullptr, *d_ab = nullptr, *d_mask = nullptr, *d_out = nullptr;   // device I/O planes
+        float *h_in = nullptr, *h_out = nullptr;                                       // pinned staging (pageable callers)
+        hipEvent_t ev_in = nullptr, ev_comp = nullptr, ev_out = nullptr;
+        hipEvent_t ev_in0 = nullptr, ev_comp0 = nullptr, ev_out0 = nullptr;             // stage starts (idc_pipeline_times)
+        bool pending = false, staged_out = false, timed = false;
+        float* user_out = nullptr; int n = 0;
+    } pipe[2];
+    hipStream_t s_in = nullptr, s_out = nullptr;
+    hipEvent_t ev_pipe_base = nullptr;
+    bool pipe_ready = false;
+    unsigned char* d_up_rgb = nullptr; double* d_up_L = nullptr; size_t up_cap = 0;    // idc_upsample_lab2rgb staging
+    unsigned char* h_up_rgb = nullptr; double* h_up_L = nullptr;
+    bool out_copy_pending = false;       // forward_host(finish = false): the ab map still has to be copied from h_out to the caller
+    bool out_resident = false;           // d_out / d_labq hold the last forward's ab map / refreshed Lab
+    bool labq_resident = false;
+    int profiling = 0;                   // 0 off, 1 = an event pair around every launch, 2 = one pair around the whole forward
+    void* d_arena = nullptr;             // all activation tensors (alloc_graph), or nullptr with IDC_ARENA=0
+    std::vector<hipEvent_t> ev;          // kProfRing slots x 2 per timed step: [pack, layers..., head, softmax]
+    int n_timed = 0;
+    long long prof_count = 0;            // forwards recorded since profiling was switched on
+    int last_n = 0;
+    // range audit (idc_set_range_audit): one sticky AuditRecord per row of the layer table in device memory, the value counts on the host
+    bool audit = false;
+    AuditRecord* d_audit = nullptr;
+    std::vector<unsigned long long> audit_values;
+    // from the blob in use (cache_blob_meta): the activation exponent of each active layer's output and its accumulator-scale word
+    std::vector<int> act_exp;
+    std::vector<float> wscale;
+};
+
+#define HIPCHK(ctx, expr)                                                                                  \
+    do {                                                                                                   \
+        hipError_t e_ = (expr);                                                                            \
+        if (e_ != hipSuccess) (void)hipGetLastError();   /* reported through our own status: do not leave it sticky for the caller's runtime */ \
+        if (e_ != hipSuccess)                                                                              \
+            return fail((ctx) ? &(ctx)->err : nullptr, IDC_ERR_HIP, "%s failed: %s (%s:%d)", #expr,        \
+                        hipGetErrorString(e_), __FILE__, __LINE__);                                        \
+    } while (0)
+
+namespace idc {
+
+static constexpr int kProfRing = 32;    // per-layer event pairs are kept for the last 32 forwards
+
+// idc_api.hip (which also owns the thread-local last-error string: fail() writes it, idc_last_error() reads it)
+int fail(std::string* err, int code, const char* fmt, ...);
+int check_device(int device_id, std::string* err);
+int ensure_post_buffers(idc_context* h);
+int run_lab_post(idc_context* h, int n, const float* d_Lp, float l_add, const float* d_abp, uint8_t* rgb, double* lab_q);
+
+// idc_pack.hip (make_blob_plan: idc_net.h)
+int f16_weight_exponent(const float* w, size_t n);
+void pack_layer_weights(uint8_t* wimg, int precision, int layout, const LayerSpec& s, const LayerBlob& lb, const float* w, int part = 0, float wmul = 1.f);
+void pack_wino_weights(uint8_t* img, int precision, const LayerSpec& s, const LayerBlob& lb, const float* w);
+void pack_wino_deconv_weights(uint8_t* img, int precision, const LayerSpec& s, const LayerBlob& lb, const float* w);
+int verify_device_blob(idc_context* h, const void* dev_blob, size_t blob_bytes);
+
+// idc_plan.hip
+int find_tensor(idc_context* c, const char* name);
+bool fuse_shortcut_enabled();
+void fill_taps(Layer& L);
+void set_geometry(Layer& L, int precision, int n, int n_policy, int Hs, int Ws, bool allow_v2 = true);
+Kernel choose_kernel(const Layer& L, int precision, int max_batch);
+hipError_t launch_kernel(Kernel k, const Layer& L, const ConvArgs& a, hipStream_t s);
+void kernel_label(const Layer& L, int precision, char* out, size_t cap);
+int build_graph(idc_context* c);
+int alloc_graph(idc_context* c);
+
+// idc_exec.hip
+int run_graph(idc_context* c, int n, const float* dL, const float* dab, const float* dmask, float maskcent, float* dout, float* ddist);
+int check_chain_abort(idc_context* c);
+int check_forward_args(idc_context* c, int n);
+hipError_t wait_stream(idc_context* c, int n);
+hipError_t copy_h2d_or_d2h(idc_context* c, void* dev, void* host, size_t bytes, bool to_device);
+bool is_pinned(const void* p);
+int drain_pipeline(idc_context* c);
+
+}  // namespace idc

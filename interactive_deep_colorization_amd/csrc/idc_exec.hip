@@ -1,0 +1,655 @@
+// idc_exec.hip -- the executor: one forward of the planned graph on the handle's stream (run_graph, the persistent kwave chain), the host-pointer
+// forward with its transfers, the two-slot transfer pipeline, and the forward entry points of the C ABI (include/ideepcolor.h).
+// Replaces: SIGGRAPHGenerator.forward (models/pytorch/model.py:6-175).
+#include <stdint.h>
+#include <string.h>
+
+#include "idc_engine.h"
+
+namespace idc {
+
+// The run of same-shape 8-chunk conv_kwave_bf16 layers that starts at layer li (conv4_2 .. conv7_3 at batch 1) as ONE persistent
+// conv_kwave_chain_bf16 launch, where the handle and the device allow it: on success L.chain_len > 0 and *chain_until = the run's last
+// layer; otherwise nothing is launched and the caller launches layer li alone.
+static int launch_kwave_chain(idc_context* c, int li, hipStream_t s, int* chain_until) {
+    Layer& L = c->layers[li];
+    const ConvArgs& a = L.args;
+    if (!options().kwave_chain || c->kw_chain_off || c->profiling == 1 || !c->d_kw_bar || L.spec->kind != kConv3x3 || a.nkc != 8 || a.si != 1 ||
+        a.img_shift != nullptr || a.out_f32)
+        return IDC_OK;
+    const int blocks = conv_kwave_chain_blocks(a.Hs, a.Ws, a.N, a.ncg, a.dy[8]);
+    KwChainArgs ch{};
+    ch.H = a.Hs; ch.W = a.Ws; ch.N = a.N; ch.ncg = a.ncg;
+    ch.spin_limit = 200000u;                   // x ~1.5 us per poll: a third of a second, then the workgroup gives up
+    int last = li, prev_dst = L.src;
+    for (int j = li; j < (int)c->layers.size() && ch.nlayers < kKwChainMax; ++j) {
+        Layer& Q = c->layers[j];
+        const bool shifted = (c->flags & IDC_FLAG_GLOBAL_HINTS) && Q.dst == c->t_conv4_3;
+        if (Q.kernel != kConvKwave || Q.spec->kind != kConv3x3 || Q.blob.nkc != 8 || Q.spec->in_stride != 1 || Q.resid >= 0 || shifted ||
+            c->tensors[Q.dst].is_f32 || Q.src != prev_dst || Q.args.Hs != a.Hs || Q.args.Ws != a.Ws || Q.args.ncg != a.ncg ||
+            conv_kwave_chain_blocks(a.Hs, a.Ws, a.N, a.ncg, Q.args.dy[8]) != blocks)
+            break;
+        KwChainLayer& y = ch.layer[ch.nlayers++];
+        y.in = c->tensors[Q.src].ptr; y.out = c->tensors[Q.dst].ptr;
+        y.wgt = c->d_blob + Q.blob.w_off;
+        y.bias = (const float*)(c->d_blob + Q.blob.bias_off);
+        y.bn_scale = Q.blob.bn_scale_off != (size_t)-1 ? (const float*)(c->d_blob + Q.blob.bn_scale_off) : nullptr;
+        y.bn_shift = Q.blob.bn_shift_off != (size_t)-1 ? (const float*)(c->d_blob + Q.blob.bn_shift_off) : nullptr;
+        y.act = Q.spec->act; y.d = Q.args.dy[8];
+        prev_dst = Q.dst; last = j;
+    }
+    if (ch.nlayers < 2 || blocks <= 0) return IDC_OK;
+    if (c->kw_chain_fits < 0) c->kw_chain_fits = conv_kwave_chain_capacity(c->device);
+    if (c->kw_chain_fits < blocks) return IDC_OK;   // more workgroups than the chip holds at once: this launch goes layer by layer
+    if (blocks != c->kw_bar_blocks) {      // counters hold (barriers so far) x (arrivals per barrier of THIS grid)
+        HIPCHK(c, hipMemsetAsync(c->d_kw_bar, 0, 1024, s));
+        c->kw_bar_count = 0; c->kw_bar_blocks = blocks;
+    }
+    ch.bar = c->d_kw_bar; ch.bar_base = c->kw_bar_count; ch.abort_flag = c->h_kw_abort;
+    // test hook (tests/test_round5_gpu.py): IDC_KW_FORCE_ABORT=1 makes the first grid barrier unreachable and the give-up
+    // counter tiny, i.e. it plays "the workgroups never become co-resident" on a healthy device
+    if (options().kw_force_abort) { ch.bar_base += 1000; ch.spin_limit = 20u; }
+    static const bool want_stamps = idc_env_int("IDC_KW_STAMPS", 0) != 0;
+    if (want_stamps && !c->d_kw_stamps) HIPCHK(c, hipMalloc((void**)&c->d_kw_stamps, (size_t)4096 * kKwChainMax * 8 * 8));
+    ch.stamps = (want_stamps && blocks <= 4096) ? c->d_kw_stamps : nullptr;
+    c->kw_stamp_layers = ch.nlayers; c->kw_stamp_blocks = blocks;
+    if (launch_conv_kwave_chain(ch, blocks, options().kwave_chain, s) != hipSuccess) {
+        (void)hipGetLastError();          // refused (e.g. hipErrorCooperativeLaunchTooLarge): one launch per layer from now on
+        c->kw_chain_off = true;
+        return IDC_OK;
+    }
+    c->kw_bar_count += (unsigned long long)(ch.nlayers - 1);
+    L.chain_len = ch.nlayers;
+    for (int j = li + 1; j <= last; ++j) c->layers[j].chained_into = li;
+    *chain_until = last;
+    return IDC_OK;
+}
+
+int run_graph(idc_context* c, int n, const float* dL, const float* dab, const float* dmask, float maskcent,
+                     float* dout, float* ddist) {
+    const Options& o = options();
+    hipStream_t s = c->stream;
+    int step = 0;
+    {   // a workgroup of an EARLIER conv_kwave_chain_bf16 launch gave up at its grid barrier and nobody has waited on that forward since
+        const int arc = check_chain_abort(c);
+        if (arc) return arc;
+    }
+    const size_t ring = (size_t)(c->prof_count % kProfRing) * c->n_timed * 2;
+    auto tic = [&]() { if (c->profiling == 1) (void)hipEventRecord(c->ev[ring + step * 2], s); };
+    auto toc = [&]() { if (c->profiling == 1) (void)hipEventRecord(c->ev[ring + step * 2 + 1], s); ++step; };
+    // range audit: the stored output of layer index lj, folded into its record right behind the launch that wrote it (outside the event pairs)
+    auto audit_layer = [&](int lj) -> hipError_t {
+        const Layer& Q = c->layers[lj];
+        const Tensor& t = c->tensors[Q.dst];
+        const int parts = t.is_f32 ? 0 : t.parts;
+        c->audit_values[lj + 1] += (unsigned long long)n * t.C * t.H * t.W;
+        return launch_range_audit(t.ptr, (long long)n * t.H * t.W, t.C, t.Cpad, parts, split_is_f16(c->precision) ? 1 : 0, c->d_audit + lj + 1, s);
+    };
+    if (c->profiling == 2) (void)hipEventRecord(c->ev[ring], s);          // whole-forward pair: slot 0
+    tic();   // (slot 0: the input pack is fused into conv1_1's operand staging; only the global-hints branch runs here)
+    if (c->flags & IDC_FLAG_GLOBAL_HINTS)      // four GEMVs per image; its output is consumed by conv4_3's epilogue
+        HIPCHK(c, launch_glob_branch(c->d_glob_in, (const float*)(c->d_blob + c->plan.glob_off), c->d_glob_vec, n, s));
+    toc();
+    // pass 1: tile family per layer, then which shortcut convs ride in their consumer's launch
+    for (auto& L : c->layers) {
+        const Tensor& ti = c->tensors[L.src];
+        const Tensor& to = c->tensors[L.dst];
+        const int Hs = L.spec->kind == kDeconv4x4 ? ti.H : to.H;
+        const int Ws = L.spec->kind == kDeconv4x4 ? ti.W : to.W;
+        set_geometry(L, L.lprec, n, c->max_batch, Hs, Ws);
+        L.fused_short = -1; L.fused_next = -1;
+    }
+    // model1 in one launch: conv1_1 (input pack fused) followed by conv1_2 on the small-tile bf16 path, >= 128 big tiles
+    for (size_t i = 0; i + 1 < c->layers.size(); ++i) {
+        Layer& L = c->layers[i];
+        const bool f16blk = c->precision == IDC_FP16 && o.fp16_fast && L.blob.w2_off != (size_t)-1;      // IDC_FP16: conv1_block_fused_th
+        if (L.spec->kind != kConvIm2col || (c->precision != IDC_BF16 && !f16blk) || !o.fuse_conv1 || L.spec->act != 1 || L.spec->bnkey) continue;
+        // 32x32 tiles when there are >= 128 of them (N = 32); else the 32x8 tile (conv1_block_fused_t<4,2>) when THAT gives >= 128
+        // workgroups -- the batch-1 click path: one launch instead of conv1_1 + conv1_2 and no 8 MB intermediate
+        const long long t32 = (long long)((c->W + 31) / 32) * ((c->H + 31) / 32) * c->max_batch;
+        const long long t8 = (long long)((c->W + 31) / 32) * ((c->H + 7) / 8) * c->max_batch;
+        if (t32 < 128 && t8 < 128) continue;
+        const int tile_req = t32 >= 128 ? 32 : 8;              // tile height request of launch_conv1_block
+        for (size_t j = 0; j < c->layers.size(); ++j) {
+            Layer& P = c->layers[j];
+            const LayerSpec& ps = *P.spec;
+            if (P.src != L.dst || (P.kernel == kConvV2 && !f16blk) || ps.kind != kConv3x3 || ps.cin != 64 || ps.cout != 64 || ps.dilation != 1 ||
+                ps.in_stride != 1 || ps.act != 1 || ps.resid || c->tensors[P.dst].is_f32 || P.args.ksplit > 1 || P.kernel == kConvClick ||
+                P.kernel == kConvWino) continue;
+            bool only_consumer = true;
+            for (const Layer& Q : c->layers) if (&Q != &P && (Q.src == L.dst || Q.resid == L.dst)) only_consumer = false;
+            if (only_consumer) { L.fused_next = (int)j; P.kernel = kFused; L.args.tiles_y = tile_req; }
+        }
+    }
+    for (auto& L : c->layers) {
+        if (L.spec->kind != kDeconv4x4 || L.resid < 0 || L.kernel != kConvV2 || !fuse_shortcut_enabled() || (L.split && !o.split_ds_fuse)) continue;
+        if (L.spec->cout % 128 != 0 || L.spec->bnkey || L.spec->act == 2 || c->tensors[L.dst].is_f32) continue;   // conv_ds_fused's domain
+        for (size_t j = 0; j < c->layers.size(); ++j) {
+            Layer& P = c->layers[j];
+            const LayerSpec& ps = *P.spec;
+            if (P.dst != L.resid) continue;
+            const Tensor& pin = c->tensors[P.src];
+            const Tensor& to = c->tensors[L.dst];
+            if (L.split) {      // operand-split: conv_ds_fused_ms (split tensors in and out, both of the same part count) or two launches
+                if (ps.kind == kConv3x3 && ps.dilation == 1 && ps.in_stride == 1 && ps.act == 0 && !ps.bnkey && !ps.resid && P.split &&
+                    ps.cout == L.spec->cout && pin.H == to.H && pin.W == to.W && !pin.is_f32 && pin.parts == to.parts &&
+                    c->tensors[L.src].parts == to.parts && !c->tensors[L.src].is_f32 &&
+                    conv_ds_m_fits(L.args.Hs, L.args.Ws, L.blob.nkc * to.parts, P.blob.nkc * to.parts)) {
+                    // both K loops land in ONE accumulator set with ONE accumulator scale: the packer made the two layers' words equal
+                    const size_t li = (size_t)(&L - &c->layers[0]);
+                    if (li < c->wscale.size() && j < c->wscale.size() && memcmp(&c->wscale[li], &c->wscale[j], 4) != 0)
+                        return fail(&c->err, IDC_ERR_INTERNAL, "layers %s and %s would share one launch but their accumulator scales differ (%g, %g): the blob "
+                                    "was not packed by this library's packer", L.spec->name, ps.name, (double)c->wscale[li], (double)c->wscale[j]);
+                    L.fused_short = (int)j; P.kernel = kFused;
+                }
+                continue;
+            }
+            if (ps.kind == kConv3x3 && ps.dilation == 1 && ps.in_stride == 1 && ps.act == 0 && !ps.bnkey && !ps.resid &&
+                ps.cout == L.spec->cout && pin.H == to.H && pin.W == to.W && !pin.is_f32 && (!kAbPartners || P.blob.w2_off != (size_t)-1) &&
+                (kAbPartners || (o.ds_m16 != 0 && conv_ds_m_fits(L.args.Hs, L.args.Ws, L.blob.nkc, P.blob.nkc)))) {      // (default library: conv_ds_fused_m or two launches)
+                L.fused_short = (int)j; P.kernel = kFused;
+            }
+        }
+    }
+    if (!kAbPartners)            // a large-tile deconv that keeps its shortcut SUM (not fused: images beyond 32-bit offsets) has no 16x16x32 kernel: small tile
+        for (auto& L : c->layers)
+            if (L.kernel == kConvV2 && !L.split && L.resid >= 0 && L.fused_short < 0) {
+                const Tensor& ti = c->tensors[L.src];
+                const Tensor& to = c->tensors[L.dst];
+                set_geometry(L, L.lprec, n, c->max_batch, L.spec->kind == kDeconv4x4 ? ti.H : to.H, L.spec->kind == kDeconv4x4 ? ti.W : to.W, false);
+            }
+    // diagnostic (IDC_DOUBLE_LAUNCH=1): every launch issued twice, the event pair around the SECOND -- a layer that is slow only as
+    // the first launch of its kernel after other kernels (cold instruction cache / first touch) shows its warm time here
+    static const bool double_launch = idc_env_int("IDC_DOUBLE_LAUNCH", 0) != 0;
+    bool head_done = false;
+    int chain_until = -1;                      // layers up to this index ran inside the conv_kwave_chain_bf16 launch of an earlier layer
+    for (auto& L : c->layers) {
+        const Tensor& ti = c->tensors[L.src];
+        const Tensor& to = c->tensors[L.dst];
+        const int li_ = (int)(&L - &c->layers[0]);
+        L.chain_len = 0;
+        if (li_ > chain_until) L.chained_into = -1;
+        if (L.kernel == kFused || li_ <= chain_until) { tic(); toc(); continue; }
+        // 1. bind: this forward's tensors, the layer's parameters in the blob (layout-1 weight images) and what rides in the launch
+        ConvArgs& a = L.args;
+        a.in = ti.ptr; a.out = to.ptr;
+        a.zeros = c->d_zeros;
+        a.warm = o.code_warm;
+        a.split_f16 = split_is_f16(c->precision) ? 1 : 0;
+        a.acc_scale = (L.split && a.split_f16 && L.blob.wscale_off != (size_t)-1) ? (const float*)(c->d_blob + L.blob.wscale_off) : nullptr;
+        a.out_f32 = to.is_f32;
+        a.img_shift = ((c->flags & IDC_FLAG_GLOBAL_HINTS) && L.dst == c->t_conv4_3) ? c->d_glob_vec : nullptr;
+        if (L.spec->kind == kConvIm2col) {          // model.py:139-148 input pack, fused into the operand staging
+            a.pk_L = dL; a.pk_ab = dab; a.pk_mask = dmask;
+            a.pk_ldiv = c->l_div; a.pk_abdiv = c->ab_div; a.pk_mmul = c->mask_mul; a.pk_mcent = maskcent;
+        } else {
+            a.pk_L = nullptr;
+        }
+        a.wgt = c->d_blob + L.blob.w_off;
+        a.bias = (const float*)(c->d_blob + L.blob.bias_off);
+        a.bn_scale = L.blob.bn_scale_off != (size_t)-1 ? (const float*)(c->d_blob + L.blob.bn_scale_off) : nullptr;
+        a.bn_shift = L.blob.bn_shift_off != (size_t)-1 ? (const float*)(c->d_blob + L.blob.bn_shift_off) : nullptr;
+        if (L.fused_short >= 0) {            // model8up(.) + model3short8(.) in one K loop (model.py:156,170,172)
+            const Layer& P = c->layers[L.fused_short];
+            a.resid = nullptr; a.resid_bf16 = 0;
+            a.in2 = c->tensors[P.src].ptr; a.wgt2 = c->d_blob + P.blob.w_off; a.nkc2 = P.blob.nkc;
+            a.bias = (const float*)(c->d_blob + L.blob.fbias_off);
+            if (L.split) a.w_part_bytes2 = P.blob.w_bytes;
+        } else {
+            a.resid = L.resid >= 0 ? c->tensors[L.resid].ptr : nullptr;
+            a.resid_bf16 = (L.resid >= 0 && !c->tensors[L.resid].is_f32) ? 1 : 0;
+            a.in2 = nullptr; a.wgt2 = nullptr; a.nkc2 = 0;
+        }
+        // the regression head rides in conv10_2's epilogue when one workgroup owns all 128 channels
+        L.fused_head = L.dst == c->t_conv10_2 && L.kernel == kConvV2 && L.cfg.wm == 2 && a.ncg == 2 && L.spec->bnkey == nullptr;
+        a.head_w = L.fused_head ? (const float*)(c->d_blob + c->plan.head_w_off) : nullptr;
+        a.head_b = (const float*)(c->d_blob + c->plan.head_b_off);
+        a.head_out = dout; a.head_mul = c->out_mul;
+        head_done = head_done || L.fused_head;
+        if (L.fused_next >= 0) {             // conv1_2 rides in conv1_1's launch (launch_conv1_block's argument convention)
+            const Layer& P = c->layers[L.fused_next];
+            a.wgt2 = c->d_blob + P.blob.w_off;
+            a.head_b = (const float*)(c->d_blob + P.blob.bias_off);
+            a.bn_scale = P.blob.bn_scale_off != (size_t)-1 ? (const float*)(c->d_blob + P.blob.bn_scale_off) : nullptr;
+            a.bn_shift = P.blob.bn_shift_off != (size_t)-1 ? (const float*)(c->d_blob + P.blob.bn_shift_off) : nullptr;
+            a.out = c->tensors[P.dst].ptr;
+            a.head_w = nullptr;
+        }
+        if (a.ksplit > 1) {
+            const size_t need = (size_t)a.ksplit * n * to.H * to.W * to.Cpad * 4;
+            if (c->partial_bytes < need) {
+                HIPCHK(c, hipStreamSynchronize(s));
+                if (c->d_partial) (void)hipFree(c->d_partial);
+                c->d_partial = nullptr; c->partial_bytes = 0;
+                HIPCHK(c, hipMalloc((void**)&c->d_partial, need));
+                c->partial_bytes = need;
+            }
+            a.partial = c->d_partial;
+        }
+        if (L.fused_next >= 0 && c->precision == IDC_FP16) {
+            a.wgt = c->d_blob + L.blob.w2_off;               // conv1_1's fp16 block (conv1_block_fused_th)
+            a.out_parts = 0; a.ksplit = 1; a.kc_per = a.nkc;
+        } else
+        if (is_split(c->precision) && !L.split) {        // fp32 island: conv_igemm<f32> with a split store (no split-K: its epilogue kernel writes fp32)
+            a.out_parts = to.is_f32 ? 0 : to.parts;
+            a.out_f32 = 1; a.ksplit = 1; a.kc_per = a.nkc;
+            if (L.kernel != kConvIgemm) return fail(&c->err, IDC_ERR_INTERNAL, "layer %s: fp32 island outside conv_igemm", L.spec->name);
+        }
+        if (L.split) {
+            // operand-split launch: nseg passes of the K loop (input part x weight part) into one accumulator set; split in / out tensors
+            a.in_parts = ti.parts; a.out_parts = (to.is_f32 || L.fused_head) ? 0 : to.parts;
+            a.nseg = split_segments(c->precision); a.seg_x = split_seg_x(c->precision); a.seg_w = split_seg_w(c->precision);
+            a.w_part_bytes = L.blob.w_bytes;
+        }
+        // 2. choose
+        L.kernel = choose_kernel(L, c->precision, c->max_batch);
+        // ... and the weight images it reads where they are not layout 1
+        if (L.kernel == kConvWino || L.kernel == kDeconvWino) a.wgt = c->d_blob + L.blob.w3_off;
+        if ((L.kernel == kConvV2 || L.kernel == kConvDs) && L.blob.w2_off != (size_t)-1) a.wgt = c->d_blob + L.blob.w2_off;
+        if (L.kernel == kConvDs && c->layers[L.fused_short].blob.w2_off != (size_t)-1) a.wgt2 = c->d_blob + c->layers[L.fused_short].blob.w2_off;
+        // 3. launch
+        for (int rep = double_launch ? 0 : 1; rep < 2; ++rep) {
+            if (rep == 1) tic();
+            bool chained = false;
+            if (L.kernel == kConvKwave && !double_launch) {
+                const int rc = launch_kwave_chain(c, li_, s, &chain_until);
+                if (rc) return rc;
+                chained = L.chain_len > 0;
+            }
+            const hipError_t le = chained ? hipSuccess : launch_kernel(L.kernel, L, a, s);
+            if (le == hipErrorInvalidConfiguration) {
+                char k[64]; kernel_label(L, c->precision, k, sizeof(k));
+                return fail(&c->err, IDC_ERR_INTERNAL, "layer %s: %s planned for a launch it does not cover%s", L.spec->name, k,
+                            kAbPartners ? "" : " (the default library has no conv_igemm_v2 / conv_ds_fused / conv1_1_bf16_kernel: -DIDC_AB_PARTNERS)");
+            }
+            HIPCHK(c, le);
+            if (a.ksplit > 1) HIPCHK(c, launch_splitk_epilogue(L.lprec, a, s));
+        }
+        toc();
+        if (c->audit) {
+            if (L.fused_next >= 0) HIPCHK(c, audit_layer(L.fused_next));              // model1 in one launch: conv1_2's output is what was stored
+            else if (L.chain_len > 0) { for (int j = li_; j <= chain_until; ++j) HIPCHK(c, audit_layer(j)); }
+            else if (!L.fused_head) HIPCHK(c, audit_layer(li_));                      // (conv10_2 under the fused head: never stored)
+        }
+    }
+    tic();
+    if (!head_done && is_split(c->precision))
+        return fail(&c->err, IDC_ERR_INTERNAL, "operand-split forward: the regression head did not ride in conv10_2's launch");
+    if (!head_done)
+        HIPCHK(c, launch_head(c->precision, c->tensors[c->t_conv10_2].ptr, (const float*)(c->d_blob + c->plan.head_w_off),
+                              (const float*)(c->d_blob + c->plan.head_b_off), dout, n, c->H, c->W, c->out_mul, s));
+    toc();
+    tic();
+    if (ddist) {
+        const Tensor& tl = c->tensors[c->t_logits];
+        HIPCHK(c, launch_softmax_nchw((const float*)tl.ptr, ddist, n, tl.H, tl.W, 529, tl.Cpad, 0.2f, s));
+    }
+    if (c->flags & IDC_FLAG_DIST313) {         // bilinear x4 + softmax(S.) + softmax(2.6 .) -> pred_ab decode
+        const Tensor& tp = c->tensors[c->t_pred313];
+        HIPCHK(c, launch_dist313((const float*)tp.ptr, (const float*)(c->d_blob + c->plan.pred_ab_off), c->d_pred_ab,
+                                 (c->want_dist313 || c->keep_dist313) ? c->d_dist313 : nullptr, n, c->H, c->W, tp.Cpad,
+                                 c->dist_S, 2.6f, s));
+    }
+    toc();
+    c->dist_n = (ddist || ((c->flags & IDC_FLAG_DIST313) && (c->want_dist313 || c->keep_dist313))) ? n : 0;
+    if (dout == c->d_out) c->last_n = n;       // images whose ab map sits in the handle's own d_out (display step source)
+    if (c->profiling == 2) (void)hipEventRecord(c->ev[ring + 1], s);
+    if (c->profiling) ++c->prof_count;
+    return IDC_OK;
+}
+
+// A conv_kwave_chain_bf16 workgroup that gave up at its grid barrier (not all workgroups co-resident: a partitioned or shared device) set the pinned
+// flag: the results of the forward that has just been waited for are invalid.  Called after the synchronising points of the blocking entry points.
+int check_chain_abort(idc_context* c) {
+    if (c->h_kw_abort && *c->h_kw_abort) {
+        *c->h_kw_abort = 0;
+        c->kw_chain_off = true;
+        return fail(&c->err, IDC_ERR_INTERNAL, "the persistent trunk launch (conv_kwave_chain_bf16) did not get all its workgroups co-resident and timed "
+                    "out: this forward's result is invalid; the handle now runs one launch per layer -- call again");
+    }
+    return IDC_OK;
+}
+
+int check_forward_args(idc_context* c, int n) {
+    if (!c) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (!c->weights_set) return fail(&c->err, IDC_ERR_NO_WEIGHTS, "I need to have a net! (no weights loaded)");
+    if (n <= 0 || n > c->max_batch) return fail(&c->err, IDC_ERR_BATCH, "batch %d outside 1..%d", n, c->max_batch);
+    return IDC_OK;
+}
+
+// The end of a click: hipStreamSynchronize parks the thread on an interrupt (tens of microseconds to come back, against a 0.3-1.1 ms forward); the calls
+// that serve ONE OR TWO images poll the stream instead (bounded: after ~4 ms of polling -- several forwards -- it blocks like everybody else).  Batches
+// keep the blocking wait: there the CPU is better spent elsewhere.  IDC_SPIN_SYNC=0 restores the blocking wait everywhere (A/B).
+hipError_t wait_stream(idc_context* c, int n) {
+    const bool spin = options().spin_sync != 0;
+    if (spin && n <= 2) {
+        for (int i = 0; i < 4000; ++i) {
+            const hipError_t e = hipStreamQuery(c->stream);
+            if (e != hipErrorNotReady) return e;
+#if defined(__x86_64__) || defined(__i386__)
+            for (int k = 0; k < 40; ++k) __builtin_ia32_pause();
+#else
+            for (volatile int k = 0; k < 40; ++k) {}
+#endif
+        }
+    }
+    return hipStreamSynchronize(c->stream);
+}
+
+// A click's transfers (<= 2 MiB between pinned host memory and HBM) run as a kernel on the forward's stream (pcie_copy_kernel, idc_kernels.hip) instead of
+// going to a copy engine: no cross-queue hand-over on either side of them.  `host` must be pinned (ours, or the caller's idc_alloc_host / hipHostMalloc /
+// mapped hipHostRegister memory); anything the device cannot address, bigger, or not 16-byte shaped takes hipMemcpyAsync.  IDC_PCIE_KERNEL=0: always (A/B).
+hipError_t copy_h2d_or_d2h(idc_context* c, void* dev, void* host, size_t bytes, bool to_device) {
+    const bool by_kernel = options().pcie_kernel != 0;
+    if (by_kernel && bytes <= ((size_t)2 << 20) && bytes % 16 == 0 && (((uintptr_t)dev | (uintptr_t)host) & 15) == 0) {
+        void* hv = nullptr;
+        if (hipHostGetDevicePointer(&hv, host, 0) == hipSuccess && hv)
+            return to_device ? launch_pcie_copy(dev, hv, bytes, c->stream) : launch_pcie_copy(hv, dev, bytes, c->stream);
+        (void)hipGetLastError();
+    }
+    return to_device ? hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, c->stream) : hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream);
+}
+
+// finish = false: everything is enqueued (the D2H of the ab map into h_out included) but the stream is NOT synchronised and
+// nothing is copied to out_ab -- idc_forward_rgb appends the colour step and synchronises once for both
+static int forward_host(idc_context* c, int n, const float* L_mc, const float* ab, const float* mask, float maskcent,
+                        float* out_ab, float* dist_q, bool keep_dist = false, bool finish = true, bool copy_out = true) {
+    int rc = check_forward_args(c, n);
+    if (rc) return rc;
+    if (!ab || !mask || (copy_out && !out_ab)) return fail(&c->err, IDC_ERR_INVALID_ARG, "null tensor pointer");
+    if (!L_mc) {                             // L_mc == NULL: the L planes idc_set_image_l left in the handle (constant between the clicks on one image)
+        if (copy_out) return fail(&c->err, IDC_ERR_INVALID_ARG, "null tensor pointer");      // (only idc_forward_rgb_lazy offers this form)
+        for (int i = 0; i < n; ++i)
+            if (!c->l_set[i]) return fail(&c->err, IDC_ERR_INVALID_ARG, "L_mc is NULL and image %d has no resident L plane (idc_set_image_l)", i);
+    }
+    if ((dist_q || keep_dist) && !(c->flags & IDC_FLAG_DIST_HEAD))
+        return fail(&c->err, IDC_ERR_UNSUPPORTED, "handle was created without IDC_FLAG_DIST_HEAD");
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = drain_pipeline(c);
+    if (rc) return rc;
+    const size_t hw = (size_t)c->H * c->W;
+    if (L_mc) for (int i = 0; i < n; ++i) c->l_set[i] = 1;
+    c->out_resident = true; c->labq_resident = false;
+    // Pinned caller buffers (idc_alloc_host / hipHostMalloc / hipHostRegister) are transferred in place; pageable ones go through
+    // the handle's pinned staging with a host memcpy (2.2 MB per click through the reference API: most of its host-side time).
+    // Staged in pieces (>= 256 KiB, at most four per tensor), each piece's DMA issued as soon as it is in the staging buffer: the copy engine moves piece k
+    // while the CPU copies piece k + 1, so a click pays the host memcpy plus ONE piece of DMA instead of memcpy + all of it.
+    float* hL = c->h_in; float* hab = hL + (size_t)n * hw; float* hm = hab + (size_t)n * hw * 2;
+    auto upload = [&](void* dst, const float* src, float* staging, size_t bytes) -> hipError_t {
+        if (is_pinned(src)) return copy_h2d_or_d2h(c, dst, (void*)src, bytes, true);
+        size_t piece = (bytes + 3) / 4;
+        if (piece < (size_t)256 * 1024) piece = (size_t)256 * 1024;
+        piece = (piece + 4095) & ~(size_t)4095;
+        for (size_t o = 0; o < bytes; o += piece) {
+            const size_t m = bytes - o < piece ? bytes - o : piece;
+            memcpy((char*)staging + o, (const char*)src + o, m);
+            const hipError_t e = copy_h2d_or_d2h(c, (char*)dst + o, (char*)staging + o, m, true);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    };
+    if (L_mc) HIPCHK(c, upload(c->d_L, L_mc, hL, (size_t)n * hw * 4));
+    HIPCHK(c, upload(c->d_ab, ab, hab, (size_t)n * hw * 2 * 4));
+    HIPCHK(c, upload(c->d_mask, mask, hm, (size_t)n * hw * 4));
+    rc = run_graph(c, n, c->d_L, c->d_ab, c->d_mask, maskcent, c->d_out, (dist_q || keep_dist) ? c->d_dist : nullptr);
+    if (rc) return rc;
+    const bool out_direct = copy_out && out_ab != c->h_out && is_pinned(out_ab);
+    c->out_copy_pending = copy_out && out_ab != c->h_out && !out_direct;
+    if (copy_out)          // (copy_out = false: the ab map stays in d_out -- idc_fetch_outputs brings it over when somebody asks)
+        HIPCHK(c, copy_h2d_or_d2h(c, c->d_out, out_direct ? out_ab : c->h_out, (size_t)n * hw * 2 * 4, false));
+    const size_t dq = (size_t)n * 529 * (hw / 16) * 4;
+    if (dist_q) HIPCHK(c, hipMemcpyAsync(c->h_dist, c->d_dist, dq, hipMemcpyDeviceToHost, c->stream));
+    if (!finish) return IDC_OK;
+    HIPCHK(c, wait_stream(c, n));
+    rc = check_chain_abort(c);
+    if (rc) return rc;
+    if (c->out_copy_pending) memcpy(out_ab, c->h_out, (size_t)n * hw * 2 * 4);
+    c->out_copy_pending = false;
+    if (dist_q) memcpy(dist_q, c->h_dist, dq);
+    return IDC_OK;
+}
+
+bool is_pinned(const void* p) {
+    hipPointerAttribute_t at;
+    const hipError_t e = hipPointerGetAttributes(&at, p);
+    (void)hipGetLastError();                      // pageable memory is "invalid value" to this query: not an error of ours, never sticky
+    return e == hipSuccess && at.type == hipMemoryTypeHost;
+}
+
+static int ensure_pipeline(idc_context* h) {
+    if (h->pipe_ready) return IDC_OK;
+    const size_t hw = (size_t)h->H * h->W, nb = (size_t)h->max_batch;
+    HIPCHK(h, hipStreamCreateWithFlags(&h->s_in, hipStreamNonBlocking));
+    HIPCHK(h, hipStreamCreateWithFlags(&h->s_out, hipStreamNonBlocking));
+    for (int k = 0; k < 2; ++k) {
+        auto& sl = h->pipe[k];
+        // both slots own their planes (50 MB each at N = 32): nothing here aliases the handle's resident L / hint / output
+        // planes, so the copy-in stream never has to be ordered against the compute stream (ordering slot 0's copies behind
+        // "everything enqueued so far" serialises them behind the OTHER slot's kernels: measured 0.89 instead of 0.97 of
+        // the device-resident rate, profiles/r03a_bench.json)
+        HIPCHK(h, hipMalloc((void**)&sl.d_L, nb * hw * 4));
+        HIPCHK(h, hipMalloc((void**)&sl.d_ab, nb * hw * 2 * 4));
+        HIPCHK(h, hipMalloc((void**)&sl.d_mask, nb * hw * 4));
+        HIPCHK(h, hipMalloc((void**)&sl.d_out, nb * hw * 2 * 4));
+        // timing-capable events: idc_pipeline_times reports where each stage of a batch sat on the device's clock
+        hipEvent_t* evs[] = {&sl.ev_in, &sl.ev_comp, &sl.ev_out, &sl.ev_in0, &sl.ev_comp0, &sl.ev_out0};
+        for (hipEvent_t* e : evs) HIPCHK(h, hipEventCreate(e));
+    }
+    HIPCHK(h, hipEventCreate(&h->ev_pipe_base));
+    HIPCHK(h, hipEventRecord(h->ev_pipe_base, h->stream));
+    h->pipe_ready = true;
+    return IDC_OK;
+}
+
+static int wait_slot(idc_context* h, int slot) {
+    auto& sl = h->pipe[slot];
+    if (!sl.pending) return IDC_OK;
+    HIPCHK(h, hipEventSynchronize(sl.ev_out));
+    sl.pending = false;
+    const int arc = check_chain_abort(h);      // the forward this slot carried ran a chain launch that gave up: its result is invalid
+    if (arc) return arc;
+    if (sl.staged_out) memcpy(sl.user_out, sl.h_out, (size_t)sl.n * h->H * h->W * 2 * 4);
+    return IDC_OK;
+}
+
+int drain_pipeline(idc_context* c) {
+    if (!c->pipe_ready) return IDC_OK;
+    for (int k = 0; k < 2; ++k) { int rc = wait_slot(c, k); if (rc) return rc; }
+    return IDC_OK;
+}
+
+}  // namespace idc
+
+extern "C" {
+
+int idc_forward(idc_handle h, int n, const float* L_mc, const float* ab, const float* mask, float maskcent,
+                float* out_ab) {
+    return forward_host(h, n, L_mc, ab, mask, maskcent, out_ab, nullptr);
+}
+
+int idc_forward_dist(idc_handle h, int n, const float* L_mc, const float* ab, const float* mask, float maskcent,
+                     float* out_ab, float* dist_q) {
+    return forward_host(h, n, L_mc, ab, mask, maskcent, out_ab, dist_q, /*keep_dist=*/true);   // NULL dist_q: resident only
+}
+
+int idc_forward_device(idc_handle h, int n, const float* d_L_mc, const float* d_ab, const float* d_mask, float maskcent,
+                       float* d_out_ab, int sync) {
+    int rc = check_forward_args(h, n);
+    if (rc) return rc;
+    if (!d_L_mc || !d_ab || !d_mask || !d_out_ab) return fail(&h->err, IDC_ERR_INVALID_ARG, "null tensor pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    // the result lands in the CALLER's buffer: whatever an earlier forward left in d_out / d_labq is no longer "the last
+    // forward's map" (idc_upsample_lab2rgb must not serve it), unless the caller handed the handle's own planes back
+    h->out_resident = d_out_ab == h->d_out;
+    h->labq_resident = false;
+    rc = run_graph(h, n, d_L_mc, d_ab, d_mask, maskcent, d_out_ab, (h->flags & IDC_FLAG_DIST_HEAD) ? h->d_dist : nullptr);
+    if (rc) return rc;
+    if (sync) {
+        HIPCHK(h, wait_stream(h, n));
+        return check_chain_abort(h);           // (every blocking wait that follows run_graph reports a timed-out chain launch itself)
+    }
+    return IDC_OK;
+}
+
+int idc_forward_dist313(idc_handle h, int n, const float* L_mc, const float* ab, const float* mask, float maskcent,
+                        float* out_ab, float* pred_ab, float* dist_S) {
+    int rc = check_forward_args(h, n);
+    if (rc) return rc;
+    if (!(h->flags & IDC_FLAG_DIST313)) return fail(&h->err, IDC_ERR_UNSUPPORTED, "handle was created without IDC_FLAG_DIST313");
+    if (!pred_ab) return fail(&h->err, IDC_ERR_INVALID_ARG, "null pred_ab");
+    const size_t hw = (size_t)h->H * h->W;
+    h->want_dist313 = dist_S != nullptr;
+    rc = forward_host(h, n, L_mc, ab, mask, maskcent, out_ab ? out_ab : h->h_out, nullptr);
+    h->want_dist313 = false;
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpy(pred_ab, h->d_pred_ab, (size_t)n * hw * 2 * 4, hipMemcpyDeviceToHost));
+    if (dist_S) HIPCHK(h, hipMemcpy(dist_S, h->d_dist313, (size_t)n * hw * 313 * 4, hipMemcpyDeviceToHost));
+    return IDC_OK;
+}
+
+int idc_forward_rgb(idc_handle h, int n, const float* L_mc, const float* ab, const float* mask, float maskcent,
+                    float l_cent, float* out_ab, uint8_t* rgb, double* lab_q) {
+    int rc = check_forward_args(h, n);
+    if (rc) return rc;
+    if (!rgb) return fail(&h->err, IDC_ERR_INVALID_ARG, "null rgb");
+    rc = ensure_post_buffers(h);
+    if (rc) return rc;
+    // forward (leaves L_mc in d_L and the ab map in d_out), then the colour step on the same stream: ONE synchronisation for
+    // both (the ab map travels to the host under the colour kernel instead of behind a sync of its own)
+    rc = forward_host(h, n, L_mc, ab, mask, maskcent, out_ab ? out_ab : h->h_out, nullptr, false, /*finish=*/false);
+    if (rc) return rc;
+    rc = run_lab_post(h, n, h->d_L, l_cent, h->d_out, rgb, lab_q);          // synchronises the stream
+    if (rc == IDC_OK && out_ab && h->out_copy_pending) memcpy(out_ab, h->h_out, (size_t)n * h->H * h->W * 2 * 4);
+    h->out_copy_pending = false;
+    h->labq_resident = rc == IDC_OK && lab_q != nullptr;
+    return rc;
+}
+
+// The click as the reference API needs it on the critical path: the colourised image.  The ab map and the refreshed Lab (2.0 MB of
+// the 2.2 MB idc_forward_rgb sends back per 256x256 click) stay on the device until idc_fetch_outputs asks for them.
+int idc_forward_rgb_lazy(idc_handle h, int n, const float* L_mc, const float* ab, const float* mask, float maskcent, float l_cent, uint8_t* rgb) {
+    int rc = check_forward_args(h, n);
+    if (rc) return rc;
+    if (!rgb) return fail(&h->err, IDC_ERR_INVALID_ARG, "null rgb");
+    rc = ensure_post_buffers(h);
+    if (rc) return rc;
+    rc = forward_host(h, n, L_mc, ab, mask, maskcent, nullptr, nullptr, false, /*finish=*/false, /*copy_out=*/false);
+    if (rc) return rc;
+    const size_t hw = (size_t)h->H * h->W;
+    HIPCHK(h, launch_lab_post(h->d_L, l_cent, h->d_out, h->d_rgb, h->d_labq, n, h->H, h->W, h->stream));
+    const bool rgb_direct = is_pinned(rgb);
+    HIPCHK(h, copy_h2d_or_d2h(h, h->d_rgb, rgb_direct ? (void*)rgb : (void*)h->h_rgb, (size_t)n * hw * 3, false));
+    HIPCHK(h, wait_stream(h, n));
+    rc = check_chain_abort(h);
+    if (rc) return rc;
+    if (!rgb_direct) memcpy(rgb, h->h_rgb, (size_t)n * hw * 3);
+    h->out_copy_pending = false;
+    h->labq_resident = true;
+    return IDC_OK;
+}
+
+int idc_fetch_outputs(idc_handle h, int n, float* out_ab, double* lab_q) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (n <= 0 || n > h->max_batch) return fail(&h->err, IDC_ERR_BATCH, "batch %d outside 1..%d", n, h->max_batch);
+    if (n > h->last_n) return fail(&h->err, IDC_ERR_UNSUPPORTED, "only %d image(s) of the last forward are resident", h->last_n);
+    if (out_ab && !h->out_resident) return fail(&h->err, IDC_ERR_UNSUPPORTED, "no forward result is resident");
+    if (lab_q && !h->labq_resident) return fail(&h->err, IDC_ERR_UNSUPPORTED, "no refreshed Lab is resident (run idc_forward_rgb_lazy / idc_forward_rgb with lab_q first)");
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t hw = (size_t)h->H * h->W;
+    const bool ab_direct = out_ab && is_pinned(out_ab), lab_direct = lab_q && is_pinned(lab_q);
+    if (out_ab) HIPCHK(h, copy_h2d_or_d2h(h, h->d_out, ab_direct ? out_ab : h->h_out, (size_t)n * hw * 2 * 4, false));
+    if (lab_q) {
+        int rc = ensure_post_buffers(h);
+        if (rc) return rc;
+        HIPCHK(h, copy_h2d_or_d2h(h, h->d_labq, lab_direct ? (void*)lab_q : (void*)h->h_labq, (size_t)n * hw * 3 * 8, false));
+    }
+    HIPCHK(h, wait_stream(h, n));
+    if (out_ab && !ab_direct) memcpy(out_ab, h->h_out, (size_t)n * hw * 2 * 4);
+    if (lab_q && !lab_direct) memcpy(lab_q, h->h_labq, (size_t)n * hw * 3 * 8);
+    return IDC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- transfer pipeline
+// End-to-end batches: two slots, three streams.  Slot k's H2D copies run on the copy-in
+// stream while the other slot computes; its D2H runs on the copy-out stream while the next batch computes.  Callers that
+// pass pinned host memory (idc_alloc_host, or their own hipHostMalloc / hipHostRegister) are copied from / to directly;
+// pageable pointers go through the slot's pinned staging with a host memcpy on the calling thread.
+void* idc_alloc_host(size_t bytes) {
+    void* p = nullptr;
+    if (hipHostMalloc(&p, bytes ? bytes : 16, hipHostMallocDefault) != hipSuccess) return nullptr;
+    return p;
+}
+
+int idc_free_host(void* p) {
+    if (!p) return IDC_OK;
+    return hipHostFree(p) == hipSuccess ? IDC_OK : fail(nullptr, IDC_ERR_HIP, "hipHostFree failed");
+}
+
+int idc_forward_async(idc_handle h, int slot, int n, const float* L_mc, const float* ab, const float* mask, float maskcent,
+                      float* out_ab) {
+    int rc = check_forward_args(h, n);
+    if (rc) return rc;
+    if (slot < 0 || slot > 1) return fail(&h->err, IDC_ERR_INVALID_ARG, "slot %d not in 0..1", slot);
+    if (!L_mc || !ab || !mask || !out_ab) return fail(&h->err, IDC_ERR_INVALID_ARG, "null tensor pointer");
+    if (h->audit) return fail(&h->err, IDC_ERR_UNSUPPORTED, "the range audit covers the blocking, resident and device-pointer forwards, not the pipelined slots");
+    HIPCHK(h, hipSetDevice(h->device));
+    rc = ensure_pipeline(h);
+    if (rc) return rc;
+    auto& sl = h->pipe[slot];
+    if (sl.pending) return fail(&h->err, IDC_ERR_INVALID_ARG, "slot %d is still in flight: idc_wait it first", slot);
+    const size_t hw = (size_t)h->H * h->W, nb = (size_t)h->max_batch;
+    const float *sL = L_mc, *sab = ab, *sm = mask;
+    if (!(is_pinned(L_mc) && is_pinned(ab) && is_pinned(mask))) {
+        if (!sl.h_in) HIPCHK(h, hipHostMalloc((void**)&sl.h_in, nb * hw * 4 * 4, hipHostMallocDefault));
+        float* hL = sl.h_in; float* hab = hL + (size_t)n * hw; float* hm = hab + (size_t)n * hw * 2;
+        memcpy(hL, L_mc, (size_t)n * hw * 4); memcpy(hab, ab, (size_t)n * hw * 2 * 4); memcpy(hm, mask, (size_t)n * hw * 4);
+        sL = hL; sab = hab; sm = hm;
+    }
+    sl.staged_out = !is_pinned(out_ab);
+    if (sl.staged_out && !sl.h_out) HIPCHK(h, hipHostMalloc((void**)&sl.h_out, nb * hw * 2 * 4, hipHostMallocDefault));
+    // copy-in stream: the slot's previous inputs were consumed (its previous forward finished: idc_wait was called)
+    HIPCHK(h, hipEventRecord(sl.ev_in0, h->s_in));
+    HIPCHK(h, hipMemcpyAsync(sl.d_L, sL, (size_t)n * hw * 4, hipMemcpyHostToDevice, h->s_in));
+    HIPCHK(h, hipMemcpyAsync(sl.d_ab, sab, (size_t)n * hw * 2 * 4, hipMemcpyHostToDevice, h->s_in));
+    HIPCHK(h, hipMemcpyAsync(sl.d_mask, sm, (size_t)n * hw * 4, hipMemcpyHostToDevice, h->s_in));
+    HIPCHK(h, hipEventRecord(sl.ev_in, h->s_in));
+    HIPCHK(h, hipStreamWaitEvent(h->stream, sl.ev_in, 0));
+    HIPCHK(h, hipEventRecord(sl.ev_comp0, h->stream));
+    rc = run_graph(h, n, sl.d_L, sl.d_ab, sl.d_mask, maskcent, sl.d_out, nullptr);
+    if (rc) return rc;
+    HIPCHK(h, hipEventRecord(sl.ev_comp, h->stream));
+    HIPCHK(h, hipStreamWaitEvent(h->s_out, sl.ev_comp, 0));
+    HIPCHK(h, hipEventRecord(sl.ev_out0, h->s_out));
+    HIPCHK(h, hipMemcpyAsync(sl.staged_out ? sl.h_out : out_ab, sl.d_out, (size_t)n * hw * 2 * 4, hipMemcpyDeviceToHost, h->s_out));
+    HIPCHK(h, hipEventRecord(sl.ev_out, h->s_out));
+    sl.pending = true; sl.timed = true; sl.user_out = out_ab; sl.n = n;
+    return IDC_OK;
+}
+
+int idc_wait(idc_handle h, int slot) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (slot < 0 || slot > 1) return fail(&h->err, IDC_ERR_INVALID_ARG, "slot %d not in 0..1", slot);
+    if (!h->pipe_ready) return IDC_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    return wait_slot(h, slot);
+}
+
+int idc_pipeline_times(idc_handle h, int slot, float* ms6) {
+    if (!h || !ms6) return fail(h ? &h->err : nullptr, IDC_ERR_INVALID_ARG, "null argument");
+    if (slot < 0 || slot > 1) return fail(&h->err, IDC_ERR_INVALID_ARG, "slot %d not in 0..1", slot);
+    if (!h->pipe_ready || !h->pipe[slot].timed) return fail(&h->err, IDC_ERR_UNSUPPORTED, "slot %d has not run a batch yet", slot);
+    auto& sl = h->pipe[slot];
+    if (sl.pending) return fail(&h->err, IDC_ERR_INVALID_ARG, "slot %d is still in flight: idc_wait it first", slot);
+    HIPCHK(h, hipSetDevice(h->device));
+    hipEvent_t evs[6] = {sl.ev_in0, sl.ev_in, sl.ev_comp0, sl.ev_comp, sl.ev_out0, sl.ev_out};
+    for (int i = 0; i < 6; ++i) HIPCHK(h, hipEventElapsedTime(&ms6[i], h->ev_pipe_base, evs[i]));
+    return IDC_OK;
+}
+
+int idc_sync(idc_handle h) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return check_chain_abort(h);
+}
+
+}  // extern "C"

@@ -99,7 +99,7 @@ __device__ __forceinline__ void idc_warm_own_code(char* lds_scratch, int lane, i
 #endif
 
 // Tuning / A-B knobs read from the environment exist only in the -DIDC_AB_PARTNERS build (make EXTRA=-DIDC_AB_PARTNERS: tools/ab_*.sh, tools/click_sweep.py,
-// tools/probe_firstuse.sh); the default library reads ONE environment variable, IDC_RCCL_PATH (idc_engine.hip), and is steered through idc_set_option only.
+// tools/probe_firstuse.sh); the default library reads ONE environment variable, IDC_RCCL_PATH (idc_rccl.hip), and is steered through idc_set_option only.
 #ifdef IDC_AB_PARTNERS
 static inline int idc_env_int(const char* name, int dflt) { const char* v = getenv(name); return (v && *v) ? atoi(v) : dflt; }
 #else

@@ -1,0 +1,496 @@
+// idc_plan.hip -- the graph planner: the static schedule of the SIGGRAPHGenerator graph (build_graph, alloc_graph), the tile family and launch
+// geometry of every layer (set_geometry), the entry point it runs (choose_kernel; launch_kernel and kernel_label read that choice), and the
+// options that steer those choices (options(), idc_set_option, idc_set_tile_policy, idc_set_splitk_policy).
+#include <stdio.h>
+#include <string.h>
+
+#include "idc_engine.h"
+
+namespace idc {
+
+Options& options() { static Options o; return o; }
+
+int find_tensor(idc_context* c, const char* name) {
+    for (size_t i = 0; i < c->tensors.size(); ++i)
+        if (c->tensors[i].name == name) return (int)i;
+    return -1;
+}
+
+static bool conv1_2_split_layer(const LayerSpec& s) {
+    return s.kind == kConv3x3 && s.cin == 64 && s.cout == 64 && s.dilation == 1 && s.in_stride == 1 && s.act == 1 && !s.resid;
+}
+
+// Shortcut fusion (conv_igemm_v2<.,.,1,true>) is correct (parity-tested under tile policy 2) but measured slower
+// than two launches on MI355X (4x re-reads of the skip tensor by the four phase workgroups, VGPR spills around
+// the staged K loop): 0.87 ms -> 1.25 ms at level 1.  Off unless the tile policy forces every variant on.
+// large-tile deconv launches also run the shortcut conv they are summed with (conv_ds_fused); IDC_FUSE_SHORTCUT=0 keeps
+// the two launches apart (A/B)
+bool fuse_shortcut_enabled() {
+    static const bool off = idc_env_int("IDC_FUSE_SHORTCUT", 1) == 0;
+    return !off;
+}
+
+// Small-tile kernel shape.  cout<=64 layers can only use one 64-wide cout group per wave column;
+// otherwise prefer 128 couts x 128 pixels and fall back to smaller pixel tiles when the launch would
+// not fill the 256 CUs.
+// Tuning knobs of the small-tile path (speed only), read once from the environment: tools/click_sweep.py walks them on
+// the GPU box and the defaults below are what it found best (profiles/r02_click_sweep.txt).
+static int env_int(const char* name, int dflt) { return idc_env_int(name, dflt); }      // (defaults only, unless built with -DIDC_AB_PARTNERS)
+struct SmallTileTuning {
+    int tiles_goal = env_int("IDC_ST_TILES_GOAL", 512);         // shrink the pixel tile until this many workgroups exist
+    int force_wp = env_int("IDC_ST_FORCE_WP", 0);               // 1/2/4: fixed rows-of-4 per workgroup (0 = automatic)
+    int force_wm = env_int("IDC_ST_FORCE_WM", 0);               // 1/2: cout groups per workgroup (0 = automatic)
+    int sk_below[2] = {env_int("IDC_SK_BELOW_FP32", 256), env_int("IDC_SK_BELOW_BF16", 128)};   // split K when fewer tiles than this
+    int sk_goal[2] = {env_int("IDC_SK_GOAL_FP32", 512), env_int("IDC_SK_GOAL_BF16", 256)};      // ... until about this many workgroups
+    int v2_min_blocks = env_int("IDC_V2_MIN_BLOCKS", 128);      // large-tile bf16 kernel from this many workgroups on
+    int v2_half_tiles = env_int("IDC_V2_HALF_TILES", 1);        // 4-wave large tiles for grids of 128..255 workgroups
+    int v2_force22 = env_int("IDC_V2_FORCE22", 0);
+    int v2_22_nkc = env_int("IDC_V2_22_NKC", 2);
+    int click = env_int("IDC_CLICK", 1);                        // conv_click for small launches (the batch-1 click path)
+    int click_max_wgs = env_int("IDC_CLICK_MAX_WGS", 1024);     // ... when its grid has at most this many workgroups
+    int click_goal = env_int("IDC_CLICK_GOAL", 512);            // ... split K over the cin chunks until about this many exist (same-box A/B: 512 beats 256 by 1.5 % bf16 / 3 % fp32)
+    int click_wp = env_int("IDC_CLICK_WP", 4);                  // rows-of-4 per workgroup (4 = 16x16 sites, 256 threads)
+};
+static const SmallTileTuning& tuning() { static const SmallTileTuning t; return t; }
+
+static ConvConfig choose_config(int n, int Hs, int Ws, int coutpad, int nphase) {
+    const SmallTileTuning& tn = tuning();
+    int wm = coutpad >= 128 ? 2 : 1;
+    if (tn.force_wm && coutpad >= 64 * tn.force_wm && (coutpad / 64) % tn.force_wm == 0) wm = tn.force_wm;
+    if (tn.force_wp == 1 || tn.force_wp == 2 || tn.force_wp == 4) return ConvConfig{wm, tn.force_wp};
+    const int cand_wp[3] = {wm == 1 ? 4 : 2, 2, 1};
+    ConvConfig best{wm, cand_wp[0]};
+    for (int i = 0; i < 3; ++i) {
+        const int wp = cand_wp[i];
+        const long long tiles = (long long)((Ws + 15) / 16) * ((Hs + 4 * wp - 1) / (4 * wp)) * n * (coutpad / (64 * wm)) * nphase;
+        best = ConvConfig{wm, wp};
+        if (tiles >= tn.tiles_goal) break;
+    }
+    return best;
+}
+
+void fill_taps(Layer& L) {
+    ConvArgs& a = L.args;
+    const LayerSpec& s = *L.spec;
+    memset(a.dy, 0, sizeof(a.dy)); memset(a.dx, 0, sizeof(a.dx)); memset(a.tw, 0, sizeof(a.tw));
+    memset(a.ro, 0, sizeof(a.ro)); memset(a.co, 0, sizeof(a.co));
+    if (s.kind == kConv3x3) {
+        a.nphase = 1; a.ntaps = 9; a.so = 1; a.si = s.in_stride;
+        for (int ky = 0; ky < 3; ++ky)
+            for (int kx = 0; kx < 3; ++kx) {
+                const int t = ky * 3 + kx;
+                a.dy[t] = (ky - 1) * s.dilation; a.dx[t] = (kx - 1) * s.dilation; a.tw[t] = t;
+            }
+        L.halo = s.dilation;
+    } else if (s.kind == kDeconv4x4) {
+        // out[co,2m+r,2n+s] = b + sum over (ky,dy) in T(r), (kx,dx) in T(s) of in[m+dy,n+dx]*W[ci,co,ky,kx]
+        // T(0) = {(1,0),(3,-1)}, T(1) = {(0,+1),(2,0)}     
+        static const int T_k[2][2] = {{1, 3}, {0, 2}};
+        static const int T_d[2][2] = {{0, -1}, {1, 0}};
+        a.nphase = 4; a.ntaps = 4; a.so = 2; a.si = 1;
+        for (int r = 0; r < 2; ++r)
+            for (int c = 0; c < 2; ++c) {
+                const int ph = r * 2 + c;
+                a.ro[ph] = r; a.co[ph] = c;
+                for (int i = 0; i < 2; ++i)
+                    for (int j = 0; j < 2; ++j) {
+                        const int t = ph * 9 + i * 2 + j;
+                        a.dy[t] = T_d[r][i]; a.dx[t] = T_d[c][j];
+                        a.tw[t] = T_k[r][i] * 4 + T_k[c][j];
+                    }
+            }
+        L.halo = 1;
+    } else {
+        a.nphase = 1; a.ntaps = 1; a.so = 1; a.si = 1;
+        L.halo = 0;
+    }
+}
+
+// n_policy: the batch the kernel variant is chosen for (the handle's max_batch, so that a handle's
+// numerics do not depend on how many images a call carries); n: the batch actually launched.
+void set_geometry(Layer& L, int precision, int n, int n_policy, int Hs, int Ws, bool allow_v2) {
+    const Options& o = options();
+    ConvArgs& a = L.args;
+    a.N = n; a.Hs = Hs; a.Ws = Ws;
+    a.nkc = L.blob.nkc; a.ncg = L.blob.ncg;
+    a.act = L.spec->act;
+    a.out_f32 = L.spec->out_f32;
+    // fp32 path: every 3x3 stride-1 layer whose U image is in the blob runs as Winograd F(2x2,3x3): 2.25x fewer multiplies
+    // on the exact-fp32 matrix pipe, no split-K at batch 1 (one workgroup per 16 tiles x 32 couts)
+    bool wino = precision == IDC_FP32 && o.wino && o.tile_policy != 1 && L.blob.w3_off != (size_t)-1 &&
+             (L.spec->kind == kDeconv4x4
+                  ? (o.wino_deconv == 2 || (o.wino_deconv == 1 && a.nkc >= 8 &&
+                                            (long long)((Ws + 7) / 8) * ((Hs + 7) / 8) * n_policy * (a.ncg * 4) <= 1024))
+                  : L.spec->resid == nullptr);
+    // (deconvs: only the small launches of the click path with Cin >= 256 -- the form is transform-bound (one 16-cout block per
+    //  workgroup at the 168-register budget of its 12 waves): model10up (4 chunks) 123 us vs 96 us direct at batch 1, and at N = 32
+    //  model8up / model9up 1.30 / 1.54 ms vs 1.23 / 1.31 ms direct; "winograd_deconv" = 2 forces it everywhere for the tests)
+    const bool wino_fits = wino_offsets_fit(Hs, Ws, L.spec->kind == kDeconv4x4 ? 1 : L.spec->in_stride, a.nkc);   // 32-bit patch offsets
+    wino = wino && wino_fits;
+    if (wino) { L.kernel = L.spec->kind == kDeconv4x4 ? kDeconvWino : kConvWino; a.ksplit = 1; a.kc_per = a.nkc; a.tiles_x = a.tiles_y = 0; return; }
+    // large-tile bf16 kernel: 256 couts x (32x8 sites) when the cout groups divide by 4, else
+    // 128 couts x (32x16 sites); used when its grid covers at least half of the 256 CUs
+    const bool split = is_split(precision);      // operand-split precisions: a throughput path, the large tile on every layer whatever the grid
+    // (default library: fp32-output launches -- class_logits -- stay on the small tile: conv_igemm_v2m / v2p write bf16 only)
+    const bool v2_covers = allow_v2 && (kAbPartners || !L.spec->out_f32);
+    if (split ? !split_island(*L.spec) : (precision == IDC_BF16 && v2_eligible(*L.spec) && o.tile_policy != 1 && v2_covers)) {
+        ConvConfig c2 = (a.ncg % 4 == 0) ? ConvConfig{4, 2} : (a.ncg % 2 == 0) ? ConvConfig{2, 4} : ConvConfig{1, 4};   // ({1,*}: split precisions only, conv1_2)
+        int tx = (Ws + 31) / 32, ty = (Hs + 4 * c2.wp - 1) / (4 * c2.wp);
+        long long blocks = (long long)tx * ty * n_policy * (a.ncg / c2.wm) * a.nphase;
+        // between one half and one full wave of workgroups (batch-1 conv10_2: 128 tiles on 256 CUs): the 4-wave tile
+        // 128 couts x (32 x 8 sites) doubles the grid
+        // ... and the same 4-wave tile wherever a CU walks several tiles with a short K loop each (128-cout layers, and
+        // layers with <= v2_22_nkc cin chunks): two 4-wave workgroups share a CU (75.5 KiB of LDS each) and run out of
+        // step, so one's prologue / epilogue hides under the other's MFMAs.  Same-box A/B at N = 32 (profiles/
+        // r02_tile22_ab.txt): conv10_2 -9.5 %, conv2_1 -8..14 %, conv2_2 -6 %, conv9_2 -6..12 %, conv3_1 -22 %; the
+        // 512->512 trunk (one tile per CU, long K) is 1-2 % (dilated: 15 %) slower with it and keeps the 8-wave tile.
+        const int force22 = tuning().v2_force22;     // experiment switch: 0 = rule above, 1 = never, 2 = everywhere
+        // (the 64-cout tile of the split precisions keeps 32 x 16 sites: conv1_2 0.84 ms as {1,4}, 1.01 ms as {1,2} at N = 32, bf16x3)
+        const bool rule22 = force22 == 2 || (force22 == 0 && (c2.wm == 2 || (c2.wm == 4 && a.nkc <= tuning().v2_22_nkc)) && blocks >= 256);
+        // operand-split precisions have no batch-1 kernels: a grid that leaves most of the chip idle (fp16x3 at 1..8 images: the 512 -> 512 trunk is 8 x N
+        // workgroups of the 8-wave tile) at least takes the 4-wave 128-cout tile -- twice the workgroups, half the K-loop time each (round 6, tools/batch_sweep.py)
+        const bool split_small = split && blocks < 128;         // (at 128 workgroups -- the trunk at N = 16 -- the 8-wave tile is still the faster one: 2546 against 2475 img/s)
+        if (a.nphase == 1 && c2.wm != 1 && ((blocks >= tuning().v2_min_blocks && blocks < 256 && tuning().v2_half_tiles) || rule22 || split_small)) {
+            c2 = ConvConfig{2, 2};
+            ty = (Hs + 4 * c2.wp - 1) / (4 * c2.wp);
+            blocks = (long long)tx * ty * n_policy * (a.ncg / c2.wm) * a.nphase;
+        }
+        if (split || o.tile_policy == 2 || blocks >= tuning().v2_min_blocks) {
+            L.kernel = kConvV2; L.cfg = c2; a.tiles_x = tx; a.tiles_y = ty;
+            a.ksplit = 1; a.kc_per = a.nkc;
+            return;
+        }
+    }
+    // batch-1 click path: small launches are chains of exposed memory round trips in conv_igemm's K loop; conv_click
+    // requests a workgroup's whole K slice at entry (as many cin chunks as fit in LDS next to their halo tiles)
+    // ... "small" = fewer than v2_min_blocks big tiles (the criterion that hands a layer to the throughput kernels, applied to
+    // every precision and cout width): conv_igemm's ring loop is the better kernel once the K loop is long and the chip full
+    const int wm_big = a.ncg % 4 == 0 ? 4 : (a.ncg % 2 == 0 ? 2 : 1), rows_big = wm_big == 4 ? 8 : 16;
+    const long long big_tiles = (long long)((Ws + 31) / 32) * ((Hs + rows_big - 1) / rows_big) * n_policy * (a.ncg / wm_big) * a.nphase;
+    // bf16 click path, deconvs: the direct form with K split over the waves of a workgroup (conv_kwave_deconv_bf16, idc_kw.hip)
+    if (precision == IDC_BF16 && o.kwave && o.tile_policy != 1 && big_tiles < tuning().v2_min_blocks && wino_fits &&
+        L.spec->kind == kDeconv4x4 && (a.nkc == 2 || a.nkc == 4 || a.nkc == 8)) {
+        L.kernel = kConvKwave; a.ksplit = 1; a.kc_per = a.nkc; a.tiles_x = a.tiles_y = 0;
+        return;
+    }
+    // bf16 click path, 3x3 stride-1 layers: the direct form with K split over the waves of a workgroup (idc_kw.hip) -- 9/16 of the Winograd
+    // form's weight stream, no reduction launch either
+    if (precision == IDC_BF16 && o.kwave && o.tile_policy != 1 && big_tiles < tuning().v2_min_blocks && wino_fits && L.spec->resid == nullptr &&
+        L.spec->kind == kConv3x3 && (a.nkc == 1 || a.nkc == 2 || a.nkc == 4 || a.nkc == 8)) {
+        L.kernel = kConvKwave; a.ksplit = 1; a.kc_per = a.nkc; a.tiles_x = a.tiles_y = 0;
+        return;
+    }
+    if ((o.click < 0 ? tuning().click : o.click) && o.tile_policy != 1 && big_tiles < tuning().v2_min_blocks &&
+        (L.spec->kind == kConv3x3 || L.spec->kind == kDeconv4x4)) {
+        int wp = tuning().click_wp;
+        while (wp > 1 && 4 * wp > Hs * 2) wp >>= 1;               // tiny images: do not launch mostly-empty tiles
+        const int maxc = conv_click_max_chunks(wp, L.halo, a.ntaps);
+        const int tx = (Ws + 15) / 16, ty = (Hs + 4 * wp - 1) / (4 * wp);
+        const long long tiles = (long long)tx * ty * n_policy * a.ncg * a.nphase;
+        if (maxc >= 1) {
+            int kc_per = maxc < a.nkc ? maxc : a.nkc;                         // split-K policy "never": one workgroup walks all chunks
+            if (o.splitk_policy == 0)
+                while (kc_per > 1 && tiles * ((a.nkc + kc_per - 1) / kc_per) < tuning().click_goal) --kc_per;
+            if (o.splitk_policy == 2) kc_per = 1;
+            if (kc_per >= 1) {
+                const int ks = (a.nkc + kc_per - 1) / kc_per;
+                if (tiles * ks <= tuning().click_max_wgs) {
+                    L.kernel = kConvClick; L.cfg = ConvConfig{1, wp};
+                    a.tiles_x = tx; a.tiles_y = ty; a.kc_per = kc_per; a.ksplit = ks;
+                    return;
+                }
+            }
+        }
+    }
+    L.kernel = kConvIgemm;
+    L.cfg = choose_config(n_policy, Hs, Ws, L.blob.ncg * kCoutGroup, a.nphase);
+    a.tiles_x = (Ws + 15) / 16;
+    a.tiles_y = (Hs + 4 * L.cfg.wp - 1) / (4 * L.cfg.wp);
+    // split-K: a launch of < 256 workgroups (batch-1: 32..128) cannot fill 256 CUs and each workgroup walks all
+    // 9*Cin/64 tap-steps alone; cut the cin chunks into slices until ~512 workgroups exist
+    a.ksplit = 1; a.kc_per = a.nkc;
+    const long long tiles = (long long)a.tiles_x * a.tiles_y * n_policy * (a.ncg / L.cfg.wm) * a.nphase;
+    const int pi = precision == IDC_FP32 ? 0 : 1;
+    if (o.splitk_policy != 1 && a.nkc >= 2 && (o.splitk_policy == 2 || tiles < tuning().sk_below[pi])) {
+        // fp32 tap-steps are 16x longer than bf16 ones: worth twice as many slices (measured: 3.0 -> 2.0 ms at N=1)
+        long long want = o.splitk_policy == 2 ? a.nkc : (tuning().sk_goal[pi] + tiles - 1) / tiles;
+        if (want > a.nkc) want = a.nkc;
+        if (want >= 2) {
+            a.kc_per = (int)((a.nkc + want - 1) / want);
+            a.ksplit = (a.nkc + a.kc_per - 1) / a.kc_per;          // every slice is non-empty
+            if (a.ksplit < 2) { a.ksplit = 1; a.kc_per = a.nkc; }
+        }
+    }
+}
+
+// The entry point a layer launches this forward: set_geometry's tile family (L.kernel) refined by the fusions planned on the layer, its bound
+// arguments and the options.  An exclusive chain in precedence order; where an entry point covers only some launches, its predicate decides
+// here, so the launch that follows is never refused (a refusal is a planning bug: run_graph / run_single_op report it).
+// max_batch: the batch the variant is chosen for (as set_geometry's n_policy), so that a result never depends on how many images share a call.
+Kernel choose_kernel(const Layer& L, int precision, int max_batch) {
+    const Options& o = options();
+    const ConvArgs& a = L.args;
+    const Kernel tile = L.kernel;
+    const long long tiles32 = (long long)((a.Ws + 31) / 32) * max_batch;       // x (tile rows) = workgroups of a 32-wide tile
+    if (tile == kFused) return kFused;
+    if (L.fused_next >= 0) return kConv1Block;
+    if (L.fused_short >= 0) {
+        if (L.split)              // IDC_FP16: conv_ds_fused_mh (the bf16 kernel's fp16 twin) where it covers the launch
+            return precision == IDC_FP16 && o.fp16_fast && conv_ds_m_applies(a) ? kConvDsM : kConvDsMs;
+        return o.ds_m16 && conv_ds_m_applies(a) ? kConvDsM : kConvDs;      // (huge images: conv_ds_fused, 64-bit addressing)
+    }
+    if (L.spec->kind == kConvIm2col) {
+        // conv1_1 with >= 128 big tiles: the 32x32-tile form (the small-tile kernel keeps the batch-1 click path)
+        if (L.lprec == IDC_BF16 && a.ksplit <= 1 && tiles32 * ((a.Hs + 31) / 32) >= 128 && conv1_1_bf16_applies(a)) return kConv1_1Bf16;
+        // the fp32 island of an operand-split handle where the grid is throughput-sized
+        if (is_split(precision) && !L.split && o.conv1_1_split && tiles32 * ((a.Hs + 15) / 16) >= 128 && conv1_1_split_applies(a)) return kConv1_1Split;
+    }
+    if (L.split) {                // (every operand-split layer is planned on the large tile: set_geometry)
+        // IDC_FP16: where the bf16 forward's own kernels cover the launch, their fp16 twins (same tile, bias in the accumulators, packed-pair epilogue)
+        if (precision == IDC_FP16 && o.fp16_fast && o.v2p && conv_v2p_applies(L.cfg, L.halo, a)) return kConvV2p;
+        if (o.conv1_2_split && conv1_2_split_layer(*L.spec) && tiles32 * ((a.Hs + 11) / 12) >= 256 && conv1_2_split_applies(a)) return kConv1_2Split;
+        return o.v2p && conv_v2ps_applies(L.cfg, L.halo, a) ? kConvV2ps : kConvV2s;
+    }
+    if (tile == kConvV2 && o.mfma16 && conv_v2m_applies(a))      // the 16x16x32-MFMA builds read the layout-1 image
+        return o.v2p && conv_v2p_applies(L.cfg, L.halo, a) ? kConvV2p : kConvV2m;
+    return tile;
+}
+
+// One launch of the entry point `k` (kConvKwave: one layer; run_graph tries the persistent chain first).
+hipError_t launch_kernel(Kernel k, const Layer& L, const ConvArgs& a, hipStream_t s) {
+    switch (k) {
+        case kConvIgemm: return launch_conv(L.lprec, L.cfg, L.halo, a, s);
+        case kConvClick: return launch_conv_click(L.lprec, L.cfg.wp, L.halo, a, s);
+        case kConvWino: return launch_conv_wino(L.lprec, a, s);
+        case kDeconvWino: return launch_deconv_wino(L.lprec, a, s);
+        case kConvKwave: return launch_conv_kwave(a, s);
+        case kConvV2: return launch_conv_v2(L.cfg, L.halo, a, s);
+        case kConvV2m: return launch_conv_v2m(L.cfg, L.halo, a, s);
+        case kConvV2p: return launch_conv_v2p(L.cfg, L.halo, a, s);
+        case kConvV2s: return launch_conv_v2s(L.cfg, L.halo, a, s);
+        case kConvV2ps: return launch_conv_v2ps(L.cfg, L.halo, a, s);
+        case kConvDs: return launch_conv_ds(a, s);
+        case kConvDsM: return launch_conv_ds_m(a, s);
+        case kConvDsMs: return launch_conv_ds_ms(a, s);
+        case kConv1Block: return launch_conv1_block(a, s);
+        case kConv1_1Bf16: return launch_conv1_1_bf16(a, s);
+        case kConv1_1Split: return launch_conv1_1_split(a, s);
+        case kConv1_2Split: return launch_conv1_2_split(a, s);
+        case kFused: break;
+    }
+    return hipErrorInvalidConfiguration;
+}
+
+// The kernel a layer's launch ran (idc_layer_info_get; the names rocprofv3 shows, template arguments as <WM,WP>), from its entry point
+void kernel_label(const Layer& L, int precision, char* out, size_t cap) {
+    const int wm = L.cfg.wm, wp = L.cfg.wp, nseg = split_segments(precision);
+    const bool f16 = split_is_f16(precision), deconv = L.spec->kind == kDeconv4x4;
+    const char* const t = L.lprec == IDC_BF16 ? "bf16" : "f32";
+    switch (L.kernel) {
+        case kConvIgemm: snprintf(out, cap, "conv_igemm<%s,%d,%d>", t, wm, wp); break;
+        case kConvClick: snprintf(out, cap, "conv_click<%s,%d,%d>", t, wm, wp); break;
+        case kConvWino: snprintf(out, cap, "conv_wino_f32"); break;
+        case kDeconvWino: snprintf(out, cap, "conv_wino_deconv_f32"); break;
+        case kConvKwave: snprintf(out, cap, deconv ? "conv_kwave_deconv_bf16" : "conv_kwave_bf16"); break;
+        case kConvV2: snprintf(out, cap, "conv_igemm_v2<%d,%d>", wm, wp); break;
+        case kConvV2m: snprintf(out, cap, "conv_igemm_v2<%d,%d>+m16", wm, wp); break;
+        case kConvV2p: snprintf(out, cap, f16 ? "conv_igemm_v2ph<%d,%d>" : "conv_igemm_v2<%d,%d>+m16p", wm, wp); break;
+        case kConvV2s: snprintf(out, cap, f16 ? "conv_igemm_v2sh<%d,%d>x%d" : "conv_igemm_v2s<%d,%d>x%d", wm, wp, nseg); break;
+        case kConvV2ps: snprintf(out, cap, f16 ? "conv_igemm_v2psh<%d,%d>x%d" : "conv_igemm_v2ps<%d,%d>x%d", wm, wp, nseg); break;
+        // (the deconv and its 3x3 shortcut conv in one K loop)
+        case kConvDs: snprintf(out, cap, "conv_ds_fused+shortcut"); break;
+        case kConvDsM: snprintf(out, cap, f16 ? "conv_ds_fused_mh+shortcut" : "conv_ds_fused_m+shortcut"); break;
+        case kConvDsMs: snprintf(out, cap, f16 ? "conv_ds_fused_msh+shortcut x%d" : "conv_ds_fused_ms+shortcut x%d", L.args.nseg); break;
+        case kConv1Block: snprintf(out, cap, "conv1_block_fused"); break;
+        case kConv1_1Bf16: snprintf(out, cap, "conv1_1_bf16_kernel"); break;
+        case kConv1_1Split: snprintf(out, cap, "conv1_1_split_kernel"); break;
+        case kConv1_2Split: snprintf(out, cap, "conv1_2_split_kernel x%d", nseg); break;
+        case kFused: snprintf(out, cap, "fused"); break;
+    }
+    if (L.fused_head) strncat(out, "+head", cap - strlen(out) - 1);
+    if (L.args.ksplit > 1) {
+        char sk[16]; snprintf(sk, sizeof(sk), " splitK%d", L.args.ksplit);
+        strncat(out, sk, cap - strlen(out) - 1);
+    }
+}
+
+static double layer_flops(const LayerSpec& s, int H, int W) {       // per image, SURVEY.md Appendix A
+    const double ho = (double)(H / s.level), wo = (double)(W / s.level);
+    switch (s.kind) {
+        case kConv3x3: case kConvIm2col: return 2.0 * s.cin * s.cout * 9.0 * ho * wo;
+        case kConv1x1: return 2.0 * s.cin * s.cout * ho * wo;
+        case kDeconv4x4: return 2.0 * s.cin * s.cout * 4.0 * ho * wo;   // 4 taps per OUTPUT pixel
+    }
+    return 0;
+}
+
+int build_graph(idc_context* c) {
+    const auto& specs = layer_specs();
+    const int eb = elem_bytes(c->precision);
+    const bool split = is_split(c->precision);
+    auto add_tensor = [&](const char* name, int C, int Cpad, int level, int f32) -> int {
+        Tensor t;
+        t.name = name; t.C = C; t.Cpad = Cpad; t.H = c->H / level; t.W = c->W / level; t.is_f32 = f32;
+        t.parts = (split && !f32) ? split_parts(c->precision) : 1;
+        t.bytes = (size_t)c->max_batch * t.H * t.W * Cpad * (f32 ? 4 : eb * t.parts);
+        c->tensors.push_back(t);
+        return (int)c->tensors.size() - 1;
+    };
+    // operand-split precisions: is tensor `name` read by a layer outside the fp32 island / summed into another layer as a shortcut?
+    auto read_by_split_layer = [&](const char* name) {
+        for (int ai : c->plan.active) { const LayerSpec& q = specs[ai]; if (!split_island(q) && strcmp(q.src, name) == 0) return true; }
+        return false;
+    };
+    auto used_as_shortcut = [&](const char* name) {
+        for (int ai : c->plan.active) { const LayerSpec& q = specs[ai]; if (q.resid && strcmp(q.resid, name) == 0) return true; }
+        return false;
+    };
+    c->t_input = add_tensor("data_l_ab_mask", 36, 64, 1, 0);      // never materialised: built inside conv1_1's operand staging
+    c->tensors[c->t_input].bytes = 256;
+    for (size_t li = 0; li < c->plan.active.size(); ++li) {
+        const LayerSpec& s = specs[c->plan.active[li]];
+        Layer L;
+        L.spec = &s; L.blob = c->plan.layers[li];
+        L.src = find_tensor(c, s.src);
+        if (L.src < 0) return fail(&c->err, IDC_ERR_INVALID_ARG, "graph: unknown source '%s'", s.src);
+        if (s.resid) {
+            L.resid = find_tensor(c, s.resid);
+            if (L.resid < 0) return fail(&c->err, IDC_ERR_INVALID_ARG, "graph: unknown residual '%s'", s.resid);
+        }
+        // fp32 storage: everything on the fp32 path; on the bf16 path the class / 313 logits and the hyper-column
+        // partial sums of the 313 head (LayerSpec.out_f32)
+        L.lprec = c->precision;
+        if (split && split_island(s)) {
+            // fp32 island (conv1_1): exact-fp32 kernel; its epilogue writes the result as split planes where the split stack reads it
+            L.lprec = IDC_FP32;
+            L.dst = add_tensor(s.name, s.cout, cout_pad(s.cout), s.level, read_by_split_layer(s.name) ? 0 : 1);
+        } else {
+            // fp32 storage: everything on the fp32 path; class / 313 logits and the hyper-column partial sums (LayerSpec.out_f32); on the
+            // operand-split path also every shortcut branch (summed in fp32 in its consumer's epilogue)
+            L.split = split;
+            L.dst = add_tensor(s.name, s.cout, cout_pad(s.cout), s.level, c->precision == IDC_FP32 || s.out_f32 || (split && used_as_shortcut(s.name)));
+        }
+        fill_taps(L);
+        L.flops = layer_flops(s, c->H, c->W);
+        const Tensor& ti = c->tensors[L.src];
+        const Tensor& to = c->tensors[L.dst];
+        const double in_px = (double)(ti.H / s.in_stride) * (ti.W / s.in_stride);
+        L.min_bytes = in_px * ti.Cpad * (ti.is_f32 ? 4 : eb * ti.parts) + (double)to.H * to.W * to.Cpad * (to.is_f32 ? 4 : eb * to.parts) +
+                      (L.resid >= 0 ? (double)to.H * to.W * to.Cpad * (c->tensors[L.resid].is_f32 ? 4 : eb) : 0.0);
+        c->layers.push_back(L);
+    }
+    c->t_conv10_2 = find_tensor(c, "conv10_2");
+    c->t_logits = find_tensor(c, "class_logits");
+    c->t_conv4_3 = find_tensor(c, "conv4_3");
+    c->t_pred313 = find_tensor(c, "pred_313");
+    return IDC_OK;
+}
+
+int alloc_graph(idc_context* c) {
+    // ONE arena for all activation tensors (3.7 GB at N = 32): a single large allocation is 2 MiB-aligned and physically as
+    // contiguous as the driver can make it, whatever the process allocated before -- with one hipMalloc per tensor, a process whose
+    // other runtime (torch) had already carved up the address space got some tensors on small pages, and the layers READING those
+    // ran 25-35 % slower on every forward (bench.py's conv3_2 / conv5_1 / conv9_2 / conv8_1 against tools/quick_layers.py, which
+    // creates the engine first).  IDC_ARENA=0 restores the per-tensor allocations for A/B.
+    static const bool use_arena = idc_env_int("IDC_ARENA", 1) != 0;
+    if (use_arena) {
+        const size_t al = (size_t)2 << 20;
+        size_t total = 0;
+        for (auto& t : c->tensors) total += align_up(t.bytes, al);
+        HIPCHK(c, hipMalloc(&c->d_arena, total));
+        size_t off = 0;
+        for (auto& t : c->tensors) { t.ptr = (char*)c->d_arena + off; off += align_up(t.bytes, al); }
+    } else {
+        for (auto& t : c->tensors) HIPCHK(c, hipMalloc(&t.ptr, t.bytes));
+    }
+    const size_t hw = (size_t)c->H * c->W, nb = (size_t)c->max_batch;
+    HIPCHK(c, hipMalloc((void**)&c->d_L, nb * hw * 4));
+    HIPCHK(c, hipMalloc((void**)&c->d_ab, nb * hw * 2 * 4));
+    HIPCHK(c, hipMalloc((void**)&c->d_mask, nb * hw * 4));
+    HIPCHK(c, hipMalloc((void**)&c->d_out, nb * hw * 2 * 4));
+    // resident planes start defined: no hints (ab = 0, mask = 0); an L plane has to be uploaded before a resident forward
+    HIPCHK(c, hipMemset(c->d_L, 0, nb * hw * 4));
+    HIPCHK(c, hipMemset(c->d_ab, 0, nb * hw * 2 * 4));
+    HIPCHK(c, hipMemset(c->d_mask, 0, nb * hw * 4));
+    HIPCHK(c, hipMemset(c->d_out, 0, nb * hw * 2 * 4));
+    c->l_set.assign(nb, 0);
+    HIPCHK(c, hipMalloc(&c->d_zeros, 256));
+    HIPCHK(c, hipMemset(c->d_zeros, 0, 256));
+    if (c->precision == IDC_BF16) {              // conv_kwave_chain_bf16's grid-barrier counter and its host-visible abort flag
+        HIPCHK(c, hipMalloc((void**)&c->d_kw_bar, 1024));
+        HIPCHK(c, hipMemset(c->d_kw_bar, 0, 1024));
+        HIPCHK(c, hipHostMalloc((void**)&c->h_kw_abort, 64, hipHostMallocMapped));
+        *c->h_kw_abort = 0;
+    }
+    // the memsets above run on the NULL stream, the kernels on the handle's non-blocking stream: every conv launch reads the
+    // zero page (out-of-image halo rows), so make the fills complete before the handle can launch anything
+    HIPCHK(c, hipStreamSynchronize(nullptr));
+    HIPCHK(c, hipEventCreateWithFlags(&c->ev_sync, hipEventDisableTiming));
+    HIPCHK(c, hipHostMalloc((void**)&c->h_in, nb * hw * 4 * 4, hipHostMallocDefault));
+    HIPCHK(c, hipHostMalloc((void**)&c->h_out, nb * hw * 2 * 4, hipHostMallocDefault));
+    if (c->flags & IDC_FLAG_DIST_HEAD) {
+        const size_t dq = nb * 529 * (hw / 16) * 4;
+        HIPCHK(c, hipMalloc((void**)&c->d_dist, dq));
+        HIPCHK(c, hipHostMalloc((void**)&c->h_dist, dq, hipHostMallocDefault));
+    }
+    if (c->flags & IDC_FLAG_DIST313) {
+        HIPCHK(c, hipMalloc((void**)&c->d_pred_ab, nb * hw * 2 * 4));
+        HIPCHK(c, hipHostMalloc((void**)&c->h_pred_ab, nb * hw * 2 * 4, hipHostMallocDefault));
+        HIPCHK(c, hipMalloc((void**)&c->d_dist313, nb * hw * 313 * 4));      // 82 MB per 256x256 image: sized for 288 GB parts
+    }
+    if (c->flags & IDC_FLAG_GLOBAL_HINTS) {
+        HIPCHK(c, hipMalloc((void**)&c->d_glob_in, nb * kGlobIn * 4));
+        HIPCHK(c, hipMalloc((void**)&c->d_glob_vec, nb * kGlobC * 4));
+        HIPCHK(c, hipMemset(c->d_glob_in, 0, nb * kGlobIn * 4));
+    }
+    c->n_timed = (int)c->layers.size() + 3;           // profiling events (2240 per handle) are created by idc_set_profiling, not here:
+    return IDC_OK;                                    // a process holding many handles must not exhaust the runtime's signal pool
+}
+
+}  // namespace idc
+
+extern "C" {
+
+int idc_set_splitk_policy(int policy) {
+    if (policy < 0 || policy > 2) return fail(nullptr, IDC_ERR_INVALID_ARG, "split-K policy %d not in 0..2", policy);
+    options().splitk_policy = policy;
+    return IDC_OK;
+}
+
+int idc_set_tile_policy(int policy) {
+    if (policy < 0 || policy > 2) return fail(nullptr, IDC_ERR_INVALID_ARG, "tile policy %d not in 0..2", policy);
+    options().tile_policy = policy;
+    return IDC_OK;
+}
+
+int idc_set_option(const char* name, int value) {
+    Options& o = options();
+    if (!name) return fail(nullptr, IDC_ERR_INVALID_ARG, "null option name");
+    if (strcmp(name, "fuse_conv1") == 0) { o.fuse_conv1 = value != 0; return IDC_OK; }
+    if (strcmp(name, "click") == 0) { o.click = value; return IDC_OK; }
+    if (strcmp(name, "winograd") == 0) {         // 0 off | 1 automatic | 2 everywhere implemented | 12 / 21 / 22 automatic, 3x3 form <TB,CB> forced
+        if (value != 0 && value != 1 && value != 2 && value != 12 && value != 21 && value != 22)
+            return fail(nullptr, IDC_ERR_INVALID_ARG, "option 'winograd': %d not in {0, 1, 2, 12, 21, 22}", value);
+        o.wino = value != 0;
+        o.wino_deconv = value == 2 ? 2 : 1;
+        set_wino_form(value >= 12 ? value : 0);
+        return IDC_OK;
+    }
+    if (!kAbPartners && ((strcmp(name, "mfma16") == 0 && value == 0) || (strcmp(name, "ds_mfma16") == 0 && value == 0)))
+        return fail(nullptr, IDC_ERR_UNSUPPORTED, "option '%s' = 0 selects a 32x32x16-MFMA partner kernel: not in the default library (build with make EXTRA=-DIDC_AB_PARTNERS)", name);
+    if (strcmp(name, "mfma16") == 0) { o.mfma16 = value != 0; return IDC_OK; }
+    if (strcmp(name, "v2p") == 0) { o.v2p = value != 0; return IDC_OK; }
+    if (strcmp(name, "ds_mfma16") == 0) { o.ds_m16 = value != 0; set_ds_half(value != 2); return IDC_OK; }     // 2: conv_ds_fused_m, 8-wave workgroups on every grid
+    if (strcmp(name, "split_ds_fuse") == 0) { o.split_ds_fuse = value != 0; return IDC_OK; }
+    if (strcmp(name, "conv1_1_split") == 0) { o.conv1_1_split = value != 0; return IDC_OK; }
+    if (strcmp(name, "conv1_2_split") == 0) { o.conv1_2_split = value != 0; return IDC_OK; }
+    if (strcmp(name, "fp16_fast") == 0) { o.fp16_fast = value != 0; return IDC_OK; }
+    if (strcmp(name, "kwave") == 0) { o.kwave = value != 0; return IDC_OK; }
+    if (strcmp(name, "spin_sync") == 0) { o.spin_sync = value != 0; return IDC_OK; }
+    if (strcmp(name, "pcie_kernel") == 0) { o.pcie_kernel = value != 0; return IDC_OK; }
+    if (strcmp(name, "kw_force_abort") == 0) { o.kw_force_abort = value != 0; return IDC_OK; }
+    if (strcmp(name, "kwave_chain") == 0) { o.kwave_chain = value < 0 ? 0 : (value > 2 ? 2 : value); return IDC_OK; }
+    return fail(nullptr, IDC_ERR_INVALID_ARG, "unknown option '%s'", name);
+}
+
+}  // extern "C"

@@ -998,7 +998,7 @@ hipError_t launch_conv_ds(const ConvArgs& a, hipStream_t s) {
 
 
 
-#else   // default library: the 16x16x32 twins only (idc_v2m.hip, idc_dsm.hip); the engine never plans these launches (idc_engine.hip, kAbPartners)
+#else   // default library: the 16x16x32 twins only (idc_v2m.hip, idc_dsm.hip); the engine never plans these launches (idc_plan.hip; kAbPartners, idc_engine.h)
 hipError_t init_kernels_v2() { return hipSuccess; }
 hipError_t launch_conv_v2(ConvConfig, int, const ConvArgs&, hipStream_t) { return hipErrorInvalidConfiguration; }
 hipError_t launch_conv_ds(const ConvArgs&, hipStream_t) { return hipErrorInvalidConfiguration; }

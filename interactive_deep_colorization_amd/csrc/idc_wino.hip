@@ -15,7 +15,7 @@
 //   * per chunk the (4+4+2)^2 = 100-pixel input patch goes global -> registers -> LDS (one chunk ahead), every thread
 //     transforms one (tile, 16-byte channel slot, row i of B^T d B) from it: 8 ds_read_b128, 8 float4 add/sub, 4
 //     ds_write_b128 into the position planes V[pos][tile][32 ch] (slot ^ (tile & 7): conflict-free both ways);
-//   * the transformed weights U = G g G^T are packed on the host (float64 transform, idc_engine.hip) in the exact order the
+//   * the transformed weights U = G g G^T are packed on the host (float64 transform, idc_pack.hip) in the exact order the
 //     MFMA A operand wants them: [chunk][pos][16 couts][ks][lane][4 floats] -- each wave streams ITS positions' fragments
 //     global -> registers with fully coalesced 1 KiB loads, one chunk ahead; no weights in LDS at all;
 //   * MFMA: v_mfma_f32_16x16x4_f32 on 16-byte fragments (4 MFMAs per fragment pair, the same K permutation on both operands),
@@ -752,7 +752,7 @@ static hipError_t launch_wino_t(ConvArgs& a, int d, int precision, hipStream_t s
     return hipGetLastError();
 }
 
-// 3x3 stride-1 conv (dilation 1 or 2), fp32, Winograd F(2x2,3x3).  a.wgt = the layer's U image (idc_engine.hip packs it),
+// 3x3 stride-1 conv (dilation 1 or 2), fp32, Winograd F(2x2,3x3).  a.wgt = the layer's U image (idc_pack.hip packs it),
 // a.nkc = Cin / 32, a.ncg = CoutPad / 64, a.Hs / a.Ws = image size, a.dy[8] = dilation; tiles_x / tiles_y are set here.
 // Form by grid size (speed only: every form computes the same sums in the same order): the throughput form <2,2> when it
 // still gives every CU a workgroup, else <1,2>.

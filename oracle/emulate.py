@@ -140,7 +140,7 @@ def split_bf16(x, terms):
 def split_f16(x, terms, scale_exp=0):
     """x (fp32) * 2^scale_exp as a sum of `terms` fp16 values (RNE, clamped to +-65504; subnormals as the hardware keeps them), each divided back by
     2^scale_exp (powers of two: exact).  IDC_FP16X3 (round 6): activations unscaled, a layer's weights with the power of two that brings max|w| into
-    [8192, 16384) -- ``f16_weight_exponent`` below, csrc/idc_engine.hip's packer -- so that the lo part of a small weight is a NORMAL fp16 number."""
+    [8192, 16384) -- ``f16_weight_exponent`` below, csrc/idc_pack.hip's packer -- so that the lo part of a small weight is a NORMAL fp16 number."""
     s = 2.0 ** scale_exp
     parts, r = [], x * s
     for _ in range(terms):

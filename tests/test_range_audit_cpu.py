@@ -1,7 +1,7 @@
 """CPU tests of the range audit's ABI surface and of the activation exponents of precision 'fp16x3' (pack time, host code only).
 
 The fp16x3 blob layout is re-derived here from the layer list tests/test_abi_cpu.py keeps (the same source test_pack_weights_layout uses), with
-what csrc/idc_engine.hip make_blob_plan adds for the operand-split precisions: conv1_1 is an fp32 island, every other layer carries two fp16
+what csrc/idc_pack.hip make_blob_plan adds for the operand-split precisions: conv1_1 is an fp32 island, every other layer carries two fp16
 weight parts and ONE fp32 accumulator-scale word ("wscale")."""
 import os
 import re

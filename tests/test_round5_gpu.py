@@ -12,7 +12,7 @@ from oracle import siggraph_torch
 from bounds import FP32_TOL, bf16_bound, check_bf16_ab  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-CHAIN_DEFAULT = 2               # the library's default for "kwave_chain" (csrc/idc_engine.hip)
+CHAIN_DEFAULT = 2               # the library's default for "kwave_chain" (Options, csrc/idc_engine.h)
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 

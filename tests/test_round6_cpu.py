@@ -1,6 +1,6 @@
 """Round 6, CPU side (no GPU): the operand-split precisions' weight blob, and this round's host-logic changes.
 
-Blob of IDC_BF16X3 / IDC_BF16X6 (csrc/idc_engine.hip make_blob_plan, re-derived here independently): conv1_1 is an fp32 island (fp32
+Blob of IDC_BF16X3 / IDC_BF16X6 (csrc/idc_pack.hip make_blob_plan, re-derived here independently): conv1_1 is an fp32 island (fp32
 layout-1 image, 32-channel chunks); every other layer carries 2 / 3 layout-1 bf16 images back to back -- part 0 = rne(w), part 1 =
 rne(w - part 0), part 2 = rne(w - part 0 - part 1) -- so that hi + lo reproduces w to 2^-16 relative and hi + mid + lo reproduces it exactly.
 Reference semantics of the weights: torch layouts of models/pytorch/model.py:13-109.
