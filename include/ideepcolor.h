@@ -111,6 +111,8 @@ int idc_set_tile_policy(int policy);
  *                      others gives up after ~0.3 s, that forward fails with IDC_ERR_INTERNAL and the handle goes back to one launch per layer.
  *   "spin_sync"   (1)  calls that serve one or two images wait by polling the stream (bounded) instead of parking on an interrupt; 0 = blocking wait.
  *   "pcie_kernel" (1)  their host <-> device transfers (<= 2 MiB, pinned) run as a copy kernel on the forward's stream; 0 = hipMemcpyAsync.
+ *   "op_policy_batch" (0)  single-operator entry points (idc_op_*): the batch the kernel variant is chosen for, as a handle's max_batch is for its
+ *                      forwards; 0 = the call's own batch.  The launch always carries the call's batch.  Not read by any forward.
  *   "kw_force_abort" (0)  TEST HOOK: 1 makes the persistent trunk launch's first grid barrier unreachable (plays "workgroups never co-resident").
  * Retired with their kernels, or folded into the above: "fuse_conv1_small", "winograd_bf16", "winograd_form", "winograd_deconv", "conv1_lw",
  * "code_warm", "kwave_deconv" (IDC_ERR_INVALID_ARG).
@@ -437,6 +439,18 @@ int idc_op_conv2d(int device_id, int precision, int n, int cin, int h, int w, co
 int idc_op_deconv4x4s2(int device_id, int precision, int n, int cin, int h, int w, const float* x,
                        int cout, const float* weight, const float* bias, int act,
                        const float* resid, float* y);
+/* The fused pair of the decoder as ONE launch, planned as the network plans it (conv_ds_fused_m / _mh / _ms / _msh):
+ * y = act(deconv4x4s2(x) + conv3x3(x_short) + b_deconv + b_short); x [n,cin,h,w], w_deconv (cin,cout,4,4), x_short [n,cin_short,2h,2w],
+ * w_short (cout,cin_short,3,3) (dilation 1, padding 1); act 0 or 1; y [n,cout,2h,2w].  IDC_ERR_UNSUPPORTED where the network would run
+ * the pair as two launches (grid below the large tile's threshold at the policy batch, cout not a multiple of 128, fp32). */
+int idc_op_deconv_shortcut(int device_id, int precision, int n, int cin, int h, int w, const float* x, int cout,
+                           const float* w_deconv, const float* b_deconv, int cin_short, const float* x_short,
+                           const float* w_short, const float* b_short, int act, float* y);
+/* The kernel the last single-operator call of this thread launched, as the layer table names it (idc_layer_info.kernel: template
+ * arguments <WM,WP>, " splitK<n>"); a conv_ds_fused_m / _mh launch adds " half" (its 64-cout 4-wave form) or " 8-wave".  Empty when
+ * the call failed before it chose a kernel.  The variant is chosen for idc_set_option("op_policy_batch", v) images (0 = the call's
+ * own batch) while the launch carries the call's n. */
+int idc_op_last_kernel(char* out, int cap);
 
 #ifdef __cplusplus
 }

@@ -24,7 +24,7 @@ EXPORTED_SYMBOLS = [
     "idc_weights_blob_bytes", "idc_pack_weights", "idc_set_weights_host", "idc_set_weights_device",
     "idc_load_weights", "idc_weights_device_ptr", "idc_forward", "idc_forward_device", "idc_forward_dist",
     "idc_lab2rgb", "idc_forward_rgb", "idc_forward_rgb_lazy", "idc_fetch_outputs", "idc_global_histogram", "idc_forward_dist313", "idc_set_dist_temperature", "idc_set_global_hints", "idc_clear_global_hints", "idc_sync", "idc_stream", "idc_num_layers", "idc_layer_info_get", "idc_set_profiling",
-    "idc_layer_times_ms", "idc_layer_times_stats", "idc_get_activation", "idc_op_conv2d", "idc_op_deconv4x4s2",
+    "idc_layer_times_ms", "idc_layer_times_stats", "idc_get_activation", "idc_op_conv2d", "idc_op_deconv4x4s2", "idc_op_deconv_shortcut", "idc_op_last_kernel",
     "idc_set_image_l", "idc_set_hints", "idc_get_hint_planes", "idc_forward_resident",
     "idc_dist_bins", "idc_keep_dist", "idc_dist_at", "idc_get_dist", "idc_suggest_colors",
     "idc_stream_wait", "idc_stream_signal", "idc_alloc_host", "idc_free_host", "idc_forward_async", "idc_wait", "idc_pipeline_times",
@@ -129,6 +129,9 @@ def load():
                                 c_float_p, c_float_p, c_float_p, c_float_p])
     proto("idc_op_deconv4x4s2", ci, [ci, ci, ci, ci, ci, ci, c_float_p, ci, c_float_p, c_float_p, ci,
                                      c_float_p, c_float_p])
+    proto("idc_op_deconv_shortcut", ci, [ci, ci, ci, ci, ci, ci, c_float_p, ci, c_float_p, c_float_p, ci, c_float_p,
+                                         c_float_p, c_float_p, ci, c_float_p])
+    proto("idc_op_last_kernel", ci, [ctypes.c_char_p, ci])
     proto("idc_set_image_l", ci, [vp, ci, c_float_p])
     proto("idc_set_hints", ci, [vp, ci, ci, ctypes.POINTER(Hint), ci, cf])
     proto("idc_get_hint_planes", ci, [vp, ci, c_float_p, c_float_p])

@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <string>
 #include <vector>
 
 #include "idc_engine.h"
@@ -216,9 +217,17 @@ int idc_get_activation(idc_handle h, const char* name, int n, float* out, size_t
 
 // ---- single operators -----------------------------------------------------------------------------
 
+// the kernel_label of the launch the last single-operator call on this thread made (idc_op_last_kernel); a conv_ds_fused_m / _mh launch also says
+// which of its two forms ran (" half" = 64 couts, 4 waves; " 8-wave"), which the layer table's label leaves to the grid
+static thread_local std::string g_op_last_kernel;
+
+// the 3x3 shortcut conv that rides in a deconv's launch (idc_op_deconv_shortcut): x [n, cin, 2h, 2w], w [cout, cin, 3, 3], b [cout]
+struct ShortcutOp { int cin; const float* x; const float* w; const float* b; };
+
 static int run_single_op(int device_id, int precision, LayerSpec spec, int n, int h, int w, const float* x,
                          const float* weight, const float* bias, const float* bn_scale, const float* bn_shift,
-                         const float* resid, float* y) {
+                         const float* resid, float* y, const ShortcutOp* sc = nullptr) {
+    g_op_last_kernel.clear();
     int rc = check_device(device_id, nullptr);
     if (rc) return rc;
     if (precision < IDC_FP32 || precision > IDC_FP16) return fail(nullptr, IDC_ERR_INVALID_ARG, "bad precision");
@@ -230,6 +239,9 @@ static int run_single_op(int device_id, int precision, LayerSpec spec, int n, in
     if (spec.cin % kc) return fail(nullptr, IDC_ERR_UNSUPPORTED, "cin must be a multiple of %d in this precision", kc);
     if (spec.in_stride != 1 && spec.in_stride != 2) return fail(nullptr, IDC_ERR_INVALID_ARG, "in_stride must be 1 or 2");
     if (h % spec.in_stride || w % spec.in_stride) return fail(nullptr, IDC_ERR_INVALID_ARG, "H, W must divide by in_stride");
+    if (sc && (!sc->x || !sc->w || !sc->b || sc->cin <= 0 || sc->cin % kc)) return fail(nullptr, IDC_ERR_INVALID_ARG, "bad shortcut operand");
+    // the batch the variant is chosen for, as a handle's max_batch is (option "op_policy_batch"; 0 = this call's own batch); the launch carries n
+    const int n_policy = options().op_policy_batch > 0 ? options().op_policy_batch : n;
     idc_context* nullctx = nullptr;
     HIPCHK(nullctx, hipSetDevice(device_id));
     HIPCHK(nullctx, init_kernels());
@@ -237,6 +249,9 @@ static int run_single_op(int device_id, int precision, LayerSpec spec, int n, in
     // the shortcut sum arrives through the `resid` pointer; every eligibility gate of set_geometry reads spec.resid (a 3x3 op with
     // a residual must not be handed to conv_kwave_bf16 / the Winograd forms, which do not take one -- ADVICE r4)
     spec.resid = resid ? "resid" : nullptr;
+    // ... and spec.out_f32: the op stores fp32 on the fp32 path only (a.out_f32 below); left at 1, the default library's planner kept every
+    // bf16 op off the large tile, which writes bf16 only, whatever the tile policy asked for
+    spec.out_f32 = (precision == IDC_BF16 || split) ? 0 : 1;
     L.spec = &spec;
     L.blob.nkc = spec.cin / kc; L.blob.ncg = cout_pad(spec.cout) / kCoutGroup;
     L.blob.w_bytes = (size_t)weight_taps(spec.kind) * L.blob.nkc * L.blob.ncg * kWBlockBytes;
@@ -254,15 +269,31 @@ static int run_single_op(int device_id, int precision, LayerSpec spec, int n, in
     const int Ho = Hs * so, Wo = Ws * so;
     fill_taps(L);
     // (default library: the large tile only where conv_igemm_v2m / v2p cover the launch -- no shortcut sum, no LeakyReLU without the fused head)
-    set_geometry(L, precision, n, n, Hs, Ws, kAbPartners || is_split(precision) || (resid == nullptr && spec.act != 2));
+    set_geometry(L, precision, n, n_policy, Hs, Ws, kAbPartners || is_split(precision) || (resid == nullptr && spec.act != 2));
     const size_t wcount = (size_t)spec.cin * spec.cout * (spec.kind == kDeconv4x4 ? 16 : spec.kind == kConv1x1 ? 1 : 9);
-    const int op_wexp = (split_is_f16(precision) && parts > 1) ? f16_weight_exponent(weight, wcount) : 0;      // as the blob packer does per layer
+    int op_wexp = (split_is_f16(precision) && parts > 1) ? f16_weight_exponent(weight, wcount) : 0;      // as the blob packer does per layer
+    // deconv + shortcut conv in one launch: run_graph's conditions for the pair (the large tile, conv_ds_fused's domain), else the network runs two launches
+    LayerSpec spec2{"op_short", "op_short", nullptr, kConv3x3, sc ? sc->cin : 0, spec.cout, 1, 1, 0, "x_short", nullptr, 1, 1, 0};
+    LayerBlob blob2 = L.blob;
+    if (sc) {
+        blob2.nkc = sc->cin / kc;
+        blob2.w_bytes = (size_t)weight_taps(kConv3x3) * blob2.nkc * blob2.ncg * kWBlockBytes;
+        const bool fits = split ? conv_ds_m_fits(Hs, Ws, L.blob.nkc * parts, blob2.nkc * parts) : conv_ds_m_fits(Hs, Ws, L.blob.nkc, blob2.nkc);
+        if (L.kernel != kConvV2 || !fuse_shortcut_enabled() || (split && !options().split_ds_fuse) || spec.cout % 128 != 0 || spec.act == 2 ||
+            (!kAbPartners && !split && !(options().ds_m16 != 0 && fits)) || (split && !fits))
+            return fail(nullptr, IDC_ERR_UNSUPPORTED, "deconv + shortcut: the network runs this pair as two launches here (policy batch %d, options)", n_policy);
+        L.fused_short = 0;
+        if (split_is_f16(precision) && parts > 1) {      // one accumulator set, one accumulator scale: the smaller of the two weight exponents, as the blob packer does
+            const int e2 = f16_weight_exponent(sc->w, (size_t)sc->cin * spec.cout * 9);
+            if (e2 < op_wexp) op_wexp = e2;
+        }
+    }
     std::vector<float> hb(cpad, 0.f), hs(cpad, 1.f), ht(cpad, 0.f);
     for (int c = 0; c < spec.cout; ++c) {
-        hb[c] = bias[c];
+        hb[c] = bias[c] + (sc ? sc->b[c] : 0.f);
         if (bn_scale) { hs[c] = bn_scale[c]; ht[c] = bn_shift ? bn_shift[c] : 0.f; }
     }
-    DevBuf d_x, d_xn, d_w, d_b, d_s, d_t, d_r, d_rn, d_yn, d_y;
+    DevBuf d_x, d_xn, d_w, d_b, d_s, d_t, d_r, d_rn, d_yn, d_y, d_x2, d_x2n, d_w2;
     const size_t xin = (size_t)n * spec.cin * h * w, yout = (size_t)n * spec.cout * Ho * Wo;
     HIPCHK(nullctx, d_x.alloc(xin * 4));
     HIPCHK(nullctx, d_xn.alloc(xin * eb * parts));
@@ -292,6 +323,17 @@ static int run_single_op(int device_id, int precision, LayerSpec spec, int n, in
     a.resid_bf16 = io_bf16;
     a.head_w = nullptr; a.head_b = nullptr; a.head_out = nullptr; a.head_mul = 0.f;
     a.in2 = nullptr; a.wgt2 = nullptr; a.nkc2 = 0;
+    if (sc) {              // bound as run_graph binds a layer's fused_short
+        const size_t x2n = (size_t)n * sc->cin * Ho * Wo;
+        HIPCHK(nullctx, d_x2.alloc(x2n * 4));
+        HIPCHK(nullctx, d_x2n.alloc(x2n * eb * parts));
+        HIPCHK(nullctx, d_w2.alloc(blob2.w_bytes * parts));
+        HIPCHK(nullctx, hipMemcpy(d_x2.p, sc->x, x2n * 4, hipMemcpyHostToDevice));
+        if (split) HIPCHK(nullctx, launch_nchw_to_split((const float*)d_x2.p, d_x2n.p, n, sc->cin, Ho, Wo, sc->cin, parts, split_is_f16(precision) ? 1 : 0, nullptr));
+        else HIPCHK(nullctx, launch_nchw_to_nhwc(precision, (const float*)d_x2.p, d_x2n.p, n, sc->cin, Ho, Wo, sc->cin, nullptr));
+        a.in2 = d_x2n.p; a.wgt2 = d_w2.p; a.nkc2 = blob2.nkc;
+        if (split) a.w_part_bytes2 = blob2.w_bytes;
+    }
     a.warm = options().code_warm;
     a.split_f16 = split_is_f16(precision) ? 1 : 0;
     a.out_f32 = (io_bf16 || split) ? 0 : 1;
@@ -315,7 +357,19 @@ static int run_single_op(int device_id, int precision, LayerSpec spec, int n, in
     HIPCHK(nullctx, hipMemset(d_zero.p, 0, 256));
     a.zeros = d_zero.p;
     // the kernel the network launches for this layer at batch n, and the weight image it reads
-    L.kernel = choose_kernel(L, precision, n);
+    L.kernel = choose_kernel(L, precision, n_policy);
+    if (sc) {
+        if (L.kernel == kConvDs) return fail(nullptr, IDC_ERR_UNSUPPORTED, "deconv + shortcut: conv_ds_fused (the 32x32x16-MFMA partner) has no single-operator entry");
+        std::vector<uint8_t> wimg2(blob2.w_bytes * parts);
+        for (int part = 0; part < parts; ++part)
+            pack_layer_weights(wimg2.data() + (size_t)part * blob2.w_bytes, precision, 1, spec2, blob2, sc->w, part, ldexpf(1.f, op_wexp));
+        HIPCHK(nullctx, hipMemcpy(d_w2.p, wimg2.data(), wimg2.size(), hipMemcpyHostToDevice));
+    }
+    {
+        char k[64]; kernel_label(L, precision, k, sizeof(k));
+        g_op_last_kernel = k;
+        if (L.kernel == kConvDsM) g_op_last_kernel += conv_ds_m_half(a) ? " half" : " 8-wave";
+    }
     std::vector<uint8_t> wimg(wimg_bytes);
     if (L.kernel == kDeconvWino) pack_wino_deconv_weights(wimg.data(), precision, spec, L.blob, weight);
     else if (L.kernel == kConvWino) pack_wino_weights(wimg.data(), precision, spec, L.blob, weight);
@@ -346,6 +400,19 @@ int idc_op_conv2d(int device_id, int precision, int n, int cin, int h, int w, co
     LayerSpec s{"op", "op", nullptr, ksize == 3 ? kConv3x3 : kConv1x1, cin, cout, dilation, in_stride, act,
                 "x", nullptr, 1, 1, 0};
     return run_single_op(device_id, precision, s, n, h, w, x, weight, bias, bn_scale, bn_shift, resid, y);
+}
+
+int idc_op_last_kernel(char* out, int cap) {
+    if (!out || cap <= 0) return fail(nullptr, IDC_ERR_INVALID_ARG, "null / empty label buffer");
+    snprintf(out, (size_t)cap, "%s", g_op_last_kernel.c_str());
+    return IDC_OK;
+}
+
+int idc_op_deconv_shortcut(int device_id, int precision, int n, int cin, int h, int w, const float* x, int cout, const float* w_deconv,
+                           const float* b_deconv, int cin_short, const float* x_short, const float* w_short, const float* b_short, int act, float* y) {
+    LayerSpec s{"op", "op", nullptr, kDeconv4x4, cin, cout, 1, 1, act, "x", nullptr, 1, 1, 0};
+    const ShortcutOp sc{cin_short, x_short, w_short, b_short};
+    return run_single_op(device_id, precision, s, n, h, w, x, w_deconv, b_deconv, nullptr, nullptr, nullptr, y, &sc);
 }
 
 int idc_op_deconv4x4s2(int device_id, int precision, int n, int cin, int h, int w, const float* x, int cout,

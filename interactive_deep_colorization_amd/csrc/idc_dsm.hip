@@ -527,14 +527,19 @@ bool conv_ds_m_applies(const ConvArgs& a) {
            conv_ds_m_fits(a.Hs, a.Ws, a.nkc, a.nkc2);
 }
 
+// fewer 128-cout workgroups than CUs (model10up + shortcut of ONE 256x256 image: 128) and a single shortcut chunk: the 64-cout, 4-wave form
+bool conv_ds_m_half(const ConvArgs& a) {
+    const long long blocks = (long long)((a.Ws + 31) / 32) * ((a.Hs + 3) / 4) * a.N * (a.ncg / 2);
+    static int n_cu = 0;
+    if (n_cu == 0) { int dev = 0; hipDeviceProp_t pr; n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : -1; }
+    return g_ds_half && a.nkc2 == 1 && n_cu > 0 && blocks < n_cu;
+}
+
 hipError_t launch_conv_ds_m(const ConvArgs& a, hipStream_t s) {
     if (!conv_ds_m_applies(a)) return hipErrorInvalidConfiguration;
     const long long blocks = (long long)((a.Ws + 31) / 32) * ((a.Hs + 3) / 4) * a.N * (a.ncg / 2);
     if (blocks <= 0 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    // fewer 128-cout workgroups than CUs (model10up + shortcut of ONE 256x256 image: 128) and a single shortcut chunk: the 64-cout, 4-wave form
-    static int n_cu = 0;
-    if (n_cu == 0) { int dev = 0; hipDeviceProp_t pr; n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : -1; }
-    const bool half = g_ds_half && a.nkc2 == 1 && n_cu > 0 && blocks < n_cu;
+    const bool half = conv_ds_m_half(a);
     if (a.split_f16) {                                           // IDC_FP16's fast path
         if (half) hipLaunchKernelGGL(conv_ds_fused_mh<1>, dim3((unsigned)(2 * blocks)), dim3(256), 160 * 1024, s, a);
         else hipLaunchKernelGGL(conv_ds_fused_mh<2>, dim3((unsigned)blocks), dim3(512), 160 * 1024, s, a);

@@ -109,6 +109,8 @@ struct Options {
     int spin_sync = 1;                   // one- and two-image calls poll the stream instead of parking on an interrupt ("spin_sync"; 0 = the blocking wait of rounds 1-4)
     int pcie_kernel = 1;                 // their host <-> device transfers as copy kernels on the forward's stream ("pcie_kernel"; 0 = hipMemcpyAsync / the copy engines)
     int kw_force_abort = 0;              // test hook ("kw_force_abort"): the persistent trunk launch's first grid barrier is unreachable and its give-up counter tiny
+    // single-operator entry points (idc_diag.hip): the batch their kernel variant is chosen for, as a handle's max_batch is ("op_policy_batch"; 0 = the call's own batch)
+    int op_policy_batch = 0;
     int click = -1;                      // conv_click for small launches: -1 = environment default (on), 0 off, 1 on (idc_set_option "click")
 };
 Options& options();

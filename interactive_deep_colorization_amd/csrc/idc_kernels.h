@@ -141,6 +141,7 @@ hipError_t launch_conv_ds_m(const ConvArgs& a, hipStream_t s);
 hipError_t launch_conv_ds_ms(const ConvArgs& a, hipStream_t s);
 bool conv_ds_m_fits(int Hs, int Ws, int nkc, int nkc2);   // (else conv_ds_fused, which addresses with 64-bit pointers)
 bool conv_ds_m_applies(const ConvArgs& a);
+bool conv_ds_m_half(const ConvArgs& a);   // launch_conv_ds_m runs its 64-cout, 4-wave form for this launch
 bool conv_ds_ms_applies(const ConvArgs& a);
 hipError_t init_kernels_dsm();
 void set_ds_half(int v);              // 1 (default): grids with fewer 128-cout workgroups than CUs run the 64-cout, 4-wave form of conv_ds_fused_m

@@ -489,6 +489,11 @@ int idc_set_option(const char* name, int value) {
     if (strcmp(name, "spin_sync") == 0) { o.spin_sync = value != 0; return IDC_OK; }
     if (strcmp(name, "pcie_kernel") == 0) { o.pcie_kernel = value != 0; return IDC_OK; }
     if (strcmp(name, "kw_force_abort") == 0) { o.kw_force_abort = value != 0; return IDC_OK; }
+    if (strcmp(name, "op_policy_batch") == 0) {
+        if (value < 0) return fail(nullptr, IDC_ERR_INVALID_ARG, "option 'op_policy_batch': %d is negative", value);
+        o.op_policy_batch = value;
+        return IDC_OK;
+    }
     if (strcmp(name, "kwave_chain") == 0) { o.kwave_chain = value < 0 ? 0 : (value > 2 ? 2 : value); return IDC_OK; }
     return fail(nullptr, IDC_ERR_INVALID_ARG, "unknown option '%s'", name);
 }

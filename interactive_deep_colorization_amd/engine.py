@@ -755,22 +755,38 @@ class HipColorizer(object):
 
 
 # ---- single operators through the same kernels (used by the parity tests) ---------------------
+# policy_batch: the batch the kernel variant is chosen for, as a handle's max_batch is (option 'op_policy_batch'); None leaves the option as it
+# is, 0 = the call's own batch.  The launch carries the call's batch either way; op_last_kernel() names what ran.
+def _set_policy_batch(policy_batch):
+    if policy_batch is not None:
+        set_option("op_policy_batch", int(policy_batch))
+
+
+def op_last_kernel():
+    """Label of the kernel the last op_* call of this thread launched, as layer_table() names kernels (``idc_op_last_kernel``)."""
+    buf = ctypes.create_string_buffer(96)
+    N.check(N.load().idc_op_last_kernel(buf, len(buf)))
+    return buf.value.decode()
+
+
 def op_conv2d(x, weight, bias, dilation=1, in_stride=1, act=0, bn_scale=None, bn_shift=None, resid=None,
-              precision="fp32", device=0):
+              precision="fp32", device=0, policy_batch=None):
     lib = N.load()
+    _set_policy_batch(policy_batch)
     x = _f32c(x); weight = _f32c(weight); bias = _f32c(bias)
     n, cin, h, w = x.shape
     cout, ksize = weight.shape[0], weight.shape[2]
     y = np.empty((n, cout, h // in_stride, w // in_stride), np.float32)
-    opt = lambda a: _fptr(_f32c(a)) if a is not None else None
-    keep = [opt(bn_scale), opt(bn_shift), opt(resid)]
+    keep = [_f32c(a) if a is not None else None for a in (bn_scale, bn_shift, resid)]
+    ptr = [_fptr(a) if a is not None else None for a in keep]
     N.check(lib.idc_op_conv2d(device, _PREC[precision], n, cin, h, w, _fptr(x), cout, ksize, dilation, in_stride,
-                              _fptr(weight), _fptr(bias), act, keep[0], keep[1], keep[2], _fptr(y)))
+                              _fptr(weight), _fptr(bias), act, ptr[0], ptr[1], ptr[2], _fptr(y)))
     return y
 
 
-def op_deconv4x4s2(x, weight, bias, act=0, resid=None, precision="fp32", device=0):
+def op_deconv4x4s2(x, weight, bias, act=0, resid=None, precision="fp32", device=0, policy_batch=None):
     lib = N.load()
+    _set_policy_batch(policy_batch)
     x = _f32c(x); weight = _f32c(weight); bias = _f32c(bias)
     n, cin, h, w = x.shape
     cout = weight.shape[1]
@@ -778,4 +794,21 @@ def op_deconv4x4s2(x, weight, bias, act=0, resid=None, precision="fp32", device=
     r = _f32c(resid) if resid is not None else None
     N.check(lib.idc_op_deconv4x4s2(device, _PREC[precision], n, cin, h, w, _fptr(x), cout, _fptr(weight),
                                    _fptr(bias), act, _fptr(r) if r is not None else None, _fptr(y)))
+    return y
+
+
+def op_deconv_shortcut(x, w_deconv, b_deconv, x_short, w_short, b_short, act=0, precision="bf16", policy_batch=None, device=0):
+    """act(deconv4x4s2(x) + conv3x3(x_short) + b_deconv + b_short) as the ONE launch the network makes of a decoder level's ConvTranspose and
+    the shortcut conv summed into it (``idc_op_deconv_shortcut``); raises IdcError (UNSUPPORTED) where the network would launch the two apart."""
+    lib = N.load()
+    _set_policy_batch(policy_batch)
+    x = _f32c(x); w_deconv = _f32c(w_deconv); b_deconv = _f32c(b_deconv)
+    x_short = _f32c(x_short); w_short = _f32c(w_short); b_short = _f32c(b_short)
+    n, cin, h, w = x.shape
+    cout, cin_short = w_deconv.shape[1], w_short.shape[1]
+    if x_short.shape != (n, cin_short, 2 * h, 2 * w) or w_short.shape != (cout, cin_short, 3, 3) or w_deconv.shape != (cin, cout, 4, 4):
+        raise ValueError("op_deconv_shortcut: shapes %s %s %s %s do not fit" % (x.shape, w_deconv.shape, x_short.shape, w_short.shape))
+    y = np.empty((n, cout, 2 * h, 2 * w), np.float32)
+    N.check(lib.idc_op_deconv_shortcut(device, _PREC[precision], n, cin, h, w, _fptr(x), cout, _fptr(w_deconv), _fptr(b_deconv),
+                                       cin_short, _fptr(x_short), _fptr(w_short), _fptr(b_short), act, _fptr(y)))
     return y

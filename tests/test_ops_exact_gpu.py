@@ -1,0 +1,205 @@
+"""Exact-integer operator tests: every conv template the library ships, at small ragged shapes, bit for bit, with the kernel that ran asserted.
+
+Operands come from the integer lattice of tests/exact_lattice.py, on which bf16, fp16, every part of the split precisions and fp32
+accumulation are exact, so a correct kernel gives the same bits whatever its summation order and the comparison is assert_array_equal
+against one float64 computation plus the storage rounding of the path.  No tolerance appears in this file.  That sees what the Gaussian
+tests (tests/test_ops_gpu.py, 2.5e-2 * (1 + max|ref|) on bf16) cannot: one tap-channel product lost at a tile corner, a halo pixel of the
+neighbouring image, a residual added after the rounding, a truncating store (with cin >= 256 many bf16 outputs are odd integers beyond
+256: exact ties).
+
+Each case first asserts engine.op_last_kernel() against its expected label: the variant is chosen for the case's POLICY batch
+(option op_policy_batch, as a handle's max_batch), the launch carries the small real batch (2 or 3: leakage across images shows).  Shapes
+are what the network's levels produce, ragged against the 32- and 16-wide tiles, the 4*wp-row tiles and the 8x8 / 8x16 Winograd blocks.
+Where the 512-channel trunk needs 256 workgroups for its shipped 8-wave tile the policy batch is 64 or 128 rather than 32: the spatial
+sizes here are a quarter of the network's.
+
+test_shipped_kernels_are_all_in_the_table builds the shipped configurations and fails when their layer tables name a kernel (template
+arguments included) that no case here reaches.  A layer table is filled by a forward's planning pass, so each handle runs ONE single-image
+forward (the variant depends on max_batch, not on the images in the call).
+
+Wall time of this file on an MI355X, as measured there: 4.4 s for its 77 tests (pytest's own figure; 7.8 s with interpreter start-up and
+imports); the slowest are the four census handles at 0.1 - 0.8 s, every exact case is below 0.15 s.
+"""
+import re
+
+import numpy as np
+import pytest
+
+import exact_lattice as xl
+from exact_lattice import case
+from interactive_deep_colorization_amd import _native, engine
+
+pytestmark = pytest.mark.gpu
+
+_OPTION_DEFAULTS = {"op_policy_batch": 0, "winograd": 1, "ds_mfma16": 1, "kwave": 1, "click": -1, "v2p": 1, "fp16_fast": 1, "split_ds_fuse": 1}
+
+CASES = [
+    # ---------------------------------------------------------------- fp32: small tile, click, Winograd
+    case("f32_igemm_leaky_resid", "conv", "fp32", 3, 64, 128, 20, 36, "conv_igemm<f32,2,1>", act=2, resid=True, tile="small", splitk="never"),
+    case("f32_igemm_stride2_splitk", "conv", "fp32", 2, 64, 128, 40, 72, "conv_igemm<f32,2,1> splitK2", in_stride=2, act=1, bn=2.0, tile="small", splitk="always"),
+    case("f32_igemm_1x1_529", "conv", "fp32", 2, 256, 529, 8, 16, "conv_igemm<f32,2,1> splitK8", ksize=1),
+    case("f32_igemm_deconv", "deconv", "fp32", 2, 128, 128, 20, 36, "conv_igemm<f32,2,1>", tile="small", splitk="never"),
+    case("f32_igemm_22_deconv_resid", "deconv", "fp32", 3, 128, 128, 20, 36, "conv_igemm<f32,2,2>", act=1, resid=True, policy=16),
+    case("f32_click_d2", "conv", "fp32", 2, 512, 512, 5, 9, "conv_click<f32,1,2> splitK16", dilation=2, act=1, bn=1.0, policy=1, opts=(("winograd", 0),)),
+    case("f32_click_leaky_resid", "conv", "fp32", 2, 256, 256, 10, 18, "conv_click<f32,1,4> splitK8", act=2, resid=True, policy=1),
+    case("f32_click_deconv", "deconv", "fp32", 2, 128, 128, 20, 36, "conv_click<f32,1,4> splitK4", act=1, resid=True, policy=1),
+    case("f32_wino12", "conv", "fp32", 2, 512, 512, 7, 33, "conv_wino_f32", act=1, bn=0.5, wmul=4, opts=(("winograd", 12),), wino="conv"),
+    case("f32_wino21_d2", "conv", "fp32", 3, 512, 512, 5, 9, "conv_wino_f32", dilation=2, wmul=4, opts=(("winograd", 21),), wino="conv"),
+    case("f32_wino22_stride2_leaky", "conv", "fp32", 3, 64, 128, 40, 72, "conv_wino_f32", in_stride=2, act=2, wmul=4, opts=(("winograd", 22),), wino="conv"),
+    case("f32_wino_auto_2x2", "conv", "fp32", 2, 256, 256, 2, 2, "conv_wino_f32", act=1, wmul=4, policy=1, wino="conv"),
+    case("f32_wino_auto_1x1px", "conv", "fp32", 3, 512, 512, 1, 1, "conv_wino_f32", dilation=2, act=1, bn=2.0, wmul=4, policy=1, wino="conv"),
+    case("f32_wino_deconv", "deconv", "fp32", 2, 512, 256, 5, 9, "conv_wino_deconv_f32", act=1, resid=True, policy=1, wino="deconv"),
+    case("f32_wino_deconv_plain", "deconv", "fp32", 3, 256, 128, 10, 18, "conv_wino_deconv_f32", policy=1, wino="deconv"),
+    # ---------------------------------------------------------------- bf16: small tile, click, K over the waves
+    case("bf16_igemm_leaky_resid", "conv", "bf16", 3, 64, 128, 20, 36, "conv_igemm<bf16,2,1>", act=2, resid=True, tile="small", splitk="never"),
+    case("bf16_igemm_splitk", "conv", "bf16", 2, 128, 128, 20, 36, "conv_igemm<bf16,2,1> splitK2", act=1, bn=2.0, tile="small", splitk="always"),
+    case("bf16_igemm_1x1_529", "conv", "bf16", 2, 256, 529, 8, 16, "conv_igemm<bf16,2,1> splitK4", ksize=1),
+    case("bf16_click_leaky_resid", "conv", "bf16", 2, 256, 256, 10, 18, "conv_click<bf16,1,4> splitK4", act=2, resid=True, policy=1),
+    case("bf16_click_d2_resid", "conv", "bf16", 3, 512, 512, 5, 9, "conv_click<bf16,1,2> splitK8", dilation=2, act=1, bn=0.5, resid=True, policy=1),
+    case("bf16_click_deconv_1chunk", "deconv", "bf16", 2, 64, 128, 20, 36, "conv_click<bf16,1,4>", act=1, policy=1),
+    case("bf16_kwave_1chunk_stride2", "conv", "bf16", 2, 64, 128, 40, 72, "conv_kwave_bf16", in_stride=2, act=1, bn=4.0, policy=1),
+    case("bf16_kwave_2chunks", "conv", "bf16", 3, 128, 128, 20, 36, "conv_kwave_bf16", policy=1),
+    case("bf16_kwave_4chunks_leaky", "conv", "bf16", 2, 256, 256, 10, 18, "conv_kwave_bf16", act=2, policy=1),
+    case("bf16_kwave_4chunks_2x2", "conv", "bf16", 3, 256, 256, 2, 2, "conv_kwave_bf16", act=1, policy=1),
+    case("bf16_kwave_8chunks", "conv", "bf16", 2, 512, 512, 7, 33, "conv_kwave_bf16", act=1, bn=1.0, policy=1),
+    case("bf16_kwave_8chunks_d2", "conv", "bf16", 3, 512, 512, 5, 9, "conv_kwave_bf16", dilation=2, act=1, policy=1),
+    case("bf16_kwave_8chunks_d2_1x1px", "conv", "bf16", 2, 512, 512, 1, 1, "conv_kwave_bf16", dilation=2, act=1, bn=2.0, policy=1),
+    case("bf16_kwave_deconv_2chunks", "deconv", "bf16", 2, 128, 128, 20, 36, "conv_kwave_deconv_bf16", act=1, resid=True, policy=1),
+    case("bf16_kwave_deconv_4chunks", "deconv", "bf16", 3, 256, 128, 10, 18, "conv_kwave_deconv_bf16", policy=1),
+    case("bf16_kwave_deconv_8chunks", "deconv", "bf16", 2, 512, 256, 5, 9, "conv_kwave_deconv_bf16", act=1, resid=True, policy=1),
+    # ---------------------------------------------------------------- bf16: the throughput tiles
+    case("bf16_v2m_24_deconv", "deconv", "bf16", 2, 256, 128, 10, 18, "conv_igemm_v2<2,4>+m16", act=1, policy=32),
+    case("bf16_v2m_42_deconv", "deconv", "bf16", 3, 512, 256, 5, 9, "conv_igemm_v2<4,2>+m16", policy=32),
+    case("bf16_v2m_24_1x1_529", "conv", "bf16", 2, 256, 529, 8, 16, "conv_igemm_v2<2,4>+m16", ksize=1, policy=16, tile="large"),
+    case("bf16_v2m_22_1x1_529", "conv", "bf16", 3, 256, 529, 8, 16, "conv_igemm_v2<2,2>+m16", ksize=1, act=1, bn=2.0, policy=32),
+    case("bf16_v2p_42_halo1", "conv", "bf16", 3, 512, 512, 7, 33, "conv_igemm_v2<4,2>+m16p", act=1, bn=0.5, policy=64),
+    case("bf16_v2p_42_halo2", "conv", "bf16", 2, 512, 512, 5, 9, "conv_igemm_v2<4,2>+m16p", dilation=2, act=1, tile="large"),
+    case("bf16_v2p_42_256ch", "conv", "bf16", 2, 256, 256, 10, 18, "conv_igemm_v2<4,2>+m16p", policy=128),
+    case("bf16_v2p_42_1x1px", "conv", "bf16", 3, 512, 512, 1, 1, "conv_igemm_v2<4,2>+m16p", dilation=2, act=1, bn=2.0, tile="large"),
+    case("bf16_v2p_42_2x2", "conv", "bf16", 2, 256, 256, 2, 2, "conv_igemm_v2<4,2>+m16p", act=1, tile="large"),
+    case("bf16_v2p_22_half_tiles", "conv", "bf16", 3, 128, 128, 20, 36, "conv_igemm_v2<2,2>+m16p", act=1, policy=32),
+    case("bf16_v2p_22_rule22", "conv", "bf16", 3, 64, 128, 40, 72, "conv_igemm_v2<2,2>+m16p", act=1, bn=2.0, policy=32),
+    case("bf16_v2p_22_stride2", "conv", "bf16", 2, 64, 128, 40, 72, "conv_igemm_v2<2,2>+m16p", in_stride=2, policy=32),
+    case("bf16_v2m_22_halo2", "conv", "bf16", 2, 512, 512, 7, 33, "conv_igemm_v2<2,2>+m16", dilation=2, act=1, policy=32),
+    case("bf16_ds_8wave", "fused", "bf16", 2, 512, 256, 5, 9, "conv_ds_fused_m+shortcut 8-wave", cin2=256, act=1, policy=32),
+    case("bf16_ds_8wave_256", "fused", "bf16", 3, 256, 128, 10, 18, "conv_ds_fused_m+shortcut 8-wave", cin2=128, policy=32),
+    case("bf16_ds_half", "fused", "bf16", 2, 128, 128, 20, 36, "conv_ds_fused_m+shortcut half", cin2=64, act=1, policy=32),
+    case("bf16_ds_8wave_forced", "fused", "bf16", 3, 128, 128, 20, 36, "conv_ds_fused_m+shortcut 8-wave", cin2=64, policy=32, opts=(("ds_mfma16", 2),)),
+    case("bf16_v2_42_partner", "conv", "bf16", 3, 512, 512, 7, 33, "conv_igemm_v2<4,2>", act=1, policy=64, opts=(("mfma16", 0),), partner=True),
+    # ---------------------------------------------------------------- fp16: the twins of the bf16 throughput kernels
+    case("fp16_v2ph_42", "conv", "fp16", 3, 512, 512, 7, 33, "conv_igemm_v2ph<4,2>", act=1, bn=0.5, policy=64),
+    case("fp16_v2ph_42_halo2", "conv", "fp16", 2, 512, 512, 5, 9, "conv_igemm_v2ph<4,2>", dilation=2, act=1, policy=128),
+    case("fp16_v2ph_22", "conv", "fp16", 2, 128, 128, 20, 36, "conv_igemm_v2ph<2,2>", policy=32),
+    case("fp16_v2ph_22_stride2", "conv", "fp16", 3, 64, 128, 40, 72, "conv_igemm_v2ph<2,2>", in_stride=2, act=1, bn=2.0, policy=32),
+    case("fp16_v2sh_22_halo2_small", "conv", "fp16", 2, 512, 512, 5, 9, "conv_igemm_v2sh<2,2>x1", dilation=2, act=1),
+    case("fp16_v2psh_leaky_resid", "conv", "fp16", 2, 256, 256, 10, 18, "conv_igemm_v2psh<2,2>x1", act=2, resid=True),
+    case("fp16_v2sh_24_deconv", "deconv", "fp16", 2, 256, 128, 10, 18, "conv_igemm_v2sh<2,4>x1", act=1, resid=True, policy=32),
+    case("fp16_ds_half", "fused", "fp16", 2, 128, 128, 20, 36, "conv_ds_fused_mh+shortcut half", cin2=64, act=1, policy=32),
+    case("fp16_ds_8wave", "fused", "fp16", 3, 512, 256, 5, 9, "conv_ds_fused_mh+shortcut 8-wave", cin2=256, policy=32),
+    # ---------------------------------------------------------------- operand-split precisions
+    case("bf16x3_v2ps_42", "conv", "bf16x3", 3, 512, 512, 7, 33, "conv_igemm_v2ps<4,2>x3", act=1, bn=0.5, policy=64),
+    case("bf16x6_v2ps_42_leaky", "conv", "bf16x6", 2, 256, 256, 10, 18, "conv_igemm_v2ps<4,2>x6", act=2, policy=128),
+    case("fp16x3_v2psh_42_halo2", "conv", "fp16x3", 2, 512, 512, 5, 9, "conv_igemm_v2psh<4,2>x3", dilation=2, act=1, policy=128),
+    case("bf16x3_v2ps_22_split_small", "conv", "bf16x3", 2, 128, 128, 20, 36, "conv_igemm_v2ps<2,2>x3", act=1, resid=True),
+    case("bf16x6_v2ps_22_split_small_1x1px", "conv", "bf16x6", 3, 512, 512, 1, 1, "conv_igemm_v2ps<2,2>x6", act=1, bn=2.0),
+    case("fp16x3_v2psh_22_rule22", "conv", "fp16x3", 2, 64, 128, 40, 72, "conv_igemm_v2psh<2,2>x3", act=1, bn=2.0, policy=32),
+    case("bf16x3_v2ps_22_stride2", "conv", "bf16x3", 3, 64, 128, 40, 72, "conv_igemm_v2ps<2,2>x3", in_stride=2, policy=32),
+    case("bf16x6_v2s_22_halo2_small", "conv", "bf16x6", 2, 512, 512, 5, 9, "conv_igemm_v2s<2,2>x6", dilation=2, act=2),
+    case("fp16x3_v2sh_22_1x1_529", "conv", "fp16x3", 2, 256, 529, 8, 16, "conv_igemm_v2sh<2,2>x3", ksize=1, policy=64),
+    case("bf16x3_v2s_24_deconv", "deconv", "bf16x3", 2, 256, 128, 10, 18, "conv_igemm_v2s<2,4>x3", act=1, resid=True, policy=32),
+    case("fp16x3_v2sh_24_deconv", "deconv", "fp16x3", 3, 128, 128, 20, 36, "conv_igemm_v2sh<2,4>x3", policy=32),
+    case("bf16x6_v2s_42_deconv", "deconv", "bf16x6", 2, 512, 256, 5, 9, "conv_igemm_v2s<4,2>x6", act=1, policy=32),
+    case("bf16x3_ds_ms", "fused", "bf16x3", 2, 128, 128, 20, 36, "conv_ds_fused_ms+shortcut x3", cin2=64, act=1, policy=32),
+    case("bf16x6_ds_ms", "fused", "bf16x6", 2, 512, 256, 5, 9, "conv_ds_fused_ms+shortcut x6", cin2=256, policy=32),
+    case("fp16x3_ds_msh", "fused", "fp16x3", 3, 256, 128, 10, 18, "conv_ds_fused_msh+shortcut x3", cin2=128, act=1, policy=32),
+]
+assert len(set(c.id for c in CASES)) == len(CASES)
+
+
+@pytest.fixture(autouse=True)
+def _reset_policies():
+    yield
+    engine.set_tile_policy("auto")
+    engine.set_splitk_policy("auto")
+    for name, value in _OPTION_DEFAULTS.items():
+        engine.set_option(name, value)
+
+
+def run_case(c, d):
+    """One op call as the case describes it -> (output, the label of the kernel that ran)."""
+    engine.set_tile_policy(c.tile)
+    engine.set_splitk_policy(c.splitk)
+    for name, value in c.opts:
+        engine.set_option(name, value)
+    if c.op == "conv":
+        got = engine.op_conv2d(d["x"], d["w"], d["b"], dilation=c.dilation, in_stride=c.in_stride, act=c.act, bn_scale=d.get("bn_s"),
+                               bn_shift=d.get("bn_t"), resid=d.get("resid"), precision=c.precision, policy_batch=c.policy)
+    elif c.op == "deconv":
+        got = engine.op_deconv4x4s2(d["x"], d["w"], d["b"], act=c.act, resid=d.get("resid"), precision=c.precision, policy_batch=c.policy)
+    else:
+        got = engine.op_deconv_shortcut(d["x"], d["w"], d["b"], d["x2"], d["w2"], d["b2"], act=c.act, precision=c.precision, policy_batch=c.policy)
+    return got, engine.op_last_kernel()
+
+
+@pytest.mark.parametrize("c", CASES, ids=[c.id for c in CASES])
+def test_exact(c):
+    if c.partner:
+        from conftest import has_ab_partners
+        if not has_ab_partners():
+            pytest.skip("partner kernel: -DIDC_AB_PARTNERS build only")
+    d = xl.draw(c)
+    exp = xl.expected(c, d)                      # asserts the lattice bounds and the storage fit before anything runs on the GPU
+    got, label = run_case(c, d)
+    assert label == c.label, "%s ran %r, the table expects %r" % (c.id, label, c.label)
+    xl.compare(got, exp, "%s [%s]" % (c.id, label))
+
+
+# ---- census: what the shipped configurations launch is what the table reaches -----------------------------------------------------------
+SHIPPED = [(32, "bf16"), (32, "fp16x3"), (1, "bf16"), (1, "fp32")]          # 256 x 256: (max_batch, precision)
+# kernels no exact case can reach, each with the test that covers it: model1's kernels and the fused head end in conv1's input pack /
+# the tanh, and the persistent trunk chain is a launch of several layers
+CENSUS_EXCEPTIONS = {
+    "conv1_block_fused": "tests/test_net_gpu.py::test_conv1_1_throughput_kernel",
+    "conv1_1_bf16_kernel": "tests/test_net_gpu.py::test_conv1_1_throughput_kernel",
+    "conv1_1_split_kernel": "tests/test_round6_gpu.py::test_conv1_1_split_kernel_against_the_generic_island",
+    "conv1_2_split_kernel": "tests/test_round6_gpu.py::test_conv1_2_split_kernel_against_the_generic_tile",
+    "conv_kwave_chain_bf16": "tests/test_round5_gpu.py::test_kwave_chain_equals_the_eleven_launches (each of its layers is conv_kwave_bf16, 8 chunks: in the table)",
+}
+CENSUS_EXCEPTION_LAYERS = {
+    # conv1_1 outside model1's fused kernels: conv_igemm / conv_click reading the fused input pack (K = 36 im2col), which no op entry stages
+    "conv1_1": "tests/test_net_gpu.py::test_fp32_matches_reference_golden_layer_by_layer",
+}
+
+
+def normalise(label):
+    """A label without the suffixes that count slices or name a launch form: ' splitK<n>', ' half', ' 8-wave'."""
+    return re.sub(r" (splitK\d+|half|8-wave)$", "", label)
+
+
+def census_misses(rows, table_labels):
+    out = []
+    for r in rows:
+        k = r["kernel"]
+        if r["launches"] <= 0 or not k.startswith("conv") or r["name"] in CENSUS_EXCEPTION_LAYERS:
+            continue
+        if "+head" in k or k.split("<")[0].split(" ")[0] in CENSUS_EXCEPTIONS:
+            continue
+        if normalise(k) not in table_labels:
+            out.append((r["name"], k))
+    return out
+
+
+@pytest.mark.parametrize("max_batch,precision", SHIPPED)
+def test_shipped_kernels_are_all_in_the_table(make_sd, max_batch, precision):
+    from interactive_deep_colorization_amd import workloads
+    table_labels = set(normalise(c.label) for c in CASES if not c.partner)
+    e = engine.HipColorizer(256, 256, max_batch=max_batch, precision=precision)
+    try:
+        e.load_state_dict(make_sd(0, "he"))
+        L, ab, m = workloads.random_batch(1, 256, seed=3)
+        e.forward(L, ab, m, 0.0)                                 # fills the layer table: the planning pass runs with a forward
+        rows = e.layer_table()
+    finally:
+        e.close()
+    missing = census_misses(rows, table_labels)
+    assert not missing, "shipped kernels no exact case reaches (max_batch %d, %s): %s" % (max_batch, precision, missing)
