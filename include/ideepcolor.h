@@ -288,6 +288,25 @@ int idc_dist_at(idc_handle h, int img, int y, int x, float* pdf);
 int idc_get_dist(idc_handle h, int n, float* dist);
 int idc_suggest_colors(idc_handle h, int img, int y, int x, int K, int N, unsigned seed, const float* centres,
                        double* out_centres, double* out_conf, unsigned* out_counts);
+/* ---- Maps of the resident distribution: one streaming pass on the device over what the last forward left there
+ *      ([n,529,H/4,W/4] or [n,313,H,W], see idc_get_dist) instead of a copy of it to the host.  Hd x Wd below is
+ *      H/4 x W/4 for the 529 head and H x W for the 313 head.
+ *      idc_dist_entropy: ent [n,Hd,Wd] = sum_q p log p -- the sign of the reference's compute_entropy
+ *      (colorize_image.py:356-357,545-546), i.e. MINUS the entropy -- logf of the stored fp32 p, products and sum in
+ *      fp64, rounded to fp32 once.  DEVIATION: a bin with p == 0 contributes 0; the reference's numpy expression
+ *      makes that pixel NaN (0 * log 0).
+ *      idc_dist_decode: ab [n,2,Hd,Wd] from centres [B,2] (pts_grid / pts_in_hull), conf [n,Hd,Wd] = p_max (may be
+ *      NULL).  IDC_DECODE_MODE: the centre of the arg-max bin, equal maxima -> the lowest bin index.
+ *      IDC_DECODE_MEAN: w_q = expf(gamma * (logf(p_q) - logf(p_max))), w_q = 0 where p_q == 0;
+ *      ab = sum_q w_q c_q / sum_q w_q, sums in fp64.  gamma = 1 is the plain mean; gamma = 2.6 / S on the 313 head
+ *      is what pred_ab computes (prototxt :826-850) without its bias.  gamma (checked in both modes) must be
+ *      positive and finite.
+ *      Both are deterministic, the result for an image does not depend on n, and the distribution is only read.
+ *      Status: IDC_ERR_UNSUPPORTED when no distribution is resident (no forward yet, no distribution head, a 313
+ *      handle without idc_keep_dist), IDC_ERR_BATCH for n outside 1..(images of the last forward). -------------- */
+enum { IDC_DECODE_MODE = 0, IDC_DECODE_MEAN = 1 };
+int idc_dist_entropy(idc_handle h, int n, float* ent);
+int idc_dist_decode(idc_handle h, int n, int mode, float gamma, const float* centres, float* ab, float* conf);
 int idc_sync(idc_handle h);
 /* The hipStream_t all work of this handle is enqueued on (as void*): a stream of its own, created non-blocking.
  * STREAM ORDERING: idc_forward_device / idc_forward_resident only ENQUEUE on that stream.  A caller that writes the

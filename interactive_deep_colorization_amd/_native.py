@@ -27,6 +27,7 @@ EXPORTED_SYMBOLS = [
     "idc_layer_times_ms", "idc_layer_times_stats", "idc_get_activation", "idc_op_conv2d", "idc_op_deconv4x4s2", "idc_op_deconv_shortcut", "idc_op_last_kernel",
     "idc_set_image_l", "idc_set_hints", "idc_get_hint_planes", "idc_forward_resident",
     "idc_dist_bins", "idc_keep_dist", "idc_dist_at", "idc_get_dist", "idc_suggest_colors",
+    "idc_dist_entropy", "idc_dist_decode",
     "idc_stream_wait", "idc_stream_signal", "idc_alloc_host", "idc_free_host", "idc_forward_async", "idc_wait", "idc_pipeline_times",
     "idc_comm_unique_id", "idc_broadcast_weights", "idc_upsample_lab2rgb",
     "idc_set_range_audit", "idc_range_reset", "idc_range_report", "idc_pack_weights_ex", "idc_load_weights_ex",
@@ -36,6 +37,7 @@ IDC_INTERP_CUBIC, IDC_INTERP_LINEAR, IDC_INTERP_NEAREST = 0, 1, 2
 IDC_SRC_OUTPUT_AB, IDC_SRC_OUTPUT_AB_RAW, IDC_SRC_INPUT_AB = 0, 1, 2
 IDC_UNIQUE_ID_BYTES = 128
 IDC_HINT_AB, IDC_HINT_RGB = 0, 1
+IDC_DECODE_MODE, IDC_DECODE_MEAN = 0, 1
 
 
 class IdcError(RuntimeError):
@@ -141,6 +143,8 @@ def load():
     proto("idc_dist_at", ci, [vp, ci, ci, ci, c_float_p])
     proto("idc_get_dist", ci, [vp, ci, c_float_p])
     proto("idc_suggest_colors", ci, [vp, ci, ci, ci, ci, ci, ctypes.c_uint, c_float_p, vp, vp, vp])
+    proto("idc_dist_entropy", ci, [vp, ci, c_float_p])
+    proto("idc_dist_decode", ci, [vp, ci, ci, cf, c_float_p, c_float_p, c_float_p])
     proto("idc_stream_wait", ci, [vp, vp])
     proto("idc_stream_signal", ci, [vp, vp])
     proto("idc_alloc_host", vp, [csz])

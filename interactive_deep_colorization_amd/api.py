@@ -540,7 +540,52 @@ class ColorizeImageTorch(ColorizeImageBase):
         return self._forward_rgb(self.mask_cent)
 
 
-class ColorizeImageTorchDist(ColorizeImageTorch):
+class _DistMaps(object):
+    """What the two distribution classes read off the device-resident distribution as whole maps.  ``_dist_rep``: the
+    distribution's grid is Xd / _dist_rep (the 529 head predicts at X/4; ``model.py:131`` upsamples nearest);
+    ``_bin_centres()``: the (B, 2) ab value of every bin, as ``get_ab_reccs`` uses."""
+    _dist_rep = 1
+
+    def _up_nearest(self, a):
+        r = self._dist_rep
+        return a if r == 1 else np.repeat(np.repeat(a, r, axis=-2), r, axis=-1)
+
+    def compute_entropy(self):
+        """``dist_entropy`` = ``sum_q p log p`` (``:356-357,545-546``).  While the distribution of the last forward is
+        still on the device alone the sum runs there (``idc_dist_entropy``: fp64 accumulation, a 0 for ``p == 0`` where
+        numpy gives NaN) and ``dist_ab`` is NOT copied out; once ``dist_ab`` has been read, or with an engine that has
+        no ``dist_entropy``, it is the reference's numpy expression."""
+        on_device = getattr(self.net, 'dist_entropy', None) if self._dist_on_device else None
+        if on_device is not None:
+            self.dist_entropy = self._up_nearest(on_device(1)[0])
+        else:
+            self.dist_entropy = np.sum(self.dist_ab * np.log(self.dist_ab), axis=0)
+
+    def get_dist_decode(self, mode='mode', gamma=1.0, return_conf=False):
+        """A colour map of what the classifier believes (not in the reference): ab (2, Xd, Xd) float32 -- ``mode='mode'``
+        the most probable bin's colour, ``mode='mean'`` the mean colour under ``(p / p_max) ** gamma`` (``gamma=1`` the
+        plain mean, larger = sharper; ``2.6 / S`` is the 313 net's own ``pred_ab`` decode) -- and with ``return_conf``
+        also ``p_max`` (Xd, Xd), low where the model is unsure.  Computed on the device (``idc_dist_decode``)."""
+        if not self.dist_ab_set:
+            print('Need to set prediction first')
+            return 0
+        out = self.net.dist_decode(self._bin_centres(), 1, mode=mode, gamma=gamma, want_conf=return_conf)
+        if return_conf:
+            return self._up_nearest(out[0][0]), self._up_nearest(out[1][0])
+        return self._up_nearest(out[0])
+
+    def get_img_dist_decode(self, mode='mode', gamma=1.0):
+        """``get_dist_decode`` as an image: (Xd, Xd, 3) uint8 with the L plane of the current image.  The colour step
+        borrows the engine's staging, so afterwards the display getters take their host route until the next forward."""
+        ab = self.get_dist_decode(mode, gamma)
+        if isinstance(ab, int):
+            return ab
+        rgb, _ = self.net.lab2rgb(self.img_l[None], ab[None], want_lab=False)
+        self._dev_out_valid = False
+        return rgb[0]
+
+
+class ColorizeImageTorchDist(_DistMaps, ColorizeImageTorch):
     """Regression + 529-bin colour distribution and colour suggestions (``:279-372``).
 
     The distribution stays on the device after ``net_forward``: ``get_ab_reccs`` runs there
@@ -575,6 +620,10 @@ class ColorizeImageTorchDist(ColorizeImageTorch):
     dist_ab = _lazy('dist_ab', '_refresh_dist')
     dist_ab_full = _lazy('dist_ab_full', '_refresh_dist')
     dist_ab_grid = _lazy('dist_ab_grid', '_refresh_dist')
+    _dist_rep = 4
+
+    def _bin_centres(self):
+        return self.pts_in_hull
 
     def prep_net(self, gpu_id=None, path='', dist=True, S=.2, state_dict=None):
         ColorizeImageTorch.prep_net(self, gpu_id=gpu_id, path=path, dist=dist, state_dict=state_dict)
@@ -614,9 +663,6 @@ class ColorizeImageTorchDist(ColorizeImageTorch):
         if return_conf:
             return centers, conf
         return centers
-
-    def compute_entropy(self):
-        self.dist_entropy = np.sum(self.dist_ab * np.log(self.dist_ab), axis=0)
 
     def plot_dist_grid(self, h, w):
         import matplotlib.pyplot as plt
@@ -759,7 +805,7 @@ class ColorizeImageCaffeGlobDist(ColorizeImageCaffe):
         return self.output_rgb
 
 
-class ColorizeImageCaffeDist(ColorizeImageCaffe):
+class ColorizeImageCaffeDist(_DistMaps, ColorizeImageCaffe):
     """Caffe model which includes distribution prediction (``:466-561``): the 313-bin net
     ``models/reference_model/deploy_nopred.prototxt``.  ``net_forward`` returns the colourised image built from
     ``pred_ab`` (the annealed-mean decode ``sum_q softmax(2.6 l)_q * pts_in_hull[q]``, prototxt ``:826-850``) and
@@ -807,6 +853,9 @@ class ColorizeImageCaffeDist(ColorizeImageCaffe):
     dist_ab_full = _lazy('dist_ab_full', '_refresh_dist')
     dist_ab_grid = _lazy('dist_ab_grid', '_refresh_dist')
 
+    def _bin_centres(self):
+        return self._centres
+
     def net_forward(self, input_ab, input_mask):
         if ColorizeImageBase.net_forward(self, input_ab, input_mask) == -1:
             return -1
@@ -831,9 +880,6 @@ class ColorizeImageCaffeDist(ColorizeImageCaffe):
         seed = int(np.random.randint(0, 2 ** 31 - 1))
         centers, conf = self.net.suggest_colors(h, w, self._centres, K=K, N_draws=N, seed=seed)
         return (centers, conf) if return_conf else centers
-
-    def compute_entropy(self):
-        self.dist_entropy = np.sum(self.dist_ab * np.log(self.dist_ab), axis=0)
 
     def plot_dist_grid(self, h, w):
         """Plots the (23 x 23 grid) distribution at pixel (h, w) (``:549-555``)."""

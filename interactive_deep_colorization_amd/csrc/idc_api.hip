@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -74,7 +75,7 @@ static void destroy_ctx(idc_context* c) {
     if (c->d_up_L) (void)hipFree(c->d_up_L);
     if (c->h_up_rgb) (void)hipHostFree(c->h_up_rgb);
     if (c->h_up_L) (void)hipHostFree(c->h_up_L);
-    void* dev[] = {c->d_L, c->d_ab, c->d_mask, c->d_out, c->d_dist, c->d_scratch, c->d_glob_in, c->d_glob_vec, c->d_pred_ab, c->d_dist313, c->d_partial, c->d_rgb, c->d_labq, c->d_hints, c->d_centres, c->d_sugg, c->d_sugg_counts, c->d_post_in};
+    void* dev[] = {c->d_L, c->d_ab, c->d_mask, c->d_out, c->d_dist, c->d_scratch, c->d_glob_in, c->d_glob_vec, c->d_pred_ab, c->d_dist313, c->d_partial, c->d_rgb, c->d_labq, c->d_hints, c->d_centres, c->d_sugg, c->d_sugg_counts, c->d_post_in, c->d_map_ab, c->d_map_s};
     for (void* p : dev) if (p) (void)hipFree(p);
     void* host[] = {c->h_in, c->h_out, c->h_dist, c->h_pred_ab, c->h_rgb, c->h_labq, c->h_hints};
     for (void* p : host) if (p) (void)hipHostFree(p);
@@ -370,6 +371,15 @@ int idc_get_dist(idc_handle h, int n, float* dist) {
     return IDC_OK;
 }
 
+// device copy of the caller's bin centres (idc_suggest_colors, idc_dist_decode) and the suggestion results: first use
+static int ensure_centres(idc_context* h) {
+    if (h->d_centres) return IDC_OK;
+    HIPCHK(h, hipMalloc((void**)&h->d_centres, (size_t)kSuggestMaxBins * 2 * 4));
+    HIPCHK(h, hipMalloc((void**)&h->d_sugg, (size_t)kSuggestMaxK * 3 * 8));
+    HIPCHK(h, hipMalloc((void**)&h->d_sugg_counts, (size_t)kSuggestMaxBins * 4));
+    return IDC_OK;
+}
+
 int idc_suggest_colors(idc_handle h, int img, int y, int x, int K, int N, unsigned seed, const float* centres,
                        double* out_centres, double* out_conf, unsigned* out_counts) {
     int B; long long stride; const float* p;
@@ -379,11 +389,8 @@ int idc_suggest_colors(idc_handle h, int img, int y, int x, int K, int N, unsign
     if (K < 1 || K > kSuggestMaxK) return fail(&h->err, IDC_ERR_INVALID_ARG, "K %d outside 1..%d", K, kSuggestMaxK);
     if (N < 1) return fail(&h->err, IDC_ERR_INVALID_ARG, "N must be positive");
     HIPCHK(h, hipSetDevice(h->device));
-    if (!h->d_centres) {
-        HIPCHK(h, hipMalloc((void**)&h->d_centres, (size_t)kSuggestMaxBins * 2 * 4));
-        HIPCHK(h, hipMalloc((void**)&h->d_sugg, (size_t)kSuggestMaxK * 3 * 8));
-        HIPCHK(h, hipMalloc((void**)&h->d_sugg_counts, (size_t)kSuggestMaxBins * 4));
-    }
+    rc = ensure_centres(h);
+    if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipMemcpy(h->d_centres, centres, (size_t)B * 2 * 4, hipMemcpyHostToDevice));
     HIPCHK(h, launch_suggest(p, stride, B, h->d_centres, K, N, seed, h->d_sugg, h->d_sugg + 2 * kSuggestMaxK, h->d_sugg_counts, h->stream));
@@ -391,6 +398,53 @@ int idc_suggest_colors(idc_handle h, int img, int y, int x, int K, int N, unsign
     HIPCHK(h, hipMemcpy(out_centres, h->d_sugg, (size_t)K * 2 * 8, hipMemcpyDeviceToHost));
     HIPCHK(h, hipMemcpy(out_conf, h->d_sugg + 2 * kSuggestMaxK, (size_t)K * 8, hipMemcpyDeviceToHost));
     if (out_counts) HIPCHK(h, hipMemcpy(out_counts, h->d_sugg_counts, (size_t)B * 4, hipMemcpyDeviceToHost));
+    return IDC_OK;
+}
+
+// the whole resident distribution of images 0..n-1: bins, pixels per bin plane, pointer; allocates the handle's result maps on first use
+static int dist_maps_begin(idc_context* h, int n, int* B, int* npix, const float** dist) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (h->dist_n <= 0) return fail(&h->err, IDC_ERR_UNSUPPORTED, "Need to set prediction first (no resident distribution)");
+    if (n <= 0 || n > h->dist_n) return fail(&h->err, IDC_ERR_BATCH, "batch %d outside 1..%d", n, h->dist_n);
+    const bool d313 = (h->flags & IDC_FLAG_DIST313) != 0;
+    *B = d313 ? 313 : 529;
+    *npix = d313 ? h->H * h->W : (h->H / 4) * (h->W / 4);
+    *dist = d313 ? h->d_dist313 : h->d_dist;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->d_map_ab) {
+        HIPCHK(h, hipMalloc((void**)&h->d_map_ab, (size_t)h->max_batch * 2 * (*npix) * 4));
+        HIPCHK(h, hipMalloc((void**)&h->d_map_s, (size_t)h->max_batch * (*npix) * 4));
+    }
+    return IDC_OK;
+}
+
+int idc_dist_entropy(idc_handle h, int n, float* ent) {
+    int B, npix; const float* dist;
+    int rc = dist_maps_begin(h, n, &B, &npix, &dist);
+    if (rc) return rc;
+    if (!ent) return fail(&h->err, IDC_ERR_INVALID_ARG, "null ent");
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, launch_dist_entropy(dist, n, B, npix, h->d_map_s, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(ent, h->d_map_s, (size_t)n * npix * 4, hipMemcpyDeviceToHost));
+    return IDC_OK;
+}
+
+int idc_dist_decode(idc_handle h, int n, int mode, float gamma, const float* centres, float* ab, float* conf) {
+    int B, npix; const float* dist;
+    int rc = dist_maps_begin(h, n, &B, &npix, &dist);
+    if (rc) return rc;
+    if (!centres || !ab) return fail(&h->err, IDC_ERR_INVALID_ARG, "null pointer");
+    if (mode != IDC_DECODE_MODE && mode != IDC_DECODE_MEAN) return fail(&h->err, IDC_ERR_INVALID_ARG, "unknown decode mode %d", mode);
+    if (!std::isfinite(gamma) || gamma <= 0.f) return fail(&h->err, IDC_ERR_INVALID_ARG, "gamma must be positive and finite");
+    rc = ensure_centres(h);
+    if (rc) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(h->d_centres, centres, (size_t)B * 2 * 4, hipMemcpyHostToDevice));
+    HIPCHK(h, launch_dist_decode(dist, n, B, npix, mode, gamma, h->d_centres, h->d_map_ab, conf ? h->d_map_s : nullptr, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(ab, h->d_map_ab, (size_t)n * 2 * npix * 4, hipMemcpyDeviceToHost));
+    if (conf) HIPCHK(h, hipMemcpy(conf, h->d_map_s, (size_t)n * npix * 4, hipMemcpyDeviceToHost));
     return IDC_OK;
 }
 

@@ -157,6 +157,7 @@ struct idc_context {
     int dist_n = 0;                      // images whose distribution is resident from the last forward (0 = none)
     HintRect *d_hints = nullptr, *h_hints = nullptr; int hints_cap = 0;   // click session: hint list staging
     float* d_centres = nullptr; double* d_sugg = nullptr; unsigned* d_sugg_counts = nullptr;   // colour suggestions
+    float *d_map_ab = nullptr, *d_map_s = nullptr;   // idc_dist_decode / idc_dist_entropy results: [max_batch][2][npix], [max_batch][npix] (first use)
     std::vector<char> l_set;             // per image slot: d_L holds an uploaded L plane (idc_forward_resident refuses otherwise)
     hipEvent_t ev_sync = nullptr;        // idc_stream_wait / idc_stream_signal
     // two-slot transfer pipeline (idc_forward_async / idc_wait): each slot owns its device planes

@@ -263,6 +263,13 @@ constexpr int kSuggestMaxBins = 1024, kSuggestMaxK = 16;
 hipError_t launch_suggest(const float* pdf, long long stride, int B, const float* centres, int K, int N, unsigned seed,
                           double* out_centres, double* out_conf, unsigned* out_counts, hipStream_t s);
 
+// Maps of the resident distribution dist [n][B][npix] (idc_session.hip): ent [n][npix] = sum_q p log p (fp64 sum, p == 0 -> 0);
+// decode -> ab [n][2][npix] and conf [n][npix] = p_max (or nullptr): mode 0 the arg-max bin's centre (ties -> lowest bin), mode 1
+// the mean of centres [B][2] under weights (p / p_max)^gamma.  The result of an image does not depend on n.
+hipError_t launch_dist_entropy(const float* dist, int n, int B, int npix, float* ent, hipStream_t s);
+hipError_t launch_dist_decode(const float* dist, int n, int B, int npix, int mode, float gamma, const float* centres, float* ab,
+                              float* conf, hipStream_t s);
+
 // Range audit (idc_audit.hip; idc_set_range_audit): one layer's sticky record in device memory, and the streaming reduction that folds a stored
 // tensor into it -- npix pixels of [parts][Cpad] 16-bit values (bf16, or fp16 when f16; value = sum of the parts) or, parts = 0, of [Cpad] fp32;
 // channels >= C are padding and skipped.  max_abs over the finite values (atomicMax on the bit pattern); |value| >= 65504 counts as saturated in

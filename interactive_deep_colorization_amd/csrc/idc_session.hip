@@ -7,7 +7,11 @@
 //  * colour suggestions -- ColorizeImageTorchDist.get_ab_reccs (data/colorize_image.py:322-354): inverse-CDF
 //    samples of one pixel's predicted distribution, k-means, clusters ordered by occupancy.
 //
-// Both are latency kernels (one pixel per thread / one workgroup); neither touches HBM beyond the planes it writes.
+//  * distribution maps -- ColorizeImageTorchDist / ColorizeImageCaffeDist.compute_entropy (data/colorize_image.py:356-357,
+//    545-546) and a mode / sharpened-mean decode of the classifier's belief (what pred_ab does for the 313 net, prototxt
+//    :826-850), as one streaming pass each over the resident distribution instead of a copy of it to the host.
+//
+// The first two are latency kernels (one pixel per thread / one workgroup); neither touches HBM beyond the planes it writes.
 #include <hip/hip_runtime.h>
 
 #include "idc_kernels.h"
@@ -199,6 +203,122 @@ hipError_t launch_suggest(const float* pdf, long long stride, int B, const float
                           double* out_centres, double* out_conf, unsigned* out_counts, hipStream_t s) {
     hipLaunchKernelGGL(suggest_kernel, dim3(1), dim3(256), 0, s, pdf, stride, B, centres, K, N, seed, out_centres, out_conf,
                        out_counts);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Maps of the resident distribution dist [n][B][npix] fp32 (npix = Hd * Wd; a bin's pixels are contiguous).
+// Geometry of both kernels: blockIdx.y = image, a workgroup owns kDistPix consecutive pixels (lane = pixel: one
+// coalesced 256-byte row per wave load) and its kDistWaves waves split the bins in a FIXED partition -- wave w walks
+// bins [w * chunk, min(B, (w + 1) * chunk)), chunk = ceil(B / kDistWaves), ascending -- so that the 529 head's
+// 4096 pixels at 256x256 still put 512 waves on the device.  The partials meet in LDS and wave 0 folds them in wave
+// order: the result of a pixel is a function of its B values alone (not of n, the grid or the timing).
+// One dword per lane on purpose: a wave's load is already one whole 256-byte row, each element costs a logf and an fp64
+// multiply-add (about as long as its 4 bytes take from HBM), and 16 bytes per lane would quarter the waves of the small
+// head and want a scalar twin for grids that are no multiple of 4 pixels.
+// ------------------------------------------------------------------------------------------------
+constexpr int kDistWaves = 8, kDistPix = 64;
+
+// ent[i][pix] = sum_q p log p (the reference's sign: MINUS the entropy).  logf of the stored fp32 p, product and sum
+// in fp64, one rounding to fp32.  A bin with p == 0 contributes 0 where the reference's numpy expression gives NaN.
+__global__ __launch_bounds__(kDistWaves * kDistPix) void dist_entropy_kernel(const float* __restrict__ dist, int B, int npix,
+                                                                             float* __restrict__ ent) {
+    __shared__ double part[kDistWaves][kDistPix];
+    const int lane = threadIdx.x % kDistPix, w = __builtin_amdgcn_readfirstlane(threadIdx.x / kDistPix);   // wave-uniform: bin indices stay scalar
+    const int pix = blockIdx.x * kDistPix + lane;
+    const bool live = pix < npix;
+    const int chunk = (B + kDistWaves - 1) / kDistWaves;
+    const int b0 = w * chunk, b1 = min(B, b0 + chunk);
+    const float* src = dist + (size_t)blockIdx.y * B * npix + pix;
+    double acc = 0.0;
+    if (live) {
+#pragma unroll 4
+        for (int b = b0; b < b1; ++b) {
+            const float p = src[(size_t)b * npix];
+            if (p != 0.f) acc += (double)p * (double)logf(p);
+        }
+    }
+    part[w][lane] = acc;
+    __syncthreads();
+    if (w == 0 && live) {
+        double s = part[0][lane];
+#pragma unroll
+        for (int k = 1; k < kDistWaves; ++k) s += part[k][lane];
+        ent[(size_t)blockIdx.y * npix + pix] = (float)s;
+    }
+}
+
+hipError_t launch_dist_entropy(const float* dist, int n, int B, int npix, float* ent, hipStream_t s) {
+    hipLaunchKernelGGL(dist_entropy_kernel, dim3((npix + kDistPix - 1) / kDistPix, n), dim3(kDistWaves * kDistPix), 0, s, dist, B, npix, ent);
+    return hipGetLastError();
+}
+
+// ab[i][2][npix] (+ conf[i][npix] = p_max unless nullptr) from centres [B][2].
+//   mode 0 (IDC_DECODE_MODE): the centre of the arg-max bin; equal maxima -> the lowest bin index (strict > inside a
+//                             wave's ascending walk, strict > again over the waves in ascending order).
+//   mode 1 (IDC_DECODE_MEAN): w_q = expf(gamma * (logf(p_q) - logf(p_max))), 0 for p_q == 0; ab = sum w_q c_q / sum w_q,
+//                             the three sums in fp64 (second walk over the same bins: L2 hits).
+__global__ __launch_bounds__(kDistWaves * kDistPix) void dist_decode_kernel(const float* __restrict__ dist, int B, int npix, int mode,
+                                                                            float gamma, const float* __restrict__ centres,
+                                                                            float* __restrict__ ab, float* __restrict__ conf) {
+    __shared__ float wmax[kDistWaves][kDistPix];
+    __shared__ int warg[kDistWaves][kDistPix];
+    __shared__ double part[3][kDistWaves][kDistPix];
+    const int lane = threadIdx.x % kDistPix, w = __builtin_amdgcn_readfirstlane(threadIdx.x / kDistPix);   // wave-uniform: bin indices stay scalar
+    const int pix = blockIdx.x * kDistPix + lane;
+    const bool live = pix < npix;
+    const int chunk = (B + kDistWaves - 1) / kDistWaves;
+    const int b0 = w * chunk, b1 = min(B, b0 + chunk);
+    const float* src = dist + (size_t)blockIdx.y * B * npix + pix;
+    float pm = -1.f; int arg = b0;                 // probabilities are >= 0: the first bin of the walk always takes over
+    if (live) {
+#pragma unroll 4
+        for (int b = b0; b < b1; ++b) {
+            const float p = src[(size_t)b * npix];
+            if (p > pm) { pm = p; arg = b; }
+        }
+    }
+    wmax[w][lane] = pm; warg[w][lane] = arg;
+    __syncthreads();
+    pm = wmax[0][lane]; arg = warg[0][lane];       // every wave needs p_max for its weights
+#pragma unroll
+    for (int k = 1; k < kDistWaves; ++k)
+        if (wmax[k][lane] > pm) { pm = wmax[k][lane]; arg = warg[k][lane]; }
+    float* dst = ab + (size_t)blockIdx.y * 2 * npix + pix;
+    if (mode == 0) {
+        if (w == 0 && live) {
+            dst[0] = centres[2 * arg]; dst[npix] = centres[2 * arg + 1];
+            if (conf) conf[(size_t)blockIdx.y * npix + pix] = pm;
+        }
+        return;
+    }
+    double sw = 0.0, sa = 0.0, sb = 0.0;
+    if (live) {
+        const float lpm = logf(pm);
+#pragma unroll 4
+        for (int b = b0; b < b1; ++b) {
+            const float p = src[(size_t)b * npix];
+            if (p != 0.f) {
+                const double wq = (double)expf(gamma * (logf(p) - lpm));
+                sw += wq; sa += wq * (double)centres[2 * b]; sb += wq * (double)centres[2 * b + 1];
+            }
+        }
+    }
+    part[0][w][lane] = sw; part[1][w][lane] = sa; part[2][w][lane] = sb;
+    __syncthreads();
+    if (w == 0 && live) {
+        sw = part[0][0][lane]; sa = part[1][0][lane]; sb = part[2][0][lane];
+#pragma unroll
+        for (int k = 1; k < kDistWaves; ++k) { sw += part[0][k][lane]; sa += part[1][k][lane]; sb += part[2][k][lane]; }
+        dst[0] = (float)(sa / sw); dst[npix] = (float)(sb / sw);
+        if (conf) conf[(size_t)blockIdx.y * npix + pix] = pm;
+    }
+}
+
+hipError_t launch_dist_decode(const float* dist, int n, int B, int npix, int mode, float gamma, const float* centres, float* ab,
+                              float* conf, hipStream_t s) {
+    hipLaunchKernelGGL(dist_decode_kernel, dim3((npix + kDistPix - 1) / kDistPix, n), dim3(kDistWaves * kDistPix), 0, s, dist, B, npix, mode,
+                       gamma, centres, ab, conf);
     return hipGetLastError();
 }
 

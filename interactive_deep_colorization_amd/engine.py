@@ -545,6 +545,28 @@ class HipColorizer(object):
                                               cnt.ctypes.data_as(vp) if want_counts else None))
         return (oc, of, cnt) if want_counts else (oc, of)
 
+    def _dist_grid(self):
+        return (self.H, self.W) if self.dist_bins() == 313 else (self.H // 4, self.W // 4)
+
+    def dist_entropy(self, n=1):
+        """``sum_q p log p`` (the reference's ``compute_entropy``: MINUS the entropy) of the resident distribution of images
+        0..n-1, on the device: (n,Hd,Wd) float32, Hd x Wd = H/4 x W/4 (529 head) or H x W (313 head).  p == 0 bins add 0."""
+        ent = np.empty((n,) + self._dist_grid(), np.float32)
+        self._chk(self.lib.idc_dist_entropy(self._h, int(n), _fptr(ent)))
+        return ent
+
+    def dist_decode(self, centres, n=1, mode='mode', gamma=1.0, want_conf=False):
+        """A colour map of the resident distribution, on the device: ab (n,2,Hd,Wd) float32 [, conf (n,Hd,Wd) = p_max].
+        ``mode='mode'``: the centre of the most probable bin; ``mode='mean'``: the mean of ``centres`` (B,2) under weights
+        ``(p / p_max) ** gamma`` (1 = plain mean; 2.6 / S = the 313 net's ``pred_ab`` without its bias)."""
+        hd, wd = self._dist_grid()
+        c = _f32c(centres, (self.dist_bins(), 2))
+        ab = np.empty((n, 2, hd, wd), np.float32)
+        conf = np.empty((n, hd, wd), np.float32) if want_conf else None
+        self._chk(self.lib.idc_dist_decode(self._h, int(n), {"mode": N.IDC_DECODE_MODE, "mean": N.IDC_DECODE_MEAN}[mode], float(gamma),
+                                           _fptr(c), _fptr(ab), _fptr(conf) if want_conf else None))
+        return (ab, conf) if want_conf else ab
+
     def global_histogram(self, rgb, centres, want_sat=True):
         """Global statistics of reference image(s) (the reference's global_stats.prototxt): rgb (n,H,W,3) or (H,W,3)
         uint8, centres (313,2) -> (hist (n,313) float32 summing to 1, s_avg (n,) mean HSV saturation or None)."""
