@@ -11,47 +11,44 @@
 
 #include "idc_engine.h"
 
-extern "C" {
+namespace idc {
 
-int idc_num_layers(idc_handle h) { return h ? h->n_timed : 0; }
-
-int idc_layer_info_get(idc_handle h, int layer, idc_layer_info* out) {
-    if (!h || !out) return fail(h ? &h->err : nullptr, IDC_ERR_INVALID_ARG, "null argument");
-    if (layer < 0 || layer >= h->n_timed) return fail(&h->err, IDC_ERR_INVALID_ARG, "layer %d out of range", layer);
+// Row `layer` of the layer table (0 = the global-hints branch, then the layers, the head, the 529-bin softmax) as the last plan_forward left it
+void layer_row(const std::vector<Layer>& layers, const std::vector<Tensor>& tensors, int precision, unsigned flags, int H, int W, int layer, idc_layer_info* out) {
     memset(out, 0, sizeof(*out));
-    const int nl = (int)h->layers.size();
-    const double hw = (double)h->H * h->W;
-    const int eb = elem_bytes(h->precision);
+    const int nl = (int)layers.size();
+    const double hw = (double)H * W;
+    const int eb = elem_bytes(precision);
     if (layer == 0) {
         snprintf(out->name, sizeof(out->name), "glob_branch");
-        snprintf(out->kernel, sizeof(out->kernel), (h->flags & IDC_FLAG_GLOBAL_HINTS) ? "glob_branch_kernel" : "(input pack fused into conv1_1)");
-        out->min_bytes = 0; out->launches = (h->flags & IDC_FLAG_GLOBAL_HINTS) ? 1 : 0;
+        snprintf(out->kernel, sizeof(out->kernel), (flags & IDC_FLAG_GLOBAL_HINTS) ? "glob_branch_kernel" : "(input pack fused into conv1_1)");
+        out->min_bytes = 0; out->launches = (flags & IDC_FLAG_GLOBAL_HINTS) ? 1 : 0;
     } else if (layer <= nl) {
-        const Layer& L = h->layers[layer - 1];
+        const Layer& L = layers[layer - 1];
         snprintf(out->name, sizeof(out->name), "%s", L.spec->name);
         if (L.kernel == kFused) {            // its MACs and bytes are accounted to the launch that runs them
-            for (const Layer& C : h->layers)
+            for (const Layer& C : layers)
                 if (C.fused_short == layer - 1 || C.fused_next == layer - 1) snprintf(out->kernel, sizeof(out->kernel), "fused into %s", C.spec->name);
             out->flops = 0; out->min_bytes = 0; out->launches = 0;
         } else if (L.chained_into >= 0) {    // ran inside the persistent trunk launch headed by another layer (its own MACs stay its own)
-            snprintf(out->kernel, sizeof(out->kernel), "chained into %s", h->layers[L.chained_into].spec->name);
+            snprintf(out->kernel, sizeof(out->kernel), "chained into %s", layers[L.chained_into].spec->name);
             out->flops = L.flops; out->min_bytes = L.min_bytes; out->launches = 0;
         } else if (L.chain_len > 0) {
             snprintf(out->kernel, sizeof(out->kernel), "conv_kwave_chain_bf16 x%d", L.chain_len);
             out->flops = L.flops; out->min_bytes = L.min_bytes; out->launches = 1;
         } else {
-            kernel_label(L, h->precision, out->kernel, sizeof(out->kernel));
+            kernel_label(L, precision, out->kernel, sizeof(out->kernel));
             out->flops = L.flops; out->min_bytes = L.min_bytes; out->launches = 1;
             if (L.fused_next >= 0) {
-                const Layer& P = h->layers[L.fused_next];
+                const Layer& P = layers[L.fused_next];
                 out->flops += P.flops;
-                out->min_bytes += P.min_bytes - 2.0 * (double)h->tensors[L.dst].H * h->tensors[L.dst].W * h->tensors[L.dst].Cpad * eb;
+                out->min_bytes += P.min_bytes - 2.0 * (double)tensors[L.dst].H * tensors[L.dst].W * tensors[L.dst].Cpad * eb;
             }
             if (L.fused_short >= 0) {
-                const Layer& P = h->layers[L.fused_short];
+                const Layer& P = layers[L.fused_short];
                 out->flops += P.flops;
                 // (the shortcut sums are neither written nor read: fp32 in the operand-split graph, bf16 otherwise)
-                out->min_bytes += P.min_bytes - 2.0 * (double)h->tensors[P.dst].H * h->tensors[P.dst].W * h->tensors[P.dst].Cpad * (h->tensors[P.dst].is_f32 ? 4 : eb);
+                out->min_bytes += P.min_bytes - 2.0 * (double)tensors[P.dst].H * tensors[P.dst].W * tensors[P.dst].Cpad * (tensors[P.dst].is_f32 ? 4 : eb);
             }
         }
     } else if (layer == nl + 1) {
@@ -61,9 +58,21 @@ int idc_layer_info_get(idc_handle h, int layer, idc_layer_info* out) {
     } else {
         snprintf(out->name, sizeof(out->name), "dist_softmax");
         snprintf(out->kernel, sizeof(out->kernel), "softmax_nchw_kernel");
-        out->launches = (h->flags & IDC_FLAG_DIST_HEAD) ? 1 : 0;
+        out->launches = (flags & IDC_FLAG_DIST_HEAD) ? 1 : 0;
         out->min_bytes = out->launches ? (hw / 16) * (640 + 529) * 4 : 0;
     }
+}
+
+}  // namespace idc
+
+extern "C" {
+
+int idc_num_layers(idc_handle h) { return h ? h->n_timed : 0; }
+
+int idc_layer_info_get(idc_handle h, int layer, idc_layer_info* out) {
+    if (!h || !out) return fail(h ? &h->err : nullptr, IDC_ERR_INVALID_ARG, "null argument");
+    if (layer < 0 || layer >= h->n_timed) return fail(&h->err, IDC_ERR_INVALID_ARG, "layer %d out of range", layer);
+    layer_row(h->layers, h->tensors, h->precision, h->flags, h->H, h->W, layer, out);
     return IDC_OK;
 }
 
@@ -178,7 +187,7 @@ int idc_layer_times_stats(idc_handle h, float* ms_min, float* ms_median, float* 
 int idc_get_activation(idc_handle h, const char* name, int n, float* out, size_t capacity_floats, int* C, int* H,
                        int* W) {
     if (!h || !name || !out) return fail(h ? &h->err : nullptr, IDC_ERR_INVALID_ARG, "null argument");
-    const int ti = find_tensor(h, name);
+    const int ti = find_tensor(h->tensors, name);
     if (ti < 0) return fail(&h->err, IDC_ERR_INVALID_ARG, "no activation named '%s'", name);
     const Tensor& t = h->tensors[ti];
     if (n <= 0 || n > h->max_batch) return fail(&h->err, IDC_ERR_BATCH, "bad n");
@@ -224,6 +233,9 @@ static thread_local std::string g_op_last_kernel;
 // the 3x3 shortcut conv that rides in a deconv's launch (idc_op_deconv_shortcut): x [n, cin, 2h, 2w], w [cout, cin, 3, 3], b [cout]
 struct ShortcutOp { int cin; const float* x; const float* w; const float* b; };
 
+// One conv / deconv as a one-layer graph -- with `sc`, a two-layer graph: the 3x3 shortcut conv, whose output is the deconv's shortcut sum -- through
+// the network's own plan_forward, bind_layer and launch_kernel.  What is left here: the argument checks, the graph, its parameters staged by LayerBlob
+// offsets (the weight image packed once the kernel is known) and the layout conversions in and out.
 static int run_single_op(int device_id, int precision, LayerSpec spec, int n, int h, int w, const float* x,
                          const float* weight, const float* bias, const float* bn_scale, const float* bn_shift,
                          const float* resid, float* y, const ShortcutOp* sc = nullptr) {
@@ -232,10 +244,10 @@ static int run_single_op(int device_id, int precision, LayerSpec spec, int n, in
     if (rc) return rc;
     if (precision < IDC_FP32 || precision > IDC_FP16) return fail(nullptr, IDC_ERR_INVALID_ARG, "bad precision");
     if (!x || !weight || !bias || !y || n <= 0 || h <= 0 || w <= 0) return fail(nullptr, IDC_ERR_INVALID_ARG, "bad argument");
-    const bool split = is_split(precision);
+    const bool split = is_split(precision), f16 = split_is_f16(precision);
     const int parts = split_parts(precision);
     if (split && !v2_eligible(spec)) return fail(nullptr, IDC_ERR_UNSUPPORTED, "operand-split precisions run the large tile only: cout >= 65");
-    const int kc = kc_elems(precision), eb = elem_bytes(precision);
+    const int kc = kc_elems(precision);
     if (spec.cin % kc) return fail(nullptr, IDC_ERR_UNSUPPORTED, "cin must be a multiple of %d in this precision", kc);
     if (spec.in_stride != 1 && spec.in_stride != 2) return fail(nullptr, IDC_ERR_INVALID_ARG, "in_stride must be 1 or 2");
     if (h % spec.in_stride || w % spec.in_stride) return fail(nullptr, IDC_ERR_INVALID_ARG, "H, W must divide by in_stride");
@@ -245,148 +257,127 @@ static int run_single_op(int device_id, int precision, LayerSpec spec, int n, in
     idc_context* nullctx = nullptr;
     HIPCHK(nullctx, hipSetDevice(device_id));
     HIPCHK(nullctx, init_kernels());
-    Layer L;
-    // the shortcut sum arrives through the `resid` pointer; every eligibility gate of set_geometry reads spec.resid (a 3x3 op with
-    // a residual must not be handed to conv_kwave_bf16 / the Winograd forms, which do not take one -- ADVICE r4)
-    spec.resid = resid ? "resid" : nullptr;
-    // ... and spec.out_f32: the op stores fp32 on the fp32 path only (a.out_f32 below); left at 1, the default library's planner kept every
-    // bf16 op off the large tile, which writes bf16 only, whatever the tile policy asked for
-    spec.out_f32 = (precision == IDC_BF16 || split) ? 0 : 1;
-    L.spec = &spec;
-    L.blob.nkc = spec.cin / kc; L.blob.ncg = cout_pad(spec.cout) / kCoutGroup;
-    L.blob.w_bytes = (size_t)weight_taps(spec.kind) * L.blob.nkc * L.blob.ncg * kWBlockBytes;
-    L.blob.w_off = 0; L.blob.w2_off = (size_t)-1; L.blob.bias_off = L.blob.bn_scale_off = L.blob.bn_shift_off = L.blob.fbias_off = (size_t)-1;
-    const int cpad = cout_pad(spec.cout);
-    // fp32 3x3 stride-1 ops without a shortcut sum take the Winograd kernel exactly as inside the network
-    const bool wino_dc = !split && wino_deconv_eligible(spec) && spec.cin % kc == 0;
-    const bool wino_ok = !split && ((wino_eligible(spec) && spec.cin % kc == 0 && resid == nullptr) || wino_dc);
-    L.blob.w3_off = wino_ok ? 0 : (size_t)-1;
-    L.blob.w3_bytes = wino_ok ? (size_t)spec.cin * cpad * (wino_dc ? 36 : 16) * eb : 0;
-    const size_t wimg_bytes = std::max(L.blob.w_bytes * parts, L.blob.w3_bytes);             // one staging buffer serves either image
-    L.lprec = precision; L.split = split;
-    const int Hs = h / spec.in_stride, Ws = w / spec.in_stride;
-    const int so = spec.kind == kDeconv4x4 ? 2 : 1;
-    const int Ho = Hs * so, Wo = Ws * so;
-    fill_taps(L);
-    // (default library: the large tile only where conv_igemm_v2m / v2p cover the launch -- no shortcut sum, no LeakyReLU without the fused head)
-    set_geometry(L, precision, n, n_policy, Hs, Ws, kAbPartners || is_split(precision) || (resid == nullptr && spec.act != 2));
-    const size_t wcount = (size_t)spec.cin * spec.cout * (spec.kind == kDeconv4x4 ? 16 : spec.kind == kConv1x1 ? 1 : 9);
-    int op_wexp = (split_is_f16(precision) && parts > 1) ? f16_weight_exponent(weight, wcount) : 0;      // as the blob packer does per layer
-    // deconv + shortcut conv in one launch: run_graph's conditions for the pair (the large tile, conv_ds_fused's domain), else the network runs two launches
-    LayerSpec spec2{"op_short", "op_short", nullptr, kConv3x3, sc ? sc->cin : 0, spec.cout, 1, 1, 0, "x_short", nullptr, 1, 1, 0};
-    LayerBlob blob2 = L.blob;
-    if (sc) {
-        blob2.nkc = sc->cin / kc;
-        blob2.w_bytes = (size_t)weight_taps(kConv3x3) * blob2.nkc * blob2.ncg * kWBlockBytes;
-        const bool fits = split ? conv_ds_m_fits(Hs, Ws, L.blob.nkc * parts, blob2.nkc * parts) : conv_ds_m_fits(Hs, Ws, L.blob.nkc, blob2.nkc);
-        if (L.kernel != kConvV2 || !fuse_shortcut_enabled() || (split && !options().split_ds_fuse) || spec.cout % 128 != 0 || spec.act == 2 ||
-            (!kAbPartners && !split && !(options().ds_m16 != 0 && fits)) || (split && !fits))
-            return fail(nullptr, IDC_ERR_UNSUPPORTED, "deconv + shortcut: the network runs this pair as two launches here (policy batch %d, options)", n_policy);
-        L.fused_short = 0;
-        if (split_is_f16(precision) && parts > 1) {      // one accumulator set, one accumulator scale: the smaller of the two weight exponents, as the blob packer does
-            const int e2 = f16_weight_exponent(sc->w, (size_t)sc->cin * spec.cout * 9);
-            if (e2 < op_wexp) op_wexp = e2;
-        }
+    // tensors as a network of this precision stores them: fp32 on the fp32 path, the shortcut sum bf16 on the bf16 path and fp32 on the operand-split ones
+    const int so = spec.kind == kDeconv4x4 ? 2 : 1, Ho = h / spec.in_stride * so, Wo = w / spec.in_stride * so, cpad = cout_pad(spec.cout);
+    std::vector<Tensor> T;
+    auto add_tensor = [&](const char* name, int C, int Cpad, int H, int W, bool f32) {
+        Tensor t;
+        t.name = name; t.C = C; t.Cpad = Cpad; t.H = H; t.W = W; t.is_f32 = f32; t.parts = (split && !f32) ? parts : 1;
+        t.bytes = (size_t)n * H * W * Cpad * (f32 ? 4 : 2 * t.parts);
+        T.push_back(t);
+        return (int)T.size() - 1;
+    };
+    const int t_x = add_tensor("x", spec.cin, spec.cin, h, w, precision == IDC_FP32), t_y = add_tensor("y", spec.cout, cpad, Ho, Wo, precision == IDC_FP32);
+    const int t_r = (resid || sc) ? add_tensor("resid", spec.cout, cpad, Ho, Wo, precision != IDC_BF16) : -1;      // (with sc: planned, never stored)
+    const int t_x2 = sc ? add_tensor("x_short", sc->cin, sc->cin, Ho, Wo, precision == IDC_FP32) : -1;
+    // layers, their parameters placed in one staging blob
+    size_t blob_bytes = 0;
+    auto place = [&](size_t bytes) { const size_t off = blob_bytes; blob_bytes += align_up(bytes, 256); return off; };
+    std::vector<Layer> layers;
+    auto add_layer = [&](const LayerSpec& s, int src, int dst, int res) -> Layer& {
+        Layer L;
+        L.spec = &s; L.src = src; L.dst = dst; L.resid = res; L.lprec = precision; L.split = split;
+        LayerBlob& lb = L.blob = LayerBlob{};
+        lb.nkc = s.cin / kc; lb.ncg = cout_pad(s.cout) / kCoutGroup; lb.parts = parts;
+        lb.w_bytes = (size_t)weight_taps(s.kind) * lb.nkc * lb.ncg * kWBlockBytes;
+        // fp32 3x3 stride-1 ops without a shortcut sum and fp32 deconvs may take a Winograd kernel, exactly as inside the network: one slot serves either
+        // image, and either layout of the direct one (the kernel decides; the packer runs after the plan)
+        const bool wino = precision == IDC_FP32 && (wino_eligible(s) || wino_deconv_eligible(s));
+        lb.w3_bytes = wino ? (size_t)s.cin * cout_pad(s.cout) * (s.kind == kDeconv4x4 ? 36 : 16) * 4 : 0;
+        lb.w_off = lb.w2_off = place(std::max(lb.w_bytes * parts, lb.w3_bytes));
+        lb.w3_off = wino ? lb.w_off : (size_t)-1;
+        lb.bias_off = lb.bn_scale_off = lb.bn_shift_off = lb.fbias_off = (size_t)-1;
+        fill_taps(L);
+        layers.push_back(L);
+        return layers.back();
+    };
+    // the shortcut sum arrives as a tensor; every eligibility gate of set_geometry reads spec.resid (a 3x3 op with a residual must not be handed
+    // to conv_kwave_bf16 / the Winograd forms, which do not take one -- ADVICE r4)
+    spec.resid = t_r >= 0 ? "resid" : nullptr;
+    const LayerSpec spec2{"op_short", "op_short", nullptr, kConv3x3, sc ? sc->cin : 0, spec.cout, 1, 1, 0, "x_short", nullptr, 0, 1, 0};
+    layers.reserve(2);
+    if (sc) add_layer(spec2, t_x2, t_r, -1);
+    Layer& op = add_layer(spec, t_x, t_y, t_r);
+    op.blob.bias_off = place((size_t)cpad * 4);
+    if (sc) op.blob.fbias_off = place((size_t)cpad * 4);
+    if (bn_scale) { op.blob.bn_scale_off = place((size_t)cpad * 4); op.blob.bn_shift_off = place((size_t)cpad * 4); }
+    if (split) op.blob.wscale_off = place(4);
+    const size_t zeros_off = place(256);
+    // IDC_FP16X3: the weight parts hold w * 2^e, as the blob packer does per layer; one accumulator set, one scale: the smaller exponent of a fused pair
+    int op_wexp = 0;
+    if (f16 && parts > 1) {
+        op_wexp = f16_weight_exponent(weight, (size_t)spec.cin * spec.cout * weight_taps(spec.kind));
+        if (sc) op_wexp = std::min(op_wexp, f16_weight_exponent(sc->w, (size_t)sc->cin * spec.cout * 9));
     }
-    std::vector<float> hb(cpad, 0.f), hs(cpad, 1.f), ht(cpad, 0.f);
-    for (int c = 0; c < spec.cout; ++c) {
-        hb[c] = bias[c] + (sc ? sc->b[c] : 0.f);
-        if (bn_scale) { hs[c] = bn_scale[c]; ht[c] = bn_shift ? bn_shift[c] : 0.f; }
+    const std::vector<float> wscale(layers.size(), ldexpf(1.f, -op_wexp));
+    PlanEnv pe;
+    pe.precision = precision; pe.H = h; pe.W = w; pe.max_batch = n_policy; pe.n = n; pe.wscale = &wscale;
+    rc = plan_forward(layers, T, pe, nullptr);
+    if (rc) return rc;
+    if (sc && op.fused_short < 0)
+        return fail(nullptr, IDC_ERR_UNSUPPORTED, "deconv + shortcut: the network runs this pair as two launches here (policy batch %d, options)", n_policy);
+    if (sc && op.kernel == kConvDs) return fail(nullptr, IDC_ERR_UNSUPPORTED, "deconv + shortcut: conv_ds_fused (the 32x32x16-MFMA partner) has no single-operator entry");
+    // parameters: the weight images the chosen kernel reads, biases (padding 0), BN (padding 1, 0), the accumulator scale, the zero page
+    std::vector<uint8_t> blob(blob_bytes, 0);
+    auto floats = [&](size_t off) { return (float*)(blob.data() + off); };
+    for (const Layer& L : layers) {
+        const float* wsrc = &L == &op ? weight : sc->w;
+        uint8_t* wimg = blob.data() + L.blob.w_off;
+        if (L.kernel == kDeconvWino) pack_wino_deconv_weights(wimg, precision, *L.spec, L.blob, wsrc);
+        else if (L.kernel == kConvWino) pack_wino_weights(wimg, precision, *L.spec, L.blob, wsrc);
+        else
+            for (int part = 0; part < parts; ++part)
+                pack_layer_weights(wimg + (size_t)part * L.blob.w_bytes, precision, L.kernel == kConvV2 ? 2 : 1, *L.spec, L.blob, wsrc, part, ldexpf(1.f, op_wexp));
     }
-    DevBuf d_x, d_xn, d_w, d_b, d_s, d_t, d_r, d_rn, d_yn, d_y, d_x2, d_x2n, d_w2;
-    const size_t xin = (size_t)n * spec.cin * h * w, yout = (size_t)n * spec.cout * Ho * Wo;
-    HIPCHK(nullctx, d_x.alloc(xin * 4));
-    HIPCHK(nullctx, d_xn.alloc(xin * eb * parts));
-    HIPCHK(nullctx, d_w.alloc(wimg_bytes));
-    HIPCHK(nullctx, d_b.alloc(cpad * 4)); HIPCHK(nullctx, d_s.alloc(cpad * 4)); HIPCHK(nullctx, d_t.alloc(cpad * 4));
-    HIPCHK(nullctx, d_yn.alloc((size_t)n * Ho * Wo * cpad * (split ? 2 * parts : 4)));
-    HIPCHK(nullctx, d_y.alloc(yout * 4));
-    HIPCHK(nullctx, hipMemcpy(d_x.p, x, xin * 4, hipMemcpyHostToDevice));
-    HIPCHK(nullctx, hipMemcpy(d_b.p, hb.data(), cpad * 4, hipMemcpyHostToDevice));
-    HIPCHK(nullctx, hipMemcpy(d_s.p, hs.data(), cpad * 4, hipMemcpyHostToDevice));
-    HIPCHK(nullctx, hipMemcpy(d_t.p, ht.data(), cpad * 4, hipMemcpyHostToDevice));
-    if (split) HIPCHK(nullctx, launch_nchw_to_split((const float*)d_x.p, d_xn.p, n, spec.cin, h, w, spec.cin, parts, split_is_f16(precision) ? 1 : 0, nullptr));
-    else HIPCHK(nullctx, launch_nchw_to_nhwc(precision, (const float*)d_x.p, d_xn.p, n, spec.cin, h, w, spec.cin, nullptr));
-    // bf16 precision: the residual arrives and the output leaves in bf16, as inside the network (operand-split: fp32 residual, split output)
-    const int io_bf16 = precision == IDC_BF16 ? 1 : 0;
-    if (resid) {
-        HIPCHK(nullctx, d_r.alloc(yout * 4));
-        HIPCHK(nullctx, d_rn.alloc((size_t)n * Ho * Wo * cpad * 4));
-        HIPCHK(nullctx, hipMemcpy(d_r.p, resid, yout * 4, hipMemcpyHostToDevice));
-        HIPCHK(nullctx, launch_nchw_to_nhwc(io_bf16, (const float*)d_r.p, d_rn.p, n, spec.cout, Ho, Wo, cpad, nullptr));
+    for (int c = 0; c < cpad; ++c) {
+        const bool real = c < spec.cout;
+        floats(op.blob.bias_off)[c] = real ? bias[c] : 0.f;
+        if (sc) floats(op.blob.fbias_off)[c] = real ? bias[c] + sc->b[c] : 0.f;
+        if (bn_scale) { floats(op.blob.bn_scale_off)[c] = real ? bn_scale[c] : 1.f; floats(op.blob.bn_shift_off)[c] = (real && bn_shift) ? bn_shift[c] : 0.f; }
     }
-    ConvArgs& a = L.args;
-    a.in = d_xn.p; a.out = d_yn.p; a.wgt = d_w.p; a.bias = (const float*)d_b.p;
-    a.bn_scale = bn_scale ? (const float*)d_s.p : nullptr;
-    a.bn_shift = bn_scale ? (const float*)d_t.p : nullptr;
-    a.resid = resid ? d_rn.p : nullptr;
-    a.resid_bf16 = io_bf16;
-    a.head_w = nullptr; a.head_b = nullptr; a.head_out = nullptr; a.head_mul = 0.f;
-    a.in2 = nullptr; a.wgt2 = nullptr; a.nkc2 = 0;
-    if (sc) {              // bound as run_graph binds a layer's fused_short
-        const size_t x2n = (size_t)n * sc->cin * Ho * Wo;
-        HIPCHK(nullctx, d_x2.alloc(x2n * 4));
-        HIPCHK(nullctx, d_x2n.alloc(x2n * eb * parts));
-        HIPCHK(nullctx, d_w2.alloc(blob2.w_bytes * parts));
-        HIPCHK(nullctx, hipMemcpy(d_x2.p, sc->x, x2n * 4, hipMemcpyHostToDevice));
-        if (split) HIPCHK(nullctx, launch_nchw_to_split((const float*)d_x2.p, d_x2n.p, n, sc->cin, Ho, Wo, sc->cin, parts, split_is_f16(precision) ? 1 : 0, nullptr));
-        else HIPCHK(nullctx, launch_nchw_to_nhwc(precision, (const float*)d_x2.p, d_x2n.p, n, sc->cin, Ho, Wo, sc->cin, nullptr));
-        a.in2 = d_x2n.p; a.wgt2 = d_w2.p; a.nkc2 = blob2.nkc;
-        if (split) a.w_part_bytes2 = blob2.w_bytes;
-    }
-    a.warm = options().code_warm;
-    a.split_f16 = split_is_f16(precision) ? 1 : 0;
-    a.out_f32 = (io_bf16 || split) ? 0 : 1;
-    if (split) {
-        a.in_parts = parts; a.out_parts = parts; a.nseg = split_segments(precision); a.seg_x = split_seg_x(precision); a.seg_w = split_seg_w(precision);
-        a.w_part_bytes = L.blob.w_bytes;
-    }
-    DevBuf d_part, d_zero, d_wsc;
-    a.acc_scale = nullptr;
-    if (split && split_is_f16(precision)) {
-        const float sc = ldexpf(1.f, -op_wexp);
-        HIPCHK(nullctx, d_wsc.alloc(256));
-        HIPCHK(nullctx, hipMemcpy(d_wsc.p, &sc, 4, hipMemcpyHostToDevice));
-        a.acc_scale = (const float*)d_wsc.p;
-    }
-    if (a.ksplit > 1) {
-        HIPCHK(nullctx, d_part.alloc((size_t)a.ksplit * n * Ho * Wo * cpad * 4));
-        a.partial = (float*)d_part.p;
-    }
-    HIPCHK(nullctx, d_zero.alloc(256));
-    HIPCHK(nullctx, hipMemset(d_zero.p, 0, 256));
-    a.zeros = d_zero.p;
-    // the kernel the network launches for this layer at batch n, and the weight image it reads
-    L.kernel = choose_kernel(L, precision, n_policy);
-    if (sc) {
-        if (L.kernel == kConvDs) return fail(nullptr, IDC_ERR_UNSUPPORTED, "deconv + shortcut: conv_ds_fused (the 32x32x16-MFMA partner) has no single-operator entry");
-        std::vector<uint8_t> wimg2(blob2.w_bytes * parts);
-        for (int part = 0; part < parts; ++part)
-            pack_layer_weights(wimg2.data() + (size_t)part * blob2.w_bytes, precision, 1, spec2, blob2, sc->w, part, ldexpf(1.f, op_wexp));
-        HIPCHK(nullctx, hipMemcpy(d_w2.p, wimg2.data(), wimg2.size(), hipMemcpyHostToDevice));
-    }
-    {
-        char k[64]; kernel_label(L, precision, k, sizeof(k));
-        g_op_last_kernel = k;
-        if (L.kernel == kConvDsM) g_op_last_kernel += conv_ds_m_half(a) ? " half" : " 8-wave";
-    }
-    std::vector<uint8_t> wimg(wimg_bytes);
-    if (L.kernel == kDeconvWino) pack_wino_deconv_weights(wimg.data(), precision, spec, L.blob, weight);
-    else if (L.kernel == kConvWino) pack_wino_weights(wimg.data(), precision, spec, L.blob, weight);
-    else
-        for (int part = 0; part < parts; ++part)
-            pack_layer_weights(wimg.data() + (size_t)part * L.blob.w_bytes, precision, L.kernel == kConvV2 ? 2 : 1, spec, L.blob, weight, part, ldexpf(1.f, op_wexp));
-    HIPCHK(nullctx, hipMemcpy(d_w.p, wimg.data(), wimg_bytes, hipMemcpyHostToDevice));
-    const hipError_t le = launch_kernel(L.kernel, L, a, nullptr);
-    if (le == hipErrorInvalidConfiguration) {
-        char k[64]; kernel_label(L, precision, k, sizeof(k));
-        return fail(nullptr, IDC_ERR_INTERNAL, "single op: %s planned for a launch it does not cover", k);
-    }
+    if (split) *floats(op.blob.wscale_off) = wscale[0];
+    DevBuf d_blob, d_part, d_nchw;
+    std::vector<DevBuf> d_t(T.size());
+    HIPCHK(nullctx, d_blob.alloc(blob_bytes));
+    HIPCHK(nullctx, hipMemcpy(d_blob.p, blob.data(), blob_bytes, hipMemcpyHostToDevice));
+    // fp32 NCHW on the host -> the tensor's storage on the device
+    auto upload = [&](int ti, const float* src) -> int {
+        Tensor& t = T[ti];
+        const size_t count = (size_t)n * t.C * t.H * t.W;
+        DevBuf raw;
+        HIPCHK(nullctx, raw.alloc(count * 4));
+        HIPCHK(nullctx, d_t[ti].alloc(t.bytes));
+        t.ptr = d_t[ti].p;
+        HIPCHK(nullctx, hipMemcpy(raw.p, src, count * 4, hipMemcpyHostToDevice));
+        if (t.parts > 1 || (split && !t.is_f32)) HIPCHK(nullctx, launch_nchw_to_split((const float*)raw.p, t.ptr, n, t.C, t.H, t.W, t.Cpad, t.parts, f16 ? 1 : 0, nullptr));
+        else HIPCHK(nullctx, launch_nchw_to_nhwc(t.is_f32 ? IDC_FP32 : IDC_BF16, (const float*)raw.p, t.ptr, n, t.C, t.H, t.W, t.Cpad, nullptr));
+        HIPCHK(nullctx, hipDeviceSynchronize());          // (raw is freed on return)
+        return IDC_OK;
+    };
+    rc = upload(t_x, x);
+    if (rc == IDC_OK && resid) rc = upload(t_r, resid);
+    if (rc == IDC_OK && sc) rc = upload(t_x2, sc->x);
+    if (rc) return rc;
+    Tensor& ty = T[t_y];
+    HIPCHK(nullctx, d_t[t_y].alloc(ty.bytes));
+    ty.ptr = d_t[t_y].p;
+    const ConvArgs& a = op.args;
+    if (a.ksplit > 1) HIPCHK(nullctx, d_part.alloc((size_t)a.ksplit * n * Ho * Wo * cpad * 4));
+    BindEnv be;
+    be.blob = (const uint8_t*)d_blob.p; be.tensors = &T; be.zeros = be.blob + zeros_off; be.partial = (float*)d_part.p;
+    bind_layer(layers, (int)layers.size() - 1, be);
+    char k[64]; kernel_label(op, precision, k, sizeof(k));
+    g_op_last_kernel = k;
+    if (op.kernel == kConvDsM) g_op_last_kernel += conv_ds_m_half(a) ? " half" : " 8-wave";
+    const hipError_t le = launch_kernel(op.kernel, op, a, nullptr);
+    if (le == hipErrorInvalidConfiguration) return fail(nullptr, IDC_ERR_INTERNAL, "single op: %s planned for a launch it does not cover", k);
     HIPCHK(nullctx, le);
     if (a.ksplit > 1) HIPCHK(nullctx, launch_splitk_epilogue(precision, a, nullptr));
-    if (split) HIPCHK(nullctx, launch_split_to_nchw(d_yn.p, (float*)d_y.p, n, spec.cout, Ho, Wo, cpad, parts, split_is_f16(precision) ? 1 : 0, nullptr));
-    else HIPCHK(nullctx, launch_nhwc_to_nchw(io_bf16, d_yn.p, (float*)d_y.p, n, spec.cout, Ho, Wo, cpad, nullptr));
-    HIPCHK(nullctx, hipMemcpy(y, d_y.p, yout * 4, hipMemcpyDeviceToHost));
+    const size_t yout = (size_t)n * spec.cout * Ho * Wo;
+    HIPCHK(nullctx, d_nchw.alloc(yout * 4));
+    if (split) HIPCHK(nullctx, launch_split_to_nchw(ty.ptr, (float*)d_nchw.p, n, spec.cout, Ho, Wo, cpad, parts, f16 ? 1 : 0, nullptr));
+    else HIPCHK(nullctx, launch_nhwc_to_nchw(ty.is_f32 ? 0 : 1, ty.ptr, (float*)d_nchw.p, n, spec.cout, Ho, Wo, cpad, nullptr));
+    HIPCHK(nullctx, hipMemcpy(y, d_nchw.p, yout * 4, hipMemcpyDeviceToHost));
     HIPCHK(nullctx, hipDeviceSynchronize());
     return IDC_OK;
 }
@@ -397,8 +388,9 @@ int idc_op_conv2d(int device_id, int precision, int n, int cin, int h, int w, co
     if (ksize != 3 && ksize != 1) return fail(nullptr, IDC_ERR_UNSUPPORTED, "ksize must be 1 or 3");
     if (dilation != 1 && dilation != 2) return fail(nullptr, IDC_ERR_UNSUPPORTED, "dilation must be 1 or 2");
     if (ksize == 1 && (dilation != 1 || in_stride != 1)) return fail(nullptr, IDC_ERR_UNSUPPORTED, "1x1 conv: d=1, stride 1 only");
+    // (out_f32 = 0 in the three specs below: an op's storage is its output tensor's; the planner keeps fp32-OUTPUT layers off the bf16 large tile)
     LayerSpec s{"op", "op", nullptr, ksize == 3 ? kConv3x3 : kConv1x1, cin, cout, dilation, in_stride, act,
-                "x", nullptr, 1, 1, 0};
+                "x", nullptr, 0, 1, 0};
     return run_single_op(device_id, precision, s, n, h, w, x, weight, bias, bn_scale, bn_shift, resid, y);
 }
 
@@ -410,14 +402,14 @@ int idc_op_last_kernel(char* out, int cap) {
 
 int idc_op_deconv_shortcut(int device_id, int precision, int n, int cin, int h, int w, const float* x, int cout, const float* w_deconv,
                            const float* b_deconv, int cin_short, const float* x_short, const float* w_short, const float* b_short, int act, float* y) {
-    LayerSpec s{"op", "op", nullptr, kDeconv4x4, cin, cout, 1, 1, act, "x", nullptr, 1, 1, 0};
+    LayerSpec s{"op", "op", nullptr, kDeconv4x4, cin, cout, 1, 1, act, "x", nullptr, 0, 1, 0};
     const ShortcutOp sc{cin_short, x_short, w_short, b_short};
     return run_single_op(device_id, precision, s, n, h, w, x, w_deconv, b_deconv, nullptr, nullptr, nullptr, y, &sc);
 }
 
 int idc_op_deconv4x4s2(int device_id, int precision, int n, int cin, int h, int w, const float* x, int cout,
                        const float* weight, const float* bias, int act, const float* resid, float* y) {
-    LayerSpec s{"op", "op", nullptr, kDeconv4x4, cin, cout, 1, 1, act, "x", nullptr, 1, 1, 0};
+    LayerSpec s{"op", "op", nullptr, kDeconv4x4, cin, cout, 1, 1, act, "x", nullptr, 0, 1, 0};
     return run_single_op(device_id, precision, s, n, h, w, x, weight, bias, nullptr, nullptr, resid, y);
 }
 

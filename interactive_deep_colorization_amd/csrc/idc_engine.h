@@ -50,16 +50,39 @@ struct Layer {
     int src = -1, dst = -1, resid = -1;
     int halo = 0;
     ConvConfig cfg{2, 2};
-    Kernel kernel = kConvIgemm;          // set_geometry's tile family until choose_kernel names the entry point (per forward)
+    Kernel kernel = kConvIgemm;          // the entry point this forward launches (plan_forward: set_geometry's tile family, then choose_kernel)
     int chain_len = 0;                   // > 0: this layer and the chain_len - 1 after it ran as ONE conv_kwave_chain_bf16 launch (last forward)
     int chained_into = -1;               // >= 0: ran inside the chain launch headed by that layer (last forward)
     bool fused_head = false;             // conv10_2 only: model_out + tanh run in this layer's epilogue
+    bool shifted = false;                // conv4_3 under global hints: the branch's per-image vector is added in this layer's epilogue
     int fused_short = -1;                // deconv layers: index of the shortcut conv layer riding in this launch's K loop
     int fused_next = -1;                 // conv1_1 only: index of conv1_2 when model1 runs as one launch (conv1_block_fused)
     int lprec = 0;                       // the precision this layer's kernels run in (the handle's; IDC_FP32 on the fp32 island of a split handle)
     bool split = false;                  // operand-split launch (conv_igemm_v2s / conv_igemm_v2ps)
-    ConvArgs args{};                     // zero-initialised; pointers patched per forward where they depend on weights
+    ConvArgs args{};                     // zero-initialised; who writes which field: the table above plan_forward (idc_plan.hip)
     double flops = 0, min_bytes = 0;
+};
+
+// What a forward's plan is a function of, besides the layers, the tensors' shapes and options(): no pointer among it.
+struct PlanEnv {
+    int precision = 0;
+    unsigned flags = 0;
+    int H = 0, W = 0, max_batch = 0, n = 0;      // max_batch: the batch the kernel variants are chosen for; n: the batch launched
+    int t_conv10_2 = -1, t_conv4_3 = -1;         // tensor indices: the regression head's input, the global-hints shift's target (-1: not in this graph)
+    const std::vector<float>* wscale = nullptr;  // accumulator-scale word per layer (operand-split blobs), or nullptr
+};
+
+// Where a launch's pointers come from: the parameter blob, the tensors and the call's I/O planes.
+struct BindEnv {
+    const uint8_t* blob = nullptr;
+    size_t head_w_off = 0, head_b_off = 0;       // model_out's parameters in the blob
+    const std::vector<Tensor>* tensors = nullptr;
+    const void* zeros = nullptr;
+    const float* glob_vec = nullptr;             // global hints: the branch's [N][512] output
+    float* partial = nullptr;                    // split-K slice sums (the caller sized them for the layer it binds)
+    const float *L = nullptr, *ab = nullptr, *mask = nullptr;      // the call's input planes ...
+    float l_div = 100.f, ab_div = 110.f, mask_mul = 1.f, mask_cent = 0.f;
+    float* out = nullptr; float out_mul = 110.f;                   // ... and its ab map
 };
 
 struct DevBuf {
@@ -219,17 +242,17 @@ void pack_wino_deconv_weights(uint8_t* img, int precision, const LayerSpec& s, c
 int verify_device_blob(idc_context* h, const void* dev_blob, size_t blob_bytes);
 
 // idc_plan.hip
-int find_tensor(idc_context* c, const char* name);
-bool fuse_shortcut_enabled();
+int find_tensor(const std::vector<Tensor>& tensors, const char* name);
 void fill_taps(Layer& L);
-void set_geometry(Layer& L, int precision, int n, int n_policy, int Hs, int Ws, bool allow_v2 = true);
-Kernel choose_kernel(const Layer& L, int precision, int max_batch);
+int plan_forward(std::vector<Layer>& layers, const std::vector<Tensor>& tensors, const PlanEnv& env, std::string* err);
 hipError_t launch_kernel(Kernel k, const Layer& L, const ConvArgs& a, hipStream_t s);
 void kernel_label(const Layer& L, int precision, char* out, size_t cap);
+int build_layers(const BlobPlan& plan, int precision, int H, int W, int max_batch, std::vector<Tensor>& tensors, std::vector<Layer>& layers, std::string* err);
 int build_graph(idc_context* c);
 int alloc_graph(idc_context* c);
 
 // idc_exec.hip
+void bind_layer(std::vector<Layer>& layers, int li, const BindEnv& env);
 int run_graph(idc_context* c, int n, const float* dL, const float* dab, const float* dmask, float maskcent, float* dout, float* ddist);
 int check_chain_abort(idc_context* c);
 int check_forward_args(idc_context* c, int n);
@@ -237,5 +260,8 @@ hipError_t wait_stream(idc_context* c, int n);
 hipError_t copy_h2d_or_d2h(idc_context* c, void* dev, void* host, size_t bytes, bool to_device);
 bool is_pinned(const void* p);
 int drain_pipeline(idc_context* c);
+
+// idc_diag.hip
+void layer_row(const std::vector<Layer>& layers, const std::vector<Tensor>& tensors, int precision, unsigned flags, int H, int W, int layer, idc_layer_info* out);
 
 }  // namespace idc

@@ -1,4 +1,4 @@
-// idc_exec.hip -- the executor: one forward of the planned graph on the handle's stream (run_graph, the persistent kwave chain), the host-pointer
+// idc_exec.hip -- the executor: one forward of the graph on the handle's stream (run_graph: plan_forward, then bind_layer and a launch per layer, or the persistent kwave chain), the host-pointer
 // forward with its transfers, the two-slot transfer pipeline, and the forward entry points of the C ABI (include/ideepcolor.h).
 // Replaces: SIGGRAPHGenerator.forward (models/pytorch/model.py:6-175).
 #include <stdint.h>
@@ -24,8 +24,7 @@ static int launch_kwave_chain(idc_context* c, int li, hipStream_t s, int* chain_
     int last = li, prev_dst = L.src;
     for (int j = li; j < (int)c->layers.size() && ch.nlayers < kKwChainMax; ++j) {
         Layer& Q = c->layers[j];
-        const bool shifted = (c->flags & IDC_FLAG_GLOBAL_HINTS) && Q.dst == c->t_conv4_3;
-        if (Q.kernel != kConvKwave || Q.spec->kind != kConv3x3 || Q.blob.nkc != 8 || Q.spec->in_stride != 1 || Q.resid >= 0 || shifted ||
+        if (Q.kernel != kConvKwave || Q.spec->kind != kConv3x3 || Q.blob.nkc != 8 || Q.spec->in_stride != 1 || Q.resid >= 0 || Q.shifted ||
             c->tensors[Q.dst].is_f32 || Q.src != prev_dst || Q.args.Hs != a.Hs || Q.args.Ws != a.Ws || Q.args.ncg != a.ncg ||
             conv_kwave_chain_blocks(a.Hs, a.Ws, a.N, a.ncg, Q.args.dy[8]) != blocks)
             break;
@@ -65,9 +64,44 @@ static int launch_kwave_chain(idc_context* c, int li, hipStream_t s, int* chain_
     return IDC_OK;
 }
 
+// A planned layer's pointers: this forward's tensors, the layer's parameters in the blob (the weight image the chosen kernel reads) and what rides
+// in the launch.  Decides nothing: which kernel runs, with which geometry and which optional operands, is the plan's (plan_forward, whose
+// args_as_bound states the same operands without the pointers).
+void bind_layer(std::vector<Layer>& layers, int li, const BindEnv& e) {
+    Layer& L = layers[li];
+    ConvArgs& a = L.args;
+    const std::vector<Tensor>& T = *e.tensors;
+    auto at = [&](size_t off) -> const float* { return off != (size_t)-1 ? (const float*)(e.blob + off) : nullptr; };
+    const Layer* S = L.fused_short >= 0 ? &layers[L.fused_short] : nullptr;      // the shortcut conv in this launch's K loop (model.py:156,170,172)
+    const Layer* P = L.fused_next >= 0 ? &layers[L.fused_next] : nullptr;        // conv1_2 in conv1_1's launch (launch_conv1_block's argument convention)
+    const bool wino = L.kernel == kConvWino || L.kernel == kDeconvWino, lay2 = L.kernel == kConvV2 || L.kernel == kConvDs;
+    a.in = T[L.src].ptr;
+    a.out = T[P ? P->dst : L.dst].ptr;
+    a.wgt = e.blob + (lay2 && L.blob.w2_off != (size_t)-1 ? L.blob.w2_off : wino ? L.blob.w3_off :
+                      (P && a.split_f16) ? L.blob.w2_off : L.blob.w_off);        // (IDC_FP16 model1: conv1_1's fp16 block, conv1_block_fused_th)
+    a.bias = at(S ? L.blob.fbias_off : L.blob.bias_off);
+    a.bn_scale = at(P ? P->blob.bn_scale_off : L.blob.bn_scale_off);
+    a.bn_shift = at(P ? P->blob.bn_shift_off : L.blob.bn_shift_off);
+    a.resid = (!S && L.resid >= 0) ? T[L.resid].ptr : nullptr;
+    a.img_shift = L.shifted ? e.glob_vec : nullptr;
+    a.in2 = S ? T[S->src].ptr : nullptr;
+    a.wgt2 = S ? e.blob + (L.kernel == kConvDs && S->blob.w2_off != (size_t)-1 ? S->blob.w2_off : S->blob.w_off) : P ? e.blob + P->blob.w_off : nullptr;
+    if (L.spec->kind == kConvIm2col) {          // model.py:139-148 input pack, fused into the operand staging
+        a.pk_L = e.L; a.pk_ab = e.ab; a.pk_mask = e.mask;
+        a.pk_ldiv = e.l_div; a.pk_abdiv = e.ab_div; a.pk_mmul = e.mask_mul; a.pk_mcent = e.mask_cent;
+    } else {
+        a.pk_L = nullptr;
+    }
+    a.head_w = L.fused_head ? at(e.head_w_off) : nullptr;
+    a.head_b = P ? at(P->blob.bias_off) : at(e.head_b_off);
+    a.head_out = e.out; a.head_mul = e.out_mul;
+    a.acc_scale = (L.split && a.split_f16) ? at(L.blob.wscale_off) : nullptr;
+    a.zeros = e.zeros;
+    a.partial = a.ksplit > 1 ? e.partial : nullptr;
+}
+
 int run_graph(idc_context* c, int n, const float* dL, const float* dab, const float* dmask, float maskcent,
                      float* dout, float* ddist) {
-    const Options& o = options();
     hipStream_t s = c->stream;
     int step = 0;
     {   // a workgroup of an EARLIER conv_kwave_chain_bf16 launch gave up at its grid barrier and nobody has waited on that forward since
@@ -90,131 +124,28 @@ int run_graph(idc_context* c, int n, const float* dL, const float* dab, const fl
     if (c->flags & IDC_FLAG_GLOBAL_HINTS)      // four GEMVs per image; its output is consumed by conv4_3's epilogue
         HIPCHK(c, launch_glob_branch(c->d_glob_in, (const float*)(c->d_blob + c->plan.glob_off), c->d_glob_vec, n, s));
     toc();
-    // pass 1: tile family per layer, then which shortcut convs ride in their consumer's launch
-    for (auto& L : c->layers) {
-        const Tensor& ti = c->tensors[L.src];
-        const Tensor& to = c->tensors[L.dst];
-        const int Hs = L.spec->kind == kDeconv4x4 ? ti.H : to.H;
-        const int Ws = L.spec->kind == kDeconv4x4 ? ti.W : to.W;
-        set_geometry(L, L.lprec, n, c->max_batch, Hs, Ws);
-        L.fused_short = -1; L.fused_next = -1;
-    }
-    // model1 in one launch: conv1_1 (input pack fused) followed by conv1_2 on the small-tile bf16 path, >= 128 big tiles
-    for (size_t i = 0; i + 1 < c->layers.size(); ++i) {
-        Layer& L = c->layers[i];
-        const bool f16blk = c->precision == IDC_FP16 && o.fp16_fast && L.blob.w2_off != (size_t)-1;      // IDC_FP16: conv1_block_fused_th
-        if (L.spec->kind != kConvIm2col || (c->precision != IDC_BF16 && !f16blk) || !o.fuse_conv1 || L.spec->act != 1 || L.spec->bnkey) continue;
-        // 32x32 tiles when there are >= 128 of them (N = 32); else the 32x8 tile (conv1_block_fused_t<4,2>) when THAT gives >= 128
-        // workgroups -- the batch-1 click path: one launch instead of conv1_1 + conv1_2 and no 8 MB intermediate
-        const long long t32 = (long long)((c->W + 31) / 32) * ((c->H + 31) / 32) * c->max_batch;
-        const long long t8 = (long long)((c->W + 31) / 32) * ((c->H + 7) / 8) * c->max_batch;
-        if (t32 < 128 && t8 < 128) continue;
-        const int tile_req = t32 >= 128 ? 32 : 8;              // tile height request of launch_conv1_block
-        for (size_t j = 0; j < c->layers.size(); ++j) {
-            Layer& P = c->layers[j];
-            const LayerSpec& ps = *P.spec;
-            if (P.src != L.dst || (P.kernel == kConvV2 && !f16blk) || ps.kind != kConv3x3 || ps.cin != 64 || ps.cout != 64 || ps.dilation != 1 ||
-                ps.in_stride != 1 || ps.act != 1 || ps.resid || c->tensors[P.dst].is_f32 || P.args.ksplit > 1 || P.kernel == kConvClick ||
-                P.kernel == kConvWino) continue;
-            bool only_consumer = true;
-            for (const Layer& Q : c->layers) if (&Q != &P && (Q.src == L.dst || Q.resid == L.dst)) only_consumer = false;
-            if (only_consumer) { L.fused_next = (int)j; P.kernel = kFused; L.args.tiles_y = tile_req; }
-        }
-    }
-    for (auto& L : c->layers) {
-        if (L.spec->kind != kDeconv4x4 || L.resid < 0 || L.kernel != kConvV2 || !fuse_shortcut_enabled() || (L.split && !o.split_ds_fuse)) continue;
-        if (L.spec->cout % 128 != 0 || L.spec->bnkey || L.spec->act == 2 || c->tensors[L.dst].is_f32) continue;   // conv_ds_fused's domain
-        for (size_t j = 0; j < c->layers.size(); ++j) {
-            Layer& P = c->layers[j];
-            const LayerSpec& ps = *P.spec;
-            if (P.dst != L.resid) continue;
-            const Tensor& pin = c->tensors[P.src];
-            const Tensor& to = c->tensors[L.dst];
-            if (L.split) {      // operand-split: conv_ds_fused_ms (split tensors in and out, both of the same part count) or two launches
-                if (ps.kind == kConv3x3 && ps.dilation == 1 && ps.in_stride == 1 && ps.act == 0 && !ps.bnkey && !ps.resid && P.split &&
-                    ps.cout == L.spec->cout && pin.H == to.H && pin.W == to.W && !pin.is_f32 && pin.parts == to.parts &&
-                    c->tensors[L.src].parts == to.parts && !c->tensors[L.src].is_f32 &&
-                    conv_ds_m_fits(L.args.Hs, L.args.Ws, L.blob.nkc * to.parts, P.blob.nkc * to.parts)) {
-                    // both K loops land in ONE accumulator set with ONE accumulator scale: the packer made the two layers' words equal
-                    const size_t li = (size_t)(&L - &c->layers[0]);
-                    if (li < c->wscale.size() && j < c->wscale.size() && memcmp(&c->wscale[li], &c->wscale[j], 4) != 0)
-                        return fail(&c->err, IDC_ERR_INTERNAL, "layers %s and %s would share one launch but their accumulator scales differ (%g, %g): the blob "
-                                    "was not packed by this library's packer", L.spec->name, ps.name, (double)c->wscale[li], (double)c->wscale[j]);
-                    L.fused_short = (int)j; P.kernel = kFused;
-                }
-                continue;
-            }
-            if (ps.kind == kConv3x3 && ps.dilation == 1 && ps.in_stride == 1 && ps.act == 0 && !ps.bnkey && !ps.resid &&
-                ps.cout == L.spec->cout && pin.H == to.H && pin.W == to.W && !pin.is_f32 && (!kAbPartners || P.blob.w2_off != (size_t)-1) &&
-                (kAbPartners || (o.ds_m16 != 0 && conv_ds_m_fits(L.args.Hs, L.args.Ws, L.blob.nkc, P.blob.nkc)))) {      // (default library: conv_ds_fused_m or two launches)
-                L.fused_short = (int)j; P.kernel = kFused;
-            }
-        }
-    }
-    if (!kAbPartners)            // a large-tile deconv that keeps its shortcut SUM (not fused: images beyond 32-bit offsets) has no 16x16x32 kernel: small tile
-        for (auto& L : c->layers)
-            if (L.kernel == kConvV2 && !L.split && L.resid >= 0 && L.fused_short < 0) {
-                const Tensor& ti = c->tensors[L.src];
-                const Tensor& to = c->tensors[L.dst];
-                set_geometry(L, L.lprec, n, c->max_batch, L.spec->kind == kDeconv4x4 ? ti.H : to.H, L.spec->kind == kDeconv4x4 ? ti.W : to.W, false);
-            }
+    PlanEnv pe;
+    pe.precision = c->precision; pe.flags = c->flags; pe.H = c->H; pe.W = c->W; pe.max_batch = c->max_batch; pe.n = n;
+    pe.t_conv10_2 = c->t_conv10_2; pe.t_conv4_3 = c->t_conv4_3; pe.wscale = &c->wscale;
+    const int prc = plan_forward(c->layers, c->tensors, pe, &c->err);
+    if (prc) return prc;
+    BindEnv be;
+    be.blob = c->d_blob; be.head_w_off = c->plan.head_w_off; be.head_b_off = c->plan.head_b_off;
+    be.tensors = &c->tensors; be.zeros = c->d_zeros; be.glob_vec = c->d_glob_vec;
+    be.L = dL; be.ab = dab; be.mask = dmask; be.l_div = c->l_div; be.ab_div = c->ab_div; be.mask_mul = c->mask_mul; be.mask_cent = maskcent;
+    be.out = dout; be.out_mul = c->out_mul;
     // diagnostic (IDC_DOUBLE_LAUNCH=1): every launch issued twice, the event pair around the SECOND -- a layer that is slow only as
     // the first launch of its kernel after other kernels (cold instruction cache / first touch) shows its warm time here
     static const bool double_launch = idc_env_int("IDC_DOUBLE_LAUNCH", 0) != 0;
     bool head_done = false;
     int chain_until = -1;                      // layers up to this index ran inside the conv_kwave_chain_bf16 launch of an earlier layer
-    for (auto& L : c->layers) {
-        const Tensor& ti = c->tensors[L.src];
+    for (int li = 0; li < (int)c->layers.size(); ++li) {
+        Layer& L = c->layers[li];
         const Tensor& to = c->tensors[L.dst];
-        const int li_ = (int)(&L - &c->layers[0]);
+        const ConvArgs& a = L.args;
         L.chain_len = 0;
-        if (li_ > chain_until) L.chained_into = -1;
-        if (L.kernel == kFused || li_ <= chain_until) { tic(); toc(); continue; }
-        // 1. bind: this forward's tensors, the layer's parameters in the blob (layout-1 weight images) and what rides in the launch
-        ConvArgs& a = L.args;
-        a.in = ti.ptr; a.out = to.ptr;
-        a.zeros = c->d_zeros;
-        a.warm = o.code_warm;
-        a.split_f16 = split_is_f16(c->precision) ? 1 : 0;
-        a.acc_scale = (L.split && a.split_f16 && L.blob.wscale_off != (size_t)-1) ? (const float*)(c->d_blob + L.blob.wscale_off) : nullptr;
-        a.out_f32 = to.is_f32;
-        a.img_shift = ((c->flags & IDC_FLAG_GLOBAL_HINTS) && L.dst == c->t_conv4_3) ? c->d_glob_vec : nullptr;
-        if (L.spec->kind == kConvIm2col) {          // model.py:139-148 input pack, fused into the operand staging
-            a.pk_L = dL; a.pk_ab = dab; a.pk_mask = dmask;
-            a.pk_ldiv = c->l_div; a.pk_abdiv = c->ab_div; a.pk_mmul = c->mask_mul; a.pk_mcent = maskcent;
-        } else {
-            a.pk_L = nullptr;
-        }
-        a.wgt = c->d_blob + L.blob.w_off;
-        a.bias = (const float*)(c->d_blob + L.blob.bias_off);
-        a.bn_scale = L.blob.bn_scale_off != (size_t)-1 ? (const float*)(c->d_blob + L.blob.bn_scale_off) : nullptr;
-        a.bn_shift = L.blob.bn_shift_off != (size_t)-1 ? (const float*)(c->d_blob + L.blob.bn_shift_off) : nullptr;
-        if (L.fused_short >= 0) {            // model8up(.) + model3short8(.) in one K loop (model.py:156,170,172)
-            const Layer& P = c->layers[L.fused_short];
-            a.resid = nullptr; a.resid_bf16 = 0;
-            a.in2 = c->tensors[P.src].ptr; a.wgt2 = c->d_blob + P.blob.w_off; a.nkc2 = P.blob.nkc;
-            a.bias = (const float*)(c->d_blob + L.blob.fbias_off);
-            if (L.split) a.w_part_bytes2 = P.blob.w_bytes;
-        } else {
-            a.resid = L.resid >= 0 ? c->tensors[L.resid].ptr : nullptr;
-            a.resid_bf16 = (L.resid >= 0 && !c->tensors[L.resid].is_f32) ? 1 : 0;
-            a.in2 = nullptr; a.wgt2 = nullptr; a.nkc2 = 0;
-        }
-        // the regression head rides in conv10_2's epilogue when one workgroup owns all 128 channels
-        L.fused_head = L.dst == c->t_conv10_2 && L.kernel == kConvV2 && L.cfg.wm == 2 && a.ncg == 2 && L.spec->bnkey == nullptr;
-        a.head_w = L.fused_head ? (const float*)(c->d_blob + c->plan.head_w_off) : nullptr;
-        a.head_b = (const float*)(c->d_blob + c->plan.head_b_off);
-        a.head_out = dout; a.head_mul = c->out_mul;
-        head_done = head_done || L.fused_head;
-        if (L.fused_next >= 0) {             // conv1_2 rides in conv1_1's launch (launch_conv1_block's argument convention)
-            const Layer& P = c->layers[L.fused_next];
-            a.wgt2 = c->d_blob + P.blob.w_off;
-            a.head_b = (const float*)(c->d_blob + P.blob.bias_off);
-            a.bn_scale = P.blob.bn_scale_off != (size_t)-1 ? (const float*)(c->d_blob + P.blob.bn_scale_off) : nullptr;
-            a.bn_shift = P.blob.bn_shift_off != (size_t)-1 ? (const float*)(c->d_blob + P.blob.bn_shift_off) : nullptr;
-            a.out = c->tensors[P.dst].ptr;
-            a.head_w = nullptr;
-        }
+        if (li > chain_until) L.chained_into = -1;
+        if (L.kernel == kFused || li <= chain_until) { tic(); toc(); continue; }
         if (a.ksplit > 1) {
             const size_t need = (size_t)a.ksplit * n * to.H * to.W * to.Cpad * 4;
             if (c->partial_bytes < need) {
@@ -224,35 +155,15 @@ int run_graph(idc_context* c, int n, const float* dL, const float* dab, const fl
                 HIPCHK(c, hipMalloc((void**)&c->d_partial, need));
                 c->partial_bytes = need;
             }
-            a.partial = c->d_partial;
         }
-        if (L.fused_next >= 0 && c->precision == IDC_FP16) {
-            a.wgt = c->d_blob + L.blob.w2_off;               // conv1_1's fp16 block (conv1_block_fused_th)
-            a.out_parts = 0; a.ksplit = 1; a.kc_per = a.nkc;
-        } else
-        if (is_split(c->precision) && !L.split) {        // fp32 island: conv_igemm<f32> with a split store (no split-K: its epilogue kernel writes fp32)
-            a.out_parts = to.is_f32 ? 0 : to.parts;
-            a.out_f32 = 1; a.ksplit = 1; a.kc_per = a.nkc;
-            if (L.kernel != kConvIgemm) return fail(&c->err, IDC_ERR_INTERNAL, "layer %s: fp32 island outside conv_igemm", L.spec->name);
-        }
-        if (L.split) {
-            // operand-split launch: nseg passes of the K loop (input part x weight part) into one accumulator set; split in / out tensors
-            a.in_parts = ti.parts; a.out_parts = (to.is_f32 || L.fused_head) ? 0 : to.parts;
-            a.nseg = split_segments(c->precision); a.seg_x = split_seg_x(c->precision); a.seg_w = split_seg_w(c->precision);
-            a.w_part_bytes = L.blob.w_bytes;
-        }
-        // 2. choose
-        L.kernel = choose_kernel(L, c->precision, c->max_batch);
-        // ... and the weight images it reads where they are not layout 1
-        if (L.kernel == kConvWino || L.kernel == kDeconvWino) a.wgt = c->d_blob + L.blob.w3_off;
-        if ((L.kernel == kConvV2 || L.kernel == kConvDs) && L.blob.w2_off != (size_t)-1) a.wgt = c->d_blob + L.blob.w2_off;
-        if (L.kernel == kConvDs && c->layers[L.fused_short].blob.w2_off != (size_t)-1) a.wgt2 = c->d_blob + c->layers[L.fused_short].blob.w2_off;
-        // 3. launch
+        be.partial = c->d_partial;
+        bind_layer(c->layers, li, be);
+        head_done = head_done || L.fused_head;
         for (int rep = double_launch ? 0 : 1; rep < 2; ++rep) {
             if (rep == 1) tic();
             bool chained = false;
             if (L.kernel == kConvKwave && !double_launch) {
-                const int rc = launch_kwave_chain(c, li_, s, &chain_until);
+                const int rc = launch_kwave_chain(c, li, s, &chain_until);
                 if (rc) return rc;
                 chained = L.chain_len > 0;
             }
@@ -268,8 +179,8 @@ int run_graph(idc_context* c, int n, const float* dL, const float* dab, const fl
         toc();
         if (c->audit) {
             if (L.fused_next >= 0) HIPCHK(c, audit_layer(L.fused_next));              // model1 in one launch: conv1_2's output is what was stored
-            else if (L.chain_len > 0) { for (int j = li_; j <= chain_until; ++j) HIPCHK(c, audit_layer(j)); }
-            else if (!L.fused_head) HIPCHK(c, audit_layer(li_));                      // (conv10_2 under the fused head: never stored)
+            else if (L.chain_len > 0) { for (int j = li; j <= chain_until; ++j) HIPCHK(c, audit_layer(j)); }
+            else if (!L.fused_head) HIPCHK(c, audit_layer(li));                      // (conv10_2 under the fused head: never stored)
         }
     }
     tic();

@@ -1,6 +1,7 @@
-// idc_plan.hip -- the graph planner: the static schedule of the SIGGRAPHGenerator graph (build_graph, alloc_graph), the tile family and launch
-// geometry of every layer (set_geometry), the entry point it runs (choose_kernel; launch_kernel and kernel_label read that choice), and the
-// options that steer those choices (options(), idc_set_option, idc_set_tile_policy, idc_set_splitk_policy).
+// idc_plan.hip -- the graph planner: the static schedule of the SIGGRAPHGenerator graph (build_layers, build_graph, alloc_graph), the plan of one
+// forward (plan_forward: tile family and launch geometry per layer -- set_geometry --, the fusions, the entry point each launch runs -- choose_kernel;
+// launch_kernel and kernel_label read that choice), and the options that steer those choices (options(), idc_set_option, idc_set_tile_policy,
+// idc_set_splitk_policy).  Nothing from build_layers to plan_forward touches the device: tools/plan_dump.cpp prints a configuration's plan without one.
 #include <stdio.h>
 #include <string.h>
 
@@ -10,9 +11,9 @@ namespace idc {
 
 Options& options() { static Options o; return o; }
 
-int find_tensor(idc_context* c, const char* name) {
-    for (size_t i = 0; i < c->tensors.size(); ++i)
-        if (c->tensors[i].name == name) return (int)i;
+int find_tensor(const std::vector<Tensor>& tensors, const char* name) {
+    for (size_t i = 0; i < tensors.size(); ++i)
+        if (tensors[i].name == name) return (int)i;
     return -1;
 }
 
@@ -25,7 +26,7 @@ static bool conv1_2_split_layer(const LayerSpec& s) {
 // the staged K loop): 0.87 ms -> 1.25 ms at level 1.  Off unless the tile policy forces every variant on.
 // large-tile deconv launches also run the shortcut conv they are summed with (conv_ds_fused); IDC_FUSE_SHORTCUT=0 keeps
 // the two launches apart (A/B)
-bool fuse_shortcut_enabled() {
+static bool fuse_shortcut_enabled() {
     static const bool off = idc_env_int("IDC_FUSE_SHORTCUT", 1) == 0;
     return !off;
 }
@@ -108,13 +109,12 @@ void fill_taps(Layer& L) {
 
 // n_policy: the batch the kernel variant is chosen for (the handle's max_batch, so that a handle's
 // numerics do not depend on how many images a call carries); n: the batch actually launched.
-void set_geometry(Layer& L, int precision, int n, int n_policy, int Hs, int Ws, bool allow_v2) {
+static void set_geometry(Layer& L, int precision, int n, int n_policy, int Hs, int Ws, bool allow_v2) {
     const Options& o = options();
     ConvArgs& a = L.args;
     a.N = n; a.Hs = Hs; a.Ws = Ws;
     a.nkc = L.blob.nkc; a.ncg = L.blob.ncg;
     a.act = L.spec->act;
-    a.out_f32 = L.spec->out_f32;
     // fp32 path: every 3x3 stride-1 layer whose U image is in the blob runs as Winograd F(2x2,3x3): 2.25x fewer multiplies
     // on the exact-fp32 matrix pipe, no split-K at batch 1 (one workgroup per 16 tiles x 32 couts)
     bool wino = precision == IDC_FP32 && o.wino && o.tile_policy != 1 && L.blob.w3_off != (size_t)-1 &&
@@ -223,13 +223,12 @@ void set_geometry(Layer& L, int precision, int n, int n_policy, int Hs, int Ws, 
     }
 }
 
-// The entry point a layer launches this forward: set_geometry's tile family (L.kernel) refined by the fusions planned on the layer, its bound
-// arguments and the options.  An exclusive chain in precedence order; where an entry point covers only some launches, its predicate decides
-// here, so the launch that follows is never refused (a refusal is a planning bug: run_graph / run_single_op report it).
+// The entry point a layer launches this forward: set_geometry's tile family (L.kernel) refined by the fusions planned on the layer, its
+// arguments `a` as they will be bound (args_as_bound) and the options.  An exclusive chain in precedence order; where an entry point covers only
+// some launches, its predicate decides here, so the launch that follows is never refused (a refusal is a planning bug: run_graph / run_single_op report it).
 // max_batch: the batch the variant is chosen for (as set_geometry's n_policy), so that a result never depends on how many images share a call.
-Kernel choose_kernel(const Layer& L, int precision, int max_batch) {
+static Kernel choose_kernel(const Layer& L, const ConvArgs& a, int precision, int max_batch) {
     const Options& o = options();
-    const ConvArgs& a = L.args;
     const Kernel tile = L.kernel;
     const long long tiles32 = (long long)((a.Ws + 31) / 32) * max_batch;       // x (tile rows) = workgroups of a 32-wide tile
     if (tile == kFused) return kFused;
@@ -254,6 +253,130 @@ Kernel choose_kernel(const Layer& L, int precision, int max_batch) {
     if (tile == kConvV2 && o.mfma16 && conv_v2m_applies(a))      // the 16x16x32-MFMA builds read the layout-1 image
         return o.v2p && conv_v2p_applies(L.cfg, L.halo, a) ? kConvV2p : kConvV2m;
     return tile;
+}
+
+// The kernel predicates (conv_*_applies, idc_kernels.h) ask which optional operands a launch carries by testing its pointers.  The plan knows that
+// before anything is bound: L's arguments with every pointer bind_layer (idc_exec.hip) will set standing in as a token that is never dereferenced.
+static ConvArgs args_as_bound(const Layer& L, const std::vector<Layer>& layers) {
+    static const float token = 0.f;
+    ConvArgs a = L.args;
+    const LayerBlob& bn = L.fused_next >= 0 ? layers[L.fused_next].blob : L.blob;
+    auto set = [&](bool carried) -> const float* { return carried ? &token : nullptr; };
+    a.in = a.wgt = a.zeros = a.bias = a.head_b = &token;
+    a.resid = set(L.fused_short < 0 && L.resid >= 0);
+    a.in2 = set(L.fused_short >= 0);
+    a.wgt2 = set(L.fused_short >= 0 || L.fused_next >= 0);
+    a.bn_scale = set(bn.bn_scale_off != (size_t)-1); a.bn_shift = set(bn.bn_shift_off != (size_t)-1);
+    a.img_shift = set(L.shifted);
+    a.pk_L = set(L.spec->kind == kConvIm2col);
+    a.head_w = set(L.fused_head);
+    return a;
+}
+
+// The plan of one forward: what every layer launches and with which geometry, as a function of the graph, `env` and options() -- and of nothing
+// else: no HIP call, no device pointer, no per-call pointer, no state an earlier forward left in the layers.  run_graph and the single-operator entry
+// points (idc_diag.hip) both run it, then bind_layer and launch_kernel per layer.  Every ConvArgs field a launch reads has exactly one writer:
+//   fill_taps (once, build_layers)    nphase ntaps so si dy dx tw ro co
+//   plan_forward (every forward)      N Hs Ws nkc ncg act tiles_x tiles_y ksplit kc_per (set_geometry; tiles_y = the tile request of a model1 launch)
+//                                     out_f32 resid_bf16 nkc2 in_parts out_parts nseg seg_x seg_w w_part_bytes w_part_bytes2 split_f16 warm
+//   bind_layer (every launch)         in out wgt bias bn_scale bn_shift resid img_shift in2 wgt2 pk_* head_* acc_scale zeros partial
+int plan_forward(std::vector<Layer>& layers, const std::vector<Tensor>& tensors, const PlanEnv& env, std::string* err) {
+    const Options& o = options();
+    auto geometry = [&](Layer& L, bool allow_v2) {
+        const Tensor& sites = tensors[L.spec->kind == kDeconv4x4 ? L.src : L.dst];
+        set_geometry(L, L.lprec, env.n, env.max_batch, sites.H, sites.W, allow_v2);
+    };
+    // the tile family per layer, then which layers ride in another one's launch
+    for (auto& L : layers) {
+        geometry(L, true);
+        L.fused_short = -1; L.fused_next = -1;
+        L.shifted = (env.flags & IDC_FLAG_GLOBAL_HINTS) && L.dst == env.t_conv4_3;
+    }
+    // model1 in one launch: conv1_1 (input pack fused) followed by conv1_2 on the small-tile bf16 path, >= 128 big tiles
+    for (size_t i = 0; i + 1 < layers.size(); ++i) {
+        Layer& L = layers[i];
+        const bool f16blk = env.precision == IDC_FP16 && o.fp16_fast && L.blob.w2_off != (size_t)-1;      // IDC_FP16: conv1_block_fused_th
+        if (L.spec->kind != kConvIm2col || (env.precision != IDC_BF16 && !f16blk) || !o.fuse_conv1 || L.spec->act != 1 || L.spec->bnkey) continue;
+        // 32x32 tiles when there are >= 128 of them (N = 32); else the 32x8 tile (conv1_block_fused_t<4,2>) when THAT gives >= 128
+        // workgroups -- the batch-1 click path: one launch instead of conv1_1 + conv1_2 and no 8 MB intermediate
+        const long long t32 = (long long)((env.W + 31) / 32) * ((env.H + 31) / 32) * env.max_batch;
+        const long long t8 = (long long)((env.W + 31) / 32) * ((env.H + 7) / 8) * env.max_batch;
+        if (t32 < 128 && t8 < 128) continue;
+        const int tile_req = t32 >= 128 ? 32 : 8;              // tile height request of launch_conv1_block
+        for (size_t j = 0; j < layers.size(); ++j) {
+            Layer& P = layers[j];
+            const LayerSpec& ps = *P.spec;
+            if (P.src != L.dst || (P.kernel == kConvV2 && !f16blk) || ps.kind != kConv3x3 || ps.cin != 64 || ps.cout != 64 || ps.dilation != 1 ||
+                ps.in_stride != 1 || ps.act != 1 || ps.resid || tensors[P.dst].is_f32 || P.args.ksplit > 1 || P.kernel == kConvClick ||
+                P.kernel == kConvWino) continue;
+            bool only_consumer = true;
+            for (const Layer& Q : layers) if (&Q != &P && (Q.src == L.dst || Q.resid == L.dst)) only_consumer = false;
+            if (only_consumer) { L.fused_next = (int)j; P.kernel = kFused; L.args.tiles_y = tile_req; }
+        }
+    }
+    // a large-tile deconv and the 3x3 shortcut conv it is summed with in one K loop (model.py:156,170,172)
+    for (size_t li = 0; li < layers.size(); ++li) {
+        Layer& L = layers[li];
+        if (L.spec->kind != kDeconv4x4 || L.resid < 0 || L.kernel != kConvV2 || !fuse_shortcut_enabled() || (L.split && !o.split_ds_fuse)) continue;
+        if (L.spec->cout % 128 != 0 || L.spec->bnkey || L.spec->act == 2 || tensors[L.dst].is_f32) continue;   // conv_ds_fused's domain
+        for (size_t j = 0; j < layers.size(); ++j) {
+            Layer& P = layers[j];
+            const LayerSpec& ps = *P.spec;
+            if (P.dst != L.resid) continue;
+            const Tensor& pin = tensors[P.src];
+            const Tensor& to = tensors[L.dst];
+            // a plain 3x3 conv (no activation, BN or sum of its own) over the deconv's output pixels
+            const bool shortcut3x3 = ps.kind == kConv3x3 && ps.dilation == 1 && ps.in_stride == 1 && ps.act == 0 && !ps.bnkey && !ps.resid &&
+                                     ps.cout == L.spec->cout && pin.H == to.H && pin.W == to.W && !pin.is_f32;
+            if (L.split) {      // operand-split: conv_ds_fused_ms (split tensors in and out, both of the same part count) or two launches
+                if (!shortcut3x3 || !P.split || pin.parts != to.parts || tensors[L.src].parts != to.parts || tensors[L.src].is_f32 ||
+                    !conv_ds_m_fits(L.args.Hs, L.args.Ws, L.blob.nkc * to.parts, P.blob.nkc * to.parts)) continue;
+                // both K loops land in ONE accumulator set with ONE accumulator scale: the packer made the two layers' words equal
+                if (env.wscale && li < env.wscale->size() && j < env.wscale->size() && memcmp(&(*env.wscale)[li], &(*env.wscale)[j], 4) != 0)
+                    return fail(err, IDC_ERR_INTERNAL, "layers %s and %s would share one launch but their accumulator scales differ (%g, %g): the blob "
+                                "was not packed by this library's packer", L.spec->name, ps.name, (double)(*env.wscale)[li], (double)(*env.wscale)[j]);
+            } else if (!shortcut3x3 || (kAbPartners ? P.blob.w2_off == (size_t)-1 : !(o.ds_m16 != 0 && conv_ds_m_fits(L.args.Hs, L.args.Ws, L.blob.nkc, P.blob.nkc)))) {
+                continue;       // (default library: conv_ds_fused_m or two launches)
+            }
+            L.fused_short = (int)j; P.kernel = kFused;
+        }
+    }
+    for (auto& L : layers) {
+        // the regression head rides in conv10_2's epilogue when one workgroup owns all 128 channels
+        L.fused_head = L.dst == env.t_conv10_2 && L.kernel == kConvV2 && L.cfg.wm == 2 && L.args.ncg == 2 && L.spec->bnkey == nullptr;
+        // default library: the large tile's 16x16x32 kernels take neither a shortcut SUM (a deconv that was not fused above: images beyond 32-bit
+        // offsets) nor a LeakyReLU without the fused head (single operators only) -- the small tile
+        if (!kAbPartners && L.kernel == kConvV2 && !L.split && ((L.resid >= 0 && L.fused_short < 0) || (L.spec->act == 2 && !L.fused_head))) {
+            geometry(L, false);
+            L.fused_head = false;
+        }
+    }
+    // what each launch carries besides pointers, and the entry point it runs
+    for (auto& L : layers) {
+        if (L.kernel == kFused) continue;
+        ConvArgs& a = L.args;
+        const Tensor& ti = tensors[L.src];
+        const Tensor& to = tensors[L.dst];
+        const Layer* S = L.fused_short >= 0 ? &layers[L.fused_short] : nullptr;
+        const bool f16_block = L.fused_next >= 0 && env.precision == IDC_FP16;       // conv1_block_fused_th
+        const bool island = is_split(env.precision) && !L.split && !f16_block;       // conv_igemm<f32> with a split store
+        a.warm = o.code_warm;
+        a.split_f16 = split_is_f16(env.precision) ? 1 : 0;
+        a.out_f32 = island ? 1 : to.is_f32;
+        a.resid_bf16 = (!S && L.resid >= 0 && !tensors[L.resid].is_f32) ? 1 : 0;
+        a.nkc2 = S ? S->blob.nkc : 0;
+        if (f16_block || island) { a.ksplit = 1; a.kc_per = a.nkc; }                 // (no split-K: its epilogue kernel writes fp32)
+        if (island && L.kernel != kConvIgemm) return fail(err, IDC_ERR_INTERNAL, "layer %s: fp32 island outside conv_igemm", L.spec->name);
+        // operand-split launch: nseg passes of the K loop (input part x weight part) into one accumulator set; split in / out tensors
+        a.in_parts = L.split ? ti.parts : 0;
+        a.out_parts = (to.is_f32 || L.fused_head || !(L.split || island)) ? 0 : to.parts;
+        a.nseg = L.split ? split_segments(env.precision) : 0;
+        a.seg_x = L.split ? split_seg_x(env.precision) : 0u; a.seg_w = L.split ? split_seg_w(env.precision) : 0u;
+        a.w_part_bytes = L.split ? L.blob.w_bytes : 0;
+        a.w_part_bytes2 = (L.split && S) ? S->blob.w_bytes : 0;
+        L.kernel = choose_kernel(L, args_as_bound(L, layers), env.precision, env.max_batch);
+    }
+    return IDC_OK;
 }
 
 // One launch of the entry point `k` (kConvKwave: one layer; run_graph tries the persistent chain first).
@@ -324,42 +447,40 @@ static double layer_flops(const LayerSpec& s, int H, int W) {       // per image
     return 0;
 }
 
-int build_graph(idc_context* c) {
+// The graph of one configuration: its tensors (shapes and storage; no memory yet) and its layers with their taps.  Needs no device.
+int build_layers(const BlobPlan& plan, int precision, int H, int W, int max_batch, std::vector<Tensor>& tensors, std::vector<Layer>& layers, std::string* err) {
     const auto& specs = layer_specs();
-    const int eb = elem_bytes(c->precision);
-    const bool split = is_split(c->precision);
+    const int eb = elem_bytes(precision);
+    const bool split = is_split(precision);
     auto add_tensor = [&](const char* name, int C, int Cpad, int level, int f32) -> int {
         Tensor t;
-        t.name = name; t.C = C; t.Cpad = Cpad; t.H = c->H / level; t.W = c->W / level; t.is_f32 = f32;
-        t.parts = (split && !f32) ? split_parts(c->precision) : 1;
-        t.bytes = (size_t)c->max_batch * t.H * t.W * Cpad * (f32 ? 4 : eb * t.parts);
-        c->tensors.push_back(t);
-        return (int)c->tensors.size() - 1;
+        t.name = name; t.C = C; t.Cpad = Cpad; t.H = H / level; t.W = W / level; t.is_f32 = f32;
+        t.parts = (split && !f32) ? split_parts(precision) : 1;
+        t.bytes = (size_t)max_batch * t.H * t.W * Cpad * (f32 ? 4 : eb * t.parts);
+        tensors.push_back(t);
+        return (int)tensors.size() - 1;
     };
     // operand-split precisions: is tensor `name` read by a layer outside the fp32 island / summed into another layer as a shortcut?
     auto read_by_split_layer = [&](const char* name) {
-        for (int ai : c->plan.active) { const LayerSpec& q = specs[ai]; if (!split_island(q) && strcmp(q.src, name) == 0) return true; }
+        for (int ai : plan.active) { const LayerSpec& q = specs[ai]; if (!split_island(q) && strcmp(q.src, name) == 0) return true; }
         return false;
     };
     auto used_as_shortcut = [&](const char* name) {
-        for (int ai : c->plan.active) { const LayerSpec& q = specs[ai]; if (q.resid && strcmp(q.resid, name) == 0) return true; }
+        for (int ai : plan.active) { const LayerSpec& q = specs[ai]; if (q.resid && strcmp(q.resid, name) == 0) return true; }
         return false;
     };
-    c->t_input = add_tensor("data_l_ab_mask", 36, 64, 1, 0);      // never materialised: built inside conv1_1's operand staging
-    c->tensors[c->t_input].bytes = 256;
-    for (size_t li = 0; li < c->plan.active.size(); ++li) {
-        const LayerSpec& s = specs[c->plan.active[li]];
+    tensors[add_tensor("data_l_ab_mask", 36, 64, 1, 0)].bytes = 256;      // never materialised: built inside conv1_1's operand staging
+    for (size_t li = 0; li < plan.active.size(); ++li) {
+        const LayerSpec& s = specs[plan.active[li]];
         Layer L;
-        L.spec = &s; L.blob = c->plan.layers[li];
-        L.src = find_tensor(c, s.src);
-        if (L.src < 0) return fail(&c->err, IDC_ERR_INVALID_ARG, "graph: unknown source '%s'", s.src);
+        L.spec = &s; L.blob = plan.layers[li];
+        L.src = find_tensor(tensors, s.src);
+        if (L.src < 0) return fail(err, IDC_ERR_INVALID_ARG, "graph: unknown source '%s'", s.src);
         if (s.resid) {
-            L.resid = find_tensor(c, s.resid);
-            if (L.resid < 0) return fail(&c->err, IDC_ERR_INVALID_ARG, "graph: unknown residual '%s'", s.resid);
+            L.resid = find_tensor(tensors, s.resid);
+            if (L.resid < 0) return fail(err, IDC_ERR_INVALID_ARG, "graph: unknown residual '%s'", s.resid);
         }
-        // fp32 storage: everything on the fp32 path; on the bf16 path the class / 313 logits and the hyper-column
-        // partial sums of the 313 head (LayerSpec.out_f32)
-        L.lprec = c->precision;
+        L.lprec = precision;
         if (split && split_island(s)) {
             // fp32 island (conv1_1): exact-fp32 kernel; its epilogue writes the result as split planes where the split stack reads it
             L.lprec = IDC_FP32;
@@ -368,21 +489,28 @@ int build_graph(idc_context* c) {
             // fp32 storage: everything on the fp32 path; class / 313 logits and the hyper-column partial sums (LayerSpec.out_f32); on the
             // operand-split path also every shortcut branch (summed in fp32 in its consumer's epilogue)
             L.split = split;
-            L.dst = add_tensor(s.name, s.cout, cout_pad(s.cout), s.level, c->precision == IDC_FP32 || s.out_f32 || (split && used_as_shortcut(s.name)));
+            L.dst = add_tensor(s.name, s.cout, cout_pad(s.cout), s.level, precision == IDC_FP32 || s.out_f32 || (split && used_as_shortcut(s.name)));
         }
         fill_taps(L);
-        L.flops = layer_flops(s, c->H, c->W);
-        const Tensor& ti = c->tensors[L.src];
-        const Tensor& to = c->tensors[L.dst];
+        L.flops = layer_flops(s, H, W);
+        const Tensor& ti = tensors[L.src];
+        const Tensor& to = tensors[L.dst];
         const double in_px = (double)(ti.H / s.in_stride) * (ti.W / s.in_stride);
         L.min_bytes = in_px * ti.Cpad * (ti.is_f32 ? 4 : eb * ti.parts) + (double)to.H * to.W * to.Cpad * (to.is_f32 ? 4 : eb * to.parts) +
-                      (L.resid >= 0 ? (double)to.H * to.W * to.Cpad * (c->tensors[L.resid].is_f32 ? 4 : eb) : 0.0);
-        c->layers.push_back(L);
+                      (L.resid >= 0 ? (double)to.H * to.W * to.Cpad * (tensors[L.resid].is_f32 ? 4 : eb) : 0.0);
+        layers.push_back(L);
     }
-    c->t_conv10_2 = find_tensor(c, "conv10_2");
-    c->t_logits = find_tensor(c, "class_logits");
-    c->t_conv4_3 = find_tensor(c, "conv4_3");
-    c->t_pred313 = find_tensor(c, "pred_313");
+    return IDC_OK;
+}
+
+int build_graph(idc_context* c) {
+    const int rc = build_layers(c->plan, c->precision, c->H, c->W, c->max_batch, c->tensors, c->layers, &c->err);
+    if (rc) return rc;
+    c->t_input = find_tensor(c->tensors, "data_l_ab_mask");
+    c->t_conv10_2 = find_tensor(c->tensors, "conv10_2");
+    c->t_logits = find_tensor(c->tensors, "class_logits");
+    c->t_conv4_3 = find_tensor(c->tensors, "conv4_3");
+    c->t_pred313 = find_tensor(c->tensors, "pred_313");
     return IDC_OK;
 }
 
