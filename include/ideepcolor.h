@@ -377,6 +377,35 @@ enum { IDC_INTERP_CUBIC = 0, IDC_INTERP_LINEAR = 1, IDC_INTERP_NEAREST = 2 };
 enum { IDC_SRC_OUTPUT_AB = 0, IDC_SRC_OUTPUT_AB_RAW = 1, IDC_SRC_INPUT_AB = 2 };
 int idc_upsample_lab2rgb(idc_handle h, int img, int source, int interp, int out_h, int out_w, const double* L, uint8_t* rgb);
 
+/* ---- image ingestion on the device: replaces the host work of ColorizeImageBase.load_image / set_image
+ *      (colorize_image.py:52-77): cv2.resize(im, (Xd, Xd)) of the uint8 image, rgb2lab of the result, img_l_mc = L - 50.
+ *      rgb [n,src_h,src_w,3] uint8 on the host (pinned memory is transferred in place) are the images of slots
+ *      img .. img+n-1.  One kernel launch for all n: net-size RGB [H,W,3] by the bilinear rule of cv2 INTER_LINEAR
+ *      (half-pixel centres, taps clamped to the image, float64, round half up; the identity when src_h == H and
+ *      src_w == W, which is set_image's case: it does not resize), Lab = skimage rgb2lab of that in float64, and the
+ *      slot's resident L plane = (float)(L - l_cent) -- what idc_set_image_l would have been given.  rgb_net [n,H,W,3]
+ *      uint8 and lab_net [n,3,H,W] float64 receive the net-size image and its Lab; each may be NULL.
+ *      IDC_INGEST_KEEP_SOURCE: the source image also stays on the device (src_h*src_w*3 bytes per slot, freed by
+ *      idc_destroy or replaced by the slot's next idc_set_image_rgb) for idc_fullres_rgb.  Without the flag the slot's
+ *      previous source is released; so it is whenever anything else overwrites the slot's L plane (idc_set_image_l, a
+ *      forward that is given L_mc).  Blocking; drains the pipelined slots first.
+ *      Status: IDC_ERR_INVALID_ARG for src_h / src_w outside 1..16384, NULL rgb or unknown flag bits; IDC_ERR_BATCH
+ *      unless n >= 1 and img + n <= max_batch.
+ *      idc_fullres_rgb: the full-resolution getters get_img_fullres / get_input_img_fullres / get_sup_fullres /
+ *      get_img_gray_fullres (colorize_image.py:123-158) from the slot's resident source, without the float64 L plane
+ *      idc_upsample_lab2rgb is handed: rgb [src_h,src_w,3] uint8 at the source's size.  (a, b): the planes `source` names,
+ *      resized by `interp` as in idc_upsample_lab2rgb (same residency rules), or IDC_SRC_NO_AB: a = b = 0.  L: IDC_L_IMAGE
+ *      = rgb2lab of the source pixel itself (img_l_fullres), IDC_L_MASK50 = 50 * zoom(mask, order 0) / mask_value with
+ *      the slot's resident hint mask and the mask_value of its last idc_set_hints (a slot that never had hints: L = 0).
+ *      An output dimension of 1 reads source coordinate 0 on that axis (scipy's zoom).  IDC_ERR_UNSUPPORTED when the
+ *      slot has no resident source. */
+enum { IDC_INGEST_KEEP_SOURCE = 1 };
+int idc_set_image_rgb(idc_handle h, int img, int n, int src_h, int src_w, const uint8_t* rgb, float l_cent, unsigned flags,
+                      uint8_t* rgb_net, double* lab_net);
+enum { IDC_SRC_NO_AB = 3 };               /* joins IDC_SRC_*: a = b = 0 */
+enum { IDC_L_IMAGE = 0, IDC_L_MASK50 = 1 };
+int idc_fullres_rgb(idc_handle h, int img, int source, int interp, int l_mode, uint8_t* rgb);
+
 /* ---- introspection for parity tests and roofline accounting -------------------------------- */
 int idc_num_layers(idc_handle h);
 typedef struct idc_layer_info {

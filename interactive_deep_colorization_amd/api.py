@@ -141,6 +141,8 @@ class ColorizeImageBase(object):
         self.net_set = False
         self.img_just_set = False
         self._l_resident = False              # the image's L plane is in the engine's slot 0
+        self._src_resident = False            # the uint8 source of the image is in the engine's slot 0 (load_image_device / set_image_device)
+        self._fullres_lab_pending = False     # img_lab_fullres / img_l_fullres / img_ab_fullres have not been computed from img_rgb_fullres yet
         self._hints_on_device = False         # input_ab / input_mask live on the device (net_forward_hints)
 
     def prep_net(self):
@@ -152,6 +154,7 @@ class ColorizeImageBase(object):
         old = getattr(self, 'net', None)
         self.net = net
         self._l_resident = False
+        self._src_resident = False
         self._hints_on_device = False
         self._dev_out_valid = False
         self._out_pending = set()
@@ -236,12 +239,18 @@ class ColorizeImageBase(object):
             f = 1. * self.Xfullres_max / longest
             big = zoom(big, (f, f, 1), order=1)
         self.img_rgb_fullres = big
+        self._fullres_lab_pending = False
         self.img_lab_fullres = colorspace.rgb2lab(big).transpose((2, 0, 1))
         self.img_l_fullres = self.img_lab_fullres[[0]]
         self.img_ab_fullres = self.img_lab_fullres[1:]
+        self._ingest_net(rgb_net, colorspace.rgb2lab(rgb_net).transpose((2, 0, 1)))
+        self._l_resident = False
+        self._src_resident = False
 
+    def _ingest_net(self, rgb_net, lab_net):
+        """The net-size attributes from the Xd x Xd image and its (3,Xd,Xd) float64 Lab."""
         self.img_rgb = rgb_net
-        self.img_lab = colorspace.rgb2lab(rgb_net).transpose((2, 0, 1))
+        self.img_lab = lab_net
         self.img_l = self.img_lab[[0]]
         self.img_ab = self.img_lab[1:]
 
@@ -253,7 +262,68 @@ class ColorizeImageBase(object):
         self._img_l_mc_f32 = np.ascontiguousarray(self.img_l_mc, dtype=np.float32)
         self._img_l_pinned = None
         self.img_l_set = True
-        self._l_resident = False
+
+    # img_lab_fullres / img_l_fullres / img_ab_fullres: plain values after load_image / set_image; after load_image_device /
+    # set_image_device the float64 rgb2lab of the full-resolution copy (0.4 s for two megapixels) runs when one of them is first read
+    def _refresh_fullres_lab(self):
+        if self._fullres_lab_pending:
+            self._fullres_lab_pending = False
+            self.img_lab_fullres = colorspace.rgb2lab(self.img_rgb_fullres).transpose((2, 0, 1))
+            self.img_l_fullres = self.img_lab_fullres[[0]]
+            self.img_ab_fullres = self.img_lab_fullres[1:]
+
+    img_lab_fullres = _lazy('img_lab_fullres', '_refresh_fullres_lab')
+    img_l_fullres = _lazy('img_l_fullres', '_refresh_fullres_lab')
+    img_ab_fullres = _lazy('img_ab_fullres', '_refresh_fullres_lab')
+
+    def _ingest_device(self, rgb_fullres):
+        """``_ingest`` with the engine doing the work (``HipColorizer.set_image_rgb``): resize to Xd x Xd, rgb2lab and the resident L
+        plane in one call, the uint8 source kept on the device for the full-resolution getters.  A source beyond ``Xfullres_max``
+        (whose full-resolution copy is a host ``zoom``) takes the host route, at the caller."""
+        if not self.net_set or not hasattr(self.net, 'set_image_rgb'):
+            raise RuntimeError('load_image_device / set_image_device need prep_net first, and an engine with set_image_rgb')
+        if self.l_norm != 1:
+            raise ValueError('device-side ingestion assumes a raw L input (l_norm 1)')
+        rgb_net, lab_net = self.net.set_image_rgb(rgb_fullres, img=0, l_cent=self.l_mean, keep_source=True)
+        self.img_rgb_fullres = rgb_fullres
+        self._fullres_lab_pending = True
+        self._ingest_net(rgb_net[0], lab_net[0])
+        self._l_resident = True               # the call left L - l_mean in slot 0: the next click uploads nothing
+        self._src_resident = True
+        self._l_serial = getattr(self.net, 'l_serial', None)
+
+    def load_image_device(self, input_path):
+        """``load_image`` with the resize, both colour conversions and the L upload on the device (not in the reference).  Same
+        attributes; the full-resolution Lab ones are computed on the host only when read."""
+        full = colorspace.imread_rgb(input_path)
+        if max(full.shape[0], full.shape[1]) > self.Xfullres_max:
+            self._ingest(full.copy(), colorspace.resize_bilinear_u8(full, self.Xd, self.Xd))
+        else:
+            self._ingest_device(full)
+
+    def set_image_device(self, input_image):
+        """``set_image`` on the device: an Xd x Xd RGB uint8 array, used as it is."""
+        image = np.ascontiguousarray(input_image, dtype=np.uint8)
+        if max(image.shape[0], image.shape[1]) > self.Xfullres_max:
+            self._ingest(image.copy(), image)
+        else:
+            self._ingest_device(image.copy())
+
+    def _source_on_device(self):
+        """The engine still holds this image's uint8 source: nothing has written slot 0's L plane since (``engine.l_serial``)."""
+        return self.net_set and self._src_resident and self.__dict__.get('_l_serial') == getattr(self.net, 'l_serial', None)
+
+    def _fullres_device(self, source, interp, l_mode):
+        """One full-resolution getter from the resident source (``HipColorizer.fullres_rgb``), or None: the host route takes over."""
+        if not self._source_on_device():
+            return None
+        try:
+            out = self.net.fullres_rgb(source, interp, l_mode, img=0)
+        except IdcError:
+            self._src_resident = False
+            return None
+        self._l_serial = getattr(self.net, 'l_serial', None)      # (the call itself moved it)
+        return out
 
     def _l_plane(self):
         """The float32 L plane of the current image in pinned memory (made once per image): every click uploads it in place."""
@@ -429,6 +499,9 @@ class ColorizeImageBase(object):
         return lab2rgb_transpose(self.img_l, self._zeros_ab(self.img_l))
 
     def get_img_gray_fullres(self):
+        dev = self._fullres_device('no_ab', 'linear', 'image')
+        if dev is not None:
+            return dev
         return lab2rgb_transpose(self.img_l_fullres, self._zeros_ab(self.img_l_fullres))
 
     def _out_on_device(self):
@@ -445,6 +518,9 @@ class ColorizeImageBase(object):
         # (the Python-side token can outlive the engine's resident map -- a direct net.forward / forward_async on the
         #  engine, a want_rgb=False forward: the engine then answers IDC_ERR_UNSUPPORTED and the host path takes over)
         if self._out_on_device():
+            dev = self._fullres_device('output_ab', 'linear', 'image')
+            if dev is not None:
+                return dev
             try:
                 return self.net.upsample_lab2rgb(self.img_l_fullres[0], 'output_ab', 'linear')
             except IdcError:
@@ -453,6 +529,9 @@ class ColorizeImageBase(object):
 
     def get_input_img_fullres(self):
         if self._in_on_device():
+            dev = self._fullres_device('input_ab', 'linear', 'image')
+            if dev is not None:
+                return dev
             try:
                 return self.net.upsample_lab2rgb(self.img_l_fullres[0], 'input_ab', 'linear')
             except IdcError:
@@ -487,6 +566,9 @@ class ColorizeImageBase(object):
 
     def get_sup_fullres(self):
         if self._in_on_device():
+            dev = self._fullres_device('input_ab', 'nearest', 'mask50')
+            if dev is not None:
+                return dev
             try:
                 return self.net.upsample_lab2rgb(50 * self._up(self.input_mask, 0)[0], 'input_ab', 'nearest')
             except IdcError:

@@ -1,6 +1,6 @@
 // idc_api.hip -- the handle and what a caller does with it besides weights and forwards (C ABI, include/ideepcolor.h): create / destroy, the last-error
 // string (fail), I/O scales, global hints, the click session, Lab -> RGB, colour suggestions and distributions, the global histogram, stream
-// ordering and the display upsample.
+// ordering, the display upsample and image ingestion (uint8 RGB in, full-resolution RGB out).
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -75,6 +75,11 @@ static void destroy_ctx(idc_context* c) {
     if (c->d_up_L) (void)hipFree(c->d_up_L);
     if (c->h_up_rgb) (void)hipHostFree(c->h_up_rgb);
     if (c->h_up_L) (void)hipHostFree(c->h_up_L);
+    for (auto& sl : c->src) if (sl.d_rgb) (void)hipFree(sl.d_rgb);
+    void* ing[] = {c->d_ingest, (void*)c->d_src_ptrs, c->d_net_rgb, c->d_net_lab, c->d_full_rgb};
+    for (void* p : ing) if (p) (void)hipFree(p);
+    if (c->h_src_ptrs) (void)hipHostFree((void*)c->h_src_ptrs);
+    if (c->h_full_rgb) (void)hipHostFree(c->h_full_rgb);
     void* dev[] = {c->d_L, c->d_ab, c->d_mask, c->d_out, c->d_dist, c->d_scratch, c->d_glob_in, c->d_glob_vec, c->d_pred_ab, c->d_dist313, c->d_partial, c->d_rgb, c->d_labq, c->d_hints, c->d_centres, c->d_sugg, c->d_sugg_counts, c->d_post_in, c->d_map_ab, c->d_map_s};
     for (void* p : dev) if (p) (void)hipFree(p);
     void* host[] = {c->h_in, c->h_out, c->h_dist, c->h_pred_ab, c->h_rgb, c->h_labq, c->h_hints};
@@ -121,6 +126,12 @@ int run_lab_post(idc_context* h, int n, const float* d_Lp, float l_add, const fl
     if (!rgb_direct) memcpy(rgb, h->h_rgb, (size_t)n * hw * 3);
     if (lab_q && !lab_direct) memcpy(lab_q, h->h_labq, (size_t)n * hw * 3 * 8);
     return IDC_OK;
+}
+
+void drop_source(idc_context* h, int slot) {
+    if (slot < 0 || slot >= (int)h->src.size() || !h->src[slot].d_rgb) return;
+    (void)hipFree(h->src[slot].d_rgb);                   // (waits for the device: nothing that reads it is in flight after that)
+    h->src[slot] = idc_context::SlotSource();
 }
 
 }  // namespace idc
@@ -242,6 +253,7 @@ int idc_set_image_l(idc_handle h, int img, const float* L_mc) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipMemcpy(h->d_L + (size_t)img * hw, L_mc, hw * 4, hipMemcpyHostToDevice));
     h->l_set[img] = 1;
+    drop_source(h, img);
     return IDC_OK;
 }
 
@@ -281,6 +293,7 @@ int idc_set_hints(idc_handle h, int img, int n_hints, const idc_hint* hints, int
     if (kept) HIPCHK(h, hipMemcpyAsync(h->d_hints, h->h_hints, (size_t)kept * sizeof(HintRect), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, launch_raster_hints(h->d_hints, kept, mode, mask_value, h->d_ab + (size_t)img * hw * 2, h->d_mask + (size_t)img * hw,
                                   h->H, h->W, h->stream));
+    h->hint_mask_value[img] = mask_value;
     return IDC_OK;
 }
 
@@ -498,25 +511,33 @@ int idc_stream_signal(idc_handle h, void* caller_stream) {
 }
 
 // ---------------------------------------------------------------------------------------------- display step
+// the resident [2,H,W] planes `source` names for image slot img (IDC_SRC_OUTPUT_AB: float64, *f64 = 1), or why they are not there
+static int resident_ab_planes(idc_context* h, int img, int source, const void** pa, const void** pb, int* f64) {
+    const size_t hw = (size_t)h->H * h->W;
+    *f64 = 0;
+    if (source == IDC_SRC_OUTPUT_AB) {
+        if (!h->labq_resident || img >= h->last_n) return fail(&h->err, IDC_ERR_UNSUPPORTED, "no refreshed output_ab is resident (run idc_forward_rgb / idc_forward_resident with lab_q first)");
+        *pa = h->d_labq + ((size_t)img * 3 + 1) * hw; *pb = h->d_labq + ((size_t)img * 3 + 2) * hw; *f64 = 1;
+    } else if (source == IDC_SRC_OUTPUT_AB_RAW) {
+        if (!h->out_resident || img >= h->last_n) return fail(&h->err, IDC_ERR_UNSUPPORTED, "no forward result is resident");
+        *pa = h->d_out + (size_t)img * 2 * hw; *pb = h->d_out + ((size_t)img * 2 + 1) * hw;
+    } else if (source == IDC_SRC_INPUT_AB) {
+        *pa = h->d_ab + (size_t)img * 2 * hw; *pb = h->d_ab + ((size_t)img * 2 + 1) * hw;
+    } else {
+        return fail(&h->err, IDC_ERR_INVALID_ARG, "source %d not in 0..2", source);
+    }
+    return IDC_OK;
+}
+
 int idc_upsample_lab2rgb(idc_handle h, int img, int source, int interp, int out_h, int out_w, const double* L, uint8_t* rgb) {
     int rc = check_img(h, img);
     if (rc) return rc;
     if (!L || !rgb || out_h <= 0 || out_w <= 0) return fail(&h->err, IDC_ERR_INVALID_ARG, "bad output geometry / null pointer");
     if (interp < 0 || interp > 2) return fail(&h->err, IDC_ERR_INVALID_ARG, "interp %d not in 0..2", interp);
     HIPCHK(h, hipSetDevice(h->device));
-    const size_t hw = (size_t)h->H * h->W;
     const void *pa = nullptr, *pb = nullptr; int f64 = 0;
-    if (source == IDC_SRC_OUTPUT_AB) {
-        if (!h->labq_resident || img >= h->last_n) return fail(&h->err, IDC_ERR_UNSUPPORTED, "no refreshed output_ab is resident (run idc_forward_rgb / idc_forward_resident with lab_q first)");
-        pa = h->d_labq + ((size_t)img * 3 + 1) * hw; pb = h->d_labq + ((size_t)img * 3 + 2) * hw; f64 = 1;
-    } else if (source == IDC_SRC_OUTPUT_AB_RAW) {
-        if (!h->out_resident || img >= h->last_n) return fail(&h->err, IDC_ERR_UNSUPPORTED, "no forward result is resident");
-        pa = h->d_out + (size_t)img * 2 * hw; pb = h->d_out + ((size_t)img * 2 + 1) * hw;
-    } else if (source == IDC_SRC_INPUT_AB) {
-        pa = h->d_ab + (size_t)img * 2 * hw; pb = h->d_ab + ((size_t)img * 2 + 1) * hw;
-    } else {
-        return fail(&h->err, IDC_ERR_INVALID_ARG, "source %d not in 0..2", source);
-    }
+    rc = resident_ab_planes(h, img, source, &pa, &pb, &f64);
+    if (rc) return rc;
     rc = drain_pipeline(h);
     if (rc) return rc;
     const size_t np = (size_t)out_h * out_w;
@@ -539,6 +560,106 @@ int idc_upsample_lab2rgb(idc_handle h, int img, int source, int interp, int out_
     HIPCHK(h, hipMemcpyAsync(h->h_up_rgb, h->d_up_rgb, np * 3, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     memcpy(rgb, h->h_up_rgb, np * 3);
+    return IDC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- image ingestion
+static int ensure_ingest_buffers(idc_context* h) {
+    if (h->d_net_rgb) return IDC_OK;
+    const size_t hw = (size_t)h->H * h->W, nb = (size_t)h->max_batch;
+    HIPCHK(h, hipMalloc((void**)&h->d_src_ptrs, nb * sizeof(void*)));
+    HIPCHK(h, hipHostMalloc((void**)&h->h_src_ptrs, nb * sizeof(void*), hipHostMallocDefault));
+    HIPCHK(h, hipMalloc((void**)&h->d_net_lab, nb * hw * 3 * 8));
+    HIPCHK(h, hipMalloc((void**)&h->d_net_rgb, nb * hw * 3));
+    return IDC_OK;
+}
+
+int idc_set_image_rgb(idc_handle h, int img, int n, int src_h, int src_w, const uint8_t* rgb, float l_cent, unsigned flags,
+                      uint8_t* rgb_net, double* lab_net) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (!rgb) return fail(&h->err, IDC_ERR_INVALID_ARG, "null rgb");
+    if (flags & ~(unsigned)IDC_INGEST_KEEP_SOURCE) return fail(&h->err, IDC_ERR_INVALID_ARG, "unknown flag bits 0x%x", flags);
+    if (src_h < 1 || src_h > 16384 || src_w < 1 || src_w > 16384)
+        return fail(&h->err, IDC_ERR_INVALID_ARG, "source size %dx%d outside 1..16384", src_h, src_w);
+    if (n < 1 || img < 0 || img >= h->max_batch || n > h->max_batch - img)
+        return fail(&h->err, IDC_ERR_BATCH, "image slots %d..%d outside 0..%d", img, img + n - 1, h->max_batch - 1);
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = drain_pipeline(h);
+    if (rc) return rc;
+    rc = ensure_ingest_buffers(h);
+    if (rc) return rc;
+    const size_t hw = (size_t)h->H * h->W, sb = (size_t)src_h * src_w * 3;
+    const bool keep = (flags & IDC_INGEST_KEEP_SOURCE) != 0;
+    HIPCHK(h, hipStreamSynchronize(h->stream));            // the pointer table and the upload buffer of the previous call may still be read
+    for (int i = 0; i < n; ++i) drop_source(h, img + i);   // a slot's previous source goes either way; a kept one gets its own allocation
+    if (keep) {
+        for (int i = 0; i < n; ++i) {
+            auto& sl = h->src[img + i];
+            HIPCHK(h, hipMalloc((void**)&sl.d_rgb, sb));
+            sl.h = src_h; sl.w = src_w;
+            h->h_src_ptrs[i] = sl.d_rgb;
+        }
+    } else {
+        if (h->ingest_cap < (size_t)n * sb) {
+            if (h->d_ingest) (void)hipFree(h->d_ingest);
+            h->d_ingest = nullptr; h->ingest_cap = 0;
+            HIPCHK(h, hipMalloc((void**)&h->d_ingest, (size_t)n * sb));
+            h->ingest_cap = (size_t)n * sb;
+        }
+        for (int i = 0; i < n; ++i) h->h_src_ptrs[i] = h->d_ingest + (size_t)i * sb;
+    }
+    const bool in_pinned = is_pinned(rgb);                 // pinned: transferred in place on the stream; pageable: the runtime stages it
+    for (int i = 0; i < n; ++i) {
+        void* dst = (void*)h->h_src_ptrs[i];
+        if (in_pinned) HIPCHK(h, hipMemcpyAsync(dst, rgb + (size_t)i * sb, sb, hipMemcpyHostToDevice, h->stream));
+        else HIPCHK(h, hipMemcpy(dst, rgb + (size_t)i * sb, sb, hipMemcpyHostToDevice));
+    }
+    HIPCHK(h, hipMemcpyAsync((void*)h->d_src_ptrs, (const void*)h->h_src_ptrs, (size_t)n * sizeof(void*), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, launch_ingest_rgb(h->d_src_ptrs, n, src_h, src_w, h->H, h->W, l_cent, h->d_L + (size_t)img * hw, rgb_net ? h->d_net_rgb : nullptr,
+                                lab_net ? h->d_net_lab : nullptr, h->stream));
+    const bool rgb_direct = rgb_net && is_pinned(rgb_net), lab_direct = lab_net && is_pinned(lab_net);
+    if (rgb_direct) HIPCHK(h, hipMemcpyAsync(rgb_net, h->d_net_rgb, (size_t)n * hw * 3, hipMemcpyDeviceToHost, h->stream));
+    if (lab_direct) HIPCHK(h, hipMemcpyAsync(lab_net, h->d_net_lab, (size_t)n * hw * 3 * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (rgb_net && !rgb_direct) HIPCHK(h, hipMemcpy(rgb_net, h->d_net_rgb, (size_t)n * hw * 3, hipMemcpyDeviceToHost));
+    if (lab_net && !lab_direct) HIPCHK(h, hipMemcpy(lab_net, h->d_net_lab, (size_t)n * hw * 3 * 8, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; ++i) h->l_set[img + i] = 1;
+    return IDC_OK;
+}
+
+int idc_fullres_rgb(idc_handle h, int img, int source, int interp, int l_mode, uint8_t* rgb) {
+    int rc = check_img(h, img);
+    if (rc) return rc;
+    if (interp < 0 || interp > 2) return fail(&h->err, IDC_ERR_INVALID_ARG, "interp %d not in 0..2", interp);
+    if (l_mode != IDC_L_IMAGE && l_mode != IDC_L_MASK50) return fail(&h->err, IDC_ERR_INVALID_ARG, "l_mode %d not in 0..1", l_mode);
+    if (source < IDC_SRC_OUTPUT_AB || source > IDC_SRC_NO_AB) return fail(&h->err, IDC_ERR_INVALID_ARG, "source %d not in 0..3", source);
+    const auto& sl = h->src[img];
+    if (!sl.d_rgb) return fail(&h->err, IDC_ERR_UNSUPPORTED, "image slot %d has no resident source (idc_set_image_rgb with IDC_INGEST_KEEP_SOURCE)", img);
+    if (!rgb) return fail(&h->err, IDC_ERR_INVALID_ARG, "null rgb");
+    HIPCHK(h, hipSetDevice(h->device));
+    const void *pa = nullptr, *pb = nullptr; int f64 = 0;
+    if (source != IDC_SRC_NO_AB) {
+        rc = resident_ab_planes(h, img, source, &pa, &pb, &f64);
+        if (rc) return rc;
+    }
+    rc = drain_pipeline(h);
+    if (rc) return rc;
+    const size_t nbytes = (size_t)sl.h * sl.w * 3;
+    const bool direct = is_pinned(rgb);                    // a pinned result buffer is written in place; a pageable one through pinned staging
+    if (h->full_cap < nbytes) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (h->d_full_rgb) (void)hipFree(h->d_full_rgb);
+        if (h->h_full_rgb) (void)hipHostFree(h->h_full_rgb);
+        h->d_full_rgb = nullptr; h->h_full_rgb = nullptr; h->full_cap = 0;
+        HIPCHK(h, hipMalloc((void**)&h->d_full_rgb, nbytes));
+        h->full_cap = nbytes;
+    }
+    if (!direct && !h->h_full_rgb) HIPCHK(h, hipHostMalloc((void**)&h->h_full_rgb, h->full_cap, hipHostMallocDefault));
+    const float* mask = l_mode == IDC_L_MASK50 ? h->d_mask + (size_t)img * h->H * h->W : nullptr;
+    HIPCHK(h, launch_fullres_rgb(sl.d_rgb, sl.h, sl.w, pa, pb, f64, h->H, h->W, interp, mask, h->hint_mask_value[img], h->d_full_rgb, h->stream));
+    HIPCHK(h, hipMemcpyAsync(direct ? rgb : h->h_full_rgb, h->d_full_rgb, nbytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (!direct) memcpy(rgb, h->h_full_rgb, nbytes);
     return IDC_OK;
 }
 

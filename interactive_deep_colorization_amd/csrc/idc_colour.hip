@@ -1,5 +1,5 @@
 // idc_colour.hip -- colour space, display and layout helpers around the forward pass: Lab -> RGB, the fused upsample + Lab -> RGB of the display step,
-// the global-statistics extractor, the PCIe copy kernel and the NCHW <-> NHWC (split) converters.
+// the global-statistics extractor, image ingestion (uint8 RGB -> net-size Lab, full-resolution RGB from the resident source), the PCIe copy kernel and the NCHW <-> NHWC (split) converters.
 #include <stdlib.h>
 #include <type_traits>
 
@@ -134,6 +134,69 @@ __device__ __forceinline__ void cubic_coeffs(float x, float* c) {       // cv2 i
     c[3] = 1.f - c[0] - c[1] - c[2];
 }
 
+// scipy.ndimage.zoom's corner-aligned source coordinate of output pixel (dy, dx); an output dimension of 1 reads source coordinate 0
+__device__ __forceinline__ void zoom_coords(int dy, int dx, int H, int W, int oh, int ow, double& cyy, double& cxx) {
+    const double zy = oh > 1 ? (double)(H - 1) / (double)(oh - 1) : 0.0, zx = ow > 1 ? (double)(W - 1) / (double)(ow - 1) : 0.0;
+    cyy = dy * zy; cxx = dx * zx;
+}
+
+// interp 2: the source pixel zoom(order=0) reads for output pixel (dy, dx)
+__device__ __forceinline__ void zoom_nearest(int dy, int dx, int H, int W, int oh, int ow, int& yy, int& xx) {
+    double cyy, cxx;
+    zoom_coords(dy, dx, H, W, oh, ow, cyy, cxx);
+    yy = (int)floor(cyy + 0.5); xx = (int)floor(cxx + 0.5);
+    yy = yy < 0 ? 0 : (yy > H - 1 ? H - 1 : yy); xx = xx < 0 ? 0 : (xx > W - 1 ? W - 1 : xx);
+}
+
+// (a, b) of output pixel (dy, dx) of an [oh,ow] image from the planes pa, pb [H,W]: the three rules above
+template <typename S>
+__device__ __forceinline__ void interp_ab(const S* __restrict__ pa, const S* __restrict__ pb, int H, int W, int interp, int dy, int dx,
+                                          int oh, int ow, double* ab) {
+    if (interp == 0) {
+        const double sc_x = (double)W / ow, sc_y = (double)H / oh;
+        float fx = (float)((dx + 0.5) * sc_x - 0.5), fy = (float)((dy + 0.5) * sc_y - 0.5);
+        const int sx = (int)floorf(fx), sy = (int)floorf(fy);
+        fx -= sx; fy -= sy;
+        float cx[4], cy[4];
+        cubic_coeffs(fx, cx); cubic_coeffs(fy, cy);
+#pragma unroll
+        for (int ch = 0; ch < 2; ++ch) {
+            const S* src = ch ? pb : pa;
+            double rows[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                int yy = sy - 1 + k; yy = yy < 0 ? 0 : (yy > H - 1 ? H - 1 : yy);
+                double v = 0.0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    int xx = sx - 1 + j; xx = xx < 0 ? 0 : (xx > W - 1 ? W - 1 : xx);
+                    v += (double)src[(size_t)yy * W + xx] * (double)cx[j];
+                }
+                rows[k] = v;
+            }
+            ab[ch] = rows[0] * (double)cy[0] + rows[1] * (double)cy[1] + rows[2] * (double)cy[2] + rows[3] * (double)cy[3];
+        }
+    } else if (interp == 2) {
+        int yy, xx;
+        zoom_nearest(dy, dx, H, W, oh, ow, yy, xx);
+        ab[0] = (double)pa[(size_t)yy * W + xx]; ab[1] = (double)pb[(size_t)yy * W + xx];
+    } else {
+        double cyy, cxx;
+        zoom_coords(dy, dx, H, W, oh, ow, cyy, cxx);
+        int y0 = (int)floor(cyy), x0 = (int)floor(cxx);
+        const double ty = cyy - y0, tx = cxx - x0;
+        y0 = y0 < 0 ? 0 : (y0 > H - 1 ? H - 1 : y0); x0 = x0 < 0 ? 0 : (x0 > W - 1 ? W - 1 : x0);
+        const int y1 = y0 + 1 > H - 1 ? H - 1 : y0 + 1, x1 = x0 + 1 > W - 1 ? W - 1 : x0 + 1;   // weight 0 there
+#pragma unroll
+        for (int ch = 0; ch < 2; ++ch) {
+            const S* src = ch ? pb : pa;
+            const double v00 = (double)src[(size_t)y0 * W + x0], v01 = (double)src[(size_t)y0 * W + x1];
+            const double v10 = (double)src[(size_t)y1 * W + x0], v11 = (double)src[(size_t)y1 * W + x1];
+            ab[ch] = v00 * ((1.0 - ty) * (1.0 - tx)) + v01 * ((1.0 - ty) * tx) + v10 * (ty * (1.0 - tx)) + v11 * (ty * tx);
+        }
+    }
+}
+
 template <typename S>
 __global__ __launch_bounds__(256) void upsample_lab2rgb_kernel(const S* __restrict__ pa, const S* __restrict__ pb, int H, int W,
                                                                int interp, const double* __restrict__ Lout, int oh, int ow,
@@ -142,50 +205,7 @@ __global__ __launch_bounds__(256) void upsample_lab2rgb_kernel(const S* __restri
     for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (long long)gridDim.x * blockDim.x) {
         const int dy = (int)(p / ow), dx = (int)(p - (long long)dy * ow);
         double ab[2];
-        if (interp == 0) {
-            const double sc_x = (double)W / ow, sc_y = (double)H / oh;
-            float fx = (float)((dx + 0.5) * sc_x - 0.5), fy = (float)((dy + 0.5) * sc_y - 0.5);
-            const int sx = (int)floorf(fx), sy = (int)floorf(fy);
-            fx -= sx; fy -= sy;
-            float cx[4], cy[4];
-            cubic_coeffs(fx, cx); cubic_coeffs(fy, cy);
-#pragma unroll
-            for (int ch = 0; ch < 2; ++ch) {
-                const S* src = ch ? pb : pa;
-                double rows[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    int yy = sy - 1 + k; yy = yy < 0 ? 0 : (yy > H - 1 ? H - 1 : yy);
-                    double v = 0.0;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        int xx = sx - 1 + j; xx = xx < 0 ? 0 : (xx > W - 1 ? W - 1 : xx);
-                        v += (double)src[(size_t)yy * W + xx] * (double)cx[j];
-                    }
-                    rows[k] = v;
-                }
-                ab[ch] = rows[0] * (double)cy[0] + rows[1] * (double)cy[1] + rows[2] * (double)cy[2] + rows[3] * (double)cy[3];
-            }
-        } else {
-            const double zy = oh > 1 ? (double)(H - 1) / (double)(oh - 1) : 0.0, zx = ow > 1 ? (double)(W - 1) / (double)(ow - 1) : 0.0;
-            const double cyy = dy * zy, cxx = dx * zx;
-            if (interp == 2) {
-                int yy = (int)floor(cyy + 0.5), xx = (int)floor(cxx + 0.5);
-                yy = yy > H - 1 ? H - 1 : yy; xx = xx > W - 1 ? W - 1 : xx;
-                ab[0] = (double)pa[(size_t)yy * W + xx]; ab[1] = (double)pb[(size_t)yy * W + xx];
-            } else {
-                const int y0 = (int)floor(cyy), x0 = (int)floor(cxx);
-                const double ty = cyy - y0, tx = cxx - x0;
-                const int y1 = y0 + 1 > H - 1 ? H - 1 : y0 + 1, x1 = x0 + 1 > W - 1 ? W - 1 : x0 + 1;   // weight 0 there
-#pragma unroll
-                for (int ch = 0; ch < 2; ++ch) {
-                    const S* src = ch ? pb : pa;
-                    const double v00 = (double)src[(size_t)y0 * W + x0], v01 = (double)src[(size_t)y0 * W + x1];
-                    const double v10 = (double)src[(size_t)y1 * W + x0], v11 = (double)src[(size_t)y1 * W + x1];
-                    ab[ch] = v00 * ((1.0 - ty) * (1.0 - tx)) + v01 * ((1.0 - ty) * tx) + v10 * (ty * (1.0 - tx)) + v11 * (ty * tx);
-                }
-            }
-        }
+        interp_ab(pa, pb, H, W, interp, dy, dx, oh, ow, ab);
         unsigned char q[3];
         lab_to_rgb_u8(Lout[p], ab[0], ab[1], q);
         rgb[p * 3 + 0] = q[0]; rgb[p * 3 + 1] = q[1]; rgb[p * 3 + 2] = q[2];
@@ -213,15 +233,10 @@ hipError_t launch_upsample_lab2rgb(const void* a_plane, const void* b_plane, int
 // counted with integer atomics (deterministic); plus the sum of the HSV saturation (BGR2HSVLayer :53-85).
 // One thread per 4x4 block.  A 256x256 image is 4096 blocks: latency-, not bandwidth-relevant.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void rgb8_to_lab(const unsigned char* q, double& L, double& a, double& b) {
+// linear RGB -> Lab: the second half of skimage's rgb2lab (after the sRGB -> linear step)
+__device__ __forceinline__ void linear_to_lab(const double* lin, double& L, double& a, double& b) {
     const double M[3][3] = {{0.412453, 0.357580, 0.180423}, {0.212671, 0.715160, 0.072169}, {0.019334, 0.119193, 0.950227}};
     const double white[3] = {0.95047, 1.0, 1.08883};
-    double lin[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const double v = (double)q[c] / 255.0;
-        lin[c] = v > 0.04045 ? pow((v + 0.055) / 1.055, 2.4) : v / 12.92;
-    }
     double g[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
@@ -229,6 +244,18 @@ __device__ __forceinline__ void rgb8_to_lab(const unsigned char* q, double& L, d
         g[i] = t > 0.008856 ? cbrt(t) : 7.787 * t + 16.0 / 116.0;
     }
     L = 116.0 * g[1] - 16.0; a = 500.0 * (g[0] - g[1]); b = 200.0 * (g[1] - g[2]);
+}
+
+__device__ __forceinline__ double srgb8_to_linear(int q) {
+    const double v = (double)q / 255.0;
+    return v > 0.04045 ? pow((v + 0.055) / 1.055, 2.4) : v / 12.92;
+}
+
+__device__ __forceinline__ void rgb8_to_lab(const unsigned char* q, double& L, double& a, double& b) {
+    double lin[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) lin[c] = srgb8_to_linear(q[c]);
+    linear_to_lab(lin, L, a, b);
 }
 
 __global__ __launch_bounds__(256) void global_stats_kernel(const unsigned char* __restrict__ rgb, const float* __restrict__ centres,
@@ -270,6 +297,159 @@ hipError_t launch_global_stats(const unsigned char* rgb, const float* centres, u
     const long long nblk = (long long)N * (H / 4) * (W / 4);
     const int blocks = (int)((nblk + 255) / 256 < 1024 ? (nblk + 255) / 256 : 1024);
     hipLaunchKernelGGL(global_stats_kernel, dim3(blocks), dim3(256), 0, s, rgb, centres, counts, sat_sum, N, H, W);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// image ingestion: what ColorizeImageBase.load_image / set_image do on the host before the first click (data/colorize_image.py:52-77):
+// cv2.resize to the net size, rgb2lab, L - l_cent; and the full-resolution getters (:123-158) from the uint8 source kept on the device.
+// A uint8 channel has 256 possible sRGB -> linear values: each workgroup fills a 256-entry float64 table in LDS with srgb8_to_linear (the
+// per-pixel expression, so the table is bit-identical to it) and reads it -- one transcendental (cbrt) per Lab component left per pixel.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void fill_srgb_table(double* tab) {      // tab: 256 doubles of LDS; ends with a barrier
+    for (int i = threadIdx.x; i < 256; i += blockDim.x) tab[i] = srgb8_to_linear(i);
+    __syncthreads();
+}
+
+// One channel of colorspace.resize_bilinear_u8's output pixel from its four (clamped) taps: float64, the same expressions in the same
+// order, contraction off (an FMA would change a rounding) -> floor(out + .5) clamped to 0..255
+__device__ __forceinline__ int bilinear_u8(double f00, double f01, double f10, double f11, double wx, double wy) {
+#pragma clang fp contract(off)
+    const double top = f00 * (1.0 - wx) + f01 * wx;
+    const double bot = f10 * (1.0 - wx) + f11 * wx;
+    const double out = top * (1.0 - wy) + bot * wy;
+    const double r = floor(out + 0.5);
+    return r < 0.0 ? 0 : (r > 255.0 ? 255 : (int)r);
+}
+
+// half-pixel source coordinate of output index i: tap0 / tap1 clamped to 0..in-1, w = the weight of tap1
+__device__ __forceinline__ void bilinear_taps(int i, int in, int out, int& t0, int& t1, double& w) {
+#pragma clang fp contract(off)
+    const double s = ((double)i + 0.5) * ((double)in / (double)out) - 0.5;
+    const double fl = floor(s);
+    w = s - fl;
+    const long long i0 = (long long)fl;
+    t0 = (int)(i0 < 0 ? 0 : (i0 > in - 1 ? in - 1 : i0));
+    t1 = (int)(i0 + 1 < 0 ? 0 : (i0 + 1 > in - 1 ? in - 1 : i0 + 1));
+}
+
+// One thread per net-size pixel of all n images: srcs[i] = image i's [src_h,src_w,3] uint8 source; Lp = the resident L plane of the first
+// slot ([n][H*W] fp32, gets L - l_cent); rgb_net [n,H,W,3] and lab_net [n,3,H,W] may be nullptr.
+__global__ __launch_bounds__(256) void ingest_rgb_kernel(const unsigned char* const* __restrict__ srcs, int n, int src_h, int src_w, int H, int W,
+                                                         float l_cent, float* __restrict__ Lp, unsigned char* __restrict__ rgb_net,
+                                                         double* __restrict__ lab_net) {
+    __shared__ double tab[256];
+    fill_srgb_table(tab);
+    const long long HW = (long long)H * W, npix = (long long)n * HW;
+    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (long long)gridDim.x * blockDim.x) {
+        const long long i = p / HW, r = p - i * HW;
+        const int y = (int)(r / W), x = (int)(r - (long long)y * W);
+        int y0, y1, x0, x1;
+        double wy, wx;
+        bilinear_taps(y, src_h, H, y0, y1, wy);
+        bilinear_taps(x, src_w, W, x0, x1, wx);
+        const unsigned char* src = srcs[i];
+        const unsigned char* p00 = src + ((long long)y0 * src_w + x0) * 3; const unsigned char* p01 = src + ((long long)y0 * src_w + x1) * 3;
+        const unsigned char* p10 = src + ((long long)y1 * src_w + x0) * 3; const unsigned char* p11 = src + ((long long)y1 * src_w + x1) * 3;
+        int q[3];
+        double lin[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            q[c] = bilinear_u8((double)p00[c], (double)p01[c], (double)p10[c], (double)p11[c], wx, wy);
+            lin[c] = tab[q[c]];
+        }
+        double L, a, b;
+        linear_to_lab(lin, L, a, b);
+        Lp[p] = (float)(L - (double)l_cent);
+        if (rgb_net != nullptr) { rgb_net[p * 3 + 0] = (unsigned char)q[0]; rgb_net[p * 3 + 1] = (unsigned char)q[1]; rgb_net[p * 3 + 2] = (unsigned char)q[2]; }
+        if (lab_net != nullptr) {
+            lab_net[(i * 3 + 0) * HW + r] = L; lab_net[(i * 3 + 1) * HW + r] = a; lab_net[(i * 3 + 2) * HW + r] = b;
+        }
+    }
+}
+
+hipError_t launch_ingest_rgb(const unsigned char* const* srcs, int n, int src_h, int src_w, int H, int W, float l_cent, float* Lp,
+                             unsigned char* rgb_net, double* lab_net, hipStream_t s) {
+    const long long npix = (long long)n * H * W;
+    if (npix <= 0 || src_h <= 0 || src_w <= 0) return hipErrorInvalidValue;
+    const int blocks = (int)((npix + 255) / 256 < 4096 ? (npix + 255) / 256 : 4096);
+    hipLaunchKernelGGL(ingest_rgb_kernel, dim3(blocks), dim3(256), 0, s, srcs, n, src_h, src_w, H, W, l_cent, Lp, rgb_net, lab_net);
+    return hipGetLastError();
+}
+
+// One full-resolution output pixel p of an [oh,ow] image from its own source colour q: L = rgb2lab(q)[0] (mask == nullptr) or
+// 50 * nearest(mask) / mask_value (0 when mask_value == 0: no hints were ever rasterised), (a, b) interpolated from pa / pb [H,W]
+// (nullptr: a = b = 0), then lab_to_rgb_u8.
+template <typename S>
+__device__ __forceinline__ void fullres_pixel(long long p, const int* q, const double* tab, const S* __restrict__ pa, const S* __restrict__ pb,
+                                              int H, int W, int interp, const float* __restrict__ mask, float mask_value, int oh, int ow,
+                                              unsigned char* out) {
+    const int dy = (int)(p / ow), dx = (int)(p - (long long)dy * ow);
+    double L, ab[2] = {0.0, 0.0};
+    if (mask == nullptr) {
+        const double lin[3] = {tab[q[0]], tab[q[1]], tab[q[2]]};
+        double a_, b_;
+        linear_to_lab(lin, L, a_, b_);
+    } else if (mask_value != 0.f) {
+        int yy, xx;
+        zoom_nearest(dy, dx, H, W, oh, ow, yy, xx);
+        L = 50.0 * ((double)mask[(size_t)yy * W + xx] / (double)mask_value);
+    } else {
+        L = 0.0;
+    }
+    if (pa != nullptr) interp_ab(pa, pb, H, W, interp, dy, dx, oh, ow, ab);
+    lab_to_rgb_u8(L, ab[0], ab[1], out);
+}
+
+// A thread takes 4 consecutive pixels of the flattened image = 12 bytes = three aligned dwords in, three out (src and rgb are 4-byte aligned:
+// device allocations); the npix % 4 pixels at the end go one per thread through byte accesses.
+template <typename S>
+__global__ __launch_bounds__(256) void fullres_rgb_kernel(const unsigned char* __restrict__ src, int oh, int ow, const S* __restrict__ pa,
+                                                          const S* __restrict__ pb, int H, int W, int interp, const float* __restrict__ mask,
+                                                          float mask_value, unsigned char* __restrict__ rgb) {
+    __shared__ double tab[256];
+    fill_srgb_table(tab);
+    const long long npix = (long long)oh * ow, ngroups = npix >> 2;
+    const unsigned* src4 = (const unsigned*)src;
+    unsigned* rgb4 = (unsigned*)rgb;
+    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (long long)gridDim.x * blockDim.x) {
+        const unsigned in[3] = {src4[g * 3 + 0], src4[g * 3 + 1], src4[g * 3 + 2]};
+        unsigned out[3] = {0u, 0u, 0u};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            int q[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) q[c] = (int)((in[(k * 3 + c) >> 2] >> (8 * ((k * 3 + c) & 3))) & 255u);
+            unsigned char o[3];
+            fullres_pixel(g * 4 + k, q, tab, pa, pb, H, W, interp, mask, mask_value, oh, ow, o);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) out[(k * 3 + c) >> 2] |= (unsigned)o[c] << (8 * ((k * 3 + c) & 3));
+        }
+        rgb4[g * 3 + 0] = out[0]; rgb4[g * 3 + 1] = out[1]; rgb4[g * 3 + 2] = out[2];
+    }
+    if (blockIdx.x == 0) {
+        const long long p = ngroups * 4 + threadIdx.x;
+        if (p < npix) {
+            const int q[3] = {src[p * 3 + 0], src[p * 3 + 1], src[p * 3 + 2]};
+            unsigned char o[3];
+            fullres_pixel(p, q, tab, pa, pb, H, W, interp, mask, mask_value, oh, ow, o);
+            rgb[p * 3 + 0] = o[0]; rgb[p * 3 + 1] = o[1]; rgb[p * 3 + 2] = o[2];
+        }
+    }
+}
+
+hipError_t launch_fullres_rgb(const unsigned char* src, int oh, int ow, const void* a_plane, const void* b_plane, int src_f64, int H, int W,
+                              int interp, const float* mask, float mask_value, unsigned char* rgb, hipStream_t s) {
+    const long long npix = (long long)oh * ow;
+    if (npix <= 0 || interp < 0 || interp > 2 || (((uintptr_t)src | (uintptr_t)rgb) & 3)) return hipErrorInvalidValue;
+    const long long ngroups = (npix + 3) >> 2;
+    const int blocks = (int)((ngroups + 255) / 256 < 8192 ? (ngroups + 255) / 256 : 8192);
+    if (src_f64)
+        hipLaunchKernelGGL(fullres_rgb_kernel<double>, dim3(blocks), dim3(256), 0, s, src, oh, ow, (const double*)a_plane, (const double*)b_plane,
+                           H, W, interp, mask, mask_value, rgb);
+    else
+        hipLaunchKernelGGL(fullres_rgb_kernel<float>, dim3(blocks), dim3(256), 0, s, src, oh, ow, (const float*)a_plane, (const float*)b_plane,
+                           H, W, interp, mask, mask_value, rgb);
     return hipGetLastError();
 }
 

@@ -182,6 +182,16 @@ struct idc_context {
     float* d_centres = nullptr; double* d_sugg = nullptr; unsigned* d_sugg_counts = nullptr;   // colour suggestions
     float *d_map_ab = nullptr, *d_map_s = nullptr;   // idc_dist_decode / idc_dist_entropy results: [max_batch][2][npix], [max_batch][npix] (first use)
     std::vector<char> l_set;             // per image slot: d_L holds an uploaded L plane (idc_forward_resident refuses otherwise)
+    // image ingestion (idc_set_image_rgb / idc_fullres_rgb): per slot the uint8 source kept on the device (IDC_INGEST_KEEP_SOURCE; nullptr = none)
+    // and its size, and the mask_value of the slot's last idc_set_hints (0 = never had hints)
+    struct SlotSource { unsigned char* d_rgb = nullptr; int h = 0, w = 0; };
+    std::vector<SlotSource> src;
+    std::vector<float> hint_mask_value;
+    unsigned char* d_ingest = nullptr; size_t ingest_cap = 0;        // upload buffer of the sources that are not kept
+    const unsigned char** d_src_ptrs = nullptr;                      // [max_batch] source pointers of one ingest launch ...
+    const unsigned char** h_src_ptrs = nullptr;                      // ... and their pinned host copy
+    unsigned char* d_net_rgb = nullptr; double* d_net_lab = nullptr; // idc_set_image_rgb results [max_batch,H,W,3] u8, [max_batch,3,H,W] f64 (first use)
+    unsigned char *d_full_rgb = nullptr, *h_full_rgb = nullptr; size_t full_cap = 0;   // idc_fullres_rgb result and (pageable callers) its pinned staging; bytes of each
     hipEvent_t ev_sync = nullptr;        // idc_stream_wait / idc_stream_signal
     // two-slot transfer pipeline (idc_forward_async / idc_wait): each slot owns its device planes
     struct PipeSlot {
@@ -233,6 +243,7 @@ int fail(std::string* err, int code, const char* fmt, ...);
 int check_device(int device_id, std::string* err);
 int ensure_post_buffers(idc_context* h);
 int run_lab_post(idc_context* h, int n, const float* d_Lp, float l_add, const float* d_abp, uint8_t* rgb, double* lab_q);
+void drop_source(idc_context* h, int slot);      // the slot's L plane is about to be overwritten by something else than idc_set_image_rgb: its resident source goes
 
 // idc_pack.hip (make_blob_plan: idc_net.h)
 int f16_weight_exponent(const float* w, size_t n);

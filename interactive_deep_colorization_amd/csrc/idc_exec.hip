@@ -279,7 +279,7 @@ static int forward_host(idc_context* c, int n, const float* L_mc, const float* a
     rc = drain_pipeline(c);
     if (rc) return rc;
     const size_t hw = (size_t)c->H * c->W;
-    if (L_mc) for (int i = 0; i < n; ++i) c->l_set[i] = 1;
+    if (L_mc) for (int i = 0; i < n; ++i) { c->l_set[i] = 1; drop_source(c, i); }
     c->out_resident = true; c->labq_resident = false;
     // Pinned caller buffers (idc_alloc_host / hipHostMalloc / hipHostRegister) are transferred in place; pageable ones go through
     // the handle's pinned staging with a host memcpy (2.2 MB per click through the reference API: most of its host-side time).

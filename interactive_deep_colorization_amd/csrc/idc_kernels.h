@@ -245,6 +245,18 @@ hipError_t launch_lab_post(const float* L, float l_add, const float* ab, unsigne
 hipError_t launch_upsample_lab2rgb(const void* a_plane, const void* b_plane, int src_f64, int H, int W, int interp, const double* L_out,
                                    int oh, int ow, unsigned char* rgb, hipStream_t s);
 
+// Image ingestion (colorize_image.py:52-77): srcs [n] device pointers to [src_h,src_w,3] u8 images -> bilinear net-size rgb_net [n,H,W,3] u8
+// (colorspace.resize_bilinear_u8's rule, float64; the identity at src == net size), lab_net [n,3,H,W] f64 = rgb2lab of it (either may be
+// nullptr) and Lp [n][H*W] fp32 = L - l_cent, in one launch
+hipError_t launch_ingest_rgb(const unsigned char* const* srcs, int n, int src_h, int src_w, int H, int W, float l_cent, float* Lp,
+                             unsigned char* rgb_net, double* lab_net, hipStream_t s);
+
+// Full-resolution getters (colorize_image.py:123-158) from the resident uint8 source src [oh,ow,3]: L = rgb2lab(src)[0] (mask == nullptr) or
+// 50 * zoom(mask, order 0) / mask_value (mask [H,W] fp32; mask_value 0: L = 0), (a, b) planes [H,W] (fp32 or fp64; nullptr: a = b = 0)
+// resized as in launch_upsample_lab2rgb, Lab -> sRGB uint8 -> rgb [oh,ow,3].  src and rgb 4-byte aligned.
+hipError_t launch_fullres_rgb(const unsigned char* src, int oh, int ow, const void* a_plane, const void* b_plane, int src_f64, int H, int W,
+                              int interp, const float* mask, float mask_value, unsigned char* rgb, hipStream_t s);
+
 // Global statistics (global_stats.prototxt): rgb u8 [N,H,W,3] -> counts [N][313] (uint32, zeroed by the caller) of
 // the 4x4-pooled ab values' nearest centre, and sat_sum [N] (float64, zeroed) = sum of HSV saturation over pixels.
 hipError_t launch_global_stats(const unsigned char* rgb, const float* centres, unsigned* counts, double* sat_sum, int N,

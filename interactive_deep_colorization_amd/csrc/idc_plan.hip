@@ -542,6 +542,8 @@ int alloc_graph(idc_context* c) {
     HIPCHK(c, hipMemset(c->d_mask, 0, nb * hw * 4));
     HIPCHK(c, hipMemset(c->d_out, 0, nb * hw * 2 * 4));
     c->l_set.assign(nb, 0);
+    c->src.assign(nb, idc_context::SlotSource());
+    c->hint_mask_value.assign(nb, 0.f);
     HIPCHK(c, hipMalloc(&c->d_zeros, 256));
     HIPCHK(c, hipMemset(c->d_zeros, 0, 256));
     if (c->precision == IDC_BF16) {              // conv_kwave_chain_bf16's grid-barrier counter and its host-visible abort flag

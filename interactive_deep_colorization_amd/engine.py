@@ -333,6 +333,7 @@ class HipColorizer(object):
         self._pool = _result_pool(self.lib)
         self.forward_serial = 0             # bumped by every call that replaces the handle's resident results (api.py's lazy output attributes)
         self.l_serial = 0                   # bumped by every call that may write image slot 0's L plane (set_image_l and every forward): api.py's resident L
+        self._src_shape = {}                # image slot -> (h, w) of the source set_image_rgb(keep_source=True) left on the device
         self.before_overwrite = None        # callable run ONCE right before the next such call: whoever still wants the resident results fetches them
 
     # ---- lifetime -------------------------------------------------------------------------
@@ -482,6 +483,60 @@ class HipColorizer(object):
         L = _f32c(np.asarray(L_mc).reshape(self.H, self.W))
         self.l_serial += 1
         self._chk(self.lib.idc_set_image_l(self._h, int(img), _fptr(L)))
+
+    def set_image_rgb(self, rgb, img=0, l_cent=50., keep_source=False, want_rgb=True, want_lab=True):
+        """Ingest uint8 RGB image(s) on the device (``idc_set_image_rgb``): rgb (h,w,3) or (n,h,w,3), any size up to 16384 a side, go to
+        slots img..img+n-1 -- bilinear resize to the net size (``colorspace.resize_bilinear_u8``'s rule; none at the net size), rgb2lab,
+        and the slot's resident plane becomes L - l_cent, as after ``set_image_l``.  Returns (rgb_net (n,H,W,3) uint8 | None,
+        lab_net (n,3,H,W) float64 | None).  ``keep_source``: the source stays on the device for ``fullres_rgb``."""
+        rgb = np.ascontiguousarray(np.asarray(rgb), dtype=np.uint8)
+        if rgb.ndim == 3:
+            rgb = rgb[None]
+        if rgb.ndim != 4 or rgb.shape[3] != 3:
+            raise ValueError("rgb must be (h,w,3) or (n,h,w,3) uint8, got %s" % (rgb.shape,))
+        n, sh, sw = rgb.shape[:3]
+        net = self._pool.take((n, self.H, self.W, 3), np.uint8) if want_rgb else None
+        lab = self._pool.take((n, 3, self.H, self.W), np.float64) if want_lab else None
+        vp = ctypes.c_void_p
+        self.l_serial += 1
+        try:
+            self._chk(self.lib.idc_set_image_rgb(self._h, int(img), n, sh, sw, rgb.ctypes.data_as(vp), float(l_cent),
+                                                 N.IDC_INGEST_KEEP_SOURCE if keep_source else 0,
+                                                 net.ctypes.data_as(vp) if want_rgb else None, lab.ctypes.data_as(vp) if want_lab else None))
+        except N.IdcError as ex:
+            if ex.status not in (-1, -6):           # (a call refused for its arguments changed nothing; after any other failure the slots' sources are gone)
+                for i in range(n):
+                    self._src_shape.pop(int(img) + i, None)
+            raise
+        for i in range(n):
+            if keep_source:
+                self._src_shape[int(img) + i] = (sh, sw)
+            else:
+                self._src_shape.pop(int(img) + i, None)
+        return net, lab
+
+    def fullres_rgb(self, source="output_ab", interp="linear", l_mode="image", img=0):
+        """The full-resolution getters from the resident source of slot ``img`` (``idc_fullres_rgb``) -> (src_h, src_w, 3) uint8.
+        source: 'output_ab', 'output_ab_raw', 'input_ab' as in ``upsample_lab2rgb``, or 'no_ab' (a = b = 0); interp: 'cubic', 'linear',
+        'nearest'; l_mode: 'image' (L of the source pixel) or 'mask50' (50 x the nearest-upsampled hint mask).  IdcError (UNSUPPORTED)
+        when the slot has no resident source: ``set_image_rgb(keep_source=True)`` first, and nothing else may have written its L plane."""
+        src = {"output_ab": N.IDC_SRC_OUTPUT_AB, "output_ab_raw": N.IDC_SRC_OUTPUT_AB_RAW, "input_ab": N.IDC_SRC_INPUT_AB,
+               "no_ab": N.IDC_SRC_NO_AB}[source]
+        itp = {"cubic": N.IDC_INTERP_CUBIC, "linear": N.IDC_INTERP_LINEAR, "nearest": N.IDC_INTERP_NEAREST}[interp]
+        lm = {"image": N.IDC_L_IMAGE, "mask50": N.IDC_L_MASK50}[l_mode]
+        shape = self._src_shape.get(int(img))
+        self.l_serial += 1
+        if shape is None:       # no source was kept through this object: the library says so (without a result pointer it cannot write anything)
+            self._chk(self.lib.idc_fullres_rgb(self._h, int(img), src, itp, lm, None))
+            raise N.IdcError(-7, "the source of image slot %d was not ingested through this object" % img)
+        rgb = self._pool.take(shape + (3,), np.uint8)
+        try:
+            self._chk(self.lib.idc_fullres_rgb(self._h, int(img), src, itp, lm, rgb.ctypes.data_as(ctypes.c_void_p)))
+        except N.IdcError as ex:
+            if ex.status == -7 and "resident source" in str(ex):
+                self._src_shape.pop(int(img), None)
+            raise
+        return rgb
 
     def set_hints(self, hints, mode="ab", img=0, mask_value=1.0):
         """Rasterise a hint list on the device.  hints: rows (y0, x0, y1, x1, c0, c1[, c2]) -- inclusive rectangle and
