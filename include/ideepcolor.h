@@ -406,6 +406,33 @@ enum { IDC_SRC_NO_AB = 3 };               /* joins IDC_SRC_*: a = b = 0 */
 enum { IDC_L_IMAGE = 0, IDC_L_MASK50 = 1 };
 int idc_fullres_rgb(idc_handle h, int img, int source, int interp, int l_mode, uint8_t* rgb);
 
+/* ---- colour picker on the device: replaces data/lab_gamut.py, the host colour maths the GUI runs on every mouse press
+ *      (ui/gui_draw.py:11,182-183,195-204; ui/gui_gamut.py:4), in float64 with the constants and operation order of idc_lab2rgb.
+ *      idc_gamut_map = abGrid(gamut_size, D).update_gamut(L[k]) (lab_gamut.py:56-78) for k = 0..n-1 in one launch.  The grid has
+ *      side A = B = len(arange(-gamut_size, gamut_size + D, D)) = ceil(2 gamut_size / D) + 1; point (i, j) is (a, b) =
+ *      (-gamut_size + i D, -gamut_size + j D): the row is a, the column b (:58-60).  Per point
+ *          pts_rgb    = (255 * clip(lab2rgb(L, a, b), 0, 1)) truncated to uint8                                       (:70)
+ *          mask       = |(L, a, b) - rgb2lab(pts_rgb / 255)|_2 < 1.0, strictly                                       (:71-74)
+ *          masked_rgb = mask ? pts_rgb : 255                                                                         (:75-77)
+ *      pts_rgb / masked_rgb [n,A,B,3] uint8, mask [n,A,B] uint8 in {0,1}; each may be NULL, not all three.
+ *      idc_snap_colors = snap_ab(L[k], rgb[k]) (lab_gamut.py:28-52) for n colours in one launch: Lab of the colour, then up to 20
+ *      rounds of "L := L[k]; lab -> clip(rgb, 0, 1) -> lab" on the UNQUANTISED sRGB triple, ending after the first round whose
+ *      sum |delta lab| < 1.  As in the reference, the Lab value that leaves the loop carries the round-tripped L, not L[k] (:36-40).
+ *          rgb_out [n,3] uint8  = round-half-even(clip(lab2rgb(that Lab), 0, 1) * 255)     return_type 'rgb'         (:46, :24)
+ *          lab_out [n,3] f64    = rgb2lab(rgb_out / 255)                                   return_type 'lab'         (:51)
+ *          iters   [n]   int32  = rounds run, 1..20 (no reference counterpart: tells a knife-edge case from a wrong formula)
+ *      each may be NULL, not all three.  rgb [n,3] uint8.
+ *      Both need a handle but no weights, enqueue on the handle's stream and block until the result is on the host.  They neither read
+ *      nor write the handle's resident state (L / hint planes, the last forward's maps and distribution, kept sources, the pipelined
+ *      slots); their staging buffers grow on demand and are freed by idc_destroy.
+ *      Status: IDC_ERR_INVALID_ARG for n < 1, n > 64 maps / n > 65536 colours, a NULL input, a non-finite L (checked on the host before
+ *      anything is launched), gamut_size outside 1..512, D outside 1..gamut_size, or every output NULL. */
+#define IDC_GAMUT_MAX_MAPS 64
+#define IDC_GAMUT_MAX_SIZE 512
+#define IDC_SNAP_MAX_COLORS 65536
+int idc_gamut_map(idc_handle h, int n, const double* L, int gamut_size, int D, uint8_t* pts_rgb, uint8_t* masked_rgb, uint8_t* mask);
+int idc_snap_colors(idc_handle h, int n, const double* L, const uint8_t* rgb, uint8_t* rgb_out, double* lab_out, int32_t* iters);
+
 /* ---- introspection for parity tests and roofline accounting -------------------------------- */
 int idc_num_layers(idc_handle h);
 typedef struct idc_layer_info {

@@ -362,10 +362,11 @@ class ColorizeImageBase(object):
         self.input_mask_mult = input_mask if self.mask_mult == 1 else input_mask * self.mask_mult
         return 0
 
-    def _stage_hints(self, hints, mode):
+    def _stage_hints(self, hints, mode, snap=False):
         """Guards of net_forward, then: L plane resident (uploaded once per image), hint list rasterised on the
         device -- what ``UIControl.get_input`` + ``rgb2lab`` (``ui/ui_control.py:177-187``, ``ui/gui_draw.py:273-277``)
-        or the notebook's ``put_point`` do on the host before every forward."""
+        or the notebook's ``put_point`` do on the host before every forward.  ``snap``: the colours are snapped into the gamut first
+        (``_snap_hints``)."""
         for ready, complaint in ((self.img_l_set, 'I need to have an image!'),
                                  (self.net_set, 'I need to have a net!')):
             if not ready:
@@ -373,17 +374,70 @@ class ColorizeImageBase(object):
                 return -1
         if self.ab_mean != 0 or self.ab_norm != 1:
             raise ValueError('device-side hints assume raw ab inputs (ab_mean 0, ab_norm 1)')
+        if snap:
+            hints = self._snap_hints(hints, mode)
         self._ensure_l_resident()
         self.net.set_hints(hints, mode=mode, img=0, mask_value=self.mask_mult)
         self._hints_on_device = True
         return 0
 
-    def net_forward_hints(self, hints, mode='rgb'):
+    # ------------------------------------------------------------------ colour picker on the device (opt-in, not in the reference class)
+    def _picker_engine(self, call):
+        if not self.net_set or not hasattr(self.net, call):
+            raise RuntimeError('get_gamut / snap_color / snap=True need prep_net first, and an engine with %s' % call)
+        if not self.img_l_set:
+            raise RuntimeError('I need to have an image!')
+        return self.net
+
+    def get_gamut(self, h, w, gamut_size=110, D=1):
+        """The colour picker's gamut at the lightness of pixel (h, w): ``abGrid(gamut_size, D).update_gamut(img_l[0, h, w])`` on the
+        device -> (masked_rgb (A,B,3) uint8, mask (A,B) bool), what ``change_color`` emits (``ui/gui_draw.py:182-183``)."""
+        masked, mask = self._picker_engine('gamut_map').gamut_map(float(self.img_l[0, h, w]), gamut_size, D)
+        return masked[0], mask[0]
+
+    def snap_color(self, h, w, rgb, return_type='rgb'):
+        """``calibrate_color`` (``ui/gui_draw.py:195-204``): ``snap_ab(img_l[0, h, w], rgb)`` on the device -> (3,) uint8
+        (return_type 'rgb') or (3,) float64 Lab ('lab'); anything else returns None, as ``snap_ab`` does."""
+        if return_type not in ('rgb', 'lab'):
+            return None
+        net = self._picker_engine('snap_colors')
+        rgb = np.asarray(rgb).astype(np.uint8)
+        if return_type == 'rgb':
+            return net.snap_colors(float(self.img_l[0, h, w]), rgb)[0]
+        return net.snap_colors(float(self.img_l[0, h, w]), rgb, want_lab=True)[1][0]
+
+    def _snap_hints(self, hints, mode):
+        """Every edit's colour snapped at the image's L under the rectangle's centre -- ``((y0+y1)//2, (x0+x1)//2)`` of the ordered
+        corners clamped into the image: the click position of ``ui/ui_control.py:52-63`` -- all edits in ONE ``snap_colors`` call.
+        Returns the edit list with the snapped colours, which are also left in ``self.snapped_hint_colors`` (n,3) uint8."""
+        if mode != 'rgb':
+            raise ValueError("snap=True needs mode='rgb' (an (a, b) hint carries no colour to snap)")
+        rows = [tuple(r) for r in hints]
+        if not rows:
+            self.snapped_hint_colors = np.zeros((0, 3), np.uint8)
+            return rows
+        net = self._picker_engine('snap_colors')
+        H, W = self.img_l.shape[1:]
+        ls = np.empty(len(rows), np.float64)
+        for i, r in enumerate(rows):
+            y0, y1 = sorted((int(r[0]), int(r[2])))
+            x0, x1 = sorted((int(r[1]), int(r[3])))
+            y0, y1 = min(max(y0, 0), H - 1), min(max(y1, 0), H - 1)
+            x0, x1 = min(max(x0, 0), W - 1), min(max(x1, 0), W - 1)
+            ls[i] = self.img_l[0, (y0 + y1) // 2, (x0 + x1) // 2]
+        cols = np.array([r[4:7] for r in rows]).astype(np.uint8)
+        snapped = net.snap_colors(ls, cols)
+        self.snapped_hint_colors = snapped
+        return [tuple(r[:4]) + tuple(int(v) for v in c) for r, c in zip(rows, snapped)]
+
+    def net_forward_hints(self, hints, mode='rgb', snap=False):
         """``net_forward`` for a list of edits instead of rasterised planes (not in the reference: it removes the last
         per-click host work).  hints: rows ``(y0, x0, y1, x1, r, g, b)`` (mode 'rgb': uint8
         colours, rectangle corners inclusive as ``cv2.rectangle``) or ``(y0, x0, y1, x1, a, b)`` (mode 'ab').
+        ``snap=True`` (mode 'rgb' only): each colour first goes through ``snap_ab`` at the image's L under its rectangle's centre, on the
+        device, as the GUI's ``calibrate_color`` does before an edit is stored; the painted colours are ``self.snapped_hint_colors``.
         Returns what ``net_forward`` returns."""
-        if self._stage_hints(hints, mode) == -1:
+        if self._stage_hints(hints, mode, snap) == -1:
             return -1
         raw, rgb, lab_q = self.net.forward_resident(1, getattr(self, 'mask_cent', 0), l_cent=self.l_mean)
         self._l_serial = getattr(self.net, 'l_serial', None)
@@ -723,8 +777,8 @@ class ColorizeImageTorchDist(_DistMaps, ColorizeImageTorch):
         self.output_ab_raw = out_ab[0]
         return out_ab[0] * np.float32(110.)
 
-    def net_forward_hints(self, hints, mode='rgb'):
-        if self._stage_hints(hints, mode) == -1:
+    def net_forward_hints(self, hints, mode='rgb', snap=False):
+        if self._stage_hints(hints, mode, snap) == -1:
             return -1
         out_ab, _, _ = self.net.forward_resident(1, self.mask_cent, want_rgb=False)
         self._dist_on_device = True
@@ -855,14 +909,14 @@ class ColorizeImageCaffeGlobDist(ColorizeImageCaffe):
             g[0, 313] = self.glob_mask_mult
         self.net.set_global_hints(g)
 
-    def net_forward_hints(self, hints, mode='rgb', glob_dist=-1):
+    def net_forward_hints(self, hints, mode='rgb', glob_dist=-1, snap=False):
         """Edit-list form; the global hint is an argument here too (default -1 = none), never a leftover of an earlier
         call."""
         if not self.net_set:
             print('I need to have a net!')
             return -1
         self._set_glob(glob_dist)
-        ret = ColorizeImageCaffe.net_forward_hints(self, hints, mode)
+        ret = ColorizeImageCaffe.net_forward_hints(self, hints, mode, snap)
         if isinstance(ret, int):
             return ret
         self._set_out_ab_()
@@ -947,9 +1001,9 @@ class ColorizeImageCaffeDist(_DistMaps, ColorizeImageCaffe):
         self.dist_ab_set = True
         return ret
 
-    def net_forward_hints(self, hints, mode='rgb'):
+    def net_forward_hints(self, hints, mode='rgb', snap=False):
         """Edits rasterised on the device, then the regular 313-head forward on the read-back planes."""
-        if self._stage_hints(hints, mode) == -1:
+        if self._stage_hints(hints, mode, snap) == -1:
             return -1
         return self.net_forward(self.input_ab, self.input_mask)
 

@@ -1,6 +1,6 @@
 // idc_api.hip -- the handle and what a caller does with it besides weights and forwards (C ABI, include/ideepcolor.h): create / destroy, the last-error
 // string (fail), I/O scales, global hints, the click session, Lab -> RGB, colour suggestions and distributions, the global histogram, stream
-// ordering, the display upsample and image ingestion (uint8 RGB in, full-resolution RGB out).
+// ordering, the display upsample, image ingestion (uint8 RGB in, full-resolution RGB out) and the colour picker (gamut map, colour snapping).
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -80,6 +80,8 @@ static void destroy_ctx(idc_context* c) {
     for (void* p : ing) if (p) (void)hipFree(p);
     if (c->h_src_ptrs) (void)hipHostFree((void*)c->h_src_ptrs);
     if (c->h_full_rgb) (void)hipHostFree(c->h_full_rgb);
+    if (c->d_pick) (void)hipFree(c->d_pick);
+    if (c->h_pick) (void)hipHostFree(c->h_pick);
     void* dev[] = {c->d_L, c->d_ab, c->d_mask, c->d_out, c->d_dist, c->d_scratch, c->d_glob_in, c->d_glob_vec, c->d_pred_ab, c->d_dist313, c->d_partial, c->d_rgb, c->d_labq, c->d_hints, c->d_centres, c->d_sugg, c->d_sugg_counts, c->d_post_in, c->d_map_ab, c->d_map_s};
     for (void* p : dev) if (p) (void)hipFree(p);
     void* host[] = {c->h_in, c->h_out, c->h_dist, c->h_pred_ab, c->h_rgb, c->h_labq, c->h_hints};
@@ -660,6 +662,81 @@ int idc_fullres_rgb(idc_handle h, int img, int source, int interp, int l_mode, u
     HIPCHK(h, hipMemcpyAsync(direct ? rgb : h->h_full_rgb, h->d_full_rgb, nbytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (!direct) memcpy(rgb, h->h_full_rgb, nbytes);
+    return IDC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- colour picker
+// One device and one pinned buffer carry a call's inputs and results; both calls block, so nothing of the previous call is in flight when they grow
+static int ensure_pick_buffers(idc_context* h, size_t bytes) {
+    if (h->pick_cap >= bytes) return IDC_OK;
+    const size_t cap = bytes < 65536 ? 65536 : bytes;
+    if (h->d_pick) (void)hipFree(h->d_pick);
+    if (h->h_pick) (void)hipHostFree(h->h_pick);
+    h->d_pick = nullptr; h->h_pick = nullptr; h->pick_cap = 0;
+    HIPCHK(h, hipMalloc((void**)&h->d_pick, cap));
+    HIPCHK(h, hipHostMalloc((void**)&h->h_pick, cap, hipHostMallocDefault));
+    h->pick_cap = cap;
+    return IDC_OK;
+}
+
+static int check_pick_L(idc_context* h, int n, const double* L) {
+    for (int k = 0; k < n; ++k)
+        if (!std::isfinite(L[k])) return fail(&h->err, IDC_ERR_INVALID_ARG, "L[%d] is not finite", k);
+    return IDC_OK;
+}
+
+int idc_gamut_map(idc_handle h, int n, const double* L, int gamut_size, int D, uint8_t* pts_rgb, uint8_t* masked_rgb, uint8_t* mask) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (n < 1 || n > IDC_GAMUT_MAX_MAPS) return fail(&h->err, IDC_ERR_INVALID_ARG, "%d maps outside 1..%d", n, IDC_GAMUT_MAX_MAPS);
+    if (!L) return fail(&h->err, IDC_ERR_INVALID_ARG, "null L");
+    if (gamut_size < 1 || gamut_size > IDC_GAMUT_MAX_SIZE) return fail(&h->err, IDC_ERR_INVALID_ARG, "gamut_size %d outside 1..%d", gamut_size, IDC_GAMUT_MAX_SIZE);
+    if (D < 1 || D > gamut_size) return fail(&h->err, IDC_ERR_INVALID_ARG, "D %d outside 1..gamut_size (%d)", D, gamut_size);
+    if (!pts_rgb && !masked_rgb && !mask) return fail(&h->err, IDC_ERR_INVALID_ARG, "every output is null");
+    int rc = check_pick_L(h, n, L);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    const int A = (2 * gamut_size + D - 1) / D + 1;        // len(arange(-gamut_size, gamut_size + D, D))
+    const size_t in_bytes = (size_t)n * 8, np = (size_t)n * A * A;
+    const size_t o_pts = in_bytes, o_masked = o_pts + (pts_rgb ? np * 3 : 0), o_mask = o_masked + (masked_rgb ? np * 3 : 0);
+    const size_t total = o_mask + (mask ? np : 0);
+    rc = ensure_pick_buffers(h, total);
+    if (rc) return rc;
+    memcpy(h->h_pick, L, in_bytes);
+    HIPCHK(h, hipMemcpyAsync(h->d_pick, h->h_pick, in_bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, launch_gamut_map((const double*)h->d_pick, n, gamut_size, D, A, pts_rgb ? h->d_pick + o_pts : nullptr,
+                               masked_rgb ? h->d_pick + o_masked : nullptr, mask ? h->d_pick + o_mask : nullptr, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->h_pick + in_bytes, h->d_pick + in_bytes, total - in_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (pts_rgb) memcpy(pts_rgb, h->h_pick + o_pts, np * 3);
+    if (masked_rgb) memcpy(masked_rgb, h->h_pick + o_masked, np * 3);
+    if (mask) memcpy(mask, h->h_pick + o_mask, np);
+    return IDC_OK;
+}
+
+int idc_snap_colors(idc_handle h, int n, const double* L, const uint8_t* rgb, uint8_t* rgb_out, double* lab_out, int32_t* iters) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (n < 1 || n > IDC_SNAP_MAX_COLORS) return fail(&h->err, IDC_ERR_INVALID_ARG, "%d colours outside 1..%d", n, IDC_SNAP_MAX_COLORS);
+    if (!L || !rgb) return fail(&h->err, IDC_ERR_INVALID_ARG, "null L or rgb");
+    if (!rgb_out && !lab_out && !iters) return fail(&h->err, IDC_ERR_INVALID_ARG, "every output is null");
+    int rc = check_pick_L(h, n, L);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    // [L n f64][rgb n*3 u8, padded to 8][lab_out n*3 f64][iters n i32][rgb_out n*3 u8]: inputs first, every section aligned for its type
+    const size_t nn = (size_t)n, o_rgb = nn * 8, in_bytes = o_rgb + ((nn * 3 + 7) & ~(size_t)7);
+    const size_t o_lab = in_bytes, o_it = o_lab + (lab_out ? nn * 24 : 0), o_out = o_it + (iters ? nn * 4 : 0);
+    const size_t total = o_out + (rgb_out ? nn * 3 : 0);
+    rc = ensure_pick_buffers(h, total);
+    if (rc) return rc;
+    memcpy(h->h_pick, L, nn * 8);
+    memcpy(h->h_pick + o_rgb, rgb, nn * 3);
+    HIPCHK(h, hipMemcpyAsync(h->d_pick, h->h_pick, in_bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, launch_snap_colors((const double*)h->d_pick, h->d_pick + o_rgb, n, rgb_out ? h->d_pick + o_out : nullptr,
+                                 lab_out ? (double*)(h->d_pick + o_lab) : nullptr, iters ? (int*)(h->d_pick + o_it) : nullptr, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->h_pick + in_bytes, h->d_pick + in_bytes, total - in_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (lab_out) memcpy(lab_out, h->h_pick + o_lab, nn * 24);
+    if (iters) memcpy(iters, h->h_pick + o_it, nn * 4);
+    if (rgb_out) memcpy(rgb_out, h->h_pick + o_out, nn * 3);
     return IDC_OK;
 }
 

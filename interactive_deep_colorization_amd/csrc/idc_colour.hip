@@ -1,5 +1,6 @@
 // idc_colour.hip -- colour space, display and layout helpers around the forward pass: Lab -> RGB, the fused upsample + Lab -> RGB of the display step,
-// the global-statistics extractor, image ingestion (uint8 RGB -> net-size Lab, full-resolution RGB from the resident source), the PCIe copy kernel and the NCHW <-> NHWC (split) converters.
+// the global-statistics extractor, image ingestion (uint8 RGB -> net-size Lab, full-resolution RGB from the resident source), the colour picker's
+// gamut map and colour snapping, the PCIe copy kernel and the NCHW <-> NHWC (split) converters.
 #include <stdlib.h>
 #include <type_traits>
 
@@ -105,7 +106,8 @@ hipError_t launch_pcie_copy(void* dst, const void* src, size_t bytes, hipStream_
 //   interp 1: scipy.ndimage.zoom(order=1): coordinate = dst * (in - 1) / (out - 1), linear, double;
 //   interp 2: scipy.ndimage.zoom(order=0): nearest of the same coordinate (floor(c + .5)).
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void lab_to_rgb_u8(double L, double a, double b, unsigned char* q) {
+// Lab -> sRGB clipped to [0, 1], not quantised: s[3].  lab_to_rgb_u8 truncates it to uint8; the colour picker's snap loop converts it straight back.
+__device__ __forceinline__ void lab_to_srgb(double L, double a, double b, double* sv) {
     const double Mi[3][3] = {{3.240481343200526, -1.5371515162713185, -0.4985363261688878},
                              {-0.9692549499965682, 1.8759900014898907, 0.04155592655829284},
                              {0.05564663913517716, -0.20404133836651123, 1.0573110696453443}};
@@ -121,9 +123,15 @@ __device__ __forceinline__ void lab_to_rgb_u8(double L, double a, double b, unsi
     for (int c = 0; c < 3; ++c) {
         const double lin = xyz[0] * Mi[c][0] + xyz[1] * Mi[c][1] + xyz[2] * Mi[c][2];
         double s = lin > 0.0031308 ? 1.055 * pow(fmax(lin, 0.0), 1.0 / 2.4) - 0.055 : 12.92 * lin;
-        s = fmin(fmax(s, 0.0), 1.0);
-        q[c] = (unsigned char)(s * 255.0);
+        sv[c] = fmin(fmax(s, 0.0), 1.0);
     }
+}
+
+__device__ __forceinline__ void lab_to_rgb_u8(double L, double a, double b, unsigned char* q) {
+    double s[3];
+    lab_to_srgb(L, a, b, s);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) q[c] = (unsigned char)(s[c] * 255.0);
 }
 
 __device__ __forceinline__ void cubic_coeffs(float x, float* c) {       // cv2 interpolateCubic
@@ -246,10 +254,9 @@ __device__ __forceinline__ void linear_to_lab(const double* lin, double& L, doub
     L = 116.0 * g[1] - 16.0; a = 500.0 * (g[0] - g[1]); b = 200.0 * (g[1] - g[2]);
 }
 
-__device__ __forceinline__ double srgb8_to_linear(int q) {
-    const double v = (double)q / 255.0;
-    return v > 0.04045 ? pow((v + 0.055) / 1.055, 2.4) : v / 12.92;
-}
+__device__ __forceinline__ double srgb_to_linear(double v) { return v > 0.04045 ? pow((v + 0.055) / 1.055, 2.4) : v / 12.92; }
+
+__device__ __forceinline__ double srgb8_to_linear(int q) { return srgb_to_linear((double)q / 255.0); }
 
 __device__ __forceinline__ void rgb8_to_lab(const unsigned char* q, double& L, double& a, double& b) {
     double lin[3];
@@ -450,6 +457,75 @@ hipError_t launch_fullres_rgb(const unsigned char* src, int oh, int ow, const vo
     else
         hipLaunchKernelGGL(fullres_rgb_kernel<float>, dim3(blocks), dim3(256), 0, s, src, oh, ow, (const float*)a_plane, (const float*)b_plane,
                            H, W, interp, mask, mask_value, rgb);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// colour picker: data/lab_gamut.py, which the GUI runs on the host on every mouse press (ui/gui_draw.py:182-183,195-204).  Latency kernels of
+// at most a few hundred workgroups: one thread per grid point / per colour, the float64 conversions above.
+// ------------------------------------------------------------------------------------------------
+// abGrid.update_gamut (lab_gamut.py:66-78): blockIdx.y = map, point p = i * A + j is (a, b) = (-gamut_size + i D, -gamut_size + j D)
+__global__ __launch_bounds__(256) void gamut_map_kernel(const double* __restrict__ Lk, int gamut_size, int D, int A, unsigned char* __restrict__ pts,
+                                                        unsigned char* __restrict__ masked, unsigned char* __restrict__ mask) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= A * A) return;
+    const int i = p / A, j = p - i * A;
+    const double L = Lk[blockIdx.y], a = (double)(i * D - gamut_size), b = (double)(j * D - gamut_size);
+    unsigned char q[3];
+    lab_to_rgb_u8(L, a, b, q);
+    double bl, ba, bb;
+    rgb8_to_lab(q, bl, ba, bb);
+    const double dl = L - bl, da = a - ba, db = b - bb;
+    const bool in = sqrt(dl * dl + da * da + db * db) < 1.0;
+    const size_t o = (size_t)blockIdx.y * A * A + p;
+    if (pts != nullptr) { pts[o * 3 + 0] = q[0]; pts[o * 3 + 1] = q[1]; pts[o * 3 + 2] = q[2]; }
+    if (masked != nullptr) { masked[o * 3 + 0] = in ? q[0] : 255; masked[o * 3 + 1] = in ? q[1] : 255; masked[o * 3 + 2] = in ? q[2] : 255; }
+    if (mask != nullptr) mask[o] = in ? 1 : 0;
+}
+
+hipError_t launch_gamut_map(const double* L, int n, int gamut_size, int D, int A, unsigned char* pts, unsigned char* masked, unsigned char* mask,
+                            hipStream_t s) {
+    if (n <= 0 || n > 65535 || A <= 0 || A > 32768) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gamut_map_kernel, dim3((A * A + 255) / 256, n), dim3(256), 0, s, L, gamut_size, D, A, pts, masked, mask);
+    return hipGetLastError();
+}
+
+// snap_ab (lab_gamut.py:28-52).  As there: L is overwritten only inside a round, so the Lab that leaves the loop carries the round-tripped L;
+// old_lab aliases conv_lab, so the difference is taken against the value with L already overwritten
+__global__ __launch_bounds__(256) void snap_colors_kernel(const double* __restrict__ Lk, const unsigned char* __restrict__ rgb, int n,
+                                                          unsigned char* __restrict__ rgb_out, double* __restrict__ lab_out, int* __restrict__ iters) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    const unsigned char q[3] = {rgb[k * 3 + 0], rgb[k * 3 + 1], rgb[k * 3 + 2]};
+    const double Lin = Lk[k];
+    double L, a, b, s[3];
+    rgb8_to_lab(q, L, a, b);
+    int t = 0;
+    while (t < 20) {
+        lab_to_srgb(Lin, a, b, s);
+        const double lin[3] = {srgb_to_linear(s[0]), srgb_to_linear(s[1]), srgb_to_linear(s[2])};
+        double nl, na, nb;
+        linear_to_lab(lin, nl, na, nb);
+        const double dif = fabs(nl - Lin) + fabs(na - a) + fabs(nb - b);
+        L = nl; a = na; b = nb;
+        ++t;
+        if (dif < 1.0) break;
+    }
+    lab_to_srgb(L, a, b, s);
+    unsigned char o[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c] = (unsigned char)rint(s[c] * 255.0);      // np.round: half to even
+    if (rgb_out != nullptr) { rgb_out[k * 3 + 0] = o[0]; rgb_out[k * 3 + 1] = o[1]; rgb_out[k * 3 + 2] = o[2]; }
+    if (lab_out != nullptr) {
+        rgb8_to_lab(o, L, a, b);
+        lab_out[k * 3 + 0] = L; lab_out[k * 3 + 1] = a; lab_out[k * 3 + 2] = b;
+    }
+    if (iters != nullptr) iters[k] = t;
+}
+
+hipError_t launch_snap_colors(const double* L, const unsigned char* rgb, int n, unsigned char* rgb_out, double* lab_out, int* iters, hipStream_t s) {
+    if (n <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(snap_colors_kernel, dim3((n + 255) / 256), dim3(256), 0, s, L, rgb, n, rgb_out, lab_out, iters);
     return hipGetLastError();
 }
 

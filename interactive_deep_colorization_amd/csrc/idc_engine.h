@@ -192,6 +192,7 @@ struct idc_context {
     const unsigned char** h_src_ptrs = nullptr;                      // ... and their pinned host copy
     unsigned char* d_net_rgb = nullptr; double* d_net_lab = nullptr; // idc_set_image_rgb results [max_batch,H,W,3] u8, [max_batch,3,H,W] f64 (first use)
     unsigned char *d_full_rgb = nullptr, *h_full_rgb = nullptr; size_t full_cap = 0;   // idc_fullres_rgb result and (pageable callers) its pinned staging; bytes of each
+    unsigned char *d_pick = nullptr, *h_pick = nullptr; size_t pick_cap = 0;   // idc_gamut_map / idc_snap_colors: inputs + results of one call, device and pinned; bytes of each
     hipEvent_t ev_sync = nullptr;        // idc_stream_wait / idc_stream_signal
     // two-slot transfer pipeline (idc_forward_async / idc_wait): each slot owns its device planes
     struct PipeSlot {

@@ -257,6 +257,14 @@ hipError_t launch_ingest_rgb(const unsigned char* const* srcs, int n, int src_h,
 hipError_t launch_fullres_rgb(const unsigned char* src, int oh, int ow, const void* a_plane, const void* b_plane, int src_f64, int H, int W,
                               int interp, const float* mask, float mask_value, unsigned char* rgb, hipStream_t s);
 
+// Colour picker (data/lab_gamut.py).  gamut_map: abGrid(gamut_size, D).update_gamut(L[k]) for k < n -- grid side A, point (i, j) = (a, b) =
+// (-gamut_size + i D, -gamut_size + j D) -> pts [n,A,A,3] u8 (truncated), mask [n,A,A] u8 (1: the uint8 colour is within 1.0 of the point in
+// Lab), masked [n,A,A,3] u8 = mask ? pts : 255; each output may be nullptr.  snap_colors: snap_ab(L[k], rgb[k]) for k < n -> rgb_out [n,3] u8,
+// lab_out [n,3] f64 = rgb2lab(rgb_out), iters [n] = loop iterations run (1..20); each may be nullptr.  float64, nothing but their arguments is touched.
+hipError_t launch_gamut_map(const double* L, int n, int gamut_size, int D, int A, unsigned char* pts, unsigned char* masked, unsigned char* mask,
+                            hipStream_t s);
+hipError_t launch_snap_colors(const double* L, const unsigned char* rgb, int n, unsigned char* rgb_out, double* lab_out, int* iters, hipStream_t s);
+
 // Global statistics (global_stats.prototxt): rgb u8 [N,H,W,3] -> counts [N][313] (uint32, zeroed by the caller) of
 // the 4x4-pooled ab values' nearest centre, and sat_sum [N] (float64, zeroed) = sum of HSV saturation over pixels.
 hipError_t launch_global_stats(const unsigned char* rgb, const float* centres, unsigned* counts, double* sat_sum, int N,

@@ -538,6 +538,40 @@ class HipColorizer(object):
             raise
         return rgb
 
+    # ---- colour picker (data/lab_gamut.py): no weights needed, nothing resident is read or written ---------
+    def gamut_map(self, L, gamut_size=110, D=1, want_pts=False):
+        """``abGrid(gamut_size, D).update_gamut(L[k])`` for every L in one launch (``idc_gamut_map``).  L: a scalar or n values.
+        Returns (masked_rgb (n,A,B,3) uint8, mask (n,A,B) bool[, pts_rgb (n,A,B,3) uint8]) with A = B = ceil(2 gamut_size / D) + 1;
+        row i is a = -gamut_size + i D, column j is b."""
+        L = np.ascontiguousarray(np.atleast_1d(np.asarray(L, np.float64)).reshape(-1))
+        n, g, d = int(L.shape[0]), int(gamut_size), int(D)
+        A = -(-2 * g // d) + 1 if g >= 1 and 1 <= d <= g else 1     # (the library refuses such arguments before it writes anything)
+        masked = np.empty((n, A, A, 3), np.uint8)
+        mask = np.empty((n, A, A), np.uint8)
+        pts = np.empty((n, A, A, 3), np.uint8) if want_pts else None
+        vp = ctypes.c_void_p
+        self._chk(self.lib.idc_gamut_map(self._h, n, L.ctypes.data_as(vp), g, d, pts.ctypes.data_as(vp) if want_pts else None,
+                                         masked.ctypes.data_as(vp), mask.ctypes.data_as(vp)))
+        return (masked, mask.view(np.bool_), pts) if want_pts else (masked, mask.view(np.bool_))
+
+    def snap_colors(self, L, rgb, want_lab=False, want_iters=False):
+        """``snap_ab(L[k], rgb[k])`` for n colours in one launch (``idc_snap_colors``).  L: a scalar or (n,); rgb: (3,) or (n,3) uint8.
+        Returns rgb_out (n,3) uint8 [return_type 'rgb'], then lab_out (n,3) float64 [return_type 'lab'] and iters (n,) int32 (loop
+        rounds run, 1..20) when asked for."""
+        L = np.ascontiguousarray(np.atleast_1d(np.asarray(L, np.float64)).reshape(-1))
+        rgb = np.ascontiguousarray(np.asarray(rgb), dtype=np.uint8).reshape(-1, 3)
+        n = int(L.shape[0])
+        if rgb.shape[0] != n:
+            raise ValueError("%d L values for %d colours" % (n, rgb.shape[0]))
+        out = np.empty((n, 3), np.uint8)
+        lab = np.empty((n, 3), np.float64) if want_lab else None
+        its = np.empty((n,), np.int32) if want_iters else None
+        vp = ctypes.c_void_p
+        self._chk(self.lib.idc_snap_colors(self._h, n, L.ctypes.data_as(vp), rgb.ctypes.data_as(vp), out.ctypes.data_as(vp),
+                                           lab.ctypes.data_as(vp) if want_lab else None, its.ctypes.data_as(vp) if want_iters else None))
+        ret = (out,) + ((lab,) if want_lab else ()) + ((its,) if want_iters else ())
+        return ret[0] if len(ret) == 1 else ret
+
     def set_hints(self, hints, mode="ab", img=0, mask_value=1.0):
         """Rasterise a hint list on the device.  hints: rows (y0, x0, y1, x1, c0, c1[, c2]) -- inclusive rectangle and
         its (a, b) [mode 'ab', the notebook's put_point] or uint8 (r, g, b) [mode 'rgb', UIControl.get_input +
