@@ -26,67 +26,33 @@ int fail(std::string* err, int code, const char* fmt, ...) {
     return code;
 }
 
+// diagnostic (IDC_KW_STAMPS=1): where a layer of the last chain launch spent its cycles (mean over workgroups)
+static void print_kw_stamps(const idc_context* c) {
+    if (!c->d_kw_stamps.get() || c->kw_stamp_blocks <= 0) return;
+    std::vector<long long> st((size_t)c->kw_stamp_blocks * kKwChainMax * 8);
+    if (hipMemcpy(st.data(), c->d_kw_stamps.get(), st.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return;
+    static const char* names[] = {"prefetch+barrier wait", "halo issue", "halo landed", "taps", "reduce+epilogue", "stores acked+wg barrier"};
+    static const int seq[] = {0, 1, 6, 2, 3, 4, 5};
+    for (int li = 0; li < c->kw_stamp_layers; ++li) {
+        double d[6] = {0, 0, 0, 0, 0, 0};
+        for (int b = 0; b < c->kw_stamp_blocks; ++b) {
+            const long long* p = &st[((size_t)b * kKwChainMax + li) * 8];
+            for (int k = 0; k < 6; ++k) {
+                if (li + 1 == c->kw_stamp_layers && k == 5) continue;
+                d[k] += (double)(p[seq[k + 1]] - p[seq[k]]);
+            }
+        }
+        fprintf(stderr, "kw_chain stamps layer %2d:", li);
+        for (int k = 0; k < 6; ++k) fprintf(stderr, " %s %.0f |", names[k], d[k] / c->kw_stamp_blocks);
+        fprintf(stderr, "\n");
+    }
+}
+
 static void destroy_ctx(idc_context* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->d_arena) (void)hipFree(c->d_arena);
-    else for (auto& t : c->tensors) if (t.ptr) (void)hipFree(t.ptr);
-    for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
-    if (c->own_blob && c->d_blob) (void)hipFree(c->d_blob);
-    for (auto& sl : c->pipe) {
-        void* dv[] = {sl.d_L, sl.d_ab, sl.d_mask, sl.d_out};
-        for (void* p : dv) if (p) (void)hipFree(p);
-        if (sl.h_in) (void)hipHostFree(sl.h_in);
-        if (sl.h_out) (void)hipHostFree(sl.h_out);
-        hipEvent_t evs[] = {sl.ev_in, sl.ev_comp, sl.ev_out, sl.ev_in0, sl.ev_comp0, sl.ev_out0};
-        for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
-    }
-    if (c->ev_pipe_base) (void)hipEventDestroy(c->ev_pipe_base);
-    if (c->s_in) (void)hipStreamDestroy(c->s_in);
-    if (c->s_out) (void)hipStreamDestroy(c->s_out);
-    if (c->ev_sync) (void)hipEventDestroy(c->ev_sync);
-    if (c->d_zeros) (void)hipFree(c->d_zeros);
-    if (c->d_audit) (void)hipFree(c->d_audit);
-    if (c->d_kw_stamps && c->kw_stamp_blocks > 0) {      // diagnostic: where a layer of the last chain launch spent its cycles (mean over workgroups)
-        std::vector<long long> st((size_t)c->kw_stamp_blocks * kKwChainMax * 8);
-        if (hipMemcpy(st.data(), c->d_kw_stamps, st.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
-            static const char* names[] = {"prefetch+barrier wait", "halo issue", "halo landed", "taps", "reduce+epilogue", "stores acked+wg barrier"};
-            static const int seq[] = {0, 1, 6, 2, 3, 4, 5};
-            for (int li = 0; li < c->kw_stamp_layers; ++li) {
-                double d[6] = {0, 0, 0, 0, 0, 0};
-                for (int b = 0; b < c->kw_stamp_blocks; ++b) {
-                    const long long* p = &st[((size_t)b * kKwChainMax + li) * 8];
-                    for (int k = 0; k < 6; ++k) {
-                        if (li + 1 == c->kw_stamp_layers && k == 5) continue;
-                        d[k] += (double)(p[seq[k + 1]] - p[seq[k]]);
-                    }
-                }
-                fprintf(stderr, "kw_chain stamps layer %2d:", li);
-                for (int k = 0; k < 6; ++k) fprintf(stderr, " %s %.0f |", names[k], d[k] / c->kw_stamp_blocks);
-                fprintf(stderr, "\n");
-            }
-        }
-        (void)hipFree(c->d_kw_stamps);
-    }
-    if (c->d_kw_bar) (void)hipFree(c->d_kw_bar);
-    if (c->h_kw_abort) (void)hipHostFree(c->h_kw_abort);
-    if (c->d_up_rgb) (void)hipFree(c->d_up_rgb);
-    if (c->d_up_L) (void)hipFree(c->d_up_L);
-    if (c->h_up_rgb) (void)hipHostFree(c->h_up_rgb);
-    if (c->h_up_L) (void)hipHostFree(c->h_up_L);
-    for (auto& sl : c->src) if (sl.d_rgb) (void)hipFree(sl.d_rgb);
-    void* ing[] = {c->d_ingest, (void*)c->d_src_ptrs, c->d_net_rgb, c->d_net_lab, c->d_full_rgb};
-    for (void* p : ing) if (p) (void)hipFree(p);
-    if (c->h_src_ptrs) (void)hipHostFree((void*)c->h_src_ptrs);
-    if (c->h_full_rgb) (void)hipHostFree(c->h_full_rgb);
-    if (c->d_pick) (void)hipFree(c->d_pick);
-    if (c->h_pick) (void)hipHostFree(c->h_pick);
-    void* dev[] = {c->d_L, c->d_ab, c->d_mask, c->d_out, c->d_dist, c->d_scratch, c->d_glob_in, c->d_glob_vec, c->d_pred_ab, c->d_dist313, c->d_partial, c->d_rgb, c->d_labq, c->d_hints, c->d_centres, c->d_sugg, c->d_sugg_counts, c->d_post_in, c->d_map_ab, c->d_map_s};
-    for (void* p : dev) if (p) (void)hipFree(p);
-    void* host[] = {c->h_in, c->h_out, c->h_dist, c->h_pred_ab, c->h_rgb, c->h_labq, c->h_hints};
-    for (void* p : host) if (p) (void)hipHostFree(p);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
+    if (c->stream.get()) (void)hipStreamSynchronize(c->stream.get());
+    print_kw_stamps(c);
     delete c;
 }
 
@@ -103,13 +69,12 @@ int check_device(int device_id, std::string* err) {
 }
 
 int ensure_post_buffers(idc_context* h) {
-    if (h->d_rgb) return IDC_OK;
     const size_t hw = (size_t)h->H * h->W, nb = (size_t)h->max_batch;
-    HIPCHK(h, hipMalloc((void**)&h->d_rgb, nb * hw * 3));
-    HIPCHK(h, hipMalloc((void**)&h->d_labq, nb * hw * 3 * 8));
-    HIPCHK(h, hipMalloc((void**)&h->d_post_in, nb * hw * 3 * 4));
-    HIPCHK(h, hipHostMalloc((void**)&h->h_rgb, nb * hw * 3, hipHostMallocDefault));
-    HIPCHK(h, hipHostMalloc((void**)&h->h_labq, nb * hw * 3 * 8, hipHostMallocDefault));
+    HIPCHK(h, h->d_rgb.ensure(nb * hw * 3));
+    HIPCHK(h, h->d_labq.ensure(nb * hw * 3 * 8));
+    HIPCHK(h, h->d_post_in.ensure(nb * hw * 3 * 4));
+    HIPCHK(h, h->h_rgb.ensure(nb * hw * 3));
+    HIPCHK(h, h->h_labq.ensure(nb * hw * 3 * 8));
     return IDC_OK;
 }
 
@@ -118,22 +83,23 @@ int run_lab_post(idc_context* h, int n, const float* d_Lp, float l_add, const fl
     const size_t hw = (size_t)h->H * h->W;
     int rc = ensure_post_buffers(h);
     if (rc) return rc;
-    HIPCHK(h, launch_lab_post(d_Lp, l_add, d_abp, h->d_rgb, lab_q ? h->d_labq : nullptr, n, h->H, h->W, h->stream));
+    HIPCHK(h, launch_lab_post(d_Lp, l_add, d_abp, h->d_rgb.get(), lab_q ? h->d_labq.get() : nullptr, n, h->H, h->W, h->stream.get()));
     const bool rgb_direct = is_pinned(rgb), lab_direct = lab_q && is_pinned(lab_q);      // pinned caller buffers: no staging copy
-    HIPCHK(h, copy_h2d_or_d2h(h, h->d_rgb, rgb_direct ? (void*)rgb : (void*)h->h_rgb, (size_t)n * hw * 3, false));
-    if (lab_q) HIPCHK(h, copy_h2d_or_d2h(h, h->d_labq, lab_direct ? (void*)lab_q : (void*)h->h_labq, (size_t)n * hw * 3 * 8, false));
+    HIPCHK(h, copy_h2d_or_d2h(h, h->d_rgb.get(), rgb_direct ? (void*)rgb : (void*)h->h_rgb.get(), (size_t)n * hw * 3, false));
+    if (lab_q) HIPCHK(h, copy_h2d_or_d2h(h, h->d_labq.get(), lab_direct ? (void*)lab_q : (void*)h->h_labq.get(), (size_t)n * hw * 3 * 8, false));
     HIPCHK(h, wait_stream(h, n));
     rc = check_chain_abort(h);
     if (rc) return rc;
-    if (!rgb_direct) memcpy(rgb, h->h_rgb, (size_t)n * hw * 3);
-    if (lab_q && !lab_direct) memcpy(lab_q, h->h_labq, (size_t)n * hw * 3 * 8);
+    if (!rgb_direct) memcpy(rgb, h->h_rgb.get(), (size_t)n * hw * 3);
+    if (lab_q && !lab_direct) memcpy(lab_q, h->h_labq.get(), (size_t)n * hw * 3 * 8);
     return IDC_OK;
 }
 
 void drop_source(idc_context* h, int slot) {
-    if (slot < 0 || slot >= (int)h->src.size() || !h->src[slot].d_rgb) return;
-    (void)hipFree(h->src[slot].d_rgb);                   // (waits for the device: nothing that reads it is in flight after that)
-    h->src[slot] = idc_context::SlotSource();
+    if (slot < 0 || slot >= (int)h->src.size()) return;
+    auto& sl = h->src[slot];
+    sl.d_rgb.reset();                                    // (freeing waits for the device: nothing that reads it is in flight after that)
+    sl.h = sl.w = 0;
 }
 
 }  // namespace idc
@@ -163,7 +129,7 @@ int idc_create(int device_id, int height, int width, int max_batch, int precisio
     idc_context* c = new idc_context();
     c->device = device_id; c->H = height; c->W = width; c->max_batch = max_batch; c->precision = precision; c->flags = flags;
     c->plan = make_blob_plan(precision, flags);
-    hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+    hipError_t e = c->stream.create(hipStreamNonBlocking);
     if (e == hipSuccess) e = init_kernels();
     if (e != hipSuccess) {
         rc = fail(nullptr, IDC_ERR_HIP, "stream/kernel init failed: %s", hipGetErrorString(e));
@@ -201,8 +167,8 @@ int idc_set_global_hints(idc_handle h, int n, const float* glob_ab_313_mask, con
         memcpy(&host[(size_t)i * kGlobIn], glob_ab_313_mask + (size_t)i * 314, 314 * 4);
         if (s_avg_mask) memcpy(&host[(size_t)i * kGlobIn + 314], s_avg_mask + (size_t)i * 2, 2 * 4);
     }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(h->d_glob_in, host.data(), host.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+    HIPCHK(h, hipMemcpy(h->d_glob_in.get(), host.data(), host.size() * 4, hipMemcpyHostToDevice));
     return IDC_OK;
 }
 
@@ -210,8 +176,8 @@ int idc_clear_global_hints(idc_handle h) {
     if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
     if (!(h->flags & IDC_FLAG_GLOBAL_HINTS)) return fail(&h->err, IDC_ERR_UNSUPPORTED, "handle was created without IDC_FLAG_GLOBAL_HINTS");
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemset(h->d_glob_in, 0, (size_t)h->max_batch * kGlobIn * 4));
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+    HIPCHK(h, hipMemset(h->d_glob_in.get(), 0, (size_t)h->max_batch * kGlobIn * 4));
     return IDC_OK;
 }
 
@@ -230,10 +196,10 @@ int idc_lab2rgb(idc_handle h, int n, const float* L, const float* ab, uint8_t* r
     int rc = ensure_post_buffers(h);
     if (rc) return rc;
     const size_t hw = (size_t)h->H * h->W;
-    memcpy(h->h_in, L, (size_t)n * hw * 4);
-    memcpy(h->h_in + (size_t)n * hw, ab, (size_t)n * hw * 2 * 4);
-    HIPCHK(h, hipMemcpyAsync(h->d_post_in, h->h_in, (size_t)n * hw * 3 * 4, hipMemcpyHostToDevice, h->stream));
-    rc = run_lab_post(h, n, h->d_post_in, 0.f, h->d_post_in + (size_t)n * hw, rgb, lab_q);
+    memcpy(h->h_in.get(), L, (size_t)n * hw * 4);
+    memcpy(h->h_in.get() + (size_t)n * hw, ab, (size_t)n * hw * 2 * 4);
+    HIPCHK(h, hipMemcpyAsync(h->d_post_in.get(), h->h_in.get(), (size_t)n * hw * 3 * 4, hipMemcpyHostToDevice, h->stream.get()));
+    rc = run_lab_post(h, n, h->d_post_in.get(), 0.f, h->d_post_in.get() + (size_t)n * hw, rgb, lab_q);
     h->labq_resident = rc == IDC_OK && lab_q != nullptr;        // d_labq = rgb2lab of exactly what was passed in
     if (h->labq_resident && h->last_n < n) h->last_n = n;
     return rc;
@@ -252,8 +218,8 @@ int idc_set_image_l(idc_handle h, int img, const float* L_mc) {
     if (!L_mc) return fail(&h->err, IDC_ERR_INVALID_ARG, "null L_mc");
     HIPCHK(h, hipSetDevice(h->device));
     const size_t hw = (size_t)h->H * h->W;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(h->d_L + (size_t)img * hw, L_mc, hw * 4, hipMemcpyHostToDevice));
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+    HIPCHK(h, hipMemcpy(h->d_L.get() + (size_t)img * hw, L_mc, hw * 4, hipMemcpyHostToDevice));
     h->l_set[img] = 1;
     drop_source(h, img);
     return IDC_OK;
@@ -265,15 +231,11 @@ int idc_set_hints(idc_handle h, int img, int n_hints, const idc_hint* hints, int
     if (n_hints < 0 || (n_hints > 0 && !hints)) return fail(&h->err, IDC_ERR_INVALID_ARG, "bad hint list");
     if (mode != IDC_HINT_AB && mode != IDC_HINT_RGB) return fail(&h->err, IDC_ERR_INVALID_ARG, "hint mode %d", mode);
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));            // the pinned list of the previous call may still be in flight
-    if (n_hints > h->hints_cap) {
-        const int cap = n_hints < 256 ? 256 : 2 * n_hints;
-        if (h->d_hints) (void)hipFree(h->d_hints);
-        if (h->h_hints) (void)hipHostFree(h->h_hints);
-        h->d_hints = nullptr; h->h_hints = nullptr; h->hints_cap = 0;
-        HIPCHK(h, hipMalloc((void**)&h->d_hints, (size_t)cap * sizeof(HintRect)));
-        HIPCHK(h, hipHostMalloc((void**)&h->h_hints, (size_t)cap * sizeof(HintRect), hipHostMallocDefault));
-        h->hints_cap = cap;
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));            // the pinned list of the previous call may still be in flight
+    {   // 256 entries to begin with, twice the list once it is longer
+        const size_t cap = n_hints < 256 ? 256 : 2 * (size_t)n_hints;
+        HIPCHK(h, h->d_hints.ensure((size_t)n_hints * sizeof(HintRect), cap * sizeof(HintRect)));
+        HIPCHK(h, h->h_hints.ensure((size_t)n_hints * sizeof(HintRect), cap * sizeof(HintRect)));
     }
     int kept = 0;
     for (int i = 0; i < n_hints; ++i) {                    // cv2.rectangle: corners in either order, inclusive, clipped
@@ -289,12 +251,12 @@ int idc_set_hints(idc_handle h, int img, int n_hints, const idc_hint* hints, int
         if (mode == IDC_HINT_RGB)
             if (!(r.c0 >= 0.f && r.c0 <= 255.f && r.c1 >= 0.f && r.c1 <= 255.f && r.c2 >= 0.f && r.c2 <= 255.f))
                 return fail(&h->err, IDC_ERR_INVALID_ARG, "hint %d: RGB outside 0..255", i);
-        h->h_hints[kept++] = r;
+        h->h_hints.get()[kept++] = r;
     }
     const size_t hw = (size_t)h->H * h->W;
-    if (kept) HIPCHK(h, hipMemcpyAsync(h->d_hints, h->h_hints, (size_t)kept * sizeof(HintRect), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, launch_raster_hints(h->d_hints, kept, mode, mask_value, h->d_ab + (size_t)img * hw * 2, h->d_mask + (size_t)img * hw,
-                                  h->H, h->W, h->stream));
+    if (kept) HIPCHK(h, hipMemcpyAsync(h->d_hints.get(), h->h_hints.get(), (size_t)kept * sizeof(HintRect), hipMemcpyHostToDevice, h->stream.get()));
+    HIPCHK(h, launch_raster_hints(h->d_hints.get(), kept, mode, mask_value, h->d_ab.get() + (size_t)img * hw * 2, h->d_mask.get() + (size_t)img * hw,
+                                  h->H, h->W, h->stream.get()));
     h->hint_mask_value[img] = mask_value;
     return IDC_OK;
 }
@@ -304,9 +266,9 @@ int idc_get_hint_planes(idc_handle h, int img, float* ab, float* mask) {
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     const size_t hw = (size_t)h->H * h->W;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (ab) HIPCHK(h, hipMemcpy(ab, h->d_ab + (size_t)img * hw * 2, hw * 2 * 4, hipMemcpyDeviceToHost));
-    if (mask) HIPCHK(h, hipMemcpy(mask, h->d_mask + (size_t)img * hw, hw * 4, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+    if (ab) HIPCHK(h, hipMemcpy(ab, h->d_ab.get() + (size_t)img * hw * 2, hw * 2 * 4, hipMemcpyDeviceToHost));
+    if (mask) HIPCHK(h, hipMemcpy(mask, h->d_mask.get() + (size_t)img * hw, hw * 4, hipMemcpyDeviceToHost));
     return IDC_OK;
 }
 
@@ -319,19 +281,19 @@ int idc_forward_resident(idc_handle h, int n, float maskcent, float l_cent, floa
     rc = drain_pipeline(h);
     if (rc) return rc;
     const size_t hw = (size_t)h->H * h->W;
-    rc = run_graph(h, n, h->d_L, h->d_ab, h->d_mask, maskcent, h->d_out, (h->flags & IDC_FLAG_DIST_HEAD) ? h->d_dist : nullptr);
+    rc = run_graph(h, n, h->d_L.get(), h->d_ab.get(), h->d_mask.get(), maskcent, h->d_out.get(), (h->flags & IDC_FLAG_DIST_HEAD) ? h->d_dist.get() : nullptr);
     if (rc) return rc;
     h->out_resident = true; h->labq_resident = rgb != nullptr && lab_q != nullptr;
-    if (out_ab) HIPCHK(h, hipMemcpyAsync(h->h_out, h->d_out, (size_t)n * hw * 2 * 4, hipMemcpyDeviceToHost, h->stream));
+    if (out_ab) HIPCHK(h, hipMemcpyAsync(h->h_out.get(), h->d_out.get(), (size_t)n * hw * 2 * 4, hipMemcpyDeviceToHost, h->stream.get()));
     if (rgb) {
-        rc = run_lab_post(h, n, h->d_L, l_cent, h->d_out, rgb, lab_q);      // synchronises the stream
+        rc = run_lab_post(h, n, h->d_L.get(), l_cent, h->d_out.get(), rgb, lab_q);      // synchronises the stream
         if (rc) return rc;
     } else {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream.get()));
     }
     rc = check_chain_abort(h);
     if (rc) return rc;
-    if (out_ab) memcpy(out_ab, h->h_out, (size_t)n * hw * 2 * 4);
+    if (out_ab) memcpy(out_ab, h->h_out.get(), (size_t)n * hw * 2 * 4);
     return IDC_OK;
 }
 
@@ -351,11 +313,11 @@ static int dist_locate(idc_context* h, int img, int y, int x, int* B, long long*
     if (y < 0 || y >= h->H || x < 0 || x >= h->W) return fail(&h->err, IDC_ERR_INVALID_ARG, "pixel (%d,%d) outside the image", y, x);
     if (h->flags & IDC_FLAG_DIST313) {
         *B = 313; *stride = (long long)h->H * h->W;
-        *p = h->d_dist313 + (size_t)img * 313 * (*stride) + (size_t)y * h->W + x;
+        *p = h->d_dist313.get() + (size_t)img * 313 * (*stride) + (size_t)y * h->W + x;
     } else {                                               // 529 bins at H/4 x W/4; out_cl is its nearest x4 upsample (model.py:131)
         const int h4 = h->H / 4, w4 = h->W / 4;
         *B = 529; *stride = (long long)h4 * w4;
-        *p = h->d_dist + (size_t)img * 529 * (*stride) + (size_t)(y / 4) * w4 + (x / 4);
+        *p = h->d_dist.get() + (size_t)img * 529 * (*stride) + (size_t)(y / 4) * w4 + (x / 4);
     }
     return IDC_OK;
 }
@@ -368,7 +330,7 @@ int idc_dist_at(idc_handle h, int img, int y, int x, float* pdf) {
     if (rc) return rc;
     if (!pdf) return fail(&h->err, IDC_ERR_INVALID_ARG, "null pdf");
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
     HIPCHK(h, hipMemcpy2D(pdf, 4, p, (size_t)stride * 4, 4, (size_t)B, hipMemcpyDeviceToHost));
     return IDC_OK;
 }
@@ -380,18 +342,17 @@ int idc_get_dist(idc_handle h, int n, float* dist) {
     if (!dist) return fail(&h->err, IDC_ERR_INVALID_ARG, "null dist");
     HIPCHK(h, hipSetDevice(h->device));
     const size_t hw = (size_t)h->H * h->W;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->flags & IDC_FLAG_DIST313) HIPCHK(h, hipMemcpy(dist, h->d_dist313, (size_t)n * 313 * hw * 4, hipMemcpyDeviceToHost));
-    else HIPCHK(h, hipMemcpy(dist, h->d_dist, (size_t)n * 529 * (hw / 16) * 4, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+    if (h->flags & IDC_FLAG_DIST313) HIPCHK(h, hipMemcpy(dist, h->d_dist313.get(), (size_t)n * 313 * hw * 4, hipMemcpyDeviceToHost));
+    else HIPCHK(h, hipMemcpy(dist, h->d_dist.get(), (size_t)n * 529 * (hw / 16) * 4, hipMemcpyDeviceToHost));
     return IDC_OK;
 }
 
 // device copy of the caller's bin centres (idc_suggest_colors, idc_dist_decode) and the suggestion results: first use
 static int ensure_centres(idc_context* h) {
-    if (h->d_centres) return IDC_OK;
-    HIPCHK(h, hipMalloc((void**)&h->d_centres, (size_t)kSuggestMaxBins * 2 * 4));
-    HIPCHK(h, hipMalloc((void**)&h->d_sugg, (size_t)kSuggestMaxK * 3 * 8));
-    HIPCHK(h, hipMalloc((void**)&h->d_sugg_counts, (size_t)kSuggestMaxBins * 4));
+    HIPCHK(h, h->d_centres.ensure((size_t)kSuggestMaxBins * 2 * 4));
+    HIPCHK(h, h->d_sugg.ensure((size_t)kSuggestMaxK * 3 * 8));
+    HIPCHK(h, h->d_sugg_counts.ensure((size_t)kSuggestMaxBins * 4));
     return IDC_OK;
 }
 
@@ -406,13 +367,13 @@ int idc_suggest_colors(idc_handle h, int img, int y, int x, int K, int N, unsign
     HIPCHK(h, hipSetDevice(h->device));
     rc = ensure_centres(h);
     if (rc) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(h->d_centres, centres, (size_t)B * 2 * 4, hipMemcpyHostToDevice));
-    HIPCHK(h, launch_suggest(p, stride, B, h->d_centres, K, N, seed, h->d_sugg, h->d_sugg + 2 * kSuggestMaxK, h->d_sugg_counts, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(out_centres, h->d_sugg, (size_t)K * 2 * 8, hipMemcpyDeviceToHost));
-    HIPCHK(h, hipMemcpy(out_conf, h->d_sugg + 2 * kSuggestMaxK, (size_t)K * 8, hipMemcpyDeviceToHost));
-    if (out_counts) HIPCHK(h, hipMemcpy(out_counts, h->d_sugg_counts, (size_t)B * 4, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+    HIPCHK(h, hipMemcpy(h->d_centres.get(), centres, (size_t)B * 2 * 4, hipMemcpyHostToDevice));
+    HIPCHK(h, launch_suggest(p, stride, B, h->d_centres.get(), K, N, seed, h->d_sugg.get(), h->d_sugg.get() + 2 * kSuggestMaxK, h->d_sugg_counts.get(), h->stream.get()));
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+    HIPCHK(h, hipMemcpy(out_centres, h->d_sugg.get(), (size_t)K * 2 * 8, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(out_conf, h->d_sugg.get() + 2 * kSuggestMaxK, (size_t)K * 8, hipMemcpyDeviceToHost));
+    if (out_counts) HIPCHK(h, hipMemcpy(out_counts, h->d_sugg_counts.get(), (size_t)B * 4, hipMemcpyDeviceToHost));
     return IDC_OK;
 }
 
@@ -424,12 +385,10 @@ static int dist_maps_begin(idc_context* h, int n, int* B, int* npix, const float
     const bool d313 = (h->flags & IDC_FLAG_DIST313) != 0;
     *B = d313 ? 313 : 529;
     *npix = d313 ? h->H * h->W : (h->H / 4) * (h->W / 4);
-    *dist = d313 ? h->d_dist313 : h->d_dist;
+    *dist = d313 ? h->d_dist313.get() : h->d_dist.get();
     HIPCHK(h, hipSetDevice(h->device));
-    if (!h->d_map_ab) {
-        HIPCHK(h, hipMalloc((void**)&h->d_map_ab, (size_t)h->max_batch * 2 * (*npix) * 4));
-        HIPCHK(h, hipMalloc((void**)&h->d_map_s, (size_t)h->max_batch * (*npix) * 4));
-    }
+    HIPCHK(h, h->d_map_ab.ensure((size_t)h->max_batch * 2 * (*npix) * 4));
+    HIPCHK(h, h->d_map_s.ensure((size_t)h->max_batch * (*npix) * 4));
     return IDC_OK;
 }
 
@@ -438,10 +397,10 @@ int idc_dist_entropy(idc_handle h, int n, float* ent) {
     int rc = dist_maps_begin(h, n, &B, &npix, &dist);
     if (rc) return rc;
     if (!ent) return fail(&h->err, IDC_ERR_INVALID_ARG, "null ent");
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, launch_dist_entropy(dist, n, B, npix, h->d_map_s, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(ent, h->d_map_s, (size_t)n * npix * 4, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+    HIPCHK(h, launch_dist_entropy(dist, n, B, npix, h->d_map_s.get(), h->stream.get()));
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+    HIPCHK(h, hipMemcpy(ent, h->d_map_s.get(), (size_t)n * npix * 4, hipMemcpyDeviceToHost));
     return IDC_OK;
 }
 
@@ -454,12 +413,12 @@ int idc_dist_decode(idc_handle h, int n, int mode, float gamma, const float* cen
     if (!std::isfinite(gamma) || gamma <= 0.f) return fail(&h->err, IDC_ERR_INVALID_ARG, "gamma must be positive and finite");
     rc = ensure_centres(h);
     if (rc) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(h->d_centres, centres, (size_t)B * 2 * 4, hipMemcpyHostToDevice));
-    HIPCHK(h, launch_dist_decode(dist, n, B, npix, mode, gamma, h->d_centres, h->d_map_ab, conf ? h->d_map_s : nullptr, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(ab, h->d_map_ab, (size_t)n * 2 * npix * 4, hipMemcpyDeviceToHost));
-    if (conf) HIPCHK(h, hipMemcpy(conf, h->d_map_s, (size_t)n * npix * 4, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+    HIPCHK(h, hipMemcpy(h->d_centres.get(), centres, (size_t)B * 2 * 4, hipMemcpyHostToDevice));
+    HIPCHK(h, launch_dist_decode(dist, n, B, npix, mode, gamma, h->d_centres.get(), h->d_map_ab.get(), conf ? h->d_map_s.get() : nullptr, h->stream.get()));
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+    HIPCHK(h, hipMemcpy(ab, h->d_map_ab.get(), (size_t)n * 2 * npix * 4, hipMemcpyDeviceToHost));
+    if (conf) HIPCHK(h, hipMemcpy(conf, h->d_map_s.get(), (size_t)n * npix * 4, hipMemcpyDeviceToHost));
     return IDC_OK;
 }
 
@@ -471,19 +430,19 @@ int idc_global_histogram(idc_handle h, int n, const uint8_t* rgb, const float* c
     int rc = ensure_post_buffers(h);                      // d_rgb doubles as the upload buffer of the reference image
     if (rc) return rc;
     const size_t hw = (size_t)h->H * h->W;
-    DevBuf d_c, d_counts, d_sat;
-    HIPCHK(h, d_c.alloc(626 * 4)); HIPCHK(h, d_counts.alloc((size_t)n * 313 * 4)); HIPCHK(h, d_sat.alloc((size_t)n * 8));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(h->d_rgb, rgb, (size_t)n * hw * 3, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_c.p, centres, 626 * 4, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemset(d_counts.p, 0, (size_t)n * 313 * 4));
-    HIPCHK(h, hipMemset(d_sat.p, 0, (size_t)n * 8));
-    HIPCHK(h, launch_global_stats(h->d_rgb, (const float*)d_c.p, (unsigned*)d_counts.p, (double*)d_sat.p, n, h->H, h->W, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    DevMem<float> d_c; DevMem<unsigned> d_counts; DevMem<double> d_sat;
+    HIPCHK(h, d_c.ensure(626 * 4)); HIPCHK(h, d_counts.ensure((size_t)n * 313 * 4)); HIPCHK(h, d_sat.ensure((size_t)n * 8));
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+    HIPCHK(h, hipMemcpy(h->d_rgb.get(), rgb, (size_t)n * hw * 3, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d_c.get(), centres, 626 * 4, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemset(d_counts.get(), 0, (size_t)n * 313 * 4));
+    HIPCHK(h, hipMemset(d_sat.get(), 0, (size_t)n * 8));
+    HIPCHK(h, launch_global_stats(h->d_rgb.get(), d_c.get(), d_counts.get(), d_sat.get(), n, h->H, h->W, h->stream.get()));
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
     std::vector<unsigned> cnt((size_t)n * 313);
     std::vector<double> sat(n);
-    HIPCHK(h, hipMemcpy(cnt.data(), d_counts.p, cnt.size() * 4, hipMemcpyDeviceToHost));
-    HIPCHK(h, hipMemcpy(sat.data(), d_sat.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(cnt.data(), d_counts.get(), cnt.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(sat.data(), d_sat.get(), (size_t)n * 8, hipMemcpyDeviceToHost));
     const double nblk = (double)(h->H / 4) * (h->W / 4);
     for (int i = 0; i < n; ++i) {
         for (int k = 0; k < 313; ++k) hist[(size_t)i * 313 + k] = (float)(cnt[(size_t)i * 313 + k] / nblk);
@@ -499,16 +458,16 @@ int idc_global_histogram(idc_handle h, int n, const uint8_t* rgb, const float* c
 int idc_stream_wait(idc_handle h, void* caller_stream) {
     if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipEventRecord(h->ev_sync, (hipStream_t)caller_stream));
-    HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_sync, 0));
+    HIPCHK(h, hipEventRecord(h->ev_sync.get(), (hipStream_t)caller_stream));
+    HIPCHK(h, hipStreamWaitEvent(h->stream.get(), h->ev_sync.get(), 0));
     return IDC_OK;
 }
 
 int idc_stream_signal(idc_handle h, void* caller_stream) {
     if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipEventRecord(h->ev_sync, h->stream));
-    HIPCHK(h, hipStreamWaitEvent((hipStream_t)caller_stream, h->ev_sync, 0));
+    HIPCHK(h, hipEventRecord(h->ev_sync.get(), h->stream.get()));
+    HIPCHK(h, hipStreamWaitEvent((hipStream_t)caller_stream, h->ev_sync.get(), 0));
     return IDC_OK;
 }
 
@@ -519,12 +478,12 @@ static int resident_ab_planes(idc_context* h, int img, int source, const void** 
     *f64 = 0;
     if (source == IDC_SRC_OUTPUT_AB) {
         if (!h->labq_resident || img >= h->last_n) return fail(&h->err, IDC_ERR_UNSUPPORTED, "no refreshed output_ab is resident (run idc_forward_rgb / idc_forward_resident with lab_q first)");
-        *pa = h->d_labq + ((size_t)img * 3 + 1) * hw; *pb = h->d_labq + ((size_t)img * 3 + 2) * hw; *f64 = 1;
+        *pa = h->d_labq.get() + ((size_t)img * 3 + 1) * hw; *pb = h->d_labq.get() + ((size_t)img * 3 + 2) * hw; *f64 = 1;
     } else if (source == IDC_SRC_OUTPUT_AB_RAW) {
         if (!h->out_resident || img >= h->last_n) return fail(&h->err, IDC_ERR_UNSUPPORTED, "no forward result is resident");
-        *pa = h->d_out + (size_t)img * 2 * hw; *pb = h->d_out + ((size_t)img * 2 + 1) * hw;
+        *pa = h->d_out.get() + (size_t)img * 2 * hw; *pb = h->d_out.get() + ((size_t)img * 2 + 1) * hw;
     } else if (source == IDC_SRC_INPUT_AB) {
-        *pa = h->d_ab + (size_t)img * 2 * hw; *pb = h->d_ab + ((size_t)img * 2 + 1) * hw;
+        *pa = h->d_ab.get() + (size_t)img * 2 * hw; *pb = h->d_ab.get() + ((size_t)img * 2 + 1) * hw;
     } else {
         return fail(&h->err, IDC_ERR_INVALID_ARG, "source %d not in 0..2", source);
     }
@@ -543,36 +502,28 @@ int idc_upsample_lab2rgb(idc_handle h, int img, int source, int interp, int out_
     rc = drain_pipeline(h);
     if (rc) return rc;
     const size_t np = (size_t)out_h * out_w;
-    if (h->up_cap < np) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (h->d_up_rgb) (void)hipFree(h->d_up_rgb);
-        if (h->d_up_L) (void)hipFree(h->d_up_L);
-        if (h->h_up_rgb) (void)hipHostFree(h->h_up_rgb);
-        if (h->h_up_L) (void)hipHostFree(h->h_up_L);
-        h->d_up_rgb = nullptr; h->d_up_L = nullptr; h->h_up_rgb = nullptr; h->h_up_L = nullptr; h->up_cap = 0;
-        HIPCHK(h, hipMalloc((void**)&h->d_up_rgb, np * 3));
-        HIPCHK(h, hipMalloc((void**)&h->d_up_L, np * 8));
-        HIPCHK(h, hipHostMalloc((void**)&h->h_up_rgb, np * 3, hipHostMallocDefault));
-        HIPCHK(h, hipHostMalloc((void**)&h->h_up_L, np * 8, hipHostMallocDefault));
-        h->up_cap = np;
-    }
-    memcpy(h->h_up_L, L, np * 8);
-    HIPCHK(h, hipMemcpyAsync(h->d_up_L, h->h_up_L, np * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, launch_upsample_lab2rgb(pa, pb, f64, h->H, h->W, interp, (const double*)h->d_up_L, out_h, out_w, h->d_up_rgb, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->h_up_rgb, h->d_up_rgb, np * 3, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    memcpy(rgb, h->h_up_rgb, np * 3);
+    if (h->d_up_rgb.bytes() < np * 3 || h->d_up_L.bytes() < np * 8 || h->h_up_rgb.bytes() < np * 3 || h->h_up_L.bytes() < np * 8)
+        HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+    HIPCHK(h, h->d_up_rgb.ensure(np * 3));
+    HIPCHK(h, h->d_up_L.ensure(np * 8));
+    HIPCHK(h, h->h_up_rgb.ensure(np * 3));
+    HIPCHK(h, h->h_up_L.ensure(np * 8));
+    memcpy(h->h_up_L.get(), L, np * 8);
+    HIPCHK(h, hipMemcpyAsync(h->d_up_L.get(), h->h_up_L.get(), np * 8, hipMemcpyHostToDevice, h->stream.get()));
+    HIPCHK(h, launch_upsample_lab2rgb(pa, pb, f64, h->H, h->W, interp, (const double*)h->d_up_L.get(), out_h, out_w, h->d_up_rgb.get(), h->stream.get()));
+    HIPCHK(h, hipMemcpyAsync(h->h_up_rgb.get(), h->d_up_rgb.get(), np * 3, hipMemcpyDeviceToHost, h->stream.get()));
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+    memcpy(rgb, h->h_up_rgb.get(), np * 3);
     return IDC_OK;
 }
 
 // ---------------------------------------------------------------------------------------------- image ingestion
 static int ensure_ingest_buffers(idc_context* h) {
-    if (h->d_net_rgb) return IDC_OK;
     const size_t hw = (size_t)h->H * h->W, nb = (size_t)h->max_batch;
-    HIPCHK(h, hipMalloc((void**)&h->d_src_ptrs, nb * sizeof(void*)));
-    HIPCHK(h, hipHostMalloc((void**)&h->h_src_ptrs, nb * sizeof(void*), hipHostMallocDefault));
-    HIPCHK(h, hipMalloc((void**)&h->d_net_lab, nb * hw * 3 * 8));
-    HIPCHK(h, hipMalloc((void**)&h->d_net_rgb, nb * hw * 3));
+    HIPCHK(h, h->d_src_ptrs.ensure(nb * sizeof(void*)));
+    HIPCHK(h, h->h_src_ptrs.ensure(nb * sizeof(void*)));
+    HIPCHK(h, h->d_net_lab.ensure(nb * hw * 3 * 8));
+    HIPCHK(h, h->d_net_rgb.ensure(nb * hw * 3));
     return IDC_OK;
 }
 
@@ -592,39 +543,34 @@ int idc_set_image_rgb(idc_handle h, int img, int n, int src_h, int src_w, const 
     if (rc) return rc;
     const size_t hw = (size_t)h->H * h->W, sb = (size_t)src_h * src_w * 3;
     const bool keep = (flags & IDC_INGEST_KEEP_SOURCE) != 0;
-    HIPCHK(h, hipStreamSynchronize(h->stream));            // the pointer table and the upload buffer of the previous call may still be read
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));            // the pointer table and the upload buffer of the previous call may still be read
     for (int i = 0; i < n; ++i) drop_source(h, img + i);   // a slot's previous source goes either way; a kept one gets its own allocation
     if (keep) {
         for (int i = 0; i < n; ++i) {
             auto& sl = h->src[img + i];
-            HIPCHK(h, hipMalloc((void**)&sl.d_rgb, sb));
+            HIPCHK(h, sl.d_rgb.ensure(sb));
             sl.h = src_h; sl.w = src_w;
-            h->h_src_ptrs[i] = sl.d_rgb;
+            h->h_src_ptrs.get()[i] = sl.d_rgb.get();
         }
     } else {
-        if (h->ingest_cap < (size_t)n * sb) {
-            if (h->d_ingest) (void)hipFree(h->d_ingest);
-            h->d_ingest = nullptr; h->ingest_cap = 0;
-            HIPCHK(h, hipMalloc((void**)&h->d_ingest, (size_t)n * sb));
-            h->ingest_cap = (size_t)n * sb;
-        }
-        for (int i = 0; i < n; ++i) h->h_src_ptrs[i] = h->d_ingest + (size_t)i * sb;
+        HIPCHK(h, h->d_ingest.ensure((size_t)n * sb));
+        for (int i = 0; i < n; ++i) h->h_src_ptrs.get()[i] = h->d_ingest.get() + (size_t)i * sb;
     }
     const bool in_pinned = is_pinned(rgb);                 // pinned: transferred in place on the stream; pageable: the runtime stages it
     for (int i = 0; i < n; ++i) {
-        void* dst = (void*)h->h_src_ptrs[i];
-        if (in_pinned) HIPCHK(h, hipMemcpyAsync(dst, rgb + (size_t)i * sb, sb, hipMemcpyHostToDevice, h->stream));
+        void* dst = (void*)h->h_src_ptrs.get()[i];
+        if (in_pinned) HIPCHK(h, hipMemcpyAsync(dst, rgb + (size_t)i * sb, sb, hipMemcpyHostToDevice, h->stream.get()));
         else HIPCHK(h, hipMemcpy(dst, rgb + (size_t)i * sb, sb, hipMemcpyHostToDevice));
     }
-    HIPCHK(h, hipMemcpyAsync((void*)h->d_src_ptrs, (const void*)h->h_src_ptrs, (size_t)n * sizeof(void*), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, launch_ingest_rgb(h->d_src_ptrs, n, src_h, src_w, h->H, h->W, l_cent, h->d_L + (size_t)img * hw, rgb_net ? h->d_net_rgb : nullptr,
-                                lab_net ? h->d_net_lab : nullptr, h->stream));
+    HIPCHK(h, hipMemcpyAsync((void*)h->d_src_ptrs.get(), (const void*)h->h_src_ptrs.get(), (size_t)n * sizeof(void*), hipMemcpyHostToDevice, h->stream.get()));
+    HIPCHK(h, launch_ingest_rgb(h->d_src_ptrs.get(), n, src_h, src_w, h->H, h->W, l_cent, h->d_L.get() + (size_t)img * hw, rgb_net ? h->d_net_rgb.get() : nullptr,
+                                lab_net ? h->d_net_lab.get() : nullptr, h->stream.get()));
     const bool rgb_direct = rgb_net && is_pinned(rgb_net), lab_direct = lab_net && is_pinned(lab_net);
-    if (rgb_direct) HIPCHK(h, hipMemcpyAsync(rgb_net, h->d_net_rgb, (size_t)n * hw * 3, hipMemcpyDeviceToHost, h->stream));
-    if (lab_direct) HIPCHK(h, hipMemcpyAsync(lab_net, h->d_net_lab, (size_t)n * hw * 3 * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (rgb_net && !rgb_direct) HIPCHK(h, hipMemcpy(rgb_net, h->d_net_rgb, (size_t)n * hw * 3, hipMemcpyDeviceToHost));
-    if (lab_net && !lab_direct) HIPCHK(h, hipMemcpy(lab_net, h->d_net_lab, (size_t)n * hw * 3 * 8, hipMemcpyDeviceToHost));
+    if (rgb_direct) HIPCHK(h, hipMemcpyAsync(rgb_net, h->d_net_rgb.get(), (size_t)n * hw * 3, hipMemcpyDeviceToHost, h->stream.get()));
+    if (lab_direct) HIPCHK(h, hipMemcpyAsync(lab_net, h->d_net_lab.get(), (size_t)n * hw * 3 * 8, hipMemcpyDeviceToHost, h->stream.get()));
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+    if (rgb_net && !rgb_direct) HIPCHK(h, hipMemcpy(rgb_net, h->d_net_rgb.get(), (size_t)n * hw * 3, hipMemcpyDeviceToHost));
+    if (lab_net && !lab_direct) HIPCHK(h, hipMemcpy(lab_net, h->d_net_lab.get(), (size_t)n * hw * 3 * 8, hipMemcpyDeviceToHost));
     for (int i = 0; i < n; ++i) h->l_set[img + i] = 1;
     return IDC_OK;
 }
@@ -636,7 +582,7 @@ int idc_fullres_rgb(idc_handle h, int img, int source, int interp, int l_mode, u
     if (l_mode != IDC_L_IMAGE && l_mode != IDC_L_MASK50) return fail(&h->err, IDC_ERR_INVALID_ARG, "l_mode %d not in 0..1", l_mode);
     if (source < IDC_SRC_OUTPUT_AB || source > IDC_SRC_NO_AB) return fail(&h->err, IDC_ERR_INVALID_ARG, "source %d not in 0..3", source);
     const auto& sl = h->src[img];
-    if (!sl.d_rgb) return fail(&h->err, IDC_ERR_UNSUPPORTED, "image slot %d has no resident source (idc_set_image_rgb with IDC_INGEST_KEEP_SOURCE)", img);
+    if (!sl.d_rgb.get()) return fail(&h->err, IDC_ERR_UNSUPPORTED, "image slot %d has no resident source (idc_set_image_rgb with IDC_INGEST_KEEP_SOURCE)", img);
     if (!rgb) return fail(&h->err, IDC_ERR_INVALID_ARG, "null rgb");
     HIPCHK(h, hipSetDevice(h->device));
     const void *pa = nullptr, *pb = nullptr; int f64 = 0;
@@ -648,34 +594,24 @@ int idc_fullres_rgb(idc_handle h, int img, int source, int interp, int l_mode, u
     if (rc) return rc;
     const size_t nbytes = (size_t)sl.h * sl.w * 3;
     const bool direct = is_pinned(rgb);                    // a pinned result buffer is written in place; a pageable one through pinned staging
-    if (h->full_cap < nbytes) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (h->d_full_rgb) (void)hipFree(h->d_full_rgb);
-        if (h->h_full_rgb) (void)hipHostFree(h->h_full_rgb);
-        h->d_full_rgb = nullptr; h->h_full_rgb = nullptr; h->full_cap = 0;
-        HIPCHK(h, hipMalloc((void**)&h->d_full_rgb, nbytes));
-        h->full_cap = nbytes;
+    if (h->d_full_rgb.bytes() < nbytes) {
+        HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+        HIPCHK(h, h->d_full_rgb.ensure(nbytes));
     }
-    if (!direct && !h->h_full_rgb) HIPCHK(h, hipHostMalloc((void**)&h->h_full_rgb, h->full_cap, hipHostMallocDefault));
-    const float* mask = l_mode == IDC_L_MASK50 ? h->d_mask + (size_t)img * h->H * h->W : nullptr;
-    HIPCHK(h, launch_fullres_rgb(sl.d_rgb, sl.h, sl.w, pa, pb, f64, h->H, h->W, interp, mask, h->hint_mask_value[img], h->d_full_rgb, h->stream));
-    HIPCHK(h, hipMemcpyAsync(direct ? rgb : h->h_full_rgb, h->d_full_rgb, nbytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (!direct) memcpy(rgb, h->h_full_rgb, nbytes);
+    if (!direct) HIPCHK(h, h->h_full_rgb.ensure(h->d_full_rgb.bytes()));
+    const float* mask = l_mode == IDC_L_MASK50 ? h->d_mask.get() + (size_t)img * h->H * h->W : nullptr;
+    HIPCHK(h, launch_fullres_rgb(sl.d_rgb.get(), sl.h, sl.w, pa, pb, f64, h->H, h->W, interp, mask, h->hint_mask_value[img], h->d_full_rgb.get(), h->stream.get()));
+    HIPCHK(h, hipMemcpyAsync(direct ? rgb : h->h_full_rgb.get(), h->d_full_rgb.get(), nbytes, hipMemcpyDeviceToHost, h->stream.get()));
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+    if (!direct) memcpy(rgb, h->h_full_rgb.get(), nbytes);
     return IDC_OK;
 }
 
 // ---------------------------------------------------------------------------------------------- colour picker
 // One device and one pinned buffer carry a call's inputs and results; both calls block, so nothing of the previous call is in flight when they grow
 static int ensure_pick_buffers(idc_context* h, size_t bytes) {
-    if (h->pick_cap >= bytes) return IDC_OK;
-    const size_t cap = bytes < 65536 ? 65536 : bytes;
-    if (h->d_pick) (void)hipFree(h->d_pick);
-    if (h->h_pick) (void)hipHostFree(h->h_pick);
-    h->d_pick = nullptr; h->h_pick = nullptr; h->pick_cap = 0;
-    HIPCHK(h, hipMalloc((void**)&h->d_pick, cap));
-    HIPCHK(h, hipHostMalloc((void**)&h->h_pick, cap, hipHostMallocDefault));
-    h->pick_cap = cap;
+    HIPCHK(h, h->d_pick.ensure(bytes, 65536));
+    HIPCHK(h, h->h_pick.ensure(bytes, 65536));
     return IDC_OK;
 }
 
@@ -701,15 +637,15 @@ int idc_gamut_map(idc_handle h, int n, const double* L, int gamut_size, int D, u
     const size_t total = o_mask + (mask ? np : 0);
     rc = ensure_pick_buffers(h, total);
     if (rc) return rc;
-    memcpy(h->h_pick, L, in_bytes);
-    HIPCHK(h, hipMemcpyAsync(h->d_pick, h->h_pick, in_bytes, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, launch_gamut_map((const double*)h->d_pick, n, gamut_size, D, A, pts_rgb ? h->d_pick + o_pts : nullptr,
-                               masked_rgb ? h->d_pick + o_masked : nullptr, mask ? h->d_pick + o_mask : nullptr, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->h_pick + in_bytes, h->d_pick + in_bytes, total - in_bytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (pts_rgb) memcpy(pts_rgb, h->h_pick + o_pts, np * 3);
-    if (masked_rgb) memcpy(masked_rgb, h->h_pick + o_masked, np * 3);
-    if (mask) memcpy(mask, h->h_pick + o_mask, np);
+    memcpy(h->h_pick.get(), L, in_bytes);
+    HIPCHK(h, hipMemcpyAsync(h->d_pick.get(), h->h_pick.get(), in_bytes, hipMemcpyHostToDevice, h->stream.get()));
+    HIPCHK(h, launch_gamut_map((const double*)h->d_pick.get(), n, gamut_size, D, A, pts_rgb ? h->d_pick.get() + o_pts : nullptr,
+                               masked_rgb ? h->d_pick.get() + o_masked : nullptr, mask ? h->d_pick.get() + o_mask : nullptr, h->stream.get()));
+    HIPCHK(h, hipMemcpyAsync(h->h_pick.get() + in_bytes, h->d_pick.get() + in_bytes, total - in_bytes, hipMemcpyDeviceToHost, h->stream.get()));
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+    if (pts_rgb) memcpy(pts_rgb, h->h_pick.get() + o_pts, np * 3);
+    if (masked_rgb) memcpy(masked_rgb, h->h_pick.get() + o_masked, np * 3);
+    if (mask) memcpy(mask, h->h_pick.get() + o_mask, np);
     return IDC_OK;
 }
 
@@ -727,19 +663,19 @@ int idc_snap_colors(idc_handle h, int n, const double* L, const uint8_t* rgb, ui
     const size_t total = o_out + (rgb_out ? nn * 3 : 0);
     rc = ensure_pick_buffers(h, total);
     if (rc) return rc;
-    memcpy(h->h_pick, L, nn * 8);
-    memcpy(h->h_pick + o_rgb, rgb, nn * 3);
-    HIPCHK(h, hipMemcpyAsync(h->d_pick, h->h_pick, in_bytes, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, launch_snap_colors((const double*)h->d_pick, h->d_pick + o_rgb, n, rgb_out ? h->d_pick + o_out : nullptr,
-                                 lab_out ? (double*)(h->d_pick + o_lab) : nullptr, iters ? (int*)(h->d_pick + o_it) : nullptr, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->h_pick + in_bytes, h->d_pick + in_bytes, total - in_bytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (lab_out) memcpy(lab_out, h->h_pick + o_lab, nn * 24);
-    if (iters) memcpy(iters, h->h_pick + o_it, nn * 4);
-    if (rgb_out) memcpy(rgb_out, h->h_pick + o_out, nn * 3);
+    memcpy(h->h_pick.get(), L, nn * 8);
+    memcpy(h->h_pick.get() + o_rgb, rgb, nn * 3);
+    HIPCHK(h, hipMemcpyAsync(h->d_pick.get(), h->h_pick.get(), in_bytes, hipMemcpyHostToDevice, h->stream.get()));
+    HIPCHK(h, launch_snap_colors((const double*)h->d_pick.get(), h->d_pick.get() + o_rgb, n, rgb_out ? h->d_pick.get() + o_out : nullptr,
+                                 lab_out ? (double*)(h->d_pick.get() + o_lab) : nullptr, iters ? (int*)(h->d_pick.get() + o_it) : nullptr, h->stream.get()));
+    HIPCHK(h, hipMemcpyAsync(h->h_pick.get() + in_bytes, h->d_pick.get() + in_bytes, total - in_bytes, hipMemcpyDeviceToHost, h->stream.get()));
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+    if (lab_out) memcpy(lab_out, h->h_pick.get() + o_lab, nn * 24);
+    if (iters) memcpy(iters, h->h_pick.get() + o_it, nn * 4);
+    if (rgb_out) memcpy(rgb_out, h->h_pick.get() + o_out, nn * 3);
     return IDC_OK;
 }
 
-void* idc_stream(idc_handle h) { return h ? (void*)h->stream : nullptr; }
+void* idc_stream(idc_handle h) { return h ? (void*)h->stream.get() : nullptr; }
 
 }  // extern "C"

@@ -78,10 +78,10 @@ int idc_layer_info_get(idc_handle h, int layer, idc_layer_info* out) {
 
 int idc_set_range_audit(idc_handle h, int on) {
     if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
-    if (on && !h->d_audit) {
+    if (on && !h->d_audit.get()) {
         HIPCHK(h, hipSetDevice(h->device));
-        HIPCHK(h, hipMalloc((void**)&h->d_audit, (size_t)h->n_timed * sizeof(AuditRecord)));
-        HIPCHK(h, hipMemsetAsync(h->d_audit, 0, (size_t)h->n_timed * sizeof(AuditRecord), h->stream));
+        HIPCHK(h, h->d_audit.ensure((size_t)h->n_timed * sizeof(AuditRecord)));
+        HIPCHK(h, hipMemsetAsync(h->d_audit.get(), 0, (size_t)h->n_timed * sizeof(AuditRecord), h->stream.get()));
         h->audit_values.assign((size_t)h->n_timed, 0);
     }
     h->audit = on != 0;
@@ -90,9 +90,9 @@ int idc_set_range_audit(idc_handle h, int on) {
 
 int idc_range_reset(idc_handle h) {
     if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
-    if (h->d_audit) {
+    if (h->d_audit.get()) {
         HIPCHK(h, hipSetDevice(h->device));
-        HIPCHK(h, hipMemsetAsync(h->d_audit, 0, (size_t)h->n_timed * sizeof(AuditRecord), h->stream));     // stream-ordered behind the audited forwards
+        HIPCHK(h, hipMemsetAsync(h->d_audit.get(), 0, (size_t)h->n_timed * sizeof(AuditRecord), h->stream.get()));     // stream-ordered behind the audited forwards
         h->audit_values.assign((size_t)h->n_timed, 0);
     }
     return IDC_OK;
@@ -114,11 +114,11 @@ int idc_range_report(idc_handle h, int layer, idc_range_info* out) {
         out->parts = f32 ? 1 : t.parts;
         if ((size_t)(layer - 1) < h->act_exp.size()) out->act_exp = h->act_exp[layer - 1];
     }
-    if (!h->d_audit) return IDC_OK;                  // never switched on: all counts zero
+    if (!h->d_audit.get()) return IDC_OK;                  // never switched on: all counts zero
     HIPCHK(h, hipSetDevice(h->device));
     AuditRecord r;
-    HIPCHK(h, hipMemcpyAsync(&r, h->d_audit + layer, sizeof(r), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpyAsync(&r, h->d_audit.get() + layer, sizeof(r), hipMemcpyDeviceToHost, h->stream.get()));
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
     rc = check_chain_abort(h);
     if (rc) return rc;
     memcpy(&out->max_abs, &r.max_abs_bits, 4);
@@ -130,10 +130,10 @@ int idc_range_report(idc_handle h, int layer, idc_range_info* out) {
 
 int idc_set_profiling(idc_handle h, int on) {
     if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
-    if (on != 0 && h->ev.empty()) {
+    if (on != 0) {
         HIPCHK(h, hipSetDevice(h->device));
-        h->ev.assign((size_t)h->n_timed * 2 * kProfRing, nullptr);
-        for (auto& e : h->ev) HIPCHK(h, hipEventCreate(&e));
+        h->ev.resize((size_t)h->n_timed * 2 * kProfRing);
+        for (auto& e : h->ev) HIPCHK(h, e.create());
     }
     h->profiling = on == 2 ? 2 : (on != 0 ? 1 : 0);
     h->prof_count = 0;
@@ -144,7 +144,7 @@ int idc_layer_times_ms(idc_handle h, float* ms, int capacity) {
     if (!h || !ms) return fail(h ? &h->err : nullptr, IDC_ERR_INVALID_ARG, "null argument");
     if (h->ev.empty()) return fail(&h->err, IDC_ERR_INVALID_ARG, "no forward was recorded with profiling on");
     if (capacity < h->n_timed) return fail(&h->err, IDC_ERR_INVALID_ARG, "capacity %d < %d", capacity, h->n_timed);
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
     const int slots = (int)(h->prof_count < kProfRing ? h->prof_count : kProfRing);
     if (slots == 0) return fail(&h->err, IDC_ERR_INVALID_ARG, "no forward was recorded with profiling on");
     for (int i = 0; i < h->n_timed; ++i) {
@@ -153,7 +153,7 @@ int idc_layer_times_ms(idc_handle h, float* ms, int capacity) {
         for (int sl = 0; sl < slots; ++sl) {
             float t = 0.f;
             const size_t base = (size_t)sl * h->n_timed * 2;
-            if (hipEventElapsedTime(&t, h->ev[base + i * 2], h->ev[base + i * 2 + 1]) != hipSuccess) { t = 0.f; (void)hipGetLastError(); }
+            if (hipEventElapsedTime(&t, h->ev[base + i * 2].get(), h->ev[base + i * 2 + 1].get()) != hipSuccess) { t = 0.f; (void)hipGetLastError(); }
             sum += t;
         }
         ms[i] = (float)(sum / slots);
@@ -165,7 +165,7 @@ int idc_layer_times_stats(idc_handle h, float* ms_min, float* ms_median, float* 
     if (!h || !ms_min || !ms_median || !ms_max) return fail(h ? &h->err : nullptr, IDC_ERR_INVALID_ARG, "null argument");
     if (h->ev.empty()) return fail(&h->err, IDC_ERR_INVALID_ARG, "no forward was recorded with profiling on");
     if (capacity < h->n_timed) return fail(&h->err, IDC_ERR_INVALID_ARG, "capacity %d < %d", capacity, h->n_timed);
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
     const int slots = (int)(h->prof_count < kProfRing ? h->prof_count : kProfRing);
     if (slots == 0) return fail(&h->err, IDC_ERR_INVALID_ARG, "no forward was recorded with profiling on");
     std::vector<float> v((size_t)slots);
@@ -174,7 +174,7 @@ int idc_layer_times_stats(idc_handle h, float* ms_min, float* ms_median, float* 
         for (int sl = 0; sl < slots; ++sl) {
             float t = 0.f;
             const size_t base = (size_t)sl * h->n_timed * 2;
-            if (hipEventElapsedTime(&t, h->ev[base + i * 2], h->ev[base + i * 2 + 1]) != hipSuccess) { t = 0.f; (void)hipGetLastError(); }
+            if (hipEventElapsedTime(&t, h->ev[base + i * 2].get(), h->ev[base + i * 2 + 1].get()) != hipSuccess) { t = 0.f; (void)hipGetLastError(); }
             v[(size_t)sl] = t;
         }
         std::sort(v.begin(), v.end());
@@ -203,18 +203,13 @@ int idc_get_activation(idc_handle h, const char* name, int n, float* out, size_t
     const size_t need = (size_t)n * t.C * t.H * t.W;
     if (capacity_floats < need) return fail(&h->err, IDC_ERR_INVALID_ARG, "need %zu floats", need);
     HIPCHK(h, hipSetDevice(h->device));
-    if (h->scratch_bytes < need * 4) {
-        if (h->d_scratch) (void)hipFree(h->d_scratch);
-        h->d_scratch = nullptr; h->scratch_bytes = 0;
-        HIPCHK(h, hipMalloc((void**)&h->d_scratch, need * 4));
-        h->scratch_bytes = need * 4;
-    }
+    HIPCHK(h, h->d_scratch.ensure(need * 4));
     const int src_bf16 = (!t.is_f32 && h->precision != IDC_FP32) ? 1 : 0;
     if (t.parts > 1 || (is_split(h->precision) && !t.is_f32)) HIPCHK(h, launch_split_to_nchw(      // (IDC_FP16: one fp16 plane)
-        t.ptr, h->d_scratch, n, t.C, t.H, t.W, t.Cpad, t.parts, split_is_f16(h->precision) ? 1 : 0, h->stream));
-    else HIPCHK(h, launch_nhwc_to_nchw(src_bf16, t.ptr, h->d_scratch, n, t.C, t.H, t.W, t.Cpad, h->stream));
-    HIPCHK(h, hipMemcpyAsync(out, h->d_scratch, need * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+        t.ptr, h->d_scratch.get(), n, t.C, t.H, t.W, t.Cpad, t.parts, split_is_f16(h->precision) ? 1 : 0, h->stream.get()));
+    else HIPCHK(h, launch_nhwc_to_nchw(src_bf16, t.ptr, h->d_scratch.get(), n, t.C, t.H, t.W, t.Cpad, h->stream.get()));
+    HIPCHK(h, hipMemcpyAsync(out, h->d_scratch.get(), need * 4, hipMemcpyDeviceToHost, h->stream.get()));
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
     for (size_t li = 0; li < h->layers.size() && li < h->act_exp.size(); ++li)      // stored as value * 2^a: hand out the value (a power of two: exact)
         if (h->layers[li].dst == ti && h->act_exp[li] != 0)
             for (size_t i = 0; i < need; ++i) out[i] = ldexpf(out[i], -h->act_exp[li]);
@@ -336,21 +331,21 @@ static int run_single_op(int device_id, int precision, LayerSpec spec, int n, in
         if (bn_scale) { floats(op.blob.bn_scale_off)[c] = real ? bn_scale[c] : 1.f; floats(op.blob.bn_shift_off)[c] = (real && bn_shift) ? bn_shift[c] : 0.f; }
     }
     if (split) *floats(op.blob.wscale_off) = wscale[0];
-    DevBuf d_blob, d_part, d_nchw;
-    std::vector<DevBuf> d_t(T.size());
-    HIPCHK(nullctx, d_blob.alloc(blob_bytes));
-    HIPCHK(nullctx, hipMemcpy(d_blob.p, blob.data(), blob_bytes, hipMemcpyHostToDevice));
+    DevMem<uint8_t> d_blob; DevMem<float> d_part, d_nchw;
+    std::vector<DevMem<void>> d_t(T.size());
+    HIPCHK(nullctx, d_blob.ensure(blob_bytes));
+    HIPCHK(nullctx, hipMemcpy(d_blob.get(), blob.data(), blob_bytes, hipMemcpyHostToDevice));
     // fp32 NCHW on the host -> the tensor's storage on the device
     auto upload = [&](int ti, const float* src) -> int {
         Tensor& t = T[ti];
         const size_t count = (size_t)n * t.C * t.H * t.W;
-        DevBuf raw;
-        HIPCHK(nullctx, raw.alloc(count * 4));
-        HIPCHK(nullctx, d_t[ti].alloc(t.bytes));
-        t.ptr = d_t[ti].p;
-        HIPCHK(nullctx, hipMemcpy(raw.p, src, count * 4, hipMemcpyHostToDevice));
-        if (t.parts > 1 || (split && !t.is_f32)) HIPCHK(nullctx, launch_nchw_to_split((const float*)raw.p, t.ptr, n, t.C, t.H, t.W, t.Cpad, t.parts, f16 ? 1 : 0, nullptr));
-        else HIPCHK(nullctx, launch_nchw_to_nhwc(t.is_f32 ? IDC_FP32 : IDC_BF16, (const float*)raw.p, t.ptr, n, t.C, t.H, t.W, t.Cpad, nullptr));
+        DevMem<float> raw;
+        HIPCHK(nullctx, raw.ensure(count * 4));
+        HIPCHK(nullctx, d_t[ti].ensure(t.bytes));
+        t.ptr = d_t[ti].get();
+        HIPCHK(nullctx, hipMemcpy(raw.get(), src, count * 4, hipMemcpyHostToDevice));
+        if (t.parts > 1 || (split && !t.is_f32)) HIPCHK(nullctx, launch_nchw_to_split(raw.get(), t.ptr, n, t.C, t.H, t.W, t.Cpad, t.parts, f16 ? 1 : 0, nullptr));
+        else HIPCHK(nullctx, launch_nchw_to_nhwc(t.is_f32 ? IDC_FP32 : IDC_BF16, raw.get(), t.ptr, n, t.C, t.H, t.W, t.Cpad, nullptr));
         HIPCHK(nullctx, hipDeviceSynchronize());          // (raw is freed on return)
         return IDC_OK;
     };
@@ -359,12 +354,12 @@ static int run_single_op(int device_id, int precision, LayerSpec spec, int n, in
     if (rc == IDC_OK && sc) rc = upload(t_x2, sc->x);
     if (rc) return rc;
     Tensor& ty = T[t_y];
-    HIPCHK(nullctx, d_t[t_y].alloc(ty.bytes));
-    ty.ptr = d_t[t_y].p;
+    HIPCHK(nullctx, d_t[t_y].ensure(ty.bytes));
+    ty.ptr = d_t[t_y].get();
     const ConvArgs& a = op.args;
-    if (a.ksplit > 1) HIPCHK(nullctx, d_part.alloc((size_t)a.ksplit * n * Ho * Wo * cpad * 4));
+    if (a.ksplit > 1) HIPCHK(nullctx, d_part.ensure((size_t)a.ksplit * n * Ho * Wo * cpad * 4));
     BindEnv be;
-    be.blob = (const uint8_t*)d_blob.p; be.tensors = &T; be.zeros = be.blob + zeros_off; be.partial = (float*)d_part.p;
+    be.blob = d_blob.get(); be.tensors = &T; be.zeros = be.blob + zeros_off; be.partial = d_part.get();
     bind_layer(layers, (int)layers.size() - 1, be);
     char k[64]; kernel_label(op, precision, k, sizeof(k));
     g_op_last_kernel = k;
@@ -374,10 +369,10 @@ static int run_single_op(int device_id, int precision, LayerSpec spec, int n, in
     HIPCHK(nullctx, le);
     if (a.ksplit > 1) HIPCHK(nullctx, launch_splitk_epilogue(precision, a, nullptr));
     const size_t yout = (size_t)n * spec.cout * Ho * Wo;
-    HIPCHK(nullctx, d_nchw.alloc(yout * 4));
-    if (split) HIPCHK(nullctx, launch_split_to_nchw(ty.ptr, (float*)d_nchw.p, n, spec.cout, Ho, Wo, cpad, parts, f16 ? 1 : 0, nullptr));
-    else HIPCHK(nullctx, launch_nhwc_to_nchw(ty.is_f32 ? 0 : 1, ty.ptr, (float*)d_nchw.p, n, spec.cout, Ho, Wo, cpad, nullptr));
-    HIPCHK(nullctx, hipMemcpy(y, d_nchw.p, yout * 4, hipMemcpyDeviceToHost));
+    HIPCHK(nullctx, d_nchw.ensure(yout * 4));
+    if (split) HIPCHK(nullctx, launch_split_to_nchw(ty.ptr, d_nchw.get(), n, spec.cout, Ho, Wo, cpad, parts, f16 ? 1 : 0, nullptr));
+    else HIPCHK(nullctx, launch_nhwc_to_nchw(ty.is_f32 ? 0 : 1, ty.ptr, d_nchw.get(), n, spec.cout, Ho, Wo, cpad, nullptr));
+    HIPCHK(nullctx, hipMemcpy(y, d_nchw.get(), yout * 4, hipMemcpyDeviceToHost));
     HIPCHK(nullctx, hipDeviceSynchronize());
     return IDC_OK;
 }

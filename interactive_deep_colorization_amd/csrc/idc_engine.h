@@ -9,6 +9,7 @@
 #include "../../include/ideepcolor.h"
 #include "idc_kernels.h"
 #include "idc_layout.h"
+#include "idc_mem.h"
 #include "idc_net.h"
 
 namespace idc {
@@ -85,12 +86,6 @@ struct BindEnv {
     float* out = nullptr; float out_mul = 110.f;                   // ... and its ab map
 };
 
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 16); }
-};
-
 // The options of idc_set_option / idc_set_tile_policy / idc_set_splitk_policy (idc_plan.hip): one object per process, options().
 struct Options {
     // Tile policy (speed only; every choice computes the same result): 0 = automatic, 1 = always the
@@ -142,84 +137,94 @@ Options& options();
 
 using namespace idc;
 
+// Everything the handle takes from the runtime is held by an owner (idc_mem.h), so destroying the handle is `delete`.  Members go in reverse order of
+// declaration: the streams are declared before every buffer and event, and so are destroyed after them.
 struct idc_context {
     int device = 0, H = 0, W = 0, max_batch = 0, precision = 0;
     unsigned flags = 0;
-    hipStream_t stream = nullptr;
+    Stream stream;
+    Stream s_in, s_out;                  // the transfer pipeline's copy-in and copy-out streams (ensure_pipeline)
     std::string err;
     float l_div = 100.f, ab_div = 110.f, mask_mul = 1.f, out_mul = 110.f;
     BlobPlan plan;
-    uint8_t* d_blob = nullptr;
-    bool own_blob = false, weights_set = false;
+    const uint8_t* d_blob = nullptr;     // the parameter blob in use: blob_mem's, or the caller's (idc_set_weights_device without copy)
+    DevMem<uint8_t> blob_mem;            // the handle's own copy (own_blob_storage); empty while the caller's is in use
+    bool weights_set = false;
     std::vector<Tensor> tensors;
     std::vector<Layer> layers;
     int t_input = -1, t_conv10_2 = -1, t_logits = -1;
     // staging for the host-pointer forward
-    float *h_in = nullptr, *h_out = nullptr, *h_dist = nullptr;
-    float *d_L = nullptr, *d_ab = nullptr, *d_mask = nullptr, *d_out = nullptr, *d_dist = nullptr;
-    float* d_scratch = nullptr; size_t scratch_bytes = 0;
-    float* d_partial = nullptr; size_t partial_bytes = 0;    // split-K slice sums (grown on demand)
-    void* d_zeros = nullptr;             // 256 zero bytes: LDS-DMA source of out-of-image halo rows (conv_click)
-    unsigned long long* d_kw_bar = nullptr;   // conv_kwave_chain_bf16's grid-barrier counter (monotone) ...
+    PinnedMem<float> h_in, h_out, h_dist;
+    DevMem<float> d_L, d_ab, d_mask, d_out, d_dist;
+    DevMem<float> d_scratch;
+    DevMem<float> d_partial;             // split-K slice sums (grown on demand)
+    DevMem<void> d_zeros;                // 256 zero bytes: LDS-DMA source of out-of-image halo rows (conv_click)
+    DevMem<unsigned long long> d_kw_bar;      // conv_kwave_chain_bf16's grid-barrier counter (monotone) ...
     unsigned long long kw_bar_count = 0;      // ... grid barriers done by every launch so far (each adds its arrivals to its counter)
     int kw_bar_blocks = 0;                    // ... workgroups per launch those counts are for (a different grid resets the counters)
-    long long* d_kw_stamps = nullptr;         // IDC_KW_STAMPS=1: per-phase cycle stamps of the last chain launch, printed when the handle is destroyed
+    DevMem<long long> d_kw_stamps;            // IDC_KW_STAMPS=1: per-phase cycle stamps of the last chain launch, printed when the handle is destroyed
     int kw_stamp_layers = 0, kw_stamp_blocks = 0;
-    int* h_kw_abort = nullptr;                // pinned, device-visible: a chain workgroup that gave up waiting sets it
+    PinnedMem<int> h_kw_abort{hipHostMallocMapped};   // pinned, device-visible: a chain workgroup that gave up waiting sets it
     bool kw_chain_off = false;                // set after a refused / aborted chain launch: the handle falls back to one launch per layer
     int kw_chain_fits = -1;                   // workgroups of the chain kernel this device holds at once (-1: not asked yet)
-    float *d_glob_in = nullptr, *d_glob_vec = nullptr;   // global hints: [max_batch][316] inputs, [max_batch][512] branch output
+    DevMem<float> d_glob_in, d_glob_vec; // global hints: [max_batch][316] inputs, [max_batch][512] branch output
     int t_conv4_3 = -1, t_pred313 = -1;
-    float *d_pred_ab = nullptr, *d_dist313 = nullptr, *h_pred_ab = nullptr, *h_dist313 = nullptr;   // 313 head outputs
+    DevMem<float> d_pred_ab, d_dist313;  // 313 head outputs
+    PinnedMem<float> h_pred_ab;
     float dist_S = 0.2f;
-    unsigned char *d_rgb = nullptr, *h_rgb = nullptr;   // colour post-processing (allocated on first use)
-    double *d_labq = nullptr, *h_labq = nullptr;
-    float* d_post_in = nullptr;          // idc_lab2rgb staging (L + ab planes): the resident L / hint planes are left alone
+    DevMem<unsigned char> d_rgb;         // colour post-processing (allocated on first use)
+    PinnedMem<unsigned char> h_rgb;
+    DevMem<double> d_labq;
+    PinnedMem<double> h_labq;
+    DevMem<float> d_post_in;             // idc_lab2rgb staging (L + ab planes): the resident L / hint planes are left alone
     bool want_dist313 = false;           // the next forward also writes the full-resolution dist_S
     bool keep_dist313 = false;           // idc_keep_dist: every forward leaves dist_S resident (colour suggestions)
     int dist_n = 0;                      // images whose distribution is resident from the last forward (0 = none)
-    HintRect *d_hints = nullptr, *h_hints = nullptr; int hints_cap = 0;   // click session: hint list staging
-    float* d_centres = nullptr; double* d_sugg = nullptr; unsigned* d_sugg_counts = nullptr;   // colour suggestions
-    float *d_map_ab = nullptr, *d_map_s = nullptr;   // idc_dist_decode / idc_dist_entropy results: [max_batch][2][npix], [max_batch][npix] (first use)
+    DevMem<HintRect> d_hints;            // click session: hint list staging
+    PinnedMem<HintRect> h_hints;
+    DevMem<float> d_centres; DevMem<double> d_sugg; DevMem<unsigned> d_sugg_counts;   // colour suggestions
+    DevMem<float> d_map_ab, d_map_s;     // idc_dist_decode / idc_dist_entropy results: [max_batch][2][npix], [max_batch][npix] (first use)
     std::vector<char> l_set;             // per image slot: d_L holds an uploaded L plane (idc_forward_resident refuses otherwise)
-    // image ingestion (idc_set_image_rgb / idc_fullres_rgb): per slot the uint8 source kept on the device (IDC_INGEST_KEEP_SOURCE; nullptr = none)
+    // image ingestion (idc_set_image_rgb / idc_fullres_rgb): per slot the uint8 source kept on the device (IDC_INGEST_KEEP_SOURCE; empty = none)
     // and its size, and the mask_value of the slot's last idc_set_hints (0 = never had hints)
-    struct SlotSource { unsigned char* d_rgb = nullptr; int h = 0, w = 0; };
+    struct SlotSource { DevMem<unsigned char> d_rgb; int h = 0, w = 0; };
     std::vector<SlotSource> src;
     std::vector<float> hint_mask_value;
-    unsigned char* d_ingest = nullptr; size_t ingest_cap = 0;        // upload buffer of the sources that are not kept
-    const unsigned char** d_src_ptrs = nullptr;                      // [max_batch] source pointers of one ingest launch ...
-    const unsigned char** h_src_ptrs = nullptr;                      // ... and their pinned host copy
-    unsigned char* d_net_rgb = nullptr; double* d_net_lab = nullptr; // idc_set_image_rgb results [max_batch,H,W,3] u8, [max_batch,3,H,W] f64 (first use)
-    unsigned char *d_full_rgb = nullptr, *h_full_rgb = nullptr; size_t full_cap = 0;   // idc_fullres_rgb result and (pageable callers) its pinned staging; bytes of each
-    unsigned char *d_pick = nullptr, *h_pick = nullptr; size_t pick_cap = 0;   // idc_gamut_map / idc_snap_colors: inputs + results of one call, device and pinned; bytes of each
-    hipEvent_t ev_sync = nullptr;        // idc_stream_wait / idc_stream_signal
+    DevMem<unsigned char> d_ingest;                                  // upload buffer of the sources that are not kept
+    DevMem<const unsigned char*> d_src_ptrs;                         // [max_batch] source pointers of one ingest launch ...
+    PinnedMem<const unsigned char*> h_src_ptrs;                      // ... and their pinned host copy
+    DevMem<unsigned char> d_net_rgb; DevMem<double> d_net_lab;       // idc_set_image_rgb results [max_batch,H,W,3] u8, [max_batch,3,H,W] f64 (first use)
+    DevMem<unsigned char> d_full_rgb;    // idc_fullres_rgb result ...
+    PinnedMem<unsigned char> h_full_rgb; // ... and (pageable callers) its pinned staging, as large
+    DevMem<unsigned char> d_pick;        // idc_gamut_map / idc_snap_colors: inputs + results of one call, device and pinned
+    PinnedMem<unsigned char> h_pick;
+    Event ev_sync;                       // idc_stream_wait / idc_stream_signal
     // two-slot transfer pipeline (idc_forward_async / idc_wait): each slot owns its device planes
     struct PipeSlot {
-        float *d_L = nullptr, *d_ab = nullptr, *d_mask = nullptr, *d_out = nullptr;   // device I/O planes
-        float *h_in = nullptr, *h_out = nullptr;                                       // pinned staging (pageable callers)
-        hipEvent_t ev_in = nullptr, ev_comp = nullptr, ev_out = nullptr;
-        hipEvent_t ev_in0 = nullptr, ev_comp0 = nullptr, ev_out0 = nullptr;             // stage starts (idc_pipeline_times)
+        DevMem<float> d_L, d_ab, d_mask, d_out;                                        // device I/O planes
+        PinnedMem<float> h_in, h_out;                                                  // pinned staging (pageable callers)
+        Event ev_in, ev_comp, ev_out;
+        Event ev_in0, ev_comp0, ev_out0;                                               // stage starts (idc_pipeline_times)
         bool pending = false, staged_out = false, timed = false;
         float* user_out = nullptr; int n = 0;
     } pipe[2];
-    hipStream_t s_in = nullptr, s_out = nullptr;
-    hipEvent_t ev_pipe_base = nullptr;
-    bool pipe_ready = false;
-    unsigned char* d_up_rgb = nullptr; double* d_up_L = nullptr; size_t up_cap = 0;    // idc_upsample_lab2rgb staging
-    unsigned char* h_up_rgb = nullptr; double* h_up_L = nullptr;
+    Event ev_pipe_base;
+    bool pipe_ready = false;             // ev_pipe_base is recorded (ensure_pipeline)
+    DevMem<unsigned char> d_up_rgb; DevMem<double> d_up_L;           // idc_upsample_lab2rgb staging
+    PinnedMem<unsigned char> h_up_rgb; PinnedMem<double> h_up_L;
     bool out_copy_pending = false;       // forward_host(finish = false): the ab map still has to be copied from h_out to the caller
     bool out_resident = false;           // d_out / d_labq hold the last forward's ab map / refreshed Lab
     bool labq_resident = false;
     int profiling = 0;                   // 0 off, 1 = an event pair around every launch, 2 = one pair around the whole forward
-    void* d_arena = nullptr;             // all activation tensors (alloc_graph), or nullptr with IDC_ARENA=0
-    std::vector<hipEvent_t> ev;          // kProfRing slots x 2 per timed step: [pack, layers..., head, softmax]
+    DevMem<void> d_arena;                // all activation tensors (alloc_graph) ...
+    std::vector<DevMem<void>> tensor_mem;    // ... or one allocation per tensor with IDC_ARENA=0; Tensor::ptr views either
+    std::vector<Event> ev;               // kProfRing slots x 2 per timed step: [pack, layers..., head, softmax]
     int n_timed = 0;
     long long prof_count = 0;            // forwards recorded since profiling was switched on
     int last_n = 0;
     // range audit (idc_set_range_audit): one sticky AuditRecord per row of the layer table in device memory, the value counts on the host
     bool audit = false;
-    AuditRecord* d_audit = nullptr;
+    DevMem<AuditRecord> d_audit;
     std::vector<unsigned long long> audit_values;
     // from the blob in use (cache_blob_meta): the activation exponent of each active layer's output and its accumulator-scale word
     std::vector<int> act_exp;
@@ -252,6 +257,7 @@ void pack_layer_weights(uint8_t* wimg, int precision, int layout, const LayerSpe
 void pack_wino_weights(uint8_t* img, int precision, const LayerSpec& s, const LayerBlob& lb, const float* w);
 void pack_wino_deconv_weights(uint8_t* img, int precision, const LayerSpec& s, const LayerBlob& lb, const float* w);
 int verify_device_blob(idc_context* h, const void* dev_blob, size_t blob_bytes);
+int own_blob_storage(idc_context* h);            // d_blob = the handle's own allocation of plan.total_bytes, made unless it already has one
 
 // idc_plan.hip
 int find_tensor(const std::vector<Tensor>& tensors, const char* name);

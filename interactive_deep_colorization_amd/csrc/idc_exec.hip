@@ -14,7 +14,7 @@ namespace idc {
 static int launch_kwave_chain(idc_context* c, int li, hipStream_t s, int* chain_until) {
     Layer& L = c->layers[li];
     const ConvArgs& a = L.args;
-    if (!options().kwave_chain || c->kw_chain_off || c->profiling == 1 || !c->d_kw_bar || L.spec->kind != kConv3x3 || a.nkc != 8 || a.si != 1 ||
+    if (!options().kwave_chain || c->kw_chain_off || c->profiling == 1 || !c->d_kw_bar.get() || L.spec->kind != kConv3x3 || a.nkc != 8 || a.si != 1 ||
         a.img_shift != nullptr || a.out_f32)
         return IDC_OK;
     const int blocks = conv_kwave_chain_blocks(a.Hs, a.Ws, a.N, a.ncg, a.dy[8]);
@@ -41,16 +41,16 @@ static int launch_kwave_chain(idc_context* c, int li, hipStream_t s, int* chain_
     if (c->kw_chain_fits < 0) c->kw_chain_fits = conv_kwave_chain_capacity(c->device);
     if (c->kw_chain_fits < blocks) return IDC_OK;   // more workgroups than the chip holds at once: this launch goes layer by layer
     if (blocks != c->kw_bar_blocks) {      // counters hold (barriers so far) x (arrivals per barrier of THIS grid)
-        HIPCHK(c, hipMemsetAsync(c->d_kw_bar, 0, 1024, s));
+        HIPCHK(c, hipMemsetAsync(c->d_kw_bar.get(), 0, 1024, s));
         c->kw_bar_count = 0; c->kw_bar_blocks = blocks;
     }
-    ch.bar = c->d_kw_bar; ch.bar_base = c->kw_bar_count; ch.abort_flag = c->h_kw_abort;
+    ch.bar = c->d_kw_bar.get(); ch.bar_base = c->kw_bar_count; ch.abort_flag = c->h_kw_abort.get();
     // test hook (tests/test_round5_gpu.py): IDC_KW_FORCE_ABORT=1 makes the first grid barrier unreachable and the give-up
     // counter tiny, i.e. it plays "the workgroups never become co-resident" on a healthy device
     if (options().kw_force_abort) { ch.bar_base += 1000; ch.spin_limit = 20u; }
     static const bool want_stamps = idc_env_int("IDC_KW_STAMPS", 0) != 0;
-    if (want_stamps && !c->d_kw_stamps) HIPCHK(c, hipMalloc((void**)&c->d_kw_stamps, (size_t)4096 * kKwChainMax * 8 * 8));
-    ch.stamps = (want_stamps && blocks <= 4096) ? c->d_kw_stamps : nullptr;
+    if (want_stamps) HIPCHK(c, c->d_kw_stamps.ensure((size_t)4096 * kKwChainMax * 8 * 8));
+    ch.stamps = (want_stamps && blocks <= 4096) ? c->d_kw_stamps.get() : nullptr;
     c->kw_stamp_layers = ch.nlayers; c->kw_stamp_blocks = blocks;
     if (launch_conv_kwave_chain(ch, blocks, options().kwave_chain, s) != hipSuccess) {
         (void)hipGetLastError();          // refused (e.g. hipErrorCooperativeLaunchTooLarge): one launch per layer from now on
@@ -102,27 +102,27 @@ void bind_layer(std::vector<Layer>& layers, int li, const BindEnv& e) {
 
 int run_graph(idc_context* c, int n, const float* dL, const float* dab, const float* dmask, float maskcent,
                      float* dout, float* ddist) {
-    hipStream_t s = c->stream;
+    hipStream_t s = c->stream.get();
     int step = 0;
     {   // a workgroup of an EARLIER conv_kwave_chain_bf16 launch gave up at its grid barrier and nobody has waited on that forward since
         const int arc = check_chain_abort(c);
         if (arc) return arc;
     }
     const size_t ring = (size_t)(c->prof_count % kProfRing) * c->n_timed * 2;
-    auto tic = [&]() { if (c->profiling == 1) (void)hipEventRecord(c->ev[ring + step * 2], s); };
-    auto toc = [&]() { if (c->profiling == 1) (void)hipEventRecord(c->ev[ring + step * 2 + 1], s); ++step; };
+    auto tic = [&]() { if (c->profiling == 1) (void)hipEventRecord(c->ev[ring + step * 2].get(), s); };
+    auto toc = [&]() { if (c->profiling == 1) (void)hipEventRecord(c->ev[ring + step * 2 + 1].get(), s); ++step; };
     // range audit: the stored output of layer index lj, folded into its record right behind the launch that wrote it (outside the event pairs)
     auto audit_layer = [&](int lj) -> hipError_t {
         const Layer& Q = c->layers[lj];
         const Tensor& t = c->tensors[Q.dst];
         const int parts = t.is_f32 ? 0 : t.parts;
         c->audit_values[lj + 1] += (unsigned long long)n * t.C * t.H * t.W;
-        return launch_range_audit(t.ptr, (long long)n * t.H * t.W, t.C, t.Cpad, parts, split_is_f16(c->precision) ? 1 : 0, c->d_audit + lj + 1, s);
+        return launch_range_audit(t.ptr, (long long)n * t.H * t.W, t.C, t.Cpad, parts, split_is_f16(c->precision) ? 1 : 0, c->d_audit.get() + lj + 1, s);
     };
-    if (c->profiling == 2) (void)hipEventRecord(c->ev[ring], s);          // whole-forward pair: slot 0
+    if (c->profiling == 2) (void)hipEventRecord(c->ev[ring].get(), s);          // whole-forward pair: slot 0
     tic();   // (slot 0: the input pack is fused into conv1_1's operand staging; only the global-hints branch runs here)
     if (c->flags & IDC_FLAG_GLOBAL_HINTS)      // four GEMVs per image; its output is consumed by conv4_3's epilogue
-        HIPCHK(c, launch_glob_branch(c->d_glob_in, (const float*)(c->d_blob + c->plan.glob_off), c->d_glob_vec, n, s));
+        HIPCHK(c, launch_glob_branch(c->d_glob_in.get(), (const float*)(c->d_blob + c->plan.glob_off), c->d_glob_vec.get(), n, s));
     toc();
     PlanEnv pe;
     pe.precision = c->precision; pe.flags = c->flags; pe.H = c->H; pe.W = c->W; pe.max_batch = c->max_batch; pe.n = n;
@@ -131,7 +131,7 @@ int run_graph(idc_context* c, int n, const float* dL, const float* dab, const fl
     if (prc) return prc;
     BindEnv be;
     be.blob = c->d_blob; be.head_w_off = c->plan.head_w_off; be.head_b_off = c->plan.head_b_off;
-    be.tensors = &c->tensors; be.zeros = c->d_zeros; be.glob_vec = c->d_glob_vec;
+    be.tensors = &c->tensors; be.zeros = c->d_zeros.get(); be.glob_vec = c->d_glob_vec.get();
     be.L = dL; be.ab = dab; be.mask = dmask; be.l_div = c->l_div; be.ab_div = c->ab_div; be.mask_mul = c->mask_mul; be.mask_cent = maskcent;
     be.out = dout; be.out_mul = c->out_mul;
     // diagnostic (IDC_DOUBLE_LAUNCH=1): every launch issued twice, the event pair around the SECOND -- a layer that is slow only as
@@ -148,15 +148,12 @@ int run_graph(idc_context* c, int n, const float* dL, const float* dab, const fl
         if (L.kernel == kFused || li <= chain_until) { tic(); toc(); continue; }
         if (a.ksplit > 1) {
             const size_t need = (size_t)a.ksplit * n * to.H * to.W * to.Cpad * 4;
-            if (c->partial_bytes < need) {
+            if (c->d_partial.bytes() < need) {
                 HIPCHK(c, hipStreamSynchronize(s));
-                if (c->d_partial) (void)hipFree(c->d_partial);
-                c->d_partial = nullptr; c->partial_bytes = 0;
-                HIPCHK(c, hipMalloc((void**)&c->d_partial, need));
-                c->partial_bytes = need;
+                HIPCHK(c, c->d_partial.ensure(need));
             }
         }
-        be.partial = c->d_partial;
+        be.partial = c->d_partial.get();
         bind_layer(c->layers, li, be);
         head_done = head_done || L.fused_head;
         for (int rep = double_launch ? 0 : 1; rep < 2; ++rep) {
@@ -197,14 +194,14 @@ int run_graph(idc_context* c, int n, const float* dL, const float* dab, const fl
     }
     if (c->flags & IDC_FLAG_DIST313) {         // bilinear x4 + softmax(S.) + softmax(2.6 .) -> pred_ab decode
         const Tensor& tp = c->tensors[c->t_pred313];
-        HIPCHK(c, launch_dist313((const float*)tp.ptr, (const float*)(c->d_blob + c->plan.pred_ab_off), c->d_pred_ab,
-                                 (c->want_dist313 || c->keep_dist313) ? c->d_dist313 : nullptr, n, c->H, c->W, tp.Cpad,
+        HIPCHK(c, launch_dist313((const float*)tp.ptr, (const float*)(c->d_blob + c->plan.pred_ab_off), c->d_pred_ab.get(),
+                                 (c->want_dist313 || c->keep_dist313) ? c->d_dist313.get() : nullptr, n, c->H, c->W, tp.Cpad,
                                  c->dist_S, 2.6f, s));
     }
     toc();
     c->dist_n = (ddist || ((c->flags & IDC_FLAG_DIST313) && (c->want_dist313 || c->keep_dist313))) ? n : 0;
-    if (dout == c->d_out) c->last_n = n;       // images whose ab map sits in the handle's own d_out (display step source)
-    if (c->profiling == 2) (void)hipEventRecord(c->ev[ring + 1], s);
+    if (dout == c->d_out.get()) c->last_n = n;       // images whose ab map sits in the handle's own d_out (display step source)
+    if (c->profiling == 2) (void)hipEventRecord(c->ev[ring + 1].get(), s);
     if (c->profiling) ++c->prof_count;
     return IDC_OK;
 }
@@ -212,8 +209,8 @@ int run_graph(idc_context* c, int n, const float* dL, const float* dab, const fl
 // A conv_kwave_chain_bf16 workgroup that gave up at its grid barrier (not all workgroups co-resident: a partitioned or shared device) set the pinned
 // flag: the results of the forward that has just been waited for are invalid.  Called after the synchronising points of the blocking entry points.
 int check_chain_abort(idc_context* c) {
-    if (c->h_kw_abort && *c->h_kw_abort) {
-        *c->h_kw_abort = 0;
+    if (c->h_kw_abort.get() && *c->h_kw_abort.get()) {
+        *c->h_kw_abort.get() = 0;
         c->kw_chain_off = true;
         return fail(&c->err, IDC_ERR_INTERNAL, "the persistent trunk launch (conv_kwave_chain_bf16) did not get all its workgroups co-resident and timed "
                     "out: this forward's result is invalid; the handle now runs one launch per layer -- call again");
@@ -235,7 +232,7 @@ hipError_t wait_stream(idc_context* c, int n) {
     const bool spin = options().spin_sync != 0;
     if (spin && n <= 2) {
         for (int i = 0; i < 4000; ++i) {
-            const hipError_t e = hipStreamQuery(c->stream);
+            const hipError_t e = hipStreamQuery(c->stream.get());
             if (e != hipErrorNotReady) return e;
 #if defined(__x86_64__) || defined(__i386__)
             for (int k = 0; k < 40; ++k) __builtin_ia32_pause();
@@ -244,7 +241,7 @@ hipError_t wait_stream(idc_context* c, int n) {
 #endif
         }
     }
-    return hipStreamSynchronize(c->stream);
+    return hipStreamSynchronize(c->stream.get());
 }
 
 // A click's transfers (<= 2 MiB between pinned host memory and HBM) run as a kernel on the forward's stream (pcie_copy_kernel, idc_kernels.hip) instead of
@@ -255,10 +252,10 @@ hipError_t copy_h2d_or_d2h(idc_context* c, void* dev, void* host, size_t bytes, 
     if (by_kernel && bytes <= ((size_t)2 << 20) && bytes % 16 == 0 && (((uintptr_t)dev | (uintptr_t)host) & 15) == 0) {
         void* hv = nullptr;
         if (hipHostGetDevicePointer(&hv, host, 0) == hipSuccess && hv)
-            return to_device ? launch_pcie_copy(dev, hv, bytes, c->stream) : launch_pcie_copy(hv, dev, bytes, c->stream);
+            return to_device ? launch_pcie_copy(dev, hv, bytes, c->stream.get()) : launch_pcie_copy(hv, dev, bytes, c->stream.get());
         (void)hipGetLastError();
     }
-    return to_device ? hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, c->stream) : hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream);
+    return to_device ? hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, c->stream.get()) : hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream.get());
 }
 
 // finish = false: everything is enqueued (the D2H of the ab map into h_out included) but the stream is NOT synchronised and
@@ -285,7 +282,7 @@ static int forward_host(idc_context* c, int n, const float* L_mc, const float* a
     // the handle's pinned staging with a host memcpy (2.2 MB per click through the reference API: most of its host-side time).
     // Staged in pieces (>= 256 KiB, at most four per tensor), each piece's DMA issued as soon as it is in the staging buffer: the copy engine moves piece k
     // while the CPU copies piece k + 1, so a click pays the host memcpy plus ONE piece of DMA instead of memcpy + all of it.
-    float* hL = c->h_in; float* hab = hL + (size_t)n * hw; float* hm = hab + (size_t)n * hw * 2;
+    float* hL = c->h_in.get(); float* hab = hL + (size_t)n * hw; float* hm = hab + (size_t)n * hw * 2;
     auto upload = [&](void* dst, const float* src, float* staging, size_t bytes) -> hipError_t {
         if (is_pinned(src)) return copy_h2d_or_d2h(c, dst, (void*)src, bytes, true);
         size_t piece = (bytes + 3) / 4;
@@ -299,24 +296,24 @@ static int forward_host(idc_context* c, int n, const float* L_mc, const float* a
         }
         return hipSuccess;
     };
-    if (L_mc) HIPCHK(c, upload(c->d_L, L_mc, hL, (size_t)n * hw * 4));
-    HIPCHK(c, upload(c->d_ab, ab, hab, (size_t)n * hw * 2 * 4));
-    HIPCHK(c, upload(c->d_mask, mask, hm, (size_t)n * hw * 4));
-    rc = run_graph(c, n, c->d_L, c->d_ab, c->d_mask, maskcent, c->d_out, (dist_q || keep_dist) ? c->d_dist : nullptr);
+    if (L_mc) HIPCHK(c, upload(c->d_L.get(), L_mc, hL, (size_t)n * hw * 4));
+    HIPCHK(c, upload(c->d_ab.get(), ab, hab, (size_t)n * hw * 2 * 4));
+    HIPCHK(c, upload(c->d_mask.get(), mask, hm, (size_t)n * hw * 4));
+    rc = run_graph(c, n, c->d_L.get(), c->d_ab.get(), c->d_mask.get(), maskcent, c->d_out.get(), (dist_q || keep_dist) ? c->d_dist.get() : nullptr);
     if (rc) return rc;
-    const bool out_direct = copy_out && out_ab != c->h_out && is_pinned(out_ab);
-    c->out_copy_pending = copy_out && out_ab != c->h_out && !out_direct;
+    const bool out_direct = copy_out && out_ab != c->h_out.get() && is_pinned(out_ab);
+    c->out_copy_pending = copy_out && out_ab != c->h_out.get() && !out_direct;
     if (copy_out)          // (copy_out = false: the ab map stays in d_out -- idc_fetch_outputs brings it over when somebody asks)
-        HIPCHK(c, copy_h2d_or_d2h(c, c->d_out, out_direct ? out_ab : c->h_out, (size_t)n * hw * 2 * 4, false));
+        HIPCHK(c, copy_h2d_or_d2h(c, c->d_out.get(), out_direct ? out_ab : c->h_out.get(), (size_t)n * hw * 2 * 4, false));
     const size_t dq = (size_t)n * 529 * (hw / 16) * 4;
-    if (dist_q) HIPCHK(c, hipMemcpyAsync(c->h_dist, c->d_dist, dq, hipMemcpyDeviceToHost, c->stream));
+    if (dist_q) HIPCHK(c, hipMemcpyAsync(c->h_dist.get(), c->d_dist.get(), dq, hipMemcpyDeviceToHost, c->stream.get()));
     if (!finish) return IDC_OK;
     HIPCHK(c, wait_stream(c, n));
     rc = check_chain_abort(c);
     if (rc) return rc;
-    if (c->out_copy_pending) memcpy(out_ab, c->h_out, (size_t)n * hw * 2 * 4);
+    if (c->out_copy_pending) memcpy(out_ab, c->h_out.get(), (size_t)n * hw * 2 * 4);
     c->out_copy_pending = false;
-    if (dist_q) memcpy(dist_q, c->h_dist, dq);
+    if (dist_q) memcpy(dist_q, c->h_dist.get(), dq);
     return IDC_OK;
 }
 
@@ -328,26 +325,24 @@ bool is_pinned(const void* p) {
 }
 
 static int ensure_pipeline(idc_context* h) {
-    if (h->pipe_ready) return IDC_OK;
     const size_t hw = (size_t)h->H * h->W, nb = (size_t)h->max_batch;
-    HIPCHK(h, hipStreamCreateWithFlags(&h->s_in, hipStreamNonBlocking));
-    HIPCHK(h, hipStreamCreateWithFlags(&h->s_out, hipStreamNonBlocking));
-    for (int k = 0; k < 2; ++k) {
-        auto& sl = h->pipe[k];
+    HIPCHK(h, h->s_in.create(hipStreamNonBlocking));
+    HIPCHK(h, h->s_out.create(hipStreamNonBlocking));
+    for (auto& sl : h->pipe) {
         // both slots own their planes (50 MB each at N = 32): nothing here aliases the handle's resident L / hint / output
         // planes, so the copy-in stream never has to be ordered against the compute stream (ordering slot 0's copies behind
         // "everything enqueued so far" serialises them behind the OTHER slot's kernels: measured 0.89 instead of 0.97 of
         // the device-resident rate, profiles/r03a_bench.json)
-        HIPCHK(h, hipMalloc((void**)&sl.d_L, nb * hw * 4));
-        HIPCHK(h, hipMalloc((void**)&sl.d_ab, nb * hw * 2 * 4));
-        HIPCHK(h, hipMalloc((void**)&sl.d_mask, nb * hw * 4));
-        HIPCHK(h, hipMalloc((void**)&sl.d_out, nb * hw * 2 * 4));
+        HIPCHK(h, sl.d_L.ensure(nb * hw * 4));
+        HIPCHK(h, sl.d_ab.ensure(nb * hw * 2 * 4));
+        HIPCHK(h, sl.d_mask.ensure(nb * hw * 4));
+        HIPCHK(h, sl.d_out.ensure(nb * hw * 2 * 4));
         // timing-capable events: idc_pipeline_times reports where each stage of a batch sat on the device's clock
-        hipEvent_t* evs[] = {&sl.ev_in, &sl.ev_comp, &sl.ev_out, &sl.ev_in0, &sl.ev_comp0, &sl.ev_out0};
-        for (hipEvent_t* e : evs) HIPCHK(h, hipEventCreate(e));
+        Event* evs[] = {&sl.ev_in, &sl.ev_comp, &sl.ev_out, &sl.ev_in0, &sl.ev_comp0, &sl.ev_out0};
+        for (Event* e : evs) HIPCHK(h, e->create());
     }
-    HIPCHK(h, hipEventCreate(&h->ev_pipe_base));
-    HIPCHK(h, hipEventRecord(h->ev_pipe_base, h->stream));
+    HIPCHK(h, h->ev_pipe_base.create());
+    if (!h->pipe_ready) HIPCHK(h, hipEventRecord(h->ev_pipe_base.get(), h->stream.get()));
     h->pipe_ready = true;
     return IDC_OK;
 }
@@ -355,11 +350,11 @@ static int ensure_pipeline(idc_context* h) {
 static int wait_slot(idc_context* h, int slot) {
     auto& sl = h->pipe[slot];
     if (!sl.pending) return IDC_OK;
-    HIPCHK(h, hipEventSynchronize(sl.ev_out));
+    HIPCHK(h, hipEventSynchronize(sl.ev_out.get()));
     sl.pending = false;
     const int arc = check_chain_abort(h);      // the forward this slot carried ran a chain launch that gave up: its result is invalid
     if (arc) return arc;
-    if (sl.staged_out) memcpy(sl.user_out, sl.h_out, (size_t)sl.n * h->H * h->W * 2 * 4);
+    if (sl.staged_out) memcpy(sl.user_out, sl.h_out.get(), (size_t)sl.n * h->H * h->W * 2 * 4);
     return IDC_OK;
 }
 
@@ -391,9 +386,9 @@ int idc_forward_device(idc_handle h, int n, const float* d_L_mc, const float* d_
     HIPCHK(h, hipSetDevice(h->device));
     // the result lands in the CALLER's buffer: whatever an earlier forward left in d_out / d_labq is no longer "the last
     // forward's map" (idc_upsample_lab2rgb must not serve it), unless the caller handed the handle's own planes back
-    h->out_resident = d_out_ab == h->d_out;
+    h->out_resident = d_out_ab == h->d_out.get();
     h->labq_resident = false;
-    rc = run_graph(h, n, d_L_mc, d_ab, d_mask, maskcent, d_out_ab, (h->flags & IDC_FLAG_DIST_HEAD) ? h->d_dist : nullptr);
+    rc = run_graph(h, n, d_L_mc, d_ab, d_mask, maskcent, d_out_ab, (h->flags & IDC_FLAG_DIST_HEAD) ? h->d_dist.get() : nullptr);
     if (rc) return rc;
     if (sync) {
         HIPCHK(h, wait_stream(h, n));
@@ -410,11 +405,11 @@ int idc_forward_dist313(idc_handle h, int n, const float* L_mc, const float* ab,
     if (!pred_ab) return fail(&h->err, IDC_ERR_INVALID_ARG, "null pred_ab");
     const size_t hw = (size_t)h->H * h->W;
     h->want_dist313 = dist_S != nullptr;
-    rc = forward_host(h, n, L_mc, ab, mask, maskcent, out_ab ? out_ab : h->h_out, nullptr);
+    rc = forward_host(h, n, L_mc, ab, mask, maskcent, out_ab ? out_ab : h->h_out.get(), nullptr);
     h->want_dist313 = false;
     if (rc) return rc;
-    HIPCHK(h, hipMemcpy(pred_ab, h->d_pred_ab, (size_t)n * hw * 2 * 4, hipMemcpyDeviceToHost));
-    if (dist_S) HIPCHK(h, hipMemcpy(dist_S, h->d_dist313, (size_t)n * hw * 313 * 4, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(pred_ab, h->d_pred_ab.get(), (size_t)n * hw * 2 * 4, hipMemcpyDeviceToHost));
+    if (dist_S) HIPCHK(h, hipMemcpy(dist_S, h->d_dist313.get(), (size_t)n * hw * 313 * 4, hipMemcpyDeviceToHost));
     return IDC_OK;
 }
 
@@ -427,10 +422,10 @@ int idc_forward_rgb(idc_handle h, int n, const float* L_mc, const float* ab, con
     if (rc) return rc;
     // forward (leaves L_mc in d_L and the ab map in d_out), then the colour step on the same stream: ONE synchronisation for
     // both (the ab map travels to the host under the colour kernel instead of behind a sync of its own)
-    rc = forward_host(h, n, L_mc, ab, mask, maskcent, out_ab ? out_ab : h->h_out, nullptr, false, /*finish=*/false);
+    rc = forward_host(h, n, L_mc, ab, mask, maskcent, out_ab ? out_ab : h->h_out.get(), nullptr, false, /*finish=*/false);
     if (rc) return rc;
-    rc = run_lab_post(h, n, h->d_L, l_cent, h->d_out, rgb, lab_q);          // synchronises the stream
-    if (rc == IDC_OK && out_ab && h->out_copy_pending) memcpy(out_ab, h->h_out, (size_t)n * h->H * h->W * 2 * 4);
+    rc = run_lab_post(h, n, h->d_L.get(), l_cent, h->d_out.get(), rgb, lab_q);          // synchronises the stream
+    if (rc == IDC_OK && out_ab && h->out_copy_pending) memcpy(out_ab, h->h_out.get(), (size_t)n * h->H * h->W * 2 * 4);
     h->out_copy_pending = false;
     h->labq_resident = rc == IDC_OK && lab_q != nullptr;
     return rc;
@@ -447,13 +442,13 @@ int idc_forward_rgb_lazy(idc_handle h, int n, const float* L_mc, const float* ab
     rc = forward_host(h, n, L_mc, ab, mask, maskcent, nullptr, nullptr, false, /*finish=*/false, /*copy_out=*/false);
     if (rc) return rc;
     const size_t hw = (size_t)h->H * h->W;
-    HIPCHK(h, launch_lab_post(h->d_L, l_cent, h->d_out, h->d_rgb, h->d_labq, n, h->H, h->W, h->stream));
+    HIPCHK(h, launch_lab_post(h->d_L.get(), l_cent, h->d_out.get(), h->d_rgb.get(), h->d_labq.get(), n, h->H, h->W, h->stream.get()));
     const bool rgb_direct = is_pinned(rgb);
-    HIPCHK(h, copy_h2d_or_d2h(h, h->d_rgb, rgb_direct ? (void*)rgb : (void*)h->h_rgb, (size_t)n * hw * 3, false));
+    HIPCHK(h, copy_h2d_or_d2h(h, h->d_rgb.get(), rgb_direct ? (void*)rgb : (void*)h->h_rgb.get(), (size_t)n * hw * 3, false));
     HIPCHK(h, wait_stream(h, n));
     rc = check_chain_abort(h);
     if (rc) return rc;
-    if (!rgb_direct) memcpy(rgb, h->h_rgb, (size_t)n * hw * 3);
+    if (!rgb_direct) memcpy(rgb, h->h_rgb.get(), (size_t)n * hw * 3);
     h->out_copy_pending = false;
     h->labq_resident = true;
     return IDC_OK;
@@ -468,15 +463,15 @@ int idc_fetch_outputs(idc_handle h, int n, float* out_ab, double* lab_q) {
     HIPCHK(h, hipSetDevice(h->device));
     const size_t hw = (size_t)h->H * h->W;
     const bool ab_direct = out_ab && is_pinned(out_ab), lab_direct = lab_q && is_pinned(lab_q);
-    if (out_ab) HIPCHK(h, copy_h2d_or_d2h(h, h->d_out, ab_direct ? out_ab : h->h_out, (size_t)n * hw * 2 * 4, false));
+    if (out_ab) HIPCHK(h, copy_h2d_or_d2h(h, h->d_out.get(), ab_direct ? out_ab : h->h_out.get(), (size_t)n * hw * 2 * 4, false));
     if (lab_q) {
         int rc = ensure_post_buffers(h);
         if (rc) return rc;
-        HIPCHK(h, copy_h2d_or_d2h(h, h->d_labq, lab_direct ? (void*)lab_q : (void*)h->h_labq, (size_t)n * hw * 3 * 8, false));
+        HIPCHK(h, copy_h2d_or_d2h(h, h->d_labq.get(), lab_direct ? (void*)lab_q : (void*)h->h_labq.get(), (size_t)n * hw * 3 * 8, false));
     }
     HIPCHK(h, wait_stream(h, n));
-    if (out_ab && !ab_direct) memcpy(out_ab, h->h_out, (size_t)n * hw * 2 * 4);
-    if (lab_q && !lab_direct) memcpy(lab_q, h->h_labq, (size_t)n * hw * 3 * 8);
+    if (out_ab && !ab_direct) memcpy(out_ab, h->h_out.get(), (size_t)n * hw * 2 * 4);
+    if (lab_q && !lab_direct) memcpy(lab_q, h->h_labq.get(), (size_t)n * hw * 3 * 8);
     return IDC_OK;
 }
 
@@ -511,28 +506,28 @@ int idc_forward_async(idc_handle h, int slot, int n, const float* L_mc, const fl
     const size_t hw = (size_t)h->H * h->W, nb = (size_t)h->max_batch;
     const float *sL = L_mc, *sab = ab, *sm = mask;
     if (!(is_pinned(L_mc) && is_pinned(ab) && is_pinned(mask))) {
-        if (!sl.h_in) HIPCHK(h, hipHostMalloc((void**)&sl.h_in, nb * hw * 4 * 4, hipHostMallocDefault));
-        float* hL = sl.h_in; float* hab = hL + (size_t)n * hw; float* hm = hab + (size_t)n * hw * 2;
+        HIPCHK(h, sl.h_in.ensure(nb * hw * 4 * 4));
+        float* hL = sl.h_in.get(); float* hab = hL + (size_t)n * hw; float* hm = hab + (size_t)n * hw * 2;
         memcpy(hL, L_mc, (size_t)n * hw * 4); memcpy(hab, ab, (size_t)n * hw * 2 * 4); memcpy(hm, mask, (size_t)n * hw * 4);
         sL = hL; sab = hab; sm = hm;
     }
     sl.staged_out = !is_pinned(out_ab);
-    if (sl.staged_out && !sl.h_out) HIPCHK(h, hipHostMalloc((void**)&sl.h_out, nb * hw * 2 * 4, hipHostMallocDefault));
+    if (sl.staged_out) HIPCHK(h, sl.h_out.ensure(nb * hw * 2 * 4));
     // copy-in stream: the slot's previous inputs were consumed (its previous forward finished: idc_wait was called)
-    HIPCHK(h, hipEventRecord(sl.ev_in0, h->s_in));
-    HIPCHK(h, hipMemcpyAsync(sl.d_L, sL, (size_t)n * hw * 4, hipMemcpyHostToDevice, h->s_in));
-    HIPCHK(h, hipMemcpyAsync(sl.d_ab, sab, (size_t)n * hw * 2 * 4, hipMemcpyHostToDevice, h->s_in));
-    HIPCHK(h, hipMemcpyAsync(sl.d_mask, sm, (size_t)n * hw * 4, hipMemcpyHostToDevice, h->s_in));
-    HIPCHK(h, hipEventRecord(sl.ev_in, h->s_in));
-    HIPCHK(h, hipStreamWaitEvent(h->stream, sl.ev_in, 0));
-    HIPCHK(h, hipEventRecord(sl.ev_comp0, h->stream));
-    rc = run_graph(h, n, sl.d_L, sl.d_ab, sl.d_mask, maskcent, sl.d_out, nullptr);
+    HIPCHK(h, hipEventRecord(sl.ev_in0.get(), h->s_in.get()));
+    HIPCHK(h, hipMemcpyAsync(sl.d_L.get(), sL, (size_t)n * hw * 4, hipMemcpyHostToDevice, h->s_in.get()));
+    HIPCHK(h, hipMemcpyAsync(sl.d_ab.get(), sab, (size_t)n * hw * 2 * 4, hipMemcpyHostToDevice, h->s_in.get()));
+    HIPCHK(h, hipMemcpyAsync(sl.d_mask.get(), sm, (size_t)n * hw * 4, hipMemcpyHostToDevice, h->s_in.get()));
+    HIPCHK(h, hipEventRecord(sl.ev_in.get(), h->s_in.get()));
+    HIPCHK(h, hipStreamWaitEvent(h->stream.get(), sl.ev_in.get(), 0));
+    HIPCHK(h, hipEventRecord(sl.ev_comp0.get(), h->stream.get()));
+    rc = run_graph(h, n, sl.d_L.get(), sl.d_ab.get(), sl.d_mask.get(), maskcent, sl.d_out.get(), nullptr);
     if (rc) return rc;
-    HIPCHK(h, hipEventRecord(sl.ev_comp, h->stream));
-    HIPCHK(h, hipStreamWaitEvent(h->s_out, sl.ev_comp, 0));
-    HIPCHK(h, hipEventRecord(sl.ev_out0, h->s_out));
-    HIPCHK(h, hipMemcpyAsync(sl.staged_out ? sl.h_out : out_ab, sl.d_out, (size_t)n * hw * 2 * 4, hipMemcpyDeviceToHost, h->s_out));
-    HIPCHK(h, hipEventRecord(sl.ev_out, h->s_out));
+    HIPCHK(h, hipEventRecord(sl.ev_comp.get(), h->stream.get()));
+    HIPCHK(h, hipStreamWaitEvent(h->s_out.get(), sl.ev_comp.get(), 0));
+    HIPCHK(h, hipEventRecord(sl.ev_out0.get(), h->s_out.get()));
+    HIPCHK(h, hipMemcpyAsync(sl.staged_out ? sl.h_out.get() : out_ab, sl.d_out.get(), (size_t)n * hw * 2 * 4, hipMemcpyDeviceToHost, h->s_out.get()));
+    HIPCHK(h, hipEventRecord(sl.ev_out.get(), h->s_out.get()));
     sl.pending = true; sl.timed = true; sl.user_out = out_ab; sl.n = n;
     return IDC_OK;
 }
@@ -552,14 +547,14 @@ int idc_pipeline_times(idc_handle h, int slot, float* ms6) {
     auto& sl = h->pipe[slot];
     if (sl.pending) return fail(&h->err, IDC_ERR_INVALID_ARG, "slot %d is still in flight: idc_wait it first", slot);
     HIPCHK(h, hipSetDevice(h->device));
-    hipEvent_t evs[6] = {sl.ev_in0, sl.ev_in, sl.ev_comp0, sl.ev_comp, sl.ev_out0, sl.ev_out};
-    for (int i = 0; i < 6; ++i) HIPCHK(h, hipEventElapsedTime(&ms6[i], h->ev_pipe_base, evs[i]));
+    hipEvent_t evs[6] = {sl.ev_in0.get(), sl.ev_in.get(), sl.ev_comp0.get(), sl.ev_comp.get(), sl.ev_out0.get(), sl.ev_out.get()};
+    for (int i = 0; i < 6; ++i) HIPCHK(h, hipEventElapsedTime(&ms6[i], h->ev_pipe_base.get(), evs[i]));
     return IDC_OK;
 }
 
 int idc_sync(idc_handle h) {
     if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
     return check_chain_abort(h);
 }
 

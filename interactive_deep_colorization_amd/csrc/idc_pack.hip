@@ -535,6 +535,13 @@ int verify_device_blob(idc_context* h, const void* dev_blob, size_t blob_bytes) 
     return IDC_OK;
 }
 
+int own_blob_storage(idc_context* h) {
+    const hipError_t e = h->blob_mem.ensure(h->plan.total_bytes);
+    h->d_blob = h->blob_mem.get();
+    HIPCHK(h, e);
+    return IDC_OK;
+}
+
 }  // namespace idc
 
 extern "C" {
@@ -559,12 +566,9 @@ int idc_set_weights_host(idc_handle h, const void* blob, size_t blob_bytes) {
     if (fnv1a((const uint8_t*)blob + sizeof(hd), h->plan.total_bytes - sizeof(hd)) != hd.checksum)
         return fail(&h->err, IDC_ERR_INVALID_ARG, "blob checksum mismatch");
     HIPCHK(h, hipSetDevice(h->device));
-    if (!h->own_blob || !h->d_blob) {
-        h->d_blob = nullptr;
-        HIPCHK(h, hipMalloc((void**)&h->d_blob, h->plan.total_bytes));
-        h->own_blob = true;
-    }
-    HIPCHK(h, hipMemcpy(h->d_blob, blob, h->plan.total_bytes, hipMemcpyHostToDevice));
+    rc = own_blob_storage(h);
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpy(h->blob_mem.get(), blob, h->plan.total_bytes, hipMemcpyHostToDevice));
     cache_blob_meta(h, (const uint8_t*)blob);
     h->weights_set = true;
     return IDC_OK;
@@ -576,16 +580,12 @@ int idc_set_weights_device(idc_handle h, const void* dev_blob, size_t blob_bytes
     int rc = verify_device_blob(h, dev_blob, blob_bytes);
     if (rc) return rc;
     if (copy) {
-        if (!h->own_blob || !h->d_blob) {
-            h->d_blob = nullptr;
-            HIPCHK(h, hipMalloc((void**)&h->d_blob, h->plan.total_bytes));
-            h->own_blob = true;
-        }
-        HIPCHK(h, hipMemcpy(h->d_blob, dev_blob, h->plan.total_bytes, hipMemcpyDeviceToDevice));
+        rc = own_blob_storage(h);
+        if (rc) return rc;
+        HIPCHK(h, hipMemcpy(h->blob_mem.get(), dev_blob, h->plan.total_bytes, hipMemcpyDeviceToDevice));
     } else {
-        if (h->own_blob && h->d_blob) (void)hipFree(h->d_blob);
-        h->d_blob = (uint8_t*)dev_blob;
-        h->own_blob = false;
+        h->blob_mem.reset();
+        h->d_blob = (const uint8_t*)dev_blob;
     }
     h->weights_set = true;
     return IDC_OK;

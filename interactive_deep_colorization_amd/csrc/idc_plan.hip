@@ -525,53 +525,57 @@ int alloc_graph(idc_context* c) {
         const size_t al = (size_t)2 << 20;
         size_t total = 0;
         for (auto& t : c->tensors) total += align_up(t.bytes, al);
-        HIPCHK(c, hipMalloc(&c->d_arena, total));
+        HIPCHK(c, c->d_arena.ensure(total));
         size_t off = 0;
-        for (auto& t : c->tensors) { t.ptr = (char*)c->d_arena + off; off += align_up(t.bytes, al); }
+        for (auto& t : c->tensors) { t.ptr = (char*)c->d_arena.get() + off; off += align_up(t.bytes, al); }
     } else {
-        for (auto& t : c->tensors) HIPCHK(c, hipMalloc(&t.ptr, t.bytes));
+        c->tensor_mem.resize(c->tensors.size());
+        for (size_t i = 0; i < c->tensors.size(); ++i) {
+            HIPCHK(c, c->tensor_mem[i].ensure(c->tensors[i].bytes));
+            c->tensors[i].ptr = c->tensor_mem[i].get();
+        }
     }
     const size_t hw = (size_t)c->H * c->W, nb = (size_t)c->max_batch;
-    HIPCHK(c, hipMalloc((void**)&c->d_L, nb * hw * 4));
-    HIPCHK(c, hipMalloc((void**)&c->d_ab, nb * hw * 2 * 4));
-    HIPCHK(c, hipMalloc((void**)&c->d_mask, nb * hw * 4));
-    HIPCHK(c, hipMalloc((void**)&c->d_out, nb * hw * 2 * 4));
+    HIPCHK(c, c->d_L.ensure(nb * hw * 4));
+    HIPCHK(c, c->d_ab.ensure(nb * hw * 2 * 4));
+    HIPCHK(c, c->d_mask.ensure(nb * hw * 4));
+    HIPCHK(c, c->d_out.ensure(nb * hw * 2 * 4));
     // resident planes start defined: no hints (ab = 0, mask = 0); an L plane has to be uploaded before a resident forward
-    HIPCHK(c, hipMemset(c->d_L, 0, nb * hw * 4));
-    HIPCHK(c, hipMemset(c->d_ab, 0, nb * hw * 2 * 4));
-    HIPCHK(c, hipMemset(c->d_mask, 0, nb * hw * 4));
-    HIPCHK(c, hipMemset(c->d_out, 0, nb * hw * 2 * 4));
+    HIPCHK(c, hipMemset(c->d_L.get(), 0, nb * hw * 4));
+    HIPCHK(c, hipMemset(c->d_ab.get(), 0, nb * hw * 2 * 4));
+    HIPCHK(c, hipMemset(c->d_mask.get(), 0, nb * hw * 4));
+    HIPCHK(c, hipMemset(c->d_out.get(), 0, nb * hw * 2 * 4));
     c->l_set.assign(nb, 0);
-    c->src.assign(nb, idc_context::SlotSource());
+    c->src.resize(nb);
     c->hint_mask_value.assign(nb, 0.f);
-    HIPCHK(c, hipMalloc(&c->d_zeros, 256));
-    HIPCHK(c, hipMemset(c->d_zeros, 0, 256));
+    HIPCHK(c, c->d_zeros.ensure(256));
+    HIPCHK(c, hipMemset(c->d_zeros.get(), 0, 256));
     if (c->precision == IDC_BF16) {              // conv_kwave_chain_bf16's grid-barrier counter and its host-visible abort flag
-        HIPCHK(c, hipMalloc((void**)&c->d_kw_bar, 1024));
-        HIPCHK(c, hipMemset(c->d_kw_bar, 0, 1024));
-        HIPCHK(c, hipHostMalloc((void**)&c->h_kw_abort, 64, hipHostMallocMapped));
-        *c->h_kw_abort = 0;
+        HIPCHK(c, c->d_kw_bar.ensure(1024));
+        HIPCHK(c, hipMemset(c->d_kw_bar.get(), 0, 1024));
+        HIPCHK(c, c->h_kw_abort.ensure(64));
+        *c->h_kw_abort.get() = 0;
     }
     // the memsets above run on the NULL stream, the kernels on the handle's non-blocking stream: every conv launch reads the
     // zero page (out-of-image halo rows), so make the fills complete before the handle can launch anything
     HIPCHK(c, hipStreamSynchronize(nullptr));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_sync, hipEventDisableTiming));
-    HIPCHK(c, hipHostMalloc((void**)&c->h_in, nb * hw * 4 * 4, hipHostMallocDefault));
-    HIPCHK(c, hipHostMalloc((void**)&c->h_out, nb * hw * 2 * 4, hipHostMallocDefault));
+    HIPCHK(c, c->ev_sync.create(hipEventDisableTiming));
+    HIPCHK(c, c->h_in.ensure(nb * hw * 4 * 4));
+    HIPCHK(c, c->h_out.ensure(nb * hw * 2 * 4));
     if (c->flags & IDC_FLAG_DIST_HEAD) {
         const size_t dq = nb * 529 * (hw / 16) * 4;
-        HIPCHK(c, hipMalloc((void**)&c->d_dist, dq));
-        HIPCHK(c, hipHostMalloc((void**)&c->h_dist, dq, hipHostMallocDefault));
+        HIPCHK(c, c->d_dist.ensure(dq));
+        HIPCHK(c, c->h_dist.ensure(dq));
     }
     if (c->flags & IDC_FLAG_DIST313) {
-        HIPCHK(c, hipMalloc((void**)&c->d_pred_ab, nb * hw * 2 * 4));
-        HIPCHK(c, hipHostMalloc((void**)&c->h_pred_ab, nb * hw * 2 * 4, hipHostMallocDefault));
-        HIPCHK(c, hipMalloc((void**)&c->d_dist313, nb * hw * 313 * 4));      // 82 MB per 256x256 image: sized for 288 GB parts
+        HIPCHK(c, c->d_pred_ab.ensure(nb * hw * 2 * 4));
+        HIPCHK(c, c->h_pred_ab.ensure(nb * hw * 2 * 4));
+        HIPCHK(c, c->d_dist313.ensure(nb * hw * 313 * 4));      // 82 MB per 256x256 image: sized for 288 GB parts
     }
     if (c->flags & IDC_FLAG_GLOBAL_HINTS) {
-        HIPCHK(c, hipMalloc((void**)&c->d_glob_in, nb * kGlobIn * 4));
-        HIPCHK(c, hipMalloc((void**)&c->d_glob_vec, nb * kGlobC * 4));
-        HIPCHK(c, hipMemset(c->d_glob_in, 0, nb * kGlobIn * 4));
+        HIPCHK(c, c->d_glob_in.ensure(nb * kGlobIn * 4));
+        HIPCHK(c, c->d_glob_vec.ensure(nb * kGlobC * 4));
+        HIPCHK(c, hipMemset(c->d_glob_in.get(), 0, nb * kGlobIn * 4));
     }
     c->n_timed = (int)c->layers.size() + 3;           // profiling events (2240 per handle) are created by idc_set_profiling, not here:
     return IDC_OK;                                    // a process holding many handles must not exhaust the runtime's signal pool

@@ -100,18 +100,17 @@ int idc_broadcast_weights(idc_handle h, const void* unique_id, int rank, int wor
     Rccl* r = rccl();
     if (!r) return fail(&h->err, IDC_ERR_UNSUPPORTED, "%s", rccl_where().c_str());
     HIPCHK(h, hipSetDevice(h->device));
-    if (rank != root && (!h->own_blob || !h->d_blob)) {
-        h->d_blob = nullptr;
-        HIPCHK(h, hipMalloc((void**)&h->d_blob, h->plan.total_bytes));
-        h->own_blob = true;
+    if (rank != root) {
+        int rc = own_blob_storage(h);
+        if (rc) return rc;
     }
     IdcNcclId id;
     memcpy(&id, unique_id, sizeof(id));
     void* comm = nullptr;
     int e = r->CommInitRank(&comm, world, id, rank);
     if (e != 0) return fail(&h->err, IDC_ERR_HIP, "ncclCommInitRank failed: %s (%s)", r->GetErrorString ? r->GetErrorString(e) : "?", rccl_where().c_str());
-    e = r->Broadcast(h->d_blob, h->d_blob, h->plan.total_bytes, /*ncclUint8*/ 1, root, comm, h->stream);
-    hipError_t he = hipStreamSynchronize(h->stream);
+    e = r->Broadcast(h->d_blob, (void*)h->d_blob, h->plan.total_bytes, /*ncclUint8*/ 1, root, comm, h->stream.get());
+    hipError_t he = hipStreamSynchronize(h->stream.get());
     (void)r->CommDestroy(comm);
     if (e != 0) return fail(&h->err, IDC_ERR_HIP, "ncclBroadcast failed: %s (%s)", r->GetErrorString ? r->GetErrorString(e) : "?", rccl_where().c_str());
     if (he != hipSuccess) return fail(&h->err, IDC_ERR_HIP, "stream sync after ncclBroadcast: %s", hipGetErrorString(he));
