@@ -33,9 +33,10 @@ of up to 2.0 (bf16), 0.25 (fp16), 7.9e-3 (bf16x3), 1.2e-4 (fp16x3) and 3.1e-5 (b
 Exact: want_dist=False gives the same pred_ab bits, image 0 of a batch equals the same image alone, probabilities sum to 1 within 529 * 2^-24
 (measured 3.4e-7 at most).
 
-Not covered, on purpose: the head fused into conv10_2's epilogue ('+head' labels: its input is never stored; every operand-split forward
-and the large-tile bf16 one take it), and the partner tile's shift (conv_igemm_v2 without +m16: -DIDC_AB_PARTNERS builds only).  Every
-other row of the table is reached by a shipped configuration.
+Not covered here: the head fused into conv10_2's epilogue ('+head' labels: conv10_2 is never stored; every operand-split forward and the
+large-tile bf16 one take it) -- tests/test_fused_head_gpu.py holds it against float64 from the stored conv10_1, one layer earlier; and, on
+purpose, the partner tile's shift (conv_igemm_v2 without +m16: -DIDC_AB_PARTNERS builds only).  Every other row of the table is reached by a
+shipped configuration.
 
 Wall time of this file on an MI355X: 9.1 s for its 42 cases (16 handles at 40 x 72 and 16 x 24 and the four 256 x 256 census handles);
 the slowest case takes 1.8 s (the first one: it draws the weights), every case after the first of a handle a few hundredths of a second.

@@ -156,18 +156,19 @@ def test_exact(c):
 
 # ---- census: what the shipped configurations launch is what the table reaches -----------------------------------------------------------
 SHIPPED = [(32, "bf16"), (32, "fp16x3"), (1, "bf16"), (1, "fp32")]          # 256 x 256: (max_batch, precision)
-# kernels no exact case can reach, each with the test that covers it: model1's kernels and the fused head end in conv1's input pack /
-# the tanh, and the persistent trunk chain is a launch of several layers
+# kernels no exact case HERE can reach, each with the test that covers it: model1's kernels start from conv1's input pack (exact through a
+# forward: tests/test_model1_exact_gpu.py), the fused head ends in the tanh (tests/test_fused_head_gpu.py), and the persistent trunk chain is a
+# launch of several layers
 CENSUS_EXCEPTIONS = {
-    "conv1_block_fused": "tests/test_net_gpu.py::test_conv1_1_throughput_kernel",
-    "conv1_1_bf16_kernel": "tests/test_net_gpu.py::test_conv1_1_throughput_kernel",
-    "conv1_1_split_kernel": "tests/test_round6_gpu.py::test_conv1_1_split_kernel_against_the_generic_island",
-    "conv1_2_split_kernel": "tests/test_round6_gpu.py::test_conv1_2_split_kernel_against_the_generic_tile",
+    "conv1_block_fused": "tests/test_model1_exact_gpu.py::test_model1_exact (bit for bit, through a forward; rows *_block_32x12, *_block_32x8)",
+    "conv1_1_bf16_kernel": "tests/test_model1_exact_gpu.py::test_model1_exact[bf16_conv1_1_partner]",
+    "conv1_1_split_kernel": "tests/test_model1_exact_gpu.py::test_model1_exact (rows *_split_pair)",
+    "conv1_2_split_kernel": "tests/test_model1_exact_gpu.py::test_model1_exact (rows *_split_pair)",
     "conv_kwave_chain_bf16": "tests/test_round5_gpu.py::test_kwave_chain_equals_the_eleven_launches (each of its layers is conv_kwave_bf16, 8 chunks: in the table)",
 }
 CENSUS_EXCEPTION_LAYERS = {
     # conv1_1 outside model1's fused kernels: conv_igemm / conv_click reading the fused input pack (K = 36 im2col), which no op entry stages
-    "conv1_1": "tests/test_net_gpu.py::test_fp32_matches_reference_golden_layer_by_layer",
+    "conv1_1": "tests/test_model1_exact_gpu.py::test_model1_exact (rows fp32_batch1 / 3 / 24, bf16_batch1 / 3, bf16_unfused)",
 }
 
 
