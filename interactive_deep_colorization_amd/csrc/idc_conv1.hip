@@ -8,14 +8,13 @@
 #include "idc_layout.h"
 
 #include "idc_common.hip.h"
-#include "idc_split.hip.h"
 
 namespace idc {
 
 // one 32x32x16 MFMA step on two 16-byte fragments: bf16 or fp16 operands, fp32 accumulate
 template <bool F16>
 __device__ __forceinline__ f32x16 mma_32x32x16(const u32x4& w, const u32x4& x, const f32x16& c) {
-    if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_m, w), __builtin_bit_cast(f16x8_m, x), c, 0, 0, 0);
+    if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, x), c, 0, 0, 0);
     else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), c, 0, 0, 0);
 }
 
@@ -251,7 +250,7 @@ __device__ __forceinline__ void conv1_block_body(const ConvArgs& a) {
             const int idx = tid + j * NT;
             uint2 c = uint2{0u, 0u};
             if (ok[j])
-                c = uint2{pack16x2_m<F16>(vl[j] / a.pk_ldiv, va[j] / a.pk_abdiv), pack16x2_m<F16>(vb[j] / a.pk_abdiv, vm[j] * a.pk_mmul - a.pk_mcent)};
+                c = uint2{pack16x2<F16>(vl[j] / a.pk_ldiv, va[j] / a.pk_abdiv), pack16x2<F16>(vb[j] / a.pk_abdiv, vm[j] * a.pk_mmul - a.pk_mcent)};
             if (idx < PW * PH) patch[idx] = c;
         }
     }
@@ -308,7 +307,7 @@ __device__ __forceinline__ void conv1_block_body(const ConvArgs& a) {
                     unsigned pk[8];
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
-                        pk[e] = pack16x2_m<F16>(c1[mi][2 * e], c1[mi][2 * e + 1]);
+                        pk[e] = pack16x2<F16>(c1[mi][2 * e], c1[mi][2 * e + 1]);
                         if (a.act == 1)
                             pk[e] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, pk[e]), s16x2{0, 0}));
                         if (!inimg) pk[e] = 0u;
@@ -475,8 +474,7 @@ __device__ __forceinline__ void conv1_block_body(const ConvArgs& a) {
                 bsh[mi][q * 4 + 0] = t4.x; bsh[mi][q * 4 + 1] = t4.y; bsh[mi][q * 4 + 2] = t4.z; bsh[mi][q * 4 + 3] = t4.w;
             }
     }
-    // (as conv_igemm_v2p's epilogue, round 5: one body per BN setting chosen once -- a run-time `if` per element was a uniform branch per packed pair --,
-    //  a row's four transposed lines read BEFORE the first store's bounds check, one 64-bit base per lane with 32-bit strides)
+    // one body per BN setting, chosen once (a run-time `if` per element was a uniform branch per packed pair); one 64-bit base per lane, 32-bit strides
     unsigned short* const out00 = (unsigned short*)a.out + (((size_t)n * Hs + ty0 + wave * RPW) * Ws + tx0 + rr) * CoutPad + cc * 8;
     auto rows = [&](auto bn_c) __attribute__((always_inline)) {
         constexpr bool BN = decltype(bn_c)::value;
@@ -489,22 +487,15 @@ __device__ __forceinline__ void conv1_block_body(const ConvArgs& a) {
                 for (int e = 0; e < 8; ++e) {
                     float v0 = fmaxf(acc[mi][pj][2 * e], 0.f), v1 = fmaxf(acc[mi][pj][2 * e + 1], 0.f);
                     if constexpr (BN) { v0 = fmaf(v0, bsc[mi][2 * e], bsh[mi][2 * e]); v1 = fmaf(v1, bsc[mi][2 * e + 1], bsh[mi][2 * e + 1]); }
-                    pk[e] = pack16x2_m<F16>(v0, v1);
+                    pk[e] = pack16x2<F16>(v0, v1);
                 }
-                const int s0 = h * 4 + mi * 2;
-                *(uint4*)(tb16 + px * 128 + ((s0 ^ (px & 7)) * 16)) = uint4{pk[0], pk[1], pk[2], pk[3]};
-                *(uint4*)(tb16 + px * 128 + (((s0 + 1) ^ (px & 7)) * 16)) = uint4{pk[4], pk[5], pk[6], pk[7]};
+                tile_write16(tb16, px, h * 4 + mi * 2, pk);
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             const int sy = ty0 + wave * RPW + pj;
-            auto line = [&](int i) { const int row = i * 8 + rr; return *(const uint4*)(tb16 + row * 128 + ((cc ^ (row & 7)) * 16)); };
-            const uint4 o0 = line(0), o1 = line(1), o2 = line(2), o3 = line(3);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            auto put = [&](int i, const uint4& o) {
+            tile_store_lines(tb16, rr, cc, [&](int i, const uint4& o) {
                 const int sx = tx0 + i * 8 + rr;
                 if (sy < Hs && sx < Ws) *(uint4*)(out00 + (pj * Ws + i * 8) * CoutPad) = o;
-            };
-            put(0, o0); put(1, o1); put(2, o2); put(3, o3);
+            });
         }
     };
     if (has_bn) rows(std::true_type{}); else rows(std::false_type{});
@@ -772,7 +763,7 @@ __global__ __launch_bounds__(256, 2) void conv1_2_split_kernel(const ConvArgs a)
             for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
                 for (int pj = 0; pj < RPW; ++pj) {
-                    if constexpr (F16) acc[mi][pj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_m, wf[mi]), __builtin_bit_cast(f16x8_m, xf[pj]), acc[mi][pj], 0, 0, 0);
+                    if constexpr (F16) acc[mi][pj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wf[mi]), __builtin_bit_cast(f16x8, xf[pj]), acc[mi][pj], 0, 0, 0);
                     else acc[mi][pj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wf[mi]), __builtin_bit_cast(bf16x8, xf[pj]), acc[mi][pj], 0, 0, 0);
                 }
         };
@@ -842,7 +833,7 @@ __global__ __launch_bounds__(256, 2) void conv1_2_split_kernel(const ConvArgs a)
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     if constexpr (F16) {
-                        const unsigned q = pack_f16x2_m(v[mi][2 * e], v[mi][2 * e + 1]);
+                        const unsigned q = pack_f16x2(v[mi][2 * e], v[mi][2 * e + 1]);
                         pk[e] = q;
                         v[mi][2 * e] -= f16_lo_to_f32(q); v[mi][2 * e + 1] -= f16_hi_to_f32(q);
                     } else {
@@ -851,20 +842,13 @@ __global__ __launch_bounds__(256, 2) void conv1_2_split_kernel(const ConvArgs a)
                         v[mi][2 * e] -= __uint_as_float(q << 16); v[mi][2 * e + 1] -= __uint_as_float(q & 0xffff0000u);
                     }
                 }
-                const int s0 = h * 4 + mi * 2;
-                *(uint4*)(tb16 + px * 128 + ((s0 ^ (px & 7)) * 16)) = uint4{pk[0], pk[1], pk[2], pk[3]};
-                *(uint4*)(tb16 + px * 128 + (((s0 + 1) ^ (px & 7)) * 16)) = uint4{pk[4], pk[5], pk[6], pk[7]};
+                tile_write16(tb16, px, h * 4 + mi * 2, pk);
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            auto line = [&](int i) { const int row = i * 8 + rr; return *(const uint4*)(tb16 + row * 128 + ((cc ^ (row & 7)) * 16)); };
-            const uint4 o0 = line(0), o1 = line(1), o2 = line(2), o3 = line(3);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            auto put = [&](int i, const uint4& o) {
+            tile_store_lines(tb16, rr, cc, [&](int i, const uint4& o) {
                 const int sx = tx0 + i * 8 + rr;
                 if (sy < Hs && sx < Ws)
                     *(uint4*)((unsigned short*)a.out + ((((size_t)n * Hs + sy) * Ws + sx) * onp + p) * CoutPad + cc * 8) = o;
-            };
-            put(0, o0); put(1, o1); put(2, o2); put(3, o3);
+            });
         }
     }
 }

@@ -24,33 +24,9 @@
 #include "idc_kernels.h"
 
 #include "idc_layout.h"
-#include "idc_split.hip.h"
+#include "idc_common.hip.h"
 
 namespace idc {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_d;
-
-#ifdef IDC_TIMING
-extern __device__ long long* g_idc_dbg;
-#define IDC_DSTAMP(i) do { if (tid == 0) g_idc_dbg[(size_t)blockIdx.x * 16 + (i)] = (long long)__builtin_readcyclecounter(); } while (0)
-#else
-#define IDC_DSTAMP(i) do {} while (0)
-#endif
-
-__device__ __forceinline__ int xcd_remap_d(int b, int nb) {
-    const int xcd = b & 7, q = nb >> 3, r = nb & 7;
-    const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + (b >> 3);
-}
-
-__device__ __forceinline__ unsigned pack_bf16x2_d(float lo, float hi) {
-    // one v_cvt_pk_bf16_f32 (RNE) as a VECTOR conversion: from `(__bf16)lo | (__bf16)hi << 16` the vectoriser pairs the conversions of NEIGHBOURING packs
-    // and un-shuffles them with and / shift / two SDWA ors -- six instructions for two dwords instead of two (round 5: the epilogues are VALU-bound).
-    // (Not inline asm: the hazard recogniser does not see an asm's reads of MFMA results, and the scheduler may move it next to the MFMAs.)
-    typedef float f32x2_pk __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2_pk __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_pk){lo, hi}, bf16x2_pk));
-}
 
 // NCW = cout waves per workgroup.  2: the tile of the N = 32 forward (128 couts, 8 waves).  1 (round 5, the batch-1 click path): 64 couts, four waves =
 // the four phases -- model10up + shortcut at 256x256 is 128 tiles of 64 x 8 output pixels, i.e. HALF the chip with 128-cout workgroups; with 64 couts per
@@ -89,7 +65,7 @@ __device__ __forceinline__ void conv_ds_fused_m_body(const ConvArgs& a) {
     const int r16 = lane & 15, g16 = lane >> 4;
     const int Hs = a.Hs, Ws = a.Ws;                            // deconv input (= site) resolution; output is 2x
     const int ntx = (Ws + 31) >> 5, nty = (Hs + 3) >> 2, nct = a.ncg / NCW;
-    int b = xcd_remap_d(blockIdx.x, gridDim.x);
+    int b = xcd_remap(blockIdx.x, gridDim.x);
     const int ct = b % nct; b /= nct;
     const int txi = b % ntx; b /= ntx;
     const int tyi = b % nty;
@@ -108,7 +84,7 @@ __device__ __forceinline__ void conv_ds_fused_m_body(const ConvArgs& a) {
     // halo rows come through buffer loads: 32-bit offsets into one image, the bounds check returns zeros for out-of-image rows (offset 2^31)
     const __amdgpu_buffer_rsrc_t rsS = __builtin_amdgcn_make_buffer_rsrc((void*)imgS, 0, 4 * Hs * Ws * pixS, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsD = __builtin_amdgcn_make_buffer_rsrc((void*)imgD, 0, Hs * Ws * pixD, 0x00020000);
-    IDC_DSTAMP(0);
+    IDC_STAMP(0);
 
     // accumulators start at the (summed) bias: lane (site r16, group g16) register j of acc[mi][.] is cout g16*16 + mi*4 + j
     f32x4 acc[4][8];
@@ -267,7 +243,7 @@ __device__ __forceinline__ void conv_ds_fused_m_body(const ConvArgs& a) {
     set_xs(0, 0, 4);
     asm volatile("s_waitcnt vmcnt(2)" ::: "memory");           // my pieces of tile 0 (tile 1 may still be in flight); 4-wave form: the halo pieces are older still
     __syncthreads();                                           // halo chunk 0 and tile 0 are visible
-    IDC_DSTAMP(1);
+    IDC_STAMP(1);
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi) read_a1(ringS, wrowS, 0, mi);
     read_b(xs, 0, 0, xlo);
@@ -339,7 +315,7 @@ __device__ __forceinline__ void conv_ds_fused_m_body(const ConvArgs& a) {
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the trailing zero-page requests target LDS the D part reuses
     // ---------------------------------------------------------------- hand-over: the D part reuses the whole LDS
-    IDC_DSTAMP(8);
+    IDC_STAMP(8);
     const int* const tdy = a.dy + ph * 9;
     const int* const tdx = a.dx + ph * 9;
     const int* const ttw = a.tw + ph * 9;
@@ -366,7 +342,7 @@ __device__ __forceinline__ void conv_ds_fused_m_body(const ConvArgs& a) {
     set_xa(__builtin_amdgcn_readlane(v_xoff, 0));
     asm volatile("s_waitcnt vmcnt(8)" ::: "memory");           // tile 0 landed (tile 1 may still be in flight)
     __syncthreads();                                           // halo chunk 0 visible
-    IDC_DSTAMP(9);
+    IDC_STAMP(9);
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi) read_a1(ringD, wrowD, 0, mi);
     read_b(xa, 0, 0, xlo);
@@ -446,60 +422,44 @@ __device__ __forceinline__ void conv_ds_fused_m_body(const ConvArgs& a) {
 #undef IDC_DSM_STAGE_A
 #undef IDC_DSM_STAGE_B
     // ---------------------------------------------------------------- epilogue: (ReLU,) round, transpose, whole-line stores
-    IDC_DSTAMP(2);
+    IDC_STAMP(2);
     __syncthreads();
     if constexpr (SPLIT != 0) {
         add_bias_after_k(a.bias + (cg0 + wco) * kCoutGroup + g16 * 16, acc, a.acc_scale);
         split_epilogue<NCW, SPLIT == 2>(a, acc, smem, n, y0, x0, 0, (cg0 + wco) * kCoutGroup, ro, cof);
-        IDC_DSTAMP(3);
+        IDC_STAMP(3);
         return;
     }
-    char* const tb16 = smem + wave * 4096;                     // wave-private [32 sites][64 couts] bf16, 128-byte rows, slot ^ (site & 7)
-    typedef short s16x2 __attribute__((ext_vector_type(2)));
+    char* const tb16 = smem + wave * 4096;
     const int rr = lane >> 3, cc = lane & 7;
     const int CoutPad = ncg * kCoutGroup;
     const int co8 = (cg0 + wco) * kCoutGroup + cc * 8;
     const int Wout = 2 * Ws, Hout = 2 * Hs;
-    // (as conv_igemm_v2p's epilogue, round 5: one body per ReLU setting chosen once, the row's four transposed lines read BEFORE the first store's
-    //  bounds check -- the compiler sank each read under its store -- and one 64-bit base per lane with 32-bit strides)
+    // one body per ReLU setting, chosen once; one 64-bit base per lane (its line of the wave's first output row), 32-bit strides
     unsigned short* const out00 = (unsigned short*)a.out + (((size_t)n * Hout + (2 * y0 + ro)) * Wout + (2 * (x0 + rr) + cof)) * CoutPad + co8;
+    const f32x4 no_bn[4] = {};
     auto rows = [&](auto relu_c) __attribute__((always_inline)) {
         constexpr bool RELU = decltype(relu_c)::value;
 #pragma unroll
         for (int pj = 0; pj < 4; ++pj) {
 #pragma unroll
             for (int hf = 0; hf < 2; ++hf) {
-                const int pt = pj * 2 + hf, site = hf * 16 + r16;
                 unsigned pk[8];
-#pragma unroll
-                for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) {
-                        unsigned p = pack16x2_m<F16>(acc[mi][pt][2 * e], acc[mi][pt][2 * e + 1]);
-                        if constexpr (RELU) p = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, p), s16x2{0, 0}));
-                        pk[mi * 2 + e] = p;
-                    }
-                const int s0 = g16 * 2;                         // the lane's 16 couts = slots 2g, 2g+1 of the site's 128-byte row
-                *(uint4*)(tb16 + site * 128 + ((s0 ^ (site & 7)) * 16)) = uint4{pk[0], pk[1], pk[2], pk[3]};
-                *(uint4*)(tb16 + site * 128 + (((s0 + 1) ^ (site & 7)) * 16)) = uint4{pk[4], pk[5], pk[6], pk[7]};
+                pack_site16<F16, false, RELU>(acc, pj * 2 + hf, no_bn, no_bn, pk);
+                tile_write16(tb16, hf * 16 + r16, g16 * 2, pk);     // the lane's 16 couts = slots 2g, 2g+1 of the site's 128-byte row
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // same-wave LDS ops are in order: the row tile is complete
             const int sy = y0 + pj;
-            auto line = [&](int i) { const int row = i * 8 + rr; return *(const uint4*)(tb16 + row * 128 + ((cc ^ (row & 7)) * 16)); };
-            const uint4 o0 = line(0), o1 = line(1), o2 = line(2), o3 = line(3);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // reads retired before the tile is rewritten (and before the first bounds check)
-            auto put = [&](int i, const uint4& o) {
+            tile_store_lines(tb16, rr, cc, [&](int i, const uint4& o) {
                 const int sx = x0 + i * 8 + rr;
                 if (sy < Hs && sx < Ws) *(uint4*)(out00 + (2 * pj * Wout + 2 * i * 8) * CoutPad) = o;
-            };
-            put(0, o0); put(1, o1); put(2, o2); put(3, o3);
+            });
         }
     };
     if (a.act == 1) rows(std::true_type{}); else rows(std::false_type{});
-    IDC_DSTAMP(3);
+    IDC_STAMP(3);
 #ifdef IDC_TIMING
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    IDC_DSTAMP(4);
+    IDC_STAMP(4);
 #endif
 }
 

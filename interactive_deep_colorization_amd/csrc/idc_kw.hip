@@ -25,24 +25,15 @@
 #include "idc_kernels.h"
 
 #include "idc_layout.h"
+#include "idc_common.hip.h"
 
 namespace idc {
-
-typedef __attribute__((ext_vector_type(4))) float f32x4_k;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4_k;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_k;
-
-__device__ __forceinline__ int xcd_remap_k(int b, int nb) {
-    const int xcd = b & 7, q = nb >> 3, r = nb & 7;
-    const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + (b >> 3);
-}
 
 // weight fragments global -> registers by inline asm with counted waits: as plain loads hipcc sinks the look-ahead loads down to their first use
 // (a tap's weights then arrive one memory latency after they are asked for, tap after tap) and joins the first use with a vmcnt(0).  Loads return in
 // order; kw_wait*<N> = "these registers have landed once at most N younger loads are in flight", the operands tie the MFMAs that read them behind it.
-__device__ __forceinline__ void kw_gload(u32x4_k& dst, const char* p) { asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dst) : "v"(p)); }
-template <int N> __device__ __forceinline__ void kw_wait4(u32x4_k& a, u32x4_k& b, u32x4_k& c, u32x4_k& d) {
+__device__ __forceinline__ void kw_gload(u32x4& dst, const char* p) { asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dst) : "v"(p)); }
+template <int N> __device__ __forceinline__ void kw_wait4(u32x4& a, u32x4& b, u32x4& c, u32x4& d) {
     asm volatile("s_waitcnt vmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N));
 }
 
@@ -89,7 +80,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_kwave_bf16(const ConvArgs a) 
     // first launch of this kernel after others (eight kernel changes per click forward): its code comes in as data, all lines at once
     // (idc_kernels.h; 7.5-10.3 KB per instantiation, the <1,2,4> form is the last kernel of its code object: stay inside)
     if (a.warm && wave == NW - 1) idc_warm_own_code(smem + kw_lds_bytes(NKC, TWB, NW) - 256, lane, NKC == 8 ? 64 : NKC == 4 ? 68 : NKC == 2 ? 76 : 48);
-    int b = xcd_remap_k(blockIdx.x, gridDim.x);               // tile blocks fastest, the cout group slowest: an XCD's L2 sees few weight slices
+    int b = xcd_remap(blockIdx.x, gridDim.x);               // tile blocks fastest, the cout group slowest: an XCD's L2 sees few weight slices
     const int d = a.dy[8];
     const int bx = b % a.tiles_x; b /= a.tiles_x;
     const int by = b % a.tiles_y; b /= a.tiles_y;
@@ -130,7 +121,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_kwave_bf16(const ConvArgs a) 
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
             wo[cb][ks] = (cb * 16 + px) * kRowBytes + (((ks * 4 + g) ^ (px & 7)) * kSlotBytes);
-    u32x4_k areg[PD][2][2];
+    u32x4 areg[PD][2][2];
     auto load_A = [&](auto slotc, int t) {
         constexpr int S = decltype(slotc)::value;
         const char* const src = wl + (size_t)(t < 8 ? t : 8) * w_tap_stride;         // past the range: a harmless re-read (same count on every wave)
@@ -149,11 +140,11 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_kwave_bf16(const ConvArgs a) 
     if constexpr (PD > 2) load_A(std::integral_constant<int, 2>{}, t0 + 2);
     if constexpr (PD > 3) load_A(std::integral_constant<int, 3>{}, t0 + 3);
 
-    f32x4_k acc[2][PB];
+    f32x4 acc[2][PB];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < PB; ++j) acc[i][j] = f32x4_k{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < PB; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     // the lane's pixel in each 16-pixel block, as a halo pixel index (tap (1,1))
     int hbase[PB];
 #pragma unroll
@@ -174,13 +165,13 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_kwave_bf16(const ConvArgs a) 
         if (t < t1) {                                          // wave-uniform
             const int ty = t / 3, tx = t - ty * 3;
             const int toff = (ty - 1) * PWD + (tx - 1);
-            u32x4_k bf[PB][2];
+            u32x4 bf[PB][2];
 #pragma unroll
             for (int pb = 0; pb < PB; ++pb) {
                 const int hr = hbase[pb] + toff;
                 const int o0 = hr * kRowBytes + ((g ^ (hr & 7)) * kSlotBytes);
-                bf[pb][0] = *(const u32x4_k*)(hchunk + o0);
-                bf[pb][1] = *(const u32x4_k*)(hchunk + (o0 ^ (4 * kSlotBytes)));
+                bf[pb][0] = *(const u32x4*)(hchunk + o0);
+                bf[pb][1] = *(const u32x4*)(hchunk + (o0 ^ (4 * kSlotBytes)));
             }
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
@@ -188,8 +179,8 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_kwave_bf16(const ConvArgs a) 
                 for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
                     for (int pb = 0; pb < PB; ++pb)
-                        acc[cb][pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_k, areg[I % PD][cb][ks]),
-                                                                              __builtin_bit_cast(bf16x8_k, bf[pb][ks]), acc[cb][pb], 0, 0, 0);
+                        acc[cb][pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, areg[I % PD][cb][ks]),
+                                                                              __builtin_bit_cast(bf16x8, bf[pb][ks]), acc[cb][pb], 0, 0, 0);
         }
         if constexpr (I + PD < MAXT) load_A(std::integral_constant<int, I % PD>{}, t0 + I + PD);
     };
@@ -214,36 +205,36 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_kwave_bf16(const ConvArgs a) 
 #pragma unroll
             for (int cb = 0; cb < 2; ++cb) {
                 const int p64 = q * 16 + px;
-                *(f32x4_k*)(smem + wave * 8192 + p64 * kRowBytes + (((g * 2 + cb) ^ (p64 & 7)) * kSlotBytes)) = acc[cb][h * 4 + q];
+                *(f32x4*)(smem + wave * 8192 + p64 * kRowBytes + (((g * 2 + cb) ^ (p64 & 7)) * kSlotBytes)) = acc[cb][h * 4 + q];
             }
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < (64 * 8) / NT; ++k) {
             const int idx = tid + k * NT;
             const int p64 = idx >> 3, slot = idx & 7;
-            f32x4_k s = *(const f32x4_k*)(smem + p64 * kRowBytes + ((slot ^ (p64 & 7)) * kSlotBytes));
+            f32x4 s = *(const f32x4*)(smem + p64 * kRowBytes + ((slot ^ (p64 & 7)) * kSlotBytes));
 #pragma unroll
-            for (int w = 1; w < NW; ++w) s += *(const f32x4_k*)(smem + w * 8192 + p64 * kRowBytes + ((slot ^ (p64 & 7)) * kSlotBytes));
+            for (int w = 1; w < NW; ++w) s += *(const f32x4*)(smem + w * 8192 + p64 * kRowBytes + ((slot ^ (p64 & 7)) * kSlotBytes));
             const int P = h * 64 + p64, pb = P >> 4, pp = P & 15;
             const int row = TWB == 1 ? pb * 2 + (pp >> 3) : pb, col = TWB == 1 ? (pp & 7) : pp;
             const int yy = Y0 + d * row, xx = X0 + d * col;
             const int co = (cg >> 1) * kCoutGroup + (slot >> 1) * 16 + (cg & 1) * 8 + (slot & 1) * 4;      // slot = g*2 + cb (see the weight rows above)
-            const f32x4_k bias = *(const f32x4_k*)(a.bias + co);
-            f32x4_k v = s + bias;
+            const f32x4 bias = *(const f32x4*)(a.bias + co);
+            f32x4 v = s + bias;
             if (a.act == 1) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
             else if (a.act == 2) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : 0.2f * v[r];
             }
             if (has_bn) {
-                const f32x4_k sc = *(const f32x4_k*)(a.bn_scale + co), sh = *(const f32x4_k*)(a.bn_shift + co);
+                const f32x4 sc = *(const f32x4*)(a.bn_scale + co), sh = *(const f32x4*)(a.bn_shift + co);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = fmaf(v[r], sc[r], sh[r]);
             }
-            if (a.img_shift) v += *(const f32x4_k*)(a.img_shift + (size_t)n * CoutPad + co);
+            if (a.img_shift) v += *(const f32x4*)(a.img_shift + (size_t)n * CoutPad + co);
             if (yy < H && xx < W) {
                 const size_t o = (((size_t)n * H + yy) * W + xx) * CoutPad + co;
-                if (a.out_f32) *(f32x4_k*)((float*)a.out + o) = v;
+                if (a.out_f32) *(f32x4*)((float*)a.out + o) = v;
                 else {
                     const __bf16 q0 = (__bf16)v[0], q1 = (__bf16)v[1], q2 = (__bf16)v[2], q3 = (__bf16)v[3];
                     uint2 pk;
@@ -283,7 +274,7 @@ __global__ __launch_bounds__(512, NKC == 8 ? 2 : 4) void conv_kwave_deconv_bf16(
     const int px = lane & 15, g = lane >> 4;
 
     if (a.warm && wave == NW - 1) idc_warm_own_code(smem + kwd_lds_bytes(NKC) - 256, lane, NKC == 8 ? 70 : NKC == 4 ? 46 : 32);   // 9.5 / 6.3 / 4.5 KB
-    int b = xcd_remap_k(blockIdx.x, gridDim.x);
+    int b = xcd_remap(blockIdx.x, gridDim.x);
     const int bx = b % a.tiles_x; b /= a.tiles_x;
     const int by = b % a.tiles_y; b /= a.tiles_y;
     const int n = b % a.N;
@@ -316,23 +307,23 @@ __global__ __launch_bounds__(512, NKC == 8 ? 2 : 4) void conv_kwave_deconv_bf16(
         const int ph = split * PHW + (I >> 2), r = ph >> 1, sx = ph & 1, i = (I >> 1) & 1, j = I & 1;
         return ((1 - r) + 2 * i) * 4 + (1 - sx) + 2 * j;
     };
-    u32x4_k areg[PD][2];
+    u32x4 areg[PD][2];
     auto load_A = [&](auto slotc, int I) {
         constexpr int S = decltype(slotc)::value;
         const char* const src = wl + (size_t)item_tw(I) * w_tap_stride;
-        areg[S][0] = *(const u32x4_k*)(src + wo0);              // (plain loads here: with two loads per item hipcc's own schedule measured 0.3 us
-        areg[S][1] = *(const u32x4_k*)(src + wo1);              //  per launch better than the counted-wait form of conv_kwave_bf16)
+        areg[S][0] = *(const u32x4*)(src + wo0);              // (plain loads here: with two loads per item hipcc's own schedule measured 0.3 us
+        areg[S][1] = *(const u32x4*)(src + wo1);              //  per launch better than the counted-wait form of conv_kwave_bf16)
     };
     if constexpr (PD > 0) load_A(std::integral_constant<int, 0>{}, 0);
     if constexpr (PD > 1) load_A(std::integral_constant<int, 1>{}, 1);
     if constexpr (PD > 2) load_A(std::integral_constant<int, 2>{}, 2);
     if constexpr (PD > 3) load_A(std::integral_constant<int, 3>{}, 3);
 
-    f32x4_k acc[PHW][4];
+    f32x4 acc[PHW][4];
 #pragma unroll
     for (int i = 0; i < PHW; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_k{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     int hbase[4];
 #pragma unroll
     for (int pb = 0; pb < 4; ++pb) hbase[pb] = (pb * 2 + (px >> 3) + 1) * PWD + (px & 7) + 1;
@@ -346,20 +337,20 @@ __global__ __launch_bounds__(512, NKC == 8 ? 2 : 4) void conv_kwave_deconv_bf16(
         const int ph = split * PHW + (I >> 2), r = ph >> 1, sx = ph & 1;
         constexpr int i = (I >> 1) & 1, j = I & 1;
         const int toff = (r - i) * PWD + (sx - j);
-        u32x4_k bf[4][2];
+        u32x4 bf[4][2];
 #pragma unroll
         for (int pb = 0; pb < 4; ++pb) {
             const int hr = hbase[pb] + toff;
             const int o0 = hr * kRowBytes + ((g ^ (hr & 7)) * kSlotBytes);
-            bf[pb][0] = *(const u32x4_k*)(hchunk + o0);
-            bf[pb][1] = *(const u32x4_k*)(hchunk + (o0 ^ (4 * kSlotBytes)));
+            bf[pb][0] = *(const u32x4*)(hchunk + o0);
+            bf[pb][1] = *(const u32x4*)(hchunk + (o0 ^ (4 * kSlotBytes)));
         }
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
             for (int pb = 0; pb < 4; ++pb)
-                acc[I >> 2][pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_k, areg[I % PD][ks]),
-                                                                          __builtin_bit_cast(bf16x8_k, bf[pb][ks]), acc[I >> 2][pb], 0, 0, 0);
+                acc[I >> 2][pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, areg[I % PD][ks]),
+                                                                          __builtin_bit_cast(bf16x8, bf[pb][ks]), acc[I >> 2][pb], 0, 0, 0);
         if constexpr (I + PD < MAXI) load_A(std::integral_constant<int, I % PD>{}, I + PD);
     };
     item(std::integral_constant<int, 0>{}); item(std::integral_constant<int, 1>{});
@@ -382,7 +373,7 @@ __global__ __launch_bounds__(512, NKC == 8 ? 2 : 4) void conv_kwave_deconv_bf16(
 #pragma unroll
         for (int pb = 0; pb < 4; ++pb) {
             const int site = pb * 16 + px;
-            *(f32x4_k*)(smem + (wave * PHW + pl) * 4096 + site * 64 + ((g ^ ((site >> 1) & 3)) * kSlotBytes)) = acc[pl][pb];
+            *(f32x4*)(smem + (wave * PHW + pl) * 4096 + site * 64 + ((g ^ ((site >> 1) & 3)) * kSlotBytes)) = acc[pl][pb];
         }
     __syncthreads();
     const int CoutPad = a.ncg * kCoutGroup;
@@ -394,13 +385,13 @@ __global__ __launch_bounds__(512, NKC == 8 ? 2 : 4) void conv_kwave_deconv_bf16(
         const int slot = idx & 3, site = (idx >> 2) & 63, ph = idx >> 8;
         const int sp = ph / PHW, pl = ph - sp * PHW;
         const char* const base = smem + ((sp * NKC) * PHW + pl) * 4096 + site * 64 + ((slot ^ ((site >> 1) & 3)) * kSlotBytes);
-        f32x4_k v = *(const f32x4_k*)base;
+        f32x4 v = *(const f32x4*)base;
 #pragma unroll
-        for (int kc = 1; kc < NKC; ++kc) v += *(const f32x4_k*)(base + kc * PHW * 4096);
+        for (int kc = 1; kc < NKC; ++kc) v += *(const f32x4*)(base + kc * PHW * 4096);
         const int pb = site >> 4, pp = site & 15;
         const int sy = Y0 + pb * 2 + (pp >> 3), sxx = X0 + (pp & 7);
         const int co = (cq >> 2) * kCoutGroup + slot * 16 + (cq & 3) * 4;
-        v += *(const f32x4_k*)(a.bias + co);
+        v += *(const f32x4*)(a.bias + co);
         if (sy < H && sxx < W) {
             const size_t o = (((size_t)n * Ho + (2 * sy + (ph >> 1))) * Wo + (2 * sxx + (ph & 1))) * CoutPad + co;
             if (a.resid) {
@@ -409,7 +400,7 @@ __global__ __launch_bounds__(512, NKC == 8 ? 2 : 4) void conv_kwave_deconv_bf16(
                     v[0] += __uint_as_float(rr.x << 16); v[1] += __uint_as_float(rr.x & 0xffff0000u);
                     v[2] += __uint_as_float(rr.y << 16); v[3] += __uint_as_float(rr.y & 0xffff0000u);
                 } else {
-                    v += *(const f32x4_k*)((const float*)a.resid + o);
+                    v += *(const f32x4*)((const float*)a.resid + o);
                 }
             }
             if (a.act == 1) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
@@ -418,11 +409,11 @@ __global__ __launch_bounds__(512, NKC == 8 ? 2 : 4) void conv_kwave_deconv_bf16(
                 for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : 0.2f * v[r];
             }
             if (has_bn) {
-                const f32x4_k sc = *(const f32x4_k*)(a.bn_scale + co), sh = *(const f32x4_k*)(a.bn_shift + co);
+                const f32x4 sc = *(const f32x4*)(a.bn_scale + co), sh = *(const f32x4*)(a.bn_shift + co);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = fmaf(v[r], sc[r], sh[r]);
             }
-            if (a.out_f32) *(f32x4_k*)((float*)a.out + o) = v;
+            if (a.out_f32) *(f32x4*)((float*)a.out + o) = v;
             else {
                 const __bf16 q0 = (__bf16)v[0], q1 = (__bf16)v[1], q2 = (__bf16)v[2], q3 = (__bf16)v[3];
                 uint2 pk;
@@ -476,7 +467,7 @@ __global__ __launch_bounds__(512, 2) void conv_kwave_chain_bf16(const KwChainArg
     const int px = lane & 15, g = lane >> 4;
     const int H = c.H, W = c.W;
     const int pix_bytes = NKC * kRowBytes;
-    const int bid = xcd_remap_k(blockIdx.x, gridDim.x);
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const unsigned long long nwg = gridDim.x;
     const size_t w_kc_stride = (size_t)c.ncg * kWBlockBytes;
     const size_t w_tap_stride = w_kc_stride * NKC;
@@ -517,7 +508,7 @@ __global__ __launch_bounds__(512, 2) void conv_kwave_chain_bf16(const KwChainArg
         const char* const wl = (const char*)Ly.wgt + (size_t)wave * w_kc_stride + (size_t)(cg >> 1) * kWBlockBytes + (cg & 1) * 32 * kRowBytes;
 
         // ---- weights, bias, BN do not depend on the previous layer: on their way before the grid barrier is waited for
-        u32x4_k areg[PD][2][2];
+        u32x4 areg[PD][2][2];
         auto load_A = [&](auto slotc, int t) {
             constexpr int S = decltype(slotc)::value;
             const char* const src = wl + (size_t)(t < 8 ? t : 8) * w_tap_stride;
@@ -537,9 +528,9 @@ __global__ __launch_bounds__(512, 2) void conv_kwave_chain_bf16(const KwChainArg
         load_A(std::integral_constant<int, 3>{}, 3);
         const int co = (cg >> 1) * kCoutGroup + (r_slot >> 1) * 16 + (cg & 1) * 8 + (r_slot & 1) * 4;
         const bool has_bn = Ly.bn_scale != nullptr;
-        const f32x4_k e_bias = *(const f32x4_k*)(Ly.bias + co);
-        f32x4_k e_sc = f32x4_k{1.f, 1.f, 1.f, 1.f}, e_sh = f32x4_k{0.f, 0.f, 0.f, 0.f};
-        if (has_bn) { e_sc = *(const f32x4_k*)(Ly.bn_scale + co); e_sh = *(const f32x4_k*)(Ly.bn_shift + co); }
+        const f32x4 e_bias = *(const f32x4*)(Ly.bias + co);
+        f32x4 e_sc = f32x4{1.f, 1.f, 1.f, 1.f}, e_sh = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (has_bn) { e_sc = *(const f32x4*)(Ly.bn_scale + co); e_sh = *(const f32x4*)(Ly.bn_shift + co); }
 
         if (li > 0) {
             // ---- grid barrier, wait side: everybody's layer li-1 output is in memory
@@ -577,11 +568,11 @@ __global__ __launch_bounds__(512, 2) void conv_kwave_chain_bf16(const KwChainArg
             }
         }
         IDC_KW_STAMP(6);
-        f32x4_k acc[2][PB];
+        f32x4 acc[2][PB];
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int j = 0; j < PB; ++j) acc[i][j] = f32x4_k{0.f, 0.f, 0.f, 0.f};
+            for (int j = 0; j < PB; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // MY halo chunk has landed (the youngest loads; the weight taps and vectors were asked for first)
         IDC_KW_STAMP(2);
 
@@ -592,13 +583,13 @@ __global__ __launch_bounds__(512, 2) void conv_kwave_chain_bf16(const KwChainArg
             {
                 constexpr int ty = I / 3, tx = I - ty * 3;
                 constexpr int toff = (ty - 1) * PWD + (tx - 1);
-                u32x4_k bf[PB][2];
+                u32x4 bf[PB][2];
 #pragma unroll
                 for (int pb = 0; pb < PB; ++pb) {
                     const int hr = hbase[pb] + toff;
                     const int o0 = hr * kRowBytes + ((g ^ (hr & 7)) * kSlotBytes);
-                    bf[pb][0] = *(const u32x4_k*)(hchunk + o0);
-                    bf[pb][1] = *(const u32x4_k*)(hchunk + (o0 ^ (4 * kSlotBytes)));
+                    bf[pb][0] = *(const u32x4*)(hchunk + o0);
+                    bf[pb][1] = *(const u32x4*)(hchunk + (o0 ^ (4 * kSlotBytes)));
                 }
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks)
@@ -606,8 +597,8 @@ __global__ __launch_bounds__(512, 2) void conv_kwave_chain_bf16(const KwChainArg
                     for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
                         for (int pb = 0; pb < PB; ++pb)
-                            acc[cb][pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_k, areg[I % PD][cb][ks]),
-                                                                                  __builtin_bit_cast(bf16x8_k, bf[pb][ks]), acc[cb][pb], 0, 0, 0);
+                            acc[cb][pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, areg[I % PD][cb][ks]),
+                                                                                  __builtin_bit_cast(bf16x8, bf[pb][ks]), acc[cb][pb], 0, 0, 0);
             }
             if constexpr (I + PD < 9) load_A(std::integral_constant<int, I % PD>{}, I + PD);
         };
@@ -623,15 +614,15 @@ __global__ __launch_bounds__(512, 2) void conv_kwave_chain_bf16(const KwChainArg
 #pragma unroll
             for (int cb = 0; cb < 2; ++cb) {
                 const int p64 = q * 16 + px;
-                *(f32x4_k*)(hchunk + p64 * kRowBytes + (((g * 2 + cb) ^ (p64 & 7)) * kSlotBytes)) = acc[cb][q];
+                *(f32x4*)(hchunk + p64 * kRowBytes + (((g * 2 + cb) ^ (p64 & 7)) * kSlotBytes)) = acc[cb][q];
             }
         __syncthreads();
         {
-            f32x4_k s = *(const f32x4_k*)(smem + r_off);
+            f32x4 s = *(const f32x4*)(smem + r_off);
 #pragma unroll
-            for (int w = 1; w < NW; ++w) s += *(const f32x4_k*)(smem + w * CHUNK + r_off);
+            for (int w = 1; w < NW; ++w) s += *(const f32x4*)(smem + w * CHUNK + r_off);
             const int yy = Y0 + d * r_row, xx = X0 + d * r_col;
-            f32x4_k v = s + e_bias;
+            f32x4 v = s + e_bias;
             if (Ly.act == 1) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
             else if (Ly.act == 2) {
 #pragma unroll

@@ -27,26 +27,9 @@
 #include "idc_kernels.h"
 
 #include "idc_layout.h"
-#include "idc_split.hip.h"
+#include "idc_common.hip.h"
 
 namespace idc {
-
-// in-kernel cycle stamps for the tuning harness (tools/ablate, -DIDC_TIMING): compiled out of the library
-#ifdef IDC_TIMING
-extern __device__ long long* g_idc_dbg;
-#define IDC_MSTAMP(i) do { if (tid == 0) g_idc_dbg[(size_t)blockIdx.x * 16 + (i)] = (long long)__builtin_readcyclecounter(); } while (0)
-#else
-#define IDC_MSTAMP(i) do {} while (0)
-#endif
-
-
-
-__device__ __forceinline__ int xcd_remap_m(int b, int nb) {
-    const int xcd = b & 7, q = nb >> 3, r = nb & 7;
-    const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + (b >> 3);
-}
-
 
 // SPLIT = false: conv_igemm_v2m as described above.  SPLIT = true: conv_igemm_v2s, the operand-split form (IDC_BF16X3 / IDC_BF16X6) -- the same
 // tile and K-loop body walked over a.nseg segments of nkc chunks (input part x weight part per segment, ConvArgs), and its own epilogue.
@@ -73,7 +56,7 @@ __device__ __forceinline__ void conv_v2m_body(const ConvArgs& a) {
     const int r16 = lane & 15, g16 = lane >> 4;
 
     // tile order as conv_igemm_v2: (deconv phase, cout tile) fastest, contiguous ranges per XCD
-    int b = xcd_remap_m(blockIdx.x, gridDim.x);
+    int b = xcd_remap(blockIdx.x, gridDim.x);
     const int nct = a.ncg / WCO;
     const int phase = b % a.nphase; b /= a.nphase;
     const int ct = b % nct; b /= nct;
@@ -268,6 +251,8 @@ __device__ __forceinline__ void conv_v2m_body(const ConvArgs& a) {
     if (WCO == 2 && a.head_w != nullptr) {
         // conv10_2 -> model_out (model.py:101-109): activation and the 128 -> 2 dot product in the MFMA layout (16 couts of one
         // site per lane); the eight partial sums of a pixel (4 lane groups x 2 cout waves) meet in LDS.  Nothing stored but the ab map.
+        // (This block, the bias start of the accumulators and the BN constant load below are written out in conv_v2p_body too: behind a
+        // shared function the same text compiles to more scratch or branches in some kernels -- profiles/shared_epilogue.txt.)
         f32x4 w0[4], w1[4];
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi) {
@@ -277,7 +262,7 @@ __device__ __forceinline__ void conv_v2m_body(const ConvArgs& a) {
             w1[mi] = f32x4{v.x, v.y, v.z, v.w};
         }
         float* const hp = (float*)smem;                        // [wave][pt 8][group 4][16 sites][2]
-        auto partial = [&](auto act_c) __attribute__((always_inline)) {        // (activation chosen once, as in conv_igemm_v2p)
+        auto partial = [&](auto act_c) __attribute__((always_inline)) {        // (activation chosen once, as in conv_v2p_body)
             constexpr int ACT = decltype(act_c)::value;
 #pragma unroll
             for (int pt = 0; pt < 8; ++pt) {
@@ -320,10 +305,9 @@ __device__ __forceinline__ void conv_v2m_body(const ConvArgs& a) {
         split_epilogue<WCO, SPLIT == 2>(a, acc, smem, n, ty0, tx0, wpx, cow, ro, cof);
         return;
     }
-    // bf16 outputs, activation (+ eval-BN) and rounding in the MFMA layout, then a wave-private [32 sites][64 couts] bf16 tile
-    // (128-byte rows, slot ^ (site & 7)) read back as lane = (site l >> 3, 8 couts l & 7): every store covers whole 128-byte lines
+    // bf16 outputs: activation (+ eval-BN) and rounding in the MFMA layout, then whole 128-byte lines through the wave-private transpose tile
+    // (idc_common.hip.h: pack_site16, tile_write16, tile_read_lines)
     char* const tb16 = smem + wave * 4096;
-    typedef short s16x2 __attribute__((ext_vector_type(2)));
     const int rr = lane >> 3, cc = lane & 7;
     const int co8 = cow + cc * 8;
     f32x4 bsc[4], bsh[4];
@@ -340,38 +324,20 @@ __device__ __forceinline__ void conv_v2m_body(const ConvArgs& a) {
             }
         }
     }
-    // (one body per (BN, ReLU) combination chosen once, a row's four lines read before the first bounds check: conv_igemm_v2p's epilogue says why)
+    // one body per (BN, ReLU) combination, chosen once (pack_site16 says why)
     auto rows = [&](auto bn_c, auto relu_c) __attribute__((always_inline)) {
         constexpr bool BN = decltype(bn_c)::value, RELU = decltype(relu_c)::value;
 #pragma unroll
         for (int pj = 0; pj < 4; ++pj) {
 #pragma unroll
             for (int hf = 0; hf < 2; ++hf) {
-                const int pt = pj * 2 + hf, site = hf * 16 + r16;
                 unsigned pk[8];
-#pragma unroll
-                for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) {
-                        float v0 = acc[mi][pt][2 * e], v1 = acc[mi][pt][2 * e + 1];
-                        if constexpr (BN) {
-                            if constexpr (RELU) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); }
-                            pk[mi * 2 + e] = pack_bf16x2_m(fmaf(v0, bsc[mi][2 * e], bsh[mi][2 * e]), fmaf(v1, bsc[mi][2 * e + 1], bsh[mi][2 * e + 1]));
-                        } else {
-                            unsigned p = pack_bf16x2_m(v0, v1);
-                            if constexpr (RELU) p = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, p), s16x2{0, 0}));
-                            pk[mi * 2 + e] = p;
-                        }
-                    }
-                const int s0 = g16 * 2;                         // the lane's 16 couts = slots 2g, 2g+1 of the site's 128-byte row
-                *(uint4*)(tb16 + site * 128 + ((s0 ^ (site & 7)) * 16)) = uint4{pk[0], pk[1], pk[2], pk[3]};
-                *(uint4*)(tb16 + site * 128 + (((s0 + 1) ^ (site & 7)) * 16)) = uint4{pk[4], pk[5], pk[6], pk[7]};
+                pack_site16<false, BN, RELU>(acc, pj * 2 + hf, bsc, bsh, pk);
+                tile_write16(tb16, hf * 16 + r16, g16 * 2, pk);     // the lane's 16 couts = slots 2g, 2g+1 of the site's 128-byte row
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // same-wave LDS ops are in order: the row tile is complete
             const int sy = ty0 + wpx * 4 + pj;
-            auto line = [&](int i) { const int row = i * 8 + rr; return *(const uint4*)(tb16 + row * 128 + ((cc ^ (row & 7)) * 16)); };
-            const uint4 o0 = line(0), o1 = line(1), o2 = line(2), o3 = line(3);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // reads retired before the tile is rewritten
+            uint4 o[4];
+            tile_read_lines(tb16, rr, cc, o);
             auto put = [&](int i, const uint4& o) {
                 const int sx = tx0 + i * 8 + rr;
                 if (sy < Hs && sx < Ws) {
@@ -379,7 +345,7 @@ __device__ __forceinline__ void conv_v2m_body(const ConvArgs& a) {
                     *(uint4*)((unsigned short*)a.out + oidx) = o;
                 }
             };
-            put(0, o0); put(1, o1); put(2, o2); put(3, o3);
+            put(0, o[0]); put(1, o[1]); put(2, o[2]); put(3, o[3]);
         }
     };
     if (has_bn) {
@@ -438,7 +404,7 @@ __device__ __forceinline__ void conv_v2p_body(const ConvArgs& a) {
     const int wco = wave % WCO, wpx = wave / WCO;
     const int r16 = lane & 15, g16 = lane >> 4;
 
-    int b = xcd_remap_m(blockIdx.x, gridDim.x);
+    int b = xcd_remap(blockIdx.x, gridDim.x);
     const int nct = a.ncg / WCO;
     const int ct = b % nct; b /= nct;
     const int txi = b % a.tiles_x; b /= a.tiles_x;
@@ -454,7 +420,7 @@ __device__ __forceinline__ void conv_v2p_body(const ConvArgs& a) {
     const char* const img = (const char*)a.in + (size_t)n * (size_t)(Hs * si) * Win * (size_t)pix_bytes;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)img, 0, (Hs * si) * Win * pix_bytes, 0x00020000);
 
-    IDC_MSTAMP(0);
+    IDC_STAMP(0);
     f32x4 acc[4][8];
     {
         const float* const bp = a.bias + (ct * WCO + wco) * kCoutGroup + g16 * 16;
@@ -518,7 +484,7 @@ __device__ __forceinline__ void conv_v2p_body(const ConvArgs& a) {
     if (wave >= 4) __builtin_amdgcn_s_setprio(1);              // second-dispatched half of an 8-wave workgroup (as conv_igemm_v2)
     int buf_off = 0;                                           // byte offset of the ring slot holding the current tap's tile
 
-    IDC_MSTAMP(1);
+    IDC_STAMP(1);
     const int nseg = SPLIT ? a.nseg : 1;
     for (;;) {
     for (int kc = 0; kc < nkc; ++kc) {
@@ -540,12 +506,12 @@ __device__ __forceinline__ void conv_v2p_body(const ConvArgs& a) {
             constexpr int dy = (t / 3 - 1) * D;
             constexpr int tn = LAST ? 0 : t + 1;
             const char* const wcur = wbuf + buf_off;
-            if (t == 4 && kc == 0) IDC_MSTAMP(9);                   // (tools/ablate: where a tap's time goes)
+            if (t == 4 && kc == 0) IDC_STAMP(9);                   // (tools/ablate: where a tap's time goes)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // my pieces of this tap's weight tile landed
-            if (t == 4 && kc == 0) IDC_MSTAMP(10);
+            if (t == 4 && kc == 0) IDC_STAMP(10);
             __syncthreads();                                        // everybody's landed; everybody left the other buffer
-            if (t == 4 && kc == 0) IDC_MSTAMP(11);
-            if (t == 5 && kc == 0) IDC_MSTAMP(12);
+            if (t == 4 && kc == 0) IDC_STAMP(11);
+            if (t == 5 && kc == 0) IDC_STAMP(12);
             const char* const a0 = wcur + wa0;
             const char* const a1 = wcur + wa1;
             u32x4 wf[4], xlo[4], xhi[4];
@@ -621,14 +587,14 @@ __device__ __forceinline__ void conv_v2p_body(const ConvArgs& a) {
         if (!SPLIT || ++seg >= nseg) break;
     }
 
-    // ---- epilogue (conv_igemm_v2m's): lane (site r16, group g16) owns couts g16*16 + mi*4 + j of its wave's 64 ----------------------
-    IDC_MSTAMP(2);
+    // ---- epilogue: lane (site r16, group g16) owns couts g16*16 + mi*4 + j of its wave's 64 -------------------------------------
+    IDC_STAMP(2);
     if constexpr (SPLIT) add_bias_after_k(a.bias + (ct * WCO + wco) * kCoutGroup + g16 * 16, acc, a.acc_scale);
     const int CoutPad = a.ncg * kCoutGroup;
     const bool has_bn = a.bn_scale != nullptr;
     const int cow = (ct * WCO + wco) * kCoutGroup;
     __syncthreads();                                           // every wave left the halo / weight tiles
-    IDC_MSTAMP(5);
+    IDC_STAMP(5);
     if (WCO == 2 && a.head_w != nullptr) {
         f32x4 w0[4], w1[4];
 #pragma unroll
@@ -661,9 +627,9 @@ __device__ __forceinline__ void conv_v2p_body(const ConvArgs& a) {
         if (a.act == 1) partial(std::integral_constant<int, 1>{});
         else if (a.act == 2) partial(std::integral_constant<int, 2>{});
         else partial(std::integral_constant<int, 0>{});
-        IDC_MSTAMP(6);
+        IDC_STAMP(6);
         __syncthreads();
-        IDC_MSTAMP(7);
+        IDC_STAMP(7);
         if (wco == 0) {
             const int px = lane & 31, ch = lane >> 5;
             const float hb = a.head_b[ch];
@@ -679,10 +645,10 @@ __device__ __forceinline__ void conv_v2p_body(const ConvArgs& a) {
                 if (sy < Hs && sx < Ws) a.head_out[(((size_t)n * 2 + ch) * Hs + sy) * Ws + sx] = tanhf(p) * a.head_mul;
             }
         }
-        IDC_MSTAMP(3);
+        IDC_STAMP(3);
 #ifdef IDC_TIMING
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        IDC_MSTAMP(4);
+        IDC_STAMP(4);
 #endif
         return;
     }
@@ -691,7 +657,6 @@ __device__ __forceinline__ void conv_v2p_body(const ConvArgs& a) {
         return;
     }
     char* const tb16 = smem + wave * 4096;
-    typedef short s16x2 __attribute__((ext_vector_type(2)));
     const int rr = lane >> 3, cc = lane & 7;
     const int co8 = cow + cc * 8;
     f32x4 bsc[4], bsh[4];
@@ -709,8 +674,8 @@ __device__ __forceinline__ void conv_v2p_body(const ConvArgs& a) {
         }
     }
     // One body per (BN, ReLU) combination, chosen ONCE: written as run-time `if`s inside the element loops the compiler kept a uniform branch per packed
-    // pair (32 taken branches per pixel row) and sank each transposed LDS read under its store's bounds check (read - wait - store, four times in a
-    // row): 2.6 k cycles per pixel row, 10.9 k per tile -- 17 % of a conv10_2-shaped tile (tools/ablate stamps, profiles/r05_v2p_tap_stamps.txt).
+    // pair (32 taken branches per pixel row) -- with the reads sunk under the bounds checks (tile_read_lines) 2.6 k cycles per pixel row, 10.9 k per
+    // tile: 17 % of a conv10_2-shaped tile (tools/ablate stamps, profiles/r05_v2p_tap_stamps.txt).
     unsigned short* const out00 = (unsigned short*)a.out + (((size_t)n * Hs + ty0 + wpx * 4) * Ws + tx0 + rr) * CoutPad + co8;   // lane's line of the wave's first pixel row
     auto rows = [&](auto bn_c, auto relu_c) __attribute__((always_inline)) {
         constexpr bool BN = decltype(bn_c)::value, RELU = decltype(relu_c)::value;
@@ -718,38 +683,17 @@ __device__ __forceinline__ void conv_v2p_body(const ConvArgs& a) {
         for (int pj = 0; pj < 4; ++pj) {
 #pragma unroll
             for (int hf = 0; hf < 2; ++hf) {
-                const int pt = pj * 2 + hf, site = hf * 16 + r16;
                 unsigned pk[8];
-#pragma unroll
-                for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) {
-                        float v0 = acc[mi][pt][2 * e], v1 = acc[mi][pt][2 * e + 1];
-                        if constexpr (BN) {
-                            if constexpr (RELU) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); }
-                            pk[mi * 2 + e] = pack16x2_m<F16>(fmaf(v0, bsc[mi][2 * e], bsh[mi][2 * e]), fmaf(v1, bsc[mi][2 * e + 1], bsh[mi][2 * e + 1]));
-                        } else {
-                            unsigned p = pack16x2_m<F16>(v0, v1);
-                            if constexpr (RELU) p = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, p), s16x2{0, 0}));
-                            pk[mi * 2 + e] = p;
-                        }
-                    }
-                const int s0 = g16 * 2;
-                *(uint4*)(tb16 + site * 128 + ((s0 ^ (site & 7)) * 16)) = uint4{pk[0], pk[1], pk[2], pk[3]};
-                *(uint4*)(tb16 + site * 128 + (((s0 + 1) ^ (site & 7)) * 16)) = uint4{pk[4], pk[5], pk[6], pk[7]};
+                pack_site16<F16, BN, RELU>(acc, pj * 2 + hf, bsc, bsh, pk);
+                tile_write16(tb16, hf * 16 + r16, g16 * 2, pk);
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             const int sy = ty0 + wpx * 4 + pj;
-            auto line = [&](int i) { const int row = i * 8 + rr; return *(const uint4*)(tb16 + row * 128 + ((cc ^ (row & 7)) * 16)); };
-            const uint4 o0 = line(0), o1 = line(1), o2 = line(2), o3 = line(3);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // all four lines read (and the tile free for the next row) before the first store's bounds check
-            auto put = [&](int i, const uint4& o) {
+            tile_store_lines(tb16, rr, cc, [&](int i, const uint4& o) {
                 const int sx = tx0 + i * 8 + rr;
                 if (sy < Hs && sx < Ws) *(uint4*)(out00 + (pj * Ws + i * 8) * CoutPad) = o;      // (one 64-bit base per lane, 32-bit strides)
-            };
-            put(0, o0); put(1, o1); put(2, o2); put(3, o3);
-            if (pj == 0) IDC_MSTAMP(6);
-            if (pj == 1) IDC_MSTAMP(7);
+            });
+            if (pj == 0) IDC_STAMP(6);
+            if (pj == 1) IDC_STAMP(7);
         }
     };
     if (has_bn) {
@@ -757,10 +701,10 @@ __device__ __forceinline__ void conv_v2p_body(const ConvArgs& a) {
     } else {
         if (a.act == 1) rows(std::false_type{}, std::true_type{}); else rows(std::false_type{}, std::false_type{});
     }
-    IDC_MSTAMP(3);
+    IDC_STAMP(3);
 #ifdef IDC_TIMING
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    IDC_MSTAMP(4);
+    IDC_STAMP(4);
 #endif
 }
 
@@ -774,12 +718,25 @@ __global__ __launch_bounds__(WCO* WPX * 64, 2) void conv_igemm_v2ps(const ConvAr
 template <int WCO, int WPX, int D>
 __global__ __launch_bounds__(WCO* WPX * 64, 2) void conv_igemm_v2psh(const ConvArgs a) { conv_v2p_body<WCO, WPX, D, 2>(a); }
 
-static constexpr size_t conv_v2p_lds_bytes_c(int wco, int wpx, int d) {            // = conv_igemm_v2m's
-    const int nt = wco * wpx * 64;
-    const int hrows = (32 + 2 * d) * (4 * wpx + 2 * d);
-    const int items = (hrows * kSlots + nt - 1) / nt;
-    return (size_t)items * nt * kSlotBytes + 2 * (size_t)(64 * wco) * kRowBytes;
-}
+// One kernel of the (32 x 4*WPX sites) x (64*WCO couts) tile with halo HALO, as the launchers and init_kernels_v2m handle it (k = nullptr: no such
+// instantiation): its LDS size (halo tile + 2-slot weight ring, the same for conv_igemm_v2m's and conv_igemm_v2p's families), its dynamic-LDS limit, its launch
+struct TileKernel {
+    void (*k)(const ConvArgs);
+    int wco, wpx, halo;
+    constexpr size_t lds_bytes() const {
+        const int nt = wco * wpx * 64;
+        const int hrows = (32 + 2 * halo) * (4 * wpx + 2 * halo);
+        const int items = (hrows * kSlots + nt - 1) / nt;
+        return (size_t)items * nt * kSlotBytes + 2 * (size_t)(64 * wco) * kRowBytes;
+    }
+    hipError_t raise_lds_limit() const { return hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes()); }
+    hipError_t launch(long long blocks, const ConvArgs& a, hipStream_t s) const {
+        if (blocks <= 0 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+        if (k == nullptr) return hipErrorInvalidConfiguration;
+        hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(wco * wpx * 64), lds_bytes(), s, a);
+        return hipGetLastError();
+    }
+};
 
 #define IDC_FOR_EACH_CONV_V2P(X) X(4, 2, 1) X(4, 2, 2) X(2, 2, 1)
 #define IDC_FOR_EACH_CONV_V2PS(X) IDC_FOR_EACH_CONV_V2P(X) X(1, 4, 1) X(1, 2, 1)      // (+ the 64-cout tiles of conv1_2)
@@ -796,27 +753,12 @@ bool conv_v2p_applies(ConvConfig cfg, int halo, const ConvArgs& a) {
 
 hipError_t launch_conv_v2p(ConvConfig cfg, int halo, const ConvArgs& a, hipStream_t s) {
     if (!conv_v2p_applies(cfg, halo, a)) return hipErrorInvalidConfiguration;
-    const int nct = a.ncg / cfg.wm;
-    const long long blocks = (long long)a.tiles_x * a.tiles_y * a.N * nct;
-    if (blocks <= 0 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-#define X(WCO, WPX, DD)                                                                                                          \
-    if (cfg.wm == WCO && cfg.wp == WPX && halo == DD) {                                                                          \
-        if (a.split_f16) hipLaunchKernelGGL((conv_igemm_v2ph<WCO, WPX, DD>), dim3((unsigned)blocks), dim3(WCO * WPX * 64),       \
-                                            conv_v2p_lds_bytes_c(WCO, WPX, DD), s, a);          /* IDC_FP16's fast path */           \
-        else hipLaunchKernelGGL((conv_igemm_v2p<WCO, WPX, DD>), dim3((unsigned)blocks), dim3(WCO * WPX * 64),                    \
-                                conv_v2p_lds_bytes_c(WCO, WPX, DD), s, a);                                                       \
-        return hipGetLastError();                                                                                                \
-    }
+    TileKernel tk{nullptr, cfg.wm, cfg.wp, halo};
+#define X(WCO, WPX, DD) \
+    if (cfg.wm == WCO && cfg.wp == WPX && halo == DD) tk.k = a.split_f16 ? conv_igemm_v2ph<WCO, WPX, DD> /* IDC_FP16's fast path */ : conv_igemm_v2p<WCO, WPX, DD>;
     IDC_FOR_EACH_CONV_V2P(X)
 #undef X
-    return hipErrorInvalidConfiguration;
-}
-
-static constexpr size_t conv_v2m_lds_bytes_c(int wco, int wpx, int halo) {
-    const int nt = wco * wpx * 64;
-    const int hrows = (32 + 2 * halo) * (4 * wpx + 2 * halo);
-    const int items = (hrows * kSlots + nt - 1) / nt;
-    return (size_t)items * nt * kSlotBytes + 2 * (size_t)(64 * wco) * kRowBytes;
+    return tk.launch((long long)a.tiles_x * a.tiles_y * a.N * (a.ncg / cfg.wm), a, s);
 }
 
 #define IDC_FOR_EACH_CONV_V2M(X) X(4, 2, 0) X(4, 2, 1) X(4, 2, 2) X(2, 4, 0) X(2, 4, 1) X(2, 4, 2) X(2, 2, 0) X(2, 2, 1) X(2, 2, 2)
@@ -829,18 +771,12 @@ bool conv_v2m_applies(const ConvArgs& a) {
 
 hipError_t launch_conv_v2m(ConvConfig cfg, int halo, const ConvArgs& a, hipStream_t s) {
     if (!conv_v2m_applies(a)) return hipErrorInvalidConfiguration;
-    const int nct = a.ncg / cfg.wm;
-    const long long blocks = (long long)a.tiles_x * a.tiles_y * a.N * nct * a.nphase;
-    if (blocks <= 0 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-#define X(WCO, WPX, HL)                                                                                                          \
-    if (cfg.wm == WCO && cfg.wp == WPX && halo == HL) {                                                                          \
-        hipLaunchKernelGGL((conv_igemm_v2m<WCO, WPX, HL>), dim3((unsigned)blocks), dim3(WCO * WPX * 64),                         \
-                           conv_v2m_lds_bytes_c(WCO, WPX, HL), s, a);                                                            \
-        return hipGetLastError();                                                                                                \
-    }
+    TileKernel tk{nullptr, cfg.wm, cfg.wp, halo};
+#define X(WCO, WPX, HL) \
+    if (cfg.wm == WCO && cfg.wp == WPX && halo == HL) tk.k = conv_igemm_v2m<WCO, WPX, HL>;
     IDC_FOR_EACH_CONV_V2M(X)
 #undef X
-    return hipErrorInvalidConfiguration;
+    return tk.launch((long long)a.tiles_x * a.tiles_y * a.N * (a.ncg / cfg.wm) * a.nphase, a, s);
 }
 
 // operand-split launches (IDC_BF16X3 / IDC_BF16X6): everything conv_igemm_v2m's geometry covers, plus fp32 shortcut sums, fp32 outputs, per-image shifts
@@ -853,20 +789,12 @@ bool conv_v2s_applies(const ConvArgs& a) {
 
 hipError_t launch_conv_v2s(ConvConfig cfg, int halo, const ConvArgs& a, hipStream_t s) {
     if (!conv_v2s_applies(a)) return hipErrorInvalidConfiguration;
-    const int nct = a.ncg / cfg.wm;
-    const long long blocks = (long long)a.tiles_x * a.tiles_y * a.N * nct * a.nphase;
-    if (blocks <= 0 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-#define X(WCO, WPX, HL)                                                                                                          \
-    if (cfg.wm == WCO && cfg.wp == WPX && halo == HL) {                                                                          \
-        if (a.split_f16) hipLaunchKernelGGL((conv_igemm_v2sh<WCO, WPX, HL>), dim3((unsigned)blocks), dim3(WCO * WPX * 64),       \
-                                            conv_v2m_lds_bytes_c(WCO, WPX, HL), s, a);                                           \
-        else hipLaunchKernelGGL((conv_igemm_v2s<WCO, WPX, HL>), dim3((unsigned)blocks), dim3(WCO * WPX * 64),                    \
-                                conv_v2m_lds_bytes_c(WCO, WPX, HL), s, a);                                                       \
-        return hipGetLastError();                                                                                                \
-    }
+    TileKernel tk{nullptr, cfg.wm, cfg.wp, halo};
+#define X(WCO, WPX, HL) \
+    if (cfg.wm == WCO && cfg.wp == WPX && halo == HL) tk.k = a.split_f16 ? conv_igemm_v2sh<WCO, WPX, HL> : conv_igemm_v2s<WCO, WPX, HL>;
     IDC_FOR_EACH_CONV_V2S(X)
 #undef X
-    return hipErrorInvalidConfiguration;
+    return tk.launch((long long)a.tiles_x * a.tiles_y * a.N * (a.ncg / cfg.wm) * a.nphase, a, s);
 }
 
 // conv_igemm_v2ps: the 3x3 launches among them on conv_igemm_v2p's body (column-swizzled halo tile, unrolled taps, buffer loads)
@@ -880,57 +808,33 @@ bool conv_v2ps_applies(ConvConfig cfg, int halo, const ConvArgs& a) {
 
 hipError_t launch_conv_v2ps(ConvConfig cfg, int halo, const ConvArgs& a, hipStream_t s) {
     if (!conv_v2ps_applies(cfg, halo, a)) return hipErrorInvalidConfiguration;
-    const int nct = a.ncg / cfg.wm;
-    const long long blocks = (long long)a.tiles_x * a.tiles_y * a.N * nct;
-    if (blocks <= 0 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-#define X(WCO, WPX, DD)                                                                                                          \
-    if (cfg.wm == WCO && cfg.wp == WPX && halo == DD) {                                                                          \
-        if (a.split_f16) hipLaunchKernelGGL((conv_igemm_v2psh<WCO, WPX, DD>), dim3((unsigned)blocks), dim3(WCO * WPX * 64),      \
-                                            conv_v2p_lds_bytes_c(WCO, WPX, DD), s, a);                                           \
-        else hipLaunchKernelGGL((conv_igemm_v2ps<WCO, WPX, DD>), dim3((unsigned)blocks), dim3(WCO * WPX * 64),                   \
-                                conv_v2p_lds_bytes_c(WCO, WPX, DD), s, a);                                                       \
-        return hipGetLastError();                                                                                                \
-    }
+    TileKernel tk{nullptr, cfg.wm, cfg.wp, halo};
+#define X(WCO, WPX, DD) \
+    if (cfg.wm == WCO && cfg.wp == WPX && halo == DD) tk.k = a.split_f16 ? conv_igemm_v2psh<WCO, WPX, DD> : conv_igemm_v2ps<WCO, WPX, DD>;
     IDC_FOR_EACH_CONV_V2PS(X)
 #undef X
-    return hipErrorInvalidConfiguration;
+    return tk.launch((long long)a.tiles_x * a.tiles_y * a.N * (a.ncg / cfg.wm), a, s);
 }
 
 hipError_t init_kernels_v2m() {
-    hipError_t e;
-#define X(WCO, WPX, DD)                                                                                                          \
-    e = hipFuncSetAttribute((const void*)conv_igemm_v2ps<WCO, WPX, DD>, hipFuncAttributeMaxDynamicSharedMemorySize,              \
-                            (int)conv_v2p_lds_bytes_c(WCO, WPX, DD));                                                            \
-    if (e != hipSuccess) return e;                                                                                               \
-    e = hipFuncSetAttribute((const void*)conv_igemm_v2psh<WCO, WPX, DD>, hipFuncAttributeMaxDynamicSharedMemorySize,             \
-                            (int)conv_v2p_lds_bytes_c(WCO, WPX, DD));                                                            \
-    if (e != hipSuccess) return e;
-    IDC_FOR_EACH_CONV_V2PS(X)
+    const TileKernel all[] = {
+#define X(WCO, WPX, DD) {conv_igemm_v2ps<WCO, WPX, DD>, WCO, WPX, DD}, {conv_igemm_v2psh<WCO, WPX, DD>, WCO, WPX, DD},
+        IDC_FOR_EACH_CONV_V2PS(X)
 #undef X
-#define X(WCO, WPX, HL)                                                                                                          \
-    e = hipFuncSetAttribute((const void*)conv_igemm_v2s<WCO, WPX, HL>, hipFuncAttributeMaxDynamicSharedMemorySize,               \
-                            (int)conv_v2m_lds_bytes_c(WCO, WPX, HL));                                                            \
-    if (e != hipSuccess) return e;                                                                                               \
-    e = hipFuncSetAttribute((const void*)conv_igemm_v2sh<WCO, WPX, HL>, hipFuncAttributeMaxDynamicSharedMemorySize,              \
-                            (int)conv_v2m_lds_bytes_c(WCO, WPX, HL));                                                            \
-    if (e != hipSuccess) return e;
-    IDC_FOR_EACH_CONV_V2S(X)
+#define X(WCO, WPX, HL) {conv_igemm_v2s<WCO, WPX, HL>, WCO, WPX, HL}, {conv_igemm_v2sh<WCO, WPX, HL>, WCO, WPX, HL},
+        IDC_FOR_EACH_CONV_V2S(X)
 #undef X
-#define X(WCO, WPX, DD)                                                                                                          \
-    e = hipFuncSetAttribute((const void*)conv_igemm_v2p<WCO, WPX, DD>, hipFuncAttributeMaxDynamicSharedMemorySize,               \
-                            (int)conv_v2p_lds_bytes_c(WCO, WPX, DD));                                                            \
-    if (e != hipSuccess) return e;                                                                                               \
-    e = hipFuncSetAttribute((const void*)conv_igemm_v2ph<WCO, WPX, DD>, hipFuncAttributeMaxDynamicSharedMemorySize,              \
-                            (int)conv_v2p_lds_bytes_c(WCO, WPX, DD));                                                            \
-    if (e != hipSuccess) return e;
-    IDC_FOR_EACH_CONV_V2P(X)
+#define X(WCO, WPX, DD) {conv_igemm_v2p<WCO, WPX, DD>, WCO, WPX, DD}, {conv_igemm_v2ph<WCO, WPX, DD>, WCO, WPX, DD},
+        IDC_FOR_EACH_CONV_V2P(X)
 #undef X
-#define X(WCO, WPX, HL)                                                                                                          \
-    e = hipFuncSetAttribute((const void*)conv_igemm_v2m<WCO, WPX, HL>, hipFuncAttributeMaxDynamicSharedMemorySize,               \
-                            (int)conv_v2m_lds_bytes_c(WCO, WPX, HL));                                                            \
-    if (e != hipSuccess) return e;
-    IDC_FOR_EACH_CONV_V2M(X)
+#define X(WCO, WPX, HL) {conv_igemm_v2m<WCO, WPX, HL>, WCO, WPX, HL},
+        IDC_FOR_EACH_CONV_V2M(X)
 #undef X
+    };
+    for (const TileKernel& tk : all) {
+        const hipError_t e = tk.raise_lds_limit();
+        if (e != hipSuccess) return e;
+    }
     return hipSuccess;
 }
 

@@ -30,21 +30,9 @@
 #include "idc_kernels.h"
 
 #include "idc_layout.h"
-
-#ifndef IDC_STAMP            // in-kernel cycle stamps exist only in the tuning harness (tools/ablate includes idc_kernels.hip first)
-#define IDC_STAMP(i) do {} while (0)
-#endif
+#include "idc_common.hip.h"
 
 namespace idc {
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-
-__device__ __forceinline__ int xcd_remap_w(int b, int nb) {
-    const int xcd = b & 7, q = nb >> 3, r = nb & 7;
-    const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + (b >> 3);
-}
 
 __device__ __forceinline__ f32x4 as_f(const u32x4& v) { return __builtin_bit_cast(f32x4, v); }
 
@@ -72,7 +60,7 @@ __global__ __launch_bounds__(kWinoNT, 2) void conv_wino_f32(const ConvArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     IDC_STAMP(0);
 
-    int b = xcd_remap_w(blockIdx.x, gridDim.x);
+    int b = xcd_remap(blockIdx.x, gridDim.x);
     // block order: tile blocks fastest, the cout group slowest -- each XCD (a contiguous range of the logical order) then
     // works on few cout groups whose U slices stay in that XCD's 4 MiB L2 for all tile blocks
     const int d = a.dy[8];                                     // dilation (tap (2,2) sits at +d)
@@ -529,7 +517,7 @@ __global__ __launch_bounds__(kWinoDNT, 3) void conv_wino_deconv_f32(const ConvAr
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    int b = xcd_remap_w(blockIdx.x, gridDim.x);
+    int b = xcd_remap(blockIdx.x, gridDim.x);
     const int bx = b % a.tiles_x; b /= a.tiles_x;
     const int by = b % a.tiles_y; b /= a.tiles_y;
     const int n = b % a.N;

@@ -157,7 +157,7 @@ def shift_difference(sd, glob, sat=None, fault=None, bn_scale=None):
 
 # ---- storage: what one unit in the last place of a stored value is --------------------------------------------------------------------
 # bits below the leading one of a value in [2^e, 2^(e+1)) that the storage keeps: bf16 7, fp16 10.  A split tensor is hi = rne(v),
-# next = rne(v - hi), ... (idc_split.hip.h): a remainder is at most half an ulp of the part above, so each further bf16 part starts
+# next = rne(v - hi), ... (idc_common.hip.h): a remainder is at most half an ulp of the part above, so each further bf16 part starts
 # 8 bits lower (two planes: the low part is below 2^(e-7), its ulp at most 2^(e-15); three: 2^(e-23)) and the fp16 pair's low part
 # 11 bits lower (ulp at most 2^(e-21)).
 _FRAC_BITS = {"bf16": 7, "fp16": 10, "bf16x3": 15, "bf16x6": 23, "fp16x3": 21, "fp32": 23}
