@@ -406,6 +406,46 @@ enum { IDC_SRC_NO_AB = 3 };               /* joins IDC_SRC_*: a = b = 0 */
 enum { IDC_L_IMAGE = 0, IDC_L_MASK50 = 1 };
 int idc_fullres_rgb(idc_handle h, int img, int source, int interp, int l_mode, uint8_t* rgb);
 
+/* ---- pipelined batches from uint8 images: the serving form of the two calls above on the two slots of idc_forward_async.
+ *      rgb_in [n,src_h,src_w,3] uint8 and per-image hint lists in, colourised uint8 images out; idc_wait completes the call and
+ *      idc_pipeline_times reports its stages (H2D: the images, the offsets and the hints; compute: the prologue kernel, the
+ *      network and the epilogue kernels; D2H: rgb_out and out_ab).  On the device, in one launch each for all n images:
+ *      the ingestion rule of idc_set_image_rgb (L - l_cent into the SLOT's L plane) together with the hint rasterisation
+ *      of idc_set_hints (image i's hints are hints[hint_offsets[i] .. hint_offsets[i+1]): clipped to the image, corners
+ *      inclusive, the later hint wins, uncovered pixels ab = 0 and mask = 0, mode IDC_HINT_AB or IDC_HINT_RGB for the whole
+ *      call; hint_offsets == NULL: no image has hints); then the network; then
+ *        rgb_out [n,H,W,3]          = what idc_forward_rgb returns for the same L, ab and mask (flags 0), or
+ *        rgb_out [n,src_h,src_w,3]  = get_img_fullres (colorize_image.py:123-131) of every image (IDC_BATCH_OUT_SOURCE): the
+ *                                     refreshed output_ab zoomed linearly to the source size under the L of the source pixels,
+ *                                     what idc_fullres_rgb with IDC_SRC_OUTPUT_AB, IDC_INTERP_LINEAR, IDC_L_IMAGE returns per image.
+ *      out_ab [n,2,H,W] receives the network's ab map; it may be NULL.  Bit-identical to the blocking route.
+ *      Cost of the hints: every net-size pixel walks its own image's clipped list, last hint first, until one covers it, so
+ *      a pixel that no hint covers reads the whole list: n * H * W * (hints per image) steps at worst, in one launch.  That
+ *      is meant for the tens of strokes of an editing session; IDC_BATCH_MAX_HINTS is the bound of the argument check, not
+ *      a size to serve (2^20 hints on one image of a 32 x 256 x 256 batch are 2e12 steps, seconds of one kernel).
+ *      Either entry point may use a slot, in any order.  The slot owns all it needs (source bytes, hint list, planes,
+ *      results, pinned staging for pageable callers), grown on demand: like idc_forward_async the call neither reads nor
+ *      replaces the handle's resident L / hint planes, kept sources, the mask_value of idc_set_hints or the ab map and
+ *      colour results of the last blocking forward.  The distribution heads are not part of this call, and the guarantee
+ *      does not extend to an IDC_FLAG_DIST313 handle: there every forward through the network, this one included, runs
+ *      the 313 head into the handle's pred_ab scratch, and while idc_keep_dist is on it also replaces the resident
+ *      distribution, which then belongs to this batch (images 0..n-1).  Without IDC_FLAG_DIST313, or with idc_keep_dist
+ *      off, the distribution of the last blocking forward stays resident and readable.
+ *      Pinned host buffers are transferred in place; all host buffers stay caller-owned and
+ *      untouched until idc_wait (hint_offsets and hints are consumed before the call returns).
+ *      Status, all decided on the host before anything is enqueued (a refused call leaves the slot as it was):
+ *      IDC_ERR_NO_WEIGHTS before weights are set; IDC_ERR_BATCH for n outside 1..max_batch; IDC_ERR_INVALID_ARG for a slot
+ *      outside 0..1 or still in flight, NULL rgb_in or rgb_out, src_h / src_w outside 1..16384, n * src_h * src_w * 3 above
+ *      IDC_BATCH_MAX_SOURCE_BYTES, unknown flag bits, a mode that is not 0 or 1, NULL hints while an offset is non-zero,
+ *      offsets that do not start at 0, decrease or end beyond IDC_BATCH_MAX_HINTS, an RGB hint colour outside 0..255;
+ *      IDC_ERR_UNSUPPORTED while the range audit is on. */
+enum { IDC_BATCH_OUT_SOURCE = 1 };
+#define IDC_BATCH_MAX_SOURCE_BYTES ((size_t)1 << 30)
+#define IDC_BATCH_MAX_HINTS (1 << 20)
+int idc_forward_async_rgb(idc_handle h, int slot, int n, int src_h, int src_w, const uint8_t* rgb_in, const int32_t* hint_offsets,
+                          const idc_hint* hints, int mode, float mask_value, float maskcent, float l_cent, unsigned flags,
+                          uint8_t* rgb_out, float* out_ab);
+
 /* ---- colour picker on the device: replaces data/lab_gamut.py, the host colour maths the GUI runs on every mouse press
  *      (ui/gui_draw.py:11,182-183,195-204; ui/gui_gamut.py:4), in float64 with the constants and operation order of idc_lab2rgb.
  *      idc_gamut_map = abGrid(gamut_size, D).update_gamut(L[k]) (lab_gamut.py:56-78) for k = 0..n-1 in one launch.  The grid has

@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = [
     "idc_dist_entropy", "idc_dist_decode",
     "idc_stream_wait", "idc_stream_signal", "idc_alloc_host", "idc_free_host", "idc_forward_async", "idc_wait", "idc_pipeline_times",
     "idc_comm_unique_id", "idc_broadcast_weights", "idc_upsample_lab2rgb", "idc_set_image_rgb", "idc_fullres_rgb",
+    "idc_forward_async_rgb",
     "idc_gamut_map", "idc_snap_colors",
     "idc_set_range_audit", "idc_range_reset", "idc_range_report", "idc_pack_weights_ex", "idc_load_weights_ex",
 ]
@@ -38,6 +39,8 @@ IDC_INTERP_CUBIC, IDC_INTERP_LINEAR, IDC_INTERP_NEAREST = 0, 1, 2
 IDC_SRC_OUTPUT_AB, IDC_SRC_OUTPUT_AB_RAW, IDC_SRC_INPUT_AB, IDC_SRC_NO_AB = 0, 1, 2, 3
 IDC_INGEST_KEEP_SOURCE = 1
 IDC_L_IMAGE, IDC_L_MASK50 = 0, 1
+IDC_BATCH_OUT_SOURCE = 1
+IDC_BATCH_MAX_SOURCE_BYTES, IDC_BATCH_MAX_HINTS = 1 << 30, 1 << 20
 IDC_GAMUT_MAX_MAPS, IDC_GAMUT_MAX_SIZE, IDC_SNAP_MAX_COLORS = 64, 512, 65536
 IDC_UNIQUE_ID_BYTES = 128
 IDC_HINT_AB, IDC_HINT_RGB = 0, 1
@@ -161,6 +164,7 @@ def load():
     proto("idc_upsample_lab2rgb", ci, [vp, ci, ci, ci, ci, ci, vp, vp])
     proto("idc_set_image_rgb", ci, [vp, ci, ci, ci, ci, vp, cf, ctypes.c_uint, vp, vp])
     proto("idc_fullres_rgb", ci, [vp, ci, ci, ci, ci, vp])
+    proto("idc_forward_async_rgb", ci, [vp, ci, ci, ci, ci, vp, vp, vp, ci, cf, cf, cf, ctypes.c_uint, vp, vp])
     proto("idc_gamut_map", ci, [vp, ci, vp, ci, ci, vp, vp, vp])
     proto("idc_snap_colors", ci, [vp, ci, vp, vp, vp, vp, vp])
     proto("idc_set_range_audit", ci, [vp, ci])

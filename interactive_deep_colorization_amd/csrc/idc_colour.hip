@@ -461,6 +461,128 @@ hipError_t launch_fullres_rgb(const unsigned char* src, int oh, int ow, const vo
 }
 
 // ------------------------------------------------------------------------------------------------
+// pipelined uint8 batches (idc_forward_async_rgb): what idc_set_image_rgb + idc_set_hints per image do before a blocking forward and what
+// idc_fullres_rgb per image does after it, each as ONE launch over a slot's packed arrays.  The per-pixel arithmetic is the device functions
+// above on the same operands, so a batch equals the blocking route bit for bit.
+// ------------------------------------------------------------------------------------------------
+// One thread per net-size pixel of all n images, grid-stride.  L: ingest_rgb_kernel's pixel (four clamped uint8 taps of image i, which starts at
+// byte i * src_h * src_w * 3 of the packed source; the taps are byte gathers, so no alignment is asked of an image's start).  Hints: image i's
+// clipped list hints[offs[i] .. offs[i+1]) walked last first, raster_hints_kernel's pixel; an RGB hint goes through the LDS table, whose
+// entries are the per-colour expression of raster_hints_kernel.  The three planes are written as coalesced fp32.
+__global__ __launch_bounds__(256) void batch_prologue_kernel(const unsigned char* __restrict__ src, int n, int src_h, int src_w, int H, int W,
+                                                             float l_cent, const int* __restrict__ offs, const HintRect* __restrict__ hints,
+                                                             int mode, float mask_value, float* __restrict__ Lp, float* __restrict__ ab,
+                                                             float* __restrict__ mask) {
+    __shared__ double tab[256];
+    fill_srgb_table(tab);
+    const long long HW = (long long)H * W, npix = (long long)n * HW, sb = (long long)src_h * src_w * 3;
+    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (long long)gridDim.x * blockDim.x) {
+        const long long i = p / HW, r = p - i * HW;
+        const int y = (int)(r / W), x = (int)(r - (long long)y * W);
+        int y0, y1, x0, x1;
+        double wy, wx;
+        bilinear_taps(y, src_h, H, y0, y1, wy);
+        bilinear_taps(x, src_w, W, x0, x1, wx);
+        const unsigned char* img = src + i * sb;
+        const unsigned char* p00 = img + ((long long)y0 * src_w + x0) * 3; const unsigned char* p01 = img + ((long long)y0 * src_w + x1) * 3;
+        const unsigned char* p10 = img + ((long long)y1 * src_w + x0) * 3; const unsigned char* p11 = img + ((long long)y1 * src_w + x1) * 3;
+        double lin[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) lin[c] = tab[bilinear_u8((double)p00[c], (double)p01[c], (double)p10[c], (double)p11[c], wx, wy)];
+        double L, a_, b_;
+        linear_to_lab(lin, L, a_, b_);
+        Lp[p] = (float)(L - (double)l_cent);
+        const int lo = offs != nullptr ? offs[i] : 0, hi = offs != nullptr ? offs[i + 1] : 0;
+        int hit = -1;
+        for (int k = hi - 1; k >= lo; --k) {
+            const HintRect h = hints[k];
+            if (y >= h.y0 && y <= h.y1 && x >= h.x0 && x <= h.x1) { hit = k; break; }
+        }
+        float a = 0.f, b = 0.f, m = 0.f;
+        if (hit >= 0) {
+            const HintRect h = hints[hit];
+            m = mask_value;
+            if (mode == 0) {
+                a = h.c0; b = h.c1;
+            } else {
+                const double hl[3] = {tab[(unsigned char)h.c0], tab[(unsigned char)h.c1], tab[(unsigned char)h.c2]};
+                double hL, da, db;
+                linear_to_lab(hl, hL, da, db);
+                a = (float)da; b = (float)db;
+            }
+        }
+        ab[(i * 2 + 0) * HW + r] = a;
+        ab[(i * 2 + 1) * HW + r] = b;
+        mask[p] = m;
+    }
+}
+
+hipError_t launch_batch_prologue(const unsigned char* src, int n, int src_h, int src_w, int H, int W, float l_cent, const int* offs,
+                                 const HintRect* hints, int mode, float mask_value, float* Lp, float* ab, float* mask, hipStream_t s) {
+    const long long npix = (long long)n * H * W;
+    if (npix <= 0 || src_h <= 0 || src_w <= 0 || (mode != 0 && mode != 1)) return hipErrorInvalidValue;
+    const int blocks = (int)((npix + 255) / 256 < 4096 ? (npix + 255) / 256 : 4096);
+    hipLaunchKernelGGL(batch_prologue_kernel, dim3(blocks), dim3(256), 0, s, src, n, src_h, src_w, H, W, l_cent, offs, hints, mode, mask_value, Lp, ab,
+                       mask);
+    return hipGetLastError();
+}
+
+// fullres_rgb_kernel over a packed [n,oh,ow,3] batch.  Image i starts at byte i * oh * ow * 3, misaligned whenever that count is no multiple of
+// 4, so neither an aligned pitch nor a scalar head and tail per image is used: the n * oh * ow pixels are taken as ONE flat run from the
+// 4-byte aligned base of the allocation.  A thread takes 4 consecutive pixels of that run = three aligned dwords in, three out, as in
+// fullres_rgb_kernel; a group may straddle two images, and every pixel finds its own image and position (one division per group, then a
+// carry).  Only the (n * oh * ow) % 4 pixels at the end of the whole batch go through byte accesses.  The arrays stay packed, so they travel
+// as one contiguous copy each way.
+__global__ __launch_bounds__(256) void batch_fullres_rgb_kernel(const unsigned char* __restrict__ src, long long total, int oh, int ow,
+                                                                const double* __restrict__ lab_q, int H, int W, int interp,
+                                                                unsigned char* __restrict__ rgb) {
+    __shared__ double tab[256];
+    fill_srgb_table(tab);
+    const long long npix = (long long)oh * ow, HW = (long long)H * W, ngroups = total >> 2;
+    const unsigned* src4 = (const unsigned*)src;
+    unsigned* rgb4 = (unsigned*)rgb;
+    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (long long)gridDim.x * blockDim.x) {
+        const unsigned in[3] = {src4[g * 3 + 0], src4[g * 3 + 1], src4[g * 3 + 2]};
+        unsigned out[3] = {0u, 0u, 0u};
+        long long i = (g * 4) / npix, p = g * 4 - i * npix;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            int q[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) q[c] = (int)((in[(k * 3 + c) >> 2] >> (8 * ((k * 3 + c) & 3))) & 255u);
+            unsigned char o[3];
+            const double* pa = lab_q + (i * 3 + 1) * HW;
+            fullres_pixel(p, q, tab, pa, pa + HW, H, W, interp, (const float*)nullptr, 0.f, oh, ow, o);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) out[(k * 3 + c) >> 2] |= (unsigned)o[c] << (8 * ((k * 3 + c) & 3));
+            if (++p == npix) { p = 0; ++i; }
+        }
+        rgb4[g * 3 + 0] = out[0]; rgb4[g * 3 + 1] = out[1]; rgb4[g * 3 + 2] = out[2];
+    }
+    if (blockIdx.x == 0) {
+        const long long t = ngroups * 4 + threadIdx.x;
+        if (t < total) {
+            const long long i = t / npix, p = t - i * npix;
+            const int q[3] = {src[t * 3 + 0], src[t * 3 + 1], src[t * 3 + 2]};
+            unsigned char o[3];
+            const double* pa = lab_q + (i * 3 + 1) * HW;
+            fullres_pixel(p, q, tab, pa, pa + HW, H, W, interp, (const float*)nullptr, 0.f, oh, ow, o);
+            rgb[t * 3 + 0] = o[0]; rgb[t * 3 + 1] = o[1]; rgb[t * 3 + 2] = o[2];
+        }
+    }
+}
+
+hipError_t launch_batch_fullres_rgb(const unsigned char* src, int n, int oh, int ow, const double* lab_q, int H, int W, int interp,
+                                    unsigned char* rgb, hipStream_t s) {
+    const long long total = (long long)n * oh * ow;
+    if (n <= 0 || oh <= 0 || ow <= 0 || interp < 0 || interp > 2 || (((uintptr_t)src | (uintptr_t)rgb) & 3)) return hipErrorInvalidValue;
+    const long long ngroups = (total + 3) >> 2;
+    const int blocks = (int)((ngroups + 255) / 256 < 8192 ? (ngroups + 255) / 256 : 8192);
+    hipLaunchKernelGGL(batch_fullres_rgb_kernel, dim3(blocks), dim3(256), 0, s, src, total, oh, ow, lab_q, H, W, interp, rgb);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
 // colour picker: data/lab_gamut.py, which the GUI runs on the host on every mouse press (ui/gui_draw.py:182-183,195-204).  Latency kernels of
 // at most a few hundred workgroups: one thread per grid point / per colour, the float64 conversions above.
 // ------------------------------------------------------------------------------------------------

@@ -207,6 +207,12 @@ struct idc_context {
         Event ev_in0, ev_comp0, ev_out0;                                               // stage starts (idc_pipeline_times)
         bool pending = false, staged_out = false, timed = false;
         float* user_out = nullptr; int n = 0;
+        // idc_forward_async_rgb: the batch's packed uint8 source, its offsets + clipped hint list (one block: int[n+1], then HintRect[] at
+        // rgb_meta_hints), the net-size result, the refreshed Lab and the source-size result (IDC_BATCH_OUT_SOURCE); grown on demand
+        DevMem<unsigned char> d_src, d_meta, d_rgb, d_full;
+        DevMem<double> d_labq;
+        PinnedMem<unsigned char> h_src, h_meta, h_rgb;                                 // pinned staging: pageable source, the list, pageable rgb_out
+        uint8_t* user_rgb = nullptr; size_t rgb_bytes = 0; bool staged_rgb = false;    // user_rgb == nullptr: the slot's batch was an idc_forward_async
     } pipe[2];
     Event ev_pipe_base;
     bool pipe_ready = false;             // ev_pipe_base is recorded (ensure_pipeline)

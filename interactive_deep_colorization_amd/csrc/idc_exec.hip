@@ -354,7 +354,8 @@ static int wait_slot(idc_context* h, int slot) {
     sl.pending = false;
     const int arc = check_chain_abort(h);      // the forward this slot carried ran a chain launch that gave up: its result is invalid
     if (arc) return arc;
-    if (sl.staged_out) memcpy(sl.user_out, sl.h_out.get(), (size_t)sl.n * h->H * h->W * 2 * 4);
+    if (sl.staged_out && sl.user_out) memcpy(sl.user_out, sl.h_out.get(), (size_t)sl.n * h->H * h->W * 2 * 4);
+    if (sl.staged_rgb && sl.user_rgb) memcpy(sl.user_rgb, sl.h_rgb.get(), sl.rgb_bytes);
     return IDC_OK;
 }
 
@@ -529,6 +530,119 @@ int idc_forward_async(idc_handle h, int slot, int n, const float* L_mc, const fl
     HIPCHK(h, hipMemcpyAsync(sl.staged_out ? sl.h_out.get() : out_ab, sl.d_out.get(), (size_t)n * hw * 2 * 4, hipMemcpyDeviceToHost, h->s_out.get()));
     HIPCHK(h, hipEventRecord(sl.ev_out.get(), h->s_out.get()));
     sl.pending = true; sl.timed = true; sl.user_out = out_ab; sl.n = n;
+    sl.user_rgb = nullptr; sl.staged_rgb = false;
+    return IDC_OK;
+}
+
+// The serving form of the product: uint8 images and hint lists in, colourised uint8 images out, on the same two slots.  The slot owns the
+// packed source, the clipped hint list, its planes and its results; every argument is checked before anything is enqueued.
+int idc_forward_async_rgb(idc_handle h, int slot, int n, int src_h, int src_w, const uint8_t* rgb_in, const int32_t* hint_offsets,
+                          const idc_hint* hints, int mode, float mask_value, float maskcent, float l_cent, unsigned flags,
+                          uint8_t* rgb_out, float* out_ab) {
+    int rc = check_forward_args(h, n);
+    if (rc) return rc;
+    if (slot < 0 || slot > 1) return fail(&h->err, IDC_ERR_INVALID_ARG, "slot %d not in 0..1", slot);
+    if (!rgb_in || !rgb_out) return fail(&h->err, IDC_ERR_INVALID_ARG, "null image pointer");
+    if (flags & ~(unsigned)IDC_BATCH_OUT_SOURCE) return fail(&h->err, IDC_ERR_INVALID_ARG, "unknown flag bits 0x%x", flags);
+    if (mode != IDC_HINT_AB && mode != IDC_HINT_RGB) return fail(&h->err, IDC_ERR_INVALID_ARG, "hint mode %d", mode);
+    if (src_h < 1 || src_h > 16384 || src_w < 1 || src_w > 16384)
+        return fail(&h->err, IDC_ERR_INVALID_ARG, "source size %dx%d outside 1..16384", src_h, src_w);
+    const size_t sb = (size_t)src_h * src_w * 3, in_bytes = (size_t)n * sb;
+    if (in_bytes > IDC_BATCH_MAX_SOURCE_BYTES)
+        return fail(&h->err, IDC_ERR_INVALID_ARG, "%d sources of %dx%d are more than %zu bytes", n, src_h, src_w, (size_t)IDC_BATCH_MAX_SOURCE_BYTES);
+    int n_hints = 0;
+    if (hint_offsets) {
+        if (hint_offsets[0] != 0) return fail(&h->err, IDC_ERR_INVALID_ARG, "hint_offsets[0] is %d, not 0", hint_offsets[0]);
+        for (int i = 0; i < n; ++i)
+            if (hint_offsets[i + 1] < hint_offsets[i]) return fail(&h->err, IDC_ERR_INVALID_ARG, "hint_offsets decrease at image %d", i);
+        n_hints = hint_offsets[n];
+        if (n_hints > IDC_BATCH_MAX_HINTS) return fail(&h->err, IDC_ERR_INVALID_ARG, "%d hints, more than %d", n_hints, IDC_BATCH_MAX_HINTS);
+        if (n_hints > 0 && !hints) return fail(&h->err, IDC_ERR_INVALID_ARG, "null hints with a non-zero offset");
+    }
+    // cv2.rectangle, as idc_set_hints reads a hint: corners in either order, inclusive, clipped; false = entirely outside the image
+    auto clip = [&](const idc_hint& u, HintRect& r) {
+        r.y0 = u.y0 < u.y1 ? u.y0 : u.y1; r.y1 = u.y0 < u.y1 ? u.y1 : u.y0;
+        r.x0 = u.x0 < u.x1 ? u.x0 : u.x1; r.x1 = u.x0 < u.x1 ? u.x1 : u.x0;
+        if (r.y0 < 0) r.y0 = 0;
+        if (r.x0 < 0) r.x0 = 0;
+        if (r.y1 > h->H - 1) r.y1 = h->H - 1;
+        if (r.x1 > h->W - 1) r.x1 = h->W - 1;
+        r.c0 = u.c0; r.c1 = u.c1; r.c2 = u.c2;
+        return r.y0 <= r.y1 && r.x0 <= r.x1;
+    };
+    int kept = 0;
+    for (int k = 0; k < n_hints; ++k) {
+        HintRect r;
+        if (!clip(hints[k], r)) continue;
+        if (mode == IDC_HINT_RGB && !(r.c0 >= 0.f && r.c0 <= 255.f && r.c1 >= 0.f && r.c1 <= 255.f && r.c2 >= 0.f && r.c2 <= 255.f))
+            return fail(&h->err, IDC_ERR_INVALID_ARG, "hint %d: RGB outside 0..255", k);
+        ++kept;
+    }
+    if (h->audit) return fail(&h->err, IDC_ERR_UNSUPPORTED, "the range audit covers the blocking, resident and device-pointer forwards, not the pipelined slots");
+    auto& sl = h->pipe[slot];
+    if (sl.pending) return fail(&h->err, IDC_ERR_INVALID_ARG, "slot %d is still in flight: idc_wait it first", slot);
+    HIPCHK(h, hipSetDevice(h->device));
+    rc = ensure_pipeline(h);
+    if (rc) return rc;
+    // The slot is idle (its last batch was waited for), so its buffers may be replaced by larger ones
+    const size_t hw = (size_t)h->H * h->W, nb = (size_t)h->max_batch;
+    const bool source_out = (flags & IDC_BATCH_OUT_SOURCE) != 0;
+    const size_t rgb_bytes = source_out ? in_bytes : (size_t)n * hw * 3;
+    const size_t hints_at = align_up((nb + 1) * sizeof(int), 16), meta_bytes = hints_at + (size_t)kept * sizeof(HintRect);
+    const size_t meta_floor = hints_at + 256 * sizeof(HintRect);
+    HIPCHK(h, sl.d_src.ensure(in_bytes));
+    HIPCHK(h, sl.d_meta.ensure(meta_bytes, meta_floor));
+    HIPCHK(h, sl.h_meta.ensure(meta_bytes, meta_floor));
+    HIPCHK(h, sl.d_rgb.ensure(nb * hw * 3));
+    if (source_out) {
+        HIPCHK(h, sl.d_labq.ensure(nb * hw * 3 * 8));
+        HIPCHK(h, sl.d_full.ensure(in_bytes));
+    }
+    const uint8_t* s_rgb = rgb_in;
+    if (!is_pinned(rgb_in)) {
+        HIPCHK(h, sl.h_src.ensure(in_bytes));
+        memcpy(sl.h_src.get(), rgb_in, in_bytes);
+        s_rgb = sl.h_src.get();
+    }
+    const bool staged_rgb = !is_pinned(rgb_out), staged_ab = out_ab && !is_pinned(out_ab);
+    if (staged_rgb) HIPCHK(h, sl.h_rgb.ensure(rgb_bytes));
+    if (staged_ab) HIPCHK(h, sl.h_out.ensure(nb * hw * 2 * 4));
+    // the list as the kernel reads it: offsets of the KEPT hints per image, then the clipped rectangles
+    int* m_offs = (int*)sl.h_meta.get();
+    HintRect* m_hints = (HintRect*)(sl.h_meta.get() + hints_at);
+    m_offs[0] = 0;
+    for (int i = 0, w = 0; i < n; ++i) {
+        for (int k = hint_offsets ? hint_offsets[i] : 0; k < (hint_offsets ? hint_offsets[i + 1] : 0); ++k) {
+            HintRect r;                               // clip fills r even for a hint it drops: only a kept one may reach the block, which has room for `kept`
+            if (clip(hints[k], r)) m_hints[w++] = r;
+        }
+        m_offs[i + 1] = w;
+    }
+    HIPCHK(h, hipEventRecord(sl.ev_in0.get(), h->s_in.get()));
+    HIPCHK(h, hipMemcpyAsync(sl.d_src.get(), s_rgb, in_bytes, hipMemcpyHostToDevice, h->s_in.get()));
+    HIPCHK(h, hipMemcpyAsync(sl.d_meta.get(), sl.h_meta.get(), meta_bytes, hipMemcpyHostToDevice, h->s_in.get()));
+    HIPCHK(h, hipEventRecord(sl.ev_in.get(), h->s_in.get()));
+    HIPCHK(h, hipStreamWaitEvent(h->stream.get(), sl.ev_in.get(), 0));
+    HIPCHK(h, hipEventRecord(sl.ev_comp0.get(), h->stream.get()));
+    HIPCHK(h, launch_batch_prologue(sl.d_src.get(), n, src_h, src_w, h->H, h->W, l_cent, kept ? (const int*)sl.d_meta.get() : nullptr,
+                                    (const HintRect*)(sl.d_meta.get() + hints_at), mode, mask_value, sl.d_L.get(), sl.d_ab.get(), sl.d_mask.get(),
+                                    h->stream.get()));
+    const int dist_n = h->dist_n;
+    rc = run_graph(h, n, sl.d_L.get(), sl.d_ab.get(), sl.d_mask.get(), maskcent, sl.d_out.get(), nullptr);
+    if (rc) return rc;
+    if (!((h->flags & IDC_FLAG_DIST313) && h->keep_dist313)) h->dist_n = dist_n;      // no distribution was written: the blocking forward's stays resident
+    HIPCHK(h, launch_lab_post(sl.d_L.get(), l_cent, sl.d_out.get(), sl.d_rgb.get(), source_out ? sl.d_labq.get() : nullptr, n, h->H, h->W, h->stream.get()));
+    if (source_out)
+        HIPCHK(h, launch_batch_fullres_rgb(sl.d_src.get(), n, src_h, src_w, sl.d_labq.get(), h->H, h->W, IDC_INTERP_LINEAR, sl.d_full.get(), h->stream.get()));
+    HIPCHK(h, hipEventRecord(sl.ev_comp.get(), h->stream.get()));
+    HIPCHK(h, hipStreamWaitEvent(h->s_out.get(), sl.ev_comp.get(), 0));
+    HIPCHK(h, hipEventRecord(sl.ev_out0.get(), h->s_out.get()));
+    HIPCHK(h, hipMemcpyAsync(staged_rgb ? sl.h_rgb.get() : rgb_out, source_out ? sl.d_full.get() : sl.d_rgb.get(), rgb_bytes, hipMemcpyDeviceToHost, h->s_out.get()));
+    if (out_ab) HIPCHK(h, hipMemcpyAsync(staged_ab ? sl.h_out.get() : out_ab, sl.d_out.get(), (size_t)n * hw * 2 * 4, hipMemcpyDeviceToHost, h->s_out.get()));
+    HIPCHK(h, hipEventRecord(sl.ev_out.get(), h->s_out.get()));
+    sl.pending = true; sl.timed = true; sl.n = n;
+    sl.user_out = out_ab; sl.staged_out = staged_ab;
+    sl.user_rgb = rgb_out; sl.staged_rgb = staged_rgb; sl.rgb_bytes = rgb_bytes;
     return IDC_OK;
 }
 

@@ -277,6 +277,16 @@ struct HintRect { int y0, x0, y1, x1; float c0, c1, c2; };
 hipError_t launch_raster_hints(const HintRect* hints, int n_hints, int mode, float mask_value, float* ab, float* mask,
                                int H, int W, hipStream_t s);
 
+// Pipelined uint8 batches (idc_forward_async_rgb; idc_colour.hip), ONE launch each for all n images.
+// batch_prologue: src [n,src_h,src_w,3] u8 packed -> Lp [n][H*W] = L - l_cent by launch_ingest_rgb's rule, and per pixel the LAST hint of
+// hints[offs[i] .. offs[i+1]) (already clipped, as for launch_raster_hints) that covers it -> ab [n,2,H,W], mask [n,1,H,W]; offs == nullptr: no
+// image has hints.  batch_fullres_rgb: launch_fullres_rgb's pixel (L of the source pixel, (a, b) = planes 1 and 2 of image i's lab_q [n,3,H,W]
+// f64 resized by `interp`) for every pixel of src [n,oh,ow,3] -> rgb [n,oh,ow,3], both packed and 4-byte aligned at their base only.
+hipError_t launch_batch_prologue(const unsigned char* src, int n, int src_h, int src_w, int H, int W, float l_cent, const int* offs,
+                                 const HintRect* hints, int mode, float mask_value, float* Lp, float* ab, float* mask, hipStream_t s);
+hipError_t launch_batch_fullres_rgb(const unsigned char* src, int n, int oh, int ow, const double* lab_q, int H, int W, int interp,
+                                    unsigned char* rgb, hipStream_t s);
+
 // Colour suggestions at one pixel (get_ab_reccs, colorize_image.py:322-354): see idc_session.hip for the algorithm.
 // pdf bin b at pdf[b*stride]; centres [B][2]; out_centres [K][2], out_conf [K] (f64); out_counts [B] or nullptr.
 constexpr int kSuggestMaxBins = 1024, kSuggestMaxK = 16;

@@ -312,6 +312,27 @@ def trim_pinned_pool():
         pool.drain()
 
 
+def flatten_hints(hints, n):
+    """Per-image hint lists -> what ``idc_forward_async_rgb`` reads: (offsets (n+1,) int32, ``N.Hint`` array).  ``hints``: ``None`` (no image
+    has hints: (None, None)) or n entries, each ``None`` / a list of rows (y0, x0, y1, x1, c0, c1[, c2]) as in ``set_hints``; image i's rows
+    are ``[offsets[i], offsets[i+1])`` of the array."""
+    if hints is None:
+        return None, None
+    lists = [[] if h is None else [tuple(r) for r in h] for h in hints]
+    if len(lists) != n:
+        raise ValueError("%d hint lists for %d images" % (len(lists), n))
+    offsets = np.zeros(n + 1, np.int32)
+    offsets[1:] = np.cumsum([len(l) for l in lists])
+    arr = (N.Hint * max(int(offsets[-1]), 1))()
+    k = 0
+    for rows in lists:
+        for r in rows:
+            arr[k].y0, arr[k].x0, arr[k].y1, arr[k].x1 = int(r[0]), int(r[1]), int(r[2]), int(r[3])
+            arr[k].c0, arr[k].c1, arr[k].c2 = float(r[4]), float(r[5]), float(r[6]) if len(r) > 6 else 0.0
+            k += 1
+    return offsets, arr
+
+
 class HipColorizer(object):
     def __init__(self, H=256, W=None, max_batch=1, precision="bf16", device=0, dist=False, global_hints=False, dist313=False,
                  throughput_blob=False):
@@ -331,6 +352,9 @@ class HipColorizer(object):
                                     ctypes.byref(self._h)))
         self._blob_keepalive = None
         self._pool = _result_pool(self.lib)
+        # pipeline slot -> the arrays forward_async_rgb handed to the library, held until wait(slot).  A blocking call drains the slots inside the
+        # library, so an entry can outlive its batch until that slot's next wait or forward_async_rgb: it only keeps the arrays alive longer
+        self._in_flight = {}
         self.forward_serial = 0             # bumped by every call that replaces the handle's resident results (api.py's lazy output attributes)
         self.l_serial = 0                   # bumped by every call that may write image slot 0's L plane (set_image_l and every forward): api.py's resident L
         self._src_shape = {}                # image slot -> (h, w) of the source set_image_rgb(keep_source=True) left on the device
@@ -787,8 +811,72 @@ class HipColorizer(object):
         self._results_will_be_replaced()
         self._chk(self.lib.idc_forward_async(self._h, int(slot), int(n), _fptr(L_mc), _fptr(ab), _fptr(mask), float(maskcent), _fptr(out)))
 
+    def forward_async_rgb(self, slot, rgb, hints, out_rgb, out_ab=None, mode="ab", mask_value=1.0, maskcent=0.0, l_cent=50.0, out="net"):
+        """Enqueue one batch of uint8 images on pipeline slot 0/1 (``idc_forward_async_rgb``): rgb (n,h,w,3) uint8 C-contiguous, any size up
+        to 16384 a side, is ingested as by ``set_image_rgb``; ``hints`` is a list of n per-image hint lists (rows as in ``set_hints``, ``None``
+        or [] for an image without) or ``None``.  ``out_rgb`` uint8 receives the colourised images: (n,H,W,3) with out='net' (what
+        ``forward_rgb`` returns), (n,h,w,3) with out='source' (``fullres_rgb('output_ab', 'linear', 'image')`` of every image); ``out_ab``
+        (n,2,H,W) float32 or None the network's ab map.  The arrays are used in place: leave them untouched until ``wait(slot)`` (the engine
+        holds a reference to each until then, so a caller that drops its own cannot have the result written into freed memory)."""
+        if not isinstance(rgb, np.ndarray) or rgb.dtype != np.uint8 or rgb.ndim != 4 or rgb.shape[3] != 3 or not rgb.flags.c_contiguous:
+            raise ValueError("forward_async_rgb needs a uint8 C-contiguous (n,h,w,3) array")
+        n, sh, sw = rgb.shape[:3]
+        flags = {"net": 0, "source": N.IDC_BATCH_OUT_SOURCE}[out]
+        shp = (n, sh, sw, 3) if flags else (n, self.H, self.W, 3)
+        if not isinstance(out_rgb, np.ndarray) or out_rgb.dtype != np.uint8 or not out_rgb.flags.c_contiguous or tuple(out_rgb.shape) != shp:
+            raise ValueError("forward_async_rgb needs a uint8 C-contiguous out_rgb of shape %s" % (shp,))
+        if out_ab is not None and (out_ab.dtype != np.float32 or not out_ab.flags.c_contiguous or tuple(out_ab.shape) != (n, 2, self.H, self.W)):
+            raise ValueError("forward_async_rgb needs a float32 C-contiguous out_ab of shape %s" % ((n, 2, self.H, self.W),))
+        offsets, arr = flatten_hints(hints, n)
+        vp = ctypes.c_void_p
+        self._chk(self.lib.idc_forward_async_rgb(self._h, int(slot), int(n), int(sh), int(sw), rgb.ctypes.data_as(vp),
+                                                 offsets.ctypes.data_as(vp) if offsets is not None else None,
+                                                 ctypes.cast(arr, vp) if arr is not None else None,
+                                                 {"ab": N.IDC_HINT_AB, "rgb": N.IDC_HINT_RGB}[mode], float(mask_value), float(maskcent),
+                                                 float(l_cent), flags, out_rgb.ctypes.data_as(vp),
+                                                 out_ab.ctypes.data_as(vp) if out_ab is not None else None))
+        self._in_flight[int(slot)] = (rgb, out_rgb, out_ab)      # the library reads / writes them until the slot's wait
+
+    def colorize_stream(self, batches, out="net", **kw):
+        """Generator: colourise a stream of uint8 batches with both pipeline slots busy.  ``batches`` yields (rgb (n,h,w,3) uint8, hints) items
+        (``hints`` as in ``forward_async_rgb``; n and the source size may change from item to item); each item's (n,H,W,3) [out='net'] or
+        (n,h,w,3) [out='source'] uint8 result is yielded in input order, as an array of the caller's own (copied out of the pinned buffer the
+        device wrote).  Item k runs on slot k % 2 while item k - 1 computes; its buffers come from the pinned pool.  ``kw``: mode, mask_value,
+        maskcent, l_cent of ``forward_async_rgb``."""
+        pending = [None, None]                      # per slot: (pinned result, pinned source) of the batch in flight
+
+        def finish(slot):
+            self.wait(slot)
+            res, pending[slot] = pending[slot][0], None
+            return np.array(res)
+
+        k = 0
+        try:
+            for rgb, hints in batches:
+                slot = k & 1
+                if pending[slot] is not None:
+                    yield finish(slot)
+                rgb = np.asarray(rgb)
+                if rgb.dtype != np.uint8 or rgb.ndim != 4 or rgb.shape[3] != 3:
+                    raise ValueError("colorize_stream needs uint8 (n,h,w,3) batches, got %s %s" % (rgb.dtype, rgb.shape))
+                src = self._pool.take(rgb.shape, np.uint8)
+                np.copyto(src, rgb)
+                dst = self._pool.take(rgb.shape if out == "source" else (rgb.shape[0], self.H, self.W, 3), np.uint8)
+                self.forward_async_rgb(slot, src, hints, dst, out=out, **kw)
+                pending[slot] = (dst, src)
+                k += 1
+            for slot in (k & 1, (k + 1) & 1):       # the older batch first
+                if pending[slot] is not None:
+                    yield finish(slot)
+        finally:                                    # a consumer that stops early: nothing stays in flight on buffers about to be recycled
+            for slot in (0, 1):
+                if pending[slot] is not None:
+                    pending[slot] = None
+                    self.wait(slot)
+
     def wait(self, slot):
         self._chk(self.lib.idc_wait(self._h, int(slot)))
+        self._in_flight.pop(int(slot), None)
 
     def pipeline_times(self, slot):
         """ms since the pipeline's first use of (H2D start, H2D end, compute start, compute end, D2H start, D2H end) of the
