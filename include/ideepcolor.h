@@ -446,6 +446,53 @@ int idc_forward_async_rgb(idc_handle h, int slot, int n, int src_h, int src_w, c
                           const idc_hint* hints, int mode, float mask_value, float maskcent, float l_cent, unsigned flags,
                           uint8_t* rgb_out, float* out_ab);
 
+/* ---- reference-image global hints on the device: "colourise in the palette of a reference photograph" from the photograph's own
+ *      uint8 bytes.  Replaces the notebook's get_global_histogram INCLUDING its resize (DemoGlobalHistogramTransfer.ipynb:176-186:
+ *      caffe.io.resize_image to the net size, then the global_stats.prototxt net) and the filling of glob_ab_313_mask / s_avg_mask
+ *      (colorize_image.py:451-459) -- idc_global_histogram + idc_set_global_hints without the histogram's round trip over the host.
+ *      refs [m]: host images [h,w,3] uint8 of INDIVIDUAL sizes (1..16384 a side, IDC_BATCH_MAX_SOURCE_BYTES in all).  Each is sampled to
+ *      the handle's H x W by the ingestion rule of idc_set_image_rgb (bilinear, half-pixel centres, clamped taps, float64, round half up;
+ *      the identity at h == H and w == W), then idc_global_histogram's statistics: rgb2lab, 4x4 mean of ab in float64, fp32 nearest of the
+ *      centres [313,2] (lowest index on a tie), integer counts; and the mean HSV saturation.  A net-size reference gives
+ *      idc_global_histogram's histogram bit for bit.  The saturation is summed in a fixed order (no float atomics): every figure of a
+ *      reference is bitwise reproducible and depends on nothing but its own pixels and (H, W) -- not on m, not on its neighbours.
+ *      DEVIATION: the reference resizes with caffe.io.resize_image (skimage, order 1), which is not runnable here; this is the
+ *      project's ingestion rule, the one load_image's replacement uses.  Both are the identity at the net size.
+ *      idc_global_stats_rgb: hist [m,313] (rows sum to 1) and s_avg [m] (may be NULL) to the host.  Needs a handle, no weights and no
+ *      IDC_FLAG_GLOBAL_HINTS.
+ *      idc_set_global_refs: the same statistics written on the device straight into the handle's global inputs of image slots
+ *      img .. img+n-1, as the rows idc_set_global_hints would have been given: the histogram, then hist_flag, then -- with
+ *      IDC_REF_SATURATION -- {mean saturation, 1}, else {0, 0}.  ref_index [n]: the reference image i takes, -1 = none (an all-zero row:
+ *      glob_dist == -1); NULL = the identity (needs m == n).  Rows outside img .. img+n-1 stay as they are (idc_set_global_hints zeroes
+ *      them).  Needs IDC_FLAG_GLOBAL_HINTS.
+ *      Both calls block: they drain the pipelined slots, enqueue on the handle's stream and return when done.  Beyond what is said
+ *      above they touch none of the handle's resident state (L / hint planes, results, distributions, kept sources, the slots).
+ *      idc_forward_async_rgb_ref: idc_forward_async_rgb with per-image references, for the same slots, idc_wait and
+ *      idc_pipeline_times.  The SLOT owns the packed references, the table, the counts and ITS OWN [max_batch][316] global inputs; the
+ *      handle's (idc_set_global_hints / idc_set_global_refs) are neither read nor written, so batch k+1's references travel while batch
+ *      k computes.  (idc_forward_async and idc_forward_async_rgb keep reading the handle's.)  On the compute stream, after the slot's
+ *      H2D event and in front of the prologue kernel: the counts are zeroed, the statistics kernel, the row kernel; idc_pipeline_times
+ *      counts them under compute and the reference bytes under H2D.  m == 0 (refs and ref_index may then be NULL): no image has a
+ *      reference, every row is zero.
+ *      In all three, refs, ref_index and centres are copied into pinned staging before the call returns: the caller may free them at once.
+ *      Status, all decided on the host before anything is enqueued (a refused call leaves slot and handle as they were); for the
+ *      arguments idc_forward_async_rgb_ref shares with idc_forward_async_rgb, that call's codes:
+ *      IDC_ERR_INVALID_ARG for m outside 1..IDC_REF_MAX (0..IDC_REF_MAX pipelined), NULL refs with m > 0, a NULL refs[r].rgb, h or w
+ *      outside 1..16384, reference bytes above IDC_BATCH_MAX_SOURCE_BYTES in all, an index outside -1..m-1, NULL ref_index with
+ *      m != n (and m > 0), NULL centres with m > 0, NULL hist in idc_global_stats_rgb, unknown flag bits, a non-finite hist_flag;
+ *      IDC_ERR_BATCH unless n >= 1 and img + n <= max_batch; IDC_ERR_UNSUPPORTED for idc_set_global_refs / idc_forward_async_rgb_ref on
+ *      a handle without IDC_FLAG_GLOBAL_HINTS.  (The 4x4 blocks need H and W to be multiples of 4: idc_create asks for 8.) */
+typedef struct idc_ref_image { const uint8_t* rgb; int32_t h, w; } idc_ref_image;   /* host, [h,w,3] uint8 */
+enum { IDC_REF_SATURATION = 1 };
+#define IDC_REF_MAX 4096
+int idc_global_stats_rgb(idc_handle h, int m, const idc_ref_image* refs, const float* centres, float* hist, float* s_avg);
+int idc_set_global_refs(idc_handle h, int img, int n, int m, const idc_ref_image* refs, const int32_t* ref_index,
+                        const float* centres, float hist_flag, unsigned flags);
+int idc_forward_async_rgb_ref(idc_handle h, int slot, int n, int src_h, int src_w, const uint8_t* rgb_in,
+                              const int32_t* hint_offsets, const idc_hint* hints, int mode, float mask_value, float maskcent,
+                              float l_cent, unsigned flags, int m, const idc_ref_image* refs, const int32_t* ref_index,
+                              const float* centres, float hist_flag, unsigned ref_flags, uint8_t* rgb_out, float* out_ab);
+
 /* ---- colour picker on the device: replaces data/lab_gamut.py, the host colour maths the GUI runs on every mouse press
  *      (ui/gui_draw.py:11,182-183,195-204; ui/gui_gamut.py:4), in float64 with the constants and operation order of idc_lab2rgb.
  *      idc_gamut_map = abGrid(gamut_size, D).update_gamut(L[k]) (lab_gamut.py:56-78) for k = 0..n-1 in one launch.  The grid has

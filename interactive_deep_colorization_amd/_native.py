@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = [
     "idc_stream_wait", "idc_stream_signal", "idc_alloc_host", "idc_free_host", "idc_forward_async", "idc_wait", "idc_pipeline_times",
     "idc_comm_unique_id", "idc_broadcast_weights", "idc_upsample_lab2rgb", "idc_set_image_rgb", "idc_fullres_rgb",
     "idc_forward_async_rgb",
+    "idc_global_stats_rgb", "idc_set_global_refs", "idc_forward_async_rgb_ref",
     "idc_gamut_map", "idc_snap_colors",
     "idc_set_range_audit", "idc_range_reset", "idc_range_report", "idc_pack_weights_ex", "idc_load_weights_ex",
 ]
@@ -41,6 +42,7 @@ IDC_INGEST_KEEP_SOURCE = 1
 IDC_L_IMAGE, IDC_L_MASK50 = 0, 1
 IDC_BATCH_OUT_SOURCE = 1
 IDC_BATCH_MAX_SOURCE_BYTES, IDC_BATCH_MAX_HINTS = 1 << 30, 1 << 20
+IDC_REF_SATURATION, IDC_REF_MAX = 1, 4096
 IDC_GAMUT_MAX_MAPS, IDC_GAMUT_MAX_SIZE, IDC_SNAP_MAX_COLORS = 64, 512, 65536
 IDC_UNIQUE_ID_BYTES = 128
 IDC_HINT_AB, IDC_HINT_RGB = 0, 1
@@ -62,6 +64,11 @@ class Hint(ctypes.Structure):
     """idc_hint: inclusive rectangle + (a, b) or (r, g, b)."""
     _fields_ = [("y0", ctypes.c_int32), ("x0", ctypes.c_int32), ("y1", ctypes.c_int32), ("x1", ctypes.c_int32),
                 ("c0", ctypes.c_float), ("c1", ctypes.c_float), ("c2", ctypes.c_float)]
+
+
+class RefImage(ctypes.Structure):
+    """idc_ref_image: one host reference photograph, [h,w,3] uint8."""
+    _fields_ = [("rgb", ctypes.c_void_p), ("h", ctypes.c_int32), ("w", ctypes.c_int32)]
 
 
 class LayerInfo(ctypes.Structure):
@@ -165,6 +172,10 @@ def load():
     proto("idc_set_image_rgb", ci, [vp, ci, ci, ci, ci, vp, cf, ctypes.c_uint, vp, vp])
     proto("idc_fullres_rgb", ci, [vp, ci, ci, ci, ci, vp])
     proto("idc_forward_async_rgb", ci, [vp, ci, ci, ci, ci, vp, vp, vp, ci, cf, cf, cf, ctypes.c_uint, vp, vp])
+    proto("idc_global_stats_rgb", ci, [vp, ci, ctypes.POINTER(RefImage), c_float_p, c_float_p, c_float_p])
+    proto("idc_set_global_refs", ci, [vp, ci, ci, ci, ctypes.POINTER(RefImage), vp, c_float_p, cf, ctypes.c_uint])
+    proto("idc_forward_async_rgb_ref", ci, [vp, ci, ci, ci, ci, vp, vp, vp, ci, cf, cf, cf, ctypes.c_uint,
+                                            ci, ctypes.POINTER(RefImage), vp, c_float_p, cf, ctypes.c_uint, vp, vp])
     proto("idc_gamut_map", ci, [vp, ci, vp, ci, ci, vp, vp, vp])
     proto("idc_snap_colors", ci, [vp, ci, vp, vp, vp, vp, vp])
     proto("idc_set_range_audit", ci, [vp, ci])

@@ -895,11 +895,39 @@ class ColorizeImageCaffeGlobDist(ColorizeImageCaffe):
 
     def get_global_histogram(self, ref_rgb, pts_in_hull=None):
         """The notebook's ``get_global_histogram`` (``DemoGlobalHistogramTransfer.ipynb:176-186``), i.e. the
-        ``global_stats.prototxt`` net, on the device: an Xd x Xd RGB uint8 reference image -> the 313-bin global ab
-        histogram to pass as ``glob_dist``.  ``pts_in_hull`` defaults to the table loaded like the reference does."""
-        centres = self.pts_in_hull if pts_in_hull is None else pts_in_hull
-        hist, _ = self.net.global_histogram(ref_rgb, np.asarray(centres, np.float32))
+        ``global_stats.prototxt`` net, on the device: an RGB uint8 reference image -> the 313-bin global ab
+        histogram to pass as ``glob_dist``.  ``pts_in_hull`` defaults to the table loaded like the reference does.
+        A reference of another size than Xd x Xd is resized on the device as the notebook resizes it inside this function (DEVIATION: by
+        the ingestion rule of ``load_image``, ``colorspace.resize_bilinear_u8``, in place of ``caffe.io.resize_image``)."""
+        centres = np.asarray(self.pts_in_hull if pts_in_hull is None else pts_in_hull, np.float32)
+        ref_rgb = np.asarray(ref_rgb)
+        if ref_rgb.shape == (self.Xd, self.Xd, 3):
+            hist, _ = self.net.global_histogram(ref_rgb, centres)
+        else:
+            hist, _ = self.net.global_stats_rgb([ref_rgb], centres, want_sat=False)
         return hist[0]
+
+    def load_reference(self, path):
+        """A reference photograph from a file, as ``get_global_histogram`` / ``net_forward_reference`` take it: (h,w,3) uint8 RGB."""
+        return colorspace.imread_rgb(path)
+
+    def _set_ref(self, ref_rgb, saturation=False):
+        # the reference's statistics straight into the net's global input on the device (flag = glob_mask_mult, as _set_glob writes it)
+        self.net.set_global_refs([ref_rgb], np.asarray(self.pts_in_hull, np.float32), hist_flag=self.glob_mask_mult, saturation=saturation)
+
+    def net_forward_reference(self, input_ab, input_mask, ref_rgb, saturation=False):
+        """``net_forward(input_ab, input_mask, get_global_histogram(ref_rgb))`` without the histogram visiting the host: the reference
+        photograph (any size) is installed on the device, then the forward runs.  ``saturation`` also feeds the reference's mean HSV
+        saturation (``s_avg_mask``, which the reference wrapper leaves at zero)."""
+        if not self.net_set:
+            print('I need to have a net!')
+            return -1
+        self._set_ref(ref_rgb, saturation)
+        self.output_rgb = ColorizeImageCaffe.net_forward(self, input_ab, input_mask)
+        if isinstance(self.output_rgb, int):
+            return self.output_rgb
+        self._set_out_ab_()
+        return self.output_rgb
 
     def _set_glob(self, glob_dist):
         # glob_dist is a 313 array, or -1 = "no global hint": histogram and flag all zero (reference :451-459)
@@ -909,13 +937,16 @@ class ColorizeImageCaffeGlobDist(ColorizeImageCaffe):
             g[0, 313] = self.glob_mask_mult
         self.net.set_global_hints(g)
 
-    def net_forward_hints(self, hints, mode='rgb', glob_dist=-1, snap=False):
+    def net_forward_hints(self, hints, mode='rgb', glob_dist=-1, snap=False, ref_rgb=None, saturation=False):
         """Edit-list form; the global hint is an argument here too (default -1 = none), never a leftover of an earlier
-        call."""
+        call.  ``ref_rgb``: a reference photograph instead of ``glob_dist``, installed on the device as in ``net_forward_reference``."""
         if not self.net_set:
             print('I need to have a net!')
             return -1
-        self._set_glob(glob_dist)
+        if ref_rgb is not None:
+            self._set_ref(ref_rgb, saturation)
+        else:
+            self._set_glob(glob_dist)
         ret = ColorizeImageCaffe.net_forward_hints(self, hints, mode, snap)
         if isinstance(ret, int):
             return ret

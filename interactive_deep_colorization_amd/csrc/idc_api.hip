@@ -1,5 +1,5 @@
 // idc_api.hip -- the handle and what a caller does with it besides weights and forwards (C ABI, include/ideepcolor.h): create / destroy, the last-error
-// string (fail), I/O scales, global hints, the click session, Lab -> RGB, colour suggestions and distributions, the global histogram, stream
+// string (fail), I/O scales, global hints, the click session, Lab -> RGB, colour suggestions and distributions, the global histogram, reference-image global hints (blocking forms), stream
 // ordering, the display upsample, image ingestion (uint8 RGB in, full-resolution RGB out) and the colour picker (gamut map, colour snapping).
 #include <stdarg.h>
 #include <stdio.h>
@@ -281,7 +281,7 @@ int idc_forward_resident(idc_handle h, int n, float maskcent, float l_cent, floa
     rc = drain_pipeline(h);
     if (rc) return rc;
     const size_t hw = (size_t)h->H * h->W;
-    rc = run_graph(h, n, h->d_L.get(), h->d_ab.get(), h->d_mask.get(), maskcent, h->d_out.get(), (h->flags & IDC_FLAG_DIST_HEAD) ? h->d_dist.get() : nullptr);
+    rc = run_graph(h, n, h->d_L.get(), h->d_ab.get(), h->d_mask.get(), maskcent, h->d_out.get(), (h->flags & IDC_FLAG_DIST_HEAD) ? h->d_dist.get() : nullptr, h->d_glob_in.get());
     if (rc) return rc;
     h->out_resident = true; h->labq_resident = rgb != nullptr && lab_q != nullptr;
     if (out_ab) HIPCHK(h, hipMemcpyAsync(h->h_out.get(), h->d_out.get(), (size_t)n * hw * 2 * 4, hipMemcpyDeviceToHost, h->stream.get()));
@@ -448,6 +448,54 @@ int idc_global_histogram(idc_handle h, int n, const uint8_t* rgb, const float* c
         for (int k = 0; k < 313; ++k) hist[(size_t)i * 313 + k] = (float)(cnt[(size_t)i * 313 + k] / nblk);
         if (s_avg) s_avg[i] = (float)(sat[i] / (double)hw);
     }
+    return IDC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- reference-image global hints
+// The blocking forms on the handle's own stage (check_refs / stage_refs / upload_refs / launch_refs: idc_exec.hip, shared with the pipelined
+// slots).  Both end synchronised, so nothing of the stage is in flight when the next call grows it.
+int idc_global_stats_rgb(idc_handle h, int m, const idc_ref_image* refs, const float* centres, float* hist, float* s_avg) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (!hist) return fail(&h->err, IDC_ERR_INVALID_ARG, "null hist");
+    RefLayout lay;
+    int rc = check_refs(h, 1, 0, m, refs, nullptr, centres, 0.f, 0u, &lay);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    rc = drain_pipeline(h);
+    if (rc) return rc;
+    rc = stage_refs(h, h->ref, lay, refs, nullptr, centres, true);
+    if (rc) return rc;
+    rc = upload_refs(h, h->ref, lay, h->stream.get());
+    if (rc) return rc;
+    rc = launch_refs(h, h->ref, lay, 0.f, IDC_REF_SATURATION, nullptr, true, h->stream.get());
+    if (rc) return rc;
+    const size_t res_bytes = lay.o_savg - lay.o_hist + (size_t)m * sizeof(float);
+    HIPCHK(h, hipMemcpyAsync(h->ref.h_res.get(), h->ref.d_work.get() + lay.o_hist, res_bytes, hipMemcpyDeviceToHost, h->stream.get()));
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+    memcpy(hist, h->ref.h_res.get(), (size_t)m * 313 * sizeof(float));
+    if (s_avg) memcpy(s_avg, h->ref.h_res.get() + (lay.o_savg - lay.o_hist), (size_t)m * sizeof(float));
+    return IDC_OK;
+}
+
+int idc_set_global_refs(idc_handle h, int img, int n, int m, const idc_ref_image* refs, const int32_t* ref_index, const float* centres,
+                        float hist_flag, unsigned flags) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (!(h->flags & IDC_FLAG_GLOBAL_HINTS)) return fail(&h->err, IDC_ERR_UNSUPPORTED, "handle was created without IDC_FLAG_GLOBAL_HINTS");
+    if (n < 1 || img < 0 || img >= h->max_batch || n > h->max_batch - img)
+        return fail(&h->err, IDC_ERR_BATCH, "image slots %d..%d outside 0..%d", img, img + n - 1, h->max_batch - 1);
+    RefLayout lay;
+    int rc = check_refs(h, 1, n, m, refs, ref_index, centres, hist_flag, flags, &lay);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    rc = drain_pipeline(h);
+    if (rc) return rc;
+    rc = stage_refs(h, h->ref, lay, refs, ref_index, centres, false);
+    if (rc) return rc;
+    rc = upload_refs(h, h->ref, lay, h->stream.get());
+    if (rc) return rc;
+    rc = launch_refs(h, h->ref, lay, hist_flag, flags, h->d_glob_in.get() + (size_t)img * kGlobIn, false, h->stream.get());
+    if (rc) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
     return IDC_OK;
 }
 

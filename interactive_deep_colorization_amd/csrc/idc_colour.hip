@@ -1,5 +1,6 @@
 // idc_colour.hip -- colour space, display and layout helpers around the forward pass: Lab -> RGB, the fused upsample + Lab -> RGB of the display step,
-// the global-statistics extractor, image ingestion (uint8 RGB -> net-size Lab, full-resolution RGB from the resident source), the colour picker's
+// the global-statistics extractor, image ingestion (uint8 RGB -> net-size Lab, full-resolution RGB from the resident source), the global hints of
+// reference photographs (statistics of m references of individual sizes, the rows of the net's global input), the colour picker's
 // gamut map and colour snapping, the PCIe copy kernel and the NCHW <-> NHWC (split) converters.
 #include <stdlib.h>
 #include <type_traits>
@@ -579,6 +580,156 @@ hipError_t launch_batch_fullres_rgb(const unsigned char* src, int n, int oh, int
     const long long ngroups = (total + 3) >> 2;
     const int blocks = (int)((ngroups + 255) / 256 < 8192 ? (ngroups + 255) / 256 : 8192);
     hipLaunchKernelGGL(batch_fullres_rgb_kernel, dim3(blocks), dim3(256), 0, s, src, total, oh, ow, lab_q, H, W, interp, rgb);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// reference-image global hints: global_stats_kernel for m reference photographs of individual sizes, resized inside the kernel (the notebook
+// resizes inside get_global_histogram, DemoGlobalHistogramTransfer.ipynb:176-182), and the kernel that turns the counts into the rows
+// glob_branch_kernel reads -- so that a reference goes from its uint8 bytes to the net's global input without visiting the host.
+// ------------------------------------------------------------------------------------------------
+// A workgroup of a reference takes 16 of its 4x4 blocks per step, one lane per net-size pixel (16 consecutive lanes = one block, dy outer, dx
+// inner): ingest_rgb_kernel's pixel from the reference's own h x w, then Lab and saturation as global_stats_kernel computes them.  The 16 values
+// of a block cross LDS and are added in global_stats_kernel's order, so a net-size reference gives that kernel's bits; the search for the nearest
+// centre is shared by the block's 16 lanes.  Counts go to an LDS histogram (integer atomics) that is flushed once; the saturation sums stay in
+// each block's first lane across steps and are added in lane order at the end, one plain store per workgroup: no float atomic anywhere, nothing
+// depends on arrival order.
+constexpr int kRefStatsMaxWg = 64;      // workgroups per reference at most (256x256: 4096 blocks = 64 workgroups x 4 steps)
+
+int ref_stats_workgroups(int H, int W) {
+    const int groups = ((H >> 2) * (W >> 2) + 15) / 16;
+    return groups < kRefStatsMaxWg ? groups : kRefStatsMaxWg;
+}
+
+__global__ __launch_bounds__(256) void ref_stats_kernel(const RefDesc* __restrict__ refs, const unsigned char* __restrict__ packed,
+                                                        const float* __restrict__ centres, int H, int W, unsigned* __restrict__ counts,
+                                                        double* __restrict__ sat_part) {
+    __shared__ double tab[256];
+    __shared__ double xa[256], xb[256], xs[256];
+    __shared__ float cc[313 * 2];
+    __shared__ float cd[256];
+    __shared__ int ck[256];
+    __shared__ unsigned bins[313];
+    for (int i = threadIdx.x; i < 626; i += blockDim.x) cc[i] = centres[i];
+    for (int i = threadIdx.x; i < 313; i += blockDim.x) bins[i] = 0u;
+    fill_srgb_table(tab);
+    const int r = blockIdx.y;
+    const RefDesc rd = refs[r];
+    const unsigned char* img = packed + rd.off;
+    const int w4 = W >> 2, nblk = (H >> 2) * w4;
+    const int sub = threadIdx.x >> 4, px = threadIdx.x & 15, dy = px >> 2, dx = px & 3;
+    double wsat = 0.0;
+    for (int g0 = blockIdx.x * 16; g0 < nblk; g0 += gridDim.x * 16) {           // uniform over the workgroup: every lane meets the barriers
+        const int blk = g0 + sub;
+        const bool live = blk < nblk;
+        double a = 0.0, b = 0.0, sat = 0.0;
+        if (live) {
+            const int by = blk / w4, bx = blk - by * w4;
+            int y0, y1, x0, x1;
+            double wy, wx;
+            bilinear_taps(by * 4 + dy, rd.h, H, y0, y1, wy);
+            bilinear_taps(bx * 4 + dx, rd.w, W, x0, x1, wx);
+            const unsigned char* p00 = img + ((long long)y0 * rd.w + x0) * 3; const unsigned char* p01 = img + ((long long)y0 * rd.w + x1) * 3;
+            const unsigned char* p10 = img + ((long long)y1 * rd.w + x0) * 3; const unsigned char* p11 = img + ((long long)y1 * rd.w + x1) * 3;
+            int q[3];
+            double lin[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                q[c] = bilinear_u8((double)p00[c], (double)p01[c], (double)p10[c], (double)p11[c], wx, wy);
+                lin[c] = tab[q[c]];
+            }
+            double L;
+            linear_to_lab(lin, L, a, b);
+            const double rr = q[0] / 255.0, gg = q[1] / 255.0, bl = q[2] / 255.0;
+            const double mx = fmax(rr, fmax(gg, bl)), mn = fmin(rr, fmin(gg, bl));
+            sat = mx > 0.0 ? (mx - mn) / mx : 0.0;                             // skimage rgb2hsv saturation
+        }
+        xa[threadIdx.x] = a; xb[threadIdx.x] = b; xs[threadIdx.x] = sat;
+        __syncthreads();
+        if (live) {
+            // every lane of the block adds the 16 values in the same order, so all 16 hold the same pooled value, and each searches the
+            // centres px, px + 16, ...: a sixteenth of global_stats_kernel's serial walk, which is what a reference costs in time
+            const int base = threadIdx.x & ~15;
+            double sa = 0.0, sb = 0.0, ssat = 0.0;
+            for (int k = 0; k < 16; ++k) { sa += xa[base + k]; sb += xb[base + k]; ssat += xs[base + k]; }
+            const float pa = (float)(sa / 16.0), pb = (float)(sb / 16.0);      // Caffe blobs are fp32
+            int best = 0;
+            float bd = 3.0e38f;
+            for (int k = px; k < 313; k += 16) {
+                const float da = pa - cc[2 * k], db = pb - cc[2 * k + 1];
+                const float d = da * da + db * db;
+                if (d < bd) { bd = d; best = k; }
+            }
+            cd[threadIdx.x] = bd; ck[threadIdx.x] = best;
+            if (px == 0) wsat += ssat;
+        }
+        __syncthreads();            // (the next step's writes to xa / xb / xs lie behind this barrier, those to cd / ck behind the next one)
+        if (live && px == 0) {
+            // the nearest of the 16 candidates, the lowest index among equal distances: what one lane walking 0..312 with `<` finds
+            float bd = cd[threadIdx.x];
+            int best = ck[threadIdx.x];
+            for (int j = 1; j < 16; ++j) {
+                const float d = cd[threadIdx.x + j];
+                const int k = ck[threadIdx.x + j];
+                if (d < bd || (d == bd && k < best)) { bd = d; best = k; }
+            }
+            atomicAdd(&bins[best], 1u);
+        }
+    }
+    if (px == 0) xs[sub] = wsat;
+    __syncthreads();
+    for (int i = threadIdx.x; i < 313; i += blockDim.x)
+        if (bins[i] != 0u) atomicAdd(&counts[(size_t)r * 313 + i], bins[i]);
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int k = 0; k < 16; ++k) s += xs[k];
+        sat_part[(size_t)r * gridDim.x + blockIdx.x] = s;
+    }
+}
+
+hipError_t launch_ref_stats(const RefDesc* refs, int m, const unsigned char* packed, const float* centres, int H, int W, unsigned* counts,
+                            double* sat_part, hipStream_t s) {
+    if (m <= 0 || m > 65535 || H < 4 || W < 4 || (H & 3) || (W & 3)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ref_stats_kernel, dim3(ref_stats_workgroups(H, W), m), dim3(256), 0, s, refs, packed, centres, H, W, counts, sat_part);
+    return hipGetLastError();
+}
+
+// Workgroups 0..n-1: one row of the global-input block each, a lane per value; workgroups n..n+m-1 (only where the caller wants them): the
+// histogram and mean saturation of one reference.  The divisions are idc_global_histogram's host expressions.
+__device__ __forceinline__ float ref_mean_saturation(const double* __restrict__ sat_part, int r, int G, int HW) {
+    double s = 0.0;
+    for (int k = 0; k < G; ++k) s += sat_part[(size_t)r * G + k];
+    return (float)(s / (double)HW);
+}
+
+__global__ __launch_bounds__(320) void glob_rows_kernel(const unsigned* __restrict__ counts, const double* __restrict__ sat_part, int G,
+                                                        const int* __restrict__ ref_index, int n, int nblk, int HW, float hist_flag,
+                                                        int with_sat, float* __restrict__ rows, float* __restrict__ hist,
+                                                        float* __restrict__ s_avg) {
+    const int t = threadIdx.x;
+    if ((int)blockIdx.x < n) {
+        const int i = blockIdx.x, r = ref_index[i];
+        float v = 0.f;
+        if (r >= 0) {
+            if (t < 313) v = (float)((double)counts[(size_t)r * 313 + t] / (double)nblk);
+            else if (t == 313) v = hist_flag;
+            else if (with_sat && t == 314) v = ref_mean_saturation(sat_part, r, G, HW);
+            else if (with_sat && t == 315) v = 1.f;
+        }
+        if (t < kGlobIn) rows[(size_t)i * kGlobIn + t] = v;
+    } else {
+        const int r = blockIdx.x - n;
+        if (t < 313) hist[(size_t)r * 313 + t] = (float)((double)counts[(size_t)r * 313 + t] / (double)nblk);
+        else if (t == 313 && s_avg != nullptr) s_avg[r] = ref_mean_saturation(sat_part, r, G, HW);
+    }
+}
+
+hipError_t launch_glob_rows(const unsigned* counts, const double* sat_part, const int* ref_index, int n, int m, int H, int W, float hist_flag,
+                            int with_sat, float* rows, float* hist, float* s_avg, hipStream_t s) {
+    const int extra = hist != nullptr ? m : 0;
+    if (n < 0 || m < 0 || n + extra <= 0 || (n > 0 && (ref_index == nullptr || rows == nullptr))) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(glob_rows_kernel, dim3(n + extra), dim3(320), 0, s, counts, sat_part, ref_stats_workgroups(H, W), ref_index, n,
+                       (H >> 2) * (W >> 2), H * W, hist_flag, with_sat, rows, hist, s_avg);
     return hipGetLastError();
 }
 

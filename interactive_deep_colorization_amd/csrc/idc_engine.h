@@ -199,6 +199,14 @@ struct idc_context {
     DevMem<unsigned char> d_pick;        // idc_gamut_map / idc_snap_colors: inputs + results of one call, device and pinned
     PinnedMem<unsigned char> h_pick;
     Event ev_sync;                       // idc_stream_wait / idc_stream_signal
+    // reference-image global hints (idc_global_stats_rgb / idc_set_global_refs; one per pipeline slot for idc_forward_async_rgb_ref): what one
+    // call sends -- the RefDesc table, the reference index, the centres and the packed uint8 references as ONE block, pinned and device -- and
+    // what its kernels work in: counts, per-workgroup saturation sums, and the histograms / mean saturations a caller asked for (RefLayout)
+    struct RefStage {
+        PinnedMem<unsigned char> h_in, h_res;
+        DevMem<unsigned char> d_in, d_work;
+    };
+    RefStage ref;
     // two-slot transfer pipeline (idc_forward_async / idc_wait): each slot owns its device planes
     struct PipeSlot {
         DevMem<float> d_L, d_ab, d_mask, d_out;                                        // device I/O planes
@@ -213,6 +221,9 @@ struct idc_context {
         DevMem<double> d_labq;
         PinnedMem<unsigned char> h_src, h_meta, h_rgb;                                 // pinned staging: pageable source, the list, pageable rgb_out
         uint8_t* user_rgb = nullptr; size_t rgb_bytes = 0; bool staged_rgb = false;    // user_rgb == nullptr: the slot's batch was an idc_forward_async
+        // idc_forward_async_rgb_ref: the batch's references and the slot's OWN [max_batch][316] global inputs (the handle's d_glob_in is not touched)
+        RefStage ref;
+        DevMem<float> d_glob_in;
     } pipe[2];
     Event ev_pipe_base;
     bool pipe_ready = false;             // ev_pipe_base is recorded (ensure_pipeline)
@@ -277,7 +288,27 @@ int alloc_graph(idc_context* c);
 
 // idc_exec.hip
 void bind_layer(std::vector<Layer>& layers, int li, const BindEnv& env);
-int run_graph(idc_context* c, int n, const float* dL, const float* dab, const float* dmask, float maskcent, float* dout, float* ddist);
+// glob_in: the [n][316] global-input block the Global-Hints branch reads (the handle's d_glob_in, or a pipeline slot's own); unused without the branch
+int run_graph(idc_context* c, int n, const float* dL, const float* dab, const float* dmask, float maskcent, float* dout, float* ddist,
+              const float* glob_in);
+// reference-image global hints: where each part of a call sits in RefStage's blocks (byte offsets; the RefDesc table is at 0 of the input block,
+// the counts at 0 of the work block)
+struct RefLayout {
+    int n = 0, m = 0;                    // images that take a row (0: idc_global_stats_rgb), references
+    size_t o_index = 0, o_centres = 0, o_packed = 0, in_bytes = 0, ref_bytes = 0;
+    size_t o_sat = 0, o_hist = 0, o_savg = 0, work_bytes = 0;
+};
+// every check of the reference arguments (include/ideepcolor.h's table), on the host, before anything is allocated or enqueued; m_min = 0 or 1
+int check_refs(idc_context* c, int m_min, int n, int m, const idc_ref_image* refs, const int32_t* ref_index, const float* centres,
+               float hist_flag, unsigned ref_flags, RefLayout* lay);
+// grow the stage (the caller knows nothing of it is in flight) and copy table, index, centres and references into its pinned block
+int stage_refs(idc_context* c, idc_context::RefStage& st, const RefLayout& lay, const idc_ref_image* refs, const int32_t* ref_index,
+               const float* centres, bool want_results);
+// one H2D copy of the input block on `copy`; then on `s`: counts zeroed, ref_stats_kernel, glob_rows_kernel into rows (n rows; may be nullptr
+// with n == 0) and, with want_hist, the stage's hist / s_avg section
+int upload_refs(idc_context* c, idc_context::RefStage& st, const RefLayout& lay, hipStream_t copy);
+int launch_refs(idc_context* c, idc_context::RefStage& st, const RefLayout& lay, float hist_flag, unsigned ref_flags, float* rows, bool want_hist,
+                hipStream_t s);
 int check_chain_abort(idc_context* c);
 int check_forward_args(idc_context* c, int n);
 hipError_t wait_stream(idc_context* c, int n);

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <cmath>
+
 #include "idc_engine.h"
 
 namespace idc {
@@ -101,7 +103,7 @@ void bind_layer(std::vector<Layer>& layers, int li, const BindEnv& e) {
 }
 
 int run_graph(idc_context* c, int n, const float* dL, const float* dab, const float* dmask, float maskcent,
-                     float* dout, float* ddist) {
+                     float* dout, float* ddist, const float* glob_in) {
     hipStream_t s = c->stream.get();
     int step = 0;
     {   // a workgroup of an EARLIER conv_kwave_chain_bf16 launch gave up at its grid barrier and nobody has waited on that forward since
@@ -122,7 +124,7 @@ int run_graph(idc_context* c, int n, const float* dL, const float* dab, const fl
     if (c->profiling == 2) (void)hipEventRecord(c->ev[ring].get(), s);          // whole-forward pair: slot 0
     tic();   // (slot 0: the input pack is fused into conv1_1's operand staging; only the global-hints branch runs here)
     if (c->flags & IDC_FLAG_GLOBAL_HINTS)      // four GEMVs per image; its output is consumed by conv4_3's epilogue
-        HIPCHK(c, launch_glob_branch(c->d_glob_in.get(), (const float*)(c->d_blob + c->plan.glob_off), c->d_glob_vec.get(), n, s));
+        HIPCHK(c, launch_glob_branch(glob_in, (const float*)(c->d_blob + c->plan.glob_off), c->d_glob_vec.get(), n, s));
     toc();
     PlanEnv pe;
     pe.precision = c->precision; pe.flags = c->flags; pe.H = c->H; pe.W = c->W; pe.max_batch = c->max_batch; pe.n = n;
@@ -299,7 +301,7 @@ static int forward_host(idc_context* c, int n, const float* L_mc, const float* a
     if (L_mc) HIPCHK(c, upload(c->d_L.get(), L_mc, hL, (size_t)n * hw * 4));
     HIPCHK(c, upload(c->d_ab.get(), ab, hab, (size_t)n * hw * 2 * 4));
     HIPCHK(c, upload(c->d_mask.get(), mask, hm, (size_t)n * hw * 4));
-    rc = run_graph(c, n, c->d_L.get(), c->d_ab.get(), c->d_mask.get(), maskcent, c->d_out.get(), (dist_q || keep_dist) ? c->d_dist.get() : nullptr);
+    rc = run_graph(c, n, c->d_L.get(), c->d_ab.get(), c->d_mask.get(), maskcent, c->d_out.get(), (dist_q || keep_dist) ? c->d_dist.get() : nullptr, c->d_glob_in.get());
     if (rc) return rc;
     const bool out_direct = copy_out && out_ab != c->h_out.get() && is_pinned(out_ab);
     c->out_copy_pending = copy_out && out_ab != c->h_out.get() && !out_direct;
@@ -365,6 +367,85 @@ int drain_pipeline(idc_context* c) {
     return IDC_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- reference-image global hints
+int check_refs(idc_context* c, int m_min, int n, int m, const idc_ref_image* refs, const int32_t* ref_index, const float* centres,
+               float hist_flag, unsigned ref_flags, RefLayout* lay) {
+    if (m < m_min || m > IDC_REF_MAX) return fail(&c->err, IDC_ERR_INVALID_ARG, "%d references outside %d..%d", m, m_min, IDC_REF_MAX);
+    if (m > 0 && !refs) return fail(&c->err, IDC_ERR_INVALID_ARG, "null refs");
+    if (m > 0 && !centres) return fail(&c->err, IDC_ERR_INVALID_ARG, "null centres");
+    if (ref_flags & ~(unsigned)IDC_REF_SATURATION) return fail(&c->err, IDC_ERR_INVALID_ARG, "unknown reference flag bits 0x%x", ref_flags);
+    if (!std::isfinite(hist_flag)) return fail(&c->err, IDC_ERR_INVALID_ARG, "hist_flag is not finite");
+    size_t bytes = 0;
+    for (int r = 0; r < m; ++r) {
+        if (!refs[r].rgb) return fail(&c->err, IDC_ERR_INVALID_ARG, "reference %d: null rgb", r);
+        if (refs[r].h < 1 || refs[r].h > 16384 || refs[r].w < 1 || refs[r].w > 16384)
+            return fail(&c->err, IDC_ERR_INVALID_ARG, "reference %d: size %dx%d outside 1..16384", r, refs[r].h, refs[r].w);
+        bytes += (size_t)refs[r].h * refs[r].w * 3;               // <= 4096 * 0.8 GB: no overflow in 64 bits
+    }
+    if (bytes > IDC_BATCH_MAX_SOURCE_BYTES)
+        return fail(&c->err, IDC_ERR_INVALID_ARG, "%d references hold %zu bytes, more than %zu", m, bytes, (size_t)IDC_BATCH_MAX_SOURCE_BYTES);
+    if (n > 0 && m > 0) {
+        if (!ref_index && m != n) return fail(&c->err, IDC_ERR_INVALID_ARG, "null ref_index needs m == n (m = %d, n = %d)", m, n);
+    }
+    if (n > 0 && ref_index)
+        for (int i = 0; i < n; ++i)
+            if (ref_index[i] < -1 || ref_index[i] >= m) return fail(&c->err, IDC_ERR_INVALID_ARG, "ref_index[%d] = %d outside -1..%d", i, ref_index[i], m - 1);
+    const size_t mm = m > 0 ? (size_t)m : 1, nn = n > 0 ? (size_t)n : 1, G = (size_t)ref_stats_workgroups(c->H, c->W);
+    lay->n = n; lay->m = m; lay->ref_bytes = bytes;
+    lay->o_index = align_up(mm * sizeof(RefDesc), 16);
+    lay->o_centres = lay->o_index + align_up(nn * sizeof(int), 16);
+    lay->o_packed = lay->o_centres + align_up(626 * sizeof(float), 16);
+    lay->in_bytes = lay->o_packed + bytes;
+    lay->o_sat = align_up(mm * 313 * sizeof(unsigned), 16);
+    lay->o_hist = lay->o_sat + align_up(mm * G * sizeof(double), 16);
+    lay->o_savg = lay->o_hist + align_up(mm * 313 * sizeof(float), 16);
+    lay->work_bytes = lay->o_savg + align_up(mm * sizeof(float), 16);
+    return IDC_OK;
+}
+
+int stage_refs(idc_context* c, idc_context::RefStage& st, const RefLayout& lay, const idc_ref_image* refs, const int32_t* ref_index,
+               const float* centres, bool want_results) {
+    HIPCHK(c, st.h_in.ensure(lay.in_bytes, 65536));
+    HIPCHK(c, st.d_in.ensure(lay.in_bytes, 65536));
+    HIPCHK(c, st.d_work.ensure(lay.work_bytes, 65536));
+    if (want_results) HIPCHK(c, st.h_res.ensure(lay.work_bytes - lay.o_hist, 65536));
+    unsigned char* base = st.h_in.get();
+    RefDesc* tab = (RefDesc*)base;
+    size_t off = 0;
+    for (int r = 0; r < lay.m; ++r) {
+        const size_t sb = (size_t)refs[r].h * refs[r].w * 3;
+        tab[r].off = (long long)off; tab[r].h = refs[r].h; tab[r].w = refs[r].w;
+        memcpy(base + lay.o_packed + off, refs[r].rgb, sb);
+        off += sb;
+    }
+    int* idx = (int*)(base + lay.o_index);
+    for (int i = 0; i < lay.n; ++i) idx[i] = lay.m == 0 ? -1 : (ref_index ? ref_index[i] : i);
+    if (lay.m > 0) memcpy(base + lay.o_centres, centres, 626 * sizeof(float));
+    return IDC_OK;
+}
+
+int upload_refs(idc_context* c, idc_context::RefStage& st, const RefLayout& lay, hipStream_t copy) {
+    // without references only the index travels (every entry -1): the table, the centres and the packed section are not read
+    const size_t bytes = lay.m > 0 ? lay.in_bytes : lay.o_centres;
+    HIPCHK(c, hipMemcpyAsync(st.d_in.get(), st.h_in.get(), bytes, hipMemcpyHostToDevice, copy));
+    return IDC_OK;
+}
+
+int launch_refs(idc_context* c, idc_context::RefStage& st, const RefLayout& lay, float hist_flag, unsigned ref_flags, float* rows, bool want_hist,
+                hipStream_t s) {
+    unsigned char* in = st.d_in.get();
+    unsigned char* work = st.d_work.get();
+    unsigned* counts = (unsigned*)work;
+    double* sat = (double*)(work + lay.o_sat);
+    if (lay.m > 0) {
+        HIPCHK(c, hipMemsetAsync(counts, 0, (size_t)lay.m * 313 * sizeof(unsigned), s));
+        HIPCHK(c, launch_ref_stats((const RefDesc*)in, lay.m, in + lay.o_packed, (const float*)(in + lay.o_centres), c->H, c->W, counts, sat, s));
+    }
+    HIPCHK(c, launch_glob_rows(counts, sat, (const int*)(in + lay.o_index), lay.n, lay.m, c->H, c->W, hist_flag, (ref_flags & IDC_REF_SATURATION) ? 1 : 0,
+                               rows, want_hist ? (float*)(work + lay.o_hist) : nullptr, want_hist ? (float*)(work + lay.o_savg) : nullptr, s));
+    return IDC_OK;
+}
+
 }  // namespace idc
 
 extern "C" {
@@ -389,7 +470,7 @@ int idc_forward_device(idc_handle h, int n, const float* d_L_mc, const float* d_
     // forward's map" (idc_upsample_lab2rgb must not serve it), unless the caller handed the handle's own planes back
     h->out_resident = d_out_ab == h->d_out.get();
     h->labq_resident = false;
-    rc = run_graph(h, n, d_L_mc, d_ab, d_mask, maskcent, d_out_ab, (h->flags & IDC_FLAG_DIST_HEAD) ? h->d_dist.get() : nullptr);
+    rc = run_graph(h, n, d_L_mc, d_ab, d_mask, maskcent, d_out_ab, (h->flags & IDC_FLAG_DIST_HEAD) ? h->d_dist.get() : nullptr, h->d_glob_in.get());
     if (rc) return rc;
     if (sync) {
         HIPCHK(h, wait_stream(h, n));
@@ -522,7 +603,7 @@ int idc_forward_async(idc_handle h, int slot, int n, const float* L_mc, const fl
     HIPCHK(h, hipEventRecord(sl.ev_in.get(), h->s_in.get()));
     HIPCHK(h, hipStreamWaitEvent(h->stream.get(), sl.ev_in.get(), 0));
     HIPCHK(h, hipEventRecord(sl.ev_comp0.get(), h->stream.get()));
-    rc = run_graph(h, n, sl.d_L.get(), sl.d_ab.get(), sl.d_mask.get(), maskcent, sl.d_out.get(), nullptr);
+    rc = run_graph(h, n, sl.d_L.get(), sl.d_ab.get(), sl.d_mask.get(), maskcent, sl.d_out.get(), nullptr, h->d_glob_in.get());
     if (rc) return rc;
     HIPCHK(h, hipEventRecord(sl.ev_comp.get(), h->stream.get()));
     HIPCHK(h, hipStreamWaitEvent(h->s_out.get(), sl.ev_comp.get(), 0));
@@ -536,9 +617,13 @@ int idc_forward_async(idc_handle h, int slot, int n, const float* L_mc, const fl
 
 // The serving form of the product: uint8 images and hint lists in, colourised uint8 images out, on the same two slots.  The slot owns the
 // packed source, the clipped hint list, its planes and its results; every argument is checked before anything is enqueued.
-int idc_forward_async_rgb(idc_handle h, int slot, int n, int src_h, int src_w, const uint8_t* rgb_in, const int32_t* hint_offsets,
-                          const idc_hint* hints, int mode, float mask_value, float maskcent, float l_cent, unsigned flags,
-                          uint8_t* rgb_out, float* out_ab) {
+// ra != nullptr (idc_forward_async_rgb_ref): the batch brings its references, and the network reads the slot's own global inputs, written on
+// the compute stream in front of the prologue; ra == nullptr: the handle's global inputs, as idc_forward_async reads them.
+struct RefArgs { int m; const idc_ref_image* refs; const int32_t* ref_index; const float* centres; float hist_flag; unsigned flags; };
+
+static int forward_async_rgb(idc_handle h, int slot, int n, int src_h, int src_w, const uint8_t* rgb_in, const int32_t* hint_offsets,
+                             const idc_hint* hints, int mode, float mask_value, float maskcent, float l_cent, unsigned flags,
+                             const RefArgs* ra, uint8_t* rgb_out, float* out_ab) {
     int rc = check_forward_args(h, n);
     if (rc) return rc;
     if (slot < 0 || slot > 1) return fail(&h->err, IDC_ERR_INVALID_ARG, "slot %d not in 0..1", slot);
@@ -577,6 +662,12 @@ int idc_forward_async_rgb(idc_handle h, int slot, int n, int src_h, int src_w, c
         if (mode == IDC_HINT_RGB && !(r.c0 >= 0.f && r.c0 <= 255.f && r.c1 >= 0.f && r.c1 <= 255.f && r.c2 >= 0.f && r.c2 <= 255.f))
             return fail(&h->err, IDC_ERR_INVALID_ARG, "hint %d: RGB outside 0..255", k);
         ++kept;
+    }
+    RefLayout lay;
+    if (ra) {
+        rc = check_refs(h, 0, n, ra->m, ra->refs, ra->ref_index, ra->centres, ra->hist_flag, ra->flags, &lay);
+        if (rc) return rc;
+        if (!(h->flags & IDC_FLAG_GLOBAL_HINTS)) return fail(&h->err, IDC_ERR_UNSUPPORTED, "handle was created without IDC_FLAG_GLOBAL_HINTS");
     }
     if (h->audit) return fail(&h->err, IDC_ERR_UNSUPPORTED, "the range audit covers the blocking, resident and device-pointer forwards, not the pipelined slots");
     auto& sl = h->pipe[slot];
@@ -618,17 +709,30 @@ int idc_forward_async_rgb(idc_handle h, int slot, int n, int src_h, int src_w, c
         }
         m_offs[i + 1] = w;
     }
+    if (ra) {
+        HIPCHK(h, sl.d_glob_in.ensure(nb * kGlobIn * sizeof(float)));
+        rc = stage_refs(h, sl.ref, lay, ra->refs, ra->ref_index, ra->centres, false);
+        if (rc) return rc;
+    }
     HIPCHK(h, hipEventRecord(sl.ev_in0.get(), h->s_in.get()));
     HIPCHK(h, hipMemcpyAsync(sl.d_src.get(), s_rgb, in_bytes, hipMemcpyHostToDevice, h->s_in.get()));
     HIPCHK(h, hipMemcpyAsync(sl.d_meta.get(), sl.h_meta.get(), meta_bytes, hipMemcpyHostToDevice, h->s_in.get()));
+    if (ra) {
+        rc = upload_refs(h, sl.ref, lay, h->s_in.get());
+        if (rc) return rc;
+    }
     HIPCHK(h, hipEventRecord(sl.ev_in.get(), h->s_in.get()));
     HIPCHK(h, hipStreamWaitEvent(h->stream.get(), sl.ev_in.get(), 0));
     HIPCHK(h, hipEventRecord(sl.ev_comp0.get(), h->stream.get()));
+    if (ra) {
+        rc = launch_refs(h, sl.ref, lay, ra->hist_flag, ra->flags, sl.d_glob_in.get(), false, h->stream.get());
+        if (rc) return rc;
+    }
     HIPCHK(h, launch_batch_prologue(sl.d_src.get(), n, src_h, src_w, h->H, h->W, l_cent, kept ? (const int*)sl.d_meta.get() : nullptr,
                                     (const HintRect*)(sl.d_meta.get() + hints_at), mode, mask_value, sl.d_L.get(), sl.d_ab.get(), sl.d_mask.get(),
                                     h->stream.get()));
     const int dist_n = h->dist_n;
-    rc = run_graph(h, n, sl.d_L.get(), sl.d_ab.get(), sl.d_mask.get(), maskcent, sl.d_out.get(), nullptr);
+    rc = run_graph(h, n, sl.d_L.get(), sl.d_ab.get(), sl.d_mask.get(), maskcent, sl.d_out.get(), nullptr, ra ? sl.d_glob_in.get() : h->d_glob_in.get());
     if (rc) return rc;
     if (!((h->flags & IDC_FLAG_DIST313) && h->keep_dist313)) h->dist_n = dist_n;      // no distribution was written: the blocking forward's stays resident
     HIPCHK(h, launch_lab_post(sl.d_L.get(), l_cent, sl.d_out.get(), sl.d_rgb.get(), source_out ? sl.d_labq.get() : nullptr, n, h->H, h->W, h->stream.get()));
@@ -644,6 +748,20 @@ int idc_forward_async_rgb(idc_handle h, int slot, int n, int src_h, int src_w, c
     sl.user_out = out_ab; sl.staged_out = staged_ab;
     sl.user_rgb = rgb_out; sl.staged_rgb = staged_rgb; sl.rgb_bytes = rgb_bytes;
     return IDC_OK;
+}
+
+int idc_forward_async_rgb(idc_handle h, int slot, int n, int src_h, int src_w, const uint8_t* rgb_in, const int32_t* hint_offsets,
+                          const idc_hint* hints, int mode, float mask_value, float maskcent, float l_cent, unsigned flags,
+                          uint8_t* rgb_out, float* out_ab) {
+    return forward_async_rgb(h, slot, n, src_h, src_w, rgb_in, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, nullptr, rgb_out, out_ab);
+}
+
+int idc_forward_async_rgb_ref(idc_handle h, int slot, int n, int src_h, int src_w, const uint8_t* rgb_in, const int32_t* hint_offsets,
+                              const idc_hint* hints, int mode, float mask_value, float maskcent, float l_cent, unsigned flags, int m,
+                              const idc_ref_image* refs, const int32_t* ref_index, const float* centres, float hist_flag, unsigned ref_flags,
+                              uint8_t* rgb_out, float* out_ab) {
+    const RefArgs ra = {m, refs, ref_index, centres, hist_flag, ref_flags};
+    return forward_async_rgb(h, slot, n, src_h, src_w, rgb_in, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, &ra, rgb_out, out_ab);
 }
 
 int idc_wait(idc_handle h, int slot) {

@@ -270,6 +270,21 @@ hipError_t launch_snap_colors(const double* L, const unsigned char* rgb, int n, 
 hipError_t launch_global_stats(const unsigned char* rgb, const float* centres, unsigned* counts, double* sat_sum, int N,
                                int H, int W, hipStream_t s);
 
+// Reference-image global hints (idc_global_stats_rgb / idc_set_global_refs / idc_forward_async_rgb_ref; idc_colour.hip).
+// ref_stats: launch_global_stats for m references of INDIVIDUAL sizes, each sampled to the net size [H,W] by launch_ingest_rgb's rule inside the
+// kernel: refs [m] = {byte offset into packed, h, w}, packed = the [h,w,3] u8 images back to back (no alignment asked) -> counts [m][313]
+// (uint32, zeroed by the caller) and sat_part [m][ref_stats_workgroups(H, W)] (float64, every entry written): the saturation sum of each of
+// a reference's workgroups, reduced in a fixed order.  A reference's figures depend on nothing but its own pixels and (H, W).
+// glob_rows: row i < n of rows [n][kGlobIn], the layout launch_glob_branch reads, from reference r = ref_index[i] (< 0: 316 zeros):
+// counts[r] / nblk, hist_flag, and with_sat ? {sum of sat_part[r] in index order / (H*W), 1} : {0, 0}; and, where hist != nullptr, hist
+// [m][313] and s_avg [m] (or nullptr) of every reference, idc_global_histogram's expressions.  n or m may be 0.
+struct RefDesc { long long off; int h, w; };
+int ref_stats_workgroups(int H, int W);
+hipError_t launch_ref_stats(const RefDesc* refs, int m, const unsigned char* packed, const float* centres, int H, int W, unsigned* counts,
+                            double* sat_part, hipStream_t s);
+hipError_t launch_glob_rows(const unsigned* counts, const double* sat_part, const int* ref_index, int n, int m, int H, int W, float hist_flag,
+                            int with_sat, float* rows, float* hist, float* s_avg, hipStream_t s);
+
 // Click session (idc_session.hip).  HintRect = idc_hint of include/ideepcolor.h after clipping: inclusive rectangle,
 // (c0,c1) = ab (mode 0) or (c0,c1,c2) = RGB 0..255 (mode 1).  raster_hints fills ab [2,H,W] and mask [1,H,W] of ONE
 // image: the last covering hint wins; uncovered pixels get ab = 0, mask = 0 (a black canvas is Lab (0,0,0)).

@@ -333,6 +333,47 @@ def flatten_hints(hints, n):
     return offsets, arr
 
 
+def ref_images(refs):
+    """Reference photographs -> what the ``idc_*_ref*`` calls read: (``N.RefImage`` array, the uint8 C-contiguous arrays it points into).  Each
+    entry is an (h,w,3) uint8 array of its own size; the library copies the pixels before the call returns, the arrays only have to live until then."""
+    keep = []
+    for r in refs:
+        a = np.ascontiguousarray(np.asarray(r), dtype=np.uint8)
+        if a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+            raise ValueError("a reference must be an (h,w,3) uint8 image, got %s" % (a.shape,))
+        keep.append(a)
+    arr = (N.RefImage * max(len(keep), 1))()
+    for k, a in enumerate(keep):
+        arr[k].rgb, arr[k].h, arr[k].w = a.ctypes.data, a.shape[0], a.shape[1]
+    return arr, keep
+
+
+def dedupe_refs(refs, n):
+    """Per-image references (n entries, each ``None`` or an array) -> (the distinct arrays in order of first use, ref_index (n,) int32 with -1
+    for ``None``).  Distinct means object identity: the same array object given for several images is uploaded once."""
+    refs = list(refs)
+    if len(refs) != n:
+        raise ValueError("%d references for %d images" % (len(refs), n))
+    uniq, where, index = [], {}, np.full(n, -1, np.int32)
+    for i, r in enumerate(refs):
+        if r is None:
+            continue
+        if id(r) not in where:
+            where[id(r)] = len(uniq)
+            uniq.append(r)
+        index[i] = where[id(r)]
+    return uniq, index
+
+
+def _ref_index(ref_index, n):
+    if ref_index is None:
+        return None
+    idx = np.ascontiguousarray(np.asarray(ref_index), dtype=np.int32)
+    if idx.shape != (n,):
+        raise ValueError("ref_index must have %d entries, got %s" % (n, idx.shape))
+    return idx
+
+
 class HipColorizer(object):
     def __init__(self, H=256, W=None, max_batch=1, precision="bf16", device=0, dist=False, global_hints=False, dist313=False,
                  throughput_blob=False):
@@ -696,6 +737,35 @@ class HipColorizer(object):
                                                 _fptr(sat) if want_sat else None))
         return hist, sat
 
+    def global_stats_rgb(self, refs, centres, want_sat=True):
+        """``global_histogram`` for reference photographs as they come (``idc_global_stats_rgb``): refs is a list of (h,w,3) uint8 arrays of
+        individual sizes (or one array), each resized on the device by ``set_image_rgb``'s rule; centres (313,2) -> (hist (m,313) float32
+        summing to 1, s_avg (m,) or None).  A reference's figures do not depend on the others in the call."""
+        if isinstance(refs, np.ndarray) and refs.ndim == 3:
+            refs = [refs]
+        arr, keep = ref_images(refs)
+        m = len(keep)
+        c = _f32c(centres, (313, 2))
+        hist = np.empty((max(m, 1), 313), np.float32)
+        sat = np.empty(max(m, 1), np.float32) if want_sat else None
+        self._chk(self.lib.idc_global_stats_rgb(self._h, m, arr, _fptr(c), _fptr(hist), _fptr(sat) if want_sat else None))
+        return hist[:m], (sat[:m] if want_sat else None)
+
+    def set_global_refs(self, refs, centres, ref_index=None, img=0, hist_flag=1.0, saturation=False):
+        """Install references as the global hints of image slots img .. img+n-1 on the device (``idc_set_global_refs``): the rows
+        ``set_global_hints`` would be given -- histogram, ``hist_flag`` and, with ``saturation``, (mean saturation, 1) -- without the histogram
+        visiting the host.  ``ref_index`` (n,): which of ``refs`` each image takes, -1 = none (a zero row); None = one reference per image in
+        order.  Other slots keep their rows; in effect until replaced or cleared."""
+        if isinstance(refs, np.ndarray) and refs.ndim == 3:
+            refs = [refs]
+        arr, keep = ref_images(refs)
+        m = len(keep)
+        n = m if ref_index is None else len(ref_index)
+        idx = _ref_index(ref_index, n)
+        c = _f32c(centres, (313, 2))
+        self._chk(self.lib.idc_set_global_refs(self._h, int(img), int(n), m, arr, idx.ctypes.data_as(ctypes.c_void_p) if idx is not None else None,
+                                               _fptr(c), float(hist_flag), N.IDC_REF_SATURATION if saturation else 0))
+
     def lab2rgb(self, L, ab, want_lab=True):
         """Device colour step: L (n,1,H,W) in [0,100], ab (n,2,H,W) -> (rgb (n,H,W,3) uint8, lab_q (n,3,H,W) f64 or None)
         = ``lab2rgb_transpose`` + the rgb->Lab refresh of the reference (colorize_image.py:20-36,196-198)."""
@@ -811,13 +881,19 @@ class HipColorizer(object):
         self._results_will_be_replaced()
         self._chk(self.lib.idc_forward_async(self._h, int(slot), int(n), _fptr(L_mc), _fptr(ab), _fptr(mask), float(maskcent), _fptr(out)))
 
-    def forward_async_rgb(self, slot, rgb, hints, out_rgb, out_ab=None, mode="ab", mask_value=1.0, maskcent=0.0, l_cent=50.0, out="net"):
+    def forward_async_rgb(self, slot, rgb, hints, out_rgb, out_ab=None, mode="ab", mask_value=1.0, maskcent=0.0, l_cent=50.0, out="net",
+                          refs=None, ref_index=None, centres=None, hist_flag=1.0, saturation=False):
         """Enqueue one batch of uint8 images on pipeline slot 0/1 (``idc_forward_async_rgb``): rgb (n,h,w,3) uint8 C-contiguous, any size up
         to 16384 a side, is ingested as by ``set_image_rgb``; ``hints`` is a list of n per-image hint lists (rows as in ``set_hints``, ``None``
         or [] for an image without) or ``None``.  ``out_rgb`` uint8 receives the colourised images: (n,H,W,3) with out='net' (what
         ``forward_rgb`` returns), (n,h,w,3) with out='source' (``fullres_rgb('output_ab', 'linear', 'image')`` of every image); ``out_ab``
         (n,2,H,W) float32 or None the network's ab map.  The arrays are used in place: leave them untouched until ``wait(slot)`` (the engine
-        holds a reference to each until then, so a caller that drops its own cannot have the result written into freed memory)."""
+        holds a reference to each until then, so a caller that drops its own cannot have the result written into freed memory).
+        ``refs`` (a ``global_hints`` engine): a list of m reference photographs, (h,w,3) uint8 each of its own size, whose statistics become
+        the batch's global hints on the device (``idc_forward_async_rgb_ref``; an empty list: no image has one); ``ref_index`` (n,) names
+        each image's reference, -1 = none, None = one per image in order; ``centres`` (313,2), ``hist_flag`` and ``saturation`` as in
+        ``set_global_refs``.  The slot keeps these global inputs to itself: ``set_global_hints`` / ``set_global_refs`` are neither read nor
+        changed.  ``refs=None``: the plain call, which reads the handle's global hints."""
         if not isinstance(rgb, np.ndarray) or rgb.dtype != np.uint8 or rgb.ndim != 4 or rgb.shape[3] != 3 or not rgb.flags.c_contiguous:
             raise ValueError("forward_async_rgb needs a uint8 C-contiguous (n,h,w,3) array")
         n, sh, sw = rgb.shape[:3]
@@ -829,12 +905,22 @@ class HipColorizer(object):
             raise ValueError("forward_async_rgb needs a float32 C-contiguous out_ab of shape %s" % ((n, 2, self.H, self.W),))
         offsets, arr = flatten_hints(hints, n)
         vp = ctypes.c_void_p
-        self._chk(self.lib.idc_forward_async_rgb(self._h, int(slot), int(n), int(sh), int(sw), rgb.ctypes.data_as(vp),
-                                                 offsets.ctypes.data_as(vp) if offsets is not None else None,
-                                                 ctypes.cast(arr, vp) if arr is not None else None,
-                                                 {"ab": N.IDC_HINT_AB, "rgb": N.IDC_HINT_RGB}[mode], float(mask_value), float(maskcent),
-                                                 float(l_cent), flags, out_rgb.ctypes.data_as(vp),
-                                                 out_ab.ctypes.data_as(vp) if out_ab is not None else None))
+        head = (self._h, int(slot), int(n), int(sh), int(sw), rgb.ctypes.data_as(vp),
+                offsets.ctypes.data_as(vp) if offsets is not None else None, ctypes.cast(arr, vp) if arr is not None else None,
+                {"ab": N.IDC_HINT_AB, "rgb": N.IDC_HINT_RGB}[mode], float(mask_value), float(maskcent), float(l_cent), flags)
+        tail = (out_rgb.ctypes.data_as(vp), out_ab.ctypes.data_as(vp) if out_ab is not None else None)
+        if refs is None:
+            self._chk(self.lib.idc_forward_async_rgb(*(head + tail)))
+        else:
+            if isinstance(refs, np.ndarray) and refs.ndim == 3:
+                refs = [refs]
+            rarr, keep = ref_images(refs)
+            m = len(keep)
+            idx = _ref_index(ref_index, n)
+            c = _f32c(centres, (313, 2)) if centres is not None else None
+            self._chk(self.lib.idc_forward_async_rgb_ref(*(head + (m, rarr if m else None, idx.ctypes.data_as(vp) if idx is not None else None,
+                                                                   _fptr(c) if c is not None else None, float(hist_flag),
+                                                                   N.IDC_REF_SATURATION if saturation else 0) + tail)))
         self._in_flight[int(slot)] = (rgb, out_rgb, out_ab)      # the library reads / writes them until the slot's wait
 
     def colorize_stream(self, batches, out="net", **kw):
@@ -842,7 +928,10 @@ class HipColorizer(object):
         (``hints`` as in ``forward_async_rgb``; n and the source size may change from item to item); each item's (n,H,W,3) [out='net'] or
         (n,h,w,3) [out='source'] uint8 result is yielded in input order, as an array of the caller's own (copied out of the pinned buffer the
         device wrote).  Item k runs on slot k % 2 while item k - 1 computes; its buffers come from the pinned pool.  ``kw``: mode, mask_value,
-        maskcent, l_cent of ``forward_async_rgb``."""
+        maskcent, l_cent of ``forward_async_rgb``.
+        An item may be (rgb, hints, refs) on a ``global_hints`` engine: ``refs`` is a list of n entries, each ``None`` or an (h,w,3) uint8
+        reference photograph for that image.  The same array OBJECT given for several images of an item is uploaded once (``dedupe_refs``);
+        ``kw`` then also carries centres (needed), hist_flag and saturation.  A two-entry item makes the plain call."""
         pending = [None, None]                      # per slot: (pinned result, pinned source) of the batch in flight
 
         def finish(slot):
@@ -852,7 +941,8 @@ class HipColorizer(object):
 
         k = 0
         try:
-            for rgb, hints in batches:
+            for item in batches:
+                rgb, hints = item[0], item[1]
                 slot = k & 1
                 if pending[slot] is not None:
                     yield finish(slot)
@@ -862,7 +952,11 @@ class HipColorizer(object):
                 src = self._pool.take(rgb.shape, np.uint8)
                 np.copyto(src, rgb)
                 dst = self._pool.take(rgb.shape if out == "source" else (rgb.shape[0], self.H, self.W, 3), np.uint8)
-                self.forward_async_rgb(slot, src, hints, dst, out=out, **kw)
+                if len(item) > 2:
+                    uniq, index = dedupe_refs(item[2], rgb.shape[0])
+                    self.forward_async_rgb(slot, src, hints, dst, out=out, refs=uniq, ref_index=index, **kw)
+                else:
+                    self.forward_async_rgb(slot, src, hints, dst, out=out, **kw)
                 pending[slot] = (dst, src)
                 k += 1
             for slot in (k & 1, (k + 1) & 1):       # the older batch first
