@@ -84,7 +84,7 @@ int idc_version(void);
  * variant at small sizes.  No reference counterpart. */
 int idc_set_tile_policy(int policy);
 /* Process-wide switches for the parity tests and A/B measurements (speed / kernel choice only: every setting computes the same
- * function).  Eleven names (round 6: three former environment switches became options; the library reads NO tuning knob from the environment):
+ * function).  Eighteen names (round 6: three former environment switches became options; the library reads NO tuning knob from the environment):
  *   "fuse_conv1"  (1)  model1 = conv1_1 + conv1_2 as one launch on the bf16 path; 0 keeps the two launches apart, so that conv1_1's own
  *                      output exists and can be read with idc_get_activation.
  *   "click"       (-1 = on)  small launches (the batch-1 click path, fp32 and what "kwave" does not cover) run conv_click
@@ -113,6 +113,11 @@ int idc_set_tile_policy(int policy);
  *   "pcie_kernel" (1)  their host <-> device transfers (<= 2 MiB, pinned) run as a copy kernel on the forward's stream; 0 = hipMemcpyAsync.
  *   "op_policy_batch" (0)  single-operator entry points (idc_op_*): the batch the kernel variant is chosen for, as a handle's max_batch is for its
  *                      forwards; 0 = the call's own batch.  The launch always carries the call's batch.  Not read by any forward.
+ *   "op_out_f32"  (0)  idc_op_conv2d / idc_op_deconv4x4s2: 1 = the op's output tensor is fp32 in every precision, as the network keeps its class / 313
+ *                      logits and hyper-column partial sums, and the kernel is chosen as for such a layer (never the bf16 large tile).
+ *                      idc_op_deconv_shortcut then answers IDC_ERR_UNSUPPORTED: the fused launch stores 16-bit outputs only.  Not read by any forward.
+ *   "op_resid_f32" (0)  ... 1 = the shortcut sum (resid) of an IDC_BF16 op is an fp32 tensor, as the one a hyper-column launch reads; every other
+ *                      precision stores it so already.  Not read by any forward.
  *   "kw_force_abort" (0)  TEST HOOK: 1 makes the persistent trunk launch's first grid barrier unreachable (plays "workgroups never co-resident").
  * Retired with their kernels, or folded into the above: "fuse_conv1_small", "winograd_bf16", "winograd_form", "winograd_deconv", "conv1_lw",
  * "code_warm", "kwave_deconv" (IDC_ERR_INVALID_ARG).

@@ -247,12 +247,17 @@ static int run_single_op(int device_id, int precision, LayerSpec spec, int n, in
     if (spec.in_stride != 1 && spec.in_stride != 2) return fail(nullptr, IDC_ERR_INVALID_ARG, "in_stride must be 1 or 2");
     if (h % spec.in_stride || w % spec.in_stride) return fail(nullptr, IDC_ERR_INVALID_ARG, "H, W must divide by in_stride");
     if (sc && (!sc->x || !sc->w || !sc->b || sc->cin <= 0 || sc->cin % kc)) return fail(nullptr, IDC_ERR_INVALID_ARG, "bad shortcut operand");
+    // storage as the network's fp32-kept layers have it (options "op_out_f32", "op_resid_f32"): class / 313 logits and the hyper-column partial sums
+    const bool out_f32 = options().op_out_f32 != 0, resid_f32 = options().op_resid_f32 != 0;
+    if (sc && out_f32) return fail(nullptr, IDC_ERR_UNSUPPORTED, "deconv + shortcut: the fused launch stores 16-bit outputs only (option 'op_out_f32')");
+    spec.out_f32 = out_f32 ? 1 : 0;          // (the planner keeps fp32-OUTPUT layers off the bf16 large tile: set_geometry's v2_covers)
     // the batch the variant is chosen for, as a handle's max_batch is (option "op_policy_batch"; 0 = this call's own batch); the launch carries n
     const int n_policy = options().op_policy_batch > 0 ? options().op_policy_batch : n;
     idc_context* nullctx = nullptr;
     HIPCHK(nullctx, hipSetDevice(device_id));
     HIPCHK(nullctx, init_kernels());
-    // tensors as a network of this precision stores them: fp32 on the fp32 path, the shortcut sum bf16 on the bf16 path and fp32 on the operand-split ones
+    // tensors as a network of this precision stores them: fp32 on the fp32 path, the shortcut sum bf16 on the bf16 path and fp32 on the operand-split ones;
+    // "op_out_f32" / "op_resid_f32": the output / the bf16 path's shortcut sum in fp32, as a layer with LayerSpec.out_f32 stores and its consumer reads
     const int so = spec.kind == kDeconv4x4 ? 2 : 1, Ho = h / spec.in_stride * so, Wo = w / spec.in_stride * so, cpad = cout_pad(spec.cout);
     std::vector<Tensor> T;
     auto add_tensor = [&](const char* name, int C, int Cpad, int H, int W, bool f32) {
@@ -262,8 +267,8 @@ static int run_single_op(int device_id, int precision, LayerSpec spec, int n, in
         T.push_back(t);
         return (int)T.size() - 1;
     };
-    const int t_x = add_tensor("x", spec.cin, spec.cin, h, w, precision == IDC_FP32), t_y = add_tensor("y", spec.cout, cpad, Ho, Wo, precision == IDC_FP32);
-    const int t_r = (resid || sc) ? add_tensor("resid", spec.cout, cpad, Ho, Wo, precision != IDC_BF16) : -1;      // (with sc: planned, never stored)
+    const int t_x = add_tensor("x", spec.cin, spec.cin, h, w, precision == IDC_FP32), t_y = add_tensor("y", spec.cout, cpad, Ho, Wo, precision == IDC_FP32 || out_f32);
+    const int t_r = (resid || sc) ? add_tensor("resid", spec.cout, cpad, Ho, Wo, precision != IDC_BF16 || resid_f32) : -1;      // (with sc: planned, never stored)
     const int t_x2 = sc ? add_tensor("x_short", sc->cin, sc->cin, Ho, Wo, precision == IDC_FP32) : -1;
     // layers, their parameters placed in one staging blob
     size_t blob_bytes = 0;
@@ -370,7 +375,7 @@ static int run_single_op(int device_id, int precision, LayerSpec spec, int n, in
     if (a.ksplit > 1) HIPCHK(nullctx, launch_splitk_epilogue(precision, a, nullptr));
     const size_t yout = (size_t)n * spec.cout * Ho * Wo;
     HIPCHK(nullctx, d_nchw.ensure(yout * 4));
-    if (split) HIPCHK(nullctx, launch_split_to_nchw(ty.ptr, d_nchw.get(), n, spec.cout, Ho, Wo, cpad, parts, f16 ? 1 : 0, nullptr));
+    if (split && !ty.is_f32) HIPCHK(nullctx, launch_split_to_nchw(ty.ptr, d_nchw.get(), n, spec.cout, Ho, Wo, cpad, parts, f16 ? 1 : 0, nullptr));
     else HIPCHK(nullctx, launch_nhwc_to_nchw(ty.is_f32 ? 0 : 1, ty.ptr, d_nchw.get(), n, spec.cout, Ho, Wo, cpad, nullptr));
     HIPCHK(nullctx, hipMemcpy(y, d_nchw.get(), yout * 4, hipMemcpyDeviceToHost));
     HIPCHK(nullctx, hipDeviceSynchronize());
@@ -383,7 +388,7 @@ int idc_op_conv2d(int device_id, int precision, int n, int cin, int h, int w, co
     if (ksize != 3 && ksize != 1) return fail(nullptr, IDC_ERR_UNSUPPORTED, "ksize must be 1 or 3");
     if (dilation != 1 && dilation != 2) return fail(nullptr, IDC_ERR_UNSUPPORTED, "dilation must be 1 or 2");
     if (ksize == 1 && (dilation != 1 || in_stride != 1)) return fail(nullptr, IDC_ERR_UNSUPPORTED, "1x1 conv: d=1, stride 1 only");
-    // (out_f32 = 0 in the three specs below: an op's storage is its output tensor's; the planner keeps fp32-OUTPUT layers off the bf16 large tile)
+    // (out_f32 = 0 in the three specs below; run_single_op sets it from option "op_out_f32", with the output tensor's storage)
     LayerSpec s{"op", "op", nullptr, ksize == 3 ? kConv3x3 : kConv1x1, cin, cout, dilation, in_stride, act,
                 "x", nullptr, 0, 1, 0};
     return run_single_op(device_id, precision, s, n, h, w, x, weight, bias, bn_scale, bn_shift, resid, y);

@@ -129,6 +129,10 @@ struct Options {
     int kw_force_abort = 0;              // test hook ("kw_force_abort"): the persistent trunk launch's first grid barrier is unreachable and its give-up counter tiny
     // single-operator entry points (idc_diag.hip): the batch their kernel variant is chosen for, as a handle's max_batch is ("op_policy_batch"; 0 = the call's own batch)
     int op_policy_batch = 0;
+    // ... and how they store: the output tensor in fp32 in every precision, LayerSpec.out_f32 set ("op_out_f32"); the shortcut sum of an IDC_BF16 op in
+    // fp32 ("op_resid_f32") -- what the class / 313 logits and the hyper-column partial sums of the distribution heads are inside a network
+    int op_out_f32 = 0;
+    int op_resid_f32 = 0;
     int click = -1;                      // conv_click for small launches: -1 = environment default (on), 0 off, 1 on (idc_set_option "click")
 };
 Options& options();

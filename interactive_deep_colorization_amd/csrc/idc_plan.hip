@@ -628,6 +628,8 @@ int idc_set_option(const char* name, int value) {
         o.op_policy_batch = value;
         return IDC_OK;
     }
+    if (strcmp(name, "op_out_f32") == 0) { o.op_out_f32 = value != 0; return IDC_OK; }
+    if (strcmp(name, "op_resid_f32") == 0) { o.op_resid_f32 = value != 0; return IDC_OK; }
     if (strcmp(name, "kwave_chain") == 0) { o.kwave_chain = value < 0 ? 0 : (value > 2 ? 2 : value); return IDC_OK; }
     return fail(nullptr, IDC_ERR_INVALID_ARG, "unknown option '%s'", name);
 }

@@ -1055,6 +1055,13 @@ def _set_policy_batch(policy_batch):
         set_option("op_policy_batch", int(policy_batch))
 
 
+# out_f32 / resid_f32: the op's output tensor / the shortcut sum of a bf16 op stored in fp32, as the network stores its class / 313 logits and the
+# hyper-column partial sums (options 'op_out_f32', 'op_resid_f32').  Set on EVERY call, so that one call's storage never reaches the next.
+def _set_op_storage(out_f32, resid_f32):
+    set_option("op_out_f32", 1 if out_f32 else 0)
+    set_option("op_resid_f32", 1 if resid_f32 else 0)
+
+
 def op_last_kernel():
     """Label of the kernel the last op_* call of this thread launched, as layer_table() names kernels (``idc_op_last_kernel``)."""
     buf = ctypes.create_string_buffer(96)
@@ -1063,9 +1070,10 @@ def op_last_kernel():
 
 
 def op_conv2d(x, weight, bias, dilation=1, in_stride=1, act=0, bn_scale=None, bn_shift=None, resid=None,
-              precision="fp32", device=0, policy_batch=None):
+              precision="fp32", device=0, policy_batch=None, out_f32=False, resid_f32=False):
     lib = N.load()
     _set_policy_batch(policy_batch)
+    _set_op_storage(out_f32, resid_f32)
     x = _f32c(x); weight = _f32c(weight); bias = _f32c(bias)
     n, cin, h, w = x.shape
     cout, ksize = weight.shape[0], weight.shape[2]
@@ -1077,9 +1085,10 @@ def op_conv2d(x, weight, bias, dilation=1, in_stride=1, act=0, bn_scale=None, bn
     return y
 
 
-def op_deconv4x4s2(x, weight, bias, act=0, resid=None, precision="fp32", device=0, policy_batch=None):
+def op_deconv4x4s2(x, weight, bias, act=0, resid=None, precision="fp32", device=0, policy_batch=None, out_f32=False, resid_f32=False):
     lib = N.load()
     _set_policy_batch(policy_batch)
+    _set_op_storage(out_f32, resid_f32)
     x = _f32c(x); weight = _f32c(weight); bias = _f32c(bias)
     n, cin, h, w = x.shape
     cout = weight.shape[1]
@@ -1095,6 +1104,7 @@ def op_deconv_shortcut(x, w_deconv, b_deconv, x_short, w_short, b_short, act=0, 
     the shortcut conv summed into it (``idc_op_deconv_shortcut``); raises IdcError (UNSUPPORTED) where the network would launch the two apart."""
     lib = N.load()
     _set_policy_batch(policy_batch)
+    _set_op_storage(False, False)                # (the fused launch stores 16-bit outputs and never reads a stored shortcut sum)
     x = _f32c(x); w_deconv = _f32c(w_deconv); b_deconv = _f32c(b_deconv)
     x_short = _f32c(x_short); w_short = _f32c(w_short); b_short = _f32c(b_short)
     n, cin, h, w = x.shape

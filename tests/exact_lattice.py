@@ -1,7 +1,7 @@
 """Integer-lattice operands for exact operator tests (tests/test_ops_exact_gpu.py, tests/test_ops_exact_cpu.py).
 
-Operands are small integers (x in [-4, 4], weights in [-2, 2], bias in [-8, 8], residual in [-16, 16], BN scale a power of two, BN shift an
-integer).  Such values are exact in bf16, in fp16 and in every part of the operand-split precisions, every product is an integer, and every
+Operands are small integers (x in [-4, 4], weights in [-2, 2], bias in [-8, 8], residual in [-16, 16] -- in [-4099, 4099] where the case stores
+it in fp32 --, BN scale a power of two, BN shift an integer).  Such values are exact in bf16, in fp16 and in every part of the operand-split precisions, every product is an integer, and every
 partial sum of a K loop stays below 2^24 -- so fp32 accumulation never rounds and EVERY summation order (tile shape, split-K, K split over
 waves, segments of a split precision, Winograd transforms) yields the same bits.  The expected output is therefore one exact float64
 computation followed by the storage rounding of the path, compared with assert_array_equal: there is no tolerance to tune.
@@ -15,6 +15,7 @@ import torch
 import torch.nn.functional as F
 
 X_MAX, W_MAX, B_MAX, R_MAX, BN_SHIFT_MAX = 4, 2, 8, 16, 8
+R32_MAX = 4099                        # an fp32-stored residual: most integers up to it need more than bf16's 8 significant bits
 BN_SCALES = (0.5, 1.0, 2.0, 4.0)
 EXACT_LIMIT = 2 ** 24                 # integers below it are exact in fp32
 # significant bits the stored parts of an operand-split output hold for certain: two bf16 parts, three bf16 parts, two fp16 parts
@@ -27,15 +28,24 @@ STORAGE = {"fp32": "fp32", "bf16": "bf16", "fp16": "fp16", "bf16x3": "split", "b
 #   wmul: weights are wmul * integers in [-2, 2] (4 for the Winograd 3x3 form: its transformed weights carry factors 1/4)
 #   policy: batch the variant is chosen for (0 = n);  tile / splitk: the two policies;  opts: idc_set_option pairs;  partner: needs -DIDC_AB_PARTNERS
 #   wino: None | "conv" | "deconv" (the Winograd bound applies);  label: what engine.op_last_kernel() must say
+#   out_f32: the output tensor is fp32 in every precision (option op_out_f32: class / 313 logits, hyper-column partial sums);  resid_f32: the
+#   residual is an fp32 tensor on the bf16 path too (option op_resid_f32) and is drawn from [-R32_MAX, R32_MAX]
 Case = collections.namedtuple("Case", "id op precision n cin cout h w ksize dilation in_stride act bn resid cin2 wmul policy tile splitk opts "
-                                      "partner wino label")
+                                      "partner wino out_f32 resid_f32 label")
 
 
 def case(id, op, precision, n, cin, cout, h, w, label, ksize=3, dilation=1, in_stride=1, act=0, bn=None, resid=False, cin2=0, wmul=1,
-         policy=0, tile="auto", splitk="auto", opts=(), partner=False, wino=None):
+         policy=0, tile="auto", splitk="auto", opts=(), partner=False, wino=None, out_f32=False, resid_f32=False):
     assert bn is None or bn in BN_SCALES
+    assert not resid_f32 or resid, "%s: resid_f32 without a residual" % id
+    assert op != "fused" or not (out_f32 or resid_f32), "%s: the fused launch stores 16-bit outputs and reads no stored shortcut sum" % id
     return Case(id, op, precision, n, cin, cout, h, w, ksize, dilation, in_stride, act, bn, resid, cin2, wmul, policy, tile, splitk,
-                tuple(opts), partner, wino, label)
+                tuple(opts), partner, wino, bool(out_f32), bool(resid_f32), label)
+
+
+def resid_max(c):
+    """The bound the case's residual is drawn within."""
+    return R32_MAX if c.resid_f32 else R_MAX
 
 
 def out_hw(c):
@@ -60,7 +70,7 @@ def draw(c):
         d["w2"] = _ints(rs, -W_MAX, W_MAX, (c.cout, c.cin2, 3, 3))
         d["b2"] = _ints(rs, -B_MAX, B_MAX, (c.cout,))
     if c.resid:
-        d["resid"] = _ints(rs, -R_MAX, R_MAX, (c.n, c.cout, ho, wo))
+        d["resid"] = _ints(rs, -resid_max(c), resid_max(c), (c.n, c.cout, ho, wo))
     if c.bn is not None:
         d["bn_s"] = np.full(c.cout, c.bn, np.float32)
         d["bn_t"] = _ints(rs, -BN_SHIFT_MAX, BN_SHIFT_MAX, (c.cout,))
@@ -85,7 +95,9 @@ def assert_bounds(c, d):
     if c.wino == "deconv":
         # F(2x2,2x2) per phase: integer G, |U| <= 4 max|w|, input transform sums 4 pixels, output transform 3 x 3
         acc = max(acc, c.cin * (4 * mx) * (4 * mw) * 9)
-    pre = acc + float(np.abs(d["b"]).max()) + (float(np.abs(d["b2"]).max()) if c.op == "fused" else 0.0) + (R_MAX if c.resid else 0.0)
+    if c.resid:
+        assert np.array_equal(d["resid"], np.round(d["resid"])) and np.abs(d["resid"]).max() <= resid_max(c), "%s: residual off its lattice" % c.id
+    pre = acc + float(np.abs(d["b"]).max()) + (float(np.abs(d["b2"]).max()) if c.op == "fused" else 0.0) + (resid_max(c) if c.resid else 0.0)
     if c.bn is not None:
         pre = pre * c.bn + BN_SHIFT_MAX
     assert acc < EXACT_LIMIT and pre < EXACT_LIMIT, "%s: worst-case sum %.0f / output %.0f leaves the exact fp32 range" % (c.id, acc, pre)
@@ -123,6 +135,12 @@ def bf16_rne(v):
     return r.astype(np.uint32).view(np.float32).reshape(np.shape(v))
 
 
+def bf16_unrepresentable(v):
+    """Fraction of the values of v that bf16 cannot hold (what a kernel that rounds before an fp32 store would change)."""
+    v = np.ascontiguousarray(v, np.float32)
+    return float((bf16_rne(v) != v).mean())
+
+
 def bf16_trunc(v):
     """fp32 -> bf16 by dropping the low 16 bits (what a store that forgets to round does)."""
     u = np.ascontiguousarray(v, np.float32).view(np.uint32) & np.uint32(0xffff0000)
@@ -154,9 +172,9 @@ def assert_split_fit(c, v):
 
 
 def store(c, v):
-    """The storage rounding of the case's path."""
+    """The storage rounding of the case's path: none where the output tensor is fp32 (any value below 2^24 fits, split-fit or not)."""
     kind = STORAGE[c.precision]
-    if kind == "fp32":
+    if kind == "fp32" or getattr(c, "out_f32", False):      # (tests/model1_ref.py passes its own rows: they carry a precision only)
         return v
     if kind == "bf16":
         return bf16_rne(v)

@@ -1,13 +1,18 @@
 """CPU side of the exact-integer operator tests (tests/test_ops_exact_gpu.py): the lattice keeps every row of the table inside the exact range
-of fp32 and inside its split storage, and the exact comparison flags three faults the Gaussian tests' tolerance lets through.  Nothing here
-touches the library."""
+of fp32 and inside its split storage, the fp32-output rows of the bf16 path expect values bf16 cannot hold, and the exact comparison flags three
+faults the Gaussian tests' tolerance lets through.  None of that touches the library.  The census of the configurations with a distribution head
+or global hints reads their plans from tools/plan_dump (the planner without a device) and holds every conv row against the table, the
+fp32-kept layers of the heads by label AND storage."""
+import subprocess
+
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import exact_lattice as xl
-from test_ops_exact_gpu import CASES, CENSUS_EXCEPTIONS, census_misses, normalise
+from test_ops_exact_gpu import CASES, CENSUS_EXCEPTIONS, FLAGGED, STORAGE_LAYERS, case_storage_key, census_misses, normalise, storage_census_misses
+from test_plan_cpu import FLAG_BITS, plan_dump  # noqa: F401  (the module-scoped fixture that compiles tools/plan_dump.cpp)
 
 BF16_TOL = 2.5e-2            # tests/test_ops_gpu.py: |err| <= 2.5e-2 * (1 + max|ref|) on the bf16 path
 
@@ -19,9 +24,40 @@ def test_lattice_bounds_hold(c):
     assert pre < xl.EXACT_LIMIT
     assert c.n in (2, 3) and max(v.size for k, v in d.items() if k in ("x", "x2")) <= 3 * 64 * 40 * 72      # batch 2 or 3, nothing beyond 3 x 64 x 40 x 72
     assert np.abs(d["x"]).max() <= xl.X_MAX and np.abs(d["w"]).max() <= xl.W_MAX * c.wmul and np.abs(d["b"]).max() <= xl.B_MAX
+    assert ("resid" in d) == bool(c.resid) and (c.resid or not c.resid_f32)
+    if c.resid:
+        bound = xl.R32_MAX if c.resid_f32 else xl.R_MAX
+        assert xl.resid_max(c) == bound and np.abs(d["resid"]).max() <= bound and np.array_equal(d["resid"], np.round(d["resid"]))
+        if c.resid_f32:       # most of an fp32 shortcut sum is beyond bf16: a kernel that reads it as bf16, or rounds it, shows
+            assert xl.bf16_unrepresentable(d["resid"]) > 0.5 and np.abs(d["resid"]).max() > 4000
+    if c.out_f32:             # stored as computed: the expectation is the pre-store value, bit for bit
+        np.testing.assert_array_equal(xl.expected(c, d), xl.pre_store(c, d))
 
 
-@pytest.mark.parametrize("c", [c for c in CASES if xl.STORAGE[c.precision] in ("split", "fp16")], ids=lambda c: c.id)
+BF16_F32OUT = [c for c in CASES if c.precision == "bf16" and c.out_f32]
+
+
+def test_the_new_storage_cases_are_all_there():
+    assert len(BF16_F32OUT) == 10 and sum(1 for c in CASES if c.precision == "bf16" and c.resid_f32) == 5
+    assert sum(1 for c in CASES if c.out_f32 and c.precision != "bf16") == 7
+    assert {c.cout for c in CASES if c.out_f32 or c.resid_f32} == {529, 384, 313} and {c.cin for c in CASES if c.out_f32} == {256, 384, 512}
+
+
+@pytest.mark.parametrize("c", BF16_F32OUT, ids=lambda c: c.id)
+def test_fp32_outputs_of_the_bf16_path_do_not_fit_bf16(c):
+    """At least 1 % of each expected output is not representable in bf16, so a kernel that rounds before its fp32 store cannot pass."""
+    frac = xl.bf16_unrepresentable(xl.expected(c))
+    assert frac >= 0.01, "%s: only %.2f %% of the expected values are beyond bf16" % (c.id, 100 * frac)
+
+
+def test_unit_weights_on_the_1x1_529_shape_would_not_see_a_rounding_store():
+    """Why the fp32-output 1x1 rows carry wmul=4: with weights in [-2, 2] the expected values of 256 -> 529 at 8 x 16 fit bf16 (|sum| beyond
+    256 is a 5-sigma event: one value in 135 424 with this seed), a hundred times short of the 1 % the condition asks."""
+    c = [c for c in CASES if c.id == "bf16_f32out_22_1x1_529"][0]
+    assert c.wmul == 4 and xl.bf16_unrepresentable(xl.expected(c._replace(wmul=1))) < 1e-4
+
+
+@pytest.mark.parametrize("c", [c for c in CASES if xl.STORAGE[c.precision] in ("split", "fp16") and not c.out_f32], ids=lambda c: c.id)
 def test_split_storage_holds_every_expected_value(c):
     exp = xl.expected(c)                         # asserts the fit (16 / 24 / 22 significant bits) and fp16's range
     assert np.isfinite(exp).all()
@@ -48,6 +84,34 @@ def test_census_filter():
             dict(name="conv1_2", kernel="fused into conv1_1", launches=0), dict(name="conv3_1", kernel="conv_igemm<bf16,2,2>", launches=1)]
     assert census_misses(rows, labels) == [("conv3_1", "conv_igemm<bf16,2,2>")]
     assert "conv1_block_fused" in CENSUS_EXCEPTIONS
+
+
+# ---- census of the flagged configurations, from the planner alone -----------------------------------------------------------------------------
+def _plan_rows(plan_dump, max_batch, precision, size, flag):
+    out = subprocess.check_output([plan_dump, precision, str(FLAG_BITS[flag]), str(size), str(size), str(max_batch), "1"], text=True)
+    return [dict(name=n, kernel=k, launches=int(l)) for n, k, l in (line.split("\t") for line in out.splitlines())]
+
+
+@pytest.mark.parametrize("max_batch,precision,size,flag", FLAGGED, ids=lambda v: str(v))
+def test_flagged_configurations_launch_only_what_the_table_reaches(plan_dump, max_batch, precision, size, flag):
+    rows = _plan_rows(plan_dump, max_batch, precision, size, flag)
+    assert sum(1 for r in rows if r["launches"] > 0 and r["kernel"].startswith("conv")) >= 20
+    if flag != "global_hints":
+        held = [r["name"] for r in rows if r["name"] in STORAGE_LAYERS]
+        assert held == (["class_logits"] if flag == "dist" else [n for n in STORAGE_LAYERS if n != "class_logits"]), held
+    missing = storage_census_misses(rows, precision, CASES)
+    assert not missing, "launches no exact case reaches (%d, %s, %d x %d, %s): %s" % (max_batch, precision, size, size, flag, missing)
+
+
+def test_storage_census_sees_a_missing_storage_key():
+    """The same label with another storage is a miss: without the fp32-output cases, class_logits on conv_igemm<bf16,2,1> is not reached although
+    the label is in the table."""
+    rows = [dict(name="class_logits", kernel="conv_igemm<bf16,2,1> splitK2", launches=1), dict(name="conv8_3", kernel="conv_igemm<bf16,2,1>", launches=1)]
+    old = [c for c in CASES if not (c.out_f32 or c.resid_f32)]
+    assert normalise("conv_igemm<bf16,2,1>") in set(normalise(c.label) for c in old)
+    assert storage_census_misses(rows, "bf16", old) == [("class_logits", "conv_igemm<bf16,2,1> splitK2", True, False)]
+    assert storage_census_misses(rows, "bf16", CASES) == []
+    assert ("conv_igemm<bf16,2,2>", True, True) in set(case_storage_key(c) for c in CASES)
 
 
 # ---- the checker sees what the tolerance does not -----------------------------------------------------------------------------------------

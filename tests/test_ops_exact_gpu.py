@@ -17,8 +17,14 @@ test_shipped_kernels_are_all_in_the_table builds the shipped configurations and 
 arguments included) that no case here reaches.  A layer table is filled by a forward's planning pass, so each handle runs ONE single-image
 forward (the variant depends on max_batch, not on the images in the call).
 
-Wall time of this file on an MI355X, as measured there: 4.4 s for its 77 tests (pytest's own figure; 7.8 s with interpreter start-up and
-imports); the slowest are the four census handles at 0.1 - 0.8 s, every exact case is below 0.15 s.
+The storage rows (out_f32 / resid_f32) run an op as the distribution heads store: the output tensor in fp32, the shortcut sum of a bf16 op in
+fp32 (options op_out_f32 / op_resid_f32, set by engine.op_conv2d / op_deconv4x4s2 on every call).  They reach what no 16-bit-output case can:
+the fp32 store of every 16-bit kernel's epilogue, the fp32-shortcut read of the bf16 kernels, and conv_igemm<bf16,2,2>, which only fp32-output
+layers take.  An fp32 shortcut sum is drawn from [-4099, 4099], and the fp32 outputs hold values bf16 cannot (tests/test_ops_exact_cpu.py).  The
+plans of the configurations with a distribution head or global hints are held against the table on the CPU (same file; STORAGE_LAYERS here).
+
+Wall time of this file on an MI355X, as measured there: 5.3 s for its 100 tests (pytest's own figure); the slowest are the four census handles
+at 0.1 - 0.8 s, every exact case is below 0.15 s.
 """
 import re
 
@@ -31,7 +37,8 @@ from interactive_deep_colorization_amd import _native, engine
 
 pytestmark = pytest.mark.gpu
 
-_OPTION_DEFAULTS = {"op_policy_batch": 0, "winograd": 1, "ds_mfma16": 1, "kwave": 1, "click": -1, "v2p": 1, "fp16_fast": 1, "split_ds_fuse": 1}
+_OPTION_DEFAULTS = {"op_policy_batch": 0, "winograd": 1, "ds_mfma16": 1, "kwave": 1, "click": -1, "v2p": 1, "fp16_fast": 1, "split_ds_fuse": 1,
+                    "op_out_f32": 0, "op_resid_f32": 0}
 
 CASES = [
     # ---------------------------------------------------------------- fp32: small tile, click, Winograd
@@ -112,6 +119,33 @@ CASES = [
     case("bf16x3_ds_ms", "fused", "bf16x3", 2, 128, 128, 20, 36, "conv_ds_fused_ms+shortcut x3", cin2=64, act=1, policy=32),
     case("bf16x6_ds_ms", "fused", "bf16x6", 2, 512, 256, 5, 9, "conv_ds_fused_ms+shortcut x6", cin2=256, policy=32),
     case("fp16x3_ds_msh", "fused", "fp16x3", 3, 256, 128, 10, 18, "conv_ds_fused_msh+shortcut x3", cin2=128, act=1, policy=32),
+    # ---------------------------------------------------------------- the distribution heads' storage: fp32 outputs, fp32 shortcut sums
+    # (class_logits 256 -> 529, conv3_pred 256 -> 384, conv34..34567_pred 512 -> 384 deconvs chained through fp32 sums, conv345678_pred
+    # reading one, pred_313 384 -> 313).  The planner keeps fp32-output layers off the bf16 large tile, so these are the only cases on
+    # conv_igemm<bf16,2,2>.  wmul=4 on the 1x1 convs: with K = 256 / 384 and weights in [-2, 2] every output would fit bf16.
+    case("bf16_f32out_22_1x1_529", "conv", "bf16", 2, 256, 529, 8, 16, "conv_igemm<bf16,2,2>", ksize=1, wmul=4, policy=128, out_f32=True),
+    case("bf16_f32out_splitk_1x1_529", "conv", "bf16", 3, 256, 529, 8, 16, "conv_igemm<bf16,2,1> splitK4", ksize=1, wmul=4, policy=1, out_f32=True),
+    case("bf16_f32out_22_384", "conv", "bf16", 2, 256, 384, 10, 18, "conv_igemm<bf16,2,2>", policy=64, out_f32=True),
+    case("bf16_f32out_kwave_384", "conv", "bf16", 3, 256, 384, 10, 18, "conv_kwave_bf16", policy=1, out_f32=True),
+    case("bf16_f32sum_22_deconv_384", "deconv", "bf16", 2, 512, 384, 5, 9, "conv_igemm<bf16,2,2>", resid=True, policy=64, out_f32=True, resid_f32=True),
+    case("bf16_f32sum_21_deconv_384", "deconv", "bf16", 3, 512, 384, 5, 9, "conv_igemm<bf16,2,1>", resid=True, policy=32, out_f32=True, resid_f32=True),
+    case("bf16_f32sum_kwave_deconv_384", "deconv", "bf16", 2, 512, 384, 5, 9, "conv_kwave_deconv_bf16", resid=True, policy=1, out_f32=True, resid_f32=True),
+    case("bf16_f32resid_22_384", "conv", "bf16", 3, 256, 384, 10, 18, "conv_igemm<bf16,2,2>", act=1, resid=True, policy=64, resid_f32=True),
+    case("bf16_f32resid_click_384", "conv", "bf16", 2, 256, 384, 10, 18, "conv_click<bf16,1,4> splitK4", act=1, resid=True, policy=1, resid_f32=True),
+    case("bf16_f32out_22_1x1_313", "conv", "bf16", 2, 384, 313, 10, 18, "conv_igemm<bf16,2,2>", ksize=1, wmul=4, policy=64, out_f32=True),
+    case("bf16_f32out_21_1x1_313", "conv", "bf16", 3, 384, 313, 10, 18, "conv_igemm<bf16,2,1>", ksize=1, wmul=4, splitk="never", out_f32=True),
+    case("bf16_f32out_splitk_1x1_313", "conv", "bf16", 2, 384, 313, 10, 18, "conv_igemm<bf16,2,1> splitK3", ksize=1, wmul=4, policy=3, out_f32=True),
+    # ... and on the operand-split precisions and fp16 (out_parts == 0 of conv_igemm_v2s / v2ps and their fp16 twins); their shortcut sum is fp32 always
+    case("fp16x3_f32out_v2psh_384", "conv", "fp16x3", 2, 256, 384, 10, 18, "conv_igemm_v2psh<2,2>x3", out_f32=True),
+    case("fp16x3_f32sum_v2sh_deconv_384", "deconv", "fp16x3", 3, 512, 384, 5, 9, "conv_igemm_v2sh<2,4>x3", resid=True, out_f32=True, resid_f32=True),
+    case("fp16x3_f32out_v2sh_1x1_313", "conv", "fp16x3", 2, 384, 313, 10, 18, "conv_igemm_v2sh<2,2>x3", ksize=1, wmul=4, out_f32=True),
+    case("bf16x6_f32sum_v2s_deconv_384", "deconv", "bf16x6", 2, 512, 384, 5, 9, "conv_igemm_v2s<2,4>x6", resid=True, out_f32=True, resid_f32=True),
+    case("fp16_f32sum_v2sh_deconv_384", "deconv", "fp16", 3, 512, 384, 5, 9, "conv_igemm_v2sh<2,4>x1", resid=True, out_f32=True, resid_f32=True),
+    case("bf16x6_f32out_v2s_1x1_313", "conv", "bf16x6", 3, 384, 313, 10, 18, "conv_igemm_v2s<2,2>x6", ksize=1, wmul=4, out_f32=True),
+    # (what the census of the flagged configurations asks for besides: conv3_pred and conv345678_pred of the operand-split handles)
+    case("bf16x6_f32out_v2ps_384", "conv", "bf16x6", 3, 256, 384, 10, 18, "conv_igemm_v2ps<2,2>x6", out_f32=True),
+    case("bf16x6_f32resid_v2ps_384", "conv", "bf16x6", 2, 256, 384, 10, 18, "conv_igemm_v2ps<2,2>x6", act=1, resid=True, resid_f32=True),
+    case("fp16x3_f32resid_v2psh_384", "conv", "fp16x3", 3, 256, 384, 10, 18, "conv_igemm_v2psh<2,2>x3", act=1, resid=True, resid_f32=True),
 ]
 assert len(set(c.id for c in CASES)) == len(CASES)
 
@@ -133,9 +167,11 @@ def run_case(c, d):
         engine.set_option(name, value)
     if c.op == "conv":
         got = engine.op_conv2d(d["x"], d["w"], d["b"], dilation=c.dilation, in_stride=c.in_stride, act=c.act, bn_scale=d.get("bn_s"),
-                               bn_shift=d.get("bn_t"), resid=d.get("resid"), precision=c.precision, policy_batch=c.policy)
+                               bn_shift=d.get("bn_t"), resid=d.get("resid"), precision=c.precision, policy_batch=c.policy,
+                               out_f32=c.out_f32, resid_f32=c.resid_f32)
     elif c.op == "deconv":
-        got = engine.op_deconv4x4s2(d["x"], d["w"], d["b"], act=c.act, resid=d.get("resid"), precision=c.precision, policy_batch=c.policy)
+        got = engine.op_deconv4x4s2(d["x"], d["w"], d["b"], act=c.act, resid=d.get("resid"), precision=c.precision, policy_batch=c.policy,
+                                    out_f32=c.out_f32, resid_f32=c.resid_f32)
     else:
         got = engine.op_deconv_shortcut(d["x"], d["w"], d["b"], d["x2"], d["w2"], d["b2"], act=c.act, precision=c.precision, policy_batch=c.policy)
     return got, engine.op_last_kernel()
@@ -152,6 +188,41 @@ def test_exact(c):
     got, label = run_case(c, d)
     assert label == c.label, "%s ran %r, the table expects %r" % (c.id, label, c.label)
     xl.compare(got, exp, "%s [%s]" % (c.id, label))
+
+
+def _by_id(case_id):
+    return [c for c in CASES if c.id == case_id][0]
+
+
+def test_storage_options_do_not_outlive_a_call():
+    """The wrappers set op_out_f32 / op_resid_f32 on every call: a 16-bit row run right after a storage row stores 16 bits again."""
+    for case_id in ("bf16_f32sum_kwave_deconv_384", "bf16_kwave_deconv_8chunks", "bf16_f32resid_click_384", "bf16_click_leaky_resid"):
+        c = _by_id(case_id)
+        d = xl.draw(c)
+        got, label = run_case(c, d)
+        assert label == c.label
+        xl.compare(got, xl.expected(c, d), "%s after the row before it" % case_id)
+
+
+def test_fused_op_refuses_an_fp32_output():
+    """The deconv + shortcut launch stores 16-bit outputs only: with op_out_f32 set (past the wrapper, which always clears it) the entry point
+    answers IDC_ERR_UNSUPPORTED before it plans anything; cleared, the same call runs."""
+    import ctypes
+    c = _by_id("bf16_ds_half")
+    d = {k: np.ascontiguousarray(v, np.float32) for k, v in xl.draw(c).items()}
+    y = np.empty((c.n, c.cout) + xl.out_hw(c), np.float32)
+    ptr = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+    lib = _native.load()
+    engine.set_option("op_policy_batch", c.policy)
+
+    def call():
+        return lib.idc_op_deconv_shortcut(0, 1, c.n, c.cin, c.h, c.w, ptr(d["x"]), c.cout, ptr(d["w"]), ptr(d["b"]), c.cin2, ptr(d["x2"]), ptr(d["w2"]),
+                                          ptr(d["b2"]), c.act, ptr(y))
+    engine.set_option("op_out_f32", 1)
+    assert _native.STATUS_NAMES[call()] == "IDC_ERR_UNSUPPORTED" and engine.op_last_kernel() == ""
+    engine.set_option("op_out_f32", 0)
+    assert call() == 0 and engine.op_last_kernel() == c.label
+    xl.compare(y, xl.expected(c), "bf16_ds_half through the C entry point")
 
 
 # ---- census: what the shipped configurations launch is what the table reaches -----------------------------------------------------------
@@ -187,6 +258,38 @@ def census_misses(rows, table_labels):
             continue
         if normalise(k) not in table_labels:
             out.append((r["name"], k))
+    return out
+
+
+# ---- census of the configurations with a distribution head or global hints (run on the CPU from tools/plan_dump: tests/test_ops_exact_cpu.py) ----
+# Their fp32-kept layers are matched on storage too: (label, output stored in fp32, shortcut sum read from an fp32 tensor).  The table mirrors the
+# out_f32 and resid columns of idc_net.h; every tensor a resid column names there is itself out_f32.
+STORAGE_LAYERS = {            # name: (out_f32, has a shortcut sum)
+    "class_logits": (True, False), "conv3_pred": (True, False), "conv34_pred": (True, True), "conv345_pred": (True, True),
+    "conv3456_pred": (True, True), "conv34567_pred": (True, True), "conv345678_pred": (False, True), "pred_313": (True, False),
+}
+FLAGGED = [(mb, p, 256, f) for mb, p in SHIPPED for f in ("dist", "dist313", "global_hints")] + [(8, "bf16x6", 256, "dist313"), (8, "bf16", 512, "global_hints")]
+
+
+def case_storage_key(c):
+    """(label, fp32 output tensor, fp32 shortcut-sum tensor) of a case: the fp32 path stores everything so, and only the bf16 path has a
+    16-bit shortcut sum."""
+    return (normalise(c.label), bool(c.out_f32 or c.precision == "fp32"), bool(c.resid and (c.resid_f32 or c.precision != "bf16")))
+
+
+def row_storage_key(name, kernel, precision):
+    out_f32, resid = STORAGE_LAYERS[name]
+    return (normalise(kernel), bool(out_f32 or precision == "fp32"), resid)
+
+
+def storage_census_misses(rows, precision, cases):
+    """census_misses, with the rows of STORAGE_LAYERS held to their storage key as well."""
+    cases = [c for c in cases if not c.partner]
+    out = census_misses([r for r in rows if r["name"] not in STORAGE_LAYERS], set(normalise(c.label) for c in cases))
+    keys = set(case_storage_key(c) for c in cases)
+    for r in rows:
+        if r["name"] in STORAGE_LAYERS and r["launches"] > 0 and row_storage_key(r["name"], r["kernel"], precision) not in keys:
+            out.append((r["name"], r["kernel"]) + row_storage_key(r["name"], r["kernel"], precision)[1:])
     return out
 
 
