@@ -498,6 +498,32 @@ int idc_forward_async_rgb_ref(idc_handle h, int slot, int n, int src_h, int src_
                               float l_cent, unsigned flags, int m, const idc_ref_image* refs, const int32_t* ref_index,
                               const float* centres, float hist_flag, unsigned ref_flags, uint8_t* rgb_out, float* out_ab);
 
+/* ---- pipelined batches of images of INDIVIDUAL sizes: idc_forward_async_rgb / idc_forward_async_rgb_ref for a folder of photographs,
+ *      where no two images need share a size.  images [n]: host images [h,w,3] uint8, each with its own pointer and size (1..16384 a
+ *      side, IDC_BATCH_MAX_SOURCE_BYTES in all); rgb_out [n]: one host pointer per image.  Image i follows exactly the semantics of
+ *      idc_forward_async_rgb called with n = 1 on image i -- ingestion, hints in net coordinates, the network, and
+ *        rgb_out[i] [H,W,3]                          (flags 0), or
+ *        rgb_out[i] [images[i].h, images[i].w, 3]    (IDC_BATCH_OUT_SOURCE): the full-resolution step under the L of its own source pixels
+ *      -- and is bit-identical to it: on the device the images lie packed back to back behind a small table (offset, size and leading
+ *      pixel count per image, sent with the hint list), and the prologue and the full-resolution epilogue are still ONE launch each for
+ *      all n images.  out_ab [n,2,H,W] or NULL, hint_offsets / hints, mode, mask_value, maskcent, l_cent and flags as in
+ *      idc_forward_async_rgb.  refs == NULL: the handle's global inputs are read; otherwise the six reference arguments of
+ *      idc_forward_async_rgb_ref, on the slot's own global inputs.  idc_wait and idc_pipeline_times as for the other two calls, and what
+ *      is said there about slot ownership, resident state, the 313 head and the range audit applies unchanged.
+ *      Host memory: each image pointer, each output pointer and out_ab is judged on its own -- pinned memory is transferred in place,
+ *      pageable memory goes through the slot's pinned staging (neighbouring staged images travel as one copy).  images, rgb_out, the
+ *      hint arrays and the reference arrays are consumed before the call returns; the image bytes and the output buffers stay the
+ *      caller's, untouched, until idc_wait.
+ *      Status, all decided on the host before anything is enqueued or any image byte is read (a refused call leaves the slot as it
+ *      was): the codes of idc_forward_async_rgb for the shared arguments and, for the reference block, those of
+ *      idc_forward_async_rgb_ref; IDC_ERR_INVALID_ARG for NULL images or rgb_out, a NULL images[i].rgb or rgb_out[i], an h or w
+ *      outside 1..16384, a sum of source bytes above IDC_BATCH_MAX_SOURCE_BYTES. */
+typedef struct idc_batch_refs { int32_t m; const idc_ref_image* refs; const int32_t* ref_index; const float* centres;
+                                float hist_flag; uint32_t flags; } idc_batch_refs;   /* as idc_forward_async_rgb_ref's six arguments */
+int idc_forward_async_images(idc_handle h, int slot, int n, const idc_ref_image* images, const int32_t* hint_offsets,
+                             const idc_hint* hints, int mode, float mask_value, float maskcent, float l_cent, unsigned flags,
+                             const idc_batch_refs* refs, uint8_t* const* rgb_out, float* out_ab);
+
 /* ---- colour picker on the device: replaces data/lab_gamut.py, the host colour maths the GUI runs on every mouse press
  *      (ui/gui_draw.py:11,182-183,195-204; ui/gui_gamut.py:4), in float64 with the constants and operation order of idc_lab2rgb.
  *      idc_gamut_map = abGrid(gamut_size, D).update_gamut(L[k]) (lab_gamut.py:56-78) for k = 0..n-1 in one launch.  The grid has

@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = [
     "idc_comm_unique_id", "idc_broadcast_weights", "idc_upsample_lab2rgb", "idc_set_image_rgb", "idc_fullres_rgb",
     "idc_forward_async_rgb",
     "idc_global_stats_rgb", "idc_set_global_refs", "idc_forward_async_rgb_ref",
+    "idc_forward_async_images",
     "idc_gamut_map", "idc_snap_colors",
     "idc_set_range_audit", "idc_range_reset", "idc_range_report", "idc_pack_weights_ex", "idc_load_weights_ex",
 ]
@@ -69,6 +70,12 @@ class Hint(ctypes.Structure):
 class RefImage(ctypes.Structure):
     """idc_ref_image: one host reference photograph, [h,w,3] uint8."""
     _fields_ = [("rgb", ctypes.c_void_p), ("h", ctypes.c_int32), ("w", ctypes.c_int32)]
+
+
+class BatchRefs(ctypes.Structure):
+    """idc_batch_refs: the six reference arguments of idc_forward_async_rgb_ref, for idc_forward_async_images."""
+    _fields_ = [("m", ctypes.c_int32), ("refs", ctypes.POINTER(RefImage)), ("ref_index", ctypes.c_void_p), ("centres", ctypes.c_void_p),
+                ("hist_flag", ctypes.c_float), ("flags", ctypes.c_uint32)]
 
 
 class LayerInfo(ctypes.Structure):
@@ -176,6 +183,8 @@ def load():
     proto("idc_set_global_refs", ci, [vp, ci, ci, ci, ctypes.POINTER(RefImage), vp, c_float_p, cf, ctypes.c_uint])
     proto("idc_forward_async_rgb_ref", ci, [vp, ci, ci, ci, ci, vp, vp, vp, ci, cf, cf, cf, ctypes.c_uint,
                                             ci, ctypes.POINTER(RefImage), vp, c_float_p, cf, ctypes.c_uint, vp, vp])
+    proto("idc_forward_async_images", ci, [vp, ci, ci, ctypes.POINTER(RefImage), vp, vp, ci, cf, cf, cf, ctypes.c_uint,
+                                           ctypes.POINTER(BatchRefs), ctypes.POINTER(vp), vp])
     proto("idc_gamut_map", ci, [vp, ci, vp, ci, ci, vp, vp, vp])
     proto("idc_snap_colors", ci, [vp, ci, vp, vp, vp, vp, vp])
     proto("idc_set_range_audit", ci, [vp, ci])

@@ -470,6 +470,43 @@ hipError_t launch_fullres_rgb(const unsigned char* src, int oh, int ow, const vo
 // byte i * src_h * src_w * 3 of the packed source; the taps are byte gathers, so no alignment is asked of an image's start).  Hints: image i's
 // clipped list hints[offs[i] .. offs[i+1]) walked last first, raster_hints_kernel's pixel; an RGB hint goes through the LDS table, whose
 // entries are the per-colour expression of raster_hints_kernel.  The three planes are written as coalesced fp32.
+// The pixel both prologue kernels compute: net-size pixel (y, x) of an image whose [sh,sw,3] source starts at img, and the image's clipped hints
+// hints[lo .. hi).  -> L - l_cent, and (a, b, mask) of the last covering hint (0, 0, 0 without one).
+__device__ __forceinline__ void prologue_pixel(const unsigned char* __restrict__ img, int sh, int sw, int H, int W, int y, int x, float l_cent,
+                                               const double* tab, const HintRect* __restrict__ hints, int lo, int hi, int mode, float mask_value,
+                                               float& Lv, float& a, float& b, float& m) {
+    int y0, y1, x0, x1;
+    double wy, wx;
+    bilinear_taps(y, sh, H, y0, y1, wy);
+    bilinear_taps(x, sw, W, x0, x1, wx);
+    const unsigned char* p00 = img + ((long long)y0 * sw + x0) * 3; const unsigned char* p01 = img + ((long long)y0 * sw + x1) * 3;
+    const unsigned char* p10 = img + ((long long)y1 * sw + x0) * 3; const unsigned char* p11 = img + ((long long)y1 * sw + x1) * 3;
+    double lin[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) lin[c] = tab[bilinear_u8((double)p00[c], (double)p01[c], (double)p10[c], (double)p11[c], wx, wy)];
+    double L, a_, b_;
+    linear_to_lab(lin, L, a_, b_);
+    Lv = (float)(L - (double)l_cent);
+    int hit = -1;
+    for (int k = hi - 1; k >= lo; --k) {
+        const HintRect h = hints[k];
+        if (y >= h.y0 && y <= h.y1 && x >= h.x0 && x <= h.x1) { hit = k; break; }
+    }
+    a = 0.f; b = 0.f; m = 0.f;
+    if (hit >= 0) {
+        const HintRect h = hints[hit];
+        m = mask_value;
+        if (mode == 0) {
+            a = h.c0; b = h.c1;
+        } else {
+            const double hl[3] = {tab[(unsigned char)h.c0], tab[(unsigned char)h.c1], tab[(unsigned char)h.c2]};
+            double hL, da, db;
+            linear_to_lab(hl, hL, da, db);
+            a = (float)da; b = (float)db;
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void batch_prologue_kernel(const unsigned char* __restrict__ src, int n, int src_h, int src_w, int H, int W,
                                                              float l_cent, const int* __restrict__ offs, const HintRect* __restrict__ hints,
                                                              int mode, float mask_value, float* __restrict__ Lp, float* __restrict__ ab,
@@ -480,38 +517,10 @@ __global__ __launch_bounds__(256) void batch_prologue_kernel(const unsigned char
     for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (long long)gridDim.x * blockDim.x) {
         const long long i = p / HW, r = p - i * HW;
         const int y = (int)(r / W), x = (int)(r - (long long)y * W);
-        int y0, y1, x0, x1;
-        double wy, wx;
-        bilinear_taps(y, src_h, H, y0, y1, wy);
-        bilinear_taps(x, src_w, W, x0, x1, wx);
-        const unsigned char* img = src + i * sb;
-        const unsigned char* p00 = img + ((long long)y0 * src_w + x0) * 3; const unsigned char* p01 = img + ((long long)y0 * src_w + x1) * 3;
-        const unsigned char* p10 = img + ((long long)y1 * src_w + x0) * 3; const unsigned char* p11 = img + ((long long)y1 * src_w + x1) * 3;
-        double lin[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) lin[c] = tab[bilinear_u8((double)p00[c], (double)p01[c], (double)p10[c], (double)p11[c], wx, wy)];
-        double L, a_, b_;
-        linear_to_lab(lin, L, a_, b_);
-        Lp[p] = (float)(L - (double)l_cent);
         const int lo = offs != nullptr ? offs[i] : 0, hi = offs != nullptr ? offs[i + 1] : 0;
-        int hit = -1;
-        for (int k = hi - 1; k >= lo; --k) {
-            const HintRect h = hints[k];
-            if (y >= h.y0 && y <= h.y1 && x >= h.x0 && x <= h.x1) { hit = k; break; }
-        }
-        float a = 0.f, b = 0.f, m = 0.f;
-        if (hit >= 0) {
-            const HintRect h = hints[hit];
-            m = mask_value;
-            if (mode == 0) {
-                a = h.c0; b = h.c1;
-            } else {
-                const double hl[3] = {tab[(unsigned char)h.c0], tab[(unsigned char)h.c1], tab[(unsigned char)h.c2]};
-                double hL, da, db;
-                linear_to_lab(hl, hL, da, db);
-                a = (float)da; b = (float)db;
-            }
-        }
+        float Lv, a, b, m;
+        prologue_pixel(src + i * sb, src_h, src_w, H, W, y, x, l_cent, tab, hints, lo, hi, mode, mask_value, Lv, a, b, m);
+        Lp[p] = Lv;
         ab[(i * 2 + 0) * HW + r] = a;
         ab[(i * 2 + 1) * HW + r] = b;
         mask[p] = m;
@@ -580,6 +589,112 @@ hipError_t launch_batch_fullres_rgb(const unsigned char* src, int n, int oh, int
     const long long ngroups = (total + 3) >> 2;
     const int blocks = (int)((ngroups + 255) / 256 < 8192 ? (ngroups + 255) / 256 : 8192);
     hipLaunchKernelGGL(batch_fullres_rgb_kernel, dim3(blocks), dim3(256), 0, s, src, total, oh, ow, lab_q, H, W, interp, rgb);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// batches of images of INDIVIDUAL sizes (idc_forward_async_images): the two kernels above over a table imgs[0..n] (ImgDesc: byte offset of
+// the image in the packed source, pixels in front of it, h, w; entry n closes the run with the totals).  Still ONE launch each for all n
+// images, and the per-pixel arithmetic is the same device functions on the same operands, so an image's bits do not depend on the route, on
+// its position or on its neighbours.  The table is at most max_batch + 1 entries and read-only, so it is read where it lies, through the cache.
+// ------------------------------------------------------------------------------------------------
+// The last image of imgs[lo .. hi] that starts at or in front of pixel t of the flat run (imgs[lo].first <= t).
+__device__ __forceinline__ int image_of_pixel(const ImgDesc* __restrict__ imgs, int lo, int hi, long long t) {
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (imgs[mid].first <= t) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// batch_prologue_kernel with pixel p's image i = p / (H*W) read from the table: its own h x w, its own start in the packed source.
+__global__ __launch_bounds__(256) void ragged_prologue_kernel(const unsigned char* __restrict__ src, const ImgDesc* __restrict__ imgs, int n, int H,
+                                                              int W, float l_cent, const int* __restrict__ offs,
+                                                              const HintRect* __restrict__ hints, int mode, float mask_value,
+                                                              float* __restrict__ Lp, float* __restrict__ ab, float* __restrict__ mask) {
+    __shared__ double tab[256];
+    fill_srgb_table(tab);
+    const long long HW = (long long)H * W, npix = (long long)n * HW;
+    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (long long)gridDim.x * blockDim.x) {
+        const long long i = p / HW, r = p - i * HW;
+        const int y = (int)(r / W), x = (int)(r - (long long)y * W);
+        const ImgDesc d = imgs[i];
+        const int lo = offs != nullptr ? offs[i] : 0, hi = offs != nullptr ? offs[i + 1] : 0;
+        float Lv, a, b, m;
+        prologue_pixel(src + d.off, d.h, d.w, H, W, y, x, l_cent, tab, hints, lo, hi, mode, mask_value, Lv, a, b, m);
+        Lp[p] = Lv;
+        ab[(i * 2 + 0) * HW + r] = a;
+        ab[(i * 2 + 1) * HW + r] = b;
+        mask[p] = m;
+    }
+}
+
+hipError_t launch_ragged_prologue(const unsigned char* src, const ImgDesc* imgs, int n, int H, int W, float l_cent, const int* offs,
+                                  const HintRect* hints, int mode, float mask_value, float* Lp, float* ab, float* mask, hipStream_t s) {
+    const long long npix = (long long)n * H * W;
+    if (npix <= 0 || imgs == nullptr || (mode != 0 && mode != 1)) return hipErrorInvalidValue;
+    const int blocks = (int)((npix + 255) / 256 < 4096 ? (npix + 255) / 256 : 4096);
+    hipLaunchKernelGGL(ragged_prologue_kernel, dim3(blocks), dim3(256), 0, s, src, imgs, n, H, W, l_cent, offs, hints, mode, mask_value, Lp, ab, mask);
+    return hipGetLastError();
+}
+
+// batch_fullres_rgb_kernel over images of individual sizes packed back to back: the sum of h_i * w_i pixels are ONE flat run from the 4-byte
+// aligned base, a thread takes 4 consecutive pixels = three aligned dwords in, three out, whatever residue an image's start has.  The images a
+// workgroup's 1024 pixels of one step touch are bracketed by two searches whose argument does not depend on the lane (the same addresses for
+// every lane: scalar loads); a lane then searches between the two, which is no step at all unless an image starts inside those 1024 pixels.
+// From its first pixel on a group carries into the next image whenever the current one is used up -- every image has a pixel, so one carry per
+// pixel is enough, and a group of four 1 x 1 images carries four times.  Only the total % 4 pixels at the end of the run use byte accesses.
+__global__ __launch_bounds__(256) void ragged_fullres_rgb_kernel(const unsigned char* __restrict__ src, const ImgDesc* __restrict__ imgs, int n,
+                                                                 const double* __restrict__ lab_q, int H, int W, int interp,
+                                                                 unsigned char* __restrict__ rgb) {
+    __shared__ double tab[256];
+    fill_srgb_table(tab);
+    const long long HW = (long long)H * W, total = imgs[n].first, ngroups = total >> 2;
+    const unsigned* src4 = (const unsigned*)src;
+    unsigned* rgb4 = (unsigned*)rgb;
+    for (long long g0 = (long long)blockIdx.x * blockDim.x; g0 < ngroups; g0 += (long long)gridDim.x * blockDim.x) {
+        const long long g = g0 + threadIdx.x, last = g0 + blockDim.x < ngroups ? g0 + blockDim.x : ngroups;
+        const int i_lo = image_of_pixel(imgs, 0, n - 1, g0 * 4), i_hi = image_of_pixel(imgs, i_lo, n - 1, last * 4 - 1);
+        if (g >= ngroups) continue;
+        const unsigned in[3] = {src4[g * 3 + 0], src4[g * 3 + 1], src4[g * 3 + 2]};
+        unsigned out[3] = {0u, 0u, 0u};
+        int i = image_of_pixel(imgs, i_lo, i_hi, g * 4);
+        ImgDesc d = imgs[i];
+        long long p = g * 4 - d.first, npix = (long long)d.h * d.w;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            int q[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) q[c] = (int)((in[(k * 3 + c) >> 2] >> (8 * ((k * 3 + c) & 3))) & 255u);
+            unsigned char o[3];
+            const double* pa = lab_q + ((long long)i * 3 + 1) * HW;
+            fullres_pixel(p, q, tab, pa, pa + HW, H, W, interp, (const float*)nullptr, 0.f, d.h, d.w, o);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) out[(k * 3 + c) >> 2] |= (unsigned)o[c] << (8 * ((k * 3 + c) & 3));
+            if (++p == npix && k < 3) { p = 0; d = imgs[++i]; npix = (long long)d.h * d.w; }      // i + 1 <= n - 1: the group's next pixel is in the run
+        }
+        rgb4[g * 3 + 0] = out[0]; rgb4[g * 3 + 1] = out[1]; rgb4[g * 3 + 2] = out[2];
+    }
+    if (blockIdx.x == 0) {
+        const long long t = ngroups * 4 + threadIdx.x;
+        if (t < total) {
+            const int i = image_of_pixel(imgs, 0, n - 1, t);
+            const ImgDesc d = imgs[i];
+            const int q[3] = {src[t * 3 + 0], src[t * 3 + 1], src[t * 3 + 2]};
+            unsigned char o[3];
+            const double* pa = lab_q + ((long long)i * 3 + 1) * HW;
+            fullres_pixel(t - d.first, q, tab, pa, pa + HW, H, W, interp, (const float*)nullptr, 0.f, d.h, d.w, o);
+            rgb[t * 3 + 0] = o[0]; rgb[t * 3 + 1] = o[1]; rgb[t * 3 + 2] = o[2];
+        }
+    }
+}
+
+hipError_t launch_ragged_fullres_rgb(const unsigned char* src, const ImgDesc* imgs, int n, long long total, const double* lab_q, int H, int W,
+                                     int interp, unsigned char* rgb, hipStream_t s) {
+    if (n <= 0 || total < n || imgs == nullptr || interp < 0 || interp > 2 || (((uintptr_t)src | (uintptr_t)rgb) & 3)) return hipErrorInvalidValue;
+    const long long ngroups = (total + 3) >> 2;
+    const int blocks = (int)((ngroups + 255) / 256 < 8192 ? (ngroups + 255) / 256 : 8192);
+    hipLaunchKernelGGL(ragged_fullres_rgb_kernel, dim3(blocks), dim3(256), 0, s, src, imgs, n, lab_q, H, W, interp, rgb);
     return hipGetLastError();
 }
 

@@ -224,7 +224,11 @@ struct idc_context {
         DevMem<unsigned char> d_src, d_meta, d_rgb, d_full;
         DevMem<double> d_labq;
         PinnedMem<unsigned char> h_src, h_meta, h_rgb;                                 // pinned staging: pageable source, the list, pageable rgb_out
-        uint8_t* user_rgb = nullptr; size_t rgb_bytes = 0; bool staged_rgb = false;    // user_rgb == nullptr: the slot's batch was an idc_forward_async
+        // the batch's pageable rgb_out buffers (one for the same-size calls, up to one per image for idc_forward_async_images): each waits in
+        // h_rgb at `at` until idc_wait copies it out; empty after an idc_forward_async.  idc_forward_async_images' image table travels in
+        // d_meta / h_meta between the hint offsets and the hint list
+        struct StagedOut { uint8_t* user; size_t at, bytes; };
+        std::vector<StagedOut> staged_outs;
         // idc_forward_async_rgb_ref: the batch's references and the slot's OWN [max_batch][316] global inputs (the handle's d_glob_in is not touched)
         RefStage ref;
         DevMem<float> d_glob_in;

@@ -357,7 +357,7 @@ static int wait_slot(idc_context* h, int slot) {
     const int arc = check_chain_abort(h);      // the forward this slot carried ran a chain launch that gave up: its result is invalid
     if (arc) return arc;
     if (sl.staged_out && sl.user_out) memcpy(sl.user_out, sl.h_out.get(), (size_t)sl.n * h->H * h->W * 2 * 4);
-    if (sl.staged_rgb && sl.user_rgb) memcpy(sl.user_rgb, sl.h_rgb.get(), sl.rgb_bytes);
+    for (const auto& o : sl.staged_outs) memcpy(o.user, sl.h_rgb.get() + o.at, o.bytes);
     return IDC_OK;
 }
 
@@ -611,7 +611,7 @@ int idc_forward_async(idc_handle h, int slot, int n, const float* L_mc, const fl
     HIPCHK(h, hipMemcpyAsync(sl.staged_out ? sl.h_out.get() : out_ab, sl.d_out.get(), (size_t)n * hw * 2 * 4, hipMemcpyDeviceToHost, h->s_out.get()));
     HIPCHK(h, hipEventRecord(sl.ev_out.get(), h->s_out.get()));
     sl.pending = true; sl.timed = true; sl.user_out = out_ab; sl.n = n;
-    sl.user_rgb = nullptr; sl.staged_rgb = false;
+    sl.staged_outs.clear();
     return IDC_OK;
 }
 
@@ -621,20 +621,70 @@ int idc_forward_async(idc_handle h, int slot, int n, const float* L_mc, const fl
 // the compute stream in front of the prologue; ra == nullptr: the handle's global inputs, as idc_forward_async reads them.
 struct RefArgs { int m; const idc_ref_image* refs; const int32_t* ref_index; const float* centres; float hist_flag; unsigned flags; };
 
-static int forward_async_rgb(idc_handle h, int slot, int n, int src_h, int src_w, const uint8_t* rgb_in, const int32_t* hint_offsets,
+// What the entry points differ in.  The same-size calls: ONE array each way, [n,src_h,src_w,3] in and [n,H,W,3] or [n,src_h,src_w,3] out.
+// idc_forward_async_images (ragged): a descriptor and an output pointer per image; on the device the sources and the source-size
+// results lie packed back to back, the layout the same-size calls have anyway, so everything but the two colour kernels is shared.
+struct BatchIO {
+    bool ragged;
+    int src_h, src_w; const uint8_t* rgb_in; uint8_t* rgb_out;
+    const idc_ref_image* images; uint8_t* const* outs;
+};
+// One host buffer of a call and the bytes of the slot's packed device array it fills (in) or receives (out)
+struct Piece { const uint8_t* in; uint8_t* out; size_t in_at, in_bytes, out_at, out_bytes; bool in_pinned, out_pinned; };
+
+// Pieces <-> a packed device array on `s`: a pinned buffer travels in place, a pageable one through `staging` at the piece's own offset (copied
+// in by the caller before, copied out by idc_wait after), and neighbouring staged pieces go as ONE copy.
+static hipError_t copy_pieces(const std::vector<Piece>& pieces, bool to_device, unsigned char* dev, unsigned char* staging, hipStream_t s) {
+    size_t run0 = 0, run1 = 0;                      // staged bytes [run0, run1) not yet enqueued
+    auto flush = [&]() -> hipError_t {
+        if (run1 == run0) return hipSuccess;
+        const hipError_t e = to_device ? hipMemcpyAsync(dev + run0, staging + run0, run1 - run0, hipMemcpyHostToDevice, s)
+                                       : hipMemcpyAsync(staging + run0, dev + run0, run1 - run0, hipMemcpyDeviceToHost, s);
+        run0 = run1;
+        return e;
+    };
+    for (const Piece& p : pieces) {
+        const size_t at = to_device ? p.in_at : p.out_at, bytes = to_device ? p.in_bytes : p.out_bytes;
+        const bool pinned = to_device ? p.in_pinned : p.out_pinned;
+        if (!pinned && at == run1) { run1 = at + bytes; continue; }
+        hipError_t e = flush();
+        if (e != hipSuccess) return e;
+        if (!pinned) { run0 = at; run1 = at + bytes; continue; }
+        e = to_device ? hipMemcpyAsync(dev + at, p.in, bytes, hipMemcpyHostToDevice, s) : hipMemcpyAsync(p.out, dev + at, bytes, hipMemcpyDeviceToHost, s);
+        if (e != hipSuccess) return e;
+        run0 = run1 = at + bytes;
+    }
+    return flush();
+}
+
+static int forward_async_rgb(idc_handle h, int slot, int n, const BatchIO& io, const int32_t* hint_offsets,
                              const idc_hint* hints, int mode, float mask_value, float maskcent, float l_cent, unsigned flags,
-                             const RefArgs* ra, uint8_t* rgb_out, float* out_ab) {
+                             const RefArgs* ra, float* out_ab) {
     int rc = check_forward_args(h, n);
     if (rc) return rc;
+    const bool ragged = io.ragged;
     if (slot < 0 || slot > 1) return fail(&h->err, IDC_ERR_INVALID_ARG, "slot %d not in 0..1", slot);
-    if (!rgb_in || !rgb_out) return fail(&h->err, IDC_ERR_INVALID_ARG, "null image pointer");
+    if (ragged ? (!io.images || !io.outs) : (!io.rgb_in || !io.rgb_out)) return fail(&h->err, IDC_ERR_INVALID_ARG, "null image pointer");
     if (flags & ~(unsigned)IDC_BATCH_OUT_SOURCE) return fail(&h->err, IDC_ERR_INVALID_ARG, "unknown flag bits 0x%x", flags);
     if (mode != IDC_HINT_AB && mode != IDC_HINT_RGB) return fail(&h->err, IDC_ERR_INVALID_ARG, "hint mode %d", mode);
-    if (src_h < 1 || src_h > 16384 || src_w < 1 || src_w > 16384)
-        return fail(&h->err, IDC_ERR_INVALID_ARG, "source size %dx%d outside 1..16384", src_h, src_w);
-    const size_t sb = (size_t)src_h * src_w * 3, in_bytes = (size_t)n * sb;
-    if (in_bytes > IDC_BATCH_MAX_SOURCE_BYTES)
-        return fail(&h->err, IDC_ERR_INVALID_ARG, "%d sources of %dx%d are more than %zu bytes", n, src_h, src_w, (size_t)IDC_BATCH_MAX_SOURCE_BYTES);
+    size_t in_bytes = 0;
+    if (ragged) {
+        for (int i = 0; i < n; ++i) {
+            const idc_ref_image& im = io.images[i];
+            if (!im.rgb || !io.outs[i]) return fail(&h->err, IDC_ERR_INVALID_ARG, "image %d: null image pointer", i);
+            if (im.h < 1 || im.h > 16384 || im.w < 1 || im.w > 16384)
+                return fail(&h->err, IDC_ERR_INVALID_ARG, "image %d: source size %dx%d outside 1..16384", i, im.h, im.w);
+            in_bytes += (size_t)im.h * im.w * 3;                  // n * 0.8 GB: no overflow in 64 bits
+        }
+        if (in_bytes > IDC_BATCH_MAX_SOURCE_BYTES)
+            return fail(&h->err, IDC_ERR_INVALID_ARG, "%d sources hold %zu bytes, more than %zu", n, in_bytes, (size_t)IDC_BATCH_MAX_SOURCE_BYTES);
+    } else {
+        if (io.src_h < 1 || io.src_h > 16384 || io.src_w < 1 || io.src_w > 16384)
+            return fail(&h->err, IDC_ERR_INVALID_ARG, "source size %dx%d outside 1..16384", io.src_h, io.src_w);
+        in_bytes = (size_t)n * io.src_h * io.src_w * 3;
+        if (in_bytes > IDC_BATCH_MAX_SOURCE_BYTES)
+            return fail(&h->err, IDC_ERR_INVALID_ARG, "%d sources of %dx%d are more than %zu bytes", n, io.src_h, io.src_w, (size_t)IDC_BATCH_MAX_SOURCE_BYTES);
+    }
     int n_hints = 0;
     if (hint_offsets) {
         if (hint_offsets[0] != 0) return fail(&h->err, IDC_ERR_INVALID_ARG, "hint_offsets[0] is %d, not 0", hint_offsets[0]);
@@ -679,8 +729,10 @@ static int forward_async_rgb(idc_handle h, int slot, int n, int src_h, int src_w
     const size_t hw = (size_t)h->H * h->W, nb = (size_t)h->max_batch;
     const bool source_out = (flags & IDC_BATCH_OUT_SOURCE) != 0;
     const size_t rgb_bytes = source_out ? in_bytes : (size_t)n * hw * 3;
-    const size_t hints_at = align_up((nb + 1) * sizeof(int), 16), meta_bytes = hints_at + (size_t)kept * sizeof(HintRect);
-    const size_t meta_floor = hints_at + 256 * sizeof(HintRect);
+    // the metadata block: the hint offsets int[max_batch + 1], (images of individual sizes) the table ImgDesc[max_batch + 1], the kept hints
+    const size_t table_at = align_up((nb + 1) * sizeof(int), 16);
+    const size_t hints_at = ragged ? table_at + align_up((nb + 1) * sizeof(ImgDesc), 16) : table_at;
+    const size_t meta_bytes = hints_at + (size_t)kept * sizeof(HintRect), meta_floor = hints_at + 256 * sizeof(HintRect);
     HIPCHK(h, sl.d_src.ensure(in_bytes));
     HIPCHK(h, sl.d_meta.ensure(meta_bytes, meta_floor));
     HIPCHK(h, sl.h_meta.ensure(meta_bytes, meta_floor));
@@ -689,14 +741,31 @@ static int forward_async_rgb(idc_handle h, int slot, int n, int src_h, int src_w
         HIPCHK(h, sl.d_labq.ensure(nb * hw * 3 * 8));
         HIPCHK(h, sl.d_full.ensure(in_bytes));
     }
-    const uint8_t* s_rgb = rgb_in;
-    if (!is_pinned(rgb_in)) {
-        HIPCHK(h, sl.h_src.ensure(in_bytes));
-        memcpy(sl.h_src.get(), rgb_in, in_bytes);
-        s_rgb = sl.h_src.get();
+    // every host buffer is judged on its own: pageable sources are copied into the slot's pinned staging here, on the calling thread
+    std::vector<Piece> pieces;
+    if (ragged) {
+        ImgDesc* tab = (ImgDesc*)(sl.h_meta.get() + table_at);
+        size_t at = 0;
+        for (int i = 0; i < n; ++i) {
+            const size_t sb = (size_t)io.images[i].h * io.images[i].w * 3;
+            tab[i].off = (long long)at; tab[i].first = (long long)(at / 3); tab[i].h = io.images[i].h; tab[i].w = io.images[i].w;
+            pieces.push_back({io.images[i].rgb, io.outs[i], at, sb, source_out ? at : (size_t)i * hw * 3, source_out ? sb : hw * 3,
+                              is_pinned(io.images[i].rgb), is_pinned(io.outs[i])});
+            at += sb;
+        }
+        tab[n].off = (long long)at; tab[n].first = (long long)(at / 3); tab[n].h = 0; tab[n].w = 0;
+    } else {
+        pieces.push_back({io.rgb_in, io.rgb_out, 0, in_bytes, 0, rgb_bytes, is_pinned(io.rgb_in), is_pinned(io.rgb_out)});
     }
-    const bool staged_rgb = !is_pinned(rgb_out), staged_ab = out_ab && !is_pinned(out_ab);
-    if (staged_rgb) HIPCHK(h, sl.h_rgb.ensure(rgb_bytes));
+    bool any_staged_in = false, any_staged_rgb = false;
+    for (const Piece& p : pieces) { any_staged_in |= !p.in_pinned; any_staged_rgb |= !p.out_pinned; }
+    if (any_staged_in) {
+        HIPCHK(h, sl.h_src.ensure(in_bytes));
+        for (const Piece& p : pieces)
+            if (!p.in_pinned) memcpy(sl.h_src.get() + p.in_at, p.in, p.in_bytes);
+    }
+    const bool staged_ab = out_ab && !is_pinned(out_ab);
+    if (any_staged_rgb) HIPCHK(h, sl.h_rgb.ensure(rgb_bytes));
     if (staged_ab) HIPCHK(h, sl.h_out.ensure(nb * hw * 2 * 4));
     // the list as the kernel reads it: offsets of the KEPT hints per image, then the clipped rectangles
     int* m_offs = (int*)sl.h_meta.get();
@@ -715,7 +784,7 @@ static int forward_async_rgb(idc_handle h, int slot, int n, int src_h, int src_w
         if (rc) return rc;
     }
     HIPCHK(h, hipEventRecord(sl.ev_in0.get(), h->s_in.get()));
-    HIPCHK(h, hipMemcpyAsync(sl.d_src.get(), s_rgb, in_bytes, hipMemcpyHostToDevice, h->s_in.get()));
+    HIPCHK(h, copy_pieces(pieces, true, sl.d_src.get(), sl.h_src.get(), h->s_in.get()));
     HIPCHK(h, hipMemcpyAsync(sl.d_meta.get(), sl.h_meta.get(), meta_bytes, hipMemcpyHostToDevice, h->s_in.get()));
     if (ra) {
         rc = upload_refs(h, sl.ref, lay, h->s_in.get());
@@ -728,32 +797,44 @@ static int forward_async_rgb(idc_handle h, int slot, int n, int src_h, int src_w
         rc = launch_refs(h, sl.ref, lay, ra->hist_flag, ra->flags, sl.d_glob_in.get(), false, h->stream.get());
         if (rc) return rc;
     }
-    HIPCHK(h, launch_batch_prologue(sl.d_src.get(), n, src_h, src_w, h->H, h->W, l_cent, kept ? (const int*)sl.d_meta.get() : nullptr,
-                                    (const HintRect*)(sl.d_meta.get() + hints_at), mode, mask_value, sl.d_L.get(), sl.d_ab.get(), sl.d_mask.get(),
-                                    h->stream.get()));
+    const int* d_offs = kept ? (const int*)sl.d_meta.get() : nullptr;
+    const HintRect* d_hints = (const HintRect*)(sl.d_meta.get() + hints_at);
+    const ImgDesc* d_tab = (const ImgDesc*)(sl.d_meta.get() + table_at);
+    if (ragged)
+        HIPCHK(h, launch_ragged_prologue(sl.d_src.get(), d_tab, n, h->H, h->W, l_cent, d_offs, d_hints, mode, mask_value, sl.d_L.get(), sl.d_ab.get(),
+                                         sl.d_mask.get(), h->stream.get()));
+    else
+        HIPCHK(h, launch_batch_prologue(sl.d_src.get(), n, io.src_h, io.src_w, h->H, h->W, l_cent, d_offs, d_hints, mode, mask_value, sl.d_L.get(),
+                                        sl.d_ab.get(), sl.d_mask.get(), h->stream.get()));
     const int dist_n = h->dist_n;
     rc = run_graph(h, n, sl.d_L.get(), sl.d_ab.get(), sl.d_mask.get(), maskcent, sl.d_out.get(), nullptr, ra ? sl.d_glob_in.get() : h->d_glob_in.get());
     if (rc) return rc;
     if (!((h->flags & IDC_FLAG_DIST313) && h->keep_dist313)) h->dist_n = dist_n;      // no distribution was written: the blocking forward's stays resident
     HIPCHK(h, launch_lab_post(sl.d_L.get(), l_cent, sl.d_out.get(), sl.d_rgb.get(), source_out ? sl.d_labq.get() : nullptr, n, h->H, h->W, h->stream.get()));
-    if (source_out)
-        HIPCHK(h, launch_batch_fullres_rgb(sl.d_src.get(), n, src_h, src_w, sl.d_labq.get(), h->H, h->W, IDC_INTERP_LINEAR, sl.d_full.get(), h->stream.get()));
+    if (source_out && ragged)
+        HIPCHK(h, launch_ragged_fullres_rgb(sl.d_src.get(), d_tab, n, (long long)(in_bytes / 3), sl.d_labq.get(), h->H, h->W, IDC_INTERP_LINEAR,
+                                            sl.d_full.get(), h->stream.get()));
+    else if (source_out)
+        HIPCHK(h, launch_batch_fullres_rgb(sl.d_src.get(), n, io.src_h, io.src_w, sl.d_labq.get(), h->H, h->W, IDC_INTERP_LINEAR, sl.d_full.get(), h->stream.get()));
     HIPCHK(h, hipEventRecord(sl.ev_comp.get(), h->stream.get()));
     HIPCHK(h, hipStreamWaitEvent(h->s_out.get(), sl.ev_comp.get(), 0));
     HIPCHK(h, hipEventRecord(sl.ev_out0.get(), h->s_out.get()));
-    HIPCHK(h, hipMemcpyAsync(staged_rgb ? sl.h_rgb.get() : rgb_out, source_out ? sl.d_full.get() : sl.d_rgb.get(), rgb_bytes, hipMemcpyDeviceToHost, h->s_out.get()));
+    HIPCHK(h, copy_pieces(pieces, false, source_out ? sl.d_full.get() : sl.d_rgb.get(), sl.h_rgb.get(), h->s_out.get()));
     if (out_ab) HIPCHK(h, hipMemcpyAsync(staged_ab ? sl.h_out.get() : out_ab, sl.d_out.get(), (size_t)n * hw * 2 * 4, hipMemcpyDeviceToHost, h->s_out.get()));
     HIPCHK(h, hipEventRecord(sl.ev_out.get(), h->s_out.get()));
     sl.pending = true; sl.timed = true; sl.n = n;
     sl.user_out = out_ab; sl.staged_out = staged_ab;
-    sl.user_rgb = rgb_out; sl.staged_rgb = staged_rgb; sl.rgb_bytes = rgb_bytes;
+    sl.staged_outs.clear();
+    for (const Piece& p : pieces)
+        if (!p.out_pinned) sl.staged_outs.push_back({p.out, p.out_at, p.out_bytes});
     return IDC_OK;
 }
 
 int idc_forward_async_rgb(idc_handle h, int slot, int n, int src_h, int src_w, const uint8_t* rgb_in, const int32_t* hint_offsets,
                           const idc_hint* hints, int mode, float mask_value, float maskcent, float l_cent, unsigned flags,
                           uint8_t* rgb_out, float* out_ab) {
-    return forward_async_rgb(h, slot, n, src_h, src_w, rgb_in, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, nullptr, rgb_out, out_ab);
+    const BatchIO io = {false, src_h, src_w, rgb_in, rgb_out, nullptr, nullptr};
+    return forward_async_rgb(h, slot, n, io, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, nullptr, out_ab);
 }
 
 int idc_forward_async_rgb_ref(idc_handle h, int slot, int n, int src_h, int src_w, const uint8_t* rgb_in, const int32_t* hint_offsets,
@@ -761,7 +842,17 @@ int idc_forward_async_rgb_ref(idc_handle h, int slot, int n, int src_h, int src_
                               const idc_ref_image* refs, const int32_t* ref_index, const float* centres, float hist_flag, unsigned ref_flags,
                               uint8_t* rgb_out, float* out_ab) {
     const RefArgs ra = {m, refs, ref_index, centres, hist_flag, ref_flags};
-    return forward_async_rgb(h, slot, n, src_h, src_w, rgb_in, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, &ra, rgb_out, out_ab);
+    const BatchIO io = {false, src_h, src_w, rgb_in, rgb_out, nullptr, nullptr};
+    return forward_async_rgb(h, slot, n, io, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, &ra, out_ab);
+}
+
+int idc_forward_async_images(idc_handle h, int slot, int n, const idc_ref_image* images, const int32_t* hint_offsets, const idc_hint* hints,
+                             int mode, float mask_value, float maskcent, float l_cent, unsigned flags, const idc_batch_refs* refs,
+                             uint8_t* const* rgb_out, float* out_ab) {
+    const BatchIO io = {true, 0, 0, nullptr, nullptr, images, rgb_out};
+    if (!refs) return forward_async_rgb(h, slot, n, io, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, nullptr, out_ab);
+    const RefArgs ra = {refs->m, refs->refs, refs->ref_index, refs->centres, refs->hist_flag, refs->flags};
+    return forward_async_rgb(h, slot, n, io, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, &ra, out_ab);
 }
 
 int idc_wait(idc_handle h, int slot) {

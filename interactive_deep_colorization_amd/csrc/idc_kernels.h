@@ -302,6 +302,17 @@ hipError_t launch_batch_prologue(const unsigned char* src, int n, int src_h, int
 hipError_t launch_batch_fullres_rgb(const unsigned char* src, int n, int oh, int ow, const double* lab_q, int H, int W, int interp,
                                     unsigned char* rgb, hipStream_t s);
 
+// Pipelined batches of images of INDIVIDUAL sizes (idc_forward_async_images; idc_colour.hip): the two launches above, still ONE each for all n
+// images, over a table in device memory.  imgs [n+1]: entry i = {byte offset of image i in src, pixels of images 0..i-1, h, w}; the [h,w,3] u8
+// images lie back to back (off = 3 * first; no alignment asked of an image's start), and entry n = {all bytes, all pixels, 0, 0} closes the
+// run.  ragged_prologue: batch_prologue with image i's own size and start.  ragged_fullres_rgb: batch_fullres_rgb for the `total` =
+// imgs[n].first pixels of the run -> rgb, packed as src is; src and rgb 4-byte aligned at their base only.
+struct ImgDesc { long long off, first; int h, w; };
+hipError_t launch_ragged_prologue(const unsigned char* src, const ImgDesc* imgs, int n, int H, int W, float l_cent, const int* offs,
+                                  const HintRect* hints, int mode, float mask_value, float* Lp, float* ab, float* mask, hipStream_t s);
+hipError_t launch_ragged_fullres_rgb(const unsigned char* src, const ImgDesc* imgs, int n, long long total, const double* lab_q, int H, int W,
+                                     int interp, unsigned char* rgb, hipStream_t s);
+
 // Colour suggestions at one pixel (get_ab_reccs, colorize_image.py:322-354): see idc_session.hip for the algorithm.
 // pdf bin b at pdf[b*stride]; centres [B][2]; out_centres [K][2], out_conf [K] (f64); out_counts [B] or nullptr.
 constexpr int kSuggestMaxBins = 1024, kSuggestMaxK = 16;

@@ -968,6 +968,125 @@ class HipColorizer(object):
                     pending[slot] = None
                     self.wait(slot)
 
+    def _pinned_slices(self, shapes):
+        """One pinned pool block (a multiple of 64 KiB, so that blocks of ragged batches recycle) sliced into uint8 arrays of ``shapes``."""
+        sizes = [int(np.prod(s)) for s in shapes]
+        block = self._pool.take((-(-max(sum(sizes), 1) // 65536) * 65536,), np.uint8)
+        ends = np.cumsum(sizes)
+        return [block[e - z:e].reshape(s) for e, z, s in zip(ends, sizes, shapes)]
+
+    def forward_async_images(self, slot, images, hints, out_rgb=None, out_ab=None, mode="ab", mask_value=1.0, maskcent=0.0, l_cent=50.0,
+                             out="net", refs=None, ref_index=None, centres=None, hist_flag=1.0, saturation=False):
+        """``forward_async_rgb`` for images of individual sizes (``idc_forward_async_images``): ``images`` is a list of n C-contiguous (h,w,3)
+        uint8 arrays, each of its own size; ``out_rgb`` a list of n uint8 arrays, (H,W,3) each with out='net', images[i].shape with
+        out='source', or ``None``: they are taken from the pinned pool.  Returns the list of outputs, valid after ``wait(slot)``.  Image i's
+        result is bit for bit what ``forward_async_rgb`` gives for it alone.  Every other argument as in ``forward_async_rgb``; pinned and
+        pageable arrays may be mixed within a call, and the engine holds a reference to each until ``wait(slot)``."""
+        images = list(images)
+        n = len(images)
+        for a in images:
+            if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or not a.flags.c_contiguous or a.size == 0:
+                raise ValueError("forward_async_images needs uint8 C-contiguous (h,w,3) arrays")
+        flags = {"net": 0, "source": N.IDC_BATCH_OUT_SOURCE}[out]
+        shapes = [tuple(a.shape) if flags else (self.H, self.W, 3) for a in images]
+        if out_rgb is None:
+            out_rgb = self._pinned_slices(shapes)
+        out_rgb = list(out_rgb)
+        if len(out_rgb) != n:
+            raise ValueError("forward_async_images needs %d outputs, got %d" % (n, len(out_rgb)))
+        for o, shp in zip(out_rgb, shapes):
+            if not isinstance(o, np.ndarray) or o.dtype != np.uint8 or not o.flags.c_contiguous or tuple(o.shape) != shp:
+                raise ValueError("forward_async_images needs a uint8 C-contiguous out_rgb of shape %s" % (shp,))
+        if out_ab is not None and (out_ab.dtype != np.float32 or not out_ab.flags.c_contiguous or tuple(out_ab.shape) != (n, 2, self.H, self.W)):
+            raise ValueError("forward_async_images needs a float32 C-contiguous out_ab of shape %s" % ((n, 2, self.H, self.W),))
+        offsets, arr = flatten_hints(hints, n)
+        vp = ctypes.c_void_p
+        table = (N.RefImage * max(n, 1))()
+        outs = (vp * max(n, 1))()
+        for i, (a, o) in enumerate(zip(images, out_rgb)):
+            table[i].rgb, table[i].h, table[i].w = a.ctypes.data, a.shape[0], a.shape[1]
+            outs[i] = o.ctypes.data
+        block = None
+        if refs is not None:
+            if isinstance(refs, np.ndarray) and refs.ndim == 3:
+                refs = [refs]
+            rarr, keep = ref_images(refs)                          # (rarr, keep, idx and c live until the call has returned: it copies them)
+            idx = _ref_index(ref_index, n)
+            c = _f32c(centres, (313, 2)) if centres is not None else None
+            block = N.BatchRefs(len(keep), rarr if keep else None, idx.ctypes.data if idx is not None else None,
+                                c.ctypes.data if c is not None else None, float(hist_flag), N.IDC_REF_SATURATION if saturation else 0)
+        self._chk(self.lib.idc_forward_async_images(
+            self._h, int(slot), int(n), table, offsets.ctypes.data_as(vp) if offsets is not None else None,
+            ctypes.cast(arr, vp) if arr is not None else None, {"ab": N.IDC_HINT_AB, "rgb": N.IDC_HINT_RGB}[mode], float(mask_value),
+            float(maskcent), float(l_cent), flags, ctypes.byref(block) if block is not None else None, outs,
+            out_ab.ctypes.data_as(vp) if out_ab is not None else None))
+        self._in_flight[int(slot)] = (images, out_rgb, out_ab)    # the library reads / writes them until the slot's wait
+        return out_rgb
+
+    def colorize_images(self, items, batch=None, out="source", **kw):
+        """Generator: colourise a stream of single images of any sizes with both pipeline slots busy.  An item is ``rgb``, ``(rgb, hints)`` or
+        ``(rgb, hints, ref)``: rgb (h,w,3) uint8, ``hints`` that image's hint list (rows as in ``set_hints``) or ``None``, ``ref`` ``None`` or an
+        (h,w,3) uint8 reference photograph (a ``global_hints`` engine; ``kw`` then carries centres).  Consecutive items are grouped into
+        batches of ``batch`` images (default ``max_batch``; the last may be shorter), batch k runs on slot k % 2 while batch k - 1 computes
+        (``forward_async_images``), and one array per image is yielded in input order: (h,w,3) [out='source'] or (H,W,3) [out='net'], the
+        caller's own copy.  Sources travel through one pinned pool block per batch; the same reference OBJECT given for several images of a
+        batch is uploaded once (``dedupe_refs``).  ``kw``: mode, mask_value, maskcent, l_cent, centres, hist_flag, saturation."""
+        batch = self.max_batch if batch is None else int(batch)
+        if not 1 <= batch <= self.max_batch:
+            raise ValueError("batch %d outside 1..%d" % (batch, self.max_batch))
+        pending = [None, None]                      # per slot: (pinned results, pinned sources) of the batch in flight
+
+        def finish(slot):
+            self.wait(slot)
+            res, pending[slot] = pending[slot][0], None
+            return [np.array(r) for r in res]
+
+        def submit(slot, group):
+            srcs = self._pinned_slices([g[0].shape for g in group])
+            for s, g in zip(srcs, group):
+                np.copyto(s, g[0])
+            hints = [g[1] for g in group]
+            if any(g[3] for g in group):
+                uniq, index = dedupe_refs([g[2] for g in group], len(group))
+                res = self.forward_async_images(slot, srcs, hints, out=out, refs=uniq, ref_index=index, **kw)
+            else:
+                res = self.forward_async_images(slot, srcs, hints, out=out, **kw)
+            pending[slot] = (res, srcs)
+
+        def parse(item):
+            item = (item,) if isinstance(item, np.ndarray) else tuple(item)
+            rgb = np.asarray(item[0])
+            if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.size == 0:
+                raise ValueError("colorize_images needs uint8 (h,w,3) images, got %s %s" % (rgb.dtype, rgb.shape))
+            return rgb, item[1] if len(item) > 1 else None, item[2] if len(item) > 2 else None, len(item) > 2
+
+        k, group = 0, []
+        try:
+            for item in items:
+                group.append(parse(item))
+                if len(group) < batch:
+                    continue
+                if pending[k & 1] is not None:
+                    for r in finish(k & 1):
+                        yield r
+                submit(k & 1, group)
+                k, group = k + 1, []
+            if group:
+                if pending[k & 1] is not None:
+                    for r in finish(k & 1):
+                        yield r
+                submit(k & 1, group)
+                k += 1
+            for slot in (k & 1, (k + 1) & 1):       # the older batch first
+                if pending[slot] is not None:
+                    for r in finish(slot):
+                        yield r
+        finally:                                    # a consumer that stops early: nothing stays in flight on buffers about to be recycled
+            for slot in (0, 1):
+                if pending[slot] is not None:
+                    pending[slot] = None
+                    self.wait(slot)
+
     def wait(self, slot):
         self._chk(self.lib.idc_wait(self._h, int(slot)))
         self._in_flight.pop(int(slot), None)
