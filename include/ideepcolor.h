@@ -524,6 +524,41 @@ int idc_forward_async_images(idc_handle h, int slot, int n, const idc_ref_image*
                              const idc_hint* hints, int mode, float mask_value, float maskcent, float l_cent, unsigned flags,
                              const idc_batch_refs* refs, uint8_t* const* rgb_out, float* out_ab);
 
+/* ---- evaluation batches: the paper's simulated user and its metric on the device.  The metric is PSNR of the colourised image against the
+ *      ground-truth colour image as a function of the number of hints (ColorizeImageBase.get_result_PSNR, data/colorize_image.py:98-108);
+ *      the simulated user reveals, per hint, the mean ground-truth ab of the image under the hint's own rectangle (what the notebook's
+ *      put_point is fed by hand).  Two device steps around the unchanged forward:
+ *        reveal: mode IDC_HINT_REVEAL -- c0..c2 of every rectangle are ignored; its colour is the float64 mean of the image's net-size
+ *                (a, b) (idc_set_image_rgb's lab_net) over the clipped rectangle, summed in a fixed order, divided by the pixel count and
+ *                rounded once to fp32.  It is a function of the image's bytes, (H, W) and the four clipped corners only.  The list then
+ *                goes through the IDC_HINT_AB path unchanged (the later hint wins, clipping, mask_value).  Cost: the rectangle's area per
+ *                hint, one workgroup per rectangle;
+ *        score:  sse [n,3] = the exact sum over the pixels of image i of (result - truth)^2 per channel (R, G, B) in unsigned 64-bit
+ *                integers: the net-size result against the net-size ground truth (idc_set_image_rgb's rgb_net; flags 0), or the
+ *                source-size result against the source bytes themselves (IDC_BATCH_OUT_SOURCE).
+ *                PSNR = 20 log10(255 / sqrt(sum_c sse / (3 h w))).
+ *      idc_reveal_hints (blocking) = idc_set_hints(h, img, n_hints, rects, IDC_HINT_AB, mask_value) with every colour revealed from the
+ *      source idc_set_image_rgb kept in slot img (IDC_INGEST_KEEP_SOURCE).  It writes the slot's hint planes and its mask_value and
+ *      nothing else of the handle.  colours [n_hints,2] (or NULL) receives the revealed (a, b) of input rectangle k; a rectangle wholly
+ *      outside the image receives (0, 0) and paints nothing.  Status: the codes of idc_set_hints; IDC_ERR_UNSUPPORTED when the slot has
+ *      no resident source.
+ *      idc_forward_async_eval = idc_forward_async_images with mode IDC_HINT_AB / IDC_HINT_RGB (score a given list) or IDC_HINT_REVEAL,
+ *      on the same two slots, with idc_wait and idc_pipeline_times: H2D, [reveal], prologue, network, lab_post, [full-resolution
+ *      epilogue], score on the compute stream, then sse [n,3] (required), hint_colours [hint_offsets[n],2] (or NULL; IDC_HINT_REVEAL
+ *      only; (0, 0) for a dropped rectangle), out_ab [n,2,H,W] (or NULL) and the images (rgb_out == NULL: no image leaves the device)
+ *      on the copy-out stream.  Pinned buffers are written in place, pageable ones at idc_wait.  The images and out_ab are bit-identical
+ *      to idc_forward_async_images in IDC_HINT_AB mode on the revealed colours.  Slot ownership, resident state, the 313 head and the
+ *      range audit: as said for idc_forward_async_images.
+ *      Status, all decided before anything is enqueued: the codes of idc_forward_async_images (a NULL rgb_out is allowed here, a NULL
+ *      rgb_out[i] in a non-NULL rgb_out is not); IDC_ERR_INVALID_ARG for a NULL sse, a mode outside 0..2, a non-NULL hint_colours with a
+ *      mode other than IDC_HINT_REVEAL; the RGB range check applies in IDC_HINT_RGB mode only.
+ *      Every other call that takes a hint mode refuses IDC_HINT_REVEAL. */
+enum { IDC_HINT_REVEAL = 2 };
+int idc_reveal_hints(idc_handle h, int img, int n_hints, const idc_hint* rects, float mask_value, float* colours);
+int idc_forward_async_eval(idc_handle h, int slot, int n, const idc_ref_image* images, const int32_t* hint_offsets,
+                           const idc_hint* hints, int mode, float mask_value, float maskcent, float l_cent, unsigned flags,
+                           const idc_batch_refs* refs, uint8_t* const* rgb_out, float* out_ab, uint64_t* sse, float* hint_colours);
+
 /* ---- colour picker on the device: replaces data/lab_gamut.py, the host colour maths the GUI runs on every mouse press
  *      (ui/gui_draw.py:11,182-183,195-204; ui/gui_gamut.py:4), in float64 with the constants and operation order of idc_lab2rgb.
  *      idc_gamut_map = abGrid(gamut_size, D).update_gamut(L[k]) (lab_gamut.py:56-78) for k = 0..n-1 in one launch.  The grid has

@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = [
     "idc_forward_async_rgb",
     "idc_global_stats_rgb", "idc_set_global_refs", "idc_forward_async_rgb_ref",
     "idc_forward_async_images",
+    "idc_reveal_hints", "idc_forward_async_eval",
     "idc_gamut_map", "idc_snap_colors",
     "idc_set_range_audit", "idc_range_reset", "idc_range_report", "idc_pack_weights_ex", "idc_load_weights_ex",
 ]
@@ -47,6 +48,7 @@ IDC_REF_SATURATION, IDC_REF_MAX = 1, 4096
 IDC_GAMUT_MAX_MAPS, IDC_GAMUT_MAX_SIZE, IDC_SNAP_MAX_COLORS = 64, 512, 65536
 IDC_UNIQUE_ID_BYTES = 128
 IDC_HINT_AB, IDC_HINT_RGB = 0, 1
+IDC_HINT_REVEAL = 2         # idc_reveal_hints / idc_forward_async_eval only
 IDC_DECODE_MODE, IDC_DECODE_MEAN = 0, 1
 
 
@@ -185,6 +187,9 @@ def load():
                                             ci, ctypes.POINTER(RefImage), vp, c_float_p, cf, ctypes.c_uint, vp, vp])
     proto("idc_forward_async_images", ci, [vp, ci, ci, ctypes.POINTER(RefImage), vp, vp, ci, cf, cf, cf, ctypes.c_uint,
                                            ctypes.POINTER(BatchRefs), ctypes.POINTER(vp), vp])
+    proto("idc_reveal_hints", ci, [vp, ci, ci, ctypes.POINTER(Hint), cf, c_float_p])
+    proto("idc_forward_async_eval", ci, [vp, ci, ci, ctypes.POINTER(RefImage), vp, vp, ci, cf, cf, cf, ctypes.c_uint,
+                                         ctypes.POINTER(BatchRefs), ctypes.POINTER(vp), vp, vp, vp])
     proto("idc_gamut_map", ci, [vp, ci, vp, ci, ci, vp, vp, vp])
     proto("idc_snap_colors", ci, [vp, ci, vp, vp, vp, vp, vp])
     proto("idc_set_range_audit", ci, [vp, ci])

@@ -443,6 +443,26 @@ class ColorizeImageBase(object):
         self._l_serial = getattr(self.net, 'l_serial', None)
         return self._finish_forward(raw[0], rgb[0], lab_q[0])
 
+    def net_forward_reveal(self, rects):
+        """``net_forward_hints`` in mode 'ab' whose colours the engine reveals from the image itself (not in the reference: the paper's
+        simulated user, what the notebook feeds ``put_point`` by hand).  rects: rows ``(y0, x0, y1, x1)``, corners inclusive; each
+        rectangle is painted with the mean ground-truth ab under it.  Needs the source on the device (``load_image_device`` /
+        ``set_image_device``); the revealed colours are left in ``self.revealed_hint_colors`` (n,2) float32.  Returns what
+        ``net_forward`` returns."""
+        if not self.net_set or not hasattr(self.net, 'reveal_hints'):
+            raise RuntimeError('load_image_device / set_image_device need prep_net first, and an engine with set_image_rgb')
+        if not self.img_l_set:
+            raise RuntimeError('I need to have an image!')
+        if not self._source_on_device():
+            raise RuntimeError('load_image_device / set_image_device need prep_net first, and an engine with set_image_rgb')
+        if self.ab_mean != 0 or self.ab_norm != 1:
+            raise ValueError('device-side hints assume raw ab inputs (ab_mean 0, ab_norm 1)')
+        self.revealed_hint_colors = self.net.reveal_hints(rects, img=0, mask_value=self.mask_mult)
+        self._hints_on_device = True
+        raw, rgb, lab_q = self.net.forward_resident(1, getattr(self, 'mask_cent', 0), l_cent=self.l_mean)
+        self._l_serial = getattr(self.net, 'l_serial', None)
+        return self._finish_forward(raw[0], rgb[0], lab_q[0])
+
     def _ensure_l_resident(self):
         """The image's L plane sits in the engine's slot 0: uploaded once per image (it is constant between the clicks,
         ``colorize_image.py:161-191`` sets it in set_image), and again whenever something else has since used the engine behind this

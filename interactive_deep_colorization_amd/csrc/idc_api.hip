@@ -261,6 +261,57 @@ int idc_set_hints(idc_handle h, int img, int n_hints, const idc_hint* hints, int
     return IDC_OK;
 }
 
+// idc_set_hints in IDC_HINT_AB mode with every colour taken from the slot's kept source: the list goes to the device clipped, reveal_hints_kernel
+// writes (c0, c1) where it lies, and raster_hints_kernel reads it from there
+int idc_reveal_hints(idc_handle h, int img, int n_hints, const idc_hint* rects, float mask_value, float* colours) {
+    int rc = check_img(h, img);
+    if (rc) return rc;
+    if (n_hints < 0 || (n_hints > 0 && !rects)) return fail(&h->err, IDC_ERR_INVALID_ARG, "bad hint list");
+    const auto& src = h->src[img];
+    if (!src.d_rgb.get()) return fail(&h->err, IDC_ERR_UNSUPPORTED, "image slot %d has no resident source (idc_set_image_rgb with IDC_INGEST_KEEP_SOURCE)", img);
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));            // the pinned lists of the previous call may still be in flight
+    const size_t cap = n_hints < 256 ? 256 : 2 * (size_t)n_hints;
+    HIPCHK(h, h->d_hints.ensure((size_t)n_hints * sizeof(HintRect), cap * sizeof(HintRect)));
+    HIPCHK(h, h->h_hints.ensure((size_t)n_hints * sizeof(HintRect), cap * sizeof(HintRect)));
+    const size_t cols_at = (size_t)n_hints * sizeof(int), cols_bytes = (size_t)n_hints * 2 * sizeof(float);
+    HIPCHK(h, h->d_reveal.ensure(cols_at + cols_bytes, cap * 12));
+    HIPCHK(h, h->h_reveal.ensure(cols_at + cols_bytes, cap * 12));
+    int* orig = (int*)h->h_reveal.get();
+    int kept = 0;
+    for (int i = 0; i < n_hints; ++i) {                    // cv2.rectangle, as idc_set_hints reads it
+        HintRect r;
+        r.y0 = rects[i].y0 < rects[i].y1 ? rects[i].y0 : rects[i].y1; r.y1 = rects[i].y0 < rects[i].y1 ? rects[i].y1 : rects[i].y0;
+        r.x0 = rects[i].x0 < rects[i].x1 ? rects[i].x0 : rects[i].x1; r.x1 = rects[i].x0 < rects[i].x1 ? rects[i].x1 : rects[i].x0;
+        if (r.y0 < 0) r.y0 = 0;
+        if (r.x0 < 0) r.x0 = 0;
+        if (r.y1 > h->H - 1) r.y1 = h->H - 1;
+        if (r.x1 > h->W - 1) r.x1 = h->W - 1;
+        if (r.y0 > r.y1 || r.x0 > r.x1) continue;          // entirely outside
+        r.c0 = 0.f; r.c1 = 0.f; r.c2 = 0.f;
+        orig[kept] = i;
+        h->h_hints.get()[kept++] = r;
+    }
+    const size_t hw = (size_t)h->H * h->W;
+    float* d_cols = (float*)(h->d_reveal.get() + cols_at);
+    if (kept) {
+        HIPCHK(h, hipMemcpyAsync(h->d_hints.get(), h->h_hints.get(), (size_t)kept * sizeof(HintRect), hipMemcpyHostToDevice, h->stream.get()));
+        HIPCHK(h, hipMemcpyAsync(h->d_reveal.get(), orig, (size_t)kept * sizeof(int), hipMemcpyHostToDevice, h->stream.get()));
+    }
+    if (n_hints) HIPCHK(h, hipMemsetAsync(d_cols, 0, cols_bytes, h->stream.get()));      // a dropped rectangle reports (0, 0)
+    HIPCHK(h, launch_reveal_hints(src.d_rgb.get(), nullptr, nullptr, 1, src.h, src.w, h->H, h->W, h->d_hints.get(), kept, (const int*)h->d_reveal.get(), d_cols,
+                                  h->stream.get()));
+    HIPCHK(h, launch_raster_hints(h->d_hints.get(), kept, IDC_HINT_AB, mask_value, h->d_ab.get() + (size_t)img * hw * 2, h->d_mask.get() + (size_t)img * hw,
+                                  h->H, h->W, h->stream.get()));
+    h->hint_mask_value[img] = mask_value;
+    if (colours && n_hints) {
+        HIPCHK(h, hipMemcpyAsync(h->h_reveal.get() + cols_at, d_cols, cols_bytes, hipMemcpyDeviceToHost, h->stream.get()));
+        HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+        memcpy(colours, h->h_reveal.get() + cols_at, cols_bytes);
+    }
+    return IDC_OK;
+}
+
 int idc_get_hint_planes(idc_handle h, int img, float* ab, float* mask) {
     int rc = check_img(h, img);
     if (rc) return rc;

@@ -699,6 +699,166 @@ hipError_t launch_ragged_fullres_rgb(const unsigned char* src, const ImgDesc* im
 }
 
 // ------------------------------------------------------------------------------------------------
+// evaluation batches (idc_reveal_hints / idc_forward_async_eval): the paper's simulated user and its metric around the unchanged forward.
+// reveal: a hint's colour = the mean ground-truth ab of the image under the hint's own rectangle, written into the device list that the
+// prologue / raster_hints_kernel then reads in IDC_HINT_AB mode.  net_truth: the net-size uint8 pixels the prologue's L comes from, kept as the
+// ground truth of a net-size score.  eval_sse: the exact integer sum of squared uint8 differences per image and channel.
+// ------------------------------------------------------------------------------------------------
+// One workgroup of 256 threads (four wave64s) per kept, clipped rectangle k of hints[0 .. gridDim.x).  Its image: the single [sh,sw,3] source at
+// src (imgs == nullptr), or image i of the packed run, offs[i] <= k < offs[i+1].  Every net-size pixel of the rectangle is ingest_rgb_kernel's /
+// prologue_pixel's pixel (the same device functions on the same operands), and a and b are summed in float64 in a FIXED order: a thread walks
+// its pixels t, t + 256, ... of the rectangle's row-major index upwards, the 64 lanes of a wave fold by halves (32, 16, ... 1), and thread 0
+// adds the four wave sums in wave order.  No float atomic: the mean is a function of the image's bytes, (H, W) and the four corners only, not
+// of n, the rectangle's place in the list, the slot or the route.  The sum is divided by the pixel count in float64 and rounded once to fp32.
+// Cost: the rectangle's AREA per hint (a 9x9 patch: 81 pixels, one step of the workgroup; the whole 256x256 image: 256 steps), against the
+// hint walk's one comparison per hint per pixel.  colours (may be nullptr) [.,2] receives the mean at the rectangle's index in the caller's list.
+__global__ __launch_bounds__(256) void reveal_hints_kernel(const unsigned char* __restrict__ src, const ImgDesc* __restrict__ imgs,
+                                                           const int* __restrict__ offs, int n, int sh, int sw, int H, int W,
+                                                           HintRect* __restrict__ hints, const int* __restrict__ orig,
+                                                           float* __restrict__ colours) {
+    __shared__ double tab[256];
+    __shared__ double part[2][4];
+    fill_srgb_table(tab);
+    const int k = blockIdx.x;
+    const unsigned char* img = src;
+    if (imgs != nullptr) {
+        int lo = 0, hi = n - 1;                     // the last image whose list starts at or in front of k (images without hints repeat an offset)
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (offs[mid] <= k) lo = mid; else hi = mid - 1;
+        }
+        const ImgDesc d = imgs[lo];
+        img = src + d.off; sh = d.h; sw = d.w;
+    }
+    const HintRect r = hints[k];
+    const int rw = r.x1 - r.x0 + 1, cnt = (r.y1 - r.y0 + 1) * rw;
+    double sa = 0.0, sb = 0.0;
+    for (int t = threadIdx.x; t < cnt; t += 256) {
+        const int ry = t / rw, y = r.y0 + ry, x = r.x0 + (t - ry * rw);
+        int y0, y1, x0, x1;
+        double wy, wx;
+        bilinear_taps(y, sh, H, y0, y1, wy);
+        bilinear_taps(x, sw, W, x0, x1, wx);
+        const unsigned char* p00 = img + ((long long)y0 * sw + x0) * 3; const unsigned char* p01 = img + ((long long)y0 * sw + x1) * 3;
+        const unsigned char* p10 = img + ((long long)y1 * sw + x0) * 3; const unsigned char* p11 = img + ((long long)y1 * sw + x1) * 3;
+        double lin[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) lin[c] = tab[bilinear_u8((double)p00[c], (double)p01[c], (double)p10[c], (double)p11[c], wx, wy)];
+        double L, a, b;
+        linear_to_lab(lin, L, a, b);
+        sa += a; sb += b;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { sa += __shfl_down(sa, o); sb += __shfl_down(sb, o); }
+    if ((threadIdx.x & 63) == 0) { part[0][threadIdx.x >> 6] = sa; part[1][threadIdx.x >> 6] = sb; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double ta = ((part[0][0] + part[0][1]) + part[0][2]) + part[0][3], tb = ((part[1][0] + part[1][1]) + part[1][2]) + part[1][3];
+        const float ma = (float)(ta / (double)cnt), mb = (float)(tb / (double)cnt);
+        hints[k].c0 = ma; hints[k].c1 = mb;
+        if (colours != nullptr) { colours[2 * orig[k] + 0] = ma; colours[2 * orig[k] + 1] = mb; }
+    }
+}
+
+hipError_t launch_reveal_hints(const unsigned char* src, const ImgDesc* imgs, const int* offs, int n, int src_h, int src_w, int H, int W,
+                               HintRect* hints, int n_rects, const int* orig, float* colours, hipStream_t s) {
+    if (n_rects <= 0) return hipSuccess;
+    if (src == nullptr || hints == nullptr || (colours != nullptr && orig == nullptr)) return hipErrorInvalidValue;
+    if (imgs != nullptr ? (offs == nullptr || n <= 0) : (src_h <= 0 || src_w <= 0)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(reveal_hints_kernel, dim3(n_rects), dim3(256), 0, s, src, imgs, offs, n, src_h, src_w, H, W, hints, orig, colours);
+    return hipGetLastError();
+}
+
+// The uint8 half of ragged_prologue_kernel's pixel: rgb_net [n,H,W,3] = cv2.resize of every image to the net size, one thread per pixel.
+__global__ __launch_bounds__(256) void ragged_net_truth_kernel(const unsigned char* __restrict__ src, const ImgDesc* __restrict__ imgs, int n, int H,
+                                                               int W, unsigned char* __restrict__ rgb_net) {
+    const long long HW = (long long)H * W, npix = (long long)n * HW;
+    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (long long)gridDim.x * blockDim.x) {
+        const long long i = p / HW, r = p - i * HW;
+        const int y = (int)(r / W), x = (int)(r - (long long)y * W);
+        const ImgDesc d = imgs[i];
+        const unsigned char* img = src + d.off;
+        int y0, y1, x0, x1;
+        double wy, wx;
+        bilinear_taps(y, d.h, H, y0, y1, wy);
+        bilinear_taps(x, d.w, W, x0, x1, wx);
+        const unsigned char* p00 = img + ((long long)y0 * d.w + x0) * 3; const unsigned char* p01 = img + ((long long)y0 * d.w + x1) * 3;
+        const unsigned char* p10 = img + ((long long)y1 * d.w + x0) * 3; const unsigned char* p11 = img + ((long long)y1 * d.w + x1) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            rgb_net[p * 3 + c] = (unsigned char)bilinear_u8((double)p00[c], (double)p01[c], (double)p10[c], (double)p11[c], wx, wy);
+    }
+}
+
+hipError_t launch_ragged_net_truth(const unsigned char* src, const ImgDesc* imgs, int n, int H, int W, unsigned char* rgb_net, hipStream_t s) {
+    const long long npix = (long long)n * H * W;
+    if (npix <= 0 || imgs == nullptr) return hipErrorInvalidValue;
+    const int blocks = (int)((npix + 255) / 256 < 4096 ? (npix + 255) / 256 : 4096);
+    hipLaunchKernelGGL(ragged_net_truth_kernel, dim3(blocks), dim3(256), 0, s, src, imgs, n, H, W, rgb_net);
+    return hipGetLastError();
+}
+
+// sse[i][c] += sum over the pixels of image i of (res - truth)^2 in channel c, for two packed uint8 arrays of the same layout: image i holds the
+// bytes [3 * first_i, 3 * first_{i+1}) of both, first_i = imgs[i].first, or i * hw when imgs == nullptr (n net-size images).  blockIdx.y is the
+// image.  An image starts on any residue mod 4, so a thread takes the ALIGNED 12-byte group g (three dwords of each array, from their 4-byte
+// aligned bases) and masks the bytes outside its image; a byte's channel is its absolute index mod 3 (every image starts at a multiple of 3),
+// which inside a 12-byte group is its position mod 3.  A dword that would reach past the arrays' `bytes` is assembled from byte loads.
+// Sums: per thread in 64 bits, wave fold, then ONE 64-bit integer atomic add per workgroup and channel into sse (zeroed by the caller on the
+// same stream).  Integer addition: exact in any order.  The worst case, 255^2 * 16384^2 = 1.75e19 for one image, is below 2^64 = 1.84e19.
+__device__ __forceinline__ unsigned load_dword_bounded(const unsigned char* __restrict__ p, long long d, long long bytes) {
+    if (d * 4 + 4 <= bytes) return ((const unsigned*)p)[d];
+    unsigned w = 0u;
+    for (int s = 0; s < 4; ++s)
+        if (d * 4 + s < bytes) w |= (unsigned)p[d * 4 + s] << (8 * s);
+    return w;
+}
+
+__global__ __launch_bounds__(256) void eval_sse_kernel(const unsigned char* __restrict__ res, const unsigned char* __restrict__ truth,
+                                                       const ImgDesc* __restrict__ imgs, long long hw, long long bytes,
+                                                       unsigned long long* __restrict__ sse) {
+    __shared__ unsigned long long part[3][4];
+    const int i = blockIdx.y;
+    const long long lo = 3 * (imgs != nullptr ? imgs[i].first : (long long)i * hw);
+    const long long hi = 3 * (imgs != nullptr ? imgs[i + 1].first : (long long)(i + 1) * hw);
+    const long long g_lo = lo / 12, g_hi = (hi + 11) / 12;
+    if (g_lo + (long long)blockIdx.x * 256 >= g_hi) return;                       // uniform over the workgroup: nothing of this image is ours
+    unsigned long long acc[3] = {0ull, 0ull, 0ull};
+    for (long long g = g_lo + (long long)blockIdx.x * 256 + threadIdx.x; g < g_hi; g += (long long)gridDim.x * 256) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            const unsigned a = load_dword_bounded(res, g * 3 + d, bytes), b = load_dword_bounded(truth, g * 3 + d, bytes);
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const long long at = g * 12 + d * 4 + s;
+                const int diff = (int)((a >> (8 * s)) & 255u) - (int)((b >> (8 * s)) & 255u);
+                if (at >= lo && at < hi) acc[(d * 4 + s) % 3] += (unsigned long long)(diff * diff);
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc[c] += __shfl_down(acc[c], o);
+        if ((threadIdx.x & 63) == 0) part[c][threadIdx.x >> 6] = acc[c];
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int c = threadIdx.x;
+        atomicAdd(&sse[(size_t)i * 3 + c], part[c][0] + part[c][1] + part[c][2] + part[c][3]);
+    }
+}
+
+hipError_t launch_eval_sse(const unsigned char* res, const unsigned char* truth, const ImgDesc* imgs, int n, long long hw, long long max_pixels,
+                           long long total_pixels, unsigned long long* sse, hipStream_t s) {
+    if (n <= 0 || max_pixels <= 0 || total_pixels < max_pixels || sse == nullptr || (((uintptr_t)res | (uintptr_t)truth) & 3))
+        return hipErrorInvalidValue;
+    const long long groups = (max_pixels * 3 + 11) / 12 + 1;                      // an image's bytes touch at most this many aligned groups
+    const int blocks = (int)((groups + 255) / 256 < 256 ? (groups + 255) / 256 : 256);
+    hipLaunchKernelGGL(eval_sse_kernel, dim3(blocks, n), dim3(256), 0, s, res, truth, imgs, hw, total_pixels * 3, sse);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
 // reference-image global hints: global_stats_kernel for m reference photographs of individual sizes, resized inside the kernel (the notebook
 // resizes inside get_global_histogram, DemoGlobalHistogramTransfer.ipynb:176-182), and the kernel that turns the counts into the rows
 // glob_branch_kernel reads -- so that a reference goes from its uint8 bytes to the net's global input without visiting the host.

@@ -186,6 +186,8 @@ struct idc_context {
     int dist_n = 0;                      // images whose distribution is resident from the last forward (0 = none)
     DevMem<HintRect> d_hints;            // click session: hint list staging
     PinnedMem<HintRect> h_hints;
+    DevMem<unsigned char> d_reveal;      // idc_reveal_hints: the kept rectangles' places in the caller's list int[kept], then colours float[n_hints][2] ...
+    PinnedMem<unsigned char> h_reveal;   // ... and their pinned copy
     DevMem<float> d_centres; DevMem<double> d_sugg; DevMem<unsigned> d_sugg_counts;   // colour suggestions
     DevMem<float> d_map_ab, d_map_s;     // idc_dist_decode / idc_dist_entropy results: [max_batch][2][npix], [max_batch][npix] (first use)
     std::vector<char> l_set;             // per image slot: d_L holds an uploaded L plane (idc_forward_resident refuses otherwise)
@@ -229,6 +231,12 @@ struct idc_context {
         // d_meta / h_meta between the hint offsets and the hint list
         struct StagedOut { uint8_t* user; size_t at, bytes; };
         std::vector<StagedOut> staged_outs;
+        // idc_forward_async_eval: the net-size ground truth [max_batch,H,W,3] (a net-size score), and one block for what the batch reports --
+        // sse uint64[max_batch][3], then hint_colours float[n_hints][2] -- on the device and pinned; a pageable sse / hint_colours waits in
+        // h_eval until idc_wait copies it out (eval_outs; empty after every other call)
+        DevMem<unsigned char> d_truth, d_eval;
+        PinnedMem<unsigned char> h_eval;
+        std::vector<StagedOut> eval_outs;
         // idc_forward_async_rgb_ref: the batch's references and the slot's OWN [max_batch][316] global inputs (the handle's d_glob_in is not touched)
         RefStage ref;
         DevMem<float> d_glob_in;

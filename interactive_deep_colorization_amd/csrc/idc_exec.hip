@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <algorithm>
 #include <cmath>
 
 #include "idc_engine.h"
@@ -358,6 +359,7 @@ static int wait_slot(idc_context* h, int slot) {
     if (arc) return arc;
     if (sl.staged_out && sl.user_out) memcpy(sl.user_out, sl.h_out.get(), (size_t)sl.n * h->H * h->W * 2 * 4);
     for (const auto& o : sl.staged_outs) memcpy(o.user, sl.h_rgb.get() + o.at, o.bytes);
+    for (const auto& o : sl.eval_outs) memcpy(o.user, sl.h_eval.get() + o.at, o.bytes);
     return IDC_OK;
 }
 
@@ -611,7 +613,7 @@ int idc_forward_async(idc_handle h, int slot, int n, const float* L_mc, const fl
     HIPCHK(h, hipMemcpyAsync(sl.staged_out ? sl.h_out.get() : out_ab, sl.d_out.get(), (size_t)n * hw * 2 * 4, hipMemcpyDeviceToHost, h->s_out.get()));
     HIPCHK(h, hipEventRecord(sl.ev_out.get(), h->s_out.get()));
     sl.pending = true; sl.timed = true; sl.user_out = out_ab; sl.n = n;
-    sl.staged_outs.clear();
+    sl.staged_outs.clear(); sl.eval_outs.clear();
     return IDC_OK;
 }
 
@@ -629,6 +631,8 @@ struct BatchIO {
     int src_h, src_w; const uint8_t* rgb_in; uint8_t* rgb_out;
     const idc_ref_image* images; uint8_t* const* outs;
 };
+// idc_forward_async_eval's own arguments (ev == nullptr: every other entry point): the score is required, the revealed colours are optional
+struct EvalArgs { uint64_t* sse; float* hint_colours; };
 // One host buffer of a call and the bytes of the slot's packed device array it fills (in) or receives (out)
 struct Piece { const uint8_t* in; uint8_t* out; size_t in_at, in_bytes, out_at, out_bytes; bool in_pinned, out_pinned; };
 
@@ -659,19 +663,23 @@ static hipError_t copy_pieces(const std::vector<Piece>& pieces, bool to_device, 
 
 static int forward_async_rgb(idc_handle h, int slot, int n, const BatchIO& io, const int32_t* hint_offsets,
                              const idc_hint* hints, int mode, float mask_value, float maskcent, float l_cent, unsigned flags,
-                             const RefArgs* ra, float* out_ab) {
+                             const RefArgs* ra, float* out_ab, const EvalArgs* ev = nullptr) {
     int rc = check_forward_args(h, n);
     if (rc) return rc;
     const bool ragged = io.ragged;
+    const bool want_rgb = ragged ? io.outs != nullptr : io.rgb_out != nullptr;      // only an evaluation batch may keep its images on the device
+    const bool reveal = ev && mode == IDC_HINT_REVEAL;
     if (slot < 0 || slot > 1) return fail(&h->err, IDC_ERR_INVALID_ARG, "slot %d not in 0..1", slot);
-    if (ragged ? (!io.images || !io.outs) : (!io.rgb_in || !io.rgb_out)) return fail(&h->err, IDC_ERR_INVALID_ARG, "null image pointer");
+    if (ragged ? (!io.images || !(io.outs || ev)) : (!io.rgb_in || !io.rgb_out)) return fail(&h->err, IDC_ERR_INVALID_ARG, "null image pointer");
     if (flags & ~(unsigned)IDC_BATCH_OUT_SOURCE) return fail(&h->err, IDC_ERR_INVALID_ARG, "unknown flag bits 0x%x", flags);
-    if (mode != IDC_HINT_AB && mode != IDC_HINT_RGB) return fail(&h->err, IDC_ERR_INVALID_ARG, "hint mode %d", mode);
+    if (mode != IDC_HINT_AB && mode != IDC_HINT_RGB && !reveal) return fail(&h->err, IDC_ERR_INVALID_ARG, "hint mode %d", mode);
+    if (ev && !ev->sse) return fail(&h->err, IDC_ERR_INVALID_ARG, "null sse");
+    if (ev && ev->hint_colours && !reveal) return fail(&h->err, IDC_ERR_INVALID_ARG, "hint_colours with hint mode %d: only IDC_HINT_REVEAL reveals colours", mode);
     size_t in_bytes = 0;
     if (ragged) {
         for (int i = 0; i < n; ++i) {
             const idc_ref_image& im = io.images[i];
-            if (!im.rgb || !io.outs[i]) return fail(&h->err, IDC_ERR_INVALID_ARG, "image %d: null image pointer", i);
+            if (!im.rgb || (want_rgb && !io.outs[i])) return fail(&h->err, IDC_ERR_INVALID_ARG, "image %d: null image pointer", i);
             if (im.h < 1 || im.h > 16384 || im.w < 1 || im.w > 16384)
                 return fail(&h->err, IDC_ERR_INVALID_ARG, "image %d: source size %dx%d outside 1..16384", i, im.h, im.w);
             in_bytes += (size_t)im.h * im.w * 3;                  // n * 0.8 GB: no overflow in 64 bits
@@ -732,7 +740,9 @@ static int forward_async_rgb(idc_handle h, int slot, int n, const BatchIO& io, c
     // the metadata block: the hint offsets int[max_batch + 1], (images of individual sizes) the table ImgDesc[max_batch + 1], the kept hints
     const size_t table_at = align_up((nb + 1) * sizeof(int), 16);
     const size_t hints_at = ragged ? table_at + align_up((nb + 1) * sizeof(ImgDesc), 16) : table_at;
-    const size_t meta_bytes = hints_at + (size_t)kept * sizeof(HintRect), meta_floor = hints_at + 256 * sizeof(HintRect);
+    // ... and (IDC_HINT_REVEAL) each kept hint's place in the caller's list int[kept], where its revealed colour is reported
+    const size_t orig_at = hints_at + (size_t)kept * sizeof(HintRect);
+    const size_t meta_bytes = orig_at + (reveal ? (size_t)kept * sizeof(int) : 0), meta_floor = hints_at + 256 * (sizeof(HintRect) + sizeof(int));
     HIPCHK(h, sl.d_src.ensure(in_bytes));
     HIPCHK(h, sl.d_meta.ensure(meta_bytes, meta_floor));
     HIPCHK(h, sl.h_meta.ensure(meta_bytes, meta_floor));
@@ -740,6 +750,12 @@ static int forward_async_rgb(idc_handle h, int slot, int n, const BatchIO& io, c
     if (source_out) {
         HIPCHK(h, sl.d_labq.ensure(nb * hw * 3 * 8));
         HIPCHK(h, sl.d_full.ensure(in_bytes));
+    }
+    const size_t cols_at = nb * 3 * sizeof(uint64_t), cols_bytes = ev && ev->hint_colours ? (size_t)n_hints * 2 * sizeof(float) : 0;
+    if (ev) {
+        if (!source_out) HIPCHK(h, sl.d_truth.ensure(nb * hw * 3));
+        HIPCHK(h, sl.d_eval.ensure(cols_at + cols_bytes, cols_at + 4096));
+        HIPCHK(h, sl.h_eval.ensure(cols_at + cols_bytes, cols_at + 4096));
     }
     // every host buffer is judged on its own: pageable sources are copied into the slot's pinned staging here, on the calling thread
     std::vector<Piece> pieces;
@@ -749,8 +765,9 @@ static int forward_async_rgb(idc_handle h, int slot, int n, const BatchIO& io, c
         for (int i = 0; i < n; ++i) {
             const size_t sb = (size_t)io.images[i].h * io.images[i].w * 3;
             tab[i].off = (long long)at; tab[i].first = (long long)(at / 3); tab[i].h = io.images[i].h; tab[i].w = io.images[i].w;
-            pieces.push_back({io.images[i].rgb, io.outs[i], at, sb, source_out ? at : (size_t)i * hw * 3, source_out ? sb : hw * 3,
-                              is_pinned(io.images[i].rgb), is_pinned(io.outs[i])});
+            uint8_t* const out = want_rgb ? io.outs[i] : nullptr;
+            pieces.push_back({io.images[i].rgb, out, at, sb, source_out ? at : (size_t)i * hw * 3, source_out ? sb : hw * 3,
+                              is_pinned(io.images[i].rgb), !want_rgb || is_pinned(out)});
             at += sb;
         }
         tab[n].off = (long long)at; tab[n].first = (long long)(at / 3); tab[n].h = 0; tab[n].w = 0;
@@ -770,11 +787,14 @@ static int forward_async_rgb(idc_handle h, int slot, int n, const BatchIO& io, c
     // the list as the kernel reads it: offsets of the KEPT hints per image, then the clipped rectangles
     int* m_offs = (int*)sl.h_meta.get();
     HintRect* m_hints = (HintRect*)(sl.h_meta.get() + hints_at);
+    int* m_orig = (int*)(sl.h_meta.get() + orig_at);
     m_offs[0] = 0;
     for (int i = 0, w = 0; i < n; ++i) {
         for (int k = hint_offsets ? hint_offsets[i] : 0; k < (hint_offsets ? hint_offsets[i + 1] : 0); ++k) {
             HintRect r;                               // clip fills r even for a hint it drops: only a kept one may reach the block, which has room for `kept`
-            if (clip(hints[k], r)) m_hints[w++] = r;
+            if (!clip(hints[k], r)) continue;
+            if (reveal) m_orig[w] = k;
+            m_hints[w++] = r;
         }
         m_offs[i + 1] = w;
     }
@@ -800,6 +820,13 @@ static int forward_async_rgb(idc_handle h, int slot, int n, const BatchIO& io, c
     const int* d_offs = kept ? (const int*)sl.d_meta.get() : nullptr;
     const HintRect* d_hints = (const HintRect*)(sl.d_meta.get() + hints_at);
     const ImgDesc* d_tab = (const ImgDesc*)(sl.d_meta.get() + table_at);
+    if (reveal) {   // the colours of the list the prologue is about to read; a dropped rectangle's (0, 0) is the memset's
+        float* d_cols = cols_bytes ? (float*)(sl.d_eval.get() + cols_at) : nullptr;
+        if (cols_bytes) HIPCHK(h, hipMemsetAsync(d_cols, 0, cols_bytes, h->stream.get()));
+        HIPCHK(h, launch_reveal_hints(sl.d_src.get(), d_tab, d_offs, n, 0, 0, h->H, h->W, (HintRect*)(sl.d_meta.get() + hints_at), kept,
+                                      (const int*)(sl.d_meta.get() + orig_at), d_cols, h->stream.get()));
+        mode = IDC_HINT_AB;
+    }
     if (ragged)
         HIPCHK(h, launch_ragged_prologue(sl.d_src.get(), d_tab, n, h->H, h->W, l_cent, d_offs, d_hints, mode, mask_value, sl.d_L.get(), sl.d_ab.get(),
                                          sl.d_mask.get(), h->stream.get()));
@@ -816,10 +843,34 @@ static int forward_async_rgb(idc_handle h, int slot, int n, const BatchIO& io, c
                                             sl.d_full.get(), h->stream.get()));
     else if (source_out)
         HIPCHK(h, launch_batch_fullres_rgb(sl.d_src.get(), n, io.src_h, io.src_w, sl.d_labq.get(), h->H, h->W, IDC_INTERP_LINEAR, sl.d_full.get(), h->stream.get()));
+    if (ev) {       // the score: the source-size result against the source bytes, or the net-size result against the net-size ground truth
+        unsigned long long* d_sse = (unsigned long long*)sl.d_eval.get();
+        HIPCHK(h, hipMemsetAsync(d_sse, 0, (size_t)n * 3 * sizeof(uint64_t), h->stream.get()));
+        if (source_out) {
+            long long max_pixels = 0;
+            for (int i = 0; i < n; ++i) max_pixels = std::max(max_pixels, (long long)io.images[i].h * io.images[i].w);
+            HIPCHK(h, launch_eval_sse(sl.d_full.get(), sl.d_src.get(), d_tab, n, 0, max_pixels, (long long)(in_bytes / 3), d_sse, h->stream.get()));
+        } else {
+            HIPCHK(h, launch_ragged_net_truth(sl.d_src.get(), d_tab, n, h->H, h->W, sl.d_truth.get(), h->stream.get()));
+            HIPCHK(h, launch_eval_sse(sl.d_rgb.get(), sl.d_truth.get(), nullptr, n, (long long)hw, (long long)hw, (long long)n * hw, d_sse, h->stream.get()));
+        }
+    }
     HIPCHK(h, hipEventRecord(sl.ev_comp.get(), h->stream.get()));
     HIPCHK(h, hipStreamWaitEvent(h->s_out.get(), sl.ev_comp.get(), 0));
     HIPCHK(h, hipEventRecord(sl.ev_out0.get(), h->s_out.get()));
-    HIPCHK(h, copy_pieces(pieces, false, source_out ? sl.d_full.get() : sl.d_rgb.get(), sl.h_rgb.get(), h->s_out.get()));
+    sl.eval_outs.clear();
+    if (ev) {
+        const size_t sse_bytes = (size_t)n * 3 * sizeof(uint64_t);
+        const bool sse_direct = is_pinned(ev->sse), cols_direct = cols_bytes && is_pinned(ev->hint_colours);
+        HIPCHK(h, hipMemcpyAsync(sse_direct ? (void*)ev->sse : (void*)sl.h_eval.get(), sl.d_eval.get(), sse_bytes, hipMemcpyDeviceToHost, h->s_out.get()));
+        if (!sse_direct) sl.eval_outs.push_back({(uint8_t*)ev->sse, 0, sse_bytes});
+        if (cols_bytes) {
+            HIPCHK(h, hipMemcpyAsync(cols_direct ? (void*)ev->hint_colours : (void*)(sl.h_eval.get() + cols_at), sl.d_eval.get() + cols_at, cols_bytes,
+                                     hipMemcpyDeviceToHost, h->s_out.get()));
+            if (!cols_direct) sl.eval_outs.push_back({(uint8_t*)ev->hint_colours, cols_at, cols_bytes});
+        }
+    }
+    if (want_rgb) HIPCHK(h, copy_pieces(pieces, false, source_out ? sl.d_full.get() : sl.d_rgb.get(), sl.h_rgb.get(), h->s_out.get()));
     if (out_ab) HIPCHK(h, hipMemcpyAsync(staged_ab ? sl.h_out.get() : out_ab, sl.d_out.get(), (size_t)n * hw * 2 * 4, hipMemcpyDeviceToHost, h->s_out.get()));
     HIPCHK(h, hipEventRecord(sl.ev_out.get(), h->s_out.get()));
     sl.pending = true; sl.timed = true; sl.n = n;
@@ -853,6 +904,16 @@ int idc_forward_async_images(idc_handle h, int slot, int n, const idc_ref_image*
     if (!refs) return forward_async_rgb(h, slot, n, io, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, nullptr, out_ab);
     const RefArgs ra = {refs->m, refs->refs, refs->ref_index, refs->centres, refs->hist_flag, refs->flags};
     return forward_async_rgb(h, slot, n, io, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, &ra, out_ab);
+}
+
+int idc_forward_async_eval(idc_handle h, int slot, int n, const idc_ref_image* images, const int32_t* hint_offsets, const idc_hint* hints,
+                           int mode, float mask_value, float maskcent, float l_cent, unsigned flags, const idc_batch_refs* refs,
+                           uint8_t* const* rgb_out, float* out_ab, uint64_t* sse, float* hint_colours) {
+    const BatchIO io = {true, 0, 0, nullptr, nullptr, images, rgb_out};
+    const EvalArgs ev = {sse, hint_colours};
+    if (!refs) return forward_async_rgb(h, slot, n, io, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, nullptr, out_ab, &ev);
+    const RefArgs ra = {refs->m, refs->refs, refs->ref_index, refs->centres, refs->hist_flag, refs->flags};
+    return forward_async_rgb(h, slot, n, io, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, &ra, out_ab, &ev);
 }
 
 int idc_wait(idc_handle h, int slot) {

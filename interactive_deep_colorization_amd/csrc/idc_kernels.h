@@ -313,6 +313,19 @@ hipError_t launch_ragged_prologue(const unsigned char* src, const ImgDesc* imgs,
 hipError_t launch_ragged_fullres_rgb(const unsigned char* src, const ImgDesc* imgs, int n, long long total, const double* lab_q, int H, int W,
                                      int interp, unsigned char* rgb, hipStream_t s);
 
+// Evaluation batches (idc_reveal_hints / idc_forward_async_eval; idc_colour.hip).  reveal_hints: (c0, c1) of each of the n_rects clipped
+// rectangles of `hints` = the float64 mean ab (rounded once to fp32) of its image's net-size pixels under it, one workgroup per rectangle, fixed
+// summation order, cost = the rectangle's area; the image is the single [src_h,src_w,3] source at src (imgs == nullptr) or image i of the packed
+// run with offs[i] <= k < offs[i+1] (offs [n+1]: the list's offsets).  colours (or nullptr) [.,2] gets the same pair at index orig[k].
+// ragged_net_truth: rgb_net [n,H,W,3] = every image resized to the net size (the prologue's uint8 pixel).  eval_sse: sse [n][3] += the sum of
+// squared differences of res and truth per image and channel (R, G, B), both packed alike from 4-byte aligned bases: n images of hw pixels
+// (imgs == nullptr) or the ImgDesc run; max_pixels / total_pixels = the largest image / all images.  The caller zeroes sse on the same stream.
+hipError_t launch_reveal_hints(const unsigned char* src, const ImgDesc* imgs, const int* offs, int n, int src_h, int src_w, int H, int W,
+                               HintRect* hints, int n_rects, const int* orig, float* colours, hipStream_t s);
+hipError_t launch_ragged_net_truth(const unsigned char* src, const ImgDesc* imgs, int n, int H, int W, unsigned char* rgb_net, hipStream_t s);
+hipError_t launch_eval_sse(const unsigned char* res, const unsigned char* truth, const ImgDesc* imgs, int n, long long hw, long long max_pixels,
+                           long long total_pixels, unsigned long long* sse, hipStream_t s);
+
 // Colour suggestions at one pixel (get_ab_reccs, colorize_image.py:322-354): see idc_session.hip for the algorithm.
 // pdf bin b at pdf[b*stride]; centres [B][2]; out_centres [K][2], out_conf [K] (f64); out_counts [B] or nullptr.
 constexpr int kSuggestMaxBins = 1024, kSuggestMaxK = 16;

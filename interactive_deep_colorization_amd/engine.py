@@ -649,6 +649,18 @@ class HipColorizer(object):
         self._chk(self.lib.idc_set_hints(self._h, int(img), len(rows), arr, {"ab": N.IDC_HINT_AB, "rgb": N.IDC_HINT_RGB}[mode],
                                          float(mask_value)))
 
+    def reveal_hints(self, rects, img=0, mask_value=1.0):
+        """``set_hints`` in 'ab' mode with every colour revealed on the device (``idc_reveal_hints``): rects are rows (y0, x0, y1, x1[, ...]),
+        and a rectangle's colour is the mean ground-truth ab of slot ``img``'s kept source (``set_image_rgb(keep_source=True)``) under it -- the
+        paper's simulated user.  Returns the revealed colours (k,2) float32, (0, 0) for a rectangle wholly outside the image."""
+        rows = [tuple(r) for r in rects]
+        arr = (N.Hint * max(len(rows), 1))()
+        for i, r in enumerate(rows):
+            arr[i].y0, arr[i].x0, arr[i].y1, arr[i].x1 = int(r[0]), int(r[1]), int(r[2]), int(r[3])
+        colours = np.zeros((len(rows), 2), np.float32)
+        self._chk(self.lib.idc_reveal_hints(self._h, int(img), len(rows), arr, float(mask_value), _fptr(colours)))
+        return colours
+
     def hint_planes(self, img=0):
         """(ab (2,H,W), mask (1,H,W)) float32 copies of the resident hint planes of one slot."""
         ab = np.empty((2, self.H, self.W), np.float32)
@@ -982,30 +994,54 @@ class HipColorizer(object):
         out='source', or ``None``: they are taken from the pinned pool.  Returns the list of outputs, valid after ``wait(slot)``.  Image i's
         result is bit for bit what ``forward_async_rgb`` gives for it alone.  Every other argument as in ``forward_async_rgb``; pinned and
         pageable arrays may be mixed within a call, and the engine holds a reference to each until ``wait(slot)``."""
+        return self._enqueue_images("forward_async_images", slot, images, hints, out_rgb, out_ab, mode, mask_value, maskcent, l_cent, out,
+                                    refs, ref_index, centres, hist_flag, saturation)
+
+    def forward_async_eval(self, slot, images, hints, out_rgb=None, out_ab=None, mode="reveal", mask_value=1.0, maskcent=0.0, l_cent=50.0,
+                           out="net", refs=None, ref_index=None, centres=None, hist_flag=1.0, saturation=False, want_rgb=False):
+        """``forward_async_images`` that also scores the batch on the device (``idc_forward_async_eval``): returns ``(sse, hint_colours,
+        out_rgb)``, valid after ``wait(slot)``.  ``sse`` (n,3) uint64 is the exact sum of squared uint8 differences per image and channel
+        between the result and the ground truth -- the images themselves at the net size (out='net') or at their own (out='source').  mode
+        'reveal' (default): ``hints`` holds per-image lists of rectangles (y0, x0, y1, x1[, ...]) whose colours the device takes from the
+        image (the mean ab under the rectangle), and ``hint_colours`` (all rectangles, 2) float32 reports them; modes 'ab' / 'rgb' score a
+        given hint list and ``hint_colours`` is None.  No image leaves the device unless ``want_rgb`` or ``out_rgb`` asks for it (``out_rgb``
+        is then the list ``forward_async_images`` returns, else None).  Array validation and every other argument as there."""
+        return self._enqueue_images("forward_async_eval", slot, images, hints, out_rgb, out_ab, mode, mask_value, maskcent, l_cent, out,
+                                    refs, ref_index, centres, hist_flag, saturation, evaluate=True, want_rgb=want_rgb or out_rgb is not None)
+
+    def _enqueue_images(self, who, slot, images, hints, out_rgb, out_ab, mode, mask_value, maskcent, l_cent, out, refs, ref_index, centres,
+                        hist_flag, saturation, evaluate=False, want_rgb=True):
         images = list(images)
         n = len(images)
         for a in images:
             if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or not a.flags.c_contiguous or a.size == 0:
-                raise ValueError("forward_async_images needs uint8 C-contiguous (h,w,3) arrays")
+                raise ValueError("%s needs uint8 C-contiguous (h,w,3) arrays" % who)
         flags = {"net": 0, "source": N.IDC_BATCH_OUT_SOURCE}[out]
         shapes = [tuple(a.shape) if flags else (self.H, self.W, 3) for a in images]
-        if out_rgb is None:
-            out_rgb = self._pinned_slices(shapes)
-        out_rgb = list(out_rgb)
-        if len(out_rgb) != n:
-            raise ValueError("forward_async_images needs %d outputs, got %d" % (n, len(out_rgb)))
-        for o, shp in zip(out_rgb, shapes):
-            if not isinstance(o, np.ndarray) or o.dtype != np.uint8 or not o.flags.c_contiguous or tuple(o.shape) != shp:
-                raise ValueError("forward_async_images needs a uint8 C-contiguous out_rgb of shape %s" % (shp,))
+        if want_rgb:
+            if out_rgb is None:
+                out_rgb = self._pinned_slices(shapes)
+            out_rgb = list(out_rgb)
+            if len(out_rgb) != n:
+                raise ValueError("%s needs %d outputs, got %d" % (who, n, len(out_rgb)))
+            for o, shp in zip(out_rgb, shapes):
+                if not isinstance(o, np.ndarray) or o.dtype != np.uint8 or not o.flags.c_contiguous or tuple(o.shape) != shp:
+                    raise ValueError("%s needs a uint8 C-contiguous out_rgb of shape %s" % (who, shp))
         if out_ab is not None and (out_ab.dtype != np.float32 or not out_ab.flags.c_contiguous or tuple(out_ab.shape) != (n, 2, self.H, self.W)):
-            raise ValueError("forward_async_images needs a float32 C-contiguous out_ab of shape %s" % ((n, 2, self.H, self.W),))
+            raise ValueError("%s needs a float32 C-contiguous out_ab of shape %s" % (who, (n, 2, self.H, self.W)))
+        modes = {"ab": N.IDC_HINT_AB, "rgb": N.IDC_HINT_RGB}
+        if evaluate:
+            modes["reveal"] = N.IDC_HINT_REVEAL
+            if mode == "reveal" and hints is not None:     # rectangles only: the colours are the device's to find
+                hints = [None if h is None else [tuple(r[:4]) + (0.0, 0.0) for r in h] for h in hints]
         offsets, arr = flatten_hints(hints, n)
         vp = ctypes.c_void_p
         table = (N.RefImage * max(n, 1))()
-        outs = (vp * max(n, 1))()
-        for i, (a, o) in enumerate(zip(images, out_rgb)):
+        outs = (vp * max(n, 1))() if want_rgb else None
+        for i, a in enumerate(images):
             table[i].rgb, table[i].h, table[i].w = a.ctypes.data, a.shape[0], a.shape[1]
-            outs[i] = o.ctypes.data
+            if want_rgb:
+                outs[i] = out_rgb[i].ctypes.data
         block = None
         if refs is not None:
             if isinstance(refs, np.ndarray) and refs.ndim == 3:
@@ -1015,13 +1051,21 @@ class HipColorizer(object):
             c = _f32c(centres, (313, 2)) if centres is not None else None
             block = N.BatchRefs(len(keep), rarr if keep else None, idx.ctypes.data if idx is not None else None,
                                 c.ctypes.data if c is not None else None, float(hist_flag), N.IDC_REF_SATURATION if saturation else 0)
-        self._chk(self.lib.idc_forward_async_images(
-            self._h, int(slot), int(n), table, offsets.ctypes.data_as(vp) if offsets is not None else None,
-            ctypes.cast(arr, vp) if arr is not None else None, {"ab": N.IDC_HINT_AB, "rgb": N.IDC_HINT_RGB}[mode], float(mask_value),
-            float(maskcent), float(l_cent), flags, ctypes.byref(block) if block is not None else None, outs,
-            out_ab.ctypes.data_as(vp) if out_ab is not None else None))
-        self._in_flight[int(slot)] = (images, out_rgb, out_ab)    # the library reads / writes them until the slot's wait
-        return out_rgb
+        args = (self._h, int(slot), int(n), table, offsets.ctypes.data_as(vp) if offsets is not None else None,
+                ctypes.cast(arr, vp) if arr is not None else None, modes[mode], float(mask_value),
+                float(maskcent), float(l_cent), flags, ctypes.byref(block) if block is not None else None, outs,
+                out_ab.ctypes.data_as(vp) if out_ab is not None else None)
+        if not evaluate:
+            self._chk(self.lib.idc_forward_async_images(*args))
+            self._in_flight[int(slot)] = (images, out_rgb, out_ab)    # the library reads / writes them until the slot's wait
+            return out_rgb
+        sse = self._pool.take((n, 3), np.uint64)
+        colours = None
+        if mode == "reveal":
+            colours = self._pool.take((int(offsets[-1]) if offsets is not None else 0, 2), np.float32)
+        self._chk(self.lib.idc_forward_async_eval(*(args + (sse.ctypes.data_as(vp), colours.ctypes.data_as(vp) if colours is not None and colours.size else None))))
+        self._in_flight[int(slot)] = (images, out_rgb, out_ab, sse, colours)
+        return sse, colours, (out_rgb if want_rgb else None)
 
     def colorize_images(self, items, batch=None, out="source", **kw):
         """Generator: colourise a stream of single images of any sizes with both pipeline slots busy.  An item is ``rgb``, ``(rgb, hints)`` or
@@ -1058,6 +1102,70 @@ class HipColorizer(object):
             rgb = np.asarray(item[0])
             if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.size == 0:
                 raise ValueError("colorize_images needs uint8 (h,w,3) images, got %s %s" % (rgb.dtype, rgb.shape))
+            return rgb, item[1] if len(item) > 1 else None, item[2] if len(item) > 2 else None, len(item) > 2
+
+        k, group = 0, []
+        try:
+            for item in items:
+                group.append(parse(item))
+                if len(group) < batch:
+                    continue
+                if pending[k & 1] is not None:
+                    for r in finish(k & 1):
+                        yield r
+                submit(k & 1, group)
+                k, group = k + 1, []
+            if group:
+                if pending[k & 1] is not None:
+                    for r in finish(k & 1):
+                        yield r
+                submit(k & 1, group)
+                k += 1
+            for slot in (k & 1, (k + 1) & 1):       # the older batch first
+                if pending[slot] is not None:
+                    for r in finish(slot):
+                        yield r
+        finally:                                    # a consumer that stops early: nothing stays in flight on buffers about to be recycled
+            for slot in (0, 1):
+                if pending[slot] is not None:
+                    pending[slot] = None
+                    self.wait(slot)
+
+    def evaluate_images(self, items, batch=None, out="net", mode="reveal", **kw):
+        """Generator: score a stream of ground-truth colour images with both pipeline slots busy -- ``colorize_images`` whose every image is
+        compared with itself on the device (``forward_async_eval``).  An item is ``rgb``, ``(rgb, rects)`` or ``(rgb, rects, ref)``; with
+        mode='reveal' (default) ``rects`` are rows (y0, x0, y1, x1) whose colours the device reveals from the image, with 'ab' / 'rgb' they
+        are hint rows as in ``set_hints``.  Grouping, slot alternation and order as in ``colorize_images``; one ``(psnr, sse)`` per image is
+        yielded: ``sse`` (3,) uint64, ``psnr`` = ``evaluate.psnr_from_sse`` of it over the image's net size (out='net') or its own
+        (out='source'), ``inf`` for an exact match.  24 bytes per image come back; no image does."""
+        from .evaluate import psnr_from_sse
+        batch = self.max_batch if batch is None else int(batch)
+        if not 1 <= batch <= self.max_batch:
+            raise ValueError("batch %d outside 1..%d" % (batch, self.max_batch))
+        pending = [None, None]                      # per slot: (pinned sse, sizes, pinned sources) of the batch in flight
+
+        def finish(slot):
+            self.wait(slot)
+            (sse, sizes, _), pending[slot] = pending[slot], None
+            sse = np.array(sse)
+            return [(psnr_from_sse(sse[i], h, w), sse[i]) for i, (h, w) in enumerate(sizes)]
+
+        def submit(slot, group):
+            srcs = self._pinned_slices([g[0].shape for g in group])
+            for s, g in zip(srcs, group):
+                np.copyto(s, g[0])
+            hints = [g[1] for g in group]
+            more = dict(kw)
+            if any(g[3] for g in group):
+                more["refs"], more["ref_index"] = dedupe_refs([g[2] for g in group], len(group))
+            sse = self.forward_async_eval(slot, srcs, hints, out=out, mode=mode, want_rgb=False, **more)[0]
+            pending[slot] = (sse, [g[0].shape[:2] if out == "source" else (self.H, self.W) for g in group], srcs)
+
+        def parse(item):
+            item = (item,) if isinstance(item, np.ndarray) else tuple(item)
+            rgb = np.asarray(item[0])
+            if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.size == 0:
+                raise ValueError("evaluate_images needs uint8 (h,w,3) images, got %s %s" % (rgb.dtype, rgb.shape))
             return rgb, item[1] if len(item) > 1 else None, item[2] if len(item) > 2 else None, len(item) > 2
 
         k, group = 0, []
