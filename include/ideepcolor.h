@@ -431,7 +431,7 @@ int idc_fullres_rgb(idc_handle h, int img, int source, int interp, int l_mode, u
  *      Either entry point may use a slot, in any order.  The slot owns all it needs (source bytes, hint list, planes,
  *      results, pinned staging for pageable callers), grown on demand: like idc_forward_async the call neither reads nor
  *      replaces the handle's resident L / hint planes, kept sources, the mask_value of idc_set_hints or the ab map and
- *      colour results of the last blocking forward.  The distribution heads are not part of this call, and the guarantee
+ *      colour results of the last blocking forward.  The distribution heads are not part of this call (idc_forward_async_dist runs them), and the guarantee
  *      does not extend to an IDC_FLAG_DIST313 handle: there every forward through the network, this one included, runs
  *      the 313 head into the handle's pred_ab scratch, and while idc_keep_dist is on it also replaces the resident
  *      distribution, which then belongs to this batch (images 0..n-1).  Without IDC_FLAG_DIST313, or with idc_keep_dist
@@ -558,6 +558,60 @@ int idc_reveal_hints(idc_handle h, int img, int n_hints, const idc_hint* rects, 
 int idc_forward_async_eval(idc_handle h, int slot, int n, const idc_ref_image* images, const int32_t* hint_offsets,
                            const idc_hint* hints, int mode, float mask_value, float maskcent, float l_cent, unsigned flags,
                            const idc_batch_refs* refs, uint8_t* const* rgb_out, float* out_ab, uint64_t* sse, float* hint_colours);
+
+/* ---- distribution batches: where the model is least sure, and what it would suggest there -- for many pixels and many images at once.
+ *      The GUI runs the distribution head on every click (ui/gui_draw.py predict_color -> ColorizeImageTorchDist.get_ab_reccs,
+ *      data/colorize_image.py:322-354) and shows its entropy map (compute_entropy, :356-357,545-546) for the user to judge where a hint is
+ *      needed; the calls below stand in for that judgement and for a loop of get_ab_reccs calls, one pixel each.
+ *      Hd x Wd is the distribution's grid as for idc_dist_entropy: H/4 x W/4 (529 head) or H x W (313 head); s = H / Hd.
+ *      idc_dist_peaks (blocking; replaces an arg-min search of compute_entropy's map on the host): runs idc_dist_entropy's launch on the
+ *      resident distribution of images 0..n-1 and picks, per image, P cells by greedy suppression.  Candidates are the cells whose ent is not
+ *      NaN; with IDC_PEAKS_SKIP_HINTS the cells whose s x s block of the handle's resident hint mask (idc_get_hint_planes, as it is at the call)
+ *      holds a non-zero value are left out.  For k = 0..P-1: the candidate with the smallest ent (ent is MINUS the entropy: the least certain
+ *      cell), ties to the lowest cy * Wd + cx; peaks[i][k] = (cy*s + s/2, cx*s + s/2) in net coordinates and peak_ent[i][k] = its ent; then
+ *      every candidate with max(|dy|, |dx|) < radius leaves (radius 1: the cell alone).  With no candidate left: (-1, -1) and +0.0f.  An
+ *      image's rows are a function of its own ent and mask values only (not of n; no float atomics; P bounded rounds in one workgroup).
+ *      idc_suggest_colors_batch (blocking; replaces nq calls of get_ab_reccs): entry q of out_centres [nq,K,2] / out_conf [nq,K] is bit for bit
+ *      what idc_suggest_colors(h, q.img, q.y, q.x, K, N, q.seed, centres, ...) returns, from one upload, one launch (a workgroup per query)
+ *      and one copy back.  A query with y == -1 && x == -1 is empty: zeros, nothing read -- the row idc_dist_peaks reports when it ran out.
+ *      Both drain the pipelined slots first and only read the distribution.
+ *      idc_forward_async_dist (pipelined) = idc_forward_async_eval -- same sixteen arguments, same slots, idc_wait and idc_pipeline_times --
+ *      with these differences: all three hint modes are accepted; sse may be NULL (no score) as rgb_out may; the distribution head runs, into
+ *      the HANDLE's distribution (d_dist of IDC_FLAG_DIST_HEAD; dist_S of IDC_FLAG_DIST313 with idc_keep_dist on); and after the network the
+ *      slot's compute stream runs, in this order, the entropy kernel, the peaks kernel (IDC_PEAKS_SKIP_HINTS reads the SLOT's own mask plane,
+ *      the one this batch's hints were rasterised into) and the suggestion kernel.  Their results land in slot-owned device memory and leave on
+ *      the copy-out stream: pinned destinations are written in place, pageable ones are filled at idc_wait.  taps->queries name images by their
+ *      index in this batch; with IDC_TAPS_SUGGEST_AT_PEAKS (queries must be NULL) the queries are the n * n_peaks peaks in order, read from the
+ *      device buffer the picker wrote (no visit to the host), peak (i, k) with seed taps->seed + i * n_peaks + k, and Q = n * n_peaks rows come back.
+ *      queries and centres are copied before the call returns.
+ *      ORDERING: the distribution is the handle's, not the slot's.  The taps read it on the one compute stream right behind this batch's network
+ *      and in front of anything enqueued later, so the other slot's network cannot replace it before they have run; what idc_get_dist /
+ *      idc_dist_at / the blocking forms above see after idc_wait is the distribution of the LAST batch enqueued (dist_n = its n), as already
+ *      said for IDC_FLAG_DIST313 handles with idc_keep_dist under idc_forward_async_rgb.
+ *      Status, all decided on the host before anything is enqueued: for the shared arguments the codes of idc_forward_async_eval;
+ *      IDC_ERR_UNSUPPORTED for a handle without a distribution head (neither IDC_FLAG_DIST_HEAD nor IDC_FLAG_DIST313 with idc_keep_dist on), for
+ *      the blocking forms without a resident distribution, and while the range audit is on; IDC_ERR_BATCH for n or a query's img outside the
+ *      resident images (pipelined: outside this batch); IDC_ERR_INVALID_ARG for NULL taps, P outside 0..IDC_PEAKS_MAX (blocking: 1..), with P > 0
+ *      a radius outside 1..max(Hd, Wd), unknown flag bits, NULL peaks with P > 0, IDC_TAPS_SUGGEST_AT_PEAKS with P == 0 or non-NULL queries, a query count
+ *      outside 0..IDC_SUGGEST_MAX_QUERIES (blocking: 1..), a query position outside the image that is not the empty query, K or N outside what
+ *      idc_suggest_colors accepts, NULL centres or outputs while queries exist. */
+enum { IDC_PEAKS_SKIP_HINTS = 1, IDC_TAPS_SUGGEST_AT_PEAKS = 2 };
+#define IDC_PEAKS_MAX 256
+#define IDC_SUGGEST_MAX_QUERIES 4096
+typedef struct idc_dist_query { int32_t img, y, x; uint32_t seed; } idc_dist_query;
+int idc_dist_peaks(idc_handle h, int n, int P, int radius, unsigned flags, int32_t* peaks /*[n,P,2]*/, float* peak_ent /*[n,P] or NULL*/);
+int idc_suggest_colors_batch(idc_handle h, int nq, const idc_dist_query* q, int K, int N, const float* centres,
+                             double* out_centres /*[nq,K,2]*/, double* out_conf /*[nq,K]*/);
+typedef struct idc_dist_taps {
+    int32_t n_peaks, radius; uint32_t flags;             /* n_peaks 0: no peaks */
+    int32_t* peaks; float* peak_ent; float* entropy;     /* [n,P,2]; [n,P] or NULL; [n,Hd,Wd] or NULL */
+    int32_t n_queries; const idc_dist_query* queries;    /* img = index in this batch */
+    int32_t K, N; uint32_t seed; const float* centres;   /* centres [B,2] */
+    double* sugg_centres; double* sugg_conf;             /* [Q,K,2], [Q,K] */
+} idc_dist_taps;
+int idc_forward_async_dist(idc_handle h, int slot, int n, const idc_ref_image* images, const int32_t* hint_offsets, const idc_hint* hints,
+                           int mode, float mask_value, float maskcent, float l_cent, unsigned flags, const idc_batch_refs* refs,
+                           uint8_t* const* rgb_out, float* out_ab, uint64_t* sse, float* hint_colours, const idc_dist_taps* taps);
 
 /* ---- colour picker on the device: replaces data/lab_gamut.py, the host colour maths the GUI runs on every mouse press
  *      (ui/gui_draw.py:11,182-183,195-204; ui/gui_gamut.py:4), in float64 with the constants and operation order of idc_lab2rgb.

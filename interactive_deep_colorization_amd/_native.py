@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = [
     "idc_global_stats_rgb", "idc_set_global_refs", "idc_forward_async_rgb_ref",
     "idc_forward_async_images",
     "idc_reveal_hints", "idc_forward_async_eval",
+    "idc_dist_peaks", "idc_suggest_colors_batch", "idc_forward_async_dist",
     "idc_gamut_map", "idc_snap_colors",
     "idc_set_range_audit", "idc_range_reset", "idc_range_report", "idc_pack_weights_ex", "idc_load_weights_ex",
 ]
@@ -50,6 +51,8 @@ IDC_UNIQUE_ID_BYTES = 128
 IDC_HINT_AB, IDC_HINT_RGB = 0, 1
 IDC_HINT_REVEAL = 2         # idc_reveal_hints / idc_forward_async_eval only
 IDC_DECODE_MODE, IDC_DECODE_MEAN = 0, 1
+IDC_PEAKS_SKIP_HINTS, IDC_TAPS_SUGGEST_AT_PEAKS = 1, 2
+IDC_PEAKS_MAX, IDC_SUGGEST_MAX_QUERIES = 256, 4096
 
 
 class IdcError(RuntimeError):
@@ -78,6 +81,20 @@ class BatchRefs(ctypes.Structure):
     """idc_batch_refs: the six reference arguments of idc_forward_async_rgb_ref, for idc_forward_async_images."""
     _fields_ = [("m", ctypes.c_int32), ("refs", ctypes.POINTER(RefImage)), ("ref_index", ctypes.c_void_p), ("centres", ctypes.c_void_p),
                 ("hist_flag", ctypes.c_float), ("flags", ctypes.c_uint32)]
+
+
+class DistQuery(ctypes.Structure):
+    """idc_dist_query: one suggestion query; (y, x) = (-1, -1) is the empty query."""
+    _fields_ = [("img", ctypes.c_int32), ("y", ctypes.c_int32), ("x", ctypes.c_int32), ("seed", ctypes.c_uint32)]
+
+
+class DistTaps(ctypes.Structure):
+    """idc_dist_taps: what idc_forward_async_dist reads off the distribution behind the network."""
+    _fields_ = [("n_peaks", ctypes.c_int32), ("radius", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("peaks", ctypes.c_void_p), ("peak_ent", ctypes.c_void_p), ("entropy", ctypes.c_void_p),
+                ("n_queries", ctypes.c_int32), ("queries", ctypes.POINTER(DistQuery)),
+                ("K", ctypes.c_int32), ("N", ctypes.c_int32), ("seed", ctypes.c_uint32), ("centres", ctypes.c_void_p),
+                ("sugg_centres", ctypes.c_void_p), ("sugg_conf", ctypes.c_void_p)]
 
 
 class LayerInfo(ctypes.Structure):
@@ -190,6 +207,10 @@ def load():
     proto("idc_reveal_hints", ci, [vp, ci, ci, ctypes.POINTER(Hint), cf, c_float_p])
     proto("idc_forward_async_eval", ci, [vp, ci, ci, ctypes.POINTER(RefImage), vp, vp, ci, cf, cf, cf, ctypes.c_uint,
                                          ctypes.POINTER(BatchRefs), ctypes.POINTER(vp), vp, vp, vp])
+    proto("idc_dist_peaks", ci, [vp, ci, ci, ci, ctypes.c_uint, vp, vp])
+    proto("idc_suggest_colors_batch", ci, [vp, ci, ctypes.POINTER(DistQuery), ci, ci, c_float_p, vp, vp])
+    proto("idc_forward_async_dist", ci, [vp, ci, ci, ctypes.POINTER(RefImage), vp, vp, ci, cf, cf, cf, ctypes.c_uint,
+                                         ctypes.POINTER(BatchRefs), ctypes.POINTER(vp), vp, vp, vp, ctypes.POINTER(DistTaps)])
     proto("idc_gamut_map", ci, [vp, ci, vp, ci, ci, vp, vp, vp])
     proto("idc_snap_colors", ci, [vp, ci, vp, vp, vp, vp, vp])
     proto("idc_set_range_audit", ci, [vp, ci])

@@ -730,6 +730,28 @@ class _DistMaps(object):
             return self._up_nearest(out[0][0]), self._up_nearest(out[1][0])
         return self._up_nearest(out[0])
 
+    def get_uncertain_points(self, P=8, radius=2, skip_hints=False):
+        """Where a hint would tell the model most (not in the reference, whose user reads ``plot_dist_entropy`` by eye): the P points (h, w) of
+        the current image where the predicted distribution's entropy is largest, no two closer than ``radius`` cells of the distribution's
+        grid, (P, 2) int32; rows are (-1, -1) once the image ran out of cells.  ``skip_hints``: not where the input mask is set.  Computed on the
+        device (``idc_dist_peaks``)."""
+        if not self.dist_ab_set:
+            print('Need to set prediction first')
+            return 0
+        return self.net.dist_peaks(1, P=P, radius=radius, skip_hints=skip_hints)[0][0]
+
+    def get_ab_reccs_multi(self, points, K=5, N=25000, return_conf=False):
+        """``get_ab_reccs`` at many points (rows (h, w)) in one device launch (``idc_suggest_colors_batch``): (len(points), K, 2) centres
+        [, (len(points), K) shares].  As in ``get_ab_reccs`` one ``np.random.randint`` seeds it; point q draws with that seed + q, so row 0 is
+        what ``get_ab_reccs`` returns at points[0] from the same RNG state.  A (-1, -1) row gives zeros."""
+        if not self.dist_ab_set:
+            print('Need to set prediction first')
+            return 0
+        seed = int(np.random.randint(0, 2 ** 31 - 1))
+        queries = [(0, int(p[0]), int(p[1]), seed + q) for q, p in enumerate(points)]
+        centers, conf = self.net.suggest_colors_batch(queries, self._bin_centres(), K=K, N_draws=N)
+        return (centers, conf) if return_conf else centers
+
     def get_img_dist_decode(self, mode='mode', gamma=1.0):
         """``get_dist_decode`` as an image: (Xd, Xd, 3) uint8 with the L plane of the current image.  The colour step
         borrows the engine's staging, so afterwards the display getters take their host route until the next forward."""

@@ -1,5 +1,6 @@
 // idc_api.hip -- the handle and what a caller does with it besides weights and forwards (C ABI, include/ideepcolor.h): create / destroy, the last-error
-// string (fail), I/O scales, global hints, the click session, Lab -> RGB, colour suggestions and distributions, the global histogram, reference-image global hints (blocking forms), stream
+// string (fail), I/O scales, global hints, the click session, Lab -> RGB, colour suggestions and distributions (one pixel, batches, uncertainty peaks: the
+// checks and launches the pipelined idc_forward_async_dist shares are here too), the global histogram, reference-image global hints (blocking forms), stream
 // ordering, the display upsample, image ingestion (uint8 RGB in, full-resolution RGB out) and the colour picker (gamut map, colour snapping).
 #include <stdarg.h>
 #include <stdio.h>
@@ -100,6 +101,76 @@ void drop_source(idc_context* h, int slot) {
     auto& sl = h->src[slot];
     sl.d_rgb.reset();                                    // (freeing waits for the device: nothing that reads it is in flight after that)
     sl.h = sl.w = 0;
+}
+
+// ---------------------------------------------------------------------------------------------- distribution taps
+static size_t taps_align(size_t x) { return (x + 15) & ~(size_t)15; }
+
+bool dist_geom(const idc_context* c, DistGeom* g) {
+    if (c->flags & IDC_FLAG_DIST313) {
+        if (!c->keep_dist313) return false;
+        g->B = 313; g->Hd = c->H; g->Wd = c->W; g->s = 1; g->dist = c->d_dist313.get();
+        return true;
+    }
+    if (!(c->flags & IDC_FLAG_DIST_HEAD)) return false;
+    g->B = 529; g->Hd = c->H / 4; g->Wd = c->W / 4; g->s = 4; g->dist = c->d_dist.get();
+    return true;
+}
+
+int check_taps(idc_context* c, const DistGeom& g, int n, int p_min, int q_min, const idc_dist_taps* taps, TapsLayout* lay) {
+    if (!taps) return fail(&c->err, IDC_ERR_INVALID_ARG, "null taps");
+    const int P = taps->n_peaks;
+    if (P < p_min || P > IDC_PEAKS_MAX) return fail(&c->err, IDC_ERR_INVALID_ARG, "%d peaks outside %d..%d", P, p_min, IDC_PEAKS_MAX);
+    if (taps->flags & ~(unsigned)(IDC_PEAKS_SKIP_HINTS | IDC_TAPS_SUGGEST_AT_PEAKS)) return fail(&c->err, IDC_ERR_INVALID_ARG, "unknown taps flag bits 0x%x", taps->flags);
+    if (P > 0) {
+        const int rmax = g.Hd > g.Wd ? g.Hd : g.Wd;
+        if (taps->radius < 1 || taps->radius > rmax) return fail(&c->err, IDC_ERR_INVALID_ARG, "radius %d outside 1..%d", taps->radius, rmax);
+        if (!taps->peaks) return fail(&c->err, IDC_ERR_INVALID_ARG, "null peaks");
+    }
+    const bool at_peaks = (taps->flags & IDC_TAPS_SUGGEST_AT_PEAKS) != 0;
+    if (at_peaks && (P == 0 || taps->queries)) return fail(&c->err, IDC_ERR_INVALID_ARG, "IDC_TAPS_SUGGEST_AT_PEAKS needs peaks and a NULL query list");
+    const long long Q = at_peaks ? (long long)n * P : (long long)taps->n_queries;
+    if ((!at_peaks && taps->n_queries < q_min) || Q < 0 || Q > IDC_SUGGEST_MAX_QUERIES)
+        return fail(&c->err, IDC_ERR_INVALID_ARG, "%lld queries outside %d..%d", Q, q_min, IDC_SUGGEST_MAX_QUERIES);
+    if (Q > 0) {
+        if (taps->K < 1 || taps->K > kSuggestMaxK) return fail(&c->err, IDC_ERR_INVALID_ARG, "K %d outside 1..%d", taps->K, kSuggestMaxK);
+        if (taps->N < 1) return fail(&c->err, IDC_ERR_INVALID_ARG, "N must be positive");
+        if (!taps->centres || !taps->sugg_centres || !taps->sugg_conf) return fail(&c->err, IDC_ERR_INVALID_ARG, "null pointer");
+        if (!at_peaks && !taps->queries) return fail(&c->err, IDC_ERR_INVALID_ARG, "null queries");
+        for (int q = 0; !at_peaks && q < (int)Q; ++q) {
+            const idc_dist_query& u = taps->queries[q];
+            if (u.img < 0 || u.img >= n) return fail(&c->err, IDC_ERR_BATCH, "query %d: image %d outside 0..%d", q, u.img, n - 1);
+            if (u.y == -1 && u.x == -1) continue;
+            if (u.y < 0 || u.y >= c->H || u.x < 0 || u.x >= c->W) return fail(&c->err, IDC_ERR_INVALID_ARG, "query %d: pixel (%d,%d) outside the image", q, u.y, u.x);
+        }
+    }
+    const size_t npix = (size_t)g.Hd * g.Wd;
+    lay->n = n; lay->P = P; lay->Q = (int)Q; lay->K = Q > 0 ? taps->K : 0; lay->at_peaks = at_peaks; lay->want_ent = taps->entropy != nullptr;
+    lay->i_centres = taps_align(at_peaks ? 0 : (size_t)Q * sizeof(DistQuery));
+    lay->in_bytes = lay->i_centres + (Q > 0 ? taps_align((size_t)g.B * 2 * sizeof(float)) : 0);
+    lay->o_ent = 0;
+    lay->o_work = taps_align((P > 0 || lay->want_ent) ? (size_t)n * npix * sizeof(float) : 0);
+    lay->o_peaks = lay->o_work + taps_align(P > 0 ? (size_t)n * npix * sizeof(float) : 0);
+    lay->o_pent = lay->o_peaks + taps_align((size_t)n * P * 2 * sizeof(int));
+    lay->o_sc = lay->o_pent + taps_align((size_t)n * P * sizeof(float));
+    lay->o_sf = lay->o_sc + taps_align((size_t)lay->Q * lay->K * 2 * sizeof(double));
+    lay->out_bytes = lay->o_sf + taps_align((size_t)lay->Q * lay->K * sizeof(double));
+    return IDC_OK;
+}
+
+int launch_taps(idc_context* c, const DistGeom& g, const TapsLayout& lay, const idc_dist_taps* taps, const float* mask, const unsigned char* in,
+                unsigned char* out, hipStream_t s) {
+    float* ent = (float*)(out + lay.o_ent);
+    int* peaks = (int*)(out + lay.o_peaks);
+    if (lay.P > 0 || lay.want_ent) HIPCHK(c, launch_dist_entropy(g.dist, lay.n, g.B, g.Hd * g.Wd, ent, s));
+    if (lay.P > 0)
+        HIPCHK(c, launch_dist_peaks(ent, (taps->flags & IDC_PEAKS_SKIP_HINTS) ? mask : nullptr, lay.n, g.Hd, g.Wd, g.s, lay.P, taps->radius,
+                                    (float*)(out + lay.o_work), peaks, (float*)(out + lay.o_pent), s));
+    if (lay.Q > 0)
+        HIPCHK(c, launch_suggest_batch(g.dist, lay.n, g.B, g.Hd, g.Wd, g.s, lay.at_peaks ? nullptr : (const DistQuery*)in, lay.at_peaks ? peaks : nullptr,
+                                       lay.P, taps->seed, lay.Q, (const float*)(in + lay.i_centres), lay.K, taps->N, (double*)(out + lay.o_sc),
+                                       (double*)(out + lay.o_sf), s));
+    return IDC_OK;
 }
 
 }  // namespace idc
@@ -471,6 +542,57 @@ int idc_dist_decode(idc_handle h, int n, int mode, float gamma, const float* cen
     HIPCHK(h, hipMemcpy(ab, h->d_map_ab.get(), (size_t)n * 2 * npix * 4, hipMemcpyDeviceToHost));
     if (conf) HIPCHK(h, hipMemcpy(conf, h->d_map_s.get(), (size_t)n * npix * 4, hipMemcpyDeviceToHost));
     return IDC_OK;
+}
+
+// The blocking forms of the distribution taps, on the handle's own blocks: checks, [one upload], the launches of launch_taps, one copy back
+static int run_taps_blocking(idc_context* h, int n, int p_min, int q_min, const idc_dist_taps* taps) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    DistGeom g;
+    if (!dist_geom(h, &g) || h->dist_n <= 0) return fail(&h->err, IDC_ERR_UNSUPPORTED, "Need to set prediction first (no resident distribution)");
+    if (n <= 0 || n > h->dist_n) return fail(&h->err, IDC_ERR_BATCH, "batch %d outside 1..%d", n, h->dist_n);
+    TapsLayout lay;
+    int rc = check_taps(h, g, n, p_min, q_min, taps, &lay);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    rc = drain_pipeline(h);
+    if (rc) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+    const size_t o_out = taps_align(lay.in_bytes), total = o_out + lay.out_bytes, res0 = lay.o_peaks;       // the entropy and work maps stay on the device
+    HIPCHK(h, h->d_taps.ensure(total, 65536));
+    HIPCHK(h, h->h_taps.ensure(total, 65536));
+    if (lay.Q > 0) {
+        memcpy(h->h_taps.get(), taps->queries, (size_t)lay.Q * sizeof(DistQuery));
+        memcpy(h->h_taps.get() + lay.i_centres, taps->centres, (size_t)g.B * 2 * sizeof(float));
+        HIPCHK(h, hipMemcpyAsync(h->d_taps.get(), h->h_taps.get(), lay.in_bytes, hipMemcpyHostToDevice, h->stream.get()));
+    }
+    rc = launch_taps(h, g, lay, taps, h->d_mask.get(), h->d_taps.get(), h->d_taps.get() + o_out, h->stream.get());
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->h_taps.get() + o_out + res0, h->d_taps.get() + o_out + res0, lay.out_bytes - res0, hipMemcpyDeviceToHost, h->stream.get()));
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+    const unsigned char* res = h->h_taps.get() + o_out;
+    if (lay.P > 0) {
+        memcpy(taps->peaks, res + lay.o_peaks, (size_t)n * lay.P * 2 * sizeof(int));
+        if (taps->peak_ent) memcpy(taps->peak_ent, res + lay.o_pent, (size_t)n * lay.P * sizeof(float));
+    }
+    if (lay.Q > 0) {
+        memcpy(taps->sugg_centres, res + lay.o_sc, (size_t)lay.Q * lay.K * 2 * sizeof(double));
+        memcpy(taps->sugg_conf, res + lay.o_sf, (size_t)lay.Q * lay.K * sizeof(double));
+    }
+    return IDC_OK;
+}
+
+int idc_dist_peaks(idc_handle h, int n, int P, int radius, unsigned flags, int32_t* peaks, float* peak_ent) {
+    if (flags & ~(unsigned)IDC_PEAKS_SKIP_HINTS) return fail(h ? &h->err : nullptr, IDC_ERR_INVALID_ARG, "unknown flag bits 0x%x", flags);
+    idc_dist_taps taps = {};
+    taps.n_peaks = P; taps.radius = radius; taps.flags = flags; taps.peaks = peaks; taps.peak_ent = peak_ent;
+    return run_taps_blocking(h, n, 1, 0, &taps);
+}
+
+int idc_suggest_colors_batch(idc_handle h, int nq, const idc_dist_query* q, int K, int N, const float* centres, double* out_centres,
+                             double* out_conf) {
+    idc_dist_taps taps = {};
+    taps.n_queries = nq; taps.queries = q; taps.K = K; taps.N = N; taps.centres = centres; taps.sugg_centres = out_centres; taps.sugg_conf = out_conf;
+    return run_taps_blocking(h, h ? (h->dist_n > 0 ? h->dist_n : 1) : 1, 0, 1, &taps);
 }
 
 int idc_global_histogram(idc_handle h, int n, const uint8_t* rgb, const float* centres, float* hist, float* s_avg) {

@@ -190,6 +190,10 @@ struct idc_context {
     PinnedMem<unsigned char> h_reveal;   // ... and their pinned copy
     DevMem<float> d_centres; DevMem<double> d_sugg; DevMem<unsigned> d_sugg_counts;   // colour suggestions
     DevMem<float> d_map_ab, d_map_s;     // idc_dist_decode / idc_dist_entropy results: [max_batch][2][npix], [max_batch][npix] (first use)
+    // idc_dist_peaks / idc_suggest_colors_batch: one device block and one pinned block per call (the picker's work map, peaks and peak_ent; the
+    // queries and centres in, the suggestions out), grown on demand: both calls block, so nothing is in flight when they grow
+    DevMem<unsigned char> d_taps;
+    PinnedMem<unsigned char> h_taps;
     std::vector<char> l_set;             // per image slot: d_L holds an uploaded L plane (idc_forward_resident refuses otherwise)
     // image ingestion (idc_set_image_rgb / idc_fullres_rgb): per slot the uint8 source kept on the device (IDC_INGEST_KEEP_SOURCE; empty = none)
     // and its size, and the mask_value of the slot's last idc_set_hints (0 = never had hints)
@@ -237,6 +241,12 @@ struct idc_context {
         DevMem<unsigned char> d_truth, d_eval;
         PinnedMem<unsigned char> h_eval;
         std::vector<StagedOut> eval_outs;
+        // idc_forward_async_dist: the taps' inputs (queries, centres: pinned and device), and one device block for what they produce -- the entropy
+        // map, the picker's work map, peaks, peak_ent, suggestions (TapsLayout) -- with its pinned twin, where a pageable destination waits at the
+        // same offset until idc_wait copies it out (taps_outs; empty after every other call)
+        DevMem<unsigned char> d_taps_in, d_taps;
+        PinnedMem<unsigned char> h_taps_in, h_taps;
+        std::vector<StagedOut> taps_outs;
         // idc_forward_async_rgb_ref: the batch's references and the slot's OWN [max_batch][316] global inputs (the handle's d_glob_in is not touched)
         RefStage ref;
         DevMem<float> d_glob_in;
@@ -325,6 +335,20 @@ int stage_refs(idc_context* c, idc_context::RefStage& st, const RefLayout& lay, 
 int upload_refs(idc_context* c, idc_context::RefStage& st, const RefLayout& lay, hipStream_t copy);
 int launch_refs(idc_context* c, idc_context::RefStage& st, const RefLayout& lay, float hist_flag, unsigned ref_flags, float* rows, bool want_hist,
                 hipStream_t s);
+// distribution taps (idc_dist_peaks / idc_suggest_colors_batch / idc_forward_async_dist): the geometry of the handle's distribution, every check of
+// include/ideepcolor.h's table on the host, and where each part sits in the input and result blocks (byte offsets, 16-byte aligned)
+struct DistGeom { int B = 0, Hd = 0, Wd = 0, s = 1; const float* dist = nullptr; };
+struct TapsLayout {
+    int n = 0, P = 0, Q = 0, K = 0;      // Q: suggestion rows (the query count, or n * P at the peaks)
+    bool at_peaks = false, want_ent = false;
+    size_t i_centres = 0, in_bytes = 0;                                        // input block: DistQuery[n_queries], then centres float[B][2]
+    size_t o_ent = 0, o_work = 0, o_peaks = 0, o_pent = 0, o_sc = 0, o_sf = 0, out_bytes = 0;
+};
+bool dist_geom(const idc_context* c, DistGeom* g);       // false: the handle has no distribution head that writes a distribution
+int check_taps(idc_context* c, const DistGeom& g, int n, int p_min, int q_min, const idc_dist_taps* taps, TapsLayout* lay);
+// on `s`: [entropy] [peaks, mask = the planes IDC_PEAKS_SKIP_HINTS reads] [suggestions] from `in` (device input block) into `out` (device result block)
+int launch_taps(idc_context* c, const DistGeom& g, const TapsLayout& lay, const idc_dist_taps* taps, const float* mask, const unsigned char* in,
+                unsigned char* out, hipStream_t s);
 int check_chain_abort(idc_context* c);
 int check_forward_args(idc_context* c, int n);
 hipError_t wait_stream(idc_context* c, int n);

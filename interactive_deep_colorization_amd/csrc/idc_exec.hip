@@ -360,6 +360,7 @@ static int wait_slot(idc_context* h, int slot) {
     if (sl.staged_out && sl.user_out) memcpy(sl.user_out, sl.h_out.get(), (size_t)sl.n * h->H * h->W * 2 * 4);
     for (const auto& o : sl.staged_outs) memcpy(o.user, sl.h_rgb.get() + o.at, o.bytes);
     for (const auto& o : sl.eval_outs) memcpy(o.user, sl.h_eval.get() + o.at, o.bytes);
+    for (const auto& o : sl.taps_outs) memcpy(o.user, sl.h_taps.get() + o.at, o.bytes);
     return IDC_OK;
 }
 
@@ -613,7 +614,7 @@ int idc_forward_async(idc_handle h, int slot, int n, const float* L_mc, const fl
     HIPCHK(h, hipMemcpyAsync(sl.staged_out ? sl.h_out.get() : out_ab, sl.d_out.get(), (size_t)n * hw * 2 * 4, hipMemcpyDeviceToHost, h->s_out.get()));
     HIPCHK(h, hipEventRecord(sl.ev_out.get(), h->s_out.get()));
     sl.pending = true; sl.timed = true; sl.user_out = out_ab; sl.n = n;
-    sl.staged_outs.clear(); sl.eval_outs.clear();
+    sl.staged_outs.clear(); sl.eval_outs.clear(); sl.taps_outs.clear();
     return IDC_OK;
 }
 
@@ -631,8 +632,9 @@ struct BatchIO {
     int src_h, src_w; const uint8_t* rgb_in; uint8_t* rgb_out;
     const idc_ref_image* images; uint8_t* const* outs;
 };
-// idc_forward_async_eval's own arguments (ev == nullptr: every other entry point): the score is required, the revealed colours are optional
-struct EvalArgs { uint64_t* sse; float* hint_colours; };
+// idc_forward_async_eval's own arguments (ev == nullptr: every other entry point): the score is required, the revealed colours are optional.
+// idc_forward_async_dist brings both and its taps (taps_call: taps itself may be NULL, which is refused); there the score is optional too
+struct EvalArgs { uint64_t* sse; float* hint_colours; bool taps_call = false; const idc_dist_taps* taps = nullptr; };
 // One host buffer of a call and the bytes of the slot's packed device array it fills (in) or receives (out)
 struct Piece { const uint8_t* in; uint8_t* out; size_t in_at, in_bytes, out_at, out_bytes; bool in_pinned, out_pinned; };
 
@@ -673,7 +675,8 @@ static int forward_async_rgb(idc_handle h, int slot, int n, const BatchIO& io, c
     if (ragged ? (!io.images || !(io.outs || ev)) : (!io.rgb_in || !io.rgb_out)) return fail(&h->err, IDC_ERR_INVALID_ARG, "null image pointer");
     if (flags & ~(unsigned)IDC_BATCH_OUT_SOURCE) return fail(&h->err, IDC_ERR_INVALID_ARG, "unknown flag bits 0x%x", flags);
     if (mode != IDC_HINT_AB && mode != IDC_HINT_RGB && !reveal) return fail(&h->err, IDC_ERR_INVALID_ARG, "hint mode %d", mode);
-    if (ev && !ev->sse) return fail(&h->err, IDC_ERR_INVALID_ARG, "null sse");
+    const bool dist = ev && ev->taps_call;
+    if (ev && !ev->sse && !dist) return fail(&h->err, IDC_ERR_INVALID_ARG, "null sse");
     if (ev && ev->hint_colours && !reveal) return fail(&h->err, IDC_ERR_INVALID_ARG, "hint_colours with hint mode %d: only IDC_HINT_REVEAL reveals colours", mode);
     size_t in_bytes = 0;
     if (ragged) {
@@ -727,6 +730,14 @@ static int forward_async_rgb(idc_handle h, int slot, int n, const BatchIO& io, c
         if (rc) return rc;
         if (!(h->flags & IDC_FLAG_GLOBAL_HINTS)) return fail(&h->err, IDC_ERR_UNSUPPORTED, "handle was created without IDC_FLAG_GLOBAL_HINTS");
     }
+    DistGeom geom;
+    TapsLayout tl;
+    if (dist) {
+        if (!dist_geom(h, &geom))
+            return fail(&h->err, IDC_ERR_UNSUPPORTED, "handle has no distribution head (IDC_FLAG_DIST_HEAD, or IDC_FLAG_DIST313 with idc_keep_dist on)");
+        rc = check_taps(h, geom, n, 0, 0, ev->taps, &tl);
+        if (rc) return rc;
+    }
     if (h->audit) return fail(&h->err, IDC_ERR_UNSUPPORTED, "the range audit covers the blocking, resident and device-pointer forwards, not the pipelined slots");
     auto& sl = h->pipe[slot];
     if (sl.pending) return fail(&h->err, IDC_ERR_INVALID_ARG, "slot %d is still in flight: idc_wait it first", slot);
@@ -756,6 +767,16 @@ static int forward_async_rgb(idc_handle h, int slot, int n, const BatchIO& io, c
         if (!source_out) HIPCHK(h, sl.d_truth.ensure(nb * hw * 3));
         HIPCHK(h, sl.d_eval.ensure(cols_at + cols_bytes, cols_at + 4096));
         HIPCHK(h, sl.h_eval.ensure(cols_at + cols_bytes, cols_at + 4096));
+    }
+    if (dist) {     // the taps' queries and centres travel with the batch; their results wait in the slot's block
+        HIPCHK(h, sl.d_taps_in.ensure(tl.in_bytes, 65536));
+        HIPCHK(h, sl.h_taps_in.ensure(tl.in_bytes, 65536));
+        HIPCHK(h, sl.d_taps.ensure(tl.out_bytes, 65536));
+        HIPCHK(h, sl.h_taps.ensure(tl.out_bytes, 65536));
+        if (tl.Q > 0) {
+            if (!tl.at_peaks) memcpy(sl.h_taps_in.get(), ev->taps->queries, (size_t)tl.Q * sizeof(DistQuery));
+            memcpy(sl.h_taps_in.get() + tl.i_centres, ev->taps->centres, (size_t)geom.B * 2 * sizeof(float));
+        }
     }
     // every host buffer is judged on its own: pageable sources are copied into the slot's pinned staging here, on the calling thread
     std::vector<Piece> pieces;
@@ -806,6 +827,7 @@ static int forward_async_rgb(idc_handle h, int slot, int n, const BatchIO& io, c
     HIPCHK(h, hipEventRecord(sl.ev_in0.get(), h->s_in.get()));
     HIPCHK(h, copy_pieces(pieces, true, sl.d_src.get(), sl.h_src.get(), h->s_in.get()));
     HIPCHK(h, hipMemcpyAsync(sl.d_meta.get(), sl.h_meta.get(), meta_bytes, hipMemcpyHostToDevice, h->s_in.get()));
+    if (dist && tl.Q > 0) HIPCHK(h, hipMemcpyAsync(sl.d_taps_in.get(), sl.h_taps_in.get(), tl.in_bytes, hipMemcpyHostToDevice, h->s_in.get()));
     if (ra) {
         rc = upload_refs(h, sl.ref, lay, h->s_in.get());
         if (rc) return rc;
@@ -834,16 +856,18 @@ static int forward_async_rgb(idc_handle h, int slot, int n, const BatchIO& io, c
         HIPCHK(h, launch_batch_prologue(sl.d_src.get(), n, io.src_h, io.src_w, h->H, h->W, l_cent, d_offs, d_hints, mode, mask_value, sl.d_L.get(),
                                         sl.d_ab.get(), sl.d_mask.get(), h->stream.get()));
     const int dist_n = h->dist_n;
-    rc = run_graph(h, n, sl.d_L.get(), sl.d_ab.get(), sl.d_mask.get(), maskcent, sl.d_out.get(), nullptr, ra ? sl.d_glob_in.get() : h->d_glob_in.get());
+    // a distribution batch runs model_class into the HANDLE's distribution (the 313 head with idc_keep_dist writes dist_S on every forward anyway)
+    rc = run_graph(h, n, sl.d_L.get(), sl.d_ab.get(), sl.d_mask.get(), maskcent, sl.d_out.get(),
+                   (dist && !(h->flags & IDC_FLAG_DIST313)) ? h->d_dist.get() : nullptr, ra ? sl.d_glob_in.get() : h->d_glob_in.get());
     if (rc) return rc;
-    if (!((h->flags & IDC_FLAG_DIST313) && h->keep_dist313)) h->dist_n = dist_n;      // no distribution was written: the blocking forward's stays resident
+    if (!dist && !((h->flags & IDC_FLAG_DIST313) && h->keep_dist313)) h->dist_n = dist_n;      // no distribution was written: the blocking forward's stays resident
     HIPCHK(h, launch_lab_post(sl.d_L.get(), l_cent, sl.d_out.get(), sl.d_rgb.get(), source_out ? sl.d_labq.get() : nullptr, n, h->H, h->W, h->stream.get()));
     if (source_out && ragged)
         HIPCHK(h, launch_ragged_fullres_rgb(sl.d_src.get(), d_tab, n, (long long)(in_bytes / 3), sl.d_labq.get(), h->H, h->W, IDC_INTERP_LINEAR,
                                             sl.d_full.get(), h->stream.get()));
     else if (source_out)
         HIPCHK(h, launch_batch_fullres_rgb(sl.d_src.get(), n, io.src_h, io.src_w, sl.d_labq.get(), h->H, h->W, IDC_INTERP_LINEAR, sl.d_full.get(), h->stream.get()));
-    if (ev) {       // the score: the source-size result against the source bytes, or the net-size result against the net-size ground truth
+    if (ev && ev->sse) {       // the score: the source-size result against the source bytes, or the net-size result against the net-size ground truth
         unsigned long long* d_sse = (unsigned long long*)sl.d_eval.get();
         HIPCHK(h, hipMemsetAsync(d_sse, 0, (size_t)n * 3 * sizeof(uint64_t), h->stream.get()));
         if (source_out) {
@@ -855,15 +879,35 @@ static int forward_async_rgb(idc_handle h, int slot, int n, const BatchIO& io, c
             HIPCHK(h, launch_eval_sse(sl.d_rgb.get(), sl.d_truth.get(), nullptr, n, (long long)hw, (long long)hw, (long long)n * hw, d_sse, h->stream.get()));
         }
     }
+    if (dist) {     // entropy, peaks, suggestions: on this stream behind this batch's network, so in front of whatever replaces the handle's distribution next
+        rc = launch_taps(h, geom, tl, ev->taps, sl.d_mask.get(), sl.d_taps_in.get(), sl.d_taps.get(), h->stream.get());
+        if (rc) return rc;
+    }
     HIPCHK(h, hipEventRecord(sl.ev_comp.get(), h->stream.get()));
     HIPCHK(h, hipStreamWaitEvent(h->s_out.get(), sl.ev_comp.get(), 0));
     HIPCHK(h, hipEventRecord(sl.ev_out0.get(), h->s_out.get()));
-    sl.eval_outs.clear();
+    sl.eval_outs.clear(); sl.taps_outs.clear();
+    if (dist) {
+        const idc_dist_taps* tp = ev->taps;
+        const size_t npix = (size_t)geom.Hd * geom.Wd;
+        const struct { void* user; size_t at, bytes; } outs[] = {
+            {tp->entropy, tl.o_ent, (size_t)n * npix * sizeof(float)},
+            {tl.P > 0 ? tp->peaks : nullptr, tl.o_peaks, (size_t)n * tl.P * 2 * sizeof(int)},
+            {tl.P > 0 ? tp->peak_ent : nullptr, tl.o_pent, (size_t)n * tl.P * sizeof(float)},
+            {tl.Q > 0 ? tp->sugg_centres : nullptr, tl.o_sc, (size_t)tl.Q * tl.K * 2 * sizeof(double)},
+            {tl.Q > 0 ? tp->sugg_conf : nullptr, tl.o_sf, (size_t)tl.Q * tl.K * sizeof(double)}};
+        for (const auto& o : outs) {
+            if (!o.user || !o.bytes) continue;
+            const bool direct = is_pinned(o.user);
+            HIPCHK(h, hipMemcpyAsync(direct ? o.user : (void*)(sl.h_taps.get() + o.at), sl.d_taps.get() + o.at, o.bytes, hipMemcpyDeviceToHost, h->s_out.get()));
+            if (!direct) sl.taps_outs.push_back({(uint8_t*)o.user, o.at, o.bytes});
+        }
+    }
     if (ev) {
         const size_t sse_bytes = (size_t)n * 3 * sizeof(uint64_t);
-        const bool sse_direct = is_pinned(ev->sse), cols_direct = cols_bytes && is_pinned(ev->hint_colours);
-        HIPCHK(h, hipMemcpyAsync(sse_direct ? (void*)ev->sse : (void*)sl.h_eval.get(), sl.d_eval.get(), sse_bytes, hipMemcpyDeviceToHost, h->s_out.get()));
-        if (!sse_direct) sl.eval_outs.push_back({(uint8_t*)ev->sse, 0, sse_bytes});
+        const bool sse_direct = ev->sse && is_pinned(ev->sse), cols_direct = cols_bytes && is_pinned(ev->hint_colours);
+        if (ev->sse) HIPCHK(h, hipMemcpyAsync(sse_direct ? (void*)ev->sse : (void*)sl.h_eval.get(), sl.d_eval.get(), sse_bytes, hipMemcpyDeviceToHost, h->s_out.get()));
+        if (ev->sse && !sse_direct) sl.eval_outs.push_back({(uint8_t*)ev->sse, 0, sse_bytes});
         if (cols_bytes) {
             HIPCHK(h, hipMemcpyAsync(cols_direct ? (void*)ev->hint_colours : (void*)(sl.h_eval.get() + cols_at), sl.d_eval.get() + cols_at, cols_bytes,
                                      hipMemcpyDeviceToHost, h->s_out.get()));
@@ -911,6 +955,16 @@ int idc_forward_async_eval(idc_handle h, int slot, int n, const idc_ref_image* i
                            uint8_t* const* rgb_out, float* out_ab, uint64_t* sse, float* hint_colours) {
     const BatchIO io = {true, 0, 0, nullptr, nullptr, images, rgb_out};
     const EvalArgs ev = {sse, hint_colours};
+    if (!refs) return forward_async_rgb(h, slot, n, io, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, nullptr, out_ab, &ev);
+    const RefArgs ra = {refs->m, refs->refs, refs->ref_index, refs->centres, refs->hist_flag, refs->flags};
+    return forward_async_rgb(h, slot, n, io, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, &ra, out_ab, &ev);
+}
+
+int idc_forward_async_dist(idc_handle h, int slot, int n, const idc_ref_image* images, const int32_t* hint_offsets, const idc_hint* hints,
+                           int mode, float mask_value, float maskcent, float l_cent, unsigned flags, const idc_batch_refs* refs,
+                           uint8_t* const* rgb_out, float* out_ab, uint64_t* sse, float* hint_colours, const idc_dist_taps* taps) {
+    const BatchIO io = {true, 0, 0, nullptr, nullptr, images, rgb_out};
+    const EvalArgs ev = {sse, hint_colours, true, taps};
     if (!refs) return forward_async_rgb(h, slot, n, io, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, nullptr, out_ab, &ev);
     const RefArgs ra = {refs->m, refs->refs, refs->ref_index, refs->centres, refs->hist_flag, refs->flags};
     return forward_async_rgb(h, slot, n, io, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, &ra, out_ab, &ev);

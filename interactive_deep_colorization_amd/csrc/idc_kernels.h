@@ -331,6 +331,13 @@ hipError_t launch_eval_sse(const unsigned char* res, const unsigned char* truth,
 constexpr int kSuggestMaxBins = 1024, kSuggestMaxK = 16;
 hipError_t launch_suggest(const float* pdf, long long stride, int B, const float* centres, int K, int N, unsigned seed,
                           double* out_centres, double* out_conf, unsigned* out_counts, hipStream_t s);
+// The same body for nq queries in one launch (workgroup = query): dist [n][B][Hd][Wd], s = 4 (529 head) or 1 (313 head); queries [nq], or
+// peaks != nullptr: query q = peak q of dist_peaks' [n][P][2] buffer, image q / P, seed seed0 + q.  out_centres [nq][K][2], out_conf [nq][K]; the
+// empty query (-1, -1) and anything outside the batch or the image write zeros.
+struct DistQuery { int img, y, x; unsigned seed; };
+hipError_t launch_suggest_batch(const float* dist, int n, int B, int Hd, int Wd, int s, const DistQuery* queries, const int* peaks, int P,
+                                unsigned seed0, int nq, const float* centres, int K, int N, double* out_centres, double* out_conf,
+                                hipStream_t st);
 
 // Maps of the resident distribution dist [n][B][npix] (idc_session.hip): ent [n][npix] = sum_q p log p (fp64 sum, p == 0 -> 0);
 // decode -> ab [n][2][npix] and conf [n][npix] = p_max (or nullptr): mode 0 the arg-max bin's centre (ties -> lowest bin), mode 1
@@ -338,6 +345,11 @@ hipError_t launch_suggest(const float* pdf, long long stride, int B, const float
 hipError_t launch_dist_entropy(const float* dist, int n, int B, int npix, float* ent, hipStream_t s);
 hipError_t launch_dist_decode(const float* dist, int n, int B, int npix, int mode, float gamma, const float* centres, float* ab,
                               float* conf, hipStream_t s);
+// Uncertainty peaks of the entropy map ent [n][Hd][Wd] (launch_dist_entropy's): P rounds of "smallest ent, ties -> lowest cell index, then every
+// cell with max(|dy|, |dx|) < radius leaves" per image, cells under a non-zero s x s block of mask [n][Hd*s][Wd*s] (or nullptr) left out;
+// peaks [n][P][2] = (cy*s + s/2, cx*s + s/2) or (-1, -1), peak_ent [n][P] (or nullptr); work [n][Hd*Wd] floats of scratch.
+hipError_t launch_dist_peaks(const float* ent, const float* mask, int n, int Hd, int Wd, int s, int P, int radius, float* work, int* peaks,
+                             float* peak_ent, hipStream_t st);
 
 // Range audit (idc_audit.hip; idc_set_range_audit): one layer's sticky record in device memory, and the streaming reduction that folds a stored
 // tensor into it -- npix pixels of [parts][Cpad] 16-bit values (bf16, or fp16 when f16; value = sum of the parts) or, parts = 0, of [Cpad] fp32;

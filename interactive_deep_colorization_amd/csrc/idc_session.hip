@@ -11,6 +11,9 @@
 //    545-546) and a mode / sharpened-mean decode of the classifier's belief (what pred_ab does for the 313 net, prototxt
 //    :826-850), as one streaming pass each over the resident distribution instead of a copy of it to the host.
 //
+//  * distribution batches -- get_ab_reccs for many pixels in one launch (suggest_batch_kernel: the same body, a workgroup per query) and the
+//    question compute_entropy's map is plotted for, "where is the model least sure", answered on the device (dist_peaks_kernel).
+//
 // The first two are latency kernels (one pixel per thread / one workgroup); neither touches HBM beyond the planes it writes.
 #include <hip/hip_runtime.h>
 
@@ -90,10 +93,10 @@ __device__ __forceinline__ unsigned lowbias32(unsigned x) {
     return x;
 }
 
-__global__ __launch_bounds__(256) void suggest_kernel(const float* __restrict__ pdf, long long stride, int B,
-                                                      const float* __restrict__ centres, int K, int N, unsigned seed,
-                                                      double* __restrict__ out_centres, double* __restrict__ out_conf,
-                                                      unsigned* __restrict__ out_counts) {
+__device__ __forceinline__ void suggest_body(const float* __restrict__ pdf, long long stride, int B,
+                                             const float* __restrict__ centres, int K, int N, unsigned seed,
+                                             double* __restrict__ out_centres, double* __restrict__ out_conf,
+                                             unsigned* __restrict__ out_counts) {
 #pragma clang fp contract(off)
     __shared__ float cmf[kSuggestMaxBins];
     __shared__ unsigned cnt[kSuggestMaxBins];
@@ -199,6 +202,44 @@ __global__ __launch_bounds__(256) void suggest_kernel(const float* __restrict__ 
     }
 }
 
+__global__ __launch_bounds__(256) void suggest_kernel(const float* __restrict__ pdf, long long stride, int B,
+                                                      const float* __restrict__ centres, int K, int N, unsigned seed,
+                                                      double* __restrict__ out_centres, double* __restrict__ out_conf,
+                                                      unsigned* __restrict__ out_counts) {
+    suggest_body(pdf, stride, B, centres, K, N, seed, out_centres, out_conf, out_counts);
+}
+
+// The same body for a batch: workgroup q serves query q = {img, y, x, seed} -- from the list, or (peaks != nullptr) peak q of dist_peaks_kernel's
+// [n][P][2] buffer with img = q / P and seed = seed0 + q, read where the picker left it -- and finds its pdf by idc_dist_at's rule: cell
+// (y / s, x / s) of dist [n][B][Hd][Wd], s = 4 for the 529 head at H/4, 1 for the 313 head.  Query q writes out_centres [q][K][2] and out_conf [q][K].
+// The empty query (-1, -1) reads nothing and writes zeros; so does a query outside the batch or the image (the host refuses those: this keeps a
+// stray index from reaching memory).  The test is uniform over the workgroup, in front of every barrier.
+__global__ __launch_bounds__(256) void suggest_batch_kernel(const float* __restrict__ dist, int n, int B, int Hd, int Wd, int s,
+                                                            const DistQuery* __restrict__ queries, const int* __restrict__ peaks, int P,
+                                                            unsigned seed0, const float* __restrict__ centres, int K, int N,
+                                                            double* __restrict__ out_centres, double* __restrict__ out_conf) {
+    const int q = blockIdx.x;
+    int img, y, x; unsigned seed;
+    if (peaks) { img = q / P; y = peaks[2 * q]; x = peaks[2 * q + 1]; seed = seed0 + (unsigned)q; }
+    else { const DistQuery u = queries[q]; img = u.img; y = u.y; x = u.x; seed = u.seed; }
+    double* oc = out_centres + (size_t)q * K * 2;
+    double* of = out_conf + (size_t)q * K;
+    if (img < 0 || img >= n || y < 0 || y >= Hd * s || x < 0 || x >= Wd * s) {
+        for (int k = threadIdx.x; k < K; k += 256) { oc[2 * k] = 0.0; oc[2 * k + 1] = 0.0; of[k] = 0.0; }
+        return;
+    }
+    const long long stride = (long long)Hd * Wd;
+    suggest_body(dist + (size_t)img * B * stride + (size_t)(y / s) * Wd + (x / s), stride, B, centres, K, N, seed, oc, of, nullptr);
+}
+
+hipError_t launch_suggest_batch(const float* dist, int n, int B, int Hd, int Wd, int s, const DistQuery* queries, const int* peaks, int P,
+                                unsigned seed0, int nq, const float* centres, int K, int N, double* out_centres, double* out_conf,
+                                hipStream_t st) {
+    hipLaunchKernelGGL(suggest_batch_kernel, dim3(nq), dim3(256), 0, st, dist, n, B, Hd, Wd, s, queries, peaks, P, seed0, centres, K, N,
+                       out_centres, out_conf);
+    return hipGetLastError();
+}
+
 hipError_t launch_suggest(const float* pdf, long long stride, int B, const float* centres, int K, int N, unsigned seed,
                           double* out_centres, double* out_conf, unsigned* out_counts, hipStream_t s) {
     hipLaunchKernelGGL(suggest_kernel, dim3(1), dim3(256), 0, s, pdf, stride, B, centres, K, N, seed, out_centres, out_conf,
@@ -250,6 +291,103 @@ __global__ __launch_bounds__(kDistWaves * kDistPix) void dist_entropy_kernel(con
 
 hipError_t launch_dist_entropy(const float* dist, int n, int B, int npix, float* ent, hipStream_t s) {
     hipLaunchKernelGGL(dist_entropy_kernel, dim3((npix + kDistPix - 1) / kDistPix, n), dim3(kDistWaves * kDistPix), 0, s, dist, B, npix, ent);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Uncertainty peaks: where should the next hint go.  ent [n][Hd][Wd] is dist_entropy_kernel's map (MINUS the entropy: the smallest value is
+// the least certain cell); mask [n][H][W] (or nullptr) the hint mask, H = Hd * s, W = Wd * s.  One workgroup per image, P rounds of greedy
+// non-maximum suppression:
+//   candidates = cells whose ent is not NaN and (mask given) whose s x s block of the mask plane is all zero;
+//   round k: the candidate with the smallest ent, ties -> the lowest cy * Wd + cx; peaks[i][k] = (cy * s + s / 2, cx * s + s / 2) in net
+//            coordinates, peak_ent[i][k] = its ent; every candidate with max(|dy|, |dx|) < radius leaves; no candidate: (-1, -1) and +0.
+// The candidate set lives in work [n][Hd * Wd]: the image's ent with NaN where a cell is not (or no longer) a candidate, so a round is one
+// strided walk (thread t sees cells t, t + 1024, ...: ascending, strict < keeps the lowest index), a shuffle arg-min per wave, the 16 wave
+// results folded by wave 0 through LDS, and the winner's window overwritten with NaN.  The comparison (value, then index) is a total order on
+// candidates, so the result is a function of the image's ent and mask values alone: not of n, the grid or timing.  No atomics; P rounds.
+// ------------------------------------------------------------------------------------------------
+constexpr int kPeakThreads = 1024;
+
+// is (v2, i2) in front of (v1, i1)?  i == INT_MAX: no candidate
+__device__ __forceinline__ bool peak_before(float v2, int i2, float v1, int i1) {
+    if (i2 == 0x7fffffff) return false;
+    if (i1 == 0x7fffffff) return true;
+    return v2 < v1 || (v2 == v1 && i2 < i1);
+}
+
+__global__ __launch_bounds__(kPeakThreads) void dist_peaks_kernel(const float* __restrict__ ent, const float* __restrict__ mask, int Hd, int Wd,
+                                                                  int s, int P, int radius, float* __restrict__ work, int* __restrict__ peaks,
+                                                                  float* __restrict__ peak_ent) {
+    __shared__ float wv[kPeakThreads / 64];
+    __shared__ int wi[kPeakThreads / 64];
+    __shared__ int pick_i;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, img = blockIdx.x;
+    const int npix = Hd * Wd, W = Wd * s;
+    const float* e = ent + (size_t)img * npix;
+    float* wk = work + (size_t)img * npix;
+    const float* m = mask ? mask + (size_t)img * npix * s * s : nullptr;
+    const float gone = __builtin_nanf("");
+    for (int c = t; c < npix; c += kPeakThreads) {
+        float v = e[c];
+        if (m) {
+            const int cy = c / Wd, cx = c - cy * Wd;
+            bool hinted = false;
+            for (int dy = 0; dy < s; ++dy)
+                for (int dx = 0; dx < s; ++dx) hinted = hinted || m[(size_t)(cy * s + dy) * W + cx * s + dx] != 0.f;
+            if (hinted) v = gone;
+        }
+        wk[c] = v;
+    }
+    __threadfence_block();
+    __syncthreads();
+    for (int k = 0; k < P; ++k) {
+        float bv = 0.f; int bi = 0x7fffffff;
+        for (int c = t; c < npix; c += kPeakThreads) {
+            const float v = wk[c];
+            if (v == v && (bi == 0x7fffffff || v < bv)) { bv = v; bi = c; }
+        }
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) {
+            const float v2 = __shfl_down(bv, d, 64); const int i2 = __shfl_down(bi, d, 64);
+            if (peak_before(v2, i2, bv, bi)) { bv = v2; bi = i2; }
+        }
+        if (lane == 0) { wv[wave] = bv; wi[wave] = bi; }
+        __syncthreads();
+        if (wave == 0) {
+            bv = lane < kPeakThreads / 64 ? wv[lane] : 0.f; bi = lane < kPeakThreads / 64 ? wi[lane] : 0x7fffffff;
+#pragma unroll
+            for (int d = 8; d > 0; d >>= 1) {
+                const float v2 = __shfl_down(bv, d, 64); const int i2 = __shfl_down(bi, d, 64);
+                if (peak_before(v2, i2, bv, bi)) { bv = v2; bi = i2; }
+            }
+            if (lane == 0) {
+                pick_i = bi;
+                const bool none = bi == 0x7fffffff;
+                const int cy = none ? 0 : bi / Wd, cx = none ? 0 : bi - cy * Wd;
+                int* out = peaks + ((size_t)img * P + k) * 2;
+                out[0] = none ? -1 : cy * s + s / 2; out[1] = none ? -1 : cx * s + s / 2;
+                if (peak_ent) peak_ent[(size_t)img * P + k] = none ? 0.f : bv;
+            }
+        }
+        __syncthreads();
+        const int pi = pick_i;
+        if (pi != 0x7fffffff) {         // uniform over the workgroup
+            const int cy = pi / Wd, cx = pi - cy * Wd;
+            const int y0 = max(cy - radius + 1, 0), y1 = min(cy + radius - 1, Hd - 1), x0 = max(cx - radius + 1, 0), x1 = min(cx + radius - 1, Wd - 1);
+            const int ww = x1 - x0 + 1, cells = (y1 - y0 + 1) * ww;
+            for (int j = t; j < cells; j += kPeakThreads) {
+                const int dy = j / ww, dx = j - dy * ww;
+                wk[(y0 + dy) * Wd + x0 + dx] = gone;
+            }
+        }
+        __threadfence_block();
+        __syncthreads();                // the window is gone before the next walk, and pick_i is read before wave 0 writes the next one
+    }
+}
+
+hipError_t launch_dist_peaks(const float* ent, const float* mask, int n, int Hd, int Wd, int s, int P, int radius, float* work, int* peaks,
+                             float* peak_ent, hipStream_t st) {
+    hipLaunchKernelGGL(dist_peaks_kernel, dim3(n), dim3(kPeakThreads), 0, st, ent, mask, Hd, Wd, s, P, radius, work, peaks, peak_ent);
     return hipGetLastError();
 }
 

@@ -333,6 +333,24 @@ def flatten_hints(hints, n):
     return offsets, arr
 
 
+def dist_queries(queries, seed=0):
+    """Suggestion queries -> the ``N.DistQuery`` array ``idc_suggest_colors_batch`` / ``idc_forward_async_dist`` read, or ``None`` for none.
+    Rows are (img, y, x[, seed]); a row without a seed takes ``seed`` + its index.  (y, x) == (-1, -1) is the empty query."""
+    rows = [] if queries is None else [tuple(int(v) for v in r) for r in queries]
+    if not rows:
+        return None
+    arr = (N.DistQuery * len(rows))()
+    for q, r in enumerate(rows):
+        arr[q].img, arr[q].y, arr[q].x = r[0], r[1], r[2]
+        arr[q].seed = (r[3] if len(r) > 3 else int(seed) + q) & 0xFFFFFFFF
+    return arr
+
+
+class DistBatch(object):
+    """What ``forward_async_dist`` returns: the arrays a distribution batch fills, valid after the slot's ``wait``; ``None`` where not asked for."""
+    sse = hint_colours = out_rgb = out_ab = peaks = peak_ent = entropy = sugg_centres = sugg_conf = None
+
+
 def ref_images(refs):
     """Reference photographs -> what the ``idc_*_ref*`` calls read: (``N.RefImage`` array, the uint8 C-contiguous arrays it points into).  Each
     entry is an (h,w,3) uint8 array of its own size; the library copies the pixels before the call returns, the arrays only have to live until then."""
@@ -714,6 +732,31 @@ class HipColorizer(object):
     def _dist_grid(self):
         return (self.H, self.W) if self.dist_bins() == 313 else (self.H // 4, self.W // 4)
 
+    def dist_peaks(self, n=1, P=8, radius=2, skip_hints=False):
+        """Where the model is least sure (``idc_dist_peaks``): per image of the resident distribution the P cells of smallest ``dist_entropy``
+        (MINUS the entropy), chosen greedily -- ties to the lowest cell index, every cell closer than ``radius`` (Chebyshev, in cells) to a
+        chosen one leaves -- as net coordinates of the cell centres.  ``skip_hints``: cells under a non-zero pixel of the resident hint mask
+        (``hint_planes``) are not candidates.  Returns (peaks (n,P,2) int32 rows (y, x), peak_ent (n,P) float32); once the candidates run out
+        the rows are (-1, -1) and 0."""
+        peaks = np.empty((n, P, 2), np.int32)
+        pent = np.empty((n, P), np.float32)
+        vp = ctypes.c_void_p
+        self._chk(self.lib.idc_dist_peaks(self._h, int(n), int(P), int(radius), N.IDC_PEAKS_SKIP_HINTS if skip_hints else 0,
+                                          peaks.ctypes.data_as(vp), pent.ctypes.data_as(vp)))
+        return peaks, pent
+
+    def suggest_colors_batch(self, queries, centres, K=5, N_draws=25000):
+        """``suggest_colors`` for many pixels in one launch (``idc_suggest_colors_batch``): ``queries`` rows (img, y, x, seed) -> (centres
+        (nq,K,2) f64, conf (nq,K) f64), row q bit for bit ``suggest_colors(y, x, centres, K, N_draws, seed, img)``.  A row with
+        (y, x) == (-1, -1) is empty and gives zeros."""
+        arr = dist_queries(queries)
+        nq = len(arr) if arr is not None else 0
+        c = _f32c(centres, (self.dist_bins(), 2))
+        oc, of = np.empty((nq, K, 2), np.float64), np.empty((nq, K), np.float64)
+        vp = ctypes.c_void_p
+        self._chk(self.lib.idc_suggest_colors_batch(self._h, nq, arr, int(K), int(N_draws), _fptr(c), oc.ctypes.data_as(vp), of.ctypes.data_as(vp)))
+        return oc, of
+
     def dist_entropy(self, n=1):
         """``sum_q p log p`` (the reference's ``compute_entropy``: MINUS the entropy) of the resident distribution of images
         0..n-1, on the device: (n,Hd,Wd) float32, Hd x Wd = H/4 x W/4 (529 head) or H x W (313 head).  p == 0 bins add 0."""
@@ -1009,8 +1052,27 @@ class HipColorizer(object):
         return self._enqueue_images("forward_async_eval", slot, images, hints, out_rgb, out_ab, mode, mask_value, maskcent, l_cent, out,
                                     refs, ref_index, centres, hist_flag, saturation, evaluate=True, want_rgb=want_rgb or out_rgb is not None)
 
+    def forward_async_dist(self, slot, images, hints, out_rgb=None, out_ab=None, mode="ab", mask_value=1.0, maskcent=0.0, l_cent=50.0,
+                           out="net", refs=None, ref_index=None, ref_centres=None, hist_flag=1.0, saturation=False, want_rgb=False,
+                           want_sse=False, peaks=8, radius=2, skip_hints=False, queries=None, K=5, N_draws=25000, seed=0, centres=None,
+                           want_entropy=False):
+        """``forward_async_eval`` on an engine with a distribution head that also runs the head and reads it on the device
+        (``idc_forward_async_dist``).  Images, hints (mode 'ab', 'rgb' or 'reveal'), outputs and reference arguments as there
+        (``ref_centres``: the (313,2) centres of the reference statistics); ``want_sse`` asks for the score.  Behind the network the slot
+        computes the entropy map (``want_entropy``), ``peaks`` uncertainty peaks per image (``dist_peaks``; ``skip_hints`` reads this batch's
+        own hint masks; 0: none) and colour suggestions (``suggest_colors_batch``) for ``queries``: rows (img, y, x[, seed]) with img the index
+        in this batch and seed defaulting to ``seed`` + row, or ``"peaks"``: at every peak, straight from the device buffer, peak (i, k) with
+        seed ``seed + i * peaks + k``.  ``centres`` (B,2): the bin centres, needed with queries.  Returns a ``DistBatch`` whose arrays
+        (sse, hint_colours, out_rgb, peaks (n,P,2), peak_ent (n,P), entropy (n,Hd,Wd), sugg_centres (Q,K,2), sugg_conf (Q,K); ``None`` where not
+        asked for) are valid after ``wait(slot)``.  Afterwards the resident distribution (``get_dist``, ``dist_at`` ...) is this batch's."""
+        taps = dict(peaks=int(peaks), radius=int(radius), skip_hints=bool(skip_hints), queries=queries, K=int(K), N=int(N_draws), seed=int(seed),
+                    centres=centres, want_entropy=bool(want_entropy), want_sse=bool(want_sse))
+        return self._enqueue_images("forward_async_dist", slot, images, hints, out_rgb, out_ab, mode, mask_value, maskcent, l_cent, out,
+                                    refs, ref_index, ref_centres, hist_flag, saturation, evaluate=True, want_rgb=want_rgb or out_rgb is not None,
+                                    taps=taps)
+
     def _enqueue_images(self, who, slot, images, hints, out_rgb, out_ab, mode, mask_value, maskcent, l_cent, out, refs, ref_index, centres,
-                        hist_flag, saturation, evaluate=False, want_rgb=True):
+                        hist_flag, saturation, evaluate=False, want_rgb=True, taps=None):
         images = list(images)
         n = len(images)
         for a in images:
@@ -1059,13 +1121,45 @@ class HipColorizer(object):
             self._chk(self.lib.idc_forward_async_images(*args))
             self._in_flight[int(slot)] = (images, out_rgb, out_ab)    # the library reads / writes them until the slot's wait
             return out_rgb
-        sse = self._pool.take((n, 3), np.uint64)
+        sse = self._pool.take((n, 3), np.uint64) if taps is None or taps["want_sse"] else None
         colours = None
         if mode == "reveal":
             colours = self._pool.take((int(offsets[-1]) if offsets is not None else 0, 2), np.float32)
-        self._chk(self.lib.idc_forward_async_eval(*(args + (sse.ctypes.data_as(vp), colours.ctypes.data_as(vp) if colours is not None and colours.size else None))))
-        self._in_flight[int(slot)] = (images, out_rgb, out_ab, sse, colours)
-        return sse, colours, (out_rgb if want_rgb else None)
+        args = args + (sse.ctypes.data_as(vp) if sse is not None else None, colours.ctypes.data_as(vp) if colours is not None and colours.size else None)
+        if taps is None:
+            self._chk(self.lib.idc_forward_async_eval(*args))
+            self._in_flight[int(slot)] = (images, out_rgb, out_ab, sse, colours)
+            return sse, colours, (out_rgb if want_rgb else None)
+        # the distribution taps: every result in pinned pool memory, written in place by the copy-out stream
+        P, hd_wd = taps["peaks"], self._dist_grid()
+        res = DistBatch()
+        res.sse, res.hint_colours, res.out_rgb, res.out_ab = sse, colours, (out_rgb if want_rgb else None), out_ab
+        t = N.DistTaps()
+        t.n_peaks, t.radius = P, taps["radius"]
+        t.flags = (N.IDC_PEAKS_SKIP_HINTS if taps["skip_hints"] else 0) | (N.IDC_TAPS_SUGGEST_AT_PEAKS if isinstance(taps["queries"], str) else 0)
+        if isinstance(taps["queries"], str) and taps["queries"] != "peaks":
+            raise ValueError("queries is a list of rows, None or 'peaks'")
+        if P > 0:
+            res.peaks, res.peak_ent = self._pool.take((n, P, 2), np.int32), self._pool.take((n, P), np.float32)
+            t.peaks, t.peak_ent = res.peaks.ctypes.data, res.peak_ent.ctypes.data
+        if taps["want_entropy"]:
+            res.entropy = self._pool.take((n,) + hd_wd, np.float32)
+            t.entropy = res.entropy.ctypes.data
+        qarr = None if isinstance(taps["queries"], str) else dist_queries(taps["queries"], taps["seed"])
+        Q = n * P if isinstance(taps["queries"], str) else (len(qarr) if qarr is not None else 0)
+        c = None
+        if Q > 0:
+            t.n_queries = 0 if qarr is None else len(qarr)
+            if qarr is not None:
+                t.queries = qarr
+            t.K, t.N, t.seed = taps["K"], taps["N"], taps["seed"] & 0xFFFFFFFF
+            c = _f32c(taps["centres"], (self.dist_bins(), 2)) if taps["centres"] is not None else None
+            t.centres = c.ctypes.data if c is not None else None
+            res.sugg_centres, res.sugg_conf = self._pool.take((Q, t.K, 2), np.float64), self._pool.take((Q, t.K), np.float64)
+            t.sugg_centres, t.sugg_conf = res.sugg_centres.ctypes.data, res.sugg_conf.ctypes.data
+        self._chk(self.lib.idc_forward_async_dist(*(args + (ctypes.byref(t),))))
+        self._in_flight[int(slot)] = (images, out_rgb, out_ab, res)
+        return res
 
     def colorize_images(self, items, batch=None, out="source", **kw):
         """Generator: colourise a stream of single images of any sizes with both pipeline slots busy.  An item is ``rgb``, ``(rgb, hints)`` or
@@ -1184,6 +1278,71 @@ class HipColorizer(object):
                     for r in finish(k & 1):
                         yield r
                 submit(k & 1, group)
+                k += 1
+            for slot in (k & 1, (k + 1) & 1):       # the older batch first
+                if pending[slot] is not None:
+                    for r in finish(slot):
+                        yield r
+        finally:                                    # a consumer that stops early: nothing stays in flight on buffers about to be recycled
+            for slot in (0, 1):
+                if pending[slot] is not None:
+                    pending[slot] = None
+                    self.wait(slot)
+
+    def suggest_images(self, items, centres, batch=None, out="source", peaks=8, radius=2, skip_hints=True, K=5, N_draws=25000, seed=0, **kw):
+        """Generator: ``colorize_images`` on an engine with a distribution head that also proposes where to put the next hints and in which
+        colours (``forward_async_dist`` with the suggestions at the peaks).  An item is ``rgb`` or ``(rgb, hints)``; grouping, slot alternation
+        and order as in ``colorize_images``.  Per image it yields ``(rgb, peaks (P,2) int32, colours (P,K,2) float64, conf (P,K) float64)``:
+        the colourised image, its ``peaks`` uncertainty peaks as net coordinates (y, x) -- (-1, -1) once the image ran out of cells -- and
+        the K suggested colours of each with their shares.  Peak k of the g-th image of the stream draws with seed ``seed + g * peaks + k``,
+        whatever the batch size.  ``centres`` (B,2): the bin centres; ``kw``: mode, mask_value, maskcent, l_cent."""
+        batch = self.max_batch if batch is None else int(batch)
+        if not 1 <= batch <= self.max_batch:
+            raise ValueError("batch %d outside 1..%d" % (batch, self.max_batch))
+        P = int(peaks)
+        if P < 1:
+            raise ValueError("suggest_images needs at least one peak per image")
+        pending = [None, None]                      # per slot: (DistBatch, pinned sources) of the batch in flight
+
+        def finish(slot):
+            self.wait(slot)
+            (res, srcs), pending[slot] = pending[slot], None
+            K_ = res.sugg_centres.shape[1]
+            sc, sf = np.array(res.sugg_centres).reshape(len(srcs), P, K_, 2), np.array(res.sugg_conf).reshape(len(srcs), P, K_)
+            pk = np.array(res.peaks)
+            return [(np.array(r), pk[i], sc[i], sf[i]) for i, r in enumerate(res.out_rgb)]
+
+        def submit(slot, group, first):
+            srcs = self._pinned_slices([g[0].shape for g in group])
+            for s, g in zip(srcs, group):
+                np.copyto(s, g[0])
+            res = self.forward_async_dist(slot, srcs, [g[1] for g in group], out=out, want_rgb=True, peaks=P, radius=radius, skip_hints=skip_hints,
+                                          queries="peaks", K=K, N_draws=N_draws, seed=int(seed) + first * P, centres=centres, **kw)
+            pending[slot] = (res, srcs)
+
+        def parse(item):
+            item = (item,) if isinstance(item, np.ndarray) else tuple(item)
+            rgb = np.asarray(item[0])
+            if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.size == 0:
+                raise ValueError("suggest_images needs uint8 (h,w,3) images, got %s %s" % (rgb.dtype, rgb.shape))
+            return rgb, item[1] if len(item) > 1 else None
+
+        k, group, done = 0, [], 0
+        try:
+            for item in items:
+                group.append(parse(item))
+                if len(group) < batch:
+                    continue
+                if pending[k & 1] is not None:
+                    for r in finish(k & 1):
+                        yield r
+                submit(k & 1, group, done)
+                k, done, group = k + 1, done + len(group), []
+            if group:
+                if pending[k & 1] is not None:
+                    for r in finish(k & 1):
+                        yield r
+                submit(k & 1, group, done)
                 k += 1
             for slot in (k & 1, (k + 1) & 1):       # the older batch first
                 if pending[slot] is not None:

@@ -2,7 +2,8 @@
 (Zhang et al., "Real-Time User-Guided Image Colorization with Learned Deep Priors", SIGGRAPH 2017: the PSNR-versus-points
 figure).  The metric is ``ColorizeImageBase.get_result_PSNR`` (``data/colorize_image.py:98-108``); the simulated user is described in the
 paper only ("simulating user interactions": the reference repository ships no code for it).  The device does the work: ``HipColorizer.evaluate_images`` reveals
-each point's colour from the image and returns 24 bytes per image."""
+each point's colour from the image and returns 24 bytes per image.  ``psnr_sweep(strategy='uncertain')`` draws the same curve for a user who
+clicks where the model is least sure (``HipColorizer.forward_async_dist``: the uncertainty peaks come from the device too)."""
 import math
 
 import numpy as np
@@ -38,11 +39,81 @@ def simulate_points(H, W, count, rs):
     return rows
 
 
-def psnr_sweep(engine, images, counts=(0, 1, 2, 5, 10, 20, 50, 100), seed=0, out="net", batch=None):
+def guided_rects(peaks, half, H, W):
+    """The patches a guided user reveals at uncertainty peaks: rows (y - half, x - half, y + half, x + half) of ``peaks`` (k,2) (y, x),
+    clipped to the H x W image, corners inclusive; the (-1, -1) rows an image reports once it ran out of cells are dropped.  (k',4) int32."""
+    peaks = np.asarray(peaks, np.int64).reshape(-1, 2)
+    peaks = peaks[~((peaks[:, 0] == -1) & (peaks[:, 1] == -1))]
+    half = int(half)
+    rows = np.stack([np.clip(peaks[:, 0] - half, 0, H - 1), np.clip(peaks[:, 1] - half, 0, W - 1),
+                     np.clip(peaks[:, 0] + half, 0, H - 1), np.clip(peaks[:, 1] + half, 0, W - 1)], axis=1)
+    return rows.astype(np.int32)
+
+
+def _sweep_uncertain(engine, images, counts, out, batch, half, radius):
+    """``psnr_sweep``'s guided user: one pipelined pass per count over all images on both slots; between passes the host only appends
+    the rectangles of the peaks the pass reported."""
+    counts = [int(c) for c in counts]
+    if any(b < a for a, b in zip(counts, counts[1:])):
+        raise ValueError("strategy 'uncertain' needs ascending counts")
+    batch = engine.max_batch if batch is None else int(batch)
+    if not 1 <= batch <= engine.max_batch:
+        raise ValueError("batch %d outside 1..%d" % (batch, engine.max_batch))
+    H, W = engine.H, engine.W
+    rects = [np.zeros((0, 4), np.int32) for _ in images]
+    table = np.zeros((len(counts), len(images)), np.float64)
+    steps = ([(None, 0)] if counts and counts[0] > 0 else []) + [(r, c) for r, c in enumerate(counts)]     # (table row | None, points during the pass)
+    for si, (row, have) in enumerate(steps):
+        more = steps[si + 1][1] - have if si + 1 < len(steps) else 0
+        pending = [None, None]
+
+        def finish(slot):
+            engine.wait(slot)
+            (res, first, sizes), pending[slot] = pending[slot], None
+            for i, (h, w) in enumerate(sizes):
+                if row is not None:
+                    table[row, first + i] = psnr_from_sse(np.array(res.sse[i]), h, w)
+                if more:
+                    rects[first + i] = np.concatenate([rects[first + i], guided_rects(np.array(res.peaks[i])[:more], half, H, W)])
+
+        try:
+            nb = 0
+            for first in range(0, len(images), batch):
+                slot = nb & 1
+                if pending[slot] is not None:
+                    finish(slot)
+                group = images[first:first + batch]
+                res = engine.forward_async_dist(slot, group, [[tuple(int(v) for v in r) for r in rects[first + i]] for i in range(len(group))],
+                                                mode="reveal", out=out, want_sse=True, peaks=more, radius=radius, skip_hints=True)
+                pending[slot] = (res, first, [g.shape[:2] if out == "source" else (H, W) for g in group])
+                nb += 1
+            for slot in (nb & 1, (nb + 1) & 1):     # the older batch first
+                if pending[slot] is not None:
+                    finish(slot)
+        finally:
+            for slot in (0, 1):
+                if pending[slot] is not None:
+                    pending[slot] = None
+                    engine.wait(slot)
+    return table, rects
+
+
+def psnr_sweep(engine, images, counts=(0, 1, 2, 5, 10, 20, 50, 100), seed=0, out="net", batch=None, strategy="random", half=1, radius=2,
+               return_rects=False):
     """The PSNR-versus-points table of ``images`` (a list of (h,w,3) uint8 ground-truth images) on ``engine`` (a ``HipColorizer`` with
     weights): (len(counts), len(images)) float64.  Image j's points are ``simulate_points(engine.H, engine.W, max(counts),
-    RandomState(seed + j))`` and count c uses the first c of them, so a row differs from the next only by the points added."""
+    RandomState(seed + j))`` and count c uses the first c of them, so a row differs from the next only by the points added.
+    ``strategy='uncertain'`` (an engine with a distribution head; ascending counts): a user who clicks where the model is least sure.  Going
+    from count c_k to c_(k+1), image j reveals ``guided_rects`` (peak +- ``half``) of the first c_(k+1) - c_k uncertainty peaks (``dist_peaks``
+    with ``radius``, hinted cells skipped) of the forward that ran with c_k points -- ``forward_async_dist`` on both slots, the host only
+    appending rectangles between passes; an image that runs out of cells keeps fewer points than the count.  ``seed`` is not used.
+    ``return_rects``: also the list of each image's final (k,4) rectangles."""
     images = list(images)
+    if strategy == "uncertain":
+        table, rects = _sweep_uncertain(engine, images, counts, out, batch, half, radius)
+        return (table, rects) if return_rects else table
+    if strategy != "random":
+        raise ValueError("strategy %r is not 'random' or 'uncertain'" % (strategy,))
     most = max(counts) if len(counts) else 0
     points = [simulate_points(engine.H, engine.W, most, np.random.RandomState(seed + j)) for j in range(len(images))]
     table = np.zeros((len(counts), len(images)), np.float64)
@@ -50,4 +121,4 @@ def psnr_sweep(engine, images, counts=(0, 1, 2, 5, 10, 20, 50, 100), seed=0, out
         items = ((img, pts[:c]) for img, pts in zip(images, points))
         for j, (psnr, _) in enumerate(engine.evaluate_images(items, batch=batch, out=out, mode="reveal")):
             table[r, j] = psnr
-    return table
+    return (table, points) if return_rects else table
