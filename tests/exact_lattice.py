@@ -1,10 +1,13 @@
 """Integer-lattice operands for exact operator tests (tests/test_ops_exact_gpu.py, tests/test_ops_exact_cpu.py).
 
 Operands are small integers (x in [-4, 4], weights in [-2, 2], bias in [-8, 8], residual in [-16, 16] -- in [-4099, 4099] where the case stores
-it in fp32 --, BN scale a power of two, BN shift an integer).  Such values are exact in bf16, in fp16 and in every part of the operand-split precisions, every product is an integer, and every
+it in fp32 --, BN scale a power of two, BN shift an integer).  Such values are exact in bf16 and in fp16, every product is an integer, and every
 partial sum of a K loop stays below 2^24 -- so fp32 accumulation never rounds and EVERY summation order (tile shape, split-K, K split over
 waves, segments of a split precision, Winograd transforms) yields the same bits.  The expected output is therefore one exact float64
 computation followed by the storage rounding of the path, compared with assert_array_equal: there is no tolerance to tune.
+On the operand-split precisions these operands fit the hi part ALONE: the lo and mid parts of inputs and weights are zero on this lattice, and
+every K segment but hi.hi multiplies zeros (only the OUTPUT's parts are exercised: expected values need up to 16 or 24 bits).  The segments
+themselves are held by tests/carry_lattice.py (tests/test_split_carry_gpu.py, tests/test_model1_carry_gpu.py), whose operands carry into lo and mid.
 
 A helper, not a conftest: nothing here touches the library or a GPU.
 """

@@ -9,7 +9,9 @@ is the three planes a forward is handed.  So the lattice of tests/exact_lattice.
             that their sums reach thousands (16-bit stores round, on exact ties too), the other half stay zero-mean (the ReLU is live)
   model1.4  running_mean 0, bias an integer in [-8, 8], weight one of 0.5 / 1 / 2, running_var float32(1 - 1e-5): the packer's float64 fold
             gamma / sqrt(var + 1e-5), rounded to fp32, is that power of two exactly (bn_fold asserts it)
-Every conv1_1 value is then an integer of at most 256 (exact in bf16, in fp16 and in every part of a split tensor), every partial sum of
+Every conv1_1 value is then an integer of at most 256: exact in bf16 and in fp16, and held by the hi part of a split tensor ALONE -- on this lattice
+the lo and mid parts of conv1_1 and of every weight are zero, so the split pair's lo / mid segments multiply zeros here; the rows of
+tests/test_model1_carry_gpu.py (keyword `carry`) give conv1_1 values and conv1_2 weights that need the other parts.  Every partial sum of
 conv1_2's K = 576 loop stays below 2^24, and the expected tensors are ONE float64 computation plus the storage rounding of the path,
 compared bit for bit (exact_lattice.compare).  The rest of the network keeps its seeded weights; only model1's tensors are read.
 
@@ -78,22 +80,30 @@ def _ints(rs, lo, hi, shape):
     return rs.randint(lo, hi + 1, size=shape).astype(np.float32)
 
 
-def model1_tensors(r):
-    """The state-dict entries of model1 for a row's draw: lattice weights, integer biases, the BN of the module docstring."""
+def model1_tensors(r, w1_max=None, w2_m=0, w2_mag=1, bn_scales=BN_SCALES):
+    """The state-dict entries of model1 for a row's draw: lattice weights, integer biases, the BN of the module docstring.
+    The keywords are those of the carry rows (tests/test_model1_carry_gpu.py; the defaults leave every draw as it was): conv1_1 weights in
+    [-w1_max, w1_max], conv1_2 weights exactly w2_m entries of +-[ceil(w2_mag / 2), w2_mag] per cout, BN scales drawn from bn_scales."""
     rs = np.random.RandomState(_seed(r, 1))
-    w1 = _ints(rs, -r.w_max, r.w_max, (64, 4, 3, 3))
+    w1 = _ints(rs, -(w1_max or r.w_max), w1_max or r.w_max, (64, 4, 3, 3))
     b1 = _ints(rs, -B1_MAX, B1_MAX, (64,))
     w2 = _ints(rs, -r.w_max, r.w_max, (64, 64, 3, 3))
     # couts 32..63 of conv1_2: half of the negative weights turned positive, so that their sums reach thousands -- beyond fp16's 11 bits as
     # odd integers and halves, deep into bf16's rounding -- while couts 0..31 stay zero-mean and keep conv1_2's ReLU live on both sides
     flip = rs.randint(0, 2, size=(32, 64, 3, 3)) > 0
     w2[32:] = np.where(flip, np.abs(w2[32:]), w2[32:])
+    if w2_m:
+        pos = np.argsort(rs.rand(64, 576), axis=1)[:, :w2_m]
+        val = _ints(rs, (w2_mag + 1) // 2, w2_mag, (64, w2_m)) * np.where(rs.randint(0, 2, size=(64, w2_m)) > 0, 1.0, -1.0).astype(np.float32)
+        w2 = np.zeros((64, 576), np.float32)
+        w2[np.arange(64)[:, None], pos] = val
+        w2 = w2.reshape(64, 64, 3, 3)
     return {
         "model1.0.weight": w1,
         "model1.0.bias": b1,
         "model1.2.weight": w2,
         "model1.2.bias": _ints(rs, -B2_MAX, B2_MAX, (64,)),
-        "model1.4.weight": rs.choice(np.asarray(BN_SCALES, np.float32), 64).astype(np.float32),
+        "model1.4.weight": rs.choice(np.asarray(bn_scales, np.float32), 64).astype(np.float32),
         "model1.4.bias": _ints(rs, -xl.BN_SHIFT_MAX, xl.BN_SHIFT_MAX, (64,)),
         "model1.4.running_mean": np.zeros(64, np.float32),
         "model1.4.running_var": np.full(64, np.float32(1.0 - BN_EPS), np.float32),
@@ -101,10 +111,10 @@ def model1_tensors(r):
     }
 
 
-def state_dict(r, base):
+def state_dict(r, base, **draw):
     """`base` (a whole seeded state dict, left unchanged) with model1's tensors replaced by the row's draw."""
     sd = dict(base)
-    sd.update(model1_tensors(r))
+    sd.update(model1_tensors(r, **draw))
     return sd
 
 
@@ -173,11 +183,15 @@ BELOW = [0, 31, 32, W - 1]
 _STAGES = {}
 
 
-def _stages(r):
-    """The fault-free computation of a row, once: operands, conv1_1, conv1_2's sums -- and the assertions of expected()'s docstring."""
-    if r.id in _STAGES:
-        return _STAGES[r.id]
-    t = model1_tensors(r)
+def _stages(r, carry=None):
+    """The fault-free computation of a row, once: operands, conv1_1, conv1_2's sums -- and the assertions of expected()'s docstring.
+    carry: the draw keywords of a carry row and "c1_limit", the largest conv1_1 value its split storage holds with zero residue."""
+    key = r.id if carry is None else (r.id,) + tuple(sorted(carry.items()))
+    if key in _STAGES:
+        return _STAGES[key]
+    draw = {k: v for k, v in (carry or {}).items() if k != "c1_limit"}
+    c1_limit = (carry or {}).get("c1_limit", C1_LIMIT)
+    t = model1_tensors(r, **draw)
     L, ab, mask, maskcent = planes(r)
     x = pack(L, ab, mask, maskcent)
     scale, shift = bn_fold(t)
@@ -185,22 +199,30 @@ def _stages(r):
     w2, b2 = t["model1.2.weight"].astype(np.float64), t["model1.2.bias"].astype(np.float64)
     for a in (w1, b1, w2, b2):
         assert np.array_equal(a, np.round(a)), "%s: a model1 tensor is not on the integer lattice" % r.id
-    assert 36 * np.abs(x).max() * np.abs(w1).max() + np.abs(b1).max() <= C1_LIMIT, "%s: conv1_1's worst case leaves bf16's exact integers" % r.id
+    assert 36 * np.abs(x).max() * np.abs(w1).max() + np.abs(b1).max() <= c1_limit, "%s: conv1_1's worst case leaves bf16's exact integers" % r.id
     pre1 = _conv3x3(_pad(x), w1) + b1[None, :, None, None]
     c1 = np.maximum(pre1, 0.0)
-    assert np.array_equal(c1, np.round(c1)) and c1.max() <= C1_LIMIT, "%s: a conv1_1 value is not a bf16-exact integer" % r.id
+    assert np.array_equal(c1, np.round(c1)) and c1.max() <= c1_limit, "%s: a conv1_1 value is not a bf16-exact integer" % r.id
     c1max = float(c1.max())
     acc_bound = 576 * c1max * np.abs(w2).max() + np.abs(b2).max()
+    if carry is not None:
+        # a carry row: at most w2_m terms meet in an output, each the sum over the kept segments of the parts' maxima (carry_lattice); the parts hold
+        # conv1_1 and conv1_2's weights with zero residue, and one of the two fits ONE part, so that no dropped segment multiplies two non-zeros
+        import carry_lattice as cl
+        acc_bound = carry["w2_m"] * cl.segment_sum(r.precision, c1max, float(np.abs(w2).max())) + np.abs(b2).max()
+        p1, p2 = cl.parts(c1.astype(np.float32), r.precision), cl.parts(w2.astype(np.float32), r.precision)
+        assert np.array_equal(sum(p.astype(np.float64) for p in p1), c1) and np.array_equal(sum(p.astype(np.float64) for p in p2), w2), r.id
+        assert not p1[1].any() or not p2[1].any(), "%s: both conv1_2 operands carry" % r.id
     # the fp32 forward may run conv1_2 as Winograd F(2x2,3x3): U = G g G^T holds quarters (|U| <= 9/4 max|w|), the input transform sums four
     # pixels, the output transform 3 x 3 products' sums -- exact in fp32 while the bound, counted in quarters, stays below 2^24
-    wino_bound = 4 * (64 * (4 * c1max) * (9 * np.abs(w2).max() / 4) * 9)
+    wino_bound = 4 * (64 * (4 * c1max) * (9 * np.abs(w2).max() / 4) * 9) if carry is None else 0.0      # (carry rows are split-precision rows: no Winograd)
     pre_bound = acc_bound * max(BN_SCALES) + xl.BN_SHIFT_MAX
     assert max(acc_bound, wino_bound, pre_bound) < xl.EXACT_LIMIT, "%s: a partial sum can leave the exact fp32 range (%.0f, %.0f, %.0f)" % (
         r.id, acc_bound, wino_bound, pre_bound)
     acc = _conv3x3(_pad(c1), w2) + b2[None, :, None, None]
-    _STAGES[r.id] = dict(x=x, w1=w1, b1=b1, w2=w2, b2=b2, scale=scale, shift=shift, pre1=pre1, c1=c1, acc=acc,
+    _STAGES[key] = dict(x=x, w1=w1, b1=b1, w2=w2, b2=b2, scale=scale, shift=shift, pre1=pre1, c1=c1, acc=acc,
                          bounds=(c1max, acc_bound, wino_bound, pre_bound))
-    return _STAGES[r.id]
+    return _STAGES[key]
 
 
 def _change_site(acc, w, n, sy, sx, delta):
@@ -213,11 +235,11 @@ def _change_site(acc, w, n, sy, sx, delta):
                 acc[n, :, oy, ox] += w[:, :, ky, kx] @ delta
 
 
-def expected(r, fault=None, site=None):
+def expected(r, fault=None, site=None, carry=None):
     """{"conv1_1": ..., "conv1_2": ...} as float32 arrays (N, 64, H, W): what activation() must return, bit for bit (shared: leave them as
     they are).  Asserts, before anything runs on a GPU: the packed planes and the BN fold are on the lattice, every conv1_1 value is a
     bf16-exact integer, every partial-sum bound is below 2^24, every expected conv1_2 value fits the storage of a split precision."""
-    st = _stages(r)
+    st = _stages(r, carry)
     x, w1, b1, w2 = st["x"], st["w1"], st["b1"], st["w2"]
     c1, acc = st["c1"], st["acc"]
     if fault in ("drop_product_conv1_1", "pack_next_image"):

@@ -1,7 +1,8 @@
 """Exact-integer operator tests: every conv template the library ships, at small ragged shapes, bit for bit, with the kernel that ran asserted.
 
-Operands come from the integer lattice of tests/exact_lattice.py, on which bf16, fp16, every part of the split precisions and fp32
-accumulation are exact, so a correct kernel gives the same bits whatever its summation order and the comparison is assert_array_equal
+Operands come from the integer lattice of tests/exact_lattice.py, on which bf16, fp16 and fp32 accumulation are exact (on the operand-split
+precisions every operand fits its hi part: the lo and mid parts of inputs and weights are ZERO in every row here, so of a split kernel's K
+segments only hi.hi is exercised -- tests/test_split_carry_gpu.py holds the others), so a correct kernel gives the same bits whatever its summation order and the comparison is assert_array_equal
 against one float64 computation plus the storage rounding of the path.  No tolerance appears in this file.  That sees what the Gaussian
 tests (tests/test_ops_gpu.py, 2.5e-2 * (1 + max|ref|) on bf16) cannot: one tap-channel product lost at a tile corner, a halo pixel of the
 neighbouring image, a residual added after the rounding, a truncating store (with cin >= 256 many bf16 outputs are odd integers beyond
