@@ -119,6 +119,10 @@ int idc_set_tile_policy(int policy);
  *   "op_resid_f32" (0)  ... 1 = the shortcut sum (resid) of an IDC_BF16 op is an fp32 tensor, as the one a hyper-column launch reads; every other
  *                      precision stores it so already.  Not read by any forward.
  *   "kw_force_abort" (0)  TEST HOOK: 1 makes the persistent trunk launch's first grid barrier unreachable (plays "workgroups never co-resident").
+ *   "grid_cap"    (0)  TEST HOOK: v > 0 lowers the grid of every grid-stride launch whose workgroup count is capped (the head, softmax, 313-bin decode,
+ *                      colour, ingest, batch, evaluation, audit, split-K epilogue, layout-converter and copy kernels: idc_grid_tag lists them) to at
+ *                      most v workgroups, so a small shape makes many passes of the loop.  It never raises a grid above the launcher's own cap and
+ *                      changes no result; 0 = off.  Process-wide, takes effect on the next launch; a negative value: IDC_ERR_INVALID_ARG.
  * Retired with their kernels, or folded into the above: "fuse_conv1_small", "winograd_bf16", "winograd_form", "winograd_deconv", "conv1_lw",
  * "code_warm", "kwave_deconv" (IDC_ERR_INVALID_ARG).
  * Take effect on the next forward; unknown names return IDC_ERR_INVALID_ARG. */
@@ -733,6 +737,13 @@ int idc_op_deconv_shortcut(int device_id, int precision, int n, int cin, int h, 
  * the call failed before it chose a kernel.  The variant is chosen for idc_set_option("op_policy_batch", v) images (0 = the call's
  * own batch) while the launch carries the call's n. */
 int idc_op_last_kernel(char* out, int cap);
+/* Diagnostics of the capped grid-stride launches (test instrumentation, see option "grid_cap").  idc_grid_tag(i): the name of capped launch
+ * site i = 0, 1, ..., NULL past the end.  idc_grid_last: what the last launch of site `tag` in this process asked for -- *want = the workgroups
+ * that would cover all its items in one pass, *blocks = the grid it got = max(1, min(want, the launcher's cap, grid_cap)); want = 0 when the
+ * site has not launched yet; an unknown tag: IDC_ERR_INVALID_ARG.  The record is process-wide, the last launch wins, and it is not
+ * synchronised with other threads.  eval_sse records the x extent of its (x, image) grid. */
+int idc_grid_last(const char* tag, long long* want, int* blocks);
+const char* idc_grid_tag(int i);
 
 #ifdef __cplusplus
 }

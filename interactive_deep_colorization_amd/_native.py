@@ -25,6 +25,7 @@ EXPORTED_SYMBOLS = [
     "idc_load_weights", "idc_weights_device_ptr", "idc_forward", "idc_forward_device", "idc_forward_dist",
     "idc_lab2rgb", "idc_forward_rgb", "idc_forward_rgb_lazy", "idc_fetch_outputs", "idc_global_histogram", "idc_forward_dist313", "idc_set_dist_temperature", "idc_set_global_hints", "idc_clear_global_hints", "idc_sync", "idc_stream", "idc_num_layers", "idc_layer_info_get", "idc_set_profiling",
     "idc_layer_times_ms", "idc_layer_times_stats", "idc_get_activation", "idc_op_conv2d", "idc_op_deconv4x4s2", "idc_op_deconv_shortcut", "idc_op_last_kernel",
+    "idc_grid_last", "idc_grid_tag",
     "idc_set_image_l", "idc_set_hints", "idc_get_hint_planes", "idc_forward_resident",
     "idc_dist_bins", "idc_keep_dist", "idc_dist_at", "idc_get_dist", "idc_suggest_colors",
     "idc_dist_entropy", "idc_dist_decode",
@@ -174,6 +175,8 @@ def load():
     proto("idc_op_deconv_shortcut", ci, [ci, ci, ci, ci, ci, ci, c_float_p, ci, c_float_p, c_float_p, ci, c_float_p,
                                          c_float_p, c_float_p, ci, c_float_p])
     proto("idc_op_last_kernel", ci, [ctypes.c_char_p, ci])
+    proto("idc_grid_last", ci, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ci)])
+    proto("idc_grid_tag", ctypes.c_char_p, [ci])
     proto("idc_set_image_l", ci, [vp, ci, c_float_p])
     proto("idc_set_hints", ci, [vp, ci, ci, ctypes.POINTER(Hint), ci, cf])
     proto("idc_get_hint_planes", ci, [vp, ci, c_float_p, c_float_p])

@@ -103,11 +103,9 @@ hipError_t launch_range_audit(const void* src, long long npix, int C, int Cpad, 
     if (!src || !rec || npix <= 0 || C <= 0 || Cpad < C || Cpad % 8 != 0 || parts < 0 || parts > 3) return hipErrorInvalidValue;
     const int vpp = parts == 0 ? Cpad / 4 : Cpad / 8;          // 16-byte vectors per pixel (per part)
     const long long nvec = npix * vpp;
-    long long blocks = (nvec + 256 * 4 - 1) / (256 * 4);
-    if (blocks > 2048) blocks = 2048;                          // 256 CUs x 8 workgroups, grid-stride beyond
-    if (blocks < 1) blocks = 1;
-    if (parts == 0) hipLaunchKernelGGL(range_audit_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, s, src, nvec, vpp, C, Cpad, parts, f16, rec);
-    else hipLaunchKernelGGL(range_audit_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, s, src, nvec, vpp, C, Cpad, parts, f16, rec);
+    const int blocks = grid_blocks(GridTag::range_audit, (nvec + 256 * 4 - 1) / (256 * 4), 2048);      // 256 CUs x 8 workgroups, grid-stride beyond
+    if (parts == 0) hipLaunchKernelGGL(range_audit_kernel<0>, dim3(blocks), dim3(256), 0, s, src, nvec, vpp, C, Cpad, parts, f16, rec);
+    else hipLaunchKernelGGL(range_audit_kernel<1>, dim3(blocks), dim3(256), 0, s, src, nvec, vpp, C, Cpad, parts, f16, rec);
     return hipGetLastError();
 }
 

@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256) void lab_post_kernel(const float* __restrict__
 hipError_t launch_lab_post(const float* L, float l_add, const float* ab, unsigned char* rgb, double* lab_q, int N,
                            int H, int W, hipStream_t s) {
     const long long npix = (long long)N * H * W;
-    const int blocks = (int)((npix + 255) / 256 < 4096 ? (npix + 255) / 256 : 4096);
+    const int blocks = grid_blocks(GridTag::lab_post, (npix + 255) / 256, 4096);
     hipLaunchKernelGGL(lab_post_kernel, dim3(blocks), dim3(256), 0, s, L, l_add, ab, rgb, lab_q, npix, H * W);
     return hipGetLastError();
 }
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(256) void pcie_copy_kernel(uint4* __restrict__ dst,
 hipError_t launch_pcie_copy(void* dst, const void* src, size_t bytes, hipStream_t s) {       // bytes % 16 == 0, both 16-byte aligned
     const unsigned n16 = (unsigned)(bytes / 16);
     if (n16 == 0) return hipSuccess;
-    const unsigned blocks = (n16 + 255) / 256 < 1024 ? (n16 + 255) / 256 : 1024;
+    const int blocks = grid_blocks(GridTag::pcie_copy, ((long long)n16 + 255) / 256, 1024);
     hipLaunchKernelGGL(pcie_copy_kernel, dim3(blocks), dim3(256), 0, s, (uint4*)dst, (const uint4*)src, n16);
     return hipGetLastError();
 }
@@ -225,7 +225,7 @@ hipError_t launch_upsample_lab2rgb(const void* a_plane, const void* b_plane, int
                                    int oh, int ow, unsigned char* rgb, hipStream_t s) {
     const long long npix = (long long)oh * ow;
     if (npix <= 0 || interp < 0 || interp > 2) return hipErrorInvalidValue;
-    const int blocks = (int)((npix + 255) / 256 < 8192 ? (npix + 255) / 256 : 8192);
+    const int blocks = grid_blocks(GridTag::upsample_lab2rgb, (npix + 255) / 256, 8192);
     if (src_f64)
         hipLaunchKernelGGL(upsample_lab2rgb_kernel<double>, dim3(blocks), dim3(256), 0, s, (const double*)a_plane, (const double*)b_plane, H, W,
                            interp, L_out, oh, ow, rgb);
@@ -303,7 +303,7 @@ __global__ __launch_bounds__(256) void global_stats_kernel(const unsigned char* 
 hipError_t launch_global_stats(const unsigned char* rgb, const float* centres, unsigned* counts, double* sat_sum, int N,
                                int H, int W, hipStream_t s) {
     const long long nblk = (long long)N * (H / 4) * (W / 4);
-    const int blocks = (int)((nblk + 255) / 256 < 1024 ? (nblk + 255) / 256 : 1024);
+    const int blocks = grid_blocks(GridTag::global_stats, (nblk + 255) / 256, 1024);
     hipLaunchKernelGGL(global_stats_kernel, dim3(blocks), dim3(256), 0, s, rgb, centres, counts, sat_sum, N, H, W);
     return hipGetLastError();
 }
@@ -380,7 +380,7 @@ hipError_t launch_ingest_rgb(const unsigned char* const* srcs, int n, int src_h,
                              unsigned char* rgb_net, double* lab_net, hipStream_t s) {
     const long long npix = (long long)n * H * W;
     if (npix <= 0 || src_h <= 0 || src_w <= 0) return hipErrorInvalidValue;
-    const int blocks = (int)((npix + 255) / 256 < 4096 ? (npix + 255) / 256 : 4096);
+    const int blocks = grid_blocks(GridTag::ingest_rgb, (npix + 255) / 256, 4096);
     hipLaunchKernelGGL(ingest_rgb_kernel, dim3(blocks), dim3(256), 0, s, srcs, n, src_h, src_w, H, W, l_cent, Lp, rgb_net, lab_net);
     return hipGetLastError();
 }
@@ -451,7 +451,7 @@ hipError_t launch_fullres_rgb(const unsigned char* src, int oh, int ow, const vo
     const long long npix = (long long)oh * ow;
     if (npix <= 0 || interp < 0 || interp > 2 || (((uintptr_t)src | (uintptr_t)rgb) & 3)) return hipErrorInvalidValue;
     const long long ngroups = (npix + 3) >> 2;
-    const int blocks = (int)((ngroups + 255) / 256 < 8192 ? (ngroups + 255) / 256 : 8192);
+    const int blocks = grid_blocks(GridTag::fullres_rgb, (ngroups + 255) / 256, 8192);
     if (src_f64)
         hipLaunchKernelGGL(fullres_rgb_kernel<double>, dim3(blocks), dim3(256), 0, s, src, oh, ow, (const double*)a_plane, (const double*)b_plane,
                            H, W, interp, mask, mask_value, rgb);
@@ -531,7 +531,7 @@ hipError_t launch_batch_prologue(const unsigned char* src, int n, int src_h, int
                                  const HintRect* hints, int mode, float mask_value, float* Lp, float* ab, float* mask, hipStream_t s) {
     const long long npix = (long long)n * H * W;
     if (npix <= 0 || src_h <= 0 || src_w <= 0 || (mode != 0 && mode != 1)) return hipErrorInvalidValue;
-    const int blocks = (int)((npix + 255) / 256 < 4096 ? (npix + 255) / 256 : 4096);
+    const int blocks = grid_blocks(GridTag::batch_prologue, (npix + 255) / 256, 4096);
     hipLaunchKernelGGL(batch_prologue_kernel, dim3(blocks), dim3(256), 0, s, src, n, src_h, src_w, H, W, l_cent, offs, hints, mode, mask_value, Lp, ab,
                        mask);
     return hipGetLastError();
@@ -587,7 +587,7 @@ hipError_t launch_batch_fullres_rgb(const unsigned char* src, int n, int oh, int
     const long long total = (long long)n * oh * ow;
     if (n <= 0 || oh <= 0 || ow <= 0 || interp < 0 || interp > 2 || (((uintptr_t)src | (uintptr_t)rgb) & 3)) return hipErrorInvalidValue;
     const long long ngroups = (total + 3) >> 2;
-    const int blocks = (int)((ngroups + 255) / 256 < 8192 ? (ngroups + 255) / 256 : 8192);
+    const int blocks = grid_blocks(GridTag::batch_fullres_rgb, (ngroups + 255) / 256, 8192);
     hipLaunchKernelGGL(batch_fullres_rgb_kernel, dim3(blocks), dim3(256), 0, s, src, total, oh, ow, lab_q, H, W, interp, rgb);
     return hipGetLastError();
 }
@@ -633,7 +633,7 @@ hipError_t launch_ragged_prologue(const unsigned char* src, const ImgDesc* imgs,
                                   const HintRect* hints, int mode, float mask_value, float* Lp, float* ab, float* mask, hipStream_t s) {
     const long long npix = (long long)n * H * W;
     if (npix <= 0 || imgs == nullptr || (mode != 0 && mode != 1)) return hipErrorInvalidValue;
-    const int blocks = (int)((npix + 255) / 256 < 4096 ? (npix + 255) / 256 : 4096);
+    const int blocks = grid_blocks(GridTag::ragged_prologue, (npix + 255) / 256, 4096);
     hipLaunchKernelGGL(ragged_prologue_kernel, dim3(blocks), dim3(256), 0, s, src, imgs, n, H, W, l_cent, offs, hints, mode, mask_value, Lp, ab, mask);
     return hipGetLastError();
 }
@@ -693,7 +693,7 @@ hipError_t launch_ragged_fullres_rgb(const unsigned char* src, const ImgDesc* im
                                      int interp, unsigned char* rgb, hipStream_t s) {
     if (n <= 0 || total < n || imgs == nullptr || interp < 0 || interp > 2 || (((uintptr_t)src | (uintptr_t)rgb) & 3)) return hipErrorInvalidValue;
     const long long ngroups = (total + 3) >> 2;
-    const int blocks = (int)((ngroups + 255) / 256 < 8192 ? (ngroups + 255) / 256 : 8192);
+    const int blocks = grid_blocks(GridTag::ragged_fullres_rgb, (ngroups + 255) / 256, 8192);
     hipLaunchKernelGGL(ragged_fullres_rgb_kernel, dim3(blocks), dim3(256), 0, s, src, imgs, n, lab_q, H, W, interp, rgb);
     return hipGetLastError();
 }
@@ -793,7 +793,7 @@ __global__ __launch_bounds__(256) void ragged_net_truth_kernel(const unsigned ch
 hipError_t launch_ragged_net_truth(const unsigned char* src, const ImgDesc* imgs, int n, int H, int W, unsigned char* rgb_net, hipStream_t s) {
     const long long npix = (long long)n * H * W;
     if (npix <= 0 || imgs == nullptr) return hipErrorInvalidValue;
-    const int blocks = (int)((npix + 255) / 256 < 4096 ? (npix + 255) / 256 : 4096);
+    const int blocks = grid_blocks(GridTag::ragged_net_truth, (npix + 255) / 256, 4096);
     hipLaunchKernelGGL(ragged_net_truth_kernel, dim3(blocks), dim3(256), 0, s, src, imgs, n, H, W, rgb_net);
     return hipGetLastError();
 }
@@ -853,7 +853,7 @@ hipError_t launch_eval_sse(const unsigned char* res, const unsigned char* truth,
     if (n <= 0 || max_pixels <= 0 || total_pixels < max_pixels || sse == nullptr || (((uintptr_t)res | (uintptr_t)truth) & 3))
         return hipErrorInvalidValue;
     const long long groups = (max_pixels * 3 + 11) / 12 + 1;                      // an image's bytes touch at most this many aligned groups
-    const int blocks = (int)((groups + 255) / 256 < 256 ? (groups + 255) / 256 : 256);
+    const int blocks = grid_blocks(GridTag::eval_sse, (groups + 255) / 256, 256);
     hipLaunchKernelGGL(eval_sse_kernel, dim3(blocks, n), dim3(256), 0, s, res, truth, imgs, hw, total_pixels * 3, sse);
     return hipGetLastError();
 }
@@ -1116,7 +1116,7 @@ __global__ void nhwc_to_nchw_kernel(const void* __restrict__ src, float* __restr
 hipError_t launch_nchw_to_nhwc(int precision, const float* src, void* dst, int N, int C, int H, int W, int Cpad,
                                hipStream_t s) {
     const long long total = (long long)N * H * W * Cpad;
-    const int blocks = (int)((total + 255) / 256 < 65535 ? (total + 255) / 256 : 65535);
+    const int blocks = grid_blocks(GridTag::nchw_to_nhwc, (total + 255) / 256, 65535);
     if (precision == 1)
         hipLaunchKernelGGL(nchw_to_nhwc_kernel<__bf16>, dim3(blocks), dim3(256), 0, s, src, (__bf16*)dst, N, C, H, W, Cpad);
     else
@@ -1127,7 +1127,7 @@ hipError_t launch_nchw_to_nhwc(int precision, const float* src, void* dst, int N
 hipError_t launch_nhwc_to_nchw(int src_is_bf16, const void* src, float* dst, int N, int C, int H, int W, int Cstride,
                                hipStream_t s) {
     const long long total = (long long)N * C * H * W;
-    const int blocks = (int)((total + 255) / 256 < 65535 ? (total + 255) / 256 : 65535);
+    const int blocks = grid_blocks(GridTag::nhwc_to_nchw, (total + 255) / 256, 65535);
     hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(blocks), dim3(256), 0, s, src, dst, N, C, H, W, Cstride, src_is_bf16);
     return hipGetLastError();
 }
@@ -1154,7 +1154,7 @@ __global__ void split_to_nchw_kernel(const unsigned short* __restrict__ src, flo
 
 hipError_t launch_split_to_nchw(const void* src, float* dst, int N, int C, int H, int W, int Cpad, int parts, int f16, hipStream_t s) {
     const long long total = (long long)N * C * H * W;
-    const int blocks = (int)((total + 255) / 256 < 65535 ? (total + 255) / 256 : 65535);
+    const int blocks = grid_blocks(GridTag::split_to_nchw, (total + 255) / 256, 65535);
     hipLaunchKernelGGL(split_to_nchw_kernel, dim3(blocks), dim3(256), 0, s, (const unsigned short*)src, dst, N, C, H, W, Cpad, parts, f16);
     return hipGetLastError();
 }
@@ -1178,7 +1178,7 @@ __global__ void nchw_to_split_kernel(const float* __restrict__ src, unsigned sho
 
 hipError_t launch_nchw_to_split(const float* src, void* dst, int N, int C, int H, int W, int Cpad, int parts, int f16, hipStream_t s) {
     const long long total = (long long)N * H * W * Cpad;
-    const int blocks = (int)((total + 255) / 256 < 65535 ? (total + 255) / 256 : 65535);
+    const int blocks = grid_blocks(GridTag::nchw_to_split, (total + 255) / 256, 65535);
     hipLaunchKernelGGL(nchw_to_split_kernel, dim3(blocks), dim3(256), 0, s, src, (unsigned short*)dst, N, C, H, W, Cpad, parts, f16);
     return hipGetLastError();
 }

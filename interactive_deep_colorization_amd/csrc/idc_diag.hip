@@ -400,6 +400,17 @@ int idc_op_last_kernel(char* out, int cap) {
     return IDC_OK;
 }
 
+int idc_grid_last(const char* tag, long long* want, int* blocks) {
+    const int i = grid_tag_index(tag);
+    if (i < 0) return fail(nullptr, IDC_ERR_INVALID_ARG, "unknown grid tag '%s'", tag ? tag : "(null)");
+    const GridRecord r = grid_last(i);
+    if (want) *want = r.want;
+    if (blocks) *blocks = r.blocks;
+    return IDC_OK;
+}
+
+const char* idc_grid_tag(int i) { return grid_tag_name(i); }
+
 int idc_op_deconv_shortcut(int device_id, int precision, int n, int cin, int h, int w, const float* x, int cout, const float* w_deconv,
                            const float* b_deconv, int cin_short, const float* x_short, const float* w_short, const float* b_short, int act, float* y) {
     LayerSpec s{"op", "op", nullptr, kDeconv4x4, cin, cout, 1, 1, act, "x", nullptr, 0, 1, 0};

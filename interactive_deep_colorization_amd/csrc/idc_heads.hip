@@ -60,8 +60,7 @@ __global__ __launch_bounds__(256) void head_kernel(const T* __restrict__ x, cons
 hipError_t launch_head(int precision, const void* x, const float* w, const float* b, float* out, int N, int H, int W,
                        float out_mul, hipStream_t s) {
     const long long npix = (long long)N * H * W;
-    const long long want = (npix + 15) / 16;
-    const int blocks = (int)(want < 8192 ? want : 8192);
+    const int blocks = grid_blocks(GridTag::head, (npix + 15) / 16, 8192);
     if (precision == 1)
         hipLaunchKernelGGL(head_kernel<__bf16>, dim3(blocks), dim3(256), 0, s, (const __bf16*)x, w, b, out, npix, H * W, out_mul);
     else
@@ -113,8 +112,7 @@ hipError_t launch_softmax_nchw(const float* logits, float* out, int N, int H, in
                                float temperature, hipStream_t s) {
     if (nclass > 1024) return hipErrorInvalidValue;
     const long long npix = (long long)N * H * W;
-    const long long want = (npix + 3) / 4;
-    const int blocks = (int)(want < 8192 ? want : 8192);
+    const int blocks = grid_blocks(GridTag::softmax_nchw, (npix + 3) / 4, 8192);
     hipLaunchKernelGGL(softmax_nchw_kernel, dim3(blocks), dim3(256), 0, s, logits, out, npix, H * W, nclass, cstride,
                        temperature);
     return hipGetLastError();
@@ -207,8 +205,7 @@ __global__ __launch_bounds__(256) void dist313_kernel(const float* __restrict__ 
 hipError_t launch_dist313(const float* logits, const float* w_ab, float* pred_ab, float* dist_S, int N, int H, int W,
                           int cstride, float S, float T, hipStream_t s) {
     const long long nblk = (long long)N * (H / 4) * (W / 4);
-    const long long want = (nblk + 3) / 4;
-    const int blocks = (int)(want < 16384 ? want : 16384);
+    const int blocks = grid_blocks(GridTag::dist313, (nblk + 3) / 4, 16384);
     hipLaunchKernelGGL(dist313_kernel, dim3(blocks), dim3(256), 0, s, logits, w_ab, pred_ab, dist_S, N, H, W, cstride, S, T);
     return hipGetLastError();
 }

@@ -775,7 +775,7 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(const ConvArgs a) 
 
 hipError_t launch_splitk_epilogue(int precision, const ConvArgs& a, hipStream_t s) {
     const long long total = (long long)a.N * a.Hs * a.so * a.Ws * a.so * (a.ncg * kCoutGroup / 8);
-    const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+    const int blocks = grid_blocks(GridTag::splitk_epilogue, (total + 255) / 256, 8192);
     if (precision == 1) hipLaunchKernelGGL(splitk_epilogue_kernel<true>, dim3(blocks), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(splitk_epilogue_kernel<false>, dim3(blocks), dim3(256), 0, s, a);
     return hipGetLastError();

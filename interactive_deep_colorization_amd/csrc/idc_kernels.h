@@ -6,6 +6,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "idc_grid.h"
+
 namespace idc {
 
 // One implicit-GEMM convolution launch.  The output is computed over a grid of "sites":

@@ -623,6 +623,11 @@ int idc_set_option(const char* name, int value) {
     if (strcmp(name, "spin_sync") == 0) { o.spin_sync = value != 0; return IDC_OK; }
     if (strcmp(name, "pcie_kernel") == 0) { o.pcie_kernel = value != 0; return IDC_OK; }
     if (strcmp(name, "kw_force_abort") == 0) { o.kw_force_abort = value != 0; return IDC_OK; }
+    if (strcmp(name, "grid_cap") == 0) {         // test hook: idc_grid.h
+        if (value < 0) return fail(nullptr, IDC_ERR_INVALID_ARG, "option 'grid_cap': %d is negative", value);
+        set_grid_cap(value);
+        return IDC_OK;
+    }
     if (strcmp(name, "op_policy_batch") == 0) {
         if (value < 0) return fail(nullptr, IDC_ERR_INVALID_ARG, "option 'op_policy_batch': %d is negative", value);
         o.op_policy_batch = value;

@@ -83,7 +83,7 @@ SPLITK_POLICIES = {"auto": 0, "never": 1, "always": 2}
 def set_option(name, value):
     """Process-wide switches (``idc_set_option``; speed / kernel choice only -- every setting computes the same function).  Names and values are
     documented in ``include/ideepcolor.h``: 'fuse_conv1', 'click', 'winograd', 'mfma16', 'v2p', 'ds_mfma16', 'kwave', 'kwave_chain', and since
-    round 6 'split_ds_fuse', 'conv1_1_split', 'conv1_2_split', 'spin_sync', 'pcie_kernel' (former environment switches) and the test hook 'kw_force_abort'.  'mfma16' = 0 / 'ds_mfma16' = 0 select the
+    round 6 'split_ds_fuse', 'conv1_1_split', 'conv1_2_split', 'spin_sync', 'pcie_kernel' (former environment switches) and the test hooks 'kw_force_abort' and 'grid_cap' (grid_tags() / grid_last()).  'mfma16' = 0 / 'ds_mfma16' = 0 select the
     32x32x16-MFMA partner kernels, which exist only in a ``make EXTRA=-DIDC_AB_PARTNERS`` build: the default library raises IdcError (UNSUPPORTED)."""
     N.check(N.load().idc_set_option(name.encode(), int(value)))
 
@@ -1501,3 +1501,23 @@ def op_deconv_shortcut(x, w_deconv, b_deconv, x_short, w_short, b_short, act=0, 
     N.check(lib.idc_op_deconv_shortcut(device, _PREC[precision], n, cin, h, w, _fptr(x), cout, _fptr(w_deconv), _fptr(b_deconv),
                                        cin_short, _fptr(x_short), _fptr(w_short), _fptr(b_short), act, _fptr(y)))
     return y
+
+
+def grid_tags():
+    """Names of the capped grid-stride launch sites (``idc_grid_tag``): what option 'grid_cap' lowers and grid_last() reports."""
+    lib = N.load()
+    tags, i = [], 0
+    while True:
+        t = lib.idc_grid_tag(i)
+        if t is None:
+            return tags
+        tags.append(t.decode())
+        i += 1
+
+
+def grid_last(tag):
+    """(want, blocks) of the last launch of capped launch site ``tag`` in this process (``idc_grid_last``): the workgroups that would cover its
+    items in one pass and the grid it got; (0, 0) before its first launch."""
+    want, blocks = ctypes.c_longlong(0), ctypes.c_int(0)
+    N.check(N.load().idc_grid_last(tag.encode(), ctypes.byref(want), ctypes.byref(blocks)))
+    return int(want.value), int(blocks.value)
