@@ -617,6 +617,59 @@ int idc_forward_async_dist(idc_handle h, int slot, int n, const idc_ref_image* i
                            int mode, float mask_value, float maskcent, float l_cent, unsigned flags, const idc_batch_refs* refs,
                            uint8_t* const* rgb_out, float* out_ab, uint64_t* sse, float* hint_colours, const idc_dist_taps* taps);
 
+/* ---- distribution scores: how much probability did the head put on the colour the pixel really has?  The question the distribution heads
+ *      were trained on: the reference's training layers encode the ground-truth ab into the colour bins with NNEncode
+ *      (caffe_files/color_quantization.py:7-33; NNEncLayer: NN = 1, sigma = 5, NN = 10 commented beside it, caffe_traininglayers.py:161-189) and
+ *      feed a softmax cross-entropy.  Scored on the device from the resident distribution and the ground-truth image's own bytes, instead of
+ *      idc_get_dist (82 MB per 256x256 image on the 313 head), a host rgb2lab and a nearest-neighbour search and a sort per cell.
+ *      Hd x Wd is the distribution's grid as for idc_dist_entropy, s = H / Hd (4: 529 head, 1: 313 head), B the bin count, centres [B,2] fp32
+ *      (a, b) as in idc_suggest_colors.  For image i and cell (cy, cx):
+ *        1. truth (a*, b*) fp32 = the colour idc_reveal_hints reports for the rectangle (cy*s, cx*s, cy*s+s-1, cx*s+s-1) of that image, bit for
+ *           bit: the same device functions per net-size pixel (bilinear_taps, bilinear_u8, linear_to_lab), the float64 sum in
+ *           reveal_hints_kernel's order for a 16-pixel rectangle -- pixel t = dy*4+dx, folded by halves (t with t+8, then +4, +2, +1) -- divided
+ *           by the count in float64 and rounded once to fp32; for s = 1 the pixel's own (a, b) rounded to fp32.
+ *        2. neighbours q_1 .. q_nn = the nn centres nearest to the truth in Euclidean distance, computed in float64 from the fp32 values
+ *           (d^2 = da*da + db*db, no fused multiply-add), ascending, ties to the lower index; t = q_1 is the target bin; nn in 1..16.  (The
+ *           device orders by d^2, which orders as d does except where two different d^2 round to one square root.)
+ *        3. weights w_j = exp(-d_j^2 / (2 sigma^2)) / sum_k exp(-d_k^2 / (2 sigma^2)) in float64, the sum with k ascending
+ *           (NNEncode.encode_points_mtx_nd); exactly 1 for nn == 1.  (A sigma so small that every term underflows gives NaN, as there.)
+ *        4. xent of the cell = 0 - sum_j w_j * log(max(p[q_j], FLT_MIN)): p the stored fp32 probability, float64 log, products and sum, j
+ *           ascending.  The floor is Caffe's softmax-loss rule: a zero probability gives a large finite value, not inf.
+ *        5. rank of the cell = the number of bins q with p[q] > p[t] || (p[q] == p[t] && q < t): int32 in 0..B-1, 0 = the head's most probable
+ *           bin is the true one.
+ *        6. hits[i][j] = the number of cells of image i with rank < ranks[j], up to 8 thresholds in 1..B: uint32, exact (integer atomics).
+ *        7. xent[i] = the float64 sum of the image's cell values in this FIXED order (no float atomics): the cells c = cy*Wd + cx in blocks of 64
+ *           consecutive cells (the last block padded with +0.0), each block folded by halves (c with c+32, then +16, +8, +4, +2, +1); then 64
+ *           running sums, sum l taking the block sums l, l+64, l+128, ... in ascending order starting from +0.0, folded by halves in the same
+ *           way.  A function of the image's own cells only -- not of n, the slot or timing.  The mean is xent[i] / (Hd*Wd): the host divides.
+ *      idc_dist_score (blocking) scores the resident distribution of images 0..n-1 against the sources idc_set_image_rgb(...,
+ *      IDC_INGEST_KEEP_SOURCE) kept in slots 0..n-1 (idc_reveal_hints' rule).  It drains the pipelined slots first, reads the distribution and the
+ *      sources and writes nothing of the handle's resident state.
+ *      idc_forward_async_dist_score = idc_forward_async_dist (its seventeen arguments first) with the score as one more tap on the slot's compute
+ *      stream, behind the batch's network and behind the other taps: that call's ORDERING paragraph applies unchanged.  The ground truth is the
+ *      slot's own packed source images.  Results land in slot-owned device memory and leave on the copy-out stream: pinned destinations are
+ *      written in place, pageable ones are filled at idc_wait.  taps may be NULL here: then only the score runs.  spec and centres are copied
+ *      before the call returns.
+ *      Status, all decided on the host before anything is enqueued (a refused call leaves slot and handle as they were): for the shared arguments
+ *      the codes of idc_forward_async_dist; IDC_ERR_UNSUPPORTED on a handle without a distribution head, for the blocking form without a resident
+ *      distribution or when one of its slots has no kept source, and while the range audit is on; IDC_ERR_INVALID_ARG for a NULL spec, out,
+ *      out->xent or centres, nn outside 1..min(16, B), a sigma that is not finite and > 0, n_ranks outside 0..8, a threshold outside 1..B, NULL
+ *      hits with n_ranks > 0; IDC_ERR_BATCH for n outside the resident images.
+ *      Not here: the class-rebalancing / prior-boost weights of the training layers. */
+#define IDC_SCORE_MAX_NN 16
+#define IDC_SCORE_MAX_RANKS 8
+typedef struct idc_dist_score_spec { int32_t nn; float sigma; int32_t n_ranks; int32_t ranks[8]; } idc_dist_score_spec;
+typedef struct idc_dist_score_out {      /* every pointer may be NULL except xent */
+    double* xent;      /* [n] */            uint32_t* hits;    /* [n,n_ranks] */
+    double* xent_map;  /* [n,Hd,Wd] */      int32_t* rank_map; /* [n,Hd,Wd] */
+    int32_t* target;   /* [n,Hd,Wd] */      float* truth_ab;   /* [n,2,Hd,Wd] */
+} idc_dist_score_out;
+int idc_dist_score(idc_handle h, int n, const idc_dist_score_spec* spec, const float* centres, const idc_dist_score_out* out);
+int idc_forward_async_dist_score(idc_handle h, int slot, int n, const idc_ref_image* images, const int32_t* hint_offsets, const idc_hint* hints,
+                                 int mode, float mask_value, float maskcent, float l_cent, unsigned flags, const idc_batch_refs* refs,
+                                 uint8_t* const* rgb_out, float* out_ab, uint64_t* sse, float* hint_colours, const idc_dist_taps* taps,
+                                 const idc_dist_score_spec* spec, const float* centres, const idc_dist_score_out* out);
+
 /* ---- colour picker on the device: replaces data/lab_gamut.py, the host colour maths the GUI runs on every mouse press
  *      (ui/gui_draw.py:11,182-183,195-204; ui/gui_gamut.py:4), in float64 with the constants and operation order of idc_lab2rgb.
  *      idc_gamut_map = abGrid(gamut_size, D).update_gamut(L[k]) (lab_gamut.py:56-78) for k = 0..n-1 in one launch.  The grid has

@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = [
     "idc_forward_async_images",
     "idc_reveal_hints", "idc_forward_async_eval",
     "idc_dist_peaks", "idc_suggest_colors_batch", "idc_forward_async_dist",
+    "idc_dist_score", "idc_forward_async_dist_score",
     "idc_gamut_map", "idc_snap_colors",
     "idc_set_range_audit", "idc_range_reset", "idc_range_report", "idc_pack_weights_ex", "idc_load_weights_ex",
 ]
@@ -54,6 +55,7 @@ IDC_HINT_REVEAL = 2         # idc_reveal_hints / idc_forward_async_eval only
 IDC_DECODE_MODE, IDC_DECODE_MEAN = 0, 1
 IDC_PEAKS_SKIP_HINTS, IDC_TAPS_SUGGEST_AT_PEAKS = 1, 2
 IDC_PEAKS_MAX, IDC_SUGGEST_MAX_QUERIES = 256, 4096
+IDC_SCORE_MAX_NN, IDC_SCORE_MAX_RANKS = 16, 8
 
 
 class IdcError(RuntimeError):
@@ -96,6 +98,17 @@ class DistTaps(ctypes.Structure):
                 ("n_queries", ctypes.c_int32), ("queries", ctypes.POINTER(DistQuery)),
                 ("K", ctypes.c_int32), ("N", ctypes.c_int32), ("seed", ctypes.c_uint32), ("centres", ctypes.c_void_p),
                 ("sugg_centres", ctypes.c_void_p), ("sugg_conf", ctypes.c_void_p)]
+
+
+class DistScoreSpec(ctypes.Structure):
+    """idc_dist_score_spec: neighbours and sigma of the soft encoding, and up to 8 top-k thresholds."""
+    _fields_ = [("nn", ctypes.c_int32), ("sigma", ctypes.c_float), ("n_ranks", ctypes.c_int32), ("ranks", ctypes.c_int32 * 8)]
+
+
+class DistScoreOut(ctypes.Structure):
+    """idc_dist_score_out: where the score's results go; every pointer but xent may be NULL."""
+    _fields_ = [("xent", ctypes.c_void_p), ("hits", ctypes.c_void_p), ("xent_map", ctypes.c_void_p), ("rank_map", ctypes.c_void_p),
+                ("target", ctypes.c_void_p), ("truth_ab", ctypes.c_void_p)]
 
 
 class LayerInfo(ctypes.Structure):
@@ -214,6 +227,10 @@ def load():
     proto("idc_suggest_colors_batch", ci, [vp, ci, ctypes.POINTER(DistQuery), ci, ci, c_float_p, vp, vp])
     proto("idc_forward_async_dist", ci, [vp, ci, ci, ctypes.POINTER(RefImage), vp, vp, ci, cf, cf, cf, ctypes.c_uint,
                                          ctypes.POINTER(BatchRefs), ctypes.POINTER(vp), vp, vp, vp, ctypes.POINTER(DistTaps)])
+    proto("idc_dist_score", ci, [vp, ci, ctypes.POINTER(DistScoreSpec), c_float_p, ctypes.POINTER(DistScoreOut)])
+    proto("idc_forward_async_dist_score", ci, [vp, ci, ci, ctypes.POINTER(RefImage), vp, vp, ci, cf, cf, cf, ctypes.c_uint,
+                                               ctypes.POINTER(BatchRefs), ctypes.POINTER(vp), vp, vp, vp, ctypes.POINTER(DistTaps),
+                                               ctypes.POINTER(DistScoreSpec), c_float_p, ctypes.POINTER(DistScoreOut)])
     proto("idc_gamut_map", ci, [vp, ci, vp, ci, ci, vp, vp, vp])
     proto("idc_snap_colors", ci, [vp, ci, vp, vp, vp, vp, vp])
     proto("idc_set_range_audit", ci, [vp, ci])

@@ -752,6 +752,36 @@ class _DistMaps(object):
         centers, conf = self.net.suggest_colors_batch(queries, self._bin_centres(), K=K, N_draws=N)
         return (centers, conf) if return_conf else centers
 
+    def score_dist(self, nn=1, sigma=5.0, ranks=(1, 5), return_maps=False):
+        """How good the predicted distribution is against the image's own colours (not in the reference, whose training layers ask the same
+        question: ``NNEncode`` of the ground-truth ab + softmax cross-entropy): ``(xent_mean, rates)`` -- the mean cross-entropy over the
+        distribution's cells against the truth encoded over its ``nn`` nearest bins with ``sigma``, and for each k of ``ranks`` the share of
+        cells whose true bin is among the k most probable.  ``return_maps`` adds a dict of per-pixel maps at (Xd, Xd): 'xent' float64, 'rank' and
+        'target' int32, 'truth_ab' (2, Xd, Xd) float32.  Computed on the device (``idc_dist_score``) from the source ``load_image_device`` /
+        ``set_image_device`` left there (uploaded again when a forward that was handed the L plane, ``net_forward``, made the engine let it go)."""
+        if not self.dist_ab_set:
+            print('Need to set prediction first')
+            return 0
+        need = 'score_dist needs the image set through load_image_device / set_image_device, and an engine with dist_score'
+        if not hasattr(self.net, 'dist_score') or not (self.net_set and self._src_resident):
+            raise RuntimeError(need)
+        try:
+            res = self.net.dist_score(self._bin_centres(), 1, nn=nn, sigma=sigma, ranks=ranks, want_maps=return_maps)
+        except IdcError as ex:
+            if ex.status != -7 or 'resident source' not in str(ex):
+                raise
+            # the engine let the source go (a forward that was handed the L plane: net_forward).  This object still has the image: the same
+            # bytes give slot 0 the same L plane and the source back; the resident distribution is not touched
+            self.net.set_image_rgb(self.img_rgb_fullres, img=0, l_cent=self.l_mean, keep_source=True, want_rgb=False, want_lab=False)
+            self._l_resident = True
+            self._l_serial = getattr(self.net, 'l_serial', None)
+            res = self.net.dist_score(self._bin_centres(), 1, nn=nn, sigma=sigma, ranks=ranks, want_maps=return_maps)
+        out = (float(res.mean()[0]), res.rates()[0])
+        if return_maps:
+            out += ({'xent': self._up_nearest(res.xent_map[0]), 'rank': self._up_nearest(res.rank_map[0]),
+                     'target': self._up_nearest(res.target[0]), 'truth_ab': self._up_nearest(res.truth_ab[0])},)
+        return out
+
     def get_img_dist_decode(self, mode='mode', gamma=1.0):
         """``get_dist_decode`` as an image: (Xd, Xd, 3) uint8 with the L plane of the current image.  The colour step
         borrows the engine's staging, so afterwards the display getters take their host route until the next forward."""

@@ -173,6 +173,42 @@ int launch_taps(idc_context* c, const DistGeom& g, const TapsLayout& lay, const 
     return IDC_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- distribution scores
+int check_score(idc_context* c, const DistGeom& g, int n, const idc_dist_score_spec* spec, const float* centres, const idc_dist_score_out* out,
+                ScoreLayout* lay) {
+    if (!spec || !out || !out->xent || !centres) return fail(&c->err, IDC_ERR_INVALID_ARG, "null score pointer (spec, out, out->xent, centres)");
+    const int nn_max = g.B < IDC_SCORE_MAX_NN ? g.B : IDC_SCORE_MAX_NN;
+    if (spec->nn < 1 || spec->nn > nn_max) return fail(&c->err, IDC_ERR_INVALID_ARG, "nn %d outside 1..%d", spec->nn, nn_max);
+    if (!std::isfinite(spec->sigma) || !(spec->sigma > 0.f)) return fail(&c->err, IDC_ERR_INVALID_ARG, "sigma must be positive and finite");
+    if (spec->n_ranks < 0 || spec->n_ranks > IDC_SCORE_MAX_RANKS)
+        return fail(&c->err, IDC_ERR_INVALID_ARG, "%d rank thresholds outside 0..%d", spec->n_ranks, IDC_SCORE_MAX_RANKS);
+    for (int j = 0; j < spec->n_ranks; ++j)
+        if (spec->ranks[j] < 1 || spec->ranks[j] > g.B) return fail(&c->err, IDC_ERR_INVALID_ARG, "rank threshold %d: %d outside 1..%d", j, spec->ranks[j], g.B);
+    if (spec->n_ranks > 0 && !out->hits) return fail(&c->err, IDC_ERR_INVALID_ARG, "null hits with %d rank thresholds", spec->n_ranks);
+    const size_t npix = (size_t)g.Hd * g.Wd, nblk = (npix + 63) / 64;
+    lay->n = n; lay->nn = spec->nn; lay->sigma = spec->sigma;
+    lay->ranks.n = spec->n_ranks;
+    for (int j = 0; j < 8; ++j) lay->ranks.thr[j] = j < spec->n_ranks ? spec->ranks[j] : 0;
+    lay->want_xmap = out->xent_map != nullptr; lay->want_rmap = out->rank_map != nullptr; lay->want_tgt = out->target != nullptr;
+    lay->o_part = 0;
+    lay->o_xent = taps_align((size_t)n * nblk * sizeof(double));
+    lay->o_hits = lay->o_xent + taps_align((size_t)n * sizeof(double));
+    lay->o_truth = lay->o_hits + taps_align((size_t)n * 8 * sizeof(unsigned));
+    lay->o_xmap = lay->o_truth + taps_align((size_t)n * 2 * npix * sizeof(float));
+    lay->o_rmap = lay->o_xmap + taps_align(lay->want_xmap ? (size_t)n * npix * sizeof(double) : 0);
+    lay->o_tgt = lay->o_rmap + taps_align(lay->want_rmap ? (size_t)n * npix * sizeof(int) : 0);
+    lay->out_bytes = lay->o_tgt + taps_align(lay->want_tgt ? (size_t)n * npix * sizeof(int) : 0);
+    return IDC_OK;
+}
+
+int launch_score(idc_context* c, const DistGeom& g, const ScoreLayout& lay, const float* centres, unsigned char* out, hipStream_t s) {
+    HIPCHK(c, launch_dist_score(g.dist, (const float*)(out + lay.o_truth), centres, lay.n, g.B, g.Hd * g.Wd, lay.nn, lay.sigma, lay.ranks,
+                                (double*)(out + lay.o_part), (double*)(out + lay.o_xent), lay.ranks.n > 0 ? (unsigned*)(out + lay.o_hits) : nullptr,
+                                lay.want_xmap ? (double*)(out + lay.o_xmap) : nullptr, lay.want_rmap ? (int*)(out + lay.o_rmap) : nullptr,
+                                lay.want_tgt ? (int*)(out + lay.o_tgt) : nullptr, s));
+    return IDC_OK;
+}
+
 }  // namespace idc
 
 extern "C" {
@@ -593,6 +629,44 @@ int idc_suggest_colors_batch(idc_handle h, int nq, const idc_dist_query* q, int 
     idc_dist_taps taps = {};
     taps.n_queries = nq; taps.queries = q; taps.K = K; taps.N = N; taps.centres = centres; taps.sugg_centres = out_centres; taps.sugg_conf = out_conf;
     return run_taps_blocking(h, h ? (h->dist_n > 0 ? h->dist_n : 1) : 1, 0, 1, &taps);
+}
+
+// The blocking form of the distribution score: checks, the centres up, one truth launch per image (each slot keeps a source of its own size), the
+// score launches, and the wanted parts of the result block straight to the caller
+int idc_dist_score(idc_handle h, int n, const idc_dist_score_spec* spec, const float* centres, const idc_dist_score_out* out) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    DistGeom g;
+    if (!dist_geom(h, &g)) return fail(&h->err, IDC_ERR_UNSUPPORTED, "handle has no distribution head (IDC_FLAG_DIST_HEAD, or IDC_FLAG_DIST313 with idc_keep_dist on)");
+    ScoreLayout lay;
+    int rc = check_score(h, g, n, spec, centres, out, &lay);
+    if (rc) return rc;
+    if (h->audit) return fail(&h->err, IDC_ERR_UNSUPPORTED, "the distribution score does not run while the range audit is on");
+    if (h->dist_n <= 0) return fail(&h->err, IDC_ERR_UNSUPPORTED, "Need to set prediction first (no resident distribution)");
+    if (n <= 0 || n > h->dist_n) return fail(&h->err, IDC_ERR_BATCH, "batch %d outside 1..%d", n, h->dist_n);
+    for (int i = 0; i < n; ++i)
+        if (!h->src[i].d_rgb.get())
+            return fail(&h->err, IDC_ERR_UNSUPPORTED, "image slot %d has no resident source (idc_set_image_rgb with IDC_INGEST_KEEP_SOURCE)", i);
+    HIPCHK(h, hipSetDevice(h->device));
+    rc = drain_pipeline(h);
+    if (rc) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+    const size_t npix = (size_t)g.Hd * g.Wd, o_out = taps_align((size_t)g.B * 2 * sizeof(float));
+    HIPCHK(h, h->d_score.ensure(o_out + lay.out_bytes, 65536));
+    unsigned char* res = h->d_score.get() + o_out;
+    HIPCHK(h, hipMemcpy(h->d_score.get(), centres, (size_t)g.B * 2 * sizeof(float), hipMemcpyHostToDevice));
+    for (int i = 0; i < n; ++i)
+        HIPCHK(h, launch_dist_truth(h->src[i].d_rgb.get(), nullptr, 1, h->src[i].h, h->src[i].w, h->H, h->W, g.s,
+                                    (float*)(res + lay.o_truth) + (size_t)i * 2 * npix, h->stream.get()));
+    rc = launch_score(h, g, lay, (const float*)h->d_score.get(), res, h->stream.get());
+    if (rc) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+    HIPCHK(h, hipMemcpy(out->xent, res + lay.o_xent, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    if (lay.ranks.n > 0) HIPCHK(h, hipMemcpy(out->hits, res + lay.o_hits, (size_t)n * lay.ranks.n * sizeof(unsigned), hipMemcpyDeviceToHost));
+    if (out->truth_ab) HIPCHK(h, hipMemcpy(out->truth_ab, res + lay.o_truth, (size_t)n * 2 * npix * sizeof(float), hipMemcpyDeviceToHost));
+    if (out->xent_map) HIPCHK(h, hipMemcpy(out->xent_map, res + lay.o_xmap, (size_t)n * npix * sizeof(double), hipMemcpyDeviceToHost));
+    if (out->rank_map) HIPCHK(h, hipMemcpy(out->rank_map, res + lay.o_rmap, (size_t)n * npix * sizeof(int), hipMemcpyDeviceToHost));
+    if (out->target) HIPCHK(h, hipMemcpy(out->target, res + lay.o_tgt, (size_t)n * npix * sizeof(int), hipMemcpyDeviceToHost));
+    return IDC_OK;
 }
 
 int idc_global_histogram(idc_handle h, int n, const uint8_t* rgb, const float* centres, float* hist, float* s_avg) {

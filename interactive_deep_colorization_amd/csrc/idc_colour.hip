@@ -769,6 +769,64 @@ hipError_t launch_reveal_hints(const unsigned char* src, const ImgDesc* imgs, co
     return hipGetLastError();
 }
 
+// Distribution scores (idc_dist_score / idc_forward_async_dist_score): the ground-truth colour of every cell of the distribution's grid,
+// truth [.][2][npix] fp32 (npix = Hd * Wd, H = Hd * S, W = Wd * S), = what reveal_hints_kernel reports for the cell's S x S rectangle, bit for bit:
+// the same device functions on the same operands per net-size pixel, and that kernel's summation order for a rectangle of at most 64 pixels --
+// its thread t holds pixel t = dy * S + dx alone (0.0 + a), lanes fold by halves, lanes without a pixel and the other three waves add +0.0.  Here
+// one thread owns the cell and folds its S * S values by halves itself (t with t + 8, then + 4, + 2, + 1 for S = 4); the sum is divided by the
+// count in float64 and rounded once to fp32.  Contraction is off: an FMA of linear_to_lab's last product into a sum would change a rounding.
+// blockIdx.y = image: image i of the packed run (imgs != nullptr), or the single [sh,sw,3] source at src.
+template <int S>
+__global__ __launch_bounds__(256) void dist_truth_kernel(const unsigned char* __restrict__ src, const ImgDesc* __restrict__ imgs, int sh, int sw,
+                                                         int H, int W, int Wd, int npix, float* __restrict__ truth) {
+#pragma clang fp contract(off)
+    __shared__ double tab[256];
+    fill_srgb_table(tab);
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= npix) return;
+    const unsigned char* img = src;
+    if (imgs != nullptr) {
+        const ImgDesc d = imgs[blockIdx.y];
+        img = src + d.off; sh = d.h; sw = d.w;
+    }
+    const int cy = c / Wd, cx = c - cy * Wd;
+    double va[S * S], vb[S * S];
+#pragma unroll
+    for (int t = 0; t < S * S; ++t) {
+        const int y = cy * S + t / S, x = cx * S + t % S;
+        int y0, y1, x0, x1;
+        double wy, wx;
+        bilinear_taps(y, sh, H, y0, y1, wy);
+        bilinear_taps(x, sw, W, x0, x1, wx);
+        const unsigned char* p00 = img + ((long long)y0 * sw + x0) * 3; const unsigned char* p01 = img + ((long long)y0 * sw + x1) * 3;
+        const unsigned char* p10 = img + ((long long)y1 * sw + x0) * 3; const unsigned char* p11 = img + ((long long)y1 * sw + x1) * 3;
+        double lin[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) lin[k] = tab[bilinear_u8((double)p00[k], (double)p01[k], (double)p10[k], (double)p11[k], wx, wy)];
+        double L, a, b;
+        linear_to_lab(lin, L, a, b);
+        va[t] = 0.0 + a; vb[t] = 0.0 + b;
+    }
+#pragma unroll
+    for (int o = S * S / 2; o > 0; o >>= 1)
+#pragma unroll
+        for (int t = 0; t < o; ++t) { va[t] += va[t + o]; vb[t] += vb[t + o]; }
+    float* dst = truth + (size_t)blockIdx.y * 2 * npix + c;
+    dst[0] = (float)(va[0] / (double)(S * S));
+    dst[npix] = (float)(vb[0] / (double)(S * S));
+}
+
+hipError_t launch_dist_truth(const unsigned char* src, const ImgDesc* imgs, int n, int src_h, int src_w, int H, int W, int s, float* truth,
+                             hipStream_t st) {
+    if (src == nullptr || truth == nullptr || n <= 0 || (s != 1 && s != 4) || H % s || W % s) return hipErrorInvalidValue;
+    if (imgs == nullptr && (n != 1 || src_h <= 0 || src_w <= 0)) return hipErrorInvalidValue;
+    const int Wd = W / s, npix = (H / s) * Wd;
+    const dim3 grid((npix + 255) / 256, n);
+    if (s == 4) hipLaunchKernelGGL(dist_truth_kernel<4>, grid, dim3(256), 0, st, src, imgs, src_h, src_w, H, W, Wd, npix, truth);
+    else hipLaunchKernelGGL(dist_truth_kernel<1>, grid, dim3(256), 0, st, src, imgs, src_h, src_w, H, W, Wd, npix, truth);
+    return hipGetLastError();
+}
+
 // The uint8 half of ragged_prologue_kernel's pixel: rgb_net [n,H,W,3] = cv2.resize of every image to the net size, one thread per pixel.
 __global__ __launch_bounds__(256) void ragged_net_truth_kernel(const unsigned char* __restrict__ src, const ImgDesc* __restrict__ imgs, int n, int H,
                                                                int W, unsigned char* __restrict__ rgb_net) {

@@ -194,6 +194,7 @@ struct idc_context {
     // queries and centres in, the suggestions out), grown on demand: both calls block, so nothing is in flight when they grow
     DevMem<unsigned char> d_taps;
     PinnedMem<unsigned char> h_taps;
+    DevMem<unsigned char> d_score;       // idc_dist_score: the centres and one block for what the score produces (ScoreLayout), grown on demand; the call blocks
     std::vector<char> l_set;             // per image slot: d_L holds an uploaded L plane (idc_forward_resident refuses otherwise)
     // image ingestion (idc_set_image_rgb / idc_fullres_rgb): per slot the uint8 source kept on the device (IDC_INGEST_KEEP_SOURCE; empty = none)
     // and its size, and the mask_value of the slot's last idc_set_hints (0 = never had hints)
@@ -247,6 +248,10 @@ struct idc_context {
         DevMem<unsigned char> d_taps_in, d_taps;
         PinnedMem<unsigned char> h_taps_in, h_taps;
         std::vector<StagedOut> taps_outs;
+        // idc_forward_async_dist_score: the centres (pinned and device) and the score's result block (ScoreLayout) with its pinned twin, as for the taps
+        DevMem<unsigned char> d_score_in, d_score;
+        PinnedMem<unsigned char> h_score_in, h_score;
+        std::vector<StagedOut> score_outs;
         // idc_forward_async_rgb_ref: the batch's references and the slot's OWN [max_batch][316] global inputs (the handle's d_glob_in is not touched)
         RefStage ref;
         DevMem<float> d_glob_in;
@@ -349,6 +354,19 @@ int check_taps(idc_context* c, const DistGeom& g, int n, int p_min, int q_min, c
 // on `s`: [entropy] [peaks, mask = the planes IDC_PEAKS_SKIP_HINTS reads] [suggestions] from `in` (device input block) into `out` (device result block)
 int launch_taps(idc_context* c, const DistGeom& g, const TapsLayout& lay, const idc_dist_taps* taps, const float* mask, const unsigned char* in,
                 unsigned char* out, hipStream_t s);
+// distribution scores (idc_dist_score / idc_forward_async_dist_score): every check of include/ideepcolor.h's table on the host, and where each part
+// sits in the result block (byte offsets, 16-byte aligned; the block sums come first and stay on the device, a map nobody asked for takes no room)
+struct ScoreLayout {
+    int n = 0, nn = 0;
+    float sigma = 0.f;
+    ScoreRanks ranks = {};
+    bool want_xmap = false, want_rmap = false, want_tgt = false;
+    size_t o_part = 0, o_xent = 0, o_hits = 0, o_truth = 0, o_xmap = 0, o_rmap = 0, o_tgt = 0, out_bytes = 0;
+};
+int check_score(idc_context* c, const DistGeom& g, int n, const idc_dist_score_spec* spec, const float* centres, const idc_dist_score_out* out,
+                ScoreLayout* lay);
+// on `s`: the score of truth (at lay.o_truth of `out`, written by launch_dist_truth before) into the device result block `out`
+int launch_score(idc_context* c, const DistGeom& g, const ScoreLayout& lay, const float* centres, unsigned char* out, hipStream_t s);
 int check_chain_abort(idc_context* c);
 int check_forward_args(idc_context* c, int n);
 hipError_t wait_stream(idc_context* c, int n);

@@ -361,6 +361,7 @@ static int wait_slot(idc_context* h, int slot) {
     for (const auto& o : sl.staged_outs) memcpy(o.user, sl.h_rgb.get() + o.at, o.bytes);
     for (const auto& o : sl.eval_outs) memcpy(o.user, sl.h_eval.get() + o.at, o.bytes);
     for (const auto& o : sl.taps_outs) memcpy(o.user, sl.h_taps.get() + o.at, o.bytes);
+    for (const auto& o : sl.score_outs) memcpy(o.user, sl.h_score.get() + o.at, o.bytes);
     return IDC_OK;
 }
 
@@ -614,7 +615,7 @@ int idc_forward_async(idc_handle h, int slot, int n, const float* L_mc, const fl
     HIPCHK(h, hipMemcpyAsync(sl.staged_out ? sl.h_out.get() : out_ab, sl.d_out.get(), (size_t)n * hw * 2 * 4, hipMemcpyDeviceToHost, h->s_out.get()));
     HIPCHK(h, hipEventRecord(sl.ev_out.get(), h->s_out.get()));
     sl.pending = true; sl.timed = true; sl.user_out = out_ab; sl.n = n;
-    sl.staged_outs.clear(); sl.eval_outs.clear(); sl.taps_outs.clear();
+    sl.staged_outs.clear(); sl.eval_outs.clear(); sl.taps_outs.clear(); sl.score_outs.clear();
     return IDC_OK;
 }
 
@@ -634,7 +635,11 @@ struct BatchIO {
 };
 // idc_forward_async_eval's own arguments (ev == nullptr: every other entry point): the score is required, the revealed colours are optional.
 // idc_forward_async_dist brings both and its taps (taps_call: taps itself may be NULL, which is refused); there the score is optional too
-struct EvalArgs { uint64_t* sse; float* hint_colours; bool taps_call = false; const idc_dist_taps* taps = nullptr; };
+// idc_forward_async_dist_score adds the score (score_call: then taps may be NULL, and spec / centres / sout are checked by check_score)
+struct EvalArgs {
+    uint64_t* sse; float* hint_colours; bool taps_call = false; const idc_dist_taps* taps = nullptr;
+    bool score_call = false; const idc_dist_score_spec* spec = nullptr; const float* centres = nullptr; const idc_dist_score_out* sout = nullptr;
+};
 // One host buffer of a call and the bytes of the slot's packed device array it fills (in) or receives (out)
 struct Piece { const uint8_t* in; uint8_t* out; size_t in_at, in_bytes, out_at, out_bytes; bool in_pinned, out_pinned; };
 
@@ -731,12 +736,20 @@ static int forward_async_rgb(idc_handle h, int slot, int n, const BatchIO& io, c
         if (!(h->flags & IDC_FLAG_GLOBAL_HINTS)) return fail(&h->err, IDC_ERR_UNSUPPORTED, "handle was created without IDC_FLAG_GLOBAL_HINTS");
     }
     DistGeom geom;
-    TapsLayout tl;
+    TapsLayout tl;                                      // (all zero without taps: nothing of them is allocated, launched or copied)
+    ScoreLayout sc;
+    const bool score = dist && ev->score_call;
     if (dist) {
         if (!dist_geom(h, &geom))
             return fail(&h->err, IDC_ERR_UNSUPPORTED, "handle has no distribution head (IDC_FLAG_DIST_HEAD, or IDC_FLAG_DIST313 with idc_keep_dist on)");
-        rc = check_taps(h, geom, n, 0, 0, ev->taps, &tl);
-        if (rc) return rc;
+        if (!score || ev->taps) {
+            rc = check_taps(h, geom, n, 0, 0, ev->taps, &tl);
+            if (rc) return rc;
+        }
+        if (score) {
+            rc = check_score(h, geom, n, ev->spec, ev->centres, ev->sout, &sc);
+            if (rc) return rc;
+        }
     }
     if (h->audit) return fail(&h->err, IDC_ERR_UNSUPPORTED, "the range audit covers the blocking, resident and device-pointer forwards, not the pipelined slots");
     auto& sl = h->pipe[slot];
@@ -777,6 +790,14 @@ static int forward_async_rgb(idc_handle h, int slot, int n, const BatchIO& io, c
             if (!tl.at_peaks) memcpy(sl.h_taps_in.get(), ev->taps->queries, (size_t)tl.Q * sizeof(DistQuery));
             memcpy(sl.h_taps_in.get() + tl.i_centres, ev->taps->centres, (size_t)geom.B * 2 * sizeof(float));
         }
+    }
+    const size_t score_in_bytes = align_up((size_t)geom.B * 2 * sizeof(float), 16);
+    if (score) {    // the centres travel with the batch; the score's results wait in the slot's block
+        HIPCHK(h, sl.d_score_in.ensure(score_in_bytes, 8192));
+        HIPCHK(h, sl.h_score_in.ensure(score_in_bytes, 8192));
+        HIPCHK(h, sl.d_score.ensure(sc.out_bytes, 65536));
+        HIPCHK(h, sl.h_score.ensure(sc.out_bytes, 65536));
+        memcpy(sl.h_score_in.get(), ev->centres, (size_t)geom.B * 2 * sizeof(float));
     }
     // every host buffer is judged on its own: pageable sources are copied into the slot's pinned staging here, on the calling thread
     std::vector<Piece> pieces;
@@ -828,6 +849,7 @@ static int forward_async_rgb(idc_handle h, int slot, int n, const BatchIO& io, c
     HIPCHK(h, copy_pieces(pieces, true, sl.d_src.get(), sl.h_src.get(), h->s_in.get()));
     HIPCHK(h, hipMemcpyAsync(sl.d_meta.get(), sl.h_meta.get(), meta_bytes, hipMemcpyHostToDevice, h->s_in.get()));
     if (dist && tl.Q > 0) HIPCHK(h, hipMemcpyAsync(sl.d_taps_in.get(), sl.h_taps_in.get(), tl.in_bytes, hipMemcpyHostToDevice, h->s_in.get()));
+    if (score) HIPCHK(h, hipMemcpyAsync(sl.d_score_in.get(), sl.h_score_in.get(), score_in_bytes, hipMemcpyHostToDevice, h->s_in.get()));
     if (ra) {
         rc = upload_refs(h, sl.ref, lay, h->s_in.get());
         if (rc) return rc;
@@ -880,14 +902,38 @@ static int forward_async_rgb(idc_handle h, int slot, int n, const BatchIO& io, c
         }
     }
     if (dist) {     // entropy, peaks, suggestions: on this stream behind this batch's network, so in front of whatever replaces the handle's distribution next
-        rc = launch_taps(h, geom, tl, ev->taps, sl.d_mask.get(), sl.d_taps_in.get(), sl.d_taps.get(), h->stream.get());
-        if (rc) return rc;
+        if (ev->taps) {
+            rc = launch_taps(h, geom, tl, ev->taps, sl.d_mask.get(), sl.d_taps_in.get(), sl.d_taps.get(), h->stream.get());
+            if (rc) return rc;
+        }
+        if (score) {    // behind the other taps: the cells' ground truth from the slot's own packed sources, then the score
+            HIPCHK(h, launch_dist_truth(sl.d_src.get(), d_tab, n, 0, 0, h->H, h->W, geom.s, (float*)(sl.d_score.get() + sc.o_truth), h->stream.get()));
+            rc = launch_score(h, geom, sc, (const float*)sl.d_score_in.get(), sl.d_score.get(), h->stream.get());
+            if (rc) return rc;
+        }
     }
     HIPCHK(h, hipEventRecord(sl.ev_comp.get(), h->stream.get()));
     HIPCHK(h, hipStreamWaitEvent(h->s_out.get(), sl.ev_comp.get(), 0));
     HIPCHK(h, hipEventRecord(sl.ev_out0.get(), h->s_out.get()));
-    sl.eval_outs.clear(); sl.taps_outs.clear();
-    if (dist) {
+    sl.eval_outs.clear(); sl.taps_outs.clear(); sl.score_outs.clear();
+    if (score) {
+        const idc_dist_score_out* so = ev->sout;
+        const size_t npix = (size_t)geom.Hd * geom.Wd;
+        const struct { void* user; size_t at, bytes; } outs[] = {
+            {so->xent, sc.o_xent, (size_t)n * sizeof(double)},
+            {sc.ranks.n > 0 ? so->hits : nullptr, sc.o_hits, (size_t)n * sc.ranks.n * sizeof(unsigned)},
+            {so->truth_ab, sc.o_truth, (size_t)n * 2 * npix * sizeof(float)},
+            {so->xent_map, sc.o_xmap, (size_t)n * npix * sizeof(double)},
+            {so->rank_map, sc.o_rmap, (size_t)n * npix * sizeof(int)},
+            {so->target, sc.o_tgt, (size_t)n * npix * sizeof(int)}};
+        for (const auto& o : outs) {
+            if (!o.user || !o.bytes) continue;
+            const bool direct = is_pinned(o.user);
+            HIPCHK(h, hipMemcpyAsync(direct ? o.user : (void*)(sl.h_score.get() + o.at), sl.d_score.get() + o.at, o.bytes, hipMemcpyDeviceToHost, h->s_out.get()));
+            if (!direct) sl.score_outs.push_back({(uint8_t*)o.user, o.at, o.bytes});
+        }
+    }
+    if (dist && ev->taps) {
         const idc_dist_taps* tp = ev->taps;
         const size_t npix = (size_t)geom.Hd * geom.Wd;
         const struct { void* user; size_t at, bytes; } outs[] = {
@@ -965,6 +1011,17 @@ int idc_forward_async_dist(idc_handle h, int slot, int n, const idc_ref_image* i
                            uint8_t* const* rgb_out, float* out_ab, uint64_t* sse, float* hint_colours, const idc_dist_taps* taps) {
     const BatchIO io = {true, 0, 0, nullptr, nullptr, images, rgb_out};
     const EvalArgs ev = {sse, hint_colours, true, taps};
+    if (!refs) return forward_async_rgb(h, slot, n, io, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, nullptr, out_ab, &ev);
+    const RefArgs ra = {refs->m, refs->refs, refs->ref_index, refs->centres, refs->hist_flag, refs->flags};
+    return forward_async_rgb(h, slot, n, io, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, &ra, out_ab, &ev);
+}
+
+int idc_forward_async_dist_score(idc_handle h, int slot, int n, const idc_ref_image* images, const int32_t* hint_offsets, const idc_hint* hints,
+                                 int mode, float mask_value, float maskcent, float l_cent, unsigned flags, const idc_batch_refs* refs,
+                                 uint8_t* const* rgb_out, float* out_ab, uint64_t* sse, float* hint_colours, const idc_dist_taps* taps,
+                                 const idc_dist_score_spec* spec, const float* centres, const idc_dist_score_out* out) {
+    const BatchIO io = {true, 0, 0, nullptr, nullptr, images, rgb_out};
+    const EvalArgs ev = {sse, hint_colours, true, taps, true, spec, centres, out};
     if (!refs) return forward_async_rgb(h, slot, n, io, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, nullptr, out_ab, &ev);
     const RefArgs ra = {refs->m, refs->refs, refs->ref_index, refs->centres, refs->hist_flag, refs->flags};
     return forward_async_rgb(h, slot, n, io, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, &ra, out_ab, &ev);

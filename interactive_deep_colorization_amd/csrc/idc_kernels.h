@@ -327,6 +327,11 @@ hipError_t launch_reveal_hints(const unsigned char* src, const ImgDesc* imgs, co
 hipError_t launch_ragged_net_truth(const unsigned char* src, const ImgDesc* imgs, int n, int H, int W, unsigned char* rgb_net, hipStream_t s);
 hipError_t launch_eval_sse(const unsigned char* res, const unsigned char* truth, const ImgDesc* imgs, int n, long long hw, long long max_pixels,
                            long long total_pixels, unsigned long long* sse, hipStream_t s);
+// Distribution scores, the ground truth (idc_colour.hip, beside the reveal kernel whose device functions and summation order it shares): truth
+// [n][2][(H/s)*(W/s)] fp32 = reveal_hints' colour of every cell's s x s rectangle (s = 1 or 4), bit for bit; image i of the packed run imgs, or
+// (imgs == nullptr, n == 1) the single [src_h,src_w,3] source at src.
+hipError_t launch_dist_truth(const unsigned char* src, const ImgDesc* imgs, int n, int src_h, int src_w, int H, int W, int s, float* truth,
+                             hipStream_t st);
 
 // Colour suggestions at one pixel (get_ab_reccs, colorize_image.py:322-354): see idc_session.hip for the algorithm.
 // pdf bin b at pdf[b*stride]; centres [B][2]; out_centres [K][2], out_conf [K] (f64); out_counts [B] or nullptr.
@@ -352,6 +357,14 @@ hipError_t launch_dist_decode(const float* dist, int n, int B, int npix, int mod
 // peaks [n][P][2] = (cy*s + s/2, cx*s + s/2) or (-1, -1), peak_ent [n][P] (or nullptr); work [n][Hd*Wd] floats of scratch.
 hipError_t launch_dist_peaks(const float* ent, const float* mask, int n, int Hd, int Wd, int s, int P, int radius, float* work, int* peaks,
                              float* peak_ent, hipStream_t st);
+// Distribution scores (include/ideepcolor.h, idc_dist_score: definitions 2-7) of dist [n][B][npix] against truth [n][2][npix] (launch_dist_truth):
+// the nn nearest of centres [B][2] per cell, cross-entropy against their soft encoding, rank of the nearest bin.  part [n][ceil(npix/64)] doubles of
+// scratch: the block sums; xent [n] = their fixed-order fold (a second, one-wave-per-image launch); hits [n][ranks.n] (or nullptr with ranks.n
+// == 0; zeroed here on the same stream); xent_map / rank_map / target [n][npix] may each be nullptr.  B <= kSuggestMaxBins, nn in 1..min(16, B).
+struct ScoreRanks { int n; int thr[8]; };
+hipError_t launch_dist_score(const float* dist, const float* truth, const float* centres, int n, int B, int npix, int nn, float sigma,
+                             ScoreRanks ranks, double* part, double* xent, unsigned* hits, double* xent_map, int* rank_map, int* target,
+                             hipStream_t st);
 
 // Range audit (idc_audit.hip; idc_set_range_audit): one layer's sticky record in device memory, and the streaming reduction that folds a stored
 // tensor into it -- npix pixels of [parts][Cpad] 16-bit values (bf16, or fp16 when f16; value = sum of the parts) or, parts = 0, of [Cpad] fp32;

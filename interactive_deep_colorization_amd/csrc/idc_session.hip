@@ -14,8 +14,14 @@
 //  * distribution batches -- get_ab_reccs for many pixels in one launch (suggest_batch_kernel: the same body, a workgroup per query) and the
 //    question compute_entropy's map is plotted for, "where is the model least sure", answered on the device (dist_peaks_kernel).
 //
+//  * distribution scores -- the question the heads were trained on (NNEncode of the ground-truth ab + softmax cross-entropy,
+//    caffe_files/color_quantization.py:7-33, caffe_traininglayers.py:161-189): cross-entropy against the soft-encoded truth and the rank of the
+//    true bin per cell, top-k hit counts and a fixed-order sum per image (dist_score_kernel, dist_score_finish_kernel).
+//
 // The first two are latency kernels (one pixel per thread / one workgroup); neither touches HBM beyond the planes it writes.
 #include <hip/hip_runtime.h>
+
+#include <cfloat>
 
 #include "idc_kernels.h"
 
@@ -457,6 +463,150 @@ hipError_t launch_dist_decode(const float* dist, int n, int B, int npix, int mod
                               float* conf, hipStream_t s) {
     hipLaunchKernelGGL(dist_decode_kernel, dim3((npix + kDistPix - 1) / kDistPix, n), dim3(kDistWaves * kDistPix), 0, s, dist, B, npix, mode,
                        gamma, centres, ab, conf);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Distribution scores (idc_dist_score / idc_forward_async_dist_score): how much probability did the head put on the colour the pixel really has.
+// The contract, per image i and cell c of dist [n][B][npix] with truth [n][2][npix] = the cell's ground-truth (a*, b*) fp32 (dist_truth_kernel,
+// idc_colour.hip: idc_reveal_hints' colour of the cell's rectangle, bit for bit) and centres [B][2] fp32:
+//   neighbours q_1 .. q_nn: the nn centres nearest to the truth, d^2 = da * da + db * db in float64 from the fp32 values (no FMA), ascending,
+//                           ties to the lower index; t = q_1 is the target bin.  (Ordered by d^2: as by d, but for two d^2 that share a root.)
+//   weights    w_j = exp(-d_j^2 / (2 sigma^2)) / sum_k exp(-d_k^2 / (2 sigma^2)), float64, k ascending; exactly 1 for nn == 1
+//   xent       = 0 - sum_j w_j * log(max(p[q_j], FLT_MIN)), float64 log, products and sum, j ascending (Caffe's softmax-loss floor: finite)
+//   rank       = #{q : p[q] > p[t] || (p[q] == p[t] && q < t)}, 0 .. B - 1
+//   hits[i][j] = #{cells of image i : rank < thr[j]}: integer atomics, exact in any order
+//   xent[i]    = the cells' values summed in a FIXED order, no float atomics: blocks of 64 consecutive cells (this kernel's workgroups; the last one
+//                padded with +0.0) folded by halves (c with c + 32, then + 16, ... + 1) into part [n][nblk]; then dist_score_finish_kernel, one
+//                wave per image: lane l adds the block sums l, l + 64, ... in ascending order onto +0.0, and the 64 lanes fold by halves.
+// Geometry: dist_entropy_kernel's -- blockIdx.y = image, a workgroup owns kDistPix consecutive cells, lane = cell in the streaming phases.
+//   phase 0  the neighbours.  Eight lanes share a cell (thread t: cell t / 8, lane t % 8 walks centres t % 8, + 8, ... held in LDS): nn passes of
+//            "the nearest after (d^2, index) of the pass before", each a strided walk and a three-step butterfly over the eight lanes on the total
+//            order (d^2, index).  No per-thread array of candidates (a dynamically indexed one would live in scratch); the lists meet in LDS.
+//   phase 1  wave w takes the neighbours j = w, w + 8: one gather p[q_j], its log and the exp term, into LDS.
+//   phase 2  the streamed count: wave w walks bins [w * chunk, min(B, (w + 1) * chunk)) against p[t], one coalesced 256-byte row per load;
+//            the eight counts meet in LDS, wave 0 adds them, forms xent in j order, writes the maps, votes the hits and folds the block sum.
+// A workgroup's dead lanes (the last block) read the image's last cell and write nothing.
+// ------------------------------------------------------------------------------------------------
+constexpr int kScoreMaxNN = 16;
+
+__global__ __launch_bounds__(kDistWaves * kDistPix) void dist_score_kernel(const float* __restrict__ dist, const float* __restrict__ truth,
+                                                                           const float* __restrict__ centres, int B, int npix, int nn, float sigma,
+                                                                           ScoreRanks ranks, double* __restrict__ part, unsigned* __restrict__ hits,
+                                                                           double* __restrict__ xent_map, int* __restrict__ rank_map,
+                                                                           int* __restrict__ target) {
+#pragma clang fp contract(off)
+    __shared__ float cen[2 * kSuggestMaxBins];
+    __shared__ int nq[kScoreMaxNN][kDistPix];
+    __shared__ double nd[kScoreMaxNN][kDistPix];       // d^2 of neighbour j, then its exp term
+    __shared__ double nl[kScoreMaxNN][kDistPix];       // log(max(p[q_j], FLT_MIN))
+    __shared__ int cnt[kDistWaves][kDistPix];
+    const int tid = threadIdx.x, img = blockIdx.y, pix0 = blockIdx.x * kDistPix;
+    for (int i = tid; i < 2 * B; i += kDistWaves * kDistPix) cen[i] = centres[i];
+    __syncthreads();
+    {
+        const int cell = tid >> 3, sub = tid & 7;
+        const int pc = min(pix0 + cell, npix - 1);
+        const double ta = (double)truth[(size_t)img * 2 * npix + pc], tb = (double)truth[((size_t)img * 2 + 1) * npix + pc];
+        double pd = -1.0; int pi = -1;                  // the pass before: every d^2 >= 0 comes after it
+        for (int j = 0; j < nn; ++j) {
+            double bd = __builtin_inf(); int bi = 0x7fffffff;
+            for (int b = sub; b < B; b += 8) {
+                const double da = ta - (double)cen[2 * b], db = tb - (double)cen[2 * b + 1];
+                const double d = da * da + db * db;
+                if ((d > pd || (d == pd && b > pi)) && d < bd) { bd = d; bi = b; }      // ascending b: the first of equals is kept
+            }
+#pragma unroll
+            for (int o = 1; o < 8; o <<= 1) {
+                const double od = __shfl_xor(bd, o, 64); const int oi = __shfl_xor(bi, o, 64);
+                if (od < bd || (od == bd && oi < bi)) { bd = od; bi = oi; }
+            }
+            if (sub == 0) { nq[j][cell] = bi < B ? bi : B - 1; nd[j][cell] = bd; }       // (no candidate: a NaN truth; keeps the gather inside)
+            pd = bd; pi = bi;
+        }
+    }
+    __syncthreads();
+    const int lane = tid % kDistPix, w = __builtin_amdgcn_readfirstlane(tid / kDistPix);   // wave-uniform: bin indices stay scalar
+    const int pix = pix0 + lane;
+    const bool live = pix < npix;
+    const float* src = dist + (size_t)img * B * npix + (live ? pix : npix - 1);
+    const int t = nq[0][lane];
+    const float pt = src[(size_t)t * npix];
+    const double two_s2 = 2.0 * ((double)sigma * (double)sigma);
+    for (int j = w; j < nn; j += kDistWaves) {
+        const float p = src[(size_t)nq[j][lane] * npix];
+        nl[j][lane] = log((double)(p > FLT_MIN ? p : FLT_MIN));
+        nd[j][lane] = exp(-nd[j][lane] / two_s2);
+    }
+    const int chunk = (B + kDistWaves - 1) / kDistWaves;
+    const int b0 = w * chunk, b1 = min(B, b0 + chunk);
+    int c = 0;
+#pragma unroll 4
+    for (int b = b0; b < b1; ++b) {
+        const float p = src[(size_t)b * npix];
+        c += (p > pt || (p == pt && b < t)) ? 1 : 0;
+    }
+    cnt[w][lane] = c;
+    __syncthreads();
+    if (w != 0) return;
+    int rank = cnt[0][lane];
+#pragma unroll
+    for (int k = 1; k < kDistWaves; ++k) rank += cnt[k][lane];
+    double xe;
+    if (nn == 1) {
+        xe = 0.0 - nl[0][lane];
+    } else {
+        double sum = 0.0, acc = 0.0;
+        for (int j = 0; j < nn; ++j) sum += nd[j][lane];
+        for (int j = 0; j < nn; ++j) acc += (nd[j][lane] / sum) * nl[j][lane];
+        xe = 0.0 - acc;
+    }
+    if (live) {
+        const size_t at = (size_t)img * npix + pix;
+        if (xent_map) xent_map[at] = xe;
+        if (rank_map) rank_map[at] = rank;
+        if (target) target[at] = t;
+    } else {
+        xe = 0.0;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        if (j < ranks.n) {
+            const unsigned long long m = __ballot(live && rank < ranks.thr[j]);
+            if (lane == 0 && m) atomicAdd(&hits[(size_t)img * ranks.n + j], (unsigned)__popcll(m));
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) xe += __shfl_down(xe, o, 64);
+    if (lane == 0) part[(size_t)img * gridDim.x + blockIdx.x] = xe;
+}
+
+// xent[i] from image i's nblk block sums: lane l of the one wave adds part[l], part[l + 64], ... in ascending order onto +0.0, the lanes fold by halves.
+__global__ __launch_bounds__(64) void dist_score_finish_kernel(const double* __restrict__ part, int nblk, double* __restrict__ xent) {
+    const double* p = part + (size_t)blockIdx.x * nblk;
+    double s = 0.0;
+    for (int k = threadIdx.x; k < nblk; k += 64) s += p[k];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+    if (threadIdx.x == 0) xent[blockIdx.x] = s;
+}
+
+hipError_t launch_dist_score(const float* dist, const float* truth, const float* centres, int n, int B, int npix, int nn, float sigma,
+                             ScoreRanks ranks, double* part, double* xent, unsigned* hits, double* xent_map, int* rank_map, int* target,
+                             hipStream_t st) {
+    if (!dist || !truth || !centres || !part || !xent || n <= 0 || npix <= 0 || B < 1 || B > kSuggestMaxBins || nn < 1 || nn > kScoreMaxNN || nn > B ||
+        ranks.n < 0 || ranks.n > 8 || (ranks.n > 0 && !hits))
+        return hipErrorInvalidValue;
+    const int nblk = (npix + kDistPix - 1) / kDistPix;
+    if (ranks.n > 0) {
+        const hipError_t e = hipMemsetAsync(hits, 0, (size_t)n * ranks.n * sizeof(unsigned), st);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(dist_score_kernel, dim3(nblk, n), dim3(kDistWaves * kDistPix), 0, st, dist, truth, centres, B, npix, nn, sigma, ranks, part,
+                       hits, xent_map, rank_map, target);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(dist_score_finish_kernel, dim3(n), dim3(64), 0, st, (const double*)part, nblk, xent);
     return hipGetLastError();
 }
 

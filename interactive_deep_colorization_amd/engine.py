@@ -348,7 +348,53 @@ def dist_queries(queries, seed=0):
 
 class DistBatch(object):
     """What ``forward_async_dist`` returns: the arrays a distribution batch fills, valid after the slot's ``wait``; ``None`` where not asked for."""
-    sse = hint_colours = out_rgb = out_ab = peaks = peak_ent = entropy = sugg_centres = sugg_conf = None
+    sse = hint_colours = out_rgb = out_ab = peaks = peak_ent = entropy = sugg_centres = sugg_conf = score = None
+
+
+class DistScore(object):
+    """What ``dist_score`` returns and ``forward_async_dist(score=...)`` fills (``DistBatch.score``): ``xent`` (n,) float64 = the SUM of the
+    cells' cross-entropies per image (``mean()`` divides by the cell count), ``hits`` (n, len(ranks)) uint32 = cells whose true bin is among the
+    head's ranks[j] most probable, and with the maps asked for ``xent_map`` (n,Hd,Wd) float64, ``rank_map`` / ``target`` (n,Hd,Wd) int32 and
+    ``truth_ab`` (n,2,Hd,Wd) float32; ``None`` otherwise."""
+    xent = hits = xent_map = rank_map = target = truth_ab = None
+    cells = 0
+
+    def mean(self):
+        """Mean cross-entropy per image, (n,) float64."""
+        return np.asarray(self.xent, np.float64) / float(self.cells)
+
+    def rates(self):
+        """Top-k rates per image, (n, len(ranks)) float64."""
+        return np.asarray(self.hits, np.float64) / float(self.cells)
+
+
+def score_spec(nn=1, sigma=5.0, ranks=(1, 5)):
+    """``N.DistScoreSpec`` of a distribution score: ``nn`` neighbours and ``sigma`` of the soft encoding, up to 8 top-k thresholds."""
+    ranks = [int(r) for r in ranks]
+    if len(ranks) > N.IDC_SCORE_MAX_RANKS:
+        raise ValueError("%d rank thresholds, more than %d" % (len(ranks), N.IDC_SCORE_MAX_RANKS))
+    spec = N.DistScoreSpec()
+    spec.nn, spec.sigma, spec.n_ranks = int(nn), float(sigma), len(ranks)
+    for j, r in enumerate(ranks):
+        spec.ranks[j] = r
+    return spec
+
+
+def score_buffers(n, grid, n_ranks, want_maps, take):
+    """(``DistScore`` with its arrays allocated by ``take(shape, dtype)``, the ``N.DistScoreOut`` that points into them)."""
+    res, out = DistScore(), N.DistScoreOut()
+    res.cells = int(grid[0]) * int(grid[1])
+    res.xent = take((n,), np.float64)
+    out.xent = res.xent.ctypes.data
+    res.hits = take((n, n_ranks), np.uint32)
+    if n_ranks:
+        out.hits = res.hits.ctypes.data
+    if want_maps:
+        res.xent_map, res.rank_map = take((n,) + tuple(grid), np.float64), take((n,) + tuple(grid), np.int32)
+        res.target, res.truth_ab = take((n,) + tuple(grid), np.int32), take((n, 2) + tuple(grid), np.float32)
+        out.xent_map, out.rank_map = res.xent_map.ctypes.data, res.rank_map.ctypes.data
+        out.target, out.truth_ab = res.target.ctypes.data, res.truth_ab.ctypes.data
+    return res, out
 
 
 def ref_images(refs):
@@ -776,6 +822,18 @@ class HipColorizer(object):
                                            _fptr(c), _fptr(ab), _fptr(conf) if want_conf else None))
         return (ab, conf) if want_conf else ab
 
+    def dist_score(self, centres, n=1, nn=1, sigma=5.0, ranks=(1, 5), want_maps=False):
+        """How much probability the head put on the colours the pixels really have (``idc_dist_score``): the resident distribution of images
+        0..n-1 against the ground-truth images ``set_image_rgb(..., keep_source=True)`` left in slots 0..n-1, on the device.  Per cell the
+        truth is the mean ab under it (``reveal_hints``' colour), soft-encoded over its ``nn`` nearest ``centres`` (B,2) with a Gaussian of
+        ``sigma`` (the training layers' NNEncode; nn = 1: the nearest bin alone), scored by cross-entropy and by the rank of the nearest bin.
+        Returns a ``DistScore``: ``xent`` sums, ``hits`` per threshold of ``ranks``, and the per-cell maps with ``want_maps``."""
+        c = _f32c(centres, (self.dist_bins(), 2))
+        spec = score_spec(nn, sigma, ranks)
+        res, out = score_buffers(int(n), self._dist_grid(), spec.n_ranks, want_maps, lambda shape, dtype: np.empty(shape, dtype))
+        self._chk(self.lib.idc_dist_score(self._h, int(n), ctypes.byref(spec), _fptr(c), ctypes.byref(out)))
+        return res
+
     def global_histogram(self, rgb, centres, want_sat=True):
         """Global statistics of reference image(s) (the reference's global_stats.prototxt): rgb (n,H,W,3) or (H,W,3)
         uint8, centres (313,2) -> (hist (n,313) float32 summing to 1, s_avg (n,) mean HSV saturation or None)."""
@@ -1055,7 +1113,7 @@ class HipColorizer(object):
     def forward_async_dist(self, slot, images, hints, out_rgb=None, out_ab=None, mode="ab", mask_value=1.0, maskcent=0.0, l_cent=50.0,
                            out="net", refs=None, ref_index=None, ref_centres=None, hist_flag=1.0, saturation=False, want_rgb=False,
                            want_sse=False, peaks=8, radius=2, skip_hints=False, queries=None, K=5, N_draws=25000, seed=0, centres=None,
-                           want_entropy=False):
+                           want_entropy=False, score=None):
         """``forward_async_eval`` on an engine with a distribution head that also runs the head and reads it on the device
         (``idc_forward_async_dist``).  Images, hints (mode 'ab', 'rgb' or 'reveal'), outputs and reference arguments as there
         (``ref_centres``: the (313,2) centres of the reference statistics); ``want_sse`` asks for the score.  Behind the network the slot
@@ -1064,9 +1122,14 @@ class HipColorizer(object):
         in this batch and seed defaulting to ``seed`` + row, or ``"peaks"``: at every peak, straight from the device buffer, peak (i, k) with
         seed ``seed + i * peaks + k``.  ``centres`` (B,2): the bin centres, needed with queries.  Returns a ``DistBatch`` whose arrays
         (sse, hint_colours, out_rgb, peaks (n,P,2), peak_ent (n,P), entropy (n,Hd,Wd), sugg_centres (Q,K,2), sugg_conf (Q,K); ``None`` where not
-        asked for) are valid after ``wait(slot)``.  Afterwards the resident distribution (``get_dist``, ``dist_at`` ...) is this batch's."""
+        asked for) are valid after ``wait(slot)``.  Afterwards the resident distribution (``get_dist``, ``dist_at`` ...) is this batch's.
+        ``score``: ``None``, or a dict of ``dist_score``'s arguments (centres, nn, sigma, ranks, want_maps) -- the batch's distribution is then
+        also scored against the batch's own images behind the other taps (``idc_forward_async_dist_score``) and ``DistBatch.score`` is the
+        ``DistScore``; with peaks=0, no queries and no entropy map only the score runs."""
         taps = dict(peaks=int(peaks), radius=int(radius), skip_hints=bool(skip_hints), queries=queries, K=int(K), N=int(N_draws), seed=int(seed),
                     centres=centres, want_entropy=bool(want_entropy), want_sse=bool(want_sse))
+        if score is not None:
+            taps["score"] = dict(score)
         return self._enqueue_images("forward_async_dist", slot, images, hints, out_rgb, out_ab, mode, mask_value, maskcent, l_cent, out,
                                     refs, ref_index, ref_centres, hist_flag, saturation, evaluate=True, want_rgb=want_rgb or out_rgb is not None,
                                     taps=taps)
@@ -1157,7 +1220,19 @@ class HipColorizer(object):
             t.centres = c.ctypes.data if c is not None else None
             res.sugg_centres, res.sugg_conf = self._pool.take((Q, t.K, 2), np.float64), self._pool.take((Q, t.K), np.float64)
             t.sugg_centres, t.sugg_conf = res.sugg_centres.ctypes.data, res.sugg_conf.ctypes.data
-        self._chk(self.lib.idc_forward_async_dist(*(args + (ctypes.byref(t),))))
+        sc = taps.get("score")
+        if sc is None:
+            self._chk(self.lib.idc_forward_async_dist(*(args + (ctypes.byref(t),))))
+        else:
+            unknown = set(sc) - {"centres", "nn", "sigma", "ranks", "want_maps"}
+            if unknown or "centres" not in sc:
+                raise ValueError("score is a dict of centres[, nn, sigma, ranks, want_maps]; got %s" % sorted(sc))
+            sc_c = _f32c(sc["centres"], (self.dist_bins(), 2))
+            spec = score_spec(sc.get("nn", 1), sc.get("sigma", 5.0), sc.get("ranks", (1, 5)))
+            res.score, sout = score_buffers(n, hd_wd, spec.n_ranks, bool(sc.get("want_maps", False)), self._pool.take)
+            only_score = P == 0 and Q == 0 and not taps["want_entropy"]
+            self._chk(self.lib.idc_forward_async_dist_score(*(args + (None if only_score else ctypes.byref(t), ctypes.byref(spec), _fptr(sc_c),
+                                                                      ctypes.byref(sout)))))
         self._in_flight[int(slot)] = (images, out_rgb, out_ab, res)
         return res
 
@@ -1343,6 +1418,68 @@ class HipColorizer(object):
                     for r in finish(k & 1):
                         yield r
                 submit(k & 1, group, done)
+                k += 1
+            for slot in (k & 1, (k + 1) & 1):       # the older batch first
+                if pending[slot] is not None:
+                    for r in finish(slot):
+                        yield r
+        finally:                                    # a consumer that stops early: nothing stays in flight on buffers about to be recycled
+            for slot in (0, 1):
+                if pending[slot] is not None:
+                    pending[slot] = None
+                    self.wait(slot)
+
+    def score_images(self, items, centres, batch=None, nn=1, sigma=5.0, ranks=(1, 5), mode="reveal", want_psnr=False, **kw):
+        """Generator: score the distribution head on a stream of ground-truth colour images with both pipeline slots busy --
+        ``evaluate_images`` for the distribution (``forward_async_dist`` with ``score`` and no other tap).  An item is ``rgb`` or
+        ``(rgb, rects)``, hints as in ``evaluate_images`` (mode 'reveal': the colours come from the image).  Per image it yields
+        ``(xent_mean, hits, psnr)``: the mean cross-entropy of its cells against the (soft-)encoded truth, ``hits`` (len(ranks),) uint32 =
+        cells whose true bin is among the ranks[j] most probable, and with ``want_psnr`` the net-size PSNR of the regression head
+        (``None`` otherwise).  A few dozen bytes per image come back; no image and no distribution does.  ``kw``: mask_value, maskcent, l_cent."""
+        from .evaluate import psnr_from_sse
+        batch = self.max_batch if batch is None else int(batch)
+        if not 1 <= batch <= self.max_batch:
+            raise ValueError("batch %d outside 1..%d" % (batch, self.max_batch))
+        score = dict(centres=centres, nn=nn, sigma=sigma, ranks=tuple(ranks))
+        pending = [None, None]                      # per slot: (DistBatch, pinned sources) of the batch in flight
+
+        def finish(slot):
+            self.wait(slot)
+            (res, _), pending[slot] = pending[slot], None
+            mean, hits = res.score.mean(), np.array(res.score.hits)
+            sse = np.array(res.sse) if want_psnr else None
+            return [(float(mean[i]), hits[i], psnr_from_sse(sse[i], self.H, self.W) if want_psnr else None) for i in range(len(mean))]
+
+        def submit(slot, group):
+            srcs = self._pinned_slices([g[0].shape for g in group])
+            for s, g in zip(srcs, group):
+                np.copyto(s, g[0])
+            res = self.forward_async_dist(slot, srcs, [g[1] for g in group], mode=mode, want_sse=bool(want_psnr), peaks=0, score=score, **kw)
+            pending[slot] = (res, srcs)
+
+        def parse(item):
+            item = (item,) if isinstance(item, np.ndarray) else tuple(item)
+            rgb = np.asarray(item[0])
+            if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.size == 0:
+                raise ValueError("score_images needs uint8 (h,w,3) images, got %s %s" % (rgb.dtype, rgb.shape))
+            return rgb, item[1] if len(item) > 1 else None
+
+        k, group = 0, []
+        try:
+            for item in items:
+                group.append(parse(item))
+                if len(group) < batch:
+                    continue
+                if pending[k & 1] is not None:
+                    for r in finish(k & 1):
+                        yield r
+                submit(k & 1, group)
+                k, group = k + 1, []
+            if group:
+                if pending[k & 1] is not None:
+                    for r in finish(k & 1):
+                        yield r
+                submit(k & 1, group)
                 k += 1
             for slot in (k & 1, (k + 1) & 1):       # the older batch first
                 if pending[slot] is not None:

@@ -122,3 +122,24 @@ def psnr_sweep(engine, images, counts=(0, 1, 2, 5, 10, 20, 50, 100), seed=0, out
         for j, (psnr, _) in enumerate(engine.evaluate_images(items, batch=batch, out=out, mode="reveal")):
             table[r, j] = psnr
     return (table, points) if return_rects else table
+
+
+def likelihood_sweep(engine, images, centres, counts=(0, 1, 2, 5, 10, 20, 50, 100), seed=0, nn=1, sigma=5.0, ranks=(1, 5), batch=None):
+    """How revealed hints sharpen the distribution: the likelihood-versus-points table of ``images`` on ``engine`` (a ``HipColorizer`` with a
+    distribution head and weights), from ``HipColorizer.score_images``.  The simulated user is ``psnr_sweep(strategy='random')``'s: image j's
+    points are ``simulate_points(engine.H, engine.W, max(counts), RandomState(seed + j))`` and count c reveals the first c of them.
+    Returns ``(xent, rates)``: xent (len(counts), len(images)) float64 = the mean cross-entropy of the image's cells against the ground truth
+    encoded over its ``nn`` nearest ``centres`` (B,2) with ``sigma``; rates (len(counts), len(images), len(ranks)) float64 = the share of
+    cells whose true bin is among the head's ranks[j] most probable.  Row means over the images are the curve."""
+    images = list(images)
+    most = max(counts) if len(counts) else 0
+    points = [simulate_points(engine.H, engine.W, most, np.random.RandomState(seed + j)) for j in range(len(images))]
+    hd, wd = engine._dist_grid()
+    xent = np.zeros((len(counts), len(images)), np.float64)
+    rates = np.zeros((len(counts), len(images), len(ranks)), np.float64)
+    for r, c in enumerate(counts):
+        items = ((img, pts[:c]) for img, pts in zip(images, points))
+        for j, (mean, hits, _) in enumerate(engine.score_images(items, centres, batch=batch, nn=nn, sigma=sigma, ranks=ranks, mode="reveal")):
+            xent[r, j] = mean
+            rates[r, j] = np.asarray(hits, np.float64) / float(hd * wd)
+    return xent, rates
