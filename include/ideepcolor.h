@@ -415,6 +415,45 @@ enum { IDC_SRC_NO_AB = 3 };               /* joins IDC_SRC_*: a = b = 0 */
 enum { IDC_L_IMAGE = 0, IDC_L_MASK50 = 1 };
 int idc_fullres_rgb(idc_handle h, int img, int source, int interp, int l_mode, uint8_t* rgb);
 
+/* ---- edge-aware full-resolution output: joint bilateral ab upsampling (Kopf et al. 2007), guided by the source's own L.  Opt-in: with it
+ *      off (the default) no launch and no output byte of any call changes.  The linear zoom above ignores the edges of the full-resolution
+ *      L: on a 4x source one net-size pixel of ab is smeared over +-4 source pixels across every object boundary.
+ *      THE RULE, for one image: source [h,w,3] uint8; net-size planes a_lo, b_lo [H,W], the planes `source` names, float64 or float32 as
+ *      today; net-size guide L_lo[j,i] = (double)Lplane[j,i] + (double)l_cent, where Lplane is the fp32 plane the ingestion wrote for that
+ *      image and l_cent is the value it was ingested with; parameters R, sigma_s, sigma_r.  For output pixel (y, x):
+ *        L = rgb2lab(source pixel)[0], exactly as IDC_L_IMAGE computes it.
+ *        u = (y + 0.5) * ((double)H / h) - 0.5 and v = (x + 0.5) * ((double)W / w) - 0.5: half-pixel centres, the geometry of the ingestion
+ *            rule, not the corner-aligned geometry of scipy's zoom.
+ *        j0 = (int)floor(u + 0.5) and i0 = (int)floor(v + 0.5).
+ *        Taps are j = j0 - R .. j0 + R (outer loop) and i = i0 - R .. i0 + R (inner loop).  A tap outside [0, H) x [0, W) is skipped.
+ *        Per tap: ws = exp(-((j - u)^2 + (i - v)^2) / (2 sigma_s^2)); d = L - L_lo[j,i];
+ *                 wt = ws * (exp(-(d * d) / (2 sigma_r^2)) + IDC_JOINT_EPS), IDC_JOINT_EPS = 1e-6: where every range weight underflows the
+ *                 rule degrades to the spatial Gaussian, not to 0/0;  num_a += wt * a_lo, num_b += wt * b_lo, den += wt.
+ *        a = num_a / den and b = num_b / den, then the Lab -> RGB of every other route.
+ *      Everything is float64 with fp contract(off).  den > 0 always, because tap (j0, i0) lies inside the image for every h, w >= 1.  (The
+ *      kernel computes ws as the product of the two one-dimensional Gaussians, the same value to a few ulp.)
+ *      Defaults: R = 2, sigma_s = 1.0 (net-size pixels), sigma_r = 8.0 (L units): plausible values from the literature.  NOBODY HAS
+ *      MEASURED THEM ON TRAINED WEIGHTS: this repository has none.
+ *      idc_set_joint_upsample: the parameters, handle state.  IDC_ERR_INVALID_ARG unless radius is in 1..4, sigma_s in [0.25, 8] and
+ *      sigma_r in [0.5, 100] (a NaN is outside); a refused call changes nothing.
+ *      IDC_INTERP_JOINT joins IDC_INTERP_* for idc_fullres_rgb: it needs l_mode == IDC_L_IMAGE, else IDC_ERR_INVALID_ARG; IDC_SRC_NO_AB
+ *      stays a = b = 0.  The handle remembers per image slot the l_cent of its last idc_set_image_rgb, and a slot has a resident source only
+ *      while that ingestion's L plane is intact, so the guide is defined whenever the call is legal.  idc_upsample_lab2rgb keeps refusing
+ *      3: its L is the caller's, it has no guide.
+ *      idc_fullres_ab: the interpolated ab map at the source size, ab [2,src_h,src_w] float64, for any of the four interps: what
+ *      idc_fullres_rgb feeds to Lab -> RGB.  Same residency rules and statuses as idc_fullres_rgb (NULL ab: IDC_ERR_INVALID_ARG).
+ *      idc_set_batch_upsample: IDC_INTERP_LINEAR (default) or IDC_INTERP_JOINT, anything else IDC_ERR_INVALID_ARG.  Handle state, copied
+ *      into the slot together with the joint parameters when a pipelined call is enqueued: changing either while a slot is in flight
+ *      affects later calls only.  While it is JOINT every source-size output (IDC_BATCH_OUT_SOURCE) of idc_forward_async_rgb, _rgb_ref,
+ *      _images, _eval, _dist and _dist_score uses the rule above, guided by the slot's own L plane and the call's l_cent, and is bit for bit
+ *      idc_fullres_rgb(IDC_SRC_OUTPUT_AB, IDC_INTERP_JOINT, IDC_L_IMAGE) of the blocking route per image; the sse of an evaluation batch
+ *      then scores the joint image. */
+enum { IDC_INTERP_JOINT = 3 };            /* joins IDC_INTERP_*: idc_fullres_rgb, idc_fullres_ab, idc_set_batch_upsample */
+#define IDC_JOINT_EPS 1e-6
+int idc_set_joint_upsample(idc_handle h, int radius, double sigma_s, double sigma_r);
+int idc_fullres_ab(idc_handle h, int img, int source, int interp, double* ab);
+int idc_set_batch_upsample(idc_handle h, int interp);
+
 /* ---- pipelined batches from uint8 images: the serving form of the two calls above on the two slots of idc_forward_async.
  *      rgb_in [n,src_h,src_w,3] uint8 and per-image hint lists in, colourised uint8 images out; idc_wait completes the call and
  *      idc_pipeline_times reports its stages (H2D: the images, the offsets and the hints; compute: the prologue kernel, the

@@ -38,10 +38,12 @@ EXPORTED_SYMBOLS = [
     "idc_dist_peaks", "idc_suggest_colors_batch", "idc_forward_async_dist",
     "idc_dist_score", "idc_forward_async_dist_score",
     "idc_gamut_map", "idc_snap_colors",
+    "idc_set_joint_upsample", "idc_fullres_ab", "idc_set_batch_upsample",
     "idc_set_range_audit", "idc_range_reset", "idc_range_report", "idc_pack_weights_ex", "idc_load_weights_ex",
 ]
 IDC_STORE_NONE, IDC_STORE_F32, IDC_STORE_BF16, IDC_STORE_F16 = 0, 1, 2, 3
 IDC_INTERP_CUBIC, IDC_INTERP_LINEAR, IDC_INTERP_NEAREST = 0, 1, 2
+IDC_INTERP_JOINT, IDC_JOINT_EPS = 3, 1e-6       # idc_fullres_rgb, idc_fullres_ab, idc_set_batch_upsample
 IDC_SRC_OUTPUT_AB, IDC_SRC_OUTPUT_AB_RAW, IDC_SRC_INPUT_AB, IDC_SRC_NO_AB = 0, 1, 2, 3
 IDC_INGEST_KEEP_SOURCE = 1
 IDC_L_IMAGE, IDC_L_MASK50 = 0, 1
@@ -233,6 +235,9 @@ def load():
                                                ctypes.POINTER(DistScoreSpec), c_float_p, ctypes.POINTER(DistScoreOut)])
     proto("idc_gamut_map", ci, [vp, ci, vp, ci, ci, vp, vp, vp])
     proto("idc_snap_colors", ci, [vp, ci, vp, vp, vp, vp, vp])
+    proto("idc_set_joint_upsample", ci, [vp, ci, ctypes.c_double, ctypes.c_double])
+    proto("idc_fullres_ab", ci, [vp, ci, ci, ci, vp])
+    proto("idc_set_batch_upsample", ci, [vp, ci])
     proto("idc_set_range_audit", ci, [vp, ci])
     proto("idc_range_reset", ci, [vp])
     proto("idc_range_report", ci, [vp, ci, ctypes.POINTER(RangeInfo)])

@@ -601,6 +601,18 @@ class ColorizeImageBase(object):
                 self._dev_out_valid = False
         return lab2rgb_transpose(self.img_l_fullres, self._up(self.output_ab, 1))
 
+    def get_img_fullres_joint(self):
+        """``get_img_fullres`` with the edge-aware upsampling of ``output_ab`` (``HipColorizer.fullres_rgb(interp='joint')``: joint
+        bilateral, guided by the full-resolution L; parameters: ``self.net.set_joint_upsample``).  Not in the reference.  Device route
+        only: the image was set through ``load_image_device`` / ``set_image_device`` and the last forward's map is still on the device;
+        there is no host twin to fall back to, so anything else is an error."""
+        if not (self._out_on_device() and self._source_on_device()):
+            raise RuntimeError('get_img_fullres_joint needs load_image_device / set_image_device and the result of the last net_forward '
+                               'on the device')
+        out = self.net.fullres_rgb('output_ab', 'joint', 'image', img=0)
+        self._l_serial = getattr(self.net, 'l_serial', None)      # (the call itself moved it)
+        return out
+
     def get_input_img_fullres(self):
         if self._in_on_device():
             dev = self._fullres_device('input_ab', 'linear', 'image')

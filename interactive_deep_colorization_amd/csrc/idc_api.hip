@@ -844,7 +844,7 @@ int idc_set_image_rgb(idc_handle h, int img, int n, int src_h, int src_w, const 
         for (int i = 0; i < n; ++i) {
             auto& sl = h->src[img + i];
             HIPCHK(h, sl.d_rgb.ensure(sb));
-            sl.h = src_h; sl.w = src_w;
+            sl.h = src_h; sl.w = src_w; sl.l_cent = l_cent;
             h->h_src_ptrs.get()[i] = sl.d_rgb.get();
         }
     } else {
@@ -870,15 +870,18 @@ int idc_set_image_rgb(idc_handle h, int img, int n, int src_h, int src_w, const 
     return IDC_OK;
 }
 
-int idc_fullres_rgb(idc_handle h, int img, int source, int interp, int l_mode, uint8_t* rgb) {
+// idc_fullres_rgb (rgb) and idc_fullres_ab (ab): one list of checks, one residency rule
+static int fullres(idc_handle h, int img, int source, int interp, int l_mode, uint8_t* rgb, double* ab, bool want_ab) {
     int rc = check_img(h, img);
     if (rc) return rc;
-    if (interp < 0 || interp > 2) return fail(&h->err, IDC_ERR_INVALID_ARG, "interp %d not in 0..2", interp);
+    if (interp < 0 || interp > IDC_INTERP_JOINT) return fail(&h->err, IDC_ERR_INVALID_ARG, "interp %d not in 0..3", interp);
     if (l_mode != IDC_L_IMAGE && l_mode != IDC_L_MASK50) return fail(&h->err, IDC_ERR_INVALID_ARG, "l_mode %d not in 0..1", l_mode);
+    if (interp == IDC_INTERP_JOINT && l_mode != IDC_L_IMAGE)
+        return fail(&h->err, IDC_ERR_INVALID_ARG, "IDC_INTERP_JOINT is guided by the L of the source pixels: it needs IDC_L_IMAGE");
     if (source < IDC_SRC_OUTPUT_AB || source > IDC_SRC_NO_AB) return fail(&h->err, IDC_ERR_INVALID_ARG, "source %d not in 0..3", source);
     const auto& sl = h->src[img];
     if (!sl.d_rgb.get()) return fail(&h->err, IDC_ERR_UNSUPPORTED, "image slot %d has no resident source (idc_set_image_rgb with IDC_INGEST_KEEP_SOURCE)", img);
-    if (!rgb) return fail(&h->err, IDC_ERR_INVALID_ARG, "null rgb");
+    if (want_ab ? !ab : !rgb) return fail(&h->err, IDC_ERR_INVALID_ARG, want_ab ? "null ab" : "null rgb");
     HIPCHK(h, hipSetDevice(h->device));
     const void *pa = nullptr, *pb = nullptr; int f64 = 0;
     if (source != IDC_SRC_NO_AB) {
@@ -887,6 +890,22 @@ int idc_fullres_rgb(idc_handle h, int img, int source, int interp, int l_mode, u
     }
     rc = drain_pipeline(h);
     if (rc) return rc;
+    const size_t hw = (size_t)h->H * h->W;
+    if (want_ab) {
+        const size_t nbytes = (size_t)sl.h * sl.w * 2 * sizeof(double);
+        const bool direct = is_pinned(ab);
+        if (h->d_full_ab.bytes() < nbytes) {
+            HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+            HIPCHK(h, h->d_full_ab.ensure(nbytes));
+        }
+        if (!direct) HIPCHK(h, h->h_full_ab.ensure(h->d_full_ab.bytes()));
+        HIPCHK(h, launch_joint_fullres(sl.d_rgb.get(), nullptr, 1, sl.h, sl.w, joint_tiles(sl.h, sl.w), pa, pb, f64, 0, h->d_L.get() + (size_t)img * hw,
+                                       sl.l_cent, h->H, h->W, interp, h->joint, nullptr, h->d_full_ab.get(), h->stream.get()));
+        HIPCHK(h, hipMemcpyAsync(direct ? ab : h->h_full_ab.get(), h->d_full_ab.get(), nbytes, hipMemcpyDeviceToHost, h->stream.get()));
+        HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+        if (!direct) memcpy(ab, h->h_full_ab.get(), nbytes);
+        return IDC_OK;
+    }
     const size_t nbytes = (size_t)sl.h * sl.w * 3;
     const bool direct = is_pinned(rgb);                    // a pinned result buffer is written in place; a pageable one through pinned staging
     if (h->d_full_rgb.bytes() < nbytes) {
@@ -894,11 +913,41 @@ int idc_fullres_rgb(idc_handle h, int img, int source, int interp, int l_mode, u
         HIPCHK(h, h->d_full_rgb.ensure(nbytes));
     }
     if (!direct) HIPCHK(h, h->h_full_rgb.ensure(h->d_full_rgb.bytes()));
-    const float* mask = l_mode == IDC_L_MASK50 ? h->d_mask.get() + (size_t)img * h->H * h->W : nullptr;
-    HIPCHK(h, launch_fullres_rgb(sl.d_rgb.get(), sl.h, sl.w, pa, pb, f64, h->H, h->W, interp, mask, h->hint_mask_value[img], h->d_full_rgb.get(), h->stream.get()));
+    const float* mask = l_mode == IDC_L_MASK50 ? h->d_mask.get() + (size_t)img * hw : nullptr;
+    if (interp == IDC_INTERP_JOINT && pa)
+        HIPCHK(h, launch_joint_fullres(sl.d_rgb.get(), nullptr, 1, sl.h, sl.w, joint_tiles(sl.h, sl.w), pa, pb, f64, 0, h->d_L.get() + (size_t)img * hw,
+                                       sl.l_cent, h->H, h->W, interp, h->joint, h->d_full_rgb.get(), nullptr, h->stream.get()));
+    else        // (IDC_SRC_NO_AB has nothing to interpolate: a = b = 0 whatever the interp)
+        HIPCHK(h, launch_fullres_rgb(sl.d_rgb.get(), sl.h, sl.w, pa, pb, f64, h->H, h->W, interp == IDC_INTERP_JOINT ? IDC_INTERP_LINEAR : interp, mask,
+                                     h->hint_mask_value[img], h->d_full_rgb.get(), h->stream.get()));
     HIPCHK(h, hipMemcpyAsync(direct ? rgb : h->h_full_rgb.get(), h->d_full_rgb.get(), nbytes, hipMemcpyDeviceToHost, h->stream.get()));
     HIPCHK(h, hipStreamSynchronize(h->stream.get()));
     if (!direct) memcpy(rgb, h->h_full_rgb.get(), nbytes);
+    return IDC_OK;
+}
+
+int idc_fullres_rgb(idc_handle h, int img, int source, int interp, int l_mode, uint8_t* rgb) {
+    return fullres(h, img, source, interp, l_mode, rgb, nullptr, false);
+}
+
+int idc_fullres_ab(idc_handle h, int img, int source, int interp, double* ab) {
+    return fullres(h, img, source, interp, IDC_L_IMAGE, nullptr, ab, true);
+}
+
+int idc_set_joint_upsample(idc_handle h, int radius, double sigma_s, double sigma_r) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (radius < 1 || radius > 4) return fail(&h->err, IDC_ERR_INVALID_ARG, "radius %d outside 1..4", radius);
+    if (!(sigma_s >= 0.25 && sigma_s <= 8.0)) return fail(&h->err, IDC_ERR_INVALID_ARG, "sigma_s %g outside 0.25..8", sigma_s);
+    if (!(sigma_r >= 0.5 && sigma_r <= 100.0)) return fail(&h->err, IDC_ERR_INVALID_ARG, "sigma_r %g outside 0.5..100", sigma_r);
+    h->joint = {radius, 2.0 * sigma_s * sigma_s, 2.0 * sigma_r * sigma_r};
+    return IDC_OK;
+}
+
+int idc_set_batch_upsample(idc_handle h, int interp) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (interp != IDC_INTERP_LINEAR && interp != IDC_INTERP_JOINT)
+        return fail(&h->err, IDC_ERR_INVALID_ARG, "interp %d is neither IDC_INTERP_LINEAR nor IDC_INTERP_JOINT", interp);
+    h->batch_interp = interp;
     return IDC_OK;
 }
 

@@ -1,5 +1,5 @@
 // idc_colour.hip -- colour space, display and layout helpers around the forward pass: Lab -> RGB, the fused upsample + Lab -> RGB of the display step,
-// the global-statistics extractor, image ingestion (uint8 RGB -> net-size Lab, full-resolution RGB from the resident source), the global hints of
+// the global-statistics extractor, image ingestion (uint8 RGB -> net-size Lab, full-resolution RGB from the resident source, linear or joint bilateral), the global hints of
 // reference photographs (statistics of m references of individual sizes, the rows of the net's global input), the colour picker's
 // gamut map and colour snapping, the PCIe copy kernel and the NCHW <-> NHWC (split) converters.
 #include <stdlib.h>
@@ -695,6 +695,174 @@ hipError_t launch_ragged_fullres_rgb(const unsigned char* src, const ImgDesc* im
     const long long ngroups = (total + 3) >> 2;
     const int blocks = grid_blocks(GridTag::ragged_fullres_rgb, (ngroups + 255) / 256, 8192);
     hipLaunchKernelGGL(ragged_fullres_rgb_kernel, dim3(blocks), dim3(256), 0, s, src, imgs, n, lab_q, H, W, interp, rgb);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// joint bilateral ab upsampling (Kopf et al. 2007; include/ideepcolor.h states the rule): the net-size ab planes go to the source size under
+// the guidance of the source's own L, so that chroma stops at the edges of the full-resolution image instead of being smeared across them.
+// ONE kernel for idc_fullres_rgb(IDC_INTERP_JOINT), idc_fullres_ab (any interp) and the source-size epilogue of the pipelined calls.
+//   tile      a workgroup owns 32 x 8 output pixels of one image (blockIdx.y), one per thread; workgroups past the image's own tile count exit.
+//   weights   the spatial Gaussian is separable and a tile has 8 rows and 32 columns: (8 + 32)(2R + 1) exps per TILE, kept in LDS, instead of
+//             (2R + 1)^2 per pixel.  Only the range weight costs an exp per tap.
+//   taps      adjacent pixels share nearly all of their taps, so the tile's net-size footprint of (L_lo, a_lo, b_lo) is staged once in LDS as
+//             float64: rows j0(first row) - R .. j0(last row) + R, likewise columns.  j0 advances by at most floor(7 H/h) + 1 over a tile,
+//             so when the source is no smaller than the net (the use of an UPsampler) the footprint is at most 18 x 42 = 756 cells at R = 4:
+//             3 x 6 KB.  A tile whose footprint is larger (h < H or w < W: several net-size pixels per output pixel) reads its taps from
+//             global memory.  The choice is uniform over the workgroup and does not change a bit: both branches hand the same float64
+//             operands to the same expressions.
+//   LDS       18.1 KB footprint + 2 KB sRGB table + 2.8 KB weights + 0.8 KB result bytes = 23.7 KB: six workgroups (24 waves) per CU by LDS.
+//   stores    the tile's result bytes cross LDS; a row of the tile is 96 consecutive bytes of the image that start on any residue mod 4 (an
+//             image of the packed run starts at byte 3 * first), so each row goes out as up to 3 head bytes, up to 24 aligned dwords and up
+//             to 3 tail bytes: no dword reaches into a neighbouring tile or image.
+// imgs == nullptr: n images of sh x sw packed back to back (the same-size batch; n = 1: the blocking calls).
+// ------------------------------------------------------------------------------------------------
+constexpr int kJointTW = 32, kJointTH = 8, kJointMaxR = 4, kJointMaxTaps = 2 * kJointMaxR + 1, kInterpJoint = 3;
+constexpr int kJointCells = (kJointTH + 2 * kJointMaxR + 2) * (kJointTW + 2 * kJointMaxR + 2);
+
+// half-pixel centre of output index i on an axis of scale sc = in / out: u, and the nearest net-size index floor(u + .5)
+__device__ __forceinline__ int joint_centre(int i, double sc, double& u) {
+#pragma clang fp contract(off)
+    u = ((double)i + 0.5) * sc - 0.5;
+    return (int)floor(u + 0.5);
+}
+
+template <typename S>
+__global__ __launch_bounds__(256) void joint_fullres_kernel(const unsigned char* __restrict__ src, const ImgDesc* __restrict__ imgs, int sh, int sw,
+                                                            const S* __restrict__ pa, const S* __restrict__ pb, long long plane_stride,
+                                                            const float* __restrict__ Lp, float l_cent, int H, int W, int interp, JointParams jp,
+                                                            unsigned char* __restrict__ rgb, double* __restrict__ ab_out) {
+#pragma clang fp contract(off)
+    __shared__ double tab[256];
+    __shared__ double sL[kJointCells], sA[kJointCells], sB[kJointCells];
+    __shared__ double wys[kJointTH][kJointMaxTaps], wxs[kJointTW][kJointMaxTaps];
+    __shared__ unsigned char outb[kJointTH][kJointTW * 3];
+    const int img = blockIdx.y;
+    ImgDesc d;
+    if (imgs != nullptr) {
+        d = imgs[img];
+    } else {
+        d.h = sh; d.w = sw; d.first = (long long)img * sh * sw; d.off = d.first * 3;
+    }
+    const int tiles_x = (d.w + kJointTW - 1) / kJointTW, tiles_y = (d.h + kJointTH - 1) / kJointTH;
+    if ((long long)blockIdx.x >= (long long)tiles_x * tiles_y) return;        // uniform over the workgroup: this image has fewer tiles than the largest
+    fill_srgb_table(tab);
+    const int ty0 = (int)(blockIdx.x / tiles_x) * kJointTH, tx0 = (int)(blockIdx.x % tiles_x) * kJointTW;
+    const int tx = threadIdx.x & (kJointTW - 1), ty = threadIdx.x / kJointTW;
+    const int y = ty0 + ty, x = tx0 + tx;
+    const bool valid = y < d.h && x < d.w;
+    const long long HW = (long long)H * W;
+    const S* ia = pa != nullptr ? pa + (long long)img * plane_stride : nullptr;
+    const S* ib = pa != nullptr ? pb + (long long)img * plane_stride : nullptr;
+    const bool joint = interp == kInterpJoint && ia != nullptr;
+    const float* iL = joint ? Lp + (long long)img * HW : nullptr;
+    const int R = jp.R, T = 2 * R + 1;
+    const double sy = (double)H / (double)d.h, sx = (double)W / (double)d.w;
+    bool staged = false;
+    int fj0 = 0, fi0 = 0, fc = 0;
+    if (joint) {
+        for (int t = threadIdx.x; t < (kJointTH + kJointTW) * kJointMaxTaps; t += 256) {
+            const int r = t / kJointMaxTaps, k = t - r * kJointMaxTaps;
+            if (k >= T) continue;
+            double u;
+            const int c0 = r < kJointTH ? joint_centre(ty0 + r, sy, u) : joint_centre(tx0 + r - kJointTH, sx, u);
+            const double dd = (double)(c0 - R + k) - u;
+            const double wgt = exp(-(dd * dd) / jp.two_ss);
+            if (r < kJointTH) wys[r][k] = wgt; else wxs[r - kJointTH][k] = wgt;
+        }
+        double u_;
+        const int y_last = ty0 + kJointTH - 1 < d.h ? ty0 + kJointTH - 1 : d.h - 1, x_last = tx0 + kJointTW - 1 < d.w ? tx0 + kJointTW - 1 : d.w - 1;
+        fj0 = joint_centre(ty0, sy, u_) - R; fi0 = joint_centre(tx0, sx, u_) - R;
+        const int fr = joint_centre(y_last, sy, u_) + R - fj0 + 1;
+        fc = joint_centre(x_last, sx, u_) + R - fi0 + 1;
+        staged = (long long)fr * fc <= kJointCells;
+        if (staged) {
+            for (int c = threadIdx.x; c < fr * fc; c += 256) {
+                const int jj = fj0 + c / fc, ii = fi0 + c % fc;
+                if (jj < 0 || jj >= H || ii < 0 || ii >= W) continue;        // a tap outside the image is skipped, so its cell is never read
+                const long long g = (long long)jj * W + ii;
+                sL[c] = (double)iL[g] + (double)l_cent; sA[c] = (double)ia[g]; sB[c] = (double)ib[g];
+            }
+        }
+        __syncthreads();
+    }
+    double L = 0.0, a = 0.0, b = 0.0;
+    if (valid) {
+        const unsigned char* q = src + d.off + ((long long)y * d.w + x) * 3;
+        const double lin[3] = {tab[q[0]], tab[q[1]], tab[q[2]]};
+        double a_, b_;
+        linear_to_lab(lin, L, a_, b_);
+        if (joint) {
+            double u, v;
+            const int j0 = joint_centre(y, sy, u), i0 = joint_centre(x, sx, v);
+            double num_a = 0.0, num_b = 0.0, den = 0.0;
+            for (int kj = 0; kj < T; ++kj) {
+                const int j = j0 - R + kj;
+                if (j < 0 || j >= H) continue;
+                const double wy = wys[ty][kj];
+                for (int ki = 0; ki < T; ++ki) {
+                    const int i = i0 - R + ki;
+                    if (i < 0 || i >= W) continue;
+                    double Lc, ac, bc;
+                    if (staged) {
+                        const int c = (j - fj0) * fc + (i - fi0);
+                        Lc = sL[c]; ac = sA[c]; bc = sB[c];
+                    } else {
+                        const long long g = (long long)j * W + i;
+                        Lc = (double)iL[g] + (double)l_cent; ac = (double)ia[g]; bc = (double)ib[g];
+                    }
+                    const double ws = wy * wxs[tx][ki], dl = L - Lc;
+                    const double wt = ws * (exp(-(dl * dl) / jp.two_sr) + 1e-6);       // IDC_JOINT_EPS
+                    num_a += wt * ac; num_b += wt * bc; den += wt;
+                }
+            }
+            a = num_a / den; b = num_b / den;
+        } else if (ia != nullptr) {
+            double ab[2];
+            interp_ab(ia, ib, H, W, interp, y, x, d.h, d.w, ab);
+            a = ab[0]; b = ab[1];
+        }
+        if (ab_out != nullptr) {
+            const long long np = (long long)d.h * d.w, p = (long long)y * d.w + x;
+            ab_out[d.first * 2 + p] = a; ab_out[d.first * 2 + np + p] = b;
+        }
+    }
+    if (rgb == nullptr) return;
+    unsigned char o[3] = {0, 0, 0};
+    if (valid) lab_to_rgb_u8(L, a, b, o);
+    outb[ty][tx * 3 + 0] = o[0]; outb[ty][tx * 3 + 1] = o[1]; outb[ty][tx * 3 + 2] = o[2];
+    __syncthreads();
+    if (y >= d.h) return;
+    const int tw = d.w - tx0 < kJointTW ? d.w - tx0 : kJointTW, nb = tw * 3;
+    unsigned char* g = rgb + d.off + ((long long)y * d.w + tx0) * 3;
+    const int mis = (int)((4 - ((uintptr_t)g & 3)) & 3), head = mis < nb ? mis : nb;
+    const int ndw = (nb - head) >> 2, tail = nb - head - ndw * 4;
+    const unsigned char* row = outb[ty];
+    if (tx < ndw) {             // at most 24 dwords: lanes 0..23
+        const unsigned char* s4 = row + head + tx * 4;
+        ((unsigned*)(g + head))[tx] = (unsigned)s4[0] | ((unsigned)s4[1] << 8) | ((unsigned)s4[2] << 16) | ((unsigned)s4[3] << 24);
+    } else if (tx >= 24) {      // lanes 24..26 the head bytes, 27..29 the tail bytes
+        const int k = tx - 24;
+        if (k < head) g[k] = row[k];
+        else if (k >= 3 && k - 3 < tail) g[head + ndw * 4 + k - 3] = row[head + ndw * 4 + k - 3];
+    }
+}
+
+hipError_t launch_joint_fullres(const unsigned char* src, const ImgDesc* imgs, int n, int sh, int sw, long long max_tiles, const void* a_plane,
+                                const void* b_plane, int src_f64, long long plane_stride, const float* Lp, float l_cent, int H, int W, int interp,
+                                JointParams jp, unsigned char* rgb, double* ab_out, hipStream_t s) {
+    if (n <= 0 || n > 65535 || src == nullptr || (imgs == nullptr && (sh <= 0 || sw <= 0)) || max_tiles <= 0 || max_tiles > 0x7fffffffll ||
+        interp < 0 || interp > kInterpJoint || (rgb == nullptr && ab_out == nullptr) || (a_plane == nullptr) != (b_plane == nullptr))
+        return hipErrorInvalidValue;
+    if (interp == kInterpJoint && a_plane != nullptr && (Lp == nullptr || jp.R < 1 || jp.R > kJointMaxR || !(jp.two_ss > 0.0) || !(jp.two_sr > 0.0)))
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)max_tiles, (unsigned)n);
+    if (src_f64)
+        hipLaunchKernelGGL(joint_fullres_kernel<double>, grid, dim3(256), 0, s, src, imgs, sh, sw, (const double*)a_plane, (const double*)b_plane,
+                           plane_stride, Lp, l_cent, H, W, interp, jp, rgb, ab_out);
+    else
+        hipLaunchKernelGGL(joint_fullres_kernel<float>, grid, dim3(256), 0, s, src, imgs, sh, sw, (const float*)a_plane, (const float*)b_plane,
+                           plane_stride, Lp, l_cent, H, W, interp, jp, rgb, ab_out);
     return hipGetLastError();
 }
 

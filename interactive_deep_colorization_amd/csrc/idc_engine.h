@@ -198,7 +198,8 @@ struct idc_context {
     std::vector<char> l_set;             // per image slot: d_L holds an uploaded L plane (idc_forward_resident refuses otherwise)
     // image ingestion (idc_set_image_rgb / idc_fullres_rgb): per slot the uint8 source kept on the device (IDC_INGEST_KEEP_SOURCE; empty = none)
     // and its size, and the mask_value of the slot's last idc_set_hints (0 = never had hints)
-    struct SlotSource { DevMem<unsigned char> d_rgb; int h = 0, w = 0; };
+    // ... and the l_cent of that ingestion: with the slot's L plane it is the guide of the joint upsampling (a source is resident only while that plane is intact)
+    struct SlotSource { DevMem<unsigned char> d_rgb; int h = 0, w = 0; float l_cent = 0.f; };
     std::vector<SlotSource> src;
     std::vector<float> hint_mask_value;
     DevMem<unsigned char> d_ingest;                                  // upload buffer of the sources that are not kept
@@ -207,6 +208,11 @@ struct idc_context {
     DevMem<unsigned char> d_net_rgb; DevMem<double> d_net_lab;       // idc_set_image_rgb results [max_batch,H,W,3] u8, [max_batch,3,H,W] f64 (first use)
     DevMem<unsigned char> d_full_rgb;    // idc_fullres_rgb result ...
     PinnedMem<unsigned char> h_full_rgb; // ... and (pageable callers) its pinned staging, as large
+    DevMem<double> d_full_ab;            // idc_fullres_ab result [2,src_h,src_w] ...
+    PinnedMem<double> h_full_ab;         // ... and its pinned staging
+    // joint bilateral upsampling: idc_set_joint_upsample's parameters and idc_set_batch_upsample's interp; a pipelined call takes its copy when it is enqueued
+    JointParams joint = {2, 2.0 * 1.0 * 1.0, 2.0 * 8.0 * 8.0};
+    int batch_interp = 1;                // IDC_INTERP_LINEAR
     DevMem<unsigned char> d_pick;        // idc_gamut_map / idc_snap_colors: inputs + results of one call, device and pinned
     PinnedMem<unsigned char> h_pick;
     Event ev_sync;                       // idc_stream_wait / idc_stream_signal
@@ -225,6 +231,7 @@ struct idc_context {
         Event ev_in, ev_comp, ev_out;
         Event ev_in0, ev_comp0, ev_out0;                                               // stage starts (idc_pipeline_times)
         bool pending = false, staged_out = false, timed = false;
+        int up_interp = 1; JointParams up_joint = {2, 2.0, 128.0};                     // the source-size upsampling the batch in flight was enqueued with
         float* user_out = nullptr; int n = 0;
         // idc_forward_async_rgb: the batch's packed uint8 source, its offsets + clipped hint list (one block: int[n+1], then HintRect[] at
         // rgb_meta_hints), the net-size result, the refreshed Lab and the source-size result (IDC_BATCH_OUT_SOURCE); grown on demand

@@ -884,7 +884,14 @@ static int forward_async_rgb(idc_handle h, int slot, int n, const BatchIO& io, c
     if (rc) return rc;
     if (!dist && !((h->flags & IDC_FLAG_DIST313) && h->keep_dist313)) h->dist_n = dist_n;      // no distribution was written: the blocking forward's stays resident
     HIPCHK(h, launch_lab_post(sl.d_L.get(), l_cent, sl.d_out.get(), sl.d_rgb.get(), source_out ? sl.d_labq.get() : nullptr, n, h->H, h->W, h->stream.get()));
-    if (source_out && ragged)
+    sl.up_interp = h->batch_interp; sl.up_joint = h->joint;       // the handle's setting as it is now: a later idc_set_batch_upsample does not reach this batch
+    if (source_out && sl.up_interp == IDC_INTERP_JOINT) {           // guide: the slot's own L plane and this call's l_cent
+        long long max_tiles = ragged ? 0 : joint_tiles(io.src_h, io.src_w);
+        for (int i = 0; ragged && i < n; ++i) max_tiles = std::max(max_tiles, joint_tiles(io.images[i].h, io.images[i].w));
+        const double* pa = sl.d_labq.get() + hw;
+        HIPCHK(h, launch_joint_fullres(sl.d_src.get(), ragged ? d_tab : nullptr, n, io.src_h, io.src_w, max_tiles, pa, pa + hw, 1, (long long)(3 * hw),
+                                       sl.d_L.get(), l_cent, h->H, h->W, IDC_INTERP_JOINT, sl.up_joint, sl.d_full.get(), nullptr, h->stream.get()));
+    } else if (source_out && ragged)
         HIPCHK(h, launch_ragged_fullres_rgb(sl.d_src.get(), d_tab, n, (long long)(in_bytes / 3), sl.d_labq.get(), h->H, h->W, IDC_INTERP_LINEAR,
                                             sl.d_full.get(), h->stream.get()));
     else if (source_out)

@@ -315,6 +315,18 @@ hipError_t launch_ragged_prologue(const unsigned char* src, const ImgDesc* imgs,
 hipError_t launch_ragged_fullres_rgb(const unsigned char* src, const ImgDesc* imgs, int n, long long total, const double* lab_q, int H, int W,
                                      int interp, unsigned char* rgb, hipStream_t s);
 
+// Joint bilateral ab upsampling (idc_fullres_rgb with IDC_INTERP_JOINT, idc_fullres_ab, the source-size epilogue of the pipelined calls while
+// idc_set_batch_upsample is JOINT; idc_colour.hip; the rule: include/ideepcolor.h).  One workgroup per 32 x 8 output tile on an exact grid
+// dim3(max_tiles, n): max_tiles = joint_tiles of the largest image.  imgs: the ImgDesc run as above, or nullptr: n images of sh x sw packed back
+// to back.  Image i reads the planes a_plane / b_plane + i * plane_stride elements ([H,W] fp32 or fp64; both nullptr: a = b = 0) and, for
+// interp 3, the guide Lp + i * H * W (fp32, L - l_cent) with jp = {R, 2 sigma_s^2, 2 sigma_r^2}; interp 0..2: launch_fullres_rgb's rules.
+// -> rgb (packed as src is, any alignment; or nullptr) and ab_out (or nullptr): image i's [2,h,w] f64 at 2 * first_i.
+struct JointParams { int R; double two_ss, two_sr; };
+inline long long joint_tiles(int h, int w) { return (long long)((h + 7) / 8) * ((w + 31) / 32); }
+hipError_t launch_joint_fullres(const unsigned char* src, const ImgDesc* imgs, int n, int sh, int sw, long long max_tiles, const void* a_plane,
+                                const void* b_plane, int src_f64, long long plane_stride, const float* Lp, float l_cent, int H, int W, int interp,
+                                JointParams jp, unsigned char* rgb, double* ab_out, hipStream_t s);
+
 // Evaluation batches (idc_reveal_hints / idc_forward_async_eval; idc_colour.hip).  reveal_hints: (c0, c1) of each of the n_rects clipped
 // rectangles of `hints` = the float64 mean ab (rounded once to fp32) of its image's net-size pixels under it, one workgroup per rectangle, fixed
 // summation order, cost = the rectangle's area; the image is the single [src_h,src_w,3] source at src (imgs == nullptr) or image i of the packed

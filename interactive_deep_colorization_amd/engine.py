@@ -20,6 +20,9 @@ _PREC = {"fp32": N.IDC_FP32, "f32": N.IDC_FP32, "float32": N.IDC_FP32, 0: N.IDC_
          "fp16x3": N.IDC_FP16X3, 4: N.IDC_FP16X3, "fp16": N.IDC_FP16, 5: N.IDC_FP16}
 
 
+_INTERP = {"cubic": N.IDC_INTERP_CUBIC, "linear": N.IDC_INTERP_LINEAR, "nearest": N.IDC_INTERP_NEAREST, "joint": N.IDC_INTERP_JOINT}
+
+
 def _fptr(a):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
 
@@ -464,6 +467,7 @@ class HipColorizer(object):
         self.l_serial = 0                   # bumped by every call that may write image slot 0's L plane (set_image_l and every forward): api.py's resident L
         self._src_shape = {}                # image slot -> (h, w) of the source set_image_rgb(keep_source=True) left on the device
         self.before_overwrite = None        # callable run ONCE right before the next such call: whoever still wants the resident results fetches them
+        self._batch_upsample = "linear"     # what set_batch_upsample last set: the source-size upsampling of the pipelined calls
 
     # ---- lifetime -------------------------------------------------------------------------
     def close(self):
@@ -647,11 +651,12 @@ class HipColorizer(object):
     def fullres_rgb(self, source="output_ab", interp="linear", l_mode="image", img=0):
         """The full-resolution getters from the resident source of slot ``img`` (``idc_fullres_rgb``) -> (src_h, src_w, 3) uint8.
         source: 'output_ab', 'output_ab_raw', 'input_ab' as in ``upsample_lab2rgb``, or 'no_ab' (a = b = 0); interp: 'cubic', 'linear',
-        'nearest'; l_mode: 'image' (L of the source pixel) or 'mask50' (50 x the nearest-upsampled hint mask).  IdcError (UNSUPPORTED)
+        'nearest', or 'joint' (the joint bilateral upsampling of ``set_joint_upsample``, guided by the source's own L; needs l_mode 'image');
+        l_mode: 'image' (L of the source pixel) or 'mask50' (50 x the nearest-upsampled hint mask).  IdcError (UNSUPPORTED)
         when the slot has no resident source: ``set_image_rgb(keep_source=True)`` first, and nothing else may have written its L plane."""
         src = {"output_ab": N.IDC_SRC_OUTPUT_AB, "output_ab_raw": N.IDC_SRC_OUTPUT_AB_RAW, "input_ab": N.IDC_SRC_INPUT_AB,
                "no_ab": N.IDC_SRC_NO_AB}[source]
-        itp = {"cubic": N.IDC_INTERP_CUBIC, "linear": N.IDC_INTERP_LINEAR, "nearest": N.IDC_INTERP_NEAREST}[interp]
+        itp = _INTERP[interp]
         lm = {"image": N.IDC_L_IMAGE, "mask50": N.IDC_L_MASK50}[l_mode]
         shape = self._src_shape.get(int(img))
         self.l_serial += 1
@@ -666,6 +671,47 @@ class HipColorizer(object):
                 self._src_shape.pop(int(img), None)
             raise
         return rgb
+
+    def fullres_ab(self, source="output_ab", interp="joint", img=0):
+        """The ab map ``fullres_rgb`` hands to Lab -> RGB (``idc_fullres_ab``): the planes ``source`` names resized to the resident source's
+        size by ``interp`` ('cubic', 'linear', 'nearest', 'joint') -> (2, src_h, src_w) float64.  Residency and errors as in ``fullres_rgb``."""
+        src = {"output_ab": N.IDC_SRC_OUTPUT_AB, "output_ab_raw": N.IDC_SRC_OUTPUT_AB_RAW, "input_ab": N.IDC_SRC_INPUT_AB,
+               "no_ab": N.IDC_SRC_NO_AB}[source]
+        itp = _INTERP[interp]
+        shape = self._src_shape.get(int(img))
+        if shape is None:
+            self._chk(self.lib.idc_fullres_ab(self._h, int(img), src, itp, None))
+            raise N.IdcError(-7, "the source of image slot %d was not ingested through this object" % img)
+        ab = self._pool.take((2,) + shape, np.float64)
+        try:
+            self._chk(self.lib.idc_fullres_ab(self._h, int(img), src, itp, ab.ctypes.data_as(ctypes.c_void_p)))
+        except N.IdcError as ex:
+            if ex.status == -7 and "resident source" in str(ex):
+                self._src_shape.pop(int(img), None)
+            raise
+        return ab
+
+    def set_joint_upsample(self, radius=2, sigma_s=1.0, sigma_r=8.0):
+        """Parameters of the joint bilateral upsampling (``idc_set_joint_upsample``): taps within ``radius`` (1..4) net-size pixels, spatial
+        sigma ``sigma_s`` in net-size pixels (0.25..8), range sigma ``sigma_r`` in L units (0.5..100).  The defaults are plausible values from
+        the literature; nobody has measured them on trained weights.  A pipelined call keeps the values it was enqueued with."""
+        self._chk(self.lib.idc_set_joint_upsample(self._h, int(radius), float(sigma_s), float(sigma_r)))
+
+    def set_batch_upsample(self, interp="linear"):
+        """How the pipelined calls bring ab to the source size with out='source' (``idc_set_batch_upsample``): 'linear' (default, the
+        reference's zoom) or 'joint'.  Handle state; a batch in flight keeps what it was enqueued with."""
+        if interp not in ("linear", "joint"):
+            raise ValueError("set_batch_upsample takes 'linear' or 'joint', got %r" % (interp,))
+        self._chk(self.lib.idc_set_batch_upsample(self._h, _INTERP[interp]))
+        self._batch_upsample = interp
+
+    def _upsample_scope(self, upsample):
+        """The ``upsample=`` keyword of the streaming generators: set the state now, return what to restore (None: leave it alone)."""
+        if upsample is None:
+            return None
+        prev = self._batch_upsample
+        self.set_batch_upsample(upsample)
+        return prev
 
     # ---- colour picker (data/lab_gamut.py): no weights needed, nothing resident is read or written ---------
     def gamut_map(self, L, gamut_size=110, D=1, want_pts=False):
@@ -1036,7 +1082,7 @@ class HipColorizer(object):
                                                                    N.IDC_REF_SATURATION if saturation else 0) + tail)))
         self._in_flight[int(slot)] = (rgb, out_rgb, out_ab)      # the library reads / writes them until the slot's wait
 
-    def colorize_stream(self, batches, out="net", **kw):
+    def colorize_stream(self, batches, out="net", upsample=None, **kw):
         """Generator: colourise a stream of uint8 batches with both pipeline slots busy.  ``batches`` yields (rgb (n,h,w,3) uint8, hints) items
         (``hints`` as in ``forward_async_rgb``; n and the source size may change from item to item); each item's (n,H,W,3) [out='net'] or
         (n,h,w,3) [out='source'] uint8 result is yielded in input order, as an array of the caller's own (copied out of the pinned buffer the
@@ -1044,7 +1090,9 @@ class HipColorizer(object):
         maskcent, l_cent of ``forward_async_rgb``.
         An item may be (rgb, hints, refs) on a ``global_hints`` engine: ``refs`` is a list of n entries, each ``None`` or an (h,w,3) uint8
         reference photograph for that image.  The same array OBJECT given for several images of an item is uploaded once (``dedupe_refs``);
-        ``kw`` then also carries centres (needed), hist_flag and saturation.  A two-entry item makes the plain call."""
+        ``kw`` then also carries centres (needed), hist_flag and saturation.  A two-entry item makes the plain call.
+        ``upsample``: 'linear' or 'joint' -- ``set_batch_upsample`` before the first batch, the previous setting back when the generator
+        ends or is abandoned; None (default) leaves the setting alone."""
         pending = [None, None]                      # per slot: (pinned result, pinned source) of the batch in flight
 
         def finish(slot):
@@ -1053,6 +1101,7 @@ class HipColorizer(object):
             return np.array(res)
 
         k = 0
+        restore = self._upsample_scope(upsample)
         try:
             for item in batches:
                 rgb, hints = item[0], item[1]
@@ -1076,10 +1125,14 @@ class HipColorizer(object):
                 if pending[slot] is not None:
                     yield finish(slot)
         finally:                                    # a consumer that stops early: nothing stays in flight on buffers about to be recycled
-            for slot in (0, 1):
-                if pending[slot] is not None:
-                    pending[slot] = None
-                    self.wait(slot)
+            try:
+                for slot in (0, 1):
+                    if pending[slot] is not None:
+                        pending[slot] = None
+                        self.wait(slot)
+            finally:
+                if restore is not None:
+                    self.set_batch_upsample(restore)
 
     def _pinned_slices(self, shapes):
         """One pinned pool block (a multiple of 64 KiB, so that blocks of ragged batches recycle) sliced into uint8 arrays of ``shapes``."""
@@ -1236,14 +1289,15 @@ class HipColorizer(object):
         self._in_flight[int(slot)] = (images, out_rgb, out_ab, res)
         return res
 
-    def colorize_images(self, items, batch=None, out="source", **kw):
+    def colorize_images(self, items, batch=None, out="source", upsample=None, **kw):
         """Generator: colourise a stream of single images of any sizes with both pipeline slots busy.  An item is ``rgb``, ``(rgb, hints)`` or
         ``(rgb, hints, ref)``: rgb (h,w,3) uint8, ``hints`` that image's hint list (rows as in ``set_hints``) or ``None``, ``ref`` ``None`` or an
         (h,w,3) uint8 reference photograph (a ``global_hints`` engine; ``kw`` then carries centres).  Consecutive items are grouped into
         batches of ``batch`` images (default ``max_batch``; the last may be shorter), batch k runs on slot k % 2 while batch k - 1 computes
         (``forward_async_images``), and one array per image is yielded in input order: (h,w,3) [out='source'] or (H,W,3) [out='net'], the
         caller's own copy.  Sources travel through one pinned pool block per batch; the same reference OBJECT given for several images of a
-        batch is uploaded once (``dedupe_refs``).  ``kw``: mode, mask_value, maskcent, l_cent, centres, hist_flag, saturation."""
+        batch is uploaded once (``dedupe_refs``).  ``kw``: mode, mask_value, maskcent, l_cent, centres, hist_flag, saturation.
+        ``upsample``: as in ``colorize_stream`` ('joint': the edge-aware source-size output)."""
         batch = self.max_batch if batch is None else int(batch)
         if not 1 <= batch <= self.max_batch:
             raise ValueError("batch %d outside 1..%d" % (batch, self.max_batch))
@@ -1274,6 +1328,7 @@ class HipColorizer(object):
             return rgb, item[1] if len(item) > 1 else None, item[2] if len(item) > 2 else None, len(item) > 2
 
         k, group = 0, []
+        restore = self._upsample_scope(upsample)
         try:
             for item in items:
                 group.append(parse(item))
@@ -1295,18 +1350,23 @@ class HipColorizer(object):
                     for r in finish(slot):
                         yield r
         finally:                                    # a consumer that stops early: nothing stays in flight on buffers about to be recycled
-            for slot in (0, 1):
-                if pending[slot] is not None:
-                    pending[slot] = None
-                    self.wait(slot)
+            try:
+                for slot in (0, 1):
+                    if pending[slot] is not None:
+                        pending[slot] = None
+                        self.wait(slot)
+            finally:
+                if restore is not None:
+                    self.set_batch_upsample(restore)
 
-    def evaluate_images(self, items, batch=None, out="net", mode="reveal", **kw):
+    def evaluate_images(self, items, batch=None, out="net", mode="reveal", upsample=None, **kw):
         """Generator: score a stream of ground-truth colour images with both pipeline slots busy -- ``colorize_images`` whose every image is
         compared with itself on the device (``forward_async_eval``).  An item is ``rgb``, ``(rgb, rects)`` or ``(rgb, rects, ref)``; with
         mode='reveal' (default) ``rects`` are rows (y0, x0, y1, x1) whose colours the device reveals from the image, with 'ab' / 'rgb' they
         are hint rows as in ``set_hints``.  Grouping, slot alternation and order as in ``colorize_images``; one ``(psnr, sse)`` per image is
         yielded: ``sse`` (3,) uint64, ``psnr`` = ``evaluate.psnr_from_sse`` of it over the image's net size (out='net') or its own
-        (out='source'), ``inf`` for an exact match.  24 bytes per image come back; no image does."""
+        (out='source'), ``inf`` for an exact match.  24 bytes per image come back; no image does.  ``upsample``: as in ``colorize_stream``;
+        with out='source' the score is then that of the joint image."""
         from .evaluate import psnr_from_sse
         batch = self.max_batch if batch is None else int(batch)
         if not 1 <= batch <= self.max_batch:
@@ -1338,6 +1398,7 @@ class HipColorizer(object):
             return rgb, item[1] if len(item) > 1 else None, item[2] if len(item) > 2 else None, len(item) > 2
 
         k, group = 0, []
+        restore = self._upsample_scope(upsample)
         try:
             for item in items:
                 group.append(parse(item))
@@ -1359,18 +1420,24 @@ class HipColorizer(object):
                     for r in finish(slot):
                         yield r
         finally:                                    # a consumer that stops early: nothing stays in flight on buffers about to be recycled
-            for slot in (0, 1):
-                if pending[slot] is not None:
-                    pending[slot] = None
-                    self.wait(slot)
+            try:
+                for slot in (0, 1):
+                    if pending[slot] is not None:
+                        pending[slot] = None
+                        self.wait(slot)
+            finally:
+                if restore is not None:
+                    self.set_batch_upsample(restore)
 
-    def suggest_images(self, items, centres, batch=None, out="source", peaks=8, radius=2, skip_hints=True, K=5, N_draws=25000, seed=0, **kw):
+    def suggest_images(self, items, centres, batch=None, out="source", peaks=8, radius=2, skip_hints=True, K=5, N_draws=25000, seed=0,
+                       upsample=None, **kw):
         """Generator: ``colorize_images`` on an engine with a distribution head that also proposes where to put the next hints and in which
         colours (``forward_async_dist`` with the suggestions at the peaks).  An item is ``rgb`` or ``(rgb, hints)``; grouping, slot alternation
         and order as in ``colorize_images``.  Per image it yields ``(rgb, peaks (P,2) int32, colours (P,K,2) float64, conf (P,K) float64)``:
         the colourised image, its ``peaks`` uncertainty peaks as net coordinates (y, x) -- (-1, -1) once the image ran out of cells -- and
         the K suggested colours of each with their shares.  Peak k of the g-th image of the stream draws with seed ``seed + g * peaks + k``,
-        whatever the batch size.  ``centres`` (B,2): the bin centres; ``kw``: mode, mask_value, maskcent, l_cent."""
+        whatever the batch size.  ``centres`` (B,2): the bin centres; ``kw``: mode, mask_value, maskcent, l_cent.  ``upsample``: as in
+        ``colorize_stream``."""
         batch = self.max_batch if batch is None else int(batch)
         if not 1 <= batch <= self.max_batch:
             raise ValueError("batch %d outside 1..%d" % (batch, self.max_batch))
@@ -1403,6 +1470,7 @@ class HipColorizer(object):
             return rgb, item[1] if len(item) > 1 else None
 
         k, group, done = 0, [], 0
+        restore = self._upsample_scope(upsample)
         try:
             for item in items:
                 group.append(parse(item))
@@ -1424,18 +1492,23 @@ class HipColorizer(object):
                     for r in finish(slot):
                         yield r
         finally:                                    # a consumer that stops early: nothing stays in flight on buffers about to be recycled
-            for slot in (0, 1):
-                if pending[slot] is not None:
-                    pending[slot] = None
-                    self.wait(slot)
+            try:
+                for slot in (0, 1):
+                    if pending[slot] is not None:
+                        pending[slot] = None
+                        self.wait(slot)
+            finally:
+                if restore is not None:
+                    self.set_batch_upsample(restore)
 
-    def score_images(self, items, centres, batch=None, nn=1, sigma=5.0, ranks=(1, 5), mode="reveal", want_psnr=False, **kw):
+    def score_images(self, items, centres, batch=None, nn=1, sigma=5.0, ranks=(1, 5), mode="reveal", want_psnr=False, upsample=None, **kw):
         """Generator: score the distribution head on a stream of ground-truth colour images with both pipeline slots busy --
         ``evaluate_images`` for the distribution (``forward_async_dist`` with ``score`` and no other tap).  An item is ``rgb`` or
         ``(rgb, rects)``, hints as in ``evaluate_images`` (mode 'reveal': the colours come from the image).  Per image it yields
         ``(xent_mean, hits, psnr)``: the mean cross-entropy of its cells against the (soft-)encoded truth, ``hits`` (len(ranks),) uint32 =
         cells whose true bin is among the ranks[j] most probable, and with ``want_psnr`` the net-size PSNR of the regression head
-        (``None`` otherwise).  A few dozen bytes per image come back; no image and no distribution does.  ``kw``: mask_value, maskcent, l_cent."""
+        (``None`` otherwise).  A few dozen bytes per image come back; no image and no distribution does.  ``kw``: mask_value, maskcent, l_cent.
+        ``upsample``: as in ``colorize_stream``."""
         from .evaluate import psnr_from_sse
         batch = self.max_batch if batch is None else int(batch)
         if not 1 <= batch <= self.max_batch:
@@ -1465,6 +1538,7 @@ class HipColorizer(object):
             return rgb, item[1] if len(item) > 1 else None
 
         k, group = 0, []
+        restore = self._upsample_scope(upsample)
         try:
             for item in items:
                 group.append(parse(item))
@@ -1486,10 +1560,14 @@ class HipColorizer(object):
                     for r in finish(slot):
                         yield r
         finally:                                    # a consumer that stops early: nothing stays in flight on buffers about to be recycled
-            for slot in (0, 1):
-                if pending[slot] is not None:
-                    pending[slot] = None
-                    self.wait(slot)
+            try:
+                for slot in (0, 1):
+                    if pending[slot] is not None:
+                        pending[slot] = None
+                        self.wait(slot)
+            finally:
+                if restore is not None:
+                    self.set_batch_upsample(restore)
 
     def wait(self, slot):
         self._chk(self.lib.idc_wait(self._h, int(slot)))
