@@ -347,14 +347,7 @@ int idc_set_hints(idc_handle h, int img, int n_hints, const idc_hint* hints, int
     int kept = 0;
     for (int i = 0; i < n_hints; ++i) {                    // cv2.rectangle: corners in either order, inclusive, clipped
         HintRect r;
-        r.y0 = hints[i].y0 < hints[i].y1 ? hints[i].y0 : hints[i].y1; r.y1 = hints[i].y0 < hints[i].y1 ? hints[i].y1 : hints[i].y0;
-        r.x0 = hints[i].x0 < hints[i].x1 ? hints[i].x0 : hints[i].x1; r.x1 = hints[i].x0 < hints[i].x1 ? hints[i].x1 : hints[i].x0;
-        if (r.y0 < 0) r.y0 = 0;
-        if (r.x0 < 0) r.x0 = 0;
-        if (r.y1 > h->H - 1) r.y1 = h->H - 1;
-        if (r.x1 > h->W - 1) r.x1 = h->W - 1;
-        if (r.y0 > r.y1 || r.x0 > r.x1) continue;          // entirely outside
-        r.c0 = hints[i].c0; r.c1 = hints[i].c1; r.c2 = hints[i].c2;
+        if (!clip_hint(hints[i], h->H, h->W, r)) continue;  // entirely outside
         if (mode == IDC_HINT_RGB)
             if (!(r.c0 >= 0.f && r.c0 <= 255.f && r.c1 >= 0.f && r.c1 <= 255.f && r.c2 >= 0.f && r.c2 <= 255.f))
                 return fail(&h->err, IDC_ERR_INVALID_ARG, "hint %d: RGB outside 0..255", i);
@@ -388,13 +381,7 @@ int idc_reveal_hints(idc_handle h, int img, int n_hints, const idc_hint* rects, 
     int kept = 0;
     for (int i = 0; i < n_hints; ++i) {                    // cv2.rectangle, as idc_set_hints reads it
         HintRect r;
-        r.y0 = rects[i].y0 < rects[i].y1 ? rects[i].y0 : rects[i].y1; r.y1 = rects[i].y0 < rects[i].y1 ? rects[i].y1 : rects[i].y0;
-        r.x0 = rects[i].x0 < rects[i].x1 ? rects[i].x0 : rects[i].x1; r.x1 = rects[i].x0 < rects[i].x1 ? rects[i].x1 : rects[i].x0;
-        if (r.y0 < 0) r.y0 = 0;
-        if (r.x0 < 0) r.x0 = 0;
-        if (r.y1 > h->H - 1) r.y1 = h->H - 1;
-        if (r.x1 > h->W - 1) r.x1 = h->W - 1;
-        if (r.y0 > r.y1 || r.x0 > r.x1) continue;          // entirely outside
+        if (!clip_hint(rects[i], h->H, h->W, r)) continue;  // entirely outside
         r.c0 = 0.f; r.c1 = 0.f; r.c2 = 0.f;
         orig[kept] = i;
         h->h_hints.get()[kept++] = r;

@@ -1,0 +1,216 @@
+// idc_batch.h -- the plan of one pipelined batch (idc_forward_async_rgb and its five relatives, idc_exec.hip): what a call passes, every check
+// of its arguments that needs neither the handle's state nor the runtime, the byte layout of what travels, and which copies move it.  Host
+// code that makes no runtime call: tools/batch_selftest.cpp includes it alone and checks the layouts without a device.
+#ifndef IDC_BATCH_H
+#define IDC_BATCH_H
+
+#include <stdarg.h>
+#include <stdio.h>
+
+#include <string>
+#include <vector>
+
+#include "../../include/ideepcolor.h"
+#include "idc_kernels.h"
+
+namespace idc {
+
+// cv2.rectangle, as every hint list is read: corners in either order, inclusive, clipped to the H x W net size.  false = entirely outside
+// the image (r is filled all the same).
+inline bool clip_hint(const idc_hint& u, int H, int W, HintRect& r) {
+    r.y0 = u.y0 < u.y1 ? u.y0 : u.y1; r.y1 = u.y0 < u.y1 ? u.y1 : u.y0;
+    r.x0 = u.x0 < u.x1 ? u.x0 : u.x1; r.x1 = u.x0 < u.x1 ? u.x1 : u.x0;
+    if (r.y0 < 0) r.y0 = 0;
+    if (r.x0 < 0) r.x0 = 0;
+    if (r.y1 > H - 1) r.y1 = H - 1;
+    if (r.x1 > W - 1) r.x1 = W - 1;
+    r.c0 = u.c0; r.c1 = u.c1; r.c2 = u.c2;
+    return r.y0 <= r.y1 && r.x0 <= r.x1;
+}
+
+// What the six entry points pass.  The same-size calls: ONE array each way, [n,src_h,src_w,3] in and [n,H,W,3] or [n,src_h,src_w,3] out.
+// ragged (idc_forward_async_images and later): a descriptor and an output pointer per image; on the device the sources and the source-size
+// results lie packed back to back, the layout the same-size calls have anyway, so everything but the two colour kernels is shared.
+struct BatchCall {
+    int slot = 0, n = 0;
+    bool ragged = false;
+    int src_h = 0, src_w = 0; const uint8_t* rgb_in = nullptr; uint8_t* rgb_out = nullptr;
+    const idc_ref_image* images = nullptr; uint8_t* const* outs = nullptr;
+    const int32_t* hint_offsets = nullptr; const idc_hint* hints = nullptr;
+    int mode = 0; float mask_value = 0.f, maskcent = 0.f, l_cent = 0.f; unsigned flags = 0;
+    float* out_ab = nullptr;
+    // has_refs: the batch brings its references, and the network reads the slot's own global inputs (else the handle's, as idc_forward_async)
+    bool has_refs = false; idc_batch_refs refs = {};
+    // eval (idc_forward_async_eval and later): the score is required, the revealed colours are optional.  taps_call (idc_forward_async_dist):
+    // the score is optional too, and a NULL taps is refused; score_call (idc_forward_async_dist_score): then taps may be NULL
+    bool eval = false; uint64_t* sse = nullptr; float* hint_colours = nullptr;
+    bool taps_call = false; const idc_dist_taps* taps = nullptr;
+    bool score_call = false; const idc_dist_score_spec* spec = nullptr; const float* centres = nullptr; const idc_dist_score_out* sout = nullptr;
+};
+
+inline void set_batch_refs(BatchCall& c, const idc_batch_refs* r) {
+    c.has_refs = r != nullptr;
+    if (r) c.refs = *r;
+}
+
+// One host buffer of a call and the bytes of the slot's packed device array it fills (in) or receives (out)
+struct Piece { const uint8_t* in; uint8_t* out; size_t in_at, in_bytes, out_at, out_bytes; bool in_pinned, out_pinned; };
+
+struct BatchPlan {
+    bool want_rgb = false;               // only an evaluation batch may keep its images on the device
+    bool reveal = false, dist = false, score = false, source_out = false;
+    int n_hints = 0, kept = 0;           // hints in the caller's list; those that survive clip_hint
+    size_t in_bytes = 0, rgb_bytes = 0;  // the packed sources; the packed results that leave the device
+    // the metadata block: the kept-hint offsets int[max_batch + 1] at 0, (ragged) the table ImgDesc[max_batch + 1] at table_at, the kept
+    // hints HintRect[kept] at hints_at, (reveal) each kept hint's place in the caller's list int[kept] at orig_at
+    size_t table_at = 0, hints_at = 0, orig_at = 0, meta_bytes = 0, meta_floor = 0;
+    size_t cols_at = 0, cols_bytes = 0;  // the evaluation block: sse uint64[max_batch][3] at 0, then hint_colours float[n_hints][2]
+    long long max_tiles = 0, max_pixels = 0;     // joint_tiles / pixels of the largest source
+    std::vector<Piece> pieces;           // in_pinned / out_pinned: the caller's to fill in (a runtime query); out_pinned without want_rgb: true
+    bool ab_pinned = false;              // ... and so is this one, of out_ab
+};
+
+inline int plan_fail(std::string* err, int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    if (err) *err = buf;
+    return code;
+}
+
+inline size_t batch_align16(size_t v) { return (v + 15) / 16 * 16; }
+
+// Every check of a call's arguments that needs neither the handle nor the runtime (c.n is in 1..max_batch: the caller checked), then the
+// layout.  0, or the status with its text in *err; *p is complete only on 0.
+inline int plan_batch(const BatchCall& c, int H, int W, int max_batch, BatchPlan* p, std::string* err) {
+    const int n = c.n;
+    *p = BatchPlan();
+    p->want_rgb = c.ragged ? c.outs != nullptr : c.rgb_out != nullptr;
+    p->reveal = c.eval && c.mode == IDC_HINT_REVEAL;
+    p->dist = c.eval && c.taps_call;
+    p->score = p->dist && c.score_call;
+    if (c.slot < 0 || c.slot > 1) return plan_fail(err, IDC_ERR_INVALID_ARG, "slot %d not in 0..1", c.slot);
+    if (c.ragged ? (!c.images || !(c.outs || c.eval)) : (!c.rgb_in || !c.rgb_out)) return plan_fail(err, IDC_ERR_INVALID_ARG, "null image pointer");
+    if (c.flags & ~(unsigned)IDC_BATCH_OUT_SOURCE) return plan_fail(err, IDC_ERR_INVALID_ARG, "unknown flag bits 0x%x", c.flags);
+    if (c.mode != IDC_HINT_AB && c.mode != IDC_HINT_RGB && !p->reveal) return plan_fail(err, IDC_ERR_INVALID_ARG, "hint mode %d", c.mode);
+    if (c.eval && !c.sse && !p->dist) return plan_fail(err, IDC_ERR_INVALID_ARG, "null sse");
+    if (c.eval && c.hint_colours && !p->reveal)
+        return plan_fail(err, IDC_ERR_INVALID_ARG, "hint_colours with hint mode %d: only IDC_HINT_REVEAL reveals colours", c.mode);
+    if (c.ragged) {
+        for (int i = 0; i < n; ++i) {
+            const idc_ref_image& im = c.images[i];
+            if (!im.rgb || (p->want_rgb && !c.outs[i])) return plan_fail(err, IDC_ERR_INVALID_ARG, "image %d: null image pointer", i);
+            if (im.h < 1 || im.h > 16384 || im.w < 1 || im.w > 16384)
+                return plan_fail(err, IDC_ERR_INVALID_ARG, "image %d: source size %dx%d outside 1..16384", i, im.h, im.w);
+            p->in_bytes += (size_t)im.h * im.w * 3;               // n * 0.8 GB: no overflow in 64 bits
+        }
+        if (p->in_bytes > IDC_BATCH_MAX_SOURCE_BYTES)
+            return plan_fail(err, IDC_ERR_INVALID_ARG, "%d sources hold %zu bytes, more than %zu", n, p->in_bytes, (size_t)IDC_BATCH_MAX_SOURCE_BYTES);
+    } else {
+        if (c.src_h < 1 || c.src_h > 16384 || c.src_w < 1 || c.src_w > 16384)
+            return plan_fail(err, IDC_ERR_INVALID_ARG, "source size %dx%d outside 1..16384", c.src_h, c.src_w);
+        p->in_bytes = (size_t)n * c.src_h * c.src_w * 3;
+        if (p->in_bytes > IDC_BATCH_MAX_SOURCE_BYTES)
+            return plan_fail(err, IDC_ERR_INVALID_ARG, "%d sources of %dx%d are more than %zu bytes", n, c.src_h, c.src_w, (size_t)IDC_BATCH_MAX_SOURCE_BYTES);
+    }
+    if (c.hint_offsets) {
+        if (c.hint_offsets[0] != 0) return plan_fail(err, IDC_ERR_INVALID_ARG, "hint_offsets[0] is %d, not 0", c.hint_offsets[0]);
+        for (int i = 0; i < n; ++i)
+            if (c.hint_offsets[i + 1] < c.hint_offsets[i]) return plan_fail(err, IDC_ERR_INVALID_ARG, "hint_offsets decrease at image %d", i);
+        p->n_hints = c.hint_offsets[n];
+        if (p->n_hints > IDC_BATCH_MAX_HINTS) return plan_fail(err, IDC_ERR_INVALID_ARG, "%d hints, more than %d", p->n_hints, IDC_BATCH_MAX_HINTS);
+        if (p->n_hints > 0 && !c.hints) return plan_fail(err, IDC_ERR_INVALID_ARG, "null hints with a non-zero offset");
+    }
+    for (int k = 0; k < p->n_hints; ++k) {
+        HintRect r;
+        if (!clip_hint(c.hints[k], H, W, r)) continue;
+        if (c.mode == IDC_HINT_RGB && !(r.c0 >= 0.f && r.c0 <= 255.f && r.c1 >= 0.f && r.c1 <= 255.f && r.c2 >= 0.f && r.c2 <= 255.f))
+            return plan_fail(err, IDC_ERR_INVALID_ARG, "hint %d: RGB outside 0..255", k);
+        ++p->kept;
+    }
+    const size_t hw = (size_t)H * W, nb = (size_t)max_batch;
+    p->source_out = (c.flags & IDC_BATCH_OUT_SOURCE) != 0;
+    p->rgb_bytes = p->source_out ? p->in_bytes : (size_t)n * hw * 3;
+    p->table_at = batch_align16((nb + 1) * sizeof(int));
+    p->hints_at = c.ragged ? p->table_at + batch_align16((nb + 1) * sizeof(ImgDesc)) : p->table_at;
+    p->orig_at = p->hints_at + (size_t)p->kept * sizeof(HintRect);
+    p->meta_bytes = p->orig_at + (p->reveal ? (size_t)p->kept * sizeof(int) : 0);
+    p->meta_floor = p->hints_at + 256 * (sizeof(HintRect) + sizeof(int));
+    p->cols_at = nb * 3 * sizeof(uint64_t);
+    p->cols_bytes = c.eval && c.hint_colours ? (size_t)p->n_hints * 2 * sizeof(float) : 0;
+    if (c.ragged) {
+        size_t at = 0;
+        for (int i = 0; i < n; ++i) {
+            const idc_ref_image& im = c.images[i];
+            const size_t sb = (size_t)im.h * im.w * 3;
+            p->pieces.push_back({im.rgb, p->want_rgb ? c.outs[i] : nullptr, at, sb, p->source_out ? at : (size_t)i * hw * 3,
+                                 p->source_out ? sb : hw * 3, false, false});
+            p->max_tiles = p->max_tiles > joint_tiles(im.h, im.w) ? p->max_tiles : joint_tiles(im.h, im.w);
+            p->max_pixels = p->max_pixels > (long long)im.h * im.w ? p->max_pixels : (long long)im.h * im.w;
+            at += sb;
+        }
+    } else {
+        p->pieces.push_back({c.rgb_in, c.rgb_out, 0, p->in_bytes, 0, p->rgb_bytes, false, false});
+        p->max_tiles = joint_tiles(c.src_h, c.src_w);
+        p->max_pixels = (long long)c.src_h * c.src_w;
+    }
+    return IDC_OK;
+}
+
+// The metadata block as the kernels read it, into h_meta (p.meta_bytes of it): offsets of the KEPT hints per image, (ragged) the image table
+// with its closing entry, the clipped rectangles, (reveal) their places in the caller's list.
+inline void fill_batch_meta(const BatchCall& c, const BatchPlan& p, int H, int W, unsigned char* h_meta) {
+    int* m_offs = (int*)h_meta;
+    HintRect* m_hints = (HintRect*)(h_meta + p.hints_at);
+    int* m_orig = (int*)(h_meta + p.orig_at);
+    if (c.ragged) {
+        ImgDesc* tab = (ImgDesc*)(h_meta + p.table_at);
+        for (int i = 0; i <= c.n; ++i) {           // entry n closes the run: where the next image would begin
+            const size_t at = i < c.n ? p.pieces[i].in_at : p.in_bytes;
+            tab[i].off = (long long)at; tab[i].first = (long long)(at / 3);
+            tab[i].h = i < c.n ? c.images[i].h : 0; tab[i].w = i < c.n ? c.images[i].w : 0;
+        }
+    }
+    m_offs[0] = 0;
+    for (int i = 0, w = 0; i < c.n; ++i) {
+        for (int k = c.hint_offsets ? c.hint_offsets[i] : 0; k < (c.hint_offsets ? c.hint_offsets[i + 1] : 0); ++k) {
+            HintRect r;                             // clip_hint fills r even for a hint it drops: only a kept one may reach the block, which has room for `kept`
+            if (!clip_hint(c.hints[k], H, W, r)) continue;
+            if (p.reveal) m_orig[w] = k;
+            m_hints[w++] = r;
+        }
+        m_offs[i + 1] = w;
+    }
+}
+
+// Pieces <-> a packed device array: a pinned buffer travels in place (piece >= 0: between that piece's own buffer and [at, at + bytes) of the
+// array), a pageable one through the staging buffer at the piece's own offset (piece < 0: staging and array at the same [at, at + bytes)),
+// and neighbouring staged pieces go as ONE copy.
+struct CopyOp { int piece; size_t at, bytes; };
+
+inline std::vector<CopyOp> copy_runs(const std::vector<Piece>& pieces, bool to_device) {
+    std::vector<CopyOp> ops;
+    size_t run0 = 0, run1 = 0;                      // staged bytes [run0, run1) not yet issued
+    auto flush = [&]() {
+        if (run1 != run0) ops.push_back({-1, run0, run1 - run0});
+        run0 = run1;
+    };
+    for (int i = 0; i < (int)pieces.size(); ++i) {
+        const Piece& p = pieces[i];
+        const size_t at = to_device ? p.in_at : p.out_at, bytes = to_device ? p.in_bytes : p.out_bytes;
+        const bool pinned = to_device ? p.in_pinned : p.out_pinned;
+        if (!pinned && at == run1) { run1 = at + bytes; continue; }
+        flush();
+        if (!pinned) { run0 = at; run1 = at + bytes; continue; }
+        ops.push_back({i, at, bytes});
+        run0 = run1 = at + bytes;
+    }
+    flush();
+    return ops;
+}
+
+}  // namespace idc
+
+#endif  // IDC_BATCH_H

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/ideepcolor.h"
+#include "idc_batch.h"
 #include "idc_kernels.h"
 #include "idc_layout.h"
 #include "idc_mem.h"
@@ -230,35 +231,27 @@ struct idc_context {
         PinnedMem<float> h_in, h_out;                                                  // pinned staging (pageable callers)
         Event ev_in, ev_comp, ev_out;
         Event ev_in0, ev_comp0, ev_out0;                                               // stage starts (idc_pipeline_times)
-        bool pending = false, staged_out = false, timed = false;
+        bool pending = false, timed = false;
         int up_interp = 1; JointParams up_joint = {2, 2.0, 128.0};                     // the source-size upsampling the batch in flight was enqueued with
-        float* user_out = nullptr; int n = 0;
-        // idc_forward_async_rgb: the batch's packed uint8 source, its offsets + clipped hint list (one block: int[n+1], then HintRect[] at
-        // rgb_meta_hints), the net-size result, the refreshed Lab and the source-size result (IDC_BATCH_OUT_SOURCE); grown on demand
+        // what idc_wait still has to copy to a pageable destination of the batch in flight: `bytes` from the slot's pinned memory, where the
+        // copy-out stream left them (one entry per pageable buffer of the call, whatever it holds; a pinned destination was written in place)
+        struct StagedOut { void* user; const void* pinned; size_t bytes; };
+        std::vector<StagedOut> outs;
+        // idc_forward_async_rgb: the batch's packed uint8 source, its metadata block (BatchPlan, idc_batch.h), the net-size result, the
+        // refreshed Lab and the source-size result (IDC_BATCH_OUT_SOURCE); grown on demand
         DevMem<unsigned char> d_src, d_meta, d_rgb, d_full;
         DevMem<double> d_labq;
-        PinnedMem<unsigned char> h_src, h_meta, h_rgb;                                 // pinned staging: pageable source, the list, pageable rgb_out
-        // the batch's pageable rgb_out buffers (one for the same-size calls, up to one per image for idc_forward_async_images): each waits in
-        // h_rgb at `at` until idc_wait copies it out; empty after an idc_forward_async.  idc_forward_async_images' image table travels in
-        // d_meta / h_meta between the hint offsets and the hint list
-        struct StagedOut { uint8_t* user; size_t at, bytes; };
-        std::vector<StagedOut> staged_outs;
-        // idc_forward_async_eval: the net-size ground truth [max_batch,H,W,3] (a net-size score), and one block for what the batch reports --
-        // sse uint64[max_batch][3], then hint_colours float[n_hints][2] -- on the device and pinned; a pageable sse / hint_colours waits in
-        // h_eval until idc_wait copies it out (eval_outs; empty after every other call)
+        PinnedMem<unsigned char> h_src, h_meta, h_rgb;                                 // pinned staging: pageable sources, the block, pageable rgb_out
+        // idc_forward_async_eval: the net-size ground truth [max_batch,H,W,3] (a net-size score), and one block for what the batch reports
+        // (BatchPlan: sse, then hint_colours), on the device and pinned
         DevMem<unsigned char> d_truth, d_eval;
         PinnedMem<unsigned char> h_eval;
-        std::vector<StagedOut> eval_outs;
-        // idc_forward_async_dist: the taps' inputs (queries, centres: pinned and device), and one device block for what they produce -- the entropy
-        // map, the picker's work map, peaks, peak_ent, suggestions (TapsLayout) -- with its pinned twin, where a pageable destination waits at the
-        // same offset until idc_wait copies it out (taps_outs; empty after every other call)
+        // idc_forward_async_dist: the taps' inputs (queries, centres) and one block for what they produce (TapsLayout), each device and pinned
         DevMem<unsigned char> d_taps_in, d_taps;
         PinnedMem<unsigned char> h_taps_in, h_taps;
-        std::vector<StagedOut> taps_outs;
-        // idc_forward_async_dist_score: the centres (pinned and device) and the score's result block (ScoreLayout) with its pinned twin, as for the taps
+        // idc_forward_async_dist_score: the centres and the score's result block (ScoreLayout), as for the taps
         DevMem<unsigned char> d_score_in, d_score;
         PinnedMem<unsigned char> h_score_in, h_score;
-        std::vector<StagedOut> score_outs;
         // idc_forward_async_rgb_ref: the batch's references and the slot's OWN [max_batch][316] global inputs (the handle's d_glob_in is not touched)
         RefStage ref;
         DevMem<float> d_glob_in;

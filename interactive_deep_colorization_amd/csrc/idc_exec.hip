@@ -357,12 +357,17 @@ static int wait_slot(idc_context* h, int slot) {
     sl.pending = false;
     const int arc = check_chain_abort(h);      // the forward this slot carried ran a chain launch that gave up: its result is invalid
     if (arc) return arc;
-    if (sl.staged_out && sl.user_out) memcpy(sl.user_out, sl.h_out.get(), (size_t)sl.n * h->H * h->W * 2 * 4);
-    for (const auto& o : sl.staged_outs) memcpy(o.user, sl.h_rgb.get() + o.at, o.bytes);
-    for (const auto& o : sl.eval_outs) memcpy(o.user, sl.h_eval.get() + o.at, o.bytes);
-    for (const auto& o : sl.taps_outs) memcpy(o.user, sl.h_taps.get() + o.at, o.bytes);
-    for (const auto& o : sl.score_outs) memcpy(o.user, sl.h_score.get() + o.at, o.bytes);
+    for (const auto& o : sl.outs) memcpy(o.user, o.pinned, o.bytes);
     return IDC_OK;
+}
+
+// `bytes` at `at` of a slot's device block to the caller's buffer, on the copy-out stream: in place when the buffer is pinned (direct), else
+// into the block's pinned twin at the same offset, where it waits for idc_wait (sl.outs)
+static hipError_t copy_out(idc_context* h, idc_context::PipeSlot& sl, void* user, bool direct, const void* dev, void* twin, size_t at, size_t bytes) {
+    void* dst = direct ? user : (void*)((unsigned char*)twin + at);
+    const hipError_t e = hipMemcpyAsync(dst, (const unsigned char*)dev + at, bytes, hipMemcpyDeviceToHost, h->s_out.get());
+    if (e == hipSuccess && !direct) sl.outs.push_back({user, dst, bytes});
+    return e;
 }
 
 int drain_pipeline(idc_context* c) {
@@ -597,8 +602,8 @@ int idc_forward_async(idc_handle h, int slot, int n, const float* L_mc, const fl
         memcpy(hL, L_mc, (size_t)n * hw * 4); memcpy(hab, ab, (size_t)n * hw * 2 * 4); memcpy(hm, mask, (size_t)n * hw * 4);
         sL = hL; sab = hab; sm = hm;
     }
-    sl.staged_out = !is_pinned(out_ab);
-    if (sl.staged_out) HIPCHK(h, sl.h_out.ensure(nb * hw * 2 * 4));
+    const bool out_direct = is_pinned(out_ab);
+    if (!out_direct) HIPCHK(h, sl.h_out.ensure(nb * hw * 2 * 4));
     // copy-in stream: the slot's previous inputs were consumed (its previous forward finished: idc_wait was called)
     HIPCHK(h, hipEventRecord(sl.ev_in0.get(), h->s_in.get()));
     HIPCHK(h, hipMemcpyAsync(sl.d_L.get(), sL, (size_t)n * hw * 4, hipMemcpyHostToDevice, h->s_in.get()));
@@ -612,426 +617,356 @@ int idc_forward_async(idc_handle h, int slot, int n, const float* L_mc, const fl
     HIPCHK(h, hipEventRecord(sl.ev_comp.get(), h->stream.get()));
     HIPCHK(h, hipStreamWaitEvent(h->s_out.get(), sl.ev_comp.get(), 0));
     HIPCHK(h, hipEventRecord(sl.ev_out0.get(), h->s_out.get()));
-    HIPCHK(h, hipMemcpyAsync(sl.staged_out ? sl.h_out.get() : out_ab, sl.d_out.get(), (size_t)n * hw * 2 * 4, hipMemcpyDeviceToHost, h->s_out.get()));
+    sl.outs.clear();
+    HIPCHK(h, copy_out(h, sl, out_ab, out_direct, sl.d_out.get(), sl.h_out.get(), 0, (size_t)n * hw * 2 * 4));
     HIPCHK(h, hipEventRecord(sl.ev_out.get(), h->s_out.get()));
-    sl.pending = true; sl.timed = true; sl.user_out = out_ab; sl.n = n;
-    sl.staged_outs.clear(); sl.eval_outs.clear(); sl.taps_outs.clear(); sl.score_outs.clear();
+    sl.pending = true; sl.timed = true;
     return IDC_OK;
 }
 
 // The serving form of the product: uint8 images and hint lists in, colourised uint8 images out, on the same two slots.  The slot owns the
-// packed source, the clipped hint list, its planes and its results; every argument is checked before anything is enqueued.
-// ra != nullptr (idc_forward_async_rgb_ref): the batch brings its references, and the network reads the slot's own global inputs, written on
-// the compute stream in front of the prologue; ra == nullptr: the handle's global inputs, as idc_forward_async reads them.
-struct RefArgs { int m; const idc_ref_image* refs; const int32_t* ref_index; const float* centres; float hist_flag; unsigned flags; };
+// packed source, the clipped hint list, its planes and its results.  A call (BatchCall, idc_batch.h) goes through forward_async_rgb's passes:
+// every argument is checked before anything is allocated, written or enqueued, and the slot counts as in flight only once all of it is.
+using Slot = idc_context::PipeSlot;
+// What a batch needs from the handle-dependent checks: where its references, taps and score sit (all zero without them: nothing of them is
+// allocated, launched or copied)
+struct BatchLayouts { RefLayout ref; DistGeom geom; TapsLayout taps; ScoreLayout score; size_t score_in_bytes = 0; };
 
-// What the entry points differ in.  The same-size calls: ONE array each way, [n,src_h,src_w,3] in and [n,H,W,3] or [n,src_h,src_w,3] out.
-// idc_forward_async_images (ragged): a descriptor and an output pointer per image; on the device the sources and the source-size
-// results lie packed back to back, the layout the same-size calls have anyway, so everything but the two colour kernels is shared.
-struct BatchIO {
-    bool ragged;
-    int src_h, src_w; const uint8_t* rgb_in; uint8_t* rgb_out;
-    const idc_ref_image* images; uint8_t* const* outs;
-};
-// idc_forward_async_eval's own arguments (ev == nullptr: every other entry point): the score is required, the revealed colours are optional.
-// idc_forward_async_dist brings both and its taps (taps_call: taps itself may be NULL, which is refused); there the score is optional too
-// idc_forward_async_dist_score adds the score (score_call: then taps may be NULL, and spec / centres / sout are checked by check_score)
-struct EvalArgs {
-    uint64_t* sse; float* hint_colours; bool taps_call = false; const idc_dist_taps* taps = nullptr;
-    bool score_call = false; const idc_dist_score_spec* spec = nullptr; const float* centres = nullptr; const idc_dist_score_out* sout = nullptr;
-};
-// One host buffer of a call and the bytes of the slot's packed device array it fills (in) or receives (out)
-struct Piece { const uint8_t* in; uint8_t* out; size_t in_at, in_bytes, out_at, out_bytes; bool in_pinned, out_pinned; };
-
-// Pieces <-> a packed device array on `s`: a pinned buffer travels in place, a pageable one through `staging` at the piece's own offset (copied
-// in by the caller before, copied out by idc_wait after), and neighbouring staged pieces go as ONE copy.
+// Pieces <-> a packed device array on `s`, as copy_runs decides; a staged piece is copied in by batch_stage before, copied out by idc_wait after
 static hipError_t copy_pieces(const std::vector<Piece>& pieces, bool to_device, unsigned char* dev, unsigned char* staging, hipStream_t s) {
-    size_t run0 = 0, run1 = 0;                      // staged bytes [run0, run1) not yet enqueued
-    auto flush = [&]() -> hipError_t {
-        if (run1 == run0) return hipSuccess;
-        const hipError_t e = to_device ? hipMemcpyAsync(dev + run0, staging + run0, run1 - run0, hipMemcpyHostToDevice, s)
-                                       : hipMemcpyAsync(staging + run0, dev + run0, run1 - run0, hipMemcpyDeviceToHost, s);
-        run0 = run1;
-        return e;
-    };
-    for (const Piece& p : pieces) {
-        const size_t at = to_device ? p.in_at : p.out_at, bytes = to_device ? p.in_bytes : p.out_bytes;
-        const bool pinned = to_device ? p.in_pinned : p.out_pinned;
-        if (!pinned && at == run1) { run1 = at + bytes; continue; }
-        hipError_t e = flush();
+    for (const CopyOp& o : copy_runs(pieces, to_device)) {
+        void* host = o.piece < 0 ? (void*)(staging + o.at) : to_device ? (void*)pieces[o.piece].in : (void*)pieces[o.piece].out;
+        const hipError_t e = to_device ? hipMemcpyAsync(dev + o.at, host, o.bytes, hipMemcpyHostToDevice, s)
+                                       : hipMemcpyAsync(host, dev + o.at, o.bytes, hipMemcpyDeviceToHost, s);
         if (e != hipSuccess) return e;
-        if (!pinned) { run0 = at; run1 = at + bytes; continue; }
-        e = to_device ? hipMemcpyAsync(dev + at, p.in, bytes, hipMemcpyHostToDevice, s) : hipMemcpyAsync(p.out, dev + at, bytes, hipMemcpyDeviceToHost, s);
-        if (e != hipSuccess) return e;
-        run0 = run1 = at + bytes;
     }
-    return flush();
+    return hipSuccess;
 }
 
-static int forward_async_rgb(idc_handle h, int slot, int n, const BatchIO& io, const int32_t* hint_offsets,
-                             const idc_hint* hints, int mode, float mask_value, float maskcent, float l_cent, unsigned flags,
-                             const RefArgs* ra, float* out_ab, const EvalArgs* ev = nullptr) {
-    int rc = check_forward_args(h, n);
-    if (rc) return rc;
-    const bool ragged = io.ragged;
-    const bool want_rgb = ragged ? io.outs != nullptr : io.rgb_out != nullptr;      // only an evaluation batch may keep its images on the device
-    const bool reveal = ev && mode == IDC_HINT_REVEAL;
-    if (slot < 0 || slot > 1) return fail(&h->err, IDC_ERR_INVALID_ARG, "slot %d not in 0..1", slot);
-    if (ragged ? (!io.images || !(io.outs || ev)) : (!io.rgb_in || !io.rgb_out)) return fail(&h->err, IDC_ERR_INVALID_ARG, "null image pointer");
-    if (flags & ~(unsigned)IDC_BATCH_OUT_SOURCE) return fail(&h->err, IDC_ERR_INVALID_ARG, "unknown flag bits 0x%x", flags);
-    if (mode != IDC_HINT_AB && mode != IDC_HINT_RGB && !reveal) return fail(&h->err, IDC_ERR_INVALID_ARG, "hint mode %d", mode);
-    const bool dist = ev && ev->taps_call;
-    if (ev && !ev->sse && !dist) return fail(&h->err, IDC_ERR_INVALID_ARG, "null sse");
-    if (ev && ev->hint_colours && !reveal) return fail(&h->err, IDC_ERR_INVALID_ARG, "hint_colours with hint mode %d: only IDC_HINT_REVEAL reveals colours", mode);
-    size_t in_bytes = 0;
-    if (ragged) {
-        for (int i = 0; i < n; ++i) {
-            const idc_ref_image& im = io.images[i];
-            if (!im.rgb || (want_rgb && !io.outs[i])) return fail(&h->err, IDC_ERR_INVALID_ARG, "image %d: null image pointer", i);
-            if (im.h < 1 || im.h > 16384 || im.w < 1 || im.w > 16384)
-                return fail(&h->err, IDC_ERR_INVALID_ARG, "image %d: source size %dx%d outside 1..16384", i, im.h, im.w);
-            in_bytes += (size_t)im.h * im.w * 3;                  // n * 0.8 GB: no overflow in 64 bits
-        }
-        if (in_bytes > IDC_BATCH_MAX_SOURCE_BYTES)
-            return fail(&h->err, IDC_ERR_INVALID_ARG, "%d sources hold %zu bytes, more than %zu", n, in_bytes, (size_t)IDC_BATCH_MAX_SOURCE_BYTES);
-    } else {
-        if (io.src_h < 1 || io.src_h > 16384 || io.src_w < 1 || io.src_w > 16384)
-            return fail(&h->err, IDC_ERR_INVALID_ARG, "source size %dx%d outside 1..16384", io.src_h, io.src_w);
-        in_bytes = (size_t)n * io.src_h * io.src_w * 3;
-        if (in_bytes > IDC_BATCH_MAX_SOURCE_BYTES)
-            return fail(&h->err, IDC_ERR_INVALID_ARG, "%d sources of %dx%d are more than %zu bytes", n, io.src_h, io.src_w, (size_t)IDC_BATCH_MAX_SOURCE_BYTES);
-    }
-    int n_hints = 0;
-    if (hint_offsets) {
-        if (hint_offsets[0] != 0) return fail(&h->err, IDC_ERR_INVALID_ARG, "hint_offsets[0] is %d, not 0", hint_offsets[0]);
-        for (int i = 0; i < n; ++i)
-            if (hint_offsets[i + 1] < hint_offsets[i]) return fail(&h->err, IDC_ERR_INVALID_ARG, "hint_offsets decrease at image %d", i);
-        n_hints = hint_offsets[n];
-        if (n_hints > IDC_BATCH_MAX_HINTS) return fail(&h->err, IDC_ERR_INVALID_ARG, "%d hints, more than %d", n_hints, IDC_BATCH_MAX_HINTS);
-        if (n_hints > 0 && !hints) return fail(&h->err, IDC_ERR_INVALID_ARG, "null hints with a non-zero offset");
-    }
-    // cv2.rectangle, as idc_set_hints reads a hint: corners in either order, inclusive, clipped; false = entirely outside the image
-    auto clip = [&](const idc_hint& u, HintRect& r) {
-        r.y0 = u.y0 < u.y1 ? u.y0 : u.y1; r.y1 = u.y0 < u.y1 ? u.y1 : u.y0;
-        r.x0 = u.x0 < u.x1 ? u.x0 : u.x1; r.x1 = u.x0 < u.x1 ? u.x1 : u.x0;
-        if (r.y0 < 0) r.y0 = 0;
-        if (r.x0 < 0) r.x0 = 0;
-        if (r.y1 > h->H - 1) r.y1 = h->H - 1;
-        if (r.x1 > h->W - 1) r.x1 = h->W - 1;
-        r.c0 = u.c0; r.c1 = u.c1; r.c2 = u.c2;
-        return r.y0 <= r.y1 && r.x0 <= r.x1;
-    };
-    int kept = 0;
-    for (int k = 0; k < n_hints; ++k) {
-        HintRect r;
-        if (!clip(hints[k], r)) continue;
-        if (mode == IDC_HINT_RGB && !(r.c0 >= 0.f && r.c0 <= 255.f && r.c1 >= 0.f && r.c1 <= 255.f && r.c2 >= 0.f && r.c2 <= 255.f))
-            return fail(&h->err, IDC_ERR_INVALID_ARG, "hint %d: RGB outside 0..255", k);
-        ++kept;
-    }
-    RefLayout lay;
-    if (ra) {
-        rc = check_refs(h, 0, n, ra->m, ra->refs, ra->ref_index, ra->centres, ra->hist_flag, ra->flags, &lay);
+// the checks that read the handle, behind plan_batch's: references, distribution taps and score, the range audit, the slot itself
+static int batch_handle_checks(idc_context* h, const BatchCall& c, const BatchPlan& p, BatchLayouts* L) {
+    if (c.has_refs) {
+        const int rc = check_refs(h, 0, c.n, c.refs.m, c.refs.refs, c.refs.ref_index, c.refs.centres, c.refs.hist_flag, c.refs.flags, &L->ref);
         if (rc) return rc;
         if (!(h->flags & IDC_FLAG_GLOBAL_HINTS)) return fail(&h->err, IDC_ERR_UNSUPPORTED, "handle was created without IDC_FLAG_GLOBAL_HINTS");
     }
-    DistGeom geom;
-    TapsLayout tl;                                      // (all zero without taps: nothing of them is allocated, launched or copied)
-    ScoreLayout sc;
-    const bool score = dist && ev->score_call;
-    if (dist) {
-        if (!dist_geom(h, &geom))
+    if (p.dist) {
+        if (!dist_geom(h, &L->geom))
             return fail(&h->err, IDC_ERR_UNSUPPORTED, "handle has no distribution head (IDC_FLAG_DIST_HEAD, or IDC_FLAG_DIST313 with idc_keep_dist on)");
-        if (!score || ev->taps) {
-            rc = check_taps(h, geom, n, 0, 0, ev->taps, &tl);
+        if (!p.score || c.taps) {
+            const int rc = check_taps(h, L->geom, c.n, 0, 0, c.taps, &L->taps);
             if (rc) return rc;
         }
-        if (score) {
-            rc = check_score(h, geom, n, ev->spec, ev->centres, ev->sout, &sc);
+        if (p.score) {
+            const int rc = check_score(h, L->geom, c.n, c.spec, c.centres, c.sout, &L->score);
             if (rc) return rc;
         }
     }
+    L->score_in_bytes = align_up((size_t)L->geom.B * 2 * sizeof(float), 16);
     if (h->audit) return fail(&h->err, IDC_ERR_UNSUPPORTED, "the range audit covers the blocking, resident and device-pointer forwards, not the pipelined slots");
-    auto& sl = h->pipe[slot];
-    if (sl.pending) return fail(&h->err, IDC_ERR_INVALID_ARG, "slot %d is still in flight: idc_wait it first", slot);
+    if (h->pipe[c.slot].pending) return fail(&h->err, IDC_ERR_INVALID_ARG, "slot %d is still in flight: idc_wait it first", c.slot);
+    return IDC_OK;
+}
+
+// every buffer of the slot this batch uses, at the size it needs: the slot is idle (its last batch was waited for), so they may be replaced by
+// larger ones (the reference stage grows in stage_refs)
+static int batch_reserve(idc_context* h, const BatchCall& c, const BatchPlan& p, const BatchLayouts& L, Slot& sl) {
+    const size_t hw = (size_t)h->H * h->W, nb = (size_t)h->max_batch;
+    HIPCHK(h, sl.d_src.ensure(p.in_bytes));
+    HIPCHK(h, sl.d_meta.ensure(p.meta_bytes, p.meta_floor));
+    HIPCHK(h, sl.h_meta.ensure(p.meta_bytes, p.meta_floor));
+    HIPCHK(h, sl.d_rgb.ensure(nb * hw * 3));
+    if (p.source_out) {
+        HIPCHK(h, sl.d_labq.ensure(nb * hw * 3 * 8));
+        HIPCHK(h, sl.d_full.ensure(p.in_bytes));
+    }
+    if (c.eval) {
+        if (!p.source_out) HIPCHK(h, sl.d_truth.ensure(nb * hw * 3));
+        HIPCHK(h, sl.d_eval.ensure(p.cols_at + p.cols_bytes, p.cols_at + 4096));
+        HIPCHK(h, sl.h_eval.ensure(p.cols_at + p.cols_bytes, p.cols_at + 4096));
+    }
+    if (p.dist) {     // the taps' queries and centres travel with the batch; their results wait in the slot's block
+        HIPCHK(h, sl.d_taps_in.ensure(L.taps.in_bytes, 65536));
+        HIPCHK(h, sl.h_taps_in.ensure(L.taps.in_bytes, 65536));
+        HIPCHK(h, sl.d_taps.ensure(L.taps.out_bytes, 65536));
+        HIPCHK(h, sl.h_taps.ensure(L.taps.out_bytes, 65536));
+    }
+    if (p.score) {    // ... and so do the score's centres and results
+        HIPCHK(h, sl.d_score_in.ensure(L.score_in_bytes, 8192));
+        HIPCHK(h, sl.h_score_in.ensure(L.score_in_bytes, 8192));
+        HIPCHK(h, sl.d_score.ensure(L.score.out_bytes, 65536));
+        HIPCHK(h, sl.h_score.ensure(L.score.out_bytes, 65536));
+    }
+    bool any_staged_in = false, any_staged_rgb = false;
+    for (const Piece& q : p.pieces) { any_staged_in |= !q.in_pinned; any_staged_rgb |= !q.out_pinned; }
+    if (any_staged_in) HIPCHK(h, sl.h_src.ensure(p.in_bytes));
+    if (any_staged_rgb) HIPCHK(h, sl.h_rgb.ensure(p.rgb_bytes));
+    if (!p.ab_pinned) HIPCHK(h, sl.h_out.ensure(nb * hw * 2 * 4));
+    if (c.has_refs) HIPCHK(h, sl.d_glob_in.ensure(nb * kGlobIn * sizeof(float)));
+    return IDC_OK;
+}
+
+// everything the copy-in stream will read from the slot's pinned memory, written here on the calling thread
+static int batch_stage(idc_context* h, const BatchCall& c, const BatchPlan& p, const BatchLayouts& L, Slot& sl) {
+    if (L.taps.Q > 0) {
+        if (!L.taps.at_peaks) memcpy(sl.h_taps_in.get(), c.taps->queries, (size_t)L.taps.Q * sizeof(DistQuery));
+        memcpy(sl.h_taps_in.get() + L.taps.i_centres, c.taps->centres, (size_t)L.geom.B * 2 * sizeof(float));
+    }
+    if (p.score) memcpy(sl.h_score_in.get(), c.centres, (size_t)L.geom.B * 2 * sizeof(float));
+    for (const Piece& q : p.pieces)      // every host buffer is judged on its own: only the pageable sources go through the staging
+        if (!q.in_pinned) memcpy(sl.h_src.get() + q.in_at, q.in, q.in_bytes);
+    fill_batch_meta(c, p, h->H, h->W, sl.h_meta.get());
+    return c.has_refs ? stage_refs(h, sl.ref, L.ref, c.refs.refs, c.refs.ref_index, c.refs.centres, false) : IDC_OK;
+}
+
+static int batch_copy_in(idc_context* h, const BatchCall& c, const BatchPlan& p, const BatchLayouts& L, Slot& sl) {
+    hipStream_t s = h->s_in.get();
+    HIPCHK(h, hipEventRecord(sl.ev_in0.get(), s));
+    HIPCHK(h, copy_pieces(p.pieces, true, sl.d_src.get(), sl.h_src.get(), s));
+    HIPCHK(h, hipMemcpyAsync(sl.d_meta.get(), sl.h_meta.get(), p.meta_bytes, hipMemcpyHostToDevice, s));
+    if (L.taps.Q > 0) HIPCHK(h, hipMemcpyAsync(sl.d_taps_in.get(), sl.h_taps_in.get(), L.taps.in_bytes, hipMemcpyHostToDevice, s));
+    if (p.score) HIPCHK(h, hipMemcpyAsync(sl.d_score_in.get(), sl.h_score_in.get(), L.score_in_bytes, hipMemcpyHostToDevice, s));
+    if (c.has_refs) {
+        const int rc = upload_refs(h, sl.ref, L.ref, s);
+        if (rc) return rc;
+    }
+    HIPCHK(h, hipEventRecord(sl.ev_in.get(), s));
+    return IDC_OK;
+}
+
+// the device's view of the slot's metadata block
+struct BatchMeta { const int* offs; HintRect* hints; const ImgDesc* tab; const int* orig; };
+static BatchMeta batch_meta(const BatchPlan& p, Slot& sl) {
+    unsigned char* m = sl.d_meta.get();
+    return {p.kept ? (const int*)m : nullptr, (HintRect*)(m + p.hints_at), (const ImgDesc*)(m + p.table_at), (const int*)(m + p.orig_at)};
+}
+
+// compute stream, first half: [global inputs from the references] [revealed colours] prologue, network, Lab -> RGB, [the source-size image]
+static int batch_colourise(idc_context* h, const BatchCall& c, const BatchPlan& p, const BatchLayouts& L, Slot& sl) {
+    hipStream_t s = h->stream.get();
+    const size_t hw = (size_t)h->H * h->W;
+    const int n = c.n;
+    const BatchMeta m = batch_meta(p, sl);
+    if (c.has_refs) {
+        const int rc = launch_refs(h, sl.ref, L.ref, c.refs.hist_flag, c.refs.flags, sl.d_glob_in.get(), false, s);
+        if (rc) return rc;
+    }
+    int mode = c.mode;
+    if (p.reveal) {   // the colours of the list the prologue is about to read; a dropped rectangle's (0, 0) is the memset's
+        float* d_cols = p.cols_bytes ? (float*)(sl.d_eval.get() + p.cols_at) : nullptr;
+        if (p.cols_bytes) HIPCHK(h, hipMemsetAsync(d_cols, 0, p.cols_bytes, s));
+        HIPCHK(h, launch_reveal_hints(sl.d_src.get(), m.tab, m.offs, n, 0, 0, h->H, h->W, m.hints, p.kept, m.orig, d_cols, s));
+        mode = IDC_HINT_AB;
+    }
+    if (c.ragged)
+        HIPCHK(h, launch_ragged_prologue(sl.d_src.get(), m.tab, n, h->H, h->W, c.l_cent, m.offs, m.hints, mode, c.mask_value, sl.d_L.get(), sl.d_ab.get(),
+                                         sl.d_mask.get(), s));
+    else
+        HIPCHK(h, launch_batch_prologue(sl.d_src.get(), n, c.src_h, c.src_w, h->H, h->W, c.l_cent, m.offs, m.hints, mode, c.mask_value, sl.d_L.get(),
+                                        sl.d_ab.get(), sl.d_mask.get(), s));
+    const int dist_n = h->dist_n;
+    // a distribution batch runs model_class into the HANDLE's distribution (the 313 head with idc_keep_dist writes dist_S on every forward anyway)
+    const int rc = run_graph(h, n, sl.d_L.get(), sl.d_ab.get(), sl.d_mask.get(), c.maskcent, sl.d_out.get(),
+                             (p.dist && !(h->flags & IDC_FLAG_DIST313)) ? h->d_dist.get() : nullptr, c.has_refs ? sl.d_glob_in.get() : h->d_glob_in.get());
+    if (rc) return rc;
+    if (!p.dist && !((h->flags & IDC_FLAG_DIST313) && h->keep_dist313)) h->dist_n = dist_n;      // no distribution was written: the blocking forward's stays resident
+    HIPCHK(h, launch_lab_post(sl.d_L.get(), c.l_cent, sl.d_out.get(), sl.d_rgb.get(), p.source_out ? sl.d_labq.get() : nullptr, n, h->H, h->W, s));
+    sl.up_interp = h->batch_interp; sl.up_joint = h->joint;       // the handle's setting as it is now: a later idc_set_batch_upsample does not reach this batch
+    if (p.source_out && sl.up_interp == IDC_INTERP_JOINT) {         // guide: the slot's own L plane and this call's l_cent
+        const double* pa = sl.d_labq.get() + hw;
+        HIPCHK(h, launch_joint_fullres(sl.d_src.get(), c.ragged ? m.tab : nullptr, n, c.src_h, c.src_w, p.max_tiles, pa, pa + hw, 1, (long long)(3 * hw),
+                                       sl.d_L.get(), c.l_cent, h->H, h->W, IDC_INTERP_JOINT, sl.up_joint, sl.d_full.get(), nullptr, s));
+    } else if (p.source_out && c.ragged)
+        HIPCHK(h, launch_ragged_fullres_rgb(sl.d_src.get(), m.tab, n, (long long)(p.in_bytes / 3), sl.d_labq.get(), h->H, h->W, IDC_INTERP_LINEAR,
+                                            sl.d_full.get(), s));
+    else if (p.source_out)
+        HIPCHK(h, launch_batch_fullres_rgb(sl.d_src.get(), n, c.src_h, c.src_w, sl.d_labq.get(), h->H, h->W, IDC_INTERP_LINEAR, sl.d_full.get(), s));
+    return IDC_OK;
+}
+
+// compute stream, second half: what an evaluation or distribution batch reads off the result
+static int batch_measure(idc_context* h, const BatchCall& c, const BatchPlan& p, const BatchLayouts& L, Slot& sl) {
+    hipStream_t s = h->stream.get();
+    const size_t hw = (size_t)h->H * h->W;
+    const int n = c.n;
+    const BatchMeta m = batch_meta(p, sl);
+    if (c.eval && c.sse) {     // the score: the source-size result against the source bytes, or the net-size result against the net-size ground truth
+        unsigned long long* d_sse = (unsigned long long*)sl.d_eval.get();
+        HIPCHK(h, hipMemsetAsync(d_sse, 0, (size_t)n * 3 * sizeof(uint64_t), s));
+        if (p.source_out) {
+            HIPCHK(h, launch_eval_sse(sl.d_full.get(), sl.d_src.get(), m.tab, n, 0, p.max_pixels, (long long)(p.in_bytes / 3), d_sse, s));
+        } else {
+            HIPCHK(h, launch_ragged_net_truth(sl.d_src.get(), m.tab, n, h->H, h->W, sl.d_truth.get(), s));
+            HIPCHK(h, launch_eval_sse(sl.d_rgb.get(), sl.d_truth.get(), nullptr, n, (long long)hw, (long long)hw, (long long)n * hw, d_sse, s));
+        }
+    }
+    if (p.dist && c.taps) {   // entropy, peaks, suggestions: behind this batch's network, so in front of whatever replaces the handle's distribution next
+        const int rc = launch_taps(h, L.geom, L.taps, c.taps, sl.d_mask.get(), sl.d_taps_in.get(), sl.d_taps.get(), s);
+        if (rc) return rc;
+    }
+    if (p.score) {    // behind the other taps: the cells' ground truth from the slot's own packed sources, then the score
+        HIPCHK(h, launch_dist_truth(sl.d_src.get(), m.tab, n, 0, 0, h->H, h->W, L.geom.s, (float*)(sl.d_score.get() + L.score.o_truth), s));
+        const int rc = launch_score(h, L.geom, L.score, (const float*)sl.d_score_in.get(), sl.d_score.get(), s);
+        if (rc) return rc;
+    }
+    return IDC_OK;
+}
+
+// rows of one result block that go to the caller's buffers; a NULL or empty one takes no copy
+struct OutRow { void* user; size_t at, bytes; };
+static int copy_out_rows(idc_context* h, Slot& sl, const OutRow* rows, size_t count, const unsigned char* dev, unsigned char* twin) {
+    for (const OutRow* o = rows; o < rows + count; ++o)
+        if (o->user && o->bytes) HIPCHK(h, copy_out(h, sl, o->user, is_pinned(o->user), dev, twin, o->at, o->bytes));
+    return IDC_OK;
+}
+
+// copy-out stream: score, taps, sse and colours, images, out_ab -- the small results first
+static int batch_copy_out(idc_context* h, const BatchCall& c, const BatchPlan& p, const BatchLayouts& L, Slot& sl) {
+    const size_t n = (size_t)c.n, hw = (size_t)h->H * h->W, npix = (size_t)L.geom.Hd * L.geom.Wd;
+    int rc = IDC_OK;
+    HIPCHK(h, hipEventRecord(sl.ev_out0.get(), h->s_out.get()));
+    sl.outs.clear();
+    if (p.score) {
+        const idc_dist_score_out* so = c.sout;
+        const ScoreLayout& sc = L.score;
+        const OutRow rows[] = {{so->xent, sc.o_xent, n * sizeof(double)},
+                               {sc.ranks.n > 0 ? so->hits : nullptr, sc.o_hits, n * sc.ranks.n * sizeof(unsigned)},
+                               {so->truth_ab, sc.o_truth, n * 2 * npix * sizeof(float)},
+                               {so->xent_map, sc.o_xmap, n * npix * sizeof(double)},
+                               {so->rank_map, sc.o_rmap, n * npix * sizeof(int)},
+                               {so->target, sc.o_tgt, n * npix * sizeof(int)}};
+        rc = copy_out_rows(h, sl, rows, sizeof(rows) / sizeof(rows[0]), sl.d_score.get(), sl.h_score.get());
+        if (rc) return rc;
+    }
+    if (p.dist && c.taps) {
+        const idc_dist_taps* tp = c.taps;
+        const TapsLayout& tl = L.taps;
+        const OutRow rows[] = {{tp->entropy, tl.o_ent, n * npix * sizeof(float)},
+                               {tl.P > 0 ? tp->peaks : nullptr, tl.o_peaks, n * tl.P * 2 * sizeof(int)},
+                               {tl.P > 0 ? tp->peak_ent : nullptr, tl.o_pent, n * tl.P * sizeof(float)},
+                               {tl.Q > 0 ? tp->sugg_centres : nullptr, tl.o_sc, (size_t)tl.Q * tl.K * 2 * sizeof(double)},
+                               {tl.Q > 0 ? tp->sugg_conf : nullptr, tl.o_sf, (size_t)tl.Q * tl.K * sizeof(double)}};
+        rc = copy_out_rows(h, sl, rows, sizeof(rows) / sizeof(rows[0]), sl.d_taps.get(), sl.h_taps.get());
+        if (rc) return rc;
+    }
+    if (c.eval) {
+        const OutRow rows[] = {{c.sse, 0, n * 3 * sizeof(uint64_t)}, {c.hint_colours, p.cols_at, p.cols_bytes}};
+        rc = copy_out_rows(h, sl, rows, sizeof(rows) / sizeof(rows[0]), sl.d_eval.get(), sl.h_eval.get());
+        if (rc) return rc;
+    }
+    if (p.want_rgb) {
+        HIPCHK(h, copy_pieces(p.pieces, false, p.source_out ? sl.d_full.get() : sl.d_rgb.get(), sl.h_rgb.get(), h->s_out.get()));
+        for (const Piece& q : p.pieces)
+            if (!q.out_pinned) sl.outs.push_back({q.out, sl.h_rgb.get() + q.out_at, q.out_bytes});
+    }
+    if (c.out_ab) HIPCHK(h, copy_out(h, sl, c.out_ab, p.ab_pinned, sl.d_out.get(), sl.h_out.get(), 0, n * hw * 2 * 4));
+    HIPCHK(h, hipEventRecord(sl.ev_out.get(), h->s_out.get()));
+    return IDC_OK;
+}
+
+// handle state -> plan_batch -> handle-dependent checks | reserve -> stage -> copy-in -> compute -> copy-out -> commit.  Left of the bar nothing
+// is allocated, written or enqueued, and for any argument list the first check that refuses it is the one include/ideepcolor.h's tables name
+static int forward_async_rgb(idc_handle h, const BatchCall& c) {
+    int rc = check_forward_args(h, c.n);
+    if (rc) return rc;
+    BatchPlan p;
+    std::string why;
+    rc = plan_batch(c, h->H, h->W, h->max_batch, &p, &why);
+    if (rc) return fail(&h->err, rc, "%s", why.c_str());
+    BatchLayouts L;
+    rc = batch_handle_checks(h, c, p, &L);
+    if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     rc = ensure_pipeline(h);
     if (rc) return rc;
-    // The slot is idle (its last batch was waited for), so its buffers may be replaced by larger ones
-    const size_t hw = (size_t)h->H * h->W, nb = (size_t)h->max_batch;
-    const bool source_out = (flags & IDC_BATCH_OUT_SOURCE) != 0;
-    const size_t rgb_bytes = source_out ? in_bytes : (size_t)n * hw * 3;
-    // the metadata block: the hint offsets int[max_batch + 1], (images of individual sizes) the table ImgDesc[max_batch + 1], the kept hints
-    const size_t table_at = align_up((nb + 1) * sizeof(int), 16);
-    const size_t hints_at = ragged ? table_at + align_up((nb + 1) * sizeof(ImgDesc), 16) : table_at;
-    // ... and (IDC_HINT_REVEAL) each kept hint's place in the caller's list int[kept], where its revealed colour is reported
-    const size_t orig_at = hints_at + (size_t)kept * sizeof(HintRect);
-    const size_t meta_bytes = orig_at + (reveal ? (size_t)kept * sizeof(int) : 0), meta_floor = hints_at + 256 * (sizeof(HintRect) + sizeof(int));
-    HIPCHK(h, sl.d_src.ensure(in_bytes));
-    HIPCHK(h, sl.d_meta.ensure(meta_bytes, meta_floor));
-    HIPCHK(h, sl.h_meta.ensure(meta_bytes, meta_floor));
-    HIPCHK(h, sl.d_rgb.ensure(nb * hw * 3));
-    if (source_out) {
-        HIPCHK(h, sl.d_labq.ensure(nb * hw * 3 * 8));
-        HIPCHK(h, sl.d_full.ensure(in_bytes));
-    }
-    const size_t cols_at = nb * 3 * sizeof(uint64_t), cols_bytes = ev && ev->hint_colours ? (size_t)n_hints * 2 * sizeof(float) : 0;
-    if (ev) {
-        if (!source_out) HIPCHK(h, sl.d_truth.ensure(nb * hw * 3));
-        HIPCHK(h, sl.d_eval.ensure(cols_at + cols_bytes, cols_at + 4096));
-        HIPCHK(h, sl.h_eval.ensure(cols_at + cols_bytes, cols_at + 4096));
-    }
-    if (dist) {     // the taps' queries and centres travel with the batch; their results wait in the slot's block
-        HIPCHK(h, sl.d_taps_in.ensure(tl.in_bytes, 65536));
-        HIPCHK(h, sl.h_taps_in.ensure(tl.in_bytes, 65536));
-        HIPCHK(h, sl.d_taps.ensure(tl.out_bytes, 65536));
-        HIPCHK(h, sl.h_taps.ensure(tl.out_bytes, 65536));
-        if (tl.Q > 0) {
-            if (!tl.at_peaks) memcpy(sl.h_taps_in.get(), ev->taps->queries, (size_t)tl.Q * sizeof(DistQuery));
-            memcpy(sl.h_taps_in.get() + tl.i_centres, ev->taps->centres, (size_t)geom.B * 2 * sizeof(float));
-        }
-    }
-    const size_t score_in_bytes = align_up((size_t)geom.B * 2 * sizeof(float), 16);
-    if (score) {    // the centres travel with the batch; the score's results wait in the slot's block
-        HIPCHK(h, sl.d_score_in.ensure(score_in_bytes, 8192));
-        HIPCHK(h, sl.h_score_in.ensure(score_in_bytes, 8192));
-        HIPCHK(h, sl.d_score.ensure(sc.out_bytes, 65536));
-        HIPCHK(h, sl.h_score.ensure(sc.out_bytes, 65536));
-        memcpy(sl.h_score_in.get(), ev->centres, (size_t)geom.B * 2 * sizeof(float));
-    }
-    // every host buffer is judged on its own: pageable sources are copied into the slot's pinned staging here, on the calling thread
-    std::vector<Piece> pieces;
-    if (ragged) {
-        ImgDesc* tab = (ImgDesc*)(sl.h_meta.get() + table_at);
-        size_t at = 0;
-        for (int i = 0; i < n; ++i) {
-            const size_t sb = (size_t)io.images[i].h * io.images[i].w * 3;
-            tab[i].off = (long long)at; tab[i].first = (long long)(at / 3); tab[i].h = io.images[i].h; tab[i].w = io.images[i].w;
-            uint8_t* const out = want_rgb ? io.outs[i] : nullptr;
-            pieces.push_back({io.images[i].rgb, out, at, sb, source_out ? at : (size_t)i * hw * 3, source_out ? sb : hw * 3,
-                              is_pinned(io.images[i].rgb), !want_rgb || is_pinned(out)});
-            at += sb;
-        }
-        tab[n].off = (long long)at; tab[n].first = (long long)(at / 3); tab[n].h = 0; tab[n].w = 0;
-    } else {
-        pieces.push_back({io.rgb_in, io.rgb_out, 0, in_bytes, 0, rgb_bytes, is_pinned(io.rgb_in), is_pinned(io.rgb_out)});
-    }
-    bool any_staged_in = false, any_staged_rgb = false;
-    for (const Piece& p : pieces) { any_staged_in |= !p.in_pinned; any_staged_rgb |= !p.out_pinned; }
-    if (any_staged_in) {
-        HIPCHK(h, sl.h_src.ensure(in_bytes));
-        for (const Piece& p : pieces)
-            if (!p.in_pinned) memcpy(sl.h_src.get() + p.in_at, p.in, p.in_bytes);
-    }
-    const bool staged_ab = out_ab && !is_pinned(out_ab);
-    if (any_staged_rgb) HIPCHK(h, sl.h_rgb.ensure(rgb_bytes));
-    if (staged_ab) HIPCHK(h, sl.h_out.ensure(nb * hw * 2 * 4));
-    // the list as the kernel reads it: offsets of the KEPT hints per image, then the clipped rectangles
-    int* m_offs = (int*)sl.h_meta.get();
-    HintRect* m_hints = (HintRect*)(sl.h_meta.get() + hints_at);
-    int* m_orig = (int*)(sl.h_meta.get() + orig_at);
-    m_offs[0] = 0;
-    for (int i = 0, w = 0; i < n; ++i) {
-        for (int k = hint_offsets ? hint_offsets[i] : 0; k < (hint_offsets ? hint_offsets[i + 1] : 0); ++k) {
-            HintRect r;                               // clip fills r even for a hint it drops: only a kept one may reach the block, which has room for `kept`
-            if (!clip(hints[k], r)) continue;
-            if (reveal) m_orig[w] = k;
-            m_hints[w++] = r;
-        }
-        m_offs[i + 1] = w;
-    }
-    if (ra) {
-        HIPCHK(h, sl.d_glob_in.ensure(nb * kGlobIn * sizeof(float)));
-        rc = stage_refs(h, sl.ref, lay, ra->refs, ra->ref_index, ra->centres, false);
-        if (rc) return rc;
-    }
-    HIPCHK(h, hipEventRecord(sl.ev_in0.get(), h->s_in.get()));
-    HIPCHK(h, copy_pieces(pieces, true, sl.d_src.get(), sl.h_src.get(), h->s_in.get()));
-    HIPCHK(h, hipMemcpyAsync(sl.d_meta.get(), sl.h_meta.get(), meta_bytes, hipMemcpyHostToDevice, h->s_in.get()));
-    if (dist && tl.Q > 0) HIPCHK(h, hipMemcpyAsync(sl.d_taps_in.get(), sl.h_taps_in.get(), tl.in_bytes, hipMemcpyHostToDevice, h->s_in.get()));
-    if (score) HIPCHK(h, hipMemcpyAsync(sl.d_score_in.get(), sl.h_score_in.get(), score_in_bytes, hipMemcpyHostToDevice, h->s_in.get()));
-    if (ra) {
-        rc = upload_refs(h, sl.ref, lay, h->s_in.get());
-        if (rc) return rc;
-    }
-    HIPCHK(h, hipEventRecord(sl.ev_in.get(), h->s_in.get()));
+    Slot& sl = h->pipe[c.slot];
+    for (Piece& q : p.pieces) { q.in_pinned = is_pinned(q.in); q.out_pinned = !p.want_rgb || is_pinned(q.out); }
+    p.ab_pinned = !c.out_ab || is_pinned(c.out_ab);
+    rc = batch_reserve(h, c, p, L, sl);
+    if (!rc) rc = batch_stage(h, c, p, L, sl);
+    if (!rc) rc = batch_copy_in(h, c, p, L, sl);
+    if (rc) return rc;
     HIPCHK(h, hipStreamWaitEvent(h->stream.get(), sl.ev_in.get(), 0));
     HIPCHK(h, hipEventRecord(sl.ev_comp0.get(), h->stream.get()));
-    if (ra) {
-        rc = launch_refs(h, sl.ref, lay, ra->hist_flag, ra->flags, sl.d_glob_in.get(), false, h->stream.get());
-        if (rc) return rc;
-    }
-    const int* d_offs = kept ? (const int*)sl.d_meta.get() : nullptr;
-    const HintRect* d_hints = (const HintRect*)(sl.d_meta.get() + hints_at);
-    const ImgDesc* d_tab = (const ImgDesc*)(sl.d_meta.get() + table_at);
-    if (reveal) {   // the colours of the list the prologue is about to read; a dropped rectangle's (0, 0) is the memset's
-        float* d_cols = cols_bytes ? (float*)(sl.d_eval.get() + cols_at) : nullptr;
-        if (cols_bytes) HIPCHK(h, hipMemsetAsync(d_cols, 0, cols_bytes, h->stream.get()));
-        HIPCHK(h, launch_reveal_hints(sl.d_src.get(), d_tab, d_offs, n, 0, 0, h->H, h->W, (HintRect*)(sl.d_meta.get() + hints_at), kept,
-                                      (const int*)(sl.d_meta.get() + orig_at), d_cols, h->stream.get()));
-        mode = IDC_HINT_AB;
-    }
-    if (ragged)
-        HIPCHK(h, launch_ragged_prologue(sl.d_src.get(), d_tab, n, h->H, h->W, l_cent, d_offs, d_hints, mode, mask_value, sl.d_L.get(), sl.d_ab.get(),
-                                         sl.d_mask.get(), h->stream.get()));
-    else
-        HIPCHK(h, launch_batch_prologue(sl.d_src.get(), n, io.src_h, io.src_w, h->H, h->W, l_cent, d_offs, d_hints, mode, mask_value, sl.d_L.get(),
-                                        sl.d_ab.get(), sl.d_mask.get(), h->stream.get()));
-    const int dist_n = h->dist_n;
-    // a distribution batch runs model_class into the HANDLE's distribution (the 313 head with idc_keep_dist writes dist_S on every forward anyway)
-    rc = run_graph(h, n, sl.d_L.get(), sl.d_ab.get(), sl.d_mask.get(), maskcent, sl.d_out.get(),
-                   (dist && !(h->flags & IDC_FLAG_DIST313)) ? h->d_dist.get() : nullptr, ra ? sl.d_glob_in.get() : h->d_glob_in.get());
+    rc = batch_colourise(h, c, p, L, sl);
+    if (!rc) rc = batch_measure(h, c, p, L, sl);
     if (rc) return rc;
-    if (!dist && !((h->flags & IDC_FLAG_DIST313) && h->keep_dist313)) h->dist_n = dist_n;      // no distribution was written: the blocking forward's stays resident
-    HIPCHK(h, launch_lab_post(sl.d_L.get(), l_cent, sl.d_out.get(), sl.d_rgb.get(), source_out ? sl.d_labq.get() : nullptr, n, h->H, h->W, h->stream.get()));
-    sl.up_interp = h->batch_interp; sl.up_joint = h->joint;       // the handle's setting as it is now: a later idc_set_batch_upsample does not reach this batch
-    if (source_out && sl.up_interp == IDC_INTERP_JOINT) {           // guide: the slot's own L plane and this call's l_cent
-        long long max_tiles = ragged ? 0 : joint_tiles(io.src_h, io.src_w);
-        for (int i = 0; ragged && i < n; ++i) max_tiles = std::max(max_tiles, joint_tiles(io.images[i].h, io.images[i].w));
-        const double* pa = sl.d_labq.get() + hw;
-        HIPCHK(h, launch_joint_fullres(sl.d_src.get(), ragged ? d_tab : nullptr, n, io.src_h, io.src_w, max_tiles, pa, pa + hw, 1, (long long)(3 * hw),
-                                       sl.d_L.get(), l_cent, h->H, h->W, IDC_INTERP_JOINT, sl.up_joint, sl.d_full.get(), nullptr, h->stream.get()));
-    } else if (source_out && ragged)
-        HIPCHK(h, launch_ragged_fullres_rgb(sl.d_src.get(), d_tab, n, (long long)(in_bytes / 3), sl.d_labq.get(), h->H, h->W, IDC_INTERP_LINEAR,
-                                            sl.d_full.get(), h->stream.get()));
-    else if (source_out)
-        HIPCHK(h, launch_batch_fullres_rgb(sl.d_src.get(), n, io.src_h, io.src_w, sl.d_labq.get(), h->H, h->W, IDC_INTERP_LINEAR, sl.d_full.get(), h->stream.get()));
-    if (ev && ev->sse) {       // the score: the source-size result against the source bytes, or the net-size result against the net-size ground truth
-        unsigned long long* d_sse = (unsigned long long*)sl.d_eval.get();
-        HIPCHK(h, hipMemsetAsync(d_sse, 0, (size_t)n * 3 * sizeof(uint64_t), h->stream.get()));
-        if (source_out) {
-            long long max_pixels = 0;
-            for (int i = 0; i < n; ++i) max_pixels = std::max(max_pixels, (long long)io.images[i].h * io.images[i].w);
-            HIPCHK(h, launch_eval_sse(sl.d_full.get(), sl.d_src.get(), d_tab, n, 0, max_pixels, (long long)(in_bytes / 3), d_sse, h->stream.get()));
-        } else {
-            HIPCHK(h, launch_ragged_net_truth(sl.d_src.get(), d_tab, n, h->H, h->W, sl.d_truth.get(), h->stream.get()));
-            HIPCHK(h, launch_eval_sse(sl.d_rgb.get(), sl.d_truth.get(), nullptr, n, (long long)hw, (long long)hw, (long long)n * hw, d_sse, h->stream.get()));
-        }
-    }
-    if (dist) {     // entropy, peaks, suggestions: on this stream behind this batch's network, so in front of whatever replaces the handle's distribution next
-        if (ev->taps) {
-            rc = launch_taps(h, geom, tl, ev->taps, sl.d_mask.get(), sl.d_taps_in.get(), sl.d_taps.get(), h->stream.get());
-            if (rc) return rc;
-        }
-        if (score) {    // behind the other taps: the cells' ground truth from the slot's own packed sources, then the score
-            HIPCHK(h, launch_dist_truth(sl.d_src.get(), d_tab, n, 0, 0, h->H, h->W, geom.s, (float*)(sl.d_score.get() + sc.o_truth), h->stream.get()));
-            rc = launch_score(h, geom, sc, (const float*)sl.d_score_in.get(), sl.d_score.get(), h->stream.get());
-            if (rc) return rc;
-        }
-    }
     HIPCHK(h, hipEventRecord(sl.ev_comp.get(), h->stream.get()));
     HIPCHK(h, hipStreamWaitEvent(h->s_out.get(), sl.ev_comp.get(), 0));
-    HIPCHK(h, hipEventRecord(sl.ev_out0.get(), h->s_out.get()));
-    sl.eval_outs.clear(); sl.taps_outs.clear(); sl.score_outs.clear();
-    if (score) {
-        const idc_dist_score_out* so = ev->sout;
-        const size_t npix = (size_t)geom.Hd * geom.Wd;
-        const struct { void* user; size_t at, bytes; } outs[] = {
-            {so->xent, sc.o_xent, (size_t)n * sizeof(double)},
-            {sc.ranks.n > 0 ? so->hits : nullptr, sc.o_hits, (size_t)n * sc.ranks.n * sizeof(unsigned)},
-            {so->truth_ab, sc.o_truth, (size_t)n * 2 * npix * sizeof(float)},
-            {so->xent_map, sc.o_xmap, (size_t)n * npix * sizeof(double)},
-            {so->rank_map, sc.o_rmap, (size_t)n * npix * sizeof(int)},
-            {so->target, sc.o_tgt, (size_t)n * npix * sizeof(int)}};
-        for (const auto& o : outs) {
-            if (!o.user || !o.bytes) continue;
-            const bool direct = is_pinned(o.user);
-            HIPCHK(h, hipMemcpyAsync(direct ? o.user : (void*)(sl.h_score.get() + o.at), sl.d_score.get() + o.at, o.bytes, hipMemcpyDeviceToHost, h->s_out.get()));
-            if (!direct) sl.score_outs.push_back({(uint8_t*)o.user, o.at, o.bytes});
-        }
-    }
-    if (dist && ev->taps) {
-        const idc_dist_taps* tp = ev->taps;
-        const size_t npix = (size_t)geom.Hd * geom.Wd;
-        const struct { void* user; size_t at, bytes; } outs[] = {
-            {tp->entropy, tl.o_ent, (size_t)n * npix * sizeof(float)},
-            {tl.P > 0 ? tp->peaks : nullptr, tl.o_peaks, (size_t)n * tl.P * 2 * sizeof(int)},
-            {tl.P > 0 ? tp->peak_ent : nullptr, tl.o_pent, (size_t)n * tl.P * sizeof(float)},
-            {tl.Q > 0 ? tp->sugg_centres : nullptr, tl.o_sc, (size_t)tl.Q * tl.K * 2 * sizeof(double)},
-            {tl.Q > 0 ? tp->sugg_conf : nullptr, tl.o_sf, (size_t)tl.Q * tl.K * sizeof(double)}};
-        for (const auto& o : outs) {
-            if (!o.user || !o.bytes) continue;
-            const bool direct = is_pinned(o.user);
-            HIPCHK(h, hipMemcpyAsync(direct ? o.user : (void*)(sl.h_taps.get() + o.at), sl.d_taps.get() + o.at, o.bytes, hipMemcpyDeviceToHost, h->s_out.get()));
-            if (!direct) sl.taps_outs.push_back({(uint8_t*)o.user, o.at, o.bytes});
-        }
-    }
-    if (ev) {
-        const size_t sse_bytes = (size_t)n * 3 * sizeof(uint64_t);
-        const bool sse_direct = ev->sse && is_pinned(ev->sse), cols_direct = cols_bytes && is_pinned(ev->hint_colours);
-        if (ev->sse) HIPCHK(h, hipMemcpyAsync(sse_direct ? (void*)ev->sse : (void*)sl.h_eval.get(), sl.d_eval.get(), sse_bytes, hipMemcpyDeviceToHost, h->s_out.get()));
-        if (ev->sse && !sse_direct) sl.eval_outs.push_back({(uint8_t*)ev->sse, 0, sse_bytes});
-        if (cols_bytes) {
-            HIPCHK(h, hipMemcpyAsync(cols_direct ? (void*)ev->hint_colours : (void*)(sl.h_eval.get() + cols_at), sl.d_eval.get() + cols_at, cols_bytes,
-                                     hipMemcpyDeviceToHost, h->s_out.get()));
-            if (!cols_direct) sl.eval_outs.push_back({(uint8_t*)ev->hint_colours, cols_at, cols_bytes});
-        }
-    }
-    if (want_rgb) HIPCHK(h, copy_pieces(pieces, false, source_out ? sl.d_full.get() : sl.d_rgb.get(), sl.h_rgb.get(), h->s_out.get()));
-    if (out_ab) HIPCHK(h, hipMemcpyAsync(staged_ab ? sl.h_out.get() : out_ab, sl.d_out.get(), (size_t)n * hw * 2 * 4, hipMemcpyDeviceToHost, h->s_out.get()));
-    HIPCHK(h, hipEventRecord(sl.ev_out.get(), h->s_out.get()));
-    sl.pending = true; sl.timed = true; sl.n = n;
-    sl.user_out = out_ab; sl.staged_out = staged_ab;
-    sl.staged_outs.clear();
-    for (const Piece& p : pieces)
-        if (!p.out_pinned) sl.staged_outs.push_back({p.out, p.out_at, p.out_bytes});
+    rc = batch_copy_out(h, c, p, L, sl);
+    if (rc) return rc;
+    sl.pending = true; sl.timed = true;      // only now: a call that failed on the way leaves the slot idle and usable
     return IDC_OK;
+}
+
+// The six entry points: fill a BatchCall, run it.  same_size_call / images_call take what idc_forward_async_rgb / idc_forward_async_images take.
+static BatchCall same_size_call(int slot, int n, int src_h, int src_w, const uint8_t* rgb_in, const int32_t* hint_offsets, const idc_hint* hints,
+                                int mode, float mask_value, float maskcent, float l_cent, unsigned flags, const idc_batch_refs* refs,
+                                uint8_t* rgb_out, float* out_ab) {
+    BatchCall c;
+    c.slot = slot; c.n = n; c.src_h = src_h; c.src_w = src_w; c.rgb_in = rgb_in; c.rgb_out = rgb_out;
+    c.hint_offsets = hint_offsets; c.hints = hints; c.mode = mode; c.mask_value = mask_value; c.maskcent = maskcent; c.l_cent = l_cent;
+    c.flags = flags; c.out_ab = out_ab;
+    set_batch_refs(c, refs);
+    return c;
+}
+
+static BatchCall images_call(int slot, int n, const idc_ref_image* images, const int32_t* hint_offsets, const idc_hint* hints, int mode,
+                             float mask_value, float maskcent, float l_cent, unsigned flags, const idc_batch_refs* refs, uint8_t* const* rgb_out,
+                             float* out_ab) {
+    BatchCall c = same_size_call(slot, n, 0, 0, nullptr, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, refs, nullptr, out_ab);
+    c.ragged = true; c.images = images; c.outs = rgb_out;
+    return c;
 }
 
 int idc_forward_async_rgb(idc_handle h, int slot, int n, int src_h, int src_w, const uint8_t* rgb_in, const int32_t* hint_offsets,
                           const idc_hint* hints, int mode, float mask_value, float maskcent, float l_cent, unsigned flags,
                           uint8_t* rgb_out, float* out_ab) {
-    const BatchIO io = {false, src_h, src_w, rgb_in, rgb_out, nullptr, nullptr};
-    return forward_async_rgb(h, slot, n, io, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, nullptr, out_ab);
+    return forward_async_rgb(h, same_size_call(slot, n, src_h, src_w, rgb_in, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, nullptr,
+                                               rgb_out, out_ab));
 }
 
 int idc_forward_async_rgb_ref(idc_handle h, int slot, int n, int src_h, int src_w, const uint8_t* rgb_in, const int32_t* hint_offsets,
                               const idc_hint* hints, int mode, float mask_value, float maskcent, float l_cent, unsigned flags, int m,
                               const idc_ref_image* refs, const int32_t* ref_index, const float* centres, float hist_flag, unsigned ref_flags,
                               uint8_t* rgb_out, float* out_ab) {
-    const RefArgs ra = {m, refs, ref_index, centres, hist_flag, ref_flags};
-    const BatchIO io = {false, src_h, src_w, rgb_in, rgb_out, nullptr, nullptr};
-    return forward_async_rgb(h, slot, n, io, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, &ra, out_ab);
+    const idc_batch_refs br = {m, refs, ref_index, centres, hist_flag, ref_flags};
+    return forward_async_rgb(h, same_size_call(slot, n, src_h, src_w, rgb_in, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, &br,
+                                               rgb_out, out_ab));
 }
 
 int idc_forward_async_images(idc_handle h, int slot, int n, const idc_ref_image* images, const int32_t* hint_offsets, const idc_hint* hints,
                              int mode, float mask_value, float maskcent, float l_cent, unsigned flags, const idc_batch_refs* refs,
                              uint8_t* const* rgb_out, float* out_ab) {
-    const BatchIO io = {true, 0, 0, nullptr, nullptr, images, rgb_out};
-    if (!refs) return forward_async_rgb(h, slot, n, io, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, nullptr, out_ab);
-    const RefArgs ra = {refs->m, refs->refs, refs->ref_index, refs->centres, refs->hist_flag, refs->flags};
-    return forward_async_rgb(h, slot, n, io, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, &ra, out_ab);
+    return forward_async_rgb(h, images_call(slot, n, images, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, refs, rgb_out, out_ab));
 }
 
 int idc_forward_async_eval(idc_handle h, int slot, int n, const idc_ref_image* images, const int32_t* hint_offsets, const idc_hint* hints,
                            int mode, float mask_value, float maskcent, float l_cent, unsigned flags, const idc_batch_refs* refs,
                            uint8_t* const* rgb_out, float* out_ab, uint64_t* sse, float* hint_colours) {
-    const BatchIO io = {true, 0, 0, nullptr, nullptr, images, rgb_out};
-    const EvalArgs ev = {sse, hint_colours};
-    if (!refs) return forward_async_rgb(h, slot, n, io, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, nullptr, out_ab, &ev);
-    const RefArgs ra = {refs->m, refs->refs, refs->ref_index, refs->centres, refs->hist_flag, refs->flags};
-    return forward_async_rgb(h, slot, n, io, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, &ra, out_ab, &ev);
+    BatchCall c = images_call(slot, n, images, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, refs, rgb_out, out_ab);
+    c.eval = true; c.sse = sse; c.hint_colours = hint_colours;
+    return forward_async_rgb(h, c);
 }
 
 int idc_forward_async_dist(idc_handle h, int slot, int n, const idc_ref_image* images, const int32_t* hint_offsets, const idc_hint* hints,
                            int mode, float mask_value, float maskcent, float l_cent, unsigned flags, const idc_batch_refs* refs,
                            uint8_t* const* rgb_out, float* out_ab, uint64_t* sse, float* hint_colours, const idc_dist_taps* taps) {
-    const BatchIO io = {true, 0, 0, nullptr, nullptr, images, rgb_out};
-    const EvalArgs ev = {sse, hint_colours, true, taps};
-    if (!refs) return forward_async_rgb(h, slot, n, io, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, nullptr, out_ab, &ev);
-    const RefArgs ra = {refs->m, refs->refs, refs->ref_index, refs->centres, refs->hist_flag, refs->flags};
-    return forward_async_rgb(h, slot, n, io, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, &ra, out_ab, &ev);
+    BatchCall c = images_call(slot, n, images, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, refs, rgb_out, out_ab);
+    c.eval = true; c.sse = sse; c.hint_colours = hint_colours;
+    c.taps_call = true; c.taps = taps;
+    return forward_async_rgb(h, c);
 }
 
 int idc_forward_async_dist_score(idc_handle h, int slot, int n, const idc_ref_image* images, const int32_t* hint_offsets, const idc_hint* hints,
                                  int mode, float mask_value, float maskcent, float l_cent, unsigned flags, const idc_batch_refs* refs,
                                  uint8_t* const* rgb_out, float* out_ab, uint64_t* sse, float* hint_colours, const idc_dist_taps* taps,
                                  const idc_dist_score_spec* spec, const float* centres, const idc_dist_score_out* out) {
-    const BatchIO io = {true, 0, 0, nullptr, nullptr, images, rgb_out};
-    const EvalArgs ev = {sse, hint_colours, true, taps, true, spec, centres, out};
-    if (!refs) return forward_async_rgb(h, slot, n, io, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, nullptr, out_ab, &ev);
-    const RefArgs ra = {refs->m, refs->refs, refs->ref_index, refs->centres, refs->hist_flag, refs->flags};
-    return forward_async_rgb(h, slot, n, io, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, &ra, out_ab, &ev);
+    BatchCall c = images_call(slot, n, images, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, refs, rgb_out, out_ab);
+    c.eval = true; c.sse = sse; c.hint_colours = hint_colours;
+    c.taps_call = true; c.taps = taps;
+    c.score_call = true; c.spec = spec; c.centres = centres; c.sout = out;
+    return forward_async_rgb(h, c);
 }
 
 int idc_wait(idc_handle h, int slot) {

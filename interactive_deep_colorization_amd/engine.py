@@ -441,6 +441,28 @@ def _ref_index(ref_index, n):
     return idx
 
 
+def _ref_args(refs, ref_index, centres, hist_flag, saturation, n):
+    """The reference arguments of a pipelined call, checked: (m, ``N.RefImage`` array or None, ref_index (n,) int32 or None, centres (313,2)
+    float32 or None, hist_flag, flags) and the arrays the table points into.  All of it has to live until the call has returned: it copies."""
+    if isinstance(refs, np.ndarray) and refs.ndim == 3:
+        refs = [refs]
+    rarr, keep = ref_images(refs)
+    idx = _ref_index(ref_index, n)
+    c = _f32c(centres, (313, 2)) if centres is not None else None
+    return (len(keep), rarr if keep else None, idx, c, float(hist_flag), N.IDC_REF_SATURATION if saturation else 0), keep
+
+
+def _image_item(who, item, with_ref):
+    """One item of ``who``'s image stream -- ``rgb``, ``(rgb, hints)`` or, ``with_ref``, ``(rgb, hints, ref)`` -- as (rgb, hints) or
+    (rgb, hints, ref, whether the item had a reference field)."""
+    item = (item,) if isinstance(item, np.ndarray) else tuple(item)
+    rgb = np.asarray(item[0])
+    if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.size == 0:
+        raise ValueError("%s needs uint8 (h,w,3) images, got %s %s" % (who, rgb.dtype, rgb.shape))
+    hints = item[1] if len(item) > 1 else None
+    return (rgb, hints, item[2] if len(item) > 2 else None, len(item) > 2) if with_ref else (rgb, hints)
+
+
 class HipColorizer(object):
     def __init__(self, H=256, W=None, max_batch=1, precision="bf16", device=0, dist=False, global_hints=False, dist313=False,
                  throughput_blob=False):
@@ -1071,15 +1093,9 @@ class HipColorizer(object):
         if refs is None:
             self._chk(self.lib.idc_forward_async_rgb(*(head + tail)))
         else:
-            if isinstance(refs, np.ndarray) and refs.ndim == 3:
-                refs = [refs]
-            rarr, keep = ref_images(refs)
-            m = len(keep)
-            idx = _ref_index(ref_index, n)
-            c = _f32c(centres, (313, 2)) if centres is not None else None
-            self._chk(self.lib.idc_forward_async_rgb_ref(*(head + (m, rarr if m else None, idx.ctypes.data_as(vp) if idx is not None else None,
-                                                                   _fptr(c) if c is not None else None, float(hist_flag),
-                                                                   N.IDC_REF_SATURATION if saturation else 0) + tail)))
+            (m, rarr, idx, c, hist_flag, rflags), keep = _ref_args(refs, ref_index, centres, hist_flag, saturation, n)
+            self._chk(self.lib.idc_forward_async_rgb_ref(*(head + (m, rarr, idx.ctypes.data_as(vp) if idx is not None else None,
+                                                                   _fptr(c) if c is not None else None, hist_flag, rflags) + tail)))
         self._in_flight[int(slot)] = (rgb, out_rgb, out_ab)      # the library reads / writes them until the slot's wait
 
     def colorize_stream(self, batches, out="net", upsample=None, **kw):
@@ -1093,38 +1109,62 @@ class HipColorizer(object):
         ``kw`` then also carries centres (needed), hist_flag and saturation.  A two-entry item makes the plain call.
         ``upsample``: 'linear' or 'joint' -- ``set_batch_upsample`` before the first batch, the previous setting back when the generator
         ends or is abandoned; None (default) leaves the setting alone."""
-        pending = [None, None]                      # per slot: (pinned result, pinned source) of the batch in flight
+        def submit(slot, group, first):
+            item = group[0]
+            rgb, hints = item[0], item[1]
+            rgb = np.asarray(rgb)
+            if rgb.dtype != np.uint8 or rgb.ndim != 4 or rgb.shape[3] != 3:
+                raise ValueError("colorize_stream needs uint8 (n,h,w,3) batches, got %s %s" % (rgb.dtype, rgb.shape))
+            src = self._pool.take(rgb.shape, np.uint8)
+            np.copyto(src, rgb)
+            dst = self._pool.take(rgb.shape if out == "source" else (rgb.shape[0], self.H, self.W, 3), np.uint8)
+            if len(item) > 2:
+                uniq, index = dedupe_refs(item[2], rgb.shape[0])
+                self.forward_async_rgb(slot, src, hints, dst, out=out, refs=uniq, ref_index=index, **kw)
+            else:
+                self.forward_async_rgb(slot, src, hints, dst, out=out, **kw)
+            return dst, src
 
-        def finish(slot):
+        # a group of one: the items are whole batches, checked in submit, behind the yield of the slot's older result
+        yield from self._two_slot_stream(batches, 1, upsample, lambda item: item, submit, lambda state: [np.array(state[0])])
+
+    def _two_slot_stream(self, items, batch, upsample, parse, submit, finish):
+        """The generator behind ``colorize_stream``, ``colorize_images`` and their relatives: ``parse(item)`` every item as it arrives, group
+        ``batch`` of them (default ``max_batch``; the last group may be shorter), ``submit(slot, group, first_index)`` group k on slot k % 2
+        once that slot's older batch is finished -- ``first_index`` is the stream index of the group's first item; what it returns (results
+        and whatever must stay alive: pinned pool memory) is kept until ``wait(slot)`` has returned -- and yield everything in
+        ``finish(state)`` of each batch in input order.  ``upsample`` as in ``colorize_stream``.  A consumer that stops early: both slots are
+        waited for, so nothing stays in flight on buffers about to be recycled, then the upsample setting goes back."""
+        batch = self._group_size(batch)
+        pending = [None, None]                      # per slot: submit's state of the batch in flight
+
+        def groups():
+            group = []
+            for item in items:
+                group.append(parse(item))
+                if len(group) == batch:
+                    yield group
+                    group = []
+            if group:
+                yield group
+
+        def drain(slot):
             self.wait(slot)
-            res, pending[slot] = pending[slot][0], None
-            return np.array(res)
+            state, pending[slot] = pending[slot], None
+            return finish(state)
 
-        k = 0
+        k, first = 0, 0
         restore = self._upsample_scope(upsample)
         try:
-            for item in batches:
-                rgb, hints = item[0], item[1]
-                slot = k & 1
-                if pending[slot] is not None:
-                    yield finish(slot)
-                rgb = np.asarray(rgb)
-                if rgb.dtype != np.uint8 or rgb.ndim != 4 or rgb.shape[3] != 3:
-                    raise ValueError("colorize_stream needs uint8 (n,h,w,3) batches, got %s %s" % (rgb.dtype, rgb.shape))
-                src = self._pool.take(rgb.shape, np.uint8)
-                np.copyto(src, rgb)
-                dst = self._pool.take(rgb.shape if out == "source" else (rgb.shape[0], self.H, self.W, 3), np.uint8)
-                if len(item) > 2:
-                    uniq, index = dedupe_refs(item[2], rgb.shape[0])
-                    self.forward_async_rgb(slot, src, hints, dst, out=out, refs=uniq, ref_index=index, **kw)
-                else:
-                    self.forward_async_rgb(slot, src, hints, dst, out=out, **kw)
-                pending[slot] = (dst, src)
-                k += 1
+            for group in groups():
+                if pending[k & 1] is not None:
+                    yield from drain(k & 1)
+                pending[k & 1] = submit(k & 1, group, first)
+                k, first = k + 1, first + len(group)
             for slot in (k & 1, (k + 1) & 1):       # the older batch first
                 if pending[slot] is not None:
-                    yield finish(slot)
-        finally:                                    # a consumer that stops early: nothing stays in flight on buffers about to be recycled
+                    yield from drain(slot)
+        finally:
             try:
                 for slot in (0, 1):
                     if pending[slot] is not None:
@@ -1133,6 +1173,20 @@ class HipColorizer(object):
             finally:
                 if restore is not None:
                     self.set_batch_upsample(restore)
+
+    def _group_size(self, batch):
+        batch = self.max_batch if batch is None else int(batch)
+        if batch != 1 and not 1 <= batch <= self.max_batch:       # (one image fits every engine)
+            raise ValueError("batch %d outside 1..%d" % (batch, self.max_batch))
+        return batch
+
+    def _pinned_sources(self, group):
+        """The images of a parsed group (``_image_item``), copied into one pinned pool block."""
+        srcs = self._pinned_slices([g[0].shape for g in group])
+        for s, g in zip(srcs, group):
+            np.copyto(s, g[0])
+        return srcs
+
 
     def _pinned_slices(self, shapes):
         """One pinned pool block (a multiple of 64 KiB, so that blocks of ragged batches recycle) sliced into uint8 arrays of ``shapes``."""
@@ -1222,13 +1276,8 @@ class HipColorizer(object):
                 outs[i] = out_rgb[i].ctypes.data
         block = None
         if refs is not None:
-            if isinstance(refs, np.ndarray) and refs.ndim == 3:
-                refs = [refs]
-            rarr, keep = ref_images(refs)                          # (rarr, keep, idx and c live until the call has returned: it copies them)
-            idx = _ref_index(ref_index, n)
-            c = _f32c(centres, (313, 2)) if centres is not None else None
-            block = N.BatchRefs(len(keep), rarr if keep else None, idx.ctypes.data if idx is not None else None,
-                                c.ctypes.data if c is not None else None, float(hist_flag), N.IDC_REF_SATURATION if saturation else 0)
+            (m, rarr, idx, c, hist_flag, rflags), keep = _ref_args(refs, ref_index, centres, hist_flag, saturation, n)
+            block = N.BatchRefs(m, rarr, idx.ctypes.data if idx is not None else None, c.ctypes.data if c is not None else None, hist_flag, rflags)
         args = (self._h, int(slot), int(n), table, offsets.ctypes.data_as(vp) if offsets is not None else None,
                 ctypes.cast(arr, vp) if arr is not None else None, modes[mode], float(mask_value),
                 float(maskcent), float(l_cent), flags, ctypes.byref(block) if block is not None else None, outs,
@@ -1298,66 +1347,15 @@ class HipColorizer(object):
         caller's own copy.  Sources travel through one pinned pool block per batch; the same reference OBJECT given for several images of a
         batch is uploaded once (``dedupe_refs``).  ``kw``: mode, mask_value, maskcent, l_cent, centres, hist_flag, saturation.
         ``upsample``: as in ``colorize_stream`` ('joint': the edge-aware source-size output)."""
-        batch = self.max_batch if batch is None else int(batch)
-        if not 1 <= batch <= self.max_batch:
-            raise ValueError("batch %d outside 1..%d" % (batch, self.max_batch))
-        pending = [None, None]                      # per slot: (pinned results, pinned sources) of the batch in flight
-
-        def finish(slot):
-            self.wait(slot)
-            res, pending[slot] = pending[slot][0], None
-            return [np.array(r) for r in res]
-
-        def submit(slot, group):
-            srcs = self._pinned_slices([g[0].shape for g in group])
-            for s, g in zip(srcs, group):
-                np.copyto(s, g[0])
-            hints = [g[1] for g in group]
+        def submit(slot, group, first):
+            srcs = self._pinned_sources(group)
+            more = dict(kw)
             if any(g[3] for g in group):
-                uniq, index = dedupe_refs([g[2] for g in group], len(group))
-                res = self.forward_async_images(slot, srcs, hints, out=out, refs=uniq, ref_index=index, **kw)
-            else:
-                res = self.forward_async_images(slot, srcs, hints, out=out, **kw)
-            pending[slot] = (res, srcs)
+                more["refs"], more["ref_index"] = dedupe_refs([g[2] for g in group], len(group))
+            return self.forward_async_images(slot, srcs, [g[1] for g in group], out=out, **more), srcs
 
-        def parse(item):
-            item = (item,) if isinstance(item, np.ndarray) else tuple(item)
-            rgb = np.asarray(item[0])
-            if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.size == 0:
-                raise ValueError("colorize_images needs uint8 (h,w,3) images, got %s %s" % (rgb.dtype, rgb.shape))
-            return rgb, item[1] if len(item) > 1 else None, item[2] if len(item) > 2 else None, len(item) > 2
-
-        k, group = 0, []
-        restore = self._upsample_scope(upsample)
-        try:
-            for item in items:
-                group.append(parse(item))
-                if len(group) < batch:
-                    continue
-                if pending[k & 1] is not None:
-                    for r in finish(k & 1):
-                        yield r
-                submit(k & 1, group)
-                k, group = k + 1, []
-            if group:
-                if pending[k & 1] is not None:
-                    for r in finish(k & 1):
-                        yield r
-                submit(k & 1, group)
-                k += 1
-            for slot in (k & 1, (k + 1) & 1):       # the older batch first
-                if pending[slot] is not None:
-                    for r in finish(slot):
-                        yield r
-        finally:                                    # a consumer that stops early: nothing stays in flight on buffers about to be recycled
-            try:
-                for slot in (0, 1):
-                    if pending[slot] is not None:
-                        pending[slot] = None
-                        self.wait(slot)
-            finally:
-                if restore is not None:
-                    self.set_batch_upsample(restore)
+        yield from self._two_slot_stream(items, batch, upsample, lambda item: _image_item("colorize_images", item, True), submit,
+                                         lambda state: [np.array(r) for r in state[0]])
 
     def evaluate_images(self, items, batch=None, out="net", mode="reveal", upsample=None, **kw):
         """Generator: score a stream of ground-truth colour images with both pipeline slots busy -- ``colorize_images`` whose every image is
@@ -1368,66 +1366,20 @@ class HipColorizer(object):
         (out='source'), ``inf`` for an exact match.  24 bytes per image come back; no image does.  ``upsample``: as in ``colorize_stream``;
         with out='source' the score is then that of the joint image."""
         from .evaluate import psnr_from_sse
-        batch = self.max_batch if batch is None else int(batch)
-        if not 1 <= batch <= self.max_batch:
-            raise ValueError("batch %d outside 1..%d" % (batch, self.max_batch))
-        pending = [None, None]                      # per slot: (pinned sse, sizes, pinned sources) of the batch in flight
 
-        def finish(slot):
-            self.wait(slot)
-            (sse, sizes, _), pending[slot] = pending[slot], None
-            sse = np.array(sse)
-            return [(psnr_from_sse(sse[i], h, w), sse[i]) for i, (h, w) in enumerate(sizes)]
-
-        def submit(slot, group):
-            srcs = self._pinned_slices([g[0].shape for g in group])
-            for s, g in zip(srcs, group):
-                np.copyto(s, g[0])
-            hints = [g[1] for g in group]
+        def submit(slot, group, first):
+            srcs = self._pinned_sources(group)
             more = dict(kw)
             if any(g[3] for g in group):
                 more["refs"], more["ref_index"] = dedupe_refs([g[2] for g in group], len(group))
-            sse = self.forward_async_eval(slot, srcs, hints, out=out, mode=mode, want_rgb=False, **more)[0]
-            pending[slot] = (sse, [g[0].shape[:2] if out == "source" else (self.H, self.W) for g in group], srcs)
+            sse = self.forward_async_eval(slot, srcs, [g[1] for g in group], out=out, mode=mode, want_rgb=False, **more)[0]
+            return sse, [g[0].shape[:2] if out == "source" else (self.H, self.W) for g in group], srcs
 
-        def parse(item):
-            item = (item,) if isinstance(item, np.ndarray) else tuple(item)
-            rgb = np.asarray(item[0])
-            if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.size == 0:
-                raise ValueError("evaluate_images needs uint8 (h,w,3) images, got %s %s" % (rgb.dtype, rgb.shape))
-            return rgb, item[1] if len(item) > 1 else None, item[2] if len(item) > 2 else None, len(item) > 2
+        def finish(state):
+            sse = np.array(state[0])
+            return [(psnr_from_sse(sse[i], h, w), sse[i]) for i, (h, w) in enumerate(state[1])]
 
-        k, group = 0, []
-        restore = self._upsample_scope(upsample)
-        try:
-            for item in items:
-                group.append(parse(item))
-                if len(group) < batch:
-                    continue
-                if pending[k & 1] is not None:
-                    for r in finish(k & 1):
-                        yield r
-                submit(k & 1, group)
-                k, group = k + 1, []
-            if group:
-                if pending[k & 1] is not None:
-                    for r in finish(k & 1):
-                        yield r
-                submit(k & 1, group)
-                k += 1
-            for slot in (k & 1, (k + 1) & 1):       # the older batch first
-                if pending[slot] is not None:
-                    for r in finish(slot):
-                        yield r
-        finally:                                    # a consumer that stops early: nothing stays in flight on buffers about to be recycled
-            try:
-                for slot in (0, 1):
-                    if pending[slot] is not None:
-                        pending[slot] = None
-                        self.wait(slot)
-            finally:
-                if restore is not None:
-                    self.set_batch_upsample(restore)
+        yield from self._two_slot_stream(items, batch, upsample, lambda item: _image_item("evaluate_images", item, True), submit, finish)
 
     def suggest_images(self, items, centres, batch=None, out="source", peaks=8, radius=2, skip_hints=True, K=5, N_draws=25000, seed=0,
                        upsample=None, **kw):
@@ -1438,68 +1390,25 @@ class HipColorizer(object):
         the K suggested colours of each with their shares.  Peak k of the g-th image of the stream draws with seed ``seed + g * peaks + k``,
         whatever the batch size.  ``centres`` (B,2): the bin centres; ``kw``: mode, mask_value, maskcent, l_cent.  ``upsample``: as in
         ``colorize_stream``."""
-        batch = self.max_batch if batch is None else int(batch)
-        if not 1 <= batch <= self.max_batch:
-            raise ValueError("batch %d outside 1..%d" % (batch, self.max_batch))
         P = int(peaks)
-        if P < 1:
-            raise ValueError("suggest_images needs at least one peak per image")
-        pending = [None, None]                      # per slot: (DistBatch, pinned sources) of the batch in flight
 
-        def finish(slot):
-            self.wait(slot)
-            (res, srcs), pending[slot] = pending[slot], None
+        def submit(slot, group, first):
+            srcs = self._pinned_sources(group)
+            res = self.forward_async_dist(slot, srcs, [g[1] for g in group], out=out, want_rgb=True, peaks=P, radius=radius, skip_hints=skip_hints,
+                                          queries="peaks", K=K, N_draws=N_draws, seed=int(seed) + first * P, centres=centres, **kw)
+            return res, srcs
+
+        def finish(state):
+            res, srcs = state
             K_ = res.sugg_centres.shape[1]
             sc, sf = np.array(res.sugg_centres).reshape(len(srcs), P, K_, 2), np.array(res.sugg_conf).reshape(len(srcs), P, K_)
             pk = np.array(res.peaks)
             return [(np.array(r), pk[i], sc[i], sf[i]) for i, r in enumerate(res.out_rgb)]
 
-        def submit(slot, group, first):
-            srcs = self._pinned_slices([g[0].shape for g in group])
-            for s, g in zip(srcs, group):
-                np.copyto(s, g[0])
-            res = self.forward_async_dist(slot, srcs, [g[1] for g in group], out=out, want_rgb=True, peaks=P, radius=radius, skip_hints=skip_hints,
-                                          queries="peaks", K=K, N_draws=N_draws, seed=int(seed) + first * P, centres=centres, **kw)
-            pending[slot] = (res, srcs)
-
-        def parse(item):
-            item = (item,) if isinstance(item, np.ndarray) else tuple(item)
-            rgb = np.asarray(item[0])
-            if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.size == 0:
-                raise ValueError("suggest_images needs uint8 (h,w,3) images, got %s %s" % (rgb.dtype, rgb.shape))
-            return rgb, item[1] if len(item) > 1 else None
-
-        k, group, done = 0, [], 0
-        restore = self._upsample_scope(upsample)
-        try:
-            for item in items:
-                group.append(parse(item))
-                if len(group) < batch:
-                    continue
-                if pending[k & 1] is not None:
-                    for r in finish(k & 1):
-                        yield r
-                submit(k & 1, group, done)
-                k, done, group = k + 1, done + len(group), []
-            if group:
-                if pending[k & 1] is not None:
-                    for r in finish(k & 1):
-                        yield r
-                submit(k & 1, group, done)
-                k += 1
-            for slot in (k & 1, (k + 1) & 1):       # the older batch first
-                if pending[slot] is not None:
-                    for r in finish(slot):
-                        yield r
-        finally:                                    # a consumer that stops early: nothing stays in flight on buffers about to be recycled
-            try:
-                for slot in (0, 1):
-                    if pending[slot] is not None:
-                        pending[slot] = None
-                        self.wait(slot)
-            finally:
-                if restore is not None:
-                    self.set_batch_upsample(restore)
+        batch = self._group_size(batch)
+        if P < 1:
+            raise ValueError("suggest_images needs at least one peak per image")
+        yield from self._two_slot_stream(items, batch, upsample, lambda item: _image_item("suggest_images", item, False), submit, finish)
 
     def score_images(self, items, centres, batch=None, nn=1, sigma=5.0, ranks=(1, 5), mode="reveal", want_psnr=False, upsample=None, **kw):
         """Generator: score the distribution head on a stream of ground-truth colour images with both pipeline slots busy --
@@ -1510,64 +1419,19 @@ class HipColorizer(object):
         (``None`` otherwise).  A few dozen bytes per image come back; no image and no distribution does.  ``kw``: mask_value, maskcent, l_cent.
         ``upsample``: as in ``colorize_stream``."""
         from .evaluate import psnr_from_sse
-        batch = self.max_batch if batch is None else int(batch)
-        if not 1 <= batch <= self.max_batch:
-            raise ValueError("batch %d outside 1..%d" % (batch, self.max_batch))
         score = dict(centres=centres, nn=nn, sigma=sigma, ranks=tuple(ranks))
-        pending = [None, None]                      # per slot: (DistBatch, pinned sources) of the batch in flight
 
-        def finish(slot):
-            self.wait(slot)
-            (res, _), pending[slot] = pending[slot], None
+        def submit(slot, group, first):
+            srcs = self._pinned_sources(group)
+            return self.forward_async_dist(slot, srcs, [g[1] for g in group], mode=mode, want_sse=bool(want_psnr), peaks=0, score=score, **kw), srcs
+
+        def finish(state):
+            res = state[0]
             mean, hits = res.score.mean(), np.array(res.score.hits)
             sse = np.array(res.sse) if want_psnr else None
             return [(float(mean[i]), hits[i], psnr_from_sse(sse[i], self.H, self.W) if want_psnr else None) for i in range(len(mean))]
 
-        def submit(slot, group):
-            srcs = self._pinned_slices([g[0].shape for g in group])
-            for s, g in zip(srcs, group):
-                np.copyto(s, g[0])
-            res = self.forward_async_dist(slot, srcs, [g[1] for g in group], mode=mode, want_sse=bool(want_psnr), peaks=0, score=score, **kw)
-            pending[slot] = (res, srcs)
-
-        def parse(item):
-            item = (item,) if isinstance(item, np.ndarray) else tuple(item)
-            rgb = np.asarray(item[0])
-            if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.size == 0:
-                raise ValueError("score_images needs uint8 (h,w,3) images, got %s %s" % (rgb.dtype, rgb.shape))
-            return rgb, item[1] if len(item) > 1 else None
-
-        k, group = 0, []
-        restore = self._upsample_scope(upsample)
-        try:
-            for item in items:
-                group.append(parse(item))
-                if len(group) < batch:
-                    continue
-                if pending[k & 1] is not None:
-                    for r in finish(k & 1):
-                        yield r
-                submit(k & 1, group)
-                k, group = k + 1, []
-            if group:
-                if pending[k & 1] is not None:
-                    for r in finish(k & 1):
-                        yield r
-                submit(k & 1, group)
-                k += 1
-            for slot in (k & 1, (k + 1) & 1):       # the older batch first
-                if pending[slot] is not None:
-                    for r in finish(slot):
-                        yield r
-        finally:                                    # a consumer that stops early: nothing stays in flight on buffers about to be recycled
-            try:
-                for slot in (0, 1):
-                    if pending[slot] is not None:
-                        pending[slot] = None
-                        self.wait(slot)
-            finally:
-                if restore is not None:
-                    self.set_batch_upsample(restore)
+        yield from self._two_slot_stream(items, batch, upsample, lambda item: _image_item("score_images", item, False), submit, finish)
 
     def wait(self, slot):
         self._chk(self.lib.idc_wait(self._h, int(slot)))
