@@ -454,6 +454,40 @@ int idc_set_joint_upsample(idc_handle h, int radius, double sigma_s, double sigm
 int idc_fullres_ab(idc_handle h, int img, int source, int interp, double* ab);
 int idc_set_batch_upsample(idc_handle h, int interp);
 
+/* ---- greyscale sources: single-channel scans in, 8- or 16-bit RGB out (blocking route).  A black-and-white photograph is one plane; an
+ *      archive's scan of one has 16 bits.  L passes through this pipeline untouched at the source size (IDC_L_IMAGE), so all 16 bits of
+ *      lightness reach the result when the entry and exit formats let them.  There is no expanded RGB copy of the plane on either side.
+ *      THE RULE.  Source: one plane [h,w] of uint8 (bits = 8) or uint16 (bits = 16, native byte order, 2-byte-aligned host pointer).  The
+ *      pixel's sRGB value is v / 255.0 or v / 65535.0 in float64, the same on all three channels.
+ *        Net-size grey: the ingestion rule of idc_set_image_rgb on the one channel (half-pixel centres, taps clamped to the image, float64,
+ *            contraction off, round half up), clamped to 0..255 or 0..65535: the 16-bit route rounds on the 16-bit lattice.  The identity
+ *            at the net size.
+ *        L = rgb2lab's second half on {t, t, t} with t = sRGB-to-linear(value / full scale): the expressions of every other route on those
+ *            operands, not a shortened Y-only formula.  The slot's L plane is (float)(L - l_cent).
+ *        Source-size output: L of the source sample itself (IDC_L_IMAGE) or IDC_L_MASK50, (a, b) by the interps of idc_fullres_rgb, joint
+ *            included, then Lab -> sRGB s in [0, 1] per channel.  8-bit out: (uint8)(s * 255.0), as everywhere.  16-bit out:
+ *            (uint16)(s * 65535.0), the same truncation; [.,.,3] uint16, native order.
+ *        Two identities follow and the tests hold both.  (I8) a uint8 plane g gives, bit for bit, what the RGB route gives for g repeated
+ *            on three channels: the L plane, gray_net == rgb_net[..., 0], l_net == lab_net[:, 0], every image and idc_fullres_ab.  (I16) a
+ *            uint16 plane 257 * g gives the results of the uint8 plane g bit for bit where nothing is resized (source size == net size):
+ *            fl(257 g / 65535) == fl(g / 255) for every g in 0..255, both the correctly rounded quotient of the same real number.  With a
+ *            resize the two differ, because the 16-bit route rounds on the finer lattice: that difference is the point.
+ *      idc_set_image_gray = idc_set_image_rgb for n planes pix [n,src_h,src_w]: same slots, same residency rules (IDC_INGEST_KEEP_SOURCE
+ *      keeps src_h*src_w*bits/8 bytes per slot), same statuses, and IDC_ERR_INVALID_ARG for bits other than 8 or 16, NULL pix, or an odd
+ *      pix / gray_net address at 16 bits.  gray_net [n,H,W] (the sample type) and l_net [n,H,W] float64 receive the net-size plane and
+ *      its L; each may be NULL.
+ *      A slot's kept source has a format, and every reader of a kept source serves it or refuses it: idc_fullres_rgb serves a grey source
+ *      (8-bit out; every source / interp / l_mode it serves for RGB) and so does idc_fullres_ab; idc_reveal_hints and idc_dist_score answer
+ *      IDC_ERR_UNSUPPORTED: a grey source has no colour to reveal or to score against.
+ *      idc_fullres_rgb16 = idc_fullres_rgb(..., IDC_L_IMAGE) with rgb [src_h,src_w,3] uint16.  IDC_ERR_UNSUPPORTED unless the slot holds a
+ *      kept 16-bit grey source; IDC_ERR_INVALID_ARG for a NULL or odd rgb; the codes of idc_fullres_rgb otherwise.
+ *      The pipelined form is idc_forward_async_gray, below.  Left out: RGB sources with 16-bit output, a mix of formats within one call,
+ *      float sources, ICC profiles and gamma other than sRGB, evaluation and scoring on grey sources. */
+int idc_set_image_gray(idc_handle h, int img, int n, int src_h, int src_w, int bits, const void* pix, float l_cent,
+                       unsigned flags /* IDC_INGEST_KEEP_SOURCE */, void* gray_net /*[n,H,W] uint8|uint16 or NULL*/,
+                       double* l_net /*[n,H,W] or NULL*/);
+int idc_fullres_rgb16(idc_handle h, int img, int source, int interp, uint16_t* rgb);   /* kept GRAY16 source, IDC_L_IMAGE */
+
 /* ---- pipelined batches from uint8 images: the serving form of the two calls above on the two slots of idc_forward_async.
  *      rgb_in [n,src_h,src_w,3] uint8 and per-image hint lists in, colourised uint8 images out; idc_wait completes the call and
  *      idc_pipeline_times reports its stages (H2D: the images, the offsets and the hints; compute: the prologue kernel, the
@@ -655,6 +689,28 @@ typedef struct idc_dist_taps {
 int idc_forward_async_dist(idc_handle h, int slot, int n, const idc_ref_image* images, const int32_t* hint_offsets, const idc_hint* hints,
                            int mode, float mask_value, float maskcent, float l_cent, unsigned flags, const idc_batch_refs* refs,
                            uint8_t* const* rgb_out, float* out_ab, uint64_t* sse, float* hint_colours, const idc_dist_taps* taps);
+
+/* ---- pipelined batches of greyscale planes: idc_forward_async_images for the sources of idc_set_image_gray (the rule stands there), one
+ *      format per call.  images [n]: host planes [h,w] of uint8 (bits 8) or uint16 (bits 16) of INDIVIDUAL sizes; on the device they lie
+ *      packed back to back as they came, one or two bytes per pixel.  Image i follows idc_set_image_gray + idc_set_hints +
+ *      idc_forward_resident + idc_fullres_rgb / idc_fullres_rgb16 of the blocking route bit for bit:
+ *        rgb_out[i] [H,W,3] uint8                      the net-size result (flags 0)
+ *        rgb_out[i] [images[i].h, images[i].w, 3] uint8   IDC_BATCH_OUT_SOURCE: L of the source samples, ab by the handle's batch upsample
+ *        ... the same as uint16, native order          IDC_BATCH_OUT_SOURCE | IDC_BATCH_OUT_RGB16 (bits 16 only): six bytes a pixel out
+ *      out_ab as idc_forward_async_images.  taps != NULL: idc_forward_async_dist without its sse and hint_colours -- peaks, and suggestions
+ *      at queries or at the peaks, for a folder of black-and-white photographs (rgb_out may then be NULL: nothing is colourised for the
+ *      caller).  Same two slots, idc_wait and idc_pipeline_times; pinned and pageable buffers are told apart per pointer, staged neighbours
+ *      travel as one copy.  Everything is decided before anything is enqueued, and a refused call leaves the slot usable.
+ *      Status: the codes of idc_forward_async_images (of idc_forward_async_dist with taps) for the shared arguments, and
+ *      IDC_ERR_INVALID_ARG for bits not 8 or 16, mode == IDC_HINT_REVEAL, IDC_BATCH_OUT_RGB16 with bits == 8 or without
+ *      IDC_BATCH_OUT_SOURCE, an odd pix or rgb_out[i] where the samples are 16-bit, unknown flag bits.  IDC_BATCH_MAX_SOURCE_BYTES bounds
+ *      the packed sources and the packed results alike. */
+typedef struct idc_gray_image { const void* pix; int32_t h, w; } idc_gray_image;   /* host, [h,w] uint8 or uint16 */
+enum { IDC_BATCH_OUT_RGB16 = 2 };          /* joins IDC_BATCH_OUT_SOURCE; idc_forward_async_gray only, bits == 16 only */
+int idc_forward_async_gray(idc_handle h, int slot, int n, int bits, const idc_gray_image* images,
+                           const int32_t* hint_offsets, const idc_hint* hints, int mode, float mask_value, float maskcent,
+                           float l_cent, unsigned flags, const idc_batch_refs* refs, void* const* rgb_out, float* out_ab,
+                           const idc_dist_taps* taps /* NULL: no distribution head */);
 
 /* ---- distribution scores: how much probability did the head put on the colour the pixel really has?  The question the distribution heads
  *      were trained on: the reference's training layers encode the ground-truth ab into the colour bins with NNEncode

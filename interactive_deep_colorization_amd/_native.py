@@ -39,6 +39,7 @@ EXPORTED_SYMBOLS = [
     "idc_dist_score", "idc_forward_async_dist_score",
     "idc_gamut_map", "idc_snap_colors",
     "idc_set_joint_upsample", "idc_fullres_ab", "idc_set_batch_upsample",
+    "idc_set_image_gray", "idc_fullres_rgb16", "idc_forward_async_gray",
     "idc_set_range_audit", "idc_range_reset", "idc_range_report", "idc_pack_weights_ex", "idc_load_weights_ex",
 ]
 IDC_STORE_NONE, IDC_STORE_F32, IDC_STORE_BF16, IDC_STORE_F16 = 0, 1, 2, 3
@@ -48,6 +49,7 @@ IDC_SRC_OUTPUT_AB, IDC_SRC_OUTPUT_AB_RAW, IDC_SRC_INPUT_AB, IDC_SRC_NO_AB = 0, 1
 IDC_INGEST_KEEP_SOURCE = 1
 IDC_L_IMAGE, IDC_L_MASK50 = 0, 1
 IDC_BATCH_OUT_SOURCE = 1
+IDC_BATCH_OUT_RGB16 = 2         # idc_forward_async_gray only, 16-bit samples only
 IDC_BATCH_MAX_SOURCE_BYTES, IDC_BATCH_MAX_HINTS = 1 << 30, 1 << 20
 IDC_REF_SATURATION, IDC_REF_MAX = 1, 4096
 IDC_GAMUT_MAX_MAPS, IDC_GAMUT_MAX_SIZE, IDC_SNAP_MAX_COLORS = 64, 512, 65536
@@ -80,6 +82,11 @@ class Hint(ctypes.Structure):
 class RefImage(ctypes.Structure):
     """idc_ref_image: one host reference photograph, [h,w,3] uint8."""
     _fields_ = [("rgb", ctypes.c_void_p), ("h", ctypes.c_int32), ("w", ctypes.c_int32)]
+
+
+class GrayImage(ctypes.Structure):
+    """idc_gray_image: one host greyscale plane, [h,w] uint8 or uint16."""
+    _fields_ = [("pix", ctypes.c_void_p), ("h", ctypes.c_int32), ("w", ctypes.c_int32)]
 
 
 class BatchRefs(ctypes.Structure):
@@ -237,6 +244,10 @@ def load():
     proto("idc_snap_colors", ci, [vp, ci, vp, vp, vp, vp, vp])
     proto("idc_set_joint_upsample", ci, [vp, ci, ctypes.c_double, ctypes.c_double])
     proto("idc_fullres_ab", ci, [vp, ci, ci, ci, vp])
+    proto("idc_set_image_gray", ci, [vp, ci, ci, ci, ci, ci, vp, cf, ctypes.c_uint, vp, vp])
+    proto("idc_fullres_rgb16", ci, [vp, ci, ci, ci, vp])
+    proto("idc_forward_async_gray", ci, [vp, ci, ci, ci, ctypes.POINTER(GrayImage), vp, vp, ci, cf, cf, cf, ctypes.c_uint,
+                                         ctypes.POINTER(BatchRefs), ctypes.POINTER(vp), vp, ctypes.POINTER(DistTaps)])
     proto("idc_set_batch_upsample", ci, [vp, ci])
     proto("idc_set_range_audit", ci, [vp, ci])
     proto("idc_range_reset", ci, [vp])

@@ -246,6 +246,7 @@ class ColorizeImageBase(object):
         self._ingest_net(rgb_net, colorspace.rgb2lab(rgb_net).transpose((2, 0, 1)))
         self._l_resident = False
         self._src_resident = False
+        self._src_gray_bits = 0
 
     def _ingest_net(self, rgb_net, lab_net):
         """The net-size attributes from the Xd x Xd image and its (3,Xd,Xd) float64 Lab."""
@@ -268,7 +269,11 @@ class ColorizeImageBase(object):
     def _refresh_fullres_lab(self):
         if self._fullres_lab_pending:
             self._fullres_lab_pending = False
-            self.img_lab_fullres = colorspace.rgb2lab(self.img_rgb_fullres).transpose((2, 0, 1))
+            src = self.img_rgb_fullres
+            if self.__dict__.get('_src_gray_bits'):        # a single-channel source: its own samples, not the 8-bit view
+                g = self.img_gray_fullres
+                src = np.repeat((g.astype(np.float64) / (255.0 if g.dtype == np.uint8 else 65535.0))[..., None], 3, 2)
+            self.img_lab_fullres = colorspace.rgb2lab(src).transpose((2, 0, 1))
             self.img_l_fullres = self.img_lab_fullres[[0]]
             self.img_ab_fullres = self.img_lab_fullres[1:]
 
@@ -290,19 +295,58 @@ class ColorizeImageBase(object):
         self._ingest_net(rgb_net[0], lab_net[0])
         self._l_resident = True               # the call left L - l_mean in slot 0: the next click uploads nothing
         self._src_resident = True
+        self._src_gray_bits = 0
+        self._l_serial = getattr(self.net, 'l_serial', None)
+
+    def _ingest_device_gray(self, gray):
+        """``_ingest_device`` for a single-channel image, (h,w) uint8 or uint16 (``HipColorizer.set_image_gray``): the plane goes to the
+        device as it is -- one or two bytes a pixel, nothing replicated, no bit of a 16-bit scan dropped -- and stays there for the
+        full-resolution getters; ``get_img_fullres(depth=16)`` then carries all 16 bits of lightness into the result.  ``img_gray_fullres``
+        keeps the plane; the uint8 attributes of the other routes (``img_rgb_fullres``, ``img_rgb``) hold its 8-bit view on three channels, and
+        the Lab attributes come from the samples themselves."""
+        if not self.net_set or not hasattr(self.net, 'set_image_gray'):
+            raise RuntimeError('load_image_device / set_image_device need prep_net first, and an engine with set_image_gray')
+        if self.l_norm != 1:
+            raise ValueError('device-side ingestion assumes a raw L input (l_norm 1)')
+        gray = np.ascontiguousarray(gray)
+        if gray.ndim != 2 or gray.dtype not in (np.uint8, np.uint16):
+            raise ValueError('a single-channel image is (h,w) uint8 or uint16, got %s %s' % (gray.dtype, gray.shape))
+        if max(gray.shape) > self.Xfullres_max:
+            raise ValueError('a single-channel image beyond Xfullres_max (%d) has no host route: resize it first' % self.Xfullres_max)
+        gray_net, l_net = self.net.set_image_gray(gray, img=0, l_cent=self.l_mean, keep_source=True)
+        full = 255.0 if gray.dtype == np.uint8 else 65535.0
+
+        def view8(g):
+            g8 = g if g.dtype == np.uint8 else ((g.astype(np.uint32) * 255 + 32767) // 65535).astype(np.uint8)
+            return np.repeat(g8[..., None], 3, 2)
+
+        self.img_gray_fullres = gray
+        self.img_rgb_fullres = view8(gray)
+        self._fullres_lab_pending = True
+        lab_net = colorspace.rgb2lab(np.repeat((gray_net[0].astype(np.float64) / full)[..., None], 3, 2)).transpose((2, 0, 1))
+        lab_net[0] = l_net[0]                 # the device's own L, whose float32 image is the resident plane
+        self._ingest_net(view8(np.asarray(gray_net[0])), lab_net)
+        self._l_resident = True
+        self._src_resident = True
+        self._src_gray_bits = 8 * gray.dtype.itemsize
         self._l_serial = getattr(self.net, 'l_serial', None)
 
     def load_image_device(self, input_path):
         """``load_image`` with the resize, both colour conversions and the L upload on the device (not in the reference).  Same
         attributes; the full-resolution Lab ones are computed on the host only when read."""
-        full = colorspace.imread_rgb(input_path)
-        if max(full.shape[0], full.shape[1]) > self.Xfullres_max:
+        full = colorspace.imread_gray_or_rgb(input_path)     # a single-channel file (PIL modes L, I;16) stays single-channel
+        if full.ndim == 2:
+            self._ingest_device_gray(full)
+        elif max(full.shape[0], full.shape[1]) > self.Xfullres_max:
             self._ingest(full.copy(), colorspace.resize_bilinear_u8(full, self.Xd, self.Xd))
         else:
             self._ingest_device(full)
 
     def set_image_device(self, input_image):
-        """``set_image`` on the device: an Xd x Xd RGB uint8 array, used as it is."""
+        """``set_image`` on the device: an Xd x Xd RGB uint8 array, used as it is; or a single-channel (h,w) uint8 / uint16 array of any
+        size (``_ingest_device_gray``)."""
+        if np.ndim(input_image) == 2:
+            return self._ingest_device_gray(np.asarray(input_image))
         image = np.ascontiguousarray(input_image, dtype=np.uint8)
         if max(image.shape[0], image.shape[1]) > self.Xfullres_max:
             self._ingest(image.copy(), image)
@@ -455,6 +499,8 @@ class ColorizeImageBase(object):
             raise RuntimeError('I need to have an image!')
         if not self._source_on_device():
             raise RuntimeError('load_image_device / set_image_device need prep_net first, and an engine with set_image_rgb')
+        if self.__dict__.get('_src_gray_bits'):
+            raise RuntimeError('the image is single-channel: it has no colour to reveal')
         if self.ab_mean != 0 or self.ab_norm != 1:
             raise ValueError('device-side hints assume raw ab inputs (ab_mean 0, ab_norm 1)')
         self.revealed_hint_colors = self.net.reveal_hints(rects, img=0, mask_value=self.mask_mult)
@@ -586,9 +632,23 @@ class ColorizeImageBase(object):
         # been edited in place since the last forward (put_point does), and the reference would show those edits
         return self.net_set and self._hints_on_device and self.ab_mean == 0 and self.ab_norm == 1
 
-    def get_img_fullres(self):
+    def _fullres16(self, interp):
+        """The 16-bit full-resolution result (``HipColorizer.fullres_rgb(depth=16)``): device route only, from a kept uint16 plane."""
+        if self.__dict__.get('_src_gray_bits') != 16 or not (self._out_on_device() and self._source_on_device()):
+            raise RuntimeError('depth=16 needs a uint16 single-channel image set through load_image_device / set_image_device and the '
+                               'result of the last net_forward on the device')
+        out = self.net.fullres_rgb('output_ab', interp, 'image', img=0, depth=16)
+        self._l_serial = getattr(self.net, 'l_serial', None)      # (the call itself moved it)
+        return out
+
+    def get_img_fullres(self, depth=8):
         """Bilinear (``scipy.ndimage.zoom`` order 1) upsample of ``output_ab`` + Lab->RGB with the full-res L
-        (``:123-131``) -- on the device when the map is still the one the last forward left there."""
+        (``:123-131``) -- on the device when the map is still the one the last forward left there.  ``depth=16`` (not in the reference):
+        (h,w,3) uint16 from a uint16 single-channel source, the L of its own 16-bit samples; device route only."""
+        if depth == 16:
+            return self._fullres16('linear')
+        if depth != 8:
+            raise ValueError('depth must be 8 or 16')
         # (the Python-side token can outlive the engine's resident map -- a direct net.forward / forward_async on the
         #  engine, a want_rgb=False forward: the engine then answers IDC_ERR_UNSUPPORTED and the host path takes over)
         if self._out_on_device():
@@ -601,11 +661,15 @@ class ColorizeImageBase(object):
                 self._dev_out_valid = False
         return lab2rgb_transpose(self.img_l_fullres, self._up(self.output_ab, 1))
 
-    def get_img_fullres_joint(self):
+    def get_img_fullres_joint(self, depth=8):
         """``get_img_fullres`` with the edge-aware upsampling of ``output_ab`` (``HipColorizer.fullres_rgb(interp='joint')``: joint
         bilateral, guided by the full-resolution L; parameters: ``self.net.set_joint_upsample``).  Not in the reference.  Device route
         only: the image was set through ``load_image_device`` / ``set_image_device`` and the last forward's map is still on the device;
-        there is no host twin to fall back to, so anything else is an error."""
+        there is no host twin to fall back to, so anything else is an error.  ``depth=16``: as in ``get_img_fullres``."""
+        if depth == 16:
+            return self._fullres16('joint')
+        if depth != 8:
+            raise ValueError('depth must be 8 or 16')
         if not (self._out_on_device() and self._source_on_device()):
             raise RuntimeError('get_img_fullres_joint needs load_image_device / set_image_device and the result of the last net_forward '
                                'on the device')
@@ -777,6 +841,8 @@ class _DistMaps(object):
         need = 'score_dist needs the image set through load_image_device / set_image_device, and an engine with dist_score'
         if not hasattr(self.net, 'dist_score') or not (self.net_set and self._src_resident):
             raise RuntimeError(need)
+        if self.__dict__.get('_src_gray_bits'):
+            raise RuntimeError('the image is single-channel: it has no colour to score against')
         try:
             res = self.net.dist_score(self._bin_centres(), 1, nn=nn, sigma=sigma, ranks=ranks, want_maps=return_maps)
         except IdcError as ex:

@@ -87,3 +87,15 @@ def imread_rgb(path):
     from PIL import Image
     with Image.open(path) as im:
         return np.asarray(im.convert("RGB")).copy()
+
+
+def imread_gray_or_rgb(path):
+    """``imread_rgb`` that keeps a single-channel file single-channel: PIL modes L -> (H,W) uint8, I;16 (either byte order) -> (H,W)
+    uint16 in native order; every other mode -> (H,W,3) uint8 RGB."""
+    from PIL import Image
+    with Image.open(path) as im:
+        if im.mode == "L":
+            return np.asarray(im).copy()
+        if im.mode.startswith("I;16"):
+            return np.asarray(im).astype(np.uint16)
+        return np.asarray(im.convert("RGB")).copy()

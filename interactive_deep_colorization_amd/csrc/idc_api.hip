@@ -100,7 +100,7 @@ void drop_source(idc_context* h, int slot) {
     if (slot < 0 || slot >= (int)h->src.size()) return;
     auto& sl = h->src[slot];
     sl.d_rgb.reset();                                    // (freeing waits for the device: nothing that reads it is in flight after that)
-    sl.h = sl.w = 0;
+    sl.h = sl.w = 0; sl.gray_bits = 0;
 }
 
 // ---------------------------------------------------------------------------------------------- distribution taps
@@ -369,6 +369,7 @@ int idc_reveal_hints(idc_handle h, int img, int n_hints, const idc_hint* rects, 
     if (n_hints < 0 || (n_hints > 0 && !rects)) return fail(&h->err, IDC_ERR_INVALID_ARG, "bad hint list");
     const auto& src = h->src[img];
     if (!src.d_rgb.get()) return fail(&h->err, IDC_ERR_UNSUPPORTED, "image slot %d has no resident source (idc_set_image_rgb with IDC_INGEST_KEEP_SOURCE)", img);
+    if (src.gray_bits) return fail(&h->err, IDC_ERR_UNSUPPORTED, "image slot %d holds a greyscale source: it has no colour to reveal", img);
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream.get()));            // the pinned lists of the previous call may still be in flight
     const size_t cap = n_hints < 256 ? 256 : 2 * (size_t)n_hints;
@@ -633,6 +634,8 @@ int idc_dist_score(idc_handle h, int n, const idc_dist_score_spec* spec, const f
     for (int i = 0; i < n; ++i)
         if (!h->src[i].d_rgb.get())
             return fail(&h->err, IDC_ERR_UNSUPPORTED, "image slot %d has no resident source (idc_set_image_rgb with IDC_INGEST_KEEP_SOURCE)", i);
+    for (int i = 0; i < n; ++i)
+        if (h->src[i].gray_bits) return fail(&h->err, IDC_ERR_UNSUPPORTED, "image slot %d holds a greyscale source: it has no colour to score against", i);
     HIPCHK(h, hipSetDevice(h->device));
     rc = drain_pipeline(h);
     if (rc) return rc;
@@ -857,8 +860,62 @@ int idc_set_image_rgb(idc_handle h, int img, int n, int src_h, int src_w, const 
     return IDC_OK;
 }
 
-// idc_fullres_rgb (rgb) and idc_fullres_ab (ab): one list of checks, one residency rule
-static int fullres(idc_handle h, int img, int source, int interp, int l_mode, uint8_t* rgb, double* ab, bool want_ab) {
+// idc_set_image_rgb for n planes [src_h,src_w] of uint8 (bits 8) or uint16 (bits 16): the same steps with the sample as the unit.  The net-size
+// plane and its L leave through the buffers of idc_set_image_rgb's results, which are large enough for either width.
+int idc_set_image_gray(idc_handle h, int img, int n, int src_h, int src_w, int bits, const void* pix, float l_cent, unsigned flags, void* gray_net,
+                       double* l_net) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (bits != 8 && bits != 16) return fail(&h->err, IDC_ERR_INVALID_ARG, "bits %d is neither 8 nor 16", bits);
+    if (!pix) return fail(&h->err, IDC_ERR_INVALID_ARG, "null pix");
+    if (bits == 16 && (((uintptr_t)pix | (uintptr_t)gray_net) & 1)) return fail(&h->err, IDC_ERR_INVALID_ARG, "16-bit samples at an odd address");
+    if (flags & ~(unsigned)IDC_INGEST_KEEP_SOURCE) return fail(&h->err, IDC_ERR_INVALID_ARG, "unknown flag bits 0x%x", flags);
+    if (src_h < 1 || src_h > 16384 || src_w < 1 || src_w > 16384)
+        return fail(&h->err, IDC_ERR_INVALID_ARG, "source size %dx%d outside 1..16384", src_h, src_w);
+    if (n < 1 || img < 0 || img >= h->max_batch || n > h->max_batch - img)
+        return fail(&h->err, IDC_ERR_BATCH, "image slots %d..%d outside 0..%d", img, img + n - 1, h->max_batch - 1);
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = drain_pipeline(h);
+    if (rc) return rc;
+    rc = ensure_ingest_buffers(h);
+    if (rc) return rc;
+    const size_t hw = (size_t)h->H * h->W, sz = (size_t)bits / 8, sb = (size_t)src_h * src_w * sz;
+    const bool keep = (flags & IDC_INGEST_KEEP_SOURCE) != 0;
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));            // the pointer table and the upload buffer of the previous call may still be read
+    for (int i = 0; i < n; ++i) drop_source(h, img + i);
+    if (keep) {
+        for (int i = 0; i < n; ++i) {
+            auto& sl = h->src[img + i];
+            HIPCHK(h, sl.d_rgb.ensure(sb));
+            sl.h = src_h; sl.w = src_w; sl.l_cent = l_cent; sl.gray_bits = bits;
+            h->h_src_ptrs.get()[i] = sl.d_rgb.get();
+        }
+    } else {
+        HIPCHK(h, h->d_ingest.ensure((size_t)n * ((sb + 3) & ~(size_t)3)));
+        for (int i = 0; i < n; ++i) h->h_src_ptrs.get()[i] = h->d_ingest.get() + (size_t)i * ((sb + 3) & ~(size_t)3);     // a uint16 plane starts even
+    }
+    const unsigned char* in = (const unsigned char*)pix;
+    const bool in_pinned = is_pinned(pix);
+    for (int i = 0; i < n; ++i) {
+        void* dst = (void*)h->h_src_ptrs.get()[i];
+        if (in_pinned) HIPCHK(h, hipMemcpyAsync(dst, in + (size_t)i * sb, sb, hipMemcpyHostToDevice, h->stream.get()));
+        else HIPCHK(h, hipMemcpy(dst, in + (size_t)i * sb, sb, hipMemcpyHostToDevice));
+    }
+    HIPCHK(h, hipMemcpyAsync((void*)h->d_src_ptrs.get(), (const void*)h->h_src_ptrs.get(), (size_t)n * sizeof(void*), hipMemcpyHostToDevice, h->stream.get()));
+    HIPCHK(h, launch_ingest_gray((const void* const*)h->d_src_ptrs.get(), bits, n, src_h, src_w, h->H, h->W, l_cent, h->d_L.get() + (size_t)img * hw,
+                                 gray_net ? h->d_net_rgb.get() : nullptr, l_net ? h->d_net_lab.get() : nullptr, h->stream.get()));
+    const bool net_direct = gray_net && is_pinned(gray_net), l_direct = l_net && is_pinned(l_net);
+    if (net_direct) HIPCHK(h, hipMemcpyAsync(gray_net, h->d_net_rgb.get(), (size_t)n * hw * sz, hipMemcpyDeviceToHost, h->stream.get()));
+    if (l_direct) HIPCHK(h, hipMemcpyAsync(l_net, h->d_net_lab.get(), (size_t)n * hw * 8, hipMemcpyDeviceToHost, h->stream.get()));
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+    if (gray_net && !net_direct) HIPCHK(h, hipMemcpy(gray_net, h->d_net_rgb.get(), (size_t)n * hw * sz, hipMemcpyDeviceToHost));
+    if (l_net && !l_direct) HIPCHK(h, hipMemcpy(l_net, h->d_net_lab.get(), (size_t)n * hw * 8, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; ++i) h->l_set[img + i] = 1;
+    return IDC_OK;
+}
+
+// idc_fullres_rgb / idc_fullres_rgb16 (rgb; out_bits 8 | 16) and idc_fullres_ab (ab): one list of checks, one residency rule.  A kept greyscale
+// source (SlotSource::gray_bits) is served by the grey kernels.
+static int fullres(idc_handle h, int img, int source, int interp, int l_mode, void* rgb, int out_bits, double* ab, bool want_ab) {
     int rc = check_img(h, img);
     if (rc) return rc;
     if (interp < 0 || interp > IDC_INTERP_JOINT) return fail(&h->err, IDC_ERR_INVALID_ARG, "interp %d not in 0..3", interp);
@@ -886,14 +943,20 @@ static int fullres(idc_handle h, int img, int source, int interp, int l_mode, ui
             HIPCHK(h, h->d_full_ab.ensure(nbytes));
         }
         if (!direct) HIPCHK(h, h->h_full_ab.ensure(h->d_full_ab.bytes()));
-        HIPCHK(h, launch_joint_fullres(sl.d_rgb.get(), nullptr, 1, sl.h, sl.w, joint_tiles(sl.h, sl.w), pa, pb, f64, 0, h->d_L.get() + (size_t)img * hw,
-                                       sl.l_cent, h->H, h->W, interp, h->joint, nullptr, h->d_full_ab.get(), h->stream.get()));
+        if (sl.gray_bits)
+            HIPCHK(h, launch_gray_joint_fullres(sl.d_rgb.get(), sl.gray_bits, nullptr, 1, sl.h, sl.w, joint_tiles(sl.h, sl.w), pa, pb, f64, 0,
+                                                h->d_L.get() + (size_t)img * hw, sl.l_cent, h->H, h->W, interp, h->joint, nullptr, 8, h->d_full_ab.get(),
+                                                h->stream.get()));
+        else
+            HIPCHK(h, launch_joint_fullres(sl.d_rgb.get(), nullptr, 1, sl.h, sl.w, joint_tiles(sl.h, sl.w), pa, pb, f64, 0,
+                                           h->d_L.get() + (size_t)img * hw, sl.l_cent, h->H, h->W, interp, h->joint, nullptr, h->d_full_ab.get(),
+                                           h->stream.get()));
         HIPCHK(h, hipMemcpyAsync(direct ? ab : h->h_full_ab.get(), h->d_full_ab.get(), nbytes, hipMemcpyDeviceToHost, h->stream.get()));
         HIPCHK(h, hipStreamSynchronize(h->stream.get()));
         if (!direct) memcpy(ab, h->h_full_ab.get(), nbytes);
         return IDC_OK;
     }
-    const size_t nbytes = (size_t)sl.h * sl.w * 3;
+    const size_t nbytes = (size_t)sl.h * sl.w * 3 * (size_t)(out_bits / 8);
     const bool direct = is_pinned(rgb);                    // a pinned result buffer is written in place; a pageable one through pinned staging
     if (h->d_full_rgb.bytes() < nbytes) {
         HIPCHK(h, hipStreamSynchronize(h->stream.get()));
@@ -901,7 +964,14 @@ static int fullres(idc_handle h, int img, int source, int interp, int l_mode, ui
     }
     if (!direct) HIPCHK(h, h->h_full_rgb.ensure(h->d_full_rgb.bytes()));
     const float* mask = l_mode == IDC_L_MASK50 ? h->d_mask.get() + (size_t)img * hw : nullptr;
-    if (interp == IDC_INTERP_JOINT && pa)
+    if (sl.gray_bits && interp == IDC_INTERP_JOINT && pa)
+        HIPCHK(h, launch_gray_joint_fullres(sl.d_rgb.get(), sl.gray_bits, nullptr, 1, sl.h, sl.w, joint_tiles(sl.h, sl.w), pa, pb, f64, 0,
+                                            h->d_L.get() + (size_t)img * hw, sl.l_cent, h->H, h->W, interp, h->joint, h->d_full_rgb.get(), out_bits, nullptr,
+                                            h->stream.get()));
+    else if (sl.gray_bits)
+        HIPCHK(h, launch_gray_fullres(sl.d_rgb.get(), sl.gray_bits, sl.h, sl.w, pa, pb, f64, h->H, h->W, interp == IDC_INTERP_JOINT ? IDC_INTERP_LINEAR : interp,
+                                      mask, h->hint_mask_value[img], h->d_full_rgb.get(), out_bits, h->stream.get()));
+    else if (interp == IDC_INTERP_JOINT && pa)
         HIPCHK(h, launch_joint_fullres(sl.d_rgb.get(), nullptr, 1, sl.h, sl.w, joint_tiles(sl.h, sl.w), pa, pb, f64, 0, h->d_L.get() + (size_t)img * hw,
                                        sl.l_cent, h->H, h->W, interp, h->joint, h->d_full_rgb.get(), nullptr, h->stream.get()));
     else        // (IDC_SRC_NO_AB has nothing to interpolate: a = b = 0 whatever the interp)
@@ -914,11 +984,20 @@ static int fullres(idc_handle h, int img, int source, int interp, int l_mode, ui
 }
 
 int idc_fullres_rgb(idc_handle h, int img, int source, int interp, int l_mode, uint8_t* rgb) {
-    return fullres(h, img, source, interp, l_mode, rgb, nullptr, false);
+    return fullres(h, img, source, interp, l_mode, rgb, 8, nullptr, false);
+}
+
+int idc_fullres_rgb16(idc_handle h, int img, int source, int interp, uint16_t* rgb) {
+    int rc = check_img(h, img);
+    if (rc) return rc;
+    if (!h->src[img].d_rgb.get() || h->src[img].gray_bits != 16)
+        return fail(&h->err, IDC_ERR_UNSUPPORTED, "image slot %d has no resident 16-bit greyscale source (idc_set_image_gray with bits 16 and IDC_INGEST_KEEP_SOURCE)", img);
+    if (!rgb || ((uintptr_t)rgb & 1)) return fail(&h->err, IDC_ERR_INVALID_ARG, rgb ? "rgb at an odd address" : "null rgb");
+    return fullres(h, img, source, interp, IDC_L_IMAGE, rgb, 16, nullptr, false);
 }
 
 int idc_fullres_ab(idc_handle h, int img, int source, int interp, double* ab) {
-    return fullres(h, img, source, interp, IDC_L_IMAGE, nullptr, ab, true);
+    return fullres(h, img, source, interp, IDC_L_IMAGE, nullptr, 8, ab, true);
 }
 
 int idc_set_joint_upsample(idc_handle h, int radius, double sigma_s, double sigma_r) {

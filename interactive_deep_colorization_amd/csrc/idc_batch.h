@@ -46,7 +46,16 @@ struct BatchCall {
     bool eval = false; uint64_t* sse = nullptr; float* hint_colours = nullptr;
     bool taps_call = false; const idc_dist_taps* taps = nullptr;
     bool score_call = false; const idc_dist_score_spec* spec = nullptr; const float* centres = nullptr; const idc_dist_score_out* sout = nullptr;
+    // the sample width and the output depth (idc_forward_async_gray; ragged only): gray_bits 0 = [h,w,3] uint8 RGB in `images`, 8 | 16 = one
+    // plane [h,w] of uint8 | uint16 in `grays`; out_bits 8 | 16 = [.,.,3] uint8 | uint16 out
+    int gray_bits = 0, out_bits = 8; const idc_gray_image* grays = nullptr;
 };
+
+// image i of a ragged call, whichever table it came in (a plane's samples stand in the place of the bytes)
+inline idc_ref_image batch_image(const BatchCall& c, int i) {
+    if (c.gray_bits == 0) return c.images[i];
+    return {(const uint8_t*)c.grays[i].pix, c.grays[i].h, c.grays[i].w};
+}
 
 inline void set_batch_refs(BatchCall& c, const idc_batch_refs* r) {
     c.has_refs = r != nullptr;
@@ -66,6 +75,7 @@ struct BatchPlan {
     size_t table_at = 0, hints_at = 0, orig_at = 0, meta_bytes = 0, meta_floor = 0;
     size_t cols_at = 0, cols_bytes = 0;  // the evaluation block: sse uint64[max_batch][3] at 0, then hint_colours float[n_hints][2]
     long long max_tiles = 0, max_pixels = 0;     // joint_tiles / pixels of the largest source
+    int bpp_in = 3, bpp_out = 3;         // bytes per pixel of the packed sources (1, 2 or 3) and of the packed source-size results (3 or 6)
     std::vector<Piece> pieces;           // in_pinned / out_pinned: the caller's to fill in (a runtime query); out_pinned without want_rgb: true
     bool ab_pinned = false;              // ... and so is this one, of out_ab
 };
@@ -91,27 +101,41 @@ inline int plan_batch(const BatchCall& c, int H, int W, int max_batch, BatchPlan
     p->reveal = c.eval && c.mode == IDC_HINT_REVEAL;
     p->dist = c.eval && c.taps_call;
     p->score = p->dist && c.score_call;
+    const bool gray = c.gray_bits != 0;
     if (c.slot < 0 || c.slot > 1) return plan_fail(err, IDC_ERR_INVALID_ARG, "slot %d not in 0..1", c.slot);
-    if (c.ragged ? (!c.images || !(c.outs || c.eval)) : (!c.rgb_in || !c.rgb_out)) return plan_fail(err, IDC_ERR_INVALID_ARG, "null image pointer");
-    if (c.flags & ~(unsigned)IDC_BATCH_OUT_SOURCE) return plan_fail(err, IDC_ERR_INVALID_ARG, "unknown flag bits 0x%x", c.flags);
+    if (gray && c.gray_bits != 8 && c.gray_bits != 16) return plan_fail(err, IDC_ERR_INVALID_ARG, "bits %d is neither 8 nor 16", c.gray_bits);
+    if (c.ragged ? (!(gray ? (const void*)c.grays : (const void*)c.images) || !(c.outs || c.eval)) : (!c.rgb_in || !c.rgb_out))
+        return plan_fail(err, IDC_ERR_INVALID_ARG, "null image pointer");
+    if (c.flags & ~(unsigned)(IDC_BATCH_OUT_SOURCE | (gray ? IDC_BATCH_OUT_RGB16 : 0))) return plan_fail(err, IDC_ERR_INVALID_ARG, "unknown flag bits 0x%x", c.flags);
+    if (gray && c.mode == IDC_HINT_REVEAL) return plan_fail(err, IDC_ERR_INVALID_ARG, "IDC_HINT_REVEAL: a greyscale source has no colour to reveal");
+    if (c.out_bits == 16 && c.gray_bits != 16) return plan_fail(err, IDC_ERR_INVALID_ARG, "IDC_BATCH_OUT_RGB16 needs 16-bit samples, not %d-bit ones", c.gray_bits);
+    if (c.out_bits == 16 && !(c.flags & IDC_BATCH_OUT_SOURCE)) return plan_fail(err, IDC_ERR_INVALID_ARG, "IDC_BATCH_OUT_RGB16 without IDC_BATCH_OUT_SOURCE: the net-size result is 8-bit");
+    p->bpp_in = gray ? c.gray_bits / 8 : 3;
+    p->bpp_out = c.out_bits == 16 ? 6 : 3;
+    size_t full_bytes = 0;               // the packed source-size results
     if (c.mode != IDC_HINT_AB && c.mode != IDC_HINT_RGB && !p->reveal) return plan_fail(err, IDC_ERR_INVALID_ARG, "hint mode %d", c.mode);
     if (c.eval && !c.sse && !p->dist) return plan_fail(err, IDC_ERR_INVALID_ARG, "null sse");
     if (c.eval && c.hint_colours && !p->reveal)
         return plan_fail(err, IDC_ERR_INVALID_ARG, "hint_colours with hint mode %d: only IDC_HINT_REVEAL reveals colours", c.mode);
     if (c.ragged) {
         for (int i = 0; i < n; ++i) {
-            const idc_ref_image& im = c.images[i];
+            const idc_ref_image im = batch_image(c, i);
             if (!im.rgb || (p->want_rgb && !c.outs[i])) return plan_fail(err, IDC_ERR_INVALID_ARG, "image %d: null image pointer", i);
+            if (c.gray_bits == 16 && ((uintptr_t)im.rgb & 1)) return plan_fail(err, IDC_ERR_INVALID_ARG, "image %d: 16-bit samples at an odd address", i);
+            if (c.out_bits == 16 && p->want_rgb && ((uintptr_t)c.outs[i] & 1)) return plan_fail(err, IDC_ERR_INVALID_ARG, "image %d: 16-bit result at an odd address", i);
             if (im.h < 1 || im.h > 16384 || im.w < 1 || im.w > 16384)
                 return plan_fail(err, IDC_ERR_INVALID_ARG, "image %d: source size %dx%d outside 1..16384", i, im.h, im.w);
-            p->in_bytes += (size_t)im.h * im.w * 3;               // n * 0.8 GB: no overflow in 64 bits
+            p->in_bytes += (size_t)im.h * im.w * p->bpp_in;       // n * 0.8 GB: no overflow in 64 bits
+            full_bytes += (size_t)im.h * im.w * p->bpp_out;
         }
         if (p->in_bytes > IDC_BATCH_MAX_SOURCE_BYTES)
             return plan_fail(err, IDC_ERR_INVALID_ARG, "%d sources hold %zu bytes, more than %zu", n, p->in_bytes, (size_t)IDC_BATCH_MAX_SOURCE_BYTES);
+        if ((c.flags & IDC_BATCH_OUT_SOURCE) && full_bytes > IDC_BATCH_MAX_SOURCE_BYTES)
+            return plan_fail(err, IDC_ERR_INVALID_ARG, "%d source-size results hold %zu bytes, more than %zu", n, full_bytes, (size_t)IDC_BATCH_MAX_SOURCE_BYTES);
     } else {
         if (c.src_h < 1 || c.src_h > 16384 || c.src_w < 1 || c.src_w > 16384)
             return plan_fail(err, IDC_ERR_INVALID_ARG, "source size %dx%d outside 1..16384", c.src_h, c.src_w);
-        p->in_bytes = (size_t)n * c.src_h * c.src_w * 3;
+        p->in_bytes = full_bytes = (size_t)n * c.src_h * c.src_w * 3;
         if (p->in_bytes > IDC_BATCH_MAX_SOURCE_BYTES)
             return plan_fail(err, IDC_ERR_INVALID_ARG, "%d sources of %dx%d are more than %zu bytes", n, c.src_h, c.src_w, (size_t)IDC_BATCH_MAX_SOURCE_BYTES);
     }
@@ -132,7 +156,7 @@ inline int plan_batch(const BatchCall& c, int H, int W, int max_batch, BatchPlan
     }
     const size_t hw = (size_t)H * W, nb = (size_t)max_batch;
     p->source_out = (c.flags & IDC_BATCH_OUT_SOURCE) != 0;
-    p->rgb_bytes = p->source_out ? p->in_bytes : (size_t)n * hw * 3;
+    p->rgb_bytes = p->source_out ? full_bytes : (size_t)n * hw * 3;
     p->table_at = batch_align16((nb + 1) * sizeof(int));
     p->hints_at = c.ragged ? p->table_at + batch_align16((nb + 1) * sizeof(ImgDesc)) : p->table_at;
     p->orig_at = p->hints_at + (size_t)p->kept * sizeof(HintRect);
@@ -143,10 +167,10 @@ inline int plan_batch(const BatchCall& c, int H, int W, int max_batch, BatchPlan
     if (c.ragged) {
         size_t at = 0;
         for (int i = 0; i < n; ++i) {
-            const idc_ref_image& im = c.images[i];
-            const size_t sb = (size_t)im.h * im.w * 3;
-            p->pieces.push_back({im.rgb, p->want_rgb ? c.outs[i] : nullptr, at, sb, p->source_out ? at : (size_t)i * hw * 3,
-                                 p->source_out ? sb : hw * 3, false, false});
+            const idc_ref_image im = batch_image(c, i);
+            const size_t px = (size_t)im.h * im.w, sb = px * p->bpp_in, first = at / p->bpp_in;
+            p->pieces.push_back({im.rgb, p->want_rgb ? c.outs[i] : nullptr, at, sb, p->source_out ? first * p->bpp_out : (size_t)i * hw * 3,
+                                 p->source_out ? px * p->bpp_out : hw * 3, false, false});
             p->max_tiles = p->max_tiles > joint_tiles(im.h, im.w) ? p->max_tiles : joint_tiles(im.h, im.w);
             p->max_pixels = p->max_pixels > (long long)im.h * im.w ? p->max_pixels : (long long)im.h * im.w;
             at += sb;
@@ -169,8 +193,8 @@ inline void fill_batch_meta(const BatchCall& c, const BatchPlan& p, int H, int W
         ImgDesc* tab = (ImgDesc*)(h_meta + p.table_at);
         for (int i = 0; i <= c.n; ++i) {           // entry n closes the run: where the next image would begin
             const size_t at = i < c.n ? p.pieces[i].in_at : p.in_bytes;
-            tab[i].off = (long long)at; tab[i].first = (long long)(at / 3);
-            tab[i].h = i < c.n ? c.images[i].h : 0; tab[i].w = i < c.n ? c.images[i].w : 0;
+            tab[i].off = (long long)at; tab[i].first = (long long)(at / p.bpp_in);
+            tab[i].h = i < c.n ? batch_image(c, i).h : 0; tab[i].w = i < c.n ? batch_image(c, i).w : 0;
         }
     }
     m_offs[0] = 0;

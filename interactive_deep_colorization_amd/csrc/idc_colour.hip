@@ -867,6 +867,440 @@ hipError_t launch_joint_fullres(const unsigned char* src, const ImgDesc* imgs, i
 }
 
 // ------------------------------------------------------------------------------------------------
+// greyscale sources (idc_set_image_gray, and idc_fullres_rgb / idc_fullres_ab / idc_fullres_rgb16 on a kept one; the rule: include/ideepcolor.h).
+// One plane [h,w] of uint8 or uint16 samples T whose sRGB value v / 255 or v / 65535 stands on all three channels; the image goes out as uint8 or
+// uint16 O.  The kernels sit beside the RGB ones and hand the SAME device functions the same operands: bilinear_taps and bilinear_u8's
+// expressions on the one channel, linear_to_lab on {t, t, t}, interp_ab / the joint rule, lab_to_srgb.  So a uint8 plane gives the bits of the
+// RGB route fed the plane three times, and a uint16 plane of 257 g gives the bits of the uint8 plane g wherever nothing is resized
+// (fl(257 g / 65535) == fl(g / 255): the correctly rounded quotient of the same real number).  There is no expanded RGB copy of the plane.
+//   sRGB -> linear   uint8: the 256-entry LDS table of the RGB kernels.  uint16: srgb_to_linear per sample -- one float64 pow beside the three
+//                    of lab_to_srgb on the way out and the cbrt of linear_to_lab; a 65 536-entry table in global memory would hold the same bits.
+//   grids            exact: every launcher covers its items in one pass and refuses a count past 2^31 - 1 (a 16384^2 source is 2.6e5 workgroups).
+// ------------------------------------------------------------------------------------------------
+template <typename T> struct GrayFmt;
+template <> struct GrayFmt<unsigned char> { static constexpr double full = 255.0; };
+template <> struct GrayFmt<unsigned short> { static constexpr double full = 65535.0; };
+
+// bilinear_u8 on T's lattice: the same expressions in the same order, contraction off -> floor(out + .5) clamped to 0..full scale
+template <typename T>
+__device__ __forceinline__ int bilinear_gray(double f00, double f01, double f10, double f11, double wx, double wy) {
+#pragma clang fp contract(off)
+    const double top = f00 * (1.0 - wx) + f01 * wx;
+    const double bot = f10 * (1.0 - wx) + f11 * wx;
+    const double out = top * (1.0 - wy) + bot * wy;
+    const double r = floor(out + 0.5);
+    return r < 0.0 ? 0 : (r > GrayFmt<T>::full ? (int)GrayFmt<T>::full : (int)r);
+}
+
+template <typename T>
+__device__ __forceinline__ void fill_gray_table(double* tab) {      // uniform over the kernel: only the uint8 forms have a table (and its barrier)
+    if constexpr (sizeof(T) == 1) fill_srgb_table(tab);
+}
+
+// L of sample q: linear_to_lab on {t, t, t}, t = srgb_to_linear(q / full scale)
+template <typename T>
+__device__ __forceinline__ double gray_L(int q, const double* tab) {
+    double t;
+    if constexpr (sizeof(T) == 1) t = tab[q]; else t = srgb_to_linear((double)q / GrayFmt<T>::full);
+    const double lin[3] = {t, t, t};
+    double L, a_, b_;
+    linear_to_lab(lin, L, a_, b_);
+    return L;
+}
+
+// lab_to_rgb_u8 for either depth: (O)(s * full scale), truncation
+template <typename O>
+__device__ __forceinline__ void lab_to_rgb_q(double L, double a, double b, O* q) {
+    double s[3];
+    lab_to_srgb(L, a, b, s);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) q[c] = (O)(s[c] * GrayFmt<O>::full);
+}
+
+// ingest_rgb_kernel for planes: one thread per net-size pixel of all n images, exact grid.  gray_net [n,H,W] T and l_net [n,H,W] f64 may be nullptr.
+template <typename T>
+__global__ __launch_bounds__(256) void ingest_gray_kernel(const T* const* __restrict__ srcs, long long npix, int src_h, int src_w, int H, int W,
+                                                          float l_cent, float* __restrict__ Lp, T* __restrict__ gray_net,
+                                                          double* __restrict__ l_net) {
+    __shared__ double tab[sizeof(T) == 1 ? 256 : 1];
+    fill_gray_table<T>(tab);
+    const long long HW = (long long)H * W, p = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= npix) return;
+    const long long i = p / HW, r = p - i * HW;
+    const int y = (int)(r / W), x = (int)(r - (long long)y * W);
+    int y0, y1, x0, x1;
+    double wy, wx;
+    bilinear_taps(y, src_h, H, y0, y1, wy);
+    bilinear_taps(x, src_w, W, x0, x1, wx);
+    const T* src = srcs[i];
+    const int q = bilinear_gray<T>((double)src[(long long)y0 * src_w + x0], (double)src[(long long)y0 * src_w + x1],
+                                   (double)src[(long long)y1 * src_w + x0], (double)src[(long long)y1 * src_w + x1], wx, wy);
+    const double L = gray_L<T>(q, tab);
+    Lp[p] = (float)(L - (double)l_cent);
+    if (gray_net != nullptr) gray_net[p] = (T)q;
+    if (l_net != nullptr) l_net[p] = L;
+}
+
+hipError_t launch_ingest_gray(const void* const* srcs, int bits, int n, int src_h, int src_w, int H, int W, float l_cent, float* Lp, void* gray_net,
+                              double* l_net, hipStream_t s) {
+    const long long npix = (long long)n * H * W, wgs = (npix + 255) / 256;
+    if (npix <= 0 || wgs > 0x7fffffffll || src_h <= 0 || src_w <= 0 || (bits != 8 && bits != 16)) return hipErrorInvalidValue;
+    if (bits == 8)
+        hipLaunchKernelGGL(ingest_gray_kernel<unsigned char>, dim3((unsigned)wgs), dim3(256), 0, s, (const unsigned char* const*)srcs, npix, src_h, src_w,
+                           H, W, l_cent, Lp, (unsigned char*)gray_net, l_net);
+    else
+        hipLaunchKernelGGL(ingest_gray_kernel<unsigned short>, dim3((unsigned)wgs), dim3(256), 0, s, (const unsigned short* const*)srcs, npix, src_h,
+                           src_w, H, W, l_cent, Lp, (unsigned short*)gray_net, l_net);
+    return hipGetLastError();
+}
+
+// fullres_pixel from a sample: L = gray_L(q) (mask == nullptr) or the mask rule, (a, b) interpolated from pa / pb (nullptr: 0), then Lab -> RGB at O's depth
+template <typename T, typename O, typename S>
+__device__ __forceinline__ void gray_fullres_pixel(long long p, int q, const double* tab, const S* __restrict__ pa, const S* __restrict__ pb, int H,
+                                                   int W, int interp, const float* __restrict__ mask, float mask_value, int oh, int ow, O* out) {
+    const int dy = (int)(p / ow), dx = (int)(p - (long long)dy * ow);
+    double L, ab[2] = {0.0, 0.0};
+    if (mask == nullptr) {
+        L = gray_L<T>(q, tab);
+    } else if (mask_value != 0.f) {
+        int yy, xx;
+        zoom_nearest(dy, dx, H, W, oh, ow, yy, xx);
+        L = 50.0 * ((double)mask[(size_t)yy * W + xx] / (double)mask_value);
+    } else {
+        L = 0.0;
+    }
+    if (pa != nullptr) interp_ab(pa, pb, H, W, interp, dy, dx, oh, ow, ab);
+    lab_to_rgb_q<O>(L, ab[0], ab[1], out);
+}
+
+// fullres_rgb_kernel for a plane, exact grid.  A thread takes 4 consecutive pixels of the flattened image: one aligned dword in (uint8) or two
+// (uint16), three (uint8 out) or six (uint16 out) aligned dwords out; src and rgb are 4-byte aligned (device allocations).  The npix % 4
+// pixels at the end go one per thread of workgroup 0 through narrow accesses.
+template <typename T, typename O, typename S>
+__global__ __launch_bounds__(256) void gray_fullres_kernel(const T* __restrict__ src, int oh, int ow, const S* __restrict__ pa,
+                                                           const S* __restrict__ pb, int H, int W, int interp, const float* __restrict__ mask,
+                                                           float mask_value, O* __restrict__ rgb) {
+    constexpr int kIn = (int)sizeof(T), kOut = 3 * (int)sizeof(O);      // dwords per group of 4 pixels
+    __shared__ double tab[sizeof(T) == 1 ? 256 : 1];
+    fill_gray_table<T>(tab);
+    const long long npix = (long long)oh * ow, ngroups = npix >> 2, g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g < ngroups) {
+        const unsigned* src4 = (const unsigned*)src;
+        unsigned* rgb4 = (unsigned*)rgb;
+        unsigned in[kIn], out[kOut];
+#pragma unroll
+        for (int j = 0; j < kIn; ++j) in[j] = src4[g * kIn + j];
+#pragma unroll
+        for (int j = 0; j < kOut; ++j) out[j] = 0u;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            int q;
+            if constexpr (sizeof(T) == 1) q = (int)((in[0] >> (8 * k)) & 255u); else q = (int)((in[k >> 1] >> (16 * (k & 1))) & 65535u);
+            O o[3];
+            gray_fullres_pixel<T, O, S>(g * 4 + k, q, tab, pa, pb, H, W, interp, mask, mask_value, oh, ow, o);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int e = k * 3 + c;
+                if constexpr (sizeof(O) == 1) out[e >> 2] |= (unsigned)o[c] << (8 * (e & 3)); else out[e >> 1] |= (unsigned)o[c] << (16 * (e & 1));
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kOut; ++j) rgb4[g * kOut + j] = out[j];
+    }
+    if (blockIdx.x == 0) {
+        const long long p = ngroups * 4 + threadIdx.x;
+        if (p < npix) {
+            O o[3];
+            gray_fullres_pixel<T, O, S>(p, (int)src[p], tab, pa, pb, H, W, interp, mask, mask_value, oh, ow, o);
+            rgb[p * 3 + 0] = o[0]; rgb[p * 3 + 1] = o[1]; rgb[p * 3 + 2] = o[2];
+        }
+    }
+}
+
+// the three (sample, output) forms times the two plane types: f(T(), O(), S()) launches its kernel<T, O, S>
+template <typename F>
+static hipError_t gray_forms(int bits, int out_bits, int src_f64, F&& f) {
+    typedef unsigned char u8;
+    typedef unsigned short u16;
+    if (bits == 8 && out_bits == 8) { if (src_f64) f(u8(), u8(), double()); else f(u8(), u8(), float()); }
+    else if (bits == 16 && out_bits == 8) { if (src_f64) f(u16(), u8(), double()); else f(u16(), u8(), float()); }
+    else if (bits == 16 && out_bits == 16) { if (src_f64) f(u16(), u16(), double()); else f(u16(), u16(), float()); }
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t launch_gray_fullres(const void* src, int bits, int oh, int ow, const void* a_plane, const void* b_plane, int src_f64, int H, int W,
+                               int interp, const float* mask, float mask_value, void* rgb, int out_bits, hipStream_t s) {
+    const long long npix = (long long)oh * ow, wgs = (((npix + 3) >> 2) + 255) / 256;
+    if (npix <= 0 || wgs > 0x7fffffffll || interp < 0 || interp > 2 || (((uintptr_t)src | (uintptr_t)rgb) & 3)) return hipErrorInvalidValue;
+    return gray_forms(bits, out_bits, src_f64, [&](auto t, auto o, auto p) {
+        typedef decltype(t) T; typedef decltype(o) O; typedef decltype(p) S;
+        hipLaunchKernelGGL((gray_fullres_kernel<T, O, S>), dim3((unsigned)wgs), dim3(256), 0, s, (const T*)src, oh, ow, (const S*)a_plane,
+                           (const S*)b_plane, H, W, interp, mask, mask_value, (O*)rgb);
+    });
+}
+
+// ragged_prologue_kernel for planes (idc_forward_async_gray): image i of the packed run starts at sample imgs[i].first, exact grid.  L is
+// ingest_gray_kernel's pixel; the hints are prologue_pixel's walk (the last covering hint of the image's clipped list wins; an RGB hint goes
+// through the 256-entry table, which every form fills: a hint's colour is uint8 whatever the samples are).
+template <typename T>
+__global__ __launch_bounds__(256) void ragged_gray_prologue_kernel(const T* __restrict__ src, const ImgDesc* __restrict__ imgs, long long npix, int H,
+                                                                   int W, float l_cent, const int* __restrict__ offs,
+                                                                   const HintRect* __restrict__ hints, int mode, float mask_value,
+                                                                   float* __restrict__ Lp, float* __restrict__ ab, float* __restrict__ mask) {
+    __shared__ double tab[256];
+    fill_srgb_table(tab);
+    const long long HW = (long long)H * W, p = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= npix) return;
+    const long long i = p / HW, r = p - i * HW;
+    const int y = (int)(r / W), x = (int)(r - (long long)y * W);
+    const ImgDesc d = imgs[i];
+    const T* img = src + d.first;
+    int y0, y1, x0, x1;
+    double wy, wx;
+    bilinear_taps(y, d.h, H, y0, y1, wy);
+    bilinear_taps(x, d.w, W, x0, x1, wx);
+    const int q = bilinear_gray<T>((double)img[(long long)y0 * d.w + x0], (double)img[(long long)y0 * d.w + x1],
+                                   (double)img[(long long)y1 * d.w + x0], (double)img[(long long)y1 * d.w + x1], wx, wy);
+    Lp[p] = (float)(gray_L<T>(q, tab) - (double)l_cent);
+    const int lo = offs != nullptr ? offs[i] : 0, hi = offs != nullptr ? offs[i + 1] : 0;
+    int hit = -1;
+    for (int k = hi - 1; k >= lo; --k) {
+        const HintRect h = hints[k];
+        if (y >= h.y0 && y <= h.y1 && x >= h.x0 && x <= h.x1) { hit = k; break; }
+    }
+    float a = 0.f, b = 0.f, m = 0.f;
+    if (hit >= 0) {
+        const HintRect h = hints[hit];
+        m = mask_value;
+        if (mode == 0) {
+            a = h.c0; b = h.c1;
+        } else {
+            const double hl[3] = {tab[(unsigned char)h.c0], tab[(unsigned char)h.c1], tab[(unsigned char)h.c2]};
+            double hL, da, db;
+            linear_to_lab(hl, hL, da, db);
+            a = (float)da; b = (float)db;
+        }
+    }
+    ab[(i * 2 + 0) * HW + r] = a;
+    ab[(i * 2 + 1) * HW + r] = b;
+    mask[p] = m;
+}
+
+hipError_t launch_ragged_gray_prologue(const void* src, int bits, const ImgDesc* imgs, int n, int H, int W, float l_cent, const int* offs,
+                                       const HintRect* hints, int mode, float mask_value, float* Lp, float* ab, float* mask, hipStream_t s) {
+    const long long npix = (long long)n * H * W, wgs = (npix + 255) / 256;
+    if (npix <= 0 || wgs > 0x7fffffffll || imgs == nullptr || (mode != 0 && mode != 1) || (bits != 8 && bits != 16)) return hipErrorInvalidValue;
+    if (bits == 8)
+        hipLaunchKernelGGL(ragged_gray_prologue_kernel<unsigned char>, dim3((unsigned)wgs), dim3(256), 0, s, (const unsigned char*)src, imgs, npix, H, W,
+                           l_cent, offs, hints, mode, mask_value, Lp, ab, mask);
+    else
+        hipLaunchKernelGGL(ragged_gray_prologue_kernel<unsigned short>, dim3((unsigned)wgs), dim3(256), 0, s, (const unsigned short*)src, imgs, npix, H,
+                           W, l_cent, offs, hints, mode, mask_value, Lp, ab, mask);
+    return hipGetLastError();
+}
+
+// ragged_fullres_rgb_kernel for planes packed back to back, exact grid: the `total` = imgs[n].first samples are ONE flat run from the 4-byte
+// aligned base.  A thread takes 4 consecutive pixels: one aligned dword in (uint8) or two (uint16), three or six aligned dwords out, whatever
+// residue mod 4 an image's start has; the bracketing searches and the carry into the next image are ragged_fullres_rgb_kernel's.  Only the
+// total % 4 pixels at the end of the run use narrow accesses.
+template <typename T, typename O>
+__global__ __launch_bounds__(256) void ragged_gray_fullres_kernel(const T* __restrict__ src, const ImgDesc* __restrict__ imgs, int n,
+                                                                  const double* __restrict__ lab_q, int H, int W, int interp, O* __restrict__ rgb) {
+    constexpr int kIn = (int)sizeof(T), kOut = 3 * (int)sizeof(O);
+    __shared__ double tab[sizeof(T) == 1 ? 256 : 1];
+    fill_gray_table<T>(tab);
+    const long long HW = (long long)H * W, total = imgs[n].first, ngroups = total >> 2;
+    const long long g0 = (long long)blockIdx.x * 256, g = g0 + threadIdx.x;
+    if (g0 < ngroups) {
+        const long long last = g0 + 256 < ngroups ? g0 + 256 : ngroups;
+        const int i_lo = image_of_pixel(imgs, 0, n - 1, g0 * 4), i_hi = image_of_pixel(imgs, i_lo, n - 1, last * 4 - 1);
+        if (g < ngroups) {
+            const unsigned* src4 = (const unsigned*)src;
+            unsigned* rgb4 = (unsigned*)rgb;
+            unsigned in[kIn], out[kOut];
+#pragma unroll
+            for (int j = 0; j < kIn; ++j) in[j] = src4[g * kIn + j];
+#pragma unroll
+            for (int j = 0; j < kOut; ++j) out[j] = 0u;
+            int i = image_of_pixel(imgs, i_lo, i_hi, g * 4);
+            ImgDesc d = imgs[i];
+            long long p = g * 4 - d.first, npix = (long long)d.h * d.w;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                int q;
+                if constexpr (sizeof(T) == 1) q = (int)((in[0] >> (8 * k)) & 255u); else q = (int)((in[k >> 1] >> (16 * (k & 1))) & 65535u);
+                O o[3];
+                const double* pa = lab_q + ((long long)i * 3 + 1) * HW;
+                gray_fullres_pixel<T, O, double>(p, q, tab, pa, pa + HW, H, W, interp, (const float*)nullptr, 0.f, d.h, d.w, o);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const int e = k * 3 + c;
+                    if constexpr (sizeof(O) == 1) out[e >> 2] |= (unsigned)o[c] << (8 * (e & 3)); else out[e >> 1] |= (unsigned)o[c] << (16 * (e & 1));
+                }
+                if (++p == npix && k < 3) { p = 0; d = imgs[++i]; npix = (long long)d.h * d.w; }      // i + 1 <= n - 1: the group's next pixel is in the run
+            }
+#pragma unroll
+            for (int j = 0; j < kOut; ++j) rgb4[g * kOut + j] = out[j];
+        }
+    }
+    if (blockIdx.x == 0) {
+        const long long t = ngroups * 4 + threadIdx.x;
+        if (t < total) {
+            const int i = image_of_pixel(imgs, 0, n - 1, t);
+            const ImgDesc d = imgs[i];
+            O o[3];
+            const double* pa = lab_q + ((long long)i * 3 + 1) * HW;
+            gray_fullres_pixel<T, O, double>(t - d.first, (int)src[t], tab, pa, pa + HW, H, W, interp, (const float*)nullptr, 0.f, d.h, d.w, o);
+            rgb[t * 3 + 0] = o[0]; rgb[t * 3 + 1] = o[1]; rgb[t * 3 + 2] = o[2];
+        }
+    }
+}
+
+hipError_t launch_ragged_gray_fullres(const void* src, int bits, const ImgDesc* imgs, int n, long long total, const double* lab_q, int H, int W,
+                                      int interp, void* rgb, int out_bits, hipStream_t s) {
+    const long long wgs = (((total + 3) >> 2) + 255) / 256;
+    if (n <= 0 || total < n || wgs > 0x7fffffffll || imgs == nullptr || interp < 0 || interp > 2 || (((uintptr_t)src | (uintptr_t)rgb) & 3))
+        return hipErrorInvalidValue;
+    return gray_forms(bits, out_bits, 1, [&](auto t, auto o, auto) {
+        typedef decltype(t) T; typedef decltype(o) O;
+        hipLaunchKernelGGL((ragged_gray_fullres_kernel<T, O>), dim3((unsigned)wgs), dim3(256), 0, s, (const T*)src, imgs, n, lab_q, H, W, interp, (O*)rgb);
+    });
+}
+
+// joint_fullres_kernel for planes (blockIdx.y = image; imgs == nullptr: one plane [sh,sw], the blocking calls; else image i of the packed run
+// starts at sample imgs[i].first): the same tile, weights, staging and tap loop; the source read is one sample and the row store knows O.  A row of the tile is 96 (uint8) or 192 (uint16) consecutive bytes of the image that start on any residue mod 4 (uint16:
+// an even one), so it goes out as up to 3 head bytes, up to 24 / 48 aligned dwords (lanes stride the row) and up to 3 tail bytes.
+template <typename T, typename O, typename S>
+__global__ __launch_bounds__(256) void gray_joint_fullres_kernel(const T* __restrict__ src, const ImgDesc* __restrict__ imgs, int sh, int sw,
+                                                                 const S* __restrict__ pa, const S* __restrict__ pb, long long plane_stride,
+                                                                 const float* __restrict__ Lp, float l_cent, int H, int W, int interp,
+                                                                 JointParams jp, O* __restrict__ rgb, double* __restrict__ ab_out) {
+#pragma clang fp contract(off)
+    __shared__ double tab[sizeof(T) == 1 ? 256 : 1];
+    __shared__ double sL[kJointCells], sA[kJointCells], sB[kJointCells];
+    __shared__ double wys[kJointTH][kJointMaxTaps], wxs[kJointTW][kJointMaxTaps];
+    __shared__ __attribute__((aligned(4))) unsigned char outb[kJointTH][kJointTW * 3 * sizeof(O)];
+    const int img = blockIdx.y;
+    long long first = 0;
+    if (imgs != nullptr) { const ImgDesc d = imgs[img]; sh = d.h; sw = d.w; first = d.first; }
+    const int tiles_x = (sw + kJointTW - 1) / kJointTW, tiles_y = (sh + kJointTH - 1) / kJointTH;
+    if ((long long)blockIdx.x >= (long long)tiles_x * tiles_y) return;        // uniform over the workgroup: this image has fewer tiles than the largest
+    src += first;
+    const S* ia = pa != nullptr ? pa + (long long)img * plane_stride : nullptr;
+    const S* ib = pa != nullptr ? pb + (long long)img * plane_stride : nullptr;
+    if (Lp != nullptr) Lp += (long long)img * H * W;
+    fill_gray_table<T>(tab);
+    const int ty0 = (int)(blockIdx.x / tiles_x) * kJointTH, tx0 = (int)(blockIdx.x % tiles_x) * kJointTW;
+    const int tx = threadIdx.x & (kJointTW - 1), ty = threadIdx.x / kJointTW;
+    const int y = ty0 + ty, x = tx0 + tx;
+    const bool valid = y < sh && x < sw;
+    const bool joint = interp == kInterpJoint && ia != nullptr;
+    const int R = jp.R, T_ = 2 * R + 1;
+    const double sy = (double)H / (double)sh, sx = (double)W / (double)sw;
+    bool staged = false;
+    int fj0 = 0, fi0 = 0, fc = 0;
+    if (joint) {
+        for (int t = threadIdx.x; t < (kJointTH + kJointTW) * kJointMaxTaps; t += 256) {
+            const int r = t / kJointMaxTaps, k = t - r * kJointMaxTaps;
+            if (k >= T_) continue;
+            double u;
+            const int c0 = r < kJointTH ? joint_centre(ty0 + r, sy, u) : joint_centre(tx0 + r - kJointTH, sx, u);
+            const double dd = (double)(c0 - R + k) - u;
+            const double wgt = exp(-(dd * dd) / jp.two_ss);
+            if (r < kJointTH) wys[r][k] = wgt; else wxs[r - kJointTH][k] = wgt;
+        }
+        double u_;
+        const int y_last = ty0 + kJointTH - 1 < sh ? ty0 + kJointTH - 1 : sh - 1, x_last = tx0 + kJointTW - 1 < sw ? tx0 + kJointTW - 1 : sw - 1;
+        fj0 = joint_centre(ty0, sy, u_) - R; fi0 = joint_centre(tx0, sx, u_) - R;
+        const int fr = joint_centre(y_last, sy, u_) + R - fj0 + 1;
+        fc = joint_centre(x_last, sx, u_) + R - fi0 + 1;
+        staged = (long long)fr * fc <= kJointCells;
+        if (staged) {
+            for (int c = threadIdx.x; c < fr * fc; c += 256) {
+                const int jj = fj0 + c / fc, ii = fi0 + c % fc;
+                if (jj < 0 || jj >= H || ii < 0 || ii >= W) continue;        // a tap outside the image is skipped, so its cell is never read
+                const long long g = (long long)jj * W + ii;
+                sL[c] = (double)Lp[g] + (double)l_cent; sA[c] = (double)ia[g]; sB[c] = (double)ib[g];
+            }
+        }
+        __syncthreads();
+    }
+    double L = 0.0, a = 0.0, b = 0.0;
+    if (valid) {
+        L = gray_L<T>((int)src[(long long)y * sw + x], tab);
+        if (joint) {
+            double u, v;
+            const int j0 = joint_centre(y, sy, u), i0 = joint_centre(x, sx, v);
+            double num_a = 0.0, num_b = 0.0, den = 0.0;
+            for (int kj = 0; kj < T_; ++kj) {
+                const int j = j0 - R + kj;
+                if (j < 0 || j >= H) continue;
+                const double wy = wys[ty][kj];
+                for (int ki = 0; ki < T_; ++ki) {
+                    const int i = i0 - R + ki;
+                    if (i < 0 || i >= W) continue;
+                    double Lc, ac, bc;
+                    if (staged) {
+                        const int c = (j - fj0) * fc + (i - fi0);
+                        Lc = sL[c]; ac = sA[c]; bc = sB[c];
+                    } else {
+                        const long long g = (long long)j * W + i;
+                        Lc = (double)Lp[g] + (double)l_cent; ac = (double)ia[g]; bc = (double)ib[g];
+                    }
+                    const double ws = wy * wxs[tx][ki], dl = L - Lc;
+                    const double wt = ws * (exp(-(dl * dl) / jp.two_sr) + 1e-6);       // IDC_JOINT_EPS
+                    num_a += wt * ac; num_b += wt * bc; den += wt;
+                }
+            }
+            a = num_a / den; b = num_b / den;
+        } else if (ia != nullptr) {
+            double ab[2];
+            interp_ab(ia, ib, H, W, interp, y, x, sh, sw, ab);
+            a = ab[0]; b = ab[1];
+        }
+        if (ab_out != nullptr) {
+            const long long np = (long long)sh * sw, p = (long long)y * sw + x;
+            ab_out[first * 2 + p] = a; ab_out[first * 2 + np + p] = b;
+        }
+    }
+    if (rgb == nullptr) return;
+    O o[3] = {0, 0, 0};
+    if (valid) lab_to_rgb_q<O>(L, a, b, o);
+    O* orow = (O*)outb[ty];
+    orow[tx * 3 + 0] = o[0]; orow[tx * 3 + 1] = o[1]; orow[tx * 3 + 2] = o[2];
+    __syncthreads();
+    if (y >= sh) return;
+    const int tw = sw - tx0 < kJointTW ? sw - tx0 : kJointTW, nb = tw * 3 * (int)sizeof(O);
+    unsigned char* g = (unsigned char*)(rgb + (first + (long long)y * sw + tx0) * 3);
+    const int mis = (int)((4 - ((uintptr_t)g & 3)) & 3), head = mis < nb ? mis : nb;
+    const int ndw = (nb - head) >> 2, tail = nb - head - ndw * 4;
+    const unsigned char* row = outb[ty];
+    for (int k = tx; k < ndw; k += kJointTW) {
+        const unsigned char* s4 = row + head + k * 4;
+        ((unsigned*)(g + head))[k] = (unsigned)s4[0] | ((unsigned)s4[1] << 8) | ((unsigned)s4[2] << 16) | ((unsigned)s4[3] << 24);
+    }
+    if (tx < head) g[tx] = row[tx];                                                  // lanes 0..2 the head bytes, 3..5 the tail bytes
+    else if (tx >= 3 && tx - 3 < tail) g[head + ndw * 4 + tx - 3] = row[head + ndw * 4 + tx - 3];
+}
+
+hipError_t launch_gray_joint_fullres(const void* src, int bits, const ImgDesc* imgs, int n, int sh, int sw, long long max_tiles, const void* a_plane,
+                                     const void* b_plane, int src_f64, long long plane_stride, const float* Lp, float l_cent, int H, int W,
+                                     int interp, JointParams jp, void* rgb, int out_bits, double* ab_out, hipStream_t s) {
+    const long long tiles = max_tiles;
+    if (n <= 0 || n > 65535 || src == nullptr || (imgs == nullptr && (n != 1 || sh <= 0 || sw <= 0)) || tiles <= 0 || tiles > 0x7fffffffll || interp < 0 || interp > kInterpJoint || (rgb == nullptr && ab_out == nullptr) ||
+        (a_plane == nullptr) != (b_plane == nullptr) || (out_bits == 16 && ((uintptr_t)rgb & 1)))
+        return hipErrorInvalidValue;
+    if (interp == kInterpJoint && a_plane != nullptr && (Lp == nullptr || jp.R < 1 || jp.R > kJointMaxR || !(jp.two_ss > 0.0) || !(jp.two_sr > 0.0)))
+        return hipErrorInvalidValue;
+    return gray_forms(bits, out_bits, src_f64, [&](auto t, auto o, auto p) {
+        typedef decltype(t) T; typedef decltype(o) O; typedef decltype(p) S;
+        hipLaunchKernelGGL((gray_joint_fullres_kernel<T, O, S>), dim3((unsigned)tiles, (unsigned)n), dim3(256), 0, s, (const T*)src, imgs, sh, sw,
+                           (const S*)a_plane, (const S*)b_plane, plane_stride, Lp, l_cent, H, W, interp, jp, (O*)rgb, ab_out);
+    });
+}
+
+// ------------------------------------------------------------------------------------------------
 // evaluation batches (idc_reveal_hints / idc_forward_async_eval): the paper's simulated user and its metric around the unchanged forward.
 // reveal: a hint's colour = the mean ground-truth ab of the image under the hint's own rectangle, written into the device list that the
 // prologue / raster_hints_kernel then reads in IDC_HINT_AB mode.  net_truth: the net-size uint8 pixels the prologue's L comes from, kept as the

@@ -200,7 +200,8 @@ struct idc_context {
     // image ingestion (idc_set_image_rgb / idc_fullres_rgb): per slot the uint8 source kept on the device (IDC_INGEST_KEEP_SOURCE; empty = none)
     // and its size, and the mask_value of the slot's last idc_set_hints (0 = never had hints)
     // ... and the l_cent of that ingestion: with the slot's L plane it is the guide of the joint upsampling (a source is resident only while that plane is intact)
-    struct SlotSource { DevMem<unsigned char> d_rgb; int h = 0, w = 0; float l_cent = 0.f; };
+    // ... and its format: gray_bits 0 = [h,w,3] uint8 RGB (idc_set_image_rgb), 8 | 16 = one plane [h,w] of uint8 | uint16 (idc_set_image_gray)
+    struct SlotSource { DevMem<unsigned char> d_rgb; int h = 0, w = 0; float l_cent = 0.f; int gray_bits = 0; };
     std::vector<SlotSource> src;
     std::vector<float> hint_mask_value;
     DevMem<unsigned char> d_ingest;                                  // upload buffer of the sources that are not kept

@@ -678,7 +678,7 @@ static int batch_reserve(idc_context* h, const BatchCall& c, const BatchPlan& p,
     HIPCHK(h, sl.d_rgb.ensure(nb * hw * 3));
     if (p.source_out) {
         HIPCHK(h, sl.d_labq.ensure(nb * hw * 3 * 8));
-        HIPCHK(h, sl.d_full.ensure(p.in_bytes));
+        HIPCHK(h, sl.d_full.ensure(p.rgb_bytes));
     }
     if (c.eval) {
         if (!p.source_out) HIPCHK(h, sl.d_truth.ensure(nb * hw * 3));
@@ -758,7 +758,10 @@ static int batch_colourise(idc_context* h, const BatchCall& c, const BatchPlan& 
         HIPCHK(h, launch_reveal_hints(sl.d_src.get(), m.tab, m.offs, n, 0, 0, h->H, h->W, m.hints, p.kept, m.orig, d_cols, s));
         mode = IDC_HINT_AB;
     }
-    if (c.ragged)
+    if (c.gray_bits)
+        HIPCHK(h, launch_ragged_gray_prologue(sl.d_src.get(), c.gray_bits, m.tab, n, h->H, h->W, c.l_cent, m.offs, m.hints, mode, c.mask_value, sl.d_L.get(),
+                                              sl.d_ab.get(), sl.d_mask.get(), s));
+    else if (c.ragged)
         HIPCHK(h, launch_ragged_prologue(sl.d_src.get(), m.tab, n, h->H, h->W, c.l_cent, m.offs, m.hints, mode, c.mask_value, sl.d_L.get(), sl.d_ab.get(),
                                          sl.d_mask.get(), s));
     else
@@ -772,7 +775,15 @@ static int batch_colourise(idc_context* h, const BatchCall& c, const BatchPlan& 
     if (!p.dist && !((h->flags & IDC_FLAG_DIST313) && h->keep_dist313)) h->dist_n = dist_n;      // no distribution was written: the blocking forward's stays resident
     HIPCHK(h, launch_lab_post(sl.d_L.get(), c.l_cent, sl.d_out.get(), sl.d_rgb.get(), p.source_out ? sl.d_labq.get() : nullptr, n, h->H, h->W, s));
     sl.up_interp = h->batch_interp; sl.up_joint = h->joint;       // the handle's setting as it is now: a later idc_set_batch_upsample does not reach this batch
-    if (p.source_out && sl.up_interp == IDC_INTERP_JOINT) {         // guide: the slot's own L plane and this call's l_cent
+    if (p.source_out && c.gray_bits) {        // the grey forms of the two kernels below, on the plan's bytes per pixel
+        const double* pa = sl.d_labq.get() + hw;
+        if (sl.up_interp == IDC_INTERP_JOINT)
+            HIPCHK(h, launch_gray_joint_fullres(sl.d_src.get(), c.gray_bits, m.tab, n, 0, 0, p.max_tiles, pa, pa + hw, 1, (long long)(3 * hw), sl.d_L.get(),
+                                                c.l_cent, h->H, h->W, IDC_INTERP_JOINT, sl.up_joint, sl.d_full.get(), c.out_bits, nullptr, s));
+        else
+            HIPCHK(h, launch_ragged_gray_fullres(sl.d_src.get(), c.gray_bits, m.tab, n, (long long)(p.in_bytes / p.bpp_in), sl.d_labq.get(), h->H, h->W,
+                                                 IDC_INTERP_LINEAR, sl.d_full.get(), c.out_bits, s));
+    } else if (p.source_out && sl.up_interp == IDC_INTERP_JOINT) {         // guide: the slot's own L plane and this call's l_cent
         const double* pa = sl.d_labq.get() + hw;
         HIPCHK(h, launch_joint_fullres(sl.d_src.get(), c.ragged ? m.tab : nullptr, n, c.src_h, c.src_w, p.max_tiles, pa, pa + hw, 1, (long long)(3 * hw),
                                        sl.d_L.get(), c.l_cent, h->H, h->W, IDC_INTERP_JOINT, sl.up_joint, sl.d_full.get(), nullptr, s));
@@ -966,6 +977,17 @@ int idc_forward_async_dist_score(idc_handle h, int slot, int n, const idc_ref_im
     c.eval = true; c.sse = sse; c.hint_colours = hint_colours;
     c.taps_call = true; c.taps = taps;
     c.score_call = true; c.spec = spec; c.centres = centres; c.sout = out;
+    return forward_async_rgb(h, c);
+}
+
+int idc_forward_async_gray(idc_handle h, int slot, int n, int bits, const idc_gray_image* images, const int32_t* hint_offsets,
+                           const idc_hint* hints, int mode, float mask_value, float maskcent, float l_cent, unsigned flags,
+                           const idc_batch_refs* refs, void* const* rgb_out, float* out_ab, const idc_dist_taps* taps) {
+    BatchCall c = images_call(slot, n, nullptr, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags, refs, (uint8_t* const*)rgb_out, out_ab);
+    c.grays = images;
+    c.gray_bits = bits ? bits : -1;      // (0 is the RGB calls' own value: like every width but 8 and 16 it is refused by the plan)
+    c.out_bits = (flags & IDC_BATCH_OUT_RGB16) ? 16 : 8;
+    if (taps) { c.eval = true; c.taps_call = true; c.taps = taps; }        // idc_forward_async_dist without a score and without revealed colours
     return forward_async_rgb(h, c);
 }
 

@@ -327,6 +327,26 @@ hipError_t launch_joint_fullres(const unsigned char* src, const ImgDesc* imgs, i
                                 const void* b_plane, int src_f64, long long plane_stride, const float* Lp, float l_cent, int H, int W, int interp,
                                 JointParams jp, unsigned char* rgb, double* ab_out, hipStream_t s);
 
+// Greyscale sources (idc_set_image_gray and the full-resolution getters on a kept plane; idc_colour.hip; the rule: include/ideepcolor.h).
+// bits = 8 | 16: the plane's samples are u8 | u16; out_bits = 8 | 16: the image goes out as u8 | u16 [.,.,3] (16 only from 16).  Exact grids.
+// ingest_gray: launch_ingest_rgb for srcs [n] device pointers to [src_h,src_w] planes -> gray_net [n,H,W] (the sample type) and l_net [n,H,W]
+// f64 (either may be nullptr) and Lp.  gray_fullres: launch_fullres_rgb for one plane src [oh,ow]; src and rgb 4-byte aligned.
+// gray_joint_fullres: launch_joint_fullres for planes -- imgs == nullptr: one plane [sh,sw] (n = 1); else the run below, grid dim3(max_tiles, n)
+// -> rgb (or nullptr) and ab_out (or nullptr).  ragged_gray_prologue / ragged_gray_fullres (idc_forward_async_gray): launch_ragged_prologue /
+// launch_ragged_fullres_rgb for planes packed back to back; image i starts at SAMPLE imgs[i].first of src and at element 3 * first of rgb
+// (ImgDesc::off is not read); src and rgb 4-byte aligned at their base only.
+hipError_t launch_ingest_gray(const void* const* srcs, int bits, int n, int src_h, int src_w, int H, int W, float l_cent, float* Lp, void* gray_net,
+                              double* l_net, hipStream_t s);
+hipError_t launch_gray_fullres(const void* src, int bits, int oh, int ow, const void* a_plane, const void* b_plane, int src_f64, int H, int W,
+                               int interp, const float* mask, float mask_value, void* rgb, int out_bits, hipStream_t s);
+hipError_t launch_gray_joint_fullres(const void* src, int bits, const ImgDesc* imgs, int n, int sh, int sw, long long max_tiles, const void* a_plane,
+                                     const void* b_plane, int src_f64, long long plane_stride, const float* Lp, float l_cent, int H, int W,
+                                     int interp, JointParams jp, void* rgb, int out_bits, double* ab_out, hipStream_t s);
+hipError_t launch_ragged_gray_prologue(const void* src, int bits, const ImgDesc* imgs, int n, int H, int W, float l_cent, const int* offs,
+                                       const HintRect* hints, int mode, float mask_value, float* Lp, float* ab, float* mask, hipStream_t s);
+hipError_t launch_ragged_gray_fullres(const void* src, int bits, const ImgDesc* imgs, int n, long long total, const double* lab_q, int H, int W,
+                                      int interp, void* rgb, int out_bits, hipStream_t s);
+
 // Evaluation batches (idc_reveal_hints / idc_forward_async_eval; idc_colour.hip).  reveal_hints: (c0, c1) of each of the n_rects clipped
 // rectangles of `hints` = the float64 mean ab (rounded once to fp32) of its image's net-size pixels under it, one workgroup per rectangle, fixed
 // summation order, cost = the rectangle's area; the image is the single [src_h,src_w,3] source at src (imgs == nullptr) or image i of the packed

@@ -463,6 +463,16 @@ def _image_item(who, item, with_ref):
     return (rgb, hints, item[2] if len(item) > 2 else None, len(item) > 2) if with_ref else (rgb, hints)
 
 
+def _gray_item(who, item, with_ref):
+    """``_image_item`` for greyscale planes: ``gray`` (h,w) uint8 or uint16, its dtype kept."""
+    item = (item,) if isinstance(item, np.ndarray) else tuple(item)
+    gray = np.asarray(item[0])
+    if gray.dtype not in (np.uint8, np.uint16) or gray.ndim != 2 or gray.size == 0:
+        raise ValueError("%s needs uint8 or uint16 (h,w) planes, got %s %s" % (who, gray.dtype, gray.shape))
+    hints = item[1] if len(item) > 1 else None
+    return (gray, hints, item[2] if len(item) > 2 else None, len(item) > 2) if with_ref else (gray, hints)
+
+
 class HipColorizer(object):
     def __init__(self, H=256, W=None, max_batch=1, precision="bf16", device=0, dist=False, global_hints=False, dist313=False,
                  throughput_blob=False):
@@ -670,8 +680,43 @@ class HipColorizer(object):
                 self._src_shape.pop(int(img) + i, None)
         return net, lab
 
-    def fullres_rgb(self, source="output_ab", interp="linear", l_mode="image", img=0):
+    def set_image_gray(self, gray, img=0, l_cent=50., keep_source=False, want_net=True, want_l=True):
+        """``set_image_rgb`` for single-channel image(s) (``idc_set_image_gray``): gray (h,w) or (n,h,w), uint8 or uint16 -- the dtype is
+        the format, nothing is converted -- whose sRGB value v / 255 or v / 65535 stands on all three channels.  Returns (gray_net (n,H,W) of
+        the same dtype | None, l_net (n,H,W) float64 | None).  ``keep_source``: the plane stays on the device for ``fullres_rgb`` (a uint16
+        plane also serves ``depth=16``) and ``fullres_ab``."""
+        gray = np.asarray(gray)
+        if gray.dtype not in (np.uint8, np.uint16):
+            raise ValueError("gray must be uint8 or uint16, got %s" % gray.dtype)
+        if gray.ndim == 2:
+            gray = gray[None]
+        if gray.ndim != 3:
+            raise ValueError("gray must be (h,w) or (n,h,w), got %s" % (gray.shape,))
+        gray = np.ascontiguousarray(gray)
+        n, sh, sw = gray.shape
+        net = self._pool.take((n, self.H, self.W), gray.dtype) if want_net else None
+        l_net = self._pool.take((n, self.H, self.W), np.float64) if want_l else None
+        vp = ctypes.c_void_p
+        self.l_serial += 1
+        try:
+            self._chk(self.lib.idc_set_image_gray(self._h, int(img), n, sh, sw, 8 * gray.dtype.itemsize, gray.ctypes.data_as(vp), float(l_cent),
+                                                  N.IDC_INGEST_KEEP_SOURCE if keep_source else 0,
+                                                  net.ctypes.data_as(vp) if want_net else None, l_net.ctypes.data_as(vp) if want_l else None))
+        except N.IdcError as ex:
+            if ex.status not in (-1, -6):
+                for i in range(n):
+                    self._src_shape.pop(int(img) + i, None)
+            raise
+        for i in range(n):
+            if keep_source:
+                self._src_shape[int(img) + i] = (sh, sw)
+            else:
+                self._src_shape.pop(int(img) + i, None)
+        return net, l_net
+
+    def fullres_rgb(self, source="output_ab", interp="linear", l_mode="image", img=0, depth=8):
         """The full-resolution getters from the resident source of slot ``img`` (``idc_fullres_rgb``) -> (src_h, src_w, 3) uint8.
+        ``depth=16`` (``idc_fullres_rgb16``): uint16, from a kept uint16 greyscale source only, l_mode 'image'.
         source: 'output_ab', 'output_ab_raw', 'input_ab' as in ``upsample_lab2rgb``, or 'no_ab' (a = b = 0); interp: 'cubic', 'linear',
         'nearest', or 'joint' (the joint bilateral upsampling of ``set_joint_upsample``, guided by the source's own L; needs l_mode 'image');
         l_mode: 'image' (L of the source pixel) or 'mask50' (50 x the nearest-upsampled hint mask).  IdcError (UNSUPPORTED)
@@ -680,14 +725,22 @@ class HipColorizer(object):
                "no_ab": N.IDC_SRC_NO_AB}[source]
         itp = _INTERP[interp]
         lm = {"image": N.IDC_L_IMAGE, "mask50": N.IDC_L_MASK50}[l_mode]
+        if depth not in (8, 16):
+            raise ValueError("depth must be 8 or 16, got %r" % (depth,))
+        if depth == 16 and l_mode != "image":
+            raise ValueError("depth=16 carries the L of the source samples: it needs l_mode 'image'")
+        if depth == 16:
+            call = lambda p: self.lib.idc_fullres_rgb16(self._h, int(img), src, itp, p)
+        else:
+            call = lambda p: self.lib.idc_fullres_rgb(self._h, int(img), src, itp, lm, p)
         shape = self._src_shape.get(int(img))
         self.l_serial += 1
         if shape is None:       # no source was kept through this object: the library says so (without a result pointer it cannot write anything)
-            self._chk(self.lib.idc_fullres_rgb(self._h, int(img), src, itp, lm, None))
+            self._chk(call(None))
             raise N.IdcError(-7, "the source of image slot %d was not ingested through this object" % img)
-        rgb = self._pool.take(shape + (3,), np.uint8)
+        rgb = self._pool.take(shape + (3,), np.uint16 if depth == 16 else np.uint8)
         try:
-            self._chk(self.lib.idc_fullres_rgb(self._h, int(img), src, itp, lm, rgb.ctypes.data_as(ctypes.c_void_p)))
+            self._chk(call(rgb.ctypes.data_as(ctypes.c_void_p)))
         except N.IdcError as ex:
             if ex.status == -7 and "resident source" in str(ex):
                 self._src_shape.pop(int(img), None)
@@ -1128,20 +1181,25 @@ class HipColorizer(object):
         # a group of one: the items are whole batches, checked in submit, behind the yield of the slot's older result
         yield from self._two_slot_stream(batches, 1, upsample, lambda item: item, submit, lambda state: [np.array(state[0])])
 
-    def _two_slot_stream(self, items, batch, upsample, parse, submit, finish):
+    def _two_slot_stream(self, items, batch, upsample, parse, submit, finish, key=None):
         """The generator behind ``colorize_stream``, ``colorize_images`` and their relatives: ``parse(item)`` every item as it arrives, group
         ``batch`` of them (default ``max_batch``; the last group may be shorter), ``submit(slot, group, first_index)`` group k on slot k % 2
         once that slot's older batch is finished -- ``first_index`` is the stream index of the group's first item; what it returns (results
         and whatever must stay alive: pinned pool memory) is kept until ``wait(slot)`` has returned -- and yield everything in
         ``finish(state)`` of each batch in input order.  ``upsample`` as in ``colorize_stream``.  A consumer that stops early: both slots are
-        waited for, so nothing stays in flight on buffers about to be recycled, then the upsample setting goes back."""
+        waited for, so nothing stays in flight on buffers about to be recycled, then the upsample setting goes back.
+        ``key`` (of a parsed item): an item whose key differs from its group's closes that group, as a full batch does."""
         batch = self._group_size(batch)
         pending = [None, None]                      # per slot: submit's state of the batch in flight
 
         def groups():
             group = []
             for item in items:
-                group.append(parse(item))
+                parsed = parse(item)
+                if key is not None and group and key(parsed) != key(group[0]):
+                    yield group
+                    group = []
+                group.append(parsed)
                 if len(group) == batch:
                     yield group
                     group = []
@@ -1337,6 +1395,157 @@ class HipColorizer(object):
                                                                       ctypes.byref(sout)))))
         self._in_flight[int(slot)] = (images, out_rgb, out_ab, res)
         return res
+
+    def forward_async_gray(self, slot, images, hints, out_rgb=None, out_ab=None, mode="ab", mask_value=1.0, maskcent=0.0, l_cent=50.0,
+                           out="net", depth=8, refs=None, ref_index=None, centres=None, hist_flag=1.0, saturation=False, want_rgb=True,
+                           peaks=0, radius=2, skip_hints=False, queries=None, K=5, N_draws=25000, seed=0, bin_centres=None):
+        """``forward_async_images`` for greyscale planes (``idc_forward_async_gray``): ``images`` is a list of n C-contiguous (h,w) arrays, all
+        uint8 or all uint16 (the dtype is the format; one format per call), each of its own size.  ``out_rgb``: a list of n arrays, (H,W,3)
+        uint8 with out='net', images[i].shape + (3,) with out='source' -- uint8, or uint16 with ``depth=16`` (uint16 planes and out='source'
+        only) -- or ``None``: taken from the pinned pool.  Without taps it returns the list of outputs.  ``peaks`` > 0 or ``queries`` (an
+        engine with a distribution head): ``forward_async_dist``'s peaks and suggestions (``bin_centres`` (B,2): the bin centres) without its
+        score and revealed colours; it then returns a ``DistBatch``, and ``want_rgb=False`` colourises nothing for the caller.  Everything is
+        valid after ``wait(slot)``.  Hints, references and the other arguments as in ``forward_async_images``; mode 'reveal' does not exist
+        here: a grey source has no colour to reveal."""
+        images = list(images)
+        n = len(images)
+        dtypes = set(a.dtype for a in images if isinstance(a, np.ndarray))
+        if len(dtypes) != 1 or not dtypes <= {np.dtype(np.uint8), np.dtype(np.uint16)}:
+            raise ValueError("forward_async_gray needs (h,w) arrays that are all uint8 or all uint16")
+        for a in images:
+            if not isinstance(a, np.ndarray) or a.ndim != 2 or not a.flags.c_contiguous or a.size == 0:
+                raise ValueError("forward_async_gray needs C-contiguous (h,w) arrays")
+        bits = 8 * images[0].dtype.itemsize
+        if depth not in (8, 16):
+            raise ValueError("depth must be 8 or 16, got %r" % (depth,))
+        if depth == 16 and (bits != 16 or out != "source"):
+            raise ValueError("depth=16 needs uint16 planes and out='source'")
+        flags = {"net": 0, "source": N.IDC_BATCH_OUT_SOURCE}[out] | (N.IDC_BATCH_OUT_RGB16 if depth == 16 else 0)
+        odt = np.uint16 if depth == 16 else np.uint8
+        shapes = [tuple(a.shape) + (3,) if flags else (self.H, self.W, 3) for a in images]
+        if want_rgb:
+            if out_rgb is None:
+                nbytes = [int(np.prod(s)) * (depth // 8) for s in shapes]           # (each output starts on an even byte of the block)
+                out_rgb = [o[:b].view(odt).reshape(s) for o, b, s in zip(self._pinned_slices([(b + 1) // 2 * 2 for b in nbytes]), nbytes, shapes)]
+            out_rgb = list(out_rgb)
+            if len(out_rgb) != n:
+                raise ValueError("forward_async_gray needs %d outputs, got %d" % (n, len(out_rgb)))
+            for o, shp in zip(out_rgb, shapes):
+                if not isinstance(o, np.ndarray) or o.dtype != odt or not o.flags.c_contiguous or tuple(o.shape) != shp:
+                    raise ValueError("forward_async_gray needs a %s C-contiguous out_rgb of shape %s" % (np.dtype(odt).name, shp))
+        else:
+            out_rgb = None
+        if out_ab is not None and (out_ab.dtype != np.float32 or not out_ab.flags.c_contiguous or tuple(out_ab.shape) != (n, 2, self.H, self.W)):
+            raise ValueError("forward_async_gray needs a float32 C-contiguous out_ab of shape %s" % ((n, 2, self.H, self.W),))
+        offsets, arr = flatten_hints(hints, n)
+        vp = ctypes.c_void_p
+        table = (N.GrayImage * max(n, 1))()
+        outs = (vp * max(n, 1))() if want_rgb else None
+        for i, a in enumerate(images):
+            table[i].pix, table[i].h, table[i].w = a.ctypes.data, a.shape[0], a.shape[1]
+            if want_rgb:
+                outs[i] = out_rgb[i].ctypes.data
+        block, keep = None, None
+        if refs is not None:
+            (m, rarr, idx, c, hist_flag, rflags), keep = _ref_args(refs, ref_index, centres, hist_flag, saturation, n)
+            block = N.BatchRefs(m, rarr, idx.ctypes.data if idx is not None else None, c.ctypes.data if c is not None else None, hist_flag, rflags)
+        res, t, held = None, None, None
+        P = int(peaks)
+        if P > 0 or queries is not None:
+            if isinstance(queries, str) and queries != "peaks":
+                raise ValueError("queries is a list of rows, None or 'peaks'")
+            at_peaks = isinstance(queries, str)
+            res, t = DistBatch(), N.DistTaps()
+            res.out_rgb, res.out_ab = out_rgb, out_ab
+            t.n_peaks, t.radius = P, int(radius)
+            t.flags = (N.IDC_PEAKS_SKIP_HINTS if skip_hints else 0) | (N.IDC_TAPS_SUGGEST_AT_PEAKS if at_peaks else 0)
+            if P > 0:
+                res.peaks, res.peak_ent = self._pool.take((n, P, 2), np.int32), self._pool.take((n, P), np.float32)
+                t.peaks, t.peak_ent = res.peaks.ctypes.data, res.peak_ent.ctypes.data
+            qarr = None if at_peaks else dist_queries(queries, int(seed))
+            Q = n * P if at_peaks else (len(qarr) if qarr is not None else 0)
+            if Q > 0:
+                t.n_queries = 0 if qarr is None else len(qarr)
+                if qarr is not None:
+                    t.queries = qarr
+                t.K, t.N, t.seed = int(K), int(N_draws), int(seed) & 0xFFFFFFFF
+                held = _f32c(bin_centres, (self.dist_bins(), 2)) if bin_centres is not None else None
+                t.centres = held.ctypes.data if held is not None else None
+                res.sugg_centres, res.sugg_conf = self._pool.take((Q, t.K, 2), np.float64), self._pool.take((Q, t.K), np.float64)
+                t.sugg_centres, t.sugg_conf = res.sugg_centres.ctypes.data, res.sugg_conf.ctypes.data
+        self._chk(self.lib.idc_forward_async_gray(self._h, int(slot), int(n), bits, table, offsets.ctypes.data_as(vp) if offsets is not None else None,
+                                                  ctypes.cast(arr, vp) if arr is not None else None, {"ab": N.IDC_HINT_AB, "rgb": N.IDC_HINT_RGB}[mode],
+                                                  float(mask_value), float(maskcent), float(l_cent), flags,
+                                                  ctypes.byref(block) if block is not None else None, outs,
+                                                  out_ab.ctypes.data_as(vp) if out_ab is not None else None, ctypes.byref(t) if t is not None else None))
+        self._in_flight[int(slot)] = (images, out_rgb, out_ab, res, held, keep)      # the library reads / writes them until the slot's wait
+        return res if res is not None else out_rgb
+
+    def _pinned_planes(self, group):
+        """The planes of a parsed group (``_gray_item``), copied into one pinned pool block; each starts on an even byte."""
+        planes = [g[0] for g in group]
+        blocks = self._pinned_slices([(p.nbytes + 1) // 2 * 2 for p in planes])
+        srcs = [b[:p.nbytes].view(p.dtype).reshape(p.shape) for b, p in zip(blocks, planes)]
+        for s, p in zip(srcs, planes):
+            np.copyto(s, p)
+        return srcs
+
+    def colorize_gray(self, items, batch=None, out="source", depth=8, upsample=None, **kw):
+        """Generator: ``colorize_images`` for greyscale planes (``forward_async_gray``).  An item is ``gray``, ``(gray, hints)`` or
+        ``(gray, hints, ref)``: gray (h,w) uint8 or uint16.  Grouping, slot alternation and order as in ``colorize_images``, and a change of
+        dtype closes the group as a full batch does: a call carries one format.  One array per image is yielded: (h,w,3) [out='source'] or
+        (H,W,3) [out='net'], uint8, or uint16 with ``depth=16`` (uint16 items and out='source' only).  ``upsample``: as in ``colorize_stream``."""
+        if depth not in (8, 16) or (depth == 16 and out != "source"):
+            raise ValueError("depth must be 8, or 16 with out='source'")
+
+        def parse(item):
+            g = _gray_item("colorize_gray", item, True)
+            if depth == 16 and g[0].dtype != np.uint16:
+                raise ValueError("colorize_gray: depth=16 needs uint16 items, got %s" % g[0].dtype)
+            return g
+
+        def submit(slot, group, first):
+            srcs = self._pinned_planes(group)
+            more = dict(kw)
+            if any(g[3] for g in group):
+                more["refs"], more["ref_index"] = dedupe_refs([g[2] for g in group], len(group))
+            return self.forward_async_gray(slot, srcs, [g[1] for g in group], out=out, depth=depth, **more), srcs
+
+        yield from self._two_slot_stream(items, batch, upsample, parse, submit, lambda state: [np.array(r) for r in state[0]],
+                                         key=lambda g: g[0].dtype)
+
+    def suggest_gray(self, items, centres, batch=None, out="source", depth=8, peaks=8, radius=2, skip_hints=True, K=5, N_draws=25000, seed=0,
+                     upsample=None, **kw):
+        """Generator: ``suggest_images`` for greyscale planes -- where to put the next hints on a folder of black-and-white photographs, and
+        in which colours.  An item is ``gray`` or ``(gray, hints)``; it yields ``(rgb, peaks, colours, conf)`` per image as ``suggest_images``
+        does, grouped as ``colorize_gray`` groups."""
+        P = int(peaks)
+        if depth not in (8, 16) or (depth == 16 and out != "source"):
+            raise ValueError("depth must be 8, or 16 with out='source'")
+
+        def parse(item):
+            g = _gray_item("suggest_gray", item, False)
+            if depth == 16 and g[0].dtype != np.uint16:
+                raise ValueError("suggest_gray: depth=16 needs uint16 items, got %s" % g[0].dtype)
+            return g
+
+        def submit(slot, group, first):
+            srcs = self._pinned_planes(group)
+            res = self.forward_async_gray(slot, srcs, [g[1] for g in group], out=out, depth=depth, peaks=P, radius=radius, skip_hints=skip_hints,
+                                          queries="peaks", K=K, N_draws=N_draws, seed=int(seed) + first * P, bin_centres=centres, **kw)
+            return res, srcs
+
+        def finish(state):
+            res, srcs = state
+            K_ = res.sugg_centres.shape[1]
+            sc, sf = np.array(res.sugg_centres).reshape(len(srcs), P, K_, 2), np.array(res.sugg_conf).reshape(len(srcs), P, K_)
+            pk = np.array(res.peaks)
+            return [(np.array(r), pk[i], sc[i], sf[i]) for i, r in enumerate(res.out_rgb)]
+
+        batch = self._group_size(batch)
+        if P < 1:
+            raise ValueError("suggest_gray needs at least one peak per image")
+        yield from self._two_slot_stream(items, batch, upsample, parse, submit, finish, key=lambda g: g[0].dtype)
 
     def colorize_images(self, items, batch=None, out="source", upsample=None, **kw):
         """Generator: colourise a stream of single images of any sizes with both pipeline slots busy.  An item is ``rgb``, ``(rgb, hints)`` or
