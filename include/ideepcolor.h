@@ -488,6 +488,46 @@ int idc_set_image_gray(idc_handle h, int img, int n, int src_h, int src_w, int b
                        double* l_net /*[n,H,W] or NULL*/);
 int idc_fullres_rgb16(idc_handle h, int img, int source, int interp, uint16_t* rgb);   /* kept GRAY16 source, IDC_L_IMAGE */
 
+/* ---- antialiased down-scaling at ingestion: a tent filter stretched by the scale, on the device.  Opt-in: with it off (the default) no
+ *      launch, no plan byte and no output byte of any call changes.  The 4-tap rule above point-samples: a 4000 x 3000 scan on a 256 x 256
+ *      net uses 4 of every ~180 source samples, and grain, halftone screens and fine texture alias straight into the L plane the network sees.
+ *      THE RULE.  One axis has `in` source samples and `out` net samples.  s = (double)in / (double)out.  For output index i:
+ *        s <= 1 (same size or up-scaling): today's two clamped taps t0, t1 and weight w of the ingestion rule.  The weights are (1 - w) and w.
+ *        s > 1:
+ *          c = (i + 0.5) * s
+ *          lo = max(0, (int)(c - s + 0.5))
+ *          hi = min(in, (int)(c + s + 0.5))
+ *          The taps are k = lo .. hi-1.  The window is never empty and holds at most ceil(2 s) + 1 taps: 512 at 16384 -> 64.
+ *          r_k = max(0, 1 - |k + 0.5 - c| / s)
+ *          tot = sum of r_k in ascending k
+ *          weight_k = r_k / tot
+ *        This is the tent filter stretched by the scale.  The window is clipped to the image and renormalised, not replicated.  It is the
+ *        rule of PIL's BILINEAR resize and of torch's interpolate(mode='bilinear', antialias=True).
+ *      Two dimensions, per channel:
+ *        t[x] = sum_y wy * f[y][x]: the vertical sum first, ascending y.
+ *        v = sum_x wx * t[x], ascending x.
+ *        Everything is float64 with contraction off.
+ *        The result is floor(v + 0.5) clamped to the source's own lattice: 0..255 for uint8, 0..65535 for uint16.  That is the rounding of
+ *        today's rule.
+ *      When it applies: to an image only when src_h > H or src_w > W.  An image that is not down-scaled on either axis takes today's
+ *      expressions in today's order.  It is then bit-identical to the filter being off.
+ *      What follows is unchanged: Lab of the rounded net-size image, L - l_cent into the L plane, hints, the network.  The kept source stays
+ *      the original source.  Source-size output takes its L from the original samples exactly as today.
+ *      On the device one pre-pass kernel writes the rounded net-size image of every down-scaled image of a call into scratch the handle or
+ *      the slot owns, and the ingestion kernels read that image at the net's own size, where their rule is the identity: an image's bits do
+ *      not depend on the route, its position or its neighbours.
+ *      idc_set_ingest_filter: IDC_FILTER_BILINEAR (default) or IDC_FILTER_ANTIALIAS; anything else is IDC_ERR_INVALID_ARG and changes
+ *      nothing.  Handle state.  Like idc_set_batch_upsample, the value is copied into the slot when a pipelined call is enqueued: a batch
+ *      in flight keeps what it was enqueued with.  It governs every place the handle brings a source to the net size: idc_set_image_rgb;
+ *      idc_set_image_gray, both widths; idc_forward_async_rgb, _rgb_ref, _images, _eval, _dist, _dist_score and _gray; the references of
+ *      idc_global_stats_rgb, idc_set_global_refs and of a batch's idc_batch_refs.  Everything that derives from the net-size image follows
+ *      it: rgb_net / lab_net / gray_net / l_net, revealed hint colours (idc_reveal_hints on a source kept while the filter was on reads the
+ *      image that ingestion made), the net-size truth of sse, the truth of idc_dist_score, the joint upsampling's guide.
+ *      Left out: any other filter (box, cubic, Lanczos), antialiasing when up-scaling, the sharded engine, and linear-light averaging: the
+ *      filter averages sRGB code values, as every resizer the reference uses does. */
+enum { IDC_FILTER_BILINEAR = 0, IDC_FILTER_ANTIALIAS = 1 };
+int idc_set_ingest_filter(idc_handle h, int filter);
+
 /* ---- pipelined batches from uint8 images: the serving form of the two calls above on the two slots of idc_forward_async.
  *      rgb_in [n,src_h,src_w,3] uint8 and per-image hint lists in, colourised uint8 images out; idc_wait completes the call and
  *      idc_pipeline_times reports its stages (H2D: the images, the offsets and the hints; compute: the prologue kernel, the

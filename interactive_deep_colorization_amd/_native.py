@@ -40,11 +40,13 @@ EXPORTED_SYMBOLS = [
     "idc_gamut_map", "idc_snap_colors",
     "idc_set_joint_upsample", "idc_fullres_ab", "idc_set_batch_upsample",
     "idc_set_image_gray", "idc_fullres_rgb16", "idc_forward_async_gray",
+    "idc_set_ingest_filter",
     "idc_set_range_audit", "idc_range_reset", "idc_range_report", "idc_pack_weights_ex", "idc_load_weights_ex",
 ]
 IDC_STORE_NONE, IDC_STORE_F32, IDC_STORE_BF16, IDC_STORE_F16 = 0, 1, 2, 3
 IDC_INTERP_CUBIC, IDC_INTERP_LINEAR, IDC_INTERP_NEAREST = 0, 1, 2
 IDC_INTERP_JOINT, IDC_JOINT_EPS = 3, 1e-6       # idc_fullres_rgb, idc_fullres_ab, idc_set_batch_upsample
+IDC_FILTER_BILINEAR, IDC_FILTER_ANTIALIAS = 0, 1    # idc_set_ingest_filter
 IDC_SRC_OUTPUT_AB, IDC_SRC_OUTPUT_AB_RAW, IDC_SRC_INPUT_AB, IDC_SRC_NO_AB = 0, 1, 2, 3
 IDC_INGEST_KEEP_SOURCE = 1
 IDC_L_IMAGE, IDC_L_MASK50 = 0, 1
@@ -249,6 +251,7 @@ def load():
     proto("idc_forward_async_gray", ci, [vp, ci, ci, ci, ctypes.POINTER(GrayImage), vp, vp, ci, cf, cf, cf, ctypes.c_uint,
                                          ctypes.POINTER(BatchRefs), ctypes.POINTER(vp), vp, ctypes.POINTER(DistTaps)])
     proto("idc_set_batch_upsample", ci, [vp, ci])
+    proto("idc_set_ingest_filter", ci, [vp, ci])
     proto("idc_set_range_audit", ci, [vp, ci])
     proto("idc_range_reset", ci, [vp])
     proto("idc_range_report", ci, [vp, ci, ctypes.POINTER(RangeInfo)])

@@ -281,6 +281,21 @@ class ColorizeImageBase(object):
     img_l_fullres = _lazy('img_l_fullres', '_refresh_fullres_lab')
     img_ab_fullres = _lazy('img_ab_fullres', '_refresh_fullres_lab')
 
+    def set_ingest_filter(self, name='bilinear'):
+        """How ``load_image_device`` / ``set_image_device`` bring a source to Xd x Xd: 'bilinear' (default, the reference's rule) or
+        'antialias' (``HipColorizer.set_ingest_filter``; on the host route of a source beyond ``Xfullres_max``,
+        ``colorspace.resize_antialias``).  ``load_image`` / ``set_image``, the reference's own methods, are not touched by it."""
+        if name not in ('bilinear', 'antialias'):
+            raise ValueError("set_ingest_filter takes 'bilinear' or 'antialias', got %r" % (name,))
+        self._ingest_filter = name
+        self._apply_ingest_filter()
+
+    def _apply_ingest_filter(self):
+        """Bring the engine's ingest filter to this object's (the engine may have been made after ``set_ingest_filter``)."""
+        name = self.__dict__.get('_ingest_filter', 'bilinear')
+        if self.net_set and hasattr(self.net, 'set_ingest_filter') and getattr(self.net, '_ingest_filter', 'bilinear') != name:
+            self.net.set_ingest_filter(name)
+
     def _ingest_device(self, rgb_fullres):
         """``_ingest`` with the engine doing the work (``HipColorizer.set_image_rgb``): resize to Xd x Xd, rgb2lab and the resident L
         plane in one call, the uint8 source kept on the device for the full-resolution getters.  A source beyond ``Xfullres_max``
@@ -289,6 +304,7 @@ class ColorizeImageBase(object):
             raise RuntimeError('load_image_device / set_image_device need prep_net first, and an engine with set_image_rgb')
         if self.l_norm != 1:
             raise ValueError('device-side ingestion assumes a raw L input (l_norm 1)')
+        self._apply_ingest_filter()
         rgb_net, lab_net = self.net.set_image_rgb(rgb_fullres, img=0, l_cent=self.l_mean, keep_source=True)
         self.img_rgb_fullres = rgb_fullres
         self._fullres_lab_pending = True
@@ -313,6 +329,7 @@ class ColorizeImageBase(object):
             raise ValueError('a single-channel image is (h,w) uint8 or uint16, got %s %s' % (gray.dtype, gray.shape))
         if max(gray.shape) > self.Xfullres_max:
             raise ValueError('a single-channel image beyond Xfullres_max (%d) has no host route: resize it first' % self.Xfullres_max)
+        self._apply_ingest_filter()
         gray_net, l_net = self.net.set_image_gray(gray, img=0, l_cent=self.l_mean, keep_source=True)
         full = 255.0 if gray.dtype == np.uint8 else 65535.0
 
@@ -338,7 +355,8 @@ class ColorizeImageBase(object):
         if full.ndim == 2:
             self._ingest_device_gray(full)
         elif max(full.shape[0], full.shape[1]) > self.Xfullres_max:
-            self._ingest(full.copy(), colorspace.resize_bilinear_u8(full, self.Xd, self.Xd))
+            resize = colorspace.resize_antialias if self.__dict__.get('_ingest_filter') == 'antialias' else colorspace.resize_bilinear_u8
+            self._ingest(full.copy(), resize(full, self.Xd, self.Xd))
         else:
             self._ingest_device(full)
 

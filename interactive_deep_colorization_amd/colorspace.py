@@ -82,6 +82,63 @@ def resize_bilinear_u8(img, out_h, out_w):
     return out if img.ndim == 3 else out[:, :, 0]
 
 
+def _antialias_axis(n_in, n_out):
+    """Taps and weights of one axis of ``resize_antialias``: (idx, wt), both (n_out, K); a row's taps ascend, and the padding at the end of
+    a row shorter than K has weight 0 (adding 0.0 last changes no sum)."""
+    i = np.arange(n_out, dtype=np.float64)
+    s = n_in / float(n_out)
+    if n_in <= n_out:                                   # the two clamped taps of resize_bilinear_u8
+        src = (i + 0.5) * s - 0.5
+        i0 = np.floor(src)
+        w = src - i0
+        i0 = i0.astype(np.int64)
+        idx = np.stack([np.clip(i0, 0, n_in - 1), np.clip(i0 + 1, 0, n_in - 1)], axis=1)
+        return idx, np.stack([1.0 - w, w], axis=1)
+    c = (i + 0.5) * s
+    lo = np.maximum(0, np.trunc(c - s + 0.5).astype(np.int64))
+    hi = np.minimum(n_in, np.trunc(c + s + 0.5).astype(np.int64))
+    k = lo[:, None] + np.arange(int((hi - lo).max()), dtype=np.int64)[None, :]
+    r = np.maximum(0.0, 1.0 - np.abs((k.astype(np.float64) + 0.5) - c[:, None]) / s) * (k < hi[:, None])
+    tot = np.zeros(n_out)
+    for j in range(r.shape[1]):                         # ascending k, one term at a time: numpy's own sum is pairwise
+        tot = tot + r[:, j]
+    return np.minimum(k, n_in - 1), r / tot[:, None]
+
+
+def resize_antialias(img, out_h, out_w):
+    """The host twin of the device's antialiased ingestion (``HipColorizer.set_ingest_filter('antialias')``; the rule:
+    include/ideepcolor.h): a source larger than the target on an axis is filtered with the tent stretched by the scale -- the window
+    clipped to the image and renormalised, the rule of PIL's BILINEAR and of torch's ``interpolate(mode='bilinear', antialias=True)`` -- in
+    float64, the vertical sums first, each in ascending order, then floor(v + .5) clamped to the lattice of the source's dtype.  uint8 or
+    uint16, (h,w) or (h,w,c).  A source that is not down-scaled on either axis takes ``resize_bilinear_u8``'s expressions (on the 16-bit
+    lattice for uint16) and is bit-identical to it."""
+    img = np.asarray(img)
+    if img.dtype not in (np.uint8, np.uint16) or img.ndim not in (2, 3):
+        raise ValueError("resize_antialias needs a uint8 or uint16 (h,w) or (h,w,c) image, got %s %s" % (img.dtype, img.shape))
+    full = 255 if img.dtype == np.uint8 else 65535
+    in_h, in_w = img.shape[:2]
+    f = img if img.ndim == 3 else img[:, :, None]
+    if in_h <= out_h and in_w <= out_w:
+        if img.dtype == np.uint8:
+            return resize_bilinear_u8(img, out_h, out_w)
+        (iy, wy), (ix, wx) = _antialias_axis(in_h, out_h), _antialias_axis(in_w, out_w)
+        g = f.astype(np.float64)
+        wxe, wye = wx[None, :, 1, None], wy[:, 1, None, None]
+        top = g[iy[:, 0]][:, ix[:, 0]] * (1 - wxe) + g[iy[:, 0]][:, ix[:, 1]] * wxe
+        bot = g[iy[:, 1]][:, ix[:, 0]] * (1 - wxe) + g[iy[:, 1]][:, ix[:, 1]] * wxe
+        out = np.floor(top * (1 - wye) + bot * wye + 0.5).clip(0, full).astype(img.dtype)
+        return out if img.ndim == 3 else out[:, :, 0]
+    (iy, wy), (ix, wx) = _antialias_axis(in_h, out_h), _antialias_axis(in_w, out_w)
+    t = np.zeros((out_h, in_w, f.shape[2]))
+    for j in range(iy.shape[1]):                        # t[x] = sum_y wy * f[y][x], ascending y
+        t = t + wy[:, j, None, None] * f[iy[:, j]].astype(np.float64)
+    v = np.zeros((out_h, out_w, f.shape[2]))
+    for j in range(ix.shape[1]):                        # v = sum_x wx * t[x], ascending x
+        v = v + wx[None, :, j, None] * t[:, ix[:, j]]
+    out = np.floor(v + 0.5).clip(0, full).astype(img.dtype)
+    return out if img.ndim == 3 else out[:, :, 0]
+
+
 def imread_rgb(path):
     """``cv2.cvtColor(cv2.imread(path, 1), cv2.COLOR_BGR2RGB)`` -> (H,W,3) uint8 RGB."""
     from PIL import Image

@@ -100,6 +100,7 @@ void drop_source(idc_context* h, int slot) {
     if (slot < 0 || slot >= (int)h->src.size()) return;
     auto& sl = h->src[slot];
     sl.d_rgb.reset();                                    // (freeing waits for the device: nothing that reads it is in flight after that)
+    sl.d_net.reset();
     sl.h = sl.w = 0; sl.gray_bits = 0;
 }
 
@@ -394,8 +395,10 @@ int idc_reveal_hints(idc_handle h, int img, int n_hints, const idc_hint* rects, 
         HIPCHK(h, hipMemcpyAsync(h->d_reveal.get(), orig, (size_t)kept * sizeof(int), hipMemcpyHostToDevice, h->stream.get()));
     }
     if (n_hints) HIPCHK(h, hipMemsetAsync(d_cols, 0, cols_bytes, h->stream.get()));      // a dropped rectangle reports (0, 0)
-    HIPCHK(h, launch_reveal_hints(src.d_rgb.get(), nullptr, nullptr, 1, src.h, src.w, h->H, h->W, h->d_hints.get(), kept, (const int*)h->d_reveal.get(), d_cols,
-                                  h->stream.get()));
+    // a source that was down-scaled under IDC_FILTER_ANTIALIAS reveals the colours of the net-size image that ingestion made (the identity at H x W)
+    const bool aa = src.d_net.get() != nullptr;
+    HIPCHK(h, launch_reveal_hints(aa ? src.d_net.get() : src.d_rgb.get(), nullptr, nullptr, 1, aa ? h->H : src.h, aa ? h->W : src.w, h->H, h->W, h->d_hints.get(),
+                                  kept, (const int*)h->d_reveal.get(), d_cols, h->stream.get()));
     HIPCHK(h, launch_raster_hints(h->d_hints.get(), kept, IDC_HINT_AB, mask_value, h->d_ab.get() + (size_t)img * hw * 2, h->d_mask.get() + (size_t)img * hw,
                                   h->H, h->W, h->stream.get()));
     h->hint_mask_value[img] = mask_value;
@@ -644,9 +647,11 @@ int idc_dist_score(idc_handle h, int n, const idc_dist_score_spec* spec, const f
     HIPCHK(h, h->d_score.ensure(o_out + lay.out_bytes, 65536));
     unsigned char* res = h->d_score.get() + o_out;
     HIPCHK(h, hipMemcpy(h->d_score.get(), centres, (size_t)g.B * 2 * sizeof(float), hipMemcpyHostToDevice));
-    for (int i = 0; i < n; ++i)
-        HIPCHK(h, launch_dist_truth(h->src[i].d_rgb.get(), nullptr, 1, h->src[i].h, h->src[i].w, h->H, h->W, g.s,
-                                    (float*)(res + lay.o_truth) + (size_t)i * 2 * npix, h->stream.get()));
+    for (int i = 0; i < n; ++i) {
+        const bool aa = h->src[i].d_net.get() != nullptr;       // the net-size image an antialiased ingestion made of this source
+        HIPCHK(h, launch_dist_truth(aa ? h->src[i].d_net.get() : h->src[i].d_rgb.get(), nullptr, 1, aa ? h->H : h->src[i].h, aa ? h->W : h->src[i].w, h->H, h->W,
+                                    g.s, (float*)(res + lay.o_truth) + (size_t)i * 2 * npix, h->stream.get()));
+    }
     rc = launch_score(h, g, lay, (const float*)h->d_score.get(), res, h->stream.get());
     if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream.get()));
@@ -812,6 +817,34 @@ static int ensure_ingest_buffers(idc_context* h) {
     return IDC_OK;
 }
 
+// The antialiased pre-pass of a blocking ingestion (the filter is on and the n sources of src_h x src_w are down-scaled: the caller checked).
+// h_src_ptrs[0..n) name the sources on the device, uploaded or on their way on the handle's stream; on return they name the net-size lattice
+// images [H,W,channels] the pre-pass writes instead -- a kept source's in its slot, the others in the handle's scratch -- for the ingestion
+// kernel to read at source size (H, W).  Nothing of the previous call is in flight (the caller synchronised), so the buffers may grow.
+static int antialias_sources(idc_context* h, int img, int n, int src_h, int src_w, int bits, int channels, bool keep) {
+    const size_t net_bytes = (size_t)h->H * h->W * channels * (size_t)(bits / 8);
+    HIPCHK(h, h->d_aa_jobs.ensure((size_t)h->max_batch * sizeof(ResampleJob)));
+    HIPCHK(h, h->h_aa_jobs.ensure((size_t)h->max_batch * sizeof(ResampleJob)));
+    if (!keep) HIPCHK(h, h->d_aa.ensure((size_t)n * net_bytes));
+    ResampleJob* jobs = (ResampleJob*)h->h_aa_jobs.get();
+    int tiles = 0;
+    for (int i = 0; i < n; ++i) {
+        unsigned char* dst = nullptr;
+        if (keep) {
+            HIPCHK(h, h->src[img + i].d_net.ensure(net_bytes));
+            dst = h->src[img + i].d_net.get();
+        } else {
+            dst = h->d_aa.get() + (size_t)i * net_bytes;
+        }
+        jobs[i] = resample_job((long long)(uintptr_t)h->h_src_ptrs.get()[i], (long long)(uintptr_t)dst, src_h, src_w, h->W, channels);
+        tiles = tiles > jobs[i].tiles ? tiles : jobs[i].tiles;
+        h->h_src_ptrs.get()[i] = dst;
+    }
+    HIPCHK(h, hipMemcpyAsync(h->d_aa_jobs.get(), jobs, (size_t)n * sizeof(ResampleJob), hipMemcpyHostToDevice, h->stream.get()));
+    HIPCHK(h, launch_resample(nullptr, nullptr, (const ResampleJob*)h->d_aa_jobs.get(), n, tiles, bits, channels, h->H, h->W, h->stream.get()));
+    return IDC_OK;
+}
+
 int idc_set_image_rgb(idc_handle h, int img, int n, int src_h, int src_w, const uint8_t* rgb, float l_cent, unsigned flags,
                       uint8_t* rgb_net, double* lab_net) {
     if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
@@ -847,9 +880,14 @@ int idc_set_image_rgb(idc_handle h, int img, int n, int src_h, int src_w, const 
         if (in_pinned) HIPCHK(h, hipMemcpyAsync(dst, rgb + (size_t)i * sb, sb, hipMemcpyHostToDevice, h->stream.get()));
         else HIPCHK(h, hipMemcpy(dst, rgb + (size_t)i * sb, sb, hipMemcpyHostToDevice));
     }
+    const bool aa = h->ingest_filter == IDC_FILTER_ANTIALIAS && resample_applies(src_h, src_w, h->H, h->W);
+    if (aa) {
+        rc = antialias_sources(h, img, n, src_h, src_w, 8, 3, keep);
+        if (rc) return rc;
+    }
     HIPCHK(h, hipMemcpyAsync((void*)h->d_src_ptrs.get(), (const void*)h->h_src_ptrs.get(), (size_t)n * sizeof(void*), hipMemcpyHostToDevice, h->stream.get()));
-    HIPCHK(h, launch_ingest_rgb(h->d_src_ptrs.get(), n, src_h, src_w, h->H, h->W, l_cent, h->d_L.get() + (size_t)img * hw, rgb_net ? h->d_net_rgb.get() : nullptr,
-                                lab_net ? h->d_net_lab.get() : nullptr, h->stream.get()));
+    HIPCHK(h, launch_ingest_rgb(h->d_src_ptrs.get(), n, aa ? h->H : src_h, aa ? h->W : src_w, h->H, h->W, l_cent, h->d_L.get() + (size_t)img * hw,
+                                rgb_net ? h->d_net_rgb.get() : nullptr, lab_net ? h->d_net_lab.get() : nullptr, h->stream.get()));
     const bool rgb_direct = rgb_net && is_pinned(rgb_net), lab_direct = lab_net && is_pinned(lab_net);
     if (rgb_direct) HIPCHK(h, hipMemcpyAsync(rgb_net, h->d_net_rgb.get(), (size_t)n * hw * 3, hipMemcpyDeviceToHost, h->stream.get()));
     if (lab_direct) HIPCHK(h, hipMemcpyAsync(lab_net, h->d_net_lab.get(), (size_t)n * hw * 3 * 8, hipMemcpyDeviceToHost, h->stream.get()));
@@ -900,8 +938,13 @@ int idc_set_image_gray(idc_handle h, int img, int n, int src_h, int src_w, int b
         if (in_pinned) HIPCHK(h, hipMemcpyAsync(dst, in + (size_t)i * sb, sb, hipMemcpyHostToDevice, h->stream.get()));
         else HIPCHK(h, hipMemcpy(dst, in + (size_t)i * sb, sb, hipMemcpyHostToDevice));
     }
+    const bool aa = h->ingest_filter == IDC_FILTER_ANTIALIAS && resample_applies(src_h, src_w, h->H, h->W);
+    if (aa) {
+        rc = antialias_sources(h, img, n, src_h, src_w, bits, 1, keep);
+        if (rc) return rc;
+    }
     HIPCHK(h, hipMemcpyAsync((void*)h->d_src_ptrs.get(), (const void*)h->h_src_ptrs.get(), (size_t)n * sizeof(void*), hipMemcpyHostToDevice, h->stream.get()));
-    HIPCHK(h, launch_ingest_gray((const void* const*)h->d_src_ptrs.get(), bits, n, src_h, src_w, h->H, h->W, l_cent, h->d_L.get() + (size_t)img * hw,
+    HIPCHK(h, launch_ingest_gray((const void* const*)h->d_src_ptrs.get(), bits, n, aa ? h->H : src_h, aa ? h->W : src_w, h->H, h->W, l_cent, h->d_L.get() + (size_t)img * hw,
                                  gray_net ? h->d_net_rgb.get() : nullptr, l_net ? h->d_net_lab.get() : nullptr, h->stream.get()));
     const bool net_direct = gray_net && is_pinned(gray_net), l_direct = l_net && is_pinned(l_net);
     if (net_direct) HIPCHK(h, hipMemcpyAsync(gray_net, h->d_net_rgb.get(), (size_t)n * hw * sz, hipMemcpyDeviceToHost, h->stream.get()));
@@ -1014,6 +1057,14 @@ int idc_set_batch_upsample(idc_handle h, int interp) {
     if (interp != IDC_INTERP_LINEAR && interp != IDC_INTERP_JOINT)
         return fail(&h->err, IDC_ERR_INVALID_ARG, "interp %d is neither IDC_INTERP_LINEAR nor IDC_INTERP_JOINT", interp);
     h->batch_interp = interp;
+    return IDC_OK;
+}
+
+int idc_set_ingest_filter(idc_handle h, int filter) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (filter != IDC_FILTER_BILINEAR && filter != IDC_FILTER_ANTIALIAS)
+        return fail(&h->err, IDC_ERR_INVALID_ARG, "filter %d is neither IDC_FILTER_BILINEAR nor IDC_FILTER_ANTIALIAS", filter);
+    h->ingest_filter = filter;
     return IDC_OK;
 }
 

@@ -49,6 +49,8 @@ struct BatchCall {
     // the sample width and the output depth (idc_forward_async_gray; ragged only): gray_bits 0 = [h,w,3] uint8 RGB in `images`, 8 | 16 = one
     // plane [h,w] of uint8 | uint16 in `grays`; out_bits 8 | 16 = [.,.,3] uint8 | uint16 out
     int gray_bits = 0, out_bits = 8; const idc_gray_image* grays = nullptr;
+    // the handle's ingest filter as the call was enqueued (idc_set_ingest_filter): IDC_FILTER_BILINEAR leaves every byte of the plan as it was
+    int ingest_filter = IDC_FILTER_BILINEAR;
 };
 
 // image i of a ragged call, whichever table it came in (a plane's samples stand in the place of the bytes)
@@ -78,6 +80,15 @@ struct BatchPlan {
     int bpp_in = 3, bpp_out = 3;         // bytes per pixel of the packed sources (1, 2 or 3) and of the packed source-size results (3 or 6)
     std::vector<Piece> pieces;           // in_pinned / out_pinned: the caller's to fill in (a runtime query); out_pinned without want_rgb: true
     bool ab_pinned = false;              // ... and so is this one, of out_ab
+    // antialiased ingestion: naa = the images of the call the pre-pass down-scales (0: the filter is off or no image is larger than the net, and
+    // everything above is the whole plan).  Their net-size lattice images [H,W] of bpp_in bytes per pixel lie behind the packed sources in the
+    // SAME device array, image k of them at byte aa_at + k * H * W * bpp_in (aa_at is a multiple of 48: a whole number of samples of every
+    // format); src_bytes = what that array holds then.  Appended to the metadata block, behind today's: (ragged) the ingestion view
+    // ImgDesc[max_batch + 1] at view_at -- the table with every down-scaled image's entry pointing at its net-size image as an H x W source,
+    // the others and the closing entry as they are: what the kernels that bring a source to the net size read -- and the pre-pass's
+    // ResampleJob[naa] at jobs_at.  aa_tiles = the largest tile count among the jobs.
+    int naa = 0, aa_tiles = 0;
+    size_t aa_at = 0, src_bytes = 0, view_at = 0, jobs_at = 0;
 };
 
 inline int plan_fail(std::string* err, int code, const char* fmt, ...) {
@@ -180,6 +191,23 @@ inline int plan_batch(const BatchCall& c, int H, int W, int max_batch, BatchPlan
         p->max_tiles = joint_tiles(c.src_h, c.src_w);
         p->max_pixels = (long long)c.src_h * c.src_w;
     }
+    p->src_bytes = p->in_bytes;
+    if (c.ingest_filter == IDC_FILTER_ANTIALIAS) {
+        for (int i = 0; i < n; ++i) {
+            const int ih = c.ragged ? batch_image(c, i).h : c.src_h, iw = c.ragged ? batch_image(c, i).w : c.src_w;
+            if (!resample_applies(ih, iw, H, W)) continue;
+            const int tiles = resample_tile_count(W, resample_tile_width(iw, W, gray ? 1 : 3));
+            p->aa_tiles = p->aa_tiles > tiles ? p->aa_tiles : tiles;
+            ++p->naa;
+        }
+    }
+    if (p->naa > 0) {
+        p->aa_at = (p->in_bytes + 47) / 48 * 48;
+        p->src_bytes = p->aa_at + (size_t)p->naa * hw * p->bpp_in;
+        p->view_at = batch_align16(p->meta_bytes);
+        p->jobs_at = c.ragged ? p->view_at + batch_align16((nb + 1) * sizeof(ImgDesc)) : p->view_at;
+        p->meta_bytes = p->jobs_at + (size_t)p->naa * sizeof(ResampleJob);
+    }
     return IDC_OK;
 }
 
@@ -206,6 +234,22 @@ inline void fill_batch_meta(const BatchCall& c, const BatchPlan& p, int H, int W
             m_hints[w++] = r;
         }
         m_offs[i + 1] = w;
+    }
+    if (p.naa > 0) {                                // the pre-pass's jobs and (ragged) the ingestion view, behind everything above
+        const size_t net_bytes = (size_t)H * W * p.bpp_in;
+        ResampleJob* jobs = (ResampleJob*)(h_meta + p.jobs_at);
+        ImgDesc* view = c.ragged ? (ImgDesc*)(h_meta + p.view_at) : nullptr;
+        const ImgDesc* tab = c.ragged ? (const ImgDesc*)(h_meta + p.table_at) : nullptr;
+        if (view) view[c.n] = tab[c.n];
+        for (int i = 0, k = 0; i < c.n; ++i) {
+            const int ih = c.ragged ? tab[i].h : c.src_h, iw = c.ragged ? tab[i].w : c.src_w;
+            const size_t at = c.ragged ? (size_t)tab[i].off : (size_t)i * c.src_h * c.src_w * 3;
+            if (view) view[i] = tab[i];
+            if (!resample_applies(ih, iw, H, W)) continue;
+            const size_t dst = p.aa_at + (size_t)k * net_bytes;
+            jobs[k++] = resample_job((long long)at, (long long)dst, ih, iw, W, c.gray_bits ? 1 : 3);
+            if (view) { view[i].off = (long long)dst; view[i].first = (long long)(dst / p.bpp_in); view[i].h = H; view[i].w = W; }
+        }
     }
 }
 

@@ -201,10 +201,17 @@ struct idc_context {
     // and its size, and the mask_value of the slot's last idc_set_hints (0 = never had hints)
     // ... and the l_cent of that ingestion: with the slot's L plane it is the guide of the joint upsampling (a source is resident only while that plane is intact)
     // ... and its format: gray_bits 0 = [h,w,3] uint8 RGB (idc_set_image_rgb), 8 | 16 = one plane [h,w] of uint8 | uint16 (idc_set_image_gray)
-    struct SlotSource { DevMem<unsigned char> d_rgb; int h = 0, w = 0; float l_cent = 0.f; int gray_bits = 0; };
+    // ... and, for a source that was down-scaled while the ingest filter was IDC_FILTER_ANTIALIAS, the net-size lattice image [H,W,3] / [H,W] the
+    // pre-pass made of it (empty otherwise): what idc_reveal_hints and idc_dist_score read in place of the source
+    struct SlotSource { DevMem<unsigned char> d_rgb, d_net; int h = 0, w = 0; float l_cent = 0.f; int gray_bits = 0; };
     std::vector<SlotSource> src;
     std::vector<float> hint_mask_value;
     DevMem<unsigned char> d_ingest;                                  // upload buffer of the sources that are not kept
+    // antialiased ingestion (idc_set_ingest_filter; a pipelined call takes its copy when it is enqueued): the net-size images of a blocking call's
+    // sources that are not kept, and the ResampleJob table of one pre-pass launch, device and pinned
+    int ingest_filter = 0;               // IDC_FILTER_BILINEAR
+    DevMem<unsigned char> d_aa, d_aa_jobs;
+    PinnedMem<unsigned char> h_aa_jobs;
     DevMem<const unsigned char*> d_src_ptrs;                         // [max_batch] source pointers of one ingest launch ...
     PinnedMem<const unsigned char*> h_src_ptrs;                      // ... and their pinned host copy
     DevMem<unsigned char> d_net_rgb; DevMem<double> d_net_lab;       // idc_set_image_rgb results [max_batch,H,W,3] u8, [max_batch,3,H,W] f64 (first use)
@@ -234,6 +241,7 @@ struct idc_context {
         Event ev_in0, ev_comp0, ev_out0;                                               // stage starts (idc_pipeline_times)
         bool pending = false, timed = false;
         int up_interp = 1; JointParams up_joint = {2, 2.0, 128.0};                     // the source-size upsampling the batch in flight was enqueued with
+        int ingest_filter = 0;                                                         // ... and the ingest filter
         // what idc_wait still has to copy to a pageable destination of the batch in flight: `bytes` from the slot's pinned memory, where the
         // copy-out stream left them (one entry per pageable buffer of the call, whatever it holds; a pinned destination was written in place)
         struct StagedOut { void* user; const void* pinned; size_t bytes; };
@@ -329,6 +337,11 @@ struct RefLayout {
     int n = 0, m = 0;                    // images that take a row (0: idc_global_stats_rgb), references
     size_t o_index = 0, o_centres = 0, o_packed = 0, in_bytes = 0, ref_bytes = 0;
     size_t o_sat = 0, o_hist = 0, o_savg = 0, work_bytes = 0;
+    // antialiased ingestion (check_refs with the handle's filter on and at least one down-scaled reference; naa = 0 otherwise, and every byte
+    // above is today's): the ResampleJob table [naa] at o_jobs, behind the packed references and uploaded with them, and the net-size images
+    // [naa,H,W,3] the pre-pass writes at o_aa of the same device block (never uploaded); the RefDesc of such a reference points there
+    int naa = 0, aa_tiles = 0;
+    size_t o_jobs = 0, o_aa = 0, up_bytes = 0, dev_bytes = 0;
 };
 // every check of the reference arguments (include/ideepcolor.h's table), on the host, before anything is allocated or enqueued; m_min = 0 or 1
 int check_refs(idc_context* c, int m_min, int n, int m, const idc_ref_image* refs, const int32_t* ref_index, const float* centres,

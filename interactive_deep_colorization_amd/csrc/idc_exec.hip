@@ -405,6 +405,20 @@ int check_refs(idc_context* c, int m_min, int n, int m, const idc_ref_image* ref
     lay->o_centres = lay->o_index + align_up(nn * sizeof(int), 16);
     lay->o_packed = lay->o_centres + align_up(626 * sizeof(float), 16);
     lay->in_bytes = lay->o_packed + bytes;
+    lay->up_bytes = lay->dev_bytes = lay->in_bytes;
+    if (c->ingest_filter == IDC_FILTER_ANTIALIAS)         // the handle's setting as it is now; a reference no larger than the net keeps today's rule
+        for (int r = 0; r < m; ++r) {
+            if (!resample_applies(refs[r].h, refs[r].w, c->H, c->W)) continue;
+            const int tiles = resample_tile_count(c->W, resample_tile_width(refs[r].w, c->W, 3));
+            lay->aa_tiles = lay->aa_tiles > tiles ? lay->aa_tiles : tiles;
+            ++lay->naa;
+        }
+    if (lay->naa > 0) {
+        lay->o_jobs = align_up(lay->in_bytes, 16);
+        lay->up_bytes = lay->o_jobs + (size_t)lay->naa * sizeof(ResampleJob);
+        lay->o_aa = align_up(lay->up_bytes, 16);
+        lay->dev_bytes = lay->o_aa + (size_t)lay->naa * c->H * c->W * 3;
+    }
     lay->o_sat = align_up(mm * 313 * sizeof(unsigned), 16);
     lay->o_hist = lay->o_sat + align_up(mm * G * sizeof(double), 16);
     lay->o_savg = lay->o_hist + align_up(mm * 313 * sizeof(float), 16);
@@ -414,17 +428,24 @@ int check_refs(idc_context* c, int m_min, int n, int m, const idc_ref_image* ref
 
 int stage_refs(idc_context* c, idc_context::RefStage& st, const RefLayout& lay, const idc_ref_image* refs, const int32_t* ref_index,
                const float* centres, bool want_results) {
-    HIPCHK(c, st.h_in.ensure(lay.in_bytes, 65536));
-    HIPCHK(c, st.d_in.ensure(lay.in_bytes, 65536));
+    HIPCHK(c, st.h_in.ensure(lay.up_bytes, 65536));
+    HIPCHK(c, st.d_in.ensure(lay.dev_bytes, 65536));
     HIPCHK(c, st.d_work.ensure(lay.work_bytes, 65536));
     if (want_results) HIPCHK(c, st.h_res.ensure(lay.work_bytes - lay.o_hist, 65536));
     unsigned char* base = st.h_in.get();
     RefDesc* tab = (RefDesc*)base;
+    ResampleJob* jobs = (ResampleJob*)(base + lay.o_jobs);
+    const size_t net_bytes = (size_t)c->H * c->W * 3;
     size_t off = 0;
-    for (int r = 0; r < lay.m; ++r) {
+    for (int r = 0, k = 0; r < lay.m; ++r) {
         const size_t sb = (size_t)refs[r].h * refs[r].w * 3;
         tab[r].off = (long long)off; tab[r].h = refs[r].h; tab[r].w = refs[r].w;
         memcpy(base + lay.o_packed + off, refs[r].rgb, sb);
+        if (lay.naa > 0 && resample_applies(refs[r].h, refs[r].w, c->H, c->W)) {   // the statistics read the net-size image the pre-pass makes of it
+            const size_t dst = lay.o_aa + (size_t)k * net_bytes;
+            jobs[k++] = resample_job((long long)(lay.o_packed + off), (long long)dst, refs[r].h, refs[r].w, c->W, 3);
+            tab[r].off = (long long)dst - (long long)lay.o_packed; tab[r].h = c->H; tab[r].w = c->W;
+        }
         off += sb;
     }
     int* idx = (int*)(base + lay.o_index);
@@ -435,7 +456,7 @@ int stage_refs(idc_context* c, idc_context::RefStage& st, const RefLayout& lay, 
 
 int upload_refs(idc_context* c, idc_context::RefStage& st, const RefLayout& lay, hipStream_t copy) {
     // without references only the index travels (every entry -1): the table, the centres and the packed section are not read
-    const size_t bytes = lay.m > 0 ? lay.in_bytes : lay.o_centres;
+    const size_t bytes = lay.m > 0 ? lay.up_bytes : lay.o_centres;
     HIPCHK(c, hipMemcpyAsync(st.d_in.get(), st.h_in.get(), bytes, hipMemcpyHostToDevice, copy));
     return IDC_OK;
 }
@@ -448,6 +469,8 @@ int launch_refs(idc_context* c, idc_context::RefStage& st, const RefLayout& lay,
     double* sat = (double*)(work + lay.o_sat);
     if (lay.m > 0) {
         HIPCHK(c, hipMemsetAsync(counts, 0, (size_t)lay.m * 313 * sizeof(unsigned), s));
+        if (lay.naa > 0)
+            HIPCHK(c, launch_resample(in, in, (const ResampleJob*)(in + lay.o_jobs), lay.naa, lay.aa_tiles, 8, 3, c->H, c->W, s));
         HIPCHK(c, launch_ref_stats((const RefDesc*)in, lay.m, in + lay.o_packed, (const float*)(in + lay.o_centres), c->H, c->W, counts, sat, s));
     }
     HIPCHK(c, launch_glob_rows(counts, sat, (const int*)(in + lay.o_index), lay.n, lay.m, c->H, c->W, hist_flag, (ref_flags & IDC_REF_SATURATION) ? 1 : 0,
@@ -672,7 +695,7 @@ static int batch_handle_checks(idc_context* h, const BatchCall& c, const BatchPl
 // larger ones (the reference stage grows in stage_refs)
 static int batch_reserve(idc_context* h, const BatchCall& c, const BatchPlan& p, const BatchLayouts& L, Slot& sl) {
     const size_t hw = (size_t)h->H * h->W, nb = (size_t)h->max_batch;
-    HIPCHK(h, sl.d_src.ensure(p.in_bytes));
+    HIPCHK(h, sl.d_src.ensure(p.src_bytes));       // the packed sources and, behind them, the net-size images of an antialiased call
     HIPCHK(h, sl.d_meta.ensure(p.meta_bytes, p.meta_floor));
     HIPCHK(h, sl.h_meta.ensure(p.meta_bytes, p.meta_floor));
     HIPCHK(h, sl.d_rgb.ensure(nb * hw * 3));
@@ -735,10 +758,13 @@ static int batch_copy_in(idc_context* h, const BatchCall& c, const BatchPlan& p,
 }
 
 // the device's view of the slot's metadata block
-struct BatchMeta { const int* offs; HintRect* hints; const ImgDesc* tab; const int* orig; };
+// (view: the table for the kernels that bring a source to the net size -- the ingestion view of an antialiased ragged call, else tab itself)
+struct BatchMeta { const int* offs; HintRect* hints; const ImgDesc* tab; const int* orig; const ImgDesc* view; const ResampleJob* jobs; };
 static BatchMeta batch_meta(const BatchPlan& p, Slot& sl) {
     unsigned char* m = sl.d_meta.get();
-    return {p.kept ? (const int*)m : nullptr, (HintRect*)(m + p.hints_at), (const ImgDesc*)(m + p.table_at), (const int*)(m + p.orig_at)};
+    const bool has_view = p.naa > 0 && p.jobs_at != p.view_at;
+    return {p.kept ? (const int*)m : nullptr, (HintRect*)(m + p.hints_at), (const ImgDesc*)(m + p.table_at), (const int*)(m + p.orig_at),
+            (const ImgDesc*)(m + (has_view ? p.view_at : p.table_at)), (const ResampleJob*)(m + p.jobs_at)};
 }
 
 // compute stream, first half: [global inputs from the references] [revealed colours] prologue, network, Lab -> RGB, [the source-size image]
@@ -751,21 +777,25 @@ static int batch_colourise(idc_context* h, const BatchCall& c, const BatchPlan& 
         const int rc = launch_refs(h, sl.ref, L.ref, c.refs.hist_flag, c.refs.flags, sl.d_glob_in.get(), false, s);
         if (rc) return rc;
     }
+    // antialiased ingestion: the net-size images of the down-scaled sources, behind the packed sources; a same-size call then reads them as its sources
+    if (p.naa > 0)
+        HIPCHK(h, launch_resample(sl.d_src.get(), sl.d_src.get(), m.jobs, p.naa, p.aa_tiles, c.gray_bits ? c.gray_bits : 8, c.gray_bits ? 1 : 3, h->H, h->W, s));
+    sl.ingest_filter = c.ingest_filter;
     int mode = c.mode;
     if (p.reveal) {   // the colours of the list the prologue is about to read; a dropped rectangle's (0, 0) is the memset's
         float* d_cols = p.cols_bytes ? (float*)(sl.d_eval.get() + p.cols_at) : nullptr;
         if (p.cols_bytes) HIPCHK(h, hipMemsetAsync(d_cols, 0, p.cols_bytes, s));
-        HIPCHK(h, launch_reveal_hints(sl.d_src.get(), m.tab, m.offs, n, 0, 0, h->H, h->W, m.hints, p.kept, m.orig, d_cols, s));
+        HIPCHK(h, launch_reveal_hints(sl.d_src.get(), m.view, m.offs, n, 0, 0, h->H, h->W, m.hints, p.kept, m.orig, d_cols, s));
         mode = IDC_HINT_AB;
     }
     if (c.gray_bits)
-        HIPCHK(h, launch_ragged_gray_prologue(sl.d_src.get(), c.gray_bits, m.tab, n, h->H, h->W, c.l_cent, m.offs, m.hints, mode, c.mask_value, sl.d_L.get(),
+        HIPCHK(h, launch_ragged_gray_prologue(sl.d_src.get(), c.gray_bits, m.view, n, h->H, h->W, c.l_cent, m.offs, m.hints, mode, c.mask_value, sl.d_L.get(),
                                               sl.d_ab.get(), sl.d_mask.get(), s));
     else if (c.ragged)
-        HIPCHK(h, launch_ragged_prologue(sl.d_src.get(), m.tab, n, h->H, h->W, c.l_cent, m.offs, m.hints, mode, c.mask_value, sl.d_L.get(), sl.d_ab.get(),
+        HIPCHK(h, launch_ragged_prologue(sl.d_src.get(), m.view, n, h->H, h->W, c.l_cent, m.offs, m.hints, mode, c.mask_value, sl.d_L.get(), sl.d_ab.get(),
                                          sl.d_mask.get(), s));
     else
-        HIPCHK(h, launch_batch_prologue(sl.d_src.get(), n, c.src_h, c.src_w, h->H, h->W, c.l_cent, m.offs, m.hints, mode, c.mask_value, sl.d_L.get(),
+        HIPCHK(h, launch_batch_prologue(sl.d_src.get() + p.aa_at, n, p.naa ? h->H : c.src_h, p.naa ? h->W : c.src_w, h->H, h->W, c.l_cent, m.offs, m.hints, mode, c.mask_value, sl.d_L.get(),
                                         sl.d_ab.get(), sl.d_mask.get(), s));
     const int dist_n = h->dist_n;
     // a distribution batch runs model_class into the HANDLE's distribution (the 313 head with idc_keep_dist writes dist_S on every forward anyway)
@@ -807,7 +837,7 @@ static int batch_measure(idc_context* h, const BatchCall& c, const BatchPlan& p,
         if (p.source_out) {
             HIPCHK(h, launch_eval_sse(sl.d_full.get(), sl.d_src.get(), m.tab, n, 0, p.max_pixels, (long long)(p.in_bytes / 3), d_sse, s));
         } else {
-            HIPCHK(h, launch_ragged_net_truth(sl.d_src.get(), m.tab, n, h->H, h->W, sl.d_truth.get(), s));
+            HIPCHK(h, launch_ragged_net_truth(sl.d_src.get(), m.view, n, h->H, h->W, sl.d_truth.get(), s));
             HIPCHK(h, launch_eval_sse(sl.d_rgb.get(), sl.d_truth.get(), nullptr, n, (long long)hw, (long long)hw, (long long)n * hw, d_sse, s));
         }
     }
@@ -816,7 +846,7 @@ static int batch_measure(idc_context* h, const BatchCall& c, const BatchPlan& p,
         if (rc) return rc;
     }
     if (p.score) {    // behind the other taps: the cells' ground truth from the slot's own packed sources, then the score
-        HIPCHK(h, launch_dist_truth(sl.d_src.get(), m.tab, n, 0, 0, h->H, h->W, L.geom.s, (float*)(sl.d_score.get() + L.score.o_truth), s));
+        HIPCHK(h, launch_dist_truth(sl.d_src.get(), m.view, n, 0, 0, h->H, h->W, L.geom.s, (float*)(sl.d_score.get() + L.score.o_truth), s));
         const int rc = launch_score(h, L.geom, L.score, (const float*)sl.d_score_in.get(), sl.d_score.get(), s);
         if (rc) return rc;
     }
@@ -877,9 +907,11 @@ static int batch_copy_out(idc_context* h, const BatchCall& c, const BatchPlan& p
 
 // handle state -> plan_batch -> handle-dependent checks | reserve -> stage -> copy-in -> compute -> copy-out -> commit.  Left of the bar nothing
 // is allocated, written or enqueued, and for any argument list the first check that refuses it is the one include/ideepcolor.h's tables name
-static int forward_async_rgb(idc_handle h, const BatchCall& c) {
-    int rc = check_forward_args(h, c.n);
+static int forward_async_rgb(idc_handle h, const BatchCall& call) {
+    int rc = check_forward_args(h, call.n);
     if (rc) return rc;
+    BatchCall c = call;
+    c.ingest_filter = h->ingest_filter;       // the handle's setting as it is now: a later idc_set_ingest_filter does not reach this batch
     BatchPlan p;
     std::string why;
     rc = plan_batch(c, h->H, h->W, h->max_batch, &p, &why);

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "idc_grid.h"
+#include "idc_resample.h"
 
 namespace idc {
 
@@ -346,6 +347,12 @@ hipError_t launch_ragged_gray_prologue(const void* src, int bits, const ImgDesc*
                                        const HintRect* hints, int mode, float mask_value, float* Lp, float* ab, float* mask, hipStream_t s);
 hipError_t launch_ragged_gray_fullres(const void* src, int bits, const ImgDesc* imgs, int n, long long total, const double* lab_q, int H, int W,
                                       int interp, void* rgb, int out_bits, hipStream_t s);
+
+// Antialiased ingestion (idc_set_ingest_filter; idc_resample.hip; the rule: include/ideepcolor.h): the pre-pass that writes the net-size lattice
+// image [H,W,channels] of each of the njobs down-scaled images (ResampleJob, idc_resample.h: byte offsets from src_base / dst_base, the image's
+// own tiling) -- uint8 x 3, uint8 x 1 or uint16 x 1.  Exact grid dim3(max_tiles, H, njobs), max_tiles = the largest jobs[.].tiles.
+hipError_t launch_resample(const void* src_base, void* dst_base, const ResampleJob* jobs, int njobs, int max_tiles, int bits, int channels, int H,
+                           int W, hipStream_t s);
 
 // Evaluation batches (idc_reveal_hints / idc_forward_async_eval; idc_colour.hip).  reveal_hints: (c0, c1) of each of the n_rects clipped
 // rectangles of `hints` = the float64 mean ab (rounded once to fp32) of its image's net-size pixels under it, one workgroup per rectangle, fixed

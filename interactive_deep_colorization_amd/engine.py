@@ -21,6 +21,7 @@ _PREC = {"fp32": N.IDC_FP32, "f32": N.IDC_FP32, "float32": N.IDC_FP32, 0: N.IDC_
 
 
 _INTERP = {"cubic": N.IDC_INTERP_CUBIC, "linear": N.IDC_INTERP_LINEAR, "nearest": N.IDC_INTERP_NEAREST, "joint": N.IDC_INTERP_JOINT}
+_INGEST_FILTER = {"bilinear": N.IDC_FILTER_BILINEAR, "antialias": N.IDC_FILTER_ANTIALIAS}
 
 
 def _fptr(a):
@@ -500,6 +501,7 @@ class HipColorizer(object):
         self._src_shape = {}                # image slot -> (h, w) of the source set_image_rgb(keep_source=True) left on the device
         self.before_overwrite = None        # callable run ONCE right before the next such call: whoever still wants the resident results fetches them
         self._batch_upsample = "linear"     # what set_batch_upsample last set: the source-size upsampling of the pipelined calls
+        self._ingest_filter = "bilinear"    # what set_ingest_filter last set: how every source is brought to the net size
 
     # ---- lifetime -------------------------------------------------------------------------
     def close(self):
@@ -651,7 +653,8 @@ class HipColorizer(object):
 
     def set_image_rgb(self, rgb, img=0, l_cent=50., keep_source=False, want_rgb=True, want_lab=True):
         """Ingest uint8 RGB image(s) on the device (``idc_set_image_rgb``): rgb (h,w,3) or (n,h,w,3), any size up to 16384 a side, go to
-        slots img..img+n-1 -- bilinear resize to the net size (``colorspace.resize_bilinear_u8``'s rule; none at the net size), rgb2lab,
+        slots img..img+n-1 -- bilinear resize to the net size (``colorspace.resize_bilinear_u8``'s rule; none at the net size; with
+        ``set_ingest_filter('antialias')`` a source larger than the net on an axis takes ``colorspace.resize_antialias``'s), rgb2lab,
         and the slot's resident plane becomes L - l_cent, as after ``set_image_l``.  Returns (rgb_net (n,H,W,3) uint8 | None,
         lab_net (n,3,H,W) float64 | None).  ``keep_source``: the source stays on the device for ``fullres_rgb``."""
         rgb = np.ascontiguousarray(np.asarray(rgb), dtype=np.uint8)
@@ -786,6 +789,23 @@ class HipColorizer(object):
             return None
         prev = self._batch_upsample
         self.set_batch_upsample(upsample)
+        return prev
+
+    def set_ingest_filter(self, name="bilinear"):
+        """How every entry point brings a source to the net size (``idc_set_ingest_filter``): 'bilinear' (default: the reference's
+        point-sampled 4-tap rule) or 'antialias' (a tent filter stretched by the scale, for sources larger than the net on an axis; the host
+        twin is ``colorspace.resize_antialias``).  Handle state; a batch in flight keeps what it was enqueued with."""
+        if name not in _INGEST_FILTER:
+            raise ValueError("set_ingest_filter takes 'bilinear' or 'antialias', got %r" % (name,))
+        self._chk(self.lib.idc_set_ingest_filter(self._h, _INGEST_FILTER[name]))
+        self._ingest_filter = name
+
+    def _ingest_scope(self, ingest):
+        """The ``ingest=`` keyword of the streaming generators: set the state now, return what to restore (None: leave it alone)."""
+        if ingest is None:
+            return None
+        prev = self._ingest_filter
+        self.set_ingest_filter(ingest)
         return prev
 
     # ---- colour picker (data/lab_gamut.py): no weights needed, nothing resident is read or written ---------
@@ -1151,7 +1171,7 @@ class HipColorizer(object):
                                                                    _fptr(c) if c is not None else None, hist_flag, rflags) + tail)))
         self._in_flight[int(slot)] = (rgb, out_rgb, out_ab)      # the library reads / writes them until the slot's wait
 
-    def colorize_stream(self, batches, out="net", upsample=None, **kw):
+    def colorize_stream(self, batches, out="net", upsample=None, ingest=None, **kw):
         """Generator: colourise a stream of uint8 batches with both pipeline slots busy.  ``batches`` yields (rgb (n,h,w,3) uint8, hints) items
         (``hints`` as in ``forward_async_rgb``; n and the source size may change from item to item); each item's (n,H,W,3) [out='net'] or
         (n,h,w,3) [out='source'] uint8 result is yielded in input order, as an array of the caller's own (copied out of the pinned buffer the
@@ -1161,7 +1181,8 @@ class HipColorizer(object):
         reference photograph for that image.  The same array OBJECT given for several images of an item is uploaded once (``dedupe_refs``);
         ``kw`` then also carries centres (needed), hist_flag and saturation.  A two-entry item makes the plain call.
         ``upsample``: 'linear' or 'joint' -- ``set_batch_upsample`` before the first batch, the previous setting back when the generator
-        ends or is abandoned; None (default) leaves the setting alone."""
+        ends or is abandoned; None (default) leaves the setting alone.
+        ``ingest``: 'bilinear' or 'antialias' -- ``set_ingest_filter`` with the same scope."""
         def submit(slot, group, first):
             item = group[0]
             rgb, hints = item[0], item[1]
@@ -1179,15 +1200,15 @@ class HipColorizer(object):
             return dst, src
 
         # a group of one: the items are whole batches, checked in submit, behind the yield of the slot's older result
-        yield from self._two_slot_stream(batches, 1, upsample, lambda item: item, submit, lambda state: [np.array(state[0])])
+        yield from self._two_slot_stream(batches, 1, upsample, lambda item: item, submit, lambda state: [np.array(state[0])], ingest=ingest)
 
-    def _two_slot_stream(self, items, batch, upsample, parse, submit, finish, key=None):
+    def _two_slot_stream(self, items, batch, upsample, parse, submit, finish, key=None, ingest=None):
         """The generator behind ``colorize_stream``, ``colorize_images`` and their relatives: ``parse(item)`` every item as it arrives, group
         ``batch`` of them (default ``max_batch``; the last group may be shorter), ``submit(slot, group, first_index)`` group k on slot k % 2
         once that slot's older batch is finished -- ``first_index`` is the stream index of the group's first item; what it returns (results
         and whatever must stay alive: pinned pool memory) is kept until ``wait(slot)`` has returned -- and yield everything in
-        ``finish(state)`` of each batch in input order.  ``upsample`` as in ``colorize_stream``.  A consumer that stops early: both slots are
-        waited for, so nothing stays in flight on buffers about to be recycled, then the upsample setting goes back.
+        ``finish(state)`` of each batch in input order.  ``upsample`` and ``ingest`` as in ``colorize_stream``.  A consumer that stops early: both slots are
+        waited for, so nothing stays in flight on buffers about to be recycled, then the upsample and ingest settings go back.
         ``key`` (of a parsed item): an item whose key differs from its group's closes that group, as a full batch does."""
         batch = self._group_size(batch)
         pending = [None, None]                      # per slot: submit's state of the batch in flight
@@ -1214,6 +1235,12 @@ class HipColorizer(object):
         k, first = 0, 0
         restore = self._upsample_scope(upsample)
         try:
+            restore_ingest = self._ingest_scope(ingest)
+        except Exception:
+            if restore is not None:
+                self.set_batch_upsample(restore)
+            raise
+        try:
             for group in groups():
                 if pending[k & 1] is not None:
                     yield from drain(k & 1)
@@ -1229,8 +1256,12 @@ class HipColorizer(object):
                         pending[slot] = None
                         self.wait(slot)
             finally:
-                if restore is not None:
-                    self.set_batch_upsample(restore)
+                try:
+                    if restore is not None:
+                        self.set_batch_upsample(restore)
+                finally:
+                    if restore_ingest is not None:
+                        self.set_ingest_filter(restore_ingest)
 
     def _group_size(self, batch):
         batch = self.max_batch if batch is None else int(batch)
@@ -1490,7 +1521,7 @@ class HipColorizer(object):
             np.copyto(s, p)
         return srcs
 
-    def colorize_gray(self, items, batch=None, out="source", depth=8, upsample=None, **kw):
+    def colorize_gray(self, items, batch=None, out="source", depth=8, upsample=None, ingest=None, **kw):
         """Generator: ``colorize_images`` for greyscale planes (``forward_async_gray``).  An item is ``gray``, ``(gray, hints)`` or
         ``(gray, hints, ref)``: gray (h,w) uint8 or uint16.  Grouping, slot alternation and order as in ``colorize_images``, and a change of
         dtype closes the group as a full batch does: a call carries one format.  One array per image is yielded: (h,w,3) [out='source'] or
@@ -1512,10 +1543,10 @@ class HipColorizer(object):
             return self.forward_async_gray(slot, srcs, [g[1] for g in group], out=out, depth=depth, **more), srcs
 
         yield from self._two_slot_stream(items, batch, upsample, parse, submit, lambda state: [np.array(r) for r in state[0]],
-                                         key=lambda g: g[0].dtype)
+                                         key=lambda g: g[0].dtype, ingest=ingest)
 
     def suggest_gray(self, items, centres, batch=None, out="source", depth=8, peaks=8, radius=2, skip_hints=True, K=5, N_draws=25000, seed=0,
-                     upsample=None, **kw):
+                     upsample=None, ingest=None, **kw):
         """Generator: ``suggest_images`` for greyscale planes -- where to put the next hints on a folder of black-and-white photographs, and
         in which colours.  An item is ``gray`` or ``(gray, hints)``; it yields ``(rgb, peaks, colours, conf)`` per image as ``suggest_images``
         does, grouped as ``colorize_gray`` groups."""
@@ -1545,9 +1576,9 @@ class HipColorizer(object):
         batch = self._group_size(batch)
         if P < 1:
             raise ValueError("suggest_gray needs at least one peak per image")
-        yield from self._two_slot_stream(items, batch, upsample, parse, submit, finish, key=lambda g: g[0].dtype)
+        yield from self._two_slot_stream(items, batch, upsample, parse, submit, finish, key=lambda g: g[0].dtype, ingest=ingest)
 
-    def colorize_images(self, items, batch=None, out="source", upsample=None, **kw):
+    def colorize_images(self, items, batch=None, out="source", upsample=None, ingest=None, **kw):
         """Generator: colourise a stream of single images of any sizes with both pipeline slots busy.  An item is ``rgb``, ``(rgb, hints)`` or
         ``(rgb, hints, ref)``: rgb (h,w,3) uint8, ``hints`` that image's hint list (rows as in ``set_hints``) or ``None``, ``ref`` ``None`` or an
         (h,w,3) uint8 reference photograph (a ``global_hints`` engine; ``kw`` then carries centres).  Consecutive items are grouped into
@@ -1564,9 +1595,9 @@ class HipColorizer(object):
             return self.forward_async_images(slot, srcs, [g[1] for g in group], out=out, **more), srcs
 
         yield from self._two_slot_stream(items, batch, upsample, lambda item: _image_item("colorize_images", item, True), submit,
-                                         lambda state: [np.array(r) for r in state[0]])
+                                         lambda state: [np.array(r) for r in state[0]], ingest=ingest)
 
-    def evaluate_images(self, items, batch=None, out="net", mode="reveal", upsample=None, **kw):
+    def evaluate_images(self, items, batch=None, out="net", mode="reveal", upsample=None, ingest=None, **kw):
         """Generator: score a stream of ground-truth colour images with both pipeline slots busy -- ``colorize_images`` whose every image is
         compared with itself on the device (``forward_async_eval``).  An item is ``rgb``, ``(rgb, rects)`` or ``(rgb, rects, ref)``; with
         mode='reveal' (default) ``rects`` are rows (y0, x0, y1, x1) whose colours the device reveals from the image, with 'ab' / 'rgb' they
@@ -1588,10 +1619,10 @@ class HipColorizer(object):
             sse = np.array(state[0])
             return [(psnr_from_sse(sse[i], h, w), sse[i]) for i, (h, w) in enumerate(state[1])]
 
-        yield from self._two_slot_stream(items, batch, upsample, lambda item: _image_item("evaluate_images", item, True), submit, finish)
+        yield from self._two_slot_stream(items, batch, upsample, lambda item: _image_item("evaluate_images", item, True), submit, finish, ingest=ingest)
 
     def suggest_images(self, items, centres, batch=None, out="source", peaks=8, radius=2, skip_hints=True, K=5, N_draws=25000, seed=0,
-                       upsample=None, **kw):
+                       upsample=None, ingest=None, **kw):
         """Generator: ``colorize_images`` on an engine with a distribution head that also proposes where to put the next hints and in which
         colours (``forward_async_dist`` with the suggestions at the peaks).  An item is ``rgb`` or ``(rgb, hints)``; grouping, slot alternation
         and order as in ``colorize_images``.  Per image it yields ``(rgb, peaks (P,2) int32, colours (P,K,2) float64, conf (P,K) float64)``:
@@ -1617,9 +1648,9 @@ class HipColorizer(object):
         batch = self._group_size(batch)
         if P < 1:
             raise ValueError("suggest_images needs at least one peak per image")
-        yield from self._two_slot_stream(items, batch, upsample, lambda item: _image_item("suggest_images", item, False), submit, finish)
+        yield from self._two_slot_stream(items, batch, upsample, lambda item: _image_item("suggest_images", item, False), submit, finish, ingest=ingest)
 
-    def score_images(self, items, centres, batch=None, nn=1, sigma=5.0, ranks=(1, 5), mode="reveal", want_psnr=False, upsample=None, **kw):
+    def score_images(self, items, centres, batch=None, nn=1, sigma=5.0, ranks=(1, 5), mode="reveal", want_psnr=False, upsample=None, ingest=None, **kw):
         """Generator: score the distribution head on a stream of ground-truth colour images with both pipeline slots busy --
         ``evaluate_images`` for the distribution (``forward_async_dist`` with ``score`` and no other tap).  An item is ``rgb`` or
         ``(rgb, rects)``, hints as in ``evaluate_images`` (mode 'reveal': the colours come from the image).  Per image it yields
@@ -1640,7 +1671,7 @@ class HipColorizer(object):
             sse = np.array(res.sse) if want_psnr else None
             return [(float(mean[i]), hits[i], psnr_from_sse(sse[i], self.H, self.W) if want_psnr else None) for i in range(len(mean))]
 
-        yield from self._two_slot_stream(items, batch, upsample, lambda item: _image_item("score_images", item, False), submit, finish)
+        yield from self._two_slot_stream(items, batch, upsample, lambda item: _image_item("score_images", item, False), submit, finish, ingest=ingest)
 
     def wait(self, slot):
         self._chk(self.lib.idc_wait(self._h, int(slot)))
