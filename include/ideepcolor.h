@@ -752,6 +752,51 @@ int idc_forward_async_gray(idc_handle h, int slot, int n, int bits, const idc_gr
                            float l_cent, unsigned flags, const idc_batch_refs* refs, void* const* rgb_out, float* out_ab,
                            const idc_dist_taps* taps /* NULL: no distribution head */);
 
+/* ---- painted hint layers: hints as an RGBA overlay -- scribbles, strokes, polygons, a partly coloured copy of the photograph -- instead of, or
+ *      under, a rectangle list.  The rectangle walk costs one comparison per rectangle per pixel; a layer costs its own pixels once.
+ *      THE RULE.  A layer is a host image [lh,lw,4] uint8 RGBA with straight alpha, 1..16384 a side, of any size whatever the source's: it is
+ *      stretched over the whole image.  alpha_min in 1..255: a layer pixel is PAINTED iff A >= alpha_min.  cover in 0..255.  For cell (y, x) of
+ *      the H x W net:
+ *        footprint    every layer pixel whose extent overlaps the cell's: rows r0 = (y*lh)/H up to, not including, r1 = ((y+1)*lh + H-1)/H in
+ *                     integer arithmetic, columns alike from (x, lw, W).  Never empty; neighbouring footprints share a pixel line when the
+ *                     ratio is no integer; a layer smaller than the net gives one pixel to several cells.
+ *        counts       tot = the footprint's pixels, cnt = the painted ones.
+ *        hinted       iff cnt >= 1 and 255*cnt >= cover*tot, in integers: cover 0 = any painted pixel hints the cell.
+ *        colour       the float64 mean over the painted footprint pixels of the (a, b) that IDC_HINT_RGB gives a rectangle of the pixel's
+ *                     RGB; alpha does not weight it.  The sum starts at 0.0 and runs in a fixed order, is divided by cnt in float64 and
+ *                     rounded once to fp32.  THE ORDER: with bh = the longest row span and bw = the longest column span of the sizes
+ *                     (l <= H: 1 if H % l == 0 else 2; l > H: l/H if l % H == 0 else l/H + 2), bh*bw <= 256: row-major upwards through the
+ *                     footprint; else 64 partial sums, partial j over the row-major footprint pixels j, j + 64, ... upwards, folded by halves
+ *                     (j with j + 32, then + 16, ... + 1).  It depends on (lh, lw, H, W) alone: not on n, the slot, the route or the image's
+ *                     place in a batch.
+ *        composition  the layer is the canvas the rectangles paint on: a cell covered by any clipped rectangle of the call's list keeps the
+ *                     rectangle's value; a cell no rectangle covers and the layer hints gets ab = the mean, mask = mask_value; everything
+ *                     else stays ab = 0, mask = 0.  A call that carries a layer needs a finite mask_value != 0.
+ *        cells        the exact number of cells the layer hinted after composition, int32 per image.
+ *      A net-size layer with cover 0 is therefore, bit for bit, a list of 1 x 1 IDC_HINT_RGB rectangles, one per painted pixel.
+ *      idc_set_hints_layer blocks, like idc_set_hints, and with layer == NULL it IS idc_set_hints.  It writes the slot's hint planes and
+ *      mask_value and nothing else: idc_get_hint_planes, the full-resolution getters, IDC_PEAKS_SKIP_HINTS and idc_forward_resident see the
+ *      result as they see a rectangle list's.  cells (or NULL) receives the one count.
+ *      idc_forward_async_layers: idc_forward_async_images (bits 0: images = idc_ref_image[n]) or idc_forward_async_gray without taps (bits 8 |
+ *      16: images = idc_gray_image[n]) with a layer per image; with layers == NULL it is that call bit for bit.  layers->layers [n]: rgba NULL
+ *      = this image has no layer.  Same two slots, idc_wait and idc_pipeline_times (the layer bytes count under H2D, the kernel under
+ *      compute); flags, references, the batch upsample and the ingest filter as in those calls.  The layers travel packed back to back into a
+ *      device array of their own: a pinned buffer in place, pageable neighbours staged and sent as one copy.  The layer bytes stay the
+ *      caller's until idc_wait; the tables are consumed before return.  An RGBA layer of the source's size is four thirds of the RGB source's
+ *      bytes on the bus: a layer may be, and usually should be, smaller than its source.
+ *      Status: everything is decided on the host before anything is enqueued, and a refused call leaves the slot and the handle as they
+ *      were.  The codes of the calls named above for the shared arguments; IDC_ERR_INVALID_ARG for a layer side outside 1..16384, alpha_min
+ *      outside 1..255, cover outside 0..255, a non-NULL layer with NULL rgba in the blocking call, a NULL layers->layers, layer bytes above
+ *      IDC_BATCH_MAX_SOURCE_BYTES in all, mask_value zero or not finite while any layer is present, bits not 0, 8 or 16,
+ *      mode == IDC_HINT_REVEAL; IDC_ERR_UNSUPPORTED while the range audit is on. */
+typedef struct idc_hint_layer { const uint8_t* rgba; int32_t h, w; } idc_hint_layer;      /* rgba NULL: this image has no layer */
+typedef struct idc_batch_layers { const idc_hint_layer* layers /*[n]*/; int32_t alpha_min, cover; int32_t* cells /*[n] or NULL*/; } idc_batch_layers;
+int idc_set_hints_layer(idc_handle h, int img, int n_hints, const idc_hint* hints, int mode, float mask_value,
+                        const idc_hint_layer* layer, int alpha_min, int cover, int32_t* cells);
+int idc_forward_async_layers(idc_handle h, int slot, int n, int bits /* 0: idc_ref_image[n] RGB; 8|16: idc_gray_image[n] */, const void* images,
+                             const idc_batch_layers* layers, const int32_t* hint_offsets, const idc_hint* hints, int mode, float mask_value,
+                             float maskcent, float l_cent, unsigned flags, const idc_batch_refs* refs, void* const* rgb_out, float* out_ab);
+
 /* ---- distribution scores: how much probability did the head put on the colour the pixel really has?  The question the distribution heads
  *      were trained on: the reference's training layers encode the ground-truth ab into the colour bins with NNEncode
  *      (caffe_files/color_quantization.py:7-33; NNEncLayer: NN = 1, sigma = 5, NN = 10 commented beside it, caffe_traininglayers.py:161-189) and

@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = [
     "idc_set_joint_upsample", "idc_fullres_ab", "idc_set_batch_upsample",
     "idc_set_image_gray", "idc_fullres_rgb16", "idc_forward_async_gray",
     "idc_set_ingest_filter",
+    "idc_set_hints_layer", "idc_forward_async_layers",
     "idc_set_range_audit", "idc_range_reset", "idc_range_report", "idc_pack_weights_ex", "idc_load_weights_ex",
 ]
 IDC_STORE_NONE, IDC_STORE_F32, IDC_STORE_BF16, IDC_STORE_F16 = 0, 1, 2, 3
@@ -84,6 +85,16 @@ class Hint(ctypes.Structure):
 class RefImage(ctypes.Structure):
     """idc_ref_image: one host reference photograph, [h,w,3] uint8."""
     _fields_ = [("rgb", ctypes.c_void_p), ("h", ctypes.c_int32), ("w", ctypes.c_int32)]
+
+
+class HintLayer(ctypes.Structure):
+    """idc_hint_layer: one host RGBA layer, [h,w,4] uint8, straight alpha; rgba NULL = the image has no layer."""
+    _fields_ = [("rgba", ctypes.c_void_p), ("h", ctypes.c_int32), ("w", ctypes.c_int32)]
+
+
+class BatchLayers(ctypes.Structure):
+    """idc_batch_layers: the layer table [n], the rule's two parameters, and where the cell counts int32[n] go (or NULL)."""
+    _fields_ = [("layers", ctypes.POINTER(HintLayer)), ("alpha_min", ctypes.c_int32), ("cover", ctypes.c_int32), ("cells", ctypes.c_void_p)]
 
 
 class GrayImage(ctypes.Structure):
@@ -250,6 +261,9 @@ def load():
     proto("idc_fullres_rgb16", ci, [vp, ci, ci, ci, vp])
     proto("idc_forward_async_gray", ci, [vp, ci, ci, ci, ctypes.POINTER(GrayImage), vp, vp, ci, cf, cf, cf, ctypes.c_uint,
                                          ctypes.POINTER(BatchRefs), ctypes.POINTER(vp), vp, ctypes.POINTER(DistTaps)])
+    proto("idc_set_hints_layer", ci, [vp, ci, ci, vp, ci, cf, ctypes.POINTER(HintLayer), ci, ci, vp])
+    proto("idc_forward_async_layers", ci, [vp, ci, ci, ci, vp, ctypes.POINTER(BatchLayers), vp, vp, ci, cf, cf, cf, ctypes.c_uint,
+                                           ctypes.POINTER(BatchRefs), ctypes.POINTER(vp), vp])
     proto("idc_set_batch_upsample", ci, [vp, ci])
     proto("idc_set_ingest_filter", ci, [vp, ci])
     proto("idc_set_range_audit", ci, [vp, ci])

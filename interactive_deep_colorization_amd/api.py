@@ -505,6 +505,29 @@ class ColorizeImageBase(object):
         self._l_serial = getattr(self.net, 'l_serial', None)
         return self._finish_forward(raw[0], rgb[0], lab_q[0])
 
+    def net_forward_layer(self, rgba, hints=(), mode='rgb', alpha_min=128, cover=0):
+        """``net_forward_hints`` with a painted layer under the edit list (not in the reference, whose ``addStroke`` / ``get_stroke_image``
+        are stubs): ``rgba`` (lh,lw,4) uint8, straight alpha, of any size -- scribbles, strokes, polygons or a partly coloured copy of the
+        photograph; it is stretched over the image.  A net cell no rectangle of ``hints`` covers is hinted iff its footprint in the layer
+        holds a pixel with A >= ``alpha_min`` and 255 * painted >= ``cover`` * pixels, with the mean Lab colour of the painted ones
+        (``include/ideepcolor.h``).  The number of cells the layer hinted is left in ``self.layer_cells``; ``input_ab`` / ``input_mask``
+        are read back lazily from the device planes, as after ``net_forward_hints``.  Returns what ``net_forward`` returns."""
+        for ready, complaint in ((self.img_l_set, 'I need to have an image!'),
+                                 (self.net_set, 'I need to have a net!')):
+            if not ready:
+                print(complaint)
+                return -1
+        if not hasattr(self.net, 'set_hint_layer'):
+            raise RuntimeError('net_forward_layer needs an engine with set_hint_layer')
+        if self.ab_mean != 0 or self.ab_norm != 1:
+            raise ValueError('device-side hints assume raw ab inputs (ab_mean 0, ab_norm 1)')
+        self._ensure_l_resident()
+        self.layer_cells = self.net.set_hint_layer(rgba, hints, mode=mode, img=0, mask_value=self.mask_mult, alpha_min=alpha_min, cover=cover)
+        self._hints_on_device = True
+        raw, rgb, lab_q = self.net.forward_resident(1, getattr(self, 'mask_cent', 0), l_cent=self.l_mean)
+        self._l_serial = getattr(self.net, 'l_serial', None)
+        return self._finish_forward(raw[0], rgb[0], lab_q[0])
+
     def net_forward_reveal(self, rects):
         """``net_forward_hints`` in mode 'ab' whose colours the engine reveals from the image itself (not in the reference: the paper's
         simulated user, what the notebook feeds ``put_point`` by hand).  rects: rows ``(y0, x0, y1, x1)``, corners inclusive; each

@@ -333,11 +333,29 @@ int idc_set_image_l(idc_handle h, int img, const float* L_mc) {
     return IDC_OK;
 }
 
-int idc_set_hints(idc_handle h, int img, int n_hints, const idc_hint* hints, int mode, float mask_value) {
+// idc_set_hints, and with a layer idc_set_hints_layer: the rectangles as ever, then the layer under them (launch_hint_layers, n = 1)
+static int set_hints(idc_context* h, int img, int n_hints, const idc_hint* hints, int mode, float mask_value, const idc_hint_layer* layer,
+                     int alpha_min, int cover, int32_t* cells) {
     int rc = check_img(h, img);
     if (rc) return rc;
     if (n_hints < 0 || (n_hints > 0 && !hints)) return fail(&h->err, IDC_ERR_INVALID_ARG, "bad hint list");
     if (mode != IDC_HINT_AB && mode != IDC_HINT_RGB) return fail(&h->err, IDC_ERR_INVALID_ARG, "hint mode %d", mode);
+    if (layer) {
+        if (!layer->rgba) return fail(&h->err, IDC_ERR_INVALID_ARG, "null layer pixels");
+        if (layer->h < 1 || layer->h > kLayerMaxSide || layer->w < 1 || layer->w > kLayerMaxSide)
+            return fail(&h->err, IDC_ERR_INVALID_ARG, "layer size %dx%d outside 1..%d", layer->h, layer->w, kLayerMaxSide);
+        if (alpha_min < 1 || alpha_min > 255) return fail(&h->err, IDC_ERR_INVALID_ARG, "alpha_min %d outside 1..255", alpha_min);
+        if (cover < 0 || cover > 255) return fail(&h->err, IDC_ERR_INVALID_ARG, "cover %d outside 0..255", cover);
+        if ((size_t)layer->h * layer->w * 4 > IDC_BATCH_MAX_SOURCE_BYTES)
+            return fail(&h->err, IDC_ERR_INVALID_ARG, "the layer holds %zu bytes, more than %zu", (size_t)layer->h * layer->w * 4, (size_t)IDC_BATCH_MAX_SOURCE_BYTES);
+        if (!(std::isfinite(mask_value) && mask_value != 0.f)) return fail(&h->err, IDC_ERR_INVALID_ARG, "a call with a layer needs a finite mask_value != 0");
+        if (h->audit) return fail(&h->err, IDC_ERR_UNSUPPORTED, "the range audit does not cover hint layers");
+        for (int i = 0; i < n_hints && mode == IDC_HINT_RGB; ++i) {      // everything is decided before anything is enqueued
+            HintRect r;
+            if (clip_hint(hints[i], h->H, h->W, r) && !(r.c0 >= 0.f && r.c0 <= 255.f && r.c1 >= 0.f && r.c1 <= 255.f && r.c2 >= 0.f && r.c2 <= 255.f))
+                return fail(&h->err, IDC_ERR_INVALID_ARG, "hint %d: RGB outside 0..255", i);
+        }
+    }
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream.get()));            // the pinned list of the previous call may still be in flight
     {   // 256 entries to begin with, twice the list once it is longer
@@ -358,8 +376,35 @@ int idc_set_hints(idc_handle h, int img, int n_hints, const idc_hint* hints, int
     if (kept) HIPCHK(h, hipMemcpyAsync(h->d_hints.get(), h->h_hints.get(), (size_t)kept * sizeof(HintRect), hipMemcpyHostToDevice, h->stream.get()));
     HIPCHK(h, launch_raster_hints(h->d_hints.get(), kept, mode, mask_value, h->d_ab.get() + (size_t)img * hw * 2, h->d_mask.get() + (size_t)img * hw,
                                   h->H, h->W, h->stream.get()));
+    if (layer) {
+        const size_t lb = (size_t)layer->h * layer->w * 4;
+        HIPCHK(h, h->d_layer.ensure(lb, 65536));
+        HIPCHK(h, h->d_layer_meta.ensure(32));
+        HIPCHK(h, h->h_layer_meta.ensure(32));
+        unsigned char* hm = h->h_layer_meta.get();
+        unsigned char* dm = h->d_layer_meta.get();
+        memset(hm, 0, 32);
+        const LayerDesc d = {0, layer->h, layer->w};
+        memcpy(hm, &d, sizeof(d));
+        HIPCHK(h, hipMemcpyAsync(dm, hm, 32, hipMemcpyHostToDevice, h->stream.get()));      // the table and a zero count
+        HIPCHK(h, hipMemcpyAsync(h->d_layer.get(), layer->rgba, lb, hipMemcpyHostToDevice, h->stream.get()));
+        HIPCHK(h, launch_hint_layers(h->d_layer.get(), (const LayerDesc*)dm, 1, layer_blocks(layer->h, layer->w, h->H, h->W), h->H, h->W, alpha_min, cover,
+                                     mask_value, h->d_ab.get() + (size_t)img * hw * 2, h->d_mask.get() + (size_t)img * hw, (int*)(dm + 16), h->stream.get()));
+        HIPCHK(h, hipMemcpyAsync(hm + 16, dm + 16, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream.get()));
+        HIPCHK(h, hipStreamSynchronize(h->stream.get()));               // the caller's pixels are read and the count is here
+        if (cells) memcpy(cells, hm + 16, sizeof(int32_t));
+    }
     h->hint_mask_value[img] = mask_value;
     return IDC_OK;
+}
+
+int idc_set_hints(idc_handle h, int img, int n_hints, const idc_hint* hints, int mode, float mask_value) {
+    return set_hints(h, img, n_hints, hints, mode, mask_value, nullptr, 0, 0, nullptr);
+}
+
+int idc_set_hints_layer(idc_handle h, int img, int n_hints, const idc_hint* hints, int mode, float mask_value, const idc_hint_layer* layer,
+                        int alpha_min, int cover, int32_t* cells) {
+    return set_hints(h, img, n_hints, hints, mode, mask_value, layer, alpha_min, cover, cells);
 }
 
 // idc_set_hints in IDC_HINT_AB mode with every colour taken from the slot's kept source: the list goes to the device clipped, reveal_hints_kernel

@@ -7,6 +7,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -51,7 +52,16 @@ struct BatchCall {
     int gray_bits = 0, out_bits = 8; const idc_gray_image* grays = nullptr;
     // the handle's ingest filter as the call was enqueued (idc_set_ingest_filter): IDC_FILTER_BILINEAR leaves every byte of the plan as it was
     int ingest_filter = IDC_FILTER_BILINEAR;
+    // painted hint layers (idc_forward_async_layers; ragged only): has_layers = the call brought an idc_batch_layers, whose three parts follow --
+    // the table [n] (rgba NULL: that image has no layer), the two parameters of the rule, and where the cell counts go (or nullptr).  Without it
+    // every byte of the plan and of the block is as it was.
+    bool has_layers = false; const idc_hint_layer* layers = nullptr; int alpha_min = 0, cover = 0; int32_t* cells = nullptr;
 };
+
+inline void set_batch_layers(BatchCall& c, const idc_batch_layers* l) {
+    c.has_layers = l != nullptr;
+    if (l) { c.layers = l->layers; c.alpha_min = l->alpha_min; c.cover = l->cover; c.cells = l->cells; }
+}
 
 // image i of a ragged call, whichever table it came in (a plane's samples stand in the place of the bytes)
 inline idc_ref_image batch_image(const BatchCall& c, int i) {
@@ -89,6 +99,15 @@ struct BatchPlan {
     // ResampleJob[naa] at jobs_at.  aa_tiles = the largest tile count among the jobs.
     int naa = 0, aa_tiles = 0;
     size_t aa_at = 0, src_bytes = 0, view_at = 0, jobs_at = 0;
+    // painted hint layers: n_layers = the images of the call that bring one (0: everything above is the whole plan).  The [lh,lw,4] layers lie
+    // packed back to back, in image order, in a device array of the slot's OWN (layer_bytes of it; every start is a multiple of 4), one piece
+    // each in layer_pieces (in_at = the start; nothing comes back), which travel by copy_runs' rule.  Appended to the metadata block, behind
+    // everything above: LayerDesc[max_batch] at layers_at, entry i = {start, lh, lw} or zeros for an image without a layer and past n.
+    // layer_blocks = grid.x of the post-pass: the largest layer_blocks (idc_layer.h) among the layers.
+    int n_layers = 0, layer_blocks = 0;
+    size_t layer_bytes = 0, layers_at = 0;
+    std::vector<Piece> layer_pieces;
+    bool cells_pinned = false;           // the caller's to fill in, as ab_pinned
 };
 
 inline int plan_fail(std::string* err, int code, const char* fmt, ...) {
@@ -165,6 +184,24 @@ inline int plan_batch(const BatchCall& c, int H, int W, int max_batch, BatchPlan
             return plan_fail(err, IDC_ERR_INVALID_ARG, "hint %d: RGB outside 0..255", k);
         ++p->kept;
     }
+    if (c.has_layers) {
+        if (!c.ragged) return plan_fail(err, IDC_ERR_INVALID_ARG, "layers with a same-size call");
+        if (!c.layers) return plan_fail(err, IDC_ERR_INVALID_ARG, "null layer table");
+        if (c.alpha_min < 1 || c.alpha_min > 255) return plan_fail(err, IDC_ERR_INVALID_ARG, "alpha_min %d outside 1..255", c.alpha_min);
+        if (c.cover < 0 || c.cover > 255) return plan_fail(err, IDC_ERR_INVALID_ARG, "cover %d outside 0..255", c.cover);
+        for (int i = 0; i < n; ++i) {
+            const idc_hint_layer& l = c.layers[i];
+            if (!l.rgba) continue;
+            if (l.h < 1 || l.h > kLayerMaxSide || l.w < 1 || l.w > kLayerMaxSide)
+                return plan_fail(err, IDC_ERR_INVALID_ARG, "image %d: layer size %dx%d outside 1..%d", i, l.h, l.w, kLayerMaxSide);
+            p->layer_bytes += (size_t)l.h * l.w * 4;              // n * 1 GB: no overflow in 64 bits
+            ++p->n_layers;
+        }
+        if (p->layer_bytes > IDC_BATCH_MAX_SOURCE_BYTES)
+            return plan_fail(err, IDC_ERR_INVALID_ARG, "%d layers hold %zu bytes, more than %zu", p->n_layers, p->layer_bytes, (size_t)IDC_BATCH_MAX_SOURCE_BYTES);
+        if (p->n_layers > 0 && !(std::isfinite(c.mask_value) && c.mask_value != 0.f))
+            return plan_fail(err, IDC_ERR_INVALID_ARG, "a call with a layer needs a finite mask_value != 0");
+    }
     const size_t hw = (size_t)H * W, nb = (size_t)max_batch;
     p->source_out = (c.flags & IDC_BATCH_OUT_SOURCE) != 0;
     p->rgb_bytes = p->source_out ? full_bytes : (size_t)n * hw * 3;
@@ -208,6 +245,20 @@ inline int plan_batch(const BatchCall& c, int H, int W, int max_batch, BatchPlan
         p->jobs_at = c.ragged ? p->view_at + batch_align16((nb + 1) * sizeof(ImgDesc)) : p->view_at;
         p->meta_bytes = p->jobs_at + (size_t)p->naa * sizeof(ResampleJob);
     }
+    if (p->n_layers > 0) {
+        size_t at = 0;
+        for (int i = 0; i < n; ++i) {
+            const idc_hint_layer& l = c.layers[i];
+            if (!l.rgba) continue;
+            const size_t lb = (size_t)l.h * l.w * 4;
+            const int blocks = layer_blocks(l.h, l.w, H, W);
+            p->layer_pieces.push_back({l.rgba, nullptr, at, lb, 0, 0, false, true});
+            p->layer_blocks = p->layer_blocks > blocks ? p->layer_blocks : blocks;
+            at += lb;
+        }
+        p->layers_at = batch_align16(p->meta_bytes);
+        p->meta_bytes = p->layers_at + nb * sizeof(LayerDesc);
+    }
     return IDC_OK;
 }
 
@@ -249,6 +300,15 @@ inline void fill_batch_meta(const BatchCall& c, const BatchPlan& p, int H, int W
             const size_t dst = p.aa_at + (size_t)k * net_bytes;
             jobs[k++] = resample_job((long long)at, (long long)dst, ih, iw, W, c.gray_bits ? 1 : 3);
             if (view) { view[i].off = (long long)dst; view[i].first = (long long)(dst / p.bpp_in); view[i].h = H; view[i].w = W; }
+        }
+    }
+    if (p.n_layers > 0) {                           // the post-pass's table, behind everything above: the block ends with its max_batch entries
+        LayerDesc* tab = (LayerDesc*)(h_meta + p.layers_at);
+        const int nb = (int)((p.meta_bytes - p.layers_at) / sizeof(LayerDesc));
+        for (int i = 0, k = 0; i < nb; ++i) {
+            const bool has = i < c.n && c.layers[i].rgba != nullptr;
+            tab[i].off = has ? (long long)p.layer_pieces[k++].in_at : 0;
+            tab[i].h = has ? c.layers[i].h : 0; tab[i].w = has ? c.layers[i].w : 0;
         }
     }
 }

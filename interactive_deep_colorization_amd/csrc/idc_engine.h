@@ -187,6 +187,9 @@ struct idc_context {
     int dist_n = 0;                      // images whose distribution is resident from the last forward (0 = none)
     DevMem<HintRect> d_hints;            // click session: hint list staging
     PinnedMem<HintRect> h_hints;
+    DevMem<unsigned char> d_layer;       // idc_set_hints_layer: the one RGBA layer ...
+    DevMem<unsigned char> d_layer_meta;  // ... its LayerDesc at 0 and the cell count int32 at 16 ...
+    PinnedMem<unsigned char> h_layer_meta;    // ... and their pinned copy
     DevMem<unsigned char> d_reveal;      // idc_reveal_hints: the kept rectangles' places in the caller's list int[kept], then colours float[n_hints][2] ...
     PinnedMem<unsigned char> h_reveal;   // ... and their pinned copy
     DevMem<float> d_centres; DevMem<double> d_sugg; DevMem<unsigned> d_sugg_counts;   // colour suggestions
@@ -264,6 +267,9 @@ struct idc_context {
         // idc_forward_async_rgb_ref: the batch's references and the slot's OWN [max_batch][316] global inputs (the handle's d_glob_in is not touched)
         RefStage ref;
         DevMem<float> d_glob_in;
+        // idc_forward_async_layers: the batch's packed RGBA layers (BatchPlan::layer_pieces) and the cell counts int32[max_batch], device and pinned
+        DevMem<unsigned char> d_layer, d_cells;
+        PinnedMem<unsigned char> h_layer, h_cells;
     } pipe[2];
     Event ev_pipe_base;
     bool pipe_ready = false;             // ev_pipe_base is recorded (ensure_pipeline)

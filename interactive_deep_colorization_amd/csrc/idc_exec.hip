@@ -726,6 +726,14 @@ static int batch_reserve(idc_context* h, const BatchCall& c, const BatchPlan& p,
     if (any_staged_rgb) HIPCHK(h, sl.h_rgb.ensure(p.rgb_bytes));
     if (!p.ab_pinned) HIPCHK(h, sl.h_out.ensure(nb * hw * 2 * 4));
     if (c.has_refs) HIPCHK(h, sl.d_glob_in.ensure(nb * kGlobIn * sizeof(float)));
+    if (c.has_layers) {   // the packed layers in an array of their own, and the cell counts
+        bool any_staged_layer = false;
+        for (const Piece& q : p.layer_pieces) any_staged_layer |= !q.in_pinned;
+        if (p.n_layers > 0) HIPCHK(h, sl.d_layer.ensure(p.layer_bytes, 65536));
+        if (any_staged_layer) HIPCHK(h, sl.h_layer.ensure(p.layer_bytes, 65536));
+        HIPCHK(h, sl.d_cells.ensure(nb * sizeof(int32_t)));
+        if (c.cells && !p.cells_pinned) HIPCHK(h, sl.h_cells.ensure(nb * sizeof(int32_t)));
+    }
     return IDC_OK;
 }
 
@@ -738,6 +746,8 @@ static int batch_stage(idc_context* h, const BatchCall& c, const BatchPlan& p, c
     if (p.score) memcpy(sl.h_score_in.get(), c.centres, (size_t)L.geom.B * 2 * sizeof(float));
     for (const Piece& q : p.pieces)      // every host buffer is judged on its own: only the pageable sources go through the staging
         if (!q.in_pinned) memcpy(sl.h_src.get() + q.in_at, q.in, q.in_bytes);
+    for (const Piece& q : p.layer_pieces)
+        if (!q.in_pinned) memcpy(sl.h_layer.get() + q.in_at, q.in, q.in_bytes);
     fill_batch_meta(c, p, h->H, h->W, sl.h_meta.get());
     return c.has_refs ? stage_refs(h, sl.ref, L.ref, c.refs.refs, c.refs.ref_index, c.refs.centres, false) : IDC_OK;
 }
@@ -746,6 +756,7 @@ static int batch_copy_in(idc_context* h, const BatchCall& c, const BatchPlan& p,
     hipStream_t s = h->s_in.get();
     HIPCHK(h, hipEventRecord(sl.ev_in0.get(), s));
     HIPCHK(h, copy_pieces(p.pieces, true, sl.d_src.get(), sl.h_src.get(), s));
+    if (p.n_layers > 0) HIPCHK(h, copy_pieces(p.layer_pieces, true, sl.d_layer.get(), sl.h_layer.get(), s));
     HIPCHK(h, hipMemcpyAsync(sl.d_meta.get(), sl.h_meta.get(), p.meta_bytes, hipMemcpyHostToDevice, s));
     if (L.taps.Q > 0) HIPCHK(h, hipMemcpyAsync(sl.d_taps_in.get(), sl.h_taps_in.get(), L.taps.in_bytes, hipMemcpyHostToDevice, s));
     if (p.score) HIPCHK(h, hipMemcpyAsync(sl.d_score_in.get(), sl.h_score_in.get(), L.score_in_bytes, hipMemcpyHostToDevice, s));
@@ -797,6 +808,12 @@ static int batch_colourise(idc_context* h, const BatchCall& c, const BatchPlan& 
     else
         HIPCHK(h, launch_batch_prologue(sl.d_src.get() + p.aa_at, n, p.naa ? h->H : c.src_h, p.naa ? h->W : c.src_w, h->H, h->W, c.l_cent, m.offs, m.hints, mode, c.mask_value, sl.d_L.get(),
                                         sl.d_ab.get(), sl.d_mask.get(), s));
+    if (c.has_layers) {   // the layers under the rectangles the prologue has just written; a call whose images all came without one reports zeros
+        HIPCHK(h, hipMemsetAsync(sl.d_cells.get(), 0, (size_t)n * sizeof(int32_t), s));
+        if (p.n_layers > 0)
+            HIPCHK(h, launch_hint_layers(sl.d_layer.get(), (const LayerDesc*)(sl.d_meta.get() + p.layers_at), n, p.layer_blocks, h->H, h->W, c.alpha_min,
+                                         c.cover, c.mask_value, sl.d_ab.get(), sl.d_mask.get(), (int*)sl.d_cells.get(), s));
+    }
     const int dist_n = h->dist_n;
     // a distribution batch runs model_class into the HANDLE's distribution (the 313 head with idc_keep_dist writes dist_S on every forward anyway)
     const int rc = run_graph(h, n, sl.d_L.get(), sl.d_ab.get(), sl.d_mask.get(), c.maskcent, sl.d_out.get(),
@@ -895,6 +912,7 @@ static int batch_copy_out(idc_context* h, const BatchCall& c, const BatchPlan& p
         rc = copy_out_rows(h, sl, rows, sizeof(rows) / sizeof(rows[0]), sl.d_eval.get(), sl.h_eval.get());
         if (rc) return rc;
     }
+    if (c.has_layers && c.cells) HIPCHK(h, copy_out(h, sl, c.cells, p.cells_pinned, sl.d_cells.get(), sl.h_cells.get(), 0, n * sizeof(int32_t)));
     if (p.want_rgb) {
         HIPCHK(h, copy_pieces(p.pieces, false, p.source_out ? sl.d_full.get() : sl.d_rgb.get(), sl.h_rgb.get(), h->s_out.get()));
         for (const Piece& q : p.pieces)
@@ -925,6 +943,8 @@ static int forward_async_rgb(idc_handle h, const BatchCall& call) {
     Slot& sl = h->pipe[c.slot];
     for (Piece& q : p.pieces) { q.in_pinned = is_pinned(q.in); q.out_pinned = !p.want_rgb || is_pinned(q.out); }
     p.ab_pinned = !c.out_ab || is_pinned(c.out_ab);
+    for (Piece& q : p.layer_pieces) q.in_pinned = is_pinned(q.in);
+    p.cells_pinned = !c.cells || is_pinned(c.cells);
     rc = batch_reserve(h, c, p, L, sl);
     if (!rc) rc = batch_stage(h, c, p, L, sl);
     if (!rc) rc = batch_copy_in(h, c, p, L, sl);
@@ -1020,6 +1040,20 @@ int idc_forward_async_gray(idc_handle h, int slot, int n, int bits, const idc_gr
     c.gray_bits = bits ? bits : -1;      // (0 is the RGB calls' own value: like every width but 8 and 16 it is refused by the plan)
     c.out_bits = (flags & IDC_BATCH_OUT_RGB16) ? 16 : 8;
     if (taps) { c.eval = true; c.taps_call = true; c.taps = taps; }        // idc_forward_async_dist without a score and without revealed colours
+    return forward_async_rgb(h, c);
+}
+
+int idc_forward_async_layers(idc_handle h, int slot, int n, int bits, const void* images, const idc_batch_layers* layers, const int32_t* hint_offsets,
+                             const idc_hint* hints, int mode, float mask_value, float maskcent, float l_cent, unsigned flags,
+                             const idc_batch_refs* refs, void* const* rgb_out, float* out_ab) {
+    BatchCall c = images_call(slot, n, bits == 0 ? (const idc_ref_image*)images : nullptr, hint_offsets, hints, mode, mask_value, maskcent, l_cent, flags,
+                              refs, (uint8_t* const*)rgb_out, out_ab);
+    if (bits != 0) {      // idc_forward_async_gray's call (a width that is neither 8 nor 16 is refused by the plan)
+        c.grays = (const idc_gray_image*)images;
+        c.gray_bits = bits;
+        c.out_bits = (flags & IDC_BATCH_OUT_RGB16) ? 16 : 8;
+    }
+    set_batch_layers(c, layers);
     return forward_async_rgb(h, c);
 }
 

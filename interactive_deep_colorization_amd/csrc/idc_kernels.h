@@ -8,6 +8,7 @@
 
 #include "idc_grid.h"
 #include "idc_resample.h"
+#include "idc_layer.h"
 
 namespace idc {
 
@@ -353,6 +354,13 @@ hipError_t launch_ragged_gray_fullres(const void* src, int bits, const ImgDesc* 
 // own tiling) -- uint8 x 3, uint8 x 1 or uint16 x 1.  Exact grid dim3(max_tiles, H, njobs), max_tiles = the largest jobs[.].tiles.
 hipError_t launch_resample(const void* src_base, void* dst_base, const ResampleJob* jobs, int njobs, int max_tiles, int bits, int channels, int H,
                            int W, hipStream_t s);
+
+// Painted hint layers (idc_set_hints_layer / idc_forward_async_layers; idc_layer.hip; the rule: include/ideepcolor.h): the post-pass behind the
+// prologue or raster_hints.  layers = the [h,w,4] u8 RGBA layers packed back to back from a 16-byte aligned base, descs [n] (LayerDesc,
+// idc_layer.h: h == 0 = no layer); ab [n,2,H,W] and mask [n,1,H,W] are composed in place; cells [n] += the cells each layer hinted (the caller
+// zeroes it on the same stream).  Exact grid dim3(max_blocks, n), max_blocks = the largest layer_blocks among the layers.
+hipError_t launch_hint_layers(const unsigned char* layers, const LayerDesc* descs, int n, int max_blocks, int H, int W, int alpha_min, int cover,
+                              float mask_value, float* ab, float* mask, int* cells, hipStream_t s);
 
 // Evaluation batches (idc_reveal_hints / idc_forward_async_eval; idc_colour.hip).  reveal_hints: (c0, c1) of each of the n_rects clipped
 // rectangles of `hints` = the float64 mean ab (rounded once to fp32) of its image's net-size pixels under it, one workgroup per rectangle, fixed

@@ -464,6 +464,14 @@ def _image_item(who, item, with_ref):
     return (rgb, hints, item[2] if len(item) > 2 else None, len(item) > 2) if with_ref else (rgb, hints)
 
 
+def _layer_array(who, layer):
+    """A painted hint layer as the library reads it: (lh,lw,4) uint8 RGBA, C-contiguous."""
+    a = np.asarray(layer)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 4 or a.size == 0:
+        raise ValueError("%s needs uint8 (h,w,4) RGBA layers, got %s %s" % (who, a.dtype, a.shape))
+    return np.ascontiguousarray(a)
+
+
 def _gray_item(who, item, with_ref):
     """``_image_item`` for greyscale planes: ``gray`` (h,w) uint8 or uint16, its dtype kept."""
     item = (item,) if isinstance(item, np.ndarray) else tuple(item)
@@ -853,6 +861,26 @@ class HipColorizer(object):
             arr[i].c0, arr[i].c1, arr[i].c2 = float(r[4]), float(r[5]), float(r[6]) if len(r) > 6 else 0.0
         self._chk(self.lib.idc_set_hints(self._h, int(img), len(rows), arr, {"ab": N.IDC_HINT_AB, "rgb": N.IDC_HINT_RGB}[mode],
                                          float(mask_value)))
+
+    def set_hint_layer(self, rgba, hints=(), mode="rgb", img=0, mask_value=1.0, alpha_min=128, cover=0):
+        """``set_hints`` with a painted layer under the rectangles (``idc_set_hints_layer``): ``rgba`` (lh,lw,4) uint8, straight alpha, of any
+        size -- it is stretched over the image.  A layer pixel is painted iff A >= ``alpha_min``; a net cell no rectangle covers is hinted
+        iff its footprint holds a painted pixel and 255 * painted >= ``cover`` * pixels, with the mean Lab colour of the painted ones.
+        Returns the number of cells the layer hinted.  ``rgba=None``: ``set_hints`` exactly (returns 0)."""
+        rows = [tuple(r) for r in hints]
+        arr = (N.Hint * max(len(rows), 1))()
+        for i, r in enumerate(rows):
+            arr[i].y0, arr[i].x0, arr[i].y1, arr[i].x1 = int(r[0]), int(r[1]), int(r[2]), int(r[3])
+            arr[i].c0, arr[i].c1, arr[i].c2 = float(r[4]), float(r[5]), float(r[6]) if len(r) > 6 else 0.0
+        layer, a = None, None
+        if rgba is not None:
+            a = _layer_array("set_hint_layer", rgba)
+            layer = N.HintLayer(a.ctypes.data, a.shape[0], a.shape[1])
+        cells = ctypes.c_int32(0)
+        self._chk(self.lib.idc_set_hints_layer(self._h, int(img), len(rows), arr, {"ab": N.IDC_HINT_AB, "rgb": N.IDC_HINT_RGB}[mode],
+                                               float(mask_value), ctypes.byref(layer) if layer is not None else None, int(alpha_min), int(cover),
+                                               ctypes.cast(ctypes.byref(cells), ctypes.c_void_p)))
+        return int(cells.value)
 
     def reveal_hints(self, rects, img=0, mask_value=1.0):
         """``set_hints`` in 'ab' mode with every colour revealed on the device (``idc_reveal_hints``): rects are rows (y0, x0, y1, x1[, ...]),
@@ -1511,6 +1539,129 @@ class HipColorizer(object):
                                                   out_ab.ctypes.data_as(vp) if out_ab is not None else None, ctypes.byref(t) if t is not None else None))
         self._in_flight[int(slot)] = (images, out_rgb, out_ab, res, held, keep)      # the library reads / writes them until the slot's wait
         return res if res is not None else out_rgb
+
+    def forward_async_layers(self, slot, images, layers, hints, out_rgb=None, out_ab=None, mode="rgb", mask_value=1.0, maskcent=0.0,
+                             l_cent=50.0, out="net", depth=8, alpha_min=128, cover=0, refs=None, ref_index=None, centres=None, hist_flag=1.0,
+                             saturation=False):
+        """``forward_async_images`` / ``forward_async_gray`` with a painted hint layer per image (``idc_forward_async_layers``).  ``images``:
+        n C-contiguous arrays, all (h,w,3) uint8 RGB, or all (h,w) uint8 or all (h,w) uint16 planes -- ``ndim`` and dtype tell which.
+        ``layers``: n entries, each ``None`` or an (lh,lw,4) uint8 RGBA array of any size (``set_hint_layer``'s rule, one ``alpha_min`` and
+        ``cover`` per call), or ``None``: the call is the layer-free one.  Returns ``(out_rgb, cells)``, valid after ``wait(slot)``: the list
+        of outputs as those calls give it (``depth=16``: uint16, for uint16 planes with out='source') and the (n,) int32 counts of the cells
+        each layer hinted (``None`` without ``layers``).  Hints (note the default mode 'rgb'), references and the rest as in those calls."""
+        who = "forward_async_layers"
+        images = list(images)
+        n = len(images)
+        kinds = set((a.ndim, a.dtype) for a in images if isinstance(a, np.ndarray))
+        if len(kinds) != 1 or len(images) == 0 or not all(isinstance(a, np.ndarray) for a in images):
+            raise ValueError("%s needs arrays of one kind: (h,w,3) uint8, (h,w) uint8 or (h,w) uint16" % who)
+        ndim, dt = next(iter(kinds))
+        if (ndim, dt) == (3, np.dtype(np.uint8)):
+            bits = 0
+        elif ndim == 2 and dt in (np.dtype(np.uint8), np.dtype(np.uint16)):
+            bits = 8 * dt.itemsize
+        else:
+            raise ValueError("%s needs arrays of one kind: (h,w,3) uint8, (h,w) uint8 or (h,w) uint16" % who)
+        for a in images:
+            if not a.flags.c_contiguous or a.size == 0 or (bits == 0 and a.shape[2] != 3):
+                raise ValueError("%s needs C-contiguous, non-empty (h,w,3) or (h,w) arrays" % who)
+        if depth not in (8, 16):
+            raise ValueError("depth must be 8 or 16, got %r" % (depth,))
+        if depth == 16 and (bits != 16 or out != "source"):
+            raise ValueError("depth=16 needs uint16 planes and out='source'")
+        flags = {"net": 0, "source": N.IDC_BATCH_OUT_SOURCE}[out] | (N.IDC_BATCH_OUT_RGB16 if depth == 16 else 0)
+        odt = np.uint16 if depth == 16 else np.uint8
+        shapes = [tuple(a.shape[:2]) + (3,) if flags else (self.H, self.W, 3) for a in images]
+        if out_rgb is None:
+            nbytes = [int(np.prod(s)) * (depth // 8) for s in shapes]           # (each output starts on an even byte of the block)
+            out_rgb = [o[:b].view(odt).reshape(s) for o, b, s in zip(self._pinned_slices([(b + 1) // 2 * 2 for b in nbytes]), nbytes, shapes)]
+        out_rgb = list(out_rgb)
+        if len(out_rgb) != n:
+            raise ValueError("%s needs %d outputs, got %d" % (who, n, len(out_rgb)))
+        for o, shp in zip(out_rgb, shapes):
+            if not isinstance(o, np.ndarray) or o.dtype != odt or not o.flags.c_contiguous or tuple(o.shape) != shp:
+                raise ValueError("%s needs a %s C-contiguous out_rgb of shape %s" % (who, np.dtype(odt).name, shp))
+        if out_ab is not None and (out_ab.dtype != np.float32 or not out_ab.flags.c_contiguous or tuple(out_ab.shape) != (n, 2, self.H, self.W)):
+            raise ValueError("%s needs a float32 C-contiguous out_ab of shape %s" % (who, (n, 2, self.H, self.W)))
+        offsets, arr = flatten_hints(hints, n)
+        vp = ctypes.c_void_p
+        table = (N.GrayImage * n)() if bits else (N.RefImage * n)()
+        outs = (vp * n)()
+        for i, a in enumerate(images):
+            if bits:
+                table[i].pix = a.ctypes.data
+            else:
+                table[i].rgb = a.ctypes.data
+            table[i].h, table[i].w = a.shape[0], a.shape[1]
+            outs[i] = out_rgb[i].ctypes.data
+        lblock, ltab, larrs, cells = None, None, None, None
+        if layers is not None:
+            layers = list(layers)
+            if len(layers) != n:
+                raise ValueError("%s: %d layers for %d images" % (who, len(layers), n))
+            larrs = [None if l is None else _layer_array(who, l) for l in layers]
+            ltab = (N.HintLayer * n)()
+            for i, l in enumerate(larrs):
+                if l is not None:
+                    ltab[i].rgba, ltab[i].h, ltab[i].w = l.ctypes.data, l.shape[0], l.shape[1]
+            cells = self._pool.take((n,), np.int32)
+            lblock = N.BatchLayers(ltab, int(alpha_min), int(cover), cells.ctypes.data)
+        block, keep = None, None
+        if refs is not None:
+            (m, rarr, idx, c, hist_flag, rflags), keep = _ref_args(refs, ref_index, centres, hist_flag, saturation, n)
+            block = N.BatchRefs(m, rarr, idx.ctypes.data if idx is not None else None, c.ctypes.data if c is not None else None, hist_flag, rflags)
+        self._chk(self.lib.idc_forward_async_layers(self._h, int(slot), int(n), bits, ctypes.cast(table, vp),
+                                                    ctypes.byref(lblock) if lblock is not None else None,
+                                                    offsets.ctypes.data_as(vp) if offsets is not None else None,
+                                                    ctypes.cast(arr, vp) if arr is not None else None, {"ab": N.IDC_HINT_AB, "rgb": N.IDC_HINT_RGB}[mode],
+                                                    float(mask_value), float(maskcent), float(l_cent), flags,
+                                                    ctypes.byref(block) if block is not None else None, outs,
+                                                    out_ab.ctypes.data_as(vp) if out_ab is not None else None))
+        self._in_flight[int(slot)] = (images, larrs, out_rgb, out_ab, cells, keep)   # the library reads / writes them until the slot's wait
+        return out_rgb, cells
+
+    def colorize_layers(self, items, batch=None, out="source", depth=8, upsample=None, ingest=None, **kw):
+        """Generator: ``colorize_images`` / ``colorize_gray`` for images with painted hint layers (``forward_async_layers``).  An item is
+        ``(image, layer_or_None, hints)``: image (h,w,3) uint8, or (h,w) uint8 or uint16; layer (lh,lw,4) uint8 RGBA of any size or ``None``;
+        hints that image's rectangle list or ``None``.  Grouping, slot alternation and order as in ``colorize_images``; a change of image kind
+        closes the group as a full batch does.  ``(rgb, cells)`` is yielded per image: the colourised image as those generators yield it and
+        the number of cells its layer hinted (0 without a layer).  ``kw``: mode, mask_value, alpha_min, cover, maskcent, l_cent, ...;
+        ``upsample`` and ``ingest`` as in ``colorize_stream``."""
+        if depth not in (8, 16) or (depth == 16 and out != "source"):
+            raise ValueError("depth must be 8, or 16 with out='source'")
+
+        def parse(item):
+            item = tuple(item)
+            if len(item) != 3:
+                raise ValueError("colorize_layers needs items (image, layer_or_None, hints)")
+            img = np.asarray(item[0])
+            if img.ndim == 3:
+                img = _image_item("colorize_layers", (img,), False)[0]
+            else:
+                img = _gray_item("colorize_layers", (img,), False)[0]
+            if depth == 16 and img.dtype != np.uint16:
+                raise ValueError("colorize_layers: depth=16 needs uint16 items, got %s" % img.dtype)
+            return img, (None if item[1] is None else _layer_array("colorize_layers", item[1])), item[2]
+
+        def submit(slot, group, first):
+            srcs = self._pinned_planes(group) if group[0][0].ndim == 2 else self._pinned_sources(group)
+            lays = [g[1] for g in group]
+            held = self._pinned_slices([l.shape for l in lays if l is not None])
+            pinned = []
+            for l in lays:
+                if l is None:
+                    pinned.append(None)
+                else:
+                    pinned.append(held[sum(1 for q in pinned if q is not None)])
+                    np.copyto(pinned[-1], l)
+            res = self.forward_async_layers(slot, srcs, pinned, [g[2] for g in group], out=out, depth=depth, **kw)
+            return res, srcs, pinned
+
+        def finish(state):
+            (rgbs, cells), _, _ = state
+            return [(np.array(r), int(c)) for r, c in zip(rgbs, cells)]
+
+        yield from self._two_slot_stream(items, batch, upsample, parse, submit, finish, key=lambda g: (g[0].ndim, g[0].dtype), ingest=ingest)
 
     def _pinned_planes(self, group):
         """The planes of a parsed group (``_gray_item``), copied into one pinned pool block; each starts on an even byte."""
