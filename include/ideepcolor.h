@@ -797,6 +797,52 @@ int idc_forward_async_layers(idc_handle h, int slot, int n, int bits /* 0: idc_r
                              const idc_batch_layers* layers, const int32_t* hint_offsets, const idc_hint* hints, int mode, float mask_value,
                              float maskcent, float l_cent, unsigned flags, const idc_batch_refs* refs, void* const* rgb_out, float* out_ab);
 
+/* ---- YCbCr 4:2:0 output planes (I420 / NV12): what a JPEG encoder (libjpeg's jpeg_write_raw_data) or a video encoder takes, made on the
+ *      device from the uint8 RGB image a call would have returned.  1.5 bytes a pixel leave the device instead of 3, and the host's colour
+ *      conversion and chroma subsampling are gone.  Opt-in: with the format IDC_OUT_RGB (the default) no launch, no plan byte and no output byte
+ *      of any call changes.
+ *      THE RULE, integers only.  Input: the [h,w,3] uint8 RGB image the call would have returned.  The Y plane is [h,w].  The chroma planes are
+ *      [ch,cw] with ch = (h + 1) / 2 and cw = (w + 1) / 2; chroma block (j, i) covers rows 2j .. min(2j+1, h-1) and columns 2i .. min(2i+1, w-1):
+ *      k = 1, 2 or 4 pixels, clipped at the image's edge, not replicated.
+ *        matrices     16.16 fixed point:
+ *                       IDC_YCC_JFIF (BT.601, full range; the constants of libjpeg's jccolor.c)
+ *                         y = (19595, 38470, 7471)   cb = (-11059, -21709, 32768)   cr = (32768, -27439, -5329)   Yoff = 0
+ *                       IDC_YCC_BT709_VIDEO (BT.709, limited range)
+ *                         y = (11966, 40254, 4064)   cb = (-6596, -22189, 28785)    cr = (28784, -26145, -2639)   Yoff = 16
+ *        per pixel    Y = ((y . (R,G,B) + 32768) >> 16) + Yoff.
+ *        per block    S_cb = the sum of cb . (R,G,B) over the block's k pixels; Cb = (S_cb + k * ((128 << 16) + 32767)) >> (16 + log2 k); Cr
+ *                     likewise.  The numerator is never negative: the shift is a floor.  For k = 1 this is libjpeg's per-pixel value.
+ *        ranges       no clamp exists or is needed: over all 2^24 colours Y, Cb, Cr lie in 0..255 (JFIF) and 16..235 / 16..240 (709), and a block
+ *                     mean cannot leave the range of its pixels.
+ *        layouts      IDC_OUT_I420: Y, then Cb, then Cr, all row-major without padding: h*w + 2*ch*cw bytes.  IDC_OUT_NV12: Y, then [ch,cw,2]
+ *                     with Cb and Cr interleaved: the same byte count.
+ *      idc_ycc420_bytes: that count; needs no handle; 0 for h or w outside 1..16384.
+ *      idc_set_batch_output: IDC_OUT_RGB (default) / IDC_OUT_I420 / IDC_OUT_NV12 and the matrix; an unknown value of either is
+ *      IDC_ERR_INVALID_ARG and changes nothing.  Handle state.  Like idc_set_batch_upsample and idc_set_ingest_filter, the pair is copied into the
+ *      slot when a pipelined call is enqueued: a batch in flight keeps what it was enqueued with.  While the format is not IDC_OUT_RGB every
+ *      image that idc_forward_async_rgb, _rgb_ref, _images, _eval, _dist, _dist_score, _gray (8-bit result) and _layers return through rgb_out /
+ *      rgb_out[i] arrives as that image's plane block, idc_ycc420_bytes(h_i, w_i) bytes in place of the 3 h_i w_i RGB bytes, at the net size and at
+ *      the source size (IDC_BATCH_OUT_SOURCE); the same-size calls receive [n][idc_ycc420_bytes(h, w)] back to back.  Everything else a call
+ *      returns (out_ab, sse, revealed colours, taps, scores) is unchanged and still derives from the RGB image.  IDC_BATCH_OUT_RGB16 together with
+ *      a YCbCr format is IDC_ERR_UNSUPPORTED, decided on the host before anything is enqueued: the slot stays usable.
+ *      On the device one post-pass kernel reads the packed RGB results the epilogue wrote and writes the blocks into an array of the slot's own,
+ *      which the copy-out stream moves in place of the RGB; idc_pipeline_times counts the kernel under compute.
+ *      idc_fullres_ycc = idc_fullres_rgb followed by the conversion: every source, interp (joint included) and l_mode, RGB and grey kept sources,
+ *      the codes of idc_fullres_rgb; a NULL out, a format that is not I420 or NV12 (IDC_OUT_RGB included) or an unknown matrix is
+ *      IDC_ERR_INVALID_ARG.  out holds idc_ycc420_bytes(src_h, src_w) bytes.
+ *      idc_rgb_to_ycc420: the conversion alone on n host images [h,w,3] uint8 of individual sizes, out[i] = image i's block.  Blocking; needs a
+ *      handle but no weights; touches none of the handle's resident state.  IDC_ERR_BATCH for n outside 1..IDC_REF_MAX; IDC_ERR_INVALID_ARG for
+ *      NULL images / out / images[i].rgb / out[i], a side outside 1..16384, more than IDC_BATCH_MAX_SOURCE_BYTES of RGB in all, an unknown
+ *      format (IDC_OUT_RGB included) or matrix.
+ *      Left out: 4:2:2 and 4:4:4, 10- and 16-bit planes, other chroma sitings or filters than the clipped box mean, YCbCr sources, the sharded
+ *      engine. */
+enum { IDC_OUT_RGB = 0, IDC_OUT_I420 = 1, IDC_OUT_NV12 = 2 };
+enum { IDC_YCC_JFIF = 0, IDC_YCC_BT709_VIDEO = 1 };
+size_t idc_ycc420_bytes(int h, int w);
+int idc_set_batch_output(idc_handle h, int format, int matrix);
+int idc_fullres_ycc(idc_handle h, int img, int source, int interp, int l_mode, int format, int matrix, uint8_t* out);
+int idc_rgb_to_ycc420(idc_handle h, int n, const idc_ref_image* images, int format, int matrix, uint8_t* const* out);
+
 /* ---- distribution scores: how much probability did the head put on the colour the pixel really has?  The question the distribution heads
  *      were trained on: the reference's training layers encode the ground-truth ab into the colour bins with NNEncode
  *      (caffe_files/color_quantization.py:7-33; NNEncLayer: NN = 1, sigma = 5, NN = 10 commented beside it, caffe_traininglayers.py:161-189) and

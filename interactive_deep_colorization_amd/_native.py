@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = [
     "idc_set_image_gray", "idc_fullres_rgb16", "idc_forward_async_gray",
     "idc_set_ingest_filter",
     "idc_set_hints_layer", "idc_forward_async_layers",
+    "idc_ycc420_bytes", "idc_set_batch_output", "idc_fullres_ycc", "idc_rgb_to_ycc420",
     "idc_set_range_audit", "idc_range_reset", "idc_range_report", "idc_pack_weights_ex", "idc_load_weights_ex",
 ]
 IDC_STORE_NONE, IDC_STORE_F32, IDC_STORE_BF16, IDC_STORE_F16 = 0, 1, 2, 3
@@ -52,6 +53,8 @@ IDC_SRC_OUTPUT_AB, IDC_SRC_OUTPUT_AB_RAW, IDC_SRC_INPUT_AB, IDC_SRC_NO_AB = 0, 1
 IDC_INGEST_KEEP_SOURCE = 1
 IDC_L_IMAGE, IDC_L_MASK50 = 0, 1
 IDC_BATCH_OUT_SOURCE = 1
+IDC_OUT_RGB, IDC_OUT_I420, IDC_OUT_NV12 = 0, 1, 2   # idc_set_batch_output / idc_fullres_ycc / idc_rgb_to_ycc420
+IDC_YCC_JFIF, IDC_YCC_BT709_VIDEO = 0, 1
 IDC_BATCH_OUT_RGB16 = 2         # idc_forward_async_gray only, 16-bit samples only
 IDC_BATCH_MAX_SOURCE_BYTES, IDC_BATCH_MAX_HINTS = 1 << 30, 1 << 20
 IDC_REF_SATURATION, IDC_REF_MAX = 1, 4096
@@ -264,6 +267,10 @@ def load():
     proto("idc_set_hints_layer", ci, [vp, ci, ci, vp, ci, cf, ctypes.POINTER(HintLayer), ci, ci, vp])
     proto("idc_forward_async_layers", ci, [vp, ci, ci, ci, vp, ctypes.POINTER(BatchLayers), vp, vp, ci, cf, cf, cf, ctypes.c_uint,
                                            ctypes.POINTER(BatchRefs), ctypes.POINTER(vp), vp])
+    proto("idc_ycc420_bytes", csz, [ci, ci])
+    proto("idc_set_batch_output", ci, [vp, ci, ci])
+    proto("idc_fullres_ycc", ci, [vp, ci, ci, ci, ci, ci, ci, vp])
+    proto("idc_rgb_to_ycc420", ci, [vp, ci, ctypes.POINTER(RefImage), ci, ci, ctypes.POINTER(vp)])
     proto("idc_set_batch_upsample", ci, [vp, ci])
     proto("idc_set_ingest_filter", ci, [vp, ci])
     proto("idc_set_range_audit", ci, [vp, ci])

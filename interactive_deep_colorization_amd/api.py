@@ -718,6 +718,19 @@ class ColorizeImageBase(object):
         self._l_serial = getattr(self.net, 'l_serial', None)      # (the call itself moved it)
         return out
 
+    def get_img_fullres_ycc(self, format='i420', matrix='jfif', interp='linear'):
+        """``get_img_fullres`` as the YCbCr 4:2:0 planes a JPEG or video encoder takes (``HipColorizer.fullres_ycc``): a ``YCC420``
+        ``(y, cb, cr, buf)`` or, with format 'nv12', an ``NV12`` ``(y, cbcr, buf)`` tuple of views into one uint8 buffer, converted on the
+        device from the image ``get_img_fullres`` (interp 'linear') or ``get_img_fullres_joint`` ('joint') returns; matrix 'jfif' or
+        'bt709'.  Not in the reference.  Device route only, as ``get_img_fullres_joint``: there is no host twin to fall back to
+        (``colorspace.rgb_to_ycc420`` converts an image the caller already has)."""
+        if not (self._out_on_device() and self._source_on_device()):
+            raise RuntimeError('get_img_fullres_ycc needs load_image_device / set_image_device and the result of the last net_forward '
+                               'on the device')
+        out = self.net.fullres_ycc('output_ab', interp, 'image', img=0, format=format, matrix=matrix)
+        self._l_serial = getattr(self.net, 'l_serial', None)      # (the call itself moved it)
+        return out
+
     def get_input_img_fullres(self):
         if self._in_on_device():
             dev = self._fullres_device('input_ab', 'linear', 'image')

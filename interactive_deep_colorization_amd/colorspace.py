@@ -139,6 +139,64 @@ def resize_antialias(img, out_h, out_w):
     return out if img.ndim == 3 else out[:, :, 0]
 
 
+# 16.16 fixed point: (luma, Cb, Cr, Yoff) of the two matrices of include/ideepcolor.h's YCbCr rule
+YCC_MATRICES = {
+    "jfif": ((19595, 38470, 7471), (-11059, -21709, 32768), (32768, -27439, -5329), 0),        # BT.601 full range, libjpeg's jccolor.c
+    "bt709": ((11966, 40254, 4064), (-6596, -22189, 28785), (28784, -26145, -2639), 16),       # BT.709 limited range
+}
+
+
+def rgb_to_ycc420(rgb, format="i420", matrix="jfif"):
+    """The host twin of the device's YCbCr 4:2:0 output (``HipColorizer.set_batch_output``; the rule: include/ideepcolor.h): rgb (h,w,3) uint8
+    -> one uint8 block of h*w + 2*ch*cw bytes, ch = (h+1)//2, cw = (w+1)//2: Y [h,w], then Cb [ch,cw] and Cr [ch,cw] ('i420') or
+    [ch,cw,2] interleaved ('nv12').  Integers only: Y = ((y.(R,G,B) + 32768) >> 16) + Yoff per pixel; a chroma block is the 2 x 2 pixels
+    clipped at the image's edge (k = 1, 2 or 4), C = (sum of c.(R,G,B) + k * ((128 << 16) + 32767)) >> (16 + log2 k)."""
+    rgb = np.asarray(rgb)
+    if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.size == 0:
+        raise ValueError("rgb_to_ycc420 needs a uint8 (h,w,3) image, got %s %s" % (rgb.dtype, rgb.shape))
+    if format not in ("i420", "nv12"):
+        raise ValueError("format is 'i420' or 'nv12', got %r" % (format,))
+    my, mcb, mcr, yoff = YCC_MATRICES[matrix]
+    h, w = rgb.shape[:2]
+    ch, cw = (h + 1) // 2, (w + 1) // 2
+    p = rgb.astype(np.int64)
+    y = ((p @ np.array(my, np.int64) + 32768) >> 16) + yoff
+    ones = np.zeros((2 * ch, 2 * cw), np.int64)
+    ones[:h, :w] = 1
+    k = ones.reshape(ch, 2, cw, 2).sum(axis=(1, 3))
+    shift = 16 + (k == 2) + 2 * (k == 4)
+    planes = []
+    for m in (mcb, mcr):
+        s = np.zeros((2 * ch, 2 * cw), np.int64)
+        s[:h, :w] = p @ np.array(m, np.int64)
+        planes.append((s.reshape(ch, 2, cw, 2).sum(axis=(1, 3)) + k * ((128 << 16) + 32767)) >> shift)
+    chroma = np.stack(planes, axis=-1) if format == "nv12" else np.stack(planes, axis=0)
+    return np.concatenate([y.reshape(-1), chroma.reshape(-1)]).astype(np.uint8)
+
+
+def ycc420_to_rgb(buf, h, w, format="i420", matrix="jfif"):
+    """The inverse of ``rgb_to_ycc420`` for display: every chroma sample is repeated over its block (nearest), the matrix is inverted in
+    float64 and the result rounded and clamped to uint8 -> (h,w,3).  Not bit-exact: 4:2:0 discards chroma resolution."""
+    h, w = int(h), int(w)
+    ch, cw = (h + 1) // 2, (w + 1) // 2
+    buf = np.asarray(buf, np.uint8).reshape(-1)
+    if buf.size < h * w + 2 * ch * cw:
+        raise ValueError("ycc420_to_rgb needs %d bytes, got %d" % (h * w + 2 * ch * cw, buf.size))
+    my, mcb, mcr, yoff = YCC_MATRICES[matrix]
+    y = buf[:h * w].reshape(h, w).astype(np.float64) - yoff
+    c = buf[h * w:h * w + 2 * ch * cw]
+    if format == "nv12":
+        cb, cr = c.reshape(ch, cw, 2)[..., 0], c.reshape(ch, cw, 2)[..., 1]
+    elif format == "i420":
+        cb, cr = c[:ch * cw].reshape(ch, cw), c[ch * cw:].reshape(ch, cw)
+    else:
+        raise ValueError("format is 'i420' or 'nv12', got %r" % (format,))
+    up = lambda a: np.repeat(np.repeat(a.astype(np.float64) - 128.0, 2, axis=0), 2, axis=1)[:h, :w]
+    ycc = np.stack([y, up(cb), up(cr)], axis=-1)
+    inv = np.linalg.inv(np.array([my, mcb, mcr], np.float64) / 65536.0)
+    return np.clip(np.floor(ycc @ inv.T + 0.5), 0, 255).astype(np.uint8)
+
+
 def imread_rgb(path):
     """``cv2.cvtColor(cv2.imread(path, 1), cv2.COLOR_BGR2RGB)`` -> (H,W,3) uint8 RGB."""
     from PIL import Image

@@ -1003,7 +1003,9 @@ int idc_set_image_gray(idc_handle h, int img, int n, int src_h, int src_w, int b
 
 // idc_fullres_rgb / idc_fullres_rgb16 (rgb; out_bits 8 | 16) and idc_fullres_ab (ab): one list of checks, one residency rule.  A kept greyscale
 // source (SlotSource::gray_bits) is served by the grey kernels.
-static int fullres(idc_handle h, int img, int source, int interp, int l_mode, void* rgb, int out_bits, double* ab, bool want_ab) {
+// ycc_format != IDC_OUT_RGB (idc_fullres_ycc): rgb receives the image's plane block, made from the RGB result where the kernels below left it.
+static int fullres(idc_handle h, int img, int source, int interp, int l_mode, void* rgb, int out_bits, double* ab, bool want_ab,
+                   int ycc_format = IDC_OUT_RGB, int ycc_matrix = IDC_YCC_JFIF) {
     int rc = check_img(h, img);
     if (rc) return rc;
     if (interp < 0 || interp > IDC_INTERP_JOINT) return fail(&h->err, IDC_ERR_INVALID_ARG, "interp %d not in 0..3", interp);
@@ -1050,7 +1052,7 @@ static int fullres(idc_handle h, int img, int source, int interp, int l_mode, vo
         HIPCHK(h, hipStreamSynchronize(h->stream.get()));
         HIPCHK(h, h->d_full_rgb.ensure(nbytes));
     }
-    if (!direct) HIPCHK(h, h->h_full_rgb.ensure(h->d_full_rgb.bytes()));
+    if (!direct && ycc_format == IDC_OUT_RGB) HIPCHK(h, h->h_full_rgb.ensure(h->d_full_rgb.bytes()));
     const float* mask = l_mode == IDC_L_MASK50 ? h->d_mask.get() + (size_t)img * hw : nullptr;
     if (sl.gray_bits && interp == IDC_INTERP_JOINT && pa)
         HIPCHK(h, launch_gray_joint_fullres(sl.d_rgb.get(), sl.gray_bits, nullptr, 1, sl.h, sl.w, joint_tiles(sl.h, sl.w), pa, pb, f64, 0,
@@ -1065,6 +1067,23 @@ static int fullres(idc_handle h, int img, int source, int interp, int l_mode, vo
     else        // (IDC_SRC_NO_AB has nothing to interpolate: a = b = 0 whatever the interp)
         HIPCHK(h, launch_fullres_rgb(sl.d_rgb.get(), sl.h, sl.w, pa, pb, f64, h->H, h->W, interp == IDC_INTERP_JOINT ? IDC_INTERP_LINEAR : interp, mask,
                                      h->hint_mask_value[img], h->d_full_rgb.get(), h->stream.get()));
+    if (ycc_format != IDC_OUT_RGB) {      // the post-pass on the one image, and its block instead of the RGB
+        const size_t yb = ycc420_bytes(sl.h, sl.w);
+        HIPCHK(h, hipStreamSynchronize(h->stream.get()));            // the table of the previous call may still be in flight
+        HIPCHK(h, h->d_ycc.ensure(yb, 65536));
+        HIPCHK(h, h->d_ycc_meta.ensure(sizeof(YccDesc), 4096));
+        HIPCHK(h, h->h_ycc_meta.ensure(sizeof(YccDesc), 4096));
+        if (!direct) HIPCHK(h, h->h_ycc.ensure(h->d_ycc.bytes()));
+        const YccDesc d = {0, 0, sl.h, sl.w};
+        memcpy(h->h_ycc_meta.get(), &d, sizeof(d));
+        HIPCHK(h, hipMemcpyAsync(h->d_ycc_meta.get(), h->h_ycc_meta.get(), sizeof(d), hipMemcpyHostToDevice, h->stream.get()));
+        HIPCHK(h, launch_ycc420(h->d_full_rgb.get(), (const YccDesc*)h->d_ycc_meta.get(), 1, ycc_blocks(sl.h, sl.w), ycc_format, ycc_matrix,
+                                h->d_ycc.get(), h->stream.get()));
+        HIPCHK(h, hipMemcpyAsync(direct ? rgb : h->h_ycc.get(), h->d_ycc.get(), yb, hipMemcpyDeviceToHost, h->stream.get()));
+        HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+        if (!direct) memcpy(rgb, h->h_ycc.get(), yb);
+        return IDC_OK;
+    }
     HIPCHK(h, hipMemcpyAsync(direct ? rgb : h->h_full_rgb.get(), h->d_full_rgb.get(), nbytes, hipMemcpyDeviceToHost, h->stream.get()));
     HIPCHK(h, hipStreamSynchronize(h->stream.get()));
     if (!direct) memcpy(rgb, h->h_full_rgb.get(), nbytes);
@@ -1110,6 +1129,89 @@ int idc_set_ingest_filter(idc_handle h, int filter) {
     if (filter != IDC_FILTER_BILINEAR && filter != IDC_FILTER_ANTIALIAS)
         return fail(&h->err, IDC_ERR_INVALID_ARG, "filter %d is neither IDC_FILTER_BILINEAR nor IDC_FILTER_ANTIALIAS", filter);
     h->ingest_filter = filter;
+    return IDC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- YCbCr 4:2:0 output
+static bool ycc_format_ok(int format) { return format == IDC_OUT_I420 || format == IDC_OUT_NV12; }
+static bool ycc_matrix_ok(int matrix) { return matrix == IDC_YCC_JFIF || matrix == IDC_YCC_BT709_VIDEO; }
+
+size_t idc_ycc420_bytes(int h, int w) { return ycc420_bytes(h, w); }
+
+int idc_set_batch_output(idc_handle h, int format, int matrix) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (format != IDC_OUT_RGB && !ycc_format_ok(format))
+        return fail(&h->err, IDC_ERR_INVALID_ARG, "format %d is none of IDC_OUT_RGB, IDC_OUT_I420, IDC_OUT_NV12", format);
+    if (!ycc_matrix_ok(matrix)) return fail(&h->err, IDC_ERR_INVALID_ARG, "matrix %d is neither IDC_YCC_JFIF nor IDC_YCC_BT709_VIDEO", matrix);
+    h->out_format = format; h->out_matrix = matrix;
+    return IDC_OK;
+}
+
+int idc_fullres_ycc(idc_handle h, int img, int source, int interp, int l_mode, int format, int matrix, uint8_t* out) {
+    int rc = check_img(h, img);
+    if (rc) return rc;
+    if (!ycc_format_ok(format)) return fail(&h->err, IDC_ERR_INVALID_ARG, "format %d is neither IDC_OUT_I420 nor IDC_OUT_NV12", format);
+    if (!ycc_matrix_ok(matrix)) return fail(&h->err, IDC_ERR_INVALID_ARG, "matrix %d is neither IDC_YCC_JFIF nor IDC_YCC_BT709_VIDEO", matrix);
+    return fullres(h, img, source, interp, l_mode, out, 8, nullptr, false, format, matrix);
+}
+
+// The conversion alone: the images packed back to back into one upload, one launch, the blocks packed back to back into one copy back
+int idc_rgb_to_ycc420(idc_handle h, int n, const idc_ref_image* images, int format, int matrix, uint8_t* const* out) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (n < 1 || n > IDC_REF_MAX) return fail(&h->err, IDC_ERR_BATCH, "%d images outside 1..%d", n, IDC_REF_MAX);
+    if (!images || !out) return fail(&h->err, IDC_ERR_INVALID_ARG, "null image table");
+    if (!ycc_format_ok(format)) return fail(&h->err, IDC_ERR_INVALID_ARG, "format %d is neither IDC_OUT_I420 nor IDC_OUT_NV12", format);
+    if (!ycc_matrix_ok(matrix)) return fail(&h->err, IDC_ERR_INVALID_ARG, "matrix %d is neither IDC_YCC_JFIF nor IDC_YCC_BT709_VIDEO", matrix);
+    size_t in_bytes = 0, out_bytes = 0;
+    int max_blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!images[i].rgb || !out[i]) return fail(&h->err, IDC_ERR_INVALID_ARG, "image %d: null pointer", i);
+        if (images[i].h < 1 || images[i].h > kYccMaxSide || images[i].w < 1 || images[i].w > kYccMaxSide)
+            return fail(&h->err, IDC_ERR_INVALID_ARG, "image %d: size %dx%d outside 1..%d", i, images[i].h, images[i].w, kYccMaxSide);
+        in_bytes += (size_t)images[i].h * images[i].w * 3;
+        out_bytes += ycc420_bytes(images[i].h, images[i].w);
+        max_blocks = max_blocks > ycc_blocks(images[i].h, images[i].w) ? max_blocks : ycc_blocks(images[i].h, images[i].w);
+    }
+    if (in_bytes > IDC_BATCH_MAX_SOURCE_BYTES)
+        return fail(&h->err, IDC_ERR_INVALID_ARG, "%d images hold %zu bytes, more than %zu", n, in_bytes, (size_t)IDC_BATCH_MAX_SOURCE_BYTES);
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = drain_pipeline(h);
+    if (rc) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));                // the buffers of the previous call may still be in flight
+    const size_t meta_bytes = (size_t)n * sizeof(YccDesc);
+    HIPCHK(h, h->d_ycc_in.ensure(in_bytes, 65536));
+    HIPCHK(h, h->h_ycc_in.ensure(in_bytes, 65536));
+    HIPCHK(h, h->d_ycc.ensure(out_bytes, 65536));
+    HIPCHK(h, h->h_ycc.ensure(h->d_ycc.bytes()));
+    HIPCHK(h, h->d_ycc_meta.ensure(meta_bytes, 4096));
+    HIPCHK(h, h->h_ycc_meta.ensure(meta_bytes, 4096));
+    YccDesc* tab = (YccDesc*)h->h_ycc_meta.get();
+    size_t src = 0, dst = 0;
+    for (int i = 0; i < n; ++i) {
+        const size_t sb = (size_t)images[i].h * images[i].w * 3;
+        tab[i].src = (long long)src; tab[i].dst = (long long)dst; tab[i].h = images[i].h; tab[i].w = images[i].w;
+        memcpy(h->h_ycc_in.get() + src, images[i].rgb, sb);
+        src += sb; dst += ycc420_bytes(images[i].h, images[i].w);
+    }
+    HIPCHK(h, hipMemcpyAsync(h->d_ycc_meta.get(), h->h_ycc_meta.get(), meta_bytes, hipMemcpyHostToDevice, h->stream.get()));
+    HIPCHK(h, hipMemcpyAsync(h->d_ycc_in.get(), h->h_ycc_in.get(), in_bytes, hipMemcpyHostToDevice, h->stream.get()));
+    HIPCHK(h, launch_ycc420(h->d_ycc_in.get(), (const YccDesc*)h->d_ycc_meta.get(), n, max_blocks, format, matrix, h->d_ycc.get(), h->stream.get()));
+    // a pinned destination is written in place, the pageable ones through the pinned twin: neighbouring pageable blocks as one copy
+    size_t run0 = 0, run1 = 0;
+    for (int i = 0; i <= n; ++i) {
+        const bool direct = i < n && is_pinned(out[i]);
+        if (i == n || direct) {
+            if (run1 != run0) HIPCHK(h, hipMemcpyAsync(h->h_ycc.get() + run0, h->d_ycc.get() + run0, run1 - run0, hipMemcpyDeviceToHost, h->stream.get()));
+            if (i == n) break;
+            HIPCHK(h, hipMemcpyAsync(out[i], h->d_ycc.get() + (size_t)tab[i].dst, ycc420_bytes(tab[i].h, tab[i].w), hipMemcpyDeviceToHost, h->stream.get()));
+            run0 = run1 = (size_t)tab[i].dst + ycc420_bytes(tab[i].h, tab[i].w);
+        } else {
+            run1 = (size_t)tab[i].dst + ycc420_bytes(tab[i].h, tab[i].w);
+        }
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream.get()));
+    for (int i = 0; i < n; ++i)
+        if (!is_pinned(out[i])) memcpy(out[i], h->h_ycc.get() + (size_t)tab[i].dst, ycc420_bytes(tab[i].h, tab[i].w));
     return IDC_OK;
 }
 

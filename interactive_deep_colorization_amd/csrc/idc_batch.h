@@ -56,6 +56,8 @@ struct BatchCall {
     // the table [n] (rgba NULL: that image has no layer), the two parameters of the rule, and where the cell counts go (or nullptr).  Without it
     // every byte of the plan and of the block is as it was.
     bool has_layers = false; const idc_hint_layer* layers = nullptr; int alpha_min = 0, cover = 0; int32_t* cells = nullptr;
+    // the handle's output format and matrix as the call was enqueued (idc_set_batch_output): IDC_OUT_RGB leaves every byte of the plan as it was
+    int out_format = IDC_OUT_RGB, out_matrix = IDC_YCC_JFIF;
 };
 
 inline void set_batch_layers(BatchCall& c, const idc_batch_layers* l) {
@@ -108,7 +110,21 @@ struct BatchPlan {
     size_t layer_bytes = 0, layers_at = 0;
     std::vector<Piece> layer_pieces;
     bool cells_pinned = false;           // the caller's to fill in, as ab_pinned
+    // YCbCr 4:2:0 output (c.out_format != IDC_OUT_RGB and the images leave the device; else ycc_bytes == 0 and everything above is the whole
+    // plan): every image's plane block (idc_ycc.h) packed back to back, in image order and without padding, in a device array of the slot's OWN,
+    // ycc_bytes of it.  The pieces' out_at / out_bytes then name THAT array: what travels back is the blocks, not the RGB, which stays where the
+    // epilogue wrote it (rgb_bytes still sizes it).  Appended to the metadata block, behind everything above: YccDesc[n] at ycc_at.
+    // ycc_blocks = grid.x of the post-pass: the largest ycc_blocks among the images.
+    size_t ycc_bytes = 0, ycc_at = 0;
+    int ycc_blocks = 0;
 };
+
+// image i's size as its result has it: the source's own (IDC_BATCH_OUT_SOURCE) or the net's
+inline void batch_out_size(const BatchCall& c, int i, int H, int W, int* oh, int* ow) {
+    const bool source_out = (c.flags & IDC_BATCH_OUT_SOURCE) != 0;
+    *oh = !source_out ? H : c.ragged ? batch_image(c, i).h : c.src_h;
+    *ow = !source_out ? W : c.ragged ? batch_image(c, i).w : c.src_w;
+}
 
 inline int plan_fail(std::string* err, int code, const char* fmt, ...) {
     char buf[512];
@@ -140,6 +156,12 @@ inline int plan_batch(const BatchCall& c, int H, int W, int max_batch, BatchPlan
     if (gray && c.mode == IDC_HINT_REVEAL) return plan_fail(err, IDC_ERR_INVALID_ARG, "IDC_HINT_REVEAL: a greyscale source has no colour to reveal");
     if (c.out_bits == 16 && c.gray_bits != 16) return plan_fail(err, IDC_ERR_INVALID_ARG, "IDC_BATCH_OUT_RGB16 needs 16-bit samples, not %d-bit ones", c.gray_bits);
     if (c.out_bits == 16 && !(c.flags & IDC_BATCH_OUT_SOURCE)) return plan_fail(err, IDC_ERR_INVALID_ARG, "IDC_BATCH_OUT_RGB16 without IDC_BATCH_OUT_SOURCE: the net-size result is 8-bit");
+    if (c.out_format != IDC_OUT_RGB && c.out_format != IDC_OUT_I420 && c.out_format != IDC_OUT_NV12)
+        return plan_fail(err, IDC_ERR_INVALID_ARG, "output format %d", c.out_format);
+    if (c.out_format != IDC_OUT_RGB && c.out_matrix != IDC_YCC_JFIF && c.out_matrix != IDC_YCC_BT709_VIDEO)
+        return plan_fail(err, IDC_ERR_INVALID_ARG, "YCbCr matrix %d", c.out_matrix);
+    if (c.out_format != IDC_OUT_RGB && c.out_bits == 16)
+        return plan_fail(err, IDC_ERR_UNSUPPORTED, "IDC_BATCH_OUT_RGB16 with a YCbCr output format: the planes are 8-bit");
     p->bpp_in = gray ? c.gray_bits / 8 : 3;
     p->bpp_out = c.out_bits == 16 ? 6 : 3;
     size_t full_bytes = 0;               // the packed source-size results
@@ -259,6 +281,19 @@ inline int plan_batch(const BatchCall& c, int H, int W, int max_batch, BatchPlan
         p->layers_at = batch_align16(p->meta_bytes);
         p->meta_bytes = p->layers_at + nb * sizeof(LayerDesc);
     }
+    if (c.out_format != IDC_OUT_RGB && p->want_rgb) {
+        for (int i = 0; i < n; ++i) {
+            int oh, ow;
+            batch_out_size(c, i, H, W, &oh, &ow);
+            const size_t yb = ycc420_bytes(oh, ow);
+            if (c.ragged) { p->pieces[i].out_at = p->ycc_bytes; p->pieces[i].out_bytes = yb; }
+            p->ycc_bytes += yb;
+            p->ycc_blocks = p->ycc_blocks > ycc_blocks(oh, ow) ? p->ycc_blocks : ycc_blocks(oh, ow);
+        }
+        if (!c.ragged) p->pieces[0].out_bytes = p->ycc_bytes;
+        p->ycc_at = batch_align16(p->meta_bytes);
+        p->meta_bytes = p->ycc_at + (size_t)n * sizeof(YccDesc);
+    }
     return IDC_OK;
 }
 
@@ -309,6 +344,16 @@ inline void fill_batch_meta(const BatchCall& c, const BatchPlan& p, int H, int W
             const bool has = i < c.n && c.layers[i].rgba != nullptr;
             tab[i].off = has ? (long long)p.layer_pieces[k++].in_at : 0;
             tab[i].h = has ? c.layers[i].h : 0; tab[i].w = has ? c.layers[i].w : 0;
+        }
+    }
+    if (p.ycc_bytes > 0) {                          // the output post-pass's table: where each image's RGB lies in the packed results, and its block
+        YccDesc* tab = (YccDesc*)(h_meta + p.ycc_at);
+        size_t src = 0, dst = 0;
+        for (int i = 0; i < c.n; ++i) {
+            int oh, ow;
+            batch_out_size(c, i, H, W, &oh, &ow);
+            tab[i].src = (long long)src; tab[i].dst = (long long)dst; tab[i].h = oh; tab[i].w = ow;
+            src += (size_t)oh * ow * 3; dst += ycc420_bytes(oh, ow);
         }
     }
 }

@@ -225,6 +225,12 @@ struct idc_context {
     // joint bilateral upsampling: idc_set_joint_upsample's parameters and idc_set_batch_upsample's interp; a pipelined call takes its copy when it is enqueued
     JointParams joint = {2, 2.0 * 1.0 * 1.0, 2.0 * 8.0 * 8.0};
     int batch_interp = 1;                // IDC_INTERP_LINEAR
+    // YCbCr 4:2:0 output (idc_set_batch_output; a pipelined call takes its copy of the pair when it is enqueued), and what the two blocking calls
+    // work in: idc_fullres_ycc's / idc_rgb_to_ycc420's packed plane blocks, the YccDesc table of one launch and idc_rgb_to_ycc420's packed RGB,
+    // device and pinned, grown on demand: both calls block, so nothing is in flight when they grow
+    int out_format = 0, out_matrix = 0;  // IDC_OUT_RGB, IDC_YCC_JFIF
+    DevMem<unsigned char> d_ycc, d_ycc_meta, d_ycc_in;
+    PinnedMem<unsigned char> h_ycc, h_ycc_meta, h_ycc_in;
     DevMem<unsigned char> d_pick;        // idc_gamut_map / idc_snap_colors: inputs + results of one call, device and pinned
     PinnedMem<unsigned char> h_pick;
     Event ev_sync;                       // idc_stream_wait / idc_stream_signal
@@ -270,6 +276,8 @@ struct idc_context {
         // idc_forward_async_layers: the batch's packed RGBA layers (BatchPlan::layer_pieces) and the cell counts int32[max_batch], device and pinned
         DevMem<unsigned char> d_layer, d_cells;
         PinnedMem<unsigned char> h_layer, h_cells;
+        // idc_set_batch_output: the batch's packed plane blocks (BatchPlan::ycc_bytes), which leave the device in place of d_rgb / d_full
+        DevMem<unsigned char> d_ycc;
     } pipe[2];
     Event ev_pipe_base;
     bool pipe_ready = false;             // ev_pipe_base is recorded (ensure_pipeline)

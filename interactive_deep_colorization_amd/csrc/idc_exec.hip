@@ -723,7 +723,8 @@ static int batch_reserve(idc_context* h, const BatchCall& c, const BatchPlan& p,
     bool any_staged_in = false, any_staged_rgb = false;
     for (const Piece& q : p.pieces) { any_staged_in |= !q.in_pinned; any_staged_rgb |= !q.out_pinned; }
     if (any_staged_in) HIPCHK(h, sl.h_src.ensure(p.in_bytes));
-    if (any_staged_rgb) HIPCHK(h, sl.h_rgb.ensure(p.rgb_bytes));
+    if (any_staged_rgb) HIPCHK(h, sl.h_rgb.ensure(p.ycc_bytes ? p.ycc_bytes : p.rgb_bytes));
+    if (p.ycc_bytes) HIPCHK(h, sl.d_ycc.ensure(p.ycc_bytes, 65536));
     if (!p.ab_pinned) HIPCHK(h, sl.h_out.ensure(nb * hw * 2 * 4));
     if (c.has_refs) HIPCHK(h, sl.d_glob_in.ensure(nb * kGlobIn * sizeof(float)));
     if (c.has_layers) {   // the packed layers in an array of their own, and the cell counts
@@ -867,6 +868,10 @@ static int batch_measure(idc_context* h, const BatchCall& c, const BatchPlan& p,
         const int rc = launch_score(h, L.geom, L.score, (const float*)sl.d_score_in.get(), sl.d_score.get(), s);
         if (rc) return rc;
     }
+    // the output format's post-pass: behind the epilogue and the score, which read and leave the RGB, and in front of the slot's D2H event
+    if (p.ycc_bytes)
+        HIPCHK(h, launch_ycc420(p.source_out ? sl.d_full.get() : sl.d_rgb.get(), (const YccDesc*)(sl.d_meta.get() + p.ycc_at), n, p.ycc_blocks,
+                                c.out_format, c.out_matrix, sl.d_ycc.get(), s));
     return IDC_OK;
 }
 
@@ -914,7 +919,7 @@ static int batch_copy_out(idc_context* h, const BatchCall& c, const BatchPlan& p
     }
     if (c.has_layers && c.cells) HIPCHK(h, copy_out(h, sl, c.cells, p.cells_pinned, sl.d_cells.get(), sl.h_cells.get(), 0, n * sizeof(int32_t)));
     if (p.want_rgb) {
-        HIPCHK(h, copy_pieces(p.pieces, false, p.source_out ? sl.d_full.get() : sl.d_rgb.get(), sl.h_rgb.get(), h->s_out.get()));
+        HIPCHK(h, copy_pieces(p.pieces, false, p.ycc_bytes ? sl.d_ycc.get() : p.source_out ? sl.d_full.get() : sl.d_rgb.get(), sl.h_rgb.get(), h->s_out.get()));
         for (const Piece& q : p.pieces)
             if (!q.out_pinned) sl.outs.push_back({q.out, sl.h_rgb.get() + q.out_at, q.out_bytes});
     }
@@ -930,6 +935,7 @@ static int forward_async_rgb(idc_handle h, const BatchCall& call) {
     if (rc) return rc;
     BatchCall c = call;
     c.ingest_filter = h->ingest_filter;       // the handle's setting as it is now: a later idc_set_ingest_filter does not reach this batch
+    c.out_format = h->out_format; c.out_matrix = h->out_matrix;      // ... and so with idc_set_batch_output
     BatchPlan p;
     std::string why;
     rc = plan_batch(c, h->H, h->W, h->max_batch, &p, &why);

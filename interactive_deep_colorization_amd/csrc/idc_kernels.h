@@ -9,6 +9,7 @@
 #include "idc_grid.h"
 #include "idc_resample.h"
 #include "idc_layer.h"
+#include "idc_ycc.h"
 
 namespace idc {
 
@@ -361,6 +362,13 @@ hipError_t launch_resample(const void* src_base, void* dst_base, const ResampleJ
 // zeroes it on the same stream).  Exact grid dim3(max_blocks, n), max_blocks = the largest layer_blocks among the layers.
 hipError_t launch_hint_layers(const unsigned char* layers, const LayerDesc* descs, int n, int max_blocks, int H, int W, int alpha_min, int cover,
                               float mask_value, float* ab, float* mask, int* cells, hipStream_t s);
+
+// YCbCr 4:2:0 output planes (idc_set_batch_output / idc_fullres_ycc / idc_rgb_to_ycc420; idc_ycc.hip; the rule: include/ideepcolor.h): the
+// post-pass behind the epilogues.  rgb = the packed [h,w,3] u8 results from a 4-byte aligned base, descs [n] (YccDesc, idc_ycc.h: where image
+// i's RGB starts in rgb and its plane block in out, and its size); out = the packed blocks from a 4-byte aligned base; format IDC_OUT_I420 |
+// IDC_OUT_NV12, matrix IDC_YCC_*.  Exact grid dim3(max_blocks, n), max_blocks = the largest ycc_blocks among the images.
+hipError_t launch_ycc420(const unsigned char* rgb, const YccDesc* descs, int n, int max_blocks, int format, int matrix, unsigned char* out,
+                         hipStream_t s);
 
 // Evaluation batches (idc_reveal_hints / idc_forward_async_eval; idc_colour.hip).  reveal_hints: (c0, c1) of each of the n_rects clipped
 // rectangles of `hints` = the float64 mean ab (rounded once to fp32) of its image's net-size pixels under it, one workgroup per rectangle, fixed

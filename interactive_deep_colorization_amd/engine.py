@@ -6,6 +6,7 @@ reference returns at ``data/colorize_image.py:263``.  All arithmetic happens in
 the HIP library behind the C ABI (``include/ideepcolor.h``); this file only
 marshals numpy arrays and weight dictionaries.
 """
+import collections
 import ctypes
 import threading
 
@@ -22,6 +23,31 @@ _PREC = {"fp32": N.IDC_FP32, "f32": N.IDC_FP32, "float32": N.IDC_FP32, 0: N.IDC_
 
 _INTERP = {"cubic": N.IDC_INTERP_CUBIC, "linear": N.IDC_INTERP_LINEAR, "nearest": N.IDC_INTERP_NEAREST, "joint": N.IDC_INTERP_JOINT}
 _INGEST_FILTER = {"bilinear": N.IDC_FILTER_BILINEAR, "antialias": N.IDC_FILTER_ANTIALIAS}
+_OUT_FORMAT = {"rgb": N.IDC_OUT_RGB, "i420": N.IDC_OUT_I420, "nv12": N.IDC_OUT_NV12}
+_YCC_MATRIX = {"jfif": N.IDC_YCC_JFIF, "bt709": N.IDC_YCC_BT709_VIDEO}
+YCC420 = collections.namedtuple("YCC420", "y cb cr buf")       # I420: views [h,w], [ch,cw], [ch,cw] into ``buf``, one uint8 block
+NV12 = collections.namedtuple("NV12", "y cbcr buf")            # NV12: views [h,w], [ch,cw,2] into ``buf``
+
+
+def ycc420_bytes(h, w):
+    """Bytes of one image's 4:2:0 plane block (``idc_ycc420_bytes``): h*w + 2*((h+1)//2)*((w+1)//2); 0 for a side outside 1..16384."""
+    return int(N.load().idc_ycc420_bytes(int(h), int(w)))
+
+
+def ycc420_views(buf, h, w, format="i420"):
+    """The planes of one image's block as numpy views into ``buf`` (uint8, at least ``ycc420_bytes(h, w)`` long): a ``YCC420``
+    ``(y, cb, cr, buf)`` for 'i420', an ``NV12`` ``(y, cbcr, buf)`` for 'nv12'."""
+    h, w = int(h), int(w)
+    ch, cw = (h + 1) // 2, (w + 1) // 2
+    buf = np.asarray(buf).reshape(-1)
+    if buf.dtype != np.uint8 or buf.size < h * w + 2 * ch * cw:
+        raise ValueError("ycc420_views needs a uint8 buffer of %d bytes" % (h * w + 2 * ch * cw))
+    y = buf[:h * w].reshape(h, w)
+    if format == "nv12":
+        return NV12(y, buf[h * w:h * w + 2 * ch * cw].reshape(ch, cw, 2), buf)
+    if format != "i420":
+        raise ValueError("format is 'i420' or 'nv12', got %r" % (format,))
+    return YCC420(y, buf[h * w:h * w + ch * cw].reshape(ch, cw), buf[h * w + ch * cw:h * w + 2 * ch * cw].reshape(ch, cw), buf)
 
 
 def _fptr(a):
@@ -483,6 +509,8 @@ def _gray_item(who, item, with_ref):
 
 
 class HipColorizer(object):
+    _out_format, _out_matrix = "rgb", "jfif"    # what set_batch_output last set (class defaults: an engine that never called it)
+
     def __init__(self, H=256, W=None, max_batch=1, precision="bf16", device=0, dist=False, global_hints=False, dist313=False,
                  throughput_blob=False):
         self.lib = N.load()
@@ -815,6 +843,83 @@ class HipColorizer(object):
         prev = self._ingest_filter
         self.set_ingest_filter(ingest)
         return prev
+
+    def set_batch_output(self, format="rgb", matrix="jfif"):
+        """What the pipelined calls return as images (``idc_set_batch_output``): 'rgb' (default: interleaved uint8 RGB), or the YCbCr 4:2:0
+        plane block of every image, 'i420' (Y, Cb, Cr) or 'nv12' (Y, interleaved CbCr), by ``matrix`` 'jfif' (BT.601 full range, what a JPEG
+        encoder takes) or 'bt709' (BT.709 limited range, video); the rule stands in ``include/ideepcolor.h`` and ``colorspace.rgb_to_ycc420``
+        is its host twin.  While it is not 'rgb' every ``out_rgb`` of the ``forward_async_*`` calls is a flat uint8 array of
+        ``ycc420_bytes(h, w)`` per image ((n, bytes) for ``forward_async_rgb``); ``ycc420_views`` gives the planes.  Handle state; a batch in
+        flight keeps what it was enqueued with."""
+        if format not in _OUT_FORMAT:
+            raise ValueError("set_batch_output takes 'rgb', 'i420' or 'nv12', got %r" % (format,))
+        if matrix not in _YCC_MATRIX:
+            raise ValueError("set_batch_output takes the matrix 'jfif' or 'bt709', got %r" % (matrix,))
+        self._chk(self.lib.idc_set_batch_output(self._h, _OUT_FORMAT[format], _YCC_MATRIX[matrix]))
+        self._out_format, self._out_matrix = format, matrix
+
+    def _output_scope(self, out_format, out_matrix):
+        """The ``out_format=`` / ``out_matrix=`` keywords of the streaming generators: set the state now, return what to restore (None: leave
+        it alone)."""
+        if out_format is None and out_matrix is None:
+            return None
+        prev = (self._out_format, self._out_matrix)
+        self.set_batch_output(prev[0] if out_format is None else out_format, prev[1] if out_matrix is None else out_matrix)
+        return prev
+
+    def _out_shapes(self, shapes, depth=8):
+        """The shapes of a pipelined call's image outputs under the output format in effect: (h,w,3) each, or flat plane blocks."""
+        if self._out_format == "rgb" or depth != 8:     # (16-bit RGB with a YCbCr format: the library refuses the call)
+            return shapes
+        return [(ycc420_bytes(s[0], s[1]),) for s in shapes]
+
+    def _own_image(self, r, hw):
+        """A generator's copy of one image result: the (h,w,3) array, or the planes of its block (``YCC420`` / ``NV12``) over one copy."""
+        if r.ndim != 1:
+            return np.array(r)
+        return ycc420_views(np.array(r), hw[0], hw[1], self._out_format)
+
+    def ycc420_bytes(self, h, w):
+        return ycc420_bytes(h, w)
+
+    def fullres_ycc(self, source="output_ab", interp="linear", l_mode="image", img=0, format="i420", matrix="jfif"):
+        """``fullres_rgb`` whose image arrives as its YCbCr 4:2:0 plane block (``idc_fullres_ycc``): a ``YCC420`` / ``NV12`` tuple of views
+        into one uint8 buffer, at the kept source's size.  Every source, interp ('joint' included) and l_mode of ``fullres_rgb``; RGB and grey
+        kept sources."""
+        if format not in ("i420", "nv12") or matrix not in _YCC_MATRIX:
+            raise ValueError("fullres_ycc takes format 'i420' | 'nv12' and matrix 'jfif' | 'bt709'")
+        shape = self._src_shape.get(int(img))
+        if shape is None:
+            raise N.IdcError(-7, "the source of image slot %d was not ingested through this object" % img)
+        buf = np.empty(ycc420_bytes(shape[0], shape[1]), np.uint8)
+        src = {"output_ab": N.IDC_SRC_OUTPUT_AB, "output_ab_raw": N.IDC_SRC_OUTPUT_AB_RAW, "input_ab": N.IDC_SRC_INPUT_AB,
+               "no_ab": N.IDC_SRC_NO_AB}[source]
+        lm = {"image": N.IDC_L_IMAGE, "mask50": N.IDC_L_MASK50}[l_mode]
+        self.l_serial += 1
+        self._chk(self.lib.idc_fullres_ycc(self._h, int(img), src, _INTERP[interp], lm, _OUT_FORMAT[format], _YCC_MATRIX[matrix],
+                                           buf.ctypes.data_as(ctypes.c_void_p)))
+        return ycc420_views(buf, shape[0], shape[1], format)
+
+    def rgb_to_ycc420(self, images, format="i420", matrix="jfif"):
+        """The conversion alone on the device (``idc_rgb_to_ycc420``): ``images`` is one (h,w,3) uint8 array or a list of them, each of its
+        own size; a ``YCC420`` / ``NV12`` tuple per image comes back (one tuple for one array).  Blocking; needs no weights."""
+        if format not in ("i420", "nv12") or matrix not in _YCC_MATRIX:
+            raise ValueError("rgb_to_ycc420 takes format 'i420' | 'nv12' and matrix 'jfif' | 'bt709'")
+        single = isinstance(images, np.ndarray) and images.ndim == 3
+        arrs = [np.ascontiguousarray(a, np.uint8) for a in ([images] if single else images)]
+        for a in arrs:
+            if a.ndim != 3 or a.shape[2] != 3 or a.size == 0:
+                raise ValueError("rgb_to_ycc420 needs (h,w,3) uint8 arrays")
+        n = len(arrs)
+        table = (N.RefImage * max(n, 1))()
+        outs = (ctypes.c_void_p * max(n, 1))()
+        bufs = [np.empty(ycc420_bytes(a.shape[0], a.shape[1]), np.uint8) for a in arrs]
+        for i, (a, b) in enumerate(zip(arrs, bufs)):
+            table[i].rgb, table[i].h, table[i].w = a.ctypes.data, a.shape[0], a.shape[1]
+            outs[i] = b.ctypes.data
+        self._chk(self.lib.idc_rgb_to_ycc420(self._h, n, table, _OUT_FORMAT[format], _YCC_MATRIX[matrix], outs))
+        res = [ycc420_views(b, a.shape[0], a.shape[1], format) for a, b in zip(arrs, bufs)]
+        return res[0] if single else res
 
     # ---- colour picker (data/lab_gamut.py): no weights needed, nothing resident is read or written ---------
     def gamut_map(self, L, gamut_size=110, D=1, want_pts=False):
@@ -1181,6 +1286,8 @@ class HipColorizer(object):
         n, sh, sw = rgb.shape[:3]
         flags = {"net": 0, "source": N.IDC_BATCH_OUT_SOURCE}[out]
         shp = (n, sh, sw, 3) if flags else (n, self.H, self.W, 3)
+        if self._out_format != "rgb":            # the plane blocks back to back (set_batch_output)
+            shp = (n, ycc420_bytes(shp[1], shp[2]))
         if not isinstance(out_rgb, np.ndarray) or out_rgb.dtype != np.uint8 or not out_rgb.flags.c_contiguous or tuple(out_rgb.shape) != shp:
             raise ValueError("forward_async_rgb needs a uint8 C-contiguous out_rgb of shape %s" % (shp,))
         if out_ab is not None and (out_ab.dtype != np.float32 or not out_ab.flags.c_contiguous or tuple(out_ab.shape) != (n, 2, self.H, self.W)):
@@ -1199,7 +1306,7 @@ class HipColorizer(object):
                                                                    _fptr(c) if c is not None else None, hist_flag, rflags) + tail)))
         self._in_flight[int(slot)] = (rgb, out_rgb, out_ab)      # the library reads / writes them until the slot's wait
 
-    def colorize_stream(self, batches, out="net", upsample=None, ingest=None, **kw):
+    def colorize_stream(self, batches, out="net", upsample=None, ingest=None, out_format=None, out_matrix=None, **kw):
         """Generator: colourise a stream of uint8 batches with both pipeline slots busy.  ``batches`` yields (rgb (n,h,w,3) uint8, hints) items
         (``hints`` as in ``forward_async_rgb``; n and the source size may change from item to item); each item's (n,H,W,3) [out='net'] or
         (n,h,w,3) [out='source'] uint8 result is yielded in input order, as an array of the caller's own (copied out of the pinned buffer the
@@ -1210,7 +1317,9 @@ class HipColorizer(object):
         ``kw`` then also carries centres (needed), hist_flag and saturation.  A two-entry item makes the plain call.
         ``upsample``: 'linear' or 'joint' -- ``set_batch_upsample`` before the first batch, the previous setting back when the generator
         ends or is abandoned; None (default) leaves the setting alone.
-        ``ingest``: 'bilinear' or 'antialias' -- ``set_ingest_filter`` with the same scope."""
+        ``ingest``: 'bilinear' or 'antialias' -- ``set_ingest_filter`` with the same scope.
+        ``out_format`` / ``out_matrix``: 'rgb' | 'i420' | 'nv12' and 'jfif' | 'bt709' -- ``set_batch_output`` with the same scope.  With a
+        YCbCr format an item's result is a list of n ``YCC420`` / ``NV12`` tuples, one per image (``ycc420_views``), not one array."""
         def submit(slot, group, first):
             item = group[0]
             rgb, hints = item[0], item[1]
@@ -1219,24 +1328,31 @@ class HipColorizer(object):
                 raise ValueError("colorize_stream needs uint8 (n,h,w,3) batches, got %s %s" % (rgb.dtype, rgb.shape))
             src = self._pool.take(rgb.shape, np.uint8)
             np.copyto(src, rgb)
-            dst = self._pool.take(rgb.shape if out == "source" else (rgb.shape[0], self.H, self.W, 3), np.uint8)
+            dims = rgb.shape[1:3] if out == "source" else (self.H, self.W)
+            dst = self._pool.take((rgb.shape[0],) + ((dims[0], dims[1], 3) if self._out_format == "rgb" else (ycc420_bytes(*dims),)), np.uint8)
             if len(item) > 2:
                 uniq, index = dedupe_refs(item[2], rgb.shape[0])
                 self.forward_async_rgb(slot, src, hints, dst, out=out, refs=uniq, ref_index=index, **kw)
             else:
                 self.forward_async_rgb(slot, src, hints, dst, out=out, **kw)
-            return dst, src
+            return dst, src, dims
+
+        def finish(state):
+            if state[0].ndim != 2:
+                return [np.array(state[0])]
+            return [[self._own_image(r, state[2]) for r in state[0]]]
 
         # a group of one: the items are whole batches, checked in submit, behind the yield of the slot's older result
-        yield from self._two_slot_stream(batches, 1, upsample, lambda item: item, submit, lambda state: [np.array(state[0])], ingest=ingest)
+        yield from self._two_slot_stream(batches, 1, upsample, lambda item: item, submit, finish, ingest=ingest, output=(out_format, out_matrix))
 
-    def _two_slot_stream(self, items, batch, upsample, parse, submit, finish, key=None, ingest=None):
+    def _two_slot_stream(self, items, batch, upsample, parse, submit, finish, key=None, ingest=None, output=(None, None)):
         """The generator behind ``colorize_stream``, ``colorize_images`` and their relatives: ``parse(item)`` every item as it arrives, group
         ``batch`` of them (default ``max_batch``; the last group may be shorter), ``submit(slot, group, first_index)`` group k on slot k % 2
         once that slot's older batch is finished -- ``first_index`` is the stream index of the group's first item; what it returns (results
         and whatever must stay alive: pinned pool memory) is kept until ``wait(slot)`` has returned -- and yield everything in
         ``finish(state)`` of each batch in input order.  ``upsample`` and ``ingest`` as in ``colorize_stream``.  A consumer that stops early: both slots are
         waited for, so nothing stays in flight on buffers about to be recycled, then the upsample and ingest settings go back.
+        ``output``: the generator's (out_format, out_matrix), ``set_batch_output`` with the same scope.
         ``key`` (of a parsed item): an item whose key differs from its group's closes that group, as a full batch does."""
         batch = self._group_size(batch)
         pending = [None, None]                      # per slot: submit's state of the batch in flight
@@ -1269,6 +1385,16 @@ class HipColorizer(object):
                 self.set_batch_upsample(restore)
             raise
         try:
+            restore_output = self._output_scope(*output)
+        except Exception:
+            try:
+                if restore is not None:
+                    self.set_batch_upsample(restore)
+            finally:
+                if restore_ingest is not None:
+                    self.set_ingest_filter(restore_ingest)
+            raise
+        try:
             for group in groups():
                 if pending[k & 1] is not None:
                     yield from drain(k & 1)
@@ -1288,8 +1414,12 @@ class HipColorizer(object):
                     if restore is not None:
                         self.set_batch_upsample(restore)
                 finally:
-                    if restore_ingest is not None:
-                        self.set_ingest_filter(restore_ingest)
+                    try:
+                        if restore_ingest is not None:
+                            self.set_ingest_filter(restore_ingest)
+                    finally:
+                        if restore_output is not None:
+                            self.set_batch_output(*restore_output)
 
     def _group_size(self, batch):
         batch = self.max_batch if batch is None else int(batch)
@@ -1366,7 +1496,7 @@ class HipColorizer(object):
             if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or not a.flags.c_contiguous or a.size == 0:
                 raise ValueError("%s needs uint8 C-contiguous (h,w,3) arrays" % who)
         flags = {"net": 0, "source": N.IDC_BATCH_OUT_SOURCE}[out]
-        shapes = [tuple(a.shape) if flags else (self.H, self.W, 3) for a in images]
+        shapes = self._out_shapes([tuple(a.shape) if flags else (self.H, self.W, 3) for a in images])
         if want_rgb:
             if out_rgb is None:
                 out_rgb = self._pinned_slices(shapes)
@@ -1481,7 +1611,7 @@ class HipColorizer(object):
             raise ValueError("depth=16 needs uint16 planes and out='source'")
         flags = {"net": 0, "source": N.IDC_BATCH_OUT_SOURCE}[out] | (N.IDC_BATCH_OUT_RGB16 if depth == 16 else 0)
         odt = np.uint16 if depth == 16 else np.uint8
-        shapes = [tuple(a.shape) + (3,) if flags else (self.H, self.W, 3) for a in images]
+        shapes = self._out_shapes([tuple(a.shape) + (3,) if flags else (self.H, self.W, 3) for a in images], depth)
         if want_rgb:
             if out_rgb is None:
                 nbytes = [int(np.prod(s)) * (depth // 8) for s in shapes]           # (each output starts on an even byte of the block)
@@ -1571,7 +1701,7 @@ class HipColorizer(object):
             raise ValueError("depth=16 needs uint16 planes and out='source'")
         flags = {"net": 0, "source": N.IDC_BATCH_OUT_SOURCE}[out] | (N.IDC_BATCH_OUT_RGB16 if depth == 16 else 0)
         odt = np.uint16 if depth == 16 else np.uint8
-        shapes = [tuple(a.shape[:2]) + (3,) if flags else (self.H, self.W, 3) for a in images]
+        shapes = self._out_shapes([tuple(a.shape[:2]) + (3,) if flags else (self.H, self.W, 3) for a in images], depth)
         if out_rgb is None:
             nbytes = [int(np.prod(s)) * (depth // 8) for s in shapes]           # (each output starts on an even byte of the block)
             out_rgb = [o[:b].view(odt).reshape(s) for o, b, s in zip(self._pinned_slices([(b + 1) // 2 * 2 for b in nbytes]), nbytes, shapes)]
@@ -1620,13 +1750,14 @@ class HipColorizer(object):
         self._in_flight[int(slot)] = (images, larrs, out_rgb, out_ab, cells, keep)   # the library reads / writes them until the slot's wait
         return out_rgb, cells
 
-    def colorize_layers(self, items, batch=None, out="source", depth=8, upsample=None, ingest=None, **kw):
+    def colorize_layers(self, items, batch=None, out="source", depth=8, upsample=None, ingest=None, out_format=None, out_matrix=None, **kw):
         """Generator: ``colorize_images`` / ``colorize_gray`` for images with painted hint layers (``forward_async_layers``).  An item is
         ``(image, layer_or_None, hints)``: image (h,w,3) uint8, or (h,w) uint8 or uint16; layer (lh,lw,4) uint8 RGBA of any size or ``None``;
         hints that image's rectangle list or ``None``.  Grouping, slot alternation and order as in ``colorize_images``; a change of image kind
         closes the group as a full batch does.  ``(rgb, cells)`` is yielded per image: the colourised image as those generators yield it and
         the number of cells its layer hinted (0 without a layer).  ``kw``: mode, mask_value, alpha_min, cover, maskcent, l_cent, ...;
-        ``upsample`` and ``ingest`` as in ``colorize_stream``."""
+        ``upsample``, ``ingest``, ``out_format`` and ``out_matrix`` as in ``colorize_stream``: with a YCbCr format the image is a ``YCC420`` /
+        ``NV12`` tuple."""
         if depth not in (8, 16) or (depth == 16 and out != "source"):
             raise ValueError("depth must be 8, or 16 with out='source'")
 
@@ -1658,10 +1789,15 @@ class HipColorizer(object):
             return res, srcs, pinned
 
         def finish(state):
-            (rgbs, cells), _, _ = state
-            return [(np.array(r), int(c)) for r, c in zip(rgbs, cells)]
+            (rgbs, cells), srcs, _ = state
+            return [(self._own_image(r, self._out_dims(s, out)), int(c)) for r, s, c in zip(rgbs, srcs, cells)]
 
-        yield from self._two_slot_stream(items, batch, upsample, parse, submit, finish, key=lambda g: (g[0].ndim, g[0].dtype), ingest=ingest)
+        yield from self._two_slot_stream(items, batch, upsample, parse, submit, finish, key=lambda g: (g[0].ndim, g[0].dtype), ingest=ingest,
+                                         output=(out_format, out_matrix))
+
+    def _out_dims(self, src, out):
+        """(h, w) of the result of the image whose source array is ``src``."""
+        return tuple(src.shape[:2]) if out == "source" else (self.H, self.W)
 
     def _pinned_planes(self, group):
         """The planes of a parsed group (``_gray_item``), copied into one pinned pool block; each starts on an even byte."""
@@ -1672,11 +1808,12 @@ class HipColorizer(object):
             np.copyto(s, p)
         return srcs
 
-    def colorize_gray(self, items, batch=None, out="source", depth=8, upsample=None, ingest=None, **kw):
+    def colorize_gray(self, items, batch=None, out="source", depth=8, upsample=None, ingest=None, out_format=None, out_matrix=None, **kw):
         """Generator: ``colorize_images`` for greyscale planes (``forward_async_gray``).  An item is ``gray``, ``(gray, hints)`` or
         ``(gray, hints, ref)``: gray (h,w) uint8 or uint16.  Grouping, slot alternation and order as in ``colorize_images``, and a change of
         dtype closes the group as a full batch does: a call carries one format.  One array per image is yielded: (h,w,3) [out='source'] or
-        (H,W,3) [out='net'], uint8, or uint16 with ``depth=16`` (uint16 items and out='source' only).  ``upsample``: as in ``colorize_stream``."""
+        (H,W,3) [out='net'], uint8, or uint16 with ``depth=16`` (uint16 items and out='source' only).  ``upsample``, ``out_format`` and ``out_matrix``: as in ``colorize_stream`` (a YCbCr format yields a ``YCC420`` /
+        ``NV12`` tuple per image and needs depth 8)."""
         if depth not in (8, 16) or (depth == 16 and out != "source"):
             raise ValueError("depth must be 8, or 16 with out='source'")
 
@@ -1693,11 +1830,12 @@ class HipColorizer(object):
                 more["refs"], more["ref_index"] = dedupe_refs([g[2] for g in group], len(group))
             return self.forward_async_gray(slot, srcs, [g[1] for g in group], out=out, depth=depth, **more), srcs
 
-        yield from self._two_slot_stream(items, batch, upsample, parse, submit, lambda state: [np.array(r) for r in state[0]],
-                                         key=lambda g: g[0].dtype, ingest=ingest)
+        yield from self._two_slot_stream(items, batch, upsample, parse, submit,
+                                         lambda state: [self._own_image(r, self._out_dims(s, out)) for r, s in zip(state[0], state[1])],
+                                         key=lambda g: g[0].dtype, ingest=ingest, output=(out_format, out_matrix))
 
     def suggest_gray(self, items, centres, batch=None, out="source", depth=8, peaks=8, radius=2, skip_hints=True, K=5, N_draws=25000, seed=0,
-                     upsample=None, ingest=None, **kw):
+                     upsample=None, ingest=None, out_format=None, out_matrix=None, **kw):
         """Generator: ``suggest_images`` for greyscale planes -- where to put the next hints on a folder of black-and-white photographs, and
         in which colours.  An item is ``gray`` or ``(gray, hints)``; it yields ``(rgb, peaks, colours, conf)`` per image as ``suggest_images``
         does, grouped as ``colorize_gray`` groups."""
@@ -1722,14 +1860,15 @@ class HipColorizer(object):
             K_ = res.sugg_centres.shape[1]
             sc, sf = np.array(res.sugg_centres).reshape(len(srcs), P, K_, 2), np.array(res.sugg_conf).reshape(len(srcs), P, K_)
             pk = np.array(res.peaks)
-            return [(np.array(r), pk[i], sc[i], sf[i]) for i, r in enumerate(res.out_rgb)]
+            return [(self._own_image(r, self._out_dims(srcs[i], out)), pk[i], sc[i], sf[i]) for i, r in enumerate(res.out_rgb)]
 
         batch = self._group_size(batch)
         if P < 1:
             raise ValueError("suggest_gray needs at least one peak per image")
-        yield from self._two_slot_stream(items, batch, upsample, parse, submit, finish, key=lambda g: g[0].dtype, ingest=ingest)
+        yield from self._two_slot_stream(items, batch, upsample, parse, submit, finish, key=lambda g: g[0].dtype, ingest=ingest,
+                                         output=(out_format, out_matrix))
 
-    def colorize_images(self, items, batch=None, out="source", upsample=None, ingest=None, **kw):
+    def colorize_images(self, items, batch=None, out="source", upsample=None, ingest=None, out_format=None, out_matrix=None, **kw):
         """Generator: colourise a stream of single images of any sizes with both pipeline slots busy.  An item is ``rgb``, ``(rgb, hints)`` or
         ``(rgb, hints, ref)``: rgb (h,w,3) uint8, ``hints`` that image's hint list (rows as in ``set_hints``) or ``None``, ``ref`` ``None`` or an
         (h,w,3) uint8 reference photograph (a ``global_hints`` engine; ``kw`` then carries centres).  Consecutive items are grouped into
@@ -1737,7 +1876,8 @@ class HipColorizer(object):
         (``forward_async_images``), and one array per image is yielded in input order: (h,w,3) [out='source'] or (H,W,3) [out='net'], the
         caller's own copy.  Sources travel through one pinned pool block per batch; the same reference OBJECT given for several images of a
         batch is uploaded once (``dedupe_refs``).  ``kw``: mode, mask_value, maskcent, l_cent, centres, hist_flag, saturation.
-        ``upsample``: as in ``colorize_stream`` ('joint': the edge-aware source-size output)."""
+        ``upsample``: as in ``colorize_stream`` ('joint': the edge-aware source-size output).  ``out_format`` / ``out_matrix``: as there; with
+        'i420' or 'nv12' a ``YCC420`` / ``NV12`` tuple of plane views into one uint8 buffer is yielded per image."""
         def submit(slot, group, first):
             srcs = self._pinned_sources(group)
             more = dict(kw)
@@ -1746,9 +1886,10 @@ class HipColorizer(object):
             return self.forward_async_images(slot, srcs, [g[1] for g in group], out=out, **more), srcs
 
         yield from self._two_slot_stream(items, batch, upsample, lambda item: _image_item("colorize_images", item, True), submit,
-                                         lambda state: [np.array(r) for r in state[0]], ingest=ingest)
+                                         lambda state: [self._own_image(r, self._out_dims(s, out)) for r, s in zip(state[0], state[1])], ingest=ingest,
+                                         output=(out_format, out_matrix))
 
-    def evaluate_images(self, items, batch=None, out="net", mode="reveal", upsample=None, ingest=None, **kw):
+    def evaluate_images(self, items, batch=None, out="net", mode="reveal", upsample=None, ingest=None, out_format=None, out_matrix=None, **kw):
         """Generator: score a stream of ground-truth colour images with both pipeline slots busy -- ``colorize_images`` whose every image is
         compared with itself on the device (``forward_async_eval``).  An item is ``rgb``, ``(rgb, rects)`` or ``(rgb, rects, ref)``; with
         mode='reveal' (default) ``rects`` are rows (y0, x0, y1, x1) whose colours the device reveals from the image, with 'ab' / 'rgb' they
@@ -1770,10 +1911,11 @@ class HipColorizer(object):
             sse = np.array(state[0])
             return [(psnr_from_sse(sse[i], h, w), sse[i]) for i, (h, w) in enumerate(state[1])]
 
-        yield from self._two_slot_stream(items, batch, upsample, lambda item: _image_item("evaluate_images", item, True), submit, finish, ingest=ingest)
+        yield from self._two_slot_stream(items, batch, upsample, lambda item: _image_item("evaluate_images", item, True), submit, finish, ingest=ingest,
+                                         output=(out_format, out_matrix))      # (scope only: no image comes back, the score reads the RGB)
 
     def suggest_images(self, items, centres, batch=None, out="source", peaks=8, radius=2, skip_hints=True, K=5, N_draws=25000, seed=0,
-                       upsample=None, ingest=None, **kw):
+                       upsample=None, ingest=None, out_format=None, out_matrix=None, **kw):
         """Generator: ``colorize_images`` on an engine with a distribution head that also proposes where to put the next hints and in which
         colours (``forward_async_dist`` with the suggestions at the peaks).  An item is ``rgb`` or ``(rgb, hints)``; grouping, slot alternation
         and order as in ``colorize_images``.  Per image it yields ``(rgb, peaks (P,2) int32, colours (P,K,2) float64, conf (P,K) float64)``:
@@ -1794,14 +1936,16 @@ class HipColorizer(object):
             K_ = res.sugg_centres.shape[1]
             sc, sf = np.array(res.sugg_centres).reshape(len(srcs), P, K_, 2), np.array(res.sugg_conf).reshape(len(srcs), P, K_)
             pk = np.array(res.peaks)
-            return [(np.array(r), pk[i], sc[i], sf[i]) for i, r in enumerate(res.out_rgb)]
+            return [(self._own_image(r, self._out_dims(srcs[i], out)), pk[i], sc[i], sf[i]) for i, r in enumerate(res.out_rgb)]
 
         batch = self._group_size(batch)
         if P < 1:
             raise ValueError("suggest_images needs at least one peak per image")
-        yield from self._two_slot_stream(items, batch, upsample, lambda item: _image_item("suggest_images", item, False), submit, finish, ingest=ingest)
+        yield from self._two_slot_stream(items, batch, upsample, lambda item: _image_item("suggest_images", item, False), submit, finish, ingest=ingest,
+                                         output=(out_format, out_matrix))
 
-    def score_images(self, items, centres, batch=None, nn=1, sigma=5.0, ranks=(1, 5), mode="reveal", want_psnr=False, upsample=None, ingest=None, **kw):
+    def score_images(self, items, centres, batch=None, nn=1, sigma=5.0, ranks=(1, 5), mode="reveal", want_psnr=False, upsample=None, ingest=None,
+                     out_format=None, out_matrix=None, **kw):
         """Generator: score the distribution head on a stream of ground-truth colour images with both pipeline slots busy --
         ``evaluate_images`` for the distribution (``forward_async_dist`` with ``score`` and no other tap).  An item is ``rgb`` or
         ``(rgb, rects)``, hints as in ``evaluate_images`` (mode 'reveal': the colours come from the image).  Per image it yields
@@ -1822,7 +1966,8 @@ class HipColorizer(object):
             sse = np.array(res.sse) if want_psnr else None
             return [(float(mean[i]), hits[i], psnr_from_sse(sse[i], self.H, self.W) if want_psnr else None) for i in range(len(mean))]
 
-        yield from self._two_slot_stream(items, batch, upsample, lambda item: _image_item("score_images", item, False), submit, finish, ingest=ingest)
+        yield from self._two_slot_stream(items, batch, upsample, lambda item: _image_item("score_images", item, False), submit, finish, ingest=ingest,
+                                         output=(out_format, out_matrix))
 
     def wait(self, slot):
         self._chk(self.lib.idc_wait(self._h, int(slot)))
