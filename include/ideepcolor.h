@@ -144,6 +144,12 @@ const char* idc_last_error(idc_handle h);
 
 /* ---- lifetime: replaces SIGGRAPHGenerator.__init__ (model.py:6-132) + net.eval()/.cuda()
  *      in ColorizeImageTorch.prep_net (colorize_image.py:216-233) ---------------------------- */
+/* height and width are positive multiples of 8; max_batch has no bound of its own (a tensor of max_batch images may pass 2^31 and 2^32 bytes:
+ * images are addressed from 64-bit bases).  The limit is on ONE image: several kernels address one image of a launch's source tensor with 32-bit
+ * offsets, and where no kernel is left for some layer of this precision -- its launch ends on the small tile (conv_igemm / conv_click), which reaches
+ * 2^31 bytes -- idc_create returns IDC_ERR_INVALID_ARG with the layer, the tensor and its bytes in idc_last_error(NULL), before it asks for a device.
+ * Square images: IDC_FP32 up to 2048 x 2048 (conv10_1: H * W * 512 bytes), IDC_BF16 up to 5792 x 5792 (conv9_2, read by the deconv that sums its
+ * unfused shortcut: H/2 * W/2 * 256 bytes); the operand-split precisions run every such layer on kernels with 64-bit tile bases. */
 int idc_create(int device_id, int height, int width, int max_batch, int precision, unsigned flags,
                idc_handle* out);
 int idc_destroy(idc_handle h);

@@ -231,7 +231,10 @@ int idc_create(int device_id, int height, int width, int max_batch, int precisio
         return fail(nullptr, IDC_ERR_INVALID_ARG, "H and W must be positive multiples of 8 (got %dx%d)", height, width);
     if (max_batch <= 0) return fail(nullptr, IDC_ERR_INVALID_ARG, "max_batch must be positive");
     if (precision < IDC_FP32 || precision > IDC_FP16) return fail(nullptr, IDC_ERR_INVALID_ARG, "bad precision %d", precision);
-    int rc = check_device(device_id, nullptr);
+    // an image so large that some layer has no kernel that can address it: IDC_ERR_INVALID_ARG with the reason, before any device is asked for
+    int rc = check_geometry(precision, flags, height, width, max_batch, nullptr);
+    if (rc) return rc;
+    rc = check_device(device_id, nullptr);
     if (rc) return rc;
     if (hipSetDevice(device_id) != hipSuccess) return fail(nullptr, IDC_ERR_HIP, "hipSetDevice(%d) failed", device_id);
     idc_context* c = new idc_context();

@@ -337,6 +337,7 @@ int plan_forward(std::vector<Layer>& layers, const std::vector<Tensor>& tensors,
 hipError_t launch_kernel(Kernel k, const Layer& L, const ConvArgs& a, hipStream_t s);
 void kernel_label(const Layer& L, int precision, char* out, size_t cap);
 int build_layers(const BlobPlan& plan, int precision, int H, int W, int max_batch, std::vector<Tensor>& tensors, std::vector<Layer>& layers, std::string* err);
+int check_geometry(int precision, unsigned flags, int H, int W, int max_batch, std::string* err);
 int build_graph(idc_context* c);
 int alloc_graph(idc_context* c);
 

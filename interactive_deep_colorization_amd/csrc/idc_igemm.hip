@@ -618,7 +618,14 @@ static hipError_t launch_click_t(const ConvArgs& a, hipStream_t s) {
 
 #define IDC_FOR_EACH_CLICK(X) X(4, 1) X(4, 2) X(2, 1) X(2, 2) X(1, 1) X(1, 2)
 
+// conv_igemm and conv_click address one source image with 32-bit halo offsets (hoff[]; -1 = out of the image).  The largest offset formed is
+// 16 bytes short of the image's size, so an image of up to 2^31 bytes (inclusive) is addressable; the fused input pack (pk_L) reads no such image.
+bool conv_igemm_offsets_fit(int Hs, int Ws, int si, int nkc) {
+    return (long long)Hs * si * (long long)Ws * si * ((long long)nkc * kRowBytes) <= 0x80000000LL;
+}
+
 hipError_t launch_conv_click(int precision, int wp, int halo, const ConvArgs& a, hipStream_t s) {
+    if (!conv_igemm_offsets_fit(a.Hs, a.Ws, a.si, a.nkc)) return hipErrorInvalidConfiguration;
 #define X(WP, HL) \
     if (wp == WP && halo == HL) return precision == 1 ? launch_click_t<__bf16, WP, HL>(a, s) : launch_click_t<float, WP, HL>(a, s);
     IDC_FOR_EACH_CLICK(X)
@@ -698,6 +705,7 @@ hipError_t init_kernels() {
 }
 
 hipError_t launch_conv(int precision, ConvConfig cfg, int halo, const ConvArgs& a, hipStream_t s) {
+    if (a.pk_L == nullptr && !conv_igemm_offsets_fit(a.Hs, a.Ws, a.si, a.nkc)) return hipErrorInvalidConfiguration;
 #define X(WM, WP, HL)                                                                   \
     if (cfg.wm == WM && cfg.wp == WP && halo == HL)                                     \
         return precision == 1 ? launch_conv_t<__bf16, WM, WP, HL>(a, s) : launch_conv_t<float, WM, WP, HL>(a, s);

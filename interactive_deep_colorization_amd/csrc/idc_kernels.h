@@ -115,6 +115,9 @@ struct ConvConfig { int wm, wp; };     // waves along cout (x64) and along pixel
 
 // precision: 0 fp32, 1 bf16.  halo: 0,1,2.  Returns hipSuccess or the launch error.
 hipError_t launch_conv(int precision, ConvConfig cfg, int halo, const ConvArgs& a, hipStream_t s);
+// conv_igemm's and conv_click's 32-bit source offsets: one source image of at most 2^31 bytes (hipErrorInvalidConfiguration from both launchers otherwise;
+// plan_forward refuses such a layer with the reason).  No family of the default library goes further for these launches, so this is the engine's limit.
+bool conv_igemm_offsets_fit(int Hs, int Ws, int si, int nkc);
 // Large-tile bf16 throughput kernel (32x32x16 MFMA, 8 waves, LDS-DMA weights).  cfg = {WCO, WPX}:
 // {4,2} = 256 couts x (32x8 sites), {2,4} = 128 couts x (32x16 sites).  a.wgt must point at the
 // layer's layout-2 weight image (idc_layout.h); tiles_x/tiles_y count 32 x 4*WPX tiles.

@@ -375,8 +375,30 @@ int plan_forward(std::vector<Layer>& layers, const std::vector<Tensor>& tensors,
         a.w_part_bytes = L.split ? L.blob.w_bytes : 0;
         a.w_part_bytes2 = (L.split && S) ? S->blob.w_bytes : 0;
         L.kernel = choose_kernel(L, args_as_bound(L, layers), env.precision, env.max_batch);
+        // The small tile is where every layer ends up that no other family covers, and it addresses one source image with 32-bit offsets
+        // (conv_igemm_offsets_fit): a layer whose source image is larger has no kernel.  Refused here with the reason -- idc_create asks this
+        // plan before it allocates anything -- instead of at the launch.  (conv1_1 reads the caller's planes, not a stored source.)
+        if ((L.kernel == kConvIgemm || L.kernel == kConvClick) && L.spec->kind != kConvIm2col && !conv_igemm_offsets_fit(a.Hs, a.Ws, a.si, a.nkc))
+            return fail(err, IDC_ERR_INVALID_ARG, "%d x %d is too large for this precision: one image of %s, the source of layer %s, holds %lld bytes; "
+                        "the kernel left for that launch (conv_igemm / conv_click) addresses an image of at most 2^31 bytes", env.H, env.W,
+                        tensors[L.src].name.c_str(), L.spec->name, (long long)a.Hs * a.si * (long long)a.Ws * a.si * ((long long)a.nkc * kRowBytes));
     }
     return IDC_OK;
+}
+
+// What idc_create asks before it touches a device: does every layer of this configuration have a kernel that can address it?  (The plan at
+// n = max_batch under the options in force; a later forward plans again and answers the same way.)
+int check_geometry(int precision, unsigned flags, int H, int W, int max_batch, std::string* err) {
+    const BlobPlan blob = make_blob_plan(precision, flags);
+    std::vector<Tensor> tensors;
+    std::vector<Layer> layers;
+    const int rc = build_layers(blob, precision, H, W, max_batch, tensors, layers, err);
+    if (rc) return rc;
+    PlanEnv env;
+    env.precision = precision; env.flags = flags; env.H = H; env.W = W; env.max_batch = max_batch; env.n = max_batch;
+    env.t_conv10_2 = find_tensor(tensors, "conv10_2");
+    env.t_conv4_3 = find_tensor(tensors, "conv4_3");
+    return plan_forward(layers, tensors, env, err);
 }
 
 // One launch of the entry point `k` (kConvKwave: one layer; run_graph tries the persistent chain first).

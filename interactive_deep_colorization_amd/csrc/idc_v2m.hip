@@ -74,6 +74,10 @@ __device__ __forceinline__ void conv_v2m_body(const ConvArgs& a) {
     const char* const wb = (const char*)a.wgt + (size_t)(ct * WCO) * kWBlockBytes + (size_t)tid * kSlotBytes;
     const int pix_chunks = SPLIT ? a.in_parts * nkc : nkc;     // 128-byte chunks per input pixel (split tensors: [part][chunk])
     const char* const img = (const char*)a.in + (size_t)n * (size_t)(Hs * si) * (Ws * si) * ((size_t)pix_chunks * kRowBytes);
+    // This family takes the images whose bytes pass 2^31 (conv_v2p_applies / conv_v2ps_applies hand them over): the halo tile's first pixel as a
+    // 64-bit, workgroup-uniform base (it may lie before the image: only addresses inside are dereferenced), 32-bit offsets from there -- they span
+    // the tile's rows, not the image (v2m_rows_fit)
+    const char* const tile = img + (long long)(((ty0 - HALO) * si) * (Ws * si) + (tx0 - HALO) * si) * ((long long)pix_chunks * kRowBytes);
 
     // accumulators start at the bias: lane (site r16, group g16) register j of acc[mi][.] is cout g16*16 + mi*4 + j of the wave's 64
     f32x4 acc[4][8];
@@ -109,8 +113,8 @@ __device__ __forceinline__ void conv_v2m_body(const ConvArgs& a) {
             const int hy = hr / HWP, hx = hr - hy * HWP;
             const int sy = ty0 - HALO + hy, sx = tx0 - HALO + hx;
             const bool inside = (unsigned)sy < (unsigned)Hs && (unsigned)sx < (unsigned)Ws && item < HROWS * kSlots;
-            const int off = ((sy * si) * Win + sx * si) * pix_bytes + ((sig ^ swz(hr)) + kc * kSlots) * kSlotBytes;
-            hreg[j] = *(const u32x4*)(inside ? img + off : (const char*)a.zeros);
+            const int off = ((hy * si) * Win + hx * si) * pix_bytes + ((sig ^ swz(hr)) + kc * kSlots) * kSlotBytes;
+            hreg[j] = *(const u32x4*)(inside ? tile + off : (const char*)a.zeros);
         }
     };
 
@@ -764,9 +768,15 @@ hipError_t launch_conv_v2p(ConvConfig cfg, int halo, const ConvArgs& a, hipStrea
 #define IDC_FOR_EACH_CONV_V2M(X) X(4, 2, 0) X(4, 2, 1) X(4, 2, 2) X(2, 4, 0) X(2, 4, 1) X(2, 4, 2) X(2, 2, 0) X(2, 2, 1) X(2, 2, 2)
 #define IDC_FOR_EACH_CONV_V2S(X) IDC_FOR_EACH_CONV_V2M(X) X(1, 4, 1) X(1, 2, 1)
 
+// conv_igemm_v2m's body (and its operand-split forms) addresses a halo tile with 32-bit offsets from the tile's own 64-bit base: the image may hold
+// any number of bytes, the tile's source rows (at most 16 + 2 * 2 of them, times the input stride) have to stay below 2^31
+static bool v2m_rows_fit(const ConvArgs& a, int parts) {
+    return 20LL * a.si * ((long long)a.Ws * a.si) * ((long long)a.nkc * parts * kRowBytes) < 0x7fffffffLL;
+}
+
 bool conv_v2m_applies(const ConvArgs& a) {
     return a.resid == nullptr && a.in2 == nullptr && !a.out_f32 && (a.img_shift == nullptr || a.bn_scale != nullptr) && a.pk_L == nullptr && a.ksplit <= 1 &&
-           (a.act != 2 || a.head_w != nullptr) && (a.head_w == nullptr || a.bn_scale == nullptr) && a.zeros != nullptr;
+           (a.act != 2 || a.head_w != nullptr) && (a.head_w == nullptr || a.bn_scale == nullptr) && a.zeros != nullptr && v2m_rows_fit(a, 1);
 }
 
 hipError_t launch_conv_v2m(ConvConfig cfg, int halo, const ConvArgs& a, hipStream_t s) {
@@ -782,7 +792,7 @@ hipError_t launch_conv_v2m(ConvConfig cfg, int halo, const ConvArgs& a, hipStrea
 // operand-split launches (IDC_BF16X3 / IDC_BF16X6): everything conv_igemm_v2m's geometry covers, plus fp32 shortcut sums, fp32 outputs, per-image shifts
 bool conv_v2s_applies(const ConvArgs& a) {
     if (a.in2 != nullptr || a.pk_L != nullptr || a.ksplit > 1 || a.zeros == nullptr || a.resid_bf16) return false;
-    if (a.in_parts < 1 || a.in_parts > 3 || a.nseg < 1 || a.nseg > 6 || a.w_part_bytes == 0) return false;
+    if (a.in_parts < 1 || a.in_parts > 3 || a.nseg < 1 || a.nseg > 6 || a.w_part_bytes == 0 || !v2m_rows_fit(a, a.in_parts)) return false;
     if (a.head_w != nullptr) return a.bn_scale == nullptr && a.resid == nullptr && a.img_shift == nullptr;
     return a.out_f32 ? a.out_parts == 0 : (a.out_parts >= 1 && a.out_parts <= 3);
 }
