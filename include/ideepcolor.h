@@ -857,7 +857,7 @@ int idc_rgb_to_ycc420(idc_handle h, int n, const idc_ref_image* images, int form
  *      Hd x Wd is the distribution's grid as for idc_dist_entropy, s = H / Hd (4: 529 head, 1: 313 head), B the bin count, centres [B,2] fp32
  *      (a, b) as in idc_suggest_colors.  For image i and cell (cy, cx):
  *        1. truth (a*, b*) fp32 = the colour idc_reveal_hints reports for the rectangle (cy*s, cx*s, cy*s+s-1, cx*s+s-1) of that image, bit for
- *           bit: the same device functions per net-size pixel (bilinear_taps, bilinear_u8, linear_to_lab), the float64 sum in
+ *           bit: the same device functions per net-size pixel (bilinear_taps, bilinear_q, linear_to_lab), the float64 sum in
  *           reveal_hints_kernel's order for a 16-pixel rectangle -- pixel t = dy*4+dx, folded by halves (t with t+8, then +4, +2, +1) -- divided
  *           by the count in float64 and rounded once to fp32; for s = 1 the pixel's own (a, b) rounded to fp32.
  *        2. neighbours q_1 .. q_nn = the nn centres nearest to the truth in Euclidean distance, computed in float64 from the fp32 values

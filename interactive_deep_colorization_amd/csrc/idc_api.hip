@@ -934,8 +934,8 @@ int idc_set_image_rgb(idc_handle h, int img, int n, int src_h, int src_w, const 
         if (rc) return rc;
     }
     HIPCHK(h, hipMemcpyAsync((void*)h->d_src_ptrs.get(), (const void*)h->h_src_ptrs.get(), (size_t)n * sizeof(void*), hipMemcpyHostToDevice, h->stream.get()));
-    HIPCHK(h, launch_ingest_rgb(h->d_src_ptrs.get(), n, aa ? h->H : src_h, aa ? h->W : src_w, h->H, h->W, l_cent, h->d_L.get() + (size_t)img * hw,
-                                rgb_net ? h->d_net_rgb.get() : nullptr, lab_net ? h->d_net_lab.get() : nullptr, h->stream.get()));
+    HIPCHK(h, launch_ingest(0, (const void* const*)h->d_src_ptrs.get(), n, aa ? h->H : src_h, aa ? h->W : src_w, h->H, h->W, l_cent, h->d_L.get() + (size_t)img * hw,
+                            rgb_net ? h->d_net_rgb.get() : nullptr, lab_net ? h->d_net_lab.get() : nullptr, h->stream.get()));
     const bool rgb_direct = rgb_net && is_pinned(rgb_net), lab_direct = lab_net && is_pinned(lab_net);
     if (rgb_direct) HIPCHK(h, hipMemcpyAsync(rgb_net, h->d_net_rgb.get(), (size_t)n * hw * 3, hipMemcpyDeviceToHost, h->stream.get()));
     if (lab_direct) HIPCHK(h, hipMemcpyAsync(lab_net, h->d_net_lab.get(), (size_t)n * hw * 3 * 8, hipMemcpyDeviceToHost, h->stream.get()));
@@ -992,8 +992,8 @@ int idc_set_image_gray(idc_handle h, int img, int n, int src_h, int src_w, int b
         if (rc) return rc;
     }
     HIPCHK(h, hipMemcpyAsync((void*)h->d_src_ptrs.get(), (const void*)h->h_src_ptrs.get(), (size_t)n * sizeof(void*), hipMemcpyHostToDevice, h->stream.get()));
-    HIPCHK(h, launch_ingest_gray((const void* const*)h->d_src_ptrs.get(), bits, n, aa ? h->H : src_h, aa ? h->W : src_w, h->H, h->W, l_cent, h->d_L.get() + (size_t)img * hw,
-                                 gray_net ? h->d_net_rgb.get() : nullptr, l_net ? h->d_net_lab.get() : nullptr, h->stream.get()));
+    HIPCHK(h, launch_ingest(bits, (const void* const*)h->d_src_ptrs.get(), n, aa ? h->H : src_h, aa ? h->W : src_w, h->H, h->W, l_cent, h->d_L.get() + (size_t)img * hw,
+                            gray_net ? h->d_net_rgb.get() : nullptr, l_net ? h->d_net_lab.get() : nullptr, h->stream.get()));
     const bool net_direct = gray_net && is_pinned(gray_net), l_direct = l_net && is_pinned(l_net);
     if (net_direct) HIPCHK(h, hipMemcpyAsync(gray_net, h->d_net_rgb.get(), (size_t)n * hw * sz, hipMemcpyDeviceToHost, h->stream.get()));
     if (l_direct) HIPCHK(h, hipMemcpyAsync(l_net, h->d_net_lab.get(), (size_t)n * hw * 8, hipMemcpyDeviceToHost, h->stream.get()));
@@ -1036,14 +1036,9 @@ static int fullres(idc_handle h, int img, int source, int interp, int l_mode, vo
             HIPCHK(h, h->d_full_ab.ensure(nbytes));
         }
         if (!direct) HIPCHK(h, h->h_full_ab.ensure(h->d_full_ab.bytes()));
-        if (sl.gray_bits)
-            HIPCHK(h, launch_gray_joint_fullres(sl.d_rgb.get(), sl.gray_bits, nullptr, 1, sl.h, sl.w, joint_tiles(sl.h, sl.w), pa, pb, f64, 0,
-                                                h->d_L.get() + (size_t)img * hw, sl.l_cent, h->H, h->W, interp, h->joint, nullptr, 8, h->d_full_ab.get(),
-                                                h->stream.get()));
-        else
-            HIPCHK(h, launch_joint_fullres(sl.d_rgb.get(), nullptr, 1, sl.h, sl.w, joint_tiles(sl.h, sl.w), pa, pb, f64, 0,
-                                           h->d_L.get() + (size_t)img * hw, sl.l_cent, h->H, h->W, interp, h->joint, nullptr, h->d_full_ab.get(),
-                                           h->stream.get()));
+        HIPCHK(h, launch_joint_fullres(sl.gray_bits, sl.d_rgb.get(), nullptr, 1, sl.h, sl.w, joint_tiles(sl.h, sl.w), pa, pb, f64, 0,
+                                       h->d_L.get() + (size_t)img * hw, sl.l_cent, h->H, h->W, interp, h->joint, nullptr, 8, h->d_full_ab.get(),
+                                       h->stream.get()));
         HIPCHK(h, hipMemcpyAsync(direct ? ab : h->h_full_ab.get(), h->d_full_ab.get(), nbytes, hipMemcpyDeviceToHost, h->stream.get()));
         HIPCHK(h, hipStreamSynchronize(h->stream.get()));
         if (!direct) memcpy(ab, h->h_full_ab.get(), nbytes);
@@ -1057,19 +1052,13 @@ static int fullres(idc_handle h, int img, int source, int interp, int l_mode, vo
     }
     if (!direct && ycc_format == IDC_OUT_RGB) HIPCHK(h, h->h_full_rgb.ensure(h->d_full_rgb.bytes()));
     const float* mask = l_mode == IDC_L_MASK50 ? h->d_mask.get() + (size_t)img * hw : nullptr;
-    if (sl.gray_bits && interp == IDC_INTERP_JOINT && pa)
-        HIPCHK(h, launch_gray_joint_fullres(sl.d_rgb.get(), sl.gray_bits, nullptr, 1, sl.h, sl.w, joint_tiles(sl.h, sl.w), pa, pb, f64, 0,
-                                            h->d_L.get() + (size_t)img * hw, sl.l_cent, h->H, h->W, interp, h->joint, h->d_full_rgb.get(), out_bits, nullptr,
-                                            h->stream.get()));
-    else if (sl.gray_bits)
-        HIPCHK(h, launch_gray_fullres(sl.d_rgb.get(), sl.gray_bits, sl.h, sl.w, pa, pb, f64, h->H, h->W, interp == IDC_INTERP_JOINT ? IDC_INTERP_LINEAR : interp,
-                                      mask, h->hint_mask_value[img], h->d_full_rgb.get(), out_bits, h->stream.get()));
-    else if (interp == IDC_INTERP_JOINT && pa)
-        HIPCHK(h, launch_joint_fullres(sl.d_rgb.get(), nullptr, 1, sl.h, sl.w, joint_tiles(sl.h, sl.w), pa, pb, f64, 0, h->d_L.get() + (size_t)img * hw,
-                                       sl.l_cent, h->H, h->W, interp, h->joint, h->d_full_rgb.get(), nullptr, h->stream.get()));
+    if (interp == IDC_INTERP_JOINT && pa)
+        HIPCHK(h, launch_joint_fullres(sl.gray_bits, sl.d_rgb.get(), nullptr, 1, sl.h, sl.w, joint_tiles(sl.h, sl.w), pa, pb, f64, 0,
+                                       h->d_L.get() + (size_t)img * hw, sl.l_cent, h->H, h->W, interp, h->joint, h->d_full_rgb.get(), out_bits, nullptr,
+                                       h->stream.get()));
     else        // (IDC_SRC_NO_AB has nothing to interpolate: a = b = 0 whatever the interp)
-        HIPCHK(h, launch_fullres_rgb(sl.d_rgb.get(), sl.h, sl.w, pa, pb, f64, h->H, h->W, interp == IDC_INTERP_JOINT ? IDC_INTERP_LINEAR : interp, mask,
-                                     h->hint_mask_value[img], h->d_full_rgb.get(), h->stream.get()));
+        HIPCHK(h, launch_fullres(sl.gray_bits, sl.d_rgb.get(), sl.h, sl.w, pa, pb, f64, h->H, h->W, interp == IDC_INTERP_JOINT ? IDC_INTERP_LINEAR : interp,
+                                 mask, h->hint_mask_value[img], h->d_full_rgb.get(), out_bits, h->stream.get()));
     if (ycc_format != IDC_OUT_RGB) {      // the post-pass on the one image, and its block instead of the RGB
         const size_t yb = ycc420_bytes(sl.h, sl.w);
         HIPCHK(h, hipStreamSynchronize(h->stream.get()));            // the table of the previous call may still be in flight

@@ -310,24 +310,63 @@ hipError_t launch_global_stats(const unsigned char* rgb, const float* centres, u
 
 // ------------------------------------------------------------------------------------------------
 // image ingestion: what ColorizeImageBase.load_image / set_image do on the host before the first click (data/colorize_image.py:52-77):
-// cv2.resize to the net size, rgb2lab, L - l_cent; and the full-resolution getters (:123-158) from the uint8 source kept on the device.
+// cv2.resize to the net size, rgb2lab, L - l_cent; and the full-resolution getters (:123-158) from the source kept on the device.
 // A uint8 channel has 256 possible sRGB -> linear values: each workgroup fills a 256-entry float64 table in LDS with srgb8_to_linear (the
 // per-pixel expression, so the table is bit-identical to it) and reads it -- one transcendental (cbrt) per Lab component left per pixel.
+//
+// Source formats.  Every kernel of this section is ONE template over SrcFmt<T, C>: C interleaved samples of type T per pixel, whose sRGB value is
+// v / 255 (uint8) or v / 65535 (uint16).  RGB8 is the colour image [h,w,3]; Gray8 / Gray16 are the greyscale sources (idc_set_image_gray, and
+// idc_fullres_rgb / idc_fullres_ab / idc_fullres_rgb16 on a kept one; the rule: include/ideepcolor.h): one plane [h,w] whose sample stands on all
+// three channels.  The image goes out as uint8 or uint16 O (16 only from 16).  All formats run the SAME device functions below, the grey ones on
+// their one channel and on {t, t, t}, so a uint8 plane gives the bits of the RGB route fed the plane three times, and a uint16 plane of 257 g
+// gives the bits of the uint8 plane g wherever nothing is resized (fl(257 g / 65535) == fl(g / 255): the correctly rounded quotient of the same
+// real number).  There is no expanded RGB copy of a plane.
+//   sRGB -> linear   uint8: the 256-entry LDS table.  uint16: srgb_to_linear per sample -- one float64 pow beside the three of lab_to_srgb on the
+//                    way out and the cbrt of linear_to_lab; a 65 536-entry table in global memory would hold the same bits.  A kernel that needs
+//                    no table sizes it [1] and skips the barrier; the prologue always fills it, because a hint's colour is uint8 whatever the
+//                    samples are.
+//   grids            every kernel walks its items in a grid-stride loop.  The launchers own the policy and state it in the kernel's first
+//                    template argument (EXACT, item_stride below): RGB launches are capped through grid_blocks under their tag and launch the
+//                    EXACT = false form, which strides by the grid; grey launches are exact -- dim3(want) covers the items, a count past 2^31 - 1
+//                    is refused (a 16384^2 source is 2.6e5 workgroups) -- and launch the EXACT = true form, one pass.
 // ------------------------------------------------------------------------------------------------
+template <typename T>
+struct Depth {      // a sample or output type: uint8 | uint16
+    static constexpr int qmax = sizeof(T) == 1 ? 255 : 65535;       // full scale
+    static constexpr double full = (double)qmax;
+};
+
+template <typename T, int C>
+struct SrcFmt : Depth<T> {
+    typedef T sample;
+    static constexpr int channels = C;
+    static constexpr bool table = sizeof(T) == 1;                   // sRGB -> linear through the LDS table
+    static constexpr int group_dwords = C * (int)sizeof(T);         // a group of 4 pixels
+};
+typedef SrcFmt<unsigned char, 3> RGB8;
+typedef SrcFmt<unsigned char, 1> Gray8;
+typedef SrcFmt<unsigned short, 1> Gray16;
+
 __device__ __forceinline__ void fill_srgb_table(double* tab) {      // tab: 256 doubles of LDS; ends with a barrier
     for (int i = threadIdx.x; i < 256; i += blockDim.x) tab[i] = srgb8_to_linear(i);
     __syncthreads();
 }
 
-// One channel of colorspace.resize_bilinear_u8's output pixel from its four (clamped) taps: float64, the same expressions in the same
-// order, contraction off (an FMA would change a rounding) -> floor(out + .5) clamped to 0..255
-__device__ __forceinline__ int bilinear_u8(double f00, double f01, double f10, double f11, double wx, double wy) {
+template <typename F>
+__device__ __forceinline__ void fill_source_table(double* tab) {    // uniform over the kernel: only the uint8 formats have a table (and its barrier)
+    if constexpr (F::table) fill_srgb_table(tab);
+}
+
+// One channel of colorspace.resize_bilinear_u8's output pixel from its four (clamped) taps, on the lattice 0..QMAX: float64, the same
+// expressions in the same order, contraction off (an FMA would change a rounding) -> floor(out + .5) clamped to 0..QMAX
+template <int QMAX>
+__device__ __forceinline__ int bilinear_q(double f00, double f01, double f10, double f11, double wx, double wy) {
 #pragma clang fp contract(off)
     const double top = f00 * (1.0 - wx) + f01 * wx;
     const double bot = f10 * (1.0 - wx) + f11 * wx;
     const double out = top * (1.0 - wy) + bot * wy;
     const double r = floor(out + 0.5);
-    return r < 0.0 ? 0 : (r > 255.0 ? 255 : (int)r);
+    return r < 0.0 ? 0 : (r > (double)QMAX ? QMAX : (int)r);
 }
 
 // half-pixel source coordinate of output index i: tap0 / tap1 clamped to 0..in-1, w = the weight of tap1
@@ -341,63 +380,157 @@ __device__ __forceinline__ void bilinear_taps(int i, int in, int out, int& t0, i
     t1 = (int)(i0 + 1 < 0 ? 0 : (i0 + 1 > in - 1 ? in - 1 : i0 + 1));
 }
 
-// One thread per net-size pixel of all n images: srcs[i] = image i's [src_h,src_w,3] uint8 source; Lp = the resident L plane of the first
-// slot ([n][H*W] fp32, gets L - l_cent); rgb_net [n,H,W,3] and lab_net [n,3,H,W] may be nullptr.
-__global__ __launch_bounds__(256) void ingest_rgb_kernel(const unsigned char* const* __restrict__ srcs, int n, int src_h, int src_w, int H, int W,
-                                                         float l_cent, float* __restrict__ Lp, unsigned char* __restrict__ rgb_net,
-                                                         double* __restrict__ lab_net) {
-    __shared__ double tab[256];
-    fill_srgb_table(tab);
-    const long long HW = (long long)H * W, npix = (long long)n * HW;
-    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (long long)gridDim.x * blockDim.x) {
+// THE net-size pixel: the C quantised channels q of pixel (y, x) of the [H,W] image resized from img [sh,sw,C] -- four clamped taps, gathered
+// sample by sample, so no alignment is asked of an image's start.  Every kernel that brings a source to the net size calls this.
+template <typename F>
+__device__ __forceinline__ void net_sample(const typename F::sample* __restrict__ img, int sh, int sw, int H, int W, int y, int x, int* q) {
+    constexpr int C = F::channels;
+    int y0, y1, x0, x1;
+    double wy, wx;
+    bilinear_taps(y, sh, H, y0, y1, wy);
+    bilinear_taps(x, sw, W, x0, x1, wx);
+    const typename F::sample* p00 = img + ((long long)y0 * sw + x0) * C; const typename F::sample* p01 = img + ((long long)y0 * sw + x1) * C;
+    const typename F::sample* p10 = img + ((long long)y1 * sw + x0) * C; const typename F::sample* p11 = img + ((long long)y1 * sw + x1) * C;
+#pragma unroll
+    for (int c = 0; c < C; ++c) q[c] = bilinear_q<F::qmax>((double)p00[c], (double)p01[c], (double)p10[c], (double)p11[c], wx, wy);
+}
+
+// Lab of the source colour q[C]: sRGB -> linear per sample (the table for uint8, srgb_to_linear(q / full scale) for uint16), a grey sample on
+// all three channels, then linear_to_lab
+template <typename F>
+__device__ __forceinline__ void source_lab(const int* q, const double* tab, double& L, double& a, double& b) {
+    constexpr int C = F::channels;
+    double t[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        if constexpr (F::table) t[c] = tab[q[c]]; else t[c] = srgb_to_linear((double)q[c] / F::full);
+    }
+    const double lin[3] = {t[0], t[C == 3 ? 1 : 0], t[C == 3 ? 2 : 0]};
+    linear_to_lab(lin, L, a, b);
+}
+
+// lab_to_rgb_u8 for either depth: (O)(s * full scale), truncation
+template <typename O>
+__device__ __forceinline__ void lab_to_rgb_q(double L, double a, double b, O* q) {
+    double s[3];
+    lab_to_srgb(L, a, b, s);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) q[c] = (O)(s[c] * Depth<O>::full);
+}
+
+// The step of a kernel's walk over its `items`, by the grid policy its LAUNCHER states in the kernel's first template argument.  EXACT = false: the
+// grid may be capped (grid_blocks), the kernel strides by it.  EXACT = true: the launcher promises gridDim.x * blockDim.x >= items, one pass; saying
+// so at compile time keeps the loop's invariants out of registers (a strided fullres_kernel<., Gray8, u8, double> takes 168 VGPRs, the single
+// pass 74: three workgroups per SIMD against six).  A launcher that caps a grid must launch the EXACT = false form: the other would skip items.
+template <bool EXACT>
+__device__ __forceinline__ long long item_stride(long long items) {
+    return EXACT ? items : (long long)gridDim.x * blockDim.x;
+}
+
+// The four pixels of a dword group.  unpack_group: the C samples of pixel k < 4 from the group's C * sizeof(T) source dwords; pack_group: the
+// three values of pixel k into the group's 3 * sizeof(O) result dwords (zeroed by the caller).
+template <typename F>
+__device__ __forceinline__ void unpack_group(const unsigned* in, int k, int* q) {
+#pragma unroll
+    for (int c = 0; c < F::channels; ++c) {
+        const int e = k * F::channels + c;
+        if constexpr (sizeof(typename F::sample) == 1) q[c] = (int)((in[e >> 2] >> (8 * (e & 3))) & 255u);
+        else q[c] = (int)((in[e >> 1] >> (16 * (e & 1))) & 65535u);
+    }
+}
+
+template <typename O>
+__device__ __forceinline__ void pack_group(unsigned* out, int k, const O* o) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int e = k * 3 + c;
+        if constexpr (sizeof(O) == 1) out[e >> 2] |= (unsigned)o[c] << (8 * (e & 3)); else out[e >> 1] |= (unsigned)o[c] << (16 * (e & 1));
+    }
+}
+
+// The grid policy of the four walking launchers.  bits 0 (RGB): capped -- one launch site per grid tag (idc_grid.h), which hands grid_blocks its
+// tag and cap and launches the RGB8 form under the tag's name (the `*_rgb_kernel` / `*_prologue_kernel` aliases below).  bits 8 | 16 (grey):
+// exact -- `want` workgroups cover the items in one pass, refused past 2^31 - 1.
+static bool exact_grid_ok(long long want) { return want <= 0x7fffffffll; }
+
+// the four (source format, output depth) forms times the two plane types: f(F(), O(), S()) launches its kernel<F, O, S>.  bits 0 = RGB8, whose
+// only output is uint8; bits 8 | 16 = Gray8 | Gray16.  WITH_RGB = false: a launcher whose RGB launches have sites of their own (the capped ones)
+// leaves the RGB8 forms out, so that no exact-grid RGB8 kernel nobody launches is compiled.
+template <bool WITH_RGB, typename Fn>
+static hipError_t source_forms(int bits, int out_bits, int src_f64, Fn&& f) {
+    typedef unsigned char u8;
+    typedef unsigned short u16;
+    if (WITH_RGB && bits == 0 && out_bits == 8) {
+        if constexpr (WITH_RGB) { if (src_f64) f(RGB8(), u8(), double()); else f(RGB8(), u8(), float()); }
+    }
+    else if (bits == 8 && out_bits == 8) { if (src_f64) f(Gray8(), u8(), double()); else f(Gray8(), u8(), float()); }
+    else if (bits == 16 && out_bits == 8) { if (src_f64) f(Gray16(), u8(), double()); else f(Gray16(), u8(), float()); }
+    else if (bits == 16 && out_bits == 16) { if (src_f64) f(Gray16(), u16(), double()); else f(Gray16(), u16(), float()); }
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// One thread per net-size pixel of all n images: srcs[i] = image i's [src_h,src_w,C] source; Lp = the resident L plane of the first slot
+// ([n][H*W] fp32, gets L - l_cent); net [n,H,W,C] (the sample type) and lab_net [n,C,H,W] f64 -- (L, a, b) of a colour image, L of a plane --
+// may be nullptr.
+template <bool EXACT, typename F>
+__global__ __launch_bounds__(256) void ingest_kernel(const typename F::sample* const* __restrict__ srcs, long long npix, int src_h, int src_w, int H,
+                                                     int W, float l_cent, float* __restrict__ Lp, typename F::sample* __restrict__ net,
+                                                     double* __restrict__ lab_net) {
+    constexpr int C = F::channels;
+    __shared__ double tab[F::table ? 256 : 1];
+    fill_source_table<F>(tab);
+    const long long HW = (long long)H * W;
+    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += item_stride<EXACT>(npix)) {
         const long long i = p / HW, r = p - i * HW;
         const int y = (int)(r / W), x = (int)(r - (long long)y * W);
-        int y0, y1, x0, x1;
-        double wy, wx;
-        bilinear_taps(y, src_h, H, y0, y1, wy);
-        bilinear_taps(x, src_w, W, x0, x1, wx);
-        const unsigned char* src = srcs[i];
-        const unsigned char* p00 = src + ((long long)y0 * src_w + x0) * 3; const unsigned char* p01 = src + ((long long)y0 * src_w + x1) * 3;
-        const unsigned char* p10 = src + ((long long)y1 * src_w + x0) * 3; const unsigned char* p11 = src + ((long long)y1 * src_w + x1) * 3;
-        int q[3];
-        double lin[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            q[c] = bilinear_u8((double)p00[c], (double)p01[c], (double)p10[c], (double)p11[c], wx, wy);
-            lin[c] = tab[q[c]];
-        }
+        int q[C];
+        net_sample<F>(srcs[i], src_h, src_w, H, W, y, x, q);
         double L, a, b;
-        linear_to_lab(lin, L, a, b);
+        source_lab<F>(q, tab, L, a, b);
         Lp[p] = (float)(L - (double)l_cent);
-        if (rgb_net != nullptr) { rgb_net[p * 3 + 0] = (unsigned char)q[0]; rgb_net[p * 3 + 1] = (unsigned char)q[1]; rgb_net[p * 3 + 2] = (unsigned char)q[2]; }
-        if (lab_net != nullptr) {
-            lab_net[(i * 3 + 0) * HW + r] = L; lab_net[(i * 3 + 1) * HW + r] = a; lab_net[(i * 3 + 2) * HW + r] = b;
+        const double lab[3] = {L, a, b};
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            if (net != nullptr) net[p * C + c] = (typename F::sample)q[c];
+            if (lab_net != nullptr) lab_net[(i * C + c) * HW + r] = lab[c];
         }
     }
 }
 
-hipError_t launch_ingest_rgb(const unsigned char* const* srcs, int n, int src_h, int src_w, int H, int W, float l_cent, float* Lp,
-                             unsigned char* rgb_net, double* lab_net, hipStream_t s) {
+// (the RGB8 form under the name of its launch site's grid tag: one tag, one launch site, one kernel name -- tests/test_grid_cap_cpu.py reads them)
+constexpr auto ingest_rgb_kernel = ingest_kernel<false, RGB8>;
+
+hipError_t launch_ingest(int bits, const void* const* srcs, int n, int src_h, int src_w, int H, int W, float l_cent, float* Lp, void* net,
+                         double* lab_net, hipStream_t s) {
     const long long npix = (long long)n * H * W;
     if (npix <= 0 || src_h <= 0 || src_w <= 0) return hipErrorInvalidValue;
-    const int blocks = grid_blocks(GridTag::ingest_rgb, (npix + 255) / 256, 4096);
-    hipLaunchKernelGGL(ingest_rgb_kernel, dim3(blocks), dim3(256), 0, s, srcs, n, src_h, src_w, H, W, l_cent, Lp, rgb_net, lab_net);
-    return hipGetLastError();
+    const long long want = (npix + 255) / 256;
+    if (bits == 0) {
+        const int blocks = grid_blocks(GridTag::ingest_rgb, want, 4096);
+        hipLaunchKernelGGL(ingest_rgb_kernel, dim3(blocks), dim3(256), 0, s, (const unsigned char* const*)srcs, npix, src_h, src_w, H, W, l_cent, Lp,
+                           (unsigned char*)net, lab_net);
+        return hipGetLastError();
+    }
+    if (!exact_grid_ok(want)) return hipErrorInvalidValue;      // grey: dim3(want) covers every item, hence the EXACT form
+    return source_forms<false>(bits, bits, 1, [&](auto f, auto, auto) {
+        typedef decltype(f) F; typedef typename F::sample T;
+        hipLaunchKernelGGL((ingest_kernel<true, F>), dim3((unsigned)want), dim3(256), 0, s, (const T* const*)srcs, npix, src_h, src_w, H, W, l_cent, Lp, (T*)net,
+                           lab_net);
+    });
 }
 
-// One full-resolution output pixel p of an [oh,ow] image from its own source colour q: L = rgb2lab(q)[0] (mask == nullptr) or
+// One full-resolution output pixel p of an [oh,ow] image from its own source colour q: L = source_lab(q)'s (mask == nullptr) or
 // 50 * nearest(mask) / mask_value (0 when mask_value == 0: no hints were ever rasterised), (a, b) interpolated from pa / pb [H,W]
-// (nullptr: a = b = 0), then lab_to_rgb_u8.
-template <typename S>
+// (nullptr: a = b = 0), then Lab -> RGB at O's depth.
+template <typename F, typename O, typename S>
 __device__ __forceinline__ void fullres_pixel(long long p, const int* q, const double* tab, const S* __restrict__ pa, const S* __restrict__ pb,
-                                              int H, int W, int interp, const float* __restrict__ mask, float mask_value, int oh, int ow,
-                                              unsigned char* out) {
+                                              int H, int W, int interp, const float* __restrict__ mask, float mask_value, int oh, int ow, O* out) {
     const int dy = (int)(p / ow), dx = (int)(p - (long long)dy * ow);
     double L, ab[2] = {0.0, 0.0};
     if (mask == nullptr) {
-        const double lin[3] = {tab[q[0]], tab[q[1]], tab[q[2]]};
         double a_, b_;
-        linear_to_lab(lin, L, a_, b_);
+        source_lab<F>(q, tab, L, a_, b_);
     } else if (mask_value != 0.f) {
         int yy, xx;
         zoom_nearest(dy, dx, H, W, oh, ow, yy, xx);
@@ -406,87 +539,92 @@ __device__ __forceinline__ void fullres_pixel(long long p, const int* q, const d
         L = 0.0;
     }
     if (pa != nullptr) interp_ab(pa, pb, H, W, interp, dy, dx, oh, ow, ab);
-    lab_to_rgb_u8(L, ab[0], ab[1], out);
+    lab_to_rgb_q<O>(L, ab[0], ab[1], out);
 }
 
-// A thread takes 4 consecutive pixels of the flattened image = 12 bytes = three aligned dwords in, three out (src and rgb are 4-byte aligned:
-// device allocations); the npix % 4 pixels at the end go one per thread through byte accesses.
-template <typename S>
-__global__ __launch_bounds__(256) void fullres_rgb_kernel(const unsigned char* __restrict__ src, int oh, int ow, const S* __restrict__ pa,
-                                                          const S* __restrict__ pb, int H, int W, int interp, const float* __restrict__ mask,
-                                                          float mask_value, unsigned char* __restrict__ rgb) {
-    __shared__ double tab[256];
-    fill_srgb_table(tab);
+// One image.  A thread takes 4 consecutive pixels of the flattened image: C * sizeof(T) aligned dwords in (RGB8 three, Gray8 one, Gray16 two),
+// 3 * sizeof(O) aligned dwords out (three or six); src and rgb are 4-byte aligned (device allocations).  The npix % 4 pixels at the end go one
+// per thread of workgroup 0 through narrow accesses.
+template <bool EXACT, typename F, typename O, typename S>
+__global__ __launch_bounds__(256) void fullres_kernel(const typename F::sample* __restrict__ src, int oh, int ow, const S* __restrict__ pa,
+                                                      const S* __restrict__ pb, int H, int W, int interp, const float* __restrict__ mask,
+                                                      float mask_value, O* __restrict__ rgb) {
+    constexpr int C = F::channels, kIn = F::group_dwords, kOut = 3 * (int)sizeof(O);      // dwords per group of 4 pixels
+    __shared__ double tab[F::table ? 256 : 1];
+    fill_source_table<F>(tab);
     const long long npix = (long long)oh * ow, ngroups = npix >> 2;
     const unsigned* src4 = (const unsigned*)src;
     unsigned* rgb4 = (unsigned*)rgb;
-    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (long long)gridDim.x * blockDim.x) {
-        const unsigned in[3] = {src4[g * 3 + 0], src4[g * 3 + 1], src4[g * 3 + 2]};
-        unsigned out[3] = {0u, 0u, 0u};
+    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += item_stride<EXACT>(ngroups)) {
+        unsigned in[kIn], out[kOut];
+#pragma unroll
+        for (int j = 0; j < kIn; ++j) in[j] = src4[g * kIn + j];
+#pragma unroll
+        for (int j = 0; j < kOut; ++j) out[j] = 0u;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            int q[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) q[c] = (int)((in[(k * 3 + c) >> 2] >> (8 * ((k * 3 + c) & 3))) & 255u);
-            unsigned char o[3];
-            fullres_pixel(g * 4 + k, q, tab, pa, pb, H, W, interp, mask, mask_value, oh, ow, o);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) out[(k * 3 + c) >> 2] |= (unsigned)o[c] << (8 * ((k * 3 + c) & 3));
+            int q[C];
+            unpack_group<F>(in, k, q);
+            O o[3];
+            fullres_pixel<F, O, S>(g * 4 + k, q, tab, pa, pb, H, W, interp, mask, mask_value, oh, ow, o);
+            pack_group<O>(out, k, o);
         }
-        rgb4[g * 3 + 0] = out[0]; rgb4[g * 3 + 1] = out[1]; rgb4[g * 3 + 2] = out[2];
+#pragma unroll
+        for (int j = 0; j < kOut; ++j) rgb4[g * kOut + j] = out[j];
     }
     if (blockIdx.x == 0) {
         const long long p = ngroups * 4 + threadIdx.x;
         if (p < npix) {
-            const int q[3] = {src[p * 3 + 0], src[p * 3 + 1], src[p * 3 + 2]};
-            unsigned char o[3];
-            fullres_pixel(p, q, tab, pa, pb, H, W, interp, mask, mask_value, oh, ow, o);
+            int q[C];
+#pragma unroll
+            for (int c = 0; c < C; ++c) q[c] = (int)src[p * C + c];
+            O o[3];
+            fullres_pixel<F, O, S>(p, q, tab, pa, pb, H, W, interp, mask, mask_value, oh, ow, o);
             rgb[p * 3 + 0] = o[0]; rgb[p * 3 + 1] = o[1]; rgb[p * 3 + 2] = o[2];
         }
     }
 }
 
-hipError_t launch_fullres_rgb(const unsigned char* src, int oh, int ow, const void* a_plane, const void* b_plane, int src_f64, int H, int W,
-                              int interp, const float* mask, float mask_value, unsigned char* rgb, hipStream_t s) {
+template <typename S> constexpr auto fullres_rgb_kernel = fullres_kernel<false, RGB8, unsigned char, S>;
+
+hipError_t launch_fullres(int bits, const void* src, int oh, int ow, const void* a_plane, const void* b_plane, int src_f64, int H, int W, int interp,
+                          const float* mask, float mask_value, void* rgb, int out_bits, hipStream_t s) {
     const long long npix = (long long)oh * ow;
     if (npix <= 0 || interp < 0 || interp > 2 || (((uintptr_t)src | (uintptr_t)rgb) & 3)) return hipErrorInvalidValue;
-    const long long ngroups = (npix + 3) >> 2;
-    const int blocks = grid_blocks(GridTag::fullres_rgb, (ngroups + 255) / 256, 8192);
-    if (src_f64)
-        hipLaunchKernelGGL(fullres_rgb_kernel<double>, dim3(blocks), dim3(256), 0, s, src, oh, ow, (const double*)a_plane, (const double*)b_plane,
-                           H, W, interp, mask, mask_value, rgb);
-    else
-        hipLaunchKernelGGL(fullres_rgb_kernel<float>, dim3(blocks), dim3(256), 0, s, src, oh, ow, (const float*)a_plane, (const float*)b_plane,
-                           H, W, interp, mask, mask_value, rgb);
-    return hipGetLastError();
+    const long long want = (((npix + 3) >> 2) + 255) / 256;
+    if (bits == 0) {
+        if (out_bits != 8) return hipErrorInvalidValue;
+        const int blocks = grid_blocks(GridTag::fullres_rgb, want, 8192);
+        if (src_f64)
+            hipLaunchKernelGGL(fullres_rgb_kernel<double>, dim3(blocks), dim3(256), 0, s, (const unsigned char*)src, oh, ow, (const double*)a_plane,
+                               (const double*)b_plane, H, W, interp, mask, mask_value, (unsigned char*)rgb);
+        else
+            hipLaunchKernelGGL(fullres_rgb_kernel<float>, dim3(blocks), dim3(256), 0, s, (const unsigned char*)src, oh, ow, (const float*)a_plane,
+                               (const float*)b_plane, H, W, interp, mask, mask_value, (unsigned char*)rgb);
+        return hipGetLastError();
+    }
+    if (!exact_grid_ok(want)) return hipErrorInvalidValue;      // grey: dim3(want) covers every item, hence the EXACT form
+    return source_forms<false>(bits, out_bits, src_f64, [&](auto f, auto o, auto p) {
+        typedef decltype(f) F; typedef decltype(o) O; typedef decltype(p) S;
+        hipLaunchKernelGGL((fullres_kernel<true, F, O, S>), dim3((unsigned)want), dim3(256), 0, s, (const typename F::sample*)src, oh, ow, (const S*)a_plane,
+                           (const S*)b_plane, H, W, interp, mask, mask_value, (O*)rgb);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
-// pipelined uint8 batches (idc_forward_async_rgb): what idc_set_image_rgb + idc_set_hints per image do before a blocking forward and what
-// idc_fullres_rgb per image does after it, each as ONE launch over a slot's packed arrays.  The per-pixel arithmetic is the device functions
+// pipelined batches (idc_forward_async_rgb / _images / _gray): what idc_set_image_rgb + idc_set_hints per image do before a blocking forward and
+// what idc_fullres_rgb per image does after it, each as ONE launch over a slot's packed arrays.  The per-pixel arithmetic is the device functions
 // above on the same operands, so a batch equals the blocking route bit for bit.
+// Images of INDIVIDUAL sizes come with a table imgs[0..n] (ImgDesc: byte offset of the image in the packed source, pixels in front of it, h, w;
+// entry n closes the run with the totals); imgs == nullptr is a uniform run of n images of sh x sw packed back to back, whose entries are
+// computed instead of loaded.  An image's bits do not depend on the route, on its position or on its neighbours.  The table is at most
+// max_batch + 1 entries and read-only, so it is read where it lies, through the cache.
 // ------------------------------------------------------------------------------------------------
-// One thread per net-size pixel of all n images, grid-stride.  L: ingest_rgb_kernel's pixel (four clamped uint8 taps of image i, which starts at
-// byte i * src_h * src_w * 3 of the packed source; the taps are byte gathers, so no alignment is asked of an image's start).  Hints: image i's
-// clipped list hints[offs[i] .. offs[i+1]) walked last first, raster_hints_kernel's pixel; an RGB hint goes through the LDS table, whose
-// entries are the per-colour expression of raster_hints_kernel.  The three planes are written as coalesced fp32.
-// The pixel both prologue kernels compute: net-size pixel (y, x) of an image whose [sh,sw,3] source starts at img, and the image's clipped hints
-// hints[lo .. hi).  -> L - l_cent, and (a, b, mask) of the last covering hint (0, 0, 0 without one).
-__device__ __forceinline__ void prologue_pixel(const unsigned char* __restrict__ img, int sh, int sw, int H, int W, int y, int x, float l_cent,
-                                               const double* tab, const HintRect* __restrict__ hints, int lo, int hi, int mode, float mask_value,
-                                               float& Lv, float& a, float& b, float& m) {
-    int y0, y1, x0, x1;
-    double wy, wx;
-    bilinear_taps(y, sh, H, y0, y1, wy);
-    bilinear_taps(x, sw, W, x0, x1, wx);
-    const unsigned char* p00 = img + ((long long)y0 * sw + x0) * 3; const unsigned char* p01 = img + ((long long)y0 * sw + x1) * 3;
-    const unsigned char* p10 = img + ((long long)y1 * sw + x0) * 3; const unsigned char* p11 = img + ((long long)y1 * sw + x1) * 3;
-    double lin[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) lin[c] = tab[bilinear_u8((double)p00[c], (double)p01[c], (double)p10[c], (double)p11[c], wx, wy)];
-    double L, a_, b_;
-    linear_to_lab(lin, L, a_, b_);
-    Lv = (float)(L - (double)l_cent);
+// The hint walk: image-local net-size pixel (y, x) against the image's clipped list hints[lo .. hi) walked last first, raster_hints_kernel's pixel
+// -> (a, b, mask) of the last covering hint (0, 0, 0 without one).  An RGB hint goes through the LDS table, whose entries are the per-colour
+// expression of raster_hints_kernel.
+__device__ __forceinline__ void hint_walk(const HintRect* __restrict__ hints, int lo, int hi, int mode, float mask_value, const double* tab, int y,
+                                          int x, float& a, float& b, float& m) {
     int hit = -1;
     for (int k = hi - 1; k >= lo; --k) {
         const HintRect h = hints[k];
@@ -507,97 +645,73 @@ __device__ __forceinline__ void prologue_pixel(const unsigned char* __restrict__
     }
 }
 
-__global__ __launch_bounds__(256) void batch_prologue_kernel(const unsigned char* __restrict__ src, int n, int src_h, int src_w, int H, int W,
-                                                             float l_cent, const int* __restrict__ offs, const HintRect* __restrict__ hints,
-                                                             int mode, float mask_value, float* __restrict__ Lp, float* __restrict__ ab,
-                                                             float* __restrict__ mask) {
+// One thread per net-size pixel of all n images, grid-stride.  L: ingest_kernel's pixel of image i = p / (H*W), which starts at byte imgs[i].off
+// of the packed source with its own h x w (uniform: at sample i * sh * sw * C); hints: the walk above over hints[offs[i] .. offs[i+1])
+// (offs == nullptr: no image has hints).  The three planes are written as coalesced fp32.
+// TABLE (the launcher's: imgs != nullptr) is a template argument, so each run form is a kernel of its own from the one body: in a uniform run the
+// source size is the same for every lane and the taps' scale stays a scalar outside the loop, and neither form carries the other's code.
+template <bool EXACT, bool TABLE, typename F>
+__global__ __launch_bounds__(256) void prologue_kernel(const typename F::sample* __restrict__ src, const ImgDesc* __restrict__ imgs, long long npix,
+                                                       int sh, int sw, int H, int W, float l_cent, const int* __restrict__ offs,
+                                                       const HintRect* __restrict__ hints, int mode, float mask_value, float* __restrict__ Lp,
+                                                       float* __restrict__ ab, float* __restrict__ mask) {
+    typedef typename F::sample T;
+    constexpr int C = F::channels;
     __shared__ double tab[256];
     fill_srgb_table(tab);
-    const long long HW = (long long)H * W, npix = (long long)n * HW, sb = (long long)src_h * src_w * 3;
-    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (long long)gridDim.x * blockDim.x) {
+    const long long HW = (long long)H * W;
+    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += item_stride<EXACT>(npix)) {
         const long long i = p / HW, r = p - i * HW;
         const int y = (int)(r / W), x = (int)(r - (long long)y * W);
+        const T* img;
+        int h, w;
+        if constexpr (TABLE) {
+            const ImgDesc d = imgs[i];
+            img = (const T*)((const unsigned char*)src + d.off); h = d.h; w = d.w;
+        } else {
+            img = src + i * ((long long)sh * sw * C); h = sh; w = sw;
+        }
+        int q[C];
+        net_sample<F>(img, h, w, H, W, y, x, q);
+        double L, a_, b_;
+        source_lab<F>(q, tab, L, a_, b_);
         const int lo = offs != nullptr ? offs[i] : 0, hi = offs != nullptr ? offs[i + 1] : 0;
-        float Lv, a, b, m;
-        prologue_pixel(src + i * sb, src_h, src_w, H, W, y, x, l_cent, tab, hints, lo, hi, mode, mask_value, Lv, a, b, m);
-        Lp[p] = Lv;
+        float a, b, m;
+        hint_walk(hints, lo, hi, mode, mask_value, tab, y, x, a, b, m);
+        Lp[p] = (float)(L - (double)l_cent);
         ab[(i * 2 + 0) * HW + r] = a;
         ab[(i * 2 + 1) * HW + r] = b;
         mask[p] = m;
     }
 }
 
-hipError_t launch_batch_prologue(const unsigned char* src, int n, int src_h, int src_w, int H, int W, float l_cent, const int* offs,
-                                 const HintRect* hints, int mode, float mask_value, float* Lp, float* ab, float* mask, hipStream_t s) {
+constexpr auto batch_prologue_kernel = prologue_kernel<false, false, RGB8>, ragged_prologue_kernel = prologue_kernel<false, true, RGB8>;      // uniform run | table
+
+hipError_t launch_prologue(int bits, const void* src, const ImgDesc* imgs, int n, int sh, int sw, int H, int W, float l_cent, const int* offs,
+                           const HintRect* hints, int mode, float mask_value, float* Lp, float* ab, float* mask, hipStream_t s) {
     const long long npix = (long long)n * H * W;
-    if (npix <= 0 || src_h <= 0 || src_w <= 0 || (mode != 0 && mode != 1)) return hipErrorInvalidValue;
-    const int blocks = grid_blocks(GridTag::batch_prologue, (npix + 255) / 256, 4096);
-    hipLaunchKernelGGL(batch_prologue_kernel, dim3(blocks), dim3(256), 0, s, src, n, src_h, src_w, H, W, l_cent, offs, hints, mode, mask_value, Lp, ab,
-                       mask);
-    return hipGetLastError();
-}
-
-// fullres_rgb_kernel over a packed [n,oh,ow,3] batch.  Image i starts at byte i * oh * ow * 3, misaligned whenever that count is no multiple of
-// 4, so neither an aligned pitch nor a scalar head and tail per image is used: the n * oh * ow pixels are taken as ONE flat run from the
-// 4-byte aligned base of the allocation.  A thread takes 4 consecutive pixels of that run = three aligned dwords in, three out, as in
-// fullres_rgb_kernel; a group may straddle two images, and every pixel finds its own image and position (one division per group, then a
-// carry).  Only the (n * oh * ow) % 4 pixels at the end of the whole batch go through byte accesses.  The arrays stay packed, so they travel
-// as one contiguous copy each way.
-__global__ __launch_bounds__(256) void batch_fullres_rgb_kernel(const unsigned char* __restrict__ src, long long total, int oh, int ow,
-                                                                const double* __restrict__ lab_q, int H, int W, int interp,
-                                                                unsigned char* __restrict__ rgb) {
-    __shared__ double tab[256];
-    fill_srgb_table(tab);
-    const long long npix = (long long)oh * ow, HW = (long long)H * W, ngroups = total >> 2;
-    const unsigned* src4 = (const unsigned*)src;
-    unsigned* rgb4 = (unsigned*)rgb;
-    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (long long)gridDim.x * blockDim.x) {
-        const unsigned in[3] = {src4[g * 3 + 0], src4[g * 3 + 1], src4[g * 3 + 2]};
-        unsigned out[3] = {0u, 0u, 0u};
-        long long i = (g * 4) / npix, p = g * 4 - i * npix;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            int q[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) q[c] = (int)((in[(k * 3 + c) >> 2] >> (8 * ((k * 3 + c) & 3))) & 255u);
-            unsigned char o[3];
-            const double* pa = lab_q + (i * 3 + 1) * HW;
-            fullres_pixel(p, q, tab, pa, pa + HW, H, W, interp, (const float*)nullptr, 0.f, oh, ow, o);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) out[(k * 3 + c) >> 2] |= (unsigned)o[c] << (8 * ((k * 3 + c) & 3));
-            if (++p == npix) { p = 0; ++i; }
-        }
-        rgb4[g * 3 + 0] = out[0]; rgb4[g * 3 + 1] = out[1]; rgb4[g * 3 + 2] = out[2];
+    if (npix <= 0 || (imgs == nullptr && (bits != 0 || sh <= 0 || sw <= 0)) || (mode != 0 && mode != 1)) return hipErrorInvalidValue;
+    const long long want = (npix + 255) / 256;
+    if (bits == 0 && imgs == nullptr) {
+        const int blocks = grid_blocks(GridTag::batch_prologue, want, 4096);
+        hipLaunchKernelGGL(batch_prologue_kernel, dim3(blocks), dim3(256), 0, s, (const unsigned char*)src, imgs, npix, sh, sw, H, W, l_cent, offs, hints,
+                           mode, mask_value, Lp, ab, mask);
+        return hipGetLastError();
     }
-    if (blockIdx.x == 0) {
-        const long long t = ngroups * 4 + threadIdx.x;
-        if (t < total) {
-            const long long i = t / npix, p = t - i * npix;
-            const int q[3] = {src[t * 3 + 0], src[t * 3 + 1], src[t * 3 + 2]};
-            unsigned char o[3];
-            const double* pa = lab_q + (i * 3 + 1) * HW;
-            fullres_pixel(p, q, tab, pa, pa + HW, H, W, interp, (const float*)nullptr, 0.f, oh, ow, o);
-            rgb[t * 3 + 0] = o[0]; rgb[t * 3 + 1] = o[1]; rgb[t * 3 + 2] = o[2];
-        }
+    if (bits == 0) {
+        const int blocks = grid_blocks(GridTag::ragged_prologue, want, 4096);
+        hipLaunchKernelGGL(ragged_prologue_kernel, dim3(blocks), dim3(256), 0, s, (const unsigned char*)src, imgs, npix, sh, sw, H, W, l_cent, offs, hints,
+                           mode, mask_value, Lp, ab, mask);
+        return hipGetLastError();
     }
+    if (!exact_grid_ok(want)) return hipErrorInvalidValue;      // grey: dim3(want) covers every item, hence the EXACT form
+    return source_forms<false>(bits, bits, 1, [&](auto f, auto, auto) {
+        typedef decltype(f) F;
+        hipLaunchKernelGGL((prologue_kernel<true, true, F>), dim3((unsigned)want), dim3(256), 0, s, (const typename F::sample*)src, imgs, npix, sh, sw, H, W, l_cent, offs,
+                           hints, mode, mask_value, Lp, ab, mask);
+    });
 }
 
-hipError_t launch_batch_fullres_rgb(const unsigned char* src, int n, int oh, int ow, const double* lab_q, int H, int W, int interp,
-                                    unsigned char* rgb, hipStream_t s) {
-    const long long total = (long long)n * oh * ow;
-    if (n <= 0 || oh <= 0 || ow <= 0 || interp < 0 || interp > 2 || (((uintptr_t)src | (uintptr_t)rgb) & 3)) return hipErrorInvalidValue;
-    const long long ngroups = (total + 3) >> 2;
-    const int blocks = grid_blocks(GridTag::batch_fullres_rgb, (ngroups + 255) / 256, 8192);
-    hipLaunchKernelGGL(batch_fullres_rgb_kernel, dim3(blocks), dim3(256), 0, s, src, total, oh, ow, lab_q, H, W, interp, rgb);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------------
-// batches of images of INDIVIDUAL sizes (idc_forward_async_images): the two kernels above over a table imgs[0..n] (ImgDesc: byte offset of
-// the image in the packed source, pixels in front of it, h, w; entry n closes the run with the totals).  Still ONE launch each for all n
-// images, and the per-pixel arithmetic is the same device functions on the same operands, so an image's bits do not depend on the route, on
-// its position or on its neighbours.  The table is at most max_batch + 1 entries and read-only, so it is read where it lies, through the cache.
-// ------------------------------------------------------------------------------------------------
 // The last image of imgs[lo .. hi] that starts at or in front of pixel t of the flat run (imgs[lo].first <= t).
 __device__ __forceinline__ int image_of_pixel(const ImgDesc* __restrict__ imgs, int lo, int hi, long long t) {
     while (lo < hi) {
@@ -607,95 +721,118 @@ __device__ __forceinline__ int image_of_pixel(const ImgDesc* __restrict__ imgs, 
     return lo;
 }
 
-// batch_prologue_kernel with pixel p's image i = p / (H*W) read from the table: its own h x w, its own start in the packed source.
-__global__ __launch_bounds__(256) void ragged_prologue_kernel(const unsigned char* __restrict__ src, const ImgDesc* __restrict__ imgs, int n, int H,
-                                                              int W, float l_cent, const int* __restrict__ offs,
-                                                              const HintRect* __restrict__ hints, int mode, float mask_value,
-                                                              float* __restrict__ Lp, float* __restrict__ ab, float* __restrict__ mask) {
-    __shared__ double tab[256];
-    fill_srgb_table(tab);
-    const long long HW = (long long)H * W, npix = (long long)n * HW;
-    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (long long)gridDim.x * blockDim.x) {
-        const long long i = p / HW, r = p - i * HW;
-        const int y = (int)(r / W), x = (int)(r - (long long)y * W);
-        const ImgDesc d = imgs[i];
-        const int lo = offs != nullptr ? offs[i] : 0, hi = offs != nullptr ? offs[i + 1] : 0;
-        float Lv, a, b, m;
-        prologue_pixel(src + d.off, d.h, d.w, H, W, y, x, l_cent, tab, hints, lo, hi, mode, mask_value, Lv, a, b, m);
-        Lp[p] = Lv;
-        ab[(i * 2 + 0) * HW + r] = a;
-        ab[(i * 2 + 1) * HW + r] = b;
-        mask[p] = m;
-    }
-}
-
-hipError_t launch_ragged_prologue(const unsigned char* src, const ImgDesc* imgs, int n, int H, int W, float l_cent, const int* offs,
-                                  const HintRect* hints, int mode, float mask_value, float* Lp, float* ab, float* mask, hipStream_t s) {
-    const long long npix = (long long)n * H * W;
-    if (npix <= 0 || imgs == nullptr || (mode != 0 && mode != 1)) return hipErrorInvalidValue;
-    const int blocks = grid_blocks(GridTag::ragged_prologue, (npix + 255) / 256, 4096);
-    hipLaunchKernelGGL(ragged_prologue_kernel, dim3(blocks), dim3(256), 0, s, src, imgs, n, H, W, l_cent, offs, hints, mode, mask_value, Lp, ab, mask);
-    return hipGetLastError();
-}
-
-// batch_fullres_rgb_kernel over images of individual sizes packed back to back: the sum of h_i * w_i pixels are ONE flat run from the 4-byte
-// aligned base, a thread takes 4 consecutive pixels = three aligned dwords in, three out, whatever residue an image's start has.  The images a
-// workgroup's 1024 pixels of one step touch are bracketed by two searches whose argument does not depend on the lane (the same addresses for
-// every lane: scalar loads); a lane then searches between the two, which is no step at all unless an image starts inside those 1024 pixels.
-// From its first pixel on a group carries into the next image whenever the current one is used up -- every image has a pixel, so one carry per
-// pixel is enough, and a group of four 1 x 1 images carries four times.  Only the total % 4 pixels at the end of the run use byte accesses.
-__global__ __launch_bounds__(256) void ragged_fullres_rgb_kernel(const unsigned char* __restrict__ src, const ImgDesc* __restrict__ imgs, int n,
-                                                                 const double* __restrict__ lab_q, int H, int W, int interp,
-                                                                 unsigned char* __restrict__ rgb) {
-    __shared__ double tab[256];
-    fill_srgb_table(tab);
-    const long long HW = (long long)H * W, total = imgs[n].first, ngroups = total >> 2;
+// fullres_kernel over a packed batch.  Image i starts at pixel first_i of the run, on any residue mod 4, so neither an aligned pitch nor a
+// scalar head and tail per image is used: the `total` pixels are taken as ONE flat run from the 4-byte aligned base of the allocation.  A
+// thread takes 4 consecutive pixels of that run = fullres_kernel's aligned dwords in and out; a group may straddle images, and every pixel
+// finds its own image and position.  Uniform run: one division per group.  Table: the images a workgroup's 1024 pixels of one step touch are
+// bracketed by two searches whose argument does not depend on the lane (the same addresses for every lane: scalar loads); a lane then searches
+// between the two, which is no step at all unless an image starts inside those 1024 pixels.  From its first pixel on a group carries into the
+// next image whenever the current one is used up -- every image has a pixel, so one carry per pixel is enough, and a group of four 1 x 1 images
+// carries four times.  Only the total % 4 pixels at the end of the whole run use narrow accesses.  The arrays stay packed, so they travel as one
+// contiguous copy each way.  (a, b) = planes 1 and 2 of image i's lab_q [n,3,H,W].
+// TABLE is a template argument as in prologue_kernel: the uniform form has no search and keeps oh x ow and its zoom factors scalar, the table form has
+// no division; merged behind a run-time branch the RGB8 form ran 1.5 to 3 % behind either.
+template <bool EXACT, bool TABLE, typename F, typename O>
+__global__ __launch_bounds__(256) void packed_fullres_kernel(const typename F::sample* __restrict__ src, const ImgDesc* __restrict__ imgs, int n,
+                                                             long long total, int oh, int ow, const double* __restrict__ lab_q, int H, int W,
+                                                             int interp, O* __restrict__ rgb) {
+    constexpr int C = F::channels, kIn = F::group_dwords, kOut = 3 * (int)sizeof(O);
+    __shared__ double tab[F::table ? 256 : 1];
+    fill_source_table<F>(tab);
+    const long long HW = (long long)H * W, ngroups = total >> 2;
     const unsigned* src4 = (const unsigned*)src;
     unsigned* rgb4 = (unsigned*)rgb;
-    for (long long g0 = (long long)blockIdx.x * blockDim.x; g0 < ngroups; g0 += (long long)gridDim.x * blockDim.x) {
-        const long long g = g0 + threadIdx.x, last = g0 + blockDim.x < ngroups ? g0 + blockDim.x : ngroups;
-        const int i_lo = image_of_pixel(imgs, 0, n - 1, g0 * 4), i_hi = image_of_pixel(imgs, i_lo, n - 1, last * 4 - 1);
+    for (long long g0 = (long long)blockIdx.x * blockDim.x; g0 < ngroups; g0 += item_stride<EXACT>(ngroups)) {
+        const long long g = g0 + threadIdx.x;
+        int i_lo = 0, i_hi = 0;
+        if constexpr (TABLE) {
+            const long long last = g0 + blockDim.x < ngroups ? g0 + blockDim.x : ngroups;
+            i_lo = image_of_pixel(imgs, 0, n - 1, g0 * 4); i_hi = image_of_pixel(imgs, i_lo, n - 1, last * 4 - 1);
+        }
         if (g >= ngroups) continue;
-        const unsigned in[3] = {src4[g * 3 + 0], src4[g * 3 + 1], src4[g * 3 + 2]};
-        unsigned out[3] = {0u, 0u, 0u};
-        int i = image_of_pixel(imgs, i_lo, i_hi, g * 4);
-        ImgDesc d = imgs[i];
-        long long p = g * 4 - d.first, npix = (long long)d.h * d.w;
+        unsigned in[kIn], out[kOut];
+#pragma unroll
+        for (int j = 0; j < kIn; ++j) in[j] = src4[g * kIn + j];
+#pragma unroll
+        for (int j = 0; j < kOut; ++j) out[j] = 0u;
+        int i, h = oh, w = ow;
+        long long p;
+        if constexpr (TABLE) {
+            i = image_of_pixel(imgs, i_lo, i_hi, g * 4);
+            const ImgDesc d = imgs[i];
+            p = g * 4 - d.first; h = d.h; w = d.w;
+        } else {
+            i = (int)((g * 4) / ((long long)oh * ow)); p = g * 4 - i * ((long long)oh * ow);
+        }
+        long long npix = (long long)h * w;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            int q[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) q[c] = (int)((in[(k * 3 + c) >> 2] >> (8 * ((k * 3 + c) & 3))) & 255u);
-            unsigned char o[3];
+            int q[C];
+            unpack_group<F>(in, k, q);
+            O o[3];
             const double* pa = lab_q + ((long long)i * 3 + 1) * HW;
-            fullres_pixel(p, q, tab, pa, pa + HW, H, W, interp, (const float*)nullptr, 0.f, d.h, d.w, o);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) out[(k * 3 + c) >> 2] |= (unsigned)o[c] << (8 * ((k * 3 + c) & 3));
-            if (++p == npix && k < 3) { p = 0; d = imgs[++i]; npix = (long long)d.h * d.w; }      // i + 1 <= n - 1: the group's next pixel is in the run
+            fullres_pixel<F, O, double>(p, q, tab, pa, pa + HW, H, W, interp, (const float*)nullptr, 0.f, h, w, o);
+            pack_group<O>(out, k, o);
+            if (++p == npix && k < 3) {      // i + 1 <= n - 1: the group's next pixel is in the run
+                p = 0; ++i;
+                if constexpr (TABLE) { const ImgDesc d = imgs[i]; h = d.h; w = d.w; npix = (long long)h * w; }
+            }
         }
-        rgb4[g * 3 + 0] = out[0]; rgb4[g * 3 + 1] = out[1]; rgb4[g * 3 + 2] = out[2];
+#pragma unroll
+        for (int j = 0; j < kOut; ++j) rgb4[g * kOut + j] = out[j];
     }
     if (blockIdx.x == 0) {
         const long long t = ngroups * 4 + threadIdx.x;
         if (t < total) {
-            const int i = image_of_pixel(imgs, 0, n - 1, t);
-            const ImgDesc d = imgs[i];
-            const int q[3] = {src[t * 3 + 0], src[t * 3 + 1], src[t * 3 + 2]};
-            unsigned char o[3];
+            int i, h = oh, w = ow;
+            long long p;
+            if constexpr (TABLE) {
+                i = image_of_pixel(imgs, 0, n - 1, t);
+                const ImgDesc d = imgs[i];
+                p = t - d.first; h = d.h; w = d.w;
+            } else {
+                i = (int)(t / ((long long)oh * ow)); p = t - i * ((long long)oh * ow);
+            }
+            int q[C];
+#pragma unroll
+            for (int c = 0; c < C; ++c) q[c] = (int)src[t * C + c];
+            O o[3];
             const double* pa = lab_q + ((long long)i * 3 + 1) * HW;
-            fullres_pixel(t - d.first, q, tab, pa, pa + HW, H, W, interp, (const float*)nullptr, 0.f, d.h, d.w, o);
+            fullres_pixel<F, O, double>(p, q, tab, pa, pa + HW, H, W, interp, (const float*)nullptr, 0.f, h, w, o);
             rgb[t * 3 + 0] = o[0]; rgb[t * 3 + 1] = o[1]; rgb[t * 3 + 2] = o[2];
         }
     }
 }
 
-hipError_t launch_ragged_fullres_rgb(const unsigned char* src, const ImgDesc* imgs, int n, long long total, const double* lab_q, int H, int W,
-                                     int interp, unsigned char* rgb, hipStream_t s) {
-    if (n <= 0 || total < n || imgs == nullptr || interp < 0 || interp > 2 || (((uintptr_t)src | (uintptr_t)rgb) & 3)) return hipErrorInvalidValue;
-    const long long ngroups = (total + 3) >> 2;
-    const int blocks = grid_blocks(GridTag::ragged_fullres_rgb, (ngroups + 255) / 256, 8192);
-    hipLaunchKernelGGL(ragged_fullres_rgb_kernel, dim3(blocks), dim3(256), 0, s, src, imgs, n, lab_q, H, W, interp, rgb);
-    return hipGetLastError();
+constexpr auto batch_fullres_rgb_kernel = packed_fullres_kernel<false, false, RGB8, unsigned char>,      // uniform run
+               ragged_fullres_rgb_kernel = packed_fullres_kernel<false, true, RGB8, unsigned char>;      // table
+
+hipError_t launch_packed_fullres(int bits, const void* src, const ImgDesc* imgs, int n, int oh, int ow, long long total, const double* lab_q, int H,
+                                 int W, int interp, void* rgb, int out_bits, hipStream_t s) {
+    if (imgs == nullptr) total = (long long)n * oh * ow;
+    if (n <= 0 || total < n || (imgs == nullptr && (bits != 0 || oh <= 0 || ow <= 0)) || interp < 0 || interp > 2 ||
+        (((uintptr_t)src | (uintptr_t)rgb) & 3))
+        return hipErrorInvalidValue;
+    const long long want = (((total + 3) >> 2) + 255) / 256;
+    if (bits == 0 && out_bits != 8) return hipErrorInvalidValue;
+    if (bits == 0 && imgs == nullptr) {
+        const int blocks = grid_blocks(GridTag::batch_fullres_rgb, want, 8192);
+        hipLaunchKernelGGL(batch_fullres_rgb_kernel, dim3(blocks), dim3(256), 0, s, (const unsigned char*)src, imgs, n, total, oh, ow, lab_q, H, W, interp,
+                           (unsigned char*)rgb);
+        return hipGetLastError();
+    }
+    if (bits == 0) {
+        const int blocks = grid_blocks(GridTag::ragged_fullres_rgb, want, 8192);
+        hipLaunchKernelGGL(ragged_fullres_rgb_kernel, dim3(blocks), dim3(256), 0, s, (const unsigned char*)src, imgs, n, total, oh, ow, lab_q, H, W, interp,
+                           (unsigned char*)rgb);
+        return hipGetLastError();
+    }
+    if (!exact_grid_ok(want)) return hipErrorInvalidValue;      // grey: dim3(want) covers every item, hence the EXACT form
+    return source_forms<false>(bits, out_bits, 1, [&](auto f, auto o, auto) {
+        typedef decltype(f) F; typedef decltype(o) O;
+        hipLaunchKernelGGL((packed_fullres_kernel<true, true, F, O>), dim3((unsigned)want), dim3(256), 0, s, (const typename F::sample*)src, imgs, n, total, oh, ow, lab_q,
+                           H, W, interp, (O*)rgb);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -711,11 +848,14 @@ hipError_t launch_ragged_fullres_rgb(const unsigned char* src, const ImgDesc* im
 //             3 x 6 KB.  A tile whose footprint is larger (h < H or w < W: several net-size pixels per output pixel) reads its taps from
 //             global memory.  The choice is uniform over the workgroup and does not change a bit: both branches hand the same float64
 //             operands to the same expressions.
-//   LDS       18.1 KB footprint + 2 KB sRGB table + 2.8 KB weights + 0.8 KB result bytes = 23.7 KB: six workgroups (24 waves) per CU by LDS.
-//   stores    the tile's result bytes cross LDS; a row of the tile is 96 consecutive bytes of the image that start on any residue mod 4 (an
-//             image of the packed run starts at byte 3 * first), so each row goes out as up to 3 head bytes, up to 24 aligned dwords and up
-//             to 3 tail bytes: no dword reaches into a neighbouring tile or image.
-// imgs == nullptr: n images of sh x sw packed back to back (the same-size batch; n = 1: the blocking calls).
+//   LDS       18.1 KB footprint + 2 KB sRGB table (uint8 sources) + 2.8 KB weights + 0.8 KB (uint8 out) or 1.5 KB (uint16 out) result bytes:
+//             23.7 KB for RGB8, six workgroups (24 waves) per CU by LDS.
+//   stores    the tile's result bytes cross LDS; a row of the tile is 96 (uint8) or 192 (uint16) consecutive bytes of the image that start on
+//             any residue mod 4 (an image of the packed run starts at element 3 * first; uint16: an even residue), so each row goes out as up
+//             to 3 head bytes (lanes 0..2), up to 24 / 48 aligned dwords (lanes stride the row) and up to 3 tail bytes (lanes 3..5): no dword
+//             reaches into a neighbouring tile or image.
+// imgs == nullptr: n images of sh x sw packed back to back (the same-size batch; n = 1: the blocking calls); else image i starts at pixel
+// imgs[i].first of the run, in src and in rgb alike (the table of the run itself: off = first pixels' bytes; ImgDesc::off is not read).
 // ------------------------------------------------------------------------------------------------
 constexpr int kJointTW = 32, kJointTH = 8, kJointMaxR = 4, kJointMaxTaps = 2 * kJointMaxR + 1, kInterpJoint = 3;
 constexpr int kJointCells = (kJointTH + 2 * kJointMaxR + 2) * (kJointTW + 2 * kJointMaxR + 2);
@@ -727,483 +867,41 @@ __device__ __forceinline__ int joint_centre(int i, double sc, double& u) {
     return (int)floor(u + 0.5);
 }
 
-template <typename S>
-__global__ __launch_bounds__(256) void joint_fullres_kernel(const unsigned char* __restrict__ src, const ImgDesc* __restrict__ imgs, int sh, int sw,
-                                                            const S* __restrict__ pa, const S* __restrict__ pb, long long plane_stride,
+template <typename F, typename O, typename S>
+__global__ __launch_bounds__(256) void joint_fullres_kernel(const typename F::sample* __restrict__ src, const ImgDesc* __restrict__ imgs, int sh,
+                                                            int sw, const S* __restrict__ pa, const S* __restrict__ pb, long long plane_stride,
                                                             const float* __restrict__ Lp, float l_cent, int H, int W, int interp, JointParams jp,
-                                                            unsigned char* __restrict__ rgb, double* __restrict__ ab_out) {
+                                                            O* __restrict__ rgb, double* __restrict__ ab_out) {
 #pragma clang fp contract(off)
-    __shared__ double tab[256];
-    __shared__ double sL[kJointCells], sA[kJointCells], sB[kJointCells];
-    __shared__ double wys[kJointTH][kJointMaxTaps], wxs[kJointTW][kJointMaxTaps];
-    __shared__ unsigned char outb[kJointTH][kJointTW * 3];
-    const int img = blockIdx.y;
-    ImgDesc d;
-    if (imgs != nullptr) {
-        d = imgs[img];
-    } else {
-        d.h = sh; d.w = sw; d.first = (long long)img * sh * sw; d.off = d.first * 3;
-    }
-    const int tiles_x = (d.w + kJointTW - 1) / kJointTW, tiles_y = (d.h + kJointTH - 1) / kJointTH;
-    if ((long long)blockIdx.x >= (long long)tiles_x * tiles_y) return;        // uniform over the workgroup: this image has fewer tiles than the largest
-    fill_srgb_table(tab);
-    const int ty0 = (int)(blockIdx.x / tiles_x) * kJointTH, tx0 = (int)(blockIdx.x % tiles_x) * kJointTW;
-    const int tx = threadIdx.x & (kJointTW - 1), ty = threadIdx.x / kJointTW;
-    const int y = ty0 + ty, x = tx0 + tx;
-    const bool valid = y < d.h && x < d.w;
-    const long long HW = (long long)H * W;
-    const S* ia = pa != nullptr ? pa + (long long)img * plane_stride : nullptr;
-    const S* ib = pa != nullptr ? pb + (long long)img * plane_stride : nullptr;
-    const bool joint = interp == kInterpJoint && ia != nullptr;
-    const float* iL = joint ? Lp + (long long)img * HW : nullptr;
-    const int R = jp.R, T = 2 * R + 1;
-    const double sy = (double)H / (double)d.h, sx = (double)W / (double)d.w;
-    bool staged = false;
-    int fj0 = 0, fi0 = 0, fc = 0;
-    if (joint) {
-        for (int t = threadIdx.x; t < (kJointTH + kJointTW) * kJointMaxTaps; t += 256) {
-            const int r = t / kJointMaxTaps, k = t - r * kJointMaxTaps;
-            if (k >= T) continue;
-            double u;
-            const int c0 = r < kJointTH ? joint_centre(ty0 + r, sy, u) : joint_centre(tx0 + r - kJointTH, sx, u);
-            const double dd = (double)(c0 - R + k) - u;
-            const double wgt = exp(-(dd * dd) / jp.two_ss);
-            if (r < kJointTH) wys[r][k] = wgt; else wxs[r - kJointTH][k] = wgt;
-        }
-        double u_;
-        const int y_last = ty0 + kJointTH - 1 < d.h ? ty0 + kJointTH - 1 : d.h - 1, x_last = tx0 + kJointTW - 1 < d.w ? tx0 + kJointTW - 1 : d.w - 1;
-        fj0 = joint_centre(ty0, sy, u_) - R; fi0 = joint_centre(tx0, sx, u_) - R;
-        const int fr = joint_centre(y_last, sy, u_) + R - fj0 + 1;
-        fc = joint_centre(x_last, sx, u_) + R - fi0 + 1;
-        staged = (long long)fr * fc <= kJointCells;
-        if (staged) {
-            for (int c = threadIdx.x; c < fr * fc; c += 256) {
-                const int jj = fj0 + c / fc, ii = fi0 + c % fc;
-                if (jj < 0 || jj >= H || ii < 0 || ii >= W) continue;        // a tap outside the image is skipped, so its cell is never read
-                const long long g = (long long)jj * W + ii;
-                sL[c] = (double)iL[g] + (double)l_cent; sA[c] = (double)ia[g]; sB[c] = (double)ib[g];
-            }
-        }
-        __syncthreads();
-    }
-    double L = 0.0, a = 0.0, b = 0.0;
-    if (valid) {
-        const unsigned char* q = src + d.off + ((long long)y * d.w + x) * 3;
-        const double lin[3] = {tab[q[0]], tab[q[1]], tab[q[2]]};
-        double a_, b_;
-        linear_to_lab(lin, L, a_, b_);
-        if (joint) {
-            double u, v;
-            const int j0 = joint_centre(y, sy, u), i0 = joint_centre(x, sx, v);
-            double num_a = 0.0, num_b = 0.0, den = 0.0;
-            for (int kj = 0; kj < T; ++kj) {
-                const int j = j0 - R + kj;
-                if (j < 0 || j >= H) continue;
-                const double wy = wys[ty][kj];
-                for (int ki = 0; ki < T; ++ki) {
-                    const int i = i0 - R + ki;
-                    if (i < 0 || i >= W) continue;
-                    double Lc, ac, bc;
-                    if (staged) {
-                        const int c = (j - fj0) * fc + (i - fi0);
-                        Lc = sL[c]; ac = sA[c]; bc = sB[c];
-                    } else {
-                        const long long g = (long long)j * W + i;
-                        Lc = (double)iL[g] + (double)l_cent; ac = (double)ia[g]; bc = (double)ib[g];
-                    }
-                    const double ws = wy * wxs[tx][ki], dl = L - Lc;
-                    const double wt = ws * (exp(-(dl * dl) / jp.two_sr) + 1e-6);       // IDC_JOINT_EPS
-                    num_a += wt * ac; num_b += wt * bc; den += wt;
-                }
-            }
-            a = num_a / den; b = num_b / den;
-        } else if (ia != nullptr) {
-            double ab[2];
-            interp_ab(ia, ib, H, W, interp, y, x, d.h, d.w, ab);
-            a = ab[0]; b = ab[1];
-        }
-        if (ab_out != nullptr) {
-            const long long np = (long long)d.h * d.w, p = (long long)y * d.w + x;
-            ab_out[d.first * 2 + p] = a; ab_out[d.first * 2 + np + p] = b;
-        }
-    }
-    if (rgb == nullptr) return;
-    unsigned char o[3] = {0, 0, 0};
-    if (valid) lab_to_rgb_u8(L, a, b, o);
-    outb[ty][tx * 3 + 0] = o[0]; outb[ty][tx * 3 + 1] = o[1]; outb[ty][tx * 3 + 2] = o[2];
-    __syncthreads();
-    if (y >= d.h) return;
-    const int tw = d.w - tx0 < kJointTW ? d.w - tx0 : kJointTW, nb = tw * 3;
-    unsigned char* g = rgb + d.off + ((long long)y * d.w + tx0) * 3;
-    const int mis = (int)((4 - ((uintptr_t)g & 3)) & 3), head = mis < nb ? mis : nb;
-    const int ndw = (nb - head) >> 2, tail = nb - head - ndw * 4;
-    const unsigned char* row = outb[ty];
-    if (tx < ndw) {             // at most 24 dwords: lanes 0..23
-        const unsigned char* s4 = row + head + tx * 4;
-        ((unsigned*)(g + head))[tx] = (unsigned)s4[0] | ((unsigned)s4[1] << 8) | ((unsigned)s4[2] << 16) | ((unsigned)s4[3] << 24);
-    } else if (tx >= 24) {      // lanes 24..26 the head bytes, 27..29 the tail bytes
-        const int k = tx - 24;
-        if (k < head) g[k] = row[k];
-        else if (k >= 3 && k - 3 < tail) g[head + ndw * 4 + k - 3] = row[head + ndw * 4 + k - 3];
-    }
-}
-
-hipError_t launch_joint_fullres(const unsigned char* src, const ImgDesc* imgs, int n, int sh, int sw, long long max_tiles, const void* a_plane,
-                                const void* b_plane, int src_f64, long long plane_stride, const float* Lp, float l_cent, int H, int W, int interp,
-                                JointParams jp, unsigned char* rgb, double* ab_out, hipStream_t s) {
-    if (n <= 0 || n > 65535 || src == nullptr || (imgs == nullptr && (sh <= 0 || sw <= 0)) || max_tiles <= 0 || max_tiles > 0x7fffffffll ||
-        interp < 0 || interp > kInterpJoint || (rgb == nullptr && ab_out == nullptr) || (a_plane == nullptr) != (b_plane == nullptr))
-        return hipErrorInvalidValue;
-    if (interp == kInterpJoint && a_plane != nullptr && (Lp == nullptr || jp.R < 1 || jp.R > kJointMaxR || !(jp.two_ss > 0.0) || !(jp.two_sr > 0.0)))
-        return hipErrorInvalidValue;
-    const dim3 grid((unsigned)max_tiles, (unsigned)n);
-    if (src_f64)
-        hipLaunchKernelGGL(joint_fullres_kernel<double>, grid, dim3(256), 0, s, src, imgs, sh, sw, (const double*)a_plane, (const double*)b_plane,
-                           plane_stride, Lp, l_cent, H, W, interp, jp, rgb, ab_out);
-    else
-        hipLaunchKernelGGL(joint_fullres_kernel<float>, grid, dim3(256), 0, s, src, imgs, sh, sw, (const float*)a_plane, (const float*)b_plane,
-                           plane_stride, Lp, l_cent, H, W, interp, jp, rgb, ab_out);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------------
-// greyscale sources (idc_set_image_gray, and idc_fullres_rgb / idc_fullres_ab / idc_fullres_rgb16 on a kept one; the rule: include/ideepcolor.h).
-// One plane [h,w] of uint8 or uint16 samples T whose sRGB value v / 255 or v / 65535 stands on all three channels; the image goes out as uint8 or
-// uint16 O.  The kernels sit beside the RGB ones and hand the SAME device functions the same operands: bilinear_taps and bilinear_u8's
-// expressions on the one channel, linear_to_lab on {t, t, t}, interp_ab / the joint rule, lab_to_srgb.  So a uint8 plane gives the bits of the
-// RGB route fed the plane three times, and a uint16 plane of 257 g gives the bits of the uint8 plane g wherever nothing is resized
-// (fl(257 g / 65535) == fl(g / 255): the correctly rounded quotient of the same real number).  There is no expanded RGB copy of the plane.
-//   sRGB -> linear   uint8: the 256-entry LDS table of the RGB kernels.  uint16: srgb_to_linear per sample -- one float64 pow beside the three
-//                    of lab_to_srgb on the way out and the cbrt of linear_to_lab; a 65 536-entry table in global memory would hold the same bits.
-//   grids            exact: every launcher covers its items in one pass and refuses a count past 2^31 - 1 (a 16384^2 source is 2.6e5 workgroups).
-// ------------------------------------------------------------------------------------------------
-template <typename T> struct GrayFmt;
-template <> struct GrayFmt<unsigned char> { static constexpr double full = 255.0; };
-template <> struct GrayFmt<unsigned short> { static constexpr double full = 65535.0; };
-
-// bilinear_u8 on T's lattice: the same expressions in the same order, contraction off -> floor(out + .5) clamped to 0..full scale
-template <typename T>
-__device__ __forceinline__ int bilinear_gray(double f00, double f01, double f10, double f11, double wx, double wy) {
-#pragma clang fp contract(off)
-    const double top = f00 * (1.0 - wx) + f01 * wx;
-    const double bot = f10 * (1.0 - wx) + f11 * wx;
-    const double out = top * (1.0 - wy) + bot * wy;
-    const double r = floor(out + 0.5);
-    return r < 0.0 ? 0 : (r > GrayFmt<T>::full ? (int)GrayFmt<T>::full : (int)r);
-}
-
-template <typename T>
-__device__ __forceinline__ void fill_gray_table(double* tab) {      // uniform over the kernel: only the uint8 forms have a table (and its barrier)
-    if constexpr (sizeof(T) == 1) fill_srgb_table(tab);
-}
-
-// L of sample q: linear_to_lab on {t, t, t}, t = srgb_to_linear(q / full scale)
-template <typename T>
-__device__ __forceinline__ double gray_L(int q, const double* tab) {
-    double t;
-    if constexpr (sizeof(T) == 1) t = tab[q]; else t = srgb_to_linear((double)q / GrayFmt<T>::full);
-    const double lin[3] = {t, t, t};
-    double L, a_, b_;
-    linear_to_lab(lin, L, a_, b_);
-    return L;
-}
-
-// lab_to_rgb_u8 for either depth: (O)(s * full scale), truncation
-template <typename O>
-__device__ __forceinline__ void lab_to_rgb_q(double L, double a, double b, O* q) {
-    double s[3];
-    lab_to_srgb(L, a, b, s);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) q[c] = (O)(s[c] * GrayFmt<O>::full);
-}
-
-// ingest_rgb_kernel for planes: one thread per net-size pixel of all n images, exact grid.  gray_net [n,H,W] T and l_net [n,H,W] f64 may be nullptr.
-template <typename T>
-__global__ __launch_bounds__(256) void ingest_gray_kernel(const T* const* __restrict__ srcs, long long npix, int src_h, int src_w, int H, int W,
-                                                          float l_cent, float* __restrict__ Lp, T* __restrict__ gray_net,
-                                                          double* __restrict__ l_net) {
-    __shared__ double tab[sizeof(T) == 1 ? 256 : 1];
-    fill_gray_table<T>(tab);
-    const long long HW = (long long)H * W, p = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (p >= npix) return;
-    const long long i = p / HW, r = p - i * HW;
-    const int y = (int)(r / W), x = (int)(r - (long long)y * W);
-    int y0, y1, x0, x1;
-    double wy, wx;
-    bilinear_taps(y, src_h, H, y0, y1, wy);
-    bilinear_taps(x, src_w, W, x0, x1, wx);
-    const T* src = srcs[i];
-    const int q = bilinear_gray<T>((double)src[(long long)y0 * src_w + x0], (double)src[(long long)y0 * src_w + x1],
-                                   (double)src[(long long)y1 * src_w + x0], (double)src[(long long)y1 * src_w + x1], wx, wy);
-    const double L = gray_L<T>(q, tab);
-    Lp[p] = (float)(L - (double)l_cent);
-    if (gray_net != nullptr) gray_net[p] = (T)q;
-    if (l_net != nullptr) l_net[p] = L;
-}
-
-hipError_t launch_ingest_gray(const void* const* srcs, int bits, int n, int src_h, int src_w, int H, int W, float l_cent, float* Lp, void* gray_net,
-                              double* l_net, hipStream_t s) {
-    const long long npix = (long long)n * H * W, wgs = (npix + 255) / 256;
-    if (npix <= 0 || wgs > 0x7fffffffll || src_h <= 0 || src_w <= 0 || (bits != 8 && bits != 16)) return hipErrorInvalidValue;
-    if (bits == 8)
-        hipLaunchKernelGGL(ingest_gray_kernel<unsigned char>, dim3((unsigned)wgs), dim3(256), 0, s, (const unsigned char* const*)srcs, npix, src_h, src_w,
-                           H, W, l_cent, Lp, (unsigned char*)gray_net, l_net);
-    else
-        hipLaunchKernelGGL(ingest_gray_kernel<unsigned short>, dim3((unsigned)wgs), dim3(256), 0, s, (const unsigned short* const*)srcs, npix, src_h,
-                           src_w, H, W, l_cent, Lp, (unsigned short*)gray_net, l_net);
-    return hipGetLastError();
-}
-
-// fullres_pixel from a sample: L = gray_L(q) (mask == nullptr) or the mask rule, (a, b) interpolated from pa / pb (nullptr: 0), then Lab -> RGB at O's depth
-template <typename T, typename O, typename S>
-__device__ __forceinline__ void gray_fullres_pixel(long long p, int q, const double* tab, const S* __restrict__ pa, const S* __restrict__ pb, int H,
-                                                   int W, int interp, const float* __restrict__ mask, float mask_value, int oh, int ow, O* out) {
-    const int dy = (int)(p / ow), dx = (int)(p - (long long)dy * ow);
-    double L, ab[2] = {0.0, 0.0};
-    if (mask == nullptr) {
-        L = gray_L<T>(q, tab);
-    } else if (mask_value != 0.f) {
-        int yy, xx;
-        zoom_nearest(dy, dx, H, W, oh, ow, yy, xx);
-        L = 50.0 * ((double)mask[(size_t)yy * W + xx] / (double)mask_value);
-    } else {
-        L = 0.0;
-    }
-    if (pa != nullptr) interp_ab(pa, pb, H, W, interp, dy, dx, oh, ow, ab);
-    lab_to_rgb_q<O>(L, ab[0], ab[1], out);
-}
-
-// fullres_rgb_kernel for a plane, exact grid.  A thread takes 4 consecutive pixels of the flattened image: one aligned dword in (uint8) or two
-// (uint16), three (uint8 out) or six (uint16 out) aligned dwords out; src and rgb are 4-byte aligned (device allocations).  The npix % 4
-// pixels at the end go one per thread of workgroup 0 through narrow accesses.
-template <typename T, typename O, typename S>
-__global__ __launch_bounds__(256) void gray_fullres_kernel(const T* __restrict__ src, int oh, int ow, const S* __restrict__ pa,
-                                                           const S* __restrict__ pb, int H, int W, int interp, const float* __restrict__ mask,
-                                                           float mask_value, O* __restrict__ rgb) {
-    constexpr int kIn = (int)sizeof(T), kOut = 3 * (int)sizeof(O);      // dwords per group of 4 pixels
-    __shared__ double tab[sizeof(T) == 1 ? 256 : 1];
-    fill_gray_table<T>(tab);
-    const long long npix = (long long)oh * ow, ngroups = npix >> 2, g = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (g < ngroups) {
-        const unsigned* src4 = (const unsigned*)src;
-        unsigned* rgb4 = (unsigned*)rgb;
-        unsigned in[kIn], out[kOut];
-#pragma unroll
-        for (int j = 0; j < kIn; ++j) in[j] = src4[g * kIn + j];
-#pragma unroll
-        for (int j = 0; j < kOut; ++j) out[j] = 0u;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            int q;
-            if constexpr (sizeof(T) == 1) q = (int)((in[0] >> (8 * k)) & 255u); else q = (int)((in[k >> 1] >> (16 * (k & 1))) & 65535u);
-            O o[3];
-            gray_fullres_pixel<T, O, S>(g * 4 + k, q, tab, pa, pb, H, W, interp, mask, mask_value, oh, ow, o);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int e = k * 3 + c;
-                if constexpr (sizeof(O) == 1) out[e >> 2] |= (unsigned)o[c] << (8 * (e & 3)); else out[e >> 1] |= (unsigned)o[c] << (16 * (e & 1));
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < kOut; ++j) rgb4[g * kOut + j] = out[j];
-    }
-    if (blockIdx.x == 0) {
-        const long long p = ngroups * 4 + threadIdx.x;
-        if (p < npix) {
-            O o[3];
-            gray_fullres_pixel<T, O, S>(p, (int)src[p], tab, pa, pb, H, W, interp, mask, mask_value, oh, ow, o);
-            rgb[p * 3 + 0] = o[0]; rgb[p * 3 + 1] = o[1]; rgb[p * 3 + 2] = o[2];
-        }
-    }
-}
-
-// the three (sample, output) forms times the two plane types: f(T(), O(), S()) launches its kernel<T, O, S>
-template <typename F>
-static hipError_t gray_forms(int bits, int out_bits, int src_f64, F&& f) {
-    typedef unsigned char u8;
-    typedef unsigned short u16;
-    if (bits == 8 && out_bits == 8) { if (src_f64) f(u8(), u8(), double()); else f(u8(), u8(), float()); }
-    else if (bits == 16 && out_bits == 8) { if (src_f64) f(u16(), u8(), double()); else f(u16(), u8(), float()); }
-    else if (bits == 16 && out_bits == 16) { if (src_f64) f(u16(), u16(), double()); else f(u16(), u16(), float()); }
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-
-hipError_t launch_gray_fullres(const void* src, int bits, int oh, int ow, const void* a_plane, const void* b_plane, int src_f64, int H, int W,
-                               int interp, const float* mask, float mask_value, void* rgb, int out_bits, hipStream_t s) {
-    const long long npix = (long long)oh * ow, wgs = (((npix + 3) >> 2) + 255) / 256;
-    if (npix <= 0 || wgs > 0x7fffffffll || interp < 0 || interp > 2 || (((uintptr_t)src | (uintptr_t)rgb) & 3)) return hipErrorInvalidValue;
-    return gray_forms(bits, out_bits, src_f64, [&](auto t, auto o, auto p) {
-        typedef decltype(t) T; typedef decltype(o) O; typedef decltype(p) S;
-        hipLaunchKernelGGL((gray_fullres_kernel<T, O, S>), dim3((unsigned)wgs), dim3(256), 0, s, (const T*)src, oh, ow, (const S*)a_plane,
-                           (const S*)b_plane, H, W, interp, mask, mask_value, (O*)rgb);
-    });
-}
-
-// ragged_prologue_kernel for planes (idc_forward_async_gray): image i of the packed run starts at sample imgs[i].first, exact grid.  L is
-// ingest_gray_kernel's pixel; the hints are prologue_pixel's walk (the last covering hint of the image's clipped list wins; an RGB hint goes
-// through the 256-entry table, which every form fills: a hint's colour is uint8 whatever the samples are).
-template <typename T>
-__global__ __launch_bounds__(256) void ragged_gray_prologue_kernel(const T* __restrict__ src, const ImgDesc* __restrict__ imgs, long long npix, int H,
-                                                                   int W, float l_cent, const int* __restrict__ offs,
-                                                                   const HintRect* __restrict__ hints, int mode, float mask_value,
-                                                                   float* __restrict__ Lp, float* __restrict__ ab, float* __restrict__ mask) {
-    __shared__ double tab[256];
-    fill_srgb_table(tab);
-    const long long HW = (long long)H * W, p = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (p >= npix) return;
-    const long long i = p / HW, r = p - i * HW;
-    const int y = (int)(r / W), x = (int)(r - (long long)y * W);
-    const ImgDesc d = imgs[i];
-    const T* img = src + d.first;
-    int y0, y1, x0, x1;
-    double wy, wx;
-    bilinear_taps(y, d.h, H, y0, y1, wy);
-    bilinear_taps(x, d.w, W, x0, x1, wx);
-    const int q = bilinear_gray<T>((double)img[(long long)y0 * d.w + x0], (double)img[(long long)y0 * d.w + x1],
-                                   (double)img[(long long)y1 * d.w + x0], (double)img[(long long)y1 * d.w + x1], wx, wy);
-    Lp[p] = (float)(gray_L<T>(q, tab) - (double)l_cent);
-    const int lo = offs != nullptr ? offs[i] : 0, hi = offs != nullptr ? offs[i + 1] : 0;
-    int hit = -1;
-    for (int k = hi - 1; k >= lo; --k) {
-        const HintRect h = hints[k];
-        if (y >= h.y0 && y <= h.y1 && x >= h.x0 && x <= h.x1) { hit = k; break; }
-    }
-    float a = 0.f, b = 0.f, m = 0.f;
-    if (hit >= 0) {
-        const HintRect h = hints[hit];
-        m = mask_value;
-        if (mode == 0) {
-            a = h.c0; b = h.c1;
-        } else {
-            const double hl[3] = {tab[(unsigned char)h.c0], tab[(unsigned char)h.c1], tab[(unsigned char)h.c2]};
-            double hL, da, db;
-            linear_to_lab(hl, hL, da, db);
-            a = (float)da; b = (float)db;
-        }
-    }
-    ab[(i * 2 + 0) * HW + r] = a;
-    ab[(i * 2 + 1) * HW + r] = b;
-    mask[p] = m;
-}
-
-hipError_t launch_ragged_gray_prologue(const void* src, int bits, const ImgDesc* imgs, int n, int H, int W, float l_cent, const int* offs,
-                                       const HintRect* hints, int mode, float mask_value, float* Lp, float* ab, float* mask, hipStream_t s) {
-    const long long npix = (long long)n * H * W, wgs = (npix + 255) / 256;
-    if (npix <= 0 || wgs > 0x7fffffffll || imgs == nullptr || (mode != 0 && mode != 1) || (bits != 8 && bits != 16)) return hipErrorInvalidValue;
-    if (bits == 8)
-        hipLaunchKernelGGL(ragged_gray_prologue_kernel<unsigned char>, dim3((unsigned)wgs), dim3(256), 0, s, (const unsigned char*)src, imgs, npix, H, W,
-                           l_cent, offs, hints, mode, mask_value, Lp, ab, mask);
-    else
-        hipLaunchKernelGGL(ragged_gray_prologue_kernel<unsigned short>, dim3((unsigned)wgs), dim3(256), 0, s, (const unsigned short*)src, imgs, npix, H,
-                           W, l_cent, offs, hints, mode, mask_value, Lp, ab, mask);
-    return hipGetLastError();
-}
-
-// ragged_fullres_rgb_kernel for planes packed back to back, exact grid: the `total` = imgs[n].first samples are ONE flat run from the 4-byte
-// aligned base.  A thread takes 4 consecutive pixels: one aligned dword in (uint8) or two (uint16), three or six aligned dwords out, whatever
-// residue mod 4 an image's start has; the bracketing searches and the carry into the next image are ragged_fullres_rgb_kernel's.  Only the
-// total % 4 pixels at the end of the run use narrow accesses.
-template <typename T, typename O>
-__global__ __launch_bounds__(256) void ragged_gray_fullres_kernel(const T* __restrict__ src, const ImgDesc* __restrict__ imgs, int n,
-                                                                  const double* __restrict__ lab_q, int H, int W, int interp, O* __restrict__ rgb) {
-    constexpr int kIn = (int)sizeof(T), kOut = 3 * (int)sizeof(O);
-    __shared__ double tab[sizeof(T) == 1 ? 256 : 1];
-    fill_gray_table<T>(tab);
-    const long long HW = (long long)H * W, total = imgs[n].first, ngroups = total >> 2;
-    const long long g0 = (long long)blockIdx.x * 256, g = g0 + threadIdx.x;
-    if (g0 < ngroups) {
-        const long long last = g0 + 256 < ngroups ? g0 + 256 : ngroups;
-        const int i_lo = image_of_pixel(imgs, 0, n - 1, g0 * 4), i_hi = image_of_pixel(imgs, i_lo, n - 1, last * 4 - 1);
-        if (g < ngroups) {
-            const unsigned* src4 = (const unsigned*)src;
-            unsigned* rgb4 = (unsigned*)rgb;
-            unsigned in[kIn], out[kOut];
-#pragma unroll
-            for (int j = 0; j < kIn; ++j) in[j] = src4[g * kIn + j];
-#pragma unroll
-            for (int j = 0; j < kOut; ++j) out[j] = 0u;
-            int i = image_of_pixel(imgs, i_lo, i_hi, g * 4);
-            ImgDesc d = imgs[i];
-            long long p = g * 4 - d.first, npix = (long long)d.h * d.w;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                int q;
-                if constexpr (sizeof(T) == 1) q = (int)((in[0] >> (8 * k)) & 255u); else q = (int)((in[k >> 1] >> (16 * (k & 1))) & 65535u);
-                O o[3];
-                const double* pa = lab_q + ((long long)i * 3 + 1) * HW;
-                gray_fullres_pixel<T, O, double>(p, q, tab, pa, pa + HW, H, W, interp, (const float*)nullptr, 0.f, d.h, d.w, o);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const int e = k * 3 + c;
-                    if constexpr (sizeof(O) == 1) out[e >> 2] |= (unsigned)o[c] << (8 * (e & 3)); else out[e >> 1] |= (unsigned)o[c] << (16 * (e & 1));
-                }
-                if (++p == npix && k < 3) { p = 0; d = imgs[++i]; npix = (long long)d.h * d.w; }      // i + 1 <= n - 1: the group's next pixel is in the run
-            }
-#pragma unroll
-            for (int j = 0; j < kOut; ++j) rgb4[g * kOut + j] = out[j];
-        }
-    }
-    if (blockIdx.x == 0) {
-        const long long t = ngroups * 4 + threadIdx.x;
-        if (t < total) {
-            const int i = image_of_pixel(imgs, 0, n - 1, t);
-            const ImgDesc d = imgs[i];
-            O o[3];
-            const double* pa = lab_q + ((long long)i * 3 + 1) * HW;
-            gray_fullres_pixel<T, O, double>(t - d.first, (int)src[t], tab, pa, pa + HW, H, W, interp, (const float*)nullptr, 0.f, d.h, d.w, o);
-            rgb[t * 3 + 0] = o[0]; rgb[t * 3 + 1] = o[1]; rgb[t * 3 + 2] = o[2];
-        }
-    }
-}
-
-hipError_t launch_ragged_gray_fullres(const void* src, int bits, const ImgDesc* imgs, int n, long long total, const double* lab_q, int H, int W,
-                                      int interp, void* rgb, int out_bits, hipStream_t s) {
-    const long long wgs = (((total + 3) >> 2) + 255) / 256;
-    if (n <= 0 || total < n || wgs > 0x7fffffffll || imgs == nullptr || interp < 0 || interp > 2 || (((uintptr_t)src | (uintptr_t)rgb) & 3))
-        return hipErrorInvalidValue;
-    return gray_forms(bits, out_bits, 1, [&](auto t, auto o, auto) {
-        typedef decltype(t) T; typedef decltype(o) O;
-        hipLaunchKernelGGL((ragged_gray_fullres_kernel<T, O>), dim3((unsigned)wgs), dim3(256), 0, s, (const T*)src, imgs, n, lab_q, H, W, interp, (O*)rgb);
-    });
-}
-
-// joint_fullres_kernel for planes (blockIdx.y = image; imgs == nullptr: one plane [sh,sw], the blocking calls; else image i of the packed run
-// starts at sample imgs[i].first): the same tile, weights, staging and tap loop; the source read is one sample and the row store knows O.  A row of the tile is 96 (uint8) or 192 (uint16) consecutive bytes of the image that start on any residue mod 4 (uint16:
-// an even one), so it goes out as up to 3 head bytes, up to 24 / 48 aligned dwords (lanes stride the row) and up to 3 tail bytes.
-template <typename T, typename O, typename S>
-__global__ __launch_bounds__(256) void gray_joint_fullres_kernel(const T* __restrict__ src, const ImgDesc* __restrict__ imgs, int sh, int sw,
-                                                                 const S* __restrict__ pa, const S* __restrict__ pb, long long plane_stride,
-                                                                 const float* __restrict__ Lp, float l_cent, int H, int W, int interp,
-                                                                 JointParams jp, O* __restrict__ rgb, double* __restrict__ ab_out) {
-#pragma clang fp contract(off)
-    __shared__ double tab[sizeof(T) == 1 ? 256 : 1];
+    constexpr int C = F::channels;
+    __shared__ double tab[F::table ? 256 : 1];
     __shared__ double sL[kJointCells], sA[kJointCells], sB[kJointCells];
     __shared__ double wys[kJointTH][kJointMaxTaps], wxs[kJointTW][kJointMaxTaps];
     __shared__ __attribute__((aligned(4))) unsigned char outb[kJointTH][kJointTW * 3 * sizeof(O)];
     const int img = blockIdx.y;
-    long long first = 0;
+    long long first;
     if (imgs != nullptr) { const ImgDesc d = imgs[img]; sh = d.h; sw = d.w; first = d.first; }
+    else first = (long long)img * sh * sw;
     const int tiles_x = (sw + kJointTW - 1) / kJointTW, tiles_y = (sh + kJointTH - 1) / kJointTH;
     if ((long long)blockIdx.x >= (long long)tiles_x * tiles_y) return;        // uniform over the workgroup: this image has fewer tiles than the largest
-    src += first;
+    src += first * C;
     const S* ia = pa != nullptr ? pa + (long long)img * plane_stride : nullptr;
     const S* ib = pa != nullptr ? pb + (long long)img * plane_stride : nullptr;
     if (Lp != nullptr) Lp += (long long)img * H * W;
-    fill_gray_table<T>(tab);
+    fill_source_table<F>(tab);
     const int ty0 = (int)(blockIdx.x / tiles_x) * kJointTH, tx0 = (int)(blockIdx.x % tiles_x) * kJointTW;
     const int tx = threadIdx.x & (kJointTW - 1), ty = threadIdx.x / kJointTW;
     const int y = ty0 + ty, x = tx0 + tx;
     const bool valid = y < sh && x < sw;
     const bool joint = interp == kInterpJoint && ia != nullptr;
-    const int R = jp.R, T_ = 2 * R + 1;
+    const int R = jp.R, NT = 2 * R + 1;
     const double sy = (double)H / (double)sh, sx = (double)W / (double)sw;
     bool staged = false;
     int fj0 = 0, fi0 = 0, fc = 0;
     if (joint) {
         for (int t = threadIdx.x; t < (kJointTH + kJointTW) * kJointMaxTaps; t += 256) {
             const int r = t / kJointMaxTaps, k = t - r * kJointMaxTaps;
-            if (k >= T_) continue;
+            if (k >= NT) continue;
             double u;
             const int c0 = r < kJointTH ? joint_centre(ty0 + r, sy, u) : joint_centre(tx0 + r - kJointTH, sx, u);
             const double dd = (double)(c0 - R + k) - u;
@@ -1228,16 +926,20 @@ __global__ __launch_bounds__(256) void gray_joint_fullres_kernel(const T* __rest
     }
     double L = 0.0, a = 0.0, b = 0.0;
     if (valid) {
-        L = gray_L<T>((int)src[(long long)y * sw + x], tab);
+        int q[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) q[c] = (int)src[((long long)y * sw + x) * C + c];
+        double a_, b_;
+        source_lab<F>(q, tab, L, a_, b_);
         if (joint) {
             double u, v;
             const int j0 = joint_centre(y, sy, u), i0 = joint_centre(x, sx, v);
             double num_a = 0.0, num_b = 0.0, den = 0.0;
-            for (int kj = 0; kj < T_; ++kj) {
+            for (int kj = 0; kj < NT; ++kj) {
                 const int j = j0 - R + kj;
                 if (j < 0 || j >= H) continue;
                 const double wy = wys[ty][kj];
-                for (int ki = 0; ki < T_; ++ki) {
+                for (int ki = 0; ki < NT; ++ki) {
                     const int i = i0 - R + ki;
                     if (i < 0 || i >= W) continue;
                     double Lc, ac, bc;
@@ -1284,19 +986,19 @@ __global__ __launch_bounds__(256) void gray_joint_fullres_kernel(const T* __rest
     else if (tx >= 3 && tx - 3 < tail) g[head + ndw * 4 + tx - 3] = row[head + ndw * 4 + tx - 3];
 }
 
-hipError_t launch_gray_joint_fullres(const void* src, int bits, const ImgDesc* imgs, int n, int sh, int sw, long long max_tiles, const void* a_plane,
-                                     const void* b_plane, int src_f64, long long plane_stride, const float* Lp, float l_cent, int H, int W,
-                                     int interp, JointParams jp, void* rgb, int out_bits, double* ab_out, hipStream_t s) {
-    const long long tiles = max_tiles;
-    if (n <= 0 || n > 65535 || src == nullptr || (imgs == nullptr && (n != 1 || sh <= 0 || sw <= 0)) || tiles <= 0 || tiles > 0x7fffffffll || interp < 0 || interp > kInterpJoint || (rgb == nullptr && ab_out == nullptr) ||
+hipError_t launch_joint_fullres(int bits, const void* src, const ImgDesc* imgs, int n, int sh, int sw, long long max_tiles, const void* a_plane,
+                                const void* b_plane, int src_f64, long long plane_stride, const float* Lp, float l_cent, int H, int W, int interp,
+                                JointParams jp, void* rgb, int out_bits, double* ab_out, hipStream_t s) {
+    if (n <= 0 || n > 65535 || src == nullptr || (imgs == nullptr && ((bits != 0 && n != 1) || sh <= 0 || sw <= 0)) || max_tiles <= 0 ||
+        max_tiles > 0x7fffffffll || interp < 0 || interp > kInterpJoint || (rgb == nullptr && ab_out == nullptr) ||
         (a_plane == nullptr) != (b_plane == nullptr) || (out_bits == 16 && ((uintptr_t)rgb & 1)))
         return hipErrorInvalidValue;
     if (interp == kInterpJoint && a_plane != nullptr && (Lp == nullptr || jp.R < 1 || jp.R > kJointMaxR || !(jp.two_ss > 0.0) || !(jp.two_sr > 0.0)))
         return hipErrorInvalidValue;
-    return gray_forms(bits, out_bits, src_f64, [&](auto t, auto o, auto p) {
-        typedef decltype(t) T; typedef decltype(o) O; typedef decltype(p) S;
-        hipLaunchKernelGGL((gray_joint_fullres_kernel<T, O, S>), dim3((unsigned)tiles, (unsigned)n), dim3(256), 0, s, (const T*)src, imgs, sh, sw,
-                           (const S*)a_plane, (const S*)b_plane, plane_stride, Lp, l_cent, H, W, interp, jp, (O*)rgb, ab_out);
+    return source_forms<true>(bits, out_bits, src_f64, [&](auto f, auto o, auto p) {
+        typedef decltype(f) F; typedef decltype(o) O; typedef decltype(p) S;
+        hipLaunchKernelGGL((joint_fullres_kernel<F, O, S>), dim3((unsigned)max_tiles, (unsigned)n), dim3(256), 0, s, (const typename F::sample*)src, imgs,
+                           sh, sw, (const S*)a_plane, (const S*)b_plane, plane_stride, Lp, l_cent, H, W, interp, jp, (O*)rgb, ab_out);
     });
 }
 
@@ -1307,8 +1009,8 @@ hipError_t launch_gray_joint_fullres(const void* src, int bits, const ImgDesc* i
 // ground truth of a net-size score.  eval_sse: the exact integer sum of squared uint8 differences per image and channel.
 // ------------------------------------------------------------------------------------------------
 // One workgroup of 256 threads (four wave64s) per kept, clipped rectangle k of hints[0 .. gridDim.x).  Its image: the single [sh,sw,3] source at
-// src (imgs == nullptr), or image i of the packed run, offs[i] <= k < offs[i+1].  Every net-size pixel of the rectangle is ingest_rgb_kernel's /
-// prologue_pixel's pixel (the same device functions on the same operands), and a and b are summed in float64 in a FIXED order: a thread walks
+// src (imgs == nullptr), or image i of the packed run, offs[i] <= k < offs[i+1].  Every net-size pixel of the rectangle is ingest_kernel's /
+// prologue_kernel's pixel (net_sample and source_lab on the same operands), and a and b are summed in float64 in a FIXED order: a thread walks
 // its pixels t, t + 256, ... of the rectangle's row-major index upwards, the 64 lanes of a wave fold by halves (32, 16, ... 1), and thread 0
 // adds the four wave sums in wave order.  No float atomic: the mean is a function of the image's bytes, (H, W) and the four corners only, not
 // of n, the rectangle's place in the list, the slot or the route.  The sum is divided by the pixel count in float64 and rounded once to fp32.
@@ -1337,17 +1039,10 @@ __global__ __launch_bounds__(256) void reveal_hints_kernel(const unsigned char* 
     double sa = 0.0, sb = 0.0;
     for (int t = threadIdx.x; t < cnt; t += 256) {
         const int ry = t / rw, y = r.y0 + ry, x = r.x0 + (t - ry * rw);
-        int y0, y1, x0, x1;
-        double wy, wx;
-        bilinear_taps(y, sh, H, y0, y1, wy);
-        bilinear_taps(x, sw, W, x0, x1, wx);
-        const unsigned char* p00 = img + ((long long)y0 * sw + x0) * 3; const unsigned char* p01 = img + ((long long)y0 * sw + x1) * 3;
-        const unsigned char* p10 = img + ((long long)y1 * sw + x0) * 3; const unsigned char* p11 = img + ((long long)y1 * sw + x1) * 3;
-        double lin[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) lin[c] = tab[bilinear_u8((double)p00[c], (double)p01[c], (double)p10[c], (double)p11[c], wx, wy)];
+        int q[3];
+        net_sample<RGB8>(img, sh, sw, H, W, y, x, q);
         double L, a, b;
-        linear_to_lab(lin, L, a, b);
+        source_lab<RGB8>(q, tab, L, a, b);
         sa += a; sb += b;
     }
 #pragma unroll
@@ -1396,17 +1091,10 @@ __global__ __launch_bounds__(256) void dist_truth_kernel(const unsigned char* __
 #pragma unroll
     for (int t = 0; t < S * S; ++t) {
         const int y = cy * S + t / S, x = cx * S + t % S;
-        int y0, y1, x0, x1;
-        double wy, wx;
-        bilinear_taps(y, sh, H, y0, y1, wy);
-        bilinear_taps(x, sw, W, x0, x1, wx);
-        const unsigned char* p00 = img + ((long long)y0 * sw + x0) * 3; const unsigned char* p01 = img + ((long long)y0 * sw + x1) * 3;
-        const unsigned char* p10 = img + ((long long)y1 * sw + x0) * 3; const unsigned char* p11 = img + ((long long)y1 * sw + x1) * 3;
-        double lin[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) lin[k] = tab[bilinear_u8((double)p00[k], (double)p01[k], (double)p10[k], (double)p11[k], wx, wy)];
+        int q[3];
+        net_sample<RGB8>(img, sh, sw, H, W, y, x, q);
         double L, a, b;
-        linear_to_lab(lin, L, a, b);
+        source_lab<RGB8>(q, tab, L, a, b);
         va[t] = 0.0 + a; vb[t] = 0.0 + b;
     }
 #pragma unroll
@@ -1429,7 +1117,7 @@ hipError_t launch_dist_truth(const unsigned char* src, const ImgDesc* imgs, int 
     return hipGetLastError();
 }
 
-// The uint8 half of ragged_prologue_kernel's pixel: rgb_net [n,H,W,3] = cv2.resize of every image to the net size, one thread per pixel.
+// The uint8 half of prologue_kernel's pixel (net_sample): rgb_net [n,H,W,3] = cv2.resize of every image to the net size, one thread per pixel.
 __global__ __launch_bounds__(256) void ragged_net_truth_kernel(const unsigned char* __restrict__ src, const ImgDesc* __restrict__ imgs, int n, int H,
                                                                int W, unsigned char* __restrict__ rgb_net) {
     const long long HW = (long long)H * W, npix = (long long)n * HW;
@@ -1437,16 +1125,10 @@ __global__ __launch_bounds__(256) void ragged_net_truth_kernel(const unsigned ch
         const long long i = p / HW, r = p - i * HW;
         const int y = (int)(r / W), x = (int)(r - (long long)y * W);
         const ImgDesc d = imgs[i];
-        const unsigned char* img = src + d.off;
-        int y0, y1, x0, x1;
-        double wy, wx;
-        bilinear_taps(y, d.h, H, y0, y1, wy);
-        bilinear_taps(x, d.w, W, x0, x1, wx);
-        const unsigned char* p00 = img + ((long long)y0 * d.w + x0) * 3; const unsigned char* p01 = img + ((long long)y0 * d.w + x1) * 3;
-        const unsigned char* p10 = img + ((long long)y1 * d.w + x0) * 3; const unsigned char* p11 = img + ((long long)y1 * d.w + x1) * 3;
+        int q[3];
+        net_sample<RGB8>(src + d.off, d.h, d.w, H, W, y, x, q);
 #pragma unroll
-        for (int c = 0; c < 3; ++c)
-            rgb_net[p * 3 + c] = (unsigned char)bilinear_u8((double)p00[c], (double)p01[c], (double)p10[c], (double)p11[c], wx, wy);
+        for (int c = 0; c < 3; ++c) rgb_net[p * 3 + c] = (unsigned char)q[c];
     }
 }
 
@@ -1524,7 +1206,7 @@ hipError_t launch_eval_sse(const unsigned char* res, const unsigned char* truth,
 // glob_branch_kernel reads -- so that a reference goes from its uint8 bytes to the net's global input without visiting the host.
 // ------------------------------------------------------------------------------------------------
 // A workgroup of a reference takes 16 of its 4x4 blocks per step, one lane per net-size pixel (16 consecutive lanes = one block, dy outer, dx
-// inner): ingest_rgb_kernel's pixel from the reference's own h x w, then Lab and saturation as global_stats_kernel computes them.  The 16 values
+// inner): ingest_kernel's pixel from the reference's own h x w, then Lab and saturation as global_stats_kernel computes them.  The 16 values
 // of a block cross LDS and are added in global_stats_kernel's order, so a net-size reference gives that kernel's bits; the search for the nearest
 // centre is shared by the block's 16 lanes.  Counts go to an LDS histogram (integer atomics) that is flushed once; the saturation sums stay in
 // each block's first lane across steps and are added in lane order at the end, one plain store per workgroup: no float atomic anywhere, nothing
@@ -1560,21 +1242,10 @@ __global__ __launch_bounds__(256) void ref_stats_kernel(const RefDesc* __restric
         double a = 0.0, b = 0.0, sat = 0.0;
         if (live) {
             const int by = blk / w4, bx = blk - by * w4;
-            int y0, y1, x0, x1;
-            double wy, wx;
-            bilinear_taps(by * 4 + dy, rd.h, H, y0, y1, wy);
-            bilinear_taps(bx * 4 + dx, rd.w, W, x0, x1, wx);
-            const unsigned char* p00 = img + ((long long)y0 * rd.w + x0) * 3; const unsigned char* p01 = img + ((long long)y0 * rd.w + x1) * 3;
-            const unsigned char* p10 = img + ((long long)y1 * rd.w + x0) * 3; const unsigned char* p11 = img + ((long long)y1 * rd.w + x1) * 3;
             int q[3];
-            double lin[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                q[c] = bilinear_u8((double)p00[c], (double)p01[c], (double)p10[c], (double)p11[c], wx, wy);
-                lin[c] = tab[q[c]];
-            }
+            net_sample<RGB8>(img, rd.h, rd.w, H, W, by * 4 + dy, bx * 4 + dx, q);
             double L;
-            linear_to_lab(lin, L, a, b);
+            source_lab<RGB8>(q, tab, L, a, b);
             const double rr = q[0] / 255.0, gg = q[1] / 255.0, bl = q[2] / 255.0;
             const double mx = fmax(rr, fmax(gg, bl)), mn = fmin(rr, fmin(gg, bl));
             sat = mx > 0.0 ? (mx - mn) / mx : 0.0;                             // skimage rgb2hsv saturation

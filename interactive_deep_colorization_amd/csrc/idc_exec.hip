@@ -800,15 +800,9 @@ static int batch_colourise(idc_context* h, const BatchCall& c, const BatchPlan& 
         HIPCHK(h, launch_reveal_hints(sl.d_src.get(), m.view, m.offs, n, 0, 0, h->H, h->W, m.hints, p.kept, m.orig, d_cols, s));
         mode = IDC_HINT_AB;
     }
-    if (c.gray_bits)
-        HIPCHK(h, launch_ragged_gray_prologue(sl.d_src.get(), c.gray_bits, m.view, n, h->H, h->W, c.l_cent, m.offs, m.hints, mode, c.mask_value, sl.d_L.get(),
-                                              sl.d_ab.get(), sl.d_mask.get(), s));
-    else if (c.ragged)
-        HIPCHK(h, launch_ragged_prologue(sl.d_src.get(), m.view, n, h->H, h->W, c.l_cent, m.offs, m.hints, mode, c.mask_value, sl.d_L.get(), sl.d_ab.get(),
-                                         sl.d_mask.get(), s));
-    else
-        HIPCHK(h, launch_batch_prologue(sl.d_src.get() + p.aa_at, n, p.naa ? h->H : c.src_h, p.naa ? h->W : c.src_w, h->H, h->W, c.l_cent, m.offs, m.hints, mode, c.mask_value, sl.d_L.get(),
-                                        sl.d_ab.get(), sl.d_mask.get(), s));
+    // a call with a table (every grey call has one) reads its images through the view; a same-size call is a uniform run, of the net-size images where it was antialiased
+    HIPCHK(h, launch_prologue(c.gray_bits, sl.d_src.get() + (c.ragged ? 0 : p.aa_at), c.ragged ? m.view : nullptr, n, p.naa ? h->H : c.src_h,
+                              p.naa ? h->W : c.src_w, h->H, h->W, c.l_cent, m.offs, m.hints, mode, c.mask_value, sl.d_L.get(), sl.d_ab.get(), sl.d_mask.get(), s));
     if (c.has_layers) {   // the layers under the rectangles the prologue has just written; a call whose images all came without one reports zeros
         HIPCHK(h, hipMemsetAsync(sl.d_cells.get(), 0, (size_t)n * sizeof(int32_t), s));
         if (p.n_layers > 0)
@@ -823,23 +817,14 @@ static int batch_colourise(idc_context* h, const BatchCall& c, const BatchPlan& 
     if (!p.dist && !((h->flags & IDC_FLAG_DIST313) && h->keep_dist313)) h->dist_n = dist_n;      // no distribution was written: the blocking forward's stays resident
     HIPCHK(h, launch_lab_post(sl.d_L.get(), c.l_cent, sl.d_out.get(), sl.d_rgb.get(), p.source_out ? sl.d_labq.get() : nullptr, n, h->H, h->W, s));
     sl.up_interp = h->batch_interp; sl.up_joint = h->joint;       // the handle's setting as it is now: a later idc_set_batch_upsample does not reach this batch
-    if (p.source_out && c.gray_bits) {        // the grey forms of the two kernels below, on the plan's bytes per pixel
+    const ImgDesc* tab = c.ragged ? m.tab : nullptr;
+    if (p.source_out && sl.up_interp == IDC_INTERP_JOINT) {         // guide: the slot's own L plane and this call's l_cent
         const double* pa = sl.d_labq.get() + hw;
-        if (sl.up_interp == IDC_INTERP_JOINT)
-            HIPCHK(h, launch_gray_joint_fullres(sl.d_src.get(), c.gray_bits, m.tab, n, 0, 0, p.max_tiles, pa, pa + hw, 1, (long long)(3 * hw), sl.d_L.get(),
-                                                c.l_cent, h->H, h->W, IDC_INTERP_JOINT, sl.up_joint, sl.d_full.get(), c.out_bits, nullptr, s));
-        else
-            HIPCHK(h, launch_ragged_gray_fullres(sl.d_src.get(), c.gray_bits, m.tab, n, (long long)(p.in_bytes / p.bpp_in), sl.d_labq.get(), h->H, h->W,
-                                                 IDC_INTERP_LINEAR, sl.d_full.get(), c.out_bits, s));
-    } else if (p.source_out && sl.up_interp == IDC_INTERP_JOINT) {         // guide: the slot's own L plane and this call's l_cent
-        const double* pa = sl.d_labq.get() + hw;
-        HIPCHK(h, launch_joint_fullres(sl.d_src.get(), c.ragged ? m.tab : nullptr, n, c.src_h, c.src_w, p.max_tiles, pa, pa + hw, 1, (long long)(3 * hw),
-                                       sl.d_L.get(), c.l_cent, h->H, h->W, IDC_INTERP_JOINT, sl.up_joint, sl.d_full.get(), nullptr, s));
-    } else if (p.source_out && c.ragged)
-        HIPCHK(h, launch_ragged_fullres_rgb(sl.d_src.get(), m.tab, n, (long long)(p.in_bytes / 3), sl.d_labq.get(), h->H, h->W, IDC_INTERP_LINEAR,
-                                            sl.d_full.get(), s));
-    else if (p.source_out)
-        HIPCHK(h, launch_batch_fullres_rgb(sl.d_src.get(), n, c.src_h, c.src_w, sl.d_labq.get(), h->H, h->W, IDC_INTERP_LINEAR, sl.d_full.get(), s));
+        HIPCHK(h, launch_joint_fullres(c.gray_bits, sl.d_src.get(), tab, n, c.src_h, c.src_w, p.max_tiles, pa, pa + hw, 1, (long long)(3 * hw), sl.d_L.get(),
+                                       c.l_cent, h->H, h->W, IDC_INTERP_JOINT, sl.up_joint, sl.d_full.get(), c.out_bits, nullptr, s));
+    } else if (p.source_out)                                        // on the plan's bytes per pixel
+        HIPCHK(h, launch_packed_fullres(c.gray_bits, sl.d_src.get(), tab, n, c.src_h, c.src_w, (long long)(p.in_bytes / p.bpp_in), sl.d_labq.get(), h->H,
+                                        h->W, IDC_INTERP_LINEAR, sl.d_full.get(), c.out_bits, s));
     return IDC_OK;
 }
 

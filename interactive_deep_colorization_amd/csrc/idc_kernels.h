@@ -253,18 +253,6 @@ hipError_t launch_lab_post(const float* L, float l_add, const float* ab, unsigne
 hipError_t launch_upsample_lab2rgb(const void* a_plane, const void* b_plane, int src_f64, int H, int W, int interp, const double* L_out,
                                    int oh, int ow, unsigned char* rgb, hipStream_t s);
 
-// Image ingestion (colorize_image.py:52-77): srcs [n] device pointers to [src_h,src_w,3] u8 images -> bilinear net-size rgb_net [n,H,W,3] u8
-// (colorspace.resize_bilinear_u8's rule, float64; the identity at src == net size), lab_net [n,3,H,W] f64 = rgb2lab of it (either may be
-// nullptr) and Lp [n][H*W] fp32 = L - l_cent, in one launch
-hipError_t launch_ingest_rgb(const unsigned char* const* srcs, int n, int src_h, int src_w, int H, int W, float l_cent, float* Lp,
-                             unsigned char* rgb_net, double* lab_net, hipStream_t s);
-
-// Full-resolution getters (colorize_image.py:123-158) from the resident uint8 source src [oh,ow,3]: L = rgb2lab(src)[0] (mask == nullptr) or
-// 50 * zoom(mask, order 0) / mask_value (mask [H,W] fp32; mask_value 0: L = 0), (a, b) planes [H,W] (fp32 or fp64; nullptr: a = b = 0)
-// resized as in launch_upsample_lab2rgb, Lab -> sRGB uint8 -> rgb [oh,ow,3].  src and rgb 4-byte aligned.
-hipError_t launch_fullres_rgb(const unsigned char* src, int oh, int ow, const void* a_plane, const void* b_plane, int src_f64, int H, int W,
-                              int interp, const float* mask, float mask_value, unsigned char* rgb, hipStream_t s);
-
 // Colour picker (data/lab_gamut.py).  gamut_map: abGrid(gamut_size, D).update_gamut(L[k]) for k < n -- grid side A, point (i, j) = (a, b) =
 // (-gamut_size + i D, -gamut_size + j D) -> pts [n,A,A,3] u8 (truncated), mask [n,A,A] u8 (1: the uint8 colour is within 1.0 of the point in
 // Lab), masked [n,A,A,3] u8 = mask ? pts : 255; each output may be nullptr.  snap_colors: snap_ab(L[k], rgb[k]) for k < n -> rgb_out [n,3] u8,
@@ -279,7 +267,7 @@ hipError_t launch_global_stats(const unsigned char* rgb, const float* centres, u
                                int H, int W, hipStream_t s);
 
 // Reference-image global hints (idc_global_stats_rgb / idc_set_global_refs / idc_forward_async_rgb_ref; idc_colour.hip).
-// ref_stats: launch_global_stats for m references of INDIVIDUAL sizes, each sampled to the net size [H,W] by launch_ingest_rgb's rule inside the
+// ref_stats: launch_global_stats for m references of INDIVIDUAL sizes, each sampled to the net size [H,W] by launch_ingest's rule inside the
 // kernel: refs [m] = {byte offset into packed, h, w}, packed = the [h,w,3] u8 images back to back (no alignment asked) -> counts [m][313]
 // (uint32, zeroed by the caller) and sat_part [m][ref_stats_workgroups(H, W)] (float64, every entry written): the saturation sum of each of
 // a reference's workgroups, reduced in a fixed order.  A reference's figures depend on nothing but its own pixels and (H, W).
@@ -300,58 +288,51 @@ struct HintRect { int y0, x0, y1, x1; float c0, c1, c2; };
 hipError_t launch_raster_hints(const HintRect* hints, int n_hints, int mode, float mask_value, float* ab, float* mask,
                                int H, int W, hipStream_t s);
 
-// Pipelined uint8 batches (idc_forward_async_rgb; idc_colour.hip), ONE launch each for all n images.
-// batch_prologue: src [n,src_h,src_w,3] u8 packed -> Lp [n][H*W] = L - l_cent by launch_ingest_rgb's rule, and per pixel the LAST hint of
-// hints[offs[i] .. offs[i+1]) (already clipped, as for launch_raster_hints) that covers it -> ab [n,2,H,W], mask [n,1,H,W]; offs == nullptr: no
-// image has hints.  batch_fullres_rgb: launch_fullres_rgb's pixel (L of the source pixel, (a, b) = planes 1 and 2 of image i's lab_q [n,3,H,W]
-// f64 resized by `interp`) for every pixel of src [n,oh,ow,3] -> rgb [n,oh,ow,3], both packed and 4-byte aligned at their base only.
-hipError_t launch_batch_prologue(const unsigned char* src, int n, int src_h, int src_w, int H, int W, float l_cent, const int* offs,
-                                 const HintRect* hints, int mode, float mask_value, float* Lp, float* ab, float* mask, hipStream_t s);
-hipError_t launch_batch_fullres_rgb(const unsigned char* src, int n, int oh, int ow, const double* lab_q, int H, int W, int interp,
-                                    unsigned char* rgb, hipStream_t s);
-
-// Pipelined batches of images of INDIVIDUAL sizes (idc_forward_async_images; idc_colour.hip): the two launches above, still ONE each for all n
-// images, over a table in device memory.  imgs [n+1]: entry i = {byte offset of image i in src, pixels of images 0..i-1, h, w}; the [h,w,3] u8
-// images lie back to back (off = 3 * first; no alignment asked of an image's start), and entry n = {all bytes, all pixels, 0, 0} closes the
-// run.  ragged_prologue: batch_prologue with image i's own size and start.  ragged_fullres_rgb: batch_fullres_rgb for the `total` =
-// imgs[n].first pixels of the run -> rgb, packed as src is; src and rgb 4-byte aligned at their base only.
+// Image kernels (idc_colour.hip): a source image on the device to the net's input, and the net's result back to the source's size.  Five
+// launchers, each ONE kernel template over the source format.  bits = 0: [h,w,3] u8 RGB; 8 | 16: one plane [h,w] of u8 | u16 samples whose value
+// stands on all three channels (idc_set_image_gray; the rule: include/ideepcolor.h).  out_bits = 8 | 16: the image goes out as u8 | u16 [.,.,3]
+// (16 only from 16-bit samples).  Grids: RGB launches walk a capped grid (idc_grid.h) in a grid-stride loop; grey launches are exact.
+//
+// ImgDesc: images of INDIVIDUAL sizes packed back to back (idc_forward_async_images / _gray).  imgs [n+1]: entry i = {byte offset of image i in
+// src, pixels of images 0..i-1, h, w}; no alignment is asked of an image's start, and entry n = {all bytes, all pixels, 0, 0} closes the run.
+// imgs == nullptr where a launcher allows it: a uniform run of n images of sh x sw (RGB only; for launch_joint_fullres also ONE plane, n = 1).
 struct ImgDesc { long long off, first; int h, w; };
-hipError_t launch_ragged_prologue(const unsigned char* src, const ImgDesc* imgs, int n, int H, int W, float l_cent, const int* offs,
-                                  const HintRect* hints, int mode, float mask_value, float* Lp, float* ab, float* mask, hipStream_t s);
-hipError_t launch_ragged_fullres_rgb(const unsigned char* src, const ImgDesc* imgs, int n, long long total, const double* lab_q, int H, int W,
-                                     int interp, unsigned char* rgb, hipStream_t s);
+
+// Ingestion (colorize_image.py:52-77): srcs [n] device pointers to [src_h,src_w,C] images -> bilinear net-size net [n,H,W,C] of the sample type
+// (colorspace.resize_bilinear_u8's rule, float64; the identity at src == net size), lab_net [n,C,H,W] f64 = rgb2lab of it -- (L, a, b) of an
+// RGB image, L of a plane -- (either may be nullptr) and Lp [n][H*W] fp32 = L - l_cent, in one launch.
+hipError_t launch_ingest(int bits, const void* const* srcs, int n, int src_h, int src_w, int H, int W, float l_cent, float* Lp, void* net,
+                         double* lab_net, hipStream_t s);
+
+// Full-resolution getters (colorize_image.py:123-158) from the resident source src [oh,ow,C]: L = rgb2lab(src)[0] (mask == nullptr) or
+// 50 * zoom(mask, order 0) / mask_value (mask [H,W] fp32; mask_value 0: L = 0), (a, b) planes [H,W] (fp32 or fp64; nullptr: a = b = 0)
+// resized as in launch_upsample_lab2rgb, Lab -> sRGB -> rgb [oh,ow,3].  src and rgb 4-byte aligned.
+hipError_t launch_fullres(int bits, const void* src, int oh, int ow, const void* a_plane, const void* b_plane, int src_f64, int H, int W, int interp,
+                          const float* mask, float mask_value, void* rgb, int out_bits, hipStream_t s);
+
+// Pipelined batches, ONE launch each for all n images.
+// prologue: the packed sources -> Lp [n][H*W] = L - l_cent by launch_ingest's rule from image i's own size and start, and per pixel the LAST
+// hint of hints[offs[i] .. offs[i+1]) (already clipped, as for launch_raster_hints) that covers it -> ab [n,2,H,W], mask [n,1,H,W];
+// offs == nullptr: no image has hints.
+// packed_fullres: launch_fullres's pixel (L of the source pixel, (a, b) = planes 1 and 2 of image i's lab_q [n,3,H,W] f64 resized by `interp`)
+// for every pixel of the run -> rgb, packed as src is (image i at element 3 * first); src and rgb 4-byte aligned at their base only.
+// total = imgs[n].first, the pixels of the run (read only with a table; a uniform run has n * oh * ow).
+hipError_t launch_prologue(int bits, const void* src, const ImgDesc* imgs, int n, int sh, int sw, int H, int W, float l_cent, const int* offs,
+                           const HintRect* hints, int mode, float mask_value, float* Lp, float* ab, float* mask, hipStream_t s);
+hipError_t launch_packed_fullres(int bits, const void* src, const ImgDesc* imgs, int n, int oh, int ow, long long total, const double* lab_q, int H,
+                                 int W, int interp, void* rgb, int out_bits, hipStream_t s);
 
 // Joint bilateral ab upsampling (idc_fullres_rgb with IDC_INTERP_JOINT, idc_fullres_ab, the source-size epilogue of the pipelined calls while
-// idc_set_batch_upsample is JOINT; idc_colour.hip; the rule: include/ideepcolor.h).  One workgroup per 32 x 8 output tile on an exact grid
-// dim3(max_tiles, n): max_tiles = joint_tiles of the largest image.  imgs: the ImgDesc run as above, or nullptr: n images of sh x sw packed back
-// to back.  Image i reads the planes a_plane / b_plane + i * plane_stride elements ([H,W] fp32 or fp64; both nullptr: a = b = 0) and, for
-// interp 3, the guide Lp + i * H * W (fp32, L - l_cent) with jp = {R, 2 sigma_s^2, 2 sigma_r^2}; interp 0..2: launch_fullres_rgb's rules.
-// -> rgb (packed as src is, any alignment; or nullptr) and ab_out (or nullptr): image i's [2,h,w] f64 at 2 * first_i.
+// idc_set_batch_upsample is JOINT; the rule: include/ideepcolor.h).  One workgroup per 32 x 8 output tile on an exact grid
+// dim3(max_tiles, n): max_tiles = joint_tiles of the largest image.  Image i reads the planes a_plane / b_plane + i * plane_stride elements
+// ([H,W] fp32 or fp64; both nullptr: a = b = 0) and, for interp 3, the guide Lp + i * H * W (fp32, L - l_cent) with
+// jp = {R, 2 sigma_s^2, 2 sigma_r^2}; interp 0..2: launch_fullres's rules.
+// -> rgb (packed as src is, any alignment, u16: even; or nullptr) and ab_out (or nullptr): image i's [2,h,w] f64 at 2 * first_i.
 struct JointParams { int R; double two_ss, two_sr; };
 inline long long joint_tiles(int h, int w) { return (long long)((h + 7) / 8) * ((w + 31) / 32); }
-hipError_t launch_joint_fullres(const unsigned char* src, const ImgDesc* imgs, int n, int sh, int sw, long long max_tiles, const void* a_plane,
+hipError_t launch_joint_fullres(int bits, const void* src, const ImgDesc* imgs, int n, int sh, int sw, long long max_tiles, const void* a_plane,
                                 const void* b_plane, int src_f64, long long plane_stride, const float* Lp, float l_cent, int H, int W, int interp,
-                                JointParams jp, unsigned char* rgb, double* ab_out, hipStream_t s);
-
-// Greyscale sources (idc_set_image_gray and the full-resolution getters on a kept plane; idc_colour.hip; the rule: include/ideepcolor.h).
-// bits = 8 | 16: the plane's samples are u8 | u16; out_bits = 8 | 16: the image goes out as u8 | u16 [.,.,3] (16 only from 16).  Exact grids.
-// ingest_gray: launch_ingest_rgb for srcs [n] device pointers to [src_h,src_w] planes -> gray_net [n,H,W] (the sample type) and l_net [n,H,W]
-// f64 (either may be nullptr) and Lp.  gray_fullres: launch_fullres_rgb for one plane src [oh,ow]; src and rgb 4-byte aligned.
-// gray_joint_fullres: launch_joint_fullres for planes -- imgs == nullptr: one plane [sh,sw] (n = 1); else the run below, grid dim3(max_tiles, n)
-// -> rgb (or nullptr) and ab_out (or nullptr).  ragged_gray_prologue / ragged_gray_fullres (idc_forward_async_gray): launch_ragged_prologue /
-// launch_ragged_fullres_rgb for planes packed back to back; image i starts at SAMPLE imgs[i].first of src and at element 3 * first of rgb
-// (ImgDesc::off is not read); src and rgb 4-byte aligned at their base only.
-hipError_t launch_ingest_gray(const void* const* srcs, int bits, int n, int src_h, int src_w, int H, int W, float l_cent, float* Lp, void* gray_net,
-                              double* l_net, hipStream_t s);
-hipError_t launch_gray_fullres(const void* src, int bits, int oh, int ow, const void* a_plane, const void* b_plane, int src_f64, int H, int W,
-                               int interp, const float* mask, float mask_value, void* rgb, int out_bits, hipStream_t s);
-hipError_t launch_gray_joint_fullres(const void* src, int bits, const ImgDesc* imgs, int n, int sh, int sw, long long max_tiles, const void* a_plane,
-                                     const void* b_plane, int src_f64, long long plane_stride, const float* Lp, float l_cent, int H, int W,
-                                     int interp, JointParams jp, void* rgb, int out_bits, double* ab_out, hipStream_t s);
-hipError_t launch_ragged_gray_prologue(const void* src, int bits, const ImgDesc* imgs, int n, int H, int W, float l_cent, const int* offs,
-                                       const HintRect* hints, int mode, float mask_value, float* Lp, float* ab, float* mask, hipStream_t s);
-hipError_t launch_ragged_gray_fullres(const void* src, int bits, const ImgDesc* imgs, int n, long long total, const double* lab_q, int H, int W,
-                                      int interp, void* rgb, int out_bits, hipStream_t s);
+                                JointParams jp, void* rgb, int out_bits, double* ab_out, hipStream_t s);
 
 // Antialiased ingestion (idc_set_ingest_filter; idc_resample.hip; the rule: include/ideepcolor.h): the pre-pass that writes the net-size lattice
 // image [H,W,channels] of each of the njobs down-scaled images (ResampleJob, idc_resample.h: byte offsets from src_base / dst_base, the image's

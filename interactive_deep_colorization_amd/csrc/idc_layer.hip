@@ -10,7 +10,7 @@
 //   wave      lane l takes the footprint's row-major pixels l, l + 64, ... upwards into its own sum from 0.0 (adjacent lanes, adjacent pixels);
 //             the 64 lanes fold by halves (32, 16, ... 1), as reveal_hints_kernel's waves do.
 //   pixel     A < alpha_min: skipped before any colour arithmetic.  Else (a, b) of raster_hints_kernel's IDC_HINT_RGB colour: the sRGB table in
-//             LDS (batch_prologue_kernel's) and linear_to_lab's expressions.
+//             LDS (prologue_kernel's) and linear_to_lab's expressions.
 //   cell      covered by a rectangle (mask != 0: a call with a layer has mask_value != 0): left alone.  Else hinted iff cnt >= 1 and
 //             255 * cnt >= cover * tot, in integers: ab = the sum / cnt in float64, rounded once to fp32, mask = mask_value.
 //   passes    a workgroup takes kLayerPasses batches of 256 (thread form) or 4 (wave form) consecutive cells, so that the table is filled and

@@ -22,6 +22,7 @@ import glob_ref
 import gray_ref as G
 import ingest_ref
 import joint_ref as J
+import ragged_ref as R
 from interactive_deep_colorization_amd import _native as N
 from interactive_deep_colorization_amd import api, engine, workloads
 
@@ -424,6 +425,50 @@ def test_gray16_pipelined_equals_blocking(eng, upsample):
             np.testing.assert_array_equal(r, _blocking(e, g, None, upsample, 16)[0])
     finally:
         e.set_batch_upsample("linear")
+
+
+# ------------------------------------------------------------------------------------------------ 8b. pipelined: groups that span many planes
+_ALONE = {}
+
+
+def _alone(e, g, hints, depth):
+    """The plane sent alone (n = 1) through the pipelined call -> (source-size image, out_ab [2,H,W]).  Made once, never written to."""
+    k = (g.shape, g.dtype.str, g.tobytes(), repr(hints), depth)
+    if k not in _ALONE:
+        ab = np.empty((1, 2, G.H, G.W), np.float32)
+        outs = e.forward_async_gray(1, [g], [hints], out_ab=ab, out="source", depth=depth)
+        e.wait(1)
+        out = np.array(outs[0])
+        for a in (out, ab):
+            a.setflags(write=False)
+        _ALONE[k] = (out, ab[0])
+    return _ALONE[k]
+
+
+@pytest.mark.parametrize("dtype,depth", [(np.uint8, 8), (np.uint16, 8), (np.uint16, 16)], ids=["u8_to_u8", "u16_to_u8", "u16_to_u16"])
+@pytest.mark.parametrize("case", range(len(R.SPANS)), ids=["four_in_one_group", "tail_is_an_image", "three_boundaries"])
+def test_groups_that_span_many_planes(eng, case, dtype, depth):
+    """test_ragged_batch_gpu.py::test_groups_that_span_many_images for planes: four 1 x 1 images in one 4-pixel group, a byte-access tail that
+    is an image of its own, three boundaries in one group.  The carry into the next image is the RGB kernel's; which source dword a pixel's
+    sample sits in and which result dwords take its three values depend on the format.  Each image equals the plane sent alone, bit for bit."""
+    e = eng()
+    assert (e.H, e.W) == (64, 64)
+    make = G.gray8 if dtype == np.uint8 else G.gray16
+    planes = [make(sh, sw, 500 + 20 * case + j) for j, (sh, sw) in enumerate(R.sizes(R.SPANS[case], G.H, G.W))]
+    n = len(planes)
+    hints = [G.HINTS[(i + 1) % 4:] for i in range(n)]
+    assert any(len(set(grp)) > 1 for grp in R.groups([p.shape for p in planes])[0])       # a group does span images
+    outs = [np.full(p.shape + (3,), 7, np.uint16 if depth == 16 else np.uint8) for p in planes]
+    ab = np.full((n, 2, G.H, G.W), 7, np.float32)
+    got = e.forward_async_gray(0, planes, hints, out_rgb=outs, out_ab=ab, out="source", depth=depth)
+    e.wait(0)
+    assert all(g is o for g, o in zip(got, outs))
+    assert np.abs(ab).max() > 0
+    for i, p in enumerate(planes):
+        want, want_ab = _alone(e, p, hints[i], depth)
+        assert outs[i].dtype == want.dtype and outs[i].shape == want.shape
+        np.testing.assert_array_equal(outs[i], want, err_msg="image %d (%dx%d)" % ((i,) + p.shape))
+        np.testing.assert_array_equal(ab[i], want_ab, err_msg="out_ab of image %d" % i)
 
 
 # ------------------------------------------------------------------------------------------------ 9. pipelined: leakage and statuses

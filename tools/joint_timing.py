@@ -4,8 +4,8 @@ bench.py leg, no pass / fail number).  The figure is the compute span of ``idc_p
 ``--batch`` images through ``forward_async_images``, which is what ``colorize_images(out='source')`` enqueues:
 
   net      out='net': prologue, network, ``lab_post_kernel`` -- no source-size epilogue at all
-  linear   out='source' with the linear zoom (``ragged_fullres_rgb_kernel``: the parent's launch, untouched by this change)
-  joint    out='source' with ``joint_fullres_kernel`` in its place (R, sigma_s, sigma_r from ``--radius`` / ``--sigma-s`` / ``--sigma-r``)
+  linear   out='source' with the linear zoom (``packed_fullres_kernel``)
+  joint    out='source' with ``joint_fullres_kernel`` in its place (both templates over the source format; these legs run RGB8) (R, sigma_s, sigma_r from ``--radius`` / ``--sigma-s`` / ``--sigma-r``)
 
 The three legs alternate on the two slots, one batch at a time (nothing else is in flight while a span is taken), ``--warmup`` untimed rounds
 first, then ``--runs`` timed ones; median (min / max) in ms.  ``epilogue`` = a leg's median minus the 'net' median: what the source-size step
