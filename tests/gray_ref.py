@@ -3,11 +3,13 @@ idc_fullres_rgb16) restated in numpy float64, the inputs the GPU file runs it on
 
 The resize is ``colorspace.resize_bilinear_u8``'s expressions restated for one channel of either width (the rounding lattice is the sample
 type's); the colour formulas are the oracle's rgb2lab / lab2rgb written out for arrays; both truncations are ``astype``.  Nothing here reads
-the project this one was modelled on.  ``variant`` swaps in one of the mistakes tests/test_gray_cpu.py shows the comparisons would catch:
+the project this one was modelled on.  Nets: SIZES / SEEDS / BATCH are for the 64 x 64 net (H, W); NET = (40, 72) with NET_SIZES / NET_SEEDS /
+NET_HINTS is the net that is not square, on which the (H, W) every grey kernel is handed cannot be swapped unseen.  ``variant`` swaps in one of the mistakes tests/test_gray_cpu.py shows the comparisons would catch:
   'drop8'       a 16-bit route that drops to 8 bits before L
   'scale65536'  full scale 65536 instead of 65535
   'round_out'   round-to-nearest where the rule truncates on output
-  'resize8'     a resize that rounds to the 8-bit lattice"""
+  'resize8'     a resize that rounds to the 8-bit lattice
+  'transposed_net'  H and W of the net swapped (``resize``): nothing on the 64 x 64 net, which is why NET = (40, 72) below has cases of its own"""
 import numpy as np
 
 import ingest_ref
@@ -41,19 +43,29 @@ def full_scale(dtype, variant=None):
     return 65536.0 if variant == "scale65536" else 65535.0
 
 
-def gray16(sh, sw, seed=0):
+# A net that is not square: an H / W swap anywhere between the resize, net_sample, zoom_nearest, interp_ab and the joint tile shows.  Planes
+# smaller than the net, of the net's size and 211 x 83 (down on rows 5.3x, on columns 1.15x); their seeds are found as SEEDS' are, for the resize
+# to 40 x 72 (tests/test_gray_cpu.py holds the condition).  ``gray16(.., net=NET)`` draws them.
+NET = (40, 72)
+NET_SIZES = [(23, 31), (40, 72), (211, 83)]
+NET_SEEDS = {(23, 31): 1016, (40, 72): 1000, (211, 83): 1005}
+NET_HINTS = [(2, 3, 12, 30, 35.0, -50.0), (10, 25, 30, 60, -30.0, 45.0), (25, 2, 38, 20, 70.0, 20.0), (0, 50, 6, 71, -60.0, -15.0)]
+
+
+def gray16(sh, sw, seed=0, net=None):
     """(sh, sw) uint16: the luma of a crop of the golden photograph on the 16-bit lattice (smooth content, real interpolation weights) plus
-    seeded noise in the low byte, so that the samples are not multiples of 257."""
+    seeded noise in the low byte, so that the samples are not multiples of 257.  ``net``: None for the 64 x 64 net's draws, NET for NET's."""
+    assert net in (None, NET)
     rgb = ingest_ref.mortar()
-    rs = np.random.RandomState(SEEDS.get((sh, sw), 0) + seed)
+    rs = np.random.RandomState((SEEDS.get((sh, sw), 0) if net is None else NET_SEEDS[(sh, sw)]) + seed)
     y, x = rs.randint(0, 256 - sh + 1), rs.randint(0, 256 - sw + 1)
     c = rgb[y:y + sh, x:x + sw].astype(np.int64)
     v = 60 * c[..., 0] + 120 * c[..., 1] + 24 * c[..., 2] + rs.randint(0, 256, (sh, sw))      # at most 204 * 255 + 255: nothing clips
     return v.astype(np.uint16)
 
 
-def gray8(sh, sw, seed=0):
-    return (gray16(sh, sw, seed) >> 8).astype(np.uint8)
+def gray8(sh, sw, seed=0, net=None):
+    return (gray16(sh, sw, seed, net) >> 8).astype(np.uint8)
 
 
 def hint_lists(n, rows=None):
@@ -92,6 +104,8 @@ def resize_unrounded(g, out_h, out_w):
 def resize(g, out_h=H, out_w=W, variant=None):
     """The net-size plane, of g's dtype: round half up on the dtype's own lattice, clamped to it."""
     g = np.asarray(g)
+    if variant == "transposed_net":                 # H and W swapped: the plane of a (W, H) net, whose rows of H are then read as rows of W
+        return resize(g, out_w, out_h).reshape(out_h, out_w)
     out = resize_unrounded(g, out_h, out_w)
     if variant == "resize8" and g.dtype == np.uint16:
         return (np.floor(out / 257.0 + 0.5).clip(0, 255) * 257).astype(np.uint16)

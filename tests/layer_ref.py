@@ -7,6 +7,10 @@ Bars (``compare``):
   ab            within one float32 ulp everywhere (the bar tests/test_eval_gpu.py holds revealed colours to: the device's pow / cbrt and
                 numpy's may differ in the last float64 bit, which moves the once-rounded fp32 by at most one step); bit for bit in every cell
                 with ONE painted pixel -- there the mean is the colour itself
+Nets: ``case`` runs on the 64 x 64 net (H, W), whose 4096 cells fill four thread-form workgroups exactly.  ``net_case`` runs on NET = (40, 72):
+2880 cells, so the thread form's third workgroup ends on a fourth pass with ONE live wave (the `p < HW` tail and the fold of the count over
+idle waves), a swap of H and W shows, and 640 x 1152 / 641 x 1152 sit on either side of the form threshold (16 x 16 = 256 pixels: thread;
+18 x 16: wave).  NET_MUTANTS break the walk over the net rather than the rule of a cell.
 Everything here is a function of its arguments and fixed seeds; references are computed once per case and cached (do not write into them)."""
 import functools
 
@@ -79,11 +83,13 @@ def raster_rects(rects, mode, mask_value, H_=H, W_=W):
 def layer_hints(rgba, alpha_min, cover, rects=(), mode="rgb", mask_value=MASK_VALUE, H_=H, W_=W, mutant=None):
     """The rule.  -> dict(ab (2,H,W) f32, mask (1,H,W) f32, cells int, single (H,W) bool: the layer hinted the cell from ONE painted pixel,
     cnt / tot (H,W) int: the counts of every cell)."""
-    assert mutant is None or mutant in MUTANTS
+    assert mutant is None or mutant in MUTANTS + NET_MUTANTS
     rgba = np.asarray(rgba)
     lh, lw = rgba.shape[:2]
     ab, mask = raster_rects(rects, mode, mask_value, H_, W_)
     covered = mask[0] != 0
+    if mutant in NET_MUTANTS:
+        return _net_mutant(rgba, alpha_min, cover, ab, mask, covered, mask_value, H_, W_, mutant)
     A = rgba[..., 3].astype(np.int64)
     painted = A > alpha_min if mutant == "alpha_gt" else A >= alpha_min
     col = rgb_to_ab(rgba[..., :3])
@@ -125,6 +131,32 @@ def layer_hints(rgba, alpha_min, cover, rects=(), mode="rgb", mask_value=MASK_VA
             cells += 0 if covered[y, x] else 1
             single[y, x] = cnt == 1
     return dict(ab=ab, mask=mask, cells=cells, single=single, cnt=cnts, tot=tots)
+
+
+def _net_mutant(rgba, alpha_min, cover, ab, mask, covered, mask_value, H_, W_, mutant):
+    """Mistakes in how the kernel walks the net, not in the rule of a cell (the kernel: a workgroup takes PASSES x 256 consecutive cells in the
+    thread form, 256 at a time, or PASSES x 4 in the wave form, one per wave; the hits of its four waves are summed into the count):
+      'transposed_net'    H and W swapped: the rule for a (W, H) net, whose rows of H cells are then read as rows of W (nothing on a square net)
+      'tail_unhinted'     cells from the last, partial pass of the last workgroup on are left alone
+      'count_first_wave'  the count takes the hits of each workgroup's first wave only"""
+    lh, lw = rgba.shape[:2]
+    if mutant == "transposed_net":
+        t = layer_hints(rgba, alpha_min, cover, (), "rgb", mask_value, W_, H_)
+        t = {k: (v.reshape(v.shape[:-2] + (H_, W_)) if isinstance(v, np.ndarray) else v) for k, v in t.items()}
+        wave = wave_form(lh, lw, W_, H_)
+    else:
+        t = layer_hints(rgba, alpha_min, cover, (), "rgb", mask_value, H_, W_)
+        wave = wave_form(lh, lw, H_, W_)
+    hinted = (t["mask"][0] != 0) & ~covered
+    p = np.arange(H_ * W_).reshape(H_, W_)
+    per_pass = 4 if wave else 256
+    if mutant == "tail_unhinted":
+        hinted &= p < (H_ * W_) // per_pass * per_pass
+    ab, mask = ab.copy(), mask.copy()
+    ab[:, hinted] = t["ab"][:, hinted]
+    mask[0, hinted] = np.float32(mask_value)
+    counted = hinted & (p % per_pass < (1 if wave else 64)) if mutant == "count_first_wave" else hinted
+    return dict(ab=ab, mask=mask, cells=int(counted.sum()), single=t["single"] & hinted, cnt=t["cnt"], tot=t["tot"])
 
 
 def _ord32(a):
@@ -189,6 +221,39 @@ def case(k):
     rgba = draw_layer(lh, lw, alpha_min, 100 + k)
     rgba.setflags(write=False)
     return rgba, alpha_min, cover, layer_hints(rgba, alpha_min, cover, RECTS)
+
+
+# ---- a net that is not square: 40 x 72 = 2880 cells.  The thread form gives 3 workgroups, the last of 832 cells: three full passes and a
+# fourth with ONE live wave (cells 2816..2879, the last 64 of the bottom row), so `p < HW` and the fold of the count over idle waves run; an
+# h / w swap shows.  The wave form takes 180 workgroups of 16 cells and has no partial pass here.
+NET = (40, 72)
+NET_SIZES = [(1, 1), (40, 72), (72, 40), (211, 83), (1000, 700), (65, 16384), (640, 1152), (641, 1152)]
+# bounds: 65 x 16384: 3 x 229, wave; 640 x 1152: 16 x 16 = 256, the largest thread-form footprint; 641 x 1152: 18 x 16, the first wave-form one
+NET_WAVE = [False, False, False, False, True, True, False, True]           # (1000 x 700: 25 x 11 = 275, wave on this net)
+NET_RECTS = [(5, 7, 9, 30, 200, 40, 60), (30, 12, 35, 13, 10, 250, 10), (38, 60, 45, 80, 30, 30, 240), (8, 28, 6, 33, 255, 255, 0)]
+NET_MUTANTS = ["transposed_net", "tail_unhinted", "count_first_wave"]
+TAIL = 64                                                               # the cells of the live wave of the last pass
+
+
+def draw_net_layer(lh, lw, alpha_min, seed, net=NET):
+    """``draw_layer`` with a fully painted strip of random colours under the bottom row of the net, from cell 20 to the right edge: hinted cells
+    among the last TAIL, some of them under NET_RECTS[2]."""
+    a = draw_layer(lh, lw, alpha_min, seed)
+    r0, c0 = footprint(net[0] - 1, lh, net[0])[0], footprint(20, lw, net[1])[0]
+    rng = np.random.RandomState(seed + 1)
+    a[r0:, c0:, :3] = rng.randint(0, 256, a[r0:, c0:, :3].shape)
+    a[r0:, c0:, 3] = 255
+    return np.ascontiguousarray(a)
+
+
+@functools.lru_cache(maxsize=None)
+def net_case(k, net=NET):
+    """GPU case k of the 40 x 72 net: NET_SIZES[k] with PARAMS[k % 4], over NET_RECTS.  -> (rgba, alpha_min, cover, want)."""
+    lh, lw = NET_SIZES[k]
+    alpha_min, cover = PARAMS[k % 4]
+    rgba = draw_net_layer(lh, lw, alpha_min, 300 + k, net)
+    rgba.setflags(write=False)
+    return rgba, alpha_min, cover, layer_hints(rgba, alpha_min, cover, NET_RECTS, H_=net[0], W_=net[1])
 
 
 def rects_of_layer(rgba, alpha_min):

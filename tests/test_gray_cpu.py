@@ -2,7 +2,9 @@
 wrapper's resize, its rgb2lab and the oracle's), the identity (I16) in float64, the conditions the GPU file's inputs have to meet, the
 mutants of gray_ref that the GPU file's comparisons have to catch, the plan of a greyscale batch (tools/gray_plan_selftest.cpp, plain and
 under the address and undefined-behaviour sanitizers), and the marshalling of HipColorizer.set_image_gray / fullres_rgb(depth=) /
-forward_async_gray and the generators colorize_gray / suggest_gray on an engine that calls no library."""
+forward_async_gray and the generators colorize_gray / suggest_gray on an engine that calls no library.  The inputs of the 40 x 72 net
+(gray_ref.NET) are held to the same rounding condition, and a swap of H and W is shown to be caught on each of them and on none of the 64 x 64
+net's."""
 import ctypes
 import os
 import re
@@ -126,6 +128,30 @@ def test_gpu_inputs_use_the_low_byte_and_every_residue():
     r = G.ramp16()
     assert r.shape == (211, 83) and len(np.unique(r)) == 300 and int(r.max()) - int(r.min()) == 299
     assert len(np.unique(r >> 8)) <= 2
+
+
+@pytest.mark.parametrize("size", G.NET_SIZES)
+def test_the_40x72_net_inputs_stay_away_from_rounding_boundaries_and_show_a_swap(size):
+    H, W = G.NET
+    for g in (G.gray16(*size, net=G.NET), G.gray8(*size, net=G.NET)):
+        assert g.shape == size
+        v = G.resize_unrounded(g, H, W) + 0.5
+        assert float(np.abs(v - np.round(v)).min()) > 1e-6, (size, g.dtype)
+        net = G.resize(g, H, W)
+        assert net.shape == (H, W) and net.dtype == g.dtype
+        if size == G.NET:
+            np.testing.assert_array_equal(net, g)                               # the net's own size: the identity
+        # 'transposed_net' is caught by the exact comparison of the net plane and by l_net, on every entry ...
+        swapped = G.resize(g, H, W, variant="transposed_net")
+        assert swapped.shape == net.shape and not G.same(swapped, net)[0]
+        assert not G.close(G.lightness(swapped), G.lightness(net), G.L_TOL)[0]
+    assert (G.gray16(*size, net=G.NET) % 257 != 0).any()
+    # ... and by no comparison on the 64 x 64 net, whatever the plane
+    for s in G.SIZES:
+        np.testing.assert_array_equal(G.resize(G.gray16(*s), variant="transposed_net"), G.resize(G.gray16(*s)))
+    assert all(0 <= r[0] <= r[2] < H and 0 <= r[1] <= r[3] < W for r in G.NET_HINTS)
+    np.testing.assert_array_equal(G.gray16(23, 31), G.gray16(23, 31, net=None))     # today's draws are as they were
+    assert not np.array_equal(G.gray16(23, 31), G.gray16(23, 31, net=G.NET))
 
 
 # ------------------------------------------------------------------------------------------------ 4. mutants

