@@ -185,6 +185,10 @@ __device__ __forceinline__ void suggest_body(const float* __restrict__ pdf, long
             if (best != asg[b]) { asg[b] = best; if (cnt[b]) changed = 1; }
         }
         __syncthreads();
+        // Read the flag HERE, between the barrier behind the assignment pass and the barrier behind the means.  Read behind the last barrier of
+        // the sweep it would race with thread 0's reset at the top of the next sweep: a wave that came late would see 0, leave the loop alone
+        // and keep stale assignments while the others went on.  Every thread holds the same copy, so the branch below is uniform.
+        const int again = changed;
         if (t < K) {                              // fixed-order (ascending bin) weighted mean of cluster t
             double sx = 0.0, sy = 0.0; unsigned long long w = 0ull;
             for (int b = 0; b < B; ++b)
@@ -193,7 +197,7 @@ __device__ __forceinline__ void suggest_body(const float* __restrict__ pdf, long
             if (w) { mx[t] = sx / (double)w; my[t] = sy / (double)w; }     // an empty cluster keeps its centre
         }
         __syncthreads();
-        if (!changed) break;
+        if (!again) break;
     }
     if (t == 0) {                                 // order by occupancy, descending, stable
         unsigned used = 0u;

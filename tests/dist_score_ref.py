@@ -4,7 +4,8 @@ sums over j, the per-image sum -- is walked in that order, one step per loop pas
 arithmetic).
 
   truth       tests/eval_ref.py's Lab of the net-size image; a cell's s x s values t = dy*s + dx folded by halves, / count, one rounding to float32
-  neighbours  d^2 = da*da + db*db, d = sqrt(d^2) in float64 from the float32 values; a FULL stable sort of d (ties keep the lower index)
+  neighbours  d^2 = da*da + db*db, d = sqrt(d^2) in float64 from the float32 values; a FULL stable sort of d (ties keep the lower index);
+              by="d2": of d^2 itself, the device's documented order (tests/test_dist_edges_gpu.py compares every cell with it)
   weights     exp(-d_j^2 / (2 sigma^2)) / their sum (j ascending); exactly 1 for nn == 1
   xent        0 - sum_j w_j * log(max(p[q_j], FLT_MIN)), j ascending
   rank        #{q : p[q] > p[t] || (p[q] == p[t] && q < t)}
@@ -46,15 +47,18 @@ def truth(src, H, W, s):
     return out
 
 
-def neighbours(truth_ab, centres, nn):
+def neighbours(truth_ab, centres, nn, by="d"):
     """truth_ab [2,...] float32, centres [B,2] float32 -> (q [...,nn] int, d2 [...,nn], margins [...,2] = (d_2 - d_1, d_(nn+1) - d_nn; inf
-    where there is no such centre), second [...] = q_2 or -1)."""
+    where there is no such centre), second [...] = q_2 or -1).  by="d": the stable sort of d = sqrt(d^2), the definition; by="d2": the stable
+    sort of d^2 itself, the device's documented rule -- the same order except where two DIFFERENT d^2 round to one square root (then "d" sees a
+    tie and takes the lower index, "d2" the smaller d^2)."""
+    assert by in ("d", "d2")
     t = np.asarray(truth_ab, np.float32).astype(np.float64)
     c = np.asarray(centres, np.float32).astype(np.float64)
     da, db = t[0][..., None] - c[:, 0], t[1][..., None] - c[:, 1]
     d2 = da * da + db * db
     d = np.sqrt(d2)
-    order = np.argsort(d, axis=-1, kind="stable")
+    order = np.argsort(d if by == "d" else d2, axis=-1, kind="stable")
     ds = np.take_along_axis(d, order, axis=-1)
     B = c.shape[0]
     inf = np.full(ds.shape[:-1], np.inf)
@@ -87,11 +91,11 @@ def rank_of(p, t, tie=True):
     return before.sum(axis=0).astype(np.int32)
 
 
-def score(dist, truth_ab, centres, nn=1, sigma=5.0, tie=True):
+def score(dist, truth_ab, centres, nn=1, sigma=5.0, tie=True, by="d"):
     """One image: dist [B,Hd,Wd] float32, truth_ab [2,Hd,Wd] float32 -> dict(target, rank int32 [Hd,Wd]; xent float64 [Hd,Wd]; margins
-    [Hd,Wd,2]; second [Hd,Wd]; w [Hd,Wd,nn]; q [Hd,Wd,nn])."""
+    [Hd,Wd,2]; second [Hd,Wd]; w [Hd,Wd,nn]; q [Hd,Wd,nn]).  ``by``: the neighbours' order, see ``neighbours``."""
     dist = np.asarray(dist, np.float32)
-    q, d2, margins, second = neighbours(truth_ab, centres, nn)
+    q, d2, margins, second = neighbours(truth_ab, centres, nn, by)
     w = weights(d2, sigma)
     acc = np.zeros(q.shape[:-1])
     for j in range(nn):

@@ -108,9 +108,8 @@ def test_resident_distribution_and_suggestions_529(sd, precision):
 
 
 def test_suggestions_on_a_peaked_distribution(sd):
-    """A distribution with three far-apart modes (written through a fabricated head bias is not possible from outside,
-    so the resident tensor is exercised through a real forward and the mixture through the oracle-equality above);
-    here: K larger than the number of drawn bins leaves empty clusters at the end with share 0."""
+    """K larger than the number of drawn bins leaves empty clusters at the end with share 0.  (Peaked, one-hot and flat distributions
+    -- through a crafted head -- are tests/test_dist_edges_gpu.py's.)"""
     L, ab, mask = workloads.random_batch(1, 64, seed=1)
     e = engine.HipColorizer(64, 64, max_batch=1, precision="fp32", dist=True)
     e.load_state_dict(sd)
