@@ -849,6 +849,60 @@ int idc_set_batch_output(idc_handle h, int format, int matrix);
 int idc_fullres_ycc(idc_handle h, int img, int source, int interp, int l_mode, int format, int matrix, uint8_t* out);
 int idc_rgb_to_ycc420(idc_handle h, int n, const idc_ref_image* images, int format, int matrix, uint8_t* const* out);
 
+/* ---- frame sequences: a motion-adaptive recursive (temporal) filter on the net-size ab map.  A network of this kind, run frame by frame,
+ *      flickers: grain and small exposure changes in L move the ab map by several units between frames of a static shot.  The filter pulls
+ *      each pixel's colour towards its own filtered value in the previous frame, strongly where the lightness did not change, not at all
+ *      where it did (motion) or where the whole frame changed (a cut).  Opt-in: with it off (the default) no launch, no plan byte and no
+ *      output byte of any call changes.
+ *      FRAMES are the images of the pipelined calls of one handle, in enqueue order: image 0 .. n-1 of a call, then the next call, whichever
+ *      slot it uses.  The handle owns ONE sequence state on the device: y_prev [2,H,W] float32, l_prev [H,W] float32, and whether a frame
+ *      has been seen.
+ *      THE RULE, for one frame: its fp32 L plane l [H,W] (the slot's plane, (float)(L - l_cent), as ingestion wrote it), the network's fp32
+ *      ab map x [2,H,W], the parameters strength s, sigma (L units), radius R, cut c (L units, 0 = never).  Everything is float64 with fp
+ *      contract(off).
+ *        no previous frame (the first after idc_create or idc_temporal_reset): y = x bit for bit; reported cut = 1, D = 0.
+ *        otherwise    e[j,i] = ((double)l[j,i] - (double)l_prev[j,i])^2.
+ *                     D = (sum of e over the plane) / (H*W) in float64; the order of the sum is the implementation's own but FIXED: the same
+ *                     bits for the same two planes whatever n, slot or position in the call (per 16 x 64 tile: 4 neighbouring pixels per
+ *                     thread, a butterfly over the wave, the four waves in order; then the tiles in row-major order).  No float atomics.
+ *                     If c > 0 and D > c*c the frame is a scene cut: y = x bit for bit, cut = 1.
+ *                     Else m[j,i] = the mean of e over rows j-R .. j+R (outer loop, ascending) and columns i-R .. i+R (inner loop,
+ *                     ascending) clipped to the plane: the sum divided by the number of taps inside; nothing is replicated.
+ *                     g = s * exp(-m / (2 sigma^2)), and per channel y = (float)((double)x + g * ((double)y_prev - (double)x)).
+ *        state        afterwards y_prev <- y (the stored floats, not the float64 values) and l_prev <- l, also after a cut.  Because the
+ *                     state is the rounded output, a sequence gives the same bits however it is split into calls.
+ *        where y goes y replaces x in the slot's ab map before anything else reads it: the Lab -> RGB epilogue, lab_q, the linear and joint
+ *                     source-size kernels, the 16-bit result, the YCbCr post-pass, sse and the returned out_ab all see the filtered map.  The
+ *                     distribution heads, their taps and scores, and pred_ab of the 313 head stay on the raw network.
+ *      Defaults: strength 0.6, sigma 4.0, radius 1, cut 12.0: plausible values.  NOBODY HAS MEASURED THEM ON TRAINED WEIGHTS: this
+ *      repository has none.
+ *      idc_set_temporal_filter: handle state, copied into the call when a pipelined call is enqueued, like idc_set_batch_upsample: a batch
+ *      in flight keeps what it was enqueued with.  IDC_ERR_INVALID_ARG unless on is 0 or 1, strength in [0, 0.95], sigma in [0.5, 100],
+ *      radius in 0..3 and cut 0 or in (0, 100] (a NaN is outside); a refused call changes nothing.  While on it governs
+ *      idc_forward_async_rgb, _rgb_ref, _images (with or without references), _eval, _dist, _dist_score, _gray and _layers, at both output
+ *      sizes and both depths.  idc_forward_async (the caller's planes) and every blocking forward are not sequences: they neither read nor
+ *      advance the state.
+ *      idc_temporal_reset: the next frame enqueued starts a sequence.  Ordered behind the batches already enqueued; does not block.
+ *      idc_temporal_info: the per-frame cut flags and D of the slot's last completed call; they travel back with the call's small results.
+ *      IDC_ERR_INVALID_ARG for a slot outside 0..1, both pointers NULL, a slot still in flight, or a slot whose last call ran with the
+ *      filter off (or that never ran), in this order.
+ *      idc_temporal_apply: the rule alone on host arrays ab [n,2,H,W], l [n,H,W] -> y [n,2,H,W] (cut [n], D [n] may be NULL), through the same
+ *      kernels; it reads and advances the handle's state with the handle's current parameters.  Blocks, drains the slots first, needs no
+ *      weights, runs whether `on` is set or not.  IDC_ERR_BATCH for n outside 1..max_batch; IDC_ERR_INVALID_ARG for a NULL ab, l or y.
+ *      idc_temporal_state: the state as it stands behind everything enqueued: y_prev [2,H,W], l_prev [H,W] (zeros while have is 0), have;
+ *      each pointer may be NULL.  Blocks.
+ *      Status: everything is decided on the host before anything is enqueued, and a call refused there leaves the state as it was.  The
+ *      pipelined calls keep their own tables; the filter adds no row to them.  A call that fails LATER, with IDC_ERR_HIP from the runtime
+ *      while it is being enqueued, may already have advanced the sequence: idc_temporal_reset before going on.
+ *      Left out: motion compensation, more than one sequence per handle, the blocking routes, the sharded engine, filtering the
+ *      distribution or pred_ab, a raw out_ab beside the filtered one (the filter-off call gives it). */
+int idc_set_temporal_filter(idc_handle h, int on, double strength, double sigma, int radius, double cut);
+int idc_temporal_reset(idc_handle h);
+int idc_temporal_info(idc_handle h, int slot, int32_t* cut /*[n]*/, double* D /*[n]*/);
+int idc_temporal_apply(idc_handle h, int n, const float* ab /*[n,2,H,W]*/, const float* l /*[n,H,W]*/, float* y /*[n,2,H,W]*/,
+                       int32_t* cut /*[n] or NULL*/, double* D /*[n] or NULL*/);
+int idc_temporal_state(idc_handle h, float* y_prev /*[2,H,W]*/, float* l_prev /*[H,W]*/, int32_t* have);
+
 /* ---- distribution scores: how much probability did the head put on the colour the pixel really has?  The question the distribution heads
  *      were trained on: the reference's training layers encode the ground-truth ab into the colour bins with NNEncode
  *      (caffe_files/color_quantization.py:7-33; NNEncLayer: NN = 1, sigma = 5, NN = 10 commented beside it, caffe_traininglayers.py:161-189) and

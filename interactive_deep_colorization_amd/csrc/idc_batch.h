@@ -58,6 +58,9 @@ struct BatchCall {
     bool has_layers = false; const idc_hint_layer* layers = nullptr; int alpha_min = 0, cover = 0; int32_t* cells = nullptr;
     // the handle's output format and matrix as the call was enqueued (idc_set_batch_output): IDC_OUT_RGB leaves every byte of the plan as it was
     int out_format = IDC_OUT_RGB, out_matrix = IDC_YCC_JFIF;
+    // the handle's temporal filter as the call was enqueued (idc_set_temporal_filter).  It takes no room in the plan or in the metadata block:
+    // on or off, every byte of both is the same
+    TemporalParams temporal = temporal_defaults();
 };
 
 inline void set_batch_layers(BatchCall& c, const idc_batch_layers* l) {

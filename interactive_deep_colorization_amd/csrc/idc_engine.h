@@ -231,6 +231,14 @@ struct idc_context {
     int out_format = 0, out_matrix = 0;  // IDC_OUT_RGB, IDC_YCC_JFIF
     DevMem<unsigned char> d_ycc, d_ycc_meta, d_ycc_in;
     PinnedMem<unsigned char> h_ycc, h_ycc_meta, h_ycc_in;
+    // temporal ab filter (idc_set_temporal_filter; a pipelined call takes its copy of the parameters when it is enqueued): the sequence state
+    // y_prev [2,H,W] and l_prev [H,W] fp32 on the device, whether a frame has been ENQUEUED since idc_create / idc_temporal_reset (every launch
+    // that reads or writes the state is on the compute stream, so the host's flag at enqueue time is the device's truth at run time), and what
+    // the blocking idc_temporal_apply works in: its frames, the two kernels' scratch and its info block, grown on demand
+    TemporalParams temporal = temporal_defaults();
+    bool temporal_have = false;
+    DevMem<float> d_t_yprev, d_t_lprev, d_t_x, d_t_l;
+    DevMem<unsigned char> d_t_scratch, d_t_info;
     DevMem<unsigned char> d_pick;        // idc_gamut_map / idc_snap_colors: inputs + results of one call, device and pinned
     PinnedMem<unsigned char> h_pick;
     Event ev_sync;                       // idc_stream_wait / idc_stream_signal
@@ -278,6 +286,12 @@ struct idc_context {
         PinnedMem<unsigned char> h_layer, h_cells;
         // idc_set_batch_output: the batch's packed plane blocks (BatchPlan::ycc_bytes), which leave the device in place of d_rgb / d_full
         DevMem<unsigned char> d_ycc;
+        // idc_set_temporal_filter: the parameters the slot's last call was enqueued with (on = 0: it ran unfiltered), its frame count, the two
+        // kernels' scratch (idc_temporal.h) and the info block D [n] + cut [n], device and pinned: it always travels back, it is small
+        TemporalParams temporal = temporal_defaults();
+        int temporal_n = 0;
+        DevMem<unsigned char> d_t_scratch, d_t_info;
+        PinnedMem<unsigned char> h_t_info;
     } pipe[2];
     Event ev_pipe_base;
     bool pipe_ready = false;             // ev_pipe_base is recorded (ensure_pipeline)

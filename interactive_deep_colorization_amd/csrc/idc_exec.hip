@@ -643,6 +643,7 @@ int idc_forward_async(idc_handle h, int slot, int n, const float* L_mc, const fl
     sl.outs.clear();
     HIPCHK(h, copy_out(h, sl, out_ab, out_direct, sl.d_out.get(), sl.h_out.get(), 0, (size_t)n * hw * 2 * 4));
     HIPCHK(h, hipEventRecord(sl.ev_out.get(), h->s_out.get()));
+    sl.temporal.on = 0;                      // the caller's planes are no sequence: idc_temporal_info has nothing to report for this call
     sl.pending = true; sl.timed = true;
     return IDC_OK;
 }
@@ -691,6 +692,26 @@ static int batch_handle_checks(idc_context* h, const BatchCall& c, const BatchPl
     return IDC_OK;
 }
 
+// the sequence state of the temporal filter, made on first use: never read before a frame has written it (idc_context::temporal_have)
+static int ensure_temporal_state(idc_context* h) {
+    const size_t hw = (size_t)h->H * h->W;
+    HIPCHK(h, h->d_t_yprev.ensure(2 * hw * sizeof(float)));
+    HIPCHK(h, h->d_t_lprev.ensure(hw * sizeof(float)));
+    return IDC_OK;
+}
+
+// the two launches of the rule on `s`: x [n,2,H,W] becomes y in place, the state advances, D and the flags land in `info` (idc_temporal.h)
+static int run_temporal(idc_context* h, const TemporalParams& tp, int n, const float* L, float* x, unsigned char* scratch, unsigned char* info,
+                        hipStream_t s) {
+    double* g = (double*)scratch;
+    double* part = (double*)(scratch + temporal_part_at(n, h->H, h->W));
+    const int have = h->temporal_have ? 1 : 0;
+    HIPCHK(h, launch_temporal_diff(L, h->d_t_lprev.get(), have, n, h->H, h->W, tp.radius, tp.strength, tp.sigma, g, part, s));
+    HIPCHK(h, launch_temporal_blend(x, g, part, L, h->d_t_yprev.get(), h->d_t_lprev.get(), have, n, h->H, h->W, tp.cut, (double*)info,
+                                    (int*)(info + temporal_info_cut_at(n)), s));
+    return IDC_OK;
+}
+
 // every buffer of the slot this batch uses, at the size it needs: the slot is idle (its last batch was waited for), so they may be replaced by
 // larger ones (the reference stage grows in stage_refs)
 static int batch_reserve(idc_context* h, const BatchCall& c, const BatchPlan& p, const BatchLayouts& L, Slot& sl) {
@@ -725,6 +746,13 @@ static int batch_reserve(idc_context* h, const BatchCall& c, const BatchPlan& p,
     if (any_staged_in) HIPCHK(h, sl.h_src.ensure(p.in_bytes));
     if (any_staged_rgb) HIPCHK(h, sl.h_rgb.ensure(p.ycc_bytes ? p.ycc_bytes : p.rgb_bytes));
     if (p.ycc_bytes) HIPCHK(h, sl.d_ycc.ensure(p.ycc_bytes, 65536));
+    if (c.temporal.on) {  // the state, the two kernels' scratch and the info block, at the handle's largest batch
+        const int rc = ensure_temporal_state(h);
+        if (rc) return rc;
+        HIPCHK(h, sl.d_t_scratch.ensure(temporal_scratch_bytes(h->max_batch, h->H, h->W)));
+        HIPCHK(h, sl.d_t_info.ensure(temporal_info_bytes(h->max_batch), 4096));
+        HIPCHK(h, sl.h_t_info.ensure(temporal_info_bytes(h->max_batch), 4096));
+    }
     if (!p.ab_pinned) HIPCHK(h, sl.h_out.ensure(nb * hw * 2 * 4));
     if (c.has_refs) HIPCHK(h, sl.d_glob_in.ensure(nb * kGlobIn * sizeof(float)));
     if (c.has_layers) {   // the packed layers in an array of their own, and the cell counts
@@ -815,6 +843,13 @@ static int batch_colourise(idc_context* h, const BatchCall& c, const BatchPlan& 
                              (p.dist && !(h->flags & IDC_FLAG_DIST313)) ? h->d_dist.get() : nullptr, c.has_refs ? sl.d_glob_in.get() : h->d_glob_in.get());
     if (rc) return rc;
     if (!p.dist && !((h->flags & IDC_FLAG_DIST313) && h->keep_dist313)) h->dist_n = dist_n;      // no distribution was written: the blocking forward's stays resident
+    // the temporal filter: y over x in the slot's ab map, in front of everything that reads it; the heads above saw the raw network
+    sl.temporal = c.temporal; sl.temporal_n = n;
+    if (c.temporal.on) {
+        const int trc = run_temporal(h, c.temporal, n, sl.d_L.get(), sl.d_out.get(), sl.d_t_scratch.get(), sl.d_t_info.get(), s);
+        if (trc) return trc;
+        h->temporal_have = true;             // the launches are enqueued: the next call's frame 0 follows this call's last one
+    }
     HIPCHK(h, launch_lab_post(sl.d_L.get(), c.l_cent, sl.d_out.get(), sl.d_rgb.get(), p.source_out ? sl.d_labq.get() : nullptr, n, h->H, h->W, s));
     sl.up_interp = h->batch_interp; sl.up_joint = h->joint;       // the handle's setting as it is now: a later idc_set_batch_upsample does not reach this batch
     const ImgDesc* tab = c.ragged ? m.tab : nullptr;
@@ -874,6 +909,8 @@ static int batch_copy_out(idc_context* h, const BatchCall& c, const BatchPlan& p
     int rc = IDC_OK;
     HIPCHK(h, hipEventRecord(sl.ev_out0.get(), h->s_out.get()));
     sl.outs.clear();
+    if (c.temporal.on)    // D and the cut flags, into the slot's own pinned block: idc_temporal_info reads them there
+        HIPCHK(h, hipMemcpyAsync(sl.h_t_info.get(), sl.d_t_info.get(), temporal_info_bytes(c.n), hipMemcpyDeviceToHost, h->s_out.get()));
     if (p.score) {
         const idc_dist_score_out* so = c.sout;
         const ScoreLayout& sc = L.score;
@@ -921,6 +958,7 @@ static int forward_async_rgb(idc_handle h, const BatchCall& call) {
     BatchCall c = call;
     c.ingest_filter = h->ingest_filter;       // the handle's setting as it is now: a later idc_set_ingest_filter does not reach this batch
     c.out_format = h->out_format; c.out_matrix = h->out_matrix;      // ... and so with idc_set_batch_output
+    c.temporal = h->temporal;                                        // ... and with idc_set_temporal_filter
     BatchPlan p;
     std::string why;
     rc = plan_batch(c, h->H, h->W, h->max_batch, &p, &why);
@@ -1065,6 +1103,87 @@ int idc_pipeline_times(idc_handle h, int slot, float* ms6) {
     HIPCHK(h, hipSetDevice(h->device));
     hipEvent_t evs[6] = {sl.ev_in0.get(), sl.ev_in.get(), sl.ev_comp0.get(), sl.ev_comp.get(), sl.ev_out0.get(), sl.ev_out.get()};
     for (int i = 0; i < 6; ++i) HIPCHK(h, hipEventElapsedTime(&ms6[i], h->ev_pipe_base.get(), evs[i]));
+    return IDC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- temporal ab filter
+int idc_set_temporal_filter(idc_handle h, int on, double strength, double sigma, int radius, double cut) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (!temporal_params_ok(on, strength, sigma, radius, cut))
+        return fail(&h->err, IDC_ERR_INVALID_ARG, "temporal filter: on %d in {0,1}, strength %g in [0, 0.95], sigma %g in [0.5, 100], radius %d in 0..%d, "
+                    "cut %g 0 or in (0, 100]", on, strength, sigma, radius, kTemporalMaxRadius, cut);
+    h->temporal = {on, strength, sigma, cut, radius};
+    return IDC_OK;
+}
+
+int idc_temporal_reset(idc_handle h) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    h->temporal_have = false;                // every launch already enqueued carried its own copy of the flag
+    return IDC_OK;
+}
+
+int idc_temporal_info(idc_handle h, int slot, int32_t* cut, double* D) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (slot < 0 || slot > 1) return fail(&h->err, IDC_ERR_INVALID_ARG, "slot %d not in 0..1", slot);
+    if (!cut && !D) return fail(&h->err, IDC_ERR_INVALID_ARG, "null cut and D");
+    auto& sl = h->pipe[slot];
+    if (sl.pending) return fail(&h->err, IDC_ERR_INVALID_ARG, "slot %d is still in flight: idc_wait it first", slot);
+    if (!h->pipe_ready || !sl.timed || !sl.temporal.on || sl.temporal_n <= 0)
+        return fail(&h->err, IDC_ERR_INVALID_ARG, "slot %d: its last call ran without the temporal filter", slot);
+    const int n = sl.temporal_n;
+    if (D) memcpy(D, sl.h_t_info.get(), (size_t)n * sizeof(double));
+    if (cut) memcpy(cut, sl.h_t_info.get() + temporal_info_cut_at(n), (size_t)n * sizeof(int32_t));
+    return IDC_OK;
+}
+
+int idc_temporal_apply(idc_handle h, int n, const float* ab, const float* l, float* y, int32_t* cut, double* D) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (n <= 0 || n > h->max_batch) return fail(&h->err, IDC_ERR_BATCH, "batch %d outside 1..%d", n, h->max_batch);
+    if (!ab || !l || !y) return fail(&h->err, IDC_ERR_INVALID_ARG, "null ab, l or y");
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = drain_pipeline(h);
+    if (rc) return rc;
+    hipStream_t s = h->stream.get();
+    HIPCHK(h, hipStreamSynchronize(s));      // the buffers of the previous call may still be in flight
+    rc = ensure_temporal_state(h);
+    if (rc) return rc;
+    const size_t hw = (size_t)h->H * h->W;
+    HIPCHK(h, h->d_t_x.ensure((size_t)n * 2 * hw * sizeof(float)));
+    HIPCHK(h, h->d_t_l.ensure((size_t)n * hw * sizeof(float)));
+    HIPCHK(h, h->d_t_scratch.ensure(temporal_scratch_bytes(n, h->H, h->W)));
+    HIPCHK(h, h->d_t_info.ensure(temporal_info_bytes(h->max_batch), 4096));
+    HIPCHK(h, hipMemcpyAsync(h->d_t_x.get(), ab, (size_t)n * 2 * hw * sizeof(float), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(h->d_t_l.get(), l, (size_t)n * hw * sizeof(float), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipStreamSynchronize(s));      // a pageable source is the caller's again
+    rc = run_temporal(h, h->temporal, n, h->d_t_l.get(), h->d_t_x.get(), h->d_t_scratch.get(), h->d_t_info.get(), s);
+    if (rc) return rc;
+    h->temporal_have = true;
+    std::vector<unsigned char> info(temporal_info_bytes(n));
+    HIPCHK(h, hipMemcpyAsync(y, h->d_t_x.get(), (size_t)n * 2 * hw * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(info.data(), h->d_t_info.get(), info.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    if (D) memcpy(D, info.data(), (size_t)n * sizeof(double));
+    if (cut) memcpy(cut, info.data() + temporal_info_cut_at(n), (size_t)n * sizeof(int32_t));
+    return IDC_OK;
+}
+
+int idc_temporal_state(idc_handle h, float* y_prev, float* l_prev, int32_t* have) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = drain_pipeline(h);
+    if (rc) return rc;
+    hipStream_t s = h->stream.get();
+    HIPCHK(h, hipStreamSynchronize(s));
+    const size_t hw = (size_t)h->H * h->W;
+    if (have) *have = h->temporal_have ? 1 : 0;
+    if (!h->temporal_have) {                 // no frame yet: the planes read as zeros
+        if (y_prev) memset(y_prev, 0, 2 * hw * sizeof(float));
+        if (l_prev) memset(l_prev, 0, hw * sizeof(float));
+        return IDC_OK;
+    }
+    if (y_prev) HIPCHK(h, hipMemcpyAsync(y_prev, h->d_t_yprev.get(), 2 * hw * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (l_prev) HIPCHK(h, hipMemcpyAsync(l_prev, h->d_t_lprev.get(), hw * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
     return IDC_OK;
 }
 

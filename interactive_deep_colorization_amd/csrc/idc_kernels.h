@@ -10,6 +10,7 @@
 #include "idc_resample.h"
 #include "idc_layer.h"
 #include "idc_ycc.h"
+#include "idc_temporal.h"
 
 namespace idc {
 
@@ -353,6 +354,16 @@ hipError_t launch_hint_layers(const unsigned char* layers, const LayerDesc* desc
 // IDC_OUT_NV12, matrix IDC_YCC_*.  Exact grid dim3(max_blocks, n), max_blocks = the largest ycc_blocks among the images.
 hipError_t launch_ycc420(const unsigned char* rgb, const YccDesc* descs, int n, int max_blocks, int format, int matrix, unsigned char* out,
                          hipStream_t s);
+
+// Motion-adaptive temporal ab filter (idc_set_temporal_filter / idc_temporal_apply; idc_temporal.hip; the rule: include/ideepcolor.h; the
+// geometry: idc_temporal.h).  L [n,H,W] fp32 = the frames' L planes, l_prev [H,W] / y_prev [2,H,W] the sequence state (read only with have != 0),
+// x [n,2,H,W] fp32 the network's ab maps, overwritten by y; g float64 [n,H,W] and part float64 [n, temporal_partials] the scratch the first
+// launch fills for the second; D float64 [n] and cut_flags int32 [n] what the call reports.  Every pointer but part, D and cut_flags is 16-byte
+// aligned.  Exact grids: dim3(temporal_tiles, n) and temporal_blend_blocks; cut = 0 never cuts.
+hipError_t launch_temporal_diff(const float* L, const float* l_prev, int have, int n, int H, int W, int radius, double strength, double sigma,
+                                double* g, double* part, hipStream_t s);
+hipError_t launch_temporal_blend(float* x, const double* g, const double* part, const float* L, float* y_prev, float* l_prev, int have, int n,
+                                 int H, int W, double cut, double* D, int* cut_flags, hipStream_t s);
 
 // Evaluation batches (idc_reveal_hints / idc_forward_async_eval; idc_colour.hip).  reveal_hints: (c0, c1) of each of the n_rects clipped
 // rectangles of `hints` = the float64 mean ab (rounded once to fp32) of its image's net-size pixels under it, one workgroup per rectangle, fixed

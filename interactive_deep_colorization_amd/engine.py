@@ -510,6 +510,7 @@ def _gray_item(who, item, with_ref):
 
 class HipColorizer(object):
     _out_format, _out_matrix = "rgb", "jfif"    # what set_batch_output last set (class defaults: an engine that never called it)
+    _temporal = None                            # what set_temporal_filter last set: None = off, else the dict of its four parameters
 
     def __init__(self, H=256, W=None, max_batch=1, precision="bf16", device=0, dist=False, global_hints=False, dist313=False,
                  throughput_blob=False):
@@ -866,6 +867,106 @@ class HipColorizer(object):
         prev = (self._out_format, self._out_matrix)
         self.set_batch_output(prev[0] if out_format is None else out_format, prev[1] if out_matrix is None else out_matrix)
         return prev
+
+    # ---- frame sequences: the temporal ab filter ---------------------------------------------
+    def set_temporal_filter(self, strength=0.6, sigma=4.0, radius=1, cut=12.0):
+        """The motion-adaptive recursive filter on the net-size ab map of the pipelined calls (``idc_set_temporal_filter``; the rule stands in
+        ``include/ideepcolor.h``): consecutive images of the ``forward_async_rgb`` / ``_images`` / ``_eval`` / ``_dist`` / ``_gray`` /
+        ``_layers`` calls are frames of one sequence, in enqueue order.  Each pixel's colour is pulled towards its filtered value in the
+        previous frame with weight ``strength`` (0..0.95) where L did not change, falling off as exp(-m / 2 sigma^2) with the mean squared L
+        difference m over a (2 radius + 1)^2 window (``sigma`` 0.5..100 L units, ``radius`` 0..3); a frame whose mean squared L difference
+        exceeds ``cut``^2 (0 < cut <= 100; 0 = never) is a scene cut and passes unfiltered.  ``set_temporal_filter(None)`` switches it off (the
+        default).  The defaults are plausible values; nobody has measured them on trained weights.  Handle state; a batch in flight keeps
+        what it was enqueued with.  ``forward_async`` and the blocking calls are no sequences."""
+        if strength is None or strength is False:
+            prev = self._temporal or dict(strength=0.6, sigma=4.0, radius=1, cut=12.0)
+            self._chk(self.lib.idc_set_temporal_filter(self._h, 0, float(prev["strength"]), float(prev["sigma"]), int(prev["radius"]),
+                                                       float(prev["cut"])))
+            self._temporal = None
+            return
+        self._chk(self.lib.idc_set_temporal_filter(self._h, 1, float(strength), float(sigma), int(radius), float(cut)))
+        self._temporal = dict(strength=float(strength), sigma=float(sigma), radius=int(radius), cut=float(cut))
+
+    def temporal_reset(self):
+        """The next frame enqueued starts a sequence (``idc_temporal_reset``): ordered behind the batches in flight, does not block."""
+        self._chk(self.lib.idc_temporal_reset(self._h))
+
+    def temporal_info(self, slot, n=None):
+        """``(cut, D)`` of the slot's last completed call (``idc_temporal_info``): per frame whether it passed unfiltered (the first frame of a
+        sequence, or a scene cut) and its mean squared L difference to its predecessor.  ``n``: the call's frame count (default: the one this
+        engine enqueued on the slot).  IdcError for a slot in flight or whose last call ran with the filter off."""
+        if n is None:
+            n = self.__dict__.get("_slot_n", {}).get(int(slot))
+            if n is None:
+                raise ValueError("temporal_info: this engine enqueued nothing on slot %d: give the call's frame count" % int(slot))
+        cut = np.zeros(self.max_batch, np.int32)
+        D = np.zeros(self.max_batch, np.float64)
+        vp = ctypes.c_void_p
+        self._chk(self.lib.idc_temporal_info(self._h, int(slot), cut.ctypes.data_as(vp), D.ctypes.data_as(vp)))
+        return cut[:int(n)].copy(), D[:int(n)].copy()
+
+    def temporal_apply(self, ab, l):
+        """The rule alone on host arrays (``idc_temporal_apply``): ab (n,2,H,W) float32 the raw maps, l (n,H,W) float32 the frames' L planes
+        (L - l_cent); reads and advances the engine's sequence state with its current parameters, whether the filter is on or not.  Returns
+        ``(y, cut, D)``.  Blocks; needs no weights."""
+        ab = np.ascontiguousarray(ab, np.float32)
+        l = np.ascontiguousarray(l, np.float32)
+        if ab.ndim != 4 or tuple(ab.shape[1:]) != (2, self.H, self.W):
+            raise ValueError("temporal_apply needs ab of shape (n,2,%d,%d), got %s" % (self.H, self.W, ab.shape))
+        n = ab.shape[0]
+        if tuple(l.shape) == (n, 1, self.H, self.W):
+            l = l.reshape(n, self.H, self.W)
+        if tuple(l.shape) != (n, self.H, self.W):
+            raise ValueError("temporal_apply needs l of shape (%d,%d,%d), got %s" % (n, self.H, self.W, l.shape))
+        y = np.empty_like(ab)
+        cut = np.zeros(max(n, 1), np.int32)
+        D = np.zeros(max(n, 1), np.float64)
+        vp = ctypes.c_void_p
+        self._chk(self.lib.idc_temporal_apply(self._h, int(n), ab.ctypes.data_as(vp), l.ctypes.data_as(vp), y.ctypes.data_as(vp),
+                                              cut.ctypes.data_as(vp), D.ctypes.data_as(vp)))
+        return y, cut[:n], D[:n]
+
+    def temporal_state(self):
+        """``(y_prev (2,H,W) float32, l_prev (H,W) float32, have)``: the sequence state behind everything enqueued
+        (``idc_temporal_state``).  Blocks."""
+        y = np.zeros((2, self.H, self.W), np.float32)
+        l = np.zeros((self.H, self.W), np.float32)
+        have = ctypes.c_int32(0)
+        vp = ctypes.c_void_p
+        self._chk(self.lib.idc_temporal_state(self._h, y.ctypes.data_as(vp), l.ctypes.data_as(vp), ctypes.cast(ctypes.byref(have), vp)))
+        return y, l, bool(have.value)
+
+    def _hold(self, slot, n, arrays):
+        """What every pipelined enqueue leaves behind: the arrays the library reads / writes until the slot's wait, and the call's image
+        count (``temporal_info``'s default)."""
+        self._in_flight[int(slot)] = arrays
+        self.__dict__.setdefault("_slot_n", {})[int(slot)] = int(n)
+
+    def _temporal_stream(self, temporal, gen):
+        """The ``temporal=`` keyword of the streaming generators around the generator ``gen``: None leaves the setting alone; True (the
+        defaults), a dict of ``set_temporal_filter``'s parameters or False (off) is set, and the sequence reset, before the first batch; the
+        previous setting comes back when the generator ends or its consumer walks away, behind the waits of the slots."""
+        if temporal is None:
+            yield from gen
+            return
+        prev = self._temporal
+        if temporal is True:
+            self.set_temporal_filter()
+        elif temporal is False:
+            self.set_temporal_filter(None)
+        else:
+            self.set_temporal_filter(**dict(temporal))
+        try:
+            self.temporal_reset()
+            yield from gen
+        finally:
+            try:
+                gen.close()
+            finally:
+                if prev is None:
+                    self.set_temporal_filter(None)
+                else:
+                    self.set_temporal_filter(**prev)
 
     def _out_shapes(self, shapes, depth=8):
         """The shapes of a pipelined call's image outputs under the output format in effect: (h,w,3) each, or flat plane blocks."""
@@ -1304,9 +1405,9 @@ class HipColorizer(object):
             (m, rarr, idx, c, hist_flag, rflags), keep = _ref_args(refs, ref_index, centres, hist_flag, saturation, n)
             self._chk(self.lib.idc_forward_async_rgb_ref(*(head + (m, rarr, idx.ctypes.data_as(vp) if idx is not None else None,
                                                                    _fptr(c) if c is not None else None, hist_flag, rflags) + tail)))
-        self._in_flight[int(slot)] = (rgb, out_rgb, out_ab)      # the library reads / writes them until the slot's wait
+        self._hold(slot, n, (rgb, out_rgb, out_ab))      # the library reads / writes them until the slot's wait
 
-    def colorize_stream(self, batches, out="net", upsample=None, ingest=None, out_format=None, out_matrix=None, **kw):
+    def colorize_stream(self, batches, out="net", upsample=None, ingest=None, out_format=None, out_matrix=None, temporal=None, **kw):
         """Generator: colourise a stream of uint8 batches with both pipeline slots busy.  ``batches`` yields (rgb (n,h,w,3) uint8, hints) items
         (``hints`` as in ``forward_async_rgb``; n and the source size may change from item to item); each item's (n,H,W,3) [out='net'] or
         (n,h,w,3) [out='source'] uint8 result is yielded in input order, as an array of the caller's own (copied out of the pinned buffer the
@@ -1319,7 +1420,9 @@ class HipColorizer(object):
         ends or is abandoned; None (default) leaves the setting alone.
         ``ingest``: 'bilinear' or 'antialias' -- ``set_ingest_filter`` with the same scope.
         ``out_format`` / ``out_matrix``: 'rgb' | 'i420' | 'nv12' and 'jfif' | 'bt709' -- ``set_batch_output`` with the same scope.  With a
-        YCbCr format an item's result is a list of n ``YCC420`` / ``NV12`` tuples, one per image (``ycc420_views``), not one array."""
+        YCbCr format an item's result is a list of n ``YCC420`` / ``NV12`` tuples, one per image (``ycc420_views``), not one array.
+        ``temporal``: True (the defaults), a dict of ``set_temporal_filter``'s parameters, or False -- the images of the stream are the frames
+        of ONE sequence: the filter is set and the sequence reset before the first batch, the previous setting back with the same scope."""
         def submit(slot, group, first):
             item = group[0]
             rgb, hints = item[0], item[1]
@@ -1343,7 +1446,8 @@ class HipColorizer(object):
             return [[self._own_image(r, state[2]) for r in state[0]]]
 
         # a group of one: the items are whole batches, checked in submit, behind the yield of the slot's older result
-        yield from self._two_slot_stream(batches, 1, upsample, lambda item: item, submit, finish, ingest=ingest, output=(out_format, out_matrix))
+        yield from self._temporal_stream(temporal, self._two_slot_stream(batches, 1, upsample, lambda item: item, submit, finish, ingest=ingest,
+                                                                         output=(out_format, out_matrix)))
 
     def _two_slot_stream(self, items, batch, upsample, parse, submit, finish, key=None, ingest=None, output=(None, None)):
         """The generator behind ``colorize_stream``, ``colorize_images`` and their relatives: ``parse(item)`` every item as it arrives, group
@@ -1531,7 +1635,7 @@ class HipColorizer(object):
                 out_ab.ctypes.data_as(vp) if out_ab is not None else None)
         if not evaluate:
             self._chk(self.lib.idc_forward_async_images(*args))
-            self._in_flight[int(slot)] = (images, out_rgb, out_ab)    # the library reads / writes them until the slot's wait
+            self._hold(slot, len(images), (images, out_rgb, out_ab))    # the library reads / writes them until the slot's wait
             return out_rgb
         sse = self._pool.take((n, 3), np.uint64) if taps is None or taps["want_sse"] else None
         colours = None
@@ -1540,7 +1644,7 @@ class HipColorizer(object):
         args = args + (sse.ctypes.data_as(vp) if sse is not None else None, colours.ctypes.data_as(vp) if colours is not None and colours.size else None)
         if taps is None:
             self._chk(self.lib.idc_forward_async_eval(*args))
-            self._in_flight[int(slot)] = (images, out_rgb, out_ab, sse, colours)
+            self._hold(slot, len(images), (images, out_rgb, out_ab, sse, colours))
             return sse, colours, (out_rgb if want_rgb else None)
         # the distribution taps: every result in pinned pool memory, written in place by the copy-out stream
         P, hd_wd = taps["peaks"], self._dist_grid()
@@ -1582,7 +1686,7 @@ class HipColorizer(object):
             only_score = P == 0 and Q == 0 and not taps["want_entropy"]
             self._chk(self.lib.idc_forward_async_dist_score(*(args + (None if only_score else ctypes.byref(t), ctypes.byref(spec), _fptr(sc_c),
                                                                       ctypes.byref(sout)))))
-        self._in_flight[int(slot)] = (images, out_rgb, out_ab, res)
+        self._hold(slot, len(images), (images, out_rgb, out_ab, res))
         return res
 
     def forward_async_gray(self, slot, images, hints, out_rgb=None, out_ab=None, mode="ab", mask_value=1.0, maskcent=0.0, l_cent=50.0,
@@ -1667,7 +1771,7 @@ class HipColorizer(object):
                                                   float(mask_value), float(maskcent), float(l_cent), flags,
                                                   ctypes.byref(block) if block is not None else None, outs,
                                                   out_ab.ctypes.data_as(vp) if out_ab is not None else None, ctypes.byref(t) if t is not None else None))
-        self._in_flight[int(slot)] = (images, out_rgb, out_ab, res, held, keep)      # the library reads / writes them until the slot's wait
+        self._hold(slot, len(images), (images, out_rgb, out_ab, res, held, keep))      # the library reads / writes them until the slot's wait
         return res if res is not None else out_rgb
 
     def forward_async_layers(self, slot, images, layers, hints, out_rgb=None, out_ab=None, mode="rgb", mask_value=1.0, maskcent=0.0,
@@ -1747,17 +1851,18 @@ class HipColorizer(object):
                                                     float(mask_value), float(maskcent), float(l_cent), flags,
                                                     ctypes.byref(block) if block is not None else None, outs,
                                                     out_ab.ctypes.data_as(vp) if out_ab is not None else None))
-        self._in_flight[int(slot)] = (images, larrs, out_rgb, out_ab, cells, keep)   # the library reads / writes them until the slot's wait
+        self._hold(slot, len(images), (images, larrs, out_rgb, out_ab, cells, keep))   # the library reads / writes them until the slot's wait
         return out_rgb, cells
 
-    def colorize_layers(self, items, batch=None, out="source", depth=8, upsample=None, ingest=None, out_format=None, out_matrix=None, **kw):
+    def colorize_layers(self, items, batch=None, out="source", depth=8, upsample=None, ingest=None, out_format=None, out_matrix=None, temporal=None,
+                        **kw):
         """Generator: ``colorize_images`` / ``colorize_gray`` for images with painted hint layers (``forward_async_layers``).  An item is
         ``(image, layer_or_None, hints)``: image (h,w,3) uint8, or (h,w) uint8 or uint16; layer (lh,lw,4) uint8 RGBA of any size or ``None``;
         hints that image's rectangle list or ``None``.  Grouping, slot alternation and order as in ``colorize_images``; a change of image kind
         closes the group as a full batch does.  ``(rgb, cells)`` is yielded per image: the colourised image as those generators yield it and
         the number of cells its layer hinted (0 without a layer).  ``kw``: mode, mask_value, alpha_min, cover, maskcent, l_cent, ...;
         ``upsample``, ``ingest``, ``out_format`` and ``out_matrix`` as in ``colorize_stream``: with a YCbCr format the image is a ``YCC420`` /
-        ``NV12`` tuple."""
+        ``NV12`` tuple.  ``temporal``: as in ``colorize_stream``."""
         if depth not in (8, 16) or (depth == 16 and out != "source"):
             raise ValueError("depth must be 8, or 16 with out='source'")
 
@@ -1792,8 +1897,9 @@ class HipColorizer(object):
             (rgbs, cells), srcs, _ = state
             return [(self._own_image(r, self._out_dims(s, out)), int(c)) for r, s, c in zip(rgbs, srcs, cells)]
 
-        yield from self._two_slot_stream(items, batch, upsample, parse, submit, finish, key=lambda g: (g[0].ndim, g[0].dtype), ingest=ingest,
-                                         output=(out_format, out_matrix))
+        yield from self._temporal_stream(temporal, self._two_slot_stream(items, batch, upsample, parse, submit, finish,
+                                                                         key=lambda g: (g[0].ndim, g[0].dtype), ingest=ingest,
+                                                                         output=(out_format, out_matrix)))
 
     def _out_dims(self, src, out):
         """(h, w) of the result of the image whose source array is ``src``."""
@@ -1808,12 +1914,13 @@ class HipColorizer(object):
             np.copyto(s, p)
         return srcs
 
-    def colorize_gray(self, items, batch=None, out="source", depth=8, upsample=None, ingest=None, out_format=None, out_matrix=None, **kw):
+    def colorize_gray(self, items, batch=None, out="source", depth=8, upsample=None, ingest=None, out_format=None, out_matrix=None, temporal=None,
+                      **kw):
         """Generator: ``colorize_images`` for greyscale planes (``forward_async_gray``).  An item is ``gray``, ``(gray, hints)`` or
         ``(gray, hints, ref)``: gray (h,w) uint8 or uint16.  Grouping, slot alternation and order as in ``colorize_images``, and a change of
         dtype closes the group as a full batch does: a call carries one format.  One array per image is yielded: (h,w,3) [out='source'] or
         (H,W,3) [out='net'], uint8, or uint16 with ``depth=16`` (uint16 items and out='source' only).  ``upsample``, ``out_format`` and ``out_matrix``: as in ``colorize_stream`` (a YCbCr format yields a ``YCC420`` /
-        ``NV12`` tuple per image and needs depth 8)."""
+        ``NV12`` tuple per image and needs depth 8).  ``temporal``: as in ``colorize_stream``."""
         if depth not in (8, 16) or (depth == 16 and out != "source"):
             raise ValueError("depth must be 8, or 16 with out='source'")
 
@@ -1830,9 +1937,9 @@ class HipColorizer(object):
                 more["refs"], more["ref_index"] = dedupe_refs([g[2] for g in group], len(group))
             return self.forward_async_gray(slot, srcs, [g[1] for g in group], out=out, depth=depth, **more), srcs
 
-        yield from self._two_slot_stream(items, batch, upsample, parse, submit,
-                                         lambda state: [self._own_image(r, self._out_dims(s, out)) for r, s in zip(state[0], state[1])],
-                                         key=lambda g: g[0].dtype, ingest=ingest, output=(out_format, out_matrix))
+        yield from self._temporal_stream(temporal, self._two_slot_stream(
+            items, batch, upsample, parse, submit, lambda state: [self._own_image(r, self._out_dims(s, out)) for r, s in zip(state[0], state[1])],
+            key=lambda g: g[0].dtype, ingest=ingest, output=(out_format, out_matrix)))
 
     def suggest_gray(self, items, centres, batch=None, out="source", depth=8, peaks=8, radius=2, skip_hints=True, K=5, N_draws=25000, seed=0,
                      upsample=None, ingest=None, out_format=None, out_matrix=None, **kw):
@@ -1868,7 +1975,7 @@ class HipColorizer(object):
         yield from self._two_slot_stream(items, batch, upsample, parse, submit, finish, key=lambda g: g[0].dtype, ingest=ingest,
                                          output=(out_format, out_matrix))
 
-    def colorize_images(self, items, batch=None, out="source", upsample=None, ingest=None, out_format=None, out_matrix=None, **kw):
+    def colorize_images(self, items, batch=None, out="source", upsample=None, ingest=None, out_format=None, out_matrix=None, temporal=None, **kw):
         """Generator: colourise a stream of single images of any sizes with both pipeline slots busy.  An item is ``rgb``, ``(rgb, hints)`` or
         ``(rgb, hints, ref)``: rgb (h,w,3) uint8, ``hints`` that image's hint list (rows as in ``set_hints``) or ``None``, ``ref`` ``None`` or an
         (h,w,3) uint8 reference photograph (a ``global_hints`` engine; ``kw`` then carries centres).  Consecutive items are grouped into
@@ -1877,7 +1984,8 @@ class HipColorizer(object):
         caller's own copy.  Sources travel through one pinned pool block per batch; the same reference OBJECT given for several images of a
         batch is uploaded once (``dedupe_refs``).  ``kw``: mode, mask_value, maskcent, l_cent, centres, hist_flag, saturation.
         ``upsample``: as in ``colorize_stream`` ('joint': the edge-aware source-size output).  ``out_format`` / ``out_matrix``: as there; with
-        'i420' or 'nv12' a ``YCC420`` / ``NV12`` tuple of plane views into one uint8 buffer is yielded per image."""
+        'i420' or 'nv12' a ``YCC420`` / ``NV12`` tuple of plane views into one uint8 buffer is yielded per image.  ``temporal``: as in
+        ``colorize_stream``."""
         def submit(slot, group, first):
             srcs = self._pinned_sources(group)
             more = dict(kw)
@@ -1885,18 +1993,75 @@ class HipColorizer(object):
                 more["refs"], more["ref_index"] = dedupe_refs([g[2] for g in group], len(group))
             return self.forward_async_images(slot, srcs, [g[1] for g in group], out=out, **more), srcs
 
-        yield from self._two_slot_stream(items, batch, upsample, lambda item: _image_item("colorize_images", item, True), submit,
-                                         lambda state: [self._own_image(r, self._out_dims(s, out)) for r, s in zip(state[0], state[1])], ingest=ingest,
-                                         output=(out_format, out_matrix))
+        yield from self._temporal_stream(temporal, self._two_slot_stream(
+            items, batch, upsample, lambda item: _image_item("colorize_images", item, True), submit,
+            lambda state: [self._own_image(r, self._out_dims(s, out)) for r, s in zip(state[0], state[1])], ingest=ingest,
+            output=(out_format, out_matrix)))
 
-    def evaluate_images(self, items, batch=None, out="net", mode="reveal", upsample=None, ingest=None, out_format=None, out_matrix=None, **kw):
+    def colorize_video(self, frames, hints=None, batch=None, out="source", depth=8, temporal=True, upsample=None, ingest=None, out_format=None,
+                       out_matrix=None, **kw):
+        """Generator: colourise the frames of one video sequence with the temporal ab filter (``set_temporal_filter``) and both pipeline slots
+        busy.  ``frames`` is an iterable of (h,w,3) uint8 RGB images, or of (h,w) uint8 / uint16 planes (``forward_async_images`` /
+        ``forward_async_gray``; a change of kind or dtype closes the batch, the sequence goes on).  ``hints``: None, a hint list held for every
+        frame, or a dict frame index -> hint list: a key frame's hints hold until the next key (frames before the first key have none).
+        ``(image, cut)`` is yielded per frame, in order: the image as ``colorize_images`` / ``colorize_gray`` yield it, and whether the
+        frame passed unfiltered (the first frame, or a scene cut); with ``temporal=False`` every cut is False.  ``temporal``: True (the
+        defaults), a dict of parameters, False, or None (the engine's setting as it stands, the sequence not reset); ``upsample``,
+        ``ingest``, ``out_format`` and ``out_matrix`` as in ``colorize_stream``; ``kw``: mode, mask_value, maskcent, l_cent."""
+        if depth not in (8, 16) or (depth == 16 and out != "source"):
+            raise ValueError("depth must be 8, or 16 with out='source'")
+        if hints is not None and not isinstance(hints, (list, tuple, dict)):
+            raise ValueError("colorize_video: hints is None, a list or a dict frame index -> list")
+        held = [None]
+
+        def indexed():
+            for k, frame in enumerate(frames):
+                if isinstance(hints, dict):
+                    if k in hints:
+                        held[0] = hints[k]
+                    yield frame, held[0]
+                else:
+                    yield frame, hints
+
+        def parse(item):
+            img = np.asarray(item[0])
+            if img.ndim == 3:
+                return _image_item("colorize_video", (img, item[1]), False)
+            g = _gray_item("colorize_video", (img, item[1]), False)
+            if depth == 16 and g[0].dtype != np.uint16:
+                raise ValueError("colorize_video: depth=16 needs uint16 planes, got %s" % g[0].dtype)
+            return g
+
+        def submit(slot, group, first):
+            if group[0][0].ndim == 2:
+                srcs = self._pinned_planes(group)
+                res = self.forward_async_gray(slot, srcs, [g[1] for g in group], out=out, depth=depth, **kw)
+            else:
+                if depth == 16:
+                    raise ValueError("colorize_video: depth=16 needs uint16 planes, got RGB frames")
+                srcs = self._pinned_sources(group)
+                res = self.forward_async_images(slot, srcs, [g[1] for g in group], out=out, **kw)
+            return res, srcs, slot, self._temporal is not None
+
+        def finish(state):
+            res, srcs, slot, filtered = state
+            cuts = self.temporal_info(slot, len(srcs))[0] if filtered else np.zeros(len(srcs), np.int32)
+            return [(self._own_image(r, self._out_dims(s, out)), bool(c)) for r, s, c in zip(res, srcs, cuts)]
+
+        yield from self._temporal_stream(temporal, self._two_slot_stream(indexed(), batch, upsample, parse, submit, finish,
+                                                                         key=lambda g: (g[0].ndim, g[0].dtype), ingest=ingest,
+                                                                         output=(out_format, out_matrix)))
+
+    def evaluate_images(self, items, batch=None, out="net", mode="reveal", upsample=None, ingest=None, out_format=None, out_matrix=None,
+                        temporal=None, **kw):
         """Generator: score a stream of ground-truth colour images with both pipeline slots busy -- ``colorize_images`` whose every image is
         compared with itself on the device (``forward_async_eval``).  An item is ``rgb``, ``(rgb, rects)`` or ``(rgb, rects, ref)``; with
         mode='reveal' (default) ``rects`` are rows (y0, x0, y1, x1) whose colours the device reveals from the image, with 'ab' / 'rgb' they
         are hint rows as in ``set_hints``.  Grouping, slot alternation and order as in ``colorize_images``; one ``(psnr, sse)`` per image is
         yielded: ``sse`` (3,) uint64, ``psnr`` = ``evaluate.psnr_from_sse`` of it over the image's net size (out='net') or its own
         (out='source'), ``inf`` for an exact match.  24 bytes per image come back; no image does.  ``upsample``: as in ``colorize_stream``;
-        with out='source' the score is then that of the joint image."""
+        with out='source' the score is then that of the joint image.  ``temporal``: as in ``colorize_stream``; the score is then that of
+        the filtered image."""
         from .evaluate import psnr_from_sse
 
         def submit(slot, group, first):
@@ -1911,8 +2076,9 @@ class HipColorizer(object):
             sse = np.array(state[0])
             return [(psnr_from_sse(sse[i], h, w), sse[i]) for i, (h, w) in enumerate(state[1])]
 
-        yield from self._two_slot_stream(items, batch, upsample, lambda item: _image_item("evaluate_images", item, True), submit, finish, ingest=ingest,
-                                         output=(out_format, out_matrix))      # (scope only: no image comes back, the score reads the RGB)
+        yield from self._temporal_stream(temporal, self._two_slot_stream(
+            items, batch, upsample, lambda item: _image_item("evaluate_images", item, True), submit, finish, ingest=ingest,
+            output=(out_format, out_matrix)))      # (output scope only: no image comes back, the score reads the RGB)
 
     def suggest_images(self, items, centres, batch=None, out="source", peaks=8, radius=2, skip_hints=True, K=5, N_draws=25000, seed=0,
                        upsample=None, ingest=None, out_format=None, out_matrix=None, **kw):
