@@ -12,7 +12,7 @@ Each case first asserts engine.op_last_kernel() against its expected label: the 
 (option op_policy_batch, as a handle's max_batch), the launch carries the small real batch (2 or 3: leakage across images shows).  Shapes
 are what the network's levels produce, ragged against the 32- and 16-wide tiles, the 4*wp-row tiles and the 8x8 / 8x16 Winograd blocks.
 Where the 512-channel trunk needs 256 workgroups for its shipped 8-wave tile the policy batch is 64 or 128 rather than 32: the spatial
-sizes here are a quarter of the network's.
+sizes here are a quarter of the network's.  (Occupancy -- the same rows on grids that fill the chip: tests/test_ops_occupancy_gpu.py.)
 
 test_shipped_kernels_are_all_in_the_table builds the shipped configurations and fails when their layer tables name a kernel (template
 arguments included) that no case here reaches.  A layer table is filled by a forward's planning pass, so each handle runs ONE single-image
