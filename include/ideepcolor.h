@@ -894,9 +894,46 @@ int idc_rgb_to_ycc420(idc_handle h, int n, const idc_ref_image* images, int form
  *      Status: everything is decided on the host before anything is enqueued, and a call refused there leaves the state as it was.  The
  *      pipelined calls keep their own tables; the filter adds no row to them.  A call that fails LATER, with IDC_ERR_HIP from the runtime
  *      while it is being enqueued, may already have advanced the sequence: idc_temporal_reset before going on.
- *      Left out: motion compensation, more than one sequence per handle, the blocking routes, the sharded engine, filtering the
- *      distribution or pred_ab, a raw out_ab beside the filtered one (the filter-off call gives it). */
+ *      Left out: more than one sequence per handle, the blocking routes, the sharded engine, filtering the distribution or pred_ab, a raw
+ *      out_ab beside the filtered one (the filter-off call gives it).  Motion compensation: the next section.
+ *
+ *      MOTION COMPENSATION of that filter (idc_set_temporal_motion).  The rule above lets go wherever L changed, by design -- and so on
+ *      everything that moves and on every pixel of a pan, where flicker shows most.  With motion on, the previous state is first warped along
+ *      block-matched vectors, so a moving surface is compared with, and pulled towards, ITSELF in the previous frame.  Opt-in, off by
+ *      default: with it off no launch, plan byte or output byte of any call changes.  Everything is at the net size, on the L planes the slots
+ *      already hold.
+ *      THE RULE, for a frame with a predecessor: its L plane l [H,W] float32, the state l_prev, y_prev, the network's x, search S in 0..7,
+ *      penalty lambda (L^2 per squared pixel of displacement).  H and W are multiples of 8 (idc_create).  All arithmetic is float64 with fp
+ *      contract(off).
+ *        blocks       8 x 8: block (by, bx) covers rows 8by .. 8by+7 and columns 8bx .. 8bx+7.
+ *        candidates   every (dy, dx) in [-S, S]^2, RANKED by (dy^2 + dx^2, dy, dx) ascending, so rank 0 is (0, 0).  A candidate is valid for a
+ *                     block iff the displaced block lies wholly inside the plane; nothing is replicated.  (0, 0) is always valid.
+ *        cost         C = sum over r = 0..7 (outer, ascending), c = 0..7 (inner, ascending) of
+ *                     ((double)l[8by+r, 8bx+c] - (double)l_prev[8by+r+dy, 8bx+c+dx])^2, with ONE accumulator starting at +0;
+ *                     J = C / 64 + lambda * (double)(dy^2 + dx^2).  The order is normative: J has the same bits in every implementation.
+ *        choice       best starts as rank 0; a later valid candidate replaces it iff its J < best strictly: ties go to the lower rank, a NaN
+ *                     never wins.  A parallel reduction over (J, rank) pairs is the same function.  v[by,bx] = (dy, dx) as int8.
+ *        warp         for every pixel p of the block: lw[p] = l_prev[p + v] and yw[ch][p] = y_prev[ch][p + v].
+ *        filter       the rule above, unchanged, with lw in place of l_prev and yw in place of y_prev: e, then D summed in the SAME fixed order
+ *                     as the plain rule (at S = 0 its bits are the plain rule's), so the cut test is on the compensated difference and a pan
+ *                     is no cut; the window mean m crosses block borders and takes each pixel's own e; then g and y.
+ *        state        afterwards y_prev <- y and l_prev <- l (UNWARPED), also after a cut.
+ *        no predecessor: y = x, and v is reported as zeros.  A cut frame: y = x, and the vectors are reported as estimated.
+ *      Defaults: search 4, penalty 0.5: plausible values.  NOBODY HAS MEASURED THEM ON TRAINED WEIGHTS: this repository has none.
+ *      idc_set_temporal_motion: handle state, copied into a pipelined call when it is enqueued, like idc_set_temporal_filter.
+ *      IDC_ERR_INVALID_ARG unless on is 0 or 1, search in 0..7 and penalty in [0, 1e6] (a NaN is outside); a refused call changes nothing.  It
+ *      acts only where the temporal filter acts -- the eight pipelined entry points and idc_temporal_apply, which uses the handle's current
+ *      setting -- and with the temporal filter off it does nothing.
+ *      idc_temporal_vectors: v int8 [n, H/8, W/8, 2] (dy, dx).  slot 0..1: of the slot's last completed call; the vectors travel back with the
+ *      call's small results, and only when motion was on.  slot -1: of the last idc_temporal_apply.  IDC_ERR_INVALID_ARG for a slot outside
+ *      -1..1, a NULL v, a slot still in flight, a slot whose last call ran with the filter off (or that never ran; slot -1: no
+ *      idc_temporal_apply yet), or a call that ran without motion, in this order.
+ *      Left out: sub-pixel vectors, a hierarchical or wider search, smoothing or a median of the vector field, overlapped-block compensation,
+ *      occlusion handling beyond what e already does, hints that follow the vectors (idc_temporal_vectors gives a caller what it needs), more
+ *      than one sequence per handle, the blocking routes and wrapper classes, the sharded engine, tuning the defaults on trained weights. */
 int idc_set_temporal_filter(idc_handle h, int on, double strength, double sigma, int radius, double cut);
+int idc_set_temporal_motion(idc_handle h, int on, int search, double penalty);
+int idc_temporal_vectors(idc_handle h, int slot, int8_t* v /*[n, H/8, W/8, 2] (dy, dx)*/);
 int idc_temporal_reset(idc_handle h);
 int idc_temporal_info(idc_handle h, int slot, int32_t* cut /*[n]*/, double* D /*[n]*/);
 int idc_temporal_apply(idc_handle h, int n, const float* ab /*[n,2,H,W]*/, const float* l /*[n,H,W]*/, float* y /*[n,2,H,W]*/,

@@ -61,6 +61,8 @@ struct BatchCall {
     // the handle's temporal filter as the call was enqueued (idc_set_temporal_filter).  It takes no room in the plan or in the metadata block:
     // on or off, every byte of both is the same
     TemporalParams temporal = temporal_defaults();
+    // ... and its motion compensation (idc_set_temporal_motion): no room in either as well
+    MotionParams motion = motion_defaults();
 };
 
 inline void set_batch_layers(BatchCall& c, const idc_batch_layers* l) {

@@ -239,7 +239,15 @@ struct idc_context {
     bool temporal_have = false;
     DevMem<float> d_t_yprev, d_t_lprev, d_t_x, d_t_l;
     DevMem<unsigned char> d_t_scratch, d_t_info;
-    DevMem<unsigned char> d_pick;        // idc_gamut_map / idc_snap_colors: inputs + results of one call, device and pinned
+    // its motion compensation (idc_set_temporal_motion; copied into a pipelined call like the filter's parameters), and what idc_temporal_apply
+    // leaves for idc_temporal_vectors(-1): the vectors of its last call (device scratch and the host's copy), its frame count (0: no call yet)
+    // and whether it ran with motion on
+    MotionParams motion = motion_defaults();
+    DevMem<unsigned char> d_t_vec;
+    std::vector<int8_t> t_apply_vec;
+    int t_apply_n = 0;
+    bool t_apply_motion = false;
+    DevMem<unsigned char> d_pick;       // idc_gamut_map / idc_snap_colors: inputs + results of one call, device and pinned
     PinnedMem<unsigned char> h_pick;
     Event ev_sync;                       // idc_stream_wait / idc_stream_signal
     // reference-image global hints (idc_global_stats_rgb / idc_set_global_refs; one per pipeline slot for idc_forward_async_rgb_ref): what one
@@ -292,6 +300,11 @@ struct idc_context {
         int temporal_n = 0;
         DevMem<unsigned char> d_t_scratch, d_t_info;
         PinnedMem<unsigned char> h_t_info;
+        // idc_set_temporal_motion: what the slot's last call was enqueued with, and its vectors (idc_motion.h), device and pinned: they travel
+        // back with the info block, only when motion was on
+        MotionParams motion = motion_defaults();
+        DevMem<unsigned char> d_t_vec;
+        PinnedMem<unsigned char> h_t_vec;
     } pipe[2];
     Event ev_pipe_base;
     bool pipe_ready = false;             // ev_pipe_base is recorded (ensure_pipeline)

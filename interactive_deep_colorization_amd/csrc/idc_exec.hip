@@ -701,11 +701,28 @@ static int ensure_temporal_state(idc_context* h) {
 }
 
 // the two launches of the rule on `s`: x [n,2,H,W] becomes y in place, the state advances, D and the flags land in `info` (idc_temporal.h)
-static int run_temporal(idc_context* h, const TemporalParams& tp, int n, const float* L, float* x, unsigned char* scratch, unsigned char* info,
-                        hipStream_t s) {
+// With motion on (idc_set_temporal_motion; idc_motion.hip): the search, the diff on the warped predecessor, one blend launch per frame -- frame f
+// reads the filtered x[f - 1] at displaced pixels -- and the state by two copies behind the last of them; the vectors land in `vec`.
+static int run_temporal(idc_context* h, const TemporalParams& tp, const MotionParams& mp, int n, const float* L, float* x, unsigned char* scratch,
+                        unsigned char* info, unsigned char* vec, hipStream_t s) {
     double* g = (double*)scratch;
     double* part = (double*)(scratch + temporal_part_at(n, h->H, h->W));
     const int have = h->temporal_have ? 1 : 0;
+    if (mp.on) {
+        const int H = h->H, W = h->W, P = temporal_partials(H, W);
+        const size_t hw = (size_t)H * W;
+        int8_t* v = (int8_t*)vec;
+        HIPCHK(h, launch_motion_search(L, h->d_t_lprev.get(), have, n, H, W, mp.search, mp.penalty, v, s));
+        HIPCHK(h, launch_motion_diff(L, h->d_t_lprev.get(), v, have, n, H, W, tp.radius, tp.strength, tp.sigma, g, part, s));
+        for (int f = 0; f < n; ++f)
+            HIPCHK(h, launch_motion_blend(x + (size_t)f * 2 * hw, f ? x + (size_t)(f - 1) * 2 * hw : h->d_t_yprev.get(), g + (size_t)f * hw,
+                                          part + (size_t)f * P, v + motion_vector_bytes(f, H, W), f == 0 && !have, H, W, tp.cut, (double*)info + f,
+                                          (int*)(info + temporal_info_cut_at(n)) + f, s));
+        // the state, behind the last launch: frame 0 of an n = 1 call read y_prev and l_prev at displaced pixels, so no launch wrote them
+        HIPCHK(h, hipMemcpyAsync(h->d_t_yprev.get(), x + (size_t)(n - 1) * 2 * hw, 2 * hw * sizeof(float), hipMemcpyDeviceToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(h->d_t_lprev.get(), L + (size_t)(n - 1) * hw, hw * sizeof(float), hipMemcpyDeviceToDevice, s));
+        return IDC_OK;
+    }
     HIPCHK(h, launch_temporal_diff(L, h->d_t_lprev.get(), have, n, h->H, h->W, tp.radius, tp.strength, tp.sigma, g, part, s));
     HIPCHK(h, launch_temporal_blend(x, g, part, L, h->d_t_yprev.get(), h->d_t_lprev.get(), have, n, h->H, h->W, tp.cut, (double*)info,
                                     (int*)(info + temporal_info_cut_at(n)), s));
@@ -752,6 +769,10 @@ static int batch_reserve(idc_context* h, const BatchCall& c, const BatchPlan& p,
         HIPCHK(h, sl.d_t_scratch.ensure(temporal_scratch_bytes(h->max_batch, h->H, h->W)));
         HIPCHK(h, sl.d_t_info.ensure(temporal_info_bytes(h->max_batch), 4096));
         HIPCHK(h, sl.h_t_info.ensure(temporal_info_bytes(h->max_batch), 4096));
+        if (c.motion.on) {
+            HIPCHK(h, sl.d_t_vec.ensure(motion_vector_bytes(h->max_batch, h->H, h->W), 4096));
+            HIPCHK(h, sl.h_t_vec.ensure(motion_vector_bytes(h->max_batch, h->H, h->W), 4096));
+        }
     }
     if (!p.ab_pinned) HIPCHK(h, sl.h_out.ensure(nb * hw * 2 * 4));
     if (c.has_refs) HIPCHK(h, sl.d_glob_in.ensure(nb * kGlobIn * sizeof(float)));
@@ -844,9 +865,10 @@ static int batch_colourise(idc_context* h, const BatchCall& c, const BatchPlan& 
     if (rc) return rc;
     if (!p.dist && !((h->flags & IDC_FLAG_DIST313) && h->keep_dist313)) h->dist_n = dist_n;      // no distribution was written: the blocking forward's stays resident
     // the temporal filter: y over x in the slot's ab map, in front of everything that reads it; the heads above saw the raw network
-    sl.temporal = c.temporal; sl.temporal_n = n;
+    sl.temporal = c.temporal; sl.temporal_n = n; sl.motion = c.motion;
     if (c.temporal.on) {
-        const int trc = run_temporal(h, c.temporal, n, sl.d_L.get(), sl.d_out.get(), sl.d_t_scratch.get(), sl.d_t_info.get(), s);
+        const int trc = run_temporal(h, c.temporal, c.motion, n, sl.d_L.get(), sl.d_out.get(), sl.d_t_scratch.get(), sl.d_t_info.get(),
+                                     sl.d_t_vec.get(), s);
         if (trc) return trc;
         h->temporal_have = true;             // the launches are enqueued: the next call's frame 0 follows this call's last one
     }
@@ -911,6 +933,8 @@ static int batch_copy_out(idc_context* h, const BatchCall& c, const BatchPlan& p
     sl.outs.clear();
     if (c.temporal.on)    // D and the cut flags, into the slot's own pinned block: idc_temporal_info reads them there
         HIPCHK(h, hipMemcpyAsync(sl.h_t_info.get(), sl.d_t_info.get(), temporal_info_bytes(c.n), hipMemcpyDeviceToHost, h->s_out.get()));
+    if (c.temporal.on && c.motion.on)    // ... and the vectors with them
+        HIPCHK(h, hipMemcpyAsync(sl.h_t_vec.get(), sl.d_t_vec.get(), motion_vector_bytes(c.n, h->H, h->W), hipMemcpyDeviceToHost, h->s_out.get()));
     if (p.score) {
         const idc_dist_score_out* so = c.sout;
         const ScoreLayout& sc = L.score;
@@ -959,6 +983,7 @@ static int forward_async_rgb(idc_handle h, const BatchCall& call) {
     c.ingest_filter = h->ingest_filter;       // the handle's setting as it is now: a later idc_set_ingest_filter does not reach this batch
     c.out_format = h->out_format; c.out_matrix = h->out_matrix;      // ... and so with idc_set_batch_output
     c.temporal = h->temporal;                                        // ... and with idc_set_temporal_filter
+    c.motion = h->motion;                                            // ... and idc_set_temporal_motion
     BatchPlan p;
     std::string why;
     rc = plan_batch(c, h->H, h->W, h->max_batch, &p, &why);
@@ -1116,6 +1141,34 @@ int idc_set_temporal_filter(idc_handle h, int on, double strength, double sigma,
     return IDC_OK;
 }
 
+int idc_set_temporal_motion(idc_handle h, int on, int search, double penalty) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (!motion_params_ok(on, search, penalty))
+        return fail(&h->err, IDC_ERR_INVALID_ARG, "temporal motion: on %d in {0,1}, search %d in 0..%d, penalty %g in [0, 1e6]", on, search,
+                    kMotionMaxSearch, penalty);
+    h->motion = {on, search, penalty};
+    return IDC_OK;
+}
+
+int idc_temporal_vectors(idc_handle h, int slot, int8_t* v) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (slot < -1 || slot > 1) return fail(&h->err, IDC_ERR_INVALID_ARG, "slot %d not in -1..1", slot);
+    if (!v) return fail(&h->err, IDC_ERR_INVALID_ARG, "null v");
+    if (slot < 0) {                          // the last idc_temporal_apply: it blocked, so nothing is in flight
+        if (h->t_apply_n <= 0) return fail(&h->err, IDC_ERR_INVALID_ARG, "no idc_temporal_apply has run on this handle yet");
+        if (!h->t_apply_motion) return fail(&h->err, IDC_ERR_INVALID_ARG, "the last idc_temporal_apply ran without motion compensation");
+        memcpy(v, h->t_apply_vec.data(), motion_vector_bytes(h->t_apply_n, h->H, h->W));
+        return IDC_OK;
+    }
+    auto& sl = h->pipe[slot];
+    if (sl.pending) return fail(&h->err, IDC_ERR_INVALID_ARG, "slot %d is still in flight: idc_wait it first", slot);
+    if (!h->pipe_ready || !sl.timed || !sl.temporal.on || sl.temporal_n <= 0)
+        return fail(&h->err, IDC_ERR_INVALID_ARG, "slot %d: its last call ran without the temporal filter", slot);
+    if (!sl.motion.on) return fail(&h->err, IDC_ERR_INVALID_ARG, "slot %d: its last call ran without motion compensation", slot);
+    memcpy(v, sl.h_t_vec.get(), motion_vector_bytes(sl.temporal_n, h->H, h->W));
+    return IDC_OK;
+}
+
 int idc_temporal_reset(idc_handle h) {
     if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
     h->temporal_have = false;                // every launch already enqueued carried its own copy of the flag
@@ -1152,13 +1205,21 @@ int idc_temporal_apply(idc_handle h, int n, const float* ab, const float* l, flo
     HIPCHK(h, h->d_t_l.ensure((size_t)n * hw * sizeof(float)));
     HIPCHK(h, h->d_t_scratch.ensure(temporal_scratch_bytes(n, h->H, h->W)));
     HIPCHK(h, h->d_t_info.ensure(temporal_info_bytes(h->max_batch), 4096));
+    const MotionParams mp = h->motion;
+    const size_t vec_bytes = motion_vector_bytes(n, h->H, h->W);
+    if (mp.on) HIPCHK(h, h->d_t_vec.ensure(motion_vector_bytes(h->max_batch, h->H, h->W), 4096));
     HIPCHK(h, hipMemcpyAsync(h->d_t_x.get(), ab, (size_t)n * 2 * hw * sizeof(float), hipMemcpyHostToDevice, s));
     HIPCHK(h, hipMemcpyAsync(h->d_t_l.get(), l, (size_t)n * hw * sizeof(float), hipMemcpyHostToDevice, s));
     HIPCHK(h, hipStreamSynchronize(s));      // a pageable source is the caller's again
-    rc = run_temporal(h, h->temporal, n, h->d_t_l.get(), h->d_t_x.get(), h->d_t_scratch.get(), h->d_t_info.get(), s);
+    rc = run_temporal(h, h->temporal, mp, n, h->d_t_l.get(), h->d_t_x.get(), h->d_t_scratch.get(), h->d_t_info.get(), h->d_t_vec.get(), s);
     if (rc) return rc;
     h->temporal_have = true;
+    h->t_apply_n = n; h->t_apply_motion = mp.on != 0;
     std::vector<unsigned char> info(temporal_info_bytes(n));
+    if (mp.on) {
+        h->t_apply_vec.resize(vec_bytes);
+        HIPCHK(h, hipMemcpyAsync(h->t_apply_vec.data(), h->d_t_vec.get(), vec_bytes, hipMemcpyDeviceToHost, s));
+    }
     HIPCHK(h, hipMemcpyAsync(y, h->d_t_x.get(), (size_t)n * 2 * hw * sizeof(float), hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipMemcpyAsync(info.data(), h->d_t_info.get(), info.size(), hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));

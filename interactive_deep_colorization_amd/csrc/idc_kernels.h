@@ -11,6 +11,7 @@
 #include "idc_layer.h"
 #include "idc_ycc.h"
 #include "idc_temporal.h"
+#include "idc_motion.h"
 
 namespace idc {
 
@@ -364,6 +365,17 @@ hipError_t launch_temporal_diff(const float* L, const float* l_prev, int have, i
                                 double* g, double* part, hipStream_t s);
 hipError_t launch_temporal_blend(float* x, const double* g, const double* part, const float* L, float* y_prev, float* l_prev, int have, int n,
                                  int H, int W, double cut, double* D, int* cut_flags, hipStream_t s);
+
+// Block-matched motion compensation of that filter (idc_set_temporal_motion; idc_motion.hip; the geometry: idc_motion.h).  v int8 [n, H/8, W/8, 2]
+// (dy, dx): written by the search for all n frames, read by the other two.  launch_motion_diff: launch_temporal_diff on the warped predecessor.
+// launch_motion_blend: ONE frame -- x [2,H,W] becomes y, y_before [2,H,W] is the previous frame's filtered map in ANOTHER buffer (never written
+// here: the caller copies the state behind the last frame), g / part / v / D / cut_flag this frame's; pass = no predecessor.  Exact grids.
+hipError_t launch_motion_search(const float* L, const float* l_prev, int have, int n, int H, int W, int search, double penalty, int8_t* v,
+                                hipStream_t s);
+hipError_t launch_motion_diff(const float* L, const float* l_prev, const int8_t* v, int have, int n, int H, int W, int radius, double strength,
+                              double sigma, double* g, double* part, hipStream_t s);
+hipError_t launch_motion_blend(float* x, const float* y_before, const double* g, const double* part, const int8_t* v, int pass, int H, int W,
+                               double cut, double* D, int* cut_flag, hipStream_t s);
 
 // Evaluation batches (idc_reveal_hints / idc_forward_async_eval; idc_colour.hip).  reveal_hints: (c0, c1) of each of the n_rects clipped
 // rectangles of `hints` = the float64 mean ab (rounded once to fp32) of its image's net-size pixels under it, one workgroup per rectangle, fixed

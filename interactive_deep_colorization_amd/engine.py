@@ -887,6 +887,34 @@ class HipColorizer(object):
         self._chk(self.lib.idc_set_temporal_filter(self._h, 1, float(strength), float(sigma), int(radius), float(cut)))
         self._temporal = dict(strength=float(strength), sigma=float(sigma), radius=int(radius), cut=float(cut))
 
+    def set_temporal_motion(self, search=4, penalty=0.5):
+        """Block-matched motion compensation inside the temporal filter (``idc_set_temporal_motion``; the rule stands in
+        ``include/ideepcolor.h``): the previous state is warped along one integer vector per 8 x 8 block of the net-size L plane before the
+        filter compares and blends, so a moving surface is held against itself.  ``search`` 0..7 pixels either way, ``penalty`` 0..1e6 L^2 per
+        squared pixel of displacement.  ``set_temporal_motion(None)`` switches it off (the default).  The defaults are plausible values;
+        nobody has measured them on trained weights.  Handle state like the filter's; it acts only where the filter is on, and in
+        ``temporal_apply``."""
+        if search is None or search is False:
+            prev = self.__dict__.get("_motion") or dict(search=4, penalty=0.5)
+            self._chk(self.lib.idc_set_temporal_motion(self._h, 0, int(prev["search"]), float(prev["penalty"])))
+            self.__dict__["_motion"] = None
+            return
+        self._chk(self.lib.idc_set_temporal_motion(self._h, 1, int(search), float(penalty)))
+        self.__dict__["_motion"] = dict(search=int(search), penalty=float(penalty))
+
+    def temporal_vectors(self, slot, n=None):
+        """The block vectors int8 (n, H/8, W/8, 2) as (dy, dx) of the slot's last completed call, or with ``slot=-1`` of the last
+        ``temporal_apply`` (``idc_temporal_vectors``).  ``n``: the call's frame count (default: the one this engine enqueued on the slot, or
+        gave ``temporal_apply``).  IdcError for a slot in flight or a call that ran with the filter or motion off."""
+        slot = int(slot)
+        if n is None:
+            n = self.__dict__.get("_apply_n") if slot < 0 else self.__dict__.get("_slot_n", {}).get(slot)
+            if n is None:
+                raise ValueError("temporal_vectors: this engine ran nothing on slot %d: give the call's frame count" % slot)
+        v = np.zeros((self.max_batch, self.H // 8, self.W // 8, 2), np.int8)
+        self._chk(self.lib.idc_temporal_vectors(self._h, slot, v.ctypes.data_as(ctypes.c_void_p)))
+        return v[:int(n)].copy()
+
     def temporal_reset(self):
         """The next frame enqueued starts a sequence (``idc_temporal_reset``): ordered behind the batches in flight, does not block."""
         self._chk(self.lib.idc_temporal_reset(self._h))
@@ -907,8 +935,9 @@ class HipColorizer(object):
 
     def temporal_apply(self, ab, l):
         """The rule alone on host arrays (``idc_temporal_apply``): ab (n,2,H,W) float32 the raw maps, l (n,H,W) float32 the frames' L planes
-        (L - l_cent); reads and advances the engine's sequence state with its current parameters, whether the filter is on or not.  Returns
-        ``(y, cut, D)``.  Blocks; needs no weights."""
+        (L - l_cent); reads and advances the engine's sequence state with its current parameters, whether the filter is on or not, and with
+        the current ``set_temporal_motion`` setting (``temporal_vectors(-1)`` then has its vectors).  Returns ``(y, cut, D)``.  Blocks; needs
+        no weights."""
         ab = np.ascontiguousarray(ab, np.float32)
         l = np.ascontiguousarray(l, np.float32)
         if ab.ndim != 4 or tuple(ab.shape[1:]) != (2, self.H, self.W):
@@ -924,6 +953,7 @@ class HipColorizer(object):
         vp = ctypes.c_void_p
         self._chk(self.lib.idc_temporal_apply(self._h, int(n), ab.ctypes.data_as(vp), l.ctypes.data_as(vp), y.ctypes.data_as(vp),
                                               cut.ctypes.data_as(vp), D.ctypes.data_as(vp)))
+        self.__dict__["_apply_n"] = int(n)
         return y, cut[:n], D[:n]
 
     def temporal_state(self):
@@ -945,28 +975,48 @@ class HipColorizer(object):
     def _temporal_stream(self, temporal, gen):
         """The ``temporal=`` keyword of the streaming generators around the generator ``gen``: None leaves the setting alone; True (the
         defaults), a dict of ``set_temporal_filter``'s parameters or False (off) is set, and the sequence reset, before the first batch; the
-        previous setting comes back when the generator ends or its consumer walks away, behind the waits of the slots."""
+        previous setting comes back when the generator ends or its consumer walks away, behind the waits of the slots.  A dict may carry a
+        key ``motion``: True (the defaults), a dict of ``set_temporal_motion``'s parameters or False (off), set and restored with the filter;
+        without the key the motion setting stands as it is."""
         if temporal is None:
             yield from gen
             return
         prev = self._temporal
+        motion, prev_motion, motion_set = None, self.__dict__.get("_motion"), False
         if temporal is True:
             self.set_temporal_filter()
         elif temporal is False:
             self.set_temporal_filter(None)
         else:
-            self.set_temporal_filter(**dict(temporal))
+            temporal = dict(temporal)
+            motion = temporal.pop("motion", None)
+            self.set_temporal_filter(**temporal)
         try:
+            if motion is not None and not (motion is False and prev_motion is None):       # (off and to stay off: no call)
+                motion_set = True
+                if motion is True:
+                    self.set_temporal_motion()
+                elif motion is False:
+                    self.set_temporal_motion(None)
+                else:
+                    self.set_temporal_motion(**dict(motion))
             self.temporal_reset()
             yield from gen
         finally:
             try:
                 gen.close()
             finally:
-                if prev is None:
-                    self.set_temporal_filter(None)
-                else:
-                    self.set_temporal_filter(**prev)
+                try:
+                    if motion_set:
+                        if prev_motion is None:
+                            self.set_temporal_motion(None)
+                        else:
+                            self.set_temporal_motion(**prev_motion)
+                finally:
+                    if prev is None:
+                        self.set_temporal_filter(None)
+                    else:
+                        self.set_temporal_filter(**prev)
 
     def _out_shapes(self, shapes, depth=8):
         """The shapes of a pipelined call's image outputs under the output format in effect: (h,w,3) each, or flat plane blocks."""
@@ -1999,14 +2049,16 @@ class HipColorizer(object):
             output=(out_format, out_matrix)))
 
     def colorize_video(self, frames, hints=None, batch=None, out="source", depth=8, temporal=True, upsample=None, ingest=None, out_format=None,
-                       out_matrix=None, **kw):
+                       out_matrix=None, vectors=False, **kw):
         """Generator: colourise the frames of one video sequence with the temporal ab filter (``set_temporal_filter``) and both pipeline slots
         busy.  ``frames`` is an iterable of (h,w,3) uint8 RGB images, or of (h,w) uint8 / uint16 planes (``forward_async_images`` /
         ``forward_async_gray``; a change of kind or dtype closes the batch, the sequence goes on).  ``hints``: None, a hint list held for every
         frame, or a dict frame index -> hint list: a key frame's hints hold until the next key (frames before the first key have none).
         ``(image, cut)`` is yielded per frame, in order: the image as ``colorize_images`` / ``colorize_gray`` yield it, and whether the
         frame passed unfiltered (the first frame, or a scene cut); with ``temporal=False`` every cut is False.  ``temporal``: True (the
-        defaults), a dict of parameters, False, or None (the engine's setting as it stands, the sequence not reset); ``upsample``,
+        defaults), a dict of parameters (``motion=True`` or a dict of ``set_temporal_motion``'s adds motion compensation), False, or None (the
+        engine's setting as it stands, the sequence not reset).  ``vectors=True``: ``(image, cut, v)`` is yielded, v int8 (H/8, W/8, 2) the
+        frame's block vectors (dy, dx), zeros where the call ran without the filter or without motion.  ``upsample``,
         ``ingest``, ``out_format`` and ``out_matrix`` as in ``colorize_stream``; ``kw``: mode, mask_value, maskcent, l_cent."""
         if depth not in (8, 16) or (depth == 16 and out != "source"):
             raise ValueError("depth must be 8, or 16 with out='source'")
@@ -2041,12 +2093,16 @@ class HipColorizer(object):
                     raise ValueError("colorize_video: depth=16 needs uint16 planes, got RGB frames")
                 srcs = self._pinned_sources(group)
                 res = self.forward_async_images(slot, srcs, [g[1] for g in group], out=out, **kw)
-            return res, srcs, slot, self._temporal is not None
+            filtered = self._temporal is not None
+            return res, srcs, slot, filtered, filtered and self.__dict__.get("_motion") is not None
 
         def finish(state):
-            res, srcs, slot, filtered = state
+            res, srcs, slot, filtered, moving = state
             cuts = self.temporal_info(slot, len(srcs))[0] if filtered else np.zeros(len(srcs), np.int32)
-            return [(self._own_image(r, self._out_dims(s, out)), bool(c)) for r, s, c in zip(res, srcs, cuts)]
+            if not vectors:
+                return [(self._own_image(r, self._out_dims(s, out)), bool(c)) for r, s, c in zip(res, srcs, cuts)]
+            v = self.temporal_vectors(slot, len(srcs)) if moving else np.zeros((len(srcs), self.H // 8, self.W // 8, 2), np.int8)
+            return [(self._own_image(r, self._out_dims(s, out)), bool(c), v[k]) for k, (r, s, c) in enumerate(zip(res, srcs, cuts))]
 
         yield from self._temporal_stream(temporal, self._two_slot_stream(indexed(), batch, upsample, parse, submit, finish,
                                                                          key=lambda g: (g[0].ndim, g[0].dtype), ingest=ingest,
