@@ -241,7 +241,12 @@ static int run_single_op(int device_id, int precision, LayerSpec spec, int n, in
     if (!x || !weight || !bias || !y || n <= 0 || h <= 0 || w <= 0) return fail(nullptr, IDC_ERR_INVALID_ARG, "bad argument");
     const bool split = is_split(precision), f16 = split_is_f16(precision);
     const int parts = split_parts(precision);
-    if (split && !v2_eligible(spec)) return fail(nullptr, IDC_ERR_UNSUPPORTED, "operand-split precisions run the large tile only: cout >= 65");
+    // operand-split precisions run the large tile only (cout >= 65) -- and, as the network runs conv1_2, its 64-cout <1,4> form on what conv1_2 is:
+    // a 3x3 conv of 64 channels at dilation 1, stride 1, without a shortcut sum
+    const bool tile64 = spec.kind == kConv3x3 && spec.cin == kCoutGroup && cout_pad(spec.cout) == kCoutGroup && spec.dilation == 1 && spec.in_stride == 1 && !resid;
+    if (split && !v2_eligible(spec) && !tile64)
+        return fail(nullptr, IDC_ERR_UNSUPPORTED, "operand-split precisions run the large tile only: cout >= 65, or a 3x3 conv (64 channels in, at most 64 out, "
+                    "dilation 1, stride 1, no shortcut sum)");
     const int kc = kc_elems(precision);
     if (spec.cin % kc) return fail(nullptr, IDC_ERR_UNSUPPORTED, "cin must be a multiple of %d in this precision", kc);
     if (spec.in_stride != 1 && spec.in_stride != 2) return fail(nullptr, IDC_ERR_INVALID_ARG, "in_stride must be 1 or 2");
@@ -317,6 +322,7 @@ static int run_single_op(int device_id, int precision, LayerSpec spec, int n, in
     if (sc && op.fused_short < 0)
         return fail(nullptr, IDC_ERR_UNSUPPORTED, "deconv + shortcut: the network runs this pair as two launches here (policy batch %d, options)", n_policy);
     if (sc && op.kernel == kConvDs) return fail(nullptr, IDC_ERR_UNSUPPORTED, "deconv + shortcut: conv_ds_fused (the 32x32x16-MFMA partner) has no single-operator entry");
+    if (op.kernel == kConv1_2Split) return fail(nullptr, IDC_ERR_UNSUPPORTED, "conv1_2_split_kernel (policy batch %d) has no single-operator entry", n_policy);
     // parameters: the weight images the chosen kernel reads, biases (padding 0), BN (padding 1, 0), the accumulator scale, the zero page
     std::vector<uint8_t> blob(blob_bytes, 0);
     auto floats = [&](size_t off) { return (float*)(blob.data() + off); };

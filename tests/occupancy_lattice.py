@@ -313,7 +313,8 @@ def half_pair_batches(c_half, cus):
 #   conv_wino_f32: the form follows the LAUNCHED grid (idc_wino.hip:751-755) and two images of 32 x 32 x 512 reach <2,2>; the shipped batch-1
 #   launch is <1,2>, so the rows force it (option winograd = 12), 256 workgroups per image as shipped.
 #   conv_click<bf16,1,2>: rows-of-4 per workgroup drop to 2 only below 8 site rows (idc_plan.hip:186), which no level of a 256 x 256 image has:
-#   that row runs at 7 x 33.
+#   that row runs at 7 x 33.  (Below 4 site rows they drop to 1: the conv_click<T,1,1> rows `*_click11_*` of tests/test_ops_exact_gpu.py, which
+#   the nets of tests/small_nets.py plan and tests/test_small_nets_gpu.py runs through whole forwards.)
 BATCH1_ROWS = [
     occupancy_row("bf16_kwave_8chunks", 2, h=32, w=32),
     occupancy_row("bf16_kwave_8chunks_d2", 2, h=32, w=32),

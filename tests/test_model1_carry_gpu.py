@@ -1,7 +1,7 @@
 """model1's operand-split pair -- conv1_1_split_kernel + conv1_2_split_kernel x3 / x6 -- bit for bit with conv1_1 values and conv1_2 weights
 that need their lo and mid parts.
 
-conv1_2_split_kernel has no single-operator entry (split ops need cout >= 65); it is reached as tests/test_model1_exact_gpu.py reaches it: a
+conv1_2_split_kernel has no single-operator entry (a 64-cout split op is the <1,4> tile or refused); it is reached as tests/test_model1_exact_gpu.py reaches it: a
 40 x 72, max_batch 32 forward, reading conv1_1 and conv1_2.  On that file's lattice every conv1_1 value is at most 256 and every weight at
 most 2: one part each, so conv1_2's lo / mid segments multiply zeros there.  Here (tests/model1_ref.py, keyword `carry`):
   conv1_1   the exact-fp32 island, integer weights in [-W1, W1]: its post-ReLU values reach 36 * 2 * W1 + 4 and need more than 8 bits (bf16

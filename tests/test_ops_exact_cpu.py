@@ -38,7 +38,7 @@ BF16_F32OUT = [c for c in CASES if c.precision == "bf16" and c.out_f32]
 
 
 def test_the_new_storage_cases_are_all_there():
-    assert len(BF16_F32OUT) == 10 and sum(1 for c in CASES if c.precision == "bf16" and c.resid_f32) == 5
+    assert len(BF16_F32OUT) == 10 and sum(1 for c in CASES if c.precision == "bf16" and c.resid_f32) == 6      # (5 + conv_click<bf16,1,1>)
     assert sum(1 for c in CASES if c.out_f32 and c.precision != "bf16") == 7
     assert {c.cout for c in CASES if c.out_f32 or c.resid_f32} == {529, 384, 313} and {c.cin for c in CASES if c.out_f32} == {256, 384, 512}
 

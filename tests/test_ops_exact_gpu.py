@@ -25,7 +25,9 @@ layers take.  An fp32 shortcut sum is drawn from [-4099, 4099], and the fp32 out
 plans of the configurations with a distribution head or global hints are held against the table on the CPU (same file; STORAGE_LAYERS here).
 
 Wall time of this file on an MI355X, as measured there: 5.3 s for its 100 tests (pytest's own figure); the slowest are the four census handles
-at 0.1 - 0.8 s, every exact case is below 0.15 s.
+at 0.1 - 0.8 s, every exact case is below 0.15 s.  With the fifteen small-net rows (`*_click11_*`, `*_14`, `f32_igemm_14_16x264`) and
+`bf16x3_v2s_22_halo2_small` it holds 117 tests, 5.9 s as measured there (every new row below 0.14 s).  The <1,4> rows go through the single-operator entry's
+64-cout form: conv1_2 as the network runs it (test_a_64_cout_split_op_is_conv1_2_as_the_network_runs_it_or_refused holds its refusing side).
 """
 import re
 
@@ -147,6 +149,30 @@ CASES = [
     case("bf16x6_f32out_v2ps_384", "conv", "bf16x6", 3, 256, 384, 10, 18, "conv_igemm_v2ps<2,2>x6", out_f32=True),
     case("bf16x6_f32resid_v2ps_384", "conv", "bf16x6", 2, 256, 384, 10, 18, "conv_igemm_v2ps<2,2>x6", act=1, resid=True, resid_f32=True),
     case("fp16x3_f32resid_v2psh_384", "conv", "fp16x3", 3, 256, 384, 10, 18, "conv_igemm_v2psh<2,2>x3", act=1, resid=True, resid_f32=True),
+    # ---------------------------------------------------------------- what only small nets reach (the census of tests/test_small_nets_cpu.py)
+    # conv_click<T,1,1>, the one-wave form: set_geometry halves wp while 4 * wp > 2 * Hs, so a click launch on at most three site rows takes it
+    # (the trunk and conv8_1 of an 8 x 8 or 24 x 24 net without Winograd / kwave; conv345678_pred of a dist313 handle on any net 8 pixels tall).
+    # Both HALO instantiations, the deconv form, a width that crosses the 16-wide tile, a halo larger than the image.
+    case("f32_click11_d2_1x1px", "conv", "fp32", 3, 512, 512, 1, 1, "conv_click<f32,1,1> splitK16", dilation=2, act=1, bn=2.0, policy=1, opts=(("winograd", 0),)),
+    case("f32_click11_3x17", "conv", "fp32", 2, 512, 512, 3, 17, "conv_click<f32,1,1> splitK16", act=1, bn=0.5, policy=1, opts=(("winograd", 0),)),
+    case("f32_click11_d2_3x3", "conv", "fp32", 3, 512, 512, 3, 3, "conv_click<f32,1,1> splitK16", dilation=2, act=1, policy=1, opts=(("winograd", 0),)),
+    case("f32_click11_deconv_resid", "deconv", "fp32", 2, 128, 128, 2, 17, "conv_click<f32,1,1> splitK4", act=1, resid=True, policy=1),
+    case("f32_click11_384_resid", "conv", "fp32", 3, 256, 384, 2, 4, "conv_click<f32,1,1> splitK8", act=1, resid=True, policy=1),
+    case("bf16_click11_d2_1x1px", "conv", "bf16", 2, 512, 512, 1, 1, "conv_click<bf16,1,1> splitK8", dilation=2, act=1, bn=2.0, policy=1, opts=(("kwave", 0),)),
+    case("bf16_click11_3x17", "conv", "bf16", 3, 512, 512, 3, 17, "conv_click<bf16,1,1> splitK8", act=1, bn=0.5, policy=1, opts=(("kwave", 0),)),
+    case("bf16_click11_d2_3x3", "conv", "bf16", 2, 512, 512, 3, 3, "conv_click<bf16,1,1> splitK8", dilation=2, act=1, policy=1, opts=(("kwave", 0),)),
+    case("bf16_click11_deconv_resid", "deconv", "bf16", 3, 128, 128, 2, 17, "conv_click<bf16,1,1> splitK2", act=1, resid=True, policy=1, opts=(("kwave", 0),)),
+    # (default options: conv345678_pred of a dist313 handle -- a ReLU over an fp32 shortcut sum keeps the layer off kwave and off Winograd)
+    case("bf16_click11_f32resid_384", "conv", "bf16", 2, 256, 384, 2, 4, "conv_click<bf16,1,1> splitK4", act=1, resid=True, policy=1, resid_f32=True),
+    # the 64-cout <1,4> tile of the operand-split precisions and fp16: conv1_2 wherever its grid stays below conv1_2_split_kernel's 256 workgroups
+    case("bf16x3_v2ps_14", "conv", "bf16x3", 3, 64, 64, 20, 36, "conv_igemm_v2ps<1,4>x3", act=1, bn=0.5, policy=1),
+    case("bf16x6_v2ps_14", "conv", "bf16x6", 3, 64, 64, 20, 36, "conv_igemm_v2ps<1,4>x6", act=1, bn=1.0, policy=1),
+    case("fp16x3_v2psh_14", "conv", "fp16x3", 3, 64, 64, 20, 36, "conv_igemm_v2psh<1,4>x3", act=1, bn=2.0, policy=1),
+    case("fp16_v2psh_14", "conv", "fp16", 3, 64, 64, 20, 36, "conv_igemm_v2psh<1,4>x1", act=1, bn=1.0, policy=1),
+    # conv_igemm_v2s<2,2>x3: the dilated trunk of a small bf16x3 net (the halo-2 form has no v2ps twin; the x6 and fp16 twins are further up)
+    case("bf16x3_v2s_22_halo2_small", "conv", "bf16x3", 2, 512, 512, 5, 9, "conv_igemm_v2s<2,2>x3", dilation=2, act=1),
+    # conv_igemm<f32,1,4>: conv1_1 and (without Winograd) conv1_2 of an fp32 max_batch-32 handle on 16 x 264, nine 32-wide tile columns
+    case("f32_igemm_14_16x264", "conv", "fp32", 2, 64, 64, 16, 264, "conv_igemm<f32,1,4>", act=1, bn=2.0, policy=32, opts=(("winograd", 0),)),
 ]
 assert len(set(c.id for c in CASES)) == len(CASES)
 
@@ -224,6 +250,32 @@ def test_fused_op_refuses_an_fp32_output():
     engine.set_option("op_out_f32", 0)
     assert call() == 0 and engine.op_last_kernel() == c.label
     xl.compare(y, xl.expected(c), "bf16_ds_half through the C entry point")
+
+
+def test_a_64_cout_split_op_is_conv1_2_as_the_network_runs_it_or_refused():
+    """The single-operator entry runs an operand-split conv of at most 64 couts only in conv1_2's own form (3x3, 64 channels in, dilation 1,
+    stride 1, no shortcut sum) and only on the <1,4> tile: anything else of 64 couts is refused before a plan is made, and a policy batch whose
+    grid hands conv1_2 to conv1_2_split_kernel (2 x 2 tiles x 64 images = 256 workgroups at 20 x 36) is refused after it, before any launch."""
+    c = _by_id("bf16x3_v2ps_14")
+    d = xl.draw(c)
+
+    def refused(what, x=d["x"], w=d["w"], policy=c.policy, **kw):
+        with pytest.raises(_native.IdcError) as ei:
+            engine.op_conv2d(x, w, d["b"], act=c.act, bn_scale=d["bn_s"], bn_shift=d["bn_t"], precision=c.precision, policy_batch=policy, **kw)
+        assert _native.STATUS_NAMES[ei.value.status] == "IDC_ERR_UNSUPPORTED" and engine.op_last_kernel() == "", (what, str(ei.value))
+        return str(ei.value)
+
+    for precision_row in ("bf16x3_v2ps_14", "fp16_v2psh_14"):
+        assert _by_id(precision_row).cin == 64 and _by_id(precision_row).cout == 64
+    assert "large tile only" in refused("dilated", dilation=2)
+    assert "large tile only" in refused("strided", in_stride=2)
+    assert "large tile only" in refused("1x1", w=np.ascontiguousarray(d["w"][:, :, :1, :1]))
+    assert "large tile only" in refused("shortcut sum", resid=np.zeros((c.n, c.cout) + xl.out_hw(c), np.float32))
+    assert "large tile only" in refused("128 channels in", x=np.concatenate([d["x"], d["x"]], axis=1), w=np.concatenate([d["w"], d["w"]], axis=1))
+    assert "conv1_2_split_kernel" in refused("policy batch 64", policy=64)
+    got, label = run_case(c, d)                                   # ... and the row itself runs as before
+    assert label == c.label
+    xl.compare(got, xl.expected(c, d), "%s after the refusals" % c.id)
 
 
 # ---- census: what the shipped configurations launch is what the table reaches -----------------------------------------------------------

@@ -16,6 +16,7 @@ X / Wc / m are typed here and held against it, never tuned against a kernel.  LA
 Wall time of this file on an MI355X, as measured there: 6.6 s for its 71 tests (pytest's own figure; 5.2 s for the 100 tests of
 tests/test_ops_exact_gpu.py in the same run).  The first row takes 0.21 s, every other at most 0.16 s -- about half of it the float64 reference of
 the 512-channel rows on the host -- against "below 0.15 s" for that file's exact cases.
+With the rows of the <1,4> tile and of conv_igemm_v2s<2,2>x3 it holds 84 tests: 7.0 s as measured there, the slowest row still 0.22 s.
 """
 import numpy as np  # noqa: F401
 import pytest
@@ -95,6 +96,21 @@ CARRY_CASES = [
     row("bf16x6_f32sum_v2s_deconv_384", "x_lo", m=15),
     row("bf16x6_f32sum_v2s_deconv_384", "w_lo"),
     row("bf16x6_f32sum_v2s_deconv_384", "both"),
+    # ---------------------------------------------------------------- the 64-cout <1,4> tile: conv1_2 of a split handle below conv1_2_split_kernel's grid
+    row("bf16x3_v2ps_14", "x_carry", 29119),                         # 64 -> 64 at 20 x 36, BN 0.5: K 576
+    row("bf16x3_v2ps_14", "w_carry", 29119),
+    row("bf16x3_v2ps_14", "both"),
+    row("fp16x3_v2psh_14", "x_carry", 14555),                        # BN 2: budget 8388595
+    row("fp16x3_v2psh_14", "w_carry", 14555),
+    row("bf16x6_v2ps_14", "x_carry", 29119),                         # BN 1
+    row("bf16x6_v2ps_14", "w_carry", 29119),
+    row("bf16x6_v2ps_14", "x_lo", m=15),
+    row("bf16x6_v2ps_14", "w_lo"),
+    row("bf16x6_v2ps_14", "both"),
+    # ---------------------------------------------------------------- conv_igemm_v2s<2,2>x3: the dilated trunk of a small bf16x3 net
+    row("bf16x3_v2s_22_halo2_small", "x_carry", 3639),               # 512 -> 512 d2 at 5 x 9: K 4608
+    row("bf16x3_v2s_22_halo2_small", "w_carry", 3639),
+    row("bf16x3_v2s_22_halo2_small", "both"),
 ]
 # The span ladder (carry_lattice's docstring): conv_igemm_v2ps<4,2>x3 and its fp16 twin on ONE geometry, sums of one sign reaching the rung
 LADDER = [
