@@ -929,11 +929,57 @@ int idc_rgb_to_ycc420(idc_handle h, int n, const idc_ref_image* images, int form
  *      -1..1, a NULL v, a slot still in flight, a slot whose last call ran with the filter off (or that never ran; slot -1: no
  *      idc_temporal_apply yet), or a call that ran without motion, in this order.
  *      Left out: sub-pixel vectors, a hierarchical or wider search, smoothing or a median of the vector field, overlapped-block compensation,
- *      occlusion handling beyond what e already does, hints that follow the vectors (idc_temporal_vectors gives a caller what it needs), more
- *      than one sequence per handle, the blocking routes and wrapper classes, the sharded engine, tuning the defaults on trained weights. */
+ *      occlusion handling beyond what e already does, more than one sequence per handle, the blocking routes and wrapper classes, the
+ *      sharded engine, tuning the defaults on trained weights.  Hints that follow the vectors: the next section (HINT TRACKING).
+ *
+ *      HINT TRACKING along those vectors (idc_set_hint_tracking).  Hints are an input of the network, and the vectors of a call's frames
+ *      exist only once the call runs: without tracking a click made on a coat stays at its net coordinates and is on the wall a dozen frames
+ *      into a pan.  With tracking on, the search runs in FRONT of the network (it reads the L planes alone) and the hint planes are carried
+ *      along its vectors on the device, so every frame of a batch gets its tracked hints in the same call.  Opt-in, off by default: with it
+ *      off no launch, plan byte or output byte of any call changes.
+ *      Parameters: life, an integer in 0..65535 (frames a hint may be carried; 0: no limit); tol, L units in [0, 100].
+ *      Defaults: life 0, tol 8.0: plausible values.  NOBODY HAS MEASURED THEM ON TRAINED WEIGHTS: this repository has none.
+ *      Tracking acts only where motion compensation acts: the eight pipelined entry points, enqueued with the temporal filter on AND motion
+ *      on.  Otherwise it does nothing.
+ *      THE RULE, for frame f of the sequence.  Its OWN planes ab_f [2,H,W] and mask_f [H,W] are what the untouched prologue wrote for this
+ *      frame (with the hint-layer kernel where the call has layers, and the revealed colours in an evaluation call); l_f is its fp32 L plane;
+ *      v_f are exactly the motion rule's vectors, estimated against the predecessor's L.  The TRACKED planes (A_f, M_f, G_f) hold ab, mask
+ *      and an int32 age.
+ *        own          where mask_f[p] != 0: A_f[p] = ab_f[p], M_f[p] = mask_f[p], G_f[p] = 0.  An own hint always wins.
+ *        carried      elsewhere, with a predecessor: q = p + v_f[p.y / 8, p.x / 8] (always inside the plane: a valid vector keeps its whole
+ *                     block inside).  The hint is carried iff M_{f-1}[q] != 0, and fabs((double)l_f[p] - (double)l_{f-1}[q]) <= tol (a NaN
+ *                     carries nothing), and life == 0 || G_{f-1}[q] + 1 <= life.  Then A_f[p] = A_{f-1}[q] and M_f[p] = M_{f-1}[q] -- the
+ *                     stored floats, so the origin call's mask_value travels with the hint -- and G_f[p] = G_{f-1}[q] + 1 (it stops at
+ *                     2^31 - 1).  Otherwise (0, 0, 0, 0) is written.
+ *        no predecessor (the first frame after idc_create or idc_temporal_reset): tracked = own.
+ *        state        the handle keeps (A, M, G) of the sequence's last frame beside y_prev / l_prev; idc_temporal_reset clears it.  A
+ *                     pipelined call enqueued with the filter on but tracking off, or with motion off, DROPS it (and so does
+ *                     idc_temporal_apply, which moves l_prev on without hints): the next tracking call's frame 0 then carries nothing.  A
+ *                     filter-off call, idc_forward_async and the blocking forwards leave it alone.  The state is the stored planes, so a
+ *                     sequence gives the same bits however it is split into calls.
+ *      The tracked planes replace the own planes before anything else reads them: the network, skip_hints of the uncertainty peaks, the
+ *      taps.  Revealed colours, `cells` of a layer call and idc_temporal_info are unchanged.  The filter's cut test is not consulted: a cut
+ *      ends the carried hints through tol, pixel by pixel.
+ *      idc_set_hint_tracking: handle state, copied into a pipelined call when it is enqueued, like idc_set_temporal_motion.
+ *      IDC_ERR_INVALID_ARG unless on is 0 or 1, life in 0..65535 and tol in [0, 100] (a NaN is outside); a refused call changes nothing.
+ *      idc_tracked_hints: the tracked planes of the slot's last completed call; each pointer may be NULL, not all three.  It copies from the
+ *      device on request only: nothing is added to a call's own D2H traffic.  IDC_ERR_INVALID_ARG for a slot outside 0..1, all pointers
+ *      NULL, a slot still in flight, a slot whose last call ran with the filter off (or that never ran), or a call that ran without
+ *      tracking, in this order.
+ *      idc_track_hints_apply: the rule alone on host arrays, through the same search and tracking kernels, with the handle's current motion
+ *      (search, penalty) and tracking (life, tol) parameters, as a self-contained sequence: frame 0 has no predecessor, and the handle's
+ *      sequence state is neither read nor written.  It blocks, drains the slots and needs no weights.  IDC_ERR_BATCH for n outside
+ *      1..max_batch, IDC_ERR_INVALID_ARG for a NULL input or output plane; v_out [n, H/8, W/8, 2] may be NULL.
+ *      Left out: dropping carried hints at a key frame, sub-block vectors, forward or bidirectional tracking, the blocking routes, the
+ *      sharded engine, tuning the defaults. */
 int idc_set_temporal_filter(idc_handle h, int on, double strength, double sigma, int radius, double cut);
 int idc_set_temporal_motion(idc_handle h, int on, int search, double penalty);
 int idc_temporal_vectors(idc_handle h, int slot, int8_t* v /*[n, H/8, W/8, 2] (dy, dx)*/);
+int idc_set_hint_tracking(idc_handle h, int on, int life, double tol);
+int idc_tracked_hints(idc_handle h, int slot, float* ab /*[n,2,H,W]*/, float* mask /*[n,H,W]*/, int32_t* age /*[n,H,W]*/);
+int idc_track_hints_apply(idc_handle h, int n, const float* l /*[n,H,W]*/, const float* ab /*[n,2,H,W]*/, const float* mask /*[n,H,W]*/,
+                          float* ab_out /*[n,2,H,W]*/, float* mask_out /*[n,H,W]*/, int32_t* age_out /*[n,H,W]*/,
+                          int8_t* v_out /*[n, H/8, W/8, 2] or NULL*/);
 int idc_temporal_reset(idc_handle h);
 int idc_temporal_info(idc_handle h, int slot, int32_t* cut /*[n]*/, double* D /*[n]*/);
 int idc_temporal_apply(idc_handle h, int n, const float* ab /*[n,2,H,W]*/, const float* l /*[n,H,W]*/, float* y /*[n,2,H,W]*/,

@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = [
     "idc_ycc420_bytes", "idc_set_batch_output", "idc_fullres_ycc", "idc_rgb_to_ycc420",
     "idc_set_temporal_filter", "idc_temporal_reset", "idc_temporal_info", "idc_temporal_apply", "idc_temporal_state",
     "idc_set_temporal_motion", "idc_temporal_vectors",
+    "idc_set_hint_tracking", "idc_tracked_hints", "idc_track_hints_apply",
     "idc_set_range_audit", "idc_range_reset", "idc_range_report", "idc_pack_weights_ex", "idc_load_weights_ex",
 ]
 IDC_STORE_NONE, IDC_STORE_F32, IDC_STORE_BF16, IDC_STORE_F16 = 0, 1, 2, 3
@@ -280,6 +281,9 @@ def load():
     proto("idc_temporal_state", ci, [vp, vp, vp, vp])
     proto("idc_set_temporal_motion", ci, [vp, ci, ci, ctypes.c_double])
     proto("idc_temporal_vectors", ci, [vp, ci, vp])
+    proto("idc_set_hint_tracking", ci, [vp, ci, ci, ctypes.c_double])
+    proto("idc_tracked_hints", ci, [vp, ci, vp, vp, vp])
+    proto("idc_track_hints_apply", ci, [vp, ci, vp, vp, vp, vp, vp, vp, vp])
     proto("idc_set_batch_upsample", ci, [vp, ci])
     proto("idc_set_ingest_filter", ci, [vp, ci])
     proto("idc_set_range_audit", ci, [vp, ci])

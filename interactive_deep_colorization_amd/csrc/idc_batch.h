@@ -63,6 +63,8 @@ struct BatchCall {
     TemporalParams temporal = temporal_defaults();
     // ... and its motion compensation (idc_set_temporal_motion): no room in either as well
     MotionParams motion = motion_defaults();
+    // ... and the hint tracking along its vectors (idc_set_hint_tracking): no room in either as well
+    TrackParams track = track_defaults();
 };
 
 inline void set_batch_layers(BatchCall& c, const idc_batch_layers* l) {

@@ -247,6 +247,12 @@ struct idc_context {
     std::vector<int8_t> t_apply_vec;
     int t_apply_n = 0;
     bool t_apply_motion = false;
+    // the hint tracking along those vectors (idc_set_hint_tracking; copied into a pipelined call like the motion parameters): the sequence state
+    // (A, M, G) of the last tracked frame in idc_track.h's one-frame layout, whether it holds a frame (a tracking call has been ENQUEUED since
+    // idc_create / idc_temporal_reset and no filtered call without tracking since), and what the blocking idc_track_hints_apply works in
+    TrackParams track = track_defaults();
+    bool track_have = false;
+    DevMem<unsigned char> d_tr_state, d_tr_in, d_tr_out;
     DevMem<unsigned char> d_pick;       // idc_gamut_map / idc_snap_colors: inputs + results of one call, device and pinned
     PinnedMem<unsigned char> h_pick;
     Event ev_sync;                       // idc_stream_wait / idc_stream_signal
@@ -305,6 +311,11 @@ struct idc_context {
         MotionParams motion = motion_defaults();
         DevMem<unsigned char> d_t_vec;
         PinnedMem<unsigned char> h_t_vec;
+        // idc_set_hint_tracking: whether the slot's last call tracked its hints, with what, and the tracked planes (idc_track.h) the network
+        // and the taps then read in place of d_ab / d_mask; idc_tracked_hints copies from here on request
+        bool tracked = false;
+        TrackParams track = track_defaults();
+        DevMem<unsigned char> d_tr;
     } pipe[2];
     Event ev_pipe_base;
     bool pipe_ready = false;             // ev_pipe_base is recorded (ensure_pipeline)

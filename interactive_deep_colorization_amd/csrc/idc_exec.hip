@@ -703,8 +703,9 @@ static int ensure_temporal_state(idc_context* h) {
 // the two launches of the rule on `s`: x [n,2,H,W] becomes y in place, the state advances, D and the flags land in `info` (idc_temporal.h)
 // With motion on (idc_set_temporal_motion; idc_motion.hip): the search, the diff on the warped predecessor, one blend launch per frame -- frame f
 // reads the filtered x[f - 1] at displaced pixels -- and the state by two copies behind the last of them; the vectors land in `vec`.
+// searched: a tracking call has run this very search in front of the network (batch_colourise); `vec` holds its vectors.
 static int run_temporal(idc_context* h, const TemporalParams& tp, const MotionParams& mp, int n, const float* L, float* x, unsigned char* scratch,
-                        unsigned char* info, unsigned char* vec, hipStream_t s) {
+                        unsigned char* info, unsigned char* vec, bool searched, hipStream_t s) {
     double* g = (double*)scratch;
     double* part = (double*)(scratch + temporal_part_at(n, h->H, h->W));
     const int have = h->temporal_have ? 1 : 0;
@@ -712,7 +713,7 @@ static int run_temporal(idc_context* h, const TemporalParams& tp, const MotionPa
         const int H = h->H, W = h->W, P = temporal_partials(H, W);
         const size_t hw = (size_t)H * W;
         int8_t* v = (int8_t*)vec;
-        HIPCHK(h, launch_motion_search(L, h->d_t_lprev.get(), have, n, H, W, mp.search, mp.penalty, v, s));
+        if (!searched) HIPCHK(h, launch_motion_search(L, h->d_t_lprev.get(), have, n, H, W, mp.search, mp.penalty, v, s));
         HIPCHK(h, launch_motion_diff(L, h->d_t_lprev.get(), v, have, n, H, W, tp.radius, tp.strength, tp.sigma, g, part, s));
         for (int f = 0; f < n; ++f)
             HIPCHK(h, launch_motion_blend(x + (size_t)f * 2 * hw, f ? x + (size_t)(f - 1) * 2 * hw : h->d_t_yprev.get(), g + (size_t)f * hw,
@@ -772,6 +773,10 @@ static int batch_reserve(idc_context* h, const BatchCall& c, const BatchPlan& p,
         if (c.motion.on) {
             HIPCHK(h, sl.d_t_vec.ensure(motion_vector_bytes(h->max_batch, h->H, h->W), 4096));
             HIPCHK(h, sl.h_t_vec.ensure(motion_vector_bytes(h->max_batch, h->H, h->W), 4096));
+            if (c.track.on) {     // the tracked planes of the slot and the sequence's (A, M, G)
+                HIPCHK(h, sl.d_tr.ensure(track_scratch_bytes(h->max_batch, h->H, h->W)));
+                HIPCHK(h, h->d_tr_state.ensure(track_state_bytes(h->H, h->W)));
+            }
         }
     }
     if (!p.ab_pinned) HIPCHK(h, sl.h_out.ensure(nb * hw * 2 * 4));
@@ -858,9 +863,32 @@ static int batch_colourise(idc_context* h, const BatchCall& c, const BatchPlan& 
             HIPCHK(h, launch_hint_layers(sl.d_layer.get(), (const LayerDesc*)(sl.d_meta.get() + p.layers_at), n, p.layer_blocks, h->H, h->W, c.alpha_min,
                                          c.cover, c.mask_value, sl.d_ab.get(), sl.d_mask.get(), (int*)sl.d_cells.get(), s));
     }
+    // hint tracking: the search moves in front of the network (it reads L and l_prev alone), the own planes are carried along its vectors into
+    // the slot's scratch in one launch, and the network and the taps read the scratch; the state by three copies behind the launch, since
+    // frame 0 read it at displaced pixels.  A filtered call without tracking drops the state.
+    const bool tracking = c.temporal.on && c.motion.on && c.track.on;
+    const float* ab_in = sl.d_ab.get();
+    const float* mask_in = sl.d_mask.get();
+    sl.tracked = tracking; sl.track = c.track;
+    if (tracking) {
+        const int H = h->H, W = h->W, have = h->temporal_have ? 1 : 0;
+        unsigned char* tr = sl.d_tr.get();
+        unsigned char* st = h->d_tr_state.get();
+        float* t_ab = (float*)tr;
+        float* t_mask = (float*)(tr + track_mask_at(n, H, W));
+        int32_t* t_age = (int32_t*)(tr + track_age_at(n, H, W));
+        HIPCHK(h, launch_motion_search(sl.d_L.get(), h->d_t_lprev.get(), have, n, H, W, c.motion.search, c.motion.penalty, (int8_t*)sl.d_t_vec.get(), s));
+        HIPCHK(h, launch_track_hints(sl.d_ab.get(), sl.d_mask.get(), sl.d_L.get(), h->d_t_lprev.get(), (const int8_t*)sl.d_t_vec.get(), (const float*)st,
+                                     (const float*)(st + track_mask_at(1, H, W)), (const int32_t*)(st + track_age_at(1, H, W)), have,
+                                     h->track_have ? 1 : 0, n, H, W, c.track.life, c.track.tol, t_ab, t_mask, t_age, s));
+        HIPCHK(h, hipMemcpyAsync(st, t_ab + (size_t)(n - 1) * 2 * hw, 2 * hw * sizeof(float), hipMemcpyDeviceToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(st + track_mask_at(1, H, W), t_mask + (size_t)(n - 1) * hw, hw * sizeof(float), hipMemcpyDeviceToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(st + track_age_at(1, H, W), t_age + (size_t)(n - 1) * hw, hw * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+        ab_in = t_ab; mask_in = t_mask;
+    }
     const int dist_n = h->dist_n;
     // a distribution batch runs model_class into the HANDLE's distribution (the 313 head with idc_keep_dist writes dist_S on every forward anyway)
-    const int rc = run_graph(h, n, sl.d_L.get(), sl.d_ab.get(), sl.d_mask.get(), c.maskcent, sl.d_out.get(),
+    const int rc = run_graph(h, n, sl.d_L.get(), ab_in, mask_in, c.maskcent, sl.d_out.get(),
                              (p.dist && !(h->flags & IDC_FLAG_DIST313)) ? h->d_dist.get() : nullptr, c.has_refs ? sl.d_glob_in.get() : h->d_glob_in.get());
     if (rc) return rc;
     if (!p.dist && !((h->flags & IDC_FLAG_DIST313) && h->keep_dist313)) h->dist_n = dist_n;      // no distribution was written: the blocking forward's stays resident
@@ -868,9 +896,10 @@ static int batch_colourise(idc_context* h, const BatchCall& c, const BatchPlan& 
     sl.temporal = c.temporal; sl.temporal_n = n; sl.motion = c.motion;
     if (c.temporal.on) {
         const int trc = run_temporal(h, c.temporal, c.motion, n, sl.d_L.get(), sl.d_out.get(), sl.d_t_scratch.get(), sl.d_t_info.get(),
-                                     sl.d_t_vec.get(), s);
+                                     sl.d_t_vec.get(), tracking, s);
         if (trc) return trc;
         h->temporal_have = true;             // the launches are enqueued: the next call's frame 0 follows this call's last one
+        h->track_have = tracking;            // ... with its tracked planes, or without any: a filtered call without tracking drops them
     }
     HIPCHK(h, launch_lab_post(sl.d_L.get(), c.l_cent, sl.d_out.get(), sl.d_rgb.get(), p.source_out ? sl.d_labq.get() : nullptr, n, h->H, h->W, s));
     sl.up_interp = h->batch_interp; sl.up_joint = h->joint;       // the handle's setting as it is now: a later idc_set_batch_upsample does not reach this batch
@@ -902,7 +931,8 @@ static int batch_measure(idc_context* h, const BatchCall& c, const BatchPlan& p,
         }
     }
     if (p.dist && c.taps) {   // entropy, peaks, suggestions: behind this batch's network, so in front of whatever replaces the handle's distribution next
-        const int rc = launch_taps(h, L.geom, L.taps, c.taps, sl.d_mask.get(), sl.d_taps_in.get(), sl.d_taps.get(), s);
+        const float* mask = sl.tracked ? (const float*)(sl.d_tr.get() + track_mask_at(n, h->H, h->W)) : sl.d_mask.get();     // skip_hints sees the tracked mask
+        const int rc = launch_taps(h, L.geom, L.taps, c.taps, mask, sl.d_taps_in.get(), sl.d_taps.get(), s);
         if (rc) return rc;
     }
     if (p.score) {    // behind the other taps: the cells' ground truth from the slot's own packed sources, then the score
@@ -984,6 +1014,7 @@ static int forward_async_rgb(idc_handle h, const BatchCall& call) {
     c.out_format = h->out_format; c.out_matrix = h->out_matrix;      // ... and so with idc_set_batch_output
     c.temporal = h->temporal;                                        // ... and with idc_set_temporal_filter
     c.motion = h->motion;                                            // ... and idc_set_temporal_motion
+    c.track = h->track;                                              // ... and idc_set_hint_tracking
     BatchPlan p;
     std::string why;
     rc = plan_batch(c, h->H, h->W, h->max_batch, &p, &why);
@@ -1169,9 +1200,79 @@ int idc_temporal_vectors(idc_handle h, int slot, int8_t* v) {
     return IDC_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- hints that follow the motion vectors
+int idc_set_hint_tracking(idc_handle h, int on, int life, double tol) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (!track_params_ok(on, life, tol))
+        return fail(&h->err, IDC_ERR_INVALID_ARG, "hint tracking: on %d in {0,1}, life %d in 0..%d, tol %g in [0, 100]", on, life, kTrackMaxLife, tol);
+    h->track = {on, life, tol};
+    return IDC_OK;
+}
+
+int idc_tracked_hints(idc_handle h, int slot, float* ab, float* mask, int32_t* age) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (slot < 0 || slot > 1) return fail(&h->err, IDC_ERR_INVALID_ARG, "slot %d not in 0..1", slot);
+    if (!ab && !mask && !age) return fail(&h->err, IDC_ERR_INVALID_ARG, "null ab, mask and age");
+    auto& sl = h->pipe[slot];
+    if (sl.pending) return fail(&h->err, IDC_ERR_INVALID_ARG, "slot %d is still in flight: idc_wait it first", slot);
+    if (!h->pipe_ready || !sl.timed || !sl.temporal.on || sl.temporal_n <= 0)
+        return fail(&h->err, IDC_ERR_INVALID_ARG, "slot %d: its last call ran without the temporal filter", slot);
+    if (!sl.tracked) return fail(&h->err, IDC_ERR_INVALID_ARG, "slot %d: its last call ran without hint tracking", slot);
+    // on request only: the planes wait in the slot's scratch, which nothing writes before the slot's next call
+    HIPCHK(h, hipSetDevice(h->device));
+    const int n = sl.temporal_n;
+    const size_t hw = (size_t)h->H * h->W;
+    const unsigned char* tr = sl.d_tr.get();
+    if (ab) HIPCHK(h, hipMemcpy(ab, tr, (size_t)n * 2 * hw * sizeof(float), hipMemcpyDeviceToHost));
+    if (mask) HIPCHK(h, hipMemcpy(mask, tr + track_mask_at(n, h->H, h->W), (size_t)n * hw * sizeof(float), hipMemcpyDeviceToHost));
+    if (age) HIPCHK(h, hipMemcpy(age, tr + track_age_at(n, h->H, h->W), (size_t)n * hw * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return IDC_OK;
+}
+
+int idc_track_hints_apply(idc_handle h, int n, const float* l, const float* ab, const float* mask, float* ab_out, float* mask_out,
+                          int32_t* age_out, int8_t* v_out) {
+    if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
+    if (n <= 0 || n > h->max_batch) return fail(&h->err, IDC_ERR_BATCH, "batch %d outside 1..%d", n, h->max_batch);
+    if (!l || !ab || !mask || !ab_out || !mask_out || !age_out) return fail(&h->err, IDC_ERR_INVALID_ARG, "null l, ab, mask, ab_out, mask_out or age_out");
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = drain_pipeline(h);
+    if (rc) return rc;
+    hipStream_t s = h->stream.get();
+    HIPCHK(h, hipStreamSynchronize(s));
+    const int H = h->H, W = h->W;
+    const size_t hw = (size_t)H * W, vec_bytes = motion_vector_bytes(n, H, W);
+    const MotionParams mp = h->motion;
+    const TrackParams tk = h->track;
+    // in: l [n,H,W], ab [n,2,H,W], mask [n,H,W], then the vectors; out: idc_track.h's layout.  A self-contained sequence: frame 0 has no
+    // predecessor, so l_prev and the state are never read -- the launchers still want pointers, and get the call's own planes
+    const size_t in_ab_at = (size_t)n * hw * 4, in_mask_at = in_ab_at + (size_t)n * 2 * hw * 4, in_vec_at = in_mask_at + (size_t)n * hw * 4;
+    HIPCHK(h, h->d_tr_in.ensure(in_vec_at + vec_bytes));
+    HIPCHK(h, h->d_tr_out.ensure(track_scratch_bytes(n, H, W)));
+    unsigned char* in = h->d_tr_in.get();
+    unsigned char* out = h->d_tr_out.get();
+    const float* d_l = (const float*)in;
+    const float* d_ab = (const float*)(in + in_ab_at);
+    const float* d_mask = (const float*)(in + in_mask_at);
+    int8_t* d_v = (int8_t*)(in + in_vec_at);
+    HIPCHK(h, hipMemcpyAsync(in, l, (size_t)n * hw * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(in + in_ab_at, ab, (size_t)n * 2 * hw * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(in + in_mask_at, mask, (size_t)n * hw * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipStreamSynchronize(s));      // a pageable source is the caller's again
+    HIPCHK(h, launch_motion_search(d_l, d_l, 0, n, H, W, mp.search, mp.penalty, d_v, s));
+    HIPCHK(h, launch_track_hints(d_ab, d_mask, d_l, d_l, d_v, d_ab, d_mask, (const int32_t*)d_mask, 0, 0, n, H, W, tk.life, tk.tol, (float*)out,
+                                 (float*)(out + track_mask_at(n, H, W)), (int32_t*)(out + track_age_at(n, H, W)), s));
+    HIPCHK(h, hipMemcpyAsync(ab_out, out, (size_t)n * 2 * hw * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(mask_out, out + track_mask_at(n, H, W), (size_t)n * hw * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(age_out, out + track_age_at(n, H, W), (size_t)n * hw * 4, hipMemcpyDeviceToHost, s));
+    if (v_out) HIPCHK(h, hipMemcpyAsync(v_out, d_v, vec_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    return IDC_OK;
+}
+
 int idc_temporal_reset(idc_handle h) {
     if (!h) return fail(nullptr, IDC_ERR_INVALID_ARG, "null handle");
     h->temporal_have = false;                // every launch already enqueued carried its own copy of the flag
+    h->track_have = false;
     return IDC_OK;
 }
 
@@ -1211,9 +1312,10 @@ int idc_temporal_apply(idc_handle h, int n, const float* ab, const float* l, flo
     HIPCHK(h, hipMemcpyAsync(h->d_t_x.get(), ab, (size_t)n * 2 * hw * sizeof(float), hipMemcpyHostToDevice, s));
     HIPCHK(h, hipMemcpyAsync(h->d_t_l.get(), l, (size_t)n * hw * sizeof(float), hipMemcpyHostToDevice, s));
     HIPCHK(h, hipStreamSynchronize(s));      // a pageable source is the caller's again
-    rc = run_temporal(h, h->temporal, mp, n, h->d_t_l.get(), h->d_t_x.get(), h->d_t_scratch.get(), h->d_t_info.get(), h->d_t_vec.get(), s);
+    rc = run_temporal(h, h->temporal, mp, n, h->d_t_l.get(), h->d_t_x.get(), h->d_t_scratch.get(), h->d_t_info.get(), h->d_t_vec.get(), false, s);
     if (rc) return rc;
     h->temporal_have = true;
+    h->track_have = false;                   // frames without hints went by: the tracked state no longer belongs to the predecessor
     h->t_apply_n = n; h->t_apply_motion = mp.on != 0;
     std::vector<unsigned char> info(temporal_info_bytes(n));
     if (mp.on) {

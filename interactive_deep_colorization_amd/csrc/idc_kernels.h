@@ -12,6 +12,7 @@
 #include "idc_ycc.h"
 #include "idc_temporal.h"
 #include "idc_motion.h"
+#include "idc_track.h"
 
 namespace idc {
 
@@ -376,6 +377,14 @@ hipError_t launch_motion_diff(const float* L, const float* l_prev, const int8_t*
                               double sigma, double* g, double* part, hipStream_t s);
 hipError_t launch_motion_blend(float* x, const float* y_before, const double* g, const double* part, const int8_t* v, int pass, int H, int W,
                                double cut, double* D, int* cut_flag, hipStream_t s);
+
+// Hints that follow those vectors (idc_set_hint_tracking; idc_track.hip; the walk and the sizes: idc_track.h).  ONE launch for all n frames: the
+// RAW own planes ab [n,2,H,W] / mask [n,H,W], L [n,H,W], l_prev, v of launch_motion_search on the same L, and the state (A [2,H,W], M, G [H,W]) are
+// read; the tracked planes go to out_* -- other buffers: the walks read the raw planes of earlier frames.  have_prev: frame 0 has a predecessor
+// (the search's `have`); have_state: the state holds a frame.  The caller copies the last frame to the state BEHIND the launch.  Exact grid.
+hipError_t launch_track_hints(const float* ab, const float* mask, const float* L, const float* l_prev, const int8_t* v, const float* state_ab,
+                              const float* state_mask, const int32_t* state_age, int have_prev, int have_state, int n, int H, int W, int life,
+                              double tol, float* out_ab, float* out_mask, int32_t* out_age, hipStream_t s);
 
 // Evaluation batches (idc_reveal_hints / idc_forward_async_eval; idc_colour.hip).  reveal_hints: (c0, c1) of each of the n_rects clipped
 // rectangles of `hints` = the float64 mean ab (rounded once to fp32) of its image's net-size pixels under it, one workgroup per rectangle, fixed

@@ -915,6 +915,70 @@ class HipColorizer(object):
         self._chk(self.lib.idc_temporal_vectors(self._h, slot, v.ctypes.data_as(ctypes.c_void_p)))
         return v[:int(n)].copy()
 
+    def set_hint_tracking(self, on=True, life=0, tol=8.0):
+        """Hints that follow the motion vectors (``idc_set_hint_tracking``; the rule stands in ``include/ideepcolor.h``): in the pipelined
+        calls enqueued with the filter and motion on, the search runs in front of the network and every frame's hint planes are its own
+        hints plus the previous frame's tracked ones, carried along the block vectors where L agrees within ``tol`` (0..100 L units) and,
+        with ``life`` > 0 (up to 65535), for at most ``life`` frames.  ``set_hint_tracking(None)`` (or False) switches it off (the default).
+        The defaults are plausible values; nobody has measured them on trained weights.  Handle state like the motion setting's."""
+        if on is None or on is False:
+            prev = self.__dict__.get("_track") or dict(life=0, tol=8.0)
+            self._chk(self.lib.idc_set_hint_tracking(self._h, 0, int(prev["life"]), float(prev["tol"])))
+            self.__dict__["_track"] = None
+            return
+        self._chk(self.lib.idc_set_hint_tracking(self._h, 1, int(life), float(tol)))
+        self.__dict__["_track"] = dict(life=int(life), tol=float(tol))
+
+    def tracked_hints(self, slot, n=None, want=("ab", "mask", "age")):
+        """``(ab (n,2,H,W) float32, mask (n,H,W) float32, age (n,H,W) int32)``: the tracked hint planes the network saw in the slot's last
+        completed call (``idc_tracked_hints``), copied from the device on request.  ``n``: the call's frame count (default: the one this
+        engine enqueued on the slot).  ``want``: which of the three to copy; the others come back as ``None`` and cost nothing.  IdcError for
+        a slot in flight or a call that ran without the filter or without tracking."""
+        slot = int(slot)
+        if n is None:
+            n = self.__dict__.get("_slot_n", {}).get(slot)
+            if n is None:
+                raise ValueError("tracked_hints: this engine ran nothing on slot %d: give the call's frame count" % slot)
+        want = set(want)
+        if not want or not want <= {"ab", "mask", "age"}:
+            raise ValueError("tracked_hints: want is a non-empty subset of ('ab', 'mask', 'age')")
+        # room for max_batch frames whatever n says (the library writes ITS frame count, packed: frame f starts f planes in); untouched
+        # pages of an np.empty block cost nothing, and a plane that is not wanted is neither allocated nor copied
+        hw, n = self.H * self.W, int(n)
+        bufs = [np.empty(self.max_batch * per * hw, dtype) if name in want else None
+                for name, per, dtype in (("ab", 2, np.float32), ("mask", 1, np.float32), ("age", 1, np.int32))]
+        vp = ctypes.c_void_p
+        self._chk(self.lib.idc_tracked_hints(self._h, slot, *[None if b is None else b.ctypes.data_as(vp) for b in bufs]))
+        shapes = ((n, 2, self.H, self.W), (n, self.H, self.W), (n, self.H, self.W))
+        return tuple(None if b is None else b[:int(np.prod(shp))].reshape(shp) for b, shp in zip(bufs, shapes))
+
+    def track_hints_apply(self, l, ab, mask, vectors=False):
+        """The tracking rule alone on host arrays (``idc_track_hints_apply``): l (n,H,W) float32 the frames' L planes, ab (n,2,H,W) and mask
+        (n,H,W) float32 their own hint planes, as one self-contained sequence with the engine's current motion and tracking parameters; the
+        engine's sequence state is neither read nor written.  Returns ``(ab, mask, age)``, with ``vectors=True`` also the block vectors
+        int8 (n,H/8,W/8,2).  Blocks; needs no weights."""
+        l = np.ascontiguousarray(l, np.float32)
+        ab = np.ascontiguousarray(ab, np.float32)
+        mask = np.ascontiguousarray(mask, np.float32)
+        if ab.ndim != 4 or tuple(ab.shape[1:]) != (2, self.H, self.W):
+            raise ValueError("track_hints_apply needs ab of shape (n,2,%d,%d), got %s" % (self.H, self.W, ab.shape))
+        n = ab.shape[0]
+        if tuple(l.shape) == (n, 1, self.H, self.W):
+            l = l.reshape(n, self.H, self.W)
+        if tuple(mask.shape) == (n, 1, self.H, self.W):
+            mask = mask.reshape(n, self.H, self.W)
+        if tuple(l.shape) != (n, self.H, self.W) or tuple(mask.shape) != (n, self.H, self.W):
+            raise ValueError("track_hints_apply needs l and mask of shape (%d,%d,%d), got %s and %s" % (n, self.H, self.W, l.shape, mask.shape))
+        ab_out = np.zeros_like(ab)
+        mask_out = np.zeros_like(mask)
+        age = np.zeros((n, self.H, self.W), np.int32)
+        v = np.zeros((max(n, 1), self.H // 8, self.W // 8, 2), np.int8) if vectors else None
+        vp = ctypes.c_void_p
+        self._chk(self.lib.idc_track_hints_apply(self._h, int(n), l.ctypes.data_as(vp), ab.ctypes.data_as(vp), mask.ctypes.data_as(vp),
+                                                 ab_out.ctypes.data_as(vp), mask_out.ctypes.data_as(vp), age.ctypes.data_as(vp),
+                                                 v.ctypes.data_as(vp) if vectors else None))
+        return (ab_out, mask_out, age, v[:n]) if vectors else (ab_out, mask_out, age)
+
     def temporal_reset(self):
         """The next frame enqueued starts a sequence (``idc_temporal_reset``): ordered behind the batches in flight, does not block."""
         self._chk(self.lib.idc_temporal_reset(self._h))
@@ -977,12 +1041,15 @@ class HipColorizer(object):
         defaults), a dict of ``set_temporal_filter``'s parameters or False (off) is set, and the sequence reset, before the first batch; the
         previous setting comes back when the generator ends or its consumer walks away, behind the waits of the slots.  A dict may carry a
         key ``motion``: True (the defaults), a dict of ``set_temporal_motion``'s parameters or False (off), set and restored with the filter;
-        without the key the motion setting stands as it is."""
+        without the key the motion setting stands as it is.  The ``motion`` dict may in turn carry a key ``track``: True (the defaults), a
+        dict of ``set_hint_tracking``'s parameters or False (off), set and restored with the motion setting; without the key no
+        tracking call is made."""
         if temporal is None:
             yield from gen
             return
         prev = self._temporal
         motion, prev_motion, motion_set = None, self.__dict__.get("_motion"), False
+        track, prev_track, track_set = None, self.__dict__.get("_track"), False
         if temporal is True:
             self.set_temporal_filter()
         elif temporal is False:
@@ -999,7 +1066,17 @@ class HipColorizer(object):
                 elif motion is False:
                     self.set_temporal_motion(None)
                 else:
-                    self.set_temporal_motion(**dict(motion))
+                    motion = dict(motion)
+                    track = motion.pop("track", None)
+                    self.set_temporal_motion(**motion)
+            if track is not None and not (track is False and prev_track is None):          # (off and to stay off: no call)
+                track_set = True
+                if track is True:
+                    self.set_hint_tracking()
+                elif track is False:
+                    self.set_hint_tracking(None)
+                else:
+                    self.set_hint_tracking(**dict(track))
             self.temporal_reset()
             yield from gen
         finally:
@@ -1007,11 +1084,18 @@ class HipColorizer(object):
                 gen.close()
             finally:
                 try:
-                    if motion_set:
-                        if prev_motion is None:
-                            self.set_temporal_motion(None)
-                        else:
-                            self.set_temporal_motion(**prev_motion)
+                    try:
+                        if track_set:
+                            if prev_track is None:
+                                self.set_hint_tracking(None)
+                            else:
+                                self.set_hint_tracking(**prev_track)
+                    finally:
+                        if motion_set:
+                            if prev_motion is None:
+                                self.set_temporal_motion(None)
+                            else:
+                                self.set_temporal_motion(**prev_motion)
                 finally:
                     if prev is None:
                         self.set_temporal_filter(None)
@@ -2049,7 +2133,7 @@ class HipColorizer(object):
             output=(out_format, out_matrix)))
 
     def colorize_video(self, frames, hints=None, batch=None, out="source", depth=8, temporal=True, upsample=None, ingest=None, out_format=None,
-                       out_matrix=None, vectors=False, **kw):
+                       out_matrix=None, vectors=False, tracked=False, **kw):
         """Generator: colourise the frames of one video sequence with the temporal ab filter (``set_temporal_filter``) and both pipeline slots
         busy.  ``frames`` is an iterable of (h,w,3) uint8 RGB images, or of (h,w) uint8 / uint16 planes (``forward_async_images`` /
         ``forward_async_gray``; a change of kind or dtype closes the batch, the sequence goes on).  ``hints``: None, a hint list held for every
@@ -2058,7 +2142,11 @@ class HipColorizer(object):
         frame passed unfiltered (the first frame, or a scene cut); with ``temporal=False`` every cut is False.  ``temporal``: True (the
         defaults), a dict of parameters (``motion=True`` or a dict of ``set_temporal_motion``'s adds motion compensation), False, or None (the
         engine's setting as it stands, the sequence not reset).  ``vectors=True``: ``(image, cut, v)`` is yielded, v int8 (H/8, W/8, 2) the
-        frame's block vectors (dy, dx), zeros where the call ran without the filter or without motion.  ``upsample``,
+        frame's block vectors (dy, dx), zeros where the call ran without the filter or without motion.  With hint tracking in force
+        (``temporal=dict(motion=dict(track=True))`` or a dict of ``set_hint_tracking``'s parameters there) and ``hints`` a dict, a key
+        frame's list goes to THAT frame only and the device carries it along the vectors; a list ``hints`` still goes to every frame.
+        ``tracked=True`` appends the frame's tracked mask plane (H,W) float32 to each yielded tuple (zeros where the call ran without
+        tracking).  ``upsample``,
         ``ingest``, ``out_format`` and ``out_matrix`` as in ``colorize_stream``; ``kw``: mode, mask_value, maskcent, l_cent."""
         if depth not in (8, 16) or (depth == 16 and out != "source"):
             raise ValueError("depth must be 8, or 16 with out='source'")
@@ -2067,8 +2155,13 @@ class HipColorizer(object):
         held = [None]
 
         def indexed():
+            # (pulled behind ``_temporal_stream``'s settings: tracking is in force iff the filter, motion and tracking are all on)
+            carried = self._temporal is not None and self.__dict__.get("_motion") is not None and self.__dict__.get("_track") is not None
             for k, frame in enumerate(frames):
                 if isinstance(hints, dict):
+                    if carried:                          # the device carries a key frame's hints: they go to that frame alone
+                        yield frame, hints.get(k)
+                        continue
                     if k in hints:
                         held[0] = hints[k]
                     yield frame, held[0]
@@ -2094,15 +2187,20 @@ class HipColorizer(object):
                 srcs = self._pinned_sources(group)
                 res = self.forward_async_images(slot, srcs, [g[1] for g in group], out=out, **kw)
             filtered = self._temporal is not None
-            return res, srcs, slot, filtered, filtered and self.__dict__.get("_motion") is not None
+            moving = filtered and self.__dict__.get("_motion") is not None
+            return res, srcs, slot, filtered, moving, moving and self.__dict__.get("_track") is not None
 
         def finish(state):
-            res, srcs, slot, filtered, moving = state
+            res, srcs, slot, filtered, moving, tracking = state
             cuts = self.temporal_info(slot, len(srcs))[0] if filtered else np.zeros(len(srcs), np.int32)
-            if not vectors:
-                return [(self._own_image(r, self._out_dims(s, out)), bool(c)) for r, s, c in zip(res, srcs, cuts)]
-            v = self.temporal_vectors(slot, len(srcs)) if moving else np.zeros((len(srcs), self.H // 8, self.W // 8, 2), np.int8)
-            return [(self._own_image(r, self._out_dims(s, out)), bool(c), v[k]) for k, (r, s, c) in enumerate(zip(res, srcs, cuts))]
+            rows = [(self._own_image(r, self._out_dims(s, out)), bool(c)) for r, s, c in zip(res, srcs, cuts)]
+            if vectors:
+                v = self.temporal_vectors(slot, len(srcs)) if moving else np.zeros((len(srcs), self.H // 8, self.W // 8, 2), np.int8)
+                rows = [row + (v[k],) for k, row in enumerate(rows)]
+            if tracked:
+                m = self.tracked_hints(slot, len(srcs), want=("mask",))[1] if tracking else np.zeros((len(srcs), self.H, self.W), np.float32)
+                rows = [row + (m[k],) for k, row in enumerate(rows)]
+            return rows
 
         yield from self._temporal_stream(temporal, self._two_slot_stream(indexed(), batch, upsample, parse, submit, finish,
                                                                          key=lambda g: (g[0].ndim, g[0].dtype), ingest=ingest,
